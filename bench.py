@@ -14,13 +14,17 @@ separately and summed"); `--overlap` puts the decode on a second stream beside t
 runs beside the forward of batch i+1), which is a few percent faster and is NOT the headline.
 
 Prints ONE JSON line (rank 0).  The K timed steps run as in production (eager launches, branch lanes on internal
-streams).  `roofline` comes from probe steps AFTER the timed loop (not part of `value`): the kernels run one at a time on
+streams).  A plain run does only what `value` and `ms_per_step` need: set-up, warm-up, the timed steps, the line.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see step_outputs).  `--full` adds, behind
+the timed loop, everything else the line can report (none of it part of `value`): the forward / decode split, the dense
+decode, the two rooflines and the CPU baseline.
+`roofline` (--full) comes from probe steps AFTER the timed loop: the kernels run one at a time on
 one stream and every convolution launch carries a start / stop HIP event pair that the runtime fills from the dispatch
 packet's own begin / end timestamps (hipExtLaunchKernelGGL, on the stream the kernel is launched on) -- the clock pair
 rocprofv3's kernel trace reports, so `avg_launch_us` is directly comparable with the serial pass committed in
 profiles/rNN_bench_kernel_stats.csv.  The dominant kernel instantiation is the one with the largest summed time.
-`decode_roofline` = compulsory decode bytes over the time of hh_decode alone, against HBM peak.  `cpu_baseline` times
-the CPU oracle (oracle/) on a bounded sample, on rank 0 at N=1 only.
+`decode_roofline` (--full) = compulsory decode bytes over the time of hh_decode alone, against HBM peak.  `cpu_baseline`
+(--full) times the CPU oracle (oracle/) on a bounded sample, on rank 0 at N=1 only.
 """
 import argparse
 import ctypes as C
@@ -180,6 +184,39 @@ def headline(metric, world, per_gpu_batch, args, elapsed, dtype, config):
     }
 
 
+DUMP_BYTES = 60 * 2 ** 20  # --dump-outputs writes at most this much array data (64 MB with the .npy headers)
+
+
+def step_outputs(out, dec):
+    """What a caller of the timed path receives from one step, as float32 / float64 arrays for --dump-outputs.
+    decode_*: the hh_decode results whole; person rows at or past an image's `num_people` are zeroed (they are not part of
+    the result: MPPEHeatmapParser.to_lists slices them off).  init_heatmaps [B,2K,H/4,W/4] and deconv_heatmaps [B,K,H/2,W/2] (forward_raw) exceed
+    the budget at the bench sizes, so each is cut to whole [h,w] planes of its [B*C,h,w] view: the first n of
+    np.random.default_rng(0).permutation(B*C), in ascending order, n = as many as fit half of the budget the decode leaves."""
+    joints, scores, num, flags = dec
+    live = torch.arange(joints.shape[1], device=num.device)[None, :] < num[:, None].long()
+    arrays = {
+        "decode_joints": torch.where(live[:, :, None, None], joints, 0.0).cpu().numpy(),
+        "decode_scores": torch.where(live, scores, 0.0).cpu().numpy(),
+        "decode_num_people": num.cpu().numpy().astype(np.float64),
+        "decode_flags": flags.cpu().numpy().astype(np.float64),
+    }
+    share = (DUMP_BYTES - sum(a.nbytes for a in arrays.values())) // 2
+    for name, t in (("init_heatmaps", out[0]), ("deconv_heatmaps", out[1])):
+        B, Ch, h, w = t.shape
+        n = min(B * Ch, share // (h * w * t.element_size()))
+        planes = torch.from_numpy(np.sort(np.random.default_rng(0).permutation(B * Ch)[:n])).to(t.device)
+        arrays[name] = t.reshape(B * Ch, h, w)[planes].float().cpu().numpy()
+    return arrays
+
+
+def dump_outputs(out_dir, arrays):
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def rehearsal_cpu(args, dist, rank, world):
     """HH_BENCH_REHEARSAL=cpu: the N > 1 launch contract without a GPU (gloo): same process-group init, same timed_loop,
     same rank-0 line; a step is a sleep whose length depends on the rank, so the test can see that the MAX was taken."""
@@ -229,6 +266,8 @@ def train_bench(args, pkg, dist, rank, world, dev):
     with torch.cuda.stream(train_stream):
         args.warmup = max(args.warmup, 1)
         elapsed, loss = timed_loop(step, args.warmup, args.steps, dist, torch.cuda.synchronize, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss.detach().double().cpu().numpy().reshape(1)})
     if rank == 0:
         print(json.dumps(headline(
             "images/sec (training step) HigherHRNet-W32 512px", world, B, args, elapsed, "bf16",
@@ -316,7 +355,14 @@ def main():
     ap.add_argument("--train", action="store_true",
                     help="time the training step of BASELINE.json configs[2] instead (forward with train-mode BN + AE loss + "
                          "backward + Adam, DistributedDataParallel over RCCL when launched on several GPUs); not the headline metric")
+    ap.add_argument("--full", action="store_true",
+                    help="behind the timed loop, also measure what the headline does not need: forward / decode split, dense decode, "
+                         "roofline probe steps, decode roofline, CPU baseline (the --no-* and --probe-steps options tune these)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB; rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     cfgd = CONFIGS[args.config]
     if args.batch is None:
@@ -371,7 +417,7 @@ def main():
     parser = pkg.MPPEHeatmapParser(K, 30, 0.05, 0.5)
     lib = pkg._lib.load()
     dense = None
-    if args.dense_people > 0:
+    if args.full and args.dense_people > 0:
         du = [pkg.synth.synth_decode_maps(K, H // 4, W // 4, args.dense_people, seed=5000 + rank * 8 + i)[:3] for i in range(8)]
         dense = tuple(torch.from_numpy(np.stack([(du[i % 8][j] if j < 2 else du[i % 8][2][0]) for i in range(B)])).to(dev) for j in range(3))
 
@@ -399,11 +445,12 @@ def main():
 
     stream = torch.cuda.current_stream(dev)
     with torch.cuda.stream(side):
-        profile = not args.no_profile
         net.use_graph = True
         elapsed, (out, dec) = timed_loop(step, args.warmup, args.steps, dist, torch.cuda.synchronize, dev)
+        if args.dump_outputs and rank == 0:  # before anything below overwrites `outs`
+            dump_outputs(args.dump_outputs, step_outputs(out, dec))
         per_cfg = {}
-        if profile:
+        if args.full and not args.no_profile:
             # probe steps, outside the timed region: conv launches one at a time on one stream, each with its own start / stop
             # event pair (hipExtLaunchKernelGGL), the decode behind them on the same stream
             lib.hh_profile_enable(net._h, 1)
@@ -422,32 +469,34 @@ def main():
                     if d.get("ghz"):
                         per_cfg[c]["ghz"] = d["ghz"]
             lib.hh_profile_enable(net._h, 0)
-        # split of the step (not part of the timed region): forward alone / decode alone, graph replay
-        net.use_graph = True
-        for fn in (lambda: net.forward_raw(images, outs), lambda: parser.decode_batch_device(hm_q, hm_h, [tags])):
-            fn()
-        parts = []
-        for fn, reps in ((lambda: net.forward_raw(images, outs), 10), (lambda: parser.decode_batch_device(hm_q, hm_h, [tags]), 40)):
-            side.synchronize()
-            t1 = time.perf_counter()
-            for _ in range(reps):  # (the decode is 0.3 ms: five calls were a 1.5 ms window and read 0.28 or 0.37 from run to run)
+        if args.full:
+            # split of the step (not part of the timed region): forward alone / decode alone, graph replay
+            net.use_graph = True
+            for fn in (lambda: net.forward_raw(images, outs), lambda: parser.decode_batch_device(hm_q, hm_h, [tags])):
                 fn()
-            side.synchronize()
-            parts.append((time.perf_counter() - t1) / reps)
-        dense_ms = dense_people = None
-        if dense is not None:  # a crowded batch through the same decoder (not part of `value`)
-            fn = lambda: parser.decode_batch_device(dense[0], dense[1], [dense[2]], adjust=True, refine=True)  # noqa: E731
-            dd = fn()
-            side.synchronize()
-            t1 = time.perf_counter()
-            for _ in range(20):
+            parts = []
+            for fn, reps in ((lambda: net.forward_raw(images, outs), 10), (lambda: parser.decode_batch_device(hm_q, hm_h, [tags]), 40)):
+                side.synchronize()
+                t1 = time.perf_counter()
+                for _ in range(reps):  # (the decode is 0.3 ms: five calls were a 1.5 ms window and read 0.28 or 0.37 from run to run)
+                    fn()
+                side.synchronize()
+                parts.append((time.perf_counter() - t1) / reps)
+            dense_ms = dense_people = None
+            if dense is not None:  # a crowded batch through the same decoder (not part of `value`)
+                fn = lambda: parser.decode_batch_device(dense[0], dense[1], [dense[2]], adjust=True, refine=True)  # noqa: E731
                 dd = fn()
-            side.synchronize()
-            dense_ms = (time.perf_counter() - t1) / 20 * 1e3
-            dense_people = int(dd[2].sum().item())
+                side.synchronize()
+                t1 = time.perf_counter()
+                for _ in range(20):
+                    dd = fn()
+                side.synchronize()
+                dense_ms = (time.perf_counter() - t1) / 20 * 1e3
+                dense_people = int(dd[2].sum().item())
     del stream
-    num_people = int(dec[2].sum().item())
-    assert not bool(dec[3].any().item()), "decode flagged an image (solver guard / no-group fallback) on the bench maps"
+    if args.full:
+        num_people = int(dec[2].sum().item())
+        assert not bool(dec[3].any().item()), "decode flagged an image (solver guard / no-group fallback) on the bench maps"
 
     if rank == 0:
         line = headline(cfgd["metric"], world, B, args, elapsed, cfgd["dtype"], {
@@ -458,16 +507,19 @@ def main():
                             ", det_thr 0.05, tag_thr 0.5, adjust+refine)",
                 "global_batch": world * B,
                 "parallelism": f"image-sharded replicas x{world}, no data-path collective",
+                "streams": "forward (+3 internal branch lanes) and decode on two streams" if args.overlap else
+                           "forward (+3 internal branch lanes), then decode, back to back on one stream: step = forward + decode",
+                "timed_region": "eager launches as in production; the per-launch roofline probe runs in separate steps behind the timed loop",
+        })
+        if args.full:
+            line["config"].update({
                 "people_decoded_per_batch": num_people,
                 "forward_ms": round(parts[0] * 1e3, 3),
                 "decode_ms": round(parts[1] * 1e3, 3),
                 "decode_dense_ms": None if dense_ms is None else round(dense_ms, 3),
                 "decode_dense_people_per_batch": dense_people,
                 "forward_tflops": round(net.forward_flops(B, H, W) / parts[0] / 1e12, 1),
-                "streams": "forward (+3 internal branch lanes) and decode on two streams" if args.overlap else
-                           "forward (+3 internal branch lanes), then decode, back to back on one stream: step = forward + decode",
-                "timed_region": "eager launches as in production; the per-launch roofline probe runs in separate steps behind the timed loop",
-        })
+            })
         if per_cfg:
             dom = max(per_cfg, key=lambda c: per_cfg[c]["ms"])
             d = per_cfg[dom]
@@ -529,16 +581,17 @@ def main():
                                for c, v in sorted(per_cfg.items(), key=lambda kv: -kv[1]["ms"])[1:(None if os.environ.get("HH_BENCH_ALL_KERNELS") else 4)]],
                 "all_conv_tflops": round(sum(v["flops"] for v in per_cfg.values()) / (total_ms * 1e-3) / 1e12, 2),
             }
-        # decode half against the HBM roofline: compulsory bytes (read every network output once) over the
-        # time of one hh_decode call alone; the kernels are latency/VALU bound by design, so this is small
-        dec_bytes = 4.0 * K * ((H // 4) * (W // 4) * 2 + (H // 2) * (W // 2)) * B  # 6,684,672 B per 512x512 image
-        line["decode_roofline"] = {
-            "bound": "hbm", "achieved": round(dec_bytes / parts[1] / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": round(dec_bytes / parts[1] / 1e9 / HBM_PEAK_GBS, 4), "traffic": traffic_for("hh_decode (all kernels of one call)"),
-            "algorithmic_bytes_per_call": dec_bytes, "ms_per_call": round(parts[1] * 1e3, 3),
-        }
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only: the other ranks would idle at the final barrier
-            line["cpu_baseline"] = cpu_baseline(pkg, sd, uniq, fwd_images=4 if H <= 512 else 2, size=H)
+        if args.full:
+            # decode half against the HBM roofline: compulsory bytes (read every network output once) over the
+            # time of one hh_decode call alone; the kernels are latency/VALU bound by design, so this is small
+            dec_bytes = 4.0 * K * ((H // 4) * (W // 4) * 2 + (H // 2) * (W // 2)) * B  # 6,684,672 B per 512x512 image
+            line["decode_roofline"] = {
+                "bound": "hbm", "achieved": round(dec_bytes / parts[1] / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(dec_bytes / parts[1] / 1e9 / HBM_PEAK_GBS, 4), "traffic": traffic_for("hh_decode (all kernels of one call)"),
+                "algorithmic_bytes_per_call": dec_bytes, "ms_per_call": round(parts[1] * 1e3, 3),
+            }
+            if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only: the other ranks would idle at the final barrier
+                line["cpu_baseline"] = cpu_baseline(pkg, sd, uniq, fwd_images=4 if H <= 512 else 2, size=H)
         print(json.dumps(line), flush=True)
     if dist is not None:
         dist.barrier()

@@ -330,3 +330,32 @@ def test_hand_counted_lds_waits_have_no_scalar_load_in_flight():
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "222 partial" in out.stdout or "partial lgkmcnt waits, 0 with" in out.stdout
+
+
+def test_bench_dump_outputs_fit_the_budget_and_repeat(tmp_path):
+    """bench.py --dump-outputs at the headline size (B = 32 @ 512^2): float32 / float64 arrays within 64 MB, the same sampled
+    [h,w] planes on every call (ascending, each one whole), decode person rows past `num_people` zeroed, the others kept."""
+    import bench
+    B, K, S, M = 32, 17, 512, 30
+    # plane p of a map holds the value p everywhere (stride-0 views: no 213 MB allocation)
+    out = tuple(torch.arange(B * c, dtype=torch.float32).view(B, c, 1, 1).expand(B, c, h, h) for c, h in ((2 * K, S // 4), (K, S // 2)))
+    num = torch.tensor([i % 7 for i in range(B)], dtype=torch.int32)
+    joints = torch.full((B, M, K, 4), float("nan"))
+    joints[:, :6] = 1.0
+    scores = torch.full((B, M), float("nan"))
+    scores[:, :6] = 2.0
+    dec = (joints, scores, num, torch.zeros(B, dtype=torch.int32))
+    a, b = bench.step_outputs(out, dec), bench.step_outputs(out, dec)
+    bench.dump_outputs(str(tmp_path), a)
+    assert sum(f.stat().st_size for f in tmp_path.iterdir()) <= 64e6
+    assert sorted(f.name for f in tmp_path.iterdir()) == sorted(k + ".npy" for k in a)
+    for k, v in a.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all() and np.array_equal(v, b[k]), k
+    for name, c in (("init_heatmaps", 2 * K), ("deconv_heatmaps", K)):
+        planes = a[name][:, 0, 0]
+        assert np.all(np.diff(planes) > 0) and B * c // 8 < len(planes) < B * c
+        assert np.array_equal(a[name], np.broadcast_to(planes[:, None, None], a[name].shape))
+    live = np.arange(M)[None, :] < num.numpy()[:, None]
+    assert (a["decode_joints"][live] == 1).all() and (a["decode_joints"][~live] == 0).all()
+    assert (a["decode_scores"][live] == 2).all() and (a["decode_scores"][~live] == 0).all()
+    assert np.array_equal(a["decode_num_people"], num.numpy())

@@ -2,7 +2,7 @@
 # alternating A/B of several environment settings on one box: bash tools/probes/ab_env.sh <rounds> "VAR=a" "VAR=b VAR2=c" ...   ("-" = no setting)
 cd $GRAFT_REPO_ROOT
 n=$1; shift
-args="--no-cpu-baseline --no-profile --steps 60 --warmup 10 --dense-people 0"
+args="--full --no-cpu-baseline --no-profile --steps 60 --warmup 10 --dense-people 0"
 for i in $(seq $n); do
   for v in "$@"; do
     if [ "$v" = "-" ]; then e=""; else e="$v"; fi

@@ -2,7 +2,7 @@
 # alternating A/B of several builds of the library on one box: bash tools/probes/ab_lib.sh <rounds> <lib|-> ...   ("-" = the in-tree build)
 cd $GRAFT_REPO_ROOT
 n=$1; shift
-args="--no-cpu-baseline --no-profile --steps 60 --warmup 10 --dense-people 0"
+args="--full --no-cpu-baseline --no-profile --steps 60 --warmup 10 --dense-people 0"
 for i in $(seq $n); do
   for l in "$@"; do
     if [ "$l" = "-" ]; then e=""; else e="HH_LIB=$l"; fi

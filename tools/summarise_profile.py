@@ -55,7 +55,7 @@ def short(n):
 
 
 lines = [f"# {tag} rocprofv3 summaries (bench.py default workload: HigherHRNet-W32, batch 32 @ 512x512, 1x MI355X)", "",
-         "Recipe: `bash tools/profile_round.sh " + tag + "` = `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py "
+         "Recipe: `bash tools/profile_round.sh " + tag + "` = `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full "
          "--no-cpu-baseline`, then separate `--pmc FETCH_SIZE` and `--pmc WRITE_SIZE` passes (`--steps 3 --warmup 1`).",
          "`avg us (overlapped)` is the default bench (4 internal streams + the decode stream: kernels share the chip, so each one's "
          "wall duration is longer than its isolated duration); `avg us (serial)` is `bench.py --single-lane --sequential` (one kernel "
@@ -167,7 +167,7 @@ DECODE = ("stage_average", "nms_classify", "nms_tile_topk", "peaks_region", "fal
 traffic.update(fp8_traffic)
 traffic["hh_decode (all kernels of one call)"] = round(sum(2 * fetch.get(n, 0.0) + write.get(n, 0.0) for n in set(fetch) | set(write)
                                                            if n.startswith(DECODE)), -5)
-json.dump({"source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of `python3 bench.py --no-cpu-baseline --steps 3 --warmup 1` "
+json.dump({"source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of `python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1` "
                      f"(profiles/{tag}_summary.md); read = 2*FETCH_SIZE KiB (gfx950 correction), write = WRITE_SIZE KiB, averaged per launch",
            "bytes_per_launch": traffic}, open(os.path.join(prof, f"traffic_{tag}.json"), "w"), indent=1)
 print("\n".join(lines[:20]))
