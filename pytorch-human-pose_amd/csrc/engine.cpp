@@ -28,6 +28,7 @@ PlanSwitches PlanSwitches::from_env()
     s.no_junc_pair = on("HH_NO_JUNC_PAIR");
     s.full_join = on("HH_FULL_JOIN");
     s.no_fusion_merge = on("HH_NO_FUSION_MERGE");
+    s.no_fused_upsum = on("HH_NO_FUSED_UPSUM");
     s.poison_ws = on("HH_POISON_WS");
     s.poison_lds = on("HH_POISON_LDS");
     s.no_head_fold = on("HH_NO_HEAD_FOLD");
@@ -40,7 +41,7 @@ PlanSwitches PlanSwitches::from_env()
     if (const char *sk = getenv("HH_DEBUG_SKIP")) {
         static const struct { const char *name; unsigned bit; } cats[] = {{"s2big", SK_S2BIG}, {"s2", SK_S2}, {"upadd", SK_UPADD}, {"c1x1", SK_C1X1},
             {"c256", SK_C256}, {"c128", SK_C128}, {"junc", SK_JUNC}, {"bb32", SK_BB32}, {"bb64", SK_BB64}, {"stem", SK_STEM}, {"deconv", SK_DECONV},
-            {"head", SK_HEAD}, {"trans0", SK_TRANS0}};
+            {"head", SK_HEAD}, {"trans0", SK_TRANS0}, {"upsum", SK_UPSUM}};
         std::string v = std::string(",") + sk + ",";
         for (const auto &c : cats)
             if (v.find(std::string(",") + c.name + ",") != std::string::npos) s.debug_skip |= c.bit;
@@ -404,6 +405,23 @@ struct Builder {
                     // OUT is the x[i] of the previous HR block, which the other lanes' fusion launches read then: before the first
                     // write to it this lane must be behind every other lane's mark (which is behind those reads)
                     auto need_all = [&]() { for (int j = 0; j < nsc; ++j) need(j); };
+                    // bf16, 32-channel branch 0: output 0 as ONE launch (fusion_up.hip) that runs the 1x1 terms once per low-resolution
+                    // pixel and keeps them on the chip; it waits for every source up front.  (HH_NO_FUSED_UPSUM=1: a 1x1 launch per
+                    // source as each becomes ready, then upadd_kernel -- the same bits)
+                    if (i == 0 && n.dtype != 2 && w[0] == 32 && !n.sw.no_fused_upsum) {
+                        Op o;
+                        o.kind = OP_UPSUM; o.in = x[0]; o.out = OUT; o.C = w[0]; o.relu = 1; o.lane = lane;
+                        for (int j = 1; j < nsc; ++j) {
+                            const std::string lp = fp + ".scales_fusion_layers.0." + std::to_string(j);
+                            o.up[o.nup] = x[j]; o.up_shift[o.nup] = j;
+                            o.up_layer[o.nup] = L(lp + ".0", lp + ".1", w[j], w[0], 1, 1);
+                            ++o.nup;
+                        }
+                        o.layer = o.up_layer[0];
+                        need_all();
+                        n.ops.push_back(o);
+                        continue;
+                    }
                     Op up;
                     up.kind = OP_UPADD; up.in = x[i]; up.out = OUT; up.C = w[i]; up.relu = (i == 0); up.lane = lane;
                     for (int j = i + 1; j < nsc; ++j) {  // low -> high: 1x1 conv + BN at low res
@@ -965,6 +983,7 @@ int hh_net::enqueue(const float *images, int B, int H, int W, float *o1, float *
         if (sw.debug_skip) {  // measurement only: the outputs are wrong
             unsigned cat = 0;
             if (op.kind == OP_UPADD) cat = SK_UPADD;
+            else if (op.kind == OP_UPSUM) cat = SK_UPSUM;
             else if (op.kind == OP_JUNC) cat = SK_JUNC;
             else if (op.kind == OP_STEM) cat = SK_STEM;
             else if (op.kind == OP_BB) cat = layers[op.layer].cout == 32 ? SK_BB32 : layers[op.layer].cout == 64 ? SK_BB64 : 0;
@@ -1102,6 +1121,45 @@ int hh_net::enqueue(const float *images, int B, int H, int W, float *o1, float *
             p.out = o.ptr; p.out_cs = o.C; p.out_coff = 0;
             p.B = B; p.H = H >> b.shift; p.W = W >> b.shift; p.C = op.C; p.relu = op.relu;
             HH_CHECK_HIP(launch_upadd(p, s));
+            break;
+        }
+        case OP_UPSUM: {  // output 0 of a fusion layer: 1x1 terms + sum + ReLU in one launch
+            const TensorDesc &b0 = tensors[op.in], &o = tensors[op.out];
+            FusionUpParams p{};
+            p.x0 = b0.ptr; p.x0_cs = b0.C;
+            p.nsrc = op.nup;
+            double flops = 0, bytes = 2.0 * B * (H >> b0.shift) * (W >> b0.shift) * op.C * 2;
+            for (int j = 0; j < op.nup; ++j) {
+                const ConvLayer &l = layers[op.up_layer[j]];
+                const TensorDesc &t = tensors[op.up[j]];
+                if (t.shift != b0.shift + j + 1 || l.KC != 32 || l.NT != 1 || l.ncg != 1 || l.cin != (op.C << (j + 1))) {
+                    hh_set_error("plan: fusion output 0 does not fit fusion_up.hip (HH_NO_FUSED_UPSUM=1)");
+                    return 1;
+                }
+                p.src[j] = t.ptr; p.src_cs[j] = t.C; p.w[j] = l.d_w; p.bias[j] = l.d_bias;
+                const double npix = (double)B * (H >> t.shift) * (W >> t.shift);
+                flops += 2.0 * npix * l.cin * l.cout;
+                bytes += 2.0 * npix * l.cin + 2.0 * l.cin * l.cout;
+            }
+            p.out = o.ptr; p.out_cs = o.C;
+            p.B = B; p.H = H >> b0.shift; p.W = W >> b0.shift;
+            if (prof_enabled) {
+                if (prof_used == prof.size()) {
+                    ProfRecord r{};
+                    HH_CHECK_HIP(hipEventCreate(&r.e0));
+                    HH_CHECK_HIP(hipEventCreate(&r.e1));
+                    prof.push_back(r);
+                }
+                ProfRecord *pr = &prof[prof_used++];
+                pr->op = (int)(&op - ops.data());
+                pr->cfg = HH_CFG_FUSION_UP;
+                pr->flops = flops;
+                pr->bytes = bytes;
+                pr->slot = prof_used <= HH_PROF_SLOTS ? (int)prof_used - 1 : -1;
+                if (pr->slot >= 0 && prof_clk) p.clk = d_clk + 4 * pr->slot;
+                hh_launch_probe() = LaunchProbe{pr->e0, pr->e1};  // the launch below stamps e0 / e1 from its dispatch packet
+            }
+            HH_CHECK_HIP(fusion_up_launch(p, s));
             break;
         }
         case OP_TAP: {
@@ -1417,7 +1475,7 @@ int hh_net::check_plan(std::string *why) const
         std::vector<int> rd, wr;
         switch (op.kind) {
         case OP_CONV: rd = {op.in, op.res, op.in2, op.in3}; wr = {op.out}; break;
-        case OP_UPADD: rd = {op.in, op.up[0], op.up[1], op.up[2]}; wr = {op.out}; break;
+        case OP_UPADD: case OP_UPSUM: rd = {op.in, op.up[0], op.up[1], op.up[2]}; wr = {op.out}; break;
         case OP_BB: rd = {op.in}; wr = {op.out}; break;
         case OP_JUNC: rd = {op.in, op.in2, op.res, op.in3}; wr = {op.out, op.out2}; break;
         case OP_STEM: wr = {op.out}; break;
@@ -1474,6 +1532,15 @@ double hh_net::flops(int B, int H, int W) const
         if (op.kind == OP_JUNC) {
             const TensorDesc &ti = tensors[op.in];
             macs += (double)(H >> ti.shift) * (W >> ti.shift) * 64.0 * 256.0 * (1 + (op.in2 >= 0 && op.layer4 < 0) + (op.layer3 >= 0));
+            continue;
+        }
+        if (op.kind == OP_UPSUM) {  // the 1x1 terms at their sources' resolution, in the order their own launches had
+            for (int j = 0; j < op.nup; ++j) {
+                const ConvLayer &l = layers[op.up_layer[j]];
+                const TensorDesc &ts = tensors[op.up[j]];
+                const double hin = H >> ts.shift, win = W >> ts.shift;
+                macs += hin * win * (double)l.cin * l.cout * l.ks * l.ks;
+            }
             continue;
         }
         if (op.kind != OP_CONV) continue;

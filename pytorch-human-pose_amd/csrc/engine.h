@@ -73,7 +73,7 @@ struct TensorDesc {
     bool shared_scale = false;  // fp8: written in channel slices by several ops (torch.cat buffer): one scale for all of them
 };
 
-enum OpKind { OP_CONV, OP_UPADD, OP_TAP, OP_BB, OP_JOIN, OP_AVGPOOL, OP_LINEAR, OP_DEP, OP_JUNC, OP_STEM, OP_MARK, OP_WAITL, OP_QUANT };
+enum OpKind { OP_CONV, OP_UPADD, OP_TAP, OP_BB, OP_JOIN, OP_AVGPOOL, OP_LINEAR, OP_DEP, OP_JUNC, OP_STEM, OP_MARK, OP_WAITL, OP_QUANT, OP_UPSUM };
 
 struct Op {
     OpKind kind = OP_CONV;
@@ -90,6 +90,7 @@ struct Op {
     int cout_store = -1;
     int scatter = 0;  // 1: write to (2*oy+py, 2*ox+px)
     int up[3] = {-1, -1, -1}, up_shift[3] = {0, 0, 0}, nup = 0;
+    int up_layer[3] = {-1, -1, -1};  // OP_UPSUM: up[j] are the sources x_j themselves and up_layer[j] their 1x1 conv (`layer` = up_layer[0])
     int C = 0;  // UPADD channel count / TAP channel count
     int tap = -1;
     bool res8 = false;  // fp8 handle: this conv's residual stays e4m3 (stage 0's 256-channel trunk: its 1x1 convs are HBM-bound and a bf16
@@ -140,6 +141,8 @@ struct PlanSwitches {
     bool no_junc_pair = false;     // HH_NO_JUNC_PAIR=1: every stage-0 junction stores its 256-channel output
     bool full_join = false;        // HH_FULL_JOIN=1: all-to-all joins of the branch lanes instead of per-source waits
     bool no_fusion_merge = false;  // HH_NO_FUSION_MERGE=1: one launch per summed stride-2 conv of a fusion layer
+    bool no_fused_upsum = false;   // HH_NO_FUSED_UPSUM=1: output 0 of a fusion layer as one 1x1 launch per source + upadd_kernel
+                                   // (default, bf16 W32: one fusion_up.hip launch, bit-identical)
     bool poison_ws = false;        // HH_POISON_WS=1 (tests): workspace filled with NaN patterns at allocation
     // Persistent workgroups of the fused 32- / 64-channel blocks INSIDE an HR module (beside the other branches' lanes).  Default 0 =
     // half the CUs each: the two fat kernels (150 KB of LDS per workgroup: a CU holds one of them and nothing else) then run side by
@@ -163,7 +166,7 @@ struct PlanSwitches {
 };
 
 enum SkipCat { SK_S2BIG = 1, SK_S2 = 2, SK_UPADD = 4, SK_C1X1 = 8, SK_C256 = 16, SK_C128 = 32, SK_JUNC = 64, SK_BB32 = 128, SK_BB64 = 256,
-               SK_STEM = 512, SK_DECONV = 1024, SK_HEAD = 2048, SK_TRANS0 = 4096 };
+               SK_STEM = 512, SK_DECONV = 1024, SK_HEAD = 2048, SK_TRANS0 = 4096, SK_UPSUM = 8192 };
 
 struct hh_net {
     int K, C, dtype;

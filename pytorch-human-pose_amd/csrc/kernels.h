@@ -233,6 +233,23 @@ struct UpAddParams {
     int B, H, W, C, relu;
 };
 hipError_t launch_upadd(const UpAddParams &p, hipStream_t s);
+// Output 0 of a fusion layer in one launch (fusion_up.hip), 32 channels:
+// out[b,y,x,c] = relu(x0[b,y,x,c] + sum_j u_j[b, y>>j, x>>j, c]),  u_j = bf16(bias_j + W_j x_j) for the sources j = 1..nsrc
+struct FusionUpParams {
+    const bf16_raw *x0; int x0_cs;      // [B, H, W, x0_cs], channels 0..31
+    const bf16_raw *src[3];             // x_j: [B, H >> j, W >> j, src_cs], 32 << j channels
+    int src_cs[3];
+    const bf16_raw *w[3];               // 1x1 conv + BN of source j, packed as conv_mfma packs KC = 32, NT = 1 layers: [cin/8][32][8]
+    const float *bias[3];               // [32]
+    int nsrc;                           // 1..3
+    bf16_raw *out; int out_cs;          // channels 0..31 written (out may be a wider buffer)
+    int B, H, W;                        // branch-0 map
+    int tiles_x, tiles_y;               // filled by fusion_up_launch
+    unsigned long long *clk;            // optional {min start, max end} device-clock probe
+};
+#define HH_CFG_FUSION_UP 107  // pseudo instantiation index used by the profiler
+bool fusion_up_supported(int C, int nsrc);
+hipError_t fusion_up_launch(FusionUpParams p, hipStream_t s);
 hipError_t launch_upadd_backward(const bf16_raw *dy, const bf16_raw *out, int relu, int B, int H, int W, int C, bf16_raw *g, bf16_raw *const *dup,
                                  const int *up_shift, int nup, hipStream_t s);
 // the same on e4m3 tensors: out = e4m3(act(base * base_scale + sum_j up_j * up_scale[j]) * out_inv_scale); C multiple of 16
