@@ -667,6 +667,31 @@ int hh_family_pick(int ks, int stride, int cin_pad, int coutp, int *KC, int *NT)
     return 1;
 }
 
+// Eval-mode BatchNorm `bn` folded into the conv in front of it: returns the scale of output channel co and sets *shift.  With a
+// conv bias *cb in front of the BN, shift = beta + (cb - mu) * scale (plain convs pass cb = 0 when they have none); with cb = nullptr
+// it is beta - mu * scale, the stem's and the merged fusion convs' form.  The two differ in the sign of a zero shift (beta = -0,
+// mu = +0), so each path keeps its own.
+float hh_net::bn_fold(const std::string &bn, int co, const float *cb, float *shift) const
+{
+    const float g = param(bn + ".weight")[co], bta = param(bn + ".bias")[co];
+    const float mu = param(bn + ".running_mean")[co], var = param(bn + ".running_var")[co];
+    const float sc = g / std::sqrt(var + 1e-5f);
+    *shift = cb ? bta + (*cb - mu) * sc : bta - mu * sc;
+    return sc;
+}
+
+// per-output-channel scale and shift of a plain conv layer (BN folded, or scale 1 and the conv bias), zero padded to coutp
+void hh_net::fold_layer(const ConvLayer &l, int coutp, std::vector<float> &scale, std::vector<float> &shift) const
+{
+    scale.assign(coutp, 0.f);
+    shift.assign(coutp, 0.f);
+    for (int co = 0; co < l.cout; ++co) {
+        const float cb = l.bias.empty() ? 0.f : param(l.bias)[co];  // conv bias (in front of the BN: classification head)
+        if (l.bn.empty()) { scale[co] = 1.f; shift[co] = cb; }
+        else scale[co] = bn_fold(l.bn, co, &cb, &shift[co]);
+    }
+}
+
 int hh_net::finalize()
 {
     for (auto &p : params)
@@ -685,28 +710,19 @@ int hh_net::finalize()
         HH_CHECK_HIP(hipGetDeviceProperties(&prop, dev));
         num_cus = prop.multiProcessorCount;
     }
-    auto get = [&](const std::string &name) -> const std::vector<float> & { return params[param_index.at(name)].data; };
     for (auto &l : layers) {
         if (l.stem) {  // [cout tile 2][k-step 2][half 2][32][8], tap = c*9 + ky*3 + kx, BN scale folded
-            const std::vector<float> &W = get(l.conv + ".weight");
+            const std::vector<float> &W = param(l.conv + ".weight");
             std::vector<bf16_raw> packed(64 * 32, 0);
             std::vector<float> shift(64);
             for (int co = 0; co < 64; ++co) {
-                const float g = get(l.bn + ".weight")[co], bta = get(l.bn + ".bias")[co];
-                const float mu = get(l.bn + ".running_mean")[co], var = get(l.bn + ".running_var")[co];
-                const float sc = g / std::sqrt(var + 1e-5f);
-                shift[co] = bta - mu * sc;
+                const float sc = bn_fold(l.bn, co, nullptr, &shift[co]);
                 for (int t = 0; t < 27; ++t) {
                     const int kk = t / 16, hh = (t % 16) / 8, j = t % 8;
                     packed[((((co / 32) * 2 + kk) * 2 + hh) * 32 + co % 32) * 8 + j] = f2bf(W[(size_t)co * 27 + t] * sc);
                 }
             }
-            if (l.d_w) { hipFree(l.d_w); l.d_w = nullptr; }
-            if (l.d_bias) { hipFree(l.d_bias); l.d_bias = nullptr; }
-            HH_CHECK_HIP(hipMalloc((void **)&l.d_w, packed.size() * 2));
-            HH_CHECK_HIP(hipMalloc((void **)&l.d_bias, 64 * 4));
-            HH_CHECK_HIP(hipMemcpy(l.d_w, packed.data(), packed.size() * 2, hipMemcpyHostToDevice));
-            HH_CHECK_HIP(hipMemcpy(l.d_bias, shift.data(), 64 * 4, hipMemcpyHostToDevice));
+            if (hh_upload(&l.d_w, packed.data(), packed.size() * 2) || hh_upload(&l.d_bias, shift.data(), 64 * 4)) return 1;
             continue;
         }
         if (dtype == 2 && !l.hi) continue;  // e4m3 weights: finalize_fp8() below
@@ -730,12 +746,11 @@ int hh_net::finalize()
             int c0 = 0;
             for (size_t m = 0; m < l.mconv.size(); ++m) {
                 if (l.mcin[m] % l.KC) { hh_set_error("merged fusion conv: input width not a multiple of the chunk size"); return 1; }
-                const std::vector<float> &Wj = get(l.mconv[m] + ".weight");
+                const std::vector<float> &Wj = param(l.mconv[m] + ".weight");
                 for (int co = 0; co < l.cout; ++co) {
-                    const float g = get(l.mbn[m] + ".weight")[co], bta = get(l.mbn[m] + ".bias")[co];
-                    const float mu = get(l.mbn[m] + ".running_mean")[co], var = get(l.mbn[m] + ".running_var")[co];
-                    const float sc = g / std::sqrt(var + 1e-5f);
-                    shift[co] += bta - mu * sc;
+                    float sh;
+                    const float sc = bn_fold(l.mbn[m], co, nullptr, &sh);
+                    shift[co] += sh;
                     for (int ci = 0; ci < l.mcin[m]; ++ci)
                         for (int t = 0; t < 9; ++t) Wm[((size_t)co * l.cin + c0 + ci) * 9 + t] = Wj[((size_t)co * l.mcin[m] + ci) * 9 + t] * sc;
                 }
@@ -743,17 +758,12 @@ int hh_net::finalize()
             }
             std::vector<bf16_raw> packed;
             hh_pack_weights(Wm.data(), one.data(), 3, l.cin, l.cout, l.KC, COUT_T, false, 0, 0, packed);
-            if (l.d_w) { hipFree(l.d_w); l.d_w = nullptr; }
-            if (l.d_bias) { hipFree(l.d_bias); l.d_bias = nullptr; }
-            HH_CHECK_HIP(hipMalloc((void **)&l.d_w, packed.size() * 2));
-            HH_CHECK_HIP(hipMalloc((void **)&l.d_bias, (size_t)coutp * 4));
-            HH_CHECK_HIP(hipMemcpy(l.d_w, packed.data(), packed.size() * 2, hipMemcpyHostToDevice));
-            HH_CHECK_HIP(hipMemcpy(l.d_bias, shift.data(), (size_t)coutp * 4, hipMemcpyHostToDevice));
+            if (hh_upload(&l.d_w, packed.data(), packed.size() * 2) || hh_upload(&l.d_bias, shift.data(), (size_t)coutp * 4)) return 1;
             continue;
         }
         std::vector<float> Wfold;
         if (!l.fold_w.empty()) {  // [C + 1, cout, 4, 4]: rows 0..C-1 = Wd_feats + sum_k Wf[k, c] * Wd_hm[k], row C = sum_k bf[k] * Wd_hm[k]
-            const std::vector<float> &Wd = get(l.conv + ".weight"), &Wf = get(l.fold_w), &bf = get(l.fold_b);
+            const std::vector<float> &Wd = param(l.conv + ".weight"), &Wf = param(l.fold_w), &bf = param(l.fold_b);
             const int Cf = l.cin - 1, K2 = (int)bf.size();
             Wfold.assign((size_t)l.cin * l.cout * 16, 0.f);
             for (int c = 0; c <= Cf; ++c)
@@ -765,21 +775,9 @@ int hh_net::finalize()
                         Wfold[((size_t)c * l.cout + co) * 16 + t] = (float)acc;
                     }
         }
-        const std::vector<float> &W = Wfold.empty() ? get(l.conv + ".weight") : Wfold;
-        std::vector<float> scale(coutp, 0.f), shift(coutp, 0.f);
-        for (int co = 0; co < l.cout; ++co) {
-            if (!l.bn.empty()) {
-                const float g = get(l.bn + ".weight")[co], bta = get(l.bn + ".bias")[co];
-                const float mu = get(l.bn + ".running_mean")[co], var = get(l.bn + ".running_var")[co];
-                const float sc = g / std::sqrt(var + 1e-5f);
-                const float cb = l.bias.empty() ? 0.f : get(l.bias)[co];  // conv bias in front of BN (classification head)
-                scale[co] = sc;
-                shift[co] = bta + (cb - mu) * sc;
-            } else {
-                scale[co] = 1.f;
-                shift[co] = l.bias.empty() ? 0.f : get(l.bias)[co];
-            }
-        }
+        const std::vector<float> &W = Wfold.empty() ? param(l.conv + ".weight") : Wfold;
+        std::vector<float> scale, shift;
+        fold_layer(l, coutp, scale, shift);
         std::vector<bf16_raw> packed;
         if (l.transposed && l.py < 0) {
             for (int ph = 0; ph < 4; ++ph) {
@@ -790,32 +788,19 @@ int hh_net::finalize()
             }
         } else
             hh_pack_weights(W.data(), scale.data(), l.ks, l.cin, l.cout, l.KC, COUT_T, l.transposed, l.py, l.px, packed);
-        if (l.d_w) { hipFree(l.d_w); l.d_w = nullptr; }
-        if (l.d_bias) { hipFree(l.d_bias); l.d_bias = nullptr; }
-        HH_CHECK_HIP(hipMalloc((void **)&l.d_w, packed.size() * 2));
-        HH_CHECK_HIP(hipMalloc((void **)&l.d_bias, (size_t)coutp * 4));
-        HH_CHECK_HIP(hipMemcpy(l.d_w, packed.data(), packed.size() * 2, hipMemcpyHostToDevice));
-        HH_CHECK_HIP(hipMemcpy(l.d_bias, shift.data(), (size_t)coutp * 4, hipMemcpyHostToDevice));
+        if (hh_upload(&l.d_w, packed.data(), packed.size() * 2) || hh_upload(&l.d_bias, shift.data(), (size_t)coutp * 4)) return 1;
         if (l.fin_head) {  // B fragments of the head inside bbpc_final_kernel: lane (cout r, half h) of k half m holds cin 16m + 8h .. +7
             std::vector<bf16_raw> wf(2 * 2 * 32 * 8, 0);
             for (int m = 0; m < 2; ++m)
                 for (int hh = 0; hh < 2; ++hh)
                     for (int co = 0; co < l.cout; ++co)
                         for (int j = 0; j < 8; ++j) wf[(((m * 2 + hh) * 32) + co) * 8 + j] = f2bf(W[(size_t)co * l.cin + 16 * m + 8 * hh + j] * scale[co]);
-            if (l.d_wfin) { hipFree(l.d_wfin); l.d_wfin = nullptr; }
-            HH_CHECK_HIP(hipMalloc((void **)&l.d_wfin, wf.size() * 2));
-            HH_CHECK_HIP(hipMemcpy(l.d_wfin, wf.data(), wf.size() * 2, hipMemcpyHostToDevice));
+            if (hh_upload(&l.d_wfin, wf.data(), wf.size() * 2)) return 1;
         }
     }
     if (kind == 1) {
-        const auto &fw = get("classification_head.classifier.weight");
-        const auto &fb = get("classification_head.classifier.bias");
-        if (d_fc_w) hipFree(d_fc_w);
-        if (d_fc_b) hipFree(d_fc_b);
-        HH_CHECK_HIP(hipMalloc((void **)&d_fc_w, fw.size() * 4));
-        HH_CHECK_HIP(hipMalloc((void **)&d_fc_b, fb.size() * 4));
-        HH_CHECK_HIP(hipMemcpy(d_fc_w, fw.data(), fw.size() * 4, hipMemcpyHostToDevice));
-        HH_CHECK_HIP(hipMemcpy(d_fc_b, fb.data(), fb.size() * 4, hipMemcpyHostToDevice));
+        const auto &fw = param("classification_head.classifier.weight"), &fb = param("classification_head.classifier.bias");
+        if (hh_upload(&d_fc_w, fw.data(), fw.size() * 4) || hh_upload(&d_fc_b, fb.data(), fb.size() * 4)) return 1;
     }
     for (auto &g : graphs) hipGraphExecDestroy(g.exec);
     graphs.clear();
@@ -890,30 +875,62 @@ int hh_net::reserve(int B, int H, int W)
 }
 
 // ------------------------------------------------------------------------- execution
-int hh_pick_config(int ks, int stride, int KC, int NT, int Wo)
+int hh_pick_config(int ks, int stride, int KC, int NT, int Wo, int db)
 {
     int best = -1;
     for (int i = 0; i < conv_num_configs(); ++i) {
         const ConvConfig &c = conv_config(i);
-        if (c.KS != ks || c.S != stride || c.KC != KC || c.NT != NT || c.DB) continue;
+        if (c.KS != ks || c.S != stride || c.KC != KC || c.NT != NT || c.DB != db) continue;
         if (best < 0) best = i;
         const bool want16 = Wo <= 16;
         if ((c.TW == 16) == want16) return i;
     }
     return best;
 }
-static int pick_config(const ConvLayer &l, int Wo)
-{
-    int best = -1;
-    for (int i = 0; i < conv_num_configs(); ++i) {
-        const ConvConfig &c = conv_config(i);
-        if (c.KS != l.ks || c.S != l.stride || c.KC != l.KC || c.NT != l.NT || c.DB != l.db) continue;
-        if (best < 0) best = i;
-        const bool want16 = Wo <= 16;
-        if ((c.TW == 16) == want16) return i;
+
+namespace {
+// The plan's edges (OP_JOIN / OP_MARK / OP_WAITL / OP_DEP) as vector clocks over the launches per lane: what every lane is already
+// ordered behind.  enqueue() issues a wait only where it orders something new, and check_plan() proves the schedule race-free on
+// the same model.
+struct LaneClocks {
+    int open = 1;         // lanes [0, open) have been forked: the caller's stream waits for their work at the end
+    int seq[4] = {};      // launches per lane
+    int vc[4][4] = {};    // vc[l][m], m != l: lane l is ordered behind the first vc[l][m] launches of lane m
+    int mark[4][4] = {};  // the clocks of the lanes the last OP_MARK recorded
+    bool marked[4] = {};
+    int launch(int l) { return ++seq[l]; }
+    bool behind(int l, int m, int t) const { return (m == l ? seq[l] : vc[l][m]) >= t; }
+    void clock(int l, int *out) const { for (int m = 0; m < 4; ++m) out[m] = m == l ? seq[l] : vc[l][m]; }
+    bool order(int l, const int *c) {  // lane l is behind clock c from now on; false: it already was
+        bool any = false;
+        for (int m = 0; m < 4; ++m)
+            if (m != l && c[m] > vc[l][m]) { vc[l][m] = c[m]; any = true; }
+        return any;
     }
-    return best;
-}
+    int join(int nlanes) {  // all lanes [0, nlanes) behind lanes [0, nrec), which record; the others have run nothing yet
+        const int nrec = std::min(nlanes, open);
+        int c[4][4];
+        for (int m = 0; m < nrec; ++m) clock(m, c[m]);
+        for (int l = 0; l < nlanes; ++l)
+            for (int m = 0; m < nrec; ++m)
+                if (m != l) order(l, c[m]);
+        open = std::max(open, nlanes);
+        return nrec;
+    }
+    int set_mark(int from, int nlanes) {  // lanes [from, nrec) record their position
+        const int nrec = std::min(nlanes, open);
+        for (int m = 0; m < 4; ++m) {
+            marked[m] = m >= from && m < nrec;
+            if (marked[m]) clock(m, mark[m]);
+        }
+        open = std::max(open, nlanes);
+        return nrec;
+    }
+    bool wait_mark(int l, int m) { return order(l, mark[m]); }
+    bool dep(int l, int m) { int c[4]; clock(m, c); return order(l, c); }  // lane l behind all that lane m has run
+};
+bool is_edge(OpKind k) { return k == OP_JOIN || k == OP_MARK || k == OP_WAITL || k == OP_DEP; }
+}  // namespace
 
 int hh_net::enqueue(const float *images, int B, int H, int W, float *o1, float *o2, hipStream_t s0)
 {
@@ -950,6 +967,13 @@ int hh_net::enqueue(const float *images, int B, int H, int W, float *o1, float *
         *e = lane_events[lane_events_used++];
         return 0;
     };
+    auto lane_wait = [&](int l, int from) -> int {  // lane l waits for all that lane `from` has been given so far
+        hipEvent_t e;
+        if (next_event(&e)) return 1;
+        HH_CHECK_HIP(hipEventRecord(e, L[from]));
+        HH_CHECK_HIP(hipStreamWaitEvent(L[l], e, 0));
+        return 0;
+    };
     if (prof_enabled && prof_used == 0) {  // first forward since hh_profile_enable: device-clock slots start as {~0, 0}
         if (!d_clk) {
             HH_CHECK_HIP(hipMalloc((void **)&d_clk, HH_PROF_SLOTS * 32));
@@ -962,206 +986,52 @@ int hh_net::enqueue(const float *images, int B, int H, int W, float *o1, float *
         for (int i = 0; i < HH_PROF_SLOTS; ++i) init[4 * i] = ~0ull;
         HH_CHECK_HIP(hipMemcpy(d_clk, init.data(), init.size() * 8, hipMemcpyHostToDevice));
     }
-    int lanes_open = 1;  // lanes [0, lanes_open) have work that the caller's stream must wait for at the end
-    hipEvent_t mark_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    // What each lane is already ordered behind, as vector clocks over the launches enqueued so far (check_plan's model, kept while
-    // enqueueing): a wait whose event names nothing newer is dropped.  A wait is a barrier packet that costs its stream ~11 us even
+    // A wait whose event orders nothing new (LaneClocks) is dropped.  A wait is a barrier packet that costs its stream ~11 us even
     // if the event completed long before (tools/probes/event_cost.py) -- e.g. the closing edges for lanes that lane 0 has joined already.
-    int seqn[4] = {0, 0, 0, 0}, vc[4][4] = {}, mark_snap[4][4] = {};
-    auto snap = [&](int l, int *out) { for (int m = 0; m < 4; ++m) out[m] = m == l ? seqn[l] : vc[l][m]; };
-    auto news = [&](int l, const int *sn) {  // does the snapshot hold anything lane l is not behind yet?  (then: l is behind it from now on)
-        bool any = false;
-        for (int m = 0; m < 4; ++m)
-            if (m != l && sn[m] > vc[l][m]) { vc[l][m] = sn[m]; any = true; }
-        return any;
-    };
+    LaneClocks lc;
+    hipEvent_t mark_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     int fin_done = -1;  // index of the head conv that the last fused block has already run
     for (const Op &op : ops) {
         hipStream_t s = L[op.lane];
         if (fin_done >= 0 && &op == &ops[fin_done]) continue;
-        if (op.kind != OP_JOIN && op.kind != OP_MARK && op.kind != OP_WAITL && op.kind != OP_DEP) ++seqn[op.lane];  // (a launch, or nothing: over-counting only keeps a wait)
-        if (sw.debug_skip) {  // measurement only: the outputs are wrong
-            unsigned cat = 0;
-            if (op.kind == OP_UPADD) cat = SK_UPADD;
-            else if (op.kind == OP_UPSUM) cat = SK_UPSUM;
-            else if (op.kind == OP_JUNC) cat = SK_JUNC;
-            else if (op.kind == OP_STEM) cat = SK_STEM;
-            else if (op.kind == OP_BB) cat = layers[op.layer].cout == 32 ? SK_BB32 : layers[op.layer].cout == 64 ? SK_BB64 : 0;
-            else if (op.kind == OP_CONV) {
-                const ConvLayer &l = layers[op.layer];
-                if (l.transposed) cat = SK_DECONV;
-                else if (op.f32_out) cat = SK_HEAD;
-                else if (l.stride == 2) cat = SK_S2 | (l.cin >= 128 ? SK_S2BIG : 0) | (l.cin == 256 && l.mconv.empty() && tensors[op.in].shift == 2 ? SK_TRANS0 : 0);
-                else if (l.ks == 1) cat = SK_C1X1;
-                else if (l.cin == 256 && l.cout == 256) cat = SK_C256;
-                else if (l.cin == 128 && l.cout == 128) cat = SK_C128;
-                else if (l.cin == 256 && tensors[op.in].shift == 2) cat = SK_TRANS0;
-            }
-            if (cat & sw.debug_skip) continue;
-        }
-        if (sw.poison_lds && op.kind != OP_JOIN && op.kind != OP_MARK && op.kind != OP_WAITL && op.kind != OP_DEP && op.kind != OP_TAP)
-            HH_CHECK_HIP(launch_lds_poison(num_cus, s));
+        if (!is_edge(op.kind)) lc.launch(op.lane);  // (a launch, or nothing: over-counting only keeps a wait)
+        if (sw.debug_skip && (hh_skip_cats(op, layers, tensors) & sw.debug_skip)) continue;  // measurement only: the outputs are wrong
+        if (sw.poison_lds && !is_edge(op.kind) && op.kind != OP_TAP) HH_CHECK_HIP(launch_lds_poison(num_cus, s));
+        int rc = 0;
         switch (op.kind) {
         case OP_JOIN: {
             if (!multi) break;
             // lanes that have not run anything yet only wait (recording on a stream that has not joined a
             // capture and then waiting on that event from the capturing stream is illegal)
             hipEvent_t e[4];
-            const int nrec = op.nlanes < lanes_open ? op.nlanes : lanes_open;
+            const int nrec = lc.join(op.nlanes);
             for (int l = 0; l < nrec; ++l) {
                 if (next_event(&e[l])) return 1;
                 HH_CHECK_HIP(hipEventRecord(e[l], L[l]));
             }
-            int sn[4][4];
-            for (int m = 0; m < nrec; ++m) snap(m, sn[m]);
             for (int l = 0; l < op.nlanes; ++l)
                 for (int m = 0; m < nrec; ++m)
-                    if (m != l) { news(l, sn[m]); HH_CHECK_HIP(hipStreamWaitEvent(L[l], e[m], 0)); }
-            if (op.nlanes > lanes_open) lanes_open = op.nlanes;
+                    if (m != l) HH_CHECK_HIP(hipStreamWaitEvent(L[l], e[m], 0));
             break;
         }
         case OP_MARK: {
             if (!multi) break;
-            const int nrec = op.nlanes < lanes_open ? op.nlanes : lanes_open;
+            const int nrec = lc.set_mark(op.dep_from, op.nlanes);
             for (int l = 0; l < 4; ++l) mark_ev[l] = nullptr;  // a wait may only name a lane THIS mark recorded
             for (int l = op.dep_from; l < nrec; ++l) {
                 if (next_event(&mark_ev[l])) return 1;
                 HH_CHECK_HIP(hipEventRecord(mark_ev[l], L[l]));
-                snap(l, mark_snap[l]);
             }
-            if (op.nlanes > lanes_open) lanes_open = op.nlanes;
             break;
         }
-        case OP_WAITL: {
+        case OP_WAITL:
             if (!multi) break;
-            if (!mark_ev[op.dep_from]) { hh_set_error("plan: OP_WAITL names a lane the last OP_MARK did not record"); return 1; }
-            if (!news(op.lane, mark_snap[op.dep_from]) && !sw.keep_waits) break;  // already behind it
-            HH_CHECK_HIP(hipStreamWaitEvent(L[op.lane], mark_ev[op.dep_from], 0));
+            if (!lc.marked[op.dep_from]) { hh_set_error("plan: OP_WAITL names a lane the last OP_MARK did not record"); return 1; }
+            if (lc.wait_mark(op.lane, op.dep_from) || sw.keep_waits) HH_CHECK_HIP(hipStreamWaitEvent(L[op.lane], mark_ev[op.dep_from], 0));
             break;
-        }
-        case OP_DEP: {
-            if (!multi) break;
-            int sn[4];
-            snap(op.dep_from, sn);
-            if (!news(op.lane, sn) && !sw.keep_waits) break;
-            hipEvent_t e;
-            if (next_event(&e)) return 1;
-            HH_CHECK_HIP(hipEventRecord(e, L[op.dep_from]));
-            HH_CHECK_HIP(hipStreamWaitEvent(L[op.lane], e, 0));
+        case OP_DEP:
+            if (multi && (lc.dep(op.lane, op.dep_from) || sw.keep_waits)) rc = lane_wait(op.lane, op.dep_from);
             break;
-        }
-        case OP_STEM: {
-            const ConvLayer &l = layers[op.layer];
-            if (op.layer2 >= 0) {  // both stem convolutions in one kernel
-                const ConvLayer &l2 = layers[op.layer2];
-                StemFusedParams q{};
-                q.images = images; q.w1 = l.d_w; q.b1 = l.d_bias; q.w2 = l2.d_w; q.b2 = l2.d_bias;
-                q.out = tensors[op.out].ptr; q.out_cs = tensors[op.out].C;
-                q.B = B; q.H = H; q.W = W;
-                if (!stem_fused_supported(q)) { hh_set_error("hh_forward: the fused stem needs H, W multiples of 4 and images below 2 GB (HH_NO_STEM_FUSED=1)"); return 1; }
-                if (prof_enabled) {
-                    if (prof_used == prof.size()) {
-                        ProfRecord r{};
-                        HH_CHECK_HIP(hipEventCreate(&r.e0));
-                        HH_CHECK_HIP(hipEventCreate(&r.e1));
-                        prof.push_back(r);
-                    }
-                    ProfRecord *pr = &prof[prof_used++];
-                    pr->op = (int)(&op - ops.data());
-                    pr->cfg = HH_CFG_STEM_FUSED;
-                    pr->flops = 2.0 * B * (H / 2) * (W / 2) * 27.0 * 64.0 + 2.0 * B * (H / 4) * (W / 4) * 576.0 * 64.0;
-                    pr->bytes = (double)B * H * W * 3 * 4 + (double)B * (H / 4) * (W / 4) * 64 * 2 + 64 * 32 * 2 + 73728;
-                    pr->slot = prof_used <= HH_PROF_SLOTS ? (int)prof_used - 1 : -1;
-                    if (pr->slot >= 0 && prof_clk) q.clk = d_clk + 4 * pr->slot;
-                    hh_launch_probe() = LaunchProbe{pr->e0, pr->e1};
-                }
-                HH_CHECK_HIP(stem_fused_launch(q, num_cus, s));
-                break;
-            }
-            StemParams p{};
-            p.images = images; p.w = l.d_w; p.bias = l.d_bias;
-            p.out = tensors[op.out].ptr; p.out_cs = tensors[op.out].C;
-            p.B = B; p.H = H; p.W = W;
-            if (dtype == 2) {
-                p.out_fp8 = (unsigned char *)tensors[op.out].ptr; p.out_inv_scale = 1.f / op.s_out;
-                if (calibrating) p.absmax = d_amax + (&op - ops.data());
-            }
-            ProfRecord *pr = nullptr;
-            if (prof_enabled) {
-                if (prof_used == prof.size()) {
-                    ProfRecord r{};
-                    HH_CHECK_HIP(hipEventCreate(&r.e0));
-                    HH_CHECK_HIP(hipEventCreate(&r.e1));
-                    prof.push_back(r);
-                }
-                pr = &prof[prof_used++];
-                pr->op = (int)(&op - ops.data());
-                pr->cfg = HH_CFG_STEM;
-                pr->flops = 2.0 * B * (H / 2) * (W / 2) * 27.0 * 64.0;
-                pr->bytes = (double)B * H * W * 3 * 4 + (double)B * (H / 2) * (W / 2) * 64 * 2 + 64 * 32 * 2;
-                pr->slot = prof_used <= HH_PROF_SLOTS ? (int)prof_used - 1 : -1;
-                if (pr->slot >= 0 && prof_clk) p.clk = d_clk + 4 * pr->slot;
-                hh_launch_probe() = LaunchProbe{pr->e0, pr->e1};  // the launch below stamps e0 / e1 from its dispatch packet
-            }
-            HH_CHECK_HIP(stem_conv_launch(p, s));
-            break;
-        }
-        case OP_UPADD: {
-            if (dtype == 2) {
-                if (enqueue_fp8_upadd(op, B, H, W, s)) return 1;
-                break;
-            }
-            UpAddParams p{};
-            const TensorDesc &b = tensors[op.in], &o = tensors[op.out];
-            p.base = b.ptr; p.base_cs = b.C; p.base_coff = 0;
-            p.nup = op.nup;
-            for (int j = 0; j < op.nup; ++j) {
-                p.up[j] = tensors[op.up[j]].ptr; p.up_cs[j] = tensors[op.up[j]].C; p.up_shift[j] = op.up_shift[j];
-            }
-            p.out = o.ptr; p.out_cs = o.C; p.out_coff = 0;
-            p.B = B; p.H = H >> b.shift; p.W = W >> b.shift; p.C = op.C; p.relu = op.relu;
-            HH_CHECK_HIP(launch_upadd(p, s));
-            break;
-        }
-        case OP_UPSUM: {  // output 0 of a fusion layer: 1x1 terms + sum + ReLU in one launch
-            const TensorDesc &b0 = tensors[op.in], &o = tensors[op.out];
-            FusionUpParams p{};
-            p.x0 = b0.ptr; p.x0_cs = b0.C;
-            p.nsrc = op.nup;
-            double flops = 0, bytes = 2.0 * B * (H >> b0.shift) * (W >> b0.shift) * op.C * 2;
-            for (int j = 0; j < op.nup; ++j) {
-                const ConvLayer &l = layers[op.up_layer[j]];
-                const TensorDesc &t = tensors[op.up[j]];
-                if (t.shift != b0.shift + j + 1 || l.KC != 32 || l.NT != 1 || l.ncg != 1 || l.cin != (op.C << (j + 1))) {
-                    hh_set_error("plan: fusion output 0 does not fit fusion_up.hip (HH_NO_FUSED_UPSUM=1)");
-                    return 1;
-                }
-                p.src[j] = t.ptr; p.src_cs[j] = t.C; p.w[j] = l.d_w; p.bias[j] = l.d_bias;
-                const double npix = (double)B * (H >> t.shift) * (W >> t.shift);
-                flops += 2.0 * npix * l.cin * l.cout;
-                bytes += 2.0 * npix * l.cin + 2.0 * l.cin * l.cout;
-            }
-            p.out = o.ptr; p.out_cs = o.C;
-            p.B = B; p.H = H >> b0.shift; p.W = W >> b0.shift;
-            if (prof_enabled) {
-                if (prof_used == prof.size()) {
-                    ProfRecord r{};
-                    HH_CHECK_HIP(hipEventCreate(&r.e0));
-                    HH_CHECK_HIP(hipEventCreate(&r.e1));
-                    prof.push_back(r);
-                }
-                ProfRecord *pr = &prof[prof_used++];
-                pr->op = (int)(&op - ops.data());
-                pr->cfg = HH_CFG_FUSION_UP;
-                pr->flops = flops;
-                pr->bytes = bytes;
-                pr->slot = prof_used <= HH_PROF_SLOTS ? (int)prof_used - 1 : -1;
-                if (pr->slot >= 0 && prof_clk) p.clk = d_clk + 4 * pr->slot;
-                hh_launch_probe() = LaunchProbe{pr->e0, pr->e1};  // the launch below stamps e0 / e1 from its dispatch packet
-            }
-            HH_CHECK_HIP(fusion_up_launch(p, s));
-            break;
-        }
         case OP_TAP: {
             if (!taps_enabled) break;
             const TapInfo &t = taps[op.tap];
@@ -1183,207 +1053,190 @@ int hh_net::enqueue(const float *images, int B, int H, int W, float *o1, float *
         case OP_LINEAR:
             HH_CHECK_HIP(launch_linear(d_pool, d_fc_w, d_fc_b, o1, B, 2048, num_classes, s));
             break;
-        case OP_JUNC: {
-            const ConvLayer &l3 = layers[op.layer];
-            JuncParams p{};
-            const TensorDesc &ti = tensors[op.in];
-            p.t2 = tensors[op.in].ptr; p.t2_cs = tensors[op.in].C;
-            if (op.res >= 0) { p.res = tensors[op.res].ptr; p.res_cs = tensors[op.res].C; }
-            if (op.in2 >= 0) { p.x = tensors[op.in2].ptr; p.x_cs = tensors[op.in2].C; p.wd = layers[op.layer2].d_w; p.bd = layers[op.layer2].d_bias; }
-            p.w3 = l3.d_w; p.b3 = l3.d_bias;
-            if (op.layer4 >= 0) {
-                p.t2a = tensors[op.in3].ptr; p.t2a_cs = tensors[op.in3].C;
-                p.w3a = layers[op.layer4].d_w; p.b3a = layers[op.layer4].d_bias;
-            }
-            if (op.layer3 >= 0) { p.w1 = layers[op.layer3].d_w; p.b1 = layers[op.layer3].d_bias; p.t1 = tensors[op.out2].ptr; p.t1_cs = tensors[op.out2].C; }
-            if (op.out >= 0) { p.y = tensors[op.out].ptr; p.y_cs = tensors[op.out].C; }
-            p.npix = B * (H >> ti.shift) * (W >> ti.shift);
-            ProfRecord *pr = nullptr;
-            if (prof_enabled) {
-                if (prof_used == prof.size()) {
-                    ProfRecord r{};
-                    HH_CHECK_HIP(hipEventCreate(&r.e0));
-                    HH_CHECK_HIP(hipEventCreate(&r.e1));
-                    prof.push_back(r);
-                }
-                pr = &prof[prof_used++];
-                pr->op = (int)(&op - ops.data());
-                pr->cfg = HH_CFG_JUNCTION;
-                pr->flops = 2.0 * p.npix * 64.0 * 256.0 * (1 + (op.in2 >= 0 && op.layer4 < 0) + (op.layer3 >= 0));
-                // (algorithmic: what the unit needs when every junction stores y and reads the previous one -- the pair mode's savings
-                // and its extra GEMMs are the implementation's business)
-                pr->bytes = 2.0 * p.npix * (64 + ((op.in2 >= 0 && op.layer4 < 0) ? 64 : 256) + 256 + (op.layer3 >= 0 ? 64 : 0)) +
-                            2.0 * 64 * 256 * (1 + (op.in2 >= 0 && op.layer4 < 0) + (op.layer3 >= 0));
-                pr->slot = prof_used <= HH_PROF_SLOTS ? (int)prof_used - 1 : -1;
-                if (pr->slot >= 0 && prof_clk) p.clk = d_clk + 4 * pr->slot;
-                hh_launch_probe() = LaunchProbe{pr->e0, pr->e1};  // the launch below stamps e0 / e1 from its dispatch packet
-            }
-            HH_CHECK_HIP(junction_launch(p, num_cus, s));
-            break;
+        case OP_STEM: rc = enqueue_stem(op, images, B, H, W, s); break;
+        case OP_UPADD: rc = dtype == 2 ? enqueue_fp8_upadd(op, B, H, W, s) : enqueue_upadd(op, B, H, W, s); break;
+        case OP_UPSUM: rc = enqueue_upsum(op, B, H, W, s); break;
+        case OP_JUNC: rc = enqueue_junc(op, B, H, W, s); break;
+        case OP_BB: rc = dtype == 2 ? enqueue_fp8_bb(op, B, H, W, s) : enqueue_bb(op, B, H, W, o2, multi, s, &fin_done); break;
+        case OP_QUANT: rc = enqueue_fp8_quant(op, B, H, W, s); break;
+        case OP_CONV: rc = dtype == 2 && !op.hi ? enqueue_fp8_conv(op, B, H, W, o1, o2, s) : enqueue_conv(op, B, H, W, o1, o2, s); break;
         }
-        case OP_BB: {
-            if (dtype == 2) {
-                ProfRecord *pr = nullptr;
-                if (prof_enabled) {
-                    if (prof_used == prof.size()) {
-                        ProfRecord r{};
-                        HH_CHECK_HIP(hipEventCreate(&r.e0));
-                        HH_CHECK_HIP(hipEventCreate(&r.e1));
-                        prof.push_back(r);
-                    }
-                    pr = &prof[prof_used++];
-                    pr->op = (int)(&op - ops.data());
-                    pr->slot = -1;
-                }
-                if (enqueue_fp8_bb(op, B, H, W, s, pr)) return 1;
-                break;
-            }
-            const ConvLayer &l1 = layers[op.layer], &l2 = layers[op.layer2];
-            const TensorDesc &ti = tensors[op.in], &to = tensors[op.out];
-            BBParams p{};
-            p.in = ti.ptr; p.in_cs = ti.C; p.out = to.ptr; p.out_cs = to.C;
-            p.w1 = l1.d_w; p.w2 = l2.d_w; p.b1 = l1.d_bias; p.b2 = l2.d_bias;
-            p.B = B; p.H = H >> ti.shift; p.W = W >> ti.shift;
-            p.tall = sw.bb_tall;
-            if (op.fin >= 0 && !sw.no_final_fuse && !sw.bb32_tile && !taps_enabled && o2 && !(sw.debug_skip & SK_HEAD)) {
-                const ConvLayer &lf = layers[ops[op.fin].layer];
-                p.fin_w = lf.d_wfin; p.fin_b = lf.d_bias; p.fin_out = o2; p.fin_K = lf.cout;
-                if (lf.d_wfin && bbpc_final_supported(p)) fin_done = op.fin;
-                else { p.fin_w = nullptr; p.fin_b = nullptr; p.fin_out = nullptr; p.fin_K = 0; }
-            }
-            ProfRecord *pr = nullptr;
-            if (prof_enabled) {
-                if (prof_used == prof.size()) {
-                    ProfRecord r{};
-                    HH_CHECK_HIP(hipEventCreate(&r.e0));
-                    HH_CHECK_HIP(hipEventCreate(&r.e1));
-                    prof.push_back(r);
-                }
-                pr = &prof[prof_used++];
-                pr->op = (int)(&op - ops.data());
-                const double Cb = l1.cout;
-                pr->cfg = l1.cout == 64 ? HH_CFG_BB64_FUSED : HH_CFG_BB_FUSED;
-                pr->slot = prof_used <= HH_PROF_SLOTS ? (int)prof_used - 1 : -1;
-                if (pr->slot >= 0 && prof_clk) p.clk = d_clk + 4 * pr->slot;
-                pr->flops = 2.0 * 2.0 * B * p.H * p.W * Cb * Cb * 9.0;
-                pr->bytes = 2.0 * B * p.H * p.W * Cb * 2 + 2.0 * 2 * 9 * Cb * Cb;
-                if (p.fin_out) {  // + the head: the block output stays on the chip, K fp32 planes leave instead
-                    pr->flops += 2.0 * B * p.H * p.W * Cb * p.fin_K;
-                    pr->bytes += (4.0 * p.fin_K - 2.0 * Cb) * B * p.H * p.W + 2.0 * Cb * p.fin_K;
-                }
-                hh_launch_probe() = LaunchProbe{pr->e0, pr->e1};  // the launch below stamps e0 / e1 from its dispatch packet
-            }
-            // inside an HR module with the lanes on: half the chip per fat kernel (PlanSwitches::fat_cus); alone: all of it
-            auto budget = [&](int want) { return !(multi && op.siblings) ? num_cus : want > 0 ? (want < num_cus ? want : num_cus) : (num_cus + 1) / 2; };
-            const int fat = budget(sw.fat_cus), fat64 = budget(sw.fat_cus64);
-            if (l1.cout == 64) HH_CHECK_HIP(bb64_fused_launch(p, fat64, s));
-            else if (!sw.bb32_tile && bbpc_supported(p)) HH_CHECK_HIP(bbpc_launch(p, fat, s));
-            else HH_CHECK_HIP(bb_fused_launch(p, num_cus, s));
-            break;
-        }
-        case OP_QUANT:
-            if (enqueue_fp8_quant(op, B, H, W, s)) return 1;
-            break;
-        case OP_CONV: {
-            if (dtype == 2 && !op.hi) {
-                ProfRecord *pr = nullptr;
-                if (prof_enabled) {
-                    if (prof_used == prof.size()) {
-                        ProfRecord r{};
-                        HH_CHECK_HIP(hipEventCreate(&r.e0));
-                        HH_CHECK_HIP(hipEventCreate(&r.e1));
-                        prof.push_back(r);
-                    }
-                    pr = &prof[prof_used++];
-                    pr->op = (int)(&op - ops.data());
-                    pr->slot = -1;
-                }
-                if (enqueue_fp8_conv(op, B, H, W, o1, o2, s, pr)) return 1;
-                break;
-            }
-            const ConvLayer &l = layers[op.layer];
-            const TensorDesc &ti = tensors[op.in];
-            ConvParams p{};
-            p.Hin = H >> ti.shift; p.Win = W >> ti.shift;
-            p.in = dtype == 2 ? ti.ptr16 : ti.ptr; p.in_cs = ti.C; p.in_coff = op.in_coff;  // (fp8 handle, op.hi: the bf16 representations)
-            p.w = l.d_w; p.bias = l.d_bias;
-            p.Ho = l.stride == 2 ? p.Hin / 2 : p.Hin;
-            p.Wo = l.stride == 2 ? p.Win / 2 : p.Win;
-            p.osy = p.osx = 1; p.ooy = p.oox = 0;
-            p.pad_y = p.pad_x = (l.ks - 1) / 2;
-            if (l.transposed) {
-                p.osy = p.osx = 2; p.ooy = l.py; p.oox = l.px;
-                p.pad_y = l.py == 0 ? 1 : 0; p.pad_x = l.px == 0 ? 1 : 0;
-                if (l.py < 0) { p.nphase = 4; p.phase_stride = l.phase_stride; }
-            }
-            p.Hob = p.Ho * p.osy; p.Wob = p.Wo * p.osx;
-            if (op.out >= 0) {
-                const TensorDesc &to = tensors[op.out];
-                p.out = dtype == 2 ? to.ptr16 : to.ptr; p.out_cs = to.C; p.out_coff = op.out_coff;
-            }
-            if (op.res >= 0) {
-                const TensorDesc &tr = tensors[op.res];
-                p.res = dtype == 2 ? tr.ptr16 : tr.ptr; p.res_cs = tr.C; p.res_coff = op.res_coff;
-            }
-            p.out_f32 = op.f32_out == 1 ? o1 : op.f32_out == 2 ? o2 : nullptr;
-            if (op.in2 >= 0) {  // conv over the concatenated channels of two or three tensors of one shape and pixel stride
-                const TensorDesc &t2 = tensors[op.in2];
-                if (t2.C != ti.C || t2.shift != ti.shift || (op.in3 >= 0 && (tensors[op.in3].C != ti.C || tensors[op.in3].shift != ti.shift))) {
-                    hh_set_error("merged fusion conv: inputs differ in shape or pixel stride");
-                    return 1;
-                }
-                p.nch0 = l.mcin[0] / l.KC;
-                p.nch1 = l.mcin[1] / l.KC;
-                p.src_delta1 = t2.ptr - (ti.ptr + op.in_coff);
-                if (op.in3 >= 0) p.src_delta2 = tensors[op.in3].ptr - (ti.ptr + op.in_coff);
-            }
-            p.cin = l.cin_pad;
-            p.cout_real = l.cout;
-            p.cout_store = op.cout_store >= 0 ? op.cout_store : round_up(l.cout, 8);
-            p.relu = op.relu;
-            p.B = B;
-            const int cfg = pick_config(l, p.Wo);
-            const ConvConfig &c = conv_config(cfg);
-            p.tiles_x = (p.Wo + c.TW - 1) / c.TW;
-            p.tiles_y = (p.Ho + c.th() - 1) / c.th();
-            p.ncg = l.ncg;
-            ProfRecord *pr = nullptr;
-            if (prof_enabled) {
-                if (prof_used == prof.size()) {
-                    ProfRecord r{};
-                    HH_CHECK_HIP(hipEventCreate(&r.e0));
-                    HH_CHECK_HIP(hipEventCreate(&r.e1));
-                    prof.push_back(r);
-                }
-                pr = &prof[prof_used++];
-                pr->op = (int)(&op - ops.data());
-                pr->cfg = cfg;
-                pr->slot = prof_used <= HH_PROF_SLOTS ? (int)prof_used - 1 : -1;
-                if (pr->slot >= 0 && prof_clk) p.clk = d_clk + 4 * pr->slot;
-                const double acin = l.acct_cin ? l.acct_cin : l.cin;  // (algorithmic: the reference layer's input width)
-                pr->flops = 2.0 * B * p.Ho * p.Wo * acin * l.cout * l.ks * l.ks * (p.nphase > 1 ? 4 : 1);
-                {
-                    const double opix = (double)B * p.Ho * p.Wo * (p.nphase > 1 ? 4 : 1);
-                    pr->bytes = 2.0 * B * p.Hin * p.Win * acin + (p.out ? 2.0 * opix * l.cout : 0.0) + (p.res ? 2.0 * opix * l.cout : 0.0) +
-                                (p.out_f32 ? 4.0 * opix * l.cout : 0.0) + 2.0 * acin * l.cout * l.ks * l.ks * (p.nphase > 1 ? 4 : 1);
-                }
-                hh_launch_probe() = LaunchProbe{pr->e0, pr->e1};  // the launch below stamps e0 / e1 from its dispatch packet
-            }
-            HH_CHECK_HIP(conv_launch(cfg, p, s));
-            break;
-        }
-        }
+        if (rc) return 1;
     }
-    if (multi)
-        for (int l = 1; l < lanes_open; ++l) {  // close the fork: the caller's stream waits for every lane it is not behind yet
-            int sn[4];
-            snap(l, sn);
-            if (!news(0, sn) && !sw.keep_waits) continue;
-            hipEvent_t e;
-            if (next_event(&e)) return 1;
-            HH_CHECK_HIP(hipEventRecord(e, L[l]));
-            HH_CHECK_HIP(hipStreamWaitEvent(s0, e, 0));
+    if (multi)  // close the fork: the caller's stream waits for every lane it is not behind yet
+        for (int l = 1; l < lc.open; ++l)
+            if ((lc.dep(0, l) || sw.keep_waits) && lane_wait(0, l)) return 1;
+    return 0;
+}
+
+// Profiling (hh_profile_enable): the next ProfRecord of this forward (its events created on first use), filled for `op`, with the
+// launch probe armed.  Call it right in front of the launch it times: the next HH_LAUNCH of this thread consumes the probe.  A kernel
+// that can stamp the device clock passes its `clk` field and gets one of the HH_PROF_SLOTS slots (nullptr: no slot).
+int hh_net::prof_record(const Op &op, int cfg, const OpCost &c, unsigned long long **clk)
+{
+    if (prof_used == prof.size()) {
+        ProfRecord r{};
+        HH_CHECK_HIP(hipEventCreate(&r.e0));
+        HH_CHECK_HIP(hipEventCreate(&r.e1));
+        prof.push_back(r);
+    }
+    ProfRecord &r = prof[prof_used++];
+    r.op = (int)(&op - ops.data());
+    r.cfg = cfg;
+    r.flops = c.flops;
+    r.bytes = c.bytes;
+    r.slot = clk && prof_used <= HH_PROF_SLOTS ? (int)prof_used - 1 : -1;
+    if (r.slot >= 0 && prof_clk) *clk = d_clk + 4 * r.slot;
+    hh_launch_probe() = LaunchProbe{r.e0, r.e1};
+    return 0;
+}
+
+int hh_net::enqueue_stem(const Op &op, const float *images, int B, int H, int W, hipStream_t s)
+{
+    const ConvLayer &l = layers[op.layer];
+    if (op.layer2 >= 0) {  // both stem convolutions in one kernel
+        const ConvLayer &l2 = layers[op.layer2];
+        StemFusedParams q{};
+        q.images = images; q.w1 = l.d_w; q.b1 = l.d_bias; q.w2 = l2.d_w; q.b2 = l2.d_bias;
+        q.out = tensors[op.out].ptr; q.out_cs = tensors[op.out].C;
+        q.B = B; q.H = H; q.W = W;
+        if (!stem_fused_supported(q)) { hh_set_error("hh_forward: the fused stem needs H, W multiples of 4 and images below 2 GB (HH_NO_STEM_FUSED=1)"); return 1; }
+        if (prof_enabled && prof_record(op, HH_CFG_STEM_FUSED, op_cost(op, B, H, W), &q.clk)) return 1;
+        HH_CHECK_HIP(stem_fused_launch(q, num_cus, s));
+        return 0;
+    }
+    StemParams p{};
+    p.images = images; p.w = l.d_w; p.bias = l.d_bias;
+    p.out = tensors[op.out].ptr; p.out_cs = tensors[op.out].C;
+    p.B = B; p.H = H; p.W = W;
+    if (dtype == 2) {
+        p.out_fp8 = (unsigned char *)tensors[op.out].ptr; p.out_inv_scale = 1.f / op.s_out;
+        if (calibrating) p.absmax = d_amax + (&op - ops.data());
+    }
+    if (prof_enabled && prof_record(op, HH_CFG_STEM, op_cost(op, B, H, W), &p.clk)) return 1;
+    HH_CHECK_HIP(stem_conv_launch(p, s));
+    return 0;
+}
+
+int hh_net::enqueue_upadd(const Op &op, int B, int H, int W, hipStream_t s)
+{
+    UpAddParams p{};
+    const TensorDesc &b = tensors[op.in], &o = tensors[op.out];
+    p.base = b.ptr; p.base_cs = b.C; p.base_coff = 0;
+    p.nup = op.nup;
+    for (int j = 0; j < op.nup; ++j) {
+        p.up[j] = tensors[op.up[j]].ptr; p.up_cs[j] = tensors[op.up[j]].C; p.up_shift[j] = op.up_shift[j];
+    }
+    p.out = o.ptr; p.out_cs = o.C; p.out_coff = 0;
+    p.B = B; p.H = H >> b.shift; p.W = W >> b.shift; p.C = op.C; p.relu = op.relu;
+    HH_CHECK_HIP(launch_upadd(p, s));
+    return 0;
+}
+
+int hh_net::enqueue_upsum(const Op &op, int B, int H, int W, hipStream_t s)  // output 0 of a fusion layer: 1x1 terms + sum + ReLU in one launch
+{
+    const TensorDesc &b0 = tensors[op.in], &o = tensors[op.out];
+    FusionUpParams p{};
+    p.x0 = b0.ptr; p.x0_cs = b0.C;
+    p.nsrc = op.nup;
+    for (int j = 0; j < op.nup; ++j) {
+        const ConvLayer &l = layers[op.up_layer[j]];
+        const TensorDesc &t = tensors[op.up[j]];
+        if (t.shift != b0.shift + j + 1 || l.KC != 32 || l.NT != 1 || l.ncg != 1 || l.cin != (op.C << (j + 1))) {
+            hh_set_error("plan: fusion output 0 does not fit fusion_up.hip (HH_NO_FUSED_UPSUM=1)");
+            return 1;
         }
+        p.src[j] = t.ptr; p.src_cs[j] = t.C; p.w[j] = l.d_w; p.bias[j] = l.d_bias;
+    }
+    p.out = o.ptr; p.out_cs = o.C;
+    p.B = B; p.H = H >> b0.shift; p.W = W >> b0.shift;
+    if (prof_enabled && prof_record(op, HH_CFG_FUSION_UP, op_cost(op, B, H, W), &p.clk)) return 1;
+    HH_CHECK_HIP(fusion_up_launch(p, s));
+    return 0;
+}
+
+int hh_net::enqueue_junc(const Op &op, int B, int H, int W, hipStream_t s)
+{
+    const ConvLayer &l3 = layers[op.layer];
+    JuncParams p{};
+    const TensorDesc &ti = tensors[op.in];
+    p.t2 = tensors[op.in].ptr; p.t2_cs = tensors[op.in].C;
+    if (op.res >= 0) { p.res = tensors[op.res].ptr; p.res_cs = tensors[op.res].C; }
+    if (op.in2 >= 0) { p.x = tensors[op.in2].ptr; p.x_cs = tensors[op.in2].C; p.wd = layers[op.layer2].d_w; p.bd = layers[op.layer2].d_bias; }
+    p.w3 = l3.d_w; p.b3 = l3.d_bias;
+    if (op.layer4 >= 0) {
+        p.t2a = tensors[op.in3].ptr; p.t2a_cs = tensors[op.in3].C;
+        p.w3a = layers[op.layer4].d_w; p.b3a = layers[op.layer4].d_bias;
+    }
+    if (op.layer3 >= 0) { p.w1 = layers[op.layer3].d_w; p.b1 = layers[op.layer3].d_bias; p.t1 = tensors[op.out2].ptr; p.t1_cs = tensors[op.out2].C; }
+    if (op.out >= 0) { p.y = tensors[op.out].ptr; p.y_cs = tensors[op.out].C; }
+    p.npix = B * (H >> ti.shift) * (W >> ti.shift);
+    if (prof_enabled && prof_record(op, HH_CFG_JUNCTION, op_cost(op, B, H, W), &p.clk)) return 1;
+    HH_CHECK_HIP(junction_launch(p, num_cus, s));
+    return 0;
+}
+
+// *fin_done = op.fin when the block also runs the head behind it in its epilogue
+int hh_net::enqueue_bb(const Op &op, int B, int H, int W, float *o2, bool multi, hipStream_t s, int *fin_done)
+{
+    const ConvLayer &l1 = layers[op.layer], &l2 = layers[op.layer2];
+    const TensorDesc &ti = tensors[op.in], &to = tensors[op.out];
+    BBParams p{};
+    p.in = ti.ptr; p.in_cs = ti.C; p.out = to.ptr; p.out_cs = to.C;
+    p.w1 = l1.d_w; p.w2 = l2.d_w; p.b1 = l1.d_bias; p.b2 = l2.d_bias;
+    p.B = B; p.H = H >> ti.shift; p.W = W >> ti.shift;
+    p.tall = sw.bb_tall;
+    if (op.fin >= 0 && !sw.no_final_fuse && !sw.bb32_tile && !taps_enabled && o2 && !(sw.debug_skip & SK_HEAD)) {
+        const ConvLayer &lf = layers[ops[op.fin].layer];
+        p.fin_w = lf.d_wfin; p.fin_b = lf.d_bias; p.fin_out = o2; p.fin_K = lf.cout;
+        if (lf.d_wfin && bbpc_final_supported(p)) *fin_done = op.fin;
+        else { p.fin_w = nullptr; p.fin_b = nullptr; p.fin_out = nullptr; p.fin_K = 0; }
+    }
+    const int cfg = l1.cout == 64 ? HH_CFG_BB64_FUSED : HH_CFG_BB_FUSED;
+    if (prof_enabled && prof_record(op, cfg, op_cost(op, B, H, W, p.fin_out != nullptr), &p.clk)) return 1;
+    // inside an HR module with the lanes on: half the chip per fat kernel (PlanSwitches::fat_cus); alone: all of it
+    auto budget = [&](int want) { return !(multi && op.siblings) ? num_cus : want > 0 ? (want < num_cus ? want : num_cus) : (num_cus + 1) / 2; };
+    const int fat = budget(sw.fat_cus), fat64 = budget(sw.fat_cus64);
+    if (l1.cout == 64) HH_CHECK_HIP(bb64_fused_launch(p, fat64, s));
+    else if (!sw.bb32_tile && bbpc_supported(p)) HH_CHECK_HIP(bbpc_launch(p, fat, s));
+    else HH_CHECK_HIP(bb_fused_launch(p, num_cus, s));
+    return 0;
+}
+
+int hh_net::enqueue_conv(const Op &op, int B, int H, int W, float *o1, float *o2, hipStream_t s)  // bf16 kernels (fp8 handle, op.hi: over the bf16 representations)
+{
+    const ConvLayer &l = layers[op.layer];
+    const TensorDesc &ti = tensors[op.in];
+    ConvParams p{};
+    hh_conv_geometry(p, l, op, B, H >> ti.shift, W >> ti.shift, o1, o2);
+    p.in = dtype == 2 ? ti.ptr16 : ti.ptr; p.in_cs = ti.C; p.in_coff = op.in_coff;
+    p.w = l.d_w; p.bias = l.d_bias;
+    if (op.out >= 0) {
+        const TensorDesc &to = tensors[op.out];
+        p.out = dtype == 2 ? to.ptr16 : to.ptr; p.out_cs = to.C; p.out_coff = op.out_coff;
+    }
+    if (op.res >= 0) {
+        const TensorDesc &tr = tensors[op.res];
+        p.res = dtype == 2 ? tr.ptr16 : tr.ptr; p.res_cs = tr.C; p.res_coff = op.res_coff;
+    }
+    if (op.in2 >= 0) {  // conv over the concatenated channels of two or three tensors of one shape and pixel stride
+        const TensorDesc &t2 = tensors[op.in2];
+        if (t2.C != ti.C || t2.shift != ti.shift || (op.in3 >= 0 && (tensors[op.in3].C != ti.C || tensors[op.in3].shift != ti.shift))) {
+            hh_set_error("merged fusion conv: inputs differ in shape or pixel stride");
+            return 1;
+        }
+        p.nch0 = l.mcin[0] / l.KC;
+        p.nch1 = l.mcin[1] / l.KC;
+        p.src_delta1 = t2.ptr - (ti.ptr + op.in_coff);
+        if (op.in3 >= 0) p.src_delta2 = tensors[op.in3].ptr - (ti.ptr + op.in_coff);
+    }
+    p.cout_store = op.cout_store >= 0 ? op.cout_store : round_up(l.cout, 8);
+    const int cfg = hh_pick_config(l.ks, l.stride, l.KC, l.NT, p.Wo, l.db);
+    const ConvConfig &c = conv_config(cfg);
+    p.tiles_x = (p.Wo + c.TW - 1) / c.TW;
+    p.tiles_y = (p.Ho + c.th() - 1) / c.th();
+    if (prof_enabled && prof_record(op, cfg, op_cost(op, B, H, W), &p.clk)) return 1;
+    HH_CHECK_HIP(conv_launch(cfg, p, s));
     return 0;
 }
 
@@ -1394,9 +1247,6 @@ int hh_net::forward(const float *images, int B, int H, int W, float *o1, float *
     if (B > rB || H > rH || W > rW || !ws_ready || (taps_enabled && !taps.empty() && !taps[0].copy))
         if (reserve(B, H, W)) return 1;
     lastB = B; lastH = H; lastW = W;
-    // hipGraph capture of the multi-stream fork/join segfaults inside the ROCm 7.2 runtime on this plan, so the
-    // multi-lane mode always launches eagerly (at B=32 eager and graph replay time identically); graphs remain
-    // available for single-lane execution (hh_set_multi_lane(net, 0)), which is what small batches want.
     // The multi-lane plan always launches eagerly.  Stream capture of its fork / join pattern segfaults inside the ROCm 7.2 runtime,
     // and the explicit graph built in round 3 (kernel nodes re-added one by one, the plan's edges as node dependencies: git log,
     // profiles/r03_ab.md) replays bit-equal but ~4 ms SLOWER per forward than the eager launches at every batch size (1.55 vs
@@ -1428,50 +1278,28 @@ int hh_net::forward(const float *images, int B, int H, int W, float *o1, float *
     return 0;
 }
 
-// Static hazard check of the multi-lane plan: replays the fork/join/dep edges of enqueue() with vector clocks (one
-// component per lane) and verifies for every op that (RAW) the last writer of each tensor it reads, and (WAR/WAW) every
-// earlier reader and the last writer of each tensor it writes, happen-before it.  Ops of one lane are ordered by the stream.
+// Static hazard check of the multi-lane plan: replays the fork/join/dep edges of enqueue() on its LaneClocks and verifies for
+// every op that (RAW) the last writer of each tensor it reads, and (WAR/WAW) every earlier reader and the last writer of each
+// tensor it writes, happen-before it.  Ops of one lane are ordered by the stream.
 int hh_net::check_plan(std::string *why) const
 {
     struct Stamp { int lane; int t; int op; };
-    int clk[4][4] = {};  // clk[l][m] = latest event of lane m that lane l is ordered after
-    int mark_clk[4][4] = {};  // the lanes' clocks at the last OP_MARK
-    bool mark_ok[4] = {false, false, false, false};  // lanes the last OP_MARK recorded
-    auto before = [&](const Stamp &st, int lane) { return st.lane < 0 || clk[lane][st.lane] >= st.t; };
+    LaneClocks lc;
+    auto before = [&](const Stamp &st, int lane) { return st.lane < 0 || lc.behind(lane, st.lane, st.t); };
     std::vector<Stamp> writer(tensors.size(), Stamp{-1, 0, -1});
     std::vector<std::vector<Stamp>> readers(tensors.size());
-    int lanes_open = 1;
     for (size_t i = 0; i < ops.size(); ++i) {
         const Op &op = ops[i];
-        if (op.kind == OP_JOIN) {
-            const int nrec = op.nlanes < lanes_open ? op.nlanes : lanes_open;
-            int merged[4] = {};
-            for (int m = 0; m < nrec; ++m)
-                for (int c = 0; c < 4; ++c) merged[c] = std::max(merged[c], clk[m][c]);
-            for (int l = 0; l < op.nlanes; ++l)
-                for (int c = 0; c < 4; ++c) clk[l][c] = std::max(clk[l][c], merged[c]);
-            if (op.nlanes > lanes_open) lanes_open = op.nlanes;
-            continue;
-        }
-        if (op.kind == OP_DEP) {
-            for (int c = 0; c < 4; ++c) clk[op.lane][c] = std::max(clk[op.lane][c], clk[op.dep_from][c]);
-            continue;
-        }
-        if (op.kind == OP_MARK) {
-            const int nrec = op.nlanes < lanes_open ? op.nlanes : lanes_open;
-            for (int m = 0; m < 4; ++m) mark_ok[m] = m >= op.dep_from && m < nrec;
-            for (int m = op.dep_from; m < nrec; ++m)
-                for (int c = 0; c < 4; ++c) mark_clk[m][c] = clk[m][c];
-            if (op.nlanes > lanes_open) lanes_open = op.nlanes;
-            continue;
-        }
+        if (op.kind == OP_JOIN) { lc.join(op.nlanes); continue; }
+        if (op.kind == OP_DEP) { lc.dep(op.lane, op.dep_from); continue; }
+        if (op.kind == OP_MARK) { lc.set_mark(op.dep_from, op.nlanes); continue; }
         if (op.kind == OP_WAITL) {
-            if (!mark_ok[op.dep_from]) { if (why) *why = "op " + std::to_string(i) + " waits for a lane the last mark did not record"; return 1; }
-            for (int c = 0; c < 4; ++c) clk[op.lane][c] = std::max(clk[op.lane][c], mark_clk[op.dep_from][c]);
+            if (!lc.marked[op.dep_from]) { if (why) *why = "op " + std::to_string(i) + " waits for a lane the last mark did not record"; return 1; }
+            lc.wait_mark(op.lane, op.dep_from);
             continue;
         }
         const int l = op.lane;
-        if (l >= lanes_open) { if (why) *why = "op " + std::to_string(i) + " runs on a lane that was never forked"; return 1; }
+        if (l >= lc.open) { if (why) *why = "op " + std::to_string(i) + " runs on a lane that was never forked"; return 1; }
         std::vector<int> rd, wr;
         switch (op.kind) {
         case OP_CONV: rd = {op.in, op.res, op.in2, op.in3}; wr = {op.out}; break;
@@ -1484,7 +1312,7 @@ int hh_net::check_plan(std::string *why) const
         case OP_AVGPOOL: rd = {op.in}; break;
         default: break;
         }
-        const int t = ++clk[l][l];
+        const int t = lc.launch(l);
         for (int x : rd) {
             if (x < 0) continue;
             if (!before(writer[x], l)) {
@@ -1514,45 +1342,82 @@ int hh_net::check_plan(std::string *why) const
     return 0;
 }
 
-double hh_net::flops(int B, int H, int W) const
+// Algorithmic cost of one op from the plan alone (OpCost); what the profile records carry and what flops() adds up.  fin (OP_BB):
+// the block also runs the head ops[op.fin] in its epilogue.  Ops without a kernel of their own cost nothing here.
+OpCost hh_net::op_cost(const Op &op, int B, int H, int W, bool fin) const
 {
-    double macs = 0;
-    for (const Op &op : ops) {
-        if (op.kind == OP_BB) {
-            const TensorDesc &ti = tensors[op.in];
-            const double Cb = layers[op.layer].cout;
-            macs += 2.0 * (double)(H >> ti.shift) * (W >> ti.shift) * Cb * Cb * 9.0;
-            continue;
+    OpCost c;
+    switch (op.kind) {
+    case OP_STEM:  // conv1 at H/2; fused: conv2 (H/4) rides in the same launch and conv1's output stays on the chip
+        c.flops = 2.0 * B * (H / 2) * (W / 2) * 27.0 * 64.0 + (op.layer2 >= 0 ? 2.0 * B * (H / 4) * (W / 4) * 576.0 * 64.0 : 0.0);
+        c.bytes = (double)B * H * W * 3 * 4 + 64 * 32 * 2 +
+                  (op.layer2 >= 0 ? (double)B * (H / 4) * (W / 4) * 64 * 2 + 73728 : (double)B * (H / 2) * (W / 2) * 64 * 2);
+        break;
+    case OP_UPSUM: {  // the 1x1 terms at their sources' resolution
+        const TensorDesc &b0 = tensors[op.in];
+        c.bytes = 2.0 * B * (H >> b0.shift) * (W >> b0.shift) * op.C * 2;
+        for (int j = 0; j < op.nup; ++j) {
+            const ConvLayer &l = layers[op.up_layer[j]];
+            const TensorDesc &t = tensors[op.up[j]];
+            const double npix = (double)B * (H >> t.shift) * (W >> t.shift);
+            c.flops += 2.0 * npix * l.cin * l.cout * l.ks * l.ks;
+            c.bytes += 2.0 * npix * l.cin + 2.0 * l.cin * l.cout;
         }
-        if (op.kind == OP_STEM) {
-            macs += (double)(H / 2) * (W / 2) * 27.0 * 64.0;
-            if (op.layer2 >= 0) macs += (double)(H / 4) * (W / 4) * 576.0 * 64.0;  // conv2 rides in the same launch
-            continue;
+        break;
+    }
+    case OP_JUNC: {
+        const TensorDesc &ti = tensors[op.in];
+        const double npix = (double)B * (H >> ti.shift) * (W >> ti.shift);
+        const int ngemm = 1 + (op.in2 >= 0 && op.layer4 < 0) + (op.layer3 >= 0);
+        c.flops = 2.0 * npix * 64.0 * 256.0 * ngemm;
+        // (algorithmic: what the unit needs when every junction stores y and reads the previous one -- the pair mode's savings
+        // and its extra GEMMs are the implementation's business)
+        c.bytes = 2.0 * npix * (64 + ((op.in2 >= 0 && op.layer4 < 0) ? 64 : 256) + 256 + (op.layer3 >= 0 ? 64 : 0)) + 2.0 * 64 * 256 * ngemm;
+        break;
+    }
+    case OP_BB: {
+        const TensorDesc &ti = tensors[op.in], &to = tensors[op.out];
+        const double Cb = layers[op.layer].cout, npix = (double)B * (H >> ti.shift) * (W >> ti.shift);
+        c.flops = 2.0 * 2.0 * npix * Cb * Cb * 9.0;
+        if (dtype == 2)  // e4m3 in / out, + the bf16 representations the plan keeps of them
+            c.bytes = (2.0 + (ti.b16 ? 2.0 : 0.0) + (to.b16 ? 2.0 : 0.0)) * npix * Cb + 2.0 * 9 * Cb * Cb;
+        else
+            c.bytes = 2.0 * npix * Cb * 2 + 2.0 * 2 * 9 * Cb * Cb;
+        if (fin) {  // + the head: the block output stays on the chip, K fp32 planes leave instead
+            const double K2 = layers[ops[op.fin].layer].cout;
+            c.flops += op_cost(ops[op.fin], B, H, W).flops;
+            c.bytes += (4.0 * K2 - 2.0 * Cb) * npix + 2.0 * Cb * K2;
         }
-        if (op.kind == OP_JUNC) {
-            const TensorDesc &ti = tensors[op.in];
-            macs += (double)(H >> ti.shift) * (W >> ti.shift) * 64.0 * 256.0 * (1 + (op.in2 >= 0 && op.layer4 < 0) + (op.layer3 >= 0));
-            continue;
-        }
-        if (op.kind == OP_UPSUM) {  // the 1x1 terms at their sources' resolution, in the order their own launches had
-            for (int j = 0; j < op.nup; ++j) {
-                const ConvLayer &l = layers[op.up_layer[j]];
-                const TensorDesc &ts = tensors[op.up[j]];
-                const double hin = H >> ts.shift, win = W >> ts.shift;
-                macs += hin * win * (double)l.cin * l.cout * l.ks * l.ks;
-            }
-            continue;
-        }
-        if (op.kind != OP_CONV) continue;
+        break;
+    }
+    case OP_CONV: {
         const ConvLayer &l = layers[op.layer];
         const TensorDesc &ti = tensors[op.in];
-        const double hin = H >> ti.shift, win = W >> ti.shift;
-        const double ho = l.stride == 2 ? hin / 2 : hin, wo = l.stride == 2 ? win / 2 : win;
+        const int hin = H >> ti.shift, win = W >> ti.shift, ho = l.stride == 2 ? hin / 2 : hin, wo = l.stride == 2 ? win / 2 : win;
         // a transposed-conv phase: every input pixel meets 4 of the 16 taps per phase (16 over the 4 phases)
-        macs += ho * wo * (double)(l.acct_cin ? l.acct_cin : l.cin) * l.cout * l.ks * l.ks * ((l.transposed && l.py < 0) ? 4 : 1);
+        const int nph = l.transposed && l.py < 0 ? 4 : 1;
+        const double acin = l.acct_cin ? l.acct_cin : l.cin;  // (algorithmic: the reference layer's input width)
+        const double opix = (double)B * ho * wo * nph;
+        const bool e4m3 = dtype == 2 && !op.hi;  // e4m3 input and weights; the output in e4m3 and / or bf16, the residual in either
+        double out_e = 0, res_e = 0;  // bytes per output / residual element
+        if (op.out >= 0) out_e = e4m3 ? (tensors[op.out].f8 ? 1 : 0) + (tensors[op.out].b16 ? 2 : 0) : 2;
+        if (op.res >= 0) res_e = e4m3 && !tensors[op.res].b16 ? 1 : 2;
+        c.flops = 2.0 * opix * acin * l.cout * l.ks * l.ks;
+        c.bytes = (e4m3 ? 1.0 : 2.0) * ((double)B * hin * win * acin + acin * l.cout * l.ks * l.ks * nph) +
+                  (out_e + res_e + (op.f32_out ? 4 : 0)) * opix * l.cout;
+        break;
     }
-    if (kind == 1) macs += 2048.0 * num_classes;
-    return 2.0 * macs * B;
+    default:
+        break;
+    }
+    return c;
+}
+
+double hh_net::flops(int B, int H, int W) const
+{
+    double f = kind == 1 ? 2.0 * B * 2048.0 * num_classes : 0.0;  // the classifier's Linear
+    for (const Op &op : ops) f += op_cost(op, B, H, W).flops;
+    return f;
 }
 
 hh_net::~hh_net()

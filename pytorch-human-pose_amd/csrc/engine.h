@@ -118,7 +118,7 @@ struct TapInfo {
 
 struct ProfRecord {
     int op, cfg;
-    double flops, bytes;  // algorithmic: 2*MACs; input + output (+ residual) + weights once, no halo re-reads
+    double flops, bytes;  // hh_net::op_cost() of the launch
     hipEvent_t e0, e1;
     int slot;  // index into d_clk ({min start, max end} device-clock ticks written by the kernel itself), -1 = none
 };
@@ -167,6 +167,31 @@ struct PlanSwitches {
 
 enum SkipCat { SK_S2BIG = 1, SK_S2 = 2, SK_UPADD = 4, SK_C1X1 = 8, SK_C256 = 16, SK_C128 = 32, SK_JUNC = 64, SK_BB32 = 128, SK_BB64 = 256,
                SK_STEM = 512, SK_DECONV = 1024, SK_HEAD = 2048, SK_TRANS0 = 4096, SK_UPSUM = 8192 };
+// the HH_DEBUG_SKIP categories of one op (0: none)
+inline unsigned hh_skip_cats(const Op &op, const std::vector<ConvLayer> &layers, const std::vector<TensorDesc> &tensors)
+{
+    switch (op.kind) {
+    case OP_UPADD: return SK_UPADD;
+    case OP_UPSUM: return SK_UPSUM;
+    case OP_JUNC: return SK_JUNC;
+    case OP_STEM: return SK_STEM;
+    case OP_BB: return layers[op.layer].cout == 32 ? SK_BB32 : layers[op.layer].cout == 64 ? SK_BB64 : 0;
+    case OP_CONV: break;
+    default: return 0;
+    }
+    const ConvLayer &l = layers[op.layer];
+    if (l.transposed) return SK_DECONV;
+    if (op.f32_out) return SK_HEAD;
+    if (l.stride == 2) return SK_S2 | (l.cin >= 128 ? SK_S2BIG : 0) | (l.cin == 256 && l.mconv.empty() && tensors[op.in].shift == 2 ? SK_TRANS0 : 0);
+    if (l.ks == 1) return SK_C1X1;
+    if (l.cin == 256 && l.cout == 256) return SK_C256;
+    if (l.cin == 128 && l.cout == 128) return SK_C128;
+    if (l.cin == 256 && tensors[op.in].shift == 2) return SK_TRANS0;
+    return 0;
+}
+
+// algorithmic cost of one launch: 2*MACs of the reference layers it computes; input + output (+ residual) + weights once, no halo re-reads
+struct OpCost { double flops = 0, bytes = 0; };
 
 struct hh_net {
     int K, C, dtype;
@@ -212,6 +237,7 @@ struct hh_net {
                                   // intermediate-tile maxima of fused BasicBlocks
     int elem() const { return dtype == 2 ? 1 : 2; }  // bytes per activation element
 
+    const std::vector<float> &param(const std::string &name) const { return params[param_index.at(name)].data; }
     int build();
     int check_plan(std::string *why) const;  // static RAW/WAR/WAW check of the multi-lane schedule
     int add_param(const std::string &name, std::vector<int64_t> shape, bool counter = false);
@@ -220,21 +246,60 @@ struct hh_net {
     int enqueue(const float *images, int B, int H, int W, float *o1, float *o2, hipStream_t s);
     int forward(const float *images, int B, int H, int W, float *o1, float *o2, int use_graph, hipStream_t s);
     double flops(int B, int H, int W) const;
+    OpCost op_cost(const Op &op, int B, int H, int W, bool fin = false) const;
+    int prof_record(const Op &op, int cfg, const OpCost &c, unsigned long long **clk);
+    float bn_fold(const std::string &bn, int co, const float *cb, float *shift) const;
+    void fold_layer(const ConvLayer &l, int coutp, std::vector<float> &scale, std::vector<float> &shift) const;
+    int enqueue_stem(const Op &op, const float *images, int B, int H, int W, hipStream_t s);
+    int enqueue_upadd(const Op &op, int B, int H, int W, hipStream_t s);
+    int enqueue_upsum(const Op &op, int B, int H, int W, hipStream_t s);
+    int enqueue_junc(const Op &op, int B, int H, int W, hipStream_t s);
+    int enqueue_bb(const Op &op, int B, int H, int W, float *o2, bool multi, hipStream_t s, int *fin_done);
+    int enqueue_conv(const Op &op, int B, int H, int W, float *o1, float *o2, hipStream_t s);
     int finalize_fp8();
     int calibrate(const float *images, int B, int H, int W, int rounds, hipStream_t s);
     int resolve_scales();  // amax -> per-op scales (plan order), d_mult of every layer
-    int enqueue_fp8_conv(const Op &op, int B, int H, int W, float *o1, float *o2, hipStream_t s, ProfRecord *pr);
+    int enqueue_fp8_conv(const Op &op, int B, int H, int W, float *o1, float *o2, hipStream_t s);
     int enqueue_fp8_upadd(const Op &op, int B, int H, int W, hipStream_t s);
     int enqueue_fp8_quant(const Op &op, int B, int H, int W, hipStream_t s);
     void assign_fp8_formats();  // which representations (e4m3 / bf16) every tensor of an fp8 plan needs, from its readers
-    int enqueue_fp8_bb(const Op &op, int B, int H, int W, hipStream_t s, ProfRecord *pr);
+    int enqueue_fp8_bb(const Op &op, int B, int H, int W, hipStream_t s);
     void release_workspace();
     ~hh_net();
 };
 
 // kernel-family / instantiation choice, shared with the standalone conv op of the training path (capi.cpp)
 int hh_family_pick(int ks, int stride, int cin_pad, int coutp, int *KC, int *NT);
-int hh_pick_config(int ks, int stride, int KC, int NT, int Wo);
+int hh_pick_config(int ks, int stride, int KC, int NT, int Wo, int db = 0);
+
+// device copy of host data: *d is freed if set, then allocated and filled
+template <class T> int hh_upload(T **d, const void *host, size_t bytes)
+{
+    if (*d) { hipFree(*d); *d = nullptr; }
+    HH_CHECK_HIP(hipMalloc((void **)d, bytes));
+    HH_CHECK_HIP(hipMemcpy(*d, host, bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// What a bf16 and an fp8 conv launch (ConvParams / Fp8ConvParams) share: extents, stride, the transposed conv's phase and
+// padding, channel counts, the fp32 head output.  The caller picks the instantiation for p.Wo and sets the tiles.
+template <class P> void hh_conv_geometry(P &p, const ConvLayer &l, const Op &op, int B, int Hin, int Win, float *o1, float *o2)
+{
+    p.Hin = Hin; p.Win = Win;
+    p.Ho = l.stride == 2 ? p.Hin / 2 : p.Hin;
+    p.Wo = l.stride == 2 ? p.Win / 2 : p.Win;
+    p.osy = p.osx = 1; p.ooy = p.oox = 0;
+    p.pad_y = p.pad_x = (l.ks - 1) / 2;
+    if (l.transposed) {
+        p.osy = p.osx = 2; p.ooy = l.py; p.oox = l.px;
+        p.pad_y = l.py == 0 ? 1 : 0; p.pad_x = l.px == 0 ? 1 : 0;
+        if (l.py < 0) { p.nphase = 4; p.phase_stride = l.phase_stride; }
+    }
+    p.Hob = p.Ho * p.osy; p.Wob = p.Wo * p.osx;
+    p.out_f32 = op.f32_out == 1 ? o1 : op.f32_out == 2 ? o2 : nullptr;
+    p.cin = l.cin_pad; p.cout_real = l.cout; p.ncg = l.ncg;
+    p.relu = op.relu; p.B = B;
+}
 
 // fp8 (e4m3, OCP) helpers shared by the engine and the C-ABI
 unsigned char hh_f32_to_e4m3(float f);

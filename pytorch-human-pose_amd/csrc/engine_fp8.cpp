@@ -91,7 +91,6 @@ static void pack_weights_fp8(const float *W, const float *bn_scale, const float 
 int hh_net::finalize_fp8()
 {
     HH_CHECK_HIP(conv_fp8_init());
-    auto get = [&](const std::string &name) -> const std::vector<float> & { return params[param_index.at(name)].data; };
     for (auto &l : layers) {
         if (l.stem || l.hi) continue;  // packed by the common path (bf16 operands)
         hh_fp8_family_pick(l.cin, l.cout, &l.KC, &l.NT);
@@ -99,21 +98,9 @@ int hh_net::finalize_fp8()
         l.cin_pad = round_up(l.cin, l.KC);
         const int COUT_T = 32 * l.NT, coutp = round_up(l.cout, COUT_T);
         l.ncg = coutp / COUT_T;
-        const std::vector<float> &W = get(l.conv + ".weight");
-        std::vector<float> scale(coutp, 0.f), shift(coutp, 0.f);
-        for (int co = 0; co < l.cout; ++co) {
-            if (!l.bn.empty()) {
-                const float g = get(l.bn + ".weight")[co], bta = get(l.bn + ".bias")[co];
-                const float mu = get(l.bn + ".running_mean")[co], var = get(l.bn + ".running_var")[co];
-                const float sc = g / std::sqrt(var + 1e-5f);
-                const float cb = l.bias.empty() ? 0.f : get(l.bias)[co];
-                scale[co] = sc;
-                shift[co] = bta + (cb - mu) * sc;
-            } else {
-                scale[co] = 1.f;
-                shift[co] = l.bias.empty() ? 0.f : get(l.bias)[co];
-            }
-        }
+        const std::vector<float> &W = param(l.conv + ".weight");
+        std::vector<float> scale, shift;
+        fold_layer(l, coutp, scale, shift);
         // one weight scale per output channel: the largest |w * bn_scale| of the channel maps to 448
         l.w_scale.assign(coutp, 0.f);
         const size_t per_co = (size_t)l.cin * l.ks * l.ks * (l.transposed ? 4 : 1);  // transposed: 4x4 kernel = 4 phases of 2x2
@@ -138,14 +125,9 @@ int hh_net::finalize_fp8()
             }
         } else
             pack_weights_fp8(W.data(), scale.data(), l.w_scale.data(), l.ks, l.cin, l.cout, l.KC, COUT_T, l.transposed, l.py, l.px, packed);
-        if (l.d_w) { hipFree(l.d_w); l.d_w = nullptr; }
-        if (l.d_bias) { hipFree(l.d_bias); l.d_bias = nullptr; }
+        if (hh_upload(&l.d_w, packed.data(), packed.size()) || hh_upload(&l.d_bias, shift.data(), (size_t)coutp * 4)) return 1;
         if (l.d_mult) { hipFree(l.d_mult); l.d_mult = nullptr; }
-        HH_CHECK_HIP(hipMalloc((void **)&l.d_w, packed.size()));
-        HH_CHECK_HIP(hipMalloc((void **)&l.d_bias, (size_t)coutp * 4));
-        HH_CHECK_HIP(hipMalloc((void **)&l.d_mult, (size_t)coutp * 4));
-        HH_CHECK_HIP(hipMemcpy(l.d_w, packed.data(), packed.size(), hipMemcpyHostToDevice));
-        HH_CHECK_HIP(hipMemcpy(l.d_bias, shift.data(), (size_t)coutp * 4, hipMemcpyHostToDevice));
+        HH_CHECK_HIP(hipMalloc((void **)&l.d_mult, (size_t)coutp * 4));  // written by resolve_scales()
     }
     if (!d_amax) HH_CHECK_HIP(hipMalloc((void **)&d_amax, 2 * ops.size() * 4));
     calibrated = false;  // new weights: the activation ranges may have moved
@@ -270,24 +252,14 @@ int hh_net::calibrate(const float *images, int B, int H, int W, int rounds, hipS
     return rc;
 }
 
-int hh_net::enqueue_fp8_conv(const Op &op, int B, int H, int W, float *o1, float *o2, hipStream_t s, ProfRecord *pr)
+int hh_net::enqueue_fp8_conv(const Op &op, int B, int H, int W, float *o1, float *o2, hipStream_t s)
 {
     const ConvLayer &l = layers[op.layer];
     const TensorDesc &ti = tensors[op.in];
     Fp8ConvParams p{};
+    hh_conv_geometry(p, l, op, B, H >> ti.shift, W >> ti.shift, o1, o2);
     p.in = (const unsigned char *)ti.ptr; p.in_cs = ti.C; p.in_coff = op.in_coff;
-    p.Hin = H >> ti.shift; p.Win = W >> ti.shift;
     p.w = (const unsigned char *)l.d_w; p.mult = l.d_mult; p.bias = l.d_bias;
-    p.Ho = l.stride == 2 ? p.Hin / 2 : p.Hin;
-    p.Wo = l.stride == 2 ? p.Win / 2 : p.Win;
-    p.osy = p.osx = 1; p.ooy = p.oox = 0;
-    p.pad_y = p.pad_x = (l.ks - 1) / 2;
-    if (l.transposed) {
-        p.osy = p.osx = 2; p.ooy = l.py; p.oox = l.px;
-        p.pad_y = l.py == 0 ? 1 : 0; p.pad_x = l.px == 0 ? 1 : 0;
-        if (l.py < 0) { p.nphase = 4; p.phase_stride = l.phase_stride; }
-    }
-    p.Hob = p.Ho * p.osy; p.Wob = p.Wo * p.osx;
     if (op.out >= 0) {  // the representations the tensor's readers need (assign_fp8_formats)
         const TensorDesc &to = tensors[op.out];
         if (to.f8) { p.out = (unsigned char *)to.ptr; p.out_cs = to.C; p.out_coff = op.out_coff; p.out_inv_scale = 1.f / op.s_out; }
@@ -298,27 +270,13 @@ int hh_net::enqueue_fp8_conv(const Op &op, int B, int H, int W, float *o1, float
         if (tr.b16) { p.res16 = tr.ptr16; p.res16_cs = tr.C; p.res16_coff = op.res_coff; }
         else { p.res = (const unsigned char *)tr.ptr; p.res_cs = tr.C; p.res_coff = op.res_coff; p.res_scale = op.s_res; }
     }
-    p.out_f32 = op.f32_out == 1 ? o1 : op.f32_out == 2 ? o2 : nullptr;
-    p.cin = l.cin_pad;
-    p.cout_real = l.cout;
     p.cout_store = op.cout_store >= 0 ? op.cout_store : round_up(l.cout, 16);
-    p.relu = op.relu;
-    p.B = B;
     const int cfg = hh_fp8_pick_config(l.ks, l.stride, l.KC, l.NT, p.Wo);
     const Fp8ConvConfig &c = conv_fp8_config(cfg);
     p.tiles_x = (p.Wo + c.TW - 1) / c.TW;
     p.tiles_y = (p.Ho + c.th() - 1) / c.th();
-    p.ncg = l.ncg;
     if (calibrating && op.out >= 0) p.absmax = d_amax + (&op - ops.data());
-    if (pr) {
-        pr->cfg = 1000 + cfg;
-        pr->flops = 2.0 * B * p.Ho * p.Wo * (double)l.cin * l.cout * l.ks * l.ks * (p.nphase > 1 ? 4 : 1);
-        const double opix = (double)B * p.Ho * p.Wo * (p.nphase > 1 ? 4 : 1);
-        pr->bytes = 1.0 * B * p.Hin * p.Win * l.cin + (p.out ? opix * l.cout : 0.0) + (p.out16 ? 2.0 * opix * l.cout : 0.0) +
-                    (p.res ? opix * l.cout : 0.0) + (p.res16 ? 2.0 * opix * l.cout : 0.0) +
-                    (p.out_f32 ? 4.0 * opix * l.cout : 0.0) + 1.0 * l.cin * l.cout * l.ks * l.ks * (p.nphase > 1 ? 4 : 1);
-        hh_launch_probe() = LaunchProbe{pr->e0, pr->e1};
-    }
+    if (prof_enabled && prof_record(op, 1000 + cfg, op_cost(op, B, H, W), nullptr)) return 1;
     HH_CHECK_HIP(conv_fp8_launch(cfg, p, s));
     return 0;
 }
@@ -344,7 +302,7 @@ int hh_net::enqueue_fp8_upadd(const Op &op, int B, int H, int W, hipStream_t s)
     return 0;
 }
 
-int hh_net::enqueue_fp8_bb(const Op &op, int B, int H, int W, hipStream_t s, ProfRecord *pr)
+int hh_net::enqueue_fp8_bb(const Op &op, int B, int H, int W, hipStream_t s)
 {
     const ConvLayer &l1 = layers[op.layer], &l2 = layers[op.layer2];
     const TensorDesc &ti = tensors[op.in], &to = tensors[op.out];
@@ -357,13 +315,7 @@ int hh_net::enqueue_fp8_bb(const Op &op, int B, int H, int W, hipStream_t s, Pro
     if (to.b16) { p.out16 = to.ptr16; p.out16_cs = to.C; }
     p.B = B; p.H = H >> ti.shift; p.W = W >> ti.shift;
     if (calibrating) { p.amax_out = d_amax + (&op - ops.data()); p.amax_mid = d_amax + ops.size() + (&op - ops.data()); }
-    if (pr) {
-        const double Cb = l1.cout;
-        pr->cfg = HH_CFG_BB_FP8;
-        pr->flops = 2.0 * 2.0 * B * p.H * p.W * Cb * Cb * 9.0;
-        pr->bytes = (2.0 + (p.res16 ? 2.0 : 0.0) + (p.out16 ? 2.0 : 0.0)) * B * p.H * p.W * Cb + 2.0 * 9 * Cb * Cb;
-        hh_launch_probe() = LaunchProbe{pr->e0, pr->e1};
-    }
+    if (prof_enabled && prof_record(op, HH_CFG_BB_FP8, op_cost(op, B, H, W), nullptr)) return 1;
     HH_CHECK_HIP(bb_fp8_launch(l1.cout, p, num_cus, s));
     return 0;
 }

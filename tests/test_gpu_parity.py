@@ -1422,3 +1422,35 @@ def test_fp8_requires_calibration_and_taps_track_the_reference(pkg, net_golden):
     net.set_taps(False)
     with pytest.raises(pkg._lib.HHError, match="hh_calibrate"):
         net(x)
+
+
+def test_profile_records_add_up_to_the_forward_flops(pkg):
+    """The FLOPs of the profile records of one forward (bench.py --full's roofline) sum to hh_forward_flops exactly: one
+    accounting per op kind, also where the last block runs the final head in its epilogue and the head has no launch of its own."""
+    import ctypes as C
+
+    lib = pkg._lib.load()
+    B, H, W = 2, 128, 128
+
+    def bf16(C_, env):
+        with _switch_env(env):
+            return _net(pkg, C_, 1)[0]
+    nets = {"w32": bf16(32, {}), "w32 no final fuse": bf16(32, {"HH_NO_FINAL_FUSE": "1"}),
+            "w32 no fused upsum": bf16(32, {"HH_NO_FUSED_UPSUM": "1"}),
+            "w32 two-launch stem, unfolded head": bf16(32, {"HH_NO_STEM_FUSED": "1", "HH_NO_HEAD_FOLD": "1"}),
+            "w48": bf16(48, {}), "fp8 w48": _fp8_net(pkg, 48, 1, (B, H, W))[0]}
+    x = torch.from_numpy(pkg.synth.synth_images(B, H, W, 0)).to(DEV)
+    cfg, flops, nbytes, ms, kms, name = C.c_int(), C.c_double(), C.c_double(), C.c_float(), C.c_float(), C.c_char_p()
+    for what, net in nets.items():
+        pkg._lib.check(lib.hh_profile_enable(net._h, 1))
+        try:
+            net(x)
+            torch.cuda.synchronize()
+            total, n = 0.0, lib.hh_profile_count(net._h)
+            for i in range(n):
+                pkg._lib.check(lib.hh_profile_get(net._h, i, C.byref(cfg), C.byref(flops), C.byref(nbytes), C.byref(ms), C.byref(kms), C.byref(name)))
+                assert flops.value > 0 and nbytes.value > 0, (what, i, name.value)
+                total += flops.value
+        finally:
+            lib.hh_profile_enable(net._h, 0)
+        assert n > 0 and total == lib.hh_forward_flops(net._h, B, H, W), (what, n, total, lib.hh_forward_flops(net._h, B, H, W))
