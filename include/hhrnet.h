@@ -122,6 +122,15 @@ int hh_debug_bb_bench(int B, int H, int W, int iters, float *ms_per_launch, unsi
 /* the two fused 32-channel block kernels (tile form / producer-consumer form) on the same input: output difference and time */
 int hh_debug_bb_compare(int B, int H, int W, int iters, float *max_diff, float *ms_classic, float *ms_pc);
 
+/* Static check of the fused 32-channel block's tile geometry (basicblock_fused_pc.hip; no GPU needed, nothing is launched): makes
+ * the launcher's tile choice for a [B,H,W,32] map (tall: 0 = per-image tiles, 1 = the batch as one tall image where that needs fewer
+ * tiles, 2 = wherever the launcher allows it; num_cus: the grid limit) and walks every tile through the kernel's own row arithmetic.
+ * counts[0] = row segments (one output row of one column tile) no tile stores, counts[1] = segments stored more than once,
+ * counts[2] = input rows a stored row needs that its tile's patch reads as zero or from elsewhere, counts[3] = the same for the
+ * rows of the intermediate (conv1) tile.  All four are 0 for a correct launch.  Non-zero return: the launcher refuses the shape.
+ * (Additive diagnostic entry point: like hh_conv_config_double_buffered it leaves HH_ABI_VERSION at 3.)                       */
+int hh_debug_bb_cover(int B, int H, int W, int tall, int num_cus, int64_t counts[4]);
+
 /* Debug taps (parity tests): when enabled, hh_forward copies selected intermediate
  * activations; hh_tap_read converts one to fp32 NCHW on the host. Names follow the
  * reference module paths, e.g. "stages.2.blocks.3#1" = output 1 of backbone.stages[2].blocks[3]. */

@@ -67,6 +67,7 @@ def _sig(lib):
         "hh_debug_conv_bench": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_float), vp, i32, C.POINTER(C.c_float)]),
         "hh_debug_bb_bench": (i32, [i32, i32, i32, i32, C.POINTER(C.c_float), vp]),
         "hh_debug_bb_compare": (i32, [i32, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+        "hh_debug_bb_cover": (i32, [i32, i32, i32, i32, i32, pi64]),
         "hh_preprocess_u8": (i32, [vp, i32, i32, C.POINTER(C.c_double), vp, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), vp]),
         "hh_preprocess_u8_batch": (i32, [vp, vp, i32, vp, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), vp]),
         "hh_flip_images": (i32, [vp, vp, i32, i32, i32, i32, vp]),

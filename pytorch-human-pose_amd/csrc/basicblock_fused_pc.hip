@@ -29,6 +29,7 @@
 #include "kernels.h"
 
 #include <utility>
+#include <vector>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -93,7 +94,7 @@ __device__ __forceinline__ void lds_wait(u32x4 &v)
 #define BBPC_STORE_AUX 0  // cache policy bits of the output stores.  Experiment: 2 (nt) makes the block itself faster when its output is never
                           // read (128x128: 28.5 -> 25.4 us in tools/bb_compare.py) and the forward SLOWER (4.67 -> 4.72 ms): the next launch reads it
 #endif
-constexpr int TH = 14, TW = 32;          // output tile
+constexpr int TH = BBPC_TH, TW = BBPC_TW;  // output tile: 14 x 32 (kernels.h, beside the tile geometry the host walk shares)
 constexpr int MH = TH + 2, MW = TW + 2;  // conv1 output (= conv2 input) tile: 16 x 34
 constexpr int IH = TH + 4, IW = TW + 4;  // input patch: 18 x 36
 constexpr int PRS = 38;                  // patch row stride in pixels (see the header: conflict-free edge tile)
@@ -177,6 +178,7 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
     // ---- tiles of this workgroup, XCD-aware order as in basicblock_fused.hip
     const int tiles_per_img = p.tiles_x * p.tiles_y;
     const int nloc = (p.ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
+    // (restated as bbpc_band in kernels.h for the host walk: keep the two alike)
     auto band = [&](int i) { return ((p.ntiles & 7) == 0 && (gridDim.x & 7) == 0) ? (i & 7) * (p.ntiles >> 3) + (i >> 3) : i; };
     // Rows.  Plain layout: a tile belongs to one image (b, first output row oy0).  TALL layout (round 4, p.VH = H + 2): the batch is
     // one image of B * (H + 2) rows -- two rows of zeros between consecutive images, what both 3x3 convolutions see as padding -- and
@@ -184,19 +186,16 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
     // tiles of 14: a tenth of the plain layout's tiles were the 2-row remainders of the images).  A tile then touches at most two
     // images: b is the image of its first output row, oy0 that row's index inside it, and a row index y = oy0 + d that reaches VH
     // belongs to image b + 1, row y - VH (rowmap); rows H, H + 1 are the gap.  Plain layout: VH = 2^30, never reached.
-    struct Geom { int b, oy0, ox0; };
+    // A third image is out of a tile's reach only while H + 2 > TH: bbpc_plan picks the tall layout for no smaller map.
+    // geom and rowmap live in kernels.h (bbpc_geom / bbpc_rowmap): bbpc_cover below walks the same functions on the host.  band and
+    // pf_load's row test stay written out here -- called as shared functions they change the kernels' register allocation (one more
+    // spilled register and ~200 more instructions over the two kernels) -- and kernels.h restates them (bbpc_band, bbpc_patch_wrap / bbpc_patch_row) over the same constants.
+    using Geom = BBGeom;
     auto geom = [&](int k) {  // k-th tile of this workgroup
-        const int tb = band((int)blockIdx.x + k * (int)gridDim.x);
-        const int u = tb / tiles_per_img, tt = tb % tiles_per_img;
-        const int oy = (tt / p.tiles_x) * TH, bq = oy / p.VH;
-        return Geom{u + bq, oy - bq * p.VH, (tt % p.tiles_x) * TW};
+        return bbpc_geom(band((int)blockIdx.x + k * (int)gridDim.x), p.tiles_x, tiles_per_img, p.VH);
     };
     // row y = oy0 + d of the tile of image b -> flat row (image * H + row) of the tensor, or -1 outside every image
-    auto rowmap = [&](int b, int y) {
-        const bool wrap = y >= p.VH;
-        const int ya = wrap ? y - p.VH : y, bb = wrap ? b + 1 : b;
-        return (((unsigned)ya < (unsigned)p.H) & (bb < p.B)) ? bb * p.H + ya : -1;
-    };
+    auto rowmap = [&](int b, int y) { return bbpc_rowmap(b, y, p.B, p.H, p.VH); };
 
     // ---- patch prefetch: global -> registers (issued early in an iteration) -> LDS (late in the same iteration).
     // Round i of 6 moves patch rows 3i..3i+2 (432 16-byte units: threads 0..431; unit = (row 3i + tid / 144, pixel (tid % 144) >> 2,
@@ -225,6 +224,7 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
     auto pf_load = [&](auto ic) {
         constexpr int i = decltype(ic)::value;
         const int yy = pf_y + 3 * i;
+        // (the row test is restated as bbpc_patch_wrap / bbpc_patch_row in kernels.h for the host walk: keep the two alike)
         const bool wrap = yy >= p.VH;  // (tall layout) the row belongs to the next image
         const bool ok = pf_xok & ((unsigned)(wrap ? yy - p.VH : yy) < (unsigned)p.H) & (!wrap | pf_next);
         const unsigned voff = ok ? pf_vbase + (unsigned)(i * pf_rowstep) - (wrap ? (unsigned)pf_gapstep : 0u) : OOB;  // outside the image: zero = conv1's padding
@@ -574,13 +574,18 @@ bool bbpc_final_supported(const BBParams &p)
     return bbpc_supported(p) && p.fin_K >= 1 && p.fin_K <= 32 && p.W % 4 == 0 && (size_t)p.B * p.fin_K * p.H * p.W * 4 < 0x7fffffffull;
 }
 
-hipError_t bbpc_launch(BBParams p, int num_cus, hipStream_t s)
+// The tile choice of a launch: fills tiles_x, tiles_y, ntiles, VH; returns the grid.
+static int bbpc_plan(BBParams &p, int num_cus)
 {
     p.tiles_x = (p.W + TW - 1) / TW;
     p.tiles_y = (p.H + TH - 1) / TH;
     p.ntiles = p.B * p.tiles_x * p.tiles_y;
     p.VH = 1 << 30;
-    if (p.tall != 0) {
+    // The tall layout needs H + 2 > TH, HH_BB_TALL=always (tall == 2) included: geom / rowmap / patch_row handle ONE image border
+    // per tile.  A tile's rows y = oy0 - 2 .. oy0 + TH + 1 with oy0 < VH = H + 2 then stay below 2 VH + 2, the rows of image b + 2
+    // that no stored row needs.  On a smaller map (the 8-row maps of a 32-pixel-high input were the case) a 14-row tile reached a
+    // third image, whose rows were never stored and whose halo rows read as zero.
+    if (p.tall != 0 && p.H + 2 > TH) {
         // the batch as one tall image (see the kernel): fewer tiles whenever H is not a multiple of the tile height.  The tile rows are
         // rounded up until the tile count is a multiple of 8 (the XCD-contiguous tile order needs that; the extra tiles lie behind
         // the last image and move nothing)
@@ -588,7 +593,57 @@ hipError_t bbpc_launch(BBParams p, int num_cus, hipStream_t s)
         while ((ty * p.tiles_x) & 7) ++ty;
         if (ty * p.tiles_x < p.ntiles || p.tall > 1) { p.tiles_y = ty; p.ntiles = ty * p.tiles_x; p.VH = p.H + 2; }
     }
-    const int grid = p.ntiles < num_cus ? p.ntiles : num_cus;
+    return p.ntiles < num_cus ? p.ntiles : num_cus;
+}
+
+// Host walk of every tile of the launch bbpc_plan would make, through the functions the kernel computes its rows with.  Counted
+// per (flat output row, column tile) = "row segment":
+//   counts[0] segments of the B * H output rows that no tile stores, counts[1] segments stored more than once,
+//   counts[2] input rows a stored output row needs (rows ya - 2 .. ya + 2 of ITS image, clipped to the image) that the tile's
+//             patch does not hold -- read as zero, or as another row -- plus patch rows that must be padding and are not,
+//   counts[3] the same for the mid rows (conv1 output rows ya - 1 .. ya + 1) the tile zeroes or keeps in error.
+// Launches nothing.  false: the launcher would refuse the shape.
+bool bbpc_cover(int B, int H, int W, int tall, int num_cus, long long counts[4])
+{
+    counts[0] = counts[1] = counts[2] = counts[3] = 0;
+    if (B <= 0 || H <= 0 || W <= 0 || num_cus <= 0 || tall < 0 || tall > 2) return false;
+    BBParams p{};
+    p.B = B; p.H = H; p.W = W; p.in_cs = p.out_cs = 32; p.tall = tall;
+    if (!bbpc_supported(p)) return false;
+    const int grid = bbpc_plan(p, num_cus);
+    const int tiles_per_img = p.tiles_x * p.tiles_y;
+    std::vector<int> stored((size_t)B * H * p.tiles_x, 0);
+    for (int wg = 0; wg < grid; ++wg) {
+        const int nloc = (p.ntiles - wg + grid - 1) / grid;
+        for (int k = 0; k < nloc; ++k) {
+            const BBGeom g = bbpc_geom(bbpc_band(wg + k * grid, p.ntiles, grid), p.tiles_x, tiles_per_img, p.VH);
+            const int tx = g.ox0 / TW;
+            if (g.ox0 >= W || tx >= p.tiles_x) return false;  // (cannot happen: the column tile comes from tt % tiles_x)
+            const bool next = g.b + 1 < p.B;  // pf_setup's pf_next
+            for (int d = 0; d < TH; ++d) {
+                const int fr = bbpc_rowmap(g.b, g.oy0 + d, p.B, p.H, p.VH);
+                if (fr < 0) continue;
+                ++stored[(size_t)fr * p.tiles_x + tx];
+                const int bb = fr / H, ya = fr % H;
+                for (int dy = -2; dy <= 2; ++dy) {  // patch row d + 2 + dy = row oy0 + d + dy of the tile
+                    const int yy = g.oy0 + d + dy, want = (unsigned)(ya + dy) < (unsigned)H ? bb * H + ya + dy : -1;
+                    const bool wrap = bbpc_patch_wrap(yy, p.VH);
+                    const bool ok = bbpc_patch_row(yy, wrap, next, p.H, p.VH);
+                    // pf_load's address: ((b H + oy0 - 2 + row) W ...) - (wrap ? (VH - H) W ... : 0), in rows
+                    const int have = ok ? g.b * H + yy - (wrap ? p.VH - H : 0) : -1;
+                    if (have != want) ++counts[2];
+                    if (dy >= -1 && dy <= 1 && bbpc_rowmap(g.b, yy, p.B, p.H, p.VH) != want) ++counts[3];
+                }
+            }
+        }
+    }
+    for (int v : stored) { counts[0] += v == 0; counts[1] += v > 1; }
+    return true;
+}
+
+hipError_t bbpc_launch(BBParams p, int num_cus, hipStream_t s)
+{
+    const int grid = bbpc_plan(p, num_cus);
     if (p.fin_out) {
         if (!bbpc_final_supported(p)) return hipErrorInvalidValue;
         HH_LAUNCH(bbpc_final_kernel, dim3(grid), dim3(NTHR), LDS_BYTES_FIN, s, p);

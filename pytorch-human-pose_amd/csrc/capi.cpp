@@ -694,6 +694,16 @@ extern "C" int hh_debug_conv_bench(int cfg, int B, int Hin, int Win, int cin, in
     return 0;
 }
 
+// Host-only walk of the producer / consumer block's tiles (bbpc_cover, basicblock_fused_pc.hip): see hhrnet.h
+extern "C" int hh_debug_bb_cover(int B, int H, int W, int tall, int num_cus, int64_t counts[4])
+{
+    long long c[4];
+    if (!counts) { hh_set_error("hh_debug_bb_cover: counts is NULL"); return 1; }
+    if (!bbpc_cover(B, H, W, tall, num_cus, c)) { hh_set_error("hh_debug_bb_cover: the launcher does not take this shape"); return 1; }
+    for (int i = 0; i < 4; ++i) counts[i] = c[i];
+    return 0;
+}
+
 // A/B of the two fused 32-channel blocks on the same random input (H, W need not be tile multiples): the largest absolute
 // difference of the outputs (both round to bf16, the accumulation orders differ: expect a few bf16 ulps) and the time per launch.
 extern "C" int hh_debug_bb_compare(int B, int H, int W, int iters, float *max_diff, float *ms_classic, float *ms_pc)

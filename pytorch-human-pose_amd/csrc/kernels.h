@@ -162,6 +162,39 @@ struct BBParams {
     unsigned long long *stamps;      // diagnostic build (-DHH_STAMP) only
     unsigned long long *clk;         // optional {min start, max end} of the launch in wall_clock64() ticks
 };
+// Tile geometry of the producer / consumer form (basicblock_fused_pc.hip) for its kernel and for bbpc_cover, the host walk behind
+// hh_debug_bb_cover.  bbpc_geom and bbpc_rowmap are the kernel's own code.  bbpc_band and bbpc_patch_wrap / bbpc_patch_row RESTATE
+// two expressions the kernel keeps written out (its `band` lambda and the row test in pf_load: as calls they changed its register
+// allocation): whoever edits one side edits the other.
+constexpr int BBPC_TH = 14, BBPC_TW = 32;  // output tile
+struct BBGeom { int b, oy0, ox0; };        // image of the tile's first output row, that row's index inside it, first column
+// XCD-aware tile order: position i of the launch's tile sequence -> tile  (= `band` in bbpc_body)
+__host__ __device__ inline int bbpc_band(int i, int ntiles, unsigned grid)
+{
+    return ((ntiles & 7) == 0 && (grid & 7) == 0) ? (i & 7) * (ntiles >> 3) + (i >> 3) : i;
+}
+__host__ __device__ __forceinline__ BBGeom bbpc_geom(int tb, int tiles_x, int tiles_per_img, int VH)
+{
+    const int u = tb / tiles_per_img, tt = tb % tiles_per_img;
+    const int oy = (tt / tiles_x) * BBPC_TH, bq = oy / VH;
+    return BBGeom{u + bq, oy - bq * VH, (tt % tiles_x) * BBPC_TW};
+}
+// row y = oy0 + d of the tile of image b -> flat row (image * H + row) of the tensor, or -1 outside every image
+__host__ __device__ __forceinline__ int bbpc_rowmap(int b, int y, int B, int H, int VH)
+{
+    const bool wrap = y >= VH;
+    const int ya = wrap ? y - VH : y, bb = wrap ? b + 1 : b;
+    return (((unsigned)ya < (unsigned)H) & (bb < B)) ? bb * H + ya : -1;
+}
+// patch row yy (counted from the first row of image b): does it belong to image b + 1 (tall layout), and is it a row of an image at
+// all (`next`: image b + 1 exists)?  Outside every image the patch holds zeros, conv1's padding.  (= `wrap`, `ok` in pf_load)
+__host__ __device__ inline bool bbpc_patch_wrap(int yy, int VH) { return yy >= VH; }
+__host__ __device__ inline bool bbpc_patch_row(int yy, bool wrap, bool next, int H, int VH)
+{
+    return ((unsigned)(wrap ? yy - VH : yy) < (unsigned)H) & (!wrap | next);
+}
+bool bbpc_cover(int B, int H, int W, int tall, int num_cus, long long counts[4]);
+
 #define HH_PROF_SLOTS 1024   // launches per forward the device-clock probe can record
 #define HH_CFG_BB_FUSED 100  // pseudo instantiation index used by the profiler
 hipError_t bb_fused_init();
