@@ -18,54 +18,9 @@
 //   * the residual is two extra MFMAs per column tile with an identity A fragment (exact: x * 1.0 in fp32)
 //     instead of 16 LDS reads + 16 converts + 16 adds per lane
 //   * epilogues pair the two half-waves with v_permlane32_swap so every lane writes 16 contiguous bytes.
-#include "kernels.h"
-
-#include <utility>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "mfma_dev.h"
 
 namespace {
-typedef short i16x2 __attribute__((ext_vector_type(2)));
-// ReLU after the rounding, on the packed pair: as signed 16-bit integers every negative bf16 (sign bit set, -0 included)
-// is below zero and every non-negative one keeps its bits, so one v_pk_max_i16 replaces two canonicalise + two v_max_f32.
-__device__ __forceinline__ unsigned pack_relu_bf16x2(float a, float b)
-{
-    f32x2 f = {a, b};
-    const i16x2 v = __builtin_bit_cast(i16x2, __builtin_convertvector(f, bf16x2));
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(v, i16x2{0, 0}));
-}
-
-template <typename F, int... I>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>)
-{
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F &&f)
-{
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-// 32 couts of one pixel: lanes (r,0) hold couts 8g..8g+3, lanes (r,1) couts 8g+4..8g+7 in acc[4g..4g+3].
-// Returns for m = 0,1 the 16 bytes (bf16, ReLU applied) of couts 16m+8h .. 16m+8h+7 of this lane's pixel.
-__device__ __forceinline__ void pack_rows16(const f32x16 &acc, u32x4 out[2])
-{
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        unsigned x0 = pack_relu_bf16x2(acc[8 * m + 0], acc[8 * m + 1]), x1 = pack_relu_bf16x2(acc[8 * m + 2], acc[8 * m + 3]);
-        unsigned y0 = pack_relu_bf16x2(acc[8 * m + 4], acc[8 * m + 5]), y1 = pack_relu_bf16x2(acc[8 * m + 6], acc[8 * m + 7]);
-        // lanes 0-31: X = couts 16m..+3, Y = 16m+8..+11; lanes 32-63: X = 16m+4..+7, Y = 16m+12..+15.
-        // swap X[32..63] <-> Y[0..31]: lanes 0-31 end with (X,Y) = couts 16m..16m+7, lanes 32-63 with 16m+8..16m+15
-        auto s0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
-        auto s1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
-        out[m] = u32x4{s0[0], s1[0], s0[1], s1[1]};
-    }
-}
-
 constexpr int TH = 16, TW = 32;          // output tile
 constexpr int MH = TH + 2, MW = TW + 2;  // conv1 output (= conv2 input) tile
 constexpr int IH = TH + 4, IW = TW + 4;  // input patch
@@ -107,16 +62,8 @@ __global__ __launch_bounds__(NTHR, 1) void bb_fused_kernel(const BBParams p)
     const int wave = tid >> 6, lane = tid & 63;
     const int r = lane & 31, h = lane >> 5;
 
-    // identity A fragments (rows = couts, k = cin): frag kk has A[r][k] = 1 where 16*kk + k == r
-    u32x4 ident[2];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-        const int j = r - 16 * kk - 8 * h;  // element index inside this lane's 8-wide k slice
-        const unsigned one = (j & 1) ? 0x3f800000u : 0x00003f80u;  // bf16 1.0 in the high / low half of a dword
-        const bool on = j >= 0 && j < 8;
-        ident[kk] = u32x4{on && (j >> 1) == 0 ? one : 0u, on && (j >> 1) == 1 ? one : 0u, on && (j >> 1) == 2 ? one : 0u,
-                          on && (j >> 1) == 3 ? one : 0u};
-    }
+    u32x4 ident[2];  // the residual enters through the matrix pipe
+    ident_frags(r, h, ident);
 
     // ---- tile-invariant per-thread geometry
     int pl_off[NPL], pl_yx[NPL];  // prefetch unit i: element offset from the tile's patch origin, (py << 8) | px
@@ -175,10 +122,6 @@ __global__ __launch_bounds__(NTHR, 1) void bb_fused_kernel(const BBParams p)
         const int u = tid + NTHR * i;  // units >= P_UNITS land in the pad behind the patch
         *reinterpret_cast<u32x4 *>(lds_p + ((u >> 6) * 16 + (u & 15)) * PS + ((u >> 4) & 3) * 16) = (pf_mask >> i) & 1u ? preg[i] : u32x4{0u, 0u, 0u, 0u};
     };
-    // Workgroup barrier that waits for LDS traffic only: __syncthreads() also drains vmcnt, i.e. it would stall every
-    // wave until the next tile's prefetch loads (issued during conv1, consumed during conv2) and the previous tile's
-    // output stores have completed.
-    auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
     int t = blockIdx.x;
     pf_setup(t);
@@ -219,6 +162,7 @@ __global__ __launch_bounds__(NTHR, 1) void bb_fused_kernel(const BBParams p)
         auto conv1_phase = [&](auto nqc) {
             constexpr int NQ = decltype(nqc)::value;
             f32x16 acc[NQ];
+            // (this init loop, here and for acc2 below, stays written out: as a shared function it changed the register allocation)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const float4 bv = *reinterpret_cast<const float4 *>(lds_b + 8 * g + 4 * h);
@@ -359,30 +303,9 @@ __global__ __launch_bounds__(NTHR, 1) void bb_fused_kernel(const BBParams p)
 #endif
 }
 
-static bf16_raw *g_trash_dev[64] = {};  // per device: 64 B every lane may scribble on (stores of lanes outside the image)
-
-hipError_t bb_fused_init()
-{
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (!g_trash_dev[dev & 63]) {
-        e = hipMalloc((void **)&g_trash_dev[dev & 63], 256);
-        if (e != hipSuccess) return e;
-    }
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(bb_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)bb_fused_lds_bytes());
-}
+hipError_t bb_fused_init() { return bb_tile_init(bb_fused_kernel, bb_fused_lds_bytes()); }
 
 hipError_t bb_fused_launch(BBParams p, int num_cus, hipStream_t s)
 {
-    p.tiles_x = (p.W + TW - 1) / TW;
-    p.tiles_y = (p.H + TH - 1) / TH;
-    p.ntiles = p.B * p.tiles_x * p.tiles_y;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || !g_trash_dev[dev & 63]) return hipErrorNotInitialized;
-    p.trash = g_trash_dev[dev & 63];
-    const int grid = p.ntiles < num_cus ? p.ntiles : num_cus;
-    HH_LAUNCH(bb_fused_kernel, dim3(grid), dim3(NTHR), bb_fused_lds_bytes(), s, p);
-    return hipGetLastError();
+    return bb_tile_launch(bb_fused_kernel, TH, TW, NTHR, bb_fused_lds_bytes(), p, num_cus, s);
 }

@@ -15,47 +15,9 @@
 //     conv2: output rows 2*part, 2*part+1                         -> 2 accumulators; a mid-row fragment is read once per
 //            (kx, k-step) and used for every output row it feeds (as in basicblock_fused.hip)
 //   MFMA roles as in conv_mfma.hip: A = weights (32 couts x 16 cin), B = pixels.
-#include "kernels.h"
-
-#include <utility>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "mfma_dev.h"
 
 namespace {
-typedef short i16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_relu_bf16x2(float a, float b)
-{
-    f32x2 f = {a, b};
-    const i16x2 v = __builtin_bit_cast(i16x2, __builtin_convertvector(f, bf16x2));
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(v, i16x2{0, 0}));
-}
-template <typename F, int... I>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>)
-{
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F &&f)
-{
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-// 32 couts of one pixel (MFMA C layout) -> for m = 0,1 the 16 bytes (bf16, ReLU applied) of couts 16m+8h .. +7
-__device__ __forceinline__ void pack_rows16(const f32x16 &acc, u32x4 out[2])
-{
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        unsigned x0 = pack_relu_bf16x2(acc[8 * m + 0], acc[8 * m + 1]), x1 = pack_relu_bf16x2(acc[8 * m + 2], acc[8 * m + 3]);
-        unsigned y0 = pack_relu_bf16x2(acc[8 * m + 4], acc[8 * m + 5]), y1 = pack_relu_bf16x2(acc[8 * m + 6], acc[8 * m + 7]);
-        auto s0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
-        auto s1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
-        out[m] = u32x4{s0[0], s1[0], s0[1], s1[1]};
-    }
-}
-
 constexpr int C = 64;
 constexpr int TH = 8, TW = 32;
 constexpr int MH = TH + 2, MW = TW + 2;
@@ -93,14 +55,7 @@ __global__ __launch_bounds__(NTHR, 1) void bb64_fused_kernel(const BBParams p)
 
     // identity A fragments (rows = couts of this cout tile, k = cin of the 32-channel chunk ct): residual via the matrix pipe
     u32x4 ident[2];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-        const int j = r - 16 * kk - 8 * h;
-        const unsigned one = (j & 1) ? 0x3f800000u : 0x00003f80u;
-        const bool on = j >= 0 && j < 8;
-        ident[kk] = u32x4{on && (j >> 1) == 0 ? one : 0u, on && (j >> 1) == 1 ? one : 0u, on && (j >> 1) == 2 ? one : 0u,
-                          on && (j >> 1) == 3 ? one : 0u};
-    }
+    ident_frags(r, h, ident);
 
     // ---- tile-invariant geometry
     int pl_yx[NPL];  // prefetch unit i: (py << 8) | px inside the patch (py = 255: an idle unit of the last round)
@@ -164,7 +119,6 @@ __global__ __launch_bounds__(NTHR, 1) void bb64_fused_kernel(const BBParams p)
             if (u < W_UNITS) reinterpret_cast<u32x4 *>(lds_w)[u] = wreg[i];
         });
     };
-    auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
     int t = blockIdx.x;
     pf_setup(t);
@@ -201,6 +155,7 @@ __global__ __launch_bounds__(NTHR, 1) void bb64_fused_kernel(const BBParams p)
         auto conv1_phase = [&](auto nqc) {
             constexpr int NQ = decltype(nqc)::value;
             f32x16 acc[NQ];
+            // (this init loop, here and for acc2 below, stays written out: as a shared function it changed the register allocation)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const float4 bv = *reinterpret_cast<const float4 *>(lds_b + ct * 32 + 8 * g + 4 * h);
@@ -351,30 +306,9 @@ __global__ __launch_bounds__(NTHR, 1) void bb64_fused_kernel(const BBParams p)
 #endif
 }
 
-static bf16_raw *g_trash64[64] = {};
-
-hipError_t bb64_fused_init()
-{
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (!g_trash64[dev & 63]) {
-        e = hipMalloc((void **)&g_trash64[dev & 63], 256);
-        if (e != hipSuccess) return e;
-    }
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(bb64_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)bb64_lds_bytes());
-}
+hipError_t bb64_fused_init() { return bb_tile_init(bb64_fused_kernel, bb64_lds_bytes()); }
 
 hipError_t bb64_fused_launch(BBParams p, int num_cus, hipStream_t s)
 {
-    p.tiles_x = (p.W + TW - 1) / TW;
-    p.tiles_y = (p.H + TH - 1) / TH;
-    p.ntiles = p.B * p.tiles_x * p.tiles_y;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || !g_trash64[dev & 63]) return hipErrorNotInitialized;
-    p.trash = g_trash64[dev & 63];
-    const int grid = p.ntiles < num_cus ? p.ntiles : num_cus;
-    HH_LAUNCH(bb64_fused_kernel, dim3(grid), dim3(NTHR), bb64_lds_bytes(), s, p);
-    return hipGetLastError();
+    return bb_tile_launch(bb64_fused_kernel, TH, TW, NTHR, bb64_lds_bytes(), p, num_cus, s);
 }

@@ -10,48 +10,17 @@
 // out = e4m3(relu(acc2 * mult2 + shift2 + q_x * s_in) / s_out), mult1 = s_in * s_w1[co], mult2 = s_mid * s_w2[co].
 // Wave roles as basicblock_fused_c64.hip: cout tile = wave & 1 (couts padded to 64), conv1 column tiles / conv2 rows by wave >> 1.
 // K is enumerated in 16-byte pieces (tap, 16-channel group) exactly as conv_fp8.hip packs the weights.
-#include "kernels.h"
-
-#include <utility>
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+#include "mfma_dev.h"
 
 namespace {
-template <typename F, int... I>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>)
-{
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F &&f)
-{
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-__device__ __forceinline__ unsigned pack_fp8x4(float a, float b, float c, float d)
-{
-    a = fminf(a, 448.f); b = fminf(b, 448.f); c = fminf(c, 448.f); d = fminf(d, 448.f);  // inputs are ReLU outputs (>= 0)
-    int w = 0;
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-    return (unsigned)w;
-}
-__device__ __forceinline__ i32x8 frag(const u32x4 &lo, const u32x4 &hi)
-{
-    return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-}
 // 16 fp32 (MFMA C layout: couts 8g + 4h + i) -> scaled e4m3, exchanged so that the lane holds couts 16h .. 16h+15 of its pixel
 __device__ __forceinline__ u32x4 pack_tile_fp8(const float y[16], float inv)
 {
     unsigned x[2], z[2];
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
-        x[m] = pack_fp8x4(y[8 * m + 0] * inv, y[8 * m + 1] * inv, y[8 * m + 2] * inv, y[8 * m + 3] * inv);
-        z[m] = pack_fp8x4(y[8 * m + 4] * inv, y[8 * m + 5] * inv, y[8 * m + 6] * inv, y[8 * m + 7] * inv);
+        x[m] = pack_fp8x4_nonneg(y[8 * m + 0] * inv, y[8 * m + 1] * inv, y[8 * m + 2] * inv, y[8 * m + 3] * inv);
+        z[m] = pack_fp8x4_nonneg(y[8 * m + 4] * inv, y[8 * m + 5] * inv, y[8 * m + 6] * inv, y[8 * m + 7] * inv);
     }
     auto s0 = __builtin_amdgcn_permlane32_swap(x[0], z[0], false, false);
     auto s1 = __builtin_amdgcn_permlane32_swap(x[1], z[1], false, false);
@@ -154,7 +123,6 @@ __global__ __launch_bounds__(NTHR, 1) void bb_fp8_kernel(const Fp8BBParams p)
         const int u = tid + NTHR * i;
         *reinterpret_cast<u32x4 *>(lds_p + (u / G) * PS + (u % G) * 16) = (pf_mask >> i) & 1u ? preg[i] : u32x4{0u, 0u, 0u, 0u};
     };
-    auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
     int t = blockIdx.x;
     pf_setup(t);

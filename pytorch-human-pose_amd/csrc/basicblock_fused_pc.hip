@@ -10,7 +10,7 @@
 //     the two waves of a SIMD (w and w+4) run in antiphase inside it: the producer issues its MFMAs first and packs / writes
 //     the mid rows second; the consumer first packs / stores the tile of the iteration before (its accumulators survive the
 //     barrier) and then issues its MFMAs;
-//   * LDS fragment reads are asm statements with hand-counted waits (lds_read_async / lds_wait): left to the compiler the
+//   * LDS fragment reads are asm statements with hand-counted waits (lds_read_async / lds_wait, mfma_dev.h): left to the compiler the
 //     software pipeline collapses (it renames the rotating fragment registers and waits right behind the reads).
 //
 // Tile: 14x32 outputs, 16x34 mid pixels, 18x36 input patch; patch and mid tile are double buffered (157 KB of LDS), pixels
@@ -26,70 +26,11 @@
 // -DBBPC_NORES) the same instruction stream runs the 256x256 case in 65 us at an in-kernel clock of 2.40 GHz; with its 268 MB
 // of HBM traffic it takes 8 % more cycles and the chip holds only 1.9-2.0 GHz (d s_memtime / d s_memrealtime, -DHH_STAMP
 // build) -- the block is bound by what the chip can power: HBM streaming at ~3 TB/s beside ~0.85 PFLOP/s of MFMA.
-#include "kernels.h"
+#include "mfma_dev.h"
 
-#include <utility>
 #include <vector>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
 namespace {
-typedef short i16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_relu_bf16x2(float a, float b)
-{
-    f32x2 f = {a, b};
-    const i16x2 v = __builtin_bit_cast(i16x2, __builtin_convertvector(f, bf16x2));
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(v, i16x2{0, 0}));
-}
-
-template <typename F, int... I>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>)
-{
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F &&f)
-{
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-// 32 couts of one pixel: lanes (r,0) hold couts 8g..8g+3, lanes (r,1) couts 8g+4..8g+7 in acc[4g..4g+3].
-// Returns for m = 0,1 the 16 bytes (bf16, ReLU applied) of couts 16m+8h .. 16m+8h+7 of this lane's pixel.
-__device__ __forceinline__ void pack_rows16(const f32x16 &acc, u32x4 out[2])
-{
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        unsigned x0 = pack_relu_bf16x2(acc[8 * m + 0], acc[8 * m + 1]), x1 = pack_relu_bf16x2(acc[8 * m + 2], acc[8 * m + 3]);
-        unsigned y0 = pack_relu_bf16x2(acc[8 * m + 4], acc[8 * m + 5]), y1 = pack_relu_bf16x2(acc[8 * m + 6], acc[8 * m + 7]);
-        auto s0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
-        auto s1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
-        out[m] = u32x4{s0[0], s1[0], s0[1], s1[1]};
-    }
-}
-
-// LDS fragment reads whose place in the instruction stream and whose wait are fixed by hand.  Left to the compiler, the
-// reads of the software pipeline below end up right in front of their MFMAs (it renames the rotating fragment registers and
-// waits lgkmcnt(0)), which exposes a full LDS round trip per step.  The read is an asm statement (volatile: the statements keep
-// their order); its result may only be used through lds_wait<N>(), which waits until at most N younger LDS operations are
-// outstanding (LDS operations complete in order; compiler-issued ones in between only make the wait conservative).
-template <int OFF>
-__device__ __forceinline__ u32x4 lds_read_async(int addr)
-{
-    u32x4 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
-}
-template <int N>
-__device__ __forceinline__ void lds_wait(u32x4 &v)
-{
-    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(N));
-}
-
 #ifndef BBPC_STORE_AUX
 #define BBPC_STORE_AUX 0  // cache policy bits of the output stores.  Experiment: 2 (nt) makes the block itself faster when its output is never
                           // read (128x128: 28.5 -> 25.4 us in tools/bb_compare.py) and the forward SLOWER (4.67 -> 4.72 ms): the next launch reads it
@@ -239,7 +180,6 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
         if (pu_act)
             *reinterpret_cast<u32x4 *>(smem + patch_off + pu_lbase + 3 * i * PRS * 64 + (((pu_key ^ ((pu_row + 3 * i) >> 1)) & 3) << 4)) = preg[i];
     };
-    auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
     pf_setup(0);
     static_for<NPL>(pf_load);

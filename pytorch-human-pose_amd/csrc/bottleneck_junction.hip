@@ -7,37 +7,9 @@
 // Why: stage 0 moves 256-channel tensors at 128x128 and is HBM bound; unfused, y is written by conv3 and read again by
 // the next conv1 (268 MB at B=32, three times), and unit 0 round-trips the downsample result (2 x 268 MB).
 // Pixel fragments of t2 / x are loaded from HBM straight into the MFMA B layout (16 B per lane), weights sit in LDS.
-#include "kernels.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short i16x2 __attribute__((ext_vector_type(2)));
+#include "mfma_dev.h"
 
 namespace {
-__device__ __forceinline__ unsigned pack_relu_bf16x2(float a, float b)
-{
-    f32x2 f = {a, b};
-    const i16x2 v = __builtin_bit_cast(i16x2, __builtin_convertvector(f, bf16x2));
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(v, i16x2{0, 0}));  // ReLU on the packed pair
-}
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-
-// acc (32 couts of this lane's pixel, MFMA C layout) -> for m = 0,1 the 16 bytes of couts 16m+8h..+7 (ReLU, bf16)
-__device__ __forceinline__ void pack_rows16(const f32x16 &acc, u32x4 out[2])
-{
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        unsigned x0 = pack_relu_bf16x2(acc[8 * m + 0], acc[8 * m + 1]), x1 = pack_relu_bf16x2(acc[8 * m + 2], acc[8 * m + 3]);
-        unsigned y0 = pack_relu_bf16x2(acc[8 * m + 4], acc[8 * m + 5]), y1 = pack_relu_bf16x2(acc[8 * m + 6], acc[8 * m + 7]);
-        auto s0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
-        auto s1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
-        out[m] = u32x4{s0[0], s1[0], s0[1], s1[1]};
-    }
-}
 // inverse for the residual: 16 bytes (couts 16m+8h..+7) per m -> added onto the accumulator in C layout
 __device__ __forceinline__ void add_rows16(f32x16 &acc, const u32x4 v[2])
 {

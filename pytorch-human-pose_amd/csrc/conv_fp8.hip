@@ -12,43 +12,7 @@
 // group) so that channel counts that are multiples of 16 but not of 64 (48, 96: HigherHRNet-W48) waste at most 3 pieces
 // per chunk: k-step s covers pieces 4s..4s+3, lane half h takes pieces 4s+2h and 4s+2h+1 (two ds_read_b128 each for A and
 // B).  The weight image is packed in exactly that order, so A and B always meet on the same k.
-#include "kernels.h"
-
-#include <utility>
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-namespace {
-template <typename F, int... I>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>)
-{
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F &&f)
-{
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-
-// four fp32 -> four e4m3 bytes (round to nearest even, clamped to the finite range +-448)
-__device__ __forceinline__ unsigned pack_fp8x4(float a, float b, float c, float d)
-{
-    a = __builtin_amdgcn_fmed3f(a, -448.f, 448.f); b = __builtin_amdgcn_fmed3f(b, -448.f, 448.f);
-    c = __builtin_amdgcn_fmed3f(c, -448.f, 448.f); d = __builtin_amdgcn_fmed3f(d, -448.f, 448.f);
-    int w = 0;
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-    return (unsigned)w;
-}
-__device__ __forceinline__ i32x8 frag(const u32x4 &lo, const u32x4 &hi)
-{
-    return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-}
-}  // namespace
+#include "mfma_dev.h"
 
 template <int KS, int S, int KC, int NT, int PT, int TW>
 __global__ __launch_bounds__(256, 2) void conv_fp8_kernel(const Fp8ConvParams p)
@@ -313,8 +277,8 @@ __global__ __launch_bounds__(256, 2) void conv_fp8_kernel(const Fp8ConvParams p)
 #pragma unroll
                 for (int m = 0; m < 2; ++m) {
                     const float s = p.out_inv_scale;
-                    x[m] = pack_fp8x4(y[8 * m + 0] * s, y[8 * m + 1] * s, y[8 * m + 2] * s, y[8 * m + 3] * s);
-                    z[m] = pack_fp8x4(y[8 * m + 4] * s, y[8 * m + 5] * s, y[8 * m + 6] * s, y[8 * m + 7] * s);
+                    x[m] = pack_fp8x4_sat(y[8 * m + 0] * s, y[8 * m + 1] * s, y[8 * m + 2] * s, y[8 * m + 3] * s);
+                    z[m] = pack_fp8x4_sat(y[8 * m + 4] * s, y[8 * m + 5] * s, y[8 * m + 6] * s, y[8 * m + 7] * s);
                 }
                 auto s0 = __builtin_amdgcn_permlane32_swap(x[0], z[0], false, false);  // half 0: couts 0..7, half 1: 8..15
                 auto s1 = __builtin_amdgcn_permlane32_swap(x[1], z[1], false, false);  // half 0: 16..23,   half 1: 24..31

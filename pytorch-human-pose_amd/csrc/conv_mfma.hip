@@ -18,41 +18,7 @@
 //                    32 lanes of a ds_read_b128 B-fragment (consecutive pixels) hit distinct
 //                    bank groups; weights are [tap][KC/8][COUT_T][8] so an A-fragment read is
 //                    512 contiguous bytes per half-wave.
-#include "kernels.h"
-
-#include <utility>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // native vector: HIP's uint4 struct kept staging arrays in scratch
-
-typedef short i16x2 __attribute__((ext_vector_type(2)));
-// Round a pair to bf16 and clamp it from below as signed 16-bit integers: floor = {0,0} is ReLU (every negative bf16,
-// -0 included, is a negative int16; non-negative ones keep their bits), floor = {-32768,-32768} is the identity.
-// One v_pk_max_i16 per pair instead of two canonicalise + two v_max_f32 on the fp32 values.
-__device__ __forceinline__ unsigned pack_bf16x2(float a, float b, i16x2 floor)
-{
-    f32x2 f = {a, b};
-    const i16x2 v = __builtin_bit_cast(i16x2, __builtin_convertvector(f, bf16x2));
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(v, floor));
-}
-__device__ __forceinline__ float bf16_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-
-// Compile-time loop: indices are constant expressions in the front end, so per-thread staging arrays are
-// promoted to registers (a "#pragma unroll" loop left them in scratch: guide rule 20).
-template <typename F, int... I>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>)
-{
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F &&f)
-{
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
+#include "mfma_dev.h"
 
 #ifdef HH_CONV_DEBUG  // phase stamps of every workgroup (wave 0), read by tools/probes/conv_probe.hip only
 __device__ long long g_conv_dbg[8192 * 8];
@@ -390,8 +356,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
     };
     CONV_STAMP(1);
     if constexpr (DB) {
-        // LDS-only barrier: __syncthreads() would also drain vmcnt, i.e. the loads of the chunk after next
-        auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+        // (the barriers below are LDS-only: __syncthreads() would also drain vmcnt, i.e. the loads of the chunk after next)
         // (the host only picks this instantiation for layers of >= 2 chunks: no run-time case split around the loads below, which
         // would cost a vmcnt(0) at the join -- the first MFMAs would wait for chunk 1)
         static_for<NL>([&](auto jc) { write_unit(jc, 0); });

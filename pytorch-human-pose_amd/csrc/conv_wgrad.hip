@@ -8,24 +8,14 @@
 // One workgroup = 4 waves = the 2x2 (co, ci) tiles of 32 of one 64x64 channel block; every wave keeps KS*KS accumulators
 // (one per tap) and the workgroup walks pixel tiles persistently; partial sums go to a workspace that a second kernel
 // reduces in a fixed order (deterministic, no atomics).
-#include "kernels.h"
+#include "mfma_dev.h"
 
-#include <utility>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short i16x4 __attribute__((ext_vector_type(4)));
 typedef short i16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 constexpr int RS = 144;  // LDS bytes per staged pixel: 64 channels + 16 pad
 constexpr int TH = 4;
-
-template <typename F, int... I>
-__device__ __forceinline__ void sfor_impl(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void sfor(F &&f) { sfor_impl(f, std::make_integer_sequence<int, N>{}); }
 
 __device__ __forceinline__ i16x4 tr_read(const char *lds, int byte_off)
 {
@@ -88,7 +78,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradParams p)
         const int b = r / tiles_y;
         const int oy0 = ty * TH, ox0 = tx * TW, iy0 = oy0 * S - pad_y, ix0 = ox0 * S - pad_x;
         ymask = 0; xmask = 0;
-        sfor<NYL>([&](auto ic) {
+        static_for<NYL>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             const int u = tid + 256 * i, px = u >> 3, part = u & 7;
             const int oy = oy0 + px / TW, ox = ox0 + px % TW, c = co0 + part * 8;
@@ -97,7 +87,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradParams p)
             yreg[i] = *reinterpret_cast<const u32x4 *>(p.dy + off);
             ymask |= ok ? (1u << i) : 0u;
         });
-        sfor<NXL>([&](auto ic) {
+        static_for<NXL>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             const int u = tid + 256 * i, px = u >> 3, part = u & 7;
             const int iy = iy0 + px / PW, ix = ix0 + px % PW, c = ci0 + part * 8;
@@ -110,12 +100,12 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradParams p)
     if ((int)blockIdx.x < ntiles) issue_loads(blockIdx.x);
     for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
         __syncthreads();  // the previous tile's reads are done
-        sfor<NYL>([&](auto ic) {
+        static_for<NYL>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             const int u = tid + 256 * i;
             if (u < Y_UNITS) *reinterpret_cast<u32x4 *>(ldsY + (u >> 3) * RS + (u & 7) * 16) = (ymask >> i) & 1u ? yreg[i] : u32x4{0u, 0u, 0u, 0u};
         });
-        sfor<NXL>([&](auto ic) {
+        static_for<NXL>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             const int u = tid + 256 * i;
             if (u < X_UNITS) *reinterpret_cast<u32x4 *>(ldsX + (u >> 3) * RS + (u & 7) * 16) = (xmask >> i) & 1u ? xreg[i] : u32x4{0u, 0u, 0u, 0u};
@@ -145,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradParams p)
         ld_a(0, 0);
         ld_b(0, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-        sfor<NSTEP>([&](auto sc) {
+        static_for<NSTEP>([&](auto sc) {
             constexpr int step = decltype(sc)::value, ks = step / NTG, tap = step % NTG;
             constexpr bool next_a = step + 1 < NSTEP && (step + 1) % NTG == 0;
             if constexpr (step + 1 < NSTEP) ld_b(step + 1, (step + 1) & 1);

@@ -3,6 +3,7 @@
 // the reference's torch-CPU / numpy arithmetic (oracle/decode_oracle.c holds the experimentally pinned formulas).
 #pragma once
 #include "decode_kernels.h"
+#include "mfma_dev.h"  // lds_barrier (__syncthreads() would also wait for the stores of cell maxima and candidate lists), static_for
 
 #include <math.h>
 
@@ -150,8 +151,3 @@ __device__ __forceinline__ unsigned short bf16_ceil(float f)
     if ((u & 0xffffu) && !(u >> 31)) ++t;  // positive and inexact: one step more positive
     return t;
 }
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt, i.e. it parks the wave until every
-// global store it has issued (cell maxima, candidate lists) is acknowledged by memory: a full round trip per barrier that no
-// thread of the workgroup depends on.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }

@@ -4,8 +4,6 @@
 // experimentally pinned formulas).
 #include "decode_dev.h"
 
-#include <utility>
-
 // ------------------------------------------------------------------ stage average
 // results.py:225-226: match_heatmaps_size (1/4 -> 1/2) then torch.stack(...).mean(dim=0)
 __global__ __launch_bounds__(256) void stage_average_kernel(const float *hm_q, int64_t hm_q_bs, const float *hm_h, int64_t hm_h_bs,
@@ -686,10 +684,6 @@ __device__ __forceinline__ int writelane_const(int val, int old)
     return old;
 }
 __device__ __forceinline__ int setlane_i32(int val, int l, int old, int lane) { return lane == l ? val : old; }
-template <typename F, int... I>
-__device__ __forceinline__ void mk_for_impl(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void mk_for(F &&f) { mk_for_impl(f, std::make_integer_sequence<int, N>{}); }
 // v of the lane ROT places further up its 16-lane row (row_ror): a vector-pipe move -- the xor shuffles they replace went through
 // the LDS crossbar, twice per double
 template <int ROT>
@@ -765,7 +759,7 @@ __device__ int munkres_wave_n(MatchShared &S, int n, int lane, int &star)
             const double v = S.Cm[(i < n ? i : 0) * MLD + cl];
             col[i] = (i < n && lane < n) ? v : 1.0;
         }
-        mk_for<NMAX>([&](auto ic) {
+        static_for<NMAX>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             if (i < n) {
                 // (lanes >= n hold 1.0 and are masked out of the ballot; their own `zt` is never read)
@@ -862,7 +856,7 @@ __device__ int munkres_wave_n(MatchShared &S, int n, int lane, int &star)
             // (the lane's column): adding or subtracting 0.0 returns c itself (up to the sign of a zero, which nothing here looks at),
             // and the selects act on one scalar and one register instead of on every element.
             const double sub = colunc ? mn : 0.0;
-            mk_for<NMAX>([&](auto ic) {
+            static_for<NMAX>([&](auto ic) {
                 constexpr int i = decltype(ic)::value;
                 if (i < n) {
                     const double a_i = ((rcm >> i) & 1u) ? mn : 0.0;

@@ -12,48 +12,11 @@
 //     v_mfma_f32_32x32x16_bf16 with the same operand roles (A = 32 couts x 16 channels, B = 16 channels x 32 pixels; lane half h
 //     holds channels 8h..8h+7 of a k-step), k-steps of 16 channels in ascending order, the same bf16 pack;
 //   * the sum is upadd_kernel's: base first, then the sources in j order, in fp32, one rounding, ReLU.
-#include "kernels.h"
-
-#include <utility>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short i16x2 __attribute__((ext_vector_type(2)));
+#include "mfma_dev.h"
 
 namespace {
 
 constexpr int TH = 8, TW = 32, CO = 32;  // branch-0 tile, output channels
-
-// conv_mfma's bf16 pack with the identity floor (the 1x1 terms have no ReLU)
-__device__ __forceinline__ unsigned pack_id(float a, float b)
-{
-    f32x2 f = {a, b};
-    const i16x2 v = __builtin_bit_cast(i16x2, __builtin_convertvector(f, bf16x2));
-    const i16x2 floor = {(short)-32768, (short)-32768};
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(v, floor));
-}
-// upadd_kernel's pack
-__device__ __forceinline__ unsigned pack2(float a, float b)
-{
-    f32x2 f = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
-}
-__device__ __forceinline__ float lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
-
-template <typename F, int... I>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>)
-{
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F &&f)
-{
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
 
 // One wave: u_J for 32 consecutive pixels (index 32 * COL ..) of the tile's J-shifted footprint, into LDS [pixel][32] bf16.
 // x_J has 32 << J channels = (2 << J) k-steps.
@@ -89,9 +52,11 @@ __device__ __forceinline__ void source_tile(const FusionUpParams &p, int b, int 
     });
     if (q < NPX) {
         unsigned *dst = reinterpret_cast<unsigned *>(lds_u + q * CO + 4 * h);
+        const i16x2 nofloor = {(short)-32768, (short)-32768};  // conv_mfma's pack with the identity floor (the 1x1 terms have no ReLU)
         static_for<4>([&](auto gc) {
             constexpr int g = decltype(gc)::value;
-            *reinterpret_cast<uint2 *>(dst + 4 * g) = make_uint2(pack_id(acc[4 * g + 0], acc[4 * g + 1]), pack_id(acc[4 * g + 2], acc[4 * g + 3]));
+            *reinterpret_cast<uint2 *>(dst + 4 * g) =
+                make_uint2(pack_bf16x2(acc[4 * g + 0], acc[4 * g + 1], nofloor), pack_bf16x2(acc[4 * g + 2], acc[4 * g + 3], nofloor));
         });
     }
 }
@@ -140,11 +105,12 @@ __global__ __launch_bounds__(256) void fusion_up_kernel(const FusionUpParams p)
         const int u = 256 * i + tid, px = u >> 2, c8 = u & 3;
         const int ly = px / TW, lx = px % TW;
         const u32x4 bv = base[i];
-        float v[8] = {lo(bv[0]), hi(bv[0]), lo(bv[1]), hi(bv[1]), lo(bv[2]), hi(bv[2]), lo(bv[3]), hi(bv[3])};
+        float v[8] = {bf16_lo(bv[0]), bf16_hi(bv[0]), bf16_lo(bv[1]), bf16_hi(bv[1]),
+                      bf16_lo(bv[2]), bf16_hi(bv[2]), bf16_lo(bv[3]), bf16_hi(bv[3])};
         auto add = [&](const bf16_raw *lds, int J) {
             const u32x4 uv = *reinterpret_cast<const u32x4 *>(lds + ((ly >> J) * (TW >> J) + (lx >> J)) * CO + c8 * 8);
-            v[0] += lo(uv[0]); v[1] += hi(uv[0]); v[2] += lo(uv[1]); v[3] += hi(uv[1]);
-            v[4] += lo(uv[2]); v[5] += hi(uv[2]); v[6] += lo(uv[3]); v[7] += hi(uv[3]);
+            v[0] += bf16_lo(uv[0]); v[1] += bf16_hi(uv[0]); v[2] += bf16_lo(uv[1]); v[3] += bf16_hi(uv[1]);
+            v[4] += bf16_lo(uv[2]); v[5] += bf16_hi(uv[2]); v[6] += bf16_lo(uv[3]); v[7] += bf16_hi(uv[3]);
         };
         add(u1, 1);
         if (p.nsrc >= 2) add(u2, 2);
@@ -152,7 +118,8 @@ __global__ __launch_bounds__(256) void fusion_up_kernel(const FusionUpParams p)
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
         if (valid[i])
-            *reinterpret_cast<u32x4 *>(p.out + opix[i] * p.out_cs + c8 * 8) = u32x4{pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
+            *reinterpret_cast<u32x4 *>(p.out + opix[i] * p.out_cs + c8 * 8) =  // (upadd_kernel's pack)
+                u32x4{round_bf16x2(v[0], v[1]), round_bf16x2(v[2], v[3]), round_bf16x2(v[4], v[5]), round_bf16x2(v[6], v[7])};
     });
 #ifndef HH_NO_CLK
     if (p.clk && tid == 0 && blockIdx.x + 256 >= gridDim.x) atomicMax(p.clk + 1, wall_clock64());

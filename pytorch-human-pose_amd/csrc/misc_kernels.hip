@@ -1,17 +1,6 @@
 // HBM-bound helper kernels of the forward path: the fused "nearest-upsample + n-way sum + ReLU" of the
 // exchange (fusion) layers, flip TTA, classifier tail, preprocessing.
-#include "kernels.h"
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned pack2(float a, float b)
-{
-    f32x2 f = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2));
-}
-__device__ __forceinline__ float lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
-__device__ __forceinline__ float hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
+#include "mfma_dev.h"
 
 // FusionLayer.forward's low->high terms and the sum (hrnet.py:200-205,214-229): the 1x1
 // conv + BN ran at low resolution; here the nearest upsample is an index shift on read and the
@@ -27,21 +16,21 @@ __global__ __launch_bounds__(256) void upadd_kernel(const UpAddParams p)
         const int y = (int)((pix / p.W) % p.H);
         const int b = (int)(pix / ((size_t)p.W * p.H));
         const uint4 bv = *reinterpret_cast<const uint4 *>(p.base + pix * p.base_cs + p.base_coff + c8 * 8);
-        float v[8] = {lo(bv.x), hi(bv.x), lo(bv.y), hi(bv.y), lo(bv.z), hi(bv.z), lo(bv.w), hi(bv.w)};
+        float v[8] = {bf16_lo(bv.x), bf16_hi(bv.x), bf16_lo(bv.y), bf16_hi(bv.y), bf16_lo(bv.z), bf16_hi(bv.z), bf16_lo(bv.w), bf16_hi(bv.w)};
 #pragma unroll
         for (int j = 0; j < 3; ++j)
             if (j < p.nup) {
                 const int sh = p.up_shift[j];
                 const size_t up = ((size_t)b * (p.H >> sh) + (y >> sh)) * (p.W >> sh) + (x >> sh);
                 const uint4 u = *reinterpret_cast<const uint4 *>(p.up[j] + up * p.up_cs[j] + c8 * 8);
-                v[0] += lo(u.x); v[1] += hi(u.x); v[2] += lo(u.y); v[3] += hi(u.y);
-                v[4] += lo(u.z); v[5] += hi(u.z); v[6] += lo(u.w); v[7] += hi(u.w);
+                v[0] += bf16_lo(u.x); v[1] += bf16_hi(u.x); v[2] += bf16_lo(u.y); v[3] += bf16_hi(u.y);
+                v[4] += bf16_lo(u.z); v[5] += bf16_hi(u.z); v[6] += bf16_lo(u.w); v[7] += bf16_hi(u.w);
             }
         if (p.relu)
 #pragma unroll
             for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
         *reinterpret_cast<uint4 *>(p.out + pix * p.out_cs + p.out_coff + c8 * 8) =
-            make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
+            make_uint4(round_bf16x2(v[0], v[1]), round_bf16x2(v[2], v[3]), round_bf16x2(v[4], v[5]), round_bf16x2(v[6], v[7]));
     }
 }
 
@@ -80,10 +69,11 @@ __global__ __launch_bounds__(256) void upadd_blocksum_kernel(const bf16_raw *__r
             for (int dx_ = 0; dx_ < (1 << sh); ++dx_) {
                 const size_t src = ((size_t)b * (h << sh) + ((y << sh) + dy_)) * W + ((x << sh) + dx_);
                 const uint4 u = *reinterpret_cast<const uint4 *>(g + src * C + c8 * 8);
-                v[0] += lo(u.x); v[1] += hi(u.x); v[2] += lo(u.y); v[3] += hi(u.y);
-                v[4] += lo(u.z); v[5] += hi(u.z); v[6] += lo(u.w); v[7] += hi(u.w);
+                v[0] += bf16_lo(u.x); v[1] += bf16_hi(u.x); v[2] += bf16_lo(u.y); v[3] += bf16_hi(u.y);
+                v[4] += bf16_lo(u.z); v[5] += bf16_hi(u.z); v[6] += bf16_lo(u.w); v[7] += bf16_hi(u.w);
             }
-        *reinterpret_cast<uint4 *>(dup + pix * C + c8 * 8) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
+        *reinterpret_cast<uint4 *>(dup + pix * C + c8 * 8) =
+            make_uint4(round_bf16x2(v[0], v[1]), round_bf16x2(v[2], v[3]), round_bf16x2(v[4], v[5]), round_bf16x2(v[6], v[7]));
     }
 }
 hipError_t launch_upadd_backward(const bf16_raw *dy, const bf16_raw *out, int relu, int B, int H, int W, int C, bf16_raw *g, bf16_raw *const *dup,
@@ -129,13 +119,6 @@ __device__ __forceinline__ void bf16x16_add(const bf16_raw *src, float v[16])
         v[2 * d + 1] += __builtin_bit_cast(float, w[d] & 0xffff0000u);
     }
 }
-__device__ __forceinline__ unsigned pack_bf16_pair(float a, float b)
-{
-    typedef float f32x2_ __attribute__((ext_vector_type(2)));
-    typedef __bf16 bf16x2_ __attribute__((ext_vector_type(2)));
-    f32x2_ f = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2_));
-}
 __global__ __launch_bounds__(256) void upadd_fp8_kernel(const UpAddFp8Params p)
 {
     const int cgn = p.C / 16;
@@ -176,8 +159,8 @@ __global__ __launch_bounds__(256) void upadd_fp8_kernel(const UpAddFp8Params p)
             q = __builtin_amdgcn_cvt_pk_fp8_f32(t[0], t[1], q, false);
             q = __builtin_amdgcn_cvt_pk_fp8_f32(t[2], t[3], q, true);
             w[d] = (unsigned)q;
-            wb[2 * d] = pack_bf16_pair(f4[0], f4[1]);
-            wb[2 * d + 1] = pack_bf16_pair(f4[2], f4[3]);
+            wb[2 * d] = round_bf16x2(f4[0], f4[1]);
+            wb[2 * d + 1] = round_bf16x2(f4[2], f4[3]);
         }
         if (p.out) *reinterpret_cast<uint4 *>(p.out + pix * p.out_cs + cg * 16) = make_uint4(w[0], w[1], w[2], w[3]);
         if (p.out16) {
@@ -309,8 +292,8 @@ __global__ __launch_bounds__(256) void avgpool_kernel(const bf16_raw *__restrict
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int p = 0; p < HW; ++p) {
         const uint4 v = *reinterpret_cast<const uint4 *>(in + ((size_t)b * HW + p) * in_cs + c8 * 8);
-        acc[0] += lo(v.x); acc[1] += hi(v.x); acc[2] += lo(v.y); acc[3] += hi(v.y);
-        acc[4] += lo(v.z); acc[5] += hi(v.z); acc[6] += lo(v.w); acc[7] += hi(v.w);
+        acc[0] += bf16_lo(v.x); acc[1] += bf16_hi(v.x); acc[2] += bf16_lo(v.y); acc[3] += bf16_hi(v.y);
+        acc[4] += bf16_lo(v.z); acc[5] += bf16_hi(v.z); acc[6] += bf16_lo(v.w); acc[7] += bf16_hi(v.w);
     }
     for (int k = 0; k < 8; ++k) out[(size_t)b * C + c8 * 8 + k] = acc[k] / (float)HW;
 }

@@ -5,27 +5,13 @@
 // that staged 16-channel pixels of which 13 were padding (536 MB, 334 us); here the image is read once.
 // Mapping: K = 27 taps (c, ky, kx) padded to 32 = two 16-wide MFMA k-steps; each lane owns one output pixel and gathers
 // its taps from a bf16 LDS patch into the B-operand layout; A = the 64 x 32 weight matrix (BN scale folded) in registers.
-#include "kernels.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short i16x2 __attribute__((ext_vector_type(2)));
+#include "mfma_dev.h"
 
 namespace {
 constexpr int TH = 8, TW = 32;                  // output tile
 constexpr int PH = 2 * TH + 1, PW = 2 * TW + 1;  // 17 x 65 input patch per channel
 constexpr int PLANE = PH * PW;                  // 1105
 constexpr int NVAL = 3 * PLANE;                 // 3315 values (+1 zero slot for the padded taps)
-
-__device__ __forceinline__ unsigned pack_relu_bf16x2(float a, float b)
-{
-    f32x2 f = {a, b};
-    const i16x2 v = __builtin_bit_cast(i16x2, __builtin_convertvector(f, bf16x2));
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(v, i16x2{0, 0}));
-}
 }  // namespace
 
 __global__ __launch_bounds__(256) void stem_conv_kernel(const StemParams p)

@@ -14,61 +14,10 @@
 //           Intermediate pixels outside the half-resolution image are conv2's zero padding;
 //   conv2   wave w = (output row w >> 1, 32-cout tile w & 1): 36 k-steps, its 36 weight fragments stay in 144 VGPRs for the life
 //           of the workgroup (no weight reads), pixel fragments by hand-pinned asm reads three steps ahead; ReLU, 16-byte stores.
-#include "kernels.h"
-
-#include <utility>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short i16x2 __attribute__((ext_vector_type(2)));
+#include "mfma_dev.h"
 
 namespace {
-template <typename F, int... I>
-__device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>)
-{
-    (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F &&f)
-{
-    static_for_impl(f, std::make_integer_sequence<int, N>{});
-}
-__device__ __forceinline__ unsigned pack_relu_bf16x2(float a, float b)
-{
-    f32x2 f = {a, b};
-    const i16x2 v = __builtin_bit_cast(i16x2, __builtin_convertvector(f, bf16x2));
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(v, i16x2{0, 0}));
-}
-// 32 couts of one pixel (lanes (r,0): couts 8g..8g+3, lanes (r,1): 8g+4..8g+7 in acc[4g..4g+3]) -> for m = 0,1 the 16 bytes
-// (bf16, ReLU applied) of couts 16m+8h .. 16m+8h+7 of this lane's pixel
-__device__ __forceinline__ void pack_rows16(const f32x16 &acc, u32x4 out[2])
-{
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        unsigned x0 = pack_relu_bf16x2(acc[8 * m + 0], acc[8 * m + 1]), x1 = pack_relu_bf16x2(acc[8 * m + 2], acc[8 * m + 3]);
-        unsigned y0 = pack_relu_bf16x2(acc[8 * m + 4], acc[8 * m + 5]), y1 = pack_relu_bf16x2(acc[8 * m + 6], acc[8 * m + 7]);
-        auto s0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
-        auto s1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
-        out[m] = u32x4{s0[0], s1[0], s0[1], s1[1]};
-    }
-}
-// LDS fragment reads pinned by hand (see basicblock_fused_pc.hip)
-template <int OFF>
-__device__ __forceinline__ u32x4 lds_read_async(int addr)
-{
-    u32x4 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF));
-    return v;
-}
-template <int N>
-__device__ __forceinline__ void lds_wait(u32x4 &v)
-{
-    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(N));
-}
-
+// (the LDS fragment reads are pinned by hand as in basicblock_fused_pc.hip: lds_read_async / lds_wait of mfma_dev.h)
 constexpr int T2H = 2, T2W = 32;                            // tile of the final (1/4 resolution) map
 constexpr int MR = 2 * T2H + 1, MC = 2 * T2W + 1;           // 5 x 65 intermediate (1/2 resolution) pixels
 constexpr int MPIX = MR * MC, NQ = (MPIX + 31) / 32;        // 325 -> 11 column tiles

@@ -21,11 +21,11 @@ CSRC = os.path.join(REPO, "pytorch-human-pose_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
-def device_asm(src: str) -> str:
+def device_asm(src: str, flags=("-O3", "-std=c++17", "--offload-arch=gfx950"), include: str = CSRC) -> str:
+    """gfx950 assembly of one translation unit (also used by tools/isa_diff.py, which passes the Makefile's own flags)"""
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "k.s")
-        subprocess.check_call([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-S", "-I", CSRC, src, "-o", out],
-                              stderr=subprocess.DEVNULL)
+        subprocess.check_call([HIPCC, *flags, "--cuda-device-only", "-S", "-I", include, src, "-o", out], stderr=subprocess.DEVNULL)
         return open(out).read()
 
 
