@@ -245,6 +245,15 @@ int hh_loss_ae_grouping(const float *tags, int64_t tags_bstride, const int32_t *
  *   dy [B,Ho,Wo,cout]; 3x3 stride 1/2 and 1x1 stride 1, channel counts % 8 == 0.  A GEMM contracted over pixels on MFMA
  *   (operands read from LDS with the transposing ds_read_b64_tr_b16), partial sums reduced in a fixed order.          */
 int64_t hh_conv2d_workspace_bytes(int cin, int cout, int ks, int mode);
+/* What would run, as host arithmetic alone (no device call; the selection code of the launches themselves):
+ *   hh_conv2d_config: the index (see hh_conv_config) of the instantiation hh_conv2d / hh_conv2d_packed launch for these
+ *     arguments on a map whose launched conv writes Wo columns (W at stride 1, W / 2 at stride 2, the W of dL/dy in mode 2,
+ *     whose four phase convs each write that many); -1 where they refuse the shape.
+ *   hh_conv2d_wgrad_plan: out = {kernel variant 0..5 (3x3 narrow maps, 3x3 small channel counts, 3x3, 1x1, 3x3 stride 2, 2x2),
+ *     persistent workers per channel block, pixel tiles they share}; 1 where hh_conv2d_wgrad refuses the shape.
+ *   (Additive diagnostic entry points: HH_ABI_VERSION stays 3.)                                                         */
+int hh_conv2d_config(int cin, int cout, int ks, int stride, int mode, int Wo);
+int hh_conv2d_wgrad_plan(int B, int H, int W, int cin, int cout, int ks, int stride, int out[3]);
 int64_t hh_conv2d_wgrad_workspace_bytes(int B, int H, int W, int cin, int cout, int ks, int stride);
 int hh_conv2d_wgrad(const void *x, const void *dy, int B, int H, int W, int cin, int cout, int ks, int stride, int pad_y, int pad_x, float *dw,
                     void *workspace, void *stream);

@@ -82,6 +82,8 @@ def _sig(lib):
         "hh_loss_heatmaps": (i32, [vp, i64, vp, vp, i32, i32, i32, i32, vp, vp, i64, vp, vp]),
         "hh_loss_ae_grouping": (i32, [vp, i64, vp, vp, i32, i32, i32, i32, i32, vp, vp, i64, C.c_float, C.c_float, vp, vp]),
         "hh_conv2d_workspace_bytes": (i64, [i32, i32, i32, i32]),
+        "hh_conv2d_config": (i32, [i32, i32, i32, i32, i32, i32]),
+        "hh_conv2d_wgrad_plan": (i32, [i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int)]),
         "hh_conv2d": (i32, [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp]),
         "hh_conv2d_wgrad_workspace_bytes": (i64, [i32, i32, i32, i32, i32, i32, i32]),
         "hh_conv2d_wgrad": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),

@@ -250,6 +250,16 @@ static int conv2d_plan(int cin, int cout, int ks, int stride, int mode, Conv2dPl
     return 0;
 }
 
+// the instantiation that runs a plan on an output map Wo columns wide (of one phase in mode 2)
+static int conv2d_pick(const Conv2dPlan &pl, int Wo) { return hh_pick_config(pl.kks, pl.kstride, pl.KC, pl.NT, Wo); }
+
+int hh_conv2d_config(int cin, int cout, int ks, int stride, int mode, int Wo)
+{
+    Conv2dPlan pl;
+    if (mode < 0 || mode > 2 || Wo <= 0 || conv2d_plan(cin, cout, ks, stride, mode, &pl, "hh_conv2d_config")) return -1;
+    return conv2d_pick(pl, Wo);
+}
+
 // w: fp32 weights (packed into `workspace` here) or, with prepacked != NULL, weight sets packed by hh_pack_conv_weights_batch
 static int conv2d_impl(const void *x, int B, int H, int W, int cin, const float *w, const bf16_raw *prepacked, int cout, int ks, int stride,
                        int mode, int pad_y, int pad_x, const float *bias, const void *res, int relu, void *y, void *workspace, void *stream,
@@ -292,7 +302,7 @@ static int conv2d_impl(const void *x, int B, int H, int W, int cin, const float 
         HH_CHECK_HIP(hipMemcpyAsync(zbias, bias, (size_t)co * 4, hipMemcpyDeviceToDevice, s));
     }
     const int Ho = pl.kstride == 2 ? H / 2 : H, Wo = pl.kstride == 2 ? W / 2 : W;
-    const int cfg = hh_pick_config(pl.kks, pl.kstride, KC, pl.NT, Wo);
+    const int cfg = conv2d_pick(pl, Wo);
     if (cfg < 0) { hh_set_error((std::string(who) + ": no kernel instantiation for this shape").c_str()); return 1; }
     const ConvConfig &cc = conv_config(cfg);
     ConvParams p{};
@@ -372,7 +382,27 @@ int64_t hh_conv2d_wgrad_workspace_bytes(int B, int H, int W, int cin, int cout, 
 {
     const int Ho = stride == 2 ? H / 2 : H, Wo = stride == 2 ? W / 2 : W;
     // one partial-sum set [ks*ks][cout64][cin64] per worker; the reduction combines them in LDS (no staging rows since round 3)
-    return (int64_t)conv_wgrad_num_workers(B, Ho, Wo, stride, cin, cout) * ks * ks * round_up_i(cout, 64) * round_up_i(cin, 64) * 4;
+    return (int64_t)conv_wgrad_num_workers(B, Ho, Wo, ks, stride, cin, cout) * ks * ks * round_up_i(cout, 64) * round_up_i(cin, 64) * 4;
+}
+
+// the shape checks of hh_conv2d_wgrad; -> 0 and the output map, or 1 with the error set
+static int wgrad_shape(int B, int H, int W, int cin, int cout, int ks, int stride, int *Ho, int *Wo)
+{
+    if (B <= 0 || H <= 0 || W <= 0) { hh_set_error("hh_conv2d_wgrad: bad argument"); return 1; }
+    if (cin <= 0 || cout <= 0 || cin % 8 || cout % 8) { hh_set_error("hh_conv2d_wgrad: channel counts must be multiples of 8"); return 1; }
+    *Ho = stride == 2 ? H / 2 : H; *Wo = stride == 2 ? W / 2 : W;
+    if (conv_wgrad_variant(ks, stride, *Wo, cin, cout) < 0) { hh_set_error("hh_conv2d_wgrad: 3x3 (stride 1 or 2), 2x2 and 1x1 (stride 1) only"); return 1; }
+    return 0;
+}
+
+int hh_conv2d_wgrad_plan(int B, int H, int W, int cin, int cout, int ks, int stride, int out[3])
+{
+    int Ho, Wo;
+    if (!out || wgrad_shape(B, H, W, cin, cout, ks, stride, &Ho, &Wo)) return 1;
+    out[0] = conv_wgrad_variant(ks, stride, Wo, cin, cout);
+    out[1] = conv_wgrad_num_workers(B, Ho, Wo, ks, stride, cin, cout);
+    out[2] = conv_wgrad_num_tiles(B, Ho, Wo, out[0]);
+    return 0;
 }
 
 int hh_conv2d_wgrad(const void *x, const void *dy, int B, int H, int W, int cin, int cout, int ks, int stride, int pad_y, int pad_x, float *dw,
@@ -380,12 +410,12 @@ int hh_conv2d_wgrad(const void *x, const void *dy, int B, int H, int W, int cin,
 {
     if (pad_y < 0) pad_y = (ks - 1) / 2;
     if (pad_x < 0) pad_x = (ks - 1) / 2;
-    if (!x || !dy || !dw || !workspace || B <= 0 || H <= 0 || W <= 0) { hh_set_error("hh_conv2d_wgrad: bad argument"); return 1; }
-    if (cin % 8 || cout % 8) { hh_set_error("hh_conv2d_wgrad: channel counts must be multiples of 8"); return 1; }
-    if (!((ks == 3 && (stride == 1 || stride == 2)) || ((ks == 1 || ks == 2) && stride == 1))) { hh_set_error("hh_conv2d_wgrad: 3x3 (stride 1 or 2), 2x2 and 1x1 (stride 1) only"); return 1; }
+    if (!x || !dy || !dw || !workspace) { hh_set_error("hh_conv2d_wgrad: bad argument"); return 1; }
+    int Ho_, Wo_;
+    if (wgrad_shape(B, H, W, cin, cout, ks, stride, &Ho_, &Wo_)) return 1;
     WgradParams p{};
     p.x = (const bf16_raw *)x; p.dy = (const bf16_raw *)dy; p.partial = (float *)workspace;
-    p.B = B; p.H = H; p.W = W; p.Ho = stride == 2 ? H / 2 : H; p.Wo = stride == 2 ? W / 2 : W; p.cin = cin; p.cout = cout;
+    p.B = B; p.H = H; p.W = W; p.Ho = Ho_; p.Wo = Wo_; p.cin = cin; p.cout = cout;
     p.pad_y = pad_y; p.pad_x = pad_x;
     HH_CHECK_HIP(conv_wgrad_launch(p, ks, stride, dw, (hipStream_t)stream));
     return 0;

@@ -219,12 +219,35 @@ static hipError_t launch_one(const WgradParams &p, int nwg, hipStream_t s)
     return hipGetLastError();
 }
 
+// The kernel variant of a shape: 0 = 3x3 narrow maps, 1 = 3x3 small channel counts, 2 = 3x3, 3 = 1x1, 4 = 3x3 stride 2, 5 = 2x2;
+// -1: none.  Host arithmetic only (hh_conv2d_wgrad_plan reports it).
+int conv_wgrad_variant(int ks, int stride, int Wo, int cin, int cout)
+{
+    if (ks == 3 && stride == 1 && Wo <= 16) return 0;  // narrow maps: no half-empty tiles
+    if (ks == 3 && stride == 1 && cin <= 32 && cout <= 32) return 1;
+    if (ks == 3 && stride == 1) return 2;
+    if (ks == 1 && stride == 1) return 3;
+    if (ks == 3 && stride == 2) return 4;
+    if (ks == 2 && stride == 1) return 5;
+    return -1;
+}
+
+// Tile width of every variant: the launches below instantiate the kernel with it and the tile count is taken with it, so the
+// host's count is the one the kernel walks.
+constexpr int VARIANT_TW[6] = {16, 32, 32, 32, 16, 32};
+
+// Pixel tiles the workers of one channel block share (variant: conv_wgrad_variant; a shape without one is counted 32 columns wide).
+int conv_wgrad_num_tiles(int B, int Ho, int Wo, int variant)
+{
+    const int TW = variant >= 0 && variant < 6 ? VARIANT_TW[variant] : 32;
+    return B * ((Ho + TH - 1) / TH) * ((Wo + TW - 1) / TW);
+}
+
 // Persistent pixel-tile workers per 64x64 channel block: enough workgroups to fill the chip (>= 512 over all channel
 // blocks), but no more partial-sum sets than that, since every one is 9 x 64 x 64 floats the reduction has to read back.
-int conv_wgrad_num_workers(int B, int Ho, int Wo, int stride, int cin, int cout)
+int conv_wgrad_num_workers(int B, int Ho, int Wo, int ks, int stride, int cin, int cout)
 {
-    const int TW = (stride == 2 || Wo <= 16) ? 16 : 32;
-    const int ntiles = B * ((Ho + TH - 1) / TH) * ((Wo + TW - 1) / TW);
+    const int ntiles = conv_wgrad_num_tiles(B, Ho, Wo, conv_wgrad_variant(ks, stride, Wo, cin, cout));
     const int nblocks = ((cin + 63) / 64) * ((cout + 63) / 64);
     int want = (HH_WGRAD_WORKERS * 2 + nblocks - 1) / nblocks;
     if (want < HH_WGRAD_WORKERS / 4) want = HH_WGRAD_WORKERS / 4;  // many channel blocks already fill the chip; every worker costs a partial set
@@ -234,16 +257,17 @@ int conv_wgrad_num_workers(int B, int Ho, int Wo, int stride, int cin, int cout)
 
 hipError_t conv_wgrad_launch(const WgradParams &p, int ks, int stride, float *dw, hipStream_t s)
 {
-    const int nwg = conv_wgrad_num_workers(p.B, p.Ho, p.Wo, stride, p.cin, p.cout);
+    const int nwg = conv_wgrad_num_workers(p.B, p.Ho, p.Wo, ks, stride, p.cin, p.cout);
+    const int variant = conv_wgrad_variant(ks, stride, p.Wo, p.cin, p.cout);
     hipError_t e = hipErrorInvalidValue;
-    if (ks == 3 && stride == 1 && p.Wo <= 16) e = launch_one<3, 1, 16>(p, nwg, s);  // narrow maps: no half-empty tiles
-    else if (ks == 3 && stride == 1 && p.cin <= 32 && p.cout <= 32) e = launch_one<3, 1, 32, true>(p, nwg, s);
-    else if (ks == 3 && stride == 1) e = launch_one<3, 1, 32>(p, nwg, s);
-    else if (ks == 1 && stride == 1) e = launch_one<1, 1, 32>(p, nwg, s);
-    else if (ks == 3 && stride == 2) e = launch_one<3, 2, 16>(p, nwg, s);
-    else if (ks == 2 && stride == 1) e = launch_one<2, 1, 32>(p, nwg, s);
+    if (variant == 0) e = launch_one<3, 1, VARIANT_TW[0]>(p, nwg, s);
+    else if (variant == 1) e = launch_one<3, 1, VARIANT_TW[1], true>(p, nwg, s);
+    else if (variant == 2) e = launch_one<3, 1, VARIANT_TW[2]>(p, nwg, s);
+    else if (variant == 3) e = launch_one<1, 1, VARIANT_TW[3]>(p, nwg, s);
+    else if (variant == 4) e = launch_one<3, 2, VARIANT_TW[4]>(p, nwg, s);
+    else if (variant == 5) e = launch_one<2, 1, VARIANT_TW[5]>(p, nwg, s);
     if (e != hipSuccess) return e;
-    const bool smallc = ks == 3 && stride == 1 && p.Wo > 16 && p.cin <= 32 && p.cout <= 32;  // the SMALLC instance ran
+    const bool smallc = variant == 1;  // the SMALLC instance ran
     const int coutp = smallc ? 32 : (p.cout + 63) / 64 * 64, cinp = smallc ? 32 : (p.cin + 63) / 64 * 64, ntap = ks * ks;
     const size_t nel = (size_t)ntap * coutp * cinp, nel4 = nel / 4;
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((nel4 + 63) / 64)), dim3(64, RG), 0, s, p.partial, nwg, nel4, ntap, p.cout, p.cin, coutp,

@@ -368,5 +368,7 @@ struct WgradParams {
     int pad_y, pad_x;    // top / left zero padding of x
 };
 #define HH_WGRAD_WORKERS 128  // base count of persistent pixel-tile workers per channel block (64 .. 512, see conv_wgrad_num_workers)
-int conv_wgrad_num_workers(int B, int Ho, int Wo, int stride, int cin, int cout);
+int conv_wgrad_num_workers(int B, int Ho, int Wo, int ks, int stride, int cin, int cout);
+int conv_wgrad_num_tiles(int B, int Ho, int Wo, int variant);  // with the tile width of that variant's kernel
+int conv_wgrad_variant(int ks, int stride, int Wo, int cin, int cout);  // 0..5 (conv_wgrad.hip), -1: no kernel
 hipError_t conv_wgrad_launch(const WgradParams &p, int ks, int stride, float *dw, hipStream_t s);
