@@ -223,6 +223,45 @@ int hh_loss_ae_grouping(const float *tags, int64_t tags_bstride, const int32_t *
                         int h, int w, float *push_pull, float *grad, int64_t grad_bstride, float push_scale, float pull_scale,
                         double *scratch, void *stream);
 
+/* The input of the training step built on the device: what the reference's dataset worker does per sample on the host with cv2 and
+ * numpy (keypoints/transforms.py:75-172 RandomAffineTransform, :56-72 RandomHorizontalFlip, :37-53 ToTensor + Normalize;
+ * keypoints/datasets/coco.py:77-121 HeatmapGenerator), batched.  The raw uint8 pixels, the crowd masks and the descriptors lie in ONE
+ * device buffer that the caller ships in one host->device copy; `descs_dev` is a DEVICE array.  The random draws, the matrices and
+ * the joints stay on the host (keypoints/train_input.py).  The warp is the one of hh_preprocess_u8 (cv2 parity UNPINNED).
+ *
+ * hh_train_desc: one sample.  Image uint8 RGB [h,w,3] at batch_base + image_offset, crowd mask uint8 [h,w] with values 0 / 255
+ *   (= (mask * 255).astype(np.uint8), transforms.py:159) at batch_base + mask_offset; flip != 0 reverses the destination columns
+ *   AFTER the warp (image[:, ::-1], transforms.py:66-68; not folded into the matrix: the fixed-point rounding is per destination
+ *   column); the dst_to_src matrices are hh_invert_affine of RandomAffineTransform._get_affine_matrix(...)[:2] for the image
+ *   (transforms.py:167-170) and for every heatmap stage (transforms.py:155-156).                                            */
+#define HH_TRAIN_MAX_STAGES 4
+typedef struct hh_train_desc {
+    long long image_offset, mask_offset; /* bytes from batch_base */
+    int h, w;                            /* raw image (and mask) size */
+    int flip, reserved;
+    double image_dst_to_src[6];
+    double mask_dst_to_src[HH_TRAIN_MAX_STAGES][6];
+} hh_train_desc;
+/* out_nchw[b,:,y,x] = Normalize(ToTensor(warpAffine(image_b)))[y, flip_b ? W-1-x : x], fp32 [n,3,H,W]; one launch. */
+int hh_train_images_u8_batch(const unsigned char *batch_base, const hh_train_desc *descs_dev, int n, float *out_nchw, int H, int W,
+                             const float mean[3], const float stdv[3], void *stream);
+/* transforms.py:155-163 + :68 for all stages in one launch: out[k] (HOST array of nstages device pointers) is fp32
+ * [n, stage_hw[2k], stage_hw[2k+1]] (stage_hw: HOST ints) = (warpAffine(mask * 255) / 255 > 0.5) as 1.0 / 0.0, then the flip.
+ * For a byte v, v / 255 > 0.5 is v >= 128, which is what the kernel tests.                                             */
+int hh_train_masks_u8_batch(const unsigned char *batch_base, const hh_train_desc *descs_dev, int n, int nstages, const int *stage_hw,
+                            float *const *out, void *stream);
+/* HeatmapGenerator (coco.py:77-121) as a gather over the packed joints the grouping loss takes (hh_loss_ae_grouping: joints int32
+ * [B,P,K,3] = x, y, vis from JointsGenerator, coco.py:124-137; num_people [B]): out fp32 [B,K,h,w], each element the maximum over
+ * the image's people p < num_people[b] with vis > 0 and (x, y) inside the map of table[y - y_p + reach][x - x_p + reach] where that
+ * index is inside the table, else 0.  `table` (device) is the reference's `gauss` (coco.py:89-92: float64 exp) cast to fp32,
+ * [n,n] with n = 2 * reach + 1 = 6 sigma + 3.  Bit-identical to the reference's float32 maps: the cast is monotone, max is
+ * order-free.  Every element is written exactly once (no memset first); deterministic.  One launch per stage.
+ * hh_heatmap_table_size (host-side): n and reach for a sigma; refuses a sigma for which 3 sigma + 1 is not an integer (the
+ * reference's np.round of the window corners then depends on the parity of the joint) or n > 63.                            */
+int hh_heatmap_table_size(double sigma, int *n, int *reach);
+int hh_render_heatmaps(const int32_t *joints, const int32_t *num_people, int B, int P, int K, const float *table, int n, int reach,
+                       float *out, int h, int w, void *stream);
+
 /* Building blocks of the training step (keypoints/module.py:43-71), assembled into the net's training forward / backward
  * by keypoints/train_net.py with torch autograd as the tape.  Activations are NHWC bf16 [B,H,W,C] (= torch channels_last),
  * parameters fp32, all device pointers.

@@ -195,6 +195,60 @@ int hh_preprocess_u8_batch(const unsigned char *images_base, const hh_image_desc
     return 0;
 }
 
+int hh_train_images_u8_batch(const unsigned char *batch_base, const hh_train_desc *descs_dev, int n, float *out_nchw, int H, int W,
+                             const float mean[3], const float stdv[3], void *stream)
+{
+    static_assert(sizeof(hh_train_desc) == sizeof(HHTrainDesc) && sizeof(HHTrainDesc) == 272 && HH_TRAIN_MAX_STAGES == HH_TRAIN_STAGES, "descriptor layout");
+    if (!batch_base || !descs_dev || !out_nchw || !mean || !stdv) { hh_set_error("hh_train_images_u8_batch: null pointer"); return 1; }
+    if (n <= 0 || n > 65535 || H <= 0 || W <= 0 || (int64_t)H * W > (1 << 30)) { hh_set_error("hh_train_images_u8_batch: need 0 < n <= 65535 and 0 < H * W <= 2^30"); return 1; }
+    HH_CHECK_HIP(launch_train_images(batch_base, reinterpret_cast<const HHTrainDesc *>(descs_dev), n, out_nchw, H, W, mean, stdv, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_train_masks_u8_batch(const unsigned char *batch_base, const hh_train_desc *descs_dev, int n, int nstages, const int *stage_hw,
+                            float *const *out, void *stream)
+{
+    if (!batch_base || !descs_dev || !stage_hw || !out) { hh_set_error("hh_train_masks_u8_batch: null pointer"); return 1; }
+    if (n <= 0 || n > 65535) { hh_set_error("hh_train_masks_u8_batch: need 0 < n <= 65535"); return 1; }
+    if (nstages <= 0 || nstages > HH_TRAIN_MAX_STAGES) { hh_set_error("hh_train_masks_u8_batch: 1..HH_TRAIN_MAX_STAGES (4) stages"); return 1; }
+    TrainMaskStages st = {};
+    st.n = nstages;
+    int64_t total = 0;
+    for (int k = 0; k < nstages; ++k) {
+        if (!out[k]) { hh_set_error("hh_train_masks_u8_batch: null output pointer in the table"); return 1; }
+        if (stage_hw[2 * k] <= 0 || stage_hw[2 * k + 1] <= 0) { hh_set_error("hh_train_masks_u8_batch: stage sizes must be positive"); return 1; }
+        st.out[k] = out[k], st.h[k] = stage_hw[2 * k], st.w[k] = stage_hw[2 * k + 1];
+        total += (int64_t)st.h[k] * st.w[k];
+    }
+    if (total > (1 << 30)) { hh_set_error("hh_train_masks_u8_batch: the stages' pixel count exceeds 2^30"); return 1; }
+    HH_CHECK_HIP(launch_train_masks(batch_base, reinterpret_cast<const HHTrainDesc *>(descs_dev), n, st, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_heatmap_table_size(double sigma, int *n, int *reach)
+{
+    if (!n || !reach) { hh_set_error("hh_heatmap_table_size: null pointer"); return 1; }
+    const double r = 3.0 * sigma + 1.0;
+    if (!(sigma > 0.0) || !(r <= 1e6) || r != std::floor(r)) { hh_set_error("hh_heatmap_table_size: 3 * sigma + 1 must be a positive integer (sigma = 1, 2, 4, ...)"); return 1; }
+    if (2 * (int)r + 1 > HH_RENDER_MAX_N) { hh_set_error("hh_heatmap_table_size: the bump table 6 * sigma + 3 would exceed 63 entries a side"); return 1; }
+    *reach = (int)r;
+    *n = 2 * (int)r + 1;
+    return 0;
+}
+
+int hh_render_heatmaps(const int32_t *joints, const int32_t *num_people, int B, int P, int K, const float *table, int n, int reach,
+                       float *out, int h, int w, void *stream)
+{
+    if (!joints || !num_people || !table || !out) { hh_set_error("hh_render_heatmaps: null pointer"); return 1; }
+    if (n <= 0 || n > HH_RENDER_MAX_N || reach < 0 || n != 2 * reach + 1) { hh_set_error("hh_render_heatmaps: need a table of n = 2 * reach + 1 <= 63 entries a side"); return 1; }
+    if (B <= 0 || B > 65535 || K <= 0 || K > 65535 || P <= 0 || h <= 0 || w <= 0 || w > HH_RENDER_MAX_W || (int64_t)h * w > (1 << 30)) {
+        hh_set_error("hh_render_heatmaps: need 0 < B, K <= 65535, P > 0, 0 < w <= 4096, h > 0");
+        return 1;
+    }
+    HH_CHECK_HIP(launch_render_heatmaps(joints, num_people, B, P, K, table, n, reach, out, h, w, (hipStream_t)stream));
+    return 0;
+}
+
 int hh_loss_heatmaps(const float *pred, int64_t pred_bstride, const float *target, const float *mask, int B, int K, int h, int w,
                      float *loss, float *grad, int64_t grad_bstride, double *scratch, void *stream)
 {

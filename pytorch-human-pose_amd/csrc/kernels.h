@@ -318,6 +318,24 @@ hipError_t launch_preprocess_batch(const unsigned char *base, const HHImageDesc 
 hipError_t launch_warp_affine_u8(const unsigned char *img, int h, int w, const double inv[6], unsigned char *out, int H, int W, hipStream_t s);
 hipError_t launch_preprocess(const unsigned char *img, int h, int w, const double inv[6], float *out, int H, int W,
                              const float mean[3], const float stdv[3], hipStream_t s);
+// The training input (hh_train_desc of include/hhrnet.h): one sample's raw image and crowd mask in the batch buffer, its flip
+// flag, and the destination -> source affines of the image and of every stage's mask.
+#define HH_TRAIN_STAGES 4
+struct HHTrainDesc {
+    long long image_offset, mask_offset;  // bytes from the batch's base pointer
+    int h, w, flip, reserved;
+    double inv_image[6];
+    double inv_mask[HH_TRAIN_STAGES][6];
+};
+struct TrainMaskStages { float *out[HH_TRAIN_STAGES]; int h[HH_TRAIN_STAGES], w[HH_TRAIN_STAGES], n; };
+hipError_t launch_train_images(const unsigned char *base, const HHTrainDesc *descs, int n, float *out, int H, int W, const float mean[3],
+                               const float stdv[3], hipStream_t s);
+hipError_t launch_train_masks(const unsigned char *base, const HHTrainDesc *descs, int n, const TrainMaskStages &st, hipStream_t s);
+// target heatmaps from the packed joints (train_input.hip); n = table side = 2 * reach + 1 <= HH_RENDER_MAX_N, w <= HH_RENDER_MAX_W
+#define HH_RENDER_MAX_N 63
+#define HH_RENDER_MAX_W 4096
+hipError_t launch_render_heatmaps(const int32_t *joints, const int32_t *num_people, int B, int P, int K, const float *table, int n, int reach,
+                                  float *out, int h, int w, hipStream_t s);
 hipError_t launch_flip_images(const float *in, float *out, int B, int C, int H, int W, hipStream_t s);
 struct FlipPerm { unsigned char v[64]; };
 hipError_t launch_flip_merge(float *hm, int64_t hm_bs, const float *hmf, int64_t hmf_bs, const float *tf, int64_t tf_bs,

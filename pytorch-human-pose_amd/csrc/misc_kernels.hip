@@ -329,7 +329,9 @@ hipError_t launch_linear(const float *x, const float *w, const float *bias, floa
 //   fraction = X & 31 (INTER_BITS = 5); weights = the int16 table entries (32-fy)(32-fx)*32 ... that sum to 32768 (entry (0,0):
 //   32767 + 1 on the bottom-right tap, as the table builder leaves it); value = (sum + 16384) >> 15; taps outside the image are 0.
 //   Every double product / sum is rounded on its own (no contraction), round = nearest-even as cvRound.
-__device__ __forceinline__ void warp_pixel_u8(const unsigned char *__restrict__ img, int h, int w, const double inv[6], int x, int y, int out[3])
+//   CH = interleaved channels per pixel: 3 for the RGB image, 1 for the crowd masks of the training transform.
+template <int CH>
+__device__ __forceinline__ void warp_pixel_u8(const unsigned char *__restrict__ img, int h, int w, const double inv[6], int x, int y, int out[CH])
 {
     auto sat_i = [](double v) -> int { return v >= 2147483647.0 ? 2147483647 : v <= -2147483648.0 ? (int)(-2147483647 - 1) : (int)v; };
     const int adelta = sat_i(rint(__dmul_rn(__dmul_rn(inv[0], (double)x), 1024.0)));
@@ -342,10 +344,10 @@ __device__ __forceinline__ void warp_pixel_u8(const unsigned char *__restrict__ 
     int w00 = (32 - fy) * (32 - fx) * 32, w01 = (32 - fy) * fx * 32, w10 = fy * (32 - fx) * 32, w11 = fy * fx * 32;
     if ((fx | fy) == 0) { w00 = 32767; w11 = 1; }
     const bool y0 = sy >= 0 && sy < h, y1 = sy + 1 >= 0 && sy + 1 < h, x0 = sx >= 0 && sx < w, x1 = sx + 1 >= 0 && sx + 1 < w;
-    const unsigned char *r0 = img + ((size_t)(y0 ? sy : 0) * w) * 3, *r1 = img + ((size_t)(y1 ? sy + 1 : 0) * w) * 3;
-    const int c0 = (x0 ? sx : 0) * 3, c1 = (x1 ? sx + 1 : 0) * 3;
+    const unsigned char *r0 = img + ((size_t)(y0 ? sy : 0) * w) * CH, *r1 = img + ((size_t)(y1 ? sy + 1 : 0) * w) * CH;
+    const int c0 = (x0 ? sx : 0) * CH, c1 = (x1 ? sx + 1 : 0) * CH;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < CH; ++c) {
         const int p00 = (y0 && x0) ? r0[c0 + c] : 0, p01 = (y0 && x1) ? r0[c1 + c] : 0;
         const int p10 = (y1 && x0) ? r1[c0 + c] : 0, p11 = (y1 && x1) ? r1[c1 + c] : 0;
         out[c] = (p00 * w00 + p01 * w01 + p10 * w10 + p11 * w11 + 16384) >> 15;
@@ -355,7 +357,7 @@ __device__ __forceinline__ void preprocess_pixel(const unsigned char *__restrict
                                                  float *__restrict__ out, int H, int W, int i, const float mean[3], const float stdv[3])
 {
     int v[3];
-    warp_pixel_u8(img, h, w, inv, i % W, i / W, v);
+    warp_pixel_u8<3>(img, h, w, inv, i % W, i / W, v);
 #pragma unroll
     for (int c = 0; c < 3; ++c) out[(size_t)c * H * W + i] = ((float)v[c] / 255.0f - mean[c]) / stdv[c];
 }
@@ -368,7 +370,7 @@ __global__ __launch_bounds__(256) void warp_affine_u8_kernel(const unsigned char
     if (i >= H * W) return;
     const double inv[6] = {i00, i01, i02, i10, i11, i12};
     int v[3];
-    warp_pixel_u8(img, h, w, inv, i % W, i / W, v);
+    warp_pixel_u8<3>(img, h, w, inv, i % W, i / W, v);
 #pragma unroll
     for (int c = 0; c < 3; ++c) out[(size_t)i * 3 + c] = (unsigned char)v[c];
 }
@@ -411,6 +413,58 @@ hipError_t launch_preprocess(const unsigned char *img, int h, int w, const doubl
 {
     hipLaunchKernelGGL(preprocess_kernel, dim3((H * W + 255) / 256), dim3(256), 0, s, img, h, w, inv[0], inv[1], inv[2], inv[3], inv[4],
                        inv[5], out, H, W, mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2]);
+    return hipGetLastError();
+}
+
+// The train-time transform on the GPU (keypoints/transforms.py:75-172 RandomAffineTransform, :56-72 RandomHorizontalFlip, :37-53
+// ToTensor + Normalize).  One descriptor per sample (hh_train_desc of include/hhrnet.h) lies behind the pixels and masks in the
+// batch buffer.  The flip is an index reversal on the DESTINATION column after the warp: cv's adelta / X0 rounding is per
+// destination column, so a flip folded into the matrix would not give the same bits.
+__global__ __launch_bounds__(256) void train_images_kernel(const unsigned char *__restrict__ base, const HHTrainDesc *__restrict__ descs,
+                                                           float *__restrict__ out, int H, int W, float m0, float m1, float m2,
+                                                           float s0, float s1, float s2)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= H * W) return;
+    const HHTrainDesc *d = descs + blockIdx.y;
+    const double inv[6] = {d->inv_image[0], d->inv_image[1], d->inv_image[2], d->inv_image[3], d->inv_image[4], d->inv_image[5]};
+    const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
+    const int x = i % W, y = i / W;
+    int v[3];
+    warp_pixel_u8<3>(base + d->image_offset, d->h, d->w, inv, x, y, v);
+    float *o = out + (size_t)blockIdx.y * 3 * H * W + (size_t)y * W + (d->flip ? W - 1 - x : x);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[(size_t)c * H * W] = ((float)v[c] / 255.0f - mean[c]) / stdv[c];
+}
+hipError_t launch_train_images(const unsigned char *base, const HHTrainDesc *descs, int n, float *out, int H, int W, const float mean[3],
+                               const float stdv[3], hipStream_t s)
+{
+    hipLaunchKernelGGL(train_images_kernel, dim3((H * W + 255) / 256, n), dim3(256), 0, s, base, descs, out, H, W, mean[0], mean[1],
+                       mean[2], stdv[0], stdv[1], stdv[2]);
+    return hipGetLastError();
+}
+// the crowd masks of every stage (transforms.py:155-163): warpAffine((mask * 255).astype(uint8)) / 255 > 0.5, i.e. the warped
+// byte >= 128, as 1.0f / 0.0f; blockIdx.x walks the stages' pixels one stage after the other
+__global__ __launch_bounds__(256) void train_masks_kernel(const unsigned char *__restrict__ base, const HHTrainDesc *__restrict__ descs,
+                                                          const TrainMaskStages st)
+{
+    int i = blockIdx.x * 256 + threadIdx.x, k = 0;
+    while (k < st.n && i >= st.h[k] * st.w[k]) i -= st.h[k] * st.w[k], ++k;
+    if (k >= st.n) return;
+    const int H = st.h[k], W = st.w[k];
+    const HHTrainDesc *d = descs + blockIdx.y;
+    const double *m = d->inv_mask[k];
+    const double inv[6] = {m[0], m[1], m[2], m[3], m[4], m[5]};
+    const int x = i % W, y = i / W;
+    int v[1];
+    warp_pixel_u8<1>(base + d->mask_offset, d->h, d->w, inv, x, y, v);
+    st.out[k][(size_t)blockIdx.y * H * W + (size_t)y * W + (d->flip ? W - 1 - x : x)] = v[0] >= 128 ? 1.0f : 0.0f;
+}
+hipError_t launch_train_masks(const unsigned char *base, const HHTrainDesc *descs, int n, const TrainMaskStages &st, hipStream_t s)
+{
+    int total = 0;
+    for (int k = 0; k < st.n; ++k) total += st.h[k] * st.w[k];
+    hipLaunchKernelGGL(train_masks_kernel, dim3((total + 255) / 256, n), dim3(256), 0, s, base, descs, st);
     return hipGetLastError();
 }
 

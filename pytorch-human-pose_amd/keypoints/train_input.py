@@ -1,0 +1,247 @@
+"""The input of the training step built on the device: augmentation warps, crowd masks and target heatmaps.
+
+Stands in for what the reference's dataset worker does per sample on the host (`src/keypoints/transforms.py:75-172`
+RandomAffineTransform, `:56-72` RandomHorizontalFlip, `:37-53` ToTensor + Normalize; `src/keypoints/datasets/coco.py:77-137`
+HeatmapGenerator / JointsGenerator; `:140-164` collate_fn).  The split:
+  * host, numpy float64 (B * P * 17 points): the random draws -- from the same global RNGs in the reference's order, so that equal
+    seeds give equal augmentations --, the affine matrices, the transformed / flipped joints and their integer form;
+  * device: the image warp + flip + normalisation (hh_train_images_u8_batch), the crowd masks of all stages
+    (hh_train_masks_u8_batch) and the target heatmaps (hh_render_heatmaps, one launch per stage).
+Raw pixels, masks and descriptors cross in ONE host->device copy from a pinned, double-buffered staging area.  The result is what
+`KeypointsModule.training_step` / `AEKeypointsLoss.calculate_loss` take: (images, [heatmaps], [masks], [DeviceJoints]).
+There is no CPU path.  The warp is the project's restatement of cv2.warpAffine (parity with cv2 itself UNPINNED, as for
+hh_preprocess_u8).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import random
+from dataclasses import dataclass
+
+import numpy as np
+
+from .. import _lib
+from .loss import DeviceJoints, pack_joints
+from .targets import JointsGenerator
+from .transforms_utils import COCO_FLIP_INDEX
+
+MAX_STAGES = 4  # HH_TRAIN_MAX_STAGES
+# hh_train_desc of include/hhrnet.h (272 bytes)
+_TRAIN_DESC = np.dtype([("image_offset", "<i8"), ("mask_offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("flip", "<i4"), ("reserved", "<i4"),
+                        ("inv_image", "<f8", (6,)), ("inv_mask", "<f8", (MAX_STAGES, 6))])
+assert _TRAIN_DESC.itemsize == 272
+
+
+@dataclass
+class AugParams:
+    """One sample's augmentation: `scale` is the reference's `scale` after `*= aug_scale` (units of 200 px), `rot` in degrees,
+    `center` in raw-image pixels after the translation."""
+    scale: float
+    rot: float
+    center: tuple
+    flip: bool
+
+
+def affine_matrix(center, scale: float, res, rot: float = 0) -> np.ndarray:
+    """RandomAffineTransform._get_affine_matrix (transforms.py:95-119) -> 3x3 float64: raw pixels -> a res = (h, w) map that shows the
+    200 * scale px square around `center`, rotated by -rot degrees about the map's centre."""
+    side = 200 * scale
+    t = np.zeros((3, 3))
+    t[0, 0], t[1, 1], t[2, 2] = float(res[1]) / side, float(res[0]) / side, 1
+    t[0, 2] = res[1] * (-float(center[0]) / side + 0.5)
+    t[1, 2] = res[0] * (-float(center[1]) / side + 0.5)
+    if not rot == 0:
+        rad = -rot * np.pi / 180
+        sn, cs = np.sin(rad), np.cos(rad)
+        turn = np.array([[cs, -sn, 0], [sn, cs, 0], [0, 0, 1]])
+        to_origin = np.eye(3)
+        to_origin[0, 2], to_origin[1, 2] = -res[1] / 2, -res[0] / 2
+        back = to_origin.copy()
+        back[:2, 2] *= -1
+        t = np.dot(back, np.dot(turn, np.dot(to_origin, t)))
+    return t
+
+
+def affine_joints(xy: np.ndarray, mat: np.ndarray) -> np.ndarray:
+    """RandomAffineTransform._affine_joints (transforms.py:121-127): (x, y, 1) @ mat.T for every point."""
+    xy = np.array(xy, np.float64)
+    pts = xy.reshape(-1, 2)
+    return np.dot(np.concatenate((pts, pts[:, 0:1] * 0 + 1), axis=1), mat.T).reshape(xy.shape)
+
+
+def bump_table(sigma: float) -> tuple[np.ndarray, int]:
+    """The reference's `gauss` (coco.py:89-92) cast to fp32, and its reach 3 sigma + 1.  Sigmas the render kernel does not take
+    (3 sigma + 1 not an integer, more than 63 entries a side) raise HHError with hh_heatmap_table_size's message."""
+    n, reach = C.c_int(), C.c_int()
+    _lib.check(_lib.load().hh_heatmap_table_size(float(sigma), C.byref(n), C.byref(reach)))
+    grid = np.arange(0, 6 * sigma + 3, 1, float)
+    centre = 3 * sigma + 1
+    table = np.exp(-((grid[None, :] - centre) ** 2 + (grid[:, None] - centre) ** 2) / (2 * sigma ** 2)).astype(np.float32)
+    assert table.shape == (n.value, n.value)
+    return np.ascontiguousarray(table), reach.value
+
+
+class _Mode:
+    """One of the two pipelines of the reference's KeypointsTransform (`.train` / `.inference`, transforms.py:190-220): the ranges
+    its RandomAffineTransform draws from, and whether a flip is drawn."""
+
+    def __init__(self, owner: "TrainInput", max_rotation, min_scale, max_scale, max_translate, flip_p):
+        self.owner = owner
+        self.max_rotation, self.min_scale, self.max_scale, self.max_translate, self.flip_p = max_rotation, min_scale, max_scale, max_translate, flip_p
+
+    def draw(self, height: int, width: int) -> AugParams:
+        """transforms.py:137-153 then :65: np.random.random() for the scale, np.random.random() for the rotation, np.random.randint
+        twice when max_translate > 0, random.random() for the flip (train only)."""
+        center = np.array((width / 2, height / 2))
+        scale = (max if self.owner.scale_type == "long" else min)(height, width) / 200
+        scale *= np.random.random() * (self.max_scale - self.min_scale) + self.min_scale
+        rot = (np.random.random() * 2 - 1) * self.max_rotation
+        if self.max_translate > 0:
+            reach = int(self.max_translate * scale)
+            center[0] += np.random.randint(-reach, reach)
+            center[1] += np.random.randint(-reach, reach)
+        flip = self.flip_p is not None and random.random() < self.flip_p
+        return AugParams(float(scale), float(rot), (float(center[0]), float(center[1])), bool(flip))
+
+    def __call__(self, samples):
+        params = [self.draw(*np.asarray(s[0]).shape[:2]) for s in samples]
+        return self.owner.build(samples, params)
+
+
+class TrainInput:
+    """The reference's `KeypointsTransform(out_size, hm_resolutions, ...)` (transforms.py:175-220) together with the target
+    generators of its dataset (`num_kpts`, `sigma`: coco.py:185-219), on batches.
+
+        ti = TrainInput(512, [1 / 4, 1 / 2])
+        batch = ti.train(samples)        # samples: [(uint8 HWC image, bool HW crowd mask, float [P,K,3] joints), ...]
+        module.training_step(batch)
+
+    `.train(samples)` / `.inference(samples)` draw the augmentation per sample (inference: no rotation / scale / translate /
+    flip) and call `build(samples, params)`, the explicit-parameter entry."""
+
+    def __init__(self, out_size: int, hm_resolutions, max_rotation: int = 30, min_scale: float = 0.75, max_scale: float = 1.5,
+                 scale_type: str = "short", max_translate: int = 40, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
+                 num_kpts: int = 17, sigma: float = 2, flip_index=COCO_FLIP_INDEX, device="cuda:0"):
+        assert scale_type in ("short", "long"), f"unknown scale type: {scale_type}"
+        self.out_size, self.scale_type, self.num_kpts, self.device = int(out_size), scale_type, num_kpts, device
+        self.hm_sizes = [int(r * out_size) for r in hm_resolutions]
+        if not 0 < len(self.hm_sizes) <= MAX_STAGES:
+            raise _lib.HHError(f"TrainInput: 1..{MAX_STAGES} heatmap stages, got {len(self.hm_sizes)}")
+        self.mean, self.std = np.asarray(mean, np.float32), np.asarray(std, np.float32)
+        self.flip_index = list(flip_index)
+        self.sigmas = [s / 64 if sigma < 0 else sigma for s in self.hm_sizes]
+        self.tables = [bump_table(s) for s in self.sigmas]  # refuses a sigma the kernel does not take, before any GPU work
+        self.joints_generators = [JointsGenerator(s) for s in self.hm_sizes]
+        self.train = _Mode(self, max_rotation, min_scale, max_scale, max_translate, 0.5)
+        self.inference = _Mode(self, 0, 1, 1, 0, None)
+        self._tables_dev = None
+        self._stage = [None, None]       # pinned staging buffers ...
+        self._stage_free = [None, None]  # ... and the event behind the copy that last read each
+        self._turn = 0
+        self.last_h2d_bytes = self.last_launches = 0  # of the last build(): what tools/train_input_time.py reports
+
+    # ------------------------------------------------------------------ host half (no GPU)
+    def geometry(self, height: int, width: int, joints, p: AugParams):
+        """-> (image matrix 2x3, [stage matrix 2x3], [float joints [P,K,3] per stage], [int32 joints [P',K,3] per stage]): the matrices
+        of transforms.py:155-170, the joints after the affine (:165) and the flip (:69-70), and after JointsGenerator."""
+        joints = np.asarray(joints, np.float64).reshape(-1, self.num_kpts, 3)
+        mat_image = affine_matrix(p.center, p.scale, (self.out_size, self.out_size), p.rot)[:2]
+        mats, floats, ints = [], [], []
+        for size, gen in zip(self.hm_sizes, self.joints_generators):
+            mat = affine_matrix(p.center, p.scale, (size, size), p.rot)[:2]
+            j = joints.copy()
+            j[:, :, 0:2] = affine_joints(j[:, :, 0:2], mat)
+            if p.flip:
+                j = j[:, self.flip_index]
+                j[:, :, 0] = size - j[:, :, 0] - 1
+            mats.append(mat)
+            floats.append(j)
+            ints.append(gen(j))
+        return mat_image, mats, floats, ints
+
+    # ------------------------------------------------------------------ device half
+    def _staging(self, total: int):
+        import torch
+        t = self._turn
+        self._turn ^= 1
+        if self._stage[t] is None or self._stage[t].numel() < total:
+            # (a larger buffer replaces the old one; the old one stays alive until its copy has run: torch keeps pinned blocks
+            # that a non_blocking copy still reads)
+            self._stage[t] = torch.empty(total, dtype=torch.uint8).pin_memory()
+        elif self._stage_free[t] is not None:
+            self._stage_free[t].synchronize()  # the copy that last read this buffer has finished
+        return t, self._stage[t]
+
+    def build(self, samples, params):
+        """samples: [(uint8 [h,w,3] image, bool [h,w] crowd mask, float [P,K,3] joints)], params: [AugParams] ->
+        (images [B,3,S,S], [heatmaps [B,K,s,s]], [masks [B,s,s]], [DeviceJoints]) on the device, in the current stream."""
+        import torch
+        lib = _lib.load()
+        B, S, K, nst = len(samples), self.out_size, self.num_kpts, len(self.hm_sizes)
+        if B == 0 or len(params) != B:
+            raise ValueError("TrainInput.build: one AugParams per sample, at least one sample")
+        dp = C.POINTER(C.c_double)
+        invert = lambda m: self._invert(lib, m, dp)  # noqa: E731
+
+        shapes = []
+        for img, mask, _ in samples:
+            if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or mask.shape != img.shape[:2]:
+                raise ValueError("TrainInput.build: uint8 [h,w,3] images with [h,w] crowd masks only")
+            shapes.append(img.shape[:2])
+        sizes = [h * w * 3 for h, w in shapes] + [h * w for h, w in shapes]
+        offs = np.cumsum([0] + sizes)
+        desc_off = (int(offs[-1]) + 63) // 64 * 64  # the descriptors travel behind the pixels and masks, in the same copy
+        total = desc_off + _TRAIN_DESC.itemsize * B
+        turn, host = self._staging(total)
+        hview = host.numpy()
+        descs = hview[desc_off:total].view(_TRAIN_DESC)
+        stage_joints = [[] for _ in range(nst)]
+        for b, ((img, mask, joints), p) in enumerate(zip(samples, params)):
+            h, w = shapes[b]
+            np.copyto(hview[offs[b]:offs[b + 1]].reshape(h, w, 3), img)
+            mview = hview[offs[B + b]:offs[B + b + 1]].reshape(h, w)
+            np.multiply(mask, 255, out=mview, casting="unsafe")  # (mask * 255).astype(np.uint8), transforms.py:159
+            mat_image, mats, _, ints = self.geometry(h, w, joints, p)
+            inv_mask = np.zeros((MAX_STAGES, 6))
+            for i, m in enumerate(mats):
+                inv_mask[i] = invert(m)
+                stage_joints[i].append(ints[i])
+            descs[b] = (int(offs[b]), int(offs[B + b]), h, w, int(p.flip), 0, invert(mat_image), inv_mask)
+
+        dev = torch.device(self.device)
+        with torch.cuda.device(dev):
+            cur = torch.cuda.current_stream(dev)
+            raw = host[:total].to(dev, non_blocking=True)
+            copied = torch.cuda.Event()
+            copied.record(cur)
+            self._stage_free[turn] = copied
+            self.last_h2d_bytes, self.last_launches = total, 2 + nst
+            if self._tables_dev is None:
+                self._tables_dev = [torch.from_numpy(t).to(dev) for t, _ in self.tables]
+            images = torch.empty((B, 3, S, S), device=dev, dtype=torch.float32)
+            masks = [torch.empty((B, s, s), device=dev, dtype=torch.float32) for s in self.hm_sizes]
+            heatmaps = [torch.empty((B, K, s, s), device=dev, dtype=torch.float32) for s in self.hm_sizes]
+            fp = C.POINTER(C.c_float)
+            base, stream = raw.data_ptr(), cur.cuda_stream
+            _lib.check(lib.hh_train_images_u8_batch(base, base + desc_off, B, images.data_ptr(), S, S, self.mean.ctypes.data_as(fp),
+                                                    self.std.ctypes.data_as(fp), stream))
+            stage_hw = (C.c_int * (2 * nst))(*[s for s in self.hm_sizes for _ in range(2)])
+            outs = (C.c_void_p * nst)(*[m.data_ptr() for m in masks])
+            _lib.check(lib.hh_train_masks_u8_batch(base, base + desc_off, B, nst, stage_hw, outs, stream))
+            device_joints = []
+            for i, s in enumerate(self.hm_sizes):
+                packed, counts = pack_joints(stage_joints[i], K, s, s)
+                self.last_h2d_bytes += packed.nbytes + counts.nbytes
+                dj = DeviceJoints(torch.from_numpy(packed).to(dev), torch.from_numpy(counts).to(dev))
+                table, reach = self._tables_dev[i], self.tables[i][1]
+                _lib.check(lib.hh_render_heatmaps(dj.packed.data_ptr(), dj.counts.data_ptr(), B, packed.shape[1], K, table.data_ptr(),
+                                                  table.shape[0], reach, heatmaps[i].data_ptr(), s, s, stream))
+                device_joints.append(dj)
+        return images, heatmaps, masks, device_joints
+
+    @staticmethod
+    def _invert(lib, m, dp) -> np.ndarray:
+        fwd = np.ascontiguousarray(np.asarray(m, np.float64).reshape(6))
+        inv = np.empty(6, np.float64)
+        _lib.check(lib.hh_invert_affine(fwd.ctypes.data_as(dp), inv.ctypes.data_as(dp)))
+        return inv

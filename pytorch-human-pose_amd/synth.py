@@ -156,6 +156,30 @@ def synth_train_targets(batch: int, num_kpts: int, input_size: int, people, seed
     return hms, masks, joints
 
 
+def synth_train_sample(height: int, width: int, people: int, seed: int = 0, num_kpts: int = 17, holes: int = 2):
+    """One raw training sample as the reference's dataset hands it to its transform (coco.py:294-298,464-467): uint8 RGB image
+    [h,w,3] (smooth gradients + noise, so that a wrong warp tap shows), bool crowd mask [h,w] (False inside `holes` rectangles;
+    holes = -1: all False) and float joints [P,K,3] = x, y, visibility 0 / 1 / 2 in raw pixels (whole numbers like COCO's, some
+    outside the image on purpose)."""
+    rs = np.random.RandomState(880001 + seed)
+    yy, xx = np.mgrid[0:height, 0:width]
+    img = np.stack([(xx * 3 + yy) % 256, (yy * 5 + xx // 2) % 256, (xx + yy * 2) // 3 % 256], -1) + rs.randint(-20, 21, (height, width, 3))
+    img = np.clip(img, 0, 255).astype(np.uint8)
+    mask = np.ones((height, width), bool)
+    if holes < 0:
+        mask[:] = False
+    for _ in range(max(holes, 0)):
+        y0, x0 = rs.randint(0, height * 3 // 4), rs.randint(0, width * 3 // 4)
+        mask[y0:y0 + rs.randint(4, height // 2), x0:x0 + rs.randint(4, width // 2)] = False
+    joints = np.zeros((people, num_kpts, 3))
+    cx, cy = rs.uniform(0.05, 0.95, people) * width, rs.uniform(0.05, 0.95, people) * height
+    for p in range(people):
+        joints[p, :, 0] = np.round(cx[p] + rs.normal(0, width / 8, num_kpts))
+        joints[p, :, 1] = np.round(cy[p] + rs.normal(0, height / 8, num_kpts))
+        joints[p, :, 2] = (rs.uniform(size=num_kpts) < 0.8) * rs.randint(1, 3, num_kpts)
+    return img, mask, joints
+
+
 def synth_train_preds(hms, seed: int = 0):
     """Predictions for a loss test: target heatmaps + N(0, 0.1) per stage, tags ~ N(0, 1) at the 1/4 stage."""
     rs = np.random.RandomState(9000 + seed)
