@@ -350,6 +350,30 @@ int hh_bn_train_backward_apply(const void *x, const void *y, const void *dy, int
 int hh_resize_accumulate(const float *src, int64_t src_bstride, int B, int K, int h, int w, float *dst, int64_t dst_bstride, int H,
                          int W, float weight, int init, void *stream);
 
+/* The whole aggregation of that test as ONE launch (csrc/tta_aggregate.hip; the batched caller is
+ * InferenceKeypointsModel.infer_images(scales=...); an extension like hh_resize_accumulate, no reference precedent).
+ * For every (b,k,y,x) of dst [B,K,H,W] and the sources i = 0 .. nsrc-1 in the order given:
+ *   tap_i(r,c) = hm_i[b,k,r,c]                                                     (hm_flipped NULL), or
+ *              = (hm_i[b,k,r,c] + hm_flipped_i[b,perm[k],r,w_i-1-c]) / 2.0f       (hh_flip_merge's expression),
+ *   v_i = weight_i * bilinear(tap_i -> HxW)(y,x)   (hh_resize_accumulate's arithmetic),  acc = v_0, then acc = acc + v_i,
+ * every step rounded on its own; dst = acc is written and never read, the elements between K*H*W and dst_bstride are left alone.
+ * The result equals hh_flip_merge on each flipped source followed by hh_resize_accumulate(init = (i == 0)) per source bit for
+ * bit, without a merged map or a partial sum in memory.  `srcs_host` and `perm_host` are HOST arrays, copied into the launch's
+ * arguments (perm_host may be NULL when no source is flipped).  Non-zero (nothing launched) for nsrc outside 1..8, K outside
+ * 1..64, a NULL srcs_host / dst / hm, non-positive sizes, dst_bstride < K*H*W or a source batch stride < K*h*w.
+ * (Additive entry point: HH_ABI_VERSION stays 3.)                                                                        */
+#define HH_MAX_SCALE_SRCS 8
+typedef struct hh_scale_src {
+    const float *hm;          /* [B,K,h,w] heatmaps of one scale pass, batch stride in elements */
+    long long bstride;
+    const float *hm_flipped;  /* the flipped pass's maps (same h,w), or NULL: no flip merge for this source */
+    long long flipped_bstride;
+    int h, w;
+    float weight;
+} hh_scale_src;
+int hh_multi_scale_aggregate(const hh_scale_src *srcs_host, int nsrc, const int32_t *perm_host, int B, int K, float *dst,
+                             int64_t dst_bstride, int H, int W, void *stream);
+
 /* Candidates of the last hh_decode/hh_parse call (MPPEHeatmapParser.top_k, grouping.py:147-170),
  * copied to host: tags_k [B,K,max_people,E], coords_k [B,K,max_people,2] (x,y), scores_k [B,K,max_people].
  * Synchronous; for parity tests.  Needs the exhaustive candidate lists: hh_decoder_set_exact_topk(dec, 1) before the decode. */

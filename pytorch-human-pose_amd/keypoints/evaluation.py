@@ -36,15 +36,17 @@ def evaluate_images(model, images, image_ids, rank: int = 0, world_size: int = 1
     """evaluate_dataset (bin/eval.py:18-49) over in-memory images, sharded by image across ranks (§8e: contiguous
     slices, no data-path collective; the packed lists are gathered to rank 0, other ranks get None).
     `multi_scale` = tuple of scales -> `model.call_multi_scale` (the cfg-4 extension) instead of `model(...)`.
-    `batch` > 1 routes the single-scale case through `model.infer_images` (identical per-image results, one forward and one
-    decode per shape bucket); `batch` = 1 is the reference's image-by-image loop."""
+    `batch` > 1 routes both cases through `model.infer_images` (identical per-image results, one forward and one decode per
+    shape bucket; with `multi_scale`, `infer_images(scales=multi_scale)`: the forwards of plan_multi_scale and one fused
+    aggregation per stage); `batch` = 1 is the reference's image-by-image loop."""
     local = []
     mine = list(shard_range(len(images), rank, world_size))
-    if multi_scale or batch <= 1:
+    if batch <= 1:
         for idx in mine:
             res = model.call_multi_scale(images[idx], None, multi_scale) if multi_scale else model(images[idx], None)
             local += pack_coco_results(image_ids[idx], res.kpts_coords, res.obj_scores)
     else:  # batched behind the same per-image results: shape buckets of up to `batch` images per forward + decode
-        for idx, res in zip(mine, model.infer_images([images[i] for i in mine], max_batch=batch)):
+        kw = {"scales": multi_scale} if multi_scale else {}
+        for idx, res in zip(mine, model.infer_images([images[i] for i in mine], max_batch=batch, **kw)):
             local += pack_coco_results(image_ids[idx], res.kpts_coords, res.obj_scores)
     return gather_results(local)

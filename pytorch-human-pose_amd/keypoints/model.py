@@ -164,6 +164,51 @@ class KeypointsModule:
 _IMAGE_DESC = np.dtype([("offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("inv", "<f8", (6,))])
 
 
+# hh_scale_src of include/hhrnet.h (48 bytes): one source of hh_multi_scale_aggregate
+class _ScaleSrc(C.Structure):
+    _fields_ = [("hm", C.c_void_p), ("bstride", C.c_longlong), ("hm_flipped", C.c_void_p), ("flipped_bstride", C.c_longlong),
+                ("h", C.c_int), ("w", C.c_int), ("weight", C.c_float)]
+
+
+class _Shape:
+    """What get_multi_scale_size reads of an image: its shape."""
+
+    def __init__(self, h: int, w: int):
+        self.shape = (int(h), int(w))
+
+
+def plan_multi_scale(shapes, input_size: int, scales, max_batch: int) -> list[dict]:
+    """Host plan of the batched multi-scale test (pure arithmetic, no device): raw image shapes [(h, w), ...] -> chunks, each
+    {"images": indices into `shapes`, "sizes": the (w, h) of the model input at every scale, "sub_batches": per scale the
+    consecutive (lo, hi) ranges of the chunk that run as one forward}; all three follow the order of `scales`, which is the
+    accumulation order of `multi_scale_maps`.
+    Buckets: images whose model-input sizes agree at EVERY scale (get_multi_scale_size truncates per scale, so the scale-1 size
+    alone need not fix the others).  Chunks: at most `max_batch` images of a bucket.  Sub-batches at scale s: n_s =
+    min(len(chunk), max(1, max_batch * h_1*w_1 // (h_s*w_s))) images, so that no forward carries more input pixels than the
+    scale-1 forward of `max_batch` images that the single-scale path runs."""
+    scales = tuple(scales)
+    if 1.0 not in scales:
+        raise ValueError("plan_multi_scale: scales must contain 1.0 (the scale-1 pass provides the tags and the output geometry)")
+    if max_batch < 1:
+        raise ValueError("plan_multi_scale: max_batch must be >= 1")
+    mn = min(scales)
+    buckets: dict[tuple, list[int]] = {}
+    for i, (h, w) in enumerate(shapes):
+        key = tuple(tuple(get_multi_scale_size(_Shape(h, w), input_size, s, mn)[0]) for s in scales)
+        buckets.setdefault(key, []).append(i)
+    plan = []
+    for sizes, idxs in buckets.items():
+        w1, h1 = sizes[scales.index(1.0)]
+        for lo in range(0, len(idxs), max_batch):
+            chunk = idxs[lo:lo + max_batch]
+            subs = []
+            for (ws, hs) in sizes:
+                n_s = min(len(chunk), max(1, max_batch * h1 * w1 // (hs * ws)))
+                subs.append([(a, min(a + n_s, len(chunk))) for a in range(0, len(chunk), n_s)])
+            plan.append({"images": chunk, "sizes": sizes, "sub_batches": subs})
+    return plan
+
+
 class InferenceKeypointsModel:
     limbs = COCO_LIMBS
 
@@ -257,6 +302,65 @@ class InferenceKeypointsModel:
         self._keep_raw = raw
         return x, center, scale
 
+    def _forward_with_mirror(self, x: Tensor) -> tuple[Tensor, Tensor]:
+        """forward_raw of the images [:B] and their mirror images [B:] (model.py:85-86), nothing merged yet."""
+        B, _, H, W = x.shape
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        # the images and their mirror images as ONE batch of 2B: images of a batch are independent (same bits as two passes), and
+        # a forward costs ~2 ms of launch structure whatever the batch -- a single image is a chain of ~350 dependent launches
+        x2 = torch.empty((2 * B, 3, H, W), device=x.device, dtype=x.dtype)
+        x2[:B].copy_(x)
+        _lib.check(self._lib.hh_flip_images(x.data_ptr(), x2[B:].data_ptr(), B, 3, H, W, stream))
+        return self.net.forward_raw(x2)
+
+    @torch.no_grad()
+    def _multi_scale_maps_batch(self, scales: tuple, sub_batches: list, x1: Tensor, prepare) -> tuple[list[Tensor], list[Tensor]]:
+        """multi_scale_maps for the images of one chunk (plan_multi_scale): `x1` = their scale-1 model inputs [n,3,h,w],
+        `prepare(si)` = their inputs at scales[si].  Every scale runs its sub-batches as forwards of their own; the scale-1 pass is
+        forward_tta as it stands (its hh_flip_merge stays: the tags come from this pass, and its merged maps enter the aggregation
+        as plain sources), the other scales' flipped passes are merged inside hh_multi_scale_aggregate.  One aggregation launch
+        per stage and per image range between two sub-batch boundaries of any scale.  -> ([hm_1/4, hm_1/2] averaged, tags)."""
+        K = self.net.num_kpts
+        n, _, h, w = x1.shape
+        i1 = scales.index(1.0)
+        parts: list = []  # per scale: (lo, hi, (stage-0 maps, their flipped pass or None), (stage-1 maps, ...)) per sub-batch
+        tags = None
+        for si in range(len(scales)):
+            xs = x1 if si == i1 else prepare(si)
+            per = []
+            for lo, hi in sub_batches[si]:
+                xb = xs[lo:hi]
+                if si == i1:
+                    assert (lo, hi) == (0, n), "the plan runs the scale-1 pass of a chunk as one forward"
+                    hms, tags = self.forward_tta(xb)
+                    per.append((lo, hi, (hms[0], None), (hms[1], None)))
+                elif not self.use_flip:
+                    init, dec = self.net.forward_raw(xb)
+                    per.append((lo, hi, (init, None), (dec, None)))
+                else:
+                    init2, dec2 = self._forward_with_mirror(xb)
+                    per.append((lo, hi, (init2[:hi - lo], init2[hi - lo:]), (dec2[:hi - lo], dec2[hi - lo:])))
+            parts.append(per)
+        acc = [torch.empty((n, K, h // 4, w // 4), device=x1.device, dtype=torch.float32),
+               torch.empty((n, K, h // 2, w // 2), device=x1.device, dtype=torch.float32)]
+        stream = torch.cuda.current_stream(x1.device).cuda_stream
+        wgt = 1.0 / len(scales)
+        cuts = sorted({lo for per in parts for lo, _, _, _ in per} | {n})
+        table = (_ScaleSrc * len(scales))()
+        with torch.cuda.device(x1.device):
+            for a, b in zip(cuts[:-1], cuts[1:]):
+                for st in range(2):
+                    for si, per in enumerate(parts):
+                        lo, _, *stages = next(p for p in per if p[0] <= a < p[1])
+                        hm, hmf = stages[st]  # [*, >=K, h_s, w_s]: the heatmaps are the first K channels
+                        table[si] = _ScaleSrc(hm.data_ptr() + 4 * (a - lo) * hm.stride(0), hm.stride(0),
+                                              hmf.data_ptr() + 4 * (a - lo) * hmf.stride(0) if hmf is not None else None,
+                                              hmf.stride(0) if hmf is not None else 0, hm.shape[2], hm.shape[3], wgt)
+                    dst = acc[st][a:b]
+                    _lib.check(self._lib.hh_multi_scale_aggregate(table, len(scales), self._perm.ctypes.data, b - a, K, dst.data_ptr(),
+                                                                  dst.stride(0), dst.shape[2], dst.shape[3], stream))
+        return acc, tags
+
     @torch.no_grad()
     def forward_tta(self, x: Tensor) -> tuple[list[Tensor], list[Tensor]]:
         """model.py:79-94 on a batch [B,3,h,w]: net forward (+ flipped pass, un-flip, joint permutation,
@@ -267,12 +371,7 @@ class InferenceKeypointsModel:
             return [init[:, :K], dec], [init[:, K:]]
         B, _, H, W = x.shape
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        # the images and their mirror images as ONE batch of 2B: images of a batch are independent (same bits as two passes), and
-        # a forward costs ~2 ms of launch structure whatever the batch -- a single image is a chain of ~350 dependent launches
-        x2 = torch.empty((2 * B, 3, H, W), device=x.device, dtype=x.dtype)
-        x2[:B].copy_(x)
-        _lib.check(self._lib.hh_flip_images(x.data_ptr(), x2[B:].data_ptr(), B, 3, H, W, stream))
-        init2, dec2 = self.net.forward_raw(x2)
+        init2, dec2 = self._forward_with_mirror(x)
         init, init_f, dec, dec_f = init2[:B], init2[B:], dec2[:B], dec2[B:]
         tags2 = torch.empty((B, K, H // 4, W // 4), device=x.device, dtype=torch.float32)
         hq, wq = H // 4, W // 4
@@ -315,20 +414,38 @@ class InferenceKeypointsModel:
         return size, center, scale, self._dst_to_src(size, center, scale)
 
     @torch.no_grad()
-    def infer_images(self, raw_images: list[np.ndarray], annots: list | None = None, max_batch: int = 32) -> list[InferenceKeypointsResult]:
+    def infer_images(self, raw_images: list[np.ndarray], annots: list | None = None, max_batch: int = 32,
+                     scales=None) -> list[InferenceKeypointsResult]:
         """The batched path behind the reference's single-image interface (`__call__` per image, bin/eval.py:18-49): images are
         bucketed by model-input shape, every bucket runs as batches of up to `max_batch` -- ONE host->device copy of the raw
         uint8 pixels, hh_preprocess_u8 per image into one [B,3,h,w] tensor, one (flip-TTA) forward, one hh_decode, one
         device->host copy of the small result arrays -- and every image gets the result `self(image, annot)` returns
-        (same kernels on the same per-image data: images of a batch are independent)."""
+        (same kernels on the same per-image data: images of a batch are independent).
+        `scales` = tuple of scales: the multi-scale test of `call_multi_scale(image, annot, scales)` for every image, batched the
+        same way (plan_multi_scale: buckets by the sizes at every scale, chunks of up to `max_batch`): the raw pixels still cross
+        once, with one descriptor block per scale behind them; one hh_preprocess_u8_batch per scale, the forwards of the plan, one
+        hh_multi_scale_aggregate per stage (and image range) instead of the per-scale flip merges and accumulations, one
+        hh_decode on the averaged maps and the scale-1 tags."""
         n = len(raw_images)
         annots = annots if annots is not None else [None] * n
         # (size, center, scale) now -- the bucket key --, the warp matrix when the image's batch is staged: the first batch should
         # not wait for n matrix inversions
-        geo: list = [get_multi_scale_size(img, self.input_size, 1, 1) for img in raw_images]
-        buckets: dict[tuple, list[int]] = {}
-        for i, g in enumerate(geo):
-            buckets.setdefault(tuple(g[0]), []).append(i)
+        if scales is None:
+            pass_scales, mn = (1,), 1
+            geo: list = [get_multi_scale_size(img, self.input_size, 1, 1) for img in raw_images]
+            buckets: dict[tuple, list[int]] = {}
+            for i, g in enumerate(geo):
+                buckets.setdefault(tuple(g[0]), []).append(i)
+            jobs = {(size,): [(idxs[lo:lo + max_batch], None) for lo in range(0, len(idxs), max_batch)] for size, idxs in buckets.items()}
+        else:
+            pass_scales = tuple(scales)
+            plan = plan_multi_scale([img.shape[:2] for img in raw_images], self.input_size, pass_scales, max_batch)
+            mn = min(pass_scales)
+            geo = [get_multi_scale_size(img, self.input_size, 1.0, mn) for img in raw_images]  # the un-warp is the scale-1 pass's
+            jobs = {}
+            for c in plan:
+                jobs.setdefault(c["sizes"], []).append((c["images"], c["sub_batches"]))
+        i1 = pass_scales.index(1)
         results: list = [None] * n
         mean, std = IMAGENET_MEAN.ctypes.data_as(C.POINTER(C.c_float)), IMAGENET_STD.ctypes.data_as(C.POINTER(C.c_float))
 
@@ -351,13 +468,13 @@ class InferenceKeypointsModel:
         stage_free: list = [None, None]
         pending = None
         turn = 0
-        for (w, h), idxs in buckets.items():
-            for lo in range(0, len(idxs), max_batch):
-                chunk = idxs[lo:lo + max_batch]
-                sizes = [raw_images[i].size for i in chunk]
-                offs = np.cumsum([0] + sizes)
+        for sizes, chunks in jobs.items():
+            for chunk, subs in chunks:
+                w, h = sizes[i1]
+                nb = len(chunk)
+                offs = np.cumsum([0] + [raw_images[i].size for i in chunk])
                 desc_off = (int(offs[-1]) + 63) // 64 * 64  # the image descriptors travel behind the pixels, in the same copy
-                total = desc_off + 64 * len(chunk)
+                total = desc_off + 64 * nb * len(sizes)  # (one block of them per scale)
                 if stage[turn] is None or stage[turn].numel() < total:
                     stage[turn] = torch.empty(total, dtype=torch.uint8).pin_memory()
                 elif stage_free[turn] is not None:
@@ -368,7 +485,9 @@ class InferenceKeypointsModel:
                 for j, i in enumerate(chunk):
                     img = raw_images[i]
                     np.copyto(hview[offs[j]:offs[j + 1]].reshape(img.shape), img, casting="same_kind")
-                    descs[j] = (int(offs[j]), img.shape[0], img.shape[1], self._dst_to_src(*geo[i]).reshape(6))
+                    for si, s in enumerate(pass_scales):
+                        g = geo[i] if si == i1 else get_multi_scale_size(img, self.input_size, s, mn)
+                        descs[si * nb + j] = (int(offs[j]), img.shape[0], img.shape[1], self._dst_to_src(*g).reshape(6))
 
                 # host -> device on a copy stream of its own, so that the pixels of this batch cross PCIe while the previous
                 # batch still computes (25 MB per batch of 32 512x512 images: ~1.7 ms that would otherwise sit on the compute stream)
@@ -381,15 +500,21 @@ class InferenceKeypointsModel:
                     copied = torch.cuda.Event()
                     copied.record()
 
-                def run(chunk=chunk, raw=raw, copied=copied, desc_off=desc_off, w=w, h=h, turn=turn):
+                def run(chunk=chunk, raw=raw, copied=copied, desc_off=desc_off, w=w, h=h, turn=turn, nb=nb, sizes=sizes, subs=subs):
                     cur = torch.cuda.current_stream(self.device)
                     cur.wait_event(copied)
                     raw.record_stream(cur)
-                    x = torch.empty((len(chunk), 3, h, w), device=self.device, dtype=torch.float32)
-                    with torch.cuda.device(x.device):  # one launch for the whole batch, whatever the raw sizes
-                        _lib.check(self._lib.hh_preprocess_u8_batch(raw.data_ptr(), raw.data_ptr() + desc_off, len(chunk), x.data_ptr(),
-                                                                    h, w, mean, std, cur.cuda_stream))
-                    hms, tags = self.forward_tta(x)
+
+                    def prepare(si):
+                        ws, hs = sizes[si]
+                        xs = torch.empty((nb, 3, hs, ws), device=self.device, dtype=torch.float32)
+                        with torch.cuda.device(xs.device):  # one launch for the whole batch, whatever the raw sizes
+                            _lib.check(self._lib.hh_preprocess_u8_batch(raw.data_ptr(), raw.data_ptr() + desc_off + 64 * nb * si, nb,
+                                                                        xs.data_ptr(), hs, ws, mean, std, cur.cuda_stream))
+                        return xs
+
+                    x = prepare(i1)
+                    hms, tags = self.forward_tta(x) if subs is None else self._multi_scale_maps_batch(pass_scales, subs, x, prepare)
                     out = self._parser.decode_batch_device(hms[0], hms[1], tags, adjust=True, refine=True)
                     # device -> host into pinned buffers kept per pipeline slot (allocating pinned memory costs ~0.4 ms per array);
                     # finish() of this slot's previous batch ran before this point and copied what it keeps
