@@ -266,6 +266,21 @@ int hh_render_heatmaps(const int32_t *joints, const int32_t *num_people, int B, 
  * by keypoints/train_net.py with torch autograd as the tape.  Activations are NHWC bf16 [B,H,W,C] (= torch channels_last),
  * parameters fp32, all device pointers.
  *
+ * Element type.  Every entry point below that reads or writes an activation (or a packed weight set) has a second form with the
+ * suffix _dt, whose first argument `act_dtype` is HH_ACT_BF16 or HH_ACT_F16: the 16-bit format of ALL activation tensors of that
+ * call, of the packed weights, and the MFMA form that multiplies them (the reference trains under fp16 autocast with a GradScaler,
+ * keypoints/module.py:43-71).  The unsuffixed function is its _dt form with HH_ACT_BF16.  Any other value returns 1 with
+ * hh_last_error set, before anything is launched.  Workspace, element-count and plan functions do not depend on the type.
+ * fp16 semantics (HH_ACT_F16):
+ *   - every store rounds to nearest even;
+ *   - a value beyond +-65504 becomes +-inf.  It is NOT saturated: the loss scaler detects an oversized scale by it;
+ *   - NaN / inf in a gradient tensor reach the data gradient and the fp32 weight, gamma and beta gradients as non-finite values
+ *     (an exception by construction: an element the ReLU mask zeroes carries nothing, whatever it held);
+ *   - subnormals are kept by every store and every fp32 <-> fp16 conversion (the kernels are compiled in the default mode).
+ *     Whether the f16 MFMA honours subnormal A / B INPUTS on gfx950 is decided by the subnormal case of
+ *     tests/test_gpu_train_f16_lattice.py; INTEGRATION.md records the outcome.
+ * (Additive entry points: HH_ABI_VERSION stays 3.)
+ *
  * hh_conv2d: y = act(conv(x, w) + bias (+ res)) with the CURRENT fp32 weights w [cout][cin][ks][ks] (packed on the device
  *   each call), ks in {1,2,3} (2x2: stride 1), stride in {1,2}; pad_y / pad_x = top / left zero padding, -1 = (ks-1)/2
  *   (the output keeps the input size at stride 1, so a 2x2 kernel with pad 0 pads bottom/right instead).  mode 1 = data gradient of the stride-1 conv with these
@@ -283,6 +298,8 @@ int hh_render_heatmaps(const int32_t *joints, const int32_t *num_people, int B, 
  * hh_conv2d_wgrad: dw [cout][cin][ks][ks] fp32 = dL/dW of y = conv(x, W) (padding (ks-1)/2) from x [B,H,W,cin] and
  *   dy [B,Ho,Wo,cout]; 3x3 stride 1/2 and 1x1 stride 1, channel counts % 8 == 0.  A GEMM contracted over pixels on MFMA
  *   (operands read from LDS with the transposing ds_read_b64_tr_b16), partial sums reduced in a fixed order.          */
+#define HH_ACT_BF16 0
+#define HH_ACT_F16 1
 int64_t hh_conv2d_workspace_bytes(int cin, int cout, int ks, int mode);
 /* What would run, as host arithmetic alone (no device call; the selection code of the launches themselves):
  *   hh_conv2d_config: the index (see hh_conv_config) of the instantiation hh_conv2d / hh_conv2d_packed launch for these
@@ -296,25 +313,41 @@ int hh_conv2d_wgrad_plan(int B, int H, int W, int cin, int cout, int ks, int str
 int64_t hh_conv2d_wgrad_workspace_bytes(int B, int H, int W, int cin, int cout, int ks, int stride);
 int hh_conv2d_wgrad(const void *x, const void *dy, int B, int H, int W, int cin, int cout, int ks, int stride, int pad_y, int pad_x, float *dw,
                     void *workspace, void *stream);
+int hh_conv2d_wgrad_dt(int act_dtype, const void *x, const void *dy, int B, int H, int W, int cin, int cout, int ks, int stride, int pad_y,
+                       int pad_x, float *dw, void *workspace, void *stream);
 int hh_conv2d(const void *x, int B, int H, int W, int cin, const float *w, int cout, int ks, int stride, int mode, int pad_y, int pad_x,
               const float *bias, const void *res, int relu, void *y, void *workspace, void *stream);
+int hh_conv2d_dt(int act_dtype, const void *x, int B, int H, int W, int cin, const float *w, int cout, int ks, int stride, int mode, int pad_y,
+                 int pad_x, const float *bias, const void *res, int relu, void *y, void *workspace, void *stream);
 /* The same convolution with weights packed ahead of it.  A training step packs ~700 weight sets (forward layout and
  * data-gradient layout of every conv); as separate launches that is ~700 tiny dependent kernels whose launch gaps cost more
  * than the packing.  hh_pack_conv_weights_batch packs n weight sets in ONE launch: w[i] fp32 [cout][cin][ks][ks] (device
  * pointers in a HOST array), packed[i] device buffers of hh_conv2d_packed_elems(cin, cout, ks, stride, mode) bf16 elements,
  * shapes host int32 [n][5] = cout, cin, ks, stride, mode (modes as in hh_conv2d), descs_dev a device scratch of
  * n * 4 * 64 bytes.  hh_conv2d_packed = hh_conv2d on such a buffer (bias NULL or a multiple of 32 long).  The packed copy
- * is valid until the fp32 weights change (the optimizer step).                                                            */
+ * is valid until the fp32 weights change (the optimizer step).  hh_pack_conv_weights_batch_dt: act_dtype is the format of all n
+ * packed buffers of the call (16-bit elements either way); hh_conv2d_packed_dt must be given the dtype they were packed with.    */
 int64_t hh_conv2d_packed_elems(int cin, int cout, int ks, int stride, int mode);
 int hh_pack_conv_weights_batch(int n, const float *const *w, void *const *packed, const int32_t *shapes, void *descs_dev, void *stream);
+int hh_pack_conv_weights_batch_dt(int act_dtype, int n, const float *const *w, void *const *packed, const int32_t *shapes, void *descs_dev,
+                                  void *stream);
 int hh_conv2d_packed(const void *x, int B, int H, int W, int cin, const void *w_packed, int cout, int ks, int stride, int mode, int pad_y,
                      int pad_x, const float *bias, const void *res, int relu, void *y, void *stream);
+int hh_conv2d_packed_dt(int act_dtype, const void *x, int B, int H, int W, int cin, const void *w_packed, int cout, int ks, int stride, int mode,
+                        int pad_y, int pad_x, const float *bias, const void *res, int relu, void *y, void *stream);
 int hh_bn_train_forward(const void *x, int64_t P, int C, const float *gamma, const float *beta, float eps, const void *res, int relu,
                         void *y, float *mean, float *invstd, double *scratch, void *stream);
 int hh_bn_train_backward(const void *x, const void *y, const void *dy, int64_t P, int C, const float *mean, const float *invstd,
                          const float *gamma, int relu, void *dx, void *dres, float *dgamma, float *dbeta, double *scratch, void *stream);
 int hh_bn_train_backward_plain(const void *x, const void *dy, int64_t P, int C, const float *mean, const float *invstd, const float *gamma,
                                const float *beta, int relu, void *dx, float *dgamma, float *dbeta, double *scratch, void *stream);
+int hh_bn_train_forward_dt(int act_dtype, const void *x, int64_t P, int C, const float *gamma, const float *beta, float eps, const void *res,
+                           int relu, void *y, float *mean, float *invstd, double *scratch, void *stream);
+int hh_bn_train_backward_dt(int act_dtype, const void *x, const void *y, const void *dy, int64_t P, int C, const float *mean, const float *invstd,
+                            const float *gamma, int relu, void *dx, void *dres, float *dgamma, float *dbeta, double *scratch, void *stream);
+int hh_bn_train_backward_plain_dt(int act_dtype, const void *x, const void *dy, int64_t P, int C, const float *mean, const float *invstd,
+                                  const float *gamma, const float *beta, int relu, void *dx, float *dgamma, float *dbeta, double *scratch,
+                                  void *stream);
 
 /* FusionLayer's sum in the training step (hrnet.py:214-229: `sum_j f_ij(x_j)` then ReLU, with nn.Upsample(nearest) on the
  * low-resolution terms, hrnet.py:200-205): out = act(sum_j term_j[b, y >> shift_j, x >> shift_j, :]) over 1..4 NHWC bf16
@@ -324,6 +357,10 @@ int hh_bn_train_backward_plain(const void *x, const void *dy, int64_t P, int C, 
 int hh_fusion_sum_forward(const void *const *terms, const int *shifts, int nterms, int B, int H, int W, int C, int relu, void *out, void *stream);
 int hh_fusion_sum_backward(const void *dy, const void *out, int relu, int B, int H, int W, int C, void *g, void *const *dup, const int *up_shift,
                            int nup, void *stream);
+int hh_fusion_sum_forward_dt(int act_dtype, const void *const *terms, const int *shifts, int nterms, int B, int H, int W, int C, int relu, void *out,
+                             void *stream);
+int hh_fusion_sum_backward_dt(int act_dtype, const void *dy, const void *out, int relu, int B, int H, int W, int C, void *g, void *const *dup,
+                              const int *up_shift, int nup, void *stream);
 
 /* SyncBatchNorm (src/base/model.py:42-44: `to_DDP(..., use_batchnorm=True)` converts every BatchNorm2d, the reference
  * trainer's default, trainer.py:44,253; experiments/keypoints/higher_hrnet_32.yaml:17 turns it off): the two passes above split around their one exchange step.
@@ -343,6 +380,14 @@ int hh_bn_train_backward_stats(const void *x, const void *y, const void *dy, int
 int hh_bn_train_backward_apply(const void *x, const void *y, const void *dy, int64_t P, int C, const float *mean, const float *invstd,
                                const float *gamma, int relu, const double *sums, double count, void *dx, void *dres, double *scratch,
                                void *stream);
+int hh_bn_train_stats_dt(int act_dtype, const void *x, int64_t P, int C, double *sums, double *scratch, void *stream);
+int hh_bn_train_normalize_dt(int act_dtype, const void *x, int64_t P, int C, const double *sums, double count, const float *gamma,
+                             const float *beta, float eps, const void *res, int relu, void *y, float *mean, float *invstd, void *stream);
+int hh_bn_train_backward_stats_dt(int act_dtype, const void *x, const void *y, const void *dy, int64_t P, int C, const float *mean,
+                                  const float *invstd, int relu, double *sums, float *dgamma, float *dbeta, double *scratch, void *stream);
+int hh_bn_train_backward_apply_dt(int act_dtype, const void *x, const void *y, const void *dy, int64_t P, int C, const float *mean,
+                                  const float *invstd, const float *gamma, int relu, const double *sums, double count, void *dx, void *dres,
+                                  double *scratch, void *stream);
 
 /* Multi-scale test-time augmentation (BASELINE.json configs[3]; an extension: the reference only calls its resize helper
  * with scale 1, keypoints/model.py:73): dst[B,K,H,W] (+)= weight * bilinear(src[B,K,h,w] -> HxW) with the arithmetic of

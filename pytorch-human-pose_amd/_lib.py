@@ -20,6 +20,9 @@ class HHError(RuntimeError):
     pass
 
 
+ACT_BF16, ACT_F16 = 0, 1  # HH_ACT_BF16 / HH_ACT_F16 of include/hhrnet.h: the act_dtype of the *_dt training entry points
+
+
 def build(force: bool = False, jobs: int = 8) -> str:
     args = ["make", "-C", CSRC, f"-j{jobs}"]
     if force:
@@ -103,6 +106,20 @@ def _sig(lib):
         "hh_bn_train_normalize": (i32, [vp, i64, i32, vp, dbl, vp, vp, C.c_float, vp, i32, vp, vp, vp, vp]),
         "hh_bn_train_backward_stats": (i32, [vp, vp, vp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
         "hh_bn_train_backward_apply": (i32, [vp, vp, vp, i64, i32, vp, vp, vp, i32, vp, dbl, vp, vp, vp, vp]),
+        # the same with the activation dtype (ACT_BF16 / ACT_F16) in front
+        "hh_conv2d_dt": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp]),
+        "hh_conv2d_wgrad_dt": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+        "hh_fusion_sum_forward_dt": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+        "hh_fusion_sum_backward_dt": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp]),
+        "hh_bn_train_forward_dt": (i32, [i32, vp, i64, i32, vp, vp, C.c_float, vp, i32, vp, vp, vp, vp, vp]),
+        "hh_bn_train_backward_dt": (i32, [i32, vp, vp, vp, i64, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "hh_bn_train_backward_plain_dt": (i32, [i32, vp, vp, i64, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "hh_pack_conv_weights_batch_dt": (i32, [i32, i32, vp, vp, vp, vp, vp]),
+        "hh_conv2d_packed_dt": (i32, [i32, vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]),
+        "hh_bn_train_stats_dt": (i32, [i32, vp, i64, i32, vp, vp, vp]),
+        "hh_bn_train_normalize_dt": (i32, [i32, vp, i64, i32, vp, dbl, vp, vp, C.c_float, vp, i32, vp, vp, vp, vp]),
+        "hh_bn_train_backward_stats_dt": (i32, [i32, vp, vp, vp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "hh_bn_train_backward_apply_dt": (i32, [i32, vp, vp, vp, i64, i32, vp, vp, vp, i32, vp, dbl, vp, vp, vp, vp]),
         "hh_resize_accumulate": (i32, [vp, i64, i32, i32, i32, i32, vp, i64, i32, i32, C.c_float, i32, vp]),
         "hh_multi_scale_aggregate": (i32, [vp, i32, vp, i32, i32, vp, i64, i32, i32, vp]),
         "hh_decoder_read_topk": (i32, [vp, vp, vp, vp]),

@@ -314,11 +314,20 @@ int hh_conv2d_config(int cin, int cout, int ks, int stride, int mode, int Wo)
     return conv2d_pick(pl, Wo);
 }
 
+// the element type of a training entry point: HH_ACT_BF16 / HH_ACT_F16, anything else is refused before any launch
+static int act_dtype_ok(int act_dtype, const char *who)
+{
+    if (act_dtype == HH_ACT_BF16 || act_dtype == HH_ACT_F16) return 1;
+    hh_set_error((std::string(who) + ": unknown activation dtype (HH_ACT_BF16 = 0, HH_ACT_F16 = 1)").c_str());
+    return 0;
+}
+
 // w: fp32 weights (packed into `workspace` here) or, with prepacked != NULL, weight sets packed by hh_pack_conv_weights_batch
-static int conv2d_impl(const void *x, int B, int H, int W, int cin, const float *w, const bf16_raw *prepacked, int cout, int ks, int stride,
+static int conv2d_impl(int act_dtype, const void *x, int B, int H, int W, int cin, const float *w, const bf16_raw *prepacked, int cout, int ks, int stride,
                        int mode, int pad_y, int pad_x, const float *bias, const void *res, int relu, void *y, void *workspace, void *stream,
                        const char *who)
 {
+    if (!act_dtype_ok(act_dtype, who)) return 1;
     if (pad_y < 0) pad_y = (ks - 1) / 2;
     if (pad_x < 0) pad_x = (ks - 1) / 2;
     static bool inited = false;
@@ -372,30 +381,40 @@ static int conv2d_impl(const void *x, int B, int H, int W, int cin, const float 
         p.Hob = 2 * H; p.Wob = 2 * W; p.osy = p.osx = 2; p.pad_y = p.pad_x = 0;
         for (int ph = 0; ph < 4; ++ph) {
             if (prepacked) p.w = prepacked + (size_t)ph * wel;
-            else HH_CHECK_HIP(launch_pack_weights(w, cout, cin, 2, 2, KC, COUT_T, packed, wel, s, ph >> 1, ph & 1));
+            else HH_CHECK_HIP(launch_pack_weights(w, cout, cin, 2, 2, KC, COUT_T, packed, wel, s, ph >> 1, ph & 1, act_dtype));
             p.ooy = ph >> 1; p.oox = ph & 1;
-            HH_CHECK_HIP(conv_launch(cfg, p, s));
+            HH_CHECK_HIP(conv_launch(cfg, p, s, act_dtype));
         }
         return 0;
     }
-    if (!prepacked) HH_CHECK_HIP(launch_pack_weights(w, cout, cin, ks, mode, KC, COUT_T, packed, wel, s));
-    HH_CHECK_HIP(conv_launch(cfg, p, s));
+    if (!prepacked) HH_CHECK_HIP(launch_pack_weights(w, cout, cin, ks, mode, KC, COUT_T, packed, wel, s, 0, 0, act_dtype));
+    HH_CHECK_HIP(conv_launch(cfg, p, s, act_dtype));
     return 0;
 }
 
+int hh_conv2d_dt(int act_dtype, const void *x, int B, int H, int W, int cin, const float *w, int cout, int ks, int stride, int mode, int pad_y,
+                 int pad_x, const float *bias, const void *res, int relu, void *y, void *workspace, void *stream)
+{
+    if (!w || !workspace) { hh_set_error("hh_conv2d: bad argument"); return 1; }
+    return conv2d_impl(act_dtype, x, B, H, W, cin, w, nullptr, cout, ks, stride, mode, pad_y, pad_x, bias, res, relu, y, workspace, stream, "hh_conv2d");
+}
 int hh_conv2d(const void *x, int B, int H, int W, int cin, const float *w, int cout, int ks, int stride, int mode, int pad_y, int pad_x,
               const float *bias, const void *res, int relu, void *y, void *workspace, void *stream)
 {
-    if (!w || !workspace) { hh_set_error("hh_conv2d: bad argument"); return 1; }
-    return conv2d_impl(x, B, H, W, cin, w, nullptr, cout, ks, stride, mode, pad_y, pad_x, bias, res, relu, y, workspace, stream, "hh_conv2d");
+    return hh_conv2d_dt(HH_ACT_BF16, x, B, H, W, cin, w, cout, ks, stride, mode, pad_y, pad_x, bias, res, relu, y, workspace, stream);
 }
 
+int hh_conv2d_packed_dt(int act_dtype, const void *x, int B, int H, int W, int cin, const void *w_packed, int cout, int ks, int stride, int mode,
+                        int pad_y, int pad_x, const float *bias, const void *res, int relu, void *y, void *stream)
+{
+    if (!w_packed) { hh_set_error("hh_conv2d_packed: bad argument"); return 1; }
+    return conv2d_impl(act_dtype, x, B, H, W, cin, nullptr, (const bf16_raw *)w_packed, cout, ks, stride, mode, pad_y, pad_x, bias, res, relu, y,
+                       nullptr, stream, "hh_conv2d_packed");
+}
 int hh_conv2d_packed(const void *x, int B, int H, int W, int cin, const void *w_packed, int cout, int ks, int stride, int mode, int pad_y,
                      int pad_x, const float *bias, const void *res, int relu, void *y, void *stream)
 {
-    if (!w_packed) { hh_set_error("hh_conv2d_packed: bad argument"); return 1; }
-    return conv2d_impl(x, B, H, W, cin, nullptr, (const bf16_raw *)w_packed, cout, ks, stride, mode, pad_y, pad_x, bias, res, relu, y, nullptr,
-                       stream, "hh_conv2d_packed");
+    return hh_conv2d_packed_dt(HH_ACT_BF16, x, B, H, W, cin, w_packed, cout, ks, stride, mode, pad_y, pad_x, bias, res, relu, y, stream);
 }
 
 int64_t hh_conv2d_packed_elems(int cin, int cout, int ks, int stride, int mode)
@@ -407,6 +426,12 @@ int64_t hh_conv2d_packed_elems(int cin, int cout, int ks, int stride, int mode)
 
 int hh_pack_conv_weights_batch(int n, const float *const *w, void *const *packed, const int32_t *shapes, void *descs_dev, void *stream)
 {
+    return hh_pack_conv_weights_batch_dt(HH_ACT_BF16, n, w, packed, shapes, descs_dev, stream);
+}
+int hh_pack_conv_weights_batch_dt(int act_dtype, int n, const float *const *w, void *const *packed, const int32_t *shapes, void *descs_dev,
+                                  void *stream)
+{
+    if (!act_dtype_ok(act_dtype, "hh_pack_conv_weights_batch")) return 1;
     if (n < 0 || (n && (!w || !packed || !shapes || !descs_dev))) { hh_set_error("hh_pack_conv_weights_batch: bad argument"); return 1; }
     std::vector<PackDesc> d;
     d.reserve((size_t)n * 4);
@@ -428,7 +453,7 @@ int hh_pack_conv_weights_batch(int n, const float *const *w, void *const *packed
     if (d.empty()) return 0;
     // (pageable source: the copy is staged before hipMemcpyAsync returns, so the vector may go)
     HH_CHECK_HIP(hipMemcpyAsync(descs_dev, d.data(), d.size() * sizeof(PackDesc), hipMemcpyHostToDevice, (hipStream_t)stream));
-    HH_CHECK_HIP(launch_pack_weights_batch((const PackDesc *)descs_dev, (int)d.size(), (hipStream_t)stream));
+    HH_CHECK_HIP(launch_pack_weights_batch((const PackDesc *)descs_dev, (int)d.size(), (hipStream_t)stream, act_dtype));
     return 0;
 }
 
@@ -459,9 +484,10 @@ int hh_conv2d_wgrad_plan(int B, int H, int W, int cin, int cout, int ks, int str
     return 0;
 }
 
-int hh_conv2d_wgrad(const void *x, const void *dy, int B, int H, int W, int cin, int cout, int ks, int stride, int pad_y, int pad_x, float *dw,
-                    void *workspace, void *stream)
+int hh_conv2d_wgrad_dt(int act_dtype, const void *x, const void *dy, int B, int H, int W, int cin, int cout, int ks, int stride, int pad_y, int pad_x,
+                       float *dw, void *workspace, void *stream)
 {
+    if (!act_dtype_ok(act_dtype, "hh_conv2d_wgrad")) return 1;
     if (pad_y < 0) pad_y = (ks - 1) / 2;
     if (pad_x < 0) pad_x = (ks - 1) / 2;
     if (!x || !dy || !dw || !workspace) { hh_set_error("hh_conv2d_wgrad: bad argument"); return 1; }
@@ -471,39 +497,64 @@ int hh_conv2d_wgrad(const void *x, const void *dy, int B, int H, int W, int cin,
     p.x = (const bf16_raw *)x; p.dy = (const bf16_raw *)dy; p.partial = (float *)workspace;
     p.B = B; p.H = H; p.W = W; p.Ho = Ho_; p.Wo = Wo_; p.cin = cin; p.cout = cout;
     p.pad_y = pad_y; p.pad_x = pad_x;
-    HH_CHECK_HIP(conv_wgrad_launch(p, ks, stride, dw, (hipStream_t)stream));
+    HH_CHECK_HIP(conv_wgrad_launch(p, ks, stride, dw, (hipStream_t)stream, act_dtype));
     return 0;
 }
-
-int hh_bn_train_forward(const void *x, int64_t P, int C, const float *gamma, const float *beta, float eps, const void *res, int relu,
-                        void *y, float *mean, float *invstd, double *scratch, void *stream)
+int hh_conv2d_wgrad(const void *x, const void *dy, int B, int H, int W, int cin, int cout, int ks, int stride, int pad_y, int pad_x, float *dw,
+                    void *workspace, void *stream)
 {
+    return hh_conv2d_wgrad_dt(HH_ACT_BF16, x, dy, B, H, W, cin, cout, ks, stride, pad_y, pad_x, dw, workspace, stream);
+}
+
+int hh_bn_train_forward_dt(int act_dtype, const void *x, int64_t P, int C, const float *gamma, const float *beta, float eps, const void *res,
+                           int relu, void *y, float *mean, float *invstd, double *scratch, void *stream)
+{
+    if (!act_dtype_ok(act_dtype, "hh_bn_train_forward")) return 1;
     if (!x || !y || !gamma || !beta || !mean || !invstd || !scratch || P <= 0 || C <= 0 || C % 8 || C > 2048) { hh_set_error("hh_bn_train_forward: bad argument (C must be a multiple of 8, <= 2048)"); return 1; }
     HH_CHECK_HIP(launch_bn_train_forward((const bf16_raw *)x, C, (size_t)P, C, gamma, beta, eps, (const bf16_raw *)res, relu, (bf16_raw *)y,
-                                         mean, invstd, scratch, (hipStream_t)stream));
+                                         mean, invstd, scratch, (hipStream_t)stream, act_dtype));
     return 0;
 }
-
-int hh_bn_train_backward(const void *x, const void *y, const void *dy, int64_t P, int C, const float *mean, const float *invstd,
-                         const float *gamma, int relu, void *dx, void *dres, float *dgamma, float *dbeta, double *scratch, void *stream)
+int hh_bn_train_forward(const void *x, int64_t P, int C, const float *gamma, const float *beta, float eps, const void *res, int relu, void *y,
+                        float *mean, float *invstd, double *scratch, void *stream)
 {
+    return hh_bn_train_forward_dt(HH_ACT_BF16, x, P, C, gamma, beta, eps, res, relu, y, mean, invstd, scratch, stream);
+}
+
+int hh_bn_train_backward_dt(int act_dtype, const void *x, const void *y, const void *dy, int64_t P, int C, const float *mean, const float *invstd,
+                            const float *gamma, int relu, void *dx, void *dres, float *dgamma, float *dbeta, double *scratch, void *stream)
+{
+    if (!act_dtype_ok(act_dtype, "hh_bn_train_backward")) return 1;
     if (!x || !y || !dy || !dx || !mean || !invstd || !gamma || !dgamma || !dbeta || !scratch || P <= 0 || C <= 0 || C % 8 || C > 2048) { hh_set_error("hh_bn_train_backward: bad argument"); return 1; }
     HH_CHECK_HIP(launch_bn_train_backward((const bf16_raw *)x, (const bf16_raw *)y, (const bf16_raw *)dy, C, (size_t)P, C, mean, invstd, gamma,
-                                          nullptr, relu, (bf16_raw *)dx, (bf16_raw *)dres, dgamma, dbeta, scratch, (hipStream_t)stream));
+                                          nullptr, relu, (bf16_raw *)dx, (bf16_raw *)dres, dgamma, dbeta, scratch, (hipStream_t)stream, act_dtype));
     return 0;
 }
+int hh_bn_train_backward(const void *x, const void *y, const void *dy, int64_t P, int C, const float *mean, const float *invstd, const float *gamma,
+                         int relu, void *dx, void *dres, float *dgamma, float *dbeta, double *scratch, void *stream)
+{
+    return hh_bn_train_backward_dt(HH_ACT_BF16, x, y, dy, P, C, mean, invstd, gamma, relu, dx, dres, dgamma, dbeta, scratch, stream);
+}
 
+int hh_bn_train_backward_plain_dt(int act_dtype, const void *x, const void *dy, int64_t P, int C, const float *mean, const float *invstd,
+                                  const float *gamma, const float *beta, int relu, void *dx, float *dgamma, float *dbeta, double *scratch, void *stream)
+{
+    if (!act_dtype_ok(act_dtype, "hh_bn_train_backward_plain")) return 1;
+    if (!x || !dy || !dx || !mean || !invstd || !gamma || !beta || !dgamma || !dbeta || !scratch || P <= 0 || C <= 0 || C % 8 || C > 2048) { hh_set_error("hh_bn_train_backward_plain: bad argument"); return 1; }
+    HH_CHECK_HIP(launch_bn_train_backward((const bf16_raw *)x, nullptr, (const bf16_raw *)dy, C, (size_t)P, C, mean, invstd, gamma, beta, relu,
+                                          (bf16_raw *)dx, nullptr, dgamma, dbeta, scratch, (hipStream_t)stream, act_dtype));
+    return 0;
+}
 int hh_bn_train_backward_plain(const void *x, const void *dy, int64_t P, int C, const float *mean, const float *invstd, const float *gamma,
                                const float *beta, int relu, void *dx, float *dgamma, float *dbeta, double *scratch, void *stream)
 {
-    if (!x || !dy || !dx || !mean || !invstd || !gamma || !beta || !dgamma || !dbeta || !scratch || P <= 0 || C <= 0 || C % 8 || C > 2048) { hh_set_error("hh_bn_train_backward_plain: bad argument"); return 1; }
-    HH_CHECK_HIP(launch_bn_train_backward((const bf16_raw *)x, nullptr, (const bf16_raw *)dy, C, (size_t)P, C, mean, invstd, gamma, beta, relu,
-                                          (bf16_raw *)dx, nullptr, dgamma, dbeta, scratch, (hipStream_t)stream));
-    return 0;
+    return hh_bn_train_backward_plain_dt(HH_ACT_BF16, x, dy, P, C, mean, invstd, gamma, beta, relu, dx, dgamma, dbeta, scratch, stream);
 }
 
-int hh_fusion_sum_forward(const void *const *terms, const int *shifts, int nterms, int B, int H, int W, int C, int relu, void *out, void *stream)
+int hh_fusion_sum_forward_dt(int act_dtype, const void *const *terms, const int *shifts, int nterms, int B, int H, int W, int C, int relu, void *out,
+                             void *stream)
 {
+    if (!act_dtype_ok(act_dtype, "hh_fusion_sum_forward")) return 1;
     if (!terms || !shifts || nterms < 1 || nterms > 4 || !out || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || shifts[0] != 0) { hh_set_error("hh_fusion_sum_forward: 1..4 terms, the first at the output resolution, C a multiple of 8"); return 1; }
     UpAddParams p{};
     p.base = (const bf16_raw *)terms[0]; p.base_cs = C;
@@ -514,53 +565,86 @@ int hh_fusion_sum_forward(const void *const *terms, const int *shifts, int nterm
     }
     p.out = (bf16_raw *)out; p.out_cs = C;
     p.B = B; p.H = H; p.W = W; p.C = C; p.relu = relu;
-    HH_CHECK_HIP(launch_upadd(p, (hipStream_t)stream));
+    HH_CHECK_HIP(launch_upadd(p, (hipStream_t)stream, act_dtype));
     return 0;
 }
-int hh_fusion_sum_backward(const void *dy, const void *out, int relu, int B, int H, int W, int C, void *g, void *const *dup, const int *up_shift, int nup,
-                           void *stream)
+int hh_fusion_sum_forward(const void *const *terms, const int *shifts, int nterms, int B, int H, int W, int C, int relu, void *out, void *stream)
 {
+    return hh_fusion_sum_forward_dt(HH_ACT_BF16, terms, shifts, nterms, B, H, W, C, relu, out, stream);
+}
+int hh_fusion_sum_backward_dt(int act_dtype, const void *dy, const void *out, int relu, int B, int H, int W, int C, void *g, void *const *dup,
+                              const int *up_shift, int nup, void *stream)
+{
+    if (!act_dtype_ok(act_dtype, "hh_fusion_sum_backward")) return 1;
     if (!dy || (relu && (!out || !g)) || nup < 0 || nup > 3 || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8) { hh_set_error("hh_fusion_sum_backward: bad argument"); return 1; }
     HH_CHECK_HIP(launch_upadd_backward((const bf16_raw *)dy, (const bf16_raw *)out, relu, B, H, W, C, (bf16_raw *)g, (bf16_raw *const *)dup, up_shift, nup,
-                                       (hipStream_t)stream));
+                                       (hipStream_t)stream, act_dtype));
     return 0;
+}
+int hh_fusion_sum_backward(const void *dy, const void *out, int relu, int B, int H, int W, int C, void *g, void *const *dup, const int *up_shift,
+                           int nup, void *stream)
+{
+    return hh_fusion_sum_backward_dt(HH_ACT_BF16, dy, out, relu, B, H, W, C, g, dup, up_shift, nup, stream);
 }
 
 static bool bn_dims_ok(int64_t P, int C) { return P > 0 && C > 0 && C % 8 == 0 && C <= 2048; }
 
-int hh_bn_train_stats(const void *x, int64_t P, int C, double *sums, double *scratch, void *stream)
+int hh_bn_train_stats_dt(int act_dtype, const void *x, int64_t P, int C, double *sums, double *scratch, void *stream)
 {
+    if (!act_dtype_ok(act_dtype, "hh_bn_train_stats")) return 1;
     if (!x || !sums || !scratch || !bn_dims_ok(P, C)) { hh_set_error("hh_bn_train_stats: bad argument (C must be a multiple of 8, <= 2048)"); return 1; }
-    HH_CHECK_HIP(launch_bn_train_stats((const bf16_raw *)x, C, (size_t)P, C, sums, scratch, (hipStream_t)stream));
+    HH_CHECK_HIP(launch_bn_train_stats((const bf16_raw *)x, C, (size_t)P, C, sums, scratch, (hipStream_t)stream, act_dtype));
     return 0;
 }
+int hh_bn_train_stats(const void *x, int64_t P, int C, double *sums, double *scratch, void *stream)
+{
+    return hh_bn_train_stats_dt(HH_ACT_BF16, x, P, C, sums, scratch, stream);
+}
 
+int hh_bn_train_normalize_dt(int act_dtype, const void *x, int64_t P, int C, const double *sums, double count, const float *gamma, const float *beta,
+                             float eps, const void *res, int relu, void *y, float *mean, float *invstd, void *stream)
+{
+    if (!act_dtype_ok(act_dtype, "hh_bn_train_normalize")) return 1;
+    if (!x || !y || !sums || !gamma || !beta || !mean || !invstd || !bn_dims_ok(P, C) || !(count >= (double)P)) { hh_set_error("hh_bn_train_normalize: bad argument (count = pixels of all ranks >= P)"); return 1; }
+    HH_CHECK_HIP(launch_bn_train_normalize((const bf16_raw *)x, C, (size_t)P, C, sums, count, gamma, beta, eps, (const bf16_raw *)res, relu,
+                                           (bf16_raw *)y, mean, invstd, (hipStream_t)stream, act_dtype));
+    return 0;
+}
 int hh_bn_train_normalize(const void *x, int64_t P, int C, const double *sums, double count, const float *gamma, const float *beta, float eps,
                           const void *res, int relu, void *y, float *mean, float *invstd, void *stream)
 {
-    if (!x || !y || !sums || !gamma || !beta || !mean || !invstd || !bn_dims_ok(P, C) || !(count >= (double)P)) { hh_set_error("hh_bn_train_normalize: bad argument (count = pixels of all ranks >= P)"); return 1; }
-    HH_CHECK_HIP(launch_bn_train_normalize((const bf16_raw *)x, C, (size_t)P, C, sums, count, gamma, beta, eps, (const bf16_raw *)res, relu,
-                                           (bf16_raw *)y, mean, invstd, (hipStream_t)stream));
-    return 0;
+    return hh_bn_train_normalize_dt(HH_ACT_BF16, x, P, C, sums, count, gamma, beta, eps, res, relu, y, mean, invstd, stream);
 }
 
+int hh_bn_train_backward_stats_dt(int act_dtype, const void *x, const void *y, const void *dy, int64_t P, int C, const float *mean,
+                                  const float *invstd, int relu, double *sums, float *dgamma, float *dbeta, double *scratch, void *stream)
+{
+    if (!act_dtype_ok(act_dtype, "hh_bn_train_backward_stats")) return 1;
+    if (!x || !y || !dy || !mean || !invstd || !sums || !dgamma || !dbeta || !scratch || !bn_dims_ok(P, C)) { hh_set_error("hh_bn_train_backward_stats: bad argument"); return 1; }
+    HH_CHECK_HIP(launch_bn_train_backward_stats((const bf16_raw *)x, (const bf16_raw *)y, (const bf16_raw *)dy, C, (size_t)P, C, mean, invstd,
+                                                relu, sums, dgamma, dbeta, scratch, (hipStream_t)stream, act_dtype));
+    return 0;
+}
 int hh_bn_train_backward_stats(const void *x, const void *y, const void *dy, int64_t P, int C, const float *mean, const float *invstd, int relu,
                                double *sums, float *dgamma, float *dbeta, double *scratch, void *stream)
 {
-    if (!x || !y || !dy || !mean || !invstd || !sums || !dgamma || !dbeta || !scratch || !bn_dims_ok(P, C)) { hh_set_error("hh_bn_train_backward_stats: bad argument"); return 1; }
-    HH_CHECK_HIP(launch_bn_train_backward_stats((const bf16_raw *)x, (const bf16_raw *)y, (const bf16_raw *)dy, C, (size_t)P, C, mean, invstd,
-                                                relu, sums, dgamma, dbeta, scratch, (hipStream_t)stream));
-    return 0;
+    return hh_bn_train_backward_stats_dt(HH_ACT_BF16, x, y, dy, P, C, mean, invstd, relu, sums, dgamma, dbeta, scratch, stream);
 }
 
-int hh_bn_train_backward_apply(const void *x, const void *y, const void *dy, int64_t P, int C, const float *mean, const float *invstd,
-                               const float *gamma, int relu, const double *sums, double count, void *dx, void *dres, double *scratch,
-                               void *stream)
+int hh_bn_train_backward_apply_dt(int act_dtype, const void *x, const void *y, const void *dy, int64_t P, int C, const float *mean,
+                                  const float *invstd, const float *gamma, int relu, const double *sums, double count, void *dx, void *dres, double *scratch,
+                                  void *stream)
 {
+    if (!act_dtype_ok(act_dtype, "hh_bn_train_backward_apply")) return 1;
     if (!x || !y || !dy || !dx || !mean || !invstd || !gamma || !sums || !scratch || !bn_dims_ok(P, C) || !(count >= (double)P)) { hh_set_error("hh_bn_train_backward_apply: bad argument"); return 1; }
     HH_CHECK_HIP(launch_bn_train_backward_apply((const bf16_raw *)x, (const bf16_raw *)y, (const bf16_raw *)dy, C, (size_t)P, C, mean, invstd,
-                                                gamma, relu, sums, count, (bf16_raw *)dx, (bf16_raw *)dres, scratch, (hipStream_t)stream));
+                                                gamma, relu, sums, count, (bf16_raw *)dx, (bf16_raw *)dres, scratch, (hipStream_t)stream, act_dtype));
     return 0;
+}
+int hh_bn_train_backward_apply(const void *x, const void *y, const void *dy, int64_t P, int C, const float *mean, const float *invstd,
+                               const float *gamma, int relu, const double *sums, double count, void *dx, void *dres, double *scratch, void *stream)
+{
+    return hh_bn_train_backward_apply_dt(HH_ACT_BF16, x, y, dy, P, C, mean, invstd, gamma, relu, sums, count, dx, dres, scratch, stream);
 }
 
 int hh_flip_images(const float *images, float *out, int B, int C, int H, int W, void *stream)

@@ -1,4 +1,4 @@
-// Implicit-GEMM convolution on gfx950 matrix cores (v_mfma_f32_32x32x16_bf16), NHWC bf16.
+// Implicit-GEMM convolution on gfx950 matrix cores (v_mfma_f32_32x32x16_bf16; _f16 on the training path's fp16 form), NHWC bf16 / fp16.
 //
 // Replaces the ATen conv2d / conv_transpose2d + batch_norm + relu + add chain the
 // reference dispatches per layer (hrnet.py:38-45,83-100,190,202,254,265,354-356;
@@ -32,7 +32,9 @@ __device__ long long g_conv_dbg[8192 * 8];
 // single-buffer form a wave's 15 ds_write_b128 per chunk (~780 clk of the CU's store path) and two barriers stand between the
 // MFMA runs, and a layer of 128 / 256 channels has one wave per SIMD, so nothing else runs meanwhile.  With KC = 16 the two
 // buffers take what one KC = 32 buffer took, so the launches keep sharing CUs with the other branch lanes.
-template <int KS, int S, int KC, int NT, int WC, int PT, int TW, int DB>
+// E: the element type (ElemBF16 / ElemF16 of mfma_dev.h): the residual unpack, the MFMA form and the 16-bit store; the fp32 NCHW
+// epilogue does not depend on it.
+template <typename E, int KS, int S, int KC, int NT, int WC, int PT, int TW, int DB>
 __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
 {
     constexpr int RPT = 32 / TW;  // image rows covered by one 32-pixel MFMA column tile
@@ -224,10 +226,10 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
                         x0 = s0[0]; y0 = s0[1]; x1 = s1[0]; y1 = s1[1];
                     }
                     const float4 ba = bs[nt][2 * m], bb = bs[nt][2 * m + 1];
-                    acc[nt][pt][8 * m + 0] = ba.x + bf16_lo(x0); acc[nt][pt][8 * m + 1] = ba.y + bf16_hi(x0);
-                    acc[nt][pt][8 * m + 2] = ba.z + bf16_lo(x1); acc[nt][pt][8 * m + 3] = ba.w + bf16_hi(x1);
-                    acc[nt][pt][8 * m + 4] = bb.x + bf16_lo(y0); acc[nt][pt][8 * m + 5] = bb.y + bf16_hi(y0);
-                    acc[nt][pt][8 * m + 6] = bb.z + bf16_lo(y1); acc[nt][pt][8 * m + 7] = bb.w + bf16_hi(y1);
+                    acc[nt][pt][8 * m + 0] = ba.x + E::lo(x0); acc[nt][pt][8 * m + 1] = ba.y + E::hi(x0);
+                    acc[nt][pt][8 * m + 2] = ba.z + E::lo(x1); acc[nt][pt][8 * m + 3] = ba.w + E::hi(x1);
+                    acc[nt][pt][8 * m + 4] = bb.x + E::lo(y0); acc[nt][pt][8 * m + 5] = bb.y + E::hi(y0);
+                    acc[nt][pt][8 * m + 6] = bb.z + E::lo(y1); acc[nt][pt][8 * m + 7] = bb.w + E::hi(y1);
                 }
     }
 
@@ -308,8 +310,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
                     if constexpr (pt >= 0 && pt < PT)
 #pragma unroll
                         for (int nt = 0; nt < NT; ++nt)
-                            acc[nt][pt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[c & 1][ky][nt]),
-                                                                                  __builtin_bit_cast(bf16x8, fb[s & 1]), acc[nt][pt], 0, 0, 0);
+                            acc[nt][pt] = E::mfma(fa[c & 1][ky][nt], fb[s & 1], acc[nt][pt]);
                 });
                 __builtin_amdgcn_sched_group_barrier(0x8, NT * (hi - lo + 1), 0);
             });
@@ -348,9 +349,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
             for (int pt = 0; pt < PT; ++pt)
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt)
-                    acc[nt][pt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[st & 1][nt]),
-                                                                          __builtin_bit_cast(bf16x8, fb[st & 1][pt]),
-                                                                          acc[nt][pt], 0, 0, 0);
+                    acc[nt][pt] = E::mfma(fa[st & 1][nt], fb[st & 1][pt], acc[nt][pt]);
             __builtin_amdgcn_sched_group_barrier(0x8, NT * PT, 0);
         });
     };
@@ -410,10 +409,10 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
                 const i16x2 floor = {fl, fl};
 #pragma unroll
                 for (int m = 0; m < 2; ++m) {
-                    const unsigned x0 = pack_bf16x2(acc[nt][pt][8 * m + 0], acc[nt][pt][8 * m + 1], floor);
-                    const unsigned x1 = pack_bf16x2(acc[nt][pt][8 * m + 2], acc[nt][pt][8 * m + 3], floor);
-                    const unsigned y0 = pack_bf16x2(acc[nt][pt][8 * m + 4], acc[nt][pt][8 * m + 5], floor);
-                    const unsigned y1 = pack_bf16x2(acc[nt][pt][8 * m + 6], acc[nt][pt][8 * m + 7], floor);
+                    const unsigned x0 = E::pack(acc[nt][pt][8 * m + 0], acc[nt][pt][8 * m + 1], floor);
+                    const unsigned x1 = E::pack(acc[nt][pt][8 * m + 2], acc[nt][pt][8 * m + 3], floor);
+                    const unsigned y0 = E::pack(acc[nt][pt][8 * m + 4], acc[nt][pt][8 * m + 5], floor);
+                    const unsigned y1 = E::pack(acc[nt][pt][8 * m + 6], acc[nt][pt][8 * m + 7], floor);
                     auto s0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
                     auto s1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
                     const int c0 = cg * COUT_T + (wc * NT + nt) * 32 + 16 * m + 8 * h;
@@ -469,8 +468,15 @@ static const ConvConfig g_configs[] = {CONV_CONFIGS(CFG_ROW)};
 #undef CFG_ROW
 
 typedef void (*conv_fn)(const ConvParams);
-#define CFG_FN(ks, s, kc, nt, wc, pt, tw, db) conv_mfma_kernel<ks, s, kc, nt, wc, pt, tw, db>,
+#define CFG_FN(ks, s, kc, nt, wc, pt, tw, db) conv_mfma_kernel<ElemBF16, ks, s, kc, nt, wc, pt, tw, db>,
 static const conv_fn g_fns[] = {CONV_CONFIGS(CFG_FN)};
+#undef CFG_FN
+// fp16 (act_dtype 1): the training path's instantiations.  hh_conv2d never picks a two-buffer (DB) one -- only the inference
+// engine does, which stays bf16 -- so those have no fp16 form and launching one is an error.
+template <int KS, int S, int KC, int NT, int WC, int PT, int TW, int DB>
+static constexpr conv_fn f16_fn() { if constexpr (DB) return nullptr; else return conv_mfma_kernel<ElemF16, KS, S, KC, NT, WC, PT, TW, 0>; }
+#define CFG_FN(ks, s, kc, nt, wc, pt, tw, db) f16_fn<ks, s, kc, nt, wc, pt, tw, db>(),
+static const conv_fn g_fns_f16[] = {CONV_CONFIGS(CFG_FN)};
 #undef CFG_FN
 
 int conv_num_configs() { return (int)(sizeof(g_configs) / sizeof(g_configs[0])); }
@@ -482,15 +488,20 @@ hipError_t conv_init()
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(g_fns[i]),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_configs[i].lds_bytes());
         if (e != hipSuccess) return e;
+        if (!g_fns_f16[i]) continue;
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(g_fns_f16[i]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_configs[i].lds_bytes());
+        if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-hipError_t conv_launch(int cfg_index, const ConvParams &p, hipStream_t stream)
+hipError_t conv_launch(int cfg_index, const ConvParams &p, hipStream_t stream, int act_dtype)
 {
+    const conv_fn fn = act_dtype == 0 ? g_fns[cfg_index] : (act_dtype == 1 ? g_fns_f16[cfg_index] : nullptr);
+    if (!fn) return hipErrorInvalidValue;  // unknown element type, or an instantiation without an fp16 form
     const ConvConfig &c = g_configs[cfg_index];
     const unsigned tiles = (unsigned)p.B * p.tiles_y * p.tiles_x, sf = (unsigned)p.ncg * (p.nphase > 1 ? p.nphase : 1);
     const unsigned grid = sf > 1 ? (tiles + 7) / 8 * 8 * sf : tiles;  // groups of 8 tiles x sf variants (see the kernel)
-    HH_LAUNCH(g_fns[cfg_index], dim3(grid), dim3(256), c.lds_bytes(), stream, p);
+    HH_LAUNCH(fn, dim3(grid), dim3(256), c.lds_bytes(), stream, p);
     return hipGetLastError();
 }

@@ -1,4 +1,4 @@
-// Weight gradient of a convolution on NHWC bf16 activations (training path):
+// Weight gradient of a convolution on NHWC bf16 (or fp16) activations (training path):
 //   dW[co][ci][ky][kx] = sum over (b, y, x) of dY[b, y, x, co] * X[b, y*S + ky - pad, x*S + kx - pad, ci]   (zero padded)
 // As MFMA work this is a GEMM whose contraction runs over PIXELS: per tap, D[co][ci] += A[co][16 px] * B[16 px][ci].
 // Both operands therefore need 8 consecutive pixels of ONE channel per lane, while NHWC keeps the channels of one pixel
@@ -30,7 +30,7 @@ __device__ __forceinline__ i16x4 tr_read(const char *lds, int byte_off)
 // SMALLC (cin, cout <= 32, the highest-resolution branch and the deconv head): the 64 x 64 channel block would leave three
 // of the four waves multiplying padding, so there every wave takes the one real 32 x 32 block and the waves split the
 // TAPS instead (wave w: taps w, w+4, w+8).
-template <int KS, int S, int TW, int NTG, bool SMALLC>
+template <typename E, int KS, int S, int TW, int NTG, bool SMALLC>  // E: ElemBF16 / ElemF16 (the MFMA form; ds_read_b64_tr_b16 moves 16-bit elements of either)
 __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradParams p)
 {
     constexpr int PH = (TH - 1) * S + KS, PW = (TW - 1) * S + KS, NTAP = KS * KS;
@@ -141,8 +141,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(const WgradParams p)
             if constexpr (step + 1 < NSTEP) ld_b(step + 1, (step + 1) & 1);
             if constexpr (next_a) ld_a(ks + 1, (ks + 1) & 1);
             if constexpr (step + 1 < NSTEP) __builtin_amdgcn_sched_group_barrier(0x100, next_a ? 4 : 2, 0);
-            acc[tap] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, afrag[ks & 1]), __builtin_bit_cast(bf16x8, bfrag[step & 1]),
-                                                               acc[tap], 0, 0, 0);
+            acc[tap] = E::mfma(afrag[ks & 1], bfrag[step & 1], acc[tap]);
             __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
         });
     }
@@ -201,13 +200,13 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_kernel(const float *__restr
     dw[((size_t)co * cin + ci) * ntap + tap] = sum;
 }
 
-template <int KS, int S, int TW, bool SMALLC = false>
+template <typename E, int KS, int S, int TW, bool SMALLC = false>
 static hipError_t launch_one(const WgradParams &p, int nwg, hipStream_t s)
 {
     constexpr int PH = (TH - 1) * S + KS, PW = (TW - 1) * S + KS;
     constexpr int NTG = SMALLC ? (KS * KS + 3) / 4 : (KS == 3 ? 5 : KS * KS), NGRP = SMALLC ? 1 : (KS * KS + NTG - 1) / NTG;
     const size_t lds = (size_t)(TH * TW + PH * PW) * RS;
-    auto fn = conv_wgrad_kernel<KS, S, TW, NTG, SMALLC>;
+    auto fn = conv_wgrad_kernel<E, KS, S, TW, NTG, SMALLC>;
     static bool configured = false;  // once per instantiation
     if (!configured) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -255,17 +254,24 @@ int conv_wgrad_num_workers(int B, int Ho, int Wo, int ks, int stride, int cin, i
     return ntiles < want ? ntiles : want;
 }
 
-hipError_t conv_wgrad_launch(const WgradParams &p, int ks, int stride, float *dw, hipStream_t s)
+template <typename E>
+static hipError_t launch_variant(int variant, const WgradParams &p, int nwg, hipStream_t s)
+{
+    if (variant == 0) return launch_one<E, 3, 1, VARIANT_TW[0]>(p, nwg, s);
+    if (variant == 1) return launch_one<E, 3, 1, VARIANT_TW[1], true>(p, nwg, s);
+    if (variant == 2) return launch_one<E, 3, 1, VARIANT_TW[2]>(p, nwg, s);
+    if (variant == 3) return launch_one<E, 1, 1, VARIANT_TW[3]>(p, nwg, s);
+    if (variant == 4) return launch_one<E, 3, 2, VARIANT_TW[4]>(p, nwg, s);
+    if (variant == 5) return launch_one<E, 2, 1, VARIANT_TW[5]>(p, nwg, s);
+    return hipErrorInvalidValue;
+}
+
+hipError_t conv_wgrad_launch(const WgradParams &p, int ks, int stride, float *dw, hipStream_t s, int act_dtype)
 {
     const int nwg = conv_wgrad_num_workers(p.B, p.Ho, p.Wo, ks, stride, p.cin, p.cout);
     const int variant = conv_wgrad_variant(ks, stride, p.Wo, p.cin, p.cout);
-    hipError_t e = hipErrorInvalidValue;
-    if (variant == 0) e = launch_one<3, 1, VARIANT_TW[0]>(p, nwg, s);
-    else if (variant == 1) e = launch_one<3, 1, VARIANT_TW[1], true>(p, nwg, s);
-    else if (variant == 2) e = launch_one<3, 1, VARIANT_TW[2]>(p, nwg, s);
-    else if (variant == 3) e = launch_one<1, 1, VARIANT_TW[3]>(p, nwg, s);
-    else if (variant == 4) e = launch_one<3, 2, VARIANT_TW[4]>(p, nwg, s);
-    else if (variant == 5) e = launch_one<2, 1, VARIANT_TW[5]>(p, nwg, s);
+    const hipError_t e = act_dtype == 0 ? launch_variant<ElemBF16>(variant, p, nwg, s)
+                                        : (act_dtype == 1 ? launch_variant<ElemF16>(variant, p, nwg, s) : hipErrorInvalidValue);
     if (e != hipSuccess) return e;
     const bool smallc = variant == 1;  // the SMALLC instance ran
     const int coutp = smallc ? 32 : (p.cout + 63) / 64 * 64, cinp = smallc ? 32 : (p.cin + 63) / 64 * 64, ntap = ks * ks;

@@ -5,7 +5,10 @@
 
 #include <hip/hip_ext.h>
 
-typedef uint16_t bf16_raw;  // storage type of a bf16 element in HBM
+typedef uint16_t bf16_raw;  // storage type of a bf16 element in HBM (and of an fp16 one on the training path)
+// act_dtype of the training launchers: the element type of activations and packed weights, 0 = bf16, 1 = fp16 (HH_ACT_BF16 / HH_ACT_F16
+// of hhrnet.h); anything else is hipErrorInvalidValue.  The two-buffer conv instantiations have no fp16 form (only the inference
+// engine, which is bf16, picks them).
 
 // Per-launch timing probe (bench.py's roofline line).  When the engine arms it, the NEXT forward-path kernel launch of this
 // thread goes through hipExtLaunchKernelGGL with a start / stop event pair: the runtime fills those from the dispatch packet's
@@ -73,7 +76,7 @@ struct ConvConfig {
 int conv_num_configs();
 const ConvConfig &conv_config(int i);
 // Launches config `cfg_index`; the grid is B*tiles_y*tiles_x*ncg blocks of 256 threads.
-hipError_t conv_launch(int cfg_index, const ConvParams &p, hipStream_t stream);
+hipError_t conv_launch(int cfg_index, const ConvParams &p, hipStream_t stream, int act_dtype = 0);
 hipError_t conv_init();  // raises the dynamic-LDS limit of every instantiation
 
 // ---- fp8 path (conv_fp8.hip): e4m3 NHWC activations with one scale per tensor, e4m3 weights with one scale per cout
@@ -265,7 +268,7 @@ struct UpAddParams {
     bf16_raw *out; int out_cs, out_coff;
     int B, H, W, C, relu;
 };
-hipError_t launch_upadd(const UpAddParams &p, hipStream_t s);
+hipError_t launch_upadd(const UpAddParams &p, hipStream_t s, int act_dtype = 0);
 // Output 0 of a fusion layer in one launch (fusion_up.hip), 32 channels:
 // out[b,y,x,c] = relu(x0[b,y,x,c] + sum_j u_j[b, y>>j, x>>j, c]),  u_j = bf16(bias_j + W_j x_j) for the sources j = 1..nsrc
 struct FusionUpParams {
@@ -284,7 +287,7 @@ struct FusionUpParams {
 bool fusion_up_supported(int C, int nsrc);
 hipError_t fusion_up_launch(FusionUpParams p, hipStream_t s);
 hipError_t launch_upadd_backward(const bf16_raw *dy, const bf16_raw *out, int relu, int B, int H, int W, int C, bf16_raw *g, bf16_raw *const *dup,
-                                 const int *up_shift, int nup, hipStream_t s);
+                                 const int *up_shift, int nup, hipStream_t s, int act_dtype = 0);
 // the same on e4m3 tensors: out = e4m3(act(base * base_scale + sum_j up_j * up_scale[j]) * out_inv_scale); C multiple of 16
 struct UpAddFp8Params {
     const unsigned char *base; int base_cs; float base_scale;
@@ -358,24 +361,24 @@ struct PackDesc {
     long long total;
     int cout, cin, ks, mode, KC, COUT_T, py, px;
 };
-hipError_t launch_pack_weights_batch(const PackDesc *descs_dev, int n, hipStream_t s);
+hipError_t launch_pack_weights_batch(const PackDesc *descs_dev, int n, hipStream_t s, int act_dtype = 0);
 hipError_t launch_pack_weights(const float *W, int cout, int cin, int ks, int mode, int KC, int COUT_T, bf16_raw *packed, size_t total,
-                               hipStream_t s, int py = 0, int px = 0);
+                               hipStream_t s, int py = 0, int px = 0, int act_dtype = 0);
 hipError_t launch_bn_train_forward(const bf16_raw *x, int cs, size_t P, int C, const float *gamma, const float *beta, float eps,
-                                   const bf16_raw *res, int relu, bf16_raw *y, float *mean, float *invstd, double *scratch, hipStream_t s);
+                                   const bf16_raw *res, int relu, bf16_raw *y, float *mean, float *invstd, double *scratch, hipStream_t s, int act_dtype = 0);
 hipError_t launch_bn_train_backward(const bf16_raw *x, const bf16_raw *y, const bf16_raw *dy, int cs, size_t P, int C, const float *mean,
                                     const float *invstd, const float *gamma, const float *beta, int relu, bf16_raw *dx, bf16_raw *dres,
-                                    float *dgamma, float *dbeta, double *scratch, hipStream_t s);  // y == nullptr: no residual, mask from x
-hipError_t launch_bn_train_stats(const bf16_raw *x, int cs, size_t P, int C, double *sums, double *scratch, hipStream_t s);
+                                    float *dgamma, float *dbeta, double *scratch, hipStream_t s, int act_dtype = 0);  // y == nullptr: no residual, mask from x
+hipError_t launch_bn_train_stats(const bf16_raw *x, int cs, size_t P, int C, double *sums, double *scratch, hipStream_t s, int act_dtype = 0);
 hipError_t launch_bn_train_normalize(const bf16_raw *x, int cs, size_t P, int C, const double *sums, double count, const float *gamma,
                                      const float *beta, float eps, const bf16_raw *res, int relu, bf16_raw *y, float *mean, float *invstd,
-                                     hipStream_t s);
+                                     hipStream_t s, int act_dtype = 0);
 hipError_t launch_bn_train_backward_stats(const bf16_raw *x, const bf16_raw *y, const bf16_raw *dy, int cs, size_t P, int C, const float *mean,
                                           const float *invstd, int relu, double *sums, float *dgamma, float *dbeta, double *scratch,
-                                          hipStream_t s);
+                                          hipStream_t s, int act_dtype = 0);
 hipError_t launch_bn_train_backward_apply(const bf16_raw *x, const bf16_raw *y, const bf16_raw *dy, int cs, size_t P, int C, const float *mean,
                                           const float *invstd, const float *gamma, int relu, const double *sums, double count, bf16_raw *dx,
-                                          bf16_raw *dres, double *scratch, hipStream_t s);
+                                          bf16_raw *dres, double *scratch, hipStream_t s, int act_dtype = 0);
 
 // Convolution weight gradient (conv_wgrad.hip): ks in {1,3} x stride 1, and 3x3 stride 2; channels multiples of 8
 struct WgradParams {
@@ -389,4 +392,4 @@ struct WgradParams {
 int conv_wgrad_num_workers(int B, int Ho, int Wo, int ks, int stride, int cin, int cout);
 int conv_wgrad_num_tiles(int B, int Ho, int Wo, int variant);  // with the tile width of that variant's kernel
 int conv_wgrad_variant(int ks, int stride, int Wo, int cin, int cout);  // 0..5 (conv_wgrad.hip), -1: no kernel
-hipError_t conv_wgrad_launch(const WgradParams &p, int ks, int stride, float *dw, hipStream_t s);
+hipError_t conv_wgrad_launch(const WgradParams &p, int ks, int stride, float *dw, hipStream_t s, int act_dtype = 0);

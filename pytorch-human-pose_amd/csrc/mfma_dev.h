@@ -10,6 +10,8 @@
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));  // fp16: the training path only
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));  // native vector: HIP's uint4 struct kept staging arrays in scratch
@@ -51,6 +53,29 @@ __device__ __forceinline__ unsigned round_bf16x2(float a, float b)
 }
 __device__ __forceinline__ float bf16_lo(unsigned u) { return __builtin_bit_cast(float, u << 16); }
 __device__ __forceinline__ float bf16_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
+__device__ __forceinline__ unsigned short f2bf_dev(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }
+
+// ---- fp16 pairs in a dword (the training path's second element type; the inference engine stays bf16)
+// Semantics of every fp16 store of the training kernels:
+//   * round to nearest even (v_cvt_pk_f16_f32 / v_cvt_f16_f32);
+//   * a value beyond +-65504 becomes +-inf, it is NOT saturated: the loss scaler detects an overflowing scale by it;
+//   * NaN / inf pass through (an operand of an MFMA or of the fp32 arithmetic around it, they reach every sum they enter);
+//   * subnormals are kept (the kernels are compiled in the default mode, which keeps fp16 subnormals).
+// The int16 clamp works as for bf16: fp16 is sign-magnitude too, so every negative value (-0 included) is a negative int16.
+__device__ __forceinline__ unsigned pack_f16x2(float a, float b, i16x2 floor)
+{
+    f32x2 f = {a, b};
+    const i16x2 v = __builtin_bit_cast(i16x2, __builtin_convertvector(f, f16x2));
+    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(v, floor));
+}
+__device__ __forceinline__ unsigned round_f16x2(float a, float b)
+{
+    f32x2 f = {a, b};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(f, f16x2));
+}
+__device__ __forceinline__ float f16_lo(unsigned u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u & 0xffffu)); }
+__device__ __forceinline__ float f16_hi(unsigned u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u >> 16)); }
+__device__ __forceinline__ unsigned short f2h_dev(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
 
 // 32 couts of one pixel: lanes (r,0) hold couts 8g..8g+3, lanes (r,1) couts 8g+4..8g+7 in acc[4g..4g+3].
 // Returns for m = 0,1 the 16 bytes (bf16, ReLU applied) of couts 16m+8h .. 16m+8h+7 of this lane's pixel.
@@ -133,6 +158,35 @@ __device__ __forceinline__ void lds_wait(u32x4 &v)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 }  // namespace
+
+// ---- the element type of a training kernel as a compile-time parameter: the 16-bit storage format of the activations and of the
+// packed weights, and the MFMA form that multiplies them.  Everything else of a kernel (tiling, staging, the fp32 accumulators,
+// the int16 ReLU clamp, the transposing LDS reads) does not depend on it.  ElemBF16 is the code the kernels had written out.  (Outside the
+// unnamed namespace: a kernel instantiated over these types keeps an ordinary external symbol.)
+struct ElemBF16 {
+    static __device__ __forceinline__ unsigned pack(float a, float b, i16x2 floor) { return pack_bf16x2(a, b, floor); }
+    static __device__ __forceinline__ unsigned round2(float a, float b) { return round_bf16x2(a, b); }
+    static __device__ __forceinline__ float lo(unsigned u) { return bf16_lo(u); }
+    static __device__ __forceinline__ float hi(unsigned u) { return bf16_hi(u); }
+    static __device__ __forceinline__ unsigned short cvt(float f) { return f2bf_dev(f); }
+    template <typename V>  // V: 16 bytes of eight elements (u32x4, or the i16x8 of the transposing reads)
+    static __device__ __forceinline__ f32x16 mfma(const V &a, const V &b, const f32x16 &c)
+    {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    }
+};
+struct ElemF16 {
+    static __device__ __forceinline__ unsigned pack(float a, float b, i16x2 floor) { return pack_f16x2(a, b, floor); }
+    static __device__ __forceinline__ unsigned round2(float a, float b) { return round_f16x2(a, b); }
+    static __device__ __forceinline__ float lo(unsigned u) { return f16_lo(u); }
+    static __device__ __forceinline__ float hi(unsigned u) { return f16_hi(u); }
+    static __device__ __forceinline__ unsigned short cvt(float f) { return f2h_dev(f); }
+    template <typename V>
+    static __device__ __forceinline__ f32x16 mfma(const V &a, const V &b, const f32x16 &c)
+    {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    }
+};
 
 // ---- host side of the tile-form BasicBlock kernels: one persistent workgroup per CU walks TH x TW output tiles
 typedef void (*BBTileKernel)(const BBParams);

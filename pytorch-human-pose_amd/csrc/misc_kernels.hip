@@ -5,6 +5,8 @@
 // FusionLayer.forward's low->high terms and the sum (hrnet.py:200-205,214-229): the 1x1
 // conv + BN ran at low resolution; here the nearest upsample is an index shift on read and the
 // upsampled tensors are never materialised.  One thread = 8 channels (16 B) of one pixel.
+// E: the element type (the inference engine launches ElemBF16, the training path either; mfma_dev.h)
+template <typename E>
 __global__ __launch_bounds__(256) void upadd_kernel(const UpAddParams p)
 {
     const int c8n = p.C / 8;
@@ -16,30 +18,32 @@ __global__ __launch_bounds__(256) void upadd_kernel(const UpAddParams p)
         const int y = (int)((pix / p.W) % p.H);
         const int b = (int)(pix / ((size_t)p.W * p.H));
         const uint4 bv = *reinterpret_cast<const uint4 *>(p.base + pix * p.base_cs + p.base_coff + c8 * 8);
-        float v[8] = {bf16_lo(bv.x), bf16_hi(bv.x), bf16_lo(bv.y), bf16_hi(bv.y), bf16_lo(bv.z), bf16_hi(bv.z), bf16_lo(bv.w), bf16_hi(bv.w)};
+        float v[8] = {E::lo(bv.x), E::hi(bv.x), E::lo(bv.y), E::hi(bv.y), E::lo(bv.z), E::hi(bv.z), E::lo(bv.w), E::hi(bv.w)};
 #pragma unroll
         for (int j = 0; j < 3; ++j)
             if (j < p.nup) {
                 const int sh = p.up_shift[j];
                 const size_t up = ((size_t)b * (p.H >> sh) + (y >> sh)) * (p.W >> sh) + (x >> sh);
                 const uint4 u = *reinterpret_cast<const uint4 *>(p.up[j] + up * p.up_cs[j] + c8 * 8);
-                v[0] += bf16_lo(u.x); v[1] += bf16_hi(u.x); v[2] += bf16_lo(u.y); v[3] += bf16_hi(u.y);
-                v[4] += bf16_lo(u.z); v[5] += bf16_hi(u.z); v[6] += bf16_lo(u.w); v[7] += bf16_hi(u.w);
+                v[0] += E::lo(u.x); v[1] += E::hi(u.x); v[2] += E::lo(u.y); v[3] += E::hi(u.y);
+                v[4] += E::lo(u.z); v[5] += E::hi(u.z); v[6] += E::lo(u.w); v[7] += E::hi(u.w);
             }
         if (p.relu)
 #pragma unroll
             for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
         *reinterpret_cast<uint4 *>(p.out + pix * p.out_cs + p.out_coff + c8 * 8) =
-            make_uint4(round_bf16x2(v[0], v[1]), round_bf16x2(v[2], v[3]), round_bf16x2(v[4], v[5]), round_bf16x2(v[6], v[7]));
+            make_uint4(E::round2(v[0], v[1]), E::round2(v[2], v[3]), E::round2(v[4], v[5]), E::round2(v[6], v[7]));
     }
 }
 
-hipError_t launch_upadd(const UpAddParams &p, hipStream_t s)
+hipError_t launch_upadd(const UpAddParams &p, hipStream_t s, int act_dtype)
 {
     const size_t total = (size_t)p.B * p.H * p.W * (p.C / 8);
     unsigned grid = (unsigned)((total + 255) / 256);
     if (grid > 16384) grid = 16384;
-    hipLaunchKernelGGL(upadd_kernel, dim3(grid), dim3(256), 0, s, p);
+    if (act_dtype == 0) hipLaunchKernelGGL(upadd_kernel<ElemBF16>, dim3(grid), dim3(256), 0, s, p);
+    else if (act_dtype == 1) hipLaunchKernelGGL(upadd_kernel<ElemF16>, dim3(grid), dim3(256), 0, s, p);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
@@ -49,13 +53,14 @@ __global__ __launch_bounds__(256) void upadd_mask_kernel(const bf16_raw *__restr
 {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
         const uint4 d = reinterpret_cast<const uint4 *>(dy)[i], o = reinterpret_cast<const uint4 *>(out)[i];
-        auto m = [](unsigned dv, unsigned ov) {  // bf16 pairs: keep dy where out > 0 (out is a ReLU output: > 0 <=> bits != 0 and sign clear)
+        auto m = [](unsigned dv, unsigned ov) {  // bf16 or fp16 pairs (bit tests only: one kernel serves both): keep dy where out > 0 (a ReLU output: > 0 <=> bits != 0 and sign clear)
             const unsigned lo = ((ov & 0xffffu) != 0u && !(ov & 0x8000u)) ? 0xffffu : 0u, hi_ = ((ov >> 16) != 0u && !(ov & 0x80000000u)) ? 0xffff0000u : 0u;
             return dv & (lo | hi_);
         };
         reinterpret_cast<uint4 *>(g)[i] = make_uint4(m(d.x, o.x), m(d.y, o.y), m(d.z, o.z), m(d.w, o.w));
     }
 }
+template <typename E>
 __global__ __launch_bounds__(256) void upadd_blocksum_kernel(const bf16_raw *__restrict__ g, bf16_raw *__restrict__ dup, int B, int h, int w, int C, int sh)
 {
     const int c8n = C / 8, W = w << sh;
@@ -69,16 +74,17 @@ __global__ __launch_bounds__(256) void upadd_blocksum_kernel(const bf16_raw *__r
             for (int dx_ = 0; dx_ < (1 << sh); ++dx_) {
                 const size_t src = ((size_t)b * (h << sh) + ((y << sh) + dy_)) * W + ((x << sh) + dx_);
                 const uint4 u = *reinterpret_cast<const uint4 *>(g + src * C + c8 * 8);
-                v[0] += bf16_lo(u.x); v[1] += bf16_hi(u.x); v[2] += bf16_lo(u.y); v[3] += bf16_hi(u.y);
-                v[4] += bf16_lo(u.z); v[5] += bf16_hi(u.z); v[6] += bf16_lo(u.w); v[7] += bf16_hi(u.w);
+                v[0] += E::lo(u.x); v[1] += E::hi(u.x); v[2] += E::lo(u.y); v[3] += E::hi(u.y);
+                v[4] += E::lo(u.z); v[5] += E::hi(u.z); v[6] += E::lo(u.w); v[7] += E::hi(u.w);
             }
         *reinterpret_cast<uint4 *>(dup + pix * C + c8 * 8) =
-            make_uint4(round_bf16x2(v[0], v[1]), round_bf16x2(v[2], v[3]), round_bf16x2(v[4], v[5]), round_bf16x2(v[6], v[7]));
+            make_uint4(E::round2(v[0], v[1]), E::round2(v[2], v[3]), E::round2(v[4], v[5]), E::round2(v[6], v[7]));
     }
 }
 hipError_t launch_upadd_backward(const bf16_raw *dy, const bf16_raw *out, int relu, int B, int H, int W, int C, bf16_raw *g, bf16_raw *const *dup,
-                                 const int *up_shift, int nup, hipStream_t s)
+                                 const int *up_shift, int nup, hipStream_t s, int act_dtype)
 {
+    if (act_dtype != 0 && act_dtype != 1) return hipErrorInvalidValue;
     const size_t n8 = (size_t)B * H * W * C / 8;
     const bf16_raw *gsrc = dy;
     if (relu) {
@@ -92,7 +98,8 @@ hipError_t launch_upadd_backward(const bf16_raw *dy, const bf16_raw *out, int re
         const size_t total = (size_t)B * h * w * (C / 8);
         unsigned grid = (unsigned)((total + 255) / 256);
         if (grid > 16384) grid = 16384;
-        hipLaunchKernelGGL(upadd_blocksum_kernel, dim3(grid), dim3(256), 0, s, gsrc, dup[j], B, h, w, C, sh);
+        if (act_dtype == 0) hipLaunchKernelGGL(upadd_blocksum_kernel<ElemBF16>, dim3(grid), dim3(256), 0, s, gsrc, dup[j], B, h, w, C, sh);
+        else hipLaunchKernelGGL(upadd_blocksum_kernel<ElemF16>, dim3(grid), dim3(256), 0, s, gsrc, dup[j], B, h, w, C, sh);
     }
     return hipGetLastError();
 }

@@ -1,14 +1,19 @@
 // Building blocks of the training path (first half): convolution with *current* fp32 weights
 // (forward, and the data gradient of a stride-1 conv as a forward conv with rotated, transposed weights) and train-mode
-// BatchNorm forward / backward, all on NHWC bf16 activations.  The convolution itself is the conv_mfma family; what is
+// BatchNorm forward / backward, all on NHWC bf16 or fp16 activations.  The convolution itself is the conv_mfma family; what is
 // new here is packing the weights ON THE DEVICE every step (the inference engine packs once on the host at finalize).
-#include <hip/hip_runtime.h>
+// Every kernel that touches an activation or a packed weight takes the element type E (ElemBF16 / ElemF16 of mfma_dev.h, where the fp16
+// store semantics are stated) as a template parameter; the launchers pick the instantiation by act_dtype (0 = bf16, 1 = fp16).
+// bf16_raw is the 16-bit storage of either.
+#include "mfma_dev.h"
 
-#include "kernels.h"
-
-namespace {
-__device__ __forceinline__ bf16_raw f2bf_dev(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }
-}
+// the launch of KERNEL<ElemBF16, ...> or KERNEL<ElemF16, ...> by act_dtype; anything else: hipErrorInvalidValue from the launcher
+#define HH_BY_DTYPE(act_dtype, ...)                      \
+    do {                                                 \
+        if ((act_dtype) == 0) { using E = ElemBF16; __VA_ARGS__; } \
+        else if ((act_dtype) == 1) { using E = ElemF16; __VA_ARGS__; } \
+        else return hipErrorInvalidValue;                \
+    } while (0)
 
 // packed[cg][chunk][tap][c8][co_in][j]  <-  W, see hh_pack_weights (engine.cpp) for the host twin.
 //   mode 0: conv weights W[cout][cin][ks][ks]                      -> out channel o = co, in channel i = ci, tap (ky,kx)
@@ -17,6 +22,7 @@ __device__ __forceinline__ bf16_raw f2bf_dev(float f) { return __builtin_bit_cas
 //   mode 2: data gradient of a 3x3 stride-2 conv, one output-parity phase (py, px) as a 2x2 conv over dL/dy:
 //           dX[2i+py, 2j+px] = sum_t W'[t] dY[i + ty, j + tx];  even parity uses the centre tap only (ty = 0 <-> ky = 1),
 //           odd parity ty = 0 <-> ky = 2 and ty = 1 <-> ky = 0 (same in x).  `ks` is then 2 (the packed kernel size).
+template <typename E>
 __device__ __forceinline__ void pack_weights_range(const float *__restrict__ W, int cout, int cin, int ks, int mode, int KC, int COUT_T,
                                                    bf16_raw *__restrict__ packed, size_t total, int py, int px, size_t first, size_t step)
 {
@@ -42,42 +48,45 @@ __device__ __forceinline__ void pack_weights_range(const float *__restrict__ W, 
                 v = W[(((size_t)oc * cin + ic) * ks + ky) * ks + kx];
             }
         }
-        packed[o] = f2bf_dev(v);
+        packed[o] = E::cvt(v);
     }
 }
+template <typename E>
 __global__ __launch_bounds__(256) void pack_weights_kernel(const float *__restrict__ W, int cout, int cin, int ks, int mode, int KC,
                                                            int COUT_T, bf16_raw *__restrict__ packed, size_t total, int py, int px)
 {
-    pack_weights_range(W, cout, cin, ks, mode, KC, COUT_T, packed, total, py, px, (size_t)blockIdx.x * 256 + threadIdx.x, (size_t)gridDim.x * 256);
+    pack_weights_range<E>(W, cout, cin, ks, mode, KC, COUT_T, packed, total, py, px, (size_t)blockIdx.x * 256 + threadIdx.x, (size_t)gridDim.x * 256);
 }
 // Every weight set of a training step in ONE launch (blockIdx.y = descriptor): ~700 tiny dependent launches per step cost more
 // in launch gaps than the packing itself.
+template <typename E>
 __global__ __launch_bounds__(256) void pack_weights_batch_kernel(const PackDesc *__restrict__ descs)
 {
     const PackDesc d = descs[blockIdx.y];
-    pack_weights_range(d.W, d.cout, d.cin, d.ks, d.mode, d.KC, d.COUT_T, d.packed, (size_t)d.total, d.py, d.px,
+    pack_weights_range<E>(d.W, d.cout, d.cin, d.ks, d.mode, d.KC, d.COUT_T, d.packed, (size_t)d.total, d.py, d.px,
                        (size_t)blockIdx.x * 256 + threadIdx.x, (size_t)gridDim.x * 256);
 }
 
-hipError_t launch_pack_weights_batch(const PackDesc *descs_dev, int n, hipStream_t s)
+hipError_t launch_pack_weights_batch(const PackDesc *descs_dev, int n, hipStream_t s, int act_dtype)
 {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(pack_weights_batch_kernel, dim3(32, n), dim3(256), 0, s, descs_dev);
+    HH_BY_DTYPE(act_dtype, hipLaunchKernelGGL(pack_weights_batch_kernel<E>, dim3(32, n), dim3(256), 0, s, descs_dev));
     return hipGetLastError();
 }
 
 hipError_t launch_pack_weights(const float *W, int cout, int cin, int ks, int mode, int KC, int COUT_T, bf16_raw *packed, size_t total,
-                               hipStream_t s, int py, int px)
+                               hipStream_t s, int py, int px, int act_dtype)
 {
     unsigned grid = (unsigned)((total + 255) / 256);
     if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(grid), dim3(256), 0, s, W, cout, cin, ks, mode, KC, COUT_T, packed, total, py, px);
+    HH_BY_DTYPE(act_dtype, hipLaunchKernelGGL(pack_weights_kernel<E>, dim3(grid), dim3(256), 0, s, W, cout, cin, ks, mode, KC, COUT_T, packed, total, py, px));
     return hipGetLastError();
 }
 
 // ------------------------------------------------------------------ train-mode BatchNorm (nn.BatchNorm2d, training=True)
-// x [P, C] bf16 (P = B*H*W pixels, channel stride cs).  Statistics in fp32 with double partial sums in a fixed order.
+// x [P, C] bf16 / fp16 (P = B*H*W pixels, channel stride cs).  Statistics in fp32 with double partial sums in a fixed order.
 // stats kernel: partial[block][c] = {sum x, sum x^2} over the block's pixels; finalize: mean, biased var -> invstd.
+template <typename E>
 __global__ __launch_bounds__(256) void bn_partial_kernel(const bf16_raw *__restrict__ x, int cs, size_t P, int C, double *__restrict__ partial)
 {
     // thread = (pixel lane pl = tid / C8, channel group g = tid % C8) over 8 channels; C % 8 == 0, C <= 2048
@@ -91,7 +100,7 @@ __global__ __launch_bounds__(256) void bn_partial_kernel(const bf16_raw *__restr
             const unsigned u[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float a = __builtin_bit_cast(float, u[i] << 16), b = __builtin_bit_cast(float, u[i] & 0xffff0000u);
+                const float a = E::lo(u[i]), b = E::hi(u[i]);
                 s[2 * i] += a; q[2 * i] += (double)a * a; s[2 * i + 1] += b; q[2 * i + 1] += (double)b * b;
             }
         };
@@ -144,6 +153,7 @@ __device__ __forceinline__ float bn_affine(float x, float mean, float invstd, fl
     return (x - mean) * invstd * gamma + beta;
 }
 // y = act(gamma * (x - mean) * invstd + beta (+ res))
+template <typename E>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const bf16_raw *__restrict__ x, int cs, size_t P, int C, const float *__restrict__ mean,
                                                        const float *__restrict__ invstd, const float *__restrict__ gamma,
                                                        const float *__restrict__ beta, const bf16_raw *__restrict__ res, int relu,
@@ -161,29 +171,29 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const bf16_raw *__restric
         unsigned o[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            float f[2] = {__builtin_bit_cast(float, u[k] << 16), __builtin_bit_cast(float, u[k] & 0xffff0000u)};
-            const float r[2] = {__builtin_bit_cast(float, ru[k] << 16), __builtin_bit_cast(float, ru[k] & 0xffff0000u)};
+            float f[2] = {E::lo(u[k]), E::hi(u[k])};
+            const float r[2] = {E::lo(ru[k]), E::hi(ru[k])};
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int c = g * 8 + 2 * k + h;
                 float t = bn_affine(f[h], mean[c], invstd[c], gamma[c], beta[c]) + r[h];
                 f[h] = relu ? fmaxf(t, 0.f) : t;
             }
-            o[k] = (unsigned)f2bf_dev(f[0]) | ((unsigned)f2bf_dev(f[1]) << 16);
+            o[k] = (unsigned)E::cvt(f[0]) | ((unsigned)E::cvt(f[1]) << 16);
         }
         *reinterpret_cast<uint4 *>(y + p * cs + g * 8) = make_uint4(o[0], o[1], o[2], o[3]);
     }
 }
 
 hipError_t launch_bn_train_forward(const bf16_raw *x, int cs, size_t P, int C, const float *gamma, const float *beta, float eps,
-                                   const bf16_raw *res, int relu, bf16_raw *y, float *mean, float *invstd, double *scratch, hipStream_t s)
+                                   const bf16_raw *res, int relu, bf16_raw *y, float *mean, float *invstd, double *scratch, hipStream_t s, int act_dtype)
 {
     const int nblocks = HH_BN_BLOCKS;
-    hipLaunchKernelGGL(bn_partial_kernel, dim3(nblocks), dim3(256), 0, s, x, cs, P, C, scratch);
+    HH_BY_DTYPE(act_dtype, hipLaunchKernelGGL(bn_partial_kernel<E>, dim3(nblocks), dim3(256), 0, s, x, cs, P, C, scratch));
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, s, scratch, nblocks, C, (double)P, eps, mean, invstd);
     unsigned grid = (unsigned)((P * (C / 8) + 255) / 256);
     if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid), dim3(256), 0, s, x, cs, P, C, mean, invstd, gamma, beta, res, relu, y);
+    HH_BY_DTYPE(act_dtype, hipLaunchKernelGGL(bn_apply_kernel<E>, dim3(grid), dim3(256), 0, s, x, cs, P, C, mean, invstd, gamma, beta, res, relu, y));
     return hipGetLastError();
 }
 
@@ -192,7 +202,7 @@ hipError_t launch_bn_train_forward(const bf16_raw *x, int cs, size_t P, int C, c
 //   dx = gamma * invstd * (g - dbeta / P - xhat * dgamma / P);  dres = g (returned in place of dy when res was used)
 // HASY = false (a BatchNorm without a residual input): y is not read -- without ReLU nothing needs it, with ReLU the mask y > 0 is
 // recomputed from x (bn_affine(x) > 0: what the forward rounded to bf16 and clamped), one tensor pass less in both kernels
-template <bool HASY>
+template <typename E, bool HASY>
 __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const bf16_raw *__restrict__ x, const bf16_raw *__restrict__ y,
                                                              const bf16_raw *__restrict__ dy, int cs, size_t P, int C,
                                                              const float *__restrict__ mean, const float *__restrict__ invstd,
@@ -214,10 +224,10 @@ __global__ __launch_bounds__(256) void bn_bwd_partial_kernel(const bf16_raw *__r
             for (int k = 0; k < 4; ++k)
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    const float xf = __builtin_bit_cast(float, h ? (xu[k] & 0xffff0000u) : (xu[k] << 16));
-                    const float yf = HASY ? __builtin_bit_cast(float, h ? (yu[k] & 0xffff0000u) : (yu[k] << 16))
+                    const float xf = (h ? E::hi(xu[k]) : E::lo(xu[k]));
+                    const float yf = HASY ? (h ? E::hi(yu[k]) : E::lo(yu[k]))
                                           : bn_affine(xf, mu[2 * k + h], is[2 * k + h], ga[2 * k + h], be[2 * k + h]);
-                    float gf = __builtin_bit_cast(float, h ? (du[k] & 0xffff0000u) : (du[k] << 16));
+                    float gf = (h ? E::hi(du[k]) : E::lo(du[k]));
                     if (relu && !(yf > 0.f)) gf = 0.f;
                     s[2 * k + h] += gf;
                     q[2 * k + h] += (double)gf * ((xf - mu[2 * k + h]) * is[2 * k + h]);
@@ -265,7 +275,7 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const double *__re
     dbeta[c] = (float)a;
     dgamma[c] = (float)b;
 }
-template <bool HASY>
+template <typename E, bool HASY>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_raw *__restrict__ x, const bf16_raw *__restrict__ y,
                                                            const bf16_raw *__restrict__ dy, int cs, size_t P, int C,
                                                            const float *__restrict__ mean, const float *__restrict__ invstd,
@@ -298,17 +308,17 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_raw *__res
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int c = 2 * k + h;
-                const float xf = __builtin_bit_cast(float, h ? (xu[k] & 0xffff0000u) : (xu[k] << 16));
-                const float yf = HASY ? __builtin_bit_cast(float, h ? (yu[k] & 0xffff0000u) : (yu[k] << 16))
+                const float xf = (h ? E::hi(xu[k]) : E::lo(xu[k]));
+                const float yf = HASY ? (h ? E::hi(yu[k]) : E::lo(yu[k]))
                                       : bn_affine(xf, mu[c], is[c], ga[c], be[c]);
-                float gf = __builtin_bit_cast(float, h ? (du[k] & 0xffff0000u) : (du[k] << 16));
+                float gf = (h ? E::hi(du[k]) : E::lo(du[k]));
                 if (relu && !(yf > 0.f)) gf = 0.f;
                 const float xh = (xf - mu[c]) * is[c];
                 out[h] = ga[c] * is[c] * (gf - db[c] * invP - xh * dg[c] * invP);
                 gr[h] = gf;
             }
-            o[k] = (unsigned)f2bf_dev(out[0]) | ((unsigned)f2bf_dev(out[1]) << 16);
-            r[k] = (unsigned)f2bf_dev(gr[0]) | ((unsigned)f2bf_dev(gr[1]) << 16);
+            o[k] = (unsigned)E::cvt(out[0]) | ((unsigned)E::cvt(out[1]) << 16);
+            r[k] = (unsigned)E::cvt(gr[0]) | ((unsigned)E::cvt(gr[1]) << 16);
         }
         *reinterpret_cast<uint4 *>(dx + p * cs + g * 8) = make_uint4(o[0], o[1], o[2], o[3]);
         if (dres) *reinterpret_cast<uint4 *>(dres + p * cs + g * 8) = make_uint4(r[0], r[1], r[2], r[3]);
@@ -318,20 +328,20 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_raw *__res
 // y == nullptr: a BatchNorm without a residual input (dres must be nullptr, beta is then needed for the mask); otherwise beta is unused
 hipError_t launch_bn_train_backward(const bf16_raw *x, const bf16_raw *y, const bf16_raw *dy, int cs, size_t P, int C, const float *mean,
                                     const float *invstd, const float *gamma, const float *beta, int relu, bf16_raw *dx, bf16_raw *dres,
-                                    float *dgamma, float *dbeta, double *scratch, hipStream_t s)
+                                    float *dgamma, float *dbeta, double *scratch, hipStream_t s, int act_dtype)
 {
     const int nblocks = HH_BN_BLOCKS;
     unsigned grid = (unsigned)((P * (C / 8) + 255) / 256);
     if (grid > 8192) grid = 8192;
     const float invP = (float)(1.0 / (double)P);
     if (y) {
-        hipLaunchKernelGGL(bn_bwd_partial_kernel<true>, dim3(nblocks), dim3(256), 0, s, x, y, dy, cs, P, C, mean, invstd, gamma, beta, relu, scratch);
+        HH_BY_DTYPE(act_dtype, hipLaunchKernelGGL((bn_bwd_partial_kernel<E, true>), dim3(nblocks), dim3(256), 0, s, x, y, dy, cs, P, C, mean, invstd, gamma, beta, relu, scratch));
         hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, s, scratch, nblocks, C, dgamma, dbeta);
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(grid), dim3(256), 0, s, x, y, dy, cs, P, C, mean, invstd, gamma, beta, dgamma, dbeta, relu, invP, dx, dres);
+        HH_BY_DTYPE(act_dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<E, true>), dim3(grid), dim3(256), 0, s, x, y, dy, cs, P, C, mean, invstd, gamma, beta, dgamma, dbeta, relu, invP, dx, dres));
     } else {
-        hipLaunchKernelGGL(bn_bwd_partial_kernel<false>, dim3(nblocks), dim3(256), 0, s, x, y, dy, cs, P, C, mean, invstd, gamma, beta, relu, scratch);
+        HH_BY_DTYPE(act_dtype, hipLaunchKernelGGL((bn_bwd_partial_kernel<E, false>), dim3(nblocks), dim3(256), 0, s, x, y, dy, cs, P, C, mean, invstd, gamma, beta, relu, scratch));
         hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, s, scratch, nblocks, C, dgamma, dbeta);
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(grid), dim3(256), 0, s, x, y, dy, cs, P, C, mean, invstd, gamma, beta, dgamma, dbeta, relu, invP, dx, dres);
+        HH_BY_DTYPE(act_dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<E, false>), dim3(grid), dim3(256), 0, s, x, y, dy, cs, P, C, mean, invstd, gamma, beta, dgamma, dbeta, relu, invP, dx, dres));
     }
     return hipGetLastError();
 }
@@ -368,39 +378,39 @@ __global__ void bn_sums_to_f32_kernel(const double *__restrict__ sums, int C, fl
     b[c] = (float)sums[2 * c + 1];
 }
 
-hipError_t launch_bn_train_stats(const bf16_raw *x, int cs, size_t P, int C, double *sums, double *scratch, hipStream_t s)
+hipError_t launch_bn_train_stats(const bf16_raw *x, int cs, size_t P, int C, double *sums, double *scratch, hipStream_t s, int act_dtype)
 {
-    hipLaunchKernelGGL(bn_partial_kernel, dim3(HH_BN_BLOCKS), dim3(256), 0, s, x, cs, P, C, scratch);
+    HH_BY_DTYPE(act_dtype, hipLaunchKernelGGL(bn_partial_kernel<E>, dim3(HH_BN_BLOCKS), dim3(256), 0, s, x, cs, P, C, scratch));
     hipLaunchKernelGGL(bn_finalize_sums_kernel, dim3((C + 3) / 4), dim3(256), 0, s, scratch, HH_BN_BLOCKS, C, sums, (float *)nullptr, (float *)nullptr);
     return hipGetLastError();
 }
 hipError_t launch_bn_train_normalize(const bf16_raw *x, int cs, size_t P, int C, const double *sums, double count, const float *gamma,
                                      const float *beta, float eps, const bf16_raw *res, int relu, bf16_raw *y, float *mean, float *invstd,
-                                     hipStream_t s)
+                                     hipStream_t s, int act_dtype)
 {
     hipLaunchKernelGGL(bn_stats_from_sums_kernel, dim3((C + 255) / 256), dim3(256), 0, s, sums, C, count, eps, mean, invstd);
     unsigned grid = (unsigned)((P * (C / 8) + 255) / 256);
     if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid), dim3(256), 0, s, x, cs, P, C, mean, invstd, gamma, beta, res, relu, y);
+    HH_BY_DTYPE(act_dtype, hipLaunchKernelGGL(bn_apply_kernel<E>, dim3(grid), dim3(256), 0, s, x, cs, P, C, mean, invstd, gamma, beta, res, relu, y));
     return hipGetLastError();
 }
 hipError_t launch_bn_train_backward_stats(const bf16_raw *x, const bf16_raw *y, const bf16_raw *dy, int cs, size_t P, int C, const float *mean,
                                           const float *invstd, int relu, double *sums, float *dgamma, float *dbeta, double *scratch,
-                                          hipStream_t s)
+                                          hipStream_t s, int act_dtype)
 {
-    hipLaunchKernelGGL(bn_bwd_partial_kernel<true>, dim3(HH_BN_BLOCKS), dim3(256), 0, s, x, y, dy, cs, P, C, mean, invstd, (const float *)nullptr, (const float *)nullptr, relu, scratch);
+    HH_BY_DTYPE(act_dtype, hipLaunchKernelGGL((bn_bwd_partial_kernel<E, true>), dim3(HH_BN_BLOCKS), dim3(256), 0, s, x, y, dy, cs, P, C, mean, invstd, (const float *)nullptr, (const float *)nullptr, relu, scratch));
     // this rank's sums are also its dbeta / dgamma (the parameter gradients are averaged by DDP like every other one)
     hipLaunchKernelGGL(bn_finalize_sums_kernel, dim3((C + 3) / 4), dim3(256), 0, s, scratch, HH_BN_BLOCKS, C, sums, dbeta, dgamma);
     return hipGetLastError();
 }
 hipError_t launch_bn_train_backward_apply(const bf16_raw *x, const bf16_raw *y, const bf16_raw *dy, int cs, size_t P, int C, const float *mean,
                                           const float *invstd, const float *gamma, int relu, const double *sums, double count, bf16_raw *dx,
-                                          bf16_raw *dres, double *scratch, hipStream_t s)
+                                          bf16_raw *dres, double *scratch, hipStream_t s, int act_dtype)
 {
     float *ga = reinterpret_cast<float *>(scratch), *gb = ga + C;  // global sum g, sum g * xhat as floats
     hipLaunchKernelGGL(bn_sums_to_f32_kernel, dim3((C + 255) / 256), dim3(256), 0, s, sums, C, ga, gb);
     unsigned grid = (unsigned)((P * (C / 8) + 255) / 256);
     if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(grid), dim3(256), 0, s, x, y, dy, cs, P, C, mean, invstd, gamma, (const float *)nullptr, gb, ga, relu, (float)(1.0 / count), dx, dres);
+    HH_BY_DTYPE(act_dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<E, true>), dim3(grid), dim3(256), 0, s, x, y, dy, cs, P, C, mean, invstd, gamma, (const float *)nullptr, gb, ga, relu, (float)(1.0 / count), dx, dres));
     return hipGetLastError();
 }

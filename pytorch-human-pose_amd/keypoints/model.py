@@ -101,10 +101,27 @@ class KeypointsModel:
 
 class KeypointsModule:
     """`KeypointsModule.training_step` (keypoints/module.py:43-71): forward, AE loss, backward, optimizer step.  The reference
-    runs under fp16 autocast with a GradScaler; this path keeps activations in bf16 (no scaler needed) and parameters fp32."""
+    runs under fp16 autocast with one GradScaler per optimizer, whose state goes into every checkpoint (base/module.py:71,109-127).
+    precision="fp16" is that: fp16 activations (HigherHRNet.set_train_precision), `scalers = {"optim": GradScaler}`, and the
+    reference's sequence scale(loss).backward() / scaler.step(optimizer) / scaler.update(); the metrics are the unscaled values.
+    precision="bf16" (default) keeps activations in bf16, which needs no scaler: `scalers` is {}.  Parameters are fp32 either way."""
 
-    def __init__(self, model: KeypointsModel, loss_fn, optimizer: torch.optim.Optimizer):
-        self.model, self.loss_fn, self.optimizer = model, loss_fn, optimizer
+    PRECISIONS = ("bf16", "fp16")
+
+    def __init__(self, model: KeypointsModel, loss_fn, optimizer: torch.optim.Optimizer, precision: str = "bf16"):
+        if precision not in self.PRECISIONS:
+            raise ValueError(f"KeypointsModule: precision {precision!r} is not one of {self.PRECISIONS}")
+        self.model, self.loss_fn, self.optimizer, self.precision = model, loss_fn, optimizer, precision
+        self.scalers: dict = {"optim": torch.amp.GradScaler("cuda")} if precision == "fp16" else {}
+        model._bare().set_train_precision(precision)
+
+    def state_dict(self) -> dict:
+        """The module's own checkpoint entries in the reference's format (base/module.py:109-127): {"scalers": {name: state}}."""
+        return {"scalers": {name: scaler.state_dict() for name, scaler in self.scalers.items()}}
+
+    def load_state_dict(self, state_dict: dict) -> None:
+        for name, scaler in self.scalers.items():
+            scaler.load_state_dict(state_dict["scalers"][name])
 
     def batch_to_device(self, batch):
         images, heatmaps, masks, joints = batch
@@ -120,8 +137,14 @@ class KeypointsModule:
             loss = loss + hl
         loss = loss + push_losses[0] + pull_losses[0]
         self.optimizer.zero_grad()
-        loss.backward()
-        self.optimizer.step()
+        scaler = self.scalers.get("optim")
+        if scaler is None:
+            loss.backward()
+            self.optimizer.step()
+        else:  # (module.py:55-60; a step whose gradients hold an inf / NaN is skipped and the scale halved)
+            scaler.scale(loss).backward()
+            scaler.step(self.optimizer)
+            scaler.update()
         self.model._bare().mark_dirty()
         metrics = {"loss": loss.detach().item()}
         for i, hl in enumerate(hm_losses):

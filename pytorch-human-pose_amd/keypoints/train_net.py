@@ -4,8 +4,12 @@ The layer graph is the reference's (`src/keypoints/architectures/hrnet.py:29-385
 the shim's parameter tree.  Convolutions (forward, data gradient, weight gradient) and train-mode BatchNorm (+ residual,
 + ReLU, forward and backward) are `torch.autograd.Function`s over the C-ABI ops of `train_ops`; torch autograd is only the
 tape, and the glue between kernels (nearest upsample, sums of the fusion layers, channel concat / slicing, bias adds) are
-torch elementwise ops on the same bf16 channels_last tensors.  Activations are bf16 (the reference trains under fp16
-autocast, `module.py:50`), parameters and their gradients fp32, so torch optimizers, GradScaler-free bf16 training and
+torch elementwise ops on the same channels_last tensors.  The activation type is the net's (`HigherHRNet.set_train_precision`):
+bf16 (the default; no loss scaling needed) or fp16, the reference's own (it trains under fp16 autocast with a GradScaler,
+`module.py:43-71`; `KeypointsModule(precision="fp16")` runs that sequence).  Nothing here names the type: the input cast takes it
+from the net, every op returns the type it was given, and the fp32 gradients the loss hands back are cast to it by autograd where
+they enter the last convolutions (the backward of the `.float()` at the end of the forward) -- in fp16 that is where an oversized
+loss scale first turns into inf.  Parameters and their gradients are fp32, so torch optimizers, GradScaler and
 DistributedDataParallel (gradient all-reduce over RCCL) work on the module unchanged.
 """
 from __future__ import annotations
@@ -22,7 +26,7 @@ from . import train_ops as ops
 class _ResBox:
     """The gradient a residual unit's skip connection carries (hrnet.py:62-74,108-124: `out += identity`), handed from the last
     BatchNorm's backward straight to the first conv's: that conv's data-gradient launch starts its accumulators from it (the
-    residual input of the conv kernels), so dL/dx = conv1's data gradient + skip gradient is rounded to bf16 once and autograd's
+    residual input of the conv kernels), so dL/dx = conv1's data gradient + skip gradient is rounded to 16 bits once and autograd's
     separate elementwise add per unit (111 launches per step) is gone.  The unit's backward always runs bn_last -> ... -> conv1."""
     __slots__ = ("g",)
 
@@ -147,12 +151,12 @@ def conv(x: Tensor, m: nn.Conv2d, stride: int | None = None, box: _ResBox | None
 _PACKED: list = [None]  # {(id(weight), stride): (forward-packed, data-gradient-packed)} of the forward in flight (_refresh_packed)
 
 
-def _refresh_packed(net) -> None:
+def _refresh_packed(net, act) -> None:
     """Pack the weights of every conv whose channel counts the kernels take unpadded - forward layout and data-gradient
     layout - in ONE launch per step (ops.PackedConvWeights) instead of one launch per conv call.  The copies are read by this
     forward and the backward that follows it; they go stale with the optimizer step and are refreshed by the next forward."""
     cache = getattr(net, "_train_packed", None)
-    if cache is None or not cache[0].pointers_current():
+    if cache is None or not cache[0].pointers_current() or cache[0].dtype != act:
         entries, index = [], {}
         for m in net.modules():
             if isinstance(m, nn.Conv2d) and m.weight.is_cuda and m.weight.dtype == torch.float32:
@@ -162,7 +166,7 @@ def _refresh_packed(net) -> None:
                     continue
                 index[(id(m.weight), stride)] = (len(entries), len(entries) + 1)
                 entries += [(m.weight, stride, False), (m.weight, stride, True)]
-        pw = ops.PackedConvWeights(entries)
+        pw = ops.PackedConvWeights(entries, act)
         cache = (pw, {k: (pw.buffers[a], pw.buffers[b]) for k, (a, b) in index.items()})
         net._train_packed = cache
     cache[0].refresh()
@@ -236,7 +240,7 @@ def deconv_k4s2(x: Tensor, m: nn.ConvTranspose2d) -> Tensor:
         x = F.pad(x, (0, 0, 0, 0, 0, cin_p - x.shape[1]))
     x = x.contiguous(memory_format=torch.channels_last)
     B, _, H, W = x.shape
-    y = torch.empty((B, cout, 2 * H, 2 * W), device=x.device, dtype=torch.bfloat16, memory_format=torch.channels_last)  # every phase is written
+    y = torch.empty((B, cout, 2 * H, 2 * W), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)  # every phase is written
     for py in range(2):
         for px in range(2):
             ky = (3, 1) if py == 0 else (2, 0)
@@ -306,8 +310,9 @@ def higher_hrnet_train_forward(net, images: Tensor):
     bb = net.backbone
     _PENDING_STATS.clear()
     _SYNC[0] = getattr(net, "sync_batchnorm", None)  # set by KeypointsModel.to_DDP(..., use_batchnorm=True)
-    _refresh_packed(net)
-    x = images.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+    act = ops.PRECISION_DTYPES[getattr(net, "train_precision", "bf16")]  # the activation type of this forward and its backward
+    _refresh_packed(net, act)
+    x = images.to(act).contiguous(memory_format=torch.channels_last)
     x = bn(conv(x, bb.conv1), bb.bn1, relu=True)
     x = bn(conv(x, bb.conv2), bb.bn2, relu=True)
     xs = [x]

@@ -1,5 +1,8 @@
-"""Python face of the training building blocks (`hh_conv2d`, `hh_bn_train_*`): NHWC bf16 activations as torch tensors
-in channels_last memory format, fp32 parameters.  `train_net.py` assembles them into the net's training forward."""
+"""Python face of the training building blocks (`hh_conv2d`, `hh_bn_train_*`): NHWC bf16 or fp16 activations as torch tensors
+in channels_last memory format, fp32 parameters.  `train_net.py` assembles them into the net's training forward.
+
+Every op takes the element type from its first activation, raises `HHError` when another activation of the same call has a different
+one, and returns tensors of the type it was given (the `*_dt` entry points of include/hhrnet.h, where the fp16 semantics are stated)."""
 from __future__ import annotations
 
 import torch
@@ -8,11 +11,23 @@ from torch import Tensor
 from .. import _lib
 
 
+ACT_DTYPES = {torch.bfloat16: _lib.ACT_BF16, torch.float16: _lib.ACT_F16}
+PRECISION_DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16}  # the names of HigherHRNet.set_train_precision / KeypointsModule(precision=)
+
+
 def _nhwc(x: Tensor) -> Tensor:
-    """[B,C,H,W] bf16 tensor whose memory is NHWC (channels_last); returns it contiguous in that format."""
-    if not x.is_cuda or x.dtype != torch.bfloat16 or x.dim() != 4:
-        raise _lib.HHError("expected a 4-d CUDA/HIP bfloat16 tensor: there is no CPU path")
+    """[B,C,H,W] bf16 / fp16 tensor whose memory is NHWC (channels_last); returns it contiguous in that format."""
+    if not x.is_cuda or x.dtype not in ACT_DTYPES or x.dim() != 4:
+        raise _lib.HHError("expected a 4-d CUDA/HIP bfloat16 or float16 tensor: there is no CPU path")
     return x.contiguous(memory_format=torch.channels_last)
+
+
+def _act(first: Tensor, *others) -> int:
+    """the act_dtype of a call: that of its first activation; every other activation (None: absent) must have the same type"""
+    for t in others:
+        if t is not None and t.dtype != first.dtype:
+            raise _lib.HHError(f"the activations of one call must share one element type: {first.dtype} and {t.dtype}")
+    return ACT_DTYPES[first.dtype]
 
 
 def conv2d(x: Tensor, w: Tensor, stride: int = 1, bias: Tensor | None = None, res: Tensor | None = None, relu: bool = False,
@@ -30,15 +45,16 @@ def conv2d(x: Tensor, w: Tensor, stride: int = 1, bias: Tensor | None = None, re
         mode = (2 if stride == 2 else 1) if data_grad else 0
         co = cin if data_grad else cout
         Ho, Wo = (2 * H, 2 * W) if mode == 2 else ((H // 2, W // 2) if stride == 2 else (H, W))
-        y = torch.empty((B, co, Ho, Wo), device=x.device, dtype=torch.bfloat16, memory_format=torch.channels_last)
+        y = torch.empty((B, co, Ho, Wo), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
         if res is not None:
             res = _nhwc(res)
+        dt = _act(x, res, packed)  # (the packed weights carry the type they were packed with)
         stream = torch.cuda.current_stream(x.device).cuda_stream
         py_, px_ = pad if pad is not None else (-1, -1)
         with torch.cuda.device(x.device):
-            _lib.check(lib.hh_conv2d_packed(x.data_ptr(), B, H, W, cin, packed.data_ptr(), cout, ks, stride, mode, py_, px_,
-                                            bias.data_ptr() if bias is not None else None, res.data_ptr() if res is not None else None,
-                                            int(relu), y.data_ptr(), stream))
+            _lib.check(lib.hh_conv2d_packed_dt(dt, x.data_ptr(), B, H, W, cin, packed.data_ptr(), cout, ks, stride, mode, py_, px_,
+                                               bias.data_ptr() if bias is not None else None, res.data_ptr() if res is not None else None,
+                                               int(relu), y.data_ptr(), stream))
         return y
     w = w.detach().to(x.device, torch.float32).contiguous()
     if Cx != (cout if data_grad else cin):
@@ -49,7 +65,7 @@ def conv2d(x: Tensor, w: Tensor, stride: int = 1, bias: Tensor | None = None, re
         Ho, Wo = 2 * H, 2 * W  # dL/dx of a stride-2 conv lives on the input grid
     else:
         Ho, Wo = (H // 2, W // 2) if stride == 2 else (H, W)
-    y = torch.empty((B, co, Ho, Wo), device=x.device, dtype=torch.bfloat16, memory_format=torch.channels_last)
+    y = torch.empty((B, co, Ho, Wo), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
     nbytes = lib.hh_conv2d_workspace_bytes(cin, cout, ks, mode)
     if nbytes < 0:
         raise _lib.HHError("conv2d: no kernel family for this shape")
@@ -61,9 +77,9 @@ def conv2d(x: Tensor, w: Tensor, stride: int = 1, bias: Tensor | None = None, re
     stream = torch.cuda.current_stream(x.device).cuda_stream
     with torch.cuda.device(x.device):
         py_, px_ = pad if pad is not None else (-1, -1)
-        _lib.check(lib.hh_conv2d(x.data_ptr(), B, H, W, cin, w.data_ptr(), cout, ks, stride, mode, py_, px_,
-                                 bias.data_ptr() if bias is not None else None, res.data_ptr() if res is not None else None,
-                                 int(relu), y.data_ptr(), ws.data_ptr(), stream))
+        _lib.check(lib.hh_conv2d_dt(_act(x, res), x.data_ptr(), B, H, W, cin, w.data_ptr(), cout, ks, stride, mode, py_, px_,
+                                    bias.data_ptr() if bias is not None else None, res.data_ptr() if res is not None else None,
+                                    int(relu), y.data_ptr(), ws.data_ptr(), stream))
     return y
 
 
@@ -80,9 +96,9 @@ def bn_train_forward(x: Tensor, gamma: Tensor, beta: Tensor, eps: float = 1e-5, 
         res = _nhwc(res)
     stream = torch.cuda.current_stream(x.device).cuda_stream
     with torch.cuda.device(x.device):
-        _lib.check(lib.hh_bn_train_forward(x.data_ptr(), B * H * W, C, gamma.float().contiguous().data_ptr(), beta.float().contiguous().data_ptr(),
-                                           eps, res.data_ptr() if res is not None else None, int(relu), y.data_ptr(), mean.data_ptr(),
-                                           invstd.data_ptr(), scratch.data_ptr(), stream))
+        _lib.check(lib.hh_bn_train_forward_dt(_act(x, res), x.data_ptr(), B * H * W, C, gamma.float().contiguous().data_ptr(),
+                                              beta.float().contiguous().data_ptr(), eps, res.data_ptr() if res is not None else None, int(relu),
+                                              y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), scratch.data_ptr(), stream))
     return y, mean, invstd
 
 
@@ -101,9 +117,9 @@ def bn_train_backward(x: Tensor, y, dy: Tensor, mean: Tensor, invstd: Tensor, ga
         scratch = torch.empty(256 * C * 2, device=x.device, dtype=torch.float64)
         g, b = gamma.float().contiguous(), beta.float().contiguous()
         with torch.cuda.device(x.device):
-            _lib.check(lib.hh_bn_train_backward_plain(x.data_ptr(), dy.data_ptr(), B * H * W, C, mean.data_ptr(), invstd.data_ptr(), g.data_ptr(),
-                                                      b.data_ptr(), int(relu), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                                      scratch.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream))
+            _lib.check(lib.hh_bn_train_backward_plain_dt(_act(x, dy), x.data_ptr(), dy.data_ptr(), B * H * W, C, mean.data_ptr(), invstd.data_ptr(),
+                                                         g.data_ptr(), b.data_ptr(), int(relu), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                                                         scratch.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream))
         return dx, dgamma, dbeta, None
     x, y, dy = _nhwc(x), _nhwc(y), _nhwc(dy)
     B, C, H, W = x.shape
@@ -115,18 +131,21 @@ def bn_train_backward(x: Tensor, y, dy: Tensor, mean: Tensor, invstd: Tensor, ga
     stream = torch.cuda.current_stream(x.device).cuda_stream
     g = gamma.float().contiguous()
     with torch.cuda.device(x.device):
-        _lib.check(lib.hh_bn_train_backward(x.data_ptr(), y.data_ptr(), dy.data_ptr(), B * H * W, C, mean.data_ptr(), invstd.data_ptr(),
-                                            g.data_ptr(), int(relu), dx.data_ptr(), dres.data_ptr() if dres is not None else None,
-                                            dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr(), stream))
+        _lib.check(lib.hh_bn_train_backward_dt(_act(x, y, dy), x.data_ptr(), y.data_ptr(), dy.data_ptr(), B * H * W, C, mean.data_ptr(),
+                                               invstd.data_ptr(), g.data_ptr(), int(relu), dx.data_ptr(), dres.data_ptr() if dres is not None else None,
+                                               dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr(), stream))
     return dx, dgamma, dbeta, dres
 
 
 class PackedConvWeights:
-    """bf16 kernel-layout copies of a set of conv weights, all refreshed by ONE launch (`refresh`, once per training step
-    before the forward).  entries: (weight [cout,cin,ks,ks] fp32 CUDA parameter, stride, data_grad)."""
+    """Kernel-layout copies (bf16, or fp16 with dtype=torch.float16) of a set of conv weights, all refreshed by ONE launch (`refresh`,
+    once per training step before the forward).  entries: (weight [cout,cin,ks,ks] fp32 CUDA parameter, stride, data_grad)."""
 
-    def __init__(self, entries: list):
+    def __init__(self, entries: list, dtype: torch.dtype = torch.bfloat16):
         import ctypes as C
+        if dtype not in ACT_DTYPES:
+            raise _lib.HHError(f"PackedConvWeights: dtype must be torch.bfloat16 or torch.float16, not {dtype}")
+        self.dtype = dtype
         lib = _lib.load()
         self.n = len(entries)
         self.buffers: list[Tensor] = []
@@ -139,7 +158,7 @@ class PackedConvWeights:
             nel = lib.hh_conv2d_packed_elems(cin, cout, ks, stride, mode)
             if nel < 0:
                 raise _lib.HHError(f"no kernel family for conv weights {tuple(w.shape)} (stride {stride}, data_grad={data_grad})")
-            self.buffers.append(torch.empty(nel, device=dev, dtype=torch.bfloat16))
+            self.buffers.append(torch.empty(nel, device=dev, dtype=dtype))
             shapes[5 * i:5 * i + 5] = [cout, cin, ks, stride, mode]
         self._shapes = shapes
         self._w = (C.c_void_p * self.n)(*[w.data_ptr() for w, _, _ in entries])
@@ -156,7 +175,7 @@ class PackedConvWeights:
         dev = self._descs.device
         stream = torch.cuda.current_stream(dev).cuda_stream
         with torch.cuda.device(dev):
-            _lib.check(lib.hh_pack_conv_weights_batch(self.n, self._w, self._p, self._shapes, self._descs.data_ptr(), stream))
+            _lib.check(lib.hh_pack_conv_weights_batch_dt(ACT_DTYPES[self.dtype], self.n, self._w, self._p, self._shapes, self._descs.data_ptr(), stream))
 
 
 def _all_reduce_sums(sums: Tensor, group) -> None:
@@ -180,12 +199,13 @@ def sync_bn_train_forward(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, re
         res = _nhwc(res)
     stream = torch.cuda.current_stream(x.device).cuda_stream
     with torch.cuda.device(x.device):
-        _lib.check(lib.hh_bn_train_stats(x.data_ptr(), P, C, sums.data_ptr(), scratch.data_ptr(), stream))
+        dt = _act(x, res)
+        _lib.check(lib.hh_bn_train_stats_dt(dt, x.data_ptr(), P, C, sums.data_ptr(), scratch.data_ptr(), stream))
         _all_reduce_sums(sums, group)
         count = float(P) * world
-        _lib.check(lib.hh_bn_train_normalize(x.data_ptr(), P, C, sums.data_ptr(), count, gamma.float().contiguous().data_ptr(),
-                                             beta.float().contiguous().data_ptr(), eps, res.data_ptr() if res is not None else None,
-                                             int(relu), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), stream))
+        _lib.check(lib.hh_bn_train_normalize_dt(dt, x.data_ptr(), P, C, sums.data_ptr(), count, gamma.float().contiguous().data_ptr(),
+                                                beta.float().contiguous().data_ptr(), eps, res.data_ptr() if res is not None else None,
+                                                int(relu), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), stream))
     return y, mean, invstd, count
 
 
@@ -205,12 +225,13 @@ def sync_bn_train_backward(x: Tensor, y: Tensor, dy: Tensor, mean: Tensor, invst
     stream = torch.cuda.current_stream(x.device).cuda_stream
     g = gamma.float().contiguous()
     with torch.cuda.device(x.device):
-        _lib.check(lib.hh_bn_train_backward_stats(x.data_ptr(), y.data_ptr(), dy.data_ptr(), P, C, mean.data_ptr(), invstd.data_ptr(),
-                                                  int(relu), sums.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr(), stream))
+        dt = _act(x, y, dy)
+        _lib.check(lib.hh_bn_train_backward_stats_dt(dt, x.data_ptr(), y.data_ptr(), dy.data_ptr(), P, C, mean.data_ptr(), invstd.data_ptr(),
+                                                     int(relu), sums.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr(), stream))
         _all_reduce_sums(sums, group)
-        _lib.check(lib.hh_bn_train_backward_apply(x.data_ptr(), y.data_ptr(), dy.data_ptr(), P, C, mean.data_ptr(), invstd.data_ptr(),
-                                                  g.data_ptr(), int(relu), sums.data_ptr(), count, dx.data_ptr(),
-                                                  dres.data_ptr() if dres is not None else None, scratch.data_ptr(), stream))
+        _lib.check(lib.hh_bn_train_backward_apply_dt(dt, x.data_ptr(), y.data_ptr(), dy.data_ptr(), P, C, mean.data_ptr(), invstd.data_ptr(),
+                                                     g.data_ptr(), int(relu), sums.data_ptr(), count, dx.data_ptr(),
+                                                     dres.data_ptr() if dres is not None else None, scratch.data_ptr(), stream))
     return dx, dgamma, dbeta, dres
 
 
@@ -225,7 +246,8 @@ def conv2d_weight_grad(x: Tensor, dy: Tensor, ks: int, stride: int = 1, pad: tup
     stream = torch.cuda.current_stream(x.device).cuda_stream
     with torch.cuda.device(x.device):
         py_, px_ = pad if pad is not None else (-1, -1)
-        _lib.check(lib.hh_conv2d_wgrad(x.data_ptr(), dy.data_ptr(), B, H, W, cin, cout, ks, stride, py_, px_, dw.data_ptr(), ws.data_ptr(), stream))
+        _lib.check(lib.hh_conv2d_wgrad_dt(_act(x, dy), x.data_ptr(), dy.data_ptr(), B, H, W, cin, cout, ks, stride, py_, px_, dw.data_ptr(), ws.data_ptr(),
+                                          stream))
     return dw
 
 
@@ -240,7 +262,7 @@ def fusion_sum(terms: list[Tensor], shifts: list[int], relu: bool = True) -> Ten
     sh = (C.c_int * len(terms))(*shifts)
     stream = torch.cuda.current_stream(out.device).cuda_stream
     with torch.cuda.device(out.device):
-        _lib.check(lib.hh_fusion_sum_forward(ptrs, sh, len(terms), B, H, W, Cc, int(relu), out.data_ptr(), stream))
+        _lib.check(lib.hh_fusion_sum_forward_dt(_act(*terms), ptrs, sh, len(terms), B, H, W, Cc, int(relu), out.data_ptr(), stream))
     return out
 
 
@@ -257,8 +279,8 @@ def fusion_sum_backward(dy: Tensor, out: Tensor, shifts: list[int], relu: bool =
     sh = (C.c_int * max(len(dups), 1))(*[s for _, s in ups])
     stream = torch.cuda.current_stream(dy.device).cuda_stream
     with torch.cuda.device(dy.device):
-        _lib.check(lib.hh_fusion_sum_backward(dy.data_ptr(), out.data_ptr(), int(relu), B, H, W, Cc, g.data_ptr() if relu else None, ptrs, sh,
-                                              len(dups), stream))
+        _lib.check(lib.hh_fusion_sum_backward_dt(_act(dy, out), dy.data_ptr(), out.data_ptr(), int(relu), B, H, W, Cc, g.data_ptr() if relu else None,
+                                                 ptrs, sh, len(dups), stream))
     grads: list = [g] * len(shifts)
     for (j, _), d in zip(ups, dups):
         grads[j] = d
