@@ -389,6 +389,39 @@ int hh_bn_train_backward_apply_dt(int act_dtype, const void *x, const void *y, c
                                   const float *invstd, const float *gamma, int relu, const double *sums, double count, void *dx, void *dres,
                                   double *scratch, void *stream);
 
+/* The classification head's tail in training form (classification/architectures/hrnet.py:55-61, classification/loss.py,
+ * classification/module.py:15-22); keypoints/train_net.py puts it behind the 4-scale backbone.  All device pointers.
+ * (Additive entry points: HH_ABI_VERSION stays 3.)
+ *   hh_global_avgpool: out fp32 [B,C] = the mean over the HW pixels of x [B,HW,C] (NHWC, 16-bit), summed in fp32 in pixel order and
+ *     divided by HW; C % 8 == 0.  The kernel the inference engine runs.  hh_global_avgpool_backward: dx [B,HW,C] (16-bit) =
+ *     g[b,c] / HW at every pixel, rounded to nearest even.  Both touch activations: the forms with the suffix _act take
+ *     act_dtype = HH_ACT_BF16 / HH_ACT_F16 in front, with the meaning it has for the _dt forms above; the unsuffixed ones are bf16.
+ *   hh_linear_forward: y [B,N] = x [B,K] W[N,K]^T + bias, fp32 throughout (nn.Linear; the engine's kernel).
+ *   hh_linear_backward: dx [B,K] = dy W, dw [N,K] = dy^T x and db [N] = sum_b dy, fp32, every sum in an order that depends
+ *     on the shape alone: identical bits from call to call.  dx, dw, db may each be NULL (not computed); w is read only for dx, x only for dw.
+ *   hh_softmax_xent: nn.CrossEntropyLoss() (mean over the batch, no label smoothing) on logits fp32 [B,N] and targets int64 [B], its
+ *     gradient and the classification metrics in ONE launch.  result (device, 16 bytes, read with one copy):
+ *       loss   = (1/B) sum_b (max_b + log sum_j exp(z_bj - max_b) - z_bt), the row sums and the batch sum in double, fixed order;
+ *       top1, top5 = the number of rows whose target has rank < 1 / < 5, where
+ *                rank = #{j : z_j > z_t} + #{j < t : z_j == z_t}
+ *              (ties go to the lower index, the project's rule; torch.topk leaves the order of equal values unspecified);
+ *       flags  bit 0: some target is outside [0, N).  Such a row adds nothing to loss, top1, top5, its dlogits row is zero, and no
+ *              logit is read at its index.  The caller decides what to do about it (classification/loss.py raises when it reads
+ *              the record).
+ *     dlogits fp32 [B,N] = (softmax(z) - onehot(t)) / B, or NULL.                                                              */
+typedef struct hh_xent_result {
+    float loss;
+    int32_t top1, top5;
+    uint32_t flags;
+} hh_xent_result;
+int hh_global_avgpool(const void *x, int B, int HW, int C, float *out, void *stream);
+int hh_global_avgpool_act(int act_dtype, const void *x, int B, int HW, int C, float *out, void *stream);
+int hh_global_avgpool_backward(const float *g, int B, int HW, int C, void *dx, void *stream);
+int hh_global_avgpool_backward_act(int act_dtype, const float *g, int B, int HW, int C, void *dx, void *stream);
+int hh_linear_forward(const float *x, const float *w, const float *bias, int B, int K, int N, float *y, void *stream);
+int hh_linear_backward(const float *x, const float *w, const float *dy, int B, int K, int N, float *dx, float *dw, float *db, void *stream);
+int hh_softmax_xent(const float *logits, const int64_t *targets, int B, int N, float *dlogits, hh_xent_result *result, void *stream);
+
 /* Multi-scale test-time augmentation (BASELINE.json configs[3]; an extension: the reference only calls its resize helper
  * with scale 1, keypoints/model.py:73): dst[B,K,H,W] (+)= weight * bilinear(src[B,K,h,w] -> HxW) with the arithmetic of
  * F.interpolate(mode="bilinear", align_corners=False); init != 0 overwrites dst.  Batch strides in elements.            */

@@ -120,6 +120,14 @@ def _sig(lib):
         "hh_bn_train_normalize_dt": (i32, [i32, vp, i64, i32, vp, dbl, vp, vp, C.c_float, vp, i32, vp, vp, vp, vp]),
         "hh_bn_train_backward_stats_dt": (i32, [i32, vp, vp, vp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
         "hh_bn_train_backward_apply_dt": (i32, [i32, vp, vp, vp, i64, i32, vp, vp, vp, i32, vp, dbl, vp, vp, vp, vp]),
+        # the classifier's tail in training form
+        "hh_global_avgpool": (i32, [vp, i32, i32, i32, vp, vp]),
+        "hh_global_avgpool_act": (i32, [i32, vp, i32, i32, i32, vp, vp]),
+        "hh_global_avgpool_backward": (i32, [vp, i32, i32, i32, vp, vp]),
+        "hh_global_avgpool_backward_act": (i32, [i32, vp, i32, i32, i32, vp, vp]),
+        "hh_linear_forward": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
+        "hh_linear_backward": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+        "hh_softmax_xent": (i32, [vp, vp, i32, i32, vp, vp, vp]),
         "hh_resize_accumulate": (i32, [vp, i64, i32, i32, i32, i32, vp, i64, i32, i32, C.c_float, i32, vp]),
         "hh_multi_scale_aggregate": (i32, [vp, i32, vp, i32, i32, vp, i64, i32, i32, vp]),
         "hh_decoder_read_topk": (i32, [vp, vp, vp, vp]),

@@ -23,6 +23,12 @@ class ClassificationHRNet(EngineModule):
         self._init_engine(classification_hrnet_rows(C, num_classes), lambda lib: lib.hh_create_classifier(C, num_classes, 1))
 
     def forward(self, images: Tensor) -> Tensor:
+        if self.training:  # batch-stat BatchNorm, differentiable: keypoints/train_net.py on the training kernels (bf16 activations by default)
+            from ...keypoints.train_net import classification_hrnet_train_forward
+            if not images.is_cuda:
+                raise _lib.HHError("ClassificationHRNet forward needs a CUDA/HIP tensor: there is no CPU path")
+            self._dirty = True  # parameters / running statistics change under training: re-fold before the next eval forward
+            return classification_hrnet_train_forward(self, images)
         x = self._check_input(images)
         B, _, H, W = x.shape
         logits = torch.empty((B, self.num_classes), device=x.device, dtype=torch.float32)

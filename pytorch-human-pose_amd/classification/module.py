@@ -1,0 +1,72 @@
+"""`ClassificationModule.training_step` / `validation_step` (src/classification/module.py:45-82) on the HIP training kernels.
+
+Precision: the reference trains this net in fp32 without a loss scaler; here the activations of the training forward / backward are
+bf16 (a stated deviation: the training kernels are 16-bit; bf16 keeps fp32's exponent range, so no scaler is needed), parameters,
+their gradients, the pooled features, the Linear and the loss are fp32.  The metrics come from the loss kernel's result record:
+one device -> host read per step (the reference copies the logits to the host and runs topk there)."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from .loss import ClassificationLoss
+from .model import ClassificationModel
+
+
+@dataclass
+class ClassificationResult:
+    """One validation image (classification/results.py:13-24 without the plot): its logits, target and prediction (the arg-max,
+    the lower index on a tie)."""
+    logits: np.ndarray
+    target: int
+    prediction: int
+    target_label: str | int | None = None
+
+
+class ClassificationModule:
+    def __init__(self, model: ClassificationModel, loss_fn: ClassificationLoss, optimizer: torch.optim.Optimizer,
+                 idx2label: dict | None = None):
+        self.model, self.loss_fn, self.optimizer, self.idx2label = model, loss_fn, optimizer, idx2label
+
+    def batch_to_device(self, batch):
+        images, targets = batch
+        dev = self.model.device
+        return images.to(dev), targets.to(dev, non_blocking=True)
+
+    def training_step(self, batch, batch_idx: int = 0) -> dict[str, float]:
+        """module.py:45-57: forward, loss, backward, optimizer step -> {"top-1_error", "top-5_error", "loss"}.  The result record is
+        read between the backward and the optimizer step, so a target outside [0, num_classes) raises IndexError before any weight or
+        momentum moves (the forward has already updated the BatchNorm running statistics by then, as in the reference, whose loss raises
+        after its forward too)."""
+        images, targets = batch
+        logits = self.model.net(images)
+        loss = self.loss_fn.calculate_loss(targets, logits)
+        self.optimizer.zero_grad()
+        loss.backward()
+        metrics = self.loss_fn.metrics()
+        self.optimizer.step()
+        self.model._bare().mark_dirty()
+        return metrics
+
+    def validation_step(self, batch, batch_idx: int = 0):
+        """module.py:59-82: the eval-mode engine forward, the same loss and metrics, one result record per image."""
+        images, targets = batch
+        net = self.model._bare()
+        was_training = net.training
+        net.eval()
+        try:
+            with torch.no_grad():
+                logits = self.model.net(images)
+                self.loss_fn.calculate_loss(targets, logits)
+        finally:
+            net.train(was_training)
+        metrics = self.loss_fn.metrics()
+        lg, tg = logits.detach().cpu().numpy(), targets.detach().cpu().numpy()
+        results = []
+        for i in range(len(lg)):
+            t = int(tg[i])
+            results.append(ClassificationResult(lg[i], t, int(np.argmax(lg[i])), self.idx2label[t] if self.idx2label is not None else None))
+        return metrics, results

@@ -647,6 +647,49 @@ int hh_bn_train_backward_apply(const void *x, const void *y, const void *dy, int
     return hh_bn_train_backward_apply_dt(HH_ACT_BF16, x, y, dy, P, C, mean, invstd, gamma, relu, sums, count, dx, dres, scratch, stream);
 }
 
+// ------------------------------------------------------------------ the classifier's tail in training form (cls_tail.hip)
+int hh_global_avgpool_act(int act_dtype, const void *x, int B, int HW, int C, float *out, void *stream)
+{
+    if (!act_dtype_ok(act_dtype, "hh_global_avgpool")) return 1;
+    if (!x || !out || B <= 0 || HW <= 0 || C <= 0 || C % 8) { hh_set_error("hh_global_avgpool: bad argument (C must be a multiple of 8)"); return 1; }
+    HH_CHECK_HIP(launch_avgpool((const bf16_raw *)x, C, out, B, HW, C, (hipStream_t)stream, act_dtype));
+    return 0;
+}
+int hh_global_avgpool(const void *x, int B, int HW, int C, float *out, void *stream) { return hh_global_avgpool_act(HH_ACT_BF16, x, B, HW, C, out, stream); }
+
+int hh_global_avgpool_backward_act(int act_dtype, const float *g, int B, int HW, int C, void *dx, void *stream)
+{
+    if (!act_dtype_ok(act_dtype, "hh_global_avgpool_backward")) return 1;
+    if (!g || !dx || B <= 0 || HW <= 0 || C <= 0 || C % 8) { hh_set_error("hh_global_avgpool_backward: bad argument (C must be a multiple of 8)"); return 1; }
+    HH_CHECK_HIP(launch_avgpool_backward(g, (bf16_raw *)dx, B, HW, C, (hipStream_t)stream, act_dtype));
+    return 0;
+}
+int hh_global_avgpool_backward(const float *g, int B, int HW, int C, void *dx, void *stream)
+{
+    return hh_global_avgpool_backward_act(HH_ACT_BF16, g, B, HW, C, dx, stream);
+}
+
+int hh_linear_forward(const float *x, const float *w, const float *bias, int B, int K, int N, float *y, void *stream)
+{
+    if (!x || !w || !bias || !y || B <= 0 || B > 65535 || K <= 0 || N <= 0) { hh_set_error("hh_linear_forward: bad argument (0 < B <= 65535)"); return 1; }
+    HH_CHECK_HIP(launch_linear(x, w, bias, y, B, K, N, (hipStream_t)stream));
+    return 0;
+}
+int hh_linear_backward(const float *x, const float *w, const float *dy, int B, int K, int N, float *dx, float *dw, float *db, void *stream)
+{
+    if (!dy || (dx && !w) || (dw && !x) || B <= 0 || K <= 0 || N <= 0 || N > 65535 || (B + 7) / 8 > 65535) { hh_set_error("hh_linear_backward: bad argument (0 < N <= 65535)"); return 1; }
+    HH_CHECK_HIP(launch_linear_backward(x, w, dy, B, K, N, dx, dw, db, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_softmax_xent(const float *logits, const int64_t *targets, int B, int N, float *dlogits, hh_xent_result *result, void *stream)
+{
+    static_assert(sizeof(hh_xent_result) == sizeof(XentResult) && sizeof(long long) == sizeof(int64_t), "hh_xent_result layout");
+    if (!logits || !targets || !result || B <= 0 || N <= 0) { hh_set_error("hh_softmax_xent: bad argument"); return 1; }
+    HH_CHECK_HIP(launch_softmax_xent(logits, (const long long *)targets, B, N, dlogits, (XentResult *)result, (hipStream_t)stream));
+    return 0;
+}
+
 int hh_flip_images(const float *images, float *out, int B, int C, int H, int W, void *stream)
 {
     HH_CHECK_HIP(launch_flip_images(images, out, B, C, H, W, (hipStream_t)stream));

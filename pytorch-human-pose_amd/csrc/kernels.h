@@ -308,8 +308,14 @@ hipError_t launch_quant_fp8(const bf16_raw *in, int in_cs, unsigned char *out, i
 
 // ClassificationHead tail: global average pool (bf16 NHWC -> fp32 [B,C]) and Linear (fp32)
 hipError_t launch_lds_poison(int num_cus, hipStream_t s);  // debug: NaN patterns into every CU's LDS (misc_kernels.hip)
-hipError_t launch_avgpool(const bf16_raw *in, int in_cs, float *out, int B, int HW, int C, hipStream_t s);
+hipError_t launch_avgpool(const bf16_raw *in, int in_cs, float *out, int B, int HW, int C, hipStream_t s, int act_dtype = 0);
 hipError_t launch_linear(const float *x, const float *w, const float *bias, float *y, int B, int K, int N, hipStream_t s);
+// The same tail in training form (cls_tail.hip): the pool's backward, the Linear's three gradients, softmax cross-entropy
+hipError_t launch_avgpool_backward(const float *g, bf16_raw *dx, int B, int HW, int C, hipStream_t s, int act_dtype = 0);
+hipError_t launch_linear_backward(const float *x, const float *w, const float *dy, int B, int K, int N, float *dx, float *dw, float *db,
+                                  hipStream_t s);
+struct XentResult { float loss; int top1, top5; unsigned flags; };  // hh_xent_result of include/hhrnet.h
+hipError_t launch_softmax_xent(const float *logits, const long long *targets, int B, int N, float *dlogits, XentResult *result, hipStream_t s);
 
 struct HHImageDesc {  // one raw image of a batch (hh_image_desc of include/hhrnet.h): 64 bytes
     long long offset;  // bytes from the batch's base pointer to the image's first pixel

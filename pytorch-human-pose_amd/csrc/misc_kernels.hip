@@ -289,7 +289,9 @@ hipError_t launch_flip_merge(float *hm, int64_t hm_bs, const float *hmf, int64_t
     return hipGetLastError();
 }
 
-// F.avg_pool2d over the whole map (classification/architectures/hrnet.py:57): one thread = 8 channels of one image
+// F.avg_pool2d over the whole map (classification/architectures/hrnet.py:57): one thread = 8 channels of one image.  E: the element
+// type of the map (ElemBF16: the inference engine and the bf16 training step; ElemF16: the fp16 training step)
+template <typename E>
 __global__ __launch_bounds__(256) void avgpool_kernel(const bf16_raw *__restrict__ in, int in_cs, float *__restrict__ out, int B,
                                                       int HW, int C)
 {
@@ -299,14 +301,17 @@ __global__ __launch_bounds__(256) void avgpool_kernel(const bf16_raw *__restrict
     float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int p = 0; p < HW; ++p) {
         const uint4 v = *reinterpret_cast<const uint4 *>(in + ((size_t)b * HW + p) * in_cs + c8 * 8);
-        acc[0] += bf16_lo(v.x); acc[1] += bf16_hi(v.x); acc[2] += bf16_lo(v.y); acc[3] += bf16_hi(v.y);
-        acc[4] += bf16_lo(v.z); acc[5] += bf16_hi(v.z); acc[6] += bf16_lo(v.w); acc[7] += bf16_hi(v.w);
+        acc[0] += E::lo(v.x); acc[1] += E::hi(v.x); acc[2] += E::lo(v.y); acc[3] += E::hi(v.y);
+        acc[4] += E::lo(v.z); acc[5] += E::hi(v.z); acc[6] += E::lo(v.w); acc[7] += E::hi(v.w);
     }
     for (int k = 0; k < 8; ++k) out[(size_t)b * C + c8 * 8 + k] = acc[k] / (float)HW;
 }
-hipError_t launch_avgpool(const bf16_raw *in, int in_cs, float *out, int B, int HW, int C, hipStream_t s)
+hipError_t launch_avgpool(const bf16_raw *in, int in_cs, float *out, int B, int HW, int C, hipStream_t s, int act_dtype)
 {
-    hipLaunchKernelGGL(avgpool_kernel, dim3((B * (C / 8) + 255) / 256), dim3(256), 0, s, in, in_cs, out, B, HW, C);
+    const dim3 grid((B * (C / 8) + 255) / 256);
+    if (act_dtype == 0) hipLaunchKernelGGL(avgpool_kernel<ElemBF16>, grid, dim3(256), 0, s, in, in_cs, out, B, HW, C);
+    else if (act_dtype == 1) hipLaunchKernelGGL(avgpool_kernel<ElemF16>, grid, dim3(256), 0, s, in, in_cs, out, B, HW, C);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -37,7 +37,10 @@ class _NetHandle:
 class EngineModule(nn.Module):
     """nn.Module whose parameters live under the reference's state-dict keys and whose forward runs in the HIP engine."""
 
+    TRAIN_PRECISIONS = ("bf16", "fp16")
+
     def _init_engine(self, rows, create) -> None:
+        self.train_precision = "bf16"
         attach_modules(self, rows)
         self._lib = _lib.load()
         self._handle = _NetHandle(self._lib, create(self._lib))
@@ -45,6 +48,14 @@ class EngineModule(nn.Module):
         self._dirty = True
         self.use_graph = True
         self.register_load_state_dict_post_hook(lambda m, _k: m.mark_dirty())
+
+    def set_train_precision(self, precision: str) -> None:
+        """The activation type of the training forward / backward (.train() mode, keypoints/train_net.py): "bf16" (default) or "fp16",
+        the reference's for HigherHRNet (fp16 autocast; train it with a loss scaler: KeypointsModule(precision="fp16")).  Parameters,
+        their gradients and the inference engine are not affected."""
+        if precision not in self.TRAIN_PRECISIONS:
+            raise ValueError(f"set_train_precision: {precision!r} is not one of {self.TRAIN_PRECISIONS}")
+        self.train_precision = precision
 
     # ---- engine plumbing
     def mark_dirty(self) -> None:
@@ -114,7 +125,6 @@ class HigherHRNet(EngineModule):
     reference has one precision).  An fp8 net needs `calibrate(images)` once after its weights are loaded."""
 
     DTYPES = {"bf16": 1, "fp8": 2}
-    TRAIN_PRECISIONS = ("bf16", "fp16")
 
     def __init__(self, num_kpts: int, C: int = 32, dtype: str = "bf16"):
         super().__init__()
@@ -122,17 +132,8 @@ class HigherHRNet(EngineModule):
         self.C = C
         self.num_deconv_layers = 1
         self.engine_dtype = dtype
-        self.train_precision = "bf16"
         code = self.DTYPES[dtype]
         self._init_engine(higher_hrnet_rows(num_kpts, C), lambda lib: lib.hh_create(num_kpts, C, code))
-
-    def set_train_precision(self, precision: str) -> None:
-        """The activation type of the training forward / backward (.train() mode, keypoints/train_net.py): "bf16" (default) or "fp16",
-        the reference's (fp16 autocast; train it with a loss scaler: KeypointsModule(precision="fp16")).  Parameters, their gradients
-        and the inference engine are not affected."""
-        if precision not in self.TRAIN_PRECISIONS:
-            raise ValueError(f"set_train_precision: {precision!r} is not one of {self.TRAIN_PRECISIONS}")
-        self.train_precision = precision
 
     def calibrate(self, images: Tensor, rounds: int = 2) -> None:
         """fp8 only: per-tensor activation scales from forwards over `images` [B,3,H,W] (hh_calibrate).  Weight changes

@@ -31,13 +31,15 @@ def parse_checkpoint(ckpt: dict) -> dict:
     return out
 
 
-class KeypointsModel:
-    """Training-side model wrapper: `KeypointsModel` (keypoints/model.py:15-40) on `BaseModel` (base/model.py:15-131)
-    without the export / summary helpers (onnx, torchinfo: out of scope)."""
+class BaseModel:
+    """What the trainer-facing model wrappers share (base/model.py:15-131 without the export / summary helpers: onnx, torchinfo are
+    out of scope): KeypointsModel below and classification/model.py's ClassificationModel."""
 
-    def __init__(self, net: nn.Module):
+    EXAMPLE_SIZE = 512
+
+    def __init__(self, net: nn.Module, input_names: list, output_names: list):
         self.net = net
-        self.input_names, self.output_names = ["images"], ["keypoints"]
+        self.input_names, self.output_names = input_names, output_names
 
     def _bare(self) -> nn.Module:
         from torch.nn.parallel import DistributedDataParallel as DDP
@@ -45,19 +47,6 @@ class KeypointsModel:
 
     def forward(self, images: Tensor):
         return self.net(images)
-
-    def init_weights(self) -> None:
-        """keypoints/model.py:19-34: conv / transposed-conv weights ~ N(0, 0.001), their biases 0, BatchNorm weight 1 / bias 0."""
-        net = self._bare()
-        for m in net.modules():
-            if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
-                nn.init.normal_(m.weight, std=0.001)
-                if m.bias is not None:
-                    nn.init.constant_(m.bias, 0)
-            elif isinstance(m, nn.BatchNorm2d):
-                nn.init.constant_(m.weight, 1)
-                nn.init.constant_(m.bias, 0)
-        net.mark_dirty()
 
     def init_pretrained_weights(self, ckpt: dict) -> None:
         """base/model.py:101-123: load the checkpoint entries whose names exist here, ignore the rest."""
@@ -96,7 +85,28 @@ class KeypointsModel:
         self._bare().load_state_dict(state_dict)
 
     def example_input(self) -> dict[str, Tensor]:
-        return {"images": torch.randn(1, 3, 512, 512, device=self.device)}
+        return {"images": torch.randn(1, 3, self.EXAMPLE_SIZE, self.EXAMPLE_SIZE, device=self.device)}
+
+
+class KeypointsModel(BaseModel):
+    """Training-side model wrapper: `KeypointsModel` (keypoints/model.py:15-40) on `BaseModel` (base/model.py:15-131)
+    without the export / summary helpers (onnx, torchinfo: out of scope)."""
+
+    def __init__(self, net: nn.Module):
+        super().__init__(net, ["images"], ["keypoints"])
+
+    def init_weights(self) -> None:
+        """keypoints/model.py:19-34: conv / transposed-conv weights ~ N(0, 0.001), their biases 0, BatchNorm weight 1 / bias 0."""
+        net = self._bare()
+        for m in net.modules():
+            if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d)):
+                nn.init.normal_(m.weight, std=0.001)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+            elif isinstance(m, nn.BatchNorm2d):
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+        net.mark_dirty()
 
 
 class KeypointsModule:

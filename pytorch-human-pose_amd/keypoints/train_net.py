@@ -1,4 +1,5 @@
-"""Train-mode forward of HigherHRNet on the HIP building blocks.
+"""Train-mode forward of HigherHRNet, and of ClassificationHRNet (the same backbone walk, then the classification head and its tail:
+global average pool, fp32 Linear), on the HIP building blocks.
 
 The layer graph is the reference's (`src/keypoints/architectures/hrnet.py:29-385`, `higher_hrnet.py:7-81`), walked over
 the shim's parameter tree.  Convolutions (forward, data gradient, weight gradient) and train-mode BatchNorm (+ residual,
@@ -126,9 +127,10 @@ def _pad_c(n: int, m: int) -> int:
     return (n + m - 1) // m * m
 
 
-def conv(x: Tensor, m: nn.Conv2d, stride: int | None = None, box: _ResBox | None = None) -> Tensor:
+def conv(x: Tensor, m: nn.Conv2d, stride: int | None = None, box: _ResBox | None = None, bias: bool = True) -> Tensor:
     """nn.Conv2d forward on the HIP kernels.  Channel counts the kernels cannot take (3, 17, 34, 66 ...) are zero padded:
-    padding and slicing are differentiable torch ops, so the gradients reach the unpadded parameter."""
+    padding and slicing are differentiable torch ops, so the gradients reach the unpadded parameter.  bias=False leaves the
+    module's bias out (conv_bias_bn adds it where it matters)."""
     w = m.weight
     cout, cin, ks, _ = w.shape
     stride = m.stride[0] if stride is None else stride
@@ -143,7 +145,7 @@ def conv(x: Tensor, m: nn.Conv2d, stride: int | None = None, box: _ResBox | None
     y = _ConvFn.apply(x.contiguous(memory_format=torch.channels_last), w, stride, None, *(pk if pk is not None else (None, None)), box)
     if cout_p != cout:
         y = y[:, :cout]
-    if m.bias is not None:
+    if m.bias is not None and bias:
         y = y + m.bias.view(1, -1, 1, 1).to(y.dtype)
     return y
 
@@ -190,15 +192,70 @@ def _sync_world():
 _PENDING_STATS: list = []  # (module, batch mean, batch invstd, pixels) of the forward in flight, applied by flush_running_stats
 
 
-def bn(x: Tensor, m: nn.BatchNorm2d, relu: bool = False, res: Tensor | None = None, box: _ResBox | None = None) -> Tensor:
+def bn(x: Tensor, m: nn.BatchNorm2d, relu: bool = False, res: Tensor | None = None, box: _ResBox | None = None,
+       mean_shift: Tensor | None = None) -> Tensor:
     """nn.BatchNorm2d in training mode (+ residual, + ReLU); the running statistics are updated like torch updates them,
-    once per forward for all layers together (flush_running_stats)."""
+    once per forward for all layers together (flush_running_stats).  mean_shift [C]: a per-channel constant that the layer's input
+    carries in the reference but x does not (conv_bias_bn); it is added to the batch mean that feeds running_mean."""
     stats: list = []
     y = _BNFn.apply(x.contiguous(memory_format=torch.channels_last), m.weight, m.bias,
                     res.contiguous(memory_format=torch.channels_last) if res is not None else None, relu, m.eps, stats, box)
     if m.track_running_stats and m.running_mean is not None:
-        _PENDING_STATS.append((m, stats[0][0], stats[0][1], stats[0][2]))  # count = pixels of all ranks under SyncBatchNorm
+        mean = stats[0][0] if mean_shift is None else stats[0][0] + mean_shift.detach().float()
+        _PENDING_STATS.append((m, mean, stats[0][1], stats[0][2]))  # count = pixels of all ranks under SyncBatchNorm
     return y
+
+
+class _SilentBiasFn(torch.autograd.Function):
+    """A conv bias in front of a train-mode BatchNorm: y = BN(conv(x) + b) does not depend on b (the batch mean takes it out again), so
+    the forward leaves x as it is and the backward hands b its true gradient, zero -- the parameter still takes part in the graph, as
+    DistributedDataParallel expects of every parameter."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, b: Tensor):
+        ctx.n = b.shape[0]
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        return dy, torch.zeros(ctx.n, device=dy.device, dtype=torch.float32)
+
+
+def conv_bias_bn(x: Tensor, c: nn.Conv2d, b: nn.BatchNorm2d, relu: bool) -> Tensor:
+    """conv (+ bias) + train-mode BatchNorm (+ ReLU) (classification/architectures/hrnet.py:21-44).  The bias cancels in the output
+    and its gradient is zero, so no kernel adds it; eval mode folds it together with running_mean, so it does enter the batch mean
+    that is recorded for the running statistics."""
+    y = conv(x, c, bias=False)
+    if c.bias is None:
+        return bn(y, b, relu=relu)
+    return bn(_SilentBiasFn.apply(y, c.bias), b, relu=relu, mean_shift=c.bias)
+
+
+class _PoolFn(torch.autograd.Function):
+    """F.avg_pool2d over the whole map + flatten (classification/architectures/hrnet.py:58): [B,C,H,W] -> fp32 [B,C]"""
+
+    @staticmethod
+    def forward(ctx, x: Tensor):
+        ctx.hw, ctx.dtype = x.shape[2:], x.dtype
+        return ops.global_avgpool(x)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        return ops.global_avgpool_backward(g, ctx.hw[0], ctx.hw[1], ctx.dtype)
+
+
+class _LinearFn(torch.autograd.Function):
+    """nn.Linear in fp32 (classification/architectures/hrnet.py:46,60)"""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, w: Tensor, b: Tensor):
+        ctx.save_for_backward(x, w)
+        return ops.linear_forward(x, w, b)
+
+    @staticmethod
+    def backward(ctx, dy: Tensor):
+        x, w = ctx.saved_tensors
+        return ops.linear_backward(x, w, dy, want=ctx.needs_input_grad)
 
 
 @torch.no_grad()
@@ -304,9 +361,10 @@ def _fusion(xs, fl, n_out):
     return outs
 
 
-def higher_hrnet_train_forward(net, images: Tensor):
-    """-> ([hm_1/4, hm_1/2] fp32, tags_1/4 fp32), differentiable w.r.t. every parameter of `net`."""
-    K = net.num_kpts
+def _backbone_train_forward(net, images: Tensor, n_last: int) -> list:
+    """The HRNet backbone (hrnet.py:378-385) in training mode -> the `n_last` outputs of its last fusion layer (1: the pose net's
+    high-resolution map; 4: all scales, for the classification head).  Starts a forward: pending statistics, SyncBatchNorm group,
+    activation type and packed weights are those of `net`."""
     bb = net.backbone
     _PENDING_STATS.clear()
     _SYNC[0] = getattr(net, "sync_batchnorm", None)  # set by KeypointsModel.to_DDP(..., use_batchnorm=True)
@@ -330,7 +388,7 @@ def higher_hrnet_train_forward(net, images: Tensor):
             xs = new
             last = s == 3 and b == nblocks[s] - 1
             if s > 0:
-                xs = _fusion(xs, st.blocks._modules[str(2 * b + 1)], 1 if last else len(xs))
+                xs = _fusion(xs, st.blocks._modules[str(2 * b + 1)], n_last if last else len(xs))
             # (stage 0 has one scale: its "fusion" is the ReLU of a ReLU output, hrnet.py:221-229 -- the identity, gradient included)
         if s < 3:
             tb = st.transition_layer.transition_blocks
@@ -341,7 +399,13 @@ def higher_hrnet_train_forward(net, images: Tensor):
                 q0 = tb._modules["0"]
                 xs = [bn(conv(xs[0], q0._modules["0"]), q0._modules["1"], relu=True)]
             xs = xs + [newb]
-    feats = xs[0]
+    return xs
+
+
+def higher_hrnet_train_forward(net, images: Tensor):
+    """-> ([hm_1/4, hm_1/2] fp32, tags_1/4 fp32), differentiable w.r.t. every parameter of `net`."""
+    K = net.num_kpts
+    feats = _backbone_train_forward(net, images, 1)[0]
     init = conv(feats, net.init_heatmaps_head)
     d = net.deconv_layers._modules["0"]
     y = torch.cat((feats, init.to(feats.dtype)), 1)
@@ -352,3 +416,20 @@ def higher_hrnet_train_forward(net, images: Tensor):
     flush_running_stats()
     init, out = init.float(), out.float()
     return [init[:, :K], out[:, :K]], init[:, K:]
+
+
+def classification_hrnet_train_forward(net, images: Tensor) -> Tensor:
+    """-> logits fp32 [B, num_classes], differentiable w.r.t. every parameter of `net` (classification/architectures/hrnet.py:48-74):
+    one Bottleneck per scale (C_i -> 128 / 256 / 512 / 1024), each joined by the stride-2 conv + BN + ReLU of the scale above (a plain
+    sum, no ReLU after it), the 1x1 conv to 2048 + BN + ReLU, the global average pool and the fp32 Linear."""
+    xs = _backbone_train_forward(net, images, 4)
+    head = net.classification_head
+    incr, down = _children(head.chann_incr_blocks), _children(head.downsample_blocks)
+    out = _bottleneck(xs[0], incr[0])
+    for i, d in enumerate(down):
+        out = _bottleneck(xs[i + 1], incr[i + 1]) + conv_bias_bn(out, d._modules["0"], d._modules["1"], relu=True)
+    f = head.final_conv
+    out = conv_bias_bn(out, f._modules["0"], f._modules["1"], relu=True)
+    flat = _PoolFn.apply(out.contiguous(memory_format=torch.channels_last))
+    flush_running_stats()
+    return _LinearFn.apply(flat, head.classifier.weight, head.classifier.bias)

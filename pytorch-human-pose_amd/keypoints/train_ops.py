@@ -285,3 +285,90 @@ def fusion_sum_backward(dy: Tensor, out: Tensor, shifts: list[int], relu: bool =
     for (j, _), d in zip(ups, dups):
         grads[j] = d
     return grads
+
+
+# ------------------------------------------------------------------------------------------ the classifier's tail
+def _f32(t: Tensor, what: str) -> Tensor:
+    if not t.is_cuda:
+        raise _lib.HHError(f"{what} must be a CUDA/HIP tensor: there is no CPU path")
+    return t.detach().to(torch.float32).contiguous()
+
+
+def global_avgpool(x: Tensor) -> Tensor:
+    """[B,C,H,W] channels_last bf16 / fp16 -> fp32 [B,C]: the mean over the map (hh_global_avgpool)."""
+    lib = _lib.load()
+    x = _nhwc(x)
+    B, C, H, W = x.shape
+    out = torch.empty((B, C), device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.hh_global_avgpool_act(_act(x), x.data_ptr(), B, H * W, C, out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream))
+    return out
+
+
+def global_avgpool_backward(g: Tensor, H: int, W: int, dtype: torch.dtype) -> Tensor:
+    """fp32 [B,C] -> [B,C,H,W] channels_last of `dtype`, every pixel g / (H W) (hh_global_avgpool_backward)."""
+    lib = _lib.load()
+    if dtype not in ACT_DTYPES:
+        raise _lib.HHError(f"global_avgpool_backward: dtype must be torch.bfloat16 or torch.float16, not {dtype}")
+    g = _f32(g, "the pooled gradient")
+    B, C = g.shape
+    dx = torch.empty((B, C, H, W), device=g.device, dtype=dtype, memory_format=torch.channels_last)
+    with torch.cuda.device(g.device):
+        _lib.check(lib.hh_global_avgpool_backward_act(ACT_DTYPES[dtype], g.data_ptr(), B, H * W, C, dx.data_ptr(),
+                                                     torch.cuda.current_stream(g.device).cuda_stream))
+    return dx
+
+
+def linear_forward(x: Tensor, w: Tensor, bias: Tensor) -> Tensor:
+    """y = x w^T + bias, fp32 (hh_linear_forward)."""
+    lib = _lib.load()
+    x, w, bias = _f32(x, "x"), _f32(w, "w"), _f32(bias, "bias")
+    (B, K), N = x.shape, w.shape[0]
+    if w.shape != (N, K) or bias.shape != (N,):
+        raise ValueError(f"linear_forward: x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}")
+    y = torch.empty((B, N), device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.hh_linear_forward(x.data_ptr(), w.data_ptr(), bias.data_ptr(), B, K, N, y.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream))
+    return y
+
+
+def linear_backward(x: Tensor, w: Tensor, dy: Tensor, want=(True, True, True)):
+    """-> (dx, dw, db) of y = x w^T + bias, fp32, each None where `want` is False (hh_linear_backward)."""
+    lib = _lib.load()
+    x, w, dy = _f32(x, "x"), _f32(w, "w"), _f32(dy, "dy")
+    (B, K), N = x.shape, w.shape[0]
+    if w.shape != (N, K) or dy.shape != (B, N):
+        raise ValueError(f"linear_backward: x {tuple(x.shape)}, w {tuple(w.shape)}, dy {tuple(dy.shape)}")
+    dx = torch.empty_like(x) if want[0] else None
+    dw = torch.empty_like(w) if want[1] else None
+    db = torch.empty(N, device=x.device, dtype=torch.float32) if want[2] else None
+    with torch.cuda.device(x.device):
+        _lib.check(lib.hh_linear_backward(x.data_ptr(), w.data_ptr(), dy.data_ptr(), B, K, N, *(t.data_ptr() if t is not None else None for t in (dx, dw, db)),
+                                          torch.cuda.current_stream(x.device).cuda_stream))
+    return dx, dw, db
+
+
+def softmax_xent(logits: Tensor, targets: Tensor, want_grad: bool = True):
+    """-> (result, dlogits or None).  result: int32 [4] on the device = hh_xent_result {loss (fp32 bits), top-1 hits, top-5 hits, flags};
+    `read_xent_result` decodes a host copy.  Nothing here waits for the device."""
+    lib = _lib.load()
+    z = _f32(logits, "logits")
+    B, N = z.shape
+    t = targets.to(z.device, torch.int64).contiguous()
+    if t.shape != (B,):
+        raise ValueError(f"softmax_xent: logits {tuple(z.shape)}, targets {tuple(t.shape)}")
+    result = torch.empty(4, device=z.device, dtype=torch.int32)
+    dz = torch.empty_like(z) if want_grad else None
+    with torch.cuda.device(z.device):
+        _lib.check(lib.hh_softmax_xent(z.data_ptr(), t.data_ptr(), B, N, dz.data_ptr() if dz is not None else None, result.data_ptr(),
+                                       torch.cuda.current_stream(z.device).cuda_stream))
+    return result, dz
+
+
+def read_xent_result(result: Tensor, B: int) -> dict:
+    """One device -> host copy of an hh_xent_result -> {"loss", "top-1_error", "top-5_error"}; raises if the flag word says that a
+    target was outside [0, N)."""
+    r = result.cpu()
+    if int(r[3]) & 1:
+        raise IndexError("softmax cross-entropy: a target is outside [0, num_classes)")
+    return {"loss": float(r[:1].view(torch.float32)), "top-1_error": 1.0 - int(r[1]) / B, "top-5_error": 1.0 - int(r[2]) / B}

@@ -15,6 +15,7 @@ What is imported from the reference (and therefore *pinned* by these fixtures):
   * src.base.transforms.utils.get_multi_scale_size               (resize geometry, a10)
   * src.keypoints.loss.AEKeypointsLoss                           (training loss + autograd gradients, a20)
   * the same HigherHRNet in .train() mode + torch autograd        (train-mode forward / backward, a20)
+  * ClassificationHRNet in .train() mode + src.classification.loss.ClassificationLoss + autograd   (cls_train)
 What is NOT importable here (cv2 / torchvision missing) and is restated inline with the
 same torch calls the reference makes: the three F.interpolate(bilinear,
 align_corners=False) + stack/mean lines of results.py:48-67,225-230 and the flip-TTA
@@ -346,6 +347,51 @@ def train_fixture(batch=2, fname="train_step.npz"):
     print("train fixture", fname, ": loss", out["loss"], "params", len(names))
 
 
+def cls_train_fixture():
+    """The reference ClassificationHRNet(32, 1000) in .train() mode on 8 seeded 128 x 128 images (the 8C branch then normalises over
+    4 x 4 x 8 = 128 samples per channel, as in train_step_b8.npz), the reference's ClassificationLoss, torch autograd.  Targets:
+    seeded, except two rows, so that the top-1 / top-5 counts are not all misses and still cannot flip under a 16-bit forward: the row
+    whose largest logit leads its second by the widest gap takes its arg-max, and of the other rows the one whose second largest logit
+    is furthest from both its first and its sixth takes that second.  Stored: targets, loss, all logits, top-1 / top-5 errors (classification/module.py:15-22), per-parameter gradient norms
+    and 4 samples each, three running statistics after the step."""
+    from src.classification.loss import ClassificationLoss
+    net = ClassificationHRNet(32, 1000)
+    load_synth(net, 11)
+    net.train()
+    x = torch.from_numpy(synth.synth_images(8, 128, 128, seed=1))
+    logits = net(x)
+    targets = torch.from_numpy(np.random.RandomState(7).randint(0, 1000, 8).astype(np.int64))
+    srt, order = logits.detach().sort(dim=1, descending=True)
+    r1 = int((srt[:, 0] - srt[:, 1]).argmax())
+    targets[r1] = order[r1, 0]
+    margin2 = torch.minimum(srt[:, 0] - srt[:, 1], srt[:, 1] - srt[:, 5])
+    margin2[r1] = -1
+    r2 = int(margin2.argmax())
+    targets[r2] = order[r2, 1]
+    loss = ClassificationLoss().calculate_loss(targets, logits)
+    loss.backward()
+    top5 = logits.detach().topk(k=5, dim=1).indices
+    top5_acc = torch.any(top5 == targets.unsqueeze(-1).expand_as(top5), dim=1).float().mean().item()
+    top1_acc = (top5[:, 0] == targets).float().mean().item()
+    out = {"loss": np.float32(loss.item()), "logits": logits.detach().numpy(), "targets": targets.numpy(),
+           "top-1_error": np.float64(1 - top1_acc), "top-5_error": np.float64(1 - top5_acc)}
+    names, norms, samples = [], [], []
+    for name, p in net.named_parameters():
+        g = p.grad.numpy().ravel()
+        names.append(name)
+        norms.append(np.linalg.norm(g.astype(np.float64)))
+        samples.append(g[np.linspace(0, g.size - 1, 4).astype(int)])
+    out["grad.names"] = np.array(names)
+    out["grad.norms"] = np.array(norms, np.float64)
+    out["grad.samples"] = np.stack(samples).astype(np.float32)
+    sd = net.state_dict()
+    for k in ("backbone.bn1.running_mean", "classification_head.downsample_blocks.0.1.running_mean", "classification_head.final_conv.1.running_var"):
+        out["stat." + k] = sd[k].numpy()
+    np.savez_compressed(os.path.join(OUT, "cls_train_step.npz"), **out)
+    print("cls train fixture: loss", out["loss"], "errors", out["top-1_error"], out["top-5_error"], "params", len(names),
+          "logits absmax", float(np.abs(out["logits"]).max()))
+
+
 def train_autocast_fixture():
     """The same step at the REFERENCE'S training precision (keypoints/module.py:48-60: forward under
     torch.autocast(dtype=float16), backward through a GradScaler): CPU autocast runs the reference net with fp16 conv operands
@@ -507,6 +553,8 @@ if __name__ == "__main__":
         train_fixture()
     if "train_b8" in which:
         train_fixture(8, "train_step_b8.npz")
+    if "cls_train" in which:
+        cls_train_fixture()
     if "loss" in which:
         loss_fixtures()
     if "munkres" in which:
