@@ -422,6 +422,52 @@ int hh_linear_forward(const float *x, const float *w, const float *bias, int B, 
 int hh_linear_backward(const float *x, const float *w, const float *dy, int B, int K, int N, float *dx, float *dw, float *db, void *stream);
 int hh_softmax_xent(const float *logits, const int64_t *targets, int B, int N, float *dlogits, hh_xent_result *result, void *stream);
 
+/* The end of the training step on the device (csrc/optim.hip): what torch.optim.Adam / AdamW / SGD and the GradScaler's non-finite
+ * check do over ~900 parameter tensors, each as ONE launch over a device-resident table (the Python classes are
+ * pytorch-human-pose_amd/optim.py; the reference picks its optimizer in utils/optim.py:40-45).  Parameters, gradients and state are
+ * fp32 device tensors, contiguous, at any 4-byte alignment (float4 access where all of a chunk's pointers are 16-byte aligned).
+ * (Additive entry points: HH_ABI_VERSION stays 3.)
+ *
+ * hh_optim_tensor: one parameter.  state0 / state1 = exp_avg / exp_avg_sq (Adam, AdamW) or momentum_buffer / unused (SGD; state0 may
+ *   be NULL where the group's momentum is 0).  step = the tensor's fp32 step counter on the device (torch's state[p]["step"]; Adam and
+ *   AdamW only).  group indexes the hyper-parameter blocks.
+ * hh_optim_group: doubles, as Python holds them; the bias corrections 1 - beta^step are formed from them in fp64 on the device.
+ *   momentum / nesterov: SGD (dampening is 0); beta1 / beta2 / eps: Adam and AdamW; weight_decay: L2 for Adam and SGD, decoupled
+ *   (p *= 1 - lr * weight_decay) for AdamW.
+ * hh_optim_table_bytes: the size of `table_dev` for these tensors (it holds the descriptors, one entry per 4096-element chunk of
+ *   every tensor, and the group blocks); -1 on a bad argument.
+ * hh_optim_step: one update launch over all chunks plus, for Adam / AdamW, a one-workgroup launch that adds 1 to every step counter
+ *   (no workgroup reads a counter another one of the same launch has advanced).  `upload` says which parts of the table this call
+ *   copies into table_dev first (one hipMemcpyAsync on `stream`): HH_OPTIM_UPLOAD_ALL, or less where the caller knows that table_dev
+ *   still holds the same part from its previous call with the same arguments.  grad_scale / found_inf (device fp32 scalars, either may be
+ *   NULL) are the contract torch.amp.GradScaler.step offers an optimizer with _step_supports_amp_scaling: with *found_inf != 0 nothing
+ *   is stored at all -- parameters, state and counters keep their bits; otherwise g / *grad_scale is used and written back to grad.
+ * hh_grads_nonfinite: *found_inf = 1.0f if any element of any gradient is inf or NaN (the caller zeroes it first), and, unless
+ *   inv_scale is NULL or holds 1, every gradient is multiplied by *inv_scale in place (_amp_foreach_non_finite_check_and_unscale_).
+ *   Works on the same table; its upload may be 0 or HH_OPTIM_UPLOAD_TENSORS (it does not read the groups).
+ * Non-zero (nothing launched or copied) for an unknown algorithm, null tables or table pointers, a negative numel or count, a
+ * group index outside [0, ngroups), a beta outside [0, 1), a table_dev that is not 16-byte aligned or smaller than hh_optim_table_bytes. */
+#define HH_OPTIM_ADAM 0
+#define HH_OPTIM_ADAMW 1
+#define HH_OPTIM_SGD 2
+#define HH_OPTIM_UPLOAD_TENSORS 1 /* descriptors and chunk list */
+#define HH_OPTIM_UPLOAD_GROUPS 2  /* hyper-parameter blocks */
+#define HH_OPTIM_UPLOAD_ALL 3
+typedef struct hh_optim_tensor {
+    float *param, *grad, *state0, *state1, *step;
+    int64_t numel;
+    int32_t group, reserved;
+} hh_optim_tensor;
+typedef struct hh_optim_group {
+    double lr, beta1, beta2, eps, weight_decay, momentum;
+    int32_t nesterov, reserved;
+} hh_optim_group;
+int64_t hh_optim_table_bytes(const hh_optim_tensor *tensors_host, int ntensors, int ngroups);
+int hh_optim_step(int algo, const hh_optim_tensor *tensors_host, int ntensors, const hh_optim_group *groups_host, int ngroups,
+                  const float *grad_scale, const float *found_inf, void *table_dev, int64_t table_bytes, int upload, void *stream);
+int hh_grads_nonfinite(const hh_optim_tensor *tensors_host, int ntensors, int ngroups, const float *inv_scale, float *found_inf,
+                       void *table_dev, int64_t table_bytes, int upload, void *stream);
+
 /* Multi-scale test-time augmentation (BASELINE.json configs[3]; an extension: the reference only calls its resize helper
  * with scale 1, keypoints/model.py:73): dst[B,K,H,W] (+)= weight * bilinear(src[B,K,h,w] -> HxW) with the arithmetic of
  * F.interpolate(mode="bilinear", align_corners=False); init != 0 overwrites dst.  Batch strides in elements.            */

@@ -3,6 +3,7 @@
 from . import _lib, synth
 from .classification.architectures import ClassificationHRNet
 from . import keypoints
+from . import optim
 from .keypoints import AEKeypointsLoss, HigherHRNet, InferenceKeypointsModel, InferenceKeypointsResult, MPPEHeatmapParser
 
-__all__ = ["ClassificationHRNet", "HigherHRNet", "MPPEHeatmapParser", "InferenceKeypointsModel", "InferenceKeypointsResult", "synth", "_lib"]
+__all__ = ["ClassificationHRNet", "HigherHRNet", "MPPEHeatmapParser", "InferenceKeypointsModel", "InferenceKeypointsResult", "synth", "optim", "_lib"]

@@ -128,6 +128,10 @@ def _sig(lib):
         "hh_linear_forward": (i32, [vp, vp, vp, i32, i32, i32, vp, vp]),
         "hh_linear_backward": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
         "hh_softmax_xent": (i32, [vp, vp, i32, i32, vp, vp, vp]),
+        # the device optimizer step (optim.py)
+        "hh_optim_table_bytes": (i64, [vp, i32, i32]),
+        "hh_optim_step": (i32, [i32, vp, i32, vp, i32, vp, vp, vp, i64, i32, vp]),
+        "hh_grads_nonfinite": (i32, [vp, i32, i32, vp, vp, vp, i64, i32, vp]),
         "hh_resize_accumulate": (i32, [vp, i64, i32, i32, i32, i32, vp, i64, i32, i32, C.c_float, i32, vp]),
         "hh_multi_scale_aggregate": (i32, [vp, i32, vp, i32, i32, vp, i64, i32, i32, vp]),
         "hh_decoder_read_topk": (i32, [vp, vp, vp, vp]),

@@ -6,6 +6,7 @@
 
 #include "../../include/hhrnet.h"
 #include "engine.h"
+#include "optim_math.h"
 
 const char *hh_get_error();
 int hh_tap_read_impl(hh_net *n, int index, float *host);
@@ -687,6 +688,111 @@ int hh_softmax_xent(const float *logits, const int64_t *targets, int B, int N, f
     static_assert(sizeof(hh_xent_result) == sizeof(XentResult) && sizeof(long long) == sizeof(int64_t), "hh_xent_result layout");
     if (!logits || !targets || !result || B <= 0 || N <= 0) { hh_set_error("hh_softmax_xent: bad argument"); return 1; }
     HH_CHECK_HIP(launch_softmax_xent(logits, (const long long *)targets, B, N, dlogits, (XentResult *)result, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- device optimizer step (optim.hip).  Table layout in table_dev: [tensors][chunks][groups], each 8-byte aligned.
+static_assert(sizeof(hh_optim_tensor) == sizeof(OptimTensor) && sizeof(hh_optim_group) == sizeof(OptimGroup) && sizeof(OptimTensor) == 56 &&
+              sizeof(OptimGroup) == 56 && sizeof(OptimChunk) == 8, "hh_optim_tensor / hh_optim_group layout");
+
+// the checks every entry point shares; -> the chunk count, or -1 with the error set
+static int64_t optim_count_chunks(const hh_optim_tensor *t, int ntensors, int ngroups, const char *who)
+{
+    if (ntensors < 0 || ngroups <= 0) { hh_set_error(std::string(who) + ": need ntensors >= 0 and ngroups > 0"); return -1; }
+    if (ntensors && !t) { hh_set_error(std::string(who) + ": null tensor table"); return -1; }
+    int64_t nchunks = 0;
+    for (int i = 0; i < ntensors; ++i) {
+        if (t[i].numel < 0) { hh_set_error(std::string(who) + ": negative numel in the table"); return -1; }
+        if (t[i].group < 0 || t[i].group >= ngroups) { hh_set_error(std::string(who) + ": group index outside [0, ngroups)"); return -1; }
+        nchunks += (t[i].numel + OPTIM_CHUNK - 1) / OPTIM_CHUNK;
+    }
+    if (nchunks > 0x7fffffffLL) { hh_set_error(std::string(who) + ": more than 2^31 - 1 chunks"); return -1; }
+    return nchunks;
+}
+
+static int64_t optim_bytes(int ntensors, int ngroups, int64_t nchunks)
+{
+    return (int64_t)ntensors * (int64_t)sizeof(OptimTensor) + nchunks * (int64_t)sizeof(OptimChunk) + (int64_t)ngroups * (int64_t)sizeof(OptimGroup);
+}
+
+int64_t hh_optim_table_bytes(const hh_optim_tensor *tensors_host, int ntensors, int ngroups)
+{
+    const int64_t nchunks = optim_count_chunks(tensors_host, ntensors, ngroups, "hh_optim_table_bytes");
+    return nchunks < 0 ? -1 : optim_bytes(ntensors, ngroups, nchunks);
+}
+
+// Builds the host image of the table parts `upload` names and ships it with one async copy (the parts are adjacent in the order
+// tensors, chunks, groups, so bit 0 and bit 1 together are still one copy).
+static int optim_upload(const hh_optim_tensor *t, int ntensors, const hh_optim_group *groups, int ngroups, int64_t nchunks, int upload,
+                        char *table_dev, hipStream_t stream)
+{
+    if (!upload) return 0;
+    // (thread-local and reused: it outlives the call, and the next call on this thread comes after the copy has been staged)
+    static thread_local std::vector<char> host;
+    const size_t tb = (size_t)ntensors * sizeof(OptimTensor), cb = (size_t)nchunks * sizeof(OptimChunk), gb = (size_t)ngroups * sizeof(OptimGroup);
+    host.resize(tb + cb + gb);
+    size_t lo = tb + cb, hi = tb + cb;
+    if (upload & HH_OPTIM_UPLOAD_TENSORS) {
+        lo = 0;
+        if (tb) std::memcpy(host.data(), t, tb);
+        OptimChunk *c = (OptimChunk *)(host.data() + tb);
+        for (int i = 0; i < ntensors; ++i) {
+            const int n = (int)((t[i].numel + OPTIM_CHUNK - 1) / OPTIM_CHUNK);
+            for (int k = 0; k < n; ++k) *c++ = OptimChunk{i, k};
+        }
+    }
+    if (upload & HH_OPTIM_UPLOAD_GROUPS) {
+        hi = tb + cb + gb;
+        std::memcpy(host.data() + tb + cb, groups, gb);
+    }
+    if (hi > lo) HH_CHECK_HIP(hipMemcpyAsync(table_dev + lo, host.data() + lo, hi - lo, hipMemcpyHostToDevice, stream));
+    return 0;
+}
+
+int hh_optim_step(int algo, const hh_optim_tensor *tensors_host, int ntensors, const hh_optim_group *groups_host, int ngroups,
+                  const float *grad_scale, const float *found_inf, void *table_dev, int64_t table_bytes, int upload, void *stream)
+{
+    if (algo != HH_OPTIM_ADAM && algo != HH_OPTIM_ADAMW && algo != HH_OPTIM_SGD) { hh_set_error("hh_optim_step: unknown algorithm (HH_OPTIM_ADAM = 0, HH_OPTIM_ADAMW = 1, HH_OPTIM_SGD = 2)"); return 1; }
+    if (!groups_host || !table_dev) { hh_set_error("hh_optim_step: null group table or device table"); return 1; }
+    if (upload < 0 || upload > HH_OPTIM_UPLOAD_ALL) { hh_set_error("hh_optim_step: upload is a mask of HH_OPTIM_UPLOAD_TENSORS | HH_OPTIM_UPLOAD_GROUPS"); return 1; }
+    if ((uintptr_t)table_dev % 16) { hh_set_error("hh_optim_step: table_dev must be 16-byte aligned"); return 1; }
+    const int64_t nchunks = optim_count_chunks(tensors_host, ntensors, ngroups, "hh_optim_step");
+    if (nchunks < 0) return 1;
+    if (table_bytes < optim_bytes(ntensors, ngroups, nchunks)) { hh_set_error("hh_optim_step: table buffer too small (hh_optim_table_bytes)"); return 1; }
+    const bool adam = algo != HH_OPTIM_SGD;
+    for (int g = 0; g < ngroups; ++g) {
+        const hh_optim_group &gr = groups_host[g];
+        if (adam && !(gr.beta1 >= 0.0 && gr.beta1 < 1.0 && gr.beta2 >= 0.0 && gr.beta2 < 1.0)) { hh_set_error("hh_optim_step: betas must lie in [0, 1)"); return 1; }
+    }
+    for (int i = 0; i < ntensors; ++i) {
+        const hh_optim_tensor &t = tensors_host[i];
+        const bool need_s0 = adam || groups_host[t.group].momentum != 0.0;
+        if (!t.param || !t.grad || (need_s0 && !t.state0) || (adam && (!t.state1 || !t.step))) { hh_set_error("hh_optim_step: null pointer in the tensor table"); return 1; }
+    }
+    if (!nchunks) return 0;
+    if (optim_upload(tensors_host, ntensors, groups_host, ngroups, nchunks, upload, (char *)table_dev, (hipStream_t)stream)) return 1;
+    const OptimTensor *td = (const OptimTensor *)table_dev;
+    const OptimChunk *cd = (const OptimChunk *)(td + ntensors);
+    const OptimGroup *gd = (const OptimGroup *)(cd + nchunks);
+    HH_CHECK_HIP(launch_optim_step(algo, td, ntensors, gd, cd, (int)nchunks, grad_scale, found_inf, adam ? 1 : 0, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_grads_nonfinite(const hh_optim_tensor *tensors_host, int ntensors, int ngroups, const float *inv_scale, float *found_inf, void *table_dev,
+                       int64_t table_bytes, int upload, void *stream)
+{
+    if (!found_inf || !table_dev) { hh_set_error("hh_grads_nonfinite: null found_inf or device table"); return 1; }
+    if (upload != 0 && upload != HH_OPTIM_UPLOAD_TENSORS) { hh_set_error("hh_grads_nonfinite: upload is 0 or HH_OPTIM_UPLOAD_TENSORS"); return 1; }
+    if ((uintptr_t)table_dev % 16) { hh_set_error("hh_grads_nonfinite: table_dev must be 16-byte aligned"); return 1; }
+    const int64_t nchunks = optim_count_chunks(tensors_host, ntensors, ngroups, "hh_grads_nonfinite");
+    if (nchunks < 0) return 1;
+    if (table_bytes < optim_bytes(ntensors, ngroups, nchunks)) { hh_set_error("hh_grads_nonfinite: table buffer too small (hh_optim_table_bytes)"); return 1; }
+    for (int i = 0; i < ntensors; ++i)
+        if (!tensors_host[i].grad) { hh_set_error("hh_grads_nonfinite: null gradient pointer in the tensor table"); return 1; }
+    if (!nchunks) return 0;
+    if (optim_upload(tensors_host, ntensors, nullptr, ngroups, nchunks, upload, (char *)table_dev, (hipStream_t)stream)) return 1;
+    const OptimTensor *td = (const OptimTensor *)table_dev;
+    HH_CHECK_HIP(launch_grads_nonfinite(td, (const OptimChunk *)(td + ntensors), (int)nchunks, inv_scale, found_inf, (hipStream_t)stream));
     return 0;
 }
 

@@ -399,3 +399,13 @@ int conv_wgrad_num_workers(int B, int Ho, int Wo, int ks, int stride, int cin, i
 int conv_wgrad_num_tiles(int B, int Ho, int Wo, int variant);  // with the tile width of that variant's kernel
 int conv_wgrad_variant(int ks, int stride, int Wo, int cin, int cout);  // 0..5 (conv_wgrad.hip), -1: no kernel
 hipError_t conv_wgrad_launch(const WgradParams &p, int ks, int stride, float *dw, hipStream_t s, int act_dtype = 0);
+
+// Device optimizer step (optim.hip): one launch over a device-resident table.  The table's structs and the arithmetic are in
+// optim_math.h (shared with a host build).
+struct OptimTensor;
+struct OptimGroup;
+struct OptimChunk;
+hipError_t launch_optim_step(int algo, const OptimTensor *tensors, int ntensors, const OptimGroup *groups, const OptimChunk *chunks, int nchunks,
+                             const float *grad_scale, const float *found_inf, int advance_steps, hipStream_t s);
+hipError_t launch_grads_nonfinite(const OptimTensor *tensors, const OptimChunk *chunks, int nchunks, const float *inv_scale, float *found_inf,
+                                  hipStream_t s);

@@ -122,7 +122,10 @@ class KeypointsModule:
         if precision not in self.PRECISIONS:
             raise ValueError(f"KeypointsModule: precision {precision!r} is not one of {self.PRECISIONS}")
         self.model, self.loss_fn, self.optimizer, self.precision = model, loss_fn, optimizer, precision
-        self.scalers: dict = {"optim": torch.amp.GradScaler("cuda")} if precision == "fp16" else {}
+        # (an optimizer of ..optim gets the scaler whose non-finite check is one launch over its table; any other, torch's own)
+        from ..optim import GradScaler, is_device_optimizer
+        scaler_cls = GradScaler if is_device_optimizer(optimizer) else torch.amp.GradScaler
+        self.scalers: dict = {"optim": scaler_cls("cuda")} if precision == "fp16" else {}
         model._bare().set_train_precision(precision)
 
     def state_dict(self) -> dict:

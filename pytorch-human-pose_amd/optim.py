@@ -1,0 +1,335 @@
+"""Optimizers whose step is one HIP launch (csrc/optim.hip): `Adam`, `AdamW`, `SGD`, the `GradScaler` that goes with them, and
+`create_optimizer`, the counterpart of the reference's utils/optim.py:40-45.
+
+The classes subclass torch.optim.Optimizer with torch's constructor arguments and defaults and keep torch's state format
+(`step`, `exp_avg`, `exp_avg_sq` / `momentum_buffer`), so param groups, LR schedulers, `state_dict()` / `load_state_dict()` and a
+hand-over to or from `torch.optim.Adam(capturable=True)` / `torch.optim.SGD` work as usual.  What they do not cover raises ValueError:
+amsgrad, maximize, differentiable, dampening != 0, sparse gradients, parameters that are not fp32 on one GPU.
+
+`_step_supports_amp_scaling = True`: a torch.amp.GradScaler hands `grad_scale` / `found_inf` to step() and never reads them on the
+host; a step with non-finite gradients is skipped on the device.  `GradScaler` below replaces the scaler's foreach non-finite check
+by one launch over the same table.  There is no fall-back to torch kernels.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _lib
+
+ALGO_ADAM, ALGO_ADAMW, ALGO_SGD = 0, 1, 2  # HH_OPTIM_* of include/hhrnet.h
+UPLOAD_TENSORS, UPLOAD_GROUPS, UPLOAD_ALL = 1, 2, 3
+# hh_optim_tensor / hh_optim_group of include/hhrnet.h (56 bytes each)
+_TENSOR = np.dtype([("param", "<u8"), ("grad", "<u8"), ("state0", "<u8"), ("state1", "<u8"), ("step", "<u8"), ("numel", "<i8"),
+                    ("group", "<i4"), ("reserved", "<i4")])
+_GROUP = np.dtype([("lr", "<f8"), ("beta1", "<f8"), ("beta2", "<f8"), ("eps", "<f8"), ("weight_decay", "<f8"), ("momentum", "<f8"),
+                   ("nesterov", "<i4"), ("reserved", "<i4")])
+assert _TENSOR.itemsize == 56 and _GROUP.itemsize == 56
+
+
+class _DeviceOptimizer(torch.optim.Optimizer):
+    """What the three classes share: the descriptor table, its upkeep, and the two launches.
+
+    Table upkeep.  The set of parameters that have a gradient decides the table's rows; while it stays the same only the gradient
+    pointers are gathered per step (they change under zero_grad(set_to_none=True)), and the table is copied to the device only when a
+    pointer or a hyper-parameter differs from what the device already holds.  A new set (first step, a parameter frozen or added, a
+    loaded state dict) rebuilds the rows, creates missing state and checks every gradient's dtype and layout."""
+
+    _step_supports_amp_scaling = True
+    ALGO = -1
+    STATE_KEYS: tuple = ()
+
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
+        devices = set()
+        for group in self.param_groups:
+            self._check_group(group)
+            for p in group["params"]:
+                if p.dtype != torch.float32 or not p.is_cuda:
+                    raise ValueError(f"{type(self).__name__}: parameters must be fp32 tensors on the GPU, got {p.dtype} on {p.device}")
+                if p.layout != torch.strided:
+                    raise ValueError(f"{type(self).__name__}: sparse parameters are not supported")
+                devices.add(p.device)
+        if len(devices) > 1:
+            raise ValueError(f"{type(self).__name__}: all parameters must be on one device, got {sorted(map(str, devices))}")
+        self._rows = None  # the table of the current active set
+
+    # ---- per-algorithm parts
+    def _check_group(self, group) -> None:
+        raise NotImplementedError
+
+    def _fill_group(self, rec, group) -> None:
+        raise NotImplementedError
+
+    def _needs_state0(self, group) -> bool:
+        return True
+
+    # ---- torch.optim.Optimizer
+    def add_param_group(self, param_group) -> None:
+        super().add_param_group(param_group)
+        self._rows = None
+
+    def load_state_dict(self, state_dict) -> None:
+        super().load_state_dict(state_dict)
+        for group in self.param_groups:
+            self._check_group(group)
+        self._rows = None
+
+    # ---- the table
+    def _rebuild(self, params, groups_of, mask: bytes):
+        name = type(self).__name__
+        dev = params[0].device
+        adam = self.ALGO != ALGO_SGD
+        active = [i for i, m in enumerate(mask) if m]
+        for i in active:
+            p, g = params[i], params[i].grad
+            if g.layout != torch.strided:
+                raise ValueError(f"{name}: sparse gradients are not supported")
+            if g.dtype != torch.float32 or g.device != p.device:
+                raise ValueError(f"{name}: gradients must be fp32 on the parameter's device, got {g.dtype} on {g.device}")
+            if not p.is_contiguous() and not (p.dim() == 4 and p.is_contiguous(memory_format=torch.channels_last)):
+                raise ValueError(f"{name}: parameters must be dense (contiguous or channels_last)")
+            if g.stride() != p.stride() and p.numel() > 1:
+                raise ValueError(f"{name}: a gradient's memory layout differs from its parameter's: strides {g.stride()} vs {p.stride()}")
+        # state of the active parameters, in torch's format; the step counters of ALL parameters are views of one buffer
+        if adam:
+            old = [self.state[p].get("step") if p in self.state else None for p in params]
+            steps = torch.zeros(len(params), dtype=torch.float32, device=dev)
+            have = [i for i, s in enumerate(old) if s is not None]
+            have_set = set(have)
+            if have:
+                vals = torch.stack([torch.as_tensor(old[i]).detach().to(device=dev, dtype=torch.float32).reshape(()) for i in have])
+                steps[torch.tensor(have, device=dev)] = vals
+            for i, p in enumerate(params):
+                if i in have_set or mask[i]:
+                    self.state[p]["step"] = steps[i]
+        rows = np.zeros(len(active), dtype=_TENSOR)
+        keep = [steps] if adam else []  # the state tensors the rows point into stay alive as long as the rows do
+        for r, i in enumerate(active):
+            p = params[i]
+            st = self.state[p]
+            need = self.STATE_KEYS if (adam or self._needs_state0(self.param_groups[groups_of[i]])) else ()
+            for k in need:
+                t = st.get(k)
+                if t is None:
+                    t = st[k] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                elif t.dtype != torch.float32 or t.device != p.device or (t.stride() != p.stride() and p.numel() > 1):
+                    t = st[k] = torch.empty_like(p, memory_format=torch.preserve_format).copy_(t)  # (a state dict from elsewhere)
+                keep.append(t)
+            rec = rows[r]
+            rec["numel"] = p.numel()
+            rec["group"] = groups_of[i]
+            for slot, k in zip(("state0", "state1"), need):
+                rec[slot] = st[k].data_ptr()
+            if adam:
+                rec["step"] = st["step"].data_ptr()
+        lib = _lib.load()
+        ngroups = len(self.param_groups)
+        nbytes = lib.hh_optim_table_bytes(rows.ctypes.data, len(rows), ngroups)
+        if nbytes < 0:
+            raise _lib.HHError(lib.hh_last_error().decode())
+        self._rows = dict(mask=mask, active=active, rows=rows, dev=dev, nbytes=nbytes,
+                          table=torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev),
+                          groups=np.zeros(ngroups, dtype=_GROUP), sent_tensors=None, sent_groups=None, sent_stream=None, keep=keep)
+        return self._rows
+
+    def _table(self):
+        """-> (table record, upload mask) for this step's gradients and hyper-parameters; None when no parameter has a gradient."""
+        params, groups_of = [], []
+        for gi, group in enumerate(self.param_groups):
+            ps = group["params"]
+            params += ps
+            groups_of += [gi] * len(ps)
+        grads = [p.grad for p in params]
+        mask = bytes(g is not None for g in grads)
+        if not any(mask):
+            return None, 0
+        T = self._rows
+        if T is None or T["mask"] != mask or len(T["groups"]) != len(self.param_groups):
+            T = self._rebuild(params, groups_of, mask)
+        rows = T["rows"]
+        # the per-step gather: parameter pointers too (module.to() / p.data = ... moves them), state pointers only on a rebuild
+        rows["param"] = [params[i].data_ptr() for i in T["active"]]
+        rows["grad"] = [g.data_ptr() for g in grads if g is not None]
+        groups = T["groups"]
+        for gi, group in enumerate(self.param_groups):
+            self._fill_group(groups[gi], group)
+        upload = 0
+        tb, gb = rows.tobytes(), groups.tobytes()
+        stream = torch.cuda.current_stream(T["dev"]).cuda_stream
+        if T["sent_stream"] != stream:  # the copies of an earlier step are ordered before this one only on their own stream
+            T["sent_tensors"] = T["sent_groups"] = None
+            T["sent_stream"] = stream
+        if T["sent_tensors"] != tb:
+            upload |= UPLOAD_TENSORS
+        if T["sent_groups"] != gb:
+            upload |= UPLOAD_GROUPS
+        T["pending"] = (tb, gb)
+        return T, upload
+
+    @staticmethod
+    def _sent(T, upload) -> None:
+        tb, gb = T.pop("pending")
+        if upload & UPLOAD_TENSORS:
+            T["sent_tensors"] = tb
+        if upload & UPLOAD_GROUPS:
+            T["sent_groups"] = gb
+
+    @staticmethod
+    def _scalar_ptr(t, what, dev):
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or t.numel() != 1:
+            raise ValueError(f"{what} must be an fp32 scalar tensor on {dev}")
+        return t.data_ptr()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        T, upload = self._table()
+        if T is not None:
+            dev, rows, groups = T["dev"], T["rows"], T["groups"]
+            scale = self._scalar_ptr(getattr(self, "grad_scale", None), "grad_scale", dev)
+            found = self._scalar_ptr(getattr(self, "found_inf", None), "found_inf", dev)
+            with torch.cuda.device(dev):
+                _lib.check(_lib.load().hh_optim_step(self.ALGO, rows.ctypes.data, len(rows), groups.ctypes.data, len(groups), scale, found,
+                                                     T["table"].data_ptr(), T["nbytes"], upload, torch.cuda.current_stream(dev).cuda_stream))
+            self._sent(T, upload)
+        return loss
+
+    @torch.no_grad()
+    def check_grads_nonfinite(self, found_inf: torch.Tensor, inv_scale: torch.Tensor | None = None) -> None:
+        """One launch over every gradient: found_inf (fp32 device scalar, zeroed by the caller) becomes 1 if any element is inf or
+        NaN, and the gradients are multiplied by inv_scale in place unless it is None or holds 1 (GradScaler.unscale_)."""
+        T, upload = self._table()
+        if T is not None:
+            dev, rows = T["dev"], T["rows"]
+            upload &= UPLOAD_TENSORS
+            with torch.cuda.device(dev):
+                _lib.check(_lib.load().hh_grads_nonfinite(rows.ctypes.data, len(rows), len(T["groups"]), self._scalar_ptr(inv_scale, "inv_scale", dev),
+                                                          self._scalar_ptr(found_inf, "found_inf", dev), T["table"].data_ptr(), T["nbytes"], upload,
+                                                          torch.cuda.current_stream(dev).cuda_stream))
+            self._sent(T, upload)
+
+
+def _refuse(name, **flags):
+    for k, v in flags.items():
+        if v:
+            raise ValueError(f"{name}: {k}={v!r} is not supported by the device optimizer")
+
+
+class _AdamBase(_DeviceOptimizer):
+    STATE_KEYS = ("exp_avg", "exp_avg_sq")
+    DECOUPLED = False
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, *, foreach=None, maximize=False,
+                 capturable=True, differentiable=False, fused=None):
+        if isinstance(lr, torch.Tensor):
+            raise ValueError(f"{type(self).__name__}: lr must be a Python number (it is read from the group at every step)")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameters: {betas}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        # torch's keys, so that a state dict loads into torch.optim.Adam(capturable=True): the step counters live on the device
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=None, capturable=True,
+                        differentiable=differentiable, fused=None, decoupled_weight_decay=self.DECOUPLED)
+        super().__init__(params, defaults)
+
+    def _check_group(self, group) -> None:
+        _refuse(type(self).__name__, amsgrad=group.get("amsgrad", False), maximize=group.get("maximize", False),
+                differentiable=group.get("differentiable", False))
+        b1, b2 = group["betas"]
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"Invalid beta parameters: {group['betas']}")
+
+    def _fill_group(self, rec, group) -> None:
+        rec["lr"], rec["eps"], rec["weight_decay"] = float(group["lr"]), float(group["eps"]), float(group["weight_decay"])
+        rec["beta1"], rec["beta2"] = float(group["betas"][0]), float(group["betas"][1])
+
+
+class Adam(_AdamBase):
+    """torch.optim.Adam (L2 weight decay) as one launch."""
+    ALGO = ALGO_ADAM
+
+
+class AdamW(_AdamBase):
+    """torch.optim.AdamW (decoupled weight decay, default 1e-2) as one launch."""
+    ALGO = ALGO_ADAMW
+    DECOUPLED = True
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, **kw):
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, **kw)
+
+
+class SGD(_DeviceOptimizer):
+    """torch.optim.SGD with weight decay, momentum and Nesterov momentum (dampening 0) as one launch.  The momentum buffer starts at
+    zero, which at dampening 0 is torch's first step (buf = g) bit for bit."""
+    ALGO = ALGO_SGD
+    STATE_KEYS = ("momentum_buffer",)
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, *, maximize=False, foreach=None,
+                 differentiable=False, fused=None):
+        if isinstance(lr, torch.Tensor):
+            raise ValueError("SGD: lr must be a Python number (it is read from the group at every step)")
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and momentum <= 0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, maximize=maximize, foreach=None,
+                        differentiable=differentiable, fused=None)
+        super().__init__(params, defaults)
+
+    def _check_group(self, group) -> None:
+        _refuse("SGD", maximize=group.get("maximize", False), differentiable=group.get("differentiable", False))
+        if group.get("dampening", 0) != 0:
+            raise ValueError(f"SGD: dampening={group['dampening']!r} is not supported by the device optimizer (only 0)")
+
+    def _needs_state0(self, group) -> bool:
+        return group["momentum"] != 0
+
+    def _fill_group(self, rec, group) -> None:
+        rec["lr"], rec["weight_decay"], rec["momentum"] = float(group["lr"]), float(group["weight_decay"]), float(group["momentum"])
+        rec["nesterov"] = 1 if group["nesterov"] else 0
+
+    def _rebuild(self, params, groups_of, mask):
+        for p in params:  # torch keeps momentum_buffer = None for a parameter it has not stepped with momentum: same as absent here
+            st = self.state.get(p)
+            if st is not None and "momentum_buffer" in st and st["momentum_buffer"] is None:
+                del st["momentum_buffer"]
+        return super()._rebuild(params, groups_of, mask)
+
+
+class GradScaler(torch.amp.GradScaler):
+    """torch.amp.GradScaler whose non-finite check (and unscale_) over an optimizer of this module is one launch instead of the foreach
+    family; any other optimizer goes through the parent.  State dict and public behaviour are the parent's."""
+
+    def _unscale_grads_(self, optimizer, inv_scale, found_inf, allow_fp16):
+        if not isinstance(optimizer, _DeviceOptimizer):
+            return super()._unscale_grads_(optimizer, inv_scale, found_inf, allow_fp16)
+        optimizer.check_grads_nonfinite(found_inf, inv_scale)
+        return {found_inf.device: found_inf}
+
+
+# utils/optim.py:10-18 of the reference: the three with a kernel here, the other four torch's own
+optimizers = {"Adam": Adam, "AdamW": AdamW, "SGD": SGD, "Adamax": torch.optim.Adamax, "Adadelta": torch.optim.Adadelta,
+              "Adagrad": torch.optim.Adagrad, "RMSprop": torch.optim.RMSprop}
+
+
+def create_optimizer(net: torch.nn.Module, name: str, **params) -> torch.optim.Optimizer:
+    """utils/optim.py:40-45: the named optimizer over the net's trainable parameters."""
+    return optimizers[name](filter(lambda p: p.requires_grad, net.parameters()), **params)
+
+
+def is_device_optimizer(optimizer) -> bool:
+    return isinstance(optimizer, _DeviceOptimizer)
