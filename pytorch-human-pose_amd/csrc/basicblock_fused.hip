@@ -18,6 +18,13 @@
 //   * the residual is two extra MFMAs per column tile with an identity A fragment (exact: x * 1.0 in fp32)
 //     instead of 16 LDS reads + 16 converts + 16 adds per lane
 //   * epilogues pair the two half-waves with v_permlane32_swap so every lane writes 16 contiguous bytes.
+//
+// What keeps this file alive: the default 32-channel block is the producer / consumer form (basicblock_fused_pc.hip).  This "tile
+// form" is (1) the launch hh_net::enqueue_bb falls back to when bbpc_supported() is false (a tensor of 2 GB or more: the other form
+// addresses with 32-bit buffer offsets), and (2) the second implementation behind HH_BB32=tile (PlanSwitches::bb32_tile), which
+// test_fused_32_channel_block_both_forms holds to the golden tolerance beside the default and test_forward_does_not_depend_on_stale_lds,
+// test_many_live_handles_interleaved_forwards_stay_bit_exact and test_multi_lane_schedule_has_no_unordered_hazard run as a plan variant.
+// tools/bb_bench.py and tools/bb_compare.py time it through the C API.
 #include "mfma_dev.h"
 
 namespace {
@@ -53,9 +60,7 @@ __global__ __launch_bounds__(NTHR, 1) void bb_fused_kernel(const BBParams p)
     float *lds_b = reinterpret_cast<float *>(lds_w2 + W_BYTES);  // [2][32] folded BN shifts (re-read at every accumulator init:
                                                                  // 32 live VGPRs would push the 256-register budget into scratch)
     const int tid = threadIdx.x;
-#ifndef HH_NO_CLK
     if (p.clk && tid == 0) atomicMin(p.clk, wall_clock64());
-#endif
 #ifdef HH_STAMP  // in-kernel clock of workgroup 0: d(s_memtime) / d(s_memrealtime) x 100 MHz (MI355X_MICROARCH.md, DVFS give-back item 6)
     if (p.stamps && blockIdx.x == 0 && tid == 0) { p.stamps[64] = __builtin_amdgcn_s_memtime(); p.stamps[65] = __builtin_amdgcn_s_memrealtime(); }
 #endif
@@ -295,9 +300,7 @@ __global__ __launch_bounds__(NTHR, 1) void bb_fused_kernel(const BBParams p)
     }
 #pragma unroll
     for (int q = 0; q < 2; ++q) store_rows(q);
-#ifndef HH_NO_CLK
     if (p.clk && tid == 0) atomicMax(p.clk + 1, wall_clock64());
-#endif
 #ifdef HH_STAMP
     if (p.stamps && blockIdx.x == 0 && tid == 0) { p.stamps[66] = __builtin_amdgcn_s_memtime(); p.stamps[67] = __builtin_amdgcn_s_memrealtime(); }
 #endif

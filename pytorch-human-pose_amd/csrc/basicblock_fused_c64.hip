@@ -46,9 +46,7 @@ __global__ __launch_bounds__(NTHR, 1) void bb64_fused_kernel(const BBParams p)
     float *lds_b = reinterpret_cast<float *>(lds_w + W_BYTES);  // [2][64] folded BN shifts
 
     const int tid = threadIdx.x;
-#ifndef HH_NO_CLK
     if (p.clk && tid == 0) atomicMin(p.clk, wall_clock64());
-#endif
     const int wave = tid >> 6, lane = tid & 63;
     const int r = lane & 31, h = lane >> 5;
     const int ct = wave & 1, part = wave >> 1;
@@ -301,9 +299,7 @@ __global__ __launch_bounds__(NTHR, 1) void bb64_fused_kernel(const BBParams p)
     }
 #pragma unroll
     for (int q = 0; q < 2; ++q) store_rows(q);
-#ifndef HH_NO_CLK
     if (p.clk && tid == 0) atomicMax(p.clk + 1, wall_clock64());
-#endif
 }
 
 hipError_t bb64_fused_init() { return bb_tile_init(bb64_fused_kernel, bb64_lds_bytes()); }

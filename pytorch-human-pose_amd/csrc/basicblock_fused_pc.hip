@@ -22,19 +22,17 @@
 //
 // Measured (tools/bb_compare.py, 1 s of back-to-back launches, B = 32): 128x128 26.9 us vs 27.4 us for the tile form, 256x256
 // 90 vs 94 us; in the forward 5.03 vs 5.12 ms (4 lanes), 5.75 vs 5.95 ms (one lane).  Halving the LDS reads bought this little
-// because neither form is bound by the LDS or by issue slots: with every load and store compiled out (-DBBPC_NOLOAD -DBBPC_NOSTORE
-// -DBBPC_NORES) the same instruction stream runs the 256x256 case in 65 us at an in-kernel clock of 2.40 GHz; with its 268 MB
-// of HBM traffic it takes 8 % more cycles and the chip holds only 1.9-2.0 GHz (d s_memtime / d s_memrealtime, -DHH_STAMP
-// build) -- the block is bound by what the chip can power: HBM streaming at ~3 TB/s beside ~0.85 PFLOP/s of MFMA.
+// because neither form is bound by the LDS or by issue slots: a diagnostic build of the same instruction stream with every load and
+// store compiled out ran the 256x256 case in 65 us at an in-kernel clock of 2.40 GHz; with its 268 MB of HBM traffic it takes 8 %
+// more cycles and the chip holds only 1.9-2.0 GHz (d s_memtime / d s_memrealtime, -DHH_STAMP build) -- the block is bound by what
+// the chip can power: HBM streaming at ~3 TB/s beside ~0.85 PFLOP/s of MFMA ("Power, not pipes" in profiles/design_notes_r01_r03.md,
+// the residual-free build in profiles/r03_ab.md).  The depth of the fragment read-ahead (RD / RDC below) moves nothing either:
+// profiles/r04_ab.md, 8.8.
 #include "mfma_dev.h"
 
 #include <vector>
 
 namespace {
-#ifndef BBPC_STORE_AUX
-#define BBPC_STORE_AUX 0  // cache policy bits of the output stores.  Experiment: 2 (nt) makes the block itself faster when its output is never
-                          // read (128x128: 28.5 -> 25.4 us in tools/bb_compare.py) and the forward SLOWER (4.67 -> 4.72 ms): the next launch reads it
-#endif
 constexpr int TH = BBPC_TH, TW = BBPC_TW;  // output tile: 14 x 32 (kernels.h, beside the tile geometry the host walk shares)
 constexpr int MH = TH + 2, MW = TW + 2;  // conv1 output (= conv2 input) tile: 16 x 34
 constexpr int IH = TH + 4, IW = TW + 4;  // input patch: 18 x 36
@@ -45,14 +43,8 @@ constexpr int MID_BYTES = MH * MW * 64;     // 34,816
 constexpr int P_UNITS = IH * IW * 4;        // 2592 16-byte units
 constexpr int NPL = (P_UNITS + NTHR - 1) / NTHR;  // 6 (the last round: 32 threads)
 // LDS fragment reads run RD steps (1-3 MFMAs each) ahead of the MFMAs that use them
-#ifndef BBPC_RD
-#define BBPC_RD 2
-#endif
-#ifndef BBPC_RDC
-#define BBPC_RDC 4
-#endif
-constexpr int RD = BBPC_RD, NFB = RD + 1;     // producer
-constexpr int RDC = BBPC_RDC, NFBC = RDC + 1;  // consumer (more registers to spare)
+constexpr int RD = 2, NFB = RD + 1;     // producer
+constexpr int RDC = 4, NFBC = RDC + 1;  // consumer (more registers to spare)
 constexpr int RP = MH / 4;                  // mid rows per producer wave
 static_assert(MH % 4 == 0 && 2 * MH == 32, "4 producer bands; the two extra mid columns make exactly one 32-pixel column tile");
 constexpr int OFF_MID = 2 * PATCH_BYTES, OFF_BIAS = OFF_MID + 2 * MID_BYTES;
@@ -77,12 +69,10 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
-#ifndef HH_NO_CLK
     if (p.clk && tid == 0) atomicMin(p.clk, wall_clock64());
     // workgroup 0 also leaves its core-cycle and wall-tick counts: their ratio is the clock the chip held during this launch
     const unsigned long long clk_c0 = p.clk && blockIdx.x == 0 ? __builtin_amdgcn_s_memtime() : 0ull;
     const unsigned long long clk_r0 = p.clk && blockIdx.x == 0 ? __builtin_amdgcn_s_memrealtime() : 0ull;
-#endif
 #ifdef HH_STAMP  // in-kernel clock of workgroup 0: d(s_memtime) / d(s_memrealtime) x 100 MHz (MI355X_MICROARCH.md, DVFS give-back item 6)
     if (p.stamps && blockIdx.x == 0 && tid == 0) { p.stamps[64] = __builtin_amdgcn_s_memtime(); p.stamps[65] = __builtin_amdgcn_s_memrealtime(); }
 #endif
@@ -169,11 +159,7 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
         const bool wrap = yy >= p.VH;  // (tall layout) the row belongs to the next image
         const bool ok = pf_xok & ((unsigned)(wrap ? yy - p.VH : yy) < (unsigned)p.H) & (!wrap | pf_next);
         const unsigned voff = ok ? pf_vbase + (unsigned)(i * pf_rowstep) - (wrap ? (unsigned)pf_gapstep : 0u) : OOB;  // outside the image: zero = conv1's padding
-#ifdef BBPC_NOLOAD  // timing experiment: no patch traffic (results are wrong)
-        preg[i] = u32x4{voff, 0u, 0u, 0u};
-#else
         preg[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)voff, 0, 0));
-#endif
     };
     auto pf_write = [&](auto ic, int patch_off) {
         constexpr int i = decltype(ic)::value;
@@ -340,13 +326,10 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
                     u32x4 o[2];
                     pack_rows16(acc[j], o);
                     const bool ok = (fr >= 0) & (ox < p.W);
-#ifdef BBPC_NOSTORE
-                    const unsigned voff = (ok && o[0][0] == 0x12345678u) ? (unsigned)((fr * p.W + ox) * p.out_cs * 2 + 16 * h) : OOB;
-#else
                     const unsigned voff = ok ? (unsigned)((fr * p.W + ox) * p.out_cs * 2 + 16 * h) : OOB;
-#endif
-                    __builtin_amdgcn_raw_buffer_store_b128(o[0], rs_out, (int)voff, 0, BBPC_STORE_AUX);
-                    __builtin_amdgcn_raw_buffer_store_b128(o[1], rs_out, (int)voff, 32, BBPC_STORE_AUX);
+                    // (cache policy 0: nt stores make the block itself faster, 128x128 28.5 -> 25.4 us, and the forward SLOWER, 4.67 -> 4.72 ms: the next launch reads the output)
+                    __builtin_amdgcn_raw_buffer_store_b128(o[0], rs_out, (int)voff, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b128(o[1], rs_out, (int)voff, 32, 0);
                 }
             };
             for (int it = 0; it <= nloc; ++it) {
@@ -368,11 +351,7 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
                         const unsigned voff = ok ? (unsigned)((fr * p.W + ox) * p.in_cs * 2 + 16 * h) : OOB;
 #pragma unroll
                         for (int m = 0; m < 2; ++m)
-#ifdef BBPC_NORES
-                            res[j][m] = u32x4{voff, 0u, 0u, 0u};
-#else
                             res[j][m] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)voff, 32 * m, 0));
-#endif
                     }
                 }
                 static_for<NPL>(pf_load);  // the next patch: written to LDS late in the MFMA loop
@@ -457,14 +436,10 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
 #pragma unroll
                             for (int q = 0; q < 4; ++q) {
                                 const bool ok = lane_ok & row_ok & (g.ox0 + 8 * q + 4 * h < p.W);  // (W % 4 == 0: the four pixels are inside together)
-#ifdef BBPC_NOSTORE
-                                const unsigned voff = (ok && d[0] == 1.2345f) ? row_off + lane_off : OOB;
-#else
                                 const unsigned voff = ok ? row_off + lane_off : OOB;
-#endif
                                 __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(d[4 * q] + fb), __float_as_uint(d[4 * q + 1] + fb),
                                                                              __float_as_uint(d[4 * q + 2] + fb), __float_as_uint(d[4 * q + 3] + fb)},
-                                                                       rs_out, (int)voff, 32 * q, BBPC_STORE_AUX);
+                                                                       rs_out, (int)voff, 32 * q, 0);
                             }
                         }
                     }
@@ -480,13 +455,11 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
         if (wj < 2) consumer_loop(std::integral_constant<int, 4>{});
         else consumer_loop(std::integral_constant<int, 3>{});
     }
-#ifndef HH_NO_CLK
     if (p.clk && tid == 0) atomicMax(p.clk + 1, wall_clock64());
     if (p.clk && blockIdx.x == 0 && tid == 0) {
         p.clk[2] = __builtin_amdgcn_s_memtime() - clk_c0;
         p.clk[3] = __builtin_amdgcn_s_memrealtime() - clk_r0;
     }
-#endif
 #ifdef HH_STAMP
     if (p.stamps && blockIdx.x == 0 && tid == 0) { p.stamps[66] = __builtin_amdgcn_s_memtime(); p.stamps[67] = __builtin_amdgcn_s_memrealtime(); }
 #endif

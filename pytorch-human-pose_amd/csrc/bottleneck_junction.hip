@@ -23,9 +23,6 @@ __device__ __forceinline__ void add_rows16(f32x16 &acc, const u32x4 v[2])
         acc[8 * m + 6] += bf16_lo(s1[1]); acc[8 * m + 7] += bf16_hi(s1[1]);
     }
 }
-#ifndef JUNC_PREFETCH
-#define JUNC_PREFETCH 1
-#endif
 constexpr int W3_BYTES = 256 * 64 * 2;  // conv3 / downsample: packed [cout group 4][chunk 2][c8 4][64][8] (conv_mfma family, NT = 2)
 constexpr int W1_BYTES = 64 * 256 * 2;  // next conv1: packed [chunk 8][c8 4][64][8]
 }  // namespace
@@ -51,9 +48,7 @@ __global__ __launch_bounds__(MODE == 1 ? 512 : 256, (MODE == 0 || MODE == 3) ? 2
     float *lds_b = reinterpret_cast<float *>(lds_w1 + (p.w1 ? W1_BYTES : 0));  // [256] y shift, [64] t1 shift, [256] previous y shift (PAIR)
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-#ifndef HH_NO_CLK
     if (p.clk && tid == 0) atomicMin(p.clk, wall_clock64());
-#endif
     for (int u = tid; u < W3_BYTES / 16; u += NT) {
         reinterpret_cast<u32x4 *>(lds_w3)[u] = reinterpret_cast<const u32x4 *>(p.w3)[u];
         if (HAS_DS) reinterpret_cast<u32x4 *>(lds_wd)[u] = reinterpret_cast<const u32x4 *>(p.wd)[u];
@@ -73,7 +68,7 @@ __global__ __launch_bounds__(MODE == 1 ? 512 : 256, (MODE == 0 || MODE == 3) ? 2
     // pixel fragments (B operands) of a group.  MODE 2 loads them one group AHEAD (round 4): its workgroup is alone on the CU, one wave per
     // SIMD, and every group began with a full HBM round trip in front of its first MFMA that nobody covered: 152 -> 125 us.  (The
     // other modes run two waves per SIMD, which cover each other: 1-2 us SLOWER with the 16-48 more registers, MODE 3 spills.)
-    constexpr bool PF = JUNC_PREFETCH && MODE == 2;
+    constexpr bool PF = MODE == 2;
     struct Frags { u32x4 bt[4], bx[HAS_DS ? 4 : 1], bta[PAIR ? 4 : 1]; };
     auto load_frags = [&](int g, Frags &f) {
         const int pixn = g * GP + wave * 32 + r;
@@ -207,9 +202,7 @@ __global__ __launch_bounds__(MODE == 1 ? 512 : 256, (MODE == 0 || MODE == 3) ? 2
             }
         }
     }
-#ifndef HH_NO_CLK
     if (p.clk && tid == 0) atomicMax(p.clk + 1, wall_clock64());
-#endif
 }
 
 static size_t junc_lds(int mode, bool w1 = true)

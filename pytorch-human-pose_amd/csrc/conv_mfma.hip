@@ -88,12 +88,10 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
     const int iy0 = oy0 * S - pad_y, ix0 = ox0 * S - pad_x;
 
     const int tid = threadIdx.x;
-#ifndef HH_NO_CLK
     // (grids reach 16384 workgroups: only the first / last 256 dispatched stamp, or the same-address atomics would show up
     // in the very duration they measure)
     CONV_STAMP(0);
     if (p.clk && tid == 0 && blockIdx.x < 256) atomicMin(p.clk, wall_clock64());
-#endif
     const int wave = tid >> 6, lane = tid & 63;
     const int r = lane & 31, h = lane >> 5;
     const int wp = wave / WC, wc = wave % WC;
@@ -434,10 +432,8 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
             }
         }
     }
-#ifndef HH_NO_CLK
     CONV_STAMP(6);
     if (p.clk && tid == 0 && blockIdx.x + 256 >= gridDim.x) atomicMax(p.clk + 1, wall_clock64());
-#endif
 }
 
 // ---------------------------------------------------------------------------------------

@@ -155,10 +155,9 @@ __device__ __forceinline__ float bound_of(unsigned short hb, const unsigned *__r
 
 }  // namespace
 
-#ifndef REFINE_THREADS
-#define REFINE_THREADS 128  // per job.  The evaluation needs ~160 registers, i.e. 3 wavefronts per SIMD: with 256-thread workgroups 768 jobs
-#endif                      // run at once and the bench's ~900 take two rounds; with 128 threads 1536 do, each a little slower
-constexpr int RT = REFINE_THREADS, RW = RT / 64;
+// Threads per job.  The evaluation needs ~160 registers, i.e. 3 wavefronts per SIMD: with 256-thread workgroups 768 jobs run at once and
+// the bench's ~900 take two rounds; with 128 threads 1536 do, each a little slower
+constexpr int RT = 128, RW = RT / 64;
 __global__ __launch_bounds__(RT, 3) void refine_bb_kernel(const DecodeSrc src, int M, const int32_t *__restrict__ ws_jobs,
                                                            const float *__restrict__ ws_prev, const unsigned short *__restrict__ cellub,
                                                            const unsigned *__restrict__ tagb, const unsigned short *__restrict__ supmax,

@@ -23,7 +23,6 @@ PlanSwitches PlanSwitches::from_env()
     PlanSwitches s;
     s.bb32_tile = is("HH_BB32", "tile");
     s.no_bb64 = on("HH_NO_BB64");
-    s.no_bb_fp8 = on("HH_NO_BB_FP8");
     s.no_stem_fused = on("HH_NO_STEM_FUSED");
     s.no_junc_pair = on("HH_NO_JUNC_PAIR");
     s.full_join = on("HH_FULL_JOIN");
@@ -37,15 +36,6 @@ PlanSwitches PlanSwitches::from_env()
     s.keep_waits = on("HH_KEEP_WAITS");
     s.event_system_fence = on("HH_EVENT_SYSTEM_FENCE");
     s.bb_tall = on("HH_NO_BB_TALL") ? 0 : is("HH_BB_TALL", "always") ? 2 : 1;
-    if (const char *fc = getenv("HH_FAT_CUS")) { s.fat_cus = s.fat_cus64 = atoi(fc); if (const char *c2 = strchr(fc, ',')) s.fat_cus64 = atoi(c2 + 1); }
-    if (const char *sk = getenv("HH_DEBUG_SKIP")) {
-        static const struct { const char *name; unsigned bit; } cats[] = {{"s2big", SK_S2BIG}, {"s2", SK_S2}, {"upadd", SK_UPADD}, {"c1x1", SK_C1X1},
-            {"c256", SK_C256}, {"c128", SK_C128}, {"junc", SK_JUNC}, {"bb32", SK_BB32}, {"bb64", SK_BB64}, {"stem", SK_STEM}, {"deconv", SK_DECONV},
-            {"head", SK_HEAD}, {"trans0", SK_TRANS0}, {"upsum", SK_UPSUM}};
-        std::string v = std::string(",") + sk + ",";
-        for (const auto &c : cats)
-            if (v.find(std::string(",") + c.name + ",") != std::string::npos) s.debug_skip |= c.bit;
-    }
     s.fp8_trunk8 = is("HH_FP8_TRUNK", "e4m3");
     s.fp8_heads8 = is("HH_FP8_HEADS", "e4m3");
     return s;
@@ -256,7 +246,7 @@ struct Builder {
         // layer-by-layer launches share CUs with the 256-channel branch.  Removed; `git log` has it.)
         for (int u = 0; u < 4; ++u) {
             const std::string up = prefix + "." + std::to_string(u);
-            const bool fused_fp8 = n.dtype == 2 && bb_fp8_supported(C) && branch == 0 && !n.sw.no_bb_fp8;  // highest-resolution branch / deconv head
+            const bool fused_fp8 = n.dtype == 2 && bb_fp8_supported(C) && branch == 0;  // highest-resolution branch / deconv head
             if (((C == 32 || (C == 64 && !n.sw.no_bb64)) && n.dtype != 2) || fused_fp8) {  // fused kernels, ping-pong x <-> m (a tile reads its neighbours' halo: no in-place)
                 Op o;
                 o.kind = OP_BB;
@@ -995,7 +985,6 @@ int hh_net::enqueue(const float *images, int B, int H, int W, float *o1, float *
         hipStream_t s = L[op.lane];
         if (fin_done >= 0 && &op == &ops[fin_done]) continue;
         if (!is_edge(op.kind)) lc.launch(op.lane);  // (a launch, or nothing: over-counting only keeps a wait)
-        if (sw.debug_skip && (hh_skip_cats(op, layers, tensors) & sw.debug_skip)) continue;  // measurement only: the outputs are wrong
         if (sw.poison_lds && !is_edge(op.kind) && op.kind != OP_TAP) HH_CHECK_HIP(launch_lds_poison(num_cus, s));
         int rc = 0;
         switch (op.kind) {
@@ -1186,7 +1175,7 @@ int hh_net::enqueue_bb(const Op &op, int B, int H, int W, float *o2, bool multi,
     p.w1 = l1.d_w; p.w2 = l2.d_w; p.b1 = l1.d_bias; p.b2 = l2.d_bias;
     p.B = B; p.H = H >> ti.shift; p.W = W >> ti.shift;
     p.tall = sw.bb_tall;
-    if (op.fin >= 0 && !sw.no_final_fuse && !sw.bb32_tile && !taps_enabled && o2 && !(sw.debug_skip & SK_HEAD)) {
+    if (op.fin >= 0 && !sw.no_final_fuse && !sw.bb32_tile && !taps_enabled && o2) {
         const ConvLayer &lf = layers[ops[op.fin].layer];
         p.fin_w = lf.d_wfin; p.fin_b = lf.d_bias; p.fin_out = o2; p.fin_K = lf.cout;
         if (lf.d_wfin && bbpc_final_supported(p)) *fin_done = op.fin;
@@ -1194,10 +1183,13 @@ int hh_net::enqueue_bb(const Op &op, int B, int H, int W, float *o2, bool multi,
     }
     const int cfg = l1.cout == 64 ? HH_CFG_BB64_FUSED : HH_CFG_BB_FUSED;
     if (prof_enabled && prof_record(op, cfg, op_cost(op, B, H, W, p.fin_out != nullptr), &p.clk)) return 1;
-    // inside an HR module with the lanes on: half the chip per fat kernel (PlanSwitches::fat_cus); alone: all of it
-    auto budget = [&](int want) { return !(multi && op.siblings) ? num_cus : want > 0 ? (want < num_cus ? want : num_cus) : (num_cus + 1) / 2; };
-    const int fat = budget(sw.fat_cus), fat64 = budget(sw.fat_cus64);
-    if (l1.cout == 64) HH_CHECK_HIP(bb64_fused_launch(p, fat64, s));
+    // Persistent workgroups of the fused 32- / 64-channel blocks.  Inside an HR module with the lanes on: half the CUs each.  The two
+    // fat kernels (150 KB of LDS per workgroup: a CU holds one of them and nothing else) then run side by side on disjoint halves of
+    // the chip instead of taking turns on all of it, and the thin launches of the 128- / 256-channel lanes find free CUs while either
+    // runs: forward 4.48 -> 4.39 ms, +1.5-2 % img/s (three alternations, profiles/r03_ab.md); a quarter of the chip for the
+    // 64-channel block loses 6 %.  Alone (outside an HR module, or with the lanes off): all of the chip.
+    const int fat = multi && op.siblings ? (num_cus + 1) / 2 : num_cus;
+    if (l1.cout == 64) HH_CHECK_HIP(bb64_fused_launch(p, fat, s));
     else if (!sw.bb32_tile && bbpc_supported(p)) HH_CHECK_HIP(bbpc_launch(p, fat, s));
     else HH_CHECK_HIP(bb_fused_launch(p, num_cus, s));
     return 0;
@@ -1252,7 +1244,7 @@ int hh_net::forward(const float *images, int B, int H, int W, float *o1, float *
     // profiles/r03_ab.md) replays bit-equal but ~4 ms SLOWER per forward than the eager launches at every batch size (1.55 vs
     // 5.6 ms at batch 1): the runtime's graph executor costs ~15 us per node.  Graphs remain for single-lane execution
     // (hh_set_multi_lane(net, 0)), where eager and replay time alike.
-    if (!use_graph || s == nullptr || taps_enabled || prof_enabled || sw.poison_lds || sw.debug_skip || multi_lane)
+    if (!use_graph || s == nullptr || taps_enabled || prof_enabled || sw.poison_lds || multi_lane)
         return enqueue(images, B, H, W, o1, o2, s);
     for (auto &g : graphs)
         if (g.images == images && g.o1 == o1 && g.o2 == o2 && g.B == B && g.H == H && g.W == W) {

@@ -130,65 +130,47 @@ struct GraphEntry {
     hipGraphExec_t exec;
 };
 
-// Plan variants behind HH_* environment switches (A/B measurements, bit-equality tests).  hh_create / hh_create_classifier read
-// them ONCE (PlanSwitches::from_env) into the handle: nothing in the engine calls getenv afterwards, so a handle's plan and
-// launch choices cannot change under it when a later handle is built with other switches in the same process.
+// Plan variants behind HH_* environment switches.  Each one is here because a test needs it, named at the end of its comment:
+// a second implementation that a GPU test holds bit-equal or within tolerance to the default, or a poison pattern.  A switch that
+// no test sets does not belong here.  hh_create / hh_create_classifier read them ONCE (PlanSwitches::from_env) into the handle:
+// nothing in the engine calls getenv afterwards, so a handle's plan and launch choices cannot change under it when a later handle
+// is built with other switches in the same process.  test_multi_lane_schedule_has_no_unordered_hazard (CPU) walks the plans of
+// most of them; test_many_live_handles_interleaved_forwards_stay_bit_exact runs them side by side.
 struct PlanSwitches {
+    // second implementations
     bool bb32_tile = false;        // HH_BB32=tile: basicblock_fused.hip instead of the producer / consumer form
-    bool no_bb64 = false;          // HH_NO_BB64=1: 64-channel BasicBlocks layer by layer
-    bool no_bb_fp8 = false;        // HH_NO_BB_FP8=1: fp8 BasicBlocks layer by layer
-    bool no_stem_fused = false;    // HH_NO_STEM_FUSED=1: the stem as two launches
-    bool no_junc_pair = false;     // HH_NO_JUNC_PAIR=1: every stage-0 junction stores its 256-channel output
-    bool full_join = false;        // HH_FULL_JOIN=1: all-to-all joins of the branch lanes instead of per-source waits
-    bool no_fusion_merge = false;  // HH_NO_FUSION_MERGE=1: one launch per summed stride-2 conv of a fusion layer
+                                   // (test_fused_32_channel_block_both_forms, test_forward_does_not_depend_on_stale_lds)
+    bool no_bb64 = false;          // HH_NO_BB64=1: 64-channel BasicBlocks layer by layer (test_forward_does_not_depend_on_stale_lds)
+    bool no_stem_fused = false;    // HH_NO_STEM_FUSED=1: the stem as two launches (test_fused_stem_matches_two_launches)
+    bool no_junc_pair = false;     // HH_NO_JUNC_PAIR=1: every stage-0 junction stores its 256-channel output (test_schedule_and_fusion_switches)
+    bool full_join = false;        // HH_FULL_JOIN=1: all-to-all joins of the branch lanes instead of per-source waits (test_schedule_and_fusion_switches)
+    bool no_fusion_merge = false;  // HH_NO_FUSION_MERGE=1: one launch per summed stride-2 conv of a fusion layer (test_schedule_and_fusion_switches)
     bool no_fused_upsum = false;   // HH_NO_FUSED_UPSUM=1: output 0 of a fusion layer as one 1x1 launch per source + upadd_kernel
-                                   // (default, bf16 W32: one fusion_up.hip launch, bit-identical)
-    bool poison_ws = false;        // HH_POISON_WS=1 (tests): workspace filled with NaN patterns at allocation
-    // Persistent workgroups of the fused 32- / 64-channel blocks INSIDE an HR module (beside the other branches' lanes).  Default 0 =
-    // half the CUs each: the two fat kernels (150 KB of LDS per workgroup: a CU holds one of them and nothing else) then run side by
-    // side on disjoint halves of the chip instead of taking turns on all of it, and the thin launches of the 128- / 256-channel
-    // lanes find free CUs while either runs: forward 4.48 -> 4.39 ms, +1.5-2 % img/s (three alternations, profiles/r03_ab.md).
-    // HH_FAT_CUS=n[,m] sets them (256 = one per CU, the round-2 plan); a quarter of the chip for the 64-channel block loses 6 %.
-    int fat_cus = 0, fat_cus64 = 0;
+                                   // (default, bf16 W32: one fusion_up.hip launch, bit-identical) (test_fused_upsum_equals_the_launch_chain)
     bool event_system_fence = false;  // HH_EVENT_SYSTEM_FENCE=1: the lane events with the default system-scope fence at record time
-    bool keep_waits = false;       // HH_KEEP_WAITS=1: enqueue() issues every wait of the plan, also those it can prove redundant (A/B)
-    bool no_final_fuse = false;    // HH_NO_FINAL_FUSE=1: the deconv head's final 1x1 as its own launch (round 4: it runs in the last block's epilogue)
+                                   // (test_schedule_and_fusion_switches)
+    bool keep_waits = false;       // HH_KEEP_WAITS=1: enqueue() issues every wait of the plan, also those it can prove redundant
+                                   // (test_schedule_and_fusion_switches)
+    bool no_final_fuse = false;    // HH_NO_FINAL_FUSE=1: the deconv head's final 1x1 as its own launch (round 4: it runs in the last block's
+                                   // epilogue) (test_final_layer_in_the_last_block_epilogue)
     int bb_tall = 1;               // the fused 32-channel block tiles the batch as one tall image when that needs fewer tiles (round 4);
                                    // HH_NO_BB_TALL=1: per-image tiles (round 3), HH_BB_TALL=always: also where it needs more
+                                   // (test_tall_layout_vs_per_image_layout, test_schedule_and_fusion_switches)
     bool no_conv_db = false;       // HH_NO_CONV_DB=1: the 128- / 256-channel 3x3 convs on the single-buffer KC = 32 instantiations (round 2)
+                                   // (test_schedule_and_fusion_switches)
     bool no_head_fold = false;     // HH_NO_HEAD_FOLD=1: init_heatmaps_head writes its output into the concat buffer, the transposed conv reads it
-    bool poison_lds = false;       // HH_POISON_LDS=1 (tests): every CU's LDS filled with NaN patterns in front of every launch
-    unsigned debug_skip = 0;       // HH_DEBUG_SKIP=cat[,cat..] (measurement only, results are WRONG): launches of these categories are not
-                                   // issued -- how much of the forward's wall time hangs on a kernel family (tools/probes/skip_sensitivity.sh)
+                                   // (test_head_folded_into_the_transposed_conv)
     bool fp8_trunk8 = false;       // HH_FP8_TRUNK=e4m3: fp8 handles re-quantise the residual trunk to e4m3 in every block (the round-2 plan)
+                                   // (test_fp8_bf16_trunk_beats_the_all_e4m3_plan)
     bool fp8_heads8 = false;       // HH_FP8_HEADS=e4m3: the two 1x1 heads and the transposed conv of an fp8 handle on the e4m3 kernels too
+                                   // (test_fp8_bf16_trunk_beats_the_all_e4m3_plan)
+    // test-only poison patterns: no second implementation, the default plan on dirty memory
+    bool poison_ws = false;        // HH_POISON_WS=1: workspace filled with NaN patterns at allocation
+                                   // (test_forward_reads_no_unwritten_workspace, test_outputs_vs_oracle_within_budget)
+    bool poison_lds = false;       // HH_POISON_LDS=1: every CU's LDS filled with NaN patterns in front of every launch
+                                   // (test_forward_does_not_depend_on_stale_lds, test_fused_upsum_on_poisoned_memory)
     static PlanSwitches from_env();
 };
-
-enum SkipCat { SK_S2BIG = 1, SK_S2 = 2, SK_UPADD = 4, SK_C1X1 = 8, SK_C256 = 16, SK_C128 = 32, SK_JUNC = 64, SK_BB32 = 128, SK_BB64 = 256,
-               SK_STEM = 512, SK_DECONV = 1024, SK_HEAD = 2048, SK_TRANS0 = 4096, SK_UPSUM = 8192 };
-// the HH_DEBUG_SKIP categories of one op (0: none)
-inline unsigned hh_skip_cats(const Op &op, const std::vector<ConvLayer> &layers, const std::vector<TensorDesc> &tensors)
-{
-    switch (op.kind) {
-    case OP_UPADD: return SK_UPADD;
-    case OP_UPSUM: return SK_UPSUM;
-    case OP_JUNC: return SK_JUNC;
-    case OP_STEM: return SK_STEM;
-    case OP_BB: return layers[op.layer].cout == 32 ? SK_BB32 : layers[op.layer].cout == 64 ? SK_BB64 : 0;
-    case OP_CONV: break;
-    default: return 0;
-    }
-    const ConvLayer &l = layers[op.layer];
-    if (l.transposed) return SK_DECONV;
-    if (op.f32_out) return SK_HEAD;
-    if (l.stride == 2) return SK_S2 | (l.cin >= 128 ? SK_S2BIG : 0) | (l.cin == 256 && l.mconv.empty() && tensors[op.in].shift == 2 ? SK_TRANS0 : 0);
-    if (l.ks == 1) return SK_C1X1;
-    if (l.cin == 256 && l.cout == 256) return SK_C256;
-    if (l.cin == 128 && l.cout == 128) return SK_C128;
-    if (l.cin == 256 && tensors[op.in].shift == 2) return SK_TRANS0;
-    return 0;
-}
 
 // algorithmic cost of one launch: 2*MACs of the reference layers it computes; input + output (+ residual) + weights once, no halo re-reads
 struct OpCost { double flops = 0, bytes = 0; };

@@ -69,9 +69,7 @@ __global__ __launch_bounds__(256) void fusion_up_kernel(const FusionUpParams p)
     __shared__ __attribute__((aligned(16))) bf16_raw u2[(TH >> 2) * (TW >> 2) * CO];
     __shared__ __attribute__((aligned(16))) bf16_raw u3[(TH >> 3) * (TW >> 3) * CO];
     const int tid = threadIdx.x;
-#ifndef HH_NO_CLK
     if (p.clk && tid == 0 && blockIdx.x < 256) atomicMin(p.clk, wall_clock64());
-#endif
     int bid = blockIdx.x;
     const int tx = bid % p.tiles_x; bid /= p.tiles_x;
     const int ty = bid % p.tiles_y;
@@ -121,9 +119,7 @@ __global__ __launch_bounds__(256) void fusion_up_kernel(const FusionUpParams p)
             *reinterpret_cast<u32x4 *>(p.out + opix[i] * p.out_cs + c8 * 8) =  // (upadd_kernel's pack)
                 u32x4{round_bf16x2(v[0], v[1]), round_bf16x2(v[2], v[3]), round_bf16x2(v[4], v[5]), round_bf16x2(v[6], v[7])};
     });
-#ifndef HH_NO_CLK
     if (p.clk && tid == 0 && blockIdx.x + 256 >= gridDim.x) atomicMax(p.clk + 1, wall_clock64());
-#endif
 }
 
 bool fusion_up_supported(int C, int nsrc) { return C == CO && nsrc >= 1 && nsrc <= 3; }

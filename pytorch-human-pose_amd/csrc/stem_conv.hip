@@ -5,6 +5,11 @@
 // that staged 16-channel pixels of which 13 were padding (536 MB, 334 us); here the image is read once.
 // Mapping: K = 27 taps (c, ky, kx) padded to 32 = two 16-wide MFMA k-steps; each lane owns one output pixel and gathers
 // its taps from a bf16 LDS patch into the B-operand layout; A = the 64 x 32 weight matrix (BN scale folded) in registers.
+//
+// What keeps this file alive: bf16 handles run both stem convolutions in stem_fused.hip by default.  hh_net::enqueue_stem launches
+// this kernel for an OP_STEM without a second layer, which the builder makes in two cases: (1) fp8 handles, whose stem is this
+// kernel writing e4m3 (p.out_fp8) followed by a conv launch; (2) bf16 handles under HH_NO_STEM_FUSED=1 (PlanSwitches::no_stem_fused),
+// the two-launch form that test_fused_stem_matches_two_launches compares the fused stem with.
 #include "mfma_dev.h"
 
 namespace {
@@ -18,11 +23,9 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemParams p)
 {
     __shared__ unsigned short patch[NVAL + 1];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-#ifndef HH_NO_CLK
     // 8192 workgroups hammering one address would dominate this short kernel: only the first and the last 256 dispatched
     // workgroups stamp (dispatch order follows blockIdx closely enough for a start/end probe)
     if (p.clk && tid == 0 && blockIdx.x < 256) atomicMin(p.clk, wall_clock64());
-#endif
     const int Ho = p.H >> 1, Wo = p.W >> 1;
     const int tiles_x = (Wo + TW - 1) / TW, tiles_y = (Ho + TH - 1) / TH;
     int bid = blockIdx.x;
@@ -141,9 +144,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const StemParams p)
         for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
         if (lane == 0 && amax > 0.f) atomicMax(p.absmax, __float_as_uint(amax));
     }
-#ifndef HH_NO_CLK
     if (p.clk && tid == 0 && blockIdx.x + 256 >= gridDim.x) atomicMax(p.clk + 1, wall_clock64());
-#endif
 }
 
 hipError_t stem_conv_launch(const StemParams &p, hipStream_t s)

@@ -36,9 +36,7 @@ __global__ __launch_bounds__(256, 1) void stem_fused_kernel(const StemFusedParam
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned short *patch = reinterpret_cast<unsigned short *>(smem + OFF_PATCH);
     const int tid = threadIdx.x;
-#ifndef HH_NO_CLK
     if (p.clk && tid == 0) atomicMin(p.clk, wall_clock64());
-#endif
     const int lds0 = (int)(size_t)(__attribute__((address_space(3))) char *)smem;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, r = lane & 31, h = lane >> 5;
     const int H1 = p.H >> 1, W1 = p.W >> 1, H2 = p.H >> 2, W2 = p.W >> 2;
@@ -200,9 +198,7 @@ __global__ __launch_bounds__(256, 1) void stem_fused_kernel(const StemFusedParam
         }
         __syncthreads();  // the intermediate tile is free, the next patch is visible
     }
-#ifndef HH_NO_CLK
     if (p.clk && tid == 0) atomicMax(p.clk + 1, wall_clock64());
-#endif
 }
 
 hipError_t stem_fused_init()

@@ -77,8 +77,8 @@ class _BNFn(torch.autograd.Function):
             y, mean, invstd = ops.bn_train_forward(x, gamma, beta, eps, res, relu)
             ctx.count = x.shape[0] * x.shape[2] * x.shape[3]
         # without a residual input the backward needs nothing of y: the ReLU mask is recomputed from x (hh_bn_train_backward_plain);
-        # beta is saved instead (HH_TRAIN_BN_KEEP_Y=1: the stored-output form, for A/B)
-        ctx.plain = res is None and ctx.sync is None and not _KEEP_Y
+        # beta is saved instead
+        ctx.plain = res is None and ctx.sync is None
         ctx.save_for_backward(x, beta.detach() if ctx.plain else y, mean, invstd, gamma)
         ctx.relu, ctx.has_res = relu, res is not None
         stats.append((mean, invstd, ctx.count))
@@ -312,7 +312,6 @@ def deconv_k4s2(x: Tensor, m: nn.ConvTranspose2d) -> Tensor:
 
 # ------------------------------------------------------------------------------------------ the net
 _NO_RESBOX = bool(os.environ.get("HH_TRAIN_NO_RESBOX"))  # A/B: the skip gradients through autograd's own accumulation
-_KEEP_Y = bool(os.environ.get("HH_TRAIN_BN_KEEP_Y"))  # A/B: every BatchNorm backward reads its stored output
 
 
 def _boxable(x, c: nn.Conv2d) -> bool:
