@@ -262,6 +262,46 @@ int hh_heatmap_table_size(double sigma, int *n, int *reach);
 int hh_render_heatmaps(const int32_t *joints, const int32_t *num_people, int B, int P, int K, const float *table, int n, int reach,
                        float *out, int h, int w, void *stream);
 
+/* The classifier's input built on the device: classification/transforms.py:14-30 (ClassificationTransform.train: ToTensor ->
+ * RandomResizedCrop(224, antialias=True) -> RandomHorizontalFlip -> Normalize; .inference: ToTensor -> Resize(256, antialias=True) ->
+ * CenterCrop(224) -> Normalize) and classification/model.py:45-57 (InferenceClassificationModel: Resize + CenterCrop of input_size),
+ * batched, one launch.  Raw uint8 pixels and descriptors lie in ONE device buffer that the caller ships in one host->device copy.
+ * The random draws and the Resize / CenterCrop geometry stay on the host (classification/input.py).
+ *
+ * hh_crop_desc: one sample.  Image uint8 RGB [h,w,3] at batch_base + image_offset.  (top, left, ch, cw) is the source rectangle: the
+ *   whole image for Resize, the drawn crop for RandomResizedCrop.  That rectangle is resampled to a VIRTUAL image of rh x rw, of
+ *   which only the H x W window at (oy, ox) is computed (CenterCrop; the whole of it when rh x rw = H x W).  flip != 0 reverses the
+ *   window's columns.  For sample b, channel c and output pixel (y, x), with xs = flip ? W-1-x : x:
+ *     out[b,c,y,x] = (resample(crop_b(ToTensor(image_b)))[c, oy + y, ox + xs] - mean[c]) / stdv[c]
+ * resample is torch's upsample_bilinear2d_aa with align_corners = False (what torchvision's tensor resize / resized_crop run),
+ *   separable, the horizontal pass first, its result kept as fp32.  Per axis, with in = crop extent, out = virtual size,
+ *   scale = in / out and support = antialias ? max(scale, 1) : 1: centre = scale (i + 0.5); taps
+ *   j in [max(0, int(centre - support + 0.5)), min(in, int(centre + support + 0.5))); weight max(0, 1 - |(j - centre + 0.5) / support|),
+ *   normalised to sum 1.  There is no cap on the tap count.  Tap indices are relative to the crop and never leave it (pixels of the
+ *   image outside the rectangle do not contribute, as for a tensor that was cropped first).  antialias = 0 is
+ *   F.interpolate(mode="bilinear", antialias=False): torchvision's T.Resize default changed between versions, so the caller says.
+ * Arithmetic: all fp32; ToTensor is the division v / 255.0f, Normalize a subtraction then a division (no reciprocal), products and
+ *   sums rounded separately, the taps summed in ascending order.  A crop whose extent equals the virtual size on both axes gives
+ *   Normalize(ToTensor(.)) of the source pixels bit for bit.  Deterministic; every output element is written exactly once.
+ * Validation: `descs_dev` is the DEVICE array the kernel reads; `descs_host` is the caller's HOST copy of the same n descriptors, and
+ *   it is what is checked (device memory is never read back).  Returns 1 with hh_last_error set, before any launch, for a null
+ *   pointer, a non-positive extent, a rectangle outside its image, a window outside rh x rw, a negative offset, an image of
+ *   h * w * 3 >= 2^31 bytes (the kernel indexes one image's bytes with 32 bits), a side beyond 2^23 (tap positions are formed in
+ *   fp32), n outside 1..65535, H or W outside 1..32768.  That the image bytes lie inside the caller's buffer cannot be checked here.
+ * (Additive entry point: HH_ABI_VERSION stays 3.)                                                                          */
+#define HH_CROP_MAX_SIDE (1 << 23)
+#define HH_CROP_MAX_EXTENT 32768
+typedef struct hh_crop_desc {
+    long long image_offset;      /* bytes from batch_base: uint8 RGB [h,w,3] */
+    int h, w;                    /* raw image */
+    int top, left, ch, cw;       /* source rectangle (the crop), inside the image */
+    int rh, rw;                  /* size of the virtual resized crop */
+    int oy, ox;                  /* origin of the H x W output window inside it */
+    int flip, antialias;
+} hh_crop_desc;
+int hh_resized_crop_u8_batch(const unsigned char *batch_base, const hh_crop_desc *descs_dev, const hh_crop_desc *descs_host, int n,
+                             float *out_nchw, int H, int W, const float mean[3], const float stdv[3], void *stream);
+
 /* Building blocks of the training step (keypoints/module.py:43-71), assembled into the net's training forward / backward
  * by keypoints/train_net.py with torch autograd as the tape.  Activations are NHWC bf16 [B,H,W,C] (= torch channels_last),
  * parameters fp32, all device pointers.

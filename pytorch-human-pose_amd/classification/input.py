@@ -1,0 +1,220 @@
+"""The classifier's input built on the device: random / centre crops of raw uint8 images, antialiased resize, flip, normalisation.
+
+Stands in for what the reference's dataset worker does per image on the host with torchvision
+(`src/classification/transforms.py:14-30` ClassificationTransform: `.train` = ToTensor -> RandomResizedCrop(224, antialias=True) ->
+RandomHorizontalFlip -> Normalize, `.inference` = ToTensor -> Resize(int(224 / 0.875), antialias=True) -> CenterCrop(224) ->
+Normalize) and for the transform of `src/classification/model.py:45-57`.  The split:
+  * host: the random draws (torch's global RNG, torchvision's published procedure) and the Resize / CenterCrop geometry: ten integers
+    per sample;
+  * device: crop, separable triangle-filter resample (torch's upsample_bilinear2d_aa, align_corners=False), window, flip, ToTensor
+    and Normalize in ONE launch per batch (hh_resized_crop_u8_batch, csrc/cls_input.hip).
+The raw pixels of every sample's source rectangle (the crop; not the image around it), the descriptors and the targets cross in ONE
+host->device copy from a pinned, double-buffered staging area.  The result is what `ClassificationModule.training_step` /
+`validation_step` take: (images [B,3,S,S] fp32, targets int64), on the device.
+There is no CPU path.
+
+UNPINNED: torchvision is not installed where this project is built and tested, so (a) the ORDER and kind of the random draws of
+`random_resized_crop_params` follow torchvision's published `RandomResizedCrop.get_params` / `RandomHorizontalFlip.forward` but
+have not been compared with a torchvision run under equal seeds, and (b) whether `T.Resize(size)` without an `antialias` argument
+antialiases a tensor depends on the torchvision version (it did not before 0.17), which is why the flag travels in the descriptor
+and `InferenceClassificationModel` takes it as an argument.  The deterministic part -- `build` from explicit parameters -- is pinned
+against torch's own F.interpolate and a float64 restatement (tests/cls_input_budget.py).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from dataclasses import dataclass
+
+import numpy as np
+
+from .. import _lib
+from ..keypoints.transforms_utils import IMAGENET_MEAN, IMAGENET_STD
+
+# hh_crop_desc of include/hhrnet.h (56 bytes)
+_CROP_DESC = np.dtype([("image_offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("top", "<i4"), ("left", "<i4"), ("ch", "<i4"), ("cw", "<i4"),
+                       ("rh", "<i4"), ("rw", "<i4"), ("oy", "<i4"), ("ox", "<i4"), ("flip", "<i4"), ("antialias", "<i4")])
+assert _CROP_DESC.itemsize == 56
+
+
+@dataclass
+class CropParams:
+    """One sample's augmentation: the crop rectangle in raw-image pixels (it is resized to the whole output) and the flip."""
+    top: int
+    left: int
+    height: int
+    width: int
+    flip: bool = False
+
+
+@dataclass
+class CropWindow:
+    """The general form of one sample (every field of hh_crop_desc but the image's own): the source rectangle, the size of the
+    virtual resized crop, the origin of the output window inside it, flip and antialias."""
+    top: int
+    left: int
+    height: int
+    width: int
+    rh: int
+    rw: int
+    oy: int = 0
+    ox: int = 0
+    flip: bool = False
+    antialias: bool = True
+
+
+def random_resized_crop_params(height: int, width: int, scale=(0.08, 1.0), ratio=(3 / 4, 4 / 3), flip_p: float | None = 0.5) -> CropParams:
+    """torchvision's RandomResizedCrop.get_params then RandomHorizontalFlip, from torch's global RNG: up to 10 attempts, each drawing
+    the area uniformly in `scale` (of the image's area) and the aspect ratio log-uniformly in `ratio`, rounding to an integer size and,
+    if that fits the image, drawing the offsets with randint; if none fits, the central crop with the image's ratio clamped to
+    `ratio`.  The flip is `torch.rand(1) < flip_p`, drawn after the crop (flip_p None: no draw).  Draw order UNPINNED against a
+    torchvision run (see the module docstring)."""
+    import torch
+    area = height * width
+    log_lo, log_hi = math.log(ratio[0]), math.log(ratio[1])
+    rect = None
+    for _ in range(10):
+        target_area = area * torch.empty(1).uniform_(scale[0], scale[1]).item()
+        aspect = math.exp(torch.empty(1).uniform_(log_lo, log_hi).item())
+        w = int(round(math.sqrt(target_area * aspect)))
+        h = int(round(math.sqrt(target_area / aspect)))
+        if 0 < w <= width and 0 < h <= height:
+            top = int(torch.randint(0, height - h + 1, size=(1,)).item())
+            left = int(torch.randint(0, width - w + 1, size=(1,)).item())
+            rect = (top, left, h, w)
+            break
+    if rect is None:
+        rect = central_crop_fallback(height, width, ratio)
+    flip = flip_p is not None and bool(torch.rand(1).item() < flip_p)
+    return CropParams(*rect, flip)
+
+
+def central_crop_fallback(height: int, width: int, ratio=(3 / 4, 4 / 3)) -> tuple:
+    """The crop RandomResizedCrop falls back to: the whole image where its width / height lies within `ratio`, else the central part
+    with the ratio clamped -> (top, left, h, w)."""
+    in_ratio = float(width) / float(height)
+    if in_ratio < min(ratio):
+        w = width
+        h = int(round(w / min(ratio)))
+    elif in_ratio > max(ratio):
+        h = height
+        w = int(round(h * max(ratio)))
+    else:
+        w, h = width, height
+    return (height - h) // 2, (width - w) // 2, h, w
+
+
+def inference_geometry(height: int, width: int, resize: int = 256, crop: int = 224) -> tuple:
+    """Resize(resize) + CenterCrop(crop) of an image of height x width -> (rh, rw, oy, ox): the short side goes to `resize`, the long
+    side to int(resize * long / short); the crop x crop window starts at int(round((r - crop) / 2.0)) on each axis."""
+    short, long = (width, height) if width <= height else (height, width)
+    new_short, new_long = resize, int(resize * long / short)
+    rw, rh = (new_short, new_long) if width <= height else (new_long, new_short)
+    return rh, rw, int(round((rh - crop) / 2.0)), int(round((rw - crop) / 2.0))
+
+
+class ClsInput:
+    """The reference's `ClassificationTransform(out_size, mean, std)` (classification/transforms.py:6-31) on batches.
+
+        ci = ClsInput(224)
+        batch = ci.train(samples)          # samples: [(uint8 HWC image, int target), ...]
+        module.training_step(batch)
+
+    `.train(samples)` draws a RandomResizedCrop + flip per sample, `.inference(samples)` takes Resize(int(out_size / resize_ratio)) +
+    CenterCrop(out_size); both call `build(samples, params)`, the explicit entry, whose params are per sample a CropParams, an
+    `inference_geometry` tuple (rh, rw, oy, ox) or a CropWindow."""
+
+    def __init__(self, out_size: int = 224, mean=IMAGENET_MEAN, std=IMAGENET_STD, resize_ratio: float = 0.875, device="cuda:0",
+                 antialias: bool = True):
+        self.out_size, self.device, self.antialias = int(out_size), device, bool(antialias)
+        self.resize = int(out_size / resize_ratio)  # transforms.py:26
+        self.mean, self.std = np.asarray(mean, np.float32), np.asarray(std, np.float32)
+        self._stage = [None, None]       # pinned staging buffers ...
+        self._stage_free = [None, None]  # ... and the event behind the copy that last read each
+        self._turn = 0
+        self.last_h2d_bytes = self.last_launches = 0  # of the last build(): what tools/cls_input_time.py reports
+
+    def train(self, samples):
+        return self.build(samples, [random_resized_crop_params(*np.asarray(s[0]).shape[:2]) for s in samples])
+
+    def inference(self, samples):
+        return self.build(samples, [inference_geometry(*np.asarray(s[0]).shape[:2], resize=self.resize, crop=self.out_size) for s in samples])
+
+    def window(self, height: int, width: int, p) -> CropWindow:
+        """One sample's parameters in the general form."""
+        S = self.out_size
+        if isinstance(p, CropWindow):
+            return p
+        if isinstance(p, CropParams):  # the crop becomes the whole output
+            return CropWindow(p.top, p.left, p.height, p.width, S, S, 0, 0, p.flip, self.antialias)
+        rh, rw, oy, ox = p             # the whole image resized, a window of it
+        return CropWindow(0, 0, height, width, rh, rw, oy, ox, False, self.antialias)
+
+    def _staging(self, total: int):
+        import torch
+        t = self._turn
+        self._turn ^= 1
+        if self._stage[t] is None or self._stage[t].numel() < total:
+            # (a larger buffer replaces the old one; the old one stays alive until its copy has run: torch keeps pinned blocks
+            # that a non_blocking copy still reads)
+            self._stage[t] = torch.empty(total, dtype=torch.uint8).pin_memory()
+        elif self._stage_free[t] is not None:
+            self._stage_free[t].synchronize()  # the copy that last read this buffer has finished
+        return t, self._stage[t]
+
+    @staticmethod
+    def layout(shapes) -> tuple:
+        """Byte layout of the one buffer that crosses, from the (height, width) of every sample's source rectangle (only the crop is
+        shipped, not the image around it): the pixels back to back, then (64-byte aligned) the descriptors, then the int64
+        targets -> (image offsets, descriptor offset, target offset, total)."""
+        offs = np.cumsum([0] + [h * w * 3 for h, w in shapes])
+        desc_off = (int(offs[-1]) + 63) // 64 * 64
+        target_off = desc_off + _CROP_DESC.itemsize * len(shapes)  # 56 B descriptors: a multiple of 8
+        return offs, desc_off, target_off, target_off + 8 * len(shapes)
+
+    def build(self, samples, params):
+        """samples: [(uint8 [h,w,3] image, int target)], params: one CropParams / (rh, rw, oy, ox) / CropWindow per sample ->
+        (images [B,3,S,S] fp32, targets [B] int64) on the device, in the current stream."""
+        import torch
+        lib = _lib.load()
+        B, S = len(samples), self.out_size
+        if B == 0 or len(params) != B:
+            raise ValueError("ClsInput.build: one parameter set per sample, at least one sample")
+        windows = []
+        for b, ((img, _), p) in enumerate(zip(samples, params)):
+            if not isinstance(img, np.ndarray) or img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
+                raise ValueError("ClsInput.build: uint8 [h,w,3] images only")
+            q = self.window(img.shape[0], img.shape[1], p)
+            # only the source rectangle is staged and shipped (a slice would silently clip a rectangle that leaves the image)
+            if q.height <= 0 or q.width <= 0 or q.top < 0 or q.left < 0 or q.top + q.height > img.shape[0] or q.left + q.width > img.shape[1]:
+                raise _lib.HHError(f"ClsInput.build: sample {b}: crop rectangle outside its image (or empty)")
+            windows.append(q)
+        shapes = [(q.height, q.width) for q in windows]
+        offs, desc_off, target_off, total = self.layout(shapes)
+        turn, host = self._staging(total)
+        hview = host.numpy()
+        descs = hview[desc_off:target_off].view(_CROP_DESC)
+        targets_host = hview[target_off:total].view(np.int64)
+        for b, ((img, target), q) in enumerate(zip(samples, windows)):
+            h, w = shapes[b]
+            np.copyto(hview[offs[b]:offs[b + 1]].reshape(h, w, 3), img[q.top:q.top + h, q.left:q.left + w])
+            # the shipped image IS the crop: tap indices are relative to the crop and never leave it, so nothing else is read
+            descs[b] = (int(offs[b]), h, w, 0, 0, h, w, q.rh, q.rw, q.oy, q.ox, int(bool(q.flip)), int(bool(q.antialias)))
+            targets_host[b] = int(target)
+
+        dev = torch.device(self.device)
+        with torch.cuda.device(dev):
+            cur = torch.cuda.current_stream(dev)
+            raw = host[:total].to(dev, non_blocking=True)
+            copied = torch.cuda.Event()
+            copied.record(cur)
+            self._stage_free[turn] = copied
+            self.last_h2d_bytes, self.last_launches = total, 1
+            images = torch.empty((B, 3, S, S), device=dev, dtype=torch.float32)
+            fp = C.POINTER(C.c_float)
+            base = raw.data_ptr()
+            # the descriptors are checked on their HOST copy in the staging buffer (nothing is read back from the device)
+            _lib.check(lib.hh_resized_crop_u8_batch(base, base + desc_off, descs.ctypes.data, B, images.data_ptr(), S, S,
+                                                    self.mean.ctypes.data_as(fp), self.std.ctypes.data_as(fp), cur.cuda_stream))
+            targets = raw[target_off:total].view(torch.int64)
+        return images, targets

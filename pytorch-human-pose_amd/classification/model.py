@@ -1,10 +1,16 @@
-"""Trainer-facing model wrapper of the classifier: stands in for `src/classification/model.py:12-31` (`ClassificationModel`).
+"""Model wrappers of the classifier: the trainer-facing `ClassificationModel` (`src/classification/model.py:12-31`) and the
+`InferenceClassificationModel` of `src/classification/model.py:34-72`.
 Device placement, DistributedDataParallel / SyncBatchNorm, checkpoints and the example input are keypoints/model.py's BaseModel."""
 from __future__ import annotations
 
+from dataclasses import dataclass
+
+import numpy as np
+import torch
 from torch import nn
 
-from ..keypoints.model import BaseModel
+from ..keypoints.model import BaseModel, parse_checkpoint
+from .input import ClsInput, inference_geometry
 
 
 class ClassificationModel(BaseModel):
@@ -24,3 +30,75 @@ class ClassificationModel(BaseModel):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
         net.mark_dirty()
+
+
+@dataclass
+class InferenceClassificationResult:
+    """classification/results.py:39-68 without the plot: one image's logits, their softmax, the prediction (the arg-max, the lower
+    index on a tie, as `ClassificationResult` has it), its label and the target label."""
+    raw_image: np.ndarray
+    logits: np.ndarray
+    probs: np.ndarray
+    prediction: int
+    pred_label: int | str
+    target_label: int | str | None = None
+
+
+class InferenceClassificationModel:
+    """`InferenceClassificationModel(net, idx2label, input_size, device, ckpt_path)` of classification/model.py:34-72.  Its transform
+    is ToTensor -> Resize(input_size) -> CenterCrop(input_size) -> Normalize; here one hh_resized_crop_u8_batch launch per batch of
+    raw images.  `antialias`: torchvision's `T.Resize` default for tensors changed between versions (off before 0.17, on since),
+    and the reference does not pass it, so it is an argument here (default: the current torchvision's behaviour)."""
+
+    def __init__(self, net: nn.Module, idx2label: dict, input_size: int = 256, device: str = "cuda:0", ckpt_path: str | None = None,
+                 antialias: bool = True):
+        self.net = net.to(device)
+        self.net.eval()
+        self.device, self.input_size, self.idx2label = device, input_size, idx2label
+        self._input = ClsInput(input_size, device=device, antialias=antialias)
+        if ckpt_path is not None:
+            self.load_checkpoint(ckpt_path)
+
+    def load_checkpoint(self, ckpt_path: str) -> None:
+        """base/model.py:167-175: a trainer checkpoint keeps the weights under ["module"]["model"]; a bare state dict is loaded as
+        it is."""
+        ckpt = torch.load(ckpt_path, map_location="cpu")
+        if "module" in ckpt.keys():
+            ckpt = ckpt["module"]["model"]
+        self.net.load_state_dict(parse_checkpoint(ckpt))
+
+    def prepare_inputs(self, images: list) -> torch.Tensor:
+        """[uint8 HWC image] -> [B,3,input_size,input_size] on the device: Resize(input_size) + CenterCrop(input_size) + Normalize."""
+        size = self.input_size
+        geometry = [inference_geometry(im.shape[0], im.shape[1], resize=size, crop=size) for im in images]
+        return self._input.build([(im, 0) for im in images], geometry)[0]
+
+    def prepare_input(self, image: np.ndarray) -> torch.Tensor:
+        """model.py:54-57 -> [1,3,input_size,input_size]."""
+        return self.prepare_inputs([image])
+
+    def _records(self, images: list, logits: torch.Tensor, target_labels) -> list:
+        lg = logits.cpu().numpy()
+        out = []
+        for i, im in enumerate(images):
+            e = np.exp(lg[i] - lg[i].max())
+            pred = int(np.argmax(lg[i]))  # the first maximum: the lower index on a tie
+            out.append(InferenceClassificationResult(im, lg[i], e / e.sum(), pred, self.idx2label[pred],
+                                                     None if target_labels is None else target_labels[i]))
+        return out
+
+    def infer_images(self, raw_images: list, target_labels: list | None = None, max_batch: int = 32) -> list:
+        """One record per image, in order, from batches of up to `max_batch` images of any sizes (one input launch + one engine
+        forward per batch): what `__call__` returns for each."""
+        if target_labels is not None and len(target_labels) != len(raw_images):
+            raise ValueError("infer_images: one target label per image")
+        out = []
+        for i in range(0, len(raw_images), max_batch):
+            chunk = raw_images[i:i + max_batch]
+            with torch.no_grad():
+                logits = self.net(self.prepare_inputs(chunk))
+            out += self._records(chunk, logits, None if target_labels is None else target_labels[i:i + max_batch])
+        return out
+
+    def __call__(self, raw_image: np.ndarray, target_label: int | str | None = None) -> InferenceClassificationResult:
+        return self.infer_images([raw_image], [target_label])[0]

@@ -1,5 +1,6 @@
 // extern "C" surface declared in include/hhrnet.h (network part).
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -223,6 +224,33 @@ int hh_train_masks_u8_batch(const unsigned char *batch_base, const hh_train_desc
     }
     if (total > (1 << 30)) { hh_set_error("hh_train_masks_u8_batch: the stages' pixel count exceeds 2^30"); return 1; }
     HH_CHECK_HIP(launch_train_masks(batch_base, reinterpret_cast<const HHTrainDesc *>(descs_dev), n, st, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_resized_crop_u8_batch(const unsigned char *batch_base, const hh_crop_desc *descs_dev, const hh_crop_desc *descs_host, int n, float *out_nchw,
+                             int H, int W, const float mean[3], const float stdv[3], void *stream)
+{
+    static_assert(sizeof(hh_crop_desc) == sizeof(HHCropDesc) && sizeof(HHCropDesc) == 56, "descriptor layout");
+    const char *fn = "hh_resized_crop_u8_batch";
+    if (!batch_base || !descs_dev || !descs_host || !out_nchw || !mean || !stdv) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if (n <= 0 || n > 65535 || H <= 0 || W <= 0 || H > HH_CROP_MAX_EXTENT || W > HH_CROP_MAX_EXTENT || (int64_t)H * W > (1 << 30)) {
+        hh_set_error(std::string(fn) + ": need 0 < n <= 65535, 0 < H, W <= 32768 and H * W <= 2^30");
+        return 1;
+    }
+    for (int c = 0; c < 3; ++c)
+        if (!(stdv[c] != 0.f)) { hh_set_error(std::string(fn) + ": std must not be zero"); return 1; }
+    for (int b = 0; b < n; ++b) {
+        const hh_crop_desc &d = descs_host[b];
+        const std::string who = std::string(fn) + ": sample " + std::to_string(b) + ": ";
+        if (d.h <= 0 || d.w <= 0 || d.ch <= 0 || d.cw <= 0 || d.rh <= 0 || d.rw <= 0) { hh_set_error(who + "non-positive extent (image, crop or virtual size)"); return 1; }
+        if (d.image_offset < 0) { hh_set_error(who + "negative image offset"); return 1; }
+        // the kernel indexes the bytes of one image with 32-bit integers and forms tap positions in fp32
+        if ((int64_t)d.h * d.w * 3 > INT32_MAX) { hh_set_error(who + "image beyond 32-bit byte indexing (h * w * 3 >= 2^31)"); return 1; }
+        if (d.h > HH_CROP_MAX_SIDE || d.w > HH_CROP_MAX_SIDE || d.rh > HH_CROP_MAX_SIDE || d.rw > HH_CROP_MAX_SIDE) { hh_set_error(who + "a side exceeds 2^23 pixels"); return 1; }
+        if (d.top < 0 || d.left < 0 || (int64_t)d.top + d.ch > d.h || (int64_t)d.left + d.cw > d.w) { hh_set_error(who + "crop rectangle outside its image"); return 1; }
+        if (d.oy < 0 || d.ox < 0 || (int64_t)d.oy + H > d.rh || (int64_t)d.ox + W > d.rw) { hh_set_error(who + "output window outside the virtual resized crop"); return 1; }
+    }
+    HH_CHECK_HIP(launch_resized_crop(batch_base, reinterpret_cast<const HHCropDesc *>(descs_dev), n, out_nchw, H, W, mean, stdv, (hipStream_t)stream));
     return 0;
 }
 

@@ -340,6 +340,14 @@ struct TrainMaskStages { float *out[HH_TRAIN_STAGES]; int h[HH_TRAIN_STAGES], w[
 hipError_t launch_train_images(const unsigned char *base, const HHTrainDesc *descs, int n, float *out, int H, int W, const float mean[3],
                                const float stdv[3], hipStream_t s);
 hipError_t launch_train_masks(const unsigned char *base, const HHTrainDesc *descs, int n, const TrainMaskStages &st, hipStream_t s);
+// The classifier's input (hh_crop_desc of include/hhrnet.h, cls_input.hip): one sample's raw image, its source rectangle, the size of
+// the virtual resized crop and the output window inside it.  56 bytes.
+struct HHCropDesc {
+    long long image_offset;  // bytes from the batch's base pointer
+    int h, w, top, left, ch, cw, rh, rw, oy, ox, flip, antialias;
+};
+hipError_t launch_resized_crop(const unsigned char *base, const HHCropDesc *descs, int n, float *out, int H, int W, const float mean[3],
+                               const float stdv[3], hipStream_t s);
 // target heatmaps from the packed joints (train_input.hip); n = table side = 2 * reach + 1 <= HH_RENDER_MAX_N, w <= HH_RENDER_MAX_W
 #define HH_RENDER_MAX_N 63
 #define HH_RENDER_MAX_W 4096
