@@ -11,7 +11,8 @@ bf16 (the default; no loss scaling needed) or fp16, the reference's own (it trai
 from the net, every op returns the type it was given, and the fp32 gradients the loss hands back are cast to it by autograd where
 they enter the last convolutions (the backward of the `.float()` at the end of the forward) -- in fp16 that is where an oversized
 loss scale first turns into inf.  Parameters and their gradients are fp32, so torch optimizers, GradScaler and
-DistributedDataParallel (gradient all-reduce over RCCL) work on the module unchanged.
+DistributedDataParallel (gradient all-reduce over RCCL) work on the module unchanged.  What a forward carries from layer to layer
+(packed weights, SyncBatchNorm group, pending running statistics) is one `TrainForward`; the module itself holds no state.
 """
 from __future__ import annotations
 
@@ -68,17 +69,17 @@ class _ConvFn(torch.autograd.Function):
 
 class _BNFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x: Tensor, gamma: Tensor, beta: Tensor, res, relu: bool, eps: float, stats: list, box=None):
+    def forward(ctx, x: Tensor, gamma: Tensor, beta: Tensor, res, relu: bool, eps: float, stats: list, box=None, sync=None):
         ctx.box = box  # not None: the residual's gradient goes into the box (for the unit's first conv), not back through autograd
-        ctx.sync = _sync_world()
-        if ctx.sync is not None:  # SyncBatchNorm: statistics over every rank's pixels
-            y, mean, invstd, ctx.count = ops.sync_bn_train_forward(x, gamma, beta, eps, res, relu, *ctx.sync)
+        ctx.sync = sync  # TrainForward.sync
+        if sync is not None:  # SyncBatchNorm: statistics over every rank's pixels
+            y, mean, invstd, ctx.count = ops.sync_bn_train_forward(x, gamma, beta, eps, res, relu, *sync)
         else:
             y, mean, invstd = ops.bn_train_forward(x, gamma, beta, eps, res, relu)
             ctx.count = x.shape[0] * x.shape[2] * x.shape[3]
         # without a residual input the backward needs nothing of y: the ReLU mask is recomputed from x (hh_bn_train_backward_plain);
         # beta is saved instead
-        ctx.plain = res is None and ctx.sync is None
+        ctx.plain = res is None and sync is None
         ctx.save_for_backward(x, beta.detach() if ctx.plain else y, mean, invstd, gamma)
         ctx.relu, ctx.has_res = relu, res is not None
         stats.append((mean, invstd, ctx.count))
@@ -87,23 +88,18 @@ class _BNFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy: Tensor):
         x, y, mean, invstd, gamma = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last)
         if ctx.sync is not None:
-            dx, dgamma, dbeta, dres = ops.sync_bn_train_backward(x, y, dy.contiguous(memory_format=torch.channels_last), mean, invstd,
-                                                                 gamma, ctx.relu, ctx.has_res, ctx.sync[0], ctx.count)
-            if ctx.box is not None:
-                _box_put(ctx.box, dres)
-                dres = None
-            return dx, dgamma, dbeta, dres, None, None, None, None
-        if ctx.plain:  # (y holds beta)
-            dx, dgamma, dbeta, dres = ops.bn_train_backward(x, None, dy.contiguous(memory_format=torch.channels_last), mean, invstd, gamma,
-                                                            ctx.relu, beta=y)
+            grads = ops.sync_bn_train_backward(x, y, dy, mean, invstd, gamma, ctx.relu, ctx.has_res, ctx.sync[0], ctx.count)
+        elif ctx.plain:  # (y holds beta)
+            grads = ops.bn_train_backward(x, None, dy, mean, invstd, gamma, ctx.relu, beta=y)
         else:
-            dx, dgamma, dbeta, dres = ops.bn_train_backward(x, y, dy.contiguous(memory_format=torch.channels_last), mean, invstd, gamma,
-                                                            ctx.relu, want_dres=ctx.has_res)
+            grads = ops.bn_train_backward(x, y, dy, mean, invstd, gamma, ctx.relu, want_dres=ctx.has_res)
+        dx, dgamma, dbeta, dres = grads
         if ctx.box is not None:
             _box_put(ctx.box, dres)
             dres = None
-        return dx, dgamma, dbeta, dres, None, None, None, None
+        return dx, dgamma, dbeta, dres, None, None, None, None, None
 
 
 class _FusionSumFn(torch.autograd.Function):
@@ -127,85 +123,6 @@ def _pad_c(n: int, m: int) -> int:
     return (n + m - 1) // m * m
 
 
-def conv(x: Tensor, m: nn.Conv2d, stride: int | None = None, box: _ResBox | None = None, bias: bool = True) -> Tensor:
-    """nn.Conv2d forward on the HIP kernels.  Channel counts the kernels cannot take (3, 17, 34, 66 ...) are zero padded:
-    padding and slicing are differentiable torch ops, so the gradients reach the unpadded parameter.  bias=False leaves the
-    module's bias out (conv_bias_bn adds it where it matters)."""
-    w = m.weight
-    cout, cin, ks, _ = w.shape
-    stride = m.stride[0] if stride is None else stride
-    cin_p, cout_p = _pad_c(cin, 16), _pad_c(cout, 16)  # the data gradient runs the conv with the roles swapped
-    if cin_p != cin or cout_p != cout:
-        w = F.pad(w, (0, 0, 0, 0, 0, cin_p - cin, 0, cout_p - cout))
-    if x.shape[1] != cin_p:
-        x = F.pad(x, (0, 0, 0, 0, 0, cin_p - x.shape[1]))
-    pk = _PACKED[0].get((id(m.weight), stride)) if (_PACKED[0] is not None and w is m.weight) else None
-    if box is not None and (cin_p != cin or x.shape[1] != cin):
-        raise ValueError("conv: a skip-gradient box needs an unpadded input")
-    y = _ConvFn.apply(x.contiguous(memory_format=torch.channels_last), w, stride, None, *(pk if pk is not None else (None, None)), box)
-    if cout_p != cout:
-        y = y[:, :cout]
-    if m.bias is not None and bias:
-        y = y + m.bias.view(1, -1, 1, 1).to(y.dtype)
-    return y
-
-
-_PACKED: list = [None]  # {(id(weight), stride): (forward-packed, data-gradient-packed)} of the forward in flight (_refresh_packed)
-
-
-def _refresh_packed(net, act) -> None:
-    """Pack the weights of every conv whose channel counts the kernels take unpadded - forward layout and data-gradient
-    layout - in ONE launch per step (ops.PackedConvWeights) instead of one launch per conv call.  The copies are read by this
-    forward and the backward that follows it; they go stale with the optimizer step and are refreshed by the next forward."""
-    cache = getattr(net, "_train_packed", None)
-    if cache is None or not cache[0].pointers_current() or cache[0].dtype != act:
-        entries, index = [], {}
-        for m in net.modules():
-            if isinstance(m, nn.Conv2d) and m.weight.is_cuda and m.weight.dtype == torch.float32:
-                cout, cin, ks, _ = m.weight.shape
-                stride = m.stride[0]
-                if cin % 16 or cout % 16 or (id(m.weight), stride) in index:
-                    continue
-                index[(id(m.weight), stride)] = (len(entries), len(entries) + 1)
-                entries += [(m.weight, stride, False), (m.weight, stride, True)]
-        pw = ops.PackedConvWeights(entries, act)
-        cache = (pw, {k: (pw.buffers[a], pw.buffers[b]) for k, (a, b) in index.items()})
-        net._train_packed = cache
-    cache[0].refresh()
-    _PACKED[0] = cache[1]
-
-
-_SYNC: list = [None]  # process group of the forward in flight when the net was converted to SyncBatchNorm (else None)
-
-
-def _sync_world():
-    """(group, world_size) when BatchNorm statistics are shared across ranks: like torch's SyncBatchNorm, only if a process
-    group with more than one rank exists; otherwise None (plain BatchNorm)."""
-    import torch.distributed as dist
-    if _SYNC[0] is None or not (dist.is_available() and dist.is_initialized()):
-        return None
-    group = None if _SYNC[0] is True else _SYNC[0]
-    world = dist.get_world_size(group)
-    return (group, world) if world > 1 else None
-
-
-_PENDING_STATS: list = []  # (module, batch mean, batch invstd, pixels) of the forward in flight, applied by flush_running_stats
-
-
-def bn(x: Tensor, m: nn.BatchNorm2d, relu: bool = False, res: Tensor | None = None, box: _ResBox | None = None,
-       mean_shift: Tensor | None = None) -> Tensor:
-    """nn.BatchNorm2d in training mode (+ residual, + ReLU); the running statistics are updated like torch updates them,
-    once per forward for all layers together (flush_running_stats).  mean_shift [C]: a per-channel constant that the layer's input
-    carries in the reference but x does not (conv_bias_bn); it is added to the batch mean that feeds running_mean."""
-    stats: list = []
-    y = _BNFn.apply(x.contiguous(memory_format=torch.channels_last), m.weight, m.bias,
-                    res.contiguous(memory_format=torch.channels_last) if res is not None else None, relu, m.eps, stats, box)
-    if m.track_running_stats and m.running_mean is not None:
-        mean = stats[0][0] if mean_shift is None else stats[0][0] + mean_shift.detach().float()
-        _PENDING_STATS.append((m, mean, stats[0][1], stats[0][2]))  # count = pixels of all ranks under SyncBatchNorm
-    return y
-
-
 class _SilentBiasFn(torch.autograd.Function):
     """A conv bias in front of a train-mode BatchNorm: y = BN(conv(x) + b) does not depend on b (the batch mean takes it out again), so
     the forward leaves x as it is and the backward hands b its true gradient, zero -- the parameter still takes part in the graph, as
@@ -219,16 +136,6 @@ class _SilentBiasFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy: Tensor):
         return dy, torch.zeros(ctx.n, device=dy.device, dtype=torch.float32)
-
-
-def conv_bias_bn(x: Tensor, c: nn.Conv2d, b: nn.BatchNorm2d, relu: bool) -> Tensor:
-    """conv (+ bias) + train-mode BatchNorm (+ ReLU) (classification/architectures/hrnet.py:21-44).  The bias cancels in the output
-    and its gradient is zero, so no kernel adds it; eval mode folds it together with running_mean, so it does enter the batch mean
-    that is recorded for the running statistics."""
-    y = conv(x, c, bias=False)
-    if c.bias is None:
-        return bn(y, b, relu=relu)
-    return bn(_SilentBiasFn.apply(y, c.bias), b, relu=relu, mean_shift=c.bias)
 
 
 class _PoolFn(torch.autograd.Function):
@@ -258,32 +165,141 @@ class _LinearFn(torch.autograd.Function):
         return ops.linear_backward(x, w, dy, want=ctx.needs_input_grad)
 
 
-@torch.no_grad()
-def flush_running_stats() -> None:
-    """running = (1 - momentum) * running + momentum * batch statistic (unbiased variance), num_batches_tracked += 1, for
-    every BatchNorm of the forward in a handful of multi-tensor launches instead of six tiny ones per layer."""
-    if not _PENDING_STATS:
-        return
-    mods = [t[0] for t in _PENDING_STATS]
-    moms = {(m.momentum if m.momentum is not None else 0.1) for m in mods}
-    means = [t[1] for t in _PENDING_STATS]
-    # unbiased batch variance = (1 / invstd^2 - eps) * n / (n - 1), for all layers in four multi-tensor launches
-    invstds = [t[2] for t in _PENDING_STATS]
-    var_unb = torch._foreach_reciprocal(torch._foreach_mul(invstds, invstds))
-    torch._foreach_sub_(var_unb, [float(t[0].eps) for t in _PENDING_STATS])
-    torch._foreach_mul_(var_unb, [float(t[3]) / max(float(t[3]) - 1.0, 1.0) for t in _PENDING_STATS])
-    if len(moms) == 1:
-        mom = moms.pop()
-        rm, rv = [m.running_mean for m in mods], [m.running_var for m in mods]
-        torch._foreach_mul_(rm, 1 - mom); torch._foreach_add_(rm, means, alpha=mom)
-        torch._foreach_mul_(rv, 1 - mom); torch._foreach_add_(rv, var_unb, alpha=mom)
-    else:
-        for m, mean, vu in zip(mods, means, var_unb):
-            mom = m.momentum if m.momentum is not None else 0.1
-            m.running_mean.mul_(1 - mom).add_(mean, alpha=mom)
-            m.running_var.mul_(1 - mom).add_(vu, alpha=mom)
-    torch._foreach_add_([m.num_batches_tracked for m in mods], 1)
-    _PENDING_STATS.clear()
+def _sync_world(sync_batchnorm):
+    """(group, world_size) when BatchNorm statistics are shared across ranks: like torch's SyncBatchNorm, only if a process
+    group with more than one rank exists; otherwise None (plain BatchNorm).  sync_batchnorm: None, True (the default group) or a group."""
+    import torch.distributed as dist
+    if sync_batchnorm is None or not (dist.is_available() and dist.is_initialized()):
+        return None
+    group = None if sync_batchnorm is True else sync_batchnorm
+    world = dist.get_world_size(group)
+    return (group, world) if world > 1 else None
+
+
+def _packed_weights(net, act) -> dict:
+    """Pack the weights of every conv whose channel counts the kernels take unpadded - forward layout and data-gradient
+    layout - in ONE launch per step (ops.PackedConvWeights) instead of one launch per conv call.  The copies are read by this
+    forward and the backward that follows it; they go stale with the optimizer step and are refreshed by the next forward.
+    -> {(id(weight), stride): (forward-packed, data-gradient-packed)}; the buffers live in the per-net cache `net._train_packed`."""
+    cache = getattr(net, "_train_packed", None)
+    if cache is None or not cache[0].pointers_current() or cache[0].dtype != act:
+        entries, index = [], {}
+        for m in net.modules():
+            if isinstance(m, nn.Conv2d) and m.weight.is_cuda and m.weight.dtype == torch.float32:
+                cout, cin, ks, _ = m.weight.shape
+                stride = m.stride[0]
+                if cin % 16 or cout % 16 or (id(m.weight), stride) in index:
+                    continue
+                index[(id(m.weight), stride)] = (len(entries), len(entries) + 1)
+                entries += [(m.weight, stride, False), (m.weight, stride, True)]
+        pw = ops.PackedConvWeights(entries, act)
+        cache = (pw, {k: (pw.buffers[a], pw.buffers[b]) for k, (a, b) in index.items()})
+        net._train_packed = cache
+    cache[0].refresh()
+    return cache[1]
+
+
+class TrainForward:
+    """The state of ONE training forward, from the weight packing at its start to the running-statistics update at its end:
+      act      the activation type (of this forward and its backward)
+      sync     (process group, world size) when BatchNorm statistics are shared across ranks, else None; resolved once, here
+      packed   {(id(weight), stride): (forward-packed, data-gradient-packed)} of `net`, just refreshed; None without a net and after the end
+      pending  [(module, batch mean, batch invstd, pixels)] of the BatchNorms run so far, applied by flush_running_stats
+    `with TrainForward(net) as fw:` ends it: the statistics are flushed if the block completes and dropped if it raises, so a forward
+    that fails midway has changed no buffer.  The backward needs nothing of it (_ConvFn keeps the packed buffers it was given).
+    Without a net (tests, single ops) there is no packed table: TrainForward(sync_batchnorm=True).bn(x, m), then flush_running_stats()."""
+
+    def __init__(self, net=None, sync_batchnorm=None):
+        if net is not None:
+            sync_batchnorm = getattr(net, "sync_batchnorm", None)  # set by KeypointsModel.to_DDP(..., use_batchnorm=True)
+        self.act = ops.PRECISION_DTYPES[getattr(net, "train_precision", "bf16")]
+        self.sync = _sync_world(sync_batchnorm)
+        self.pending: list = []
+        self.packed = _packed_weights(net, self.act) if net is not None else None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is None:
+            self.flush_running_stats()
+        self.pending, self.packed = [], None
+
+    def conv(self, x: Tensor, m: nn.Conv2d, stride: int | None = None, box: _ResBox | None = None, bias: bool = True) -> Tensor:
+        """nn.Conv2d forward on the HIP kernels.  Channel counts the kernels cannot take (3, 17, 34, 66 ...) are zero padded:
+        padding and slicing are differentiable torch ops, so the gradients reach the unpadded parameter.  bias=False leaves the
+        module's bias out (conv_bias_bn adds it where it matters)."""
+        w = m.weight
+        cout, cin, ks, _ = w.shape
+        stride = m.stride[0] if stride is None else stride
+        cin_p, cout_p = _pad_c(cin, 16), _pad_c(cout, 16)  # the data gradient runs the conv with the roles swapped
+        if cin_p != cin or cout_p != cout:
+            w = F.pad(w, (0, 0, 0, 0, 0, cin_p - cin, 0, cout_p - cout))
+        if x.shape[1] != cin_p:
+            x = F.pad(x, (0, 0, 0, 0, 0, cin_p - x.shape[1]))
+        pk = self.packed.get((id(m.weight), stride)) if (self.packed is not None and w is m.weight) else None
+        if box is not None and (cin_p != cin or x.shape[1] != cin):
+            raise ValueError("conv: a skip-gradient box needs an unpadded input")
+        y = _ConvFn.apply(x.contiguous(memory_format=torch.channels_last), w, stride, None, *(pk if pk is not None else (None, None)), box)
+        if cout_p != cout:
+            y = y[:, :cout]
+        if m.bias is not None and bias:
+            y = y + m.bias.view(1, -1, 1, 1).to(y.dtype)
+        return y
+
+    def bn(self, x: Tensor, m: nn.BatchNorm2d, relu: bool = False, res: Tensor | None = None, box: _ResBox | None = None,
+           mean_shift: Tensor | None = None) -> Tensor:
+        """nn.BatchNorm2d in training mode (+ residual, + ReLU); the running statistics are updated like torch updates them,
+        once per forward for all layers together (flush_running_stats).  mean_shift [C]: a per-channel constant that the layer's input
+        carries in the reference but x does not (conv_bias_bn); it is added to the batch mean that feeds running_mean."""
+        stats: list = []
+        y = _BNFn.apply(x.contiguous(memory_format=torch.channels_last), m.weight, m.bias,
+                        res.contiguous(memory_format=torch.channels_last) if res is not None else None, relu, m.eps, stats, box, self.sync)
+        if m.track_running_stats and m.running_mean is not None:
+            mean = stats[0][0] if mean_shift is None else stats[0][0] + mean_shift.detach().float()
+            self.pending.append((m, mean, stats[0][1], stats[0][2]))  # count = pixels of all ranks under SyncBatchNorm
+        return y
+
+    def conv_bias_bn(self, x: Tensor, c: nn.Conv2d, b: nn.BatchNorm2d, relu: bool) -> Tensor:
+        """conv (+ bias) + train-mode BatchNorm (+ ReLU) (classification/architectures/hrnet.py:21-44).  The bias cancels in the output
+        and its gradient is zero, so no kernel adds it; eval mode folds it together with running_mean, so it does enter the batch mean
+        that is recorded for the running statistics."""
+        y = self.conv(x, c, bias=False)
+        if c.bias is None:
+            return self.bn(y, b, relu=relu)
+        return self.bn(_SilentBiasFn.apply(y, c.bias), b, relu=relu, mean_shift=c.bias)
+
+    @torch.no_grad()
+    def flush_running_stats(self) -> None:
+        """running = (1 - momentum) * running + momentum * batch statistic (unbiased variance), num_batches_tracked += 1, for
+        every BatchNorm of the forward in a handful of multi-tensor launches instead of six tiny ones per layer.  (momentum=None counts
+        as 0.1 here; torch would take the cumulative average.  The reference never sets None.)"""
+        pending, self.pending = self.pending, []
+        if not pending:
+            return
+        mods = [t[0] for t in pending]
+        moms = [m.momentum if m.momentum is not None else 0.1 for m in mods]
+        means = [t[1] for t in pending]
+        # unbiased batch variance = (1 / invstd^2 - eps) * n / (n - 1), for all layers in four multi-tensor launches
+        invstds = [t[2] for t in pending]
+        var_unb = torch._foreach_reciprocal(torch._foreach_mul(invstds, invstds))
+        torch._foreach_sub_(var_unb, [float(m.eps) for m in mods])
+        torch._foreach_mul_(var_unb, [float(t[3]) / max(float(t[3]) - 1.0, 1.0) for t in pending])
+        if len(set(moms)) == 1:
+            mom = moms[0]
+            rm, rv = [m.running_mean for m in mods], [m.running_var for m in mods]
+            torch._foreach_mul_(rm, 1 - mom); torch._foreach_add_(rm, means, alpha=mom)
+            torch._foreach_mul_(rv, 1 - mom); torch._foreach_add_(rv, var_unb, alpha=mom)
+        else:
+            for m, mom, mean, vu in zip(mods, moms, means, var_unb):
+                m.running_mean.mul_(1 - mom).add_(mean, alpha=mom)
+                m.running_var.mul_(1 - mom).add_(vu, alpha=mom)
+        torch._foreach_add_([m.num_batches_tracked for m in mods], 1)
+
+
+def conv(x: Tensor, m: nn.Conv2d, stride: int | None = None, box: _ResBox | None = None, bias: bool = True) -> Tensor:
+    """TrainForward.conv outside a forward: no packed table is consulted, the kernel packs m.weight as it is now."""
+    return TrainForward().conv(x, m, stride, box, bias)
 
 
 def deconv_k4s2(x: Tensor, m: nn.ConvTranspose2d) -> Tensor:
@@ -318,26 +334,26 @@ def _boxable(x, c: nn.Conv2d) -> bool:
     return not _NO_RESBOX and x.requires_grad and c.weight.shape[1] % 16 == 0 and x.shape[1] == c.weight.shape[1]
 
 
-def _bottleneck(x, u):
+def _bottleneck(fw: TrainForward, x, u):
     ds = u._modules.get("downsample")
     box = _ResBox() if ds is None and _boxable(x, u.conv1) else None  # identity skip: its gradient joins conv1's data gradient
-    y = bn(conv(x, u.conv1, box=box), u.bn1, relu=True)
-    y = bn(conv(y, u.conv2), u.bn2, relu=True)
-    r = bn(conv(x, ds._modules["0"]), ds._modules["1"]) if ds is not None else x
-    return bn(conv(y, u.conv3), u.bn3, relu=True, res=r, box=box)
+    y = fw.bn(fw.conv(x, u.conv1, box=box), u.bn1, relu=True)
+    y = fw.bn(fw.conv(y, u.conv2), u.bn2, relu=True)
+    r = fw.bn(fw.conv(x, ds._modules["0"]), ds._modules["1"]) if ds is not None else x
+    return fw.bn(fw.conv(y, u.conv3), u.bn3, relu=True, res=r, box=box)
 
 
-def _basic(x, u):
+def _basic(fw: TrainForward, x, u):
     box = _ResBox() if _boxable(x, u.conv1) else None
-    y = bn(conv(x, u.conv1, box=box), u.bn1, relu=True)
-    return bn(conv(y, u.conv2), u.bn2, relu=True, res=x, box=box)
+    y = fw.bn(fw.conv(x, u.conv1, box=box), u.bn1, relu=True)
+    return fw.bn(fw.conv(y, u.conv2), u.bn2, relu=True, res=x, box=box)
 
 
 def _children(m):
     return [m._modules[k] for k in sorted(m._modules, key=int)]
 
 
-def _fusion(xs, fl, n_out):
+def _fusion(fw: TrainForward, xs, fl, n_out):
     outs = []
     for i in range(n_out):
         row = fl.scales_fusion_layers._modules.get(str(i)) if hasattr(fl, "scales_fusion_layers") else None
@@ -347,31 +363,25 @@ def _fusion(xs, fl, n_out):
                 continue
             q = row._modules[str(j)]
             if j > i:  # 1x1 conv + BN at the low resolution; nn.Upsample(nearest) happens inside the sum
-                terms.append(bn(conv(x, q._modules["0"]), q._modules["1"]))
+                terms.append(fw.bn(fw.conv(x, q._modules["0"]), q._modules["1"]))
                 shifts.append(j - i)
             else:
                 t = x
                 for k in range(i - j):
                     qq = q._modules[str(k)]
-                    t = bn(conv(t, qq._modules["0"]), qq._modules["1"], relu=(k != i - j - 1))
+                    t = fw.bn(fw.conv(t, qq._modules["0"]), qq._modules["1"], relu=(k != i - j - 1))
                 terms.append(t)
                 shifts.append(0)
         outs.append(_FusionSumFn.apply(tuple(shifts), *terms))
     return outs
 
 
-def _backbone_train_forward(net, images: Tensor, n_last: int) -> list:
+def _backbone_train_forward(fw: TrainForward, bb, images: Tensor, n_last: int) -> list:
     """The HRNet backbone (hrnet.py:378-385) in training mode -> the `n_last` outputs of its last fusion layer (1: the pose net's
-    high-resolution map; 4: all scales, for the classification head).  Starts a forward: pending statistics, SyncBatchNorm group,
-    activation type and packed weights are those of `net`."""
-    bb = net.backbone
-    _PENDING_STATS.clear()
-    _SYNC[0] = getattr(net, "sync_batchnorm", None)  # set by KeypointsModel.to_DDP(..., use_batchnorm=True)
-    act = ops.PRECISION_DTYPES[getattr(net, "train_precision", "bf16")]  # the activation type of this forward and its backward
-    _refresh_packed(net, act)
-    x = images.to(act).contiguous(memory_format=torch.channels_last)
-    x = bn(conv(x, bb.conv1), bb.bn1, relu=True)
-    x = bn(conv(x, bb.conv2), bb.bn2, relu=True)
+    high-resolution map; 4: all scales, for the classification head)."""
+    x = images.to(fw.act).contiguous(memory_format=torch.channels_last)
+    x = fw.bn(fw.conv(x, bb.conv1), bb.bn1, relu=True)
+    x = fw.bn(fw.conv(x, bb.conv2), bb.bn2, relu=True)
     xs = [x]
     nblocks = [1, 1, 4, 3]
     for s in range(4):
@@ -382,21 +392,21 @@ def _backbone_train_forward(net, images: Tensor, n_last: int) -> list:
             new = []
             for i, t in enumerate(xs):
                 for u in _children(blk.scales_blocks._modules[str(i)]):
-                    t = unit(t, u)
+                    t = unit(fw, t, u)
                 new.append(t)
             xs = new
             last = s == 3 and b == nblocks[s] - 1
             if s > 0:
-                xs = _fusion(xs, st.blocks._modules[str(2 * b + 1)], n_last if last else len(xs))
+                xs = _fusion(fw, xs, st.blocks._modules[str(2 * b + 1)], n_last if last else len(xs))
             # (stage 0 has one scale: its "fusion" is the ReLU of a ReLU output, hrnet.py:221-229 -- the identity, gradient included)
         if s < 3:
             tb = st.transition_layer.transition_blocks
             n = len(xs)
             q = tb._modules[str(n)]
-            newb = bn(conv(xs[-1], q._modules["0"]), q._modules["1"], relu=True)
+            newb = fw.bn(fw.conv(xs[-1], q._modules["0"]), q._modules["1"], relu=True)
             if s == 0:
                 q0 = tb._modules["0"]
-                xs = [bn(conv(xs[0], q0._modules["0"]), q0._modules["1"], relu=True)]
+                xs = [fw.bn(fw.conv(xs[0], q0._modules["0"]), q0._modules["1"], relu=True)]
             xs = xs + [newb]
     return xs
 
@@ -404,15 +414,15 @@ def _backbone_train_forward(net, images: Tensor, n_last: int) -> list:
 def higher_hrnet_train_forward(net, images: Tensor):
     """-> ([hm_1/4, hm_1/2] fp32, tags_1/4 fp32), differentiable w.r.t. every parameter of `net`."""
     K = net.num_kpts
-    feats = _backbone_train_forward(net, images, 1)[0]
-    init = conv(feats, net.init_heatmaps_head)
-    d = net.deconv_layers._modules["0"]
-    y = torch.cat((feats, init.to(feats.dtype)), 1)
-    y = bn(deconv_k4s2(y, d.deconv._modules["0"]), d.deconv._modules["1"], relu=True)
-    for u in _children(d.resid_blocks):
-        y = _basic(y, u)
-    out = conv(y, d.final_layer)
-    flush_running_stats()
+    with TrainForward(net) as fw:
+        feats = _backbone_train_forward(fw, net.backbone, images, 1)[0]
+        init = fw.conv(feats, net.init_heatmaps_head)
+        d = net.deconv_layers._modules["0"]
+        y = torch.cat((feats, init.to(feats.dtype)), 1)
+        y = fw.bn(deconv_k4s2(y, d.deconv._modules["0"]), d.deconv._modules["1"], relu=True)
+        for u in _children(d.resid_blocks):
+            y = _basic(fw, y, u)
+        out = fw.conv(y, d.final_layer)
     init, out = init.float(), out.float()
     return [init[:, :K], out[:, :K]], init[:, K:]
 
@@ -421,14 +431,14 @@ def classification_hrnet_train_forward(net, images: Tensor) -> Tensor:
     """-> logits fp32 [B, num_classes], differentiable w.r.t. every parameter of `net` (classification/architectures/hrnet.py:48-74):
     one Bottleneck per scale (C_i -> 128 / 256 / 512 / 1024), each joined by the stride-2 conv + BN + ReLU of the scale above (a plain
     sum, no ReLU after it), the 1x1 conv to 2048 + BN + ReLU, the global average pool and the fp32 Linear."""
-    xs = _backbone_train_forward(net, images, 4)
     head = net.classification_head
     incr, down = _children(head.chann_incr_blocks), _children(head.downsample_blocks)
-    out = _bottleneck(xs[0], incr[0])
-    for i, d in enumerate(down):
-        out = _bottleneck(xs[i + 1], incr[i + 1]) + conv_bias_bn(out, d._modules["0"], d._modules["1"], relu=True)
-    f = head.final_conv
-    out = conv_bias_bn(out, f._modules["0"], f._modules["1"], relu=True)
-    flat = _PoolFn.apply(out.contiguous(memory_format=torch.channels_last))
-    flush_running_stats()
+    with TrainForward(net) as fw:
+        xs = _backbone_train_forward(fw, net.backbone, images, 4)
+        out = _bottleneck(fw, xs[0], incr[0])
+        for i, d in enumerate(down):
+            out = _bottleneck(fw, xs[i + 1], incr[i + 1]) + fw.conv_bias_bn(out, d._modules["0"], d._modules["1"], relu=True)
+        f = head.final_conv
+        out = fw.conv_bias_bn(out, f._modules["0"], f._modules["1"], relu=True)
+        flat = _PoolFn.apply(out.contiguous(memory_format=torch.channels_last))
     return _LinearFn.apply(flat, head.classifier.weight, head.classifier.bias)

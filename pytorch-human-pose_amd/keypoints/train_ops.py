@@ -30,57 +30,67 @@ def _act(first: Tensor, *others) -> int:
     return ACT_DTYPES[first.dtype]
 
 
-def conv2d(x: Tensor, w: Tensor, stride: int = 1, bias: Tensor | None = None, res: Tensor | None = None, relu: bool = False,
-           data_grad: bool = False, pad: tuple[int, int] | None = None, packed: Tensor | None = None) -> Tensor:
-    """y = act(conv(x, w) + bias (+ res)), padding (ks-1)/2.  data_grad=True: x is dL/dy of the conv with weights
-    w [cout,cin,ks,ks] and this stride, and the result is dL/dx (stride 2: 3x3 only, even input sizes).
-    packed: the weights of this (w, stride, data_grad) already packed by `pack_conv_weights` (w then only gives the shape)."""
-    lib = _lib.load()
-    x = _nhwc(x)
-    B, Cx, H, W = x.shape
-    cout, cin, ks, _ = w.shape
-    if packed is not None:
-        if Cx != (cout if data_grad else cin):
-            raise ValueError(f"conv2d: input has {Cx} channels, weights {tuple(w.shape)}, data_grad={data_grad}")
-        mode = (2 if stride == 2 else 1) if data_grad else 0
-        co = cin if data_grad else cout
-        Ho, Wo = (2 * H, 2 * W) if mode == 2 else ((H // 2, W // 2) if stride == 2 else (H, W))
-        y = torch.empty((B, co, Ho, Wo), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
-        if res is not None:
-            res = _nhwc(res)
-        dt = _act(x, res, packed)  # (the packed weights carry the type they were packed with)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        py_, px_ = pad if pad is not None else (-1, -1)
-        with torch.cuda.device(x.device):
-            _lib.check(lib.hh_conv2d_packed_dt(dt, x.data_ptr(), B, H, W, cin, packed.data_ptr(), cout, ks, stride, mode, py_, px_,
-                                               bias.data_ptr() if bias is not None else None, res.data_ptr() if res is not None else None,
-                                               int(relu), y.data_ptr(), stream))
-        return y
-    w = w.detach().to(x.device, torch.float32).contiguous()
-    if Cx != (cout if data_grad else cin):
-        raise ValueError(f"conv2d: input has {Cx} channels, weights {tuple(w.shape)}, data_grad={data_grad}")
-    co = cin if data_grad else cout
+BN_BLOCKS = 256  # HH_BN_BLOCKS of csrc/kernels.h: the BatchNorm reductions write BN_BLOCKS * C * 2 partial sums into their scratch
+
+
+def _launch(dev, fn, *args) -> None:
+    """One C-ABI call with `dev` current, on its current stream (the last argument of every entry point); raises on its status."""
+    with torch.cuda.device(dev):
+        _lib.check(fn(*args, torch.cuda.current_stream(dev).cuda_stream))
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _conv_geometry(wshape, stride: int, data_grad: bool, H: int = 0, W: int = 0):
+    """-> (mode of hh_conv2d, channels the input must have, channels of the output, Ho, Wo) for weights [cout,cin,ks,ks]"""
+    cout, cin = wshape[:2]
     mode = (2 if stride == 2 else 1) if data_grad else 0
     if mode == 2:
         Ho, Wo = 2 * H, 2 * W  # dL/dx of a stride-2 conv lives on the input grid
     else:
         Ho, Wo = (H // 2, W // 2) if stride == 2 else (H, W)
+    return (mode, cout, cin, Ho, Wo) if data_grad else (mode, cin, cout, Ho, Wo)
+
+
+def conv2d(x: Tensor, w: Tensor, stride: int = 1, bias: Tensor | None = None, res: Tensor | None = None, relu: bool = False,
+           data_grad: bool = False, pad: tuple[int, int] | None = None, packed: Tensor | None = None) -> Tensor:
+    """y = act(conv(x, w) + bias (+ res)), padding (ks-1)/2.  data_grad=True: x is dL/dy of the conv with weights
+    w [cout,cin,ks,ks] and this stride, and the result is dL/dx (stride 2: 3x3 only, even input sizes).
+    packed: the weights of this (w, stride, data_grad) already packed by `PackedConvWeights` (w then only gives the shape)."""
+    lib = _lib.load()
+    x = _nhwc(x)
+    B, Cx, H, W = x.shape
+    cout, cin, ks, _ = w.shape
+    mode, ci, co, Ho, Wo = _conv_geometry(w.shape, stride, data_grad, H, W)
+    if Cx != ci:
+        raise ValueError(f"conv2d: input has {Cx} channels, weights {tuple(w.shape)}, data_grad={data_grad}")
     y = torch.empty((B, co, Ho, Wo), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
-    nbytes = lib.hh_conv2d_workspace_bytes(cin, cout, ks, mode)
-    if nbytes < 0:
-        raise _lib.HHError("conv2d: no kernel family for this shape")
-    ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+    if packed is not None:
+        fn, wk, tail = lib.hh_conv2d_packed_dt, packed, ()
+    else:  # the kernel packs w itself, into a workspace
+        nbytes = lib.hh_conv2d_workspace_bytes(cin, cout, ks, mode)
+        if nbytes < 0:
+            raise _lib.HHError("conv2d: no kernel family for this shape")
+        ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)  # (alive until the launch is enqueued)
+        fn, wk, tail = lib.hh_conv2d_dt, w.detach().to(x.device, torch.float32).contiguous(), (ws.data_ptr(),)
     if res is not None:
         res = _nhwc(res)
     if bias is not None:
         bias = bias.detach().to(x.device, torch.float32).contiguous()
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    with torch.cuda.device(x.device):
-        py_, px_ = pad if pad is not None else (-1, -1)
-        _lib.check(lib.hh_conv2d_dt(_act(x, res), x.data_ptr(), B, H, W, cin, w.data_ptr(), cout, ks, stride, mode, py_, px_,
-                                    bias.data_ptr() if bias is not None else None, res.data_ptr() if res is not None else None,
-                                    int(relu), y.data_ptr(), ws.data_ptr(), stream))
+    py_, px_ = pad if pad is not None else (-1, -1)
+    # (the packed weights carry the type they were packed with)
+    _launch(x.device, fn, _act(x, res, packed), x.data_ptr(), B, H, W, cin, wk.data_ptr(), cout, ks, stride, mode, py_, px_, _ptr(bias), _ptr(res),
+            int(relu), y.data_ptr(), *tail)
     return y
+
+
+def _bn_buffers(x: Tensor):
+    """-> (two per-channel fp32 outputs: mean, invstd or dgamma, dbeta; the partial-sum scratch of the reductions)"""
+    C = x.shape[1]
+    return (torch.empty(C, device=x.device, dtype=torch.float32), torch.empty(C, device=x.device, dtype=torch.float32),
+            torch.empty(BN_BLOCKS * C * 2, device=x.device, dtype=torch.float64))
 
 
 def bn_train_forward(x: Tensor, gamma: Tensor, beta: Tensor, eps: float = 1e-5, res: Tensor | None = None, relu: bool = False):
@@ -89,16 +99,11 @@ def bn_train_forward(x: Tensor, gamma: Tensor, beta: Tensor, eps: float = 1e-5, 
     x = _nhwc(x)
     B, C, H, W = x.shape
     y = torch.empty_like(x)
-    mean = torch.empty(C, device=x.device, dtype=torch.float32)
-    invstd = torch.empty(C, device=x.device, dtype=torch.float32)
-    scratch = torch.empty(256 * C * 2, device=x.device, dtype=torch.float64)
+    mean, invstd, scratch = _bn_buffers(x)
     if res is not None:
         res = _nhwc(res)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    with torch.cuda.device(x.device):
-        _lib.check(lib.hh_bn_train_forward_dt(_act(x, res), x.data_ptr(), B * H * W, C, gamma.float().contiguous().data_ptr(),
-                                              beta.float().contiguous().data_ptr(), eps, res.data_ptr() if res is not None else None, int(relu),
-                                              y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), scratch.data_ptr(), stream))
+    _launch(x.device, lib.hh_bn_train_forward_dt, _act(x, res), x.data_ptr(), B * H * W, C, gamma.float().contiguous().data_ptr(),
+            beta.float().contiguous().data_ptr(), eps, _ptr(res), int(relu), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), scratch.data_ptr())
     return y, mean, invstd
 
 
@@ -109,31 +114,19 @@ def bn_train_backward(x: Tensor, y, dy: Tensor, mean: Tensor, invstd: Tensor, ga
     lib = _lib.load()
     if y is None:
         assert beta is not None and not want_dres
-        x, dy = _nhwc(x), _nhwc(dy)
-        B, C, H, W = x.shape
-        dx = torch.empty_like(x)
-        dgamma = torch.empty(C, device=x.device, dtype=torch.float32)
-        dbeta = torch.empty(C, device=x.device, dtype=torch.float32)
-        scratch = torch.empty(256 * C * 2, device=x.device, dtype=torch.float64)
-        g, b = gamma.float().contiguous(), beta.float().contiguous()
-        with torch.cuda.device(x.device):
-            _lib.check(lib.hh_bn_train_backward_plain_dt(_act(x, dy), x.data_ptr(), dy.data_ptr(), B * H * W, C, mean.data_ptr(), invstd.data_ptr(),
-                                                         g.data_ptr(), b.data_ptr(), int(relu), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-                                                         scratch.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream))
-        return dx, dgamma, dbeta, None
-    x, y, dy = _nhwc(x), _nhwc(y), _nhwc(dy)
+    x, y, dy = _nhwc(x), _nhwc(y) if y is not None else None, _nhwc(dy)
     B, C, H, W = x.shape
     dx = torch.empty_like(x)
     dres = torch.empty_like(x) if want_dres else None
-    dgamma = torch.empty(C, device=x.device, dtype=torch.float32)
-    dbeta = torch.empty(C, device=x.device, dtype=torch.float32)
-    scratch = torch.empty(256 * C * 2, device=x.device, dtype=torch.float64)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
+    dgamma, dbeta, scratch = _bn_buffers(x)
     g = gamma.float().contiguous()
-    with torch.cuda.device(x.device):
-        _lib.check(lib.hh_bn_train_backward_dt(_act(x, y, dy), x.data_ptr(), y.data_ptr(), dy.data_ptr(), B * H * W, C, mean.data_ptr(),
-                                               invstd.data_ptr(), g.data_ptr(), int(relu), dx.data_ptr(), dres.data_ptr() if dres is not None else None,
-                                               dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr(), stream))
+    if y is None:
+        b = beta.float().contiguous()
+        _launch(x.device, lib.hh_bn_train_backward_plain_dt, _act(x, dy), x.data_ptr(), dy.data_ptr(), B * H * W, C, mean.data_ptr(), invstd.data_ptr(),
+                g.data_ptr(), b.data_ptr(), int(relu), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr())
+    else:
+        _launch(x.device, lib.hh_bn_train_backward_dt, _act(x, y, dy), x.data_ptr(), y.data_ptr(), dy.data_ptr(), B * H * W, C, mean.data_ptr(),
+                invstd.data_ptr(), g.data_ptr(), int(relu), dx.data_ptr(), _ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr())
     return dx, dgamma, dbeta, dres
 
 
@@ -154,7 +147,7 @@ class PackedConvWeights:
         dev = entries[0][0].device if entries else None
         for i, (w, stride, data_grad) in enumerate(entries):
             cout, cin, ks, _ = w.shape
-            mode = (2 if stride == 2 else 1) if data_grad else 0
+            mode = _conv_geometry(w.shape, stride, data_grad)[0]
             nel = lib.hh_conv2d_packed_elems(cin, cout, ks, stride, mode)
             if nel < 0:
                 raise _lib.HHError(f"no kernel family for conv weights {tuple(w.shape)} (stride {stride}, data_grad={data_grad})")
@@ -169,13 +162,9 @@ class PackedConvWeights:
         return all(w.data_ptr() == p for w, p in zip(self._keep, self._w))
 
     def refresh(self) -> None:
-        if not self.n:
-            return
-        lib = _lib.load()
-        dev = self._descs.device
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        with torch.cuda.device(dev):
-            _lib.check(lib.hh_pack_conv_weights_batch_dt(ACT_DTYPES[self.dtype], self.n, self._w, self._p, self._shapes, self._descs.data_ptr(), stream))
+        if self.n:
+            _launch(self._descs.device, _lib.load().hh_pack_conv_weights_batch_dt, ACT_DTYPES[self.dtype], self.n, self._w, self._p, self._shapes,
+                    self._descs.data_ptr())
 
 
 def _all_reduce_sums(sums: Tensor, group) -> None:
@@ -191,21 +180,16 @@ def sync_bn_train_forward(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, re
     B, C, H, W = x.shape
     P = B * H * W
     y = torch.empty_like(x)
-    mean = torch.empty(C, device=x.device, dtype=torch.float32)
-    invstd = torch.empty(C, device=x.device, dtype=torch.float32)
+    mean, invstd, scratch = _bn_buffers(x)
     sums = torch.empty(2 * C, device=x.device, dtype=torch.float64)
-    scratch = torch.empty(256 * C * 2, device=x.device, dtype=torch.float64)
     if res is not None:
         res = _nhwc(res)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    with torch.cuda.device(x.device):
-        dt = _act(x, res)
-        _lib.check(lib.hh_bn_train_stats_dt(dt, x.data_ptr(), P, C, sums.data_ptr(), scratch.data_ptr(), stream))
-        _all_reduce_sums(sums, group)
-        count = float(P) * world
-        _lib.check(lib.hh_bn_train_normalize_dt(dt, x.data_ptr(), P, C, sums.data_ptr(), count, gamma.float().contiguous().data_ptr(),
-                                                beta.float().contiguous().data_ptr(), eps, res.data_ptr() if res is not None else None,
-                                                int(relu), y.data_ptr(), mean.data_ptr(), invstd.data_ptr(), stream))
+    dt = _act(x, res)
+    _launch(x.device, lib.hh_bn_train_stats_dt, dt, x.data_ptr(), P, C, sums.data_ptr(), scratch.data_ptr())
+    _all_reduce_sums(sums, group)
+    count = float(P) * world
+    _launch(x.device, lib.hh_bn_train_normalize_dt, dt, x.data_ptr(), P, C, sums.data_ptr(), count, gamma.float().contiguous().data_ptr(),
+            beta.float().contiguous().data_ptr(), eps, _ptr(res), int(relu), y.data_ptr(), mean.data_ptr(), invstd.data_ptr())
     return y, mean, invstd, count
 
 
@@ -218,20 +202,15 @@ def sync_bn_train_backward(x: Tensor, y: Tensor, dy: Tensor, mean: Tensor, invst
     P = B * H * W
     dx = torch.empty_like(x)
     dres = torch.empty_like(x) if want_dres else None
-    dgamma = torch.empty(C, device=x.device, dtype=torch.float32)
-    dbeta = torch.empty(C, device=x.device, dtype=torch.float32)
+    dgamma, dbeta, scratch = _bn_buffers(x)
     sums = torch.empty(2 * C, device=x.device, dtype=torch.float64)
-    scratch = torch.empty(256 * C * 2, device=x.device, dtype=torch.float64)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
     g = gamma.float().contiguous()
-    with torch.cuda.device(x.device):
-        dt = _act(x, y, dy)
-        _lib.check(lib.hh_bn_train_backward_stats_dt(dt, x.data_ptr(), y.data_ptr(), dy.data_ptr(), P, C, mean.data_ptr(), invstd.data_ptr(),
-                                                     int(relu), sums.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr(), stream))
-        _all_reduce_sums(sums, group)
-        _lib.check(lib.hh_bn_train_backward_apply_dt(dt, x.data_ptr(), y.data_ptr(), dy.data_ptr(), P, C, mean.data_ptr(), invstd.data_ptr(),
-                                                     g.data_ptr(), int(relu), sums.data_ptr(), count, dx.data_ptr(),
-                                                     dres.data_ptr() if dres is not None else None, scratch.data_ptr(), stream))
+    dt = _act(x, y, dy)
+    _launch(x.device, lib.hh_bn_train_backward_stats_dt, dt, x.data_ptr(), y.data_ptr(), dy.data_ptr(), P, C, mean.data_ptr(), invstd.data_ptr(),
+            int(relu), sums.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), scratch.data_ptr())
+    _all_reduce_sums(sums, group)
+    _launch(x.device, lib.hh_bn_train_backward_apply_dt, dt, x.data_ptr(), y.data_ptr(), dy.data_ptr(), P, C, mean.data_ptr(), invstd.data_ptr(),
+            g.data_ptr(), int(relu), sums.data_ptr(), count, dx.data_ptr(), _ptr(dres), scratch.data_ptr())
     return dx, dgamma, dbeta, dres
 
 
@@ -243,11 +222,8 @@ def conv2d_weight_grad(x: Tensor, dy: Tensor, ks: int, stride: int = 1, pad: tup
     cout = dy.shape[1]
     dw = torch.empty((cout, cin, ks, ks), device=x.device, dtype=torch.float32)
     ws = torch.empty(lib.hh_conv2d_wgrad_workspace_bytes(B, H, W, cin, cout, ks, stride), device=x.device, dtype=torch.uint8)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    with torch.cuda.device(x.device):
-        py_, px_ = pad if pad is not None else (-1, -1)
-        _lib.check(lib.hh_conv2d_wgrad_dt(_act(x, dy), x.data_ptr(), dy.data_ptr(), B, H, W, cin, cout, ks, stride, py_, px_, dw.data_ptr(), ws.data_ptr(),
-                                          stream))
+    py_, px_ = pad if pad is not None else (-1, -1)
+    _launch(x.device, lib.hh_conv2d_wgrad_dt, _act(x, dy), x.data_ptr(), dy.data_ptr(), B, H, W, cin, cout, ks, stride, py_, px_, dw.data_ptr(), ws.data_ptr())
     return dw
 
 
@@ -260,9 +236,7 @@ def fusion_sum(terms: list[Tensor], shifts: list[int], relu: bool = True) -> Ten
     out = torch.empty_like(terms[0])
     ptrs = (C.c_void_p * len(terms))(*[t.data_ptr() for t in terms])
     sh = (C.c_int * len(terms))(*shifts)
-    stream = torch.cuda.current_stream(out.device).cuda_stream
-    with torch.cuda.device(out.device):
-        _lib.check(lib.hh_fusion_sum_forward_dt(_act(*terms), ptrs, sh, len(terms), B, H, W, Cc, int(relu), out.data_ptr(), stream))
+    _launch(out.device, lib.hh_fusion_sum_forward_dt, _act(*terms), ptrs, sh, len(terms), B, H, W, Cc, int(relu), out.data_ptr())
     return out
 
 
@@ -277,10 +251,8 @@ def fusion_sum_backward(dy: Tensor, out: Tensor, shifts: list[int], relu: bool =
     dups = [torch.empty((B, Cc, H >> s, W >> s), device=dy.device, dtype=dy.dtype).contiguous(memory_format=torch.channels_last) for _, s in ups]
     ptrs = (C.c_void_p * max(len(dups), 1))(*[t.data_ptr() for t in dups])
     sh = (C.c_int * max(len(dups), 1))(*[s for _, s in ups])
-    stream = torch.cuda.current_stream(dy.device).cuda_stream
-    with torch.cuda.device(dy.device):
-        _lib.check(lib.hh_fusion_sum_backward_dt(_act(dy, out), dy.data_ptr(), out.data_ptr(), int(relu), B, H, W, Cc, g.data_ptr() if relu else None,
-                                                 ptrs, sh, len(dups), stream))
+    _launch(dy.device, lib.hh_fusion_sum_backward_dt, _act(dy, out), dy.data_ptr(), out.data_ptr(), int(relu), B, H, W, Cc, g.data_ptr() if relu else None,
+            ptrs, sh, len(dups))
     grads: list = [g] * len(shifts)
     for (j, _), d in zip(ups, dups):
         grads[j] = d
@@ -300,8 +272,7 @@ def global_avgpool(x: Tensor) -> Tensor:
     x = _nhwc(x)
     B, C, H, W = x.shape
     out = torch.empty((B, C), device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.hh_global_avgpool_act(_act(x), x.data_ptr(), B, H * W, C, out.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream))
+    _launch(x.device, lib.hh_global_avgpool_act, _act(x), x.data_ptr(), B, H * W, C, out.data_ptr())
     return out
 
 
@@ -313,9 +284,7 @@ def global_avgpool_backward(g: Tensor, H: int, W: int, dtype: torch.dtype) -> Te
     g = _f32(g, "the pooled gradient")
     B, C = g.shape
     dx = torch.empty((B, C, H, W), device=g.device, dtype=dtype, memory_format=torch.channels_last)
-    with torch.cuda.device(g.device):
-        _lib.check(lib.hh_global_avgpool_backward_act(ACT_DTYPES[dtype], g.data_ptr(), B, H * W, C, dx.data_ptr(),
-                                                     torch.cuda.current_stream(g.device).cuda_stream))
+    _launch(g.device, lib.hh_global_avgpool_backward_act, ACT_DTYPES[dtype], g.data_ptr(), B, H * W, C, dx.data_ptr())
     return dx
 
 
@@ -327,8 +296,7 @@ def linear_forward(x: Tensor, w: Tensor, bias: Tensor) -> Tensor:
     if w.shape != (N, K) or bias.shape != (N,):
         raise ValueError(f"linear_forward: x {tuple(x.shape)}, w {tuple(w.shape)}, bias {tuple(bias.shape)}")
     y = torch.empty((B, N), device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.hh_linear_forward(x.data_ptr(), w.data_ptr(), bias.data_ptr(), B, K, N, y.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream))
+    _launch(x.device, lib.hh_linear_forward, x.data_ptr(), w.data_ptr(), bias.data_ptr(), B, K, N, y.data_ptr())
     return y
 
 
@@ -342,9 +310,7 @@ def linear_backward(x: Tensor, w: Tensor, dy: Tensor, want=(True, True, True)):
     dx = torch.empty_like(x) if want[0] else None
     dw = torch.empty_like(w) if want[1] else None
     db = torch.empty(N, device=x.device, dtype=torch.float32) if want[2] else None
-    with torch.cuda.device(x.device):
-        _lib.check(lib.hh_linear_backward(x.data_ptr(), w.data_ptr(), dy.data_ptr(), B, K, N, *(t.data_ptr() if t is not None else None for t in (dx, dw, db)),
-                                          torch.cuda.current_stream(x.device).cuda_stream))
+    _launch(x.device, lib.hh_linear_backward, x.data_ptr(), w.data_ptr(), dy.data_ptr(), B, K, N, _ptr(dx), _ptr(dw), _ptr(db))
     return dx, dw, db
 
 
@@ -359,9 +325,7 @@ def softmax_xent(logits: Tensor, targets: Tensor, want_grad: bool = True):
         raise ValueError(f"softmax_xent: logits {tuple(z.shape)}, targets {tuple(t.shape)}")
     result = torch.empty(4, device=z.device, dtype=torch.int32)
     dz = torch.empty_like(z) if want_grad else None
-    with torch.cuda.device(z.device):
-        _lib.check(lib.hh_softmax_xent(z.data_ptr(), t.data_ptr(), B, N, dz.data_ptr() if dz is not None else None, result.data_ptr(),
-                                       torch.cuda.current_stream(z.device).cuda_stream))
+    _launch(z.device, lib.hh_softmax_xent, z.data_ptr(), t.data_ptr(), B, N, _ptr(dz), result.data_ptr())
     return result, dz
 
 

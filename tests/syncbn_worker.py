@@ -32,14 +32,13 @@ def main() -> int:
     with torch.no_grad():
         m.weight.copy_(torch.rand(C, generator=g) + 0.5); m.bias.copy_(torch.randn(C, generator=g) * 0.2)
     def run(sl, sync):
-        tn._SYNC[0] = True if sync else None
-        tn._PENDING_STATS.clear()
+        fw = tn.TrainForward(sync_batchnorm=True if sync else None)
         m.zero_grad(); m.running_mean.zero_(); m.running_var.fill_(1.0)
         x = xf[sl].to(dev).contiguous(memory_format=torch.channels_last).requires_grad_(True)
         r = rf[sl].to(dev).contiguous(memory_format=torch.channels_last).requires_grad_(True)
-        y = tn.bn(x, m, relu=True, res=r)
+        y = fw.bn(x, m, relu=True, res=r)
         (y.float() * wf[sl].to(dev)).sum().backward()
-        tn.flush_running_stats()
+        fw.flush_running_stats()
         return [t.detach().float().cpu() for t in (y, x.grad, r.grad, m.weight.grad, m.bias.grad, m.running_mean, m.running_var)]
     per = Bf // world
     mine = slice(rank * per, (rank + 1) * per)

@@ -40,19 +40,17 @@ def test_shard_and_gather_two_ranks(n_items):
 
 
 def _syncbn_worker(rank, world, port, q):
-    """The exchange step of SyncBatchNorm as the training forward runs it (train_net._sync_world, train_ops._all_reduce_sums):
+    """The exchange step of SyncBatchNorm as the training forward runs it (train_net.TrainForward.sync, train_ops._all_reduce_sums):
     per-rank {sum, sum of squares} doubles -> all-reduce -> the full-batch mean / biased variance on every rank."""
     import numpy as np, torch
     sys.path.insert(0, REPO)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     tn = importlib.import_module(PKG + ".keypoints.train_net")
     ops = importlib.import_module(PKG + ".keypoints.train_ops")
-    tn._SYNC[0] = True
-    before = tn._sync_world()          # no process group yet: plain BatchNorm, like torch's SyncBatchNorm
+    before = tn.TrainForward(sync_batchnorm=True).sync  # no process group yet: plain BatchNorm, like torch's SyncBatchNorm
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    with_group = tn._sync_world()
-    tn._SYNC[0] = None
-    unset = tn._sync_world()
+    with_group = tn.TrainForward(sync_batchnorm=True).sync
+    unset = tn.TrainForward(sync_batchnorm=None).sync
     x = np.random.default_rng(5).normal(0.3, 2.0, (4, 6, 5, 8))  # [B, C, H, W], the same on both ranks
     mine = x[rank * 2:(rank + 1) * 2]
     sums = torch.from_numpy(np.stack([mine.sum((0, 2, 3)), (mine ** 2).sum((0, 2, 3))], 1).reshape(-1).copy())

@@ -1007,7 +1007,7 @@ def test_fusion_sum_training_op_matches_torch(pkg):
 
 
 def test_running_statistics_match_torch_batchnorm(pkg):
-    """The training forward's BatchNorm bookkeeping (train_net.bn + flush_running_stats: the unbiased variance is rebuilt from
+    """The training forward's BatchNorm bookkeeping (train_net.TrainForward.bn + flush_running_stats: the unbiased variance is rebuilt from
     the kernel's invstd as (1 / invstd^2 - eps) * n / (n - 1)) against nn.BatchNorm2d on the same bf16-rounded input, over
     three steps with changing inputs: running_mean, running_var, num_batches_tracked."""
     from torch import nn
@@ -1021,8 +1021,9 @@ def test_running_statistics_match_torch_batchnorm(pkg):
         ours.train(); ref.train()
         for step in range(3):
             x = _bf(torch.randn(B, C, hw, hw, generator=g) * (1 + step) + 0.3 * step)
-            y = tn.bn(x.to(DEV, torch.bfloat16), ours, relu=False)
-            tn.flush_running_stats()
+            fw = tn.TrainForward()
+            y = fw.bn(x.to(DEV, torch.bfloat16), ours, relu=False)
+            fw.flush_running_stats()
             yr = ref(x)
             assert (y.float().cpu() - yr).abs().max().item() < 1.5e-2 * yr.abs().max().item()
         np.testing.assert_allclose(ours.running_mean.cpu().numpy(), ref.running_mean.numpy(), rtol=1e-4, atol=1e-5)
