@@ -212,7 +212,8 @@ int hh_parse(hh_decoder *dec, const float *hm_full, const float *tags_full, int 
  *
  * hh_loss_heatmaps = HeatmapsLoss.forward (loss.py:12-16): *loss = mean((pred - target)^2 * mask[:,None]);
  *   pred [B,K,h,w] with batch stride pred_bstride (a channel slice of a wider tensor is fine), target [B,K,h,w] and
- *   mask [B,h,w] contiguous; if grad != NULL, grad[b,k] (batch stride grad_bstride) = d loss / d pred.
+ *   mask [B,h,w] contiguous; if grad != NULL, grad[b,k] (batch stride grad_bstride) = d loss / d pred.  h*w and both batch strides
+ *   are multiples of 4 and all four pointers 16-byte aligned (the kernel moves float4); anything else is refused before the launch.
  * hh_loss_ae_grouping = AEGroupingLoss.forward (loss.py:20-61): push_pull[0] = push, [1] = pull, both / batch size
  *   (calculate_loss, loss.py:90-92, scales them by 1e-3 afterwards); tags [B,K,h,w]; joints [B,P,K,3] int32 (x, y, vis)
  *   padded to P people, num_people[b] of them valid, x in [0,w), y in [0,h) wherever vis > 0 (the caller checks);

@@ -283,6 +283,8 @@ int hh_loss_heatmaps(const float *pred, int64_t pred_bstride, const float *targe
 {
     if (!pred || !target || !mask || !loss || !scratch || B <= 0 || K <= 0 || h <= 0 || w <= 0) { hh_set_error("hh_loss_heatmaps: bad argument"); return 1; }
     if ((h * w) % 4 || pred_bstride % 4 || (grad && grad_bstride % 4)) { hh_set_error("hh_loss_heatmaps: h*w and the batch strides must be multiples of 4"); return 1; }
+    // the kernel reads float4 from all three inputs and stores float4 to grad (NULL counts as aligned)
+    if (((uintptr_t)pred | (uintptr_t)target | (uintptr_t)mask | (uintptr_t)grad) & 15) { hh_set_error("hh_loss_heatmaps: pred, target, mask and grad must be 16-byte aligned"); return 1; }
     HH_CHECK_HIP(launch_masked_mse(pred, pred_bstride, target, mask, B, K, h, w, loss, grad, grad_bstride, scratch, (hipStream_t)stream));
     return 0;
 }

@@ -30,14 +30,19 @@ def _plane_view(t: Tensor, what: str) -> Tensor:
     return t
 
 
+def _aligned(t: Tensor) -> Tensor:
+    """The MSE kernel moves float4: a view that starts at an odd element of its storage (`.contiguous()` keeps it) is copied."""
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 class _HeatmapsLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred: Tensor, target: Tensor, mask: Tensor) -> Tensor:
         lib = _lib.load()
-        p = _plane_view(pred.detach(), "pred_heatmaps")
+        p = _aligned(_plane_view(pred.detach(), "pred_heatmaps"))
         B, K, h, w = p.shape
-        t = target.to(p.device, torch.float32).contiguous()
-        m = mask.to(p.device, torch.float32).contiguous()
+        t = _aligned(target.to(p.device, torch.float32).contiguous())
+        m = _aligned(mask.to(p.device, torch.float32).contiguous())
         if t.shape != p.shape or m.shape != (B, h, w):
             raise ValueError(f"HeatmapsLoss: shapes {tuple(pred.shape)}, {tuple(target.shape)}, {tuple(mask.shape)} do not match")
         loss = torch.empty((), device=p.device, dtype=torch.float32)
@@ -117,10 +122,12 @@ class _AEGroupingFn(torch.autograd.Function):
 
 class DeviceJoints:
     """The joints of a batch already packed and uploaded (`upload_joints`): lets a caller keep the host -> device copy out
-    of the step, e.g. to capture the whole training step in a hipGraph.  Not in the reference (it passes host lists)."""
+    of the step, e.g. to capture the whole training step in a hipGraph.  Not in the reference (it passes host lists).
+    `geometry` = the (K, h, w) whose range `pack_joints` checked the visible joints against: the kernel gathers unchecked, so
+    `AEGroupingLoss` takes the joints only with a tag map of exactly that geometry."""
 
-    def __init__(self, packed: Tensor, counts: Tensor):
-        self.packed, self.counts = packed, counts
+    def __init__(self, packed: Tensor, counts: Tensor, geometry: tuple[int, int, int]):
+        self.packed, self.counts, self.geometry = packed, counts, tuple(int(v) for v in geometry)
 
     def __len__(self) -> int:
         return int(self.counts.shape[0])
@@ -128,7 +135,7 @@ class DeviceJoints:
 
 def upload_joints(joints: list, K: int, h: int, w: int, device) -> DeviceJoints:
     packed, counts = pack_joints(joints, K, h, w)
-    return DeviceJoints(torch.from_numpy(packed).to(device), torch.from_numpy(counts).to(device))
+    return DeviceJoints(torch.from_numpy(packed).to(device), torch.from_numpy(counts).to(device), (K, h, w))
 
 
 class AEGroupingLoss(_Loss):
@@ -142,6 +149,8 @@ class AEGroupingLoss(_Loss):
             raise ValueError(f"joints has {len(joints)} entries for a batch of {B}")
         if not isinstance(joints, DeviceJoints):
             joints = upload_joints(joints, K, h, w, pred_tags.device)
+        elif joints.geometry != (K, h, w):
+            raise ValueError(f"joints were packed for (K, h, w) = {joints.geometry}, the tag map is {(K, h, w)}")
         return _AEGroupingFn.apply(pred_tags, joints.packed, joints.counts)
 
 

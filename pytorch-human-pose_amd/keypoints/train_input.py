@@ -232,7 +232,7 @@ class TrainInput:
             for i, s in enumerate(self.hm_sizes):
                 packed, counts = pack_joints(stage_joints[i], K, s, s)
                 self.last_h2d_bytes += packed.nbytes + counts.nbytes
-                dj = DeviceJoints(torch.from_numpy(packed).to(dev), torch.from_numpy(counts).to(dev))
+                dj = DeviceJoints(torch.from_numpy(packed).to(dev), torch.from_numpy(counts).to(dev), (K, s, s))
                 table, reach = self._tables_dev[i], self.tables[i][1]
                 _lib.check(lib.hh_render_heatmaps(dj.packed.data_ptr(), dj.counts.data_ptr(), B, packed.shape[1], K, table.data_ptr(),
                                                   table.shape[0], reach, heatmaps[i].data_ptr(), s, s, stream))
