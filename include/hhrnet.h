@@ -251,6 +251,50 @@ int hh_train_images_u8_batch(const unsigned char *batch_base, const hh_train_des
  * For a byte v, v / 255 > 0.5 is v >= 128, which is what the kernel tests.                                             */
 int hh_train_masks_u8_batch(const unsigned char *batch_base, const hh_train_desc *descs_dev, int n, int nstages, const int *stage_hw,
                             float *const *out, void *stream);
+/* The mosaic of the reference's training dataset (keypoints/datasets/coco.py:300-370, get_raw_mosaiced_data; applied with
+ * `mosaic_probability`, coco.py:459-462) composed on the device, for all mosaic samples of a batch in ONE launch.  For sample i,
+ * tile t (0 top-left, 1 top-right, 2 bottom-left, 3 bottom-right, coco.py:318-325) is resized to S x S and written at
+ * (s_y, s_x) = (S * (t / 2), S * (t % 2)): the image (uint8 RGB [h,w,3] at batch_base + image_offset) into the uint8 RGB
+ * [2S,2S,3] canvas at batch_base + canvas_image_offset, the crowd mask (uint8 [h,w], 0 / 255, at batch_base + mask_offset) into the
+ * uint8 [2S,2S] canvas at batch_base + canvas_mask_offset, which holds 255 where the resized mask is non-zero and 0 elsewhere
+ * (cv2.resize(mask * 255) > 0.5, coco.py:328, then (mask * 255).astype(np.uint8), transforms.py:159).  Every canvas byte is written
+ * exactly once; deterministic.  The canvases are ordinary sources of hh_train_images_u8_batch / hh_train_masks_u8_batch (a
+ * hh_train_desc with h = w = 2S pointing at them), launched afterwards on the same stream.
+ *
+ * The resize is cv2.resize(src, (S, S)): 8-bit INTER_LINEAR, restated from OpenCV 4.x modules/imgproc/src/resize.cpp (resize(),
+ * resizeGeneric_Invoker, HResizeLinear / VResizeLinear with INTER_RESIZE_COEF_BITS = 11).  cv2 is not available where the fixtures
+ * are made, so parity with cv2 itself is UNPINNED, as for the warp of hh_preprocess_u8; kernel, tests/cv_resize.py and the golden
+ * implement exactly this text (an OpenCV built with IPP or another HAL may take a different 8-bit path):
+ *   scale     per axis, scale = 1.0 / ((double)S / src) in double.
+ *   area      if h == 2S and w == 2S (both scales exactly 2) OpenCV switches to INTER_AREA: every output byte is
+ *             (a + b + c + d + 2) >> 2 of its 2 x 2 source block.  Needs BOTH axes at 2; one alone stays bilinear.
+ *             (The bilinear text below gives the same bytes there: all four weights are 1024 and every shift is exact.)
+ *   columns   fx = (float)((dx + 0.5) * scale_x - 0.5) (double product and difference, rounded separately, no fused multiply-add),
+ *             sx = floor(fx), fx -= sx (fp32); if sx < 0: sx = 0, fx = 0; if sx >= w - 1: sx = w - 1, fx = 0; taps sx and
+ *             min(sx + 1, w - 1) with the weights a0 = cvRound((1.f - fx) * 2048), a1 = cvRound(fx * 2048) as shorts (cvRound: to
+ *             nearest, half to even); horizontal result H = src[sx] * a0 + src[sx + 1] * a1, an int.
+ *   rows      fy, sy formed the same way from dy, scale_y and h, but fy is NOT zeroed at the borders: the two row indices sy and
+ *             sy + 1 are clamped into [0, h - 1]; weights b0 = cvRound((1.f - fy) * 2048), b1 = cvRound(fy * 2048).
+ *   vertical  with H0, H1 the horizontal results of the two rows:
+ *             dst = (uint8)((((b0 * (H0 >> 4)) >> 16) + ((b1 * (H1 >> 4)) >> 16) + 2) >> 2).
+ * Validation: `descs_dev` is the DEVICE array the kernel reads; `descs_host` is the caller's HOST copy of the same n descriptors, and
+ *   it is what is checked (device memory is never read back).  Returns 1 with hh_last_error set, before any launch, for a null
+ *   pointer, n outside 1..65535, S outside 4..HH_MOSAIC_MAX_S or not a multiple of 4 (a thread stores four adjacent pixels as whole
+ *   dwords), a canvas offset that is negative or not a multiple of 4, a tile with h or w < 1 or h * w * 3 >= 2^31 (the kernel
+ *   indexes one tile's bytes with 32 bits), a negative tile offset.  batch_base itself must be 4-byte aligned.  That tiles and
+ *   canvases lie inside the caller's buffer and that no canvas overlaps a tile or another canvas cannot be checked here.
+ * (Additive entry point: HH_ABI_VERSION stays 3.)                                                                          */
+#define HH_MOSAIC_MAX_S 8192
+typedef struct hh_mosaic_tile {
+    long long image_offset, mask_offset; /* bytes from batch_base: raw uint8 RGB [h,w,3], crowd mask uint8 [h,w] 0 / 255 */
+    int h, w;
+} hh_mosaic_tile;
+typedef struct hh_mosaic_desc {
+    hh_mosaic_tile tile[4];                                /* top-left, top-right, bottom-left, bottom-right */
+    long long canvas_image_offset, canvas_mask_offset;     /* bytes from batch_base: uint8 [2S,2S,3] and uint8 [2S,2S] */
+} hh_mosaic_desc;
+int hh_mosaic_u8_batch(unsigned char *batch_base, const hh_mosaic_desc *descs_dev, const hh_mosaic_desc *descs_host, int n, int S,
+                       void *stream);
 /* HeatmapGenerator (coco.py:77-121) as a gather over the packed joints the grouping loss takes (hh_loss_ae_grouping: joints int32
  * [B,P,K,3] = x, y, vis from JointsGenerator, coco.py:124-137; num_people [B]): out fp32 [B,K,h,w], each element the maximum over
  * the image's people p < num_people[b] with vis > 0 and (x, y) inside the map of table[y - y_p + reach][x - x_p + reach] where that

@@ -254,6 +254,31 @@ int hh_resized_crop_u8_batch(const unsigned char *batch_base, const hh_crop_desc
     return 0;
 }
 
+int hh_mosaic_u8_batch(unsigned char *batch_base, const hh_mosaic_desc *descs_dev, const hh_mosaic_desc *descs_host, int n, int S, void *stream)
+{
+    static_assert(sizeof(hh_mosaic_desc) == sizeof(HHMosaicDesc) && sizeof(HHMosaicDesc) == 112 && sizeof(hh_mosaic_tile) == sizeof(HHMosaicTile), "descriptor layout");
+    const char *fn = "hh_mosaic_u8_batch";
+    if (!batch_base || !descs_dev || !descs_host) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if (n <= 0 || n > 65535) { hh_set_error(std::string(fn) + ": need 0 < n <= 65535"); return 1; }
+    if (S < 4 || S > HH_MOSAIC_MAX_S || S % 4) { hh_set_error(std::string(fn) + ": S must be a multiple of 4 in 4..8192"); return 1; }
+    if ((uintptr_t)batch_base % 4) { hh_set_error(std::string(fn) + ": batch_base must be 4-byte aligned"); return 1; }
+    for (int b = 0; b < n; ++b) {
+        const hh_mosaic_desc &d = descs_host[b];
+        const std::string who = std::string(fn) + ": sample " + std::to_string(b) + ": ";
+        if (d.canvas_image_offset < 0 || d.canvas_mask_offset < 0) { hh_set_error(who + "negative canvas offset"); return 1; }
+        if (d.canvas_image_offset % 4 || d.canvas_mask_offset % 4) { hh_set_error(who + "canvas offsets must be multiples of 4"); return 1; }
+        for (int t = 0; t < 4; ++t) {
+            const hh_mosaic_tile &q = d.tile[t];
+            const std::string tile = who + "tile " + std::to_string(t) + ": ";
+            if (q.h < 1 || q.w < 1) { hh_set_error(tile + "non-positive extent"); return 1; }
+            if ((int64_t)q.h * q.w * 3 > INT32_MAX) { hh_set_error(tile + "beyond 32-bit byte indexing (h * w * 3 >= 2^31)"); return 1; }
+            if (q.image_offset < 0 || q.mask_offset < 0) { hh_set_error(tile + "negative offset"); return 1; }
+        }
+    }
+    HH_CHECK_HIP(launch_mosaic(batch_base, reinterpret_cast<const HHMosaicDesc *>(descs_dev), n, S, (hipStream_t)stream));
+    return 0;
+}
+
 int hh_heatmap_table_size(double sigma, int *n, int *reach)
 {
     if (!n || !reach) { hh_set_error("hh_heatmap_table_size: null pointer"); return 1; }

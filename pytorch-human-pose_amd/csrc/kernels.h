@@ -348,6 +348,11 @@ struct HHCropDesc {
 };
 hipError_t launch_resized_crop(const unsigned char *base, const HHCropDesc *descs, int n, float *out, int H, int W, const float mean[3],
                                const float stdv[3], hipStream_t s);
+// The mosaic of the training input (hh_mosaic_desc of include/hhrnet.h, train_mosaic.hip): four raw tiles (image + crowd mask) and the
+// two canvases they are resized into, all as byte offsets from the batch's base pointer.  112 bytes.
+struct HHMosaicTile { long long image_offset, mask_offset; int h, w; };
+struct HHMosaicDesc { HHMosaicTile tile[4]; long long canvas_image_offset, canvas_mask_offset; };
+hipError_t launch_mosaic(unsigned char *base, const HHMosaicDesc *descs, int n, int S, hipStream_t s);
 // target heatmaps from the packed joints (train_input.hip); n = table side = 2 * reach + 1 <= HH_RENDER_MAX_N, w <= HH_RENDER_MAX_W
 #define HH_RENDER_MAX_N 63
 #define HH_RENDER_MAX_W 4096

@@ -6,4 +6,4 @@ from .results import InferenceKeypointsResult, KeypointsResult
 __all__ = ["HigherHRNet", "MPPEHeatmapParser", "InferenceKeypointsModel", "InferenceKeypointsResult", "KeypointsModel", "KeypointsModule"]
 from .loss import AEGroupingLoss, AEKeypointsLoss, HeatmapsLoss
 from . import coco_eval, evaluation, targets
-from .train_input import TrainInput
+from .train_input import Mosaic, TrainInput, mosaic_joints

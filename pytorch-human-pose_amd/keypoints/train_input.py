@@ -11,6 +11,13 @@ Raw pixels, masks and descriptors cross in ONE host->device copy from a pinned, 
 `KeypointsModule.training_step` / `AEKeypointsLoss.calculate_loss` take: (images, [heatmaps], [masks], [DeviceJoints]).
 There is no CPU path.  The warp is the project's restatement of cv2.warpAffine (parity with cv2 itself UNPINNED, as for
 hh_preprocess_u8).
+
+The mosaic of the reference's dataset (`mosaic_probability`, src/keypoints/config.py:44; coco.py:459-462 and :300-370
+get_raw_mosaiced_data) is part of it: a `Mosaic` entry of the batch ships its four raw tiles in the same copy, ONE
+hh_mosaic_u8_batch launch resizes them into a 2S x 2S image canvas and mask canvas behind the staged bytes on the device (S =
+out_size), and the two warp launches read those canvases like any raw sample.  The joints of the four tiles are shifted and scaled
+on the host (`mosaic_joints`).  The resize is the project's restatement of cv2.resize's 8-bit INTER_LINEAR (include/hhrnet.h;
+parity with cv2 itself UNPINNED as well).
 """
 from __future__ import annotations
 
@@ -30,6 +37,10 @@ MAX_STAGES = 4  # HH_TRAIN_MAX_STAGES
 _TRAIN_DESC = np.dtype([("image_offset", "<i8"), ("mask_offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("flip", "<i4"), ("reserved", "<i4"),
                         ("inv_image", "<f8", (6,)), ("inv_mask", "<f8", (MAX_STAGES, 6))])
 assert _TRAIN_DESC.itemsize == 272
+# hh_mosaic_desc of include/hhrnet.h (112 bytes)
+_MOSAIC_TILE = np.dtype([("image_offset", "<i8"), ("mask_offset", "<i8"), ("h", "<i4"), ("w", "<i4")])
+_MOSAIC_DESC = np.dtype([("tile", _MOSAIC_TILE, (4,)), ("canvas_image_offset", "<i8"), ("canvas_mask_offset", "<i8")])
+assert _MOSAIC_DESC.itemsize == 112
 
 
 @dataclass
@@ -40,6 +51,33 @@ class AugParams:
     rot: float
     center: tuple
     flip: bool
+
+
+class Mosaic:
+    """A batch entry of `TrainInput.build` that stands where a raw sample may stand: four raw samples (image, mask, joints) that are
+    resized to out_size x out_size each and tiled top-left, top-right, bottom-left, bottom-right (coco.py:318-325)."""
+
+    def __init__(self, tiles):
+        self.tiles = list(tiles)
+        if len(self.tiles) != 4:
+            raise ValueError("Mosaic: exactly four raw samples")
+
+
+def mosaic_joints(tiles, S: int, num_kpts: int = 17) -> np.ndarray:
+    """The joints of get_raw_mosaiced_data (coco.py:330-342) followed by get_coco_joints (:68-74): per tile x * (S / w) + s_x,
+    y * (S / h) + s_y, rows with vis <= 0 zeroed, the four tiles' people concatenated in tile order -> float64 [P_total,K,3].  The
+    assignment is numpy's, as in the reference: joints given as an INTEGER array (COCO's annotations) are truncated toward zero,
+    joints given as a float array are not.  The tiles' arrays are not modified."""
+    out = [np.zeros((0, num_kpts, 3))]
+    for i, (img, _, joints) in enumerate(tiles):
+        h, w = np.asarray(img).shape[:2]
+        k = np.array(joints).reshape(-1, num_kpts, 3)  # a copy that keeps the dtype
+        hidden = k[:, :, 2] <= 0
+        k[:, :, 0] = k[:, :, 0] * (S / w) + (i % 2) * S
+        k[:, :, 1] = k[:, :, 1] * (S / h) + (i // 2) * S
+        k[hidden] = k[hidden] * 0
+        out.append(k.astype(np.float64))
+    return np.concatenate(out)
 
 
 def affine_matrix(center, scale: float, res, rot: float = 0) -> np.ndarray:
@@ -103,9 +141,27 @@ class _Mode:
         flip = self.flip_p is not None and random.random() < self.flip_p
         return AugParams(float(scale), float(rot), (float(center[0]), float(center[1])), bool(flip))
 
-    def __call__(self, samples):
-        params = [self.draw(*np.asarray(s[0]).shape[:2]) for s in samples]
-        return self.owner.build(samples, params)
+    def choose(self, samples, pool=None):
+        """The per-item draws of the reference's dataset and transform in its order (coco.py:459, :305, then `draw`): with
+        mosaic_probability > 0 one random.random() per sample, for a mosaic three random.randint(0, len(pool) - 1) (the sample
+        itself is tile 0, repeats are allowed) and the augmentation of a 2S x 2S image.  -> (entries for `build`, [AugParams]).
+        With mosaic_probability == 0 no extra draw is made (the reference draws random.random() even then: a stated deviation that
+        keeps the draws of the existing path)."""
+        prob, S = self.owner.mosaic_probability, self.owner.out_size
+        if prob > 0 and pool is None:
+            raise ValueError("TrainInput: mosaic_probability > 0 needs a pool of raw samples: .train(samples, pool)")
+        entries, params = [], []
+        for s in samples:
+            if prob > 0 and random.random() < prob:
+                s = Mosaic([s] + [pool[random.randint(0, len(pool) - 1)] for _ in range(3)])
+                params.append(self.draw(2 * S, 2 * S))
+            else:
+                params.append(self.draw(*np.asarray(s[0]).shape[:2]))
+            entries.append(s)
+        return entries, params
+
+    def __call__(self, samples, pool=None):
+        return self.owner.build(*self.choose(samples, pool))
 
 
 class TrainInput:
@@ -117,13 +173,19 @@ class TrainInput:
         module.training_step(batch)
 
     `.train(samples)` / `.inference(samples)` draw the augmentation per sample (inference: no rotation / scale / translate /
-    flip) and call `build(samples, params)`, the explicit-parameter entry."""
+    flip) and call `build(samples, params)`, the explicit-parameter entry.
+
+    `mosaic_probability` is the field of the reference's dataset (both modes honour it: the dataset decides, not the transform).
+    With a value > 0 a mode is called as `ti.train(samples, pool)`: `pool` is any object with len() and [i] -> (image, mask, joints)
+    raw samples (the reference's get_raw_data), from which the three other tiles of a mosaic are drawn.  `build` takes a
+    `Mosaic(tiles)` wherever it takes a raw sample."""
 
     def __init__(self, out_size: int, hm_resolutions, max_rotation: int = 30, min_scale: float = 0.75, max_scale: float = 1.5,
                  scale_type: str = "short", max_translate: int = 40, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
-                 num_kpts: int = 17, sigma: float = 2, flip_index=COCO_FLIP_INDEX, device="cuda:0"):
+                 num_kpts: int = 17, sigma: float = 2, flip_index=COCO_FLIP_INDEX, device="cuda:0", mosaic_probability: float = 0.0):
         assert scale_type in ("short", "long"), f"unknown scale type: {scale_type}"
         self.out_size, self.scale_type, self.num_kpts, self.device = int(out_size), scale_type, num_kpts, device
+        self.mosaic_probability = float(mosaic_probability)
         self.hm_sizes = [int(r * out_size) for r in hm_resolutions]
         if not 0 < len(self.hm_sizes) <= MAX_STAGES:
             raise _lib.HHError(f"TrainInput: 1..{MAX_STAGES} heatmap stages, got {len(self.hm_sizes)}")
@@ -173,8 +235,9 @@ class TrainInput:
         return t, self._stage[t]
 
     def build(self, samples, params):
-        """samples: [(uint8 [h,w,3] image, bool [h,w] crowd mask, float [P,K,3] joints)], params: [AugParams] ->
-        (images [B,3,S,S], [heatmaps [B,K,s,s]], [masks [B,s,s]], [DeviceJoints]) on the device, in the current stream."""
+        """samples: [(uint8 [h,w,3] image, bool [h,w] crowd mask, float [P,K,3] joints) or Mosaic of four of them], params: [AugParams]
+        (of a 2S x 2S image for a Mosaic) -> (images [B,3,S,S], [heatmaps [B,K,s,s]], [masks [B,s,s]], [DeviceJoints]) on the device,
+        in the current stream."""
         import torch
         lib = _lib.load()
         B, S, K, nst = len(samples), self.out_size, self.num_kpts, len(self.hm_sizes)
@@ -183,39 +246,66 @@ class TrainInput:
         dp = C.POINTER(C.c_double)
         invert = lambda m: self._invert(lib, m, dp)  # noqa: E731
 
-        shapes = []
-        for img, mask, _ in samples:
-            if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or mask.shape != img.shape[:2]:
-                raise ValueError("TrainInput.build: uint8 [h,w,3] images with [h,w] crowd masks only")
-            shapes.append(img.shape[:2])
+        # what travels: every raw sample once, a Mosaic's four tiles in its place (images first, then masks, as before)
+        raws, slots = [], []  # slots[b]: index into raws, or the four indices of a Mosaic's tiles
+        for entry in samples:
+            tiles = entry.tiles if isinstance(entry, Mosaic) else [entry]
+            for img, mask, _ in tiles:
+                if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or mask.shape != img.shape[:2]:
+                    raise ValueError("TrainInput.build: uint8 [h,w,3] images with [h,w] crowd masks only")
+            first = len(raws)
+            raws.extend(tiles)
+            slots.append(list(range(first, first + 4)) if isinstance(entry, Mosaic) else first)
+        R, M = len(raws), sum(isinstance(e, Mosaic) for e in samples)
+        shapes = [img.shape[:2] for img, _, _ in raws]
         sizes = [h * w * 3 for h, w in shapes] + [h * w for h, w in shapes]
         offs = np.cumsum([0] + sizes)
         desc_off = (int(offs[-1]) + 63) // 64 * 64  # the descriptors travel behind the pixels and masks, in the same copy
-        total = desc_off + _TRAIN_DESC.itemsize * B
+        mosaic_off = desc_off + _TRAIN_DESC.itemsize * B
+        total = mosaic_off + _MOSAIC_DESC.itemsize * M
+        # the canvases of the mosaic samples lie behind the staged bytes in the device buffer; nothing of them is copied
+        canvas_off = (total + 63) // 64 * 64
+        if M and (S % 4 or S < 4):
+            raise _lib.HHError("TrainInput.build: a mosaic needs an out_size that is a multiple of 4 (hh_mosaic_u8_batch)")
         turn, host = self._staging(total)
         hview = host.numpy()
-        descs = hview[desc_off:total].view(_TRAIN_DESC)
-        stage_joints = [[] for _ in range(nst)]
-        for b, ((img, mask, joints), p) in enumerate(zip(samples, params)):
-            h, w = shapes[b]
-            np.copyto(hview[offs[b]:offs[b + 1]].reshape(h, w, 3), img)
-            mview = hview[offs[B + b]:offs[B + b + 1]].reshape(h, w)
+        descs = hview[desc_off:mosaic_off].view(_TRAIN_DESC)
+        mdescs = hview[mosaic_off:total].view(_MOSAIC_DESC)
+        for r, (img, mask, _) in enumerate(raws):
+            h, w = shapes[r]
+            np.copyto(hview[offs[r]:offs[r + 1]].reshape(h, w, 3), img)
+            mview = hview[offs[R + r]:offs[R + r + 1]].reshape(h, w)
             np.multiply(mask, 255, out=mview, casting="unsafe")  # (mask * 255).astype(np.uint8), transforms.py:159
+        stage_joints = [[] for _ in range(nst)]
+        m = 0
+        for b, (entry, p) in enumerate(zip(samples, params)):
+            if isinstance(entry, Mosaic):
+                image_at, mask_at = canvas_off + m * 16 * S * S, canvas_off + m * 16 * S * S + 12 * S * S
+                mdescs[m] = ([(int(offs[r]), int(offs[R + r]), *shapes[r]) for r in slots[b]], image_at, mask_at)
+                h = w = 2 * S
+                joints = mosaic_joints(entry.tiles, S, K)
+                m += 1
+            else:
+                image_at, mask_at, (h, w), joints = int(offs[slots[b]]), int(offs[R + slots[b]]), shapes[slots[b]], entry[2]
             mat_image, mats, _, ints = self.geometry(h, w, joints, p)
             inv_mask = np.zeros((MAX_STAGES, 6))
-            for i, m in enumerate(mats):
-                inv_mask[i] = invert(m)
+            for i, mat in enumerate(mats):
+                inv_mask[i] = invert(mat)
                 stage_joints[i].append(ints[i])
-            descs[b] = (int(offs[b]), int(offs[B + b]), h, w, int(p.flip), 0, invert(mat_image), inv_mask)
+            descs[b] = (image_at, mask_at, h, w, int(p.flip), 0, invert(mat_image), inv_mask)
 
         dev = torch.device(self.device)
         with torch.cuda.device(dev):
             cur = torch.cuda.current_stream(dev)
-            raw = host[:total].to(dev, non_blocking=True)
+            if M:
+                raw = torch.empty(canvas_off + M * 16 * S * S, device=dev, dtype=torch.uint8)
+                raw[:total].copy_(host[:total], non_blocking=True)
+            else:
+                raw = host[:total].to(dev, non_blocking=True)
             copied = torch.cuda.Event()
             copied.record(cur)
             self._stage_free[turn] = copied
-            self.last_h2d_bytes, self.last_launches = total, 2 + nst
+            self.last_h2d_bytes, self.last_launches = total, 2 + nst + (1 if M else 0)
             if self._tables_dev is None:
                 self._tables_dev = [torch.from_numpy(t).to(dev) for t, _ in self.tables]
             images = torch.empty((B, 3, S, S), device=dev, dtype=torch.float32)
@@ -223,6 +313,8 @@ class TrainInput:
             heatmaps = [torch.empty((B, K, s, s), device=dev, dtype=torch.float32) for s in self.hm_sizes]
             fp = C.POINTER(C.c_float)
             base, stream = raw.data_ptr(), cur.cuda_stream
+            if M:  # the canvases first: the two warp launches below read them
+                _lib.check(lib.hh_mosaic_u8_batch(base, base + mosaic_off, mdescs.ctypes.data, M, S, stream))
             _lib.check(lib.hh_train_images_u8_batch(base, base + desc_off, B, images.data_ptr(), S, S, self.mean.ctypes.data_as(fp),
                                                     self.std.ctypes.data_as(fp), stream))
             stage_hw = (C.c_int * (2 * nst))(*[s for s in self.hm_sizes for _ in range(2)])
