@@ -295,6 +295,86 @@ typedef struct hh_mosaic_desc {
 } hh_mosaic_desc;
 int hh_mosaic_u8_batch(unsigned char *batch_base, const hh_mosaic_desc *descs_dev, const hh_mosaic_desc *descs_host, int n, int S,
                        void *stream);
+/* Pose overlays: plot_connections (keypoints/visualization.py:43-90, with draw_elipsis :13-40) for n frames of mixed sizes in ONE
+ * launch, on the raw uint8 RGB frames that are on the device for hh_preprocess_u8 anyway.  The host forms the primitive table
+ * (keypoints/visualization.py build_primitives here); the kernel does the per-pixel work; the result is bit-identical to this text
+ * (tests/render_ref.py restates it in numpy).
+ *
+ * The drawing rule.  plot_connections(image, coords [P,K,2], scores [P,K], limbs, thr, color_mode, alpha) makes connections_image =
+ * image.copy() and draws into it, a later primitive overwriting an earlier one:
+ *   for person i ascending: draw size s_i = max(2, int((max_k y - min_k y) / 100)) over ALL K keypoints, drawn or not;
+ *     its limbs j ascending (skipped if either end has score < thr), one filled ellipse each;
+ *     then its keypoints j ascending (skipped if score < thr; a score equal to thr is drawn), each a filled disc of radius s_i in the
+ *     colour followed by a black ring of radius s_i + 1.  Scores and thr are compared as float64.
+ *   Coordinates are int() of the float64 value (truncated toward zero).  Colour: palette[i] in mode "person"; in mode "limb"
+ *   palette[j], j the limb index for limbs and the keypoint index for keypoints.
+ * Then out = addWeighted(image, 1 - alpha, connections_image, alpha, 0) over every pixel, covered or not.
+ * Rasterisation (this project's rule; all centres and radii are integers; pixel (x, y), dx = x - cx, dy = y - cy):
+ *   disc     radius r: inside iff dx^2 + dy^2 <= r^2 + r (radius r + 1/2).  Exact in int32.
+ *   ring     the reference's circle(radius R = r + 1, thickness 1, black): inside iff R^2 - R < dx^2 + dy^2 <= R^2 + R.  Exact in int32.
+ *   ellipse  draw_elipsis on the truncated ends (x1, y1), (x2, y2): centre ((x1 + x2) // 2, (y1 + y2) // 2) with Python's floor
+ *            division; Dx = x2 - x1, Dy = y2 - y1; hyp = sqrt(Dx^2 + Dy^2) in float64, dist = int(hyp).  If |Dx| > |Dy|:
+ *            (a, b) = (dist // 2, s_i) and (c, s) = (Dx, Dy) / hyp; otherwise (a, b) = (s_i, dist // 2) and (c, s) = (Dy, -Dx) / hyp;
+ *            (c, s) = (1, 0) when hyp == 0.  (The reference's arctan2 angle without a libm call: sqrt and division are correctly
+ *            rounded, so the table is the same on every machine.)  c and s are rounded once to fp32.  With A = 2a + 1, B = 2b + 1
+ *            (semi-axes a + 1/2 and b + 1/2: a zero axis still draws a line one pixel wide), every operation in fp32, rounded on
+ *            its own, in this order:  fx = (float)dx, fy = (float)dy;  u = fx * c + fy * s;  v = fy * c - fx * s;
+ *            p = (2 * u) * B;  q = (2 * v) * A;  lhs = p * p + q * q;  ab = A * B;  rhs = ab * ab;  inside iff lhs <= rhs.
+ *   blend    per channel rintf(img * w0 + conn * w1) in fp32, the two products and the sum rounded separately, clamped to 0..255;
+ *            w0 = (float)(1.0 - alpha), w1 = (float)alpha, both formed in double on the host.
+ *   Primitives are clipped to the frame; centres may lie outside it and may be negative.
+ * Stated deviation from OpenCV: cv2.ellipse rounds the angle to whole degrees and fills a polygon approximation (ellipse2Poly),
+ *   cv2.circle is a midpoint circle.  Parity of the covered pixel set with cv2 itself is therefore UNPINNED: it differs on boundary
+ *   pixels only; the size of that difference is not measured, and cv2 is not available where the fixtures are made.  Everything in
+ *   front of the rasteriser IS pinned to the reference by tests/golden/render.npz, written by the reference's own plot_connections
+ *   with recording stand-ins for cv2.ellipse / circle / addWeighted: which primitives, in what order, where, how large, which colour,
+ *   the thresholds, the truncations and the blend weights.
+ *
+ * The primitive table: hh_render_prim rows of 32 bytes, in draw order.  kind: HH_RENDER_DISC (A = B = r), HH_RENDER_RING (A = B = R), HH_RENDER_ELLIPSE (A, B, c, s
+ *   as above).  (x0, y0)..(x1, y1) is an inclusive bounding box clipped to 0..16383 that must contain every pixel of the primitive
+ *   that can lie in a frame; it is empty (x1 < x0 or y1 < y0) for a primitive wholly outside.  Pixels outside the box are not drawn.
+ * The frame descriptors: one hh_render_desc of 48 bytes per frame: the RGB source [h,w,3] at batch_base + src_offset, the output [h,w,3] at batch_base +
+ *   dst_offset (another place than any source), the frame's primitives table[prim_offset .. prim_offset + prim_count), the blend
+ *   weights, flags bit 0 = store B,G,R instead of R,G,B.  Every output byte is written exactly once, also for prim_count == 0;
+ *   deterministic.  Descriptors and table are meant to travel to the device in one copy (the binding does so).
+ * Validation: the *_dev arrays are what the kernel reads, the *_host arrays the caller's HOST copies of the same data, and those are
+ *   what is checked (device memory is never read back).  Returns 1 with hh_last_error set, before any launch, for a null pointer,
+ *   n outside 1..65535, num_prims < 0, descs_dev not 8-byte or prims_dev not 4-byte aligned, a frame with h or w outside 1..16384, a
+ *   negative offset, a primitive range outside [0, num_prims), more than HH_RENDER_MAX_PRIMS primitives in one frame (refused, never
+ *   capped), a weight that is not finite, an unknown flag or kind, A or B < 1, a disc or ring radius above 32767, a centre beyond
+ *   +-2^23, a box outside 0..16383 or reaching further from the centre than 32767 (disc, ring) or 65536 (ellipse): inside the box
+ *   dx^2 + dy^2 stays below 2^31 and (float)dx is exact.  That frames lie inside the caller's buffer cannot be checked here.
+ * hh_render_config: out[4] = tile height, tile width, primitives culled per chunk, pixels per thread (a workgroup owns one tile and
+ *   walks the frame's primitives a chunk at a time, keeping the draw order within and across chunks).
+ * hh_debug_render_host: one frame through the same tile walk compiled for the host (src, dst: the frame's own HOST buffers; the
+ *   descriptor's offsets are ignored); same validation.  For tests and tools/render_host_check.cpp.
+ * hh_resize_u8: cv2.resize(src, (W, H)) for a uint8 [h,w] (channels = 1) or [h,w,3] (channels = 3) device array, the general form of
+ *   the resize stated at hh_mosaic_u8_batch above with S replaced by W on the columns and H on the rows: INTER_LINEAR with 11-bit
+ *   weights and the 2 x 2 mean iff h == 2H and w == 2W.  Every side in 1..HH_RESIZE_MAX_SIDE; no alignment requirement (dword stores
+ *   where a thread's four pixels are 4-byte aligned, bytes otherwise).  Every output byte is written exactly once; deterministic.
+ * (Additive entry points: HH_ABI_VERSION stays 3.)                                                                           */
+#define HH_RENDER_MAX_PRIMS 4096 /* per frame; 30 people x (19 limbs + 2 x 17 keypoints) = 1590 */
+#define HH_RESIZE_MAX_SIDE 16384
+enum { HH_RENDER_DISC = 0, HH_RENDER_RING = 1, HH_RENDER_ELLIPSE = 2 };
+typedef struct hh_render_prim {
+    int32_t cx, cy;
+    uint16_t A, B;
+    float c, s;
+    uint8_t r, g, b, kind;
+    int16_t x0, y0, x1, y1;
+} hh_render_prim;
+typedef struct hh_render_desc {
+    long long src_offset, dst_offset;
+    int32_t h, w;
+    int32_t prim_offset, prim_count;
+    float w0, w1;
+    int32_t flags, reserved;
+} hh_render_desc;
+int hh_render_poses_u8_batch(unsigned char *batch_base, const hh_render_desc *descs_dev, const hh_render_desc *descs_host,
+                             const hh_render_prim *prims_dev, const hh_render_prim *prims_host, int num_prims, int n, void *stream);
+int hh_render_config(int out[4]);
+int hh_debug_render_host(const unsigned char *src, unsigned char *dst, const hh_render_desc *desc, const hh_render_prim *prims, int num_prims);
+int hh_resize_u8(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, void *stream);
 /* HeatmapGenerator (coco.py:77-121) as a gather over the packed joints the grouping loss takes (hh_loss_ae_grouping: joints int32
  * [B,P,K,3] = x, y, vis from JointsGenerator, coco.py:124-137; num_people [B]): out fp32 [B,K,h,w], each element the maximum over
  * the image's people p < num_people[b] with vis > 0 and (x, y) inside the map of table[y - y_p + reach][x - x_p + reach] where that

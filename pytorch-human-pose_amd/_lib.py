@@ -77,6 +77,10 @@ def _sig(lib):
         "hh_train_masks_u8_batch": (i32, [vp, vp, i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_void_p), vp]),
         "hh_resized_crop_u8_batch": (i32, [vp, vp, vp, i32, vp, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), vp]),
         "hh_mosaic_u8_batch": (i32, [vp, vp, vp, i32, i32, vp]),
+        "hh_render_poses_u8_batch": (i32, [vp, vp, vp, vp, vp, i32, i32, vp]),
+        "hh_render_config": (i32, [C.POINTER(C.c_int)]),
+        "hh_debug_render_host": (i32, [vp, vp, vp, vp, i32]),
+        "hh_resize_u8": (i32, [vp, i32, i32, i32, vp, i32, i32, vp]),
         "hh_heatmap_table_size": (i32, [dbl, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "hh_render_heatmaps": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp]),
         "hh_flip_images": (i32, [vp, vp, i32, i32, i32, i32, vp]),

@@ -8,6 +8,7 @@
 #include "../../include/hhrnet.h"
 #include "engine.h"
 #include "optim_math.h"
+#include "render_math.h"
 
 const char *hh_get_error();
 int hh_tap_read_impl(hh_net *n, int index, float *host);
@@ -276,6 +277,71 @@ int hh_mosaic_u8_batch(unsigned char *batch_base, const hh_mosaic_desc *descs_de
         }
     }
     HH_CHECK_HIP(launch_mosaic(batch_base, reinterpret_cast<const HHMosaicDesc *>(descs_dev), n, S, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_render_config(int out[4])
+{
+    if (!out) { hh_set_error("hh_render_config: null pointer"); return 1; }
+    out[0] = RENDER_TH, out[1] = RENDER_TW, out[2] = RENDER_CHUNK, out[3] = RENDER_PX;
+    return 0;
+}
+
+// The checks of a render call that need no device: every frame's descriptor and its primitives, on the caller's host copy.
+static int render_check(const char *fn, const hh_render_desc *descs_host, const hh_render_prim *prims_host, int num_prims, int n, int *max_tiles)
+{
+    static_assert(sizeof(hh_render_desc) == sizeof(RenderDesc) && sizeof(hh_render_prim) == sizeof(RenderPrim), "table layout");
+    if (n <= 0 || n > 65535) { hh_set_error(std::string(fn) + ": need 0 < n <= 65535"); return 1; }
+    if (num_prims < 0) { hh_set_error(std::string(fn) + ": negative table length"); return 1; }
+    int tiles = 1;
+    for (int b = 0; b < n; ++b) {
+        const RenderDesc &d = reinterpret_cast<const RenderDesc *>(descs_host)[b];
+        if (d.prim_count > 0 && !prims_host) { hh_set_error(std::string(fn) + ": null primitive table"); return 1; }
+        const char *why = render_check_frame(d, reinterpret_cast<const RenderPrim *>(prims_host), num_prims, HH_RENDER_MAX_PRIMS);
+        if (why) { hh_set_error(std::string(fn) + ": frame " + std::to_string(b) + ": " + why); return 1; }
+        const int t = ((d.h + RENDER_TH - 1) / RENDER_TH) * ((d.w + RENDER_TW - 1) / RENDER_TW);
+        tiles = t > tiles ? t : tiles;
+    }
+    *max_tiles = tiles;
+    return 0;
+}
+
+int hh_render_poses_u8_batch(unsigned char *batch_base, const hh_render_desc *descs_dev, const hh_render_desc *descs_host,
+                             const hh_render_prim *prims_dev, const hh_render_prim *prims_host, int num_prims, int n, void *stream)
+{
+    const char *fn = "hh_render_poses_u8_batch";
+    if (!batch_base || !descs_dev || !descs_host || (num_prims > 0 && (!prims_dev || !prims_host))) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if ((uintptr_t)descs_dev % 8 || (uintptr_t)prims_dev % 4) { hh_set_error(std::string(fn) + ": descs_dev must be 8-byte and prims_dev 4-byte aligned"); return 1; }
+    int max_tiles = 0;
+    if (render_check(fn, descs_host, prims_host, num_prims, n, &max_tiles)) return 1;
+    HH_CHECK_HIP(launch_render_poses(batch_base, reinterpret_cast<const RenderDesc *>(descs_dev), reinterpret_cast<const RenderPrim *>(prims_dev), n,
+                                     max_tiles, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_debug_render_host(const unsigned char *src, unsigned char *dst, const hh_render_desc *desc, const hh_render_prim *prims, int num_prims)
+{
+    const char *fn = "hh_debug_render_host";
+    if (!src || !dst || !desc) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    int max_tiles = 0;
+    if (render_check(fn, desc, prims, num_prims, 1, &max_tiles)) return 1;
+    RenderDesc d = *reinterpret_cast<const RenderDesc *>(desc);  // src and dst are the frame's own buffers here
+    d.src_offset = d.dst_offset = 0;
+    render_debug_host(src, dst, d, reinterpret_cast<const RenderPrim *>(prims));
+    return 0;
+}
+
+int hh_resize_u8(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, void *stream)
+{
+    const char *fn = "hh_resize_u8";
+    if (!src || !dst) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if (channels != 1 && channels != 3) { hh_set_error(std::string(fn) + ": channels must be 1 or 3"); return 1; }
+    if (h < 1 || w < 1 || H < 1 || W < 1 || h > HH_RESIZE_MAX_SIDE || w > HH_RESIZE_MAX_SIDE || H > HH_RESIZE_MAX_SIDE || W > HH_RESIZE_MAX_SIDE) {
+        hh_set_error(std::string(fn) + ": every side must lie in 1..16384");
+        return 1;
+    }
+    // (with sides <= 16384 and 3 channels both images stay below 2^31 bytes: the kernel indexes the source with 32 bits)
+    HH_CHECK_HIP(launch_resize_u8(src, h, w, channels, dst, H, W, (hipStream_t)stream));
     return 0;
 }
 

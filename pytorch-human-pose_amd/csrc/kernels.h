@@ -353,6 +353,13 @@ hipError_t launch_resized_crop(const unsigned char *base, const HHCropDesc *desc
 struct HHMosaicTile { long long image_offset, mask_offset; int h, w; };
 struct HHMosaicDesc { HHMosaicTile tile[4]; long long canvas_image_offset, canvas_mask_offset; };
 hipError_t launch_mosaic(unsigned char *base, const HHMosaicDesc *descs, int n, int S, hipStream_t s);
+// Pose overlays (hh_render_desc / hh_render_prim of include/hhrnet.h; structs and arithmetic in render_math.h, kernels in render.hip):
+// n frames in one launch, `max_tiles` = the largest frame's tile count; the same walk on the host for one frame; the general 8-bit resize.
+struct RenderDesc;
+struct RenderPrim;
+hipError_t launch_render_poses(unsigned char *base, const RenderDesc *descs, const RenderPrim *prims, int n, int max_tiles, hipStream_t s);
+void render_debug_host(const unsigned char *src, unsigned char *dst, const RenderDesc &d, const RenderPrim *prims);
+hipError_t launch_resize_u8(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, hipStream_t s);
 // target heatmaps from the packed joints (train_input.hip); n = table side = 2 * reach + 1 <= HH_RENDER_MAX_N, w <= HH_RENDER_MAX_W
 #define HH_RENDER_MAX_N 63
 #define HH_RENDER_MAX_W 4096

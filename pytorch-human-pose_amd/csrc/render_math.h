@@ -1,0 +1,140 @@
+// The arithmetic of the pose overlay (render.hip; the drawing rule is stated at hh_render_poses_u8_batch in include/hhrnet.h), kept
+// apart from the kernel so that the same text also compiles for the host (hh_debug_render_host, tools/render_host_check.cpp): the
+// primitive and frame descriptors, the tile cull, the inside test of the three primitive kinds, the blend, and a whole frame walked
+// tile by tile in plain loops.  Compile with -ffp-contract=off: every fp32 operation below rounds on its own.
+#ifndef HH_RENDER_MATH_H
+#define HH_RENDER_MATH_H
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define HH_RHD __host__ __device__ __forceinline__
+#else
+#define HH_RHD inline
+#endif
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+
+enum { RENDER_DISC = 0, RENDER_RING = 1, RENDER_ELLIPSE = 2 };  // HH_RENDER_DISC / _RING / _ELLIPSE of include/hhrnet.h
+// The launch geometry, reported by hh_render_config: a workgroup of RENDER_TW / RENDER_PX x RENDER_TH threads owns one RENDER_TH x
+// RENDER_TW tile of the output, a thread RENDER_PX horizontally adjacent pixels of it; the frame's primitives are culled against the
+// tile RENDER_CHUNK at a time, one per lane.
+enum { RENDER_TH = 16, RENDER_TW = 64, RENDER_PX = 4, RENDER_THREADS = RENDER_TH * RENDER_TW / RENDER_PX, RENDER_CHUNK = RENDER_THREADS };
+static_assert(RENDER_THREADS == 256 && RENDER_TW % RENDER_PX == 0, "one lane per primitive of a chunk, whole pixel groups per tile row");
+
+// hh_render_prim of include/hhrnet.h (32 bytes).
+struct RenderPrim {
+    int32_t cx, cy;              // centre, may lie outside the frame
+    uint16_t A, B;               // disc: A = B = r; ring: A = B = R; ellipse: A = 2a + 1, B = 2b + 1
+    float c, s;                  // ellipse: unit direction of the A axis, rounded once to fp32
+    uint8_t r, g, b, kind;       // colour as drawn into the RGB frame, RENDER_*
+    int16_t x0, y0, x1, y1;      // inclusive bounding box, clipped to 0..16383 (empty: x1 < x0 or y1 < y0)
+};
+// hh_render_desc of include/hhrnet.h (48 bytes).
+struct RenderDesc {
+    long long src_offset, dst_offset;  // bytes from batch_base: uint8 RGB [h,w,3] in, uint8 [h,w,3] out
+    int32_t h, w;
+    int32_t prim_offset, prim_count;   // this frame's primitives in the table, in draw order
+    float w0, w1;                      // (float)(1.0 - alpha), (float)alpha
+    int32_t flags, reserved;           // bit 0: store B,G,R
+};
+static_assert(sizeof(RenderPrim) == 32 && sizeof(RenderDesc) == 48, "table layout");
+
+// Does the primitive's box meet the tile [tx0, tx1] x [ty0, ty1] (inclusive, already inside the frame)?
+HH_RHD bool render_box_meets(const RenderPrim &p, int tx0, int ty0, int tx1, int ty1)
+{
+    return p.x0 <= tx1 && p.x1 >= tx0 && p.y0 <= ty1 && p.y1 >= ty0;
+}
+
+// Is pixel (x, y) inside the primitive?  The box is a superset of every kind's set (the host forms it with a margin beyond the fp32
+// rounding of the ellipse test), so testing it first changes nothing and keeps dx, dy small enough for the exact int32 forms:
+// |dx|, |dy| <= 32767 inside a disc's or ring's box (render_check_frame), dx^2 + dy^2 < 2^31; an ellipse's dx, dy are exact in fp32.
+HH_RHD bool render_inside(const RenderPrim &p, int x, int y)
+{
+    if (x < p.x0 || x > p.x1 || y < p.y0 || y > p.y1) return false;
+    const int dx = x - p.cx, dy = y - p.cy;
+    if (p.kind == RENDER_ELLIPSE) {
+        // one order, every operation rounded to fp32: u = dx c + dy s, v = dy c - dx s, (2u B)^2 + (2v A)^2 <= (A B)^2
+        const float fx = (float)dx, fy = (float)dy, Af = (float)p.A, Bf = (float)p.B;
+        const float t0 = fx * p.c, t1 = fy * p.s, t2 = fy * p.c, t3 = fx * p.s;
+        const float u = t0 + t1, v = t2 - t3;
+        const float pu = (2.f * u) * Bf, qv = (2.f * v) * Af;
+        const float pp = pu * pu, qq = qv * qv;
+        const float lhs = pp + qq;
+        const float ab = Af * Bf;
+        const float rhs = ab * ab;
+        return lhs <= rhs;
+    }
+    const int d2 = dx * dx + dy * dy, R = (int)p.A;
+    if (p.kind == RENDER_DISC) return d2 <= R * R + R;
+    return d2 > R * R - R && d2 <= R * R + R;  // RENDER_RING
+}
+
+// addWeighted on one channel: rintf(img w0 + conn w1), products and sum rounded separately, clamped to 0..255.
+HH_RHD uint8_t render_blend(uint8_t img, uint8_t conn, float w0, float w1)
+{
+    const float a = (float)img * w0, b = (float)conn * w1;
+    float v = rintf(a + b);
+    v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
+    return (uint8_t)(int)v;
+}
+
+// One frame on the host, in the kernel's own walk: tile by tile, the primitives culled chunk by chunk into a list in draw order, every
+// pixel walking the list with the last hit winning, then blended.  `list` is the caller's scratch of RENDER_CHUNK entries.
+inline void render_frame_host(const uint8_t *src, uint8_t *dst, const RenderDesc &d, const RenderPrim *prims, RenderPrim *list)
+{
+    const int h = d.h, w = d.w;
+    for (int ty0 = 0; ty0 < h; ty0 += RENDER_TH)
+        for (int tx0 = 0; tx0 < w; tx0 += RENDER_TW) {
+            const int ty1 = (ty0 + RENDER_TH < h ? ty0 + RENDER_TH : h) - 1, tx1 = (tx0 + RENDER_TW < w ? tx0 + RENDER_TW : w) - 1;
+            uint8_t conn[RENDER_TH][RENDER_TW][3];
+            for (int y = ty0; y <= ty1; ++y)
+                for (int x = tx0; x <= tx1; ++x)
+                    for (int ch = 0; ch < 3; ++ch) conn[y - ty0][x - tx0][ch] = src[((size_t)y * w + x) * 3 + ch];
+            for (int base = 0; base < d.prim_count; base += RENDER_CHUNK) {
+                int n = 0;
+                for (int i = base; i < d.prim_count && i < base + RENDER_CHUNK; ++i)
+                    if (render_box_meets(prims[d.prim_offset + i], tx0, ty0, tx1, ty1)) list[n++] = prims[d.prim_offset + i];
+                for (int y = ty0; y <= ty1; ++y)
+                    for (int x = tx0; x <= tx1; ++x)
+                        for (int i = 0; i < n; ++i)
+                            if (render_inside(list[i], x, y)) {
+                                uint8_t *c = conn[y - ty0][x - tx0];
+                                c[0] = list[i].r, c[1] = list[i].g, c[2] = list[i].b;
+                            }
+            }
+            for (int y = ty0; y <= ty1; ++y)
+                for (int x = tx0; x <= tx1; ++x)
+                    for (int ch = 0; ch < 3; ++ch) {
+                        const size_t at = ((size_t)y * w + x) * 3;
+                        dst[at + ((d.flags & 1) ? 2 - ch : ch)] = render_blend(src[at + ch], conn[y - ty0][x - tx0][ch], d.w0, d.w1);
+                    }
+        }
+}
+
+// What hh_render_poses_u8_batch refuses, on the caller's host copy; nullptr = accepted.  `max_prims` is HH_RENDER_MAX_PRIMS.
+inline const char *render_check_frame(const RenderDesc &d, const RenderPrim *prims, long long table_len, int max_prims)
+{
+    if (d.h < 1 || d.w < 1 || d.h > 16384 || d.w > 16384) return "frame size outside 1..16384";
+    if (d.src_offset < 0 || d.dst_offset < 0) return "negative offset";
+    if (d.prim_count < 0 || d.prim_offset < 0 || (long long)d.prim_offset + d.prim_count > table_len) return "primitive range outside the table";
+    if (d.prim_count > max_prims) return "more than HH_RENDER_MAX_PRIMS primitives in one frame";
+    if (!(d.w0 == d.w0) || !(d.w1 == d.w1) || fabsf(d.w0) > 1e6f || fabsf(d.w1) > 1e6f) return "blend weight not finite";
+    if (d.flags & ~1) return "unknown flag";
+    for (int i = 0; i < d.prim_count; ++i) {
+        const RenderPrim &p = prims[d.prim_offset + i];
+        if (p.kind > RENDER_ELLIPSE) return "unknown primitive kind";
+        if (p.A < 1 || p.B < 1) return "primitive with A or B < 1";
+        if (p.kind != RENDER_ELLIPSE && p.A > 32767) return "disc or ring radius above 32767";
+        if (p.cx < -(1 << 23) || p.cx > (1 << 23) || p.cy < -(1 << 23) || p.cy > (1 << 23)) return "primitive centre beyond 2^23";
+        if (p.x0 < 0 || p.y0 < 0 || p.x1 > 16383 || p.y1 > 16383) return "bounding box outside 0..16383";
+        // the box may not reach further from the centre than the exact forms allow (an empty box is always fine)
+        const long long reach = p.kind == RENDER_ELLIPSE ? 65536 : 32767;
+        if (p.x0 <= p.x1 && p.y0 <= p.y1 &&
+            ((long long)p.x0 - p.cx < -reach || (long long)p.x1 - p.cx > reach || (long long)p.y0 - p.cy < -reach || (long long)p.y1 - p.cy > reach))
+            return "bounding box too far from the centre (32767 for discs and rings, 65536 for ellipses)";
+    }
+    return nullptr;
+}
+#endif

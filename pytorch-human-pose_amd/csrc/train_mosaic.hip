@@ -15,40 +15,12 @@
 // pixels are formed once per thread, the row taps and weights once per row.  The gathers are byte loads (at most 4 source pixels
 // per output pixel); no LDS.  Every canvas byte is written exactly once by exactly one thread; nothing depends on the launch.
 #include "kernels.h"
+#include "resize_dev.h"
 
 #define MOSAIC_PX 4     // output pixels per thread and row
 #define MOSAIC_TX 64    // threads along x: a block spans 256 output columns
 #define MOSAIC_TY 4     // thread rows
 #define MOSAIC_ROWS 4   // output rows per thread (rows yi, yi + MOSAIC_TY, ...): a block spans 16 output rows
-
-struct AxisTap {
-    int i0, i1;  // the two source indices
-    int w0, w1;  // their weights, sum 2048 (shorts in OpenCV)
-};
-
-// cv2.resize's INTER_LINEAR tap of destination index d on an axis of `src` source samples.  Columns zero the fraction at the
-// borders; rows keep it and clamp the two indices instead (resize.cpp: the x loop of resize() and resizeGeneric_Invoker).
-__device__ __forceinline__ AxisTap axis_tap(int d, int src, double scale, bool column)
-{
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    AxisTap t;
-    if (column) {
-        if (s < 0) s = 0, f = 0.f;
-        if (s >= src - 1) s = src - 1, f = 0.f;
-        t.i0 = s;
-        t.i1 = min(s + 1, src - 1);
-    } else {
-        t.i0 = min(max(s, 0), src - 1);
-        t.i1 = min(max(s + 1, 0), src - 1);
-    }
-    t.w0 = (int)(short)__float2int_rn((1.f - f) * 2048.f);  // cvRound: half to even
-    t.w1 = (int)(short)__float2int_rn(f * 2048.f);
-    return t;
-}
-
-__device__ __forceinline__ int vertical_pass(int h0, int h1, int b0, int b1) { return (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2; }
 
 __global__ __launch_bounds__(MOSAIC_TX *MOSAIC_TY) void mosaic_kernel(unsigned char *base, const HHMosaicDesc *__restrict__ descs, int S,
                                                                       int xtiles)

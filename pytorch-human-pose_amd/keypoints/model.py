@@ -451,7 +451,7 @@ class InferenceKeypointsModel:
 
     @torch.no_grad()
     def infer_images(self, raw_images: list[np.ndarray], annots: list | None = None, max_batch: int = 32,
-                     scales=None) -> list[InferenceKeypointsResult]:
+                     scales=None, render: dict | None = None) -> list[InferenceKeypointsResult]:
         """The batched path behind the reference's single-image interface (`__call__` per image, bin/eval.py:18-49): images are
         bucketed by model-input shape, every bucket runs as batches of up to `max_batch` -- ONE host->device copy of the raw
         uint8 pixels, hh_preprocess_u8 per image into one [B,3,h,w] tensor, one (flip-TTA) forward, one hh_decode, one
@@ -461,7 +461,16 @@ class InferenceKeypointsModel:
         same way (plan_multi_scale: buckets by the sizes at every scale, chunks of up to `max_batch`): the raw pixels still cross
         once, with one descriptor block per scale behind them; one hh_preprocess_u8_batch per scale, the forwards of the plan, one
         hh_multi_scale_aggregate per stage (and image range) instead of the per-scale flip merges and accumulations, one
-        hh_decode on the averaged maps and the scale-1 tags."""
+        hh_decode on the averaged maps and the scale-1 tags.
+        `render` = dict(color_mode="person", alpha=0.8, bgr=False, out_height=None): every result also carries `.rendered`, the
+        overlay frame of `result.plot_connections(color_mode, alpha)` (B,G,R order if `bgr`; resized to `out_height` with the aspect
+        ratio kept, as the reference's resize_with_aspect_ratio, if given).  The frames of a batch are drawn in ONE
+        hh_render_poses_u8_batch from the staged device pixels of that batch, which stay alive until then; with render=None nothing
+        of the pipeline changes."""
+        if render is not None:
+            unknown = set(render) - {"color_mode", "alpha", "bgr", "out_height"}
+            if unknown:
+                raise ValueError(f"infer_images: unknown render option(s) {sorted(unknown)}")
         n = len(raw_images)
         annots = annots if annots is not None else [None] * n
         # (size, center, scale) now -- the bucket key --, the warp matrix when the image's batch is staged: the first batch should
@@ -487,7 +496,7 @@ class InferenceKeypointsModel:
 
         def finish(job):
             """device -> host results of one enqueued batch, un-warp, result objects"""
-            chunk, (w, h), x, hms, tags, host_out, done = job
+            chunk, (w, h), x, hms, tags, host_out, done, staged = job
             done.synchronize()
             lists = self._parser.to_lists(*host_out)  # (copies what it returns: the pinned buffers are reused two batches later)
             self.model_input_shape = (h, w)
@@ -497,6 +506,8 @@ class InferenceKeypointsModel:
                 results[i] = InferenceKeypointsResult(raw_images[i], annots[i], x[j], coords, joints[..., 2], joints[..., 3:], scores,
                                                       self.det_thr, self.tag_thr, self.limbs, [t[j:j + 1] for t in hms],
                                                       [t[j:j + 1] for t in tags])
+            if staged is not None:
+                self._render_chunk([results[i] for i in chunk], *staged, **render)
 
         # Two-deep software pipeline: while the GPU works on batch k the host stages the pixels of batch k+1 into a pinned
         # buffer and only then collects the results of batch k (two staging buffers, each guarded by the event of its last use).
@@ -536,7 +547,7 @@ class InferenceKeypointsModel:
                     copied = torch.cuda.Event()
                     copied.record()
 
-                def run(chunk=chunk, raw=raw, copied=copied, desc_off=desc_off, w=w, h=h, turn=turn, nb=nb, sizes=sizes, subs=subs):
+                def run(chunk=chunk, raw=raw, copied=copied, desc_off=desc_off, w=w, h=h, turn=turn, nb=nb, sizes=sizes, subs=subs, offs=offs):
                     cur = torch.cuda.current_stream(self.device)
                     cur.wait_event(copied)
                     raw.record_stream(cur)
@@ -568,7 +579,8 @@ class InferenceKeypointsModel:
                         done.record()
                     for t in out:
                         t.record_stream(self._d2h_stream)
-                    return (chunk, (w, h), x, hms, tags, host_out, done), copied, raw
+                    staged = (raw, offs) if render is not None else None  # the batch's device pixels, kept until its render has run
+                    return (chunk, (w, h), x, hms, tags, host_out, done, staged), copied, raw
 
                 # (the model's high-priority stream, for batches as for single images: same-box alternation with the caller's
                 # stream, tools/api_throughput.py: 3820 / 3380 against 2600 / 2970 img/s)
@@ -581,6 +593,46 @@ class InferenceKeypointsModel:
         if pending is not None:
             finish(pending)
         return results
+
+    def _render_chunk(self, results: list, raw: Tensor, offs, color_mode: str = "person", alpha: float = 0.8, bgr: bool = False,
+                      out_height: int | None = None) -> None:
+        """`.rendered` of the results of one batch: one render launch on the batch's staged pixels (`raw`: the device copy of the
+        staging buffer, image j at bytes offs[j]..offs[j+1]), the optional resizes, one pinned buffer back."""
+        from . import visualization as vz
+        cur = torch.cuda.current_stream(self.device)
+        raw.record_stream(cur)
+        frames, tables = [], []
+        for j, r in enumerate(results):
+            frames.append(raw[int(offs[j]):int(offs[j + 1])].view(r.raw_image.shape))
+            tables.append(vz.build_primitives(r.kpts_coords, r.kpts_scores, r.limbs, r.det_thr, color_mode, vz.DEFAULT_PALETTE, alpha))
+        out = vz.render_frames_device(frames, tables, alpha, bgr)
+        if out_height is not None:
+            out = [f if f.shape[0] == out_height else vz.resize_device(f, int(out_height * f.shape[1] / f.shape[0]), out_height) for f in out]
+        sizes = np.cumsum([0] + [f.numel() for f in out])
+        host = torch.empty(int(sizes[-1]), dtype=torch.uint8, pin_memory=True)
+        for j, f in enumerate(out):
+            host[int(sizes[j]):int(sizes[j + 1])].view(f.shape).copy_(f, non_blocking=True)
+        cur.synchronize()
+        hv = host.numpy()
+        for j, (r, f) in enumerate(zip(results, out)):
+            r.rendered = hv[int(sizes[j]):int(sizes[j + 1])].reshape(tuple(f.shape)).copy()
+
+    def video_frame(self, image: np.ndarray):
+        """`video_processing_fn` (keypoints/bin/inference.py:49-75) without its text labels -> (result, out_frame): one inference,
+        the people ordered by their mean tag (same colours for the same person from frame to frame), limb colours at alpha 0.65 with
+        thr = det_thr, B,G,R order, resized to height 640 (new_w = int(640 * w / h); no resize launch when h == 640).  The frame is
+        drawn from the uint8 pixels prepare_input already put on the device: the raw image crosses PCIe once, the finished frame
+        comes back through one pinned buffer."""
+        from . import visualization as vz
+        result = self(image, None)
+        raw = self._keep_raw  # uint8 [h,w,3] on the device (prepare_input)
+        order = np.argsort(result.kpts_tags.mean(axis=1)[:, 0])
+        table = vz.build_primitives(result.kpts_coords[order], result.kpts_scores[order], result.limbs, result.det_thr, "limb", vz.DEFAULT_PALETTE, 0.65)
+        frame = vz.render_frames_device([raw], [table], 0.65, bgr=True)[0]
+        h, w = raw.shape[:2]
+        if h != 640:
+            frame = vz.resize_device(frame, int(640 * w / h), 640)
+        return result, vz.to_host(frame)
 
     def __call__(self, raw_image: np.ndarray, annot: list | None) -> InferenceKeypointsResult:
         """model.py:78-111"""

@@ -3,7 +3,8 @@
 Stands in for the non-plotting part of `/root/reference/src/keypoints/results.py:175-263`
 (`InferenceKeypointsResult.from_preds`): stage-heatmap aggregation and decode run fused on
 the GPU (hh_decode), the coordinate un-warp (results.py:158-171,189-201) on the host.
-Plotting / OKS helpers are out of scope.
+`plot_connections` / `plot` draw the pose overlay on the GPU (keypoints/visualization.py, hh_render_poses_u8_batch).  OKS helpers, the
+heatmap and associative-embedding panels and text labels are out of scope.
 """
 from __future__ import annotations
 
@@ -75,6 +76,7 @@ class InferenceKeypointsResult:
     limbs: list = field(default_factory=list)
     _stage_hms: list | None = None
     _tags: list | None = None
+    rendered: np.ndarray | None = None  # infer_images(render=...): the finished overlay frame
 
     @classmethod
     def from_preds(cls, raw_image, annot, model_input_image: Tensor, kpts_heatmaps: list[Tensor], tags_heatmaps: list[Tensor],
@@ -89,6 +91,16 @@ class InferenceKeypointsResult:
         coords = transform_coords(joints[..., :2], center, scale, (img_w, img_h))
         return cls(raw_image, annot, model_input_image, coords, joints[..., 2], joints[..., 3:], scores, det_thr, tag_thr, limbs,
                    kpts_heatmaps, tags_heatmaps)
+
+    def plot_connections(self, color_mode: str = "person", alpha: float = 0.8) -> np.ndarray:
+        """The reference's plot_connections on `raw_image` with thr = det_thr -> uint8 [h,w,3], drawn on the GPU."""
+        from .visualization import plot_connections
+        return plot_connections(self.raw_image, self.kpts_coords, self.kpts_scores, self.limbs, self.det_thr, color_mode, alpha)
+
+    def plot(self) -> dict[str, np.ndarray]:
+        """results.py:265-300 as far as it is built here: {"connections": ...}.  The reference's "heatmaps" and
+        "associative_embedding" entries need cv2's JET colour map and matplotlib: out of scope."""
+        return {"connections": self.plot_connections()}
 
     # visualisation-only views of the reference (resized maps on the host); not on the hot path
     @property

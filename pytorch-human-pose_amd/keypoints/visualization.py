@@ -1,0 +1,268 @@
+"""Pose overlays: `plot_connections` of the reference (keypoints/visualization.py:13-90) with the per-pixel work on the GPU.
+
+The host does the small float64 / integer bookkeeping (`build_primitives`: which primitives, in what order, where, how large, which
+colour), one hh_render_poses_u8_batch launch draws and blends a batch of frames.  The drawing rule, its rasterisation and the stated
+deviation from OpenCV's rasteriser are written at hh_render_poses_u8_batch in include/hhrnet.h.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .. import _lib
+
+# hh_render_prim / hh_render_desc of include/hhrnet.h
+PRIM = np.dtype([("cx", "<i4"), ("cy", "<i4"), ("A", "<u2"), ("B", "<u2"), ("c", "<f4"), ("s", "<f4"), ("rgb", "u1", (3,)), ("kind", "u1"),
+                 ("box", "<i2", (4,))])
+DESC = np.dtype([("src_offset", "<i8"), ("dst_offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("prim_offset", "<i4"), ("prim_count", "<i4"),
+                 ("w0", "<f4"), ("w1", "<f4"), ("flags", "<i4"), ("reserved", "<i4")])
+assert PRIM.itemsize == 32 and DESC.itemsize == 48
+DISC, RING, ELLIPSE = 0, 1, 2
+MAX_PRIMS = 4096       # HH_RENDER_MAX_PRIMS
+MAX_SIDE = 16384
+MAX_COORD = 1 << 23
+FLAG_BGR = 1
+
+# utils/image.py:168-195 (`colors`, get_color): 20 entries repeated five times; tests/golden/render.npz records get_color(0..99)
+_COLORS = [(144, 238, 144), (255, 105, 180), (135, 206, 250), (255, 215, 0), (255, 69, 0), (255, 182, 193), (0, 128, 128), (255, 160, 122),
+           (0, 191, 255), (70, 130, 180), (255, 99, 71), (0, 255, 255), (0, 255, 127), (255, 0, 255), (255, 215, 0), (255, 140, 0),
+           (30, 144, 255), (255, 20, 147), (255, 165, 0), (218, 112, 214)]
+DEFAULT_PALETTE = np.array(_COLORS * 5, dtype=np.uint8)
+
+
+def blend_weights(alpha: float) -> tuple[np.float32, np.float32]:
+    """addWeighted(image, 1 - alpha, connections_image, alpha, 0): both weights formed in double, rounded once to fp32."""
+    alpha = float(alpha)
+    if not np.isfinite(alpha):
+        raise ValueError("alpha must be finite")
+    return np.float32(1.0 - alpha), np.float32(alpha)
+
+
+def _box(cx: int, cy: int, ex: int, ey: int):
+    """Inclusive box centre +- extent clipped to 0..16383; wholly outside -> empty (x1 < x0 or y1 < y0)."""
+    return (min(max(cx - ex, 0), MAX_SIDE), min(max(cy - ey, 0), MAX_SIDE), min(max(cx + ex, -1), MAX_SIDE - 1), min(max(cy + ey, -1), MAX_SIDE - 1))
+
+
+def _boxes(cx, cy, ex, ey) -> np.ndarray:
+    """_box on arrays -> [..., 4]."""
+    return np.stack([np.clip(cx - ex, 0, MAX_SIDE), np.clip(cy - ey, 0, MAX_SIDE), np.clip(cx + ex, -1, MAX_SIDE - 1), np.clip(cy + ey, -1, MAX_SIDE - 1)], -1)
+
+
+def ellipse_prim(cx: int, cy: int, a: int, b: int, c, s, colour) -> tuple:
+    """One hh_render_prim row: the filled ellipse with semi-axes a + 1/2 along (c, s) and b + 1/2 across, c and s rounded to fp32 here."""
+    if a > 32767 or b > 32767:
+        raise ValueError("ellipse axis beyond 32767 pixels")
+    c, s = np.float32(c), np.float32(s)
+    # half extents of the rotated ellipse plus 2: beyond the fp32 rounding of the inside test
+    ha, hb, cd, sd = a + 0.5, b + 0.5, float(c), float(s)
+    ex, ey = int(np.sqrt((ha * cd) ** 2 + (hb * sd) ** 2)) + 2, int(np.sqrt((ha * sd) ** 2 + (hb * cd) ** 2)) + 2
+    return (cx, cy, 2 * a + 1, 2 * b + 1, c, s, tuple(colour)[:3], ELLIPSE, _box(cx, cy, ex, ey))
+
+
+def circle_prim(cx: int, cy: int, radius: int, colour, ring: bool = False) -> tuple:
+    """One hh_render_prim row: the filled disc of `radius`, or the one-pixel ring of `radius` (ring=True)."""
+    if not 1 <= radius <= 32767:
+        raise ValueError("radius outside 1..32767")
+    return (cx, cy, radius, radius, 1.0, 0.0, tuple(colour)[:3], RING if ring else DISC, _box(cx, cy, radius, radius))
+
+
+def table_of(rows: list) -> np.ndarray:
+    table = np.zeros(len(rows), PRIM)
+    for n, row in enumerate(rows):
+        table[n] = row
+    return table
+
+
+def build_primitives(coords, scores, limbs, thr, color_mode, palette=DEFAULT_PALETTE, alpha: float = 0.8, return_direction: bool = False):
+    """The primitive table of one frame in draw order (structured array of hh_render_prim): numpy only, float64 / int64.
+    coords [P,K,2] (x, y), scores [P,K] or [P,K,1]; `limbs` may be None (keypoints only).  `alpha` is only checked (the weights
+    belong to the frame's descriptor: blend_weights).  Raises where the reference would raise (a palette shorter than needed) and
+    where the table cannot express the frame (a coordinate beyond +-2^23, an axis or radius beyond 32767).
+    `return_direction`: also the float64 (c, s) of every row before its one rounding to fp32 ([N,2]; (1, 0) for discs and rings)."""
+    blend_weights(alpha)
+    if color_mode not in ("person", "limb"):
+        raise ValueError(f"color_mode {color_mode!r} is not 'person' or 'limb'")
+    coords = np.asarray(coords, dtype=np.float64)
+    P = len(coords)
+    if P == 0:
+        return (np.zeros(0, PRIM), np.zeros((0, 2))) if return_direction else np.zeros(0, PRIM)
+    scores = np.asarray(scores, dtype=np.float64).reshape(P, -1)
+    K = coords.shape[1]
+    assert coords.shape == (P, K, 2) and scores.shape == (P, K)
+    if not np.isfinite(coords).all():
+        raise ValueError("non-finite keypoint coordinate")
+    palette = np.asarray(palette)
+    limbs = list(limbs) if limbs is not None else []
+    need = P if color_mode == "person" else max(len(limbs), K)
+    if len(palette) < need:
+        raise IndexError(f"palette of {len(palette)} colours, {need} needed")
+    xy = np.trunc(coords)  # int(): toward zero
+    if np.abs(xy).max() > MAX_COORD:
+        raise ValueError("keypoint coordinate beyond +-2^23")
+    xy = xy.astype(np.int64)
+    size = np.maximum(2, ((coords[..., 1].max(1) - coords[..., 1].min(1)) / 100).astype(np.int32)).astype(np.int64)  # over ALL K keypoints
+    if size.max() + 1 > 32767:
+        raise ValueError("draw size beyond 32766")
+    drawn = ~(scores < float(thr))  # a score equal to thr is drawn
+    L = len(limbs)
+    # every possible row of every person, [P, L + 2K]: the limbs, then disc and ring of each keypoint; the rows that are drawn are
+    # picked at the end, which keeps this order
+    full = np.zeros((P, L + 2 * K), PRIM)
+    dirs = np.zeros((P, L + 2 * K, 2))
+    dirs[..., 0] = 1.0
+    keep = np.zeros((P, L + 2 * K), bool)
+    person = np.arange(P)[:, None]
+    if L:
+        k0, k1 = np.array(limbs, np.int64).reshape(L, 2).T
+        x1, y1, x2, y2 = xy[:, k0, 0], xy[:, k0, 1], xy[:, k1, 0], xy[:, k1, 1]
+        dx, dy = x2 - x1, y2 - y1
+        hyp = np.sqrt((dx * dx + dy * dy).astype(np.float64))
+        half = hyp.astype(np.int64) // 2
+        major = np.abs(dx) > np.abs(dy)
+        safe = np.where(hyp == 0, 1.0, hyp)
+        c = np.where(hyp == 0, 1.0, np.where(major, dx, dy) / safe)
+        s = np.where(hyp == 0, 0.0, np.where(major, dy, -dx) / safe)
+        a, b = np.where(major, half, size[:, None]), np.where(major, size[:, None], half)
+        valid = drawn[:, k0] & drawn[:, k1]
+        if (valid & (half > 32767)).any():
+            raise ValueError("limb longer than 65535 pixels")
+        a, b = np.minimum(a, 32767), np.minimum(b, 32767)  # (rows that are not drawn)
+        c32, s32 = c.astype(np.float32), s.astype(np.float32)
+        # half extents of the rotated ellipse with semi-axes a + 1/2, b + 1/2, plus 2: beyond the fp32 rounding of the inside test
+        ha, hb, cd, sd = a + 0.5, b + 0.5, c32.astype(np.float64), s32.astype(np.float64)
+        ex = np.sqrt((ha * cd) ** 2 + (hb * sd) ** 2).astype(np.int64) + 2
+        ey = np.sqrt((ha * sd) ** 2 + (hb * cd) ** 2).astype(np.int64) + 2
+        cx, cy = (x1 + x2) // 2, (y1 + y2) // 2  # floor division
+        e = full[:, :L]
+        e["cx"], e["cy"], e["A"], e["B"], e["c"], e["s"], e["kind"] = cx, cy, 2 * a + 1, 2 * b + 1, c32, s32, ELLIPSE
+        e["rgb"] = palette[person if color_mode == "person" else np.arange(L)[None, :], :3] + np.zeros((P, L, 1), np.uint8)
+        e["box"] = _boxes(cx, cy, ex, ey)
+        dirs[:, :L, 0], dirs[:, :L, 1] = c, s
+        keep[:, :L] = valid
+    for ring in (0, 1):
+        k = full[:, L + ring::2]
+        radius = (size + ring)[:, None] + np.zeros((P, K), np.int64)
+        k["cx"], k["cy"], k["A"], k["B"], k["c"], k["kind"] = xy[..., 0], xy[..., 1], radius, radius, 1.0, RING if ring else DISC
+        if not ring:
+            k["rgb"] = palette[person if color_mode == "person" else np.arange(K)[None, :], :3] + np.zeros((P, K, 1), np.uint8)
+        k["box"] = _boxes(xy[..., 0], xy[..., 1], radius, radius)
+        keep[:, L + ring::2] = drawn
+    table = np.ascontiguousarray(full[keep])
+    return (table, dirs[keep]) if return_direction else table
+
+
+def render_config() -> tuple[int, int, int, int]:
+    """(tile height, tile width, primitives per chunk, pixels per thread) of the render kernel."""
+    import ctypes as C
+    cfg = (C.c_int * 4)()
+    _lib.check(_lib.load().hh_render_config(cfg))
+    return tuple(cfg)
+
+
+def render_host(image: np.ndarray, prims: np.ndarray, alpha: float, bgr: bool = False) -> np.ndarray:
+    """hh_debug_render_host: one frame through the kernel's tile walk compiled for the host (tests; needs the library, no GPU)."""
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    prims = np.ascontiguousarray(prims, dtype=PRIM)
+    h, w = image.shape[:2]
+    desc = np.zeros(1, DESC)
+    w0, w1 = blend_weights(alpha)
+    desc[0] = (0, 0, h, w, 0, len(prims), w0, w1, FLAG_BGR if bgr else 0, 0)
+    out = np.empty_like(image)
+    _lib.check(_lib.load().hh_debug_render_host(image.ctypes.data, out.ctypes.data, desc.ctypes.data, prims.ctypes.data if len(prims) else None, len(prims)))
+    return out
+
+
+def _align(n: int, a: int = 64) -> int:
+    return (n + a - 1) // a * a
+
+
+def render_frames_device(frames: list, tables: list, alphas, bgr=False) -> list:
+    """One hh_render_poses_u8_batch, on the current stream, for a batch of frames of mixed sizes.  `frames`: uint8 RGB [h,w,3], each a
+    numpy array (uploaded here) or a contiguous device tensor (read in place; the caller keeps it alive until the stream has passed
+    this call).  `tables`: one build_primitives table per frame.  `alphas`, `bgr`: one value, or one per frame.  Descriptors, the
+    primitive table and the pixels of the host frames travel in ONE async copy from one pinned block.
+    -> list of device uint8 tensors [h,w,3], views of one allocation."""
+    n = len(frames)
+    if n == 0:
+        return []
+    lib = _lib.load()
+    alphas = list(alphas) if np.ndim(alphas) else [alphas] * n
+    bgrs = list(bgr) if np.ndim(bgr) else [bgr] * n
+    on_dev = [isinstance(f, torch.Tensor) for f in frames]
+    device = next((f.device for f in frames if isinstance(f, torch.Tensor)), None) or torch.device("cuda", torch.cuda.current_device())
+    counts = [len(t) for t in tables]
+    total_prims = int(sum(counts))
+    prim_at = _align(DESC.itemsize * n)
+    at = _align(prim_at + PRIM.itemsize * total_prims)
+    src_at = []
+    for f, dev in zip(frames, on_dev):
+        if dev:
+            if not (f.dtype == torch.uint8 and f.is_contiguous() and f.dim() == 3 and f.shape[2] == 3 and f.device == device):
+                raise ValueError("a device frame must be a contiguous uint8 [h,w,3] tensor on one device")
+            src_at.append(None)
+        else:
+            if not (f.dtype == np.uint8 and f.ndim == 3 and f.shape[2] == 3):
+                raise ValueError("a host frame must be a uint8 [h,w,3] array")
+            src_at.append(at)
+            at = _align(at + f.size)
+    upload = at
+    out_at = []
+    for f in frames:
+        out_at.append(at)
+        at = _align(at + int(f.shape[0]) * int(f.shape[1]) * 3)
+    host = torch.empty(upload, dtype=torch.uint8).pin_memory()
+    hv = host.numpy()
+    descs = hv[:DESC.itemsize * n].view(DESC)
+    prims = hv[prim_at:prim_at + PRIM.itemsize * total_prims].view(PRIM)
+    buf = torch.empty(at, dtype=torch.uint8, device=device)  # [descriptors | table | uploaded frames | outputs]
+    # offsets are counted from the lowest address involved, so that none is negative (the base itself is never dereferenced)
+    base = min([buf.data_ptr()] + [f.data_ptr() for f, dev in zip(frames, on_dev) if dev])
+    rel = buf.data_ptr() - base
+    first = 0
+    for j, (f, t) in enumerate(zip(frames, tables)):
+        if on_dev[j]:
+            src = f.data_ptr() - base
+        else:
+            np.copyto(hv[src_at[j]:src_at[j] + f.size].reshape(f.shape), f)
+            src = rel + src_at[j]
+        prims[first:first + counts[j]] = t
+        w0, w1 = blend_weights(alphas[j])
+        descs[j] = (src, rel + out_at[j], f.shape[0], f.shape[1], first, counts[j], w0, w1, FLAG_BGR if bgrs[j] else 0, 0)
+        first += counts[j]
+    buf[:upload].copy_(host, non_blocking=True)
+    with torch.cuda.device(device):
+        _lib.check(lib.hh_render_poses_u8_batch(base, buf.data_ptr(), descs.ctypes.data, buf.data_ptr() + prim_at if total_prims else None,
+                                                prims.ctypes.data if total_prims else None, total_prims, n,
+                                                torch.cuda.current_stream(device).cuda_stream))
+    return [buf[o:o + int(f.shape[0]) * int(f.shape[1]) * 3].view(int(f.shape[0]), int(f.shape[1]), 3) for o, f in zip(out_at, frames)]
+
+
+def resize_device(src: torch.Tensor, W: int, H: int) -> torch.Tensor:
+    """cv2.resize(src, (W, H)) of a contiguous device uint8 [h,w] or [h,w,3] tensor on the current stream (hh_resize_u8)."""
+    if not (src.dtype == torch.uint8 and src.is_cuda and src.is_contiguous() and (src.dim() == 2 or (src.dim() == 3 and src.shape[2] in (1, 3)))):
+        raise ValueError("resize_device: a contiguous device uint8 [h,w], [h,w,1] or [h,w,3] tensor is needed")
+    ch = 1 if src.dim() == 2 else int(src.shape[2])
+    out = torch.empty((H, W) + tuple(src.shape[2:]), dtype=torch.uint8, device=src.device)
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.load().hh_resize_u8(src.data_ptr(), src.shape[0], src.shape[1], ch, out.data_ptr(), H, W,
+                                            torch.cuda.current_stream(src.device).cuda_stream))
+    return out
+
+
+def to_host(t: torch.Tensor) -> np.ndarray:
+    """A finished frame back through one pinned buffer."""
+    host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    host.copy_(t, non_blocking=True)
+    torch.cuda.current_stream(t.device).synchronize()
+    return host.numpy().copy()
+
+
+def plot_connections(image: np.ndarray, grouped_kpts_coords, grouped_kpts_scores, limbs=None, thr: float = 0.05, color_mode: str = "person",
+                     alpha: float = 0.8) -> np.ndarray:
+    """The reference's plot_connections (visualization.py:43-90), same signature: uploads, renders, returns uint8 [h,w,3].  Raises when
+    the library or the GPU is missing."""
+    if not torch.cuda.is_available():
+        raise _lib.HHError("plot_connections needs the GPU: there is no CPU renderer")
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    table = build_primitives(grouped_kpts_coords, grouped_kpts_scores, limbs, thr, color_mode, DEFAULT_PALETTE, alpha)
+    return to_host(render_frames_device([image], [table], alpha)[0])

@@ -1,0 +1,96 @@
+// The pose overlay's code (pytorch-human-pose_amd/csrc/render_math.h: tile cull, inside tests, blend, one frame walked tile by tile)
+// compiled for the HOST and run over frames and primitive tables aimed at the tile, chunk and pixel-group boundaries, so that the
+// address arithmetic can be put under the sanitizers without a GPU:
+//
+//   c++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all \
+//       -I pytorch-human-pose_amd/csrc tools/render_host_check.cpp -o /tmp/render_host_check && /tmp/render_host_check
+//
+// Source and destination are heap blocks of exactly h * w * 3 bytes and the table a block of exactly its rows, so a read or write one
+// byte past a frame or one row past the table is an AddressSanitizer report.  Checked besides: every destination byte was written (the
+// block starts as a pattern no blend of the source can give everywhere), a frame without primitives is the blend of the source with
+// itself, a primitive wholly outside changes nothing, the validation accepts what is drawn here and refuses a table row out of range.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "render_math.h"
+
+static unsigned long long rng_state = 88172645463325252ull;
+static unsigned rnd()
+{
+    rng_state ^= rng_state << 13; rng_state ^= rng_state >> 7; rng_state ^= rng_state << 17;
+    return (unsigned)(rng_state >> 33);
+}
+
+static int16_t clip16(long long v, long long lo, long long hi) { return (int16_t)(v < lo ? lo : (v > hi ? hi : v)); }
+static RenderPrim prim(int kind, int cx, int cy, int a, int b, double ang)
+{
+    RenderPrim p;
+    memset(&p, 0, sizeof(p));
+    p.kind = (uint8_t)kind; p.cx = cx; p.cy = cy;
+    p.r = (uint8_t)rnd(); p.g = (uint8_t)rnd(); p.b = (uint8_t)rnd();
+    int ex, ey;
+    if (kind == RENDER_ELLIPSE) {
+        p.A = (uint16_t)(2 * a + 1); p.B = (uint16_t)(2 * b + 1); p.c = (float)cos(ang); p.s = (float)sin(ang);
+        const double ha = a + 0.5, hb = b + 0.5;
+        ex = (int)sqrt(ha * p.c * ha * p.c + hb * p.s * hb * p.s) + 2; ey = (int)sqrt(ha * p.s * ha * p.s + hb * p.c * hb * p.c) + 2;
+    } else {
+        p.A = p.B = (uint16_t)a; p.c = 1.f; p.s = 0.f; ex = ey = a;
+    }
+    p.x0 = clip16((long long)cx - ex, 0, 16384); p.y0 = clip16((long long)cy - ey, 0, 16384);
+    p.x1 = clip16((long long)cx + ex, -1, 16383); p.y1 = clip16((long long)cy + ey, -1, 16383);
+    return p;
+}
+
+static int run(int h, int w, int count, int flags)
+{
+    const size_t bytes = (size_t)h * w * 3;
+    uint8_t *src = (uint8_t *)malloc(bytes), *dst = (uint8_t *)malloc(bytes), *plain = (uint8_t *)malloc(bytes);
+    RenderPrim *table = (RenderPrim *)malloc(count ? sizeof(RenderPrim) * count : 1);
+    for (size_t i = 0; i < bytes; ++i) src[i] = (uint8_t)rnd();
+    int outside = 0;
+    for (int i = 0; i < count; ++i) {
+        const int kind = i % 3;
+        int cx = (int)(rnd() % (unsigned)(w + 40)) - 20, cy = (int)(rnd() % (unsigned)(h + 40)) - 20;
+        if (i % 17 == 5) cx = w + 500, ++outside;           // wholly outside
+        if (i % 17 == 11) cy = -(1 << 22);                  // far outside: the box is empty, dx is never formed for a pixel
+        table[i] = prim(kind, cx, cy, kind == RENDER_ELLIPSE ? (int)(rnd() % 60) : 1 + (int)(rnd() % 9), (int)(rnd() % 5), 0.1 * i);
+    }
+    RenderDesc d;
+    memset(&d, 0, sizeof(d));
+    d.h = h; d.w = w; d.prim_count = count; d.w0 = (float)(1.0 - 0.65); d.w1 = (float)0.65; d.flags = flags;
+    int bad = 0;
+    if (render_check_frame(d, table, count, 4096)) { printf("  refused: %s\n", render_check_frame(d, table, count, 4096)); ++bad; }
+    d.prim_count = count + 1;
+    if (!render_check_frame(d, table, count, 4096)) { printf("  a range past the table was accepted\n"); ++bad; }
+    d.prim_count = count;
+    RenderPrim list[RENDER_CHUNK];
+    memset(dst, 0xA5, bytes);
+    render_frame_host(src, dst, d, table, list);
+    RenderDesc e = d;
+    e.prim_count = 0;
+    render_frame_host(src, plain, e, table, list);
+    size_t changed = 0;
+    for (size_t i = 0; i < bytes; ++i) {
+        const size_t px = i / 3, ch = i % 3;
+        const uint8_t s = src[px * 3 + ((flags & 1) ? 2 - ch : ch)];
+        if (plain[i] != render_blend(s, s, d.w0, d.w1)) { ++bad; break; }
+        changed += dst[i] != plain[i];
+    }
+    printf("%5d x %5d, %4d primitives (%d outside), flags %d: %zu of %zu bytes differ from the plain blend%s\n", h, w, count, outside, flags, changed, bytes,
+           bad ? "  FAILED" : "");
+    free(src); free(dst); free(plain); free(table);
+    return bad;
+}
+
+int main()
+{
+    int bad = 0;
+    const int sizes[][2] = {{1, 1}, {5, 7}, {RENDER_TH, RENDER_TW}, {RENDER_TH + 1, RENDER_TW + 1}, {2 * RENDER_TH + 3, 3 * RENDER_TW - 1}, {3, 2 * RENDER_TW + 2}, {200, 1}};
+    const int counts[] = {0, 1, RENDER_CHUNK - 1, RENDER_CHUNK, RENDER_CHUNK + 1, 4096};
+    for (const auto &s : sizes)
+        for (int c : counts) bad += run(s[0], s[1], c, c & 1);
+    printf(bad ? "FAILED\n" : "render_host_check: clean\n");
+    return bad ? 1 : 0;
+}
