@@ -375,6 +375,73 @@ int hh_render_poses_u8_batch(unsigned char *batch_base, const hh_render_desc *de
 int hh_render_config(int out[4]);
 int hh_debug_render_host(const unsigned char *src, unsigned char *dst, const hh_render_desc *desc, const hh_render_prim *prims, int num_prims);
 int hh_resize_u8(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, void *stream);
+/* Heatmap panels: plot_heatmaps + make_grid of the reference (keypoints/visualization.py:93-110, utils/image.py:15-38) for every grid
+ * of one figure in ONE call (one min/max launch, skipped when no map asks for it, and one paint launch), from the stage outputs of the
+ * net as they are: no full-resolution fp32 map is stored or copied to the host.  tests/panels_ref.py restates the rule in numpy /
+ * torch-CPU; the result is bit-identical to it.
+ *
+ * The per-pixel rule.  A figure is a uint8 canvas [Hc, Wc, 3] with `pitch` bytes between rows.  It is zero everywhere except in its
+ * cells.  Cell m is H x W pixels at origin (oy_m, ox_m) and shows map m over the same uint8 image [H, W, 3].  The value v of map m at
+ * (y, x) of its cell, by the map's kind (src_index / bilerp: torch CPU's F.interpolate(bilinear, align_corners=False) in fp32, the
+ * decode's own, scale = (float)in / (float)out):
+ *   HH_PANEL_DIRECT   src[y][x]; src is H x W.  No arithmetic.
+ *   HH_PANEL_SINGLE   one interpolate from h x w: bilerp(src, w, src_index(h, (float)h / H, y), src_index(w, (float)w / W, x)).
+ *   HH_PANEL_NESTED   src is the quarter-resolution map (H == 4h, W == 4w), resized x2 and then to H x W (match_heatmaps_size, then
+ *                     resize_heatmaps: stage 0 of KeypointsResult): the four half-resolution taps (r, c) of the second resize are each
+ *                     bilerp(src, w, src_index(h, 0.5f, r), src_index(w, 0.5f, c)) and are combined as hh_decode combines its taps.
+ *   HH_PANEL_AVERAGE  the same with every tap averaged with the half-resolution map: (tap + src2[r][c]) / 2.0f, src2 [2h, 2w]: the
+ *                     stage average as InferenceKeypointsResult.from_preds decodes it.
+ * From v to the pixel, in fp32, every operation rounded on its own:
+ *   1. HH_PANEL_CLIP: v = np.clip(v, 0, 1); NaN stays NaN.
+ *   2. HH_PANEL_MINMAX: v = (v - mx) / (mx - mn), mx and mn the np.max / np.min of this map's values after step 1 over all H W pixels:
+ *      a NaN anywhere makes both NaN.  The subtraction is v - mx, the reference's expression (visualization.py:104), so v lies in
+ *      [-1, 0]; a constant map gives 0 / 0.
+ *   3. q = v * 255.0f; t = q truncated toward zero as int32, 0 when q is not finite or outside int32; level = t & 255: what
+ *      (hm * 255).astype(np.uint8) gives with numpy on x86-64 (-1.0 -> 255, -3.7 -> 253, NaN -> 0).
+ *   4. c = 255 - level; colour = lut[c], lut a uint8 [256, 3] table of the caller's, applied channel for channel next to the image's
+ *      channels with no B <-> R swap (the reference blends applyColorMap's B,G,R onto an R,G,B image as it is).
+ *   5. out[ch] = rintf(image[y][x][ch] * 0.25f + colour[ch] * 0.75f), half to even, clamped to 0..255.
+ * Pinned to torch: the resampling.  Pinned to numpy: the quantiser and the un-normalise below.  Pinned to this text: the blend and the
+ * grid layout.  UNPINNED for want of cv2 where the fixtures are made: the default table (keypoints/visualization.py jet_lut: in B,G,R
+ * order X2 = clamp(765 - |8 i - 510 k|, 0, 510) for k = 1 (B), 2 (G), 3 (R), entry (X2 + 1) >> 1, a reading of COLORMAP_JET) and the
+ * fx / fy form of the resize.  The table is a parameter: a user with cv2 passes applyColorMap(arange(256), COLORMAP_JET).
+ *
+ * hh_heatmap_panels_u8: maps_dev / maps_host are the device copy the kernels read and the caller's HOST copy of the same n rows, which
+ *   is what is checked.  src / src2 are device pointers to contiguous fp32 planes.  image, lut, canvas, scratch: device.  scratch:
+ *   n * HH_PANEL_PARTS * 2 floats, may be null when no map has HH_PANEL_MINMAX; every element that is read is written earlier in the
+ *   same call, so it needs no clearing and carries nothing from call to call.  The Wc * 3 bytes of every canvas row are all written
+ *   (cells, padding, unused cells) exactly once; bytes between Wc * 3 and pitch are left alone; no alignment requirement on canvas, pitch
+ *   or origins.  Of two cells that overlap the later row of the table wins.  Deterministic.  Returns 1 with hh_last_error set, before any
+ *   launch, for a null pointer (image, lut, canvas, table, a map's src, an AVERAGE map's src2), n outside 1..HH_PANEL_MAX_MAPS, a kind or
+ *   flag out of range, a side outside 1..16384, pitch < Wc * 3, a DIRECT map whose size is not H x W, a NESTED / AVERAGE map whose size
+ *   is not H/4 x W/4, a cell that does not lie inside the canvas.
+ * hh_debug_heatmap_panels_host: the same arithmetic (csrc/panel_math.h) compiled for the host on one figure in HOST memory (every
+ *   pointer, those in the table too); same validation.  For tests and tools/panels_host_check.cpp.
+ * hh_unnormalize_u8: KeypointsTransform.inverse_transform (base/transforms/base.py:33-41): out[y][x][c] = the cast of step 3 applied
+ *   to ((double)x[c][y][x] * std[c] + mean[c]) * 255 in float64 (product, sum, product rounded separately), fp32 [3,H,W] -> uint8
+ *   [H,W,3], both on the device.  The truncation can give one less than the raw byte; that is the reference's behaviour.
+ * hh_resize_u8_scaled: cv2.resize(src, (0, 0), fx=fx, fy=fy): hh_resize_u8 with the coordinate scales 1 / fx and 1 / fy (not w / W);
+ *   H x W must be cvRound(h * fy) x cvRound(w * fx), half to even, or the call is refused.  The 2 x 2 mean applies iff h == 2H and
+ *   w == 2W, as in hh_resize_u8.  UNPINNED against cv2 like the rest of that resize.
+ * (Additive entry points: HH_ABI_VERSION stays 3.)                                                                           */
+#define HH_PANEL_MAX_MAPS 256 /* per figure */
+#define HH_PANEL_PARTS 32     /* (max, min) pairs per map in the scratch */
+enum { HH_PANEL_DIRECT = 0, HH_PANEL_SINGLE = 1, HH_PANEL_NESTED = 2, HH_PANEL_AVERAGE = 3 };
+enum { HH_PANEL_CLIP = 1, HH_PANEL_MINMAX = 2 };
+typedef struct hh_panel_map {
+    const float *src;    /* DIRECT [H,W]; SINGLE [h,w]; NESTED, AVERAGE: the quarter-resolution map [h,w] */
+    const float *src2;   /* AVERAGE: the half-resolution map [2h,2w]; otherwise ignored */
+    int32_t h, w;        /* size of src */
+    int32_t kind, flags;
+    int32_t oy, ox;      /* the cell's origin in the canvas */
+} hh_panel_map;
+int hh_heatmap_panels_u8(const hh_panel_map *maps_dev, const hh_panel_map *maps_host, int n, const unsigned char *image, int H, int W,
+                         const unsigned char *lut, unsigned char *canvas, int Hc, int Wc, long long pitch, float *scratch, void *stream);
+int hh_debug_heatmap_panels_host(const hh_panel_map *maps, int n, const unsigned char *image, int H, int W, const unsigned char *lut,
+                                 unsigned char *canvas, int Hc, int Wc, long long pitch);
+int hh_unnormalize_u8(const float *x_chw, int H, int W, const double mean[3], const double stdv[3], unsigned char *out_hwc, void *stream);
+int hh_resize_u8_scaled(const unsigned char *src, int h, int w, int channels, double fx, double fy, unsigned char *dst, int H, int W,
+                        void *stream);
 /* HeatmapGenerator (coco.py:77-121) as a gather over the packed joints the grouping loss takes (hh_loss_ae_grouping: joints int32
  * [B,P,K,3] = x, y, vis from JointsGenerator, coco.py:124-137; num_people [B]): out fp32 [B,K,h,w], each element the maximum over
  * the image's people p < num_people[b] with vis > 0 and (x, y) inside the map of table[y - y_p + reach][x - x_p + reach] where that

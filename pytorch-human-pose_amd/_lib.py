@@ -81,6 +81,10 @@ def _sig(lib):
         "hh_render_config": (i32, [C.POINTER(C.c_int)]),
         "hh_debug_render_host": (i32, [vp, vp, vp, vp, i32]),
         "hh_resize_u8": (i32, [vp, i32, i32, i32, vp, i32, i32, vp]),
+        "hh_resize_u8_scaled": (i32, [vp, i32, i32, i32, dbl, dbl, vp, i32, i32, vp]),
+        "hh_unnormalize_u8": (i32, [vp, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp]),
+        "hh_heatmap_panels_u8": (i32, [vp, vp, i32, vp, i32, i32, vp, vp, i32, i32, C.c_longlong, vp, vp]),
+        "hh_debug_heatmap_panels_host": (i32, [vp, i32, vp, i32, i32, vp, vp, i32, i32, C.c_longlong]),
         "hh_heatmap_table_size": (i32, [dbl, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "hh_render_heatmaps": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp]),
         "hh_flip_images": (i32, [vp, vp, i32, i32, i32, i32, vp]),

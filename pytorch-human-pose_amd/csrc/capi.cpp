@@ -9,6 +9,7 @@
 #include "engine.h"
 #include "optim_math.h"
 #include "render_math.h"
+#include "panel_math.h"
 
 const char *hh_get_error();
 int hh_tap_read_impl(hh_net *n, int index, float *host);
@@ -342,6 +343,74 @@ int hh_resize_u8(const unsigned char *src, int h, int w, int channels, unsigned 
     }
     // (with sides <= 16384 and 3 channels both images stay below 2^31 bytes: the kernel indexes the source with 32 bits)
     HH_CHECK_HIP(launch_resize_u8(src, h, w, channels, dst, H, W, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_resize_u8_scaled(const unsigned char *src, int h, int w, int channels, double fx, double fy, unsigned char *dst, int H, int W, void *stream)
+{
+    const char *fn = "hh_resize_u8_scaled";
+    if (!src || !dst) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if (channels != 1 && channels != 3) { hh_set_error(std::string(fn) + ": channels must be 1 or 3"); return 1; }
+    if (!(fx > 0.0) || !(fy > 0.0) || !std::isfinite(fx) || !std::isfinite(fy)) { hh_set_error(std::string(fn) + ": fx and fy must be positive and finite"); return 1; }
+    if (h < 1 || w < 1 || H < 1 || W < 1 || h > HH_RESIZE_MAX_SIDE || w > HH_RESIZE_MAX_SIDE || H > HH_RESIZE_MAX_SIDE || W > HH_RESIZE_MAX_SIDE) {
+        hh_set_error(std::string(fn) + ": every side must lie in 1..16384");
+        return 1;
+    }
+    // cvRound of the double product: to nearest, half to even (the default rounding mode)
+    if ((double)W != std::nearbyint((double)w * fx) || (double)H != std::nearbyint((double)h * fy)) {
+        hh_set_error(std::string(fn) + ": H x W must be cvRound(h * fy) x cvRound(w * fx)");
+        return 1;
+    }
+    HH_CHECK_HIP(launch_resize_u8_scaled(src, h, w, channels, dst, H, W, fx, fy, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_unnormalize_u8(const float *x_chw, int H, int W, const double mean[3], const double stdv[3], unsigned char *out_hwc, void *stream)
+{
+    const char *fn = "hh_unnormalize_u8";
+    if (!x_chw || !out_hwc || !mean || !stdv) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if (H < 1 || W < 1 || H > HH_RESIZE_MAX_SIDE || W > HH_RESIZE_MAX_SIDE) { hh_set_error(std::string(fn) + ": every side must lie in 1..16384"); return 1; }
+    HH_CHECK_HIP(launch_unnormalize_u8(x_chw, H, W, out_hwc, mean, stdv, (hipStream_t)stream));
+    return 0;
+}
+
+// The checks of a panels call that need no device, on the caller's host copy of the table; *any_minmax: does any map ask for the range.
+static int panels_check(const char *fn, const hh_panel_map *maps_host, int n, const void *image, int H, int W, const void *lut, const void *canvas, int Hc,
+                        int Wc, long long pitch, bool *any_minmax)
+{
+    static_assert(sizeof(hh_panel_map) == sizeof(PanelMap), "table layout");
+    static_assert(HH_PANEL_MAX_MAPS == PANEL_MAX_MAPS && HH_PANEL_PARTS == PANEL_PARTS, "limits of include/hhrnet.h");
+    static_assert(HH_PANEL_DIRECT == PANEL_DIRECT && HH_PANEL_SINGLE == PANEL_SINGLE && HH_PANEL_NESTED == PANEL_NESTED && HH_PANEL_AVERAGE == PANEL_AVERAGE, "kinds");
+    static_assert(HH_PANEL_CLIP == PANEL_CLIP && HH_PANEL_MINMAX == PANEL_MINMAX, "flags");
+    if (!maps_host || !image || !lut || !canvas) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    const char *why = panel_check(reinterpret_cast<const PanelMap *>(maps_host), n, H, W, Hc, Wc, pitch);
+    if (why) { hh_set_error(std::string(fn) + ": " + why); return 1; }
+    *any_minmax = false;
+    for (int i = 0; i < n; ++i) *any_minmax |= (maps_host[i].flags & HH_PANEL_MINMAX) != 0;
+    return 0;
+}
+
+int hh_heatmap_panels_u8(const hh_panel_map *maps_dev, const hh_panel_map *maps_host, int n, const unsigned char *image, int H, int W,
+                         const unsigned char *lut, unsigned char *canvas, int Hc, int Wc, long long pitch, float *scratch, void *stream)
+{
+    const char *fn = "hh_heatmap_panels_u8";
+    bool any_minmax = false;
+    if (!maps_dev) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if ((uintptr_t)maps_dev % 8) { hh_set_error(std::string(fn) + ": maps_dev must be 8-byte aligned"); return 1; }
+    if (panels_check(fn, maps_host, n, image, H, W, lut, canvas, Hc, Wc, pitch, &any_minmax)) return 1;
+    if (any_minmax && (!scratch || (uintptr_t)scratch % 4)) { hh_set_error(std::string(fn) + ": a map asks for min-max and scratch is null or misaligned"); return 1; }
+    HH_CHECK_HIP(launch_panels(reinterpret_cast<const PanelMap *>(maps_dev), n, any_minmax, image, H, W, lut, canvas, Hc, Wc, pitch, scratch, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_debug_heatmap_panels_host(const hh_panel_map *maps, int n, const unsigned char *image, int H, int W, const unsigned char *lut, unsigned char *canvas,
+                                 int Hc, int Wc, long long pitch)
+{
+    const char *fn = "hh_debug_heatmap_panels_host";
+    bool any_minmax = false;
+    if (panels_check(fn, maps, n, image, H, W, lut, canvas, Hc, Wc, pitch, &any_minmax)) return 1;
+    std::vector<PanelRange> ranges(n);
+    panels_debug_host(reinterpret_cast<const PanelMap *>(maps), n, image, H, W, lut, canvas, Hc, Wc, pitch, ranges.data());
     return 0;
 }
 

@@ -360,6 +360,16 @@ struct RenderPrim;
 hipError_t launch_render_poses(unsigned char *base, const RenderDesc *descs, const RenderPrim *prims, int n, int max_tiles, hipStream_t s);
 void render_debug_host(const unsigned char *src, unsigned char *dst, const RenderDesc &d, const RenderPrim *prims);
 hipError_t launch_resize_u8(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, hipStream_t s);
+hipError_t launch_resize_u8_scaled(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, double fx, double fy, hipStream_t s);
+// Heatmap panels (hh_panel_map of include/hhrnet.h; struct and arithmetic in panel_math.h, kernels in panels.hip): the min/max launch
+// (only if any_minmax) and the paint launch of one figure; the same figure on the host; the un-normalise of the model input.
+struct PanelMap;
+struct PanelRange;
+hipError_t launch_panels(const PanelMap *maps, int n, bool any_minmax, const unsigned char *image, int H, int W, const unsigned char *lut,
+                         unsigned char *canvas, int Hc, int Wc, long long pitch, float *parts, hipStream_t s);
+void panels_debug_host(const PanelMap *maps, int n, const unsigned char *image, int H, int W, const unsigned char *lut, unsigned char *canvas, int Hc,
+                       int Wc, long long pitch, PanelRange *ranges);
+hipError_t launch_unnormalize_u8(const float *x, int H, int W, unsigned char *out, const double *mean, const double *stdv, hipStream_t s);
 // target heatmaps from the packed joints (train_input.hip); n = table side = 2 * reach + 1 <= HH_RENDER_MAX_N, w <= HH_RENDER_MAX_W
 #define HH_RENDER_MAX_N 63
 #define HH_RENDER_MAX_W 4096

@@ -136,7 +136,7 @@ void render_debug_host(const unsigned char *src, unsigned char *dst, const Rende
 
 template <int CH>
 __global__ __launch_bounds__(RESIZE_TX *RESIZE_TY) void resize_u8_kernel(const unsigned char *__restrict__ src, int h, int w, unsigned char *__restrict__ dst,
-                                                                         int H, int W, int xtiles)
+                                                                         int H, int W, int xtiles, double scale_x, double scale_y)
 {
     const int xi = threadIdx.x % RESIZE_TX, yi = threadIdx.x / RESIZE_TX;
     const int x0 = ((int)(blockIdx.x % xtiles) * RESIZE_TX + xi) * RESIZE_PX;
@@ -144,7 +144,6 @@ __global__ __launch_bounds__(RESIZE_TX *RESIZE_TY) void resize_u8_kernel(const u
     if (x0 >= W) return;
     const int npx = min(RESIZE_PX, W - x0);
     const bool area = h == 2 * H && w == 2 * W;  // both scales exactly 2: OpenCV takes INTER_AREA's 2 x 2 mean
-    const double scale_x = 1.0 / ((double)W / (double)w), scale_y = 1.0 / ((double)H / (double)h);
 
     AxisTap tx[RESIZE_PX];
 #pragma unroll
@@ -189,11 +188,24 @@ __global__ __launch_bounds__(RESIZE_TX *RESIZE_TY) void resize_u8_kernel(const u
     }
 }
 
-hipError_t launch_resize_u8(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, hipStream_t s)
+// scale_x, scale_y: the source step per destination pixel, formed in double by the caller (cv2.resize's scale_x = 1 / inv_scale_x)
+static hipError_t resize_u8(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, double scale_x, double scale_y, hipStream_t s)
 {
     const int xtiles = (W + RESIZE_TX * RESIZE_PX - 1) / (RESIZE_TX * RESIZE_PX), ytiles = (H + RESIZE_TY * RESIZE_ROWS - 1) / (RESIZE_TY * RESIZE_ROWS);
     const dim3 grid(xtiles * ytiles), block(RESIZE_TX * RESIZE_TY);
-    if (channels == 3) hipLaunchKernelGGL(resize_u8_kernel<3>, grid, block, 0, s, src, h, w, dst, H, W, xtiles);
-    else hipLaunchKernelGGL(resize_u8_kernel<1>, grid, block, 0, s, src, h, w, dst, H, W, xtiles);
+    if (channels == 3) hipLaunchKernelGGL(resize_u8_kernel<3>, grid, block, 0, s, src, h, w, dst, H, W, xtiles, scale_x, scale_y);
+    else hipLaunchKernelGGL(resize_u8_kernel<1>, grid, block, 0, s, src, h, w, dst, H, W, xtiles, scale_x, scale_y);
     return hipGetLastError();
+}
+
+// cv2.resize(src, (W, H)): inv_scale = (double)W / w, scale = 1 / inv_scale
+hipError_t launch_resize_u8(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, hipStream_t s)
+{
+    return resize_u8(src, h, w, channels, dst, H, W, 1.0 / ((double)W / (double)w), 1.0 / ((double)H / (double)h), s);
+}
+
+// cv2.resize(src, (0, 0), fx=fx, fy=fy): the destination size H x W = cvRound(h fy) x cvRound(w fx) is formed by the caller; scale = 1 / f
+hipError_t launch_resize_u8_scaled(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, double fx, double fy, hipStream_t s)
+{
+    return resize_u8(src, h, w, channels, dst, H, W, 1.0 / fx, 1.0 / fy, s);
 }

@@ -7,4 +7,4 @@ __all__ = ["HigherHRNet", "MPPEHeatmapParser", "InferenceKeypointsModel", "Infer
 from .loss import AEGroupingLoss, AEKeypointsLoss, HeatmapsLoss
 from . import coco_eval, evaluation, targets
 from .train_input import Mosaic, TrainInput, mosaic_joints
-from .visualization import DEFAULT_PALETTE, build_primitives, plot_connections
+from .visualization import DEFAULT_PALETTE, build_primitives, jet_lut, plot_connections, plot_heatmaps

@@ -3,8 +3,9 @@
 Stands in for the non-plotting part of `/root/reference/src/keypoints/results.py:175-263`
 (`InferenceKeypointsResult.from_preds`): stage-heatmap aggregation and decode run fused on
 the GPU (hh_decode), the coordinate un-warp (results.py:158-171,189-201) on the host.
-`plot_connections` / `plot` draw the pose overlay on the GPU (keypoints/visualization.py, hh_render_poses_u8_batch).  OKS helpers, the
-heatmap and associative-embedding panels and text labels are out of scope.
+`plot_connections` / `plot` draw the pose overlay and the heatmap panels on the GPU (keypoints/visualization.py,
+hh_render_poses_u8_batch, hh_heatmap_panels_u8).  OKS helpers, the associative-embedding scatter and text labels are out of scope
+(SURVEY.md §2).
 """
 from __future__ import annotations
 
@@ -29,7 +30,7 @@ def transform_coords(kpts_coords: np.ndarray, center, scale, output_size) -> np.
 
 
 class KeypointsResult:
-    """Validation-time result of one image (`results.py:70-124`, without the plotting helpers): the stage heatmaps and tags of
+    """Validation-time result of one image (`results.py:70-155`): the stage heatmaps and tags of
     the net as they come out of `forward` (batch dim kept: [1,K,h,w]), decoded on demand by `set_preds()` with this result's
     own thresholds (validation uses max_num_people=20, det_thr=0.1, tag_thr=1.0, `keypoints/module.py:100-108`).  Coordinates
     are model-input pixels (no un-warp: the validation image IS the model input)."""
@@ -60,6 +61,23 @@ class KeypointsResult:
         parser = results[0].hm_parser
         for r, (j, s) in zip(results, parser.to_lists(*parser.decode_batch_device(stages[0], stages[1], [tags], adjust=True, refine=True))):
             r._assign(j, s)
+
+    def plot(self) -> dict[str, np.ndarray]:
+        """results.py:126-155 after set_preds(): {"heatmaps": figure}.  Left, the connections overlay on the un-normalised model input
+        (thr = det_thr, alpha = 0.8); right, per stage a one-row grid of that stage's maps clipped to 0..1 (stage 0 resized twice, as
+        set_preds resizes it) followed, while the stage index is below the embedding dimension (1), by a one-row grid of the tags with
+        min-max; the grids stacked, shrunk by 0.4 and put next to the overlay.  Everything per pixel runs on the GPU
+        (hh_unnormalize_u8, hh_render_poses_u8_batch, hh_heatmap_panels_u8, hh_resize_u8_scaled, hh_resize_u8)."""
+        from . import visualization as vis
+        a, b = (t[0].float().contiguous() for t in self._kpts_heatmaps)
+        tags = self._tags_heatmaps[0].float().contiguous()
+        image = vis.unnormalize_device(self.model_input_image.to(a.device, torch.float32))
+        table = vis.build_primitives(self.kpts_coords, self.kpts_scores, self.limbs, self.det_thr, "person", vis.DEFAULT_PALETTE, 0.8)
+        connections = vis.render_frames_device([image], [table], 0.8)[0]
+        grids = [([(vis.NESTED, m, None, vis.CLIP) for m in a], 1, 5), ([(vis.SINGLE, m, None, vis.MINMAX) for m in tags], 1, 5),
+                 ([(vis.SINGLE, m, None, vis.CLIP) for m in b], 1, 5)]
+        figure = vis.figure_device(image, grids, 0.4)
+        return {"heatmaps": vis.to_host(vis.stack_horizontally_device([connections, figure]))}
 
 
 @dataclass
@@ -97,10 +115,25 @@ class InferenceKeypointsResult:
         from .visualization import plot_connections
         return plot_connections(self.raw_image, self.kpts_coords, self.kpts_scores, self.limbs, self.det_thr, color_mode, alpha)
 
+    def plot_heatmaps_figure(self) -> np.ndarray:
+        """results.py:317-328: the K stage-average maps and the K tag maps of the first embedding, both with min-max, each as a grid of
+        two rows over the un-normalised model input, stacked and shrunk by 0.6 -> uint8 [h,w,3].  Painted on the GPU from the stage
+        outputs (hh_heatmap_panels_u8); only the finished figure is copied to the host."""
+        from . import visualization as vis
+        a, b = (t[0].float().contiguous() for t in self._stage_hms)
+        tags = self._tags[0][0].float().contiguous()
+        image = vis.unnormalize_device(self.model_input_image.to(a.device, torch.float32))
+        grids = [([(vis.AVERAGE, q, h, vis.MINMAX) for q, h in zip(a, b)], 2, 5), ([(vis.SINGLE, m, None, vis.MINMAX) for m in tags], 2, 5)]
+        return vis.to_host(vis.figure_device(image, grids, 0.6))
+
     def plot(self) -> dict[str, np.ndarray]:
-        """results.py:265-300 as far as it is built here: {"connections": ...}.  The reference's "heatmaps" and
-        "associative_embedding" entries need cv2's JET colour map and matplotlib: out of scope."""
-        return {"connections": self.plot_connections()}
+        """results.py:300-339 as far as it is built here: {"connections": ...} and, when the result holds its stage maps, tags and
+        model input, {"heatmaps": ...} (plot_heatmaps_figure).  The reference's "associative_embedding" entry is a matplotlib scatter:
+        out of scope."""
+        plots = {"connections": self.plot_connections()}
+        if self._stage_hms is not None and self._tags is not None and self.model_input_image is not None:
+            plots["heatmaps"] = self.plot_heatmaps_figure()
+        return plots
 
     # visualisation-only views of the reference (resized maps on the host); not on the hot path
     @property

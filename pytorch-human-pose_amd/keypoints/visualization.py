@@ -3,6 +3,12 @@
 The host does the small float64 / integer bookkeeping (`build_primitives`: which primitives, in what order, where, how large, which
 colour), one hh_render_poses_u8_batch launch draws and blends a batch of frames.  The drawing rule, its rasterisation and the stated
 deviation from OpenCV's rasteriser are written at hh_render_poses_u8_batch in include/hhrnet.h.  There is no CPU fallback.
+
+Heatmap panels: `plot_heatmaps`, `make_grid`, `np.concatenate` and `stack_horizontally` of the reference (visualization.py:93-110,
+utils/image.py:15-61).  The host does the integer bookkeeping (`figure_layout`: cell origins, canvas size); hh_heatmap_panels_u8
+resamples, colours, blends and tiles every map of a figure in one call from the stage outputs as they are, hh_resize_u8_scaled shrinks
+the figure, and only the finished uint8 figure crosses to the host.  The per-pixel rule and what is UNPINNED for want of cv2 (the JET
+table, the fx / fy resize) are written at hh_heatmap_panels_u8 in include/hhrnet.h.
 """
 from __future__ import annotations
 
@@ -266,3 +272,182 @@ def plot_connections(image: np.ndarray, grouped_kpts_coords, grouped_kpts_scores
     image = np.ascontiguousarray(image, dtype=np.uint8)
     table = build_primitives(grouped_kpts_coords, grouped_kpts_scores, limbs, thr, color_mode, DEFAULT_PALETTE, alpha)
     return to_host(render_frames_device([image], [table], alpha)[0])
+
+
+# ---------------------------------------------------------------- heatmap panels (hh_heatmap_panels_u8)
+# hh_panel_map of include/hhrnet.h
+PANEL = np.dtype([("src", "<u8"), ("src2", "<u8"), ("h", "<i4"), ("w", "<i4"), ("kind", "<i4"), ("flags", "<i4"), ("oy", "<i4"), ("ox", "<i4")])
+assert PANEL.itemsize == 40
+DIRECT, SINGLE, NESTED, AVERAGE = 0, 1, 2, 3   # HH_PANEL_*
+CLIP, MINMAX = 1, 2
+PANEL_MAX_MAPS = 256                           # HH_PANEL_MAX_MAPS
+PANEL_PARTS = 32                               # HH_PANEL_PARTS
+MEAN = (0.485, 0.456, 0.406)                   # base/transforms/base.py:5-6
+STD = (0.229, 0.224, 0.225)
+
+
+def jet_lut() -> np.ndarray:
+    """The default colour table, uint8 [256,3] in B,G,R order as cv2.applyColorMap(arange(256), COLORMAP_JET) lists it: channel X of
+    entry i is (X2 + 1) >> 1 with X2 = clamp(765 - |8 i - 510 k|, 0, 510), k = 1 (B), 2 (G), 3 (R).  A reading of OpenCV's table;
+    parity with cv2 is UNPINNED (include/hhrnet.h).  The panels take any [256,3] table in its place."""
+    i = np.arange(256, dtype=np.int64)[:, None]
+    x2 = np.clip(765 - np.abs(8 * i - 510 * np.array([1, 2, 3], np.int64)[None, :]), 0, 510)
+    return ((x2 + 1) >> 1).astype(np.uint8)
+
+
+def grid_layout(n: int, nrows: int, H: int, W: int, pad: int) -> tuple[int, int, list]:
+    """make_grid (utils/image.py:25-36) as bookkeeping: (grid height, grid width, [(y, x) of cell 0..n-1])."""
+    if n < 1 or nrows < 1 or pad < 0:
+        raise ValueError("grid_layout: need n >= 1, nrows >= 1, pad >= 0")
+    ncols = -(-n // nrows)
+    return (H + pad) * nrows + pad, (W + pad) * ncols + pad, [(pad + (i // ncols) * (H + pad), pad + (i % ncols) * (W + pad)) for i in range(n)]
+
+
+def figure_layout(grids: list, H: int, W: int) -> tuple[list, int, int]:
+    """The grids of a figure stacked vertically (np.concatenate(axis=0): all must come out equally wide).  grids: [(maps, nrows, pad)],
+    maps a list of (kind, src, src2, flags).  -> ([(kind, src, src2, flags, oy, ox)], canvas height, canvas width)."""
+    placed, top, width = [], 0, None
+    for maps, nrows, pad in grids:
+        gh, gw, at = grid_layout(len(maps), nrows, H, W, pad)
+        if width not in (None, gw):
+            raise ValueError("figure_layout: the grids of a figure must have one width")
+        width = gw
+        placed += [(kind, src, src2, flags, top + y, x) for (kind, src, src2, flags), (y, x) in zip(maps, at)]
+        top += gh
+    return placed, top, width
+
+
+def _panel_table(placed: list, ptr) -> np.ndarray:
+    table = np.zeros(len(placed), PANEL)
+    for i, (kind, src, src2, flags, oy, ox) in enumerate(placed):
+        table[i] = (ptr(src), ptr(src2) if src2 is not None else 0, src.shape[0], src.shape[1], kind, flags, oy, ox)
+    return table
+
+
+def panels_host(image: np.ndarray, placed: list, Hc: int, Wc: int, lut: np.ndarray | None = None) -> np.ndarray:
+    """hh_debug_heatmap_panels_host: one figure through the kernels' arithmetic compiled for the host (tests; needs the library, no
+    GPU).  placed: [(kind, src, src2, flags, oy, ox)] with float32 numpy planes."""
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    lut = np.ascontiguousarray(jet_lut() if lut is None else lut, dtype=np.uint8)
+    keep = [(k, np.ascontiguousarray(a, np.float32), None if b is None else np.ascontiguousarray(b, np.float32), f, oy, ox) for k, a, b, f, oy, ox in placed]
+    table = _panel_table(keep, lambda a: a.ctypes.data)
+    out = np.empty((Hc, Wc, 3), np.uint8)
+    _lib.check(_lib.load().hh_debug_heatmap_panels_host(table.ctypes.data, len(table), image.ctypes.data, image.shape[0], image.shape[1],
+                                                        lut.ctypes.data, out.ctypes.data, Hc, Wc, Wc * 3))
+    return out
+
+
+def panels_device(image: torch.Tensor, placed: list, Hc: int, Wc: int, lut: np.ndarray | None = None, canvas: torch.Tensor | None = None,
+                  pitch: int | None = None) -> torch.Tensor:
+    """One hh_heatmap_panels_u8 on the current stream: every map of a figure resampled, coloured, blended over `image` (contiguous
+    device uint8 [H,W,3]) and tiled, padding and unused cells zeroed.  placed: [(kind, src, src2, flags, oy, ox)], src / src2
+    contiguous device float32 planes that the caller keeps alive until the stream has passed this call.  The table and the colour
+    table travel in one async copy from one pinned block.  `canvas` / `pitch`: write into the caller's uint8 device buffer (row r at
+    byte r * pitch of it) instead of a fresh contiguous [Hc,Wc,3].  -> the canvas."""
+    if not (image.dtype == torch.uint8 and image.is_cuda and image.is_contiguous() and image.dim() == 3 and image.shape[2] == 3):
+        raise ValueError("panels_device: the image must be a contiguous device uint8 [H,W,3] tensor")
+    device = image.device
+    H, W = int(image.shape[0]), int(image.shape[1])
+    for kind, src, src2, *_ in placed:
+        for t in (src,) + ((src2,) if src2 is not None else ()):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == device and t.is_contiguous() and t.dim() == 2):
+                raise ValueError("panels_device: a map must be a contiguous float32 [h,w] tensor on the image's device")
+    lut = np.ascontiguousarray(jet_lut() if lut is None else lut, dtype=np.uint8)
+    if lut.shape != (256, 3):
+        raise ValueError("panels_device: the colour table must be uint8 [256,3]")
+    n = len(placed)
+    lut_at = _align(PANEL.itemsize * n)
+    host = torch.empty(lut_at + 768, dtype=torch.uint8).pin_memory()
+    hv = host.numpy()
+    table = hv[:PANEL.itemsize * n].view(PANEL)
+    table[:] = _panel_table(placed, lambda t: t.data_ptr())
+    hv[lut_at:] = lut.reshape(-1)
+    buf = torch.empty(lut_at + 768, dtype=torch.uint8, device=device)
+    buf.copy_(host, non_blocking=True)
+    scratch = torch.empty(max(n, 1) * PANEL_PARTS * 2, dtype=torch.float32, device=device)
+    if canvas is None:
+        canvas, pitch = torch.empty((Hc, Wc, 3), dtype=torch.uint8, device=device), Wc * 3
+    elif not (canvas.dtype == torch.uint8 and canvas.device == device and canvas.is_contiguous() and pitch is not None
+              and canvas.numel() >= (Hc - 1) * pitch + Wc * 3):
+        raise ValueError("panels_device: the canvas must be a contiguous device uint8 buffer that holds Hc rows of `pitch` bytes")
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().hh_heatmap_panels_u8(buf.data_ptr(), table.ctypes.data, n, image.data_ptr(), H, W, buf.data_ptr() + lut_at,
+                                                    canvas.data_ptr(), Hc, Wc, pitch, scratch.data_ptr(),
+                                                    torch.cuda.current_stream(device).cuda_stream))
+    return canvas
+
+
+def unnormalize_device(x: torch.Tensor, mean=MEAN, std=STD) -> torch.Tensor:
+    """KeypointsTransform.inverse_transform (base/transforms/base.py:33-41) of a device float32 [3,H,W] tensor -> device uint8 [H,W,3]
+    on the current stream (hh_unnormalize_u8)."""
+    import ctypes as C
+    if not (x.dtype == torch.float32 and x.is_cuda and x.dim() == 3 and x.shape[0] == 3):
+        raise ValueError("unnormalize_device: a device float32 [3,H,W] tensor is needed")
+    x = x.contiguous()
+    out = torch.empty((x.shape[1], x.shape[2], 3), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().hh_unnormalize_u8(x.data_ptr(), x.shape[1], x.shape[2], (C.c_double * 3)(*mean), (C.c_double * 3)(*std), out.data_ptr(),
+                                                 torch.cuda.current_stream(x.device).cuda_stream))
+    return out
+
+
+def scaled_size(n: int, f: float) -> int:
+    """cvRound(n * f): to nearest, half to even."""
+    return int(round(float(n) * float(f)))
+
+
+def resize_scaled_device(src: torch.Tensor, fx: float, fy: float) -> torch.Tensor:
+    """cv2.resize(src, (0, 0), fx=fx, fy=fy) of a contiguous device uint8 [h,w] or [h,w,3] tensor on the current stream
+    (hh_resize_u8_scaled)."""
+    if not (src.dtype == torch.uint8 and src.is_cuda and src.is_contiguous() and (src.dim() == 2 or (src.dim() == 3 and src.shape[2] in (1, 3)))):
+        raise ValueError("resize_scaled_device: a contiguous device uint8 [h,w], [h,w,1] or [h,w,3] tensor is needed")
+    ch = 1 if src.dim() == 2 else int(src.shape[2])
+    H, W = scaled_size(src.shape[0], fy), scaled_size(src.shape[1], fx)
+    out = torch.empty((H, W) + tuple(src.shape[2:]), dtype=torch.uint8, device=src.device)
+    with torch.cuda.device(src.device):
+        _lib.check(_lib.load().hh_resize_u8_scaled(src.data_ptr(), src.shape[0], src.shape[1], ch, float(fx), float(fy), out.data_ptr(), H, W,
+                                                   torch.cuda.current_stream(src.device).cuda_stream))
+    return out
+
+
+def figure_device(image: torch.Tensor, grids: list, fx: float | None = None, lut: np.ndarray | None = None) -> torch.Tensor:
+    """The grids of one figure (figure_layout) painted in one hh_heatmap_panels_u8 call, then shrunk by fx = fy (None: as painted).
+    -> device uint8 [h,w,3]."""
+    placed, Hc, Wc = figure_layout(grids, int(image.shape[0]), int(image.shape[1]))
+    canvas = panels_device(image, placed, Hc, Wc, lut)
+    return canvas if fx is None else resize_scaled_device(canvas, fx, fx)
+
+
+def stack_horizontally_device(images: list, pad: int = 5) -> torch.Tensor:
+    """stack_horizontally (utils/image.py:41-61) of device uint8 [h,w,3] tensors: the lower ones resized to the tallest one's height
+    (hh_resize_u8), all placed side by side on a zero canvas."""
+    new_h = max(int(im.shape[0]) for im in images)
+    resized = [im if im.shape[0] == new_h else resize_device(im.contiguous(), int(im.shape[1] / im.shape[0] * new_h), new_h) for im in images]
+    grid = torch.zeros((pad + new_h + pad, sum(int(im.shape[1]) + pad for im in resized) + pad, 3), dtype=torch.uint8, device=images[0].device)
+    x = pad
+    for im in resized:
+        grid[pad:pad + new_h, x:x + im.shape[1]] = im
+        x += int(im.shape[1]) + pad
+    return grid
+
+
+def plot_heatmaps(image, heatmaps, clip_0_1: bool = False, minmax: bool = False, lut: np.ndarray | None = None) -> list[np.ndarray]:
+    """The reference's plot_heatmaps (visualization.py:93-110), same signature plus the colour table: image uint8 [H,W,3], heatmaps
+    [K,H,W], each a numpy array (uploaded here) or a device tensor; the maps are taken as float32.  -> list of K uint8 [H,W,3].
+    Raises when the library or the GPU is missing."""
+    if not torch.cuda.is_available():
+        raise _lib.HHError("plot_heatmaps needs the GPU: there is no CPU renderer")
+    device = next((t.device for t in (image, heatmaps) if isinstance(t, torch.Tensor) and t.is_cuda), None) or torch.device("cuda", torch.cuda.current_device())
+    img = (image if isinstance(image, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(image, dtype=np.uint8))).to(device).contiguous()
+    hms = (heatmaps if isinstance(heatmaps, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(heatmaps, dtype=np.float32))).to(device, torch.float32).contiguous()
+    if hms.dim() != 3 or tuple(hms.shape[1:]) != tuple(img.shape[:2]):
+        raise ValueError("plot_heatmaps: heatmaps must be [K,H,W] with the image's H and W")
+    K, H, W = hms.shape
+    flags = (CLIP if clip_0_1 else 0) | (MINMAX if minmax else 0)
+    out = []
+    for first in range(0, K, PANEL_MAX_MAPS):
+        part = hms[first:first + PANEL_MAX_MAPS]
+        placed = [(DIRECT, m, None, flags, i * H, 0) for i, m in enumerate(part)]
+        cells = to_host(panels_device(img, placed, len(part) * H, W, lut))
+        out += [cells[i * H:(i + 1) * H] for i in range(len(part))]
+    return out
