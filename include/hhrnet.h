@@ -442,6 +442,68 @@ int hh_debug_heatmap_panels_host(const hh_panel_map *maps, int n, const unsigned
 int hh_unnormalize_u8(const float *x_chw, int H, int W, const double mean[3], const double stdv[3], unsigned char *out_hwc, void *stream);
 int hh_resize_u8_scaled(const unsigned char *src, int h, int w, int channels, double fx, double fy, unsigned char *dst, int H, int W,
                         void *stream);
+/* COCO keypoint scoring on the device: computeOks + evaluateImg of pycocotools' COCOeval(iouType="keypoints") as keypoints/coco_eval.py
+ * restates them (`_oks`, `_evaluate_img`; the `eval_coco` step of keypoints/bin/eval.py:52-65), for every image, area range and threshold
+ * in ONE launch over packed tables.  What is pinned is "device = this repository's host evaluator"; parity with pycocotools itself stays
+ * UNPINNED (the package is absent where the fixtures are made).  The arithmetic is csrc/coco_eval_math.h, shared with the host.
+ *
+ * The tables (keypoints.coco_eval.pack_tables builds them): I images; the detections of image i are rows dt_off[i] .. dt_off[i+1]-1 of
+ * the N detection rows, in the evaluator's order (stable by descending score, cut to maxDets = 20 by the packer; the kernels accept up
+ * to HH_COCO_MAX_DET); its ground truths rows gt_off[i] .. gt_off[i+1]-1 of the M ground-truth rows, in annotation order.  oks_off[i] is
+ * the sum of D_j * G_j over j < i.  All floating-point tables are fp64.  gt_flags: HH_COCO_GT_IGNORE (_prepare: iscrowd or
+ * num_keypoints == 0) | HH_COCO_GT_CROWD.  vars[k] = (2 sigma_k)^2, formed by the caller: the sigmas are a parameter.
+ *
+ * OKS of one pair, fp64, every operation rounded on its own: k1 = #{k : v_k > 0}; if k1 > 0, dx = xd - xg, dy = yd - yg, else the
+ * distance to the doubled box dx = max(0, x0 - xd) + max(0, xd - x1), x0 = bx - bw, x1 = bx + 2 bw (the same in y);
+ * e_k = (dx dx + dy dy) / vars[k] / (area + 2^-52) / 2; OKS = sum of exp(-e_k) over the labelled joints (all K when k1 = 0), ascending
+ * k, divided by their number.  e_k is bit-identical to numpy's; exp and the order of the sum may differ from the host evaluator.
+ * Matching of one (image, area range a, threshold t), no floating-point arithmetic: a ground truth is ignored iff its flag is set or its
+ * area is outside [lo_a, hi_a]; they are walked not-ignored first, each half in table order; per detection, in table order, the running
+ * best starts at min(t, 1 - 1e-10), a ground truth already matched is skipped unless it is a crowd, the walk stops when the best so far
+ * is not ignored and the ignored ones begin, an OKS below the running best is skipped (an equal one on a later ground truth wins).
+ *
+ * Outputs (device): dt_match int32 [A,T,N] = the matched ground truth's row in the table + 1, 0 for none; dt_ignore uint8 [A,T,N] = the
+ * matched ground truth's ignore flag, or "the detection's area is outside the range" when unmatched; gt_ignore uint8 [A,M] in table
+ * order.  Every element is written exactly once (no clearing first), nothing else is; nothing is carried between calls; deterministic.
+ * hh_coco_evaluate: the fused launch; the OKS values stay in LDS.  hh_coco_oks: only the OKS matrices, image i's D_i x G_i row-major at
+ *   oks[oks_off[i]], oks_off[I] doubles in all.  hh_coco_match: only the matching, on such a buffer of the caller's.
+ * hh_coco_evaluate_host: the same code compiled for the host over tables in HOST memory: with oks_in the matching alone on that buffer,
+ *   otherwise OKS (stored to oks_out if it is not null) and matching; the three outputs may all be null to get the OKS only.
+ * tables_dev / tables_host are two structs in HOST memory: the one holds the device addresses the kernel reads, the other the caller's
+ *   host copy of the same tables, which is what is checked (device memory is never read back).  Returns 1 with hh_last_error set, before
+ *   any launch, for a null pointer, a misaligned table, offsets that do not start at 0, decrease, or leave N / M, an image with more than
+ *   HH_COCO_MAX_DET detections or HH_COCO_MAX_GT ground truths (the message names the image), K, T or A over its limit, a non-finite
+ *   area, a var that is not finite and > 0, a NaN range or threshold.  (Additive entry points: HH_ABI_VERSION stays 3.)            */
+#define HH_COCO_MAX_DET 32 /* per image (the evaluator uses 20) */
+#define HH_COCO_MAX_GT 128 /* per image */
+#define HH_COCO_MAX_K 64
+#define HH_COCO_MAX_T 16
+#define HH_COCO_MAX_A 4
+enum { HH_COCO_GT_IGNORE = 1, HH_COCO_GT_CROWD = 2 };
+typedef struct hh_coco_tables {
+    const int32_t *dt_off;          /* [I+1] */
+    const int32_t *gt_off;          /* [I+1] */
+    const int64_t *oks_off;         /* [I+1] */
+    const double *dt_xy;            /* [N,K,2] */
+    const double *dt_score;         /* [N] (not read by the kernels) */
+    const double *dt_area;          /* [N] */
+    const double *gt_xyv;           /* [M,K,3] */
+    const double *gt_area;          /* [M] */
+    const double *gt_bbox;          /* [M,4] x, y, w, h */
+    const unsigned char *gt_flags;  /* [M] */
+    const double *vars;             /* [K] */
+    const double *area_rng;         /* [A,2] */
+    const double *thr;              /* [T] */
+    int32_t I, N, M, K, A, T;
+    int32_t reserved[2];
+} hh_coco_tables;
+int hh_coco_oks(const hh_coco_tables *tables_dev, const hh_coco_tables *tables_host, double *oks, void *stream);
+int hh_coco_match(const hh_coco_tables *tables_dev, const hh_coco_tables *tables_host, const double *oks, int32_t *dt_match,
+                  unsigned char *dt_ignore, unsigned char *gt_ignore, void *stream);
+int hh_coco_evaluate(const hh_coco_tables *tables_dev, const hh_coco_tables *tables_host, int32_t *dt_match, unsigned char *dt_ignore,
+                     unsigned char *gt_ignore, void *stream);
+int hh_coco_evaluate_host(const hh_coco_tables *tables_host, const double *oks_in, double *oks_out, int32_t *dt_match,
+                          unsigned char *dt_ignore, unsigned char *gt_ignore);
 /* HeatmapGenerator (coco.py:77-121) as a gather over the packed joints the grouping loss takes (hh_loss_ae_grouping: joints int32
  * [B,P,K,3] = x, y, vis from JointsGenerator, coco.py:124-137; num_people [B]): out fp32 [B,K,h,w], each element the maximum over
  * the image's people p < num_people[b] with vis > 0 and (x, y) inside the map of table[y - y_p + reach][x - x_p + reach] where that

@@ -85,6 +85,11 @@ def _sig(lib):
         "hh_unnormalize_u8": (i32, [vp, i32, i32, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp]),
         "hh_heatmap_panels_u8": (i32, [vp, vp, i32, vp, i32, i32, vp, vp, i32, i32, C.c_longlong, vp, vp]),
         "hh_debug_heatmap_panels_host": (i32, [vp, i32, vp, i32, i32, vp, vp, i32, i32, C.c_longlong]),
+        # COCO keypoint scoring (keypoints/coco_eval.py): tables_dev, tables_host = hh_coco_tables structs in host memory
+        "hh_coco_oks": (i32, [vp, vp, vp, vp]),
+        "hh_coco_match": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+        "hh_coco_evaluate": (i32, [vp, vp, vp, vp, vp, vp]),
+        "hh_coco_evaluate_host": (i32, [vp, vp, vp, vp, vp, vp]),
         "hh_heatmap_table_size": (i32, [dbl, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "hh_render_heatmaps": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp]),
         "hh_flip_images": (i32, [vp, vp, i32, i32, i32, i32, vp]),

@@ -10,6 +10,7 @@
 #include "optim_math.h"
 #include "render_math.h"
 #include "panel_math.h"
+#include "coco_eval_math.h"
 
 const char *hh_get_error();
 int hh_tap_read_impl(hh_net *n, int index, float *host);
@@ -411,6 +412,81 @@ int hh_debug_heatmap_panels_host(const hh_panel_map *maps, int n, const unsigned
     if (panels_check(fn, maps, n, image, H, W, lut, canvas, Hc, Wc, pitch, &any_minmax)) return 1;
     std::vector<PanelRange> ranges(n);
     panels_debug_host(reinterpret_cast<const PanelMap *>(maps), n, image, H, W, lut, canvas, Hc, Wc, pitch, ranges.data());
+    return 0;
+}
+
+// The checks of a COCO scoring call that need no device: the host copy's contents (coco_check), and of the device copy only that its
+// pointers are there and aligned and that its counts are the host copy's.  Nothing behind a device pointer is read.
+static int coco_tables_check(const char *fn, const hh_coco_tables *dev, const hh_coco_tables *host)
+{
+    static_assert(sizeof(hh_coco_tables) == sizeof(CocoTables), "table layout");
+    static_assert(HH_COCO_MAX_DET == COCO_MAX_DET && HH_COCO_MAX_GT == COCO_MAX_GT && HH_COCO_MAX_K == COCO_MAX_K && HH_COCO_MAX_T == COCO_MAX_T &&
+                      HH_COCO_MAX_A == COCO_MAX_A && HH_COCO_GT_IGNORE == COCO_GT_IGNORE && HH_COCO_GT_CROWD == COCO_GT_CROWD,
+                  "limits and flags of include/hhrnet.h");
+    char msg[192];
+    const char *why = coco_check(reinterpret_cast<const CocoTables *>(host), msg, sizeof msg);
+    if (why) { hh_set_error(std::string(fn) + ": " + why); return 1; }
+    if (!dev) return 0;  // (the host entry point)
+    const void *p8[] = {dev->oks_off, dev->dt_xy, dev->dt_score, dev->dt_area, dev->gt_xyv, dev->gt_area, dev->gt_bbox, dev->vars, dev->area_rng, dev->thr};
+    for (const void *p : p8) {
+        if (!p) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+        if ((uintptr_t)p % 8) { hh_set_error(std::string(fn) + ": a device table is not 8-byte aligned"); return 1; }
+    }
+    if (!dev->dt_off || !dev->gt_off || !dev->gt_flags) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if ((uintptr_t)dev->dt_off % 4 || (uintptr_t)dev->gt_off % 4) { hh_set_error(std::string(fn) + ": a device table is not 4-byte aligned"); return 1; }
+    if (dev->I != host->I || dev->N != host->N || dev->M != host->M || dev->K != host->K || dev->A != host->A || dev->T != host->T) {
+        hh_set_error(std::string(fn) + ": the device tables' counts differ from the host copy's");
+        return 1;
+    }
+    return 0;
+}
+static int coco_outputs_check(const char *fn, const int32_t *dt_match, const uint8_t *dt_ignore, const uint8_t *gt_ignore)
+{
+    if (!dt_match || !dt_ignore || !gt_ignore) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if ((uintptr_t)dt_match % 4) { hh_set_error(std::string(fn) + ": dt_match is not 4-byte aligned"); return 1; }
+    return 0;
+}
+
+int hh_coco_oks(const hh_coco_tables *tables_dev, const hh_coco_tables *tables_host, double *oks, void *stream)
+{
+    const char *fn = "hh_coco_oks";
+    if (!tables_dev || !oks) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if ((uintptr_t)oks % 8) { hh_set_error(std::string(fn) + ": oks is not 8-byte aligned"); return 1; }
+    if (coco_tables_check(fn, tables_dev, tables_host)) return 1;
+    HH_CHECK_HIP(launch_coco_eval(1, *reinterpret_cast<const CocoTables *>(tables_dev), nullptr, oks, nullptr, nullptr, nullptr, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_coco_match(const hh_coco_tables *tables_dev, const hh_coco_tables *tables_host, const double *oks, int32_t *dt_match, unsigned char *dt_ignore,
+                  unsigned char *gt_ignore, void *stream)
+{
+    const char *fn = "hh_coco_match";
+    if (!tables_dev || !oks) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if ((uintptr_t)oks % 8) { hh_set_error(std::string(fn) + ": oks is not 8-byte aligned"); return 1; }
+    if (coco_outputs_check(fn, dt_match, dt_ignore, gt_ignore) || coco_tables_check(fn, tables_dev, tables_host)) return 1;
+    HH_CHECK_HIP(launch_coco_eval(2, *reinterpret_cast<const CocoTables *>(tables_dev), oks, nullptr, dt_match, dt_ignore, gt_ignore, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_coco_evaluate(const hh_coco_tables *tables_dev, const hh_coco_tables *tables_host, int32_t *dt_match, unsigned char *dt_ignore,
+                     unsigned char *gt_ignore, void *stream)
+{
+    const char *fn = "hh_coco_evaluate";
+    if (!tables_dev) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if (coco_outputs_check(fn, dt_match, dt_ignore, gt_ignore) || coco_tables_check(fn, tables_dev, tables_host)) return 1;
+    HH_CHECK_HIP(launch_coco_eval(0, *reinterpret_cast<const CocoTables *>(tables_dev), nullptr, nullptr, dt_match, dt_ignore, gt_ignore, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_coco_evaluate_host(const hh_coco_tables *tables_host, const double *oks_in, double *oks_out, int32_t *dt_match, unsigned char *dt_ignore,
+                          unsigned char *gt_ignore)
+{
+    const char *fn = "hh_coco_evaluate_host";
+    const bool match = dt_match || dt_ignore || gt_ignore;
+    if (match && coco_outputs_check(fn, dt_match, dt_ignore, gt_ignore)) return 1;
+    if (!match && !oks_out) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if (coco_tables_check(fn, nullptr, tables_host)) return 1;
+    coco_eval_host(*reinterpret_cast<const CocoTables *>(tables_host), oks_in, oks_in ? nullptr : oks_out, match, dt_match, dt_ignore, gt_ignore);
     return 0;
 }
 

@@ -370,6 +370,12 @@ hipError_t launch_panels(const PanelMap *maps, int n, bool any_minmax, const uns
 void panels_debug_host(const PanelMap *maps, int n, const unsigned char *image, int H, int W, const unsigned char *lut, unsigned char *canvas, int Hc,
                        int Wc, long long pitch, PanelRange *ranges);
 hipError_t launch_unnormalize_u8(const float *x, int H, int W, unsigned char *out, const double *mean, const double *stdv, hipStream_t s);
+// COCO keypoint scoring (hh_coco_tables of include/hhrnet.h; struct, OKS and matching walk in coco_eval_math.h, kernel in coco_eval.hip):
+// mode 0 = OKS + matching fused, 1 = OKS only into oks_out, 2 = matching only from oks_in; the same on the host.
+struct CocoTables;
+hipError_t launch_coco_eval(int mode, const CocoTables &dev, const double *oks_in, double *oks_out, int32_t *dt_match, uint8_t *dt_ignore, uint8_t *gt_ignore,
+                            hipStream_t s);
+void coco_eval_host(const CocoTables &t, const double *oks_in, double *oks_out, bool match, int32_t *dt_match, uint8_t *dt_ignore, uint8_t *gt_ignore);
 // target heatmaps from the packed joints (train_input.hip); n = table side = 2 * reach + 1 <= HH_RENDER_MAX_N, w <= HH_RENDER_MAX_W
 #define HH_RENDER_MAX_N 63
 #define HH_RENDER_MAX_W 4096

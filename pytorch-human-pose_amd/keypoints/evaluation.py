@@ -1,7 +1,8 @@
 """COCO result packing of the evaluation harness (`src/keypoints/bin/eval.py:18-49`).
 
-Only the packing and the image-sharded loop live here: AP itself is computed by pycocotools 2.0.7 in the reference
-(`bin/eval.py:52-65`), a third-party evaluator that is not in this image, so nothing below restates it.
+The packing and the image-sharded loop live here.  AP itself is computed by pycocotools 2.0.7 in the reference (`bin/eval.py:52-65`),
+a third-party evaluator that is not in this image; `keypoints.coco_eval` restates it, on the host and on the device, and
+`evaluate_images(..., gt_annotations=..., score_device=...)` runs the device form on the gathered list.
 """
 from __future__ import annotations
 
@@ -32,13 +33,17 @@ def pack_coco_results(image_id: int, kpts_coords: np.ndarray, obj_scores: np.nda
     return results
 
 
-def evaluate_images(model, images, image_ids, rank: int = 0, world_size: int = 1, multi_scale=None, batch: int = 32) -> list[dict] | None:
+def evaluate_images(model, images, image_ids, rank: int = 0, world_size: int = 1, multi_scale=None, batch: int = 32, gt_annotations=None,
+                    score_device=None):
     """evaluate_dataset (bin/eval.py:18-49) over in-memory images, sharded by image across ranks (§8e: contiguous
     slices, no data-path collective; the packed lists are gathered to rank 0, other ranks get None).
     `multi_scale` = tuple of scales -> `model.call_multi_scale` (the cfg-4 extension) instead of `model(...)`.
     `batch` > 1 routes both cases through `model.infer_images` (identical per-image results, one forward and one decode per
     shape bucket; with `multi_scale`, `infer_images(scales=multi_scale)`: the forwards of plan_multi_scale and one fused
-    aggregation per stage); `batch` = 1 is the reference's image-by-image loop."""
+    aggregation per stage); `batch` = 1 is the reference's image-by-image loop.
+    With both `gt_annotations` (the "annotations" list of a person_keypoints json) and `score_device` (e.g. "cuda:0") rank 0 returns
+    (packed list, stats): the list scored over `image_ids` by `coco_eval.evaluate_device`, the `eval_coco` step on the device; the
+    other ranks return (None, None).  Without them the return value is the packed list alone, as before."""
     local = []
     mine = list(shard_range(len(images), rank, world_size))
     if batch <= 1:
@@ -49,4 +54,10 @@ def evaluate_images(model, images, image_ids, rank: int = 0, world_size: int = 1
         kw = {"scales": multi_scale} if multi_scale else {}
         for idx, res in zip(mine, model.infer_images([images[i] for i in mine], max_batch=batch, **kw)):
             local += pack_coco_results(image_ids[idx], res.kpts_coords, res.obj_scores)
-    return gather_results(local)
+    packed = gather_results(local)
+    if gt_annotations is None or score_device is None:
+        return packed
+    if packed is None:
+        return None, None
+    from .coco_eval import evaluate_device
+    return packed, evaluate_device(gt_annotations, packed, score_device, img_ids=[int(i) for i in image_ids])[2]
