@@ -32,7 +32,5 @@ class ClassificationHRNet(EngineModule):
         x = self._check_input(images)
         B, _, H, W = x.shape
         logits = torch.empty((B, self.num_classes), device=x.device, dtype=torch.float32)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        with torch.cuda.device(x.device):
-            _lib.check(self._lib.hh_forward_classifier(self._h, x.data_ptr(), B, H, W, logits.data_ptr(), stream))
+        _lib.launch(x.device, self._lib.hh_forward_classifier, self._h, x.data_ptr(), B, H, W, logits.data_ptr())
         return logits

@@ -22,7 +22,6 @@ against torch's own F.interpolate and a float64 restatement (tests/cls_input_bud
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from dataclasses import dataclass
 
@@ -211,10 +210,9 @@ class ClsInput:
             self._stage_free[turn] = copied
             self.last_h2d_bytes, self.last_launches = total, 1
             images = torch.empty((B, 3, S, S), device=dev, dtype=torch.float32)
-            fp = C.POINTER(C.c_float)
             base = raw.data_ptr()
             # the descriptors are checked on their HOST copy in the staging buffer (nothing is read back from the device)
-            _lib.check(lib.hh_resized_crop_u8_batch(base, base + desc_off, descs.ctypes.data, B, images.data_ptr(), S, S,
-                                                    self.mean.ctypes.data_as(fp), self.std.ctypes.data_as(fp), cur.cuda_stream))
+            _lib.launch(dev, lib.hh_resized_crop_u8_batch, base, base + desc_off, descs.ctypes.data, B, images.data_ptr(), S, S,
+                        self.mean.ctypes.data, self.std.ctypes.data)
             targets = raw[target_off:total].view(torch.int64)
         return images, targets

@@ -100,7 +100,8 @@ class EngineModule(nn.Module):
         if not images.is_cuda:
             raise _lib.HHError(f"{type(self).__name__} forward needs a CUDA/HIP tensor: there is no CPU path")
         if self._dirty:
-            self.sync_weights()
+            with torch.cuda.device(images.device):  # hh_finalize allocates and uploads on the current device: where the forward runs
+                self.sync_weights()
         x = images.contiguous().float()
         assert x.dim() == 4 and x.shape[1] == 3
         return x
@@ -140,9 +141,7 @@ class HigherHRNet(EngineModule):
         (load_state_dict, optimizer steps) invalidate it."""
         x = self._check_input(images)
         B, _, H, W = x.shape
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        with torch.cuda.device(x.device):
-            _lib.check(self._lib.hh_calibrate(self._h, x.data_ptr(), B, H, W, rounds, stream))
+        _lib.launch(x.device, self._lib.hh_calibrate, self._h, x.data_ptr(), B, H, W, rounds)
 
     def forward_raw(self, images: Tensor, out: tuple[Tensor, Tensor] | None = None) -> tuple[Tensor, Tensor]:
         """-> (init_heatmaps [B,2K,H/4,W/4], deconv_heatmaps [B,K,H/2,W/2]) fp32.
@@ -157,10 +156,7 @@ class HigherHRNet(EngineModule):
         else:
             init = torch.empty((B, 2 * K, H // 4, W // 4), device=x.device, dtype=torch.float32)
             dec = torch.empty((B, K, H // 2, W // 2), device=x.device, dtype=torch.float32)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        with torch.cuda.device(x.device):
-            _lib.check(self._lib.hh_forward(self._h, x.data_ptr(), B, H, W, init.data_ptr(), dec.data_ptr(),
-                                            int(self.use_graph), stream))
+        _lib.launch(x.device, self._lib.hh_forward, self._h, x.data_ptr(), B, H, W, init.data_ptr(), dec.data_ptr(), int(self.use_graph))
         return init, dec
 
     def forward(self, images: Tensor) -> tuple[list[Tensor], Tensor]:

@@ -348,9 +348,8 @@ def match_tables_device(tables: dict, device):
     out = torch.empty(n_match * 4 + n_match + A * M + 8, dtype=torch.uint8, device=device)  # dt_match | dt_ignore | gt_ignore
     dev = tables_struct(tables, lambda n: dev_blob.data_ptr() + offs[n])
     host = host_struct(tables)
-    with torch.cuda.device(dev_blob.device):
-        _lib.check(lib.hh_coco_evaluate(ctypes.byref(dev), ctypes.byref(host), out.data_ptr(), out.data_ptr() + n_match * 4, out.data_ptr() + n_match * 5,
-                                        torch.cuda.current_stream().cuda_stream))
+    _lib.launch(dev_blob.device, lib.hh_coco_evaluate, ctypes.byref(dev), ctypes.byref(host), out.data_ptr(), out.data_ptr() + n_match * 4,
+                out.data_ptr() + n_match * 5)
     back = out.cpu().numpy()
     dt_match = back[:n_match * 4].view(np.int32).reshape(A, T, N)
     dt_ignore = back[n_match * 4:n_match * 5].reshape(A, T, N) != 0

@@ -67,10 +67,8 @@ class MPPEHeatmapParser:
         E = tg.shape[-1]
         assert K == self.num_kpts and tuple(tg.shape[:4]) == (B, K, H, W)
         joints, scores, num, flags = self._outputs(B, E, hm.device)
-        stream = torch.cuda.current_stream(hm.device).cuda_stream
-        with torch.cuda.device(hm.device):
-            _lib.check(self._lib.hh_parse(self._h, hm.data_ptr(), tg.data_ptr(), E, B, H, W, int(adjust), int(refine),
-                                          joints.data_ptr(), scores.data_ptr(), num.data_ptr(), flags.data_ptr(), stream))
+        _lib.launch(hm.device, self._lib.hh_parse, self._h, hm.data_ptr(), tg.data_ptr(), E, B, H, W, int(adjust), int(refine),
+                    joints.data_ptr(), scores.data_ptr(), num.data_ptr(), flags.data_ptr())
         return joints, scores, num, flags
 
     def decode_batch_device(self, hm_q: Tensor, hm_h: Tensor, tags_q: list[Tensor], adjust: bool = True, refine: bool = True):
@@ -91,12 +89,9 @@ class MPPEHeatmapParser:
         joints, scores, num, flags = self._outputs(B, E, hm_q.device)
         tptr = (C.c_void_p * E)(*[t.data_ptr() for t in tags_q])
         tbs = (C.c_int64 * E)(*[t.stride(0) for t in tags_q])
-        stream = torch.cuda.current_stream(hm_q.device).cuda_stream
         self._keep = (hm_q, hm_h, tags_q)
-        with torch.cuda.device(hm_q.device):
-            _lib.check(self._lib.hh_decode(self._h, hm_q.data_ptr(), hm_q.stride(0), hm_h.data_ptr(), hm_h.stride(0), tptr, tbs,
-                                           E, B, hq, wq, int(adjust), int(refine), joints.data_ptr(), scores.data_ptr(),
-                                           num.data_ptr(), flags.data_ptr(), stream))
+        _lib.launch(hm_q.device, self._lib.hh_decode, self._h, hm_q.data_ptr(), hm_q.stride(0), hm_h.data_ptr(), hm_h.stride(0), tptr, tbs,
+                    E, B, hq, wq, int(adjust), int(refine), joints.data_ptr(), scores.data_ptr(), num.data_ptr(), flags.data_ptr())
         return joints, scores, num, flags
 
     @staticmethod

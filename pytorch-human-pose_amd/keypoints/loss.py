@@ -47,11 +47,8 @@ class _HeatmapsLossFn(torch.autograd.Function):
             raise ValueError(f"HeatmapsLoss: shapes {tuple(pred.shape)}, {tuple(target.shape)}, {tuple(mask.shape)} do not match")
         loss = torch.empty((), device=p.device, dtype=torch.float32)
         grad = torch.empty((B, K, h, w), device=p.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
-        stream = torch.cuda.current_stream(p.device).cuda_stream
-        with torch.cuda.device(p.device):
-            _lib.check(lib.hh_loss_heatmaps(p.data_ptr(), p.stride(0), t.data_ptr(), m.data_ptr(), B, K, h, w, loss.data_ptr(),
-                                            grad.data_ptr() if grad is not None else None, K * h * w,
-                                            _scratch(p.device, 0).data_ptr(), stream))
+        _lib.launch(p.device, lib.hh_loss_heatmaps, p.data_ptr(), p.stride(0), t.data_ptr(), m.data_ptr(), B, K, h, w, loss.data_ptr(),
+                    _lib.ptr(grad), K * h * w, _scratch(p.device, 0).data_ptr())
         ctx.grad, ctx.dtype = grad, pred.dtype
         return loss
 
@@ -97,21 +94,16 @@ class _AEGroupingFn(torch.autograd.Function):
         B, K, h, w = t.shape
         P = packed.shape[1]
         out = torch.empty(2, device=t.device, dtype=torch.float32)
-        stream = torch.cuda.current_stream(t.device).cuda_stream
         need = ctx.needs_input_grad[0]
         # push and pull get separate gradient maps: the caller may weight the two losses differently
         gpush = torch.zeros((B, K, h, w), device=t.device, dtype=torch.float32) if need else None
         gpull = torch.zeros((B, K, h, w), device=t.device, dtype=torch.float32) if need else None
-        with torch.cuda.device(t.device):
-            sc = _scratch(t.device, 2 * B)
-            if need:
-                _lib.check(lib.hh_loss_ae_grouping(t.data_ptr(), t.stride(0), packed.data_ptr(), counts.data_ptr(), B, P, K, h, w,
-                                                   out.data_ptr(), gpush.data_ptr(), K * h * w, 1.0, 0.0, sc.data_ptr(), stream))
-                _lib.check(lib.hh_loss_ae_grouping(t.data_ptr(), t.stride(0), packed.data_ptr(), counts.data_ptr(), B, P, K, h, w,
-                                                   out.data_ptr(), gpull.data_ptr(), K * h * w, 0.0, 1.0, sc.data_ptr(), stream))
-            else:
-                _lib.check(lib.hh_loss_ae_grouping(t.data_ptr(), t.stride(0), packed.data_ptr(), counts.data_ptr(), B, P, K, h, w,
-                                                   out.data_ptr(), None, 0, 0.0, 0.0, sc.data_ptr(), stream))
+        sc = _scratch(t.device, 2 * B)
+        # (grad, its batch stride, push scale, pull scale) of each launch
+        passes = ((gpush.data_ptr(), K * h * w, 1.0, 0.0), (gpull.data_ptr(), K * h * w, 0.0, 1.0)) if need else ((None, 0, 0.0, 0.0),)
+        for grad_args in passes:
+            _lib.launch(t.device, lib.hh_loss_ae_grouping, t.data_ptr(), t.stride(0), packed.data_ptr(), counts.data_ptr(), B, P, K, h, w,
+                        out.data_ptr(), *grad_args, sc.data_ptr())
         ctx.gpush, ctx.gpull, ctx.dtype = gpush, gpull, pred_tags.dtype
         return out[0], out[1]
 

@@ -278,15 +278,11 @@ class InferenceKeypointsModel:
     def prepare_input_scaled(self, image: np.ndarray, current_scale: float, min_scale: float):
         """prepare_input for one entry of a multi-scale test (get_multi_scale_size, base/transforms/utils.py:60-86)."""
         size, center, scale = get_multi_scale_size(image, self.input_size, current_scale, min_scale)
-        m = dst_to_src_matrix(center, scale, size)
+        m = dst_to_src_matrix(center, scale, size)  # destination -> source, as cv2.warpAffine inverts the forward matrix
         raw = torch.from_numpy(np.ascontiguousarray(image, dtype=np.uint8)).to(self.device)
         x = torch.empty((1, 3, size[1], size[0]), device=self.device, dtype=torch.float32)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        with torch.cuda.device(x.device):
-            _lib.check(self._lib.hh_preprocess_u8(raw.data_ptr(), image.shape[0], image.shape[1],
-                                                  m.ctypes.data_as(C.POINTER(C.c_double)), x.data_ptr(), size[1], size[0],
-                                                  IMAGENET_MEAN.ctypes.data_as(C.POINTER(C.c_float)),
-                                                  IMAGENET_STD.ctypes.data_as(C.POINTER(C.c_float)), stream))
+        _lib.launch(x.device, self._lib.hh_preprocess_u8, raw.data_ptr(), image.shape[0], image.shape[1], m.ctypes.data, x.data_ptr(),
+                    size[1], size[0], IMAGENET_MEAN.ctypes.data, IMAGENET_STD.ctypes.data)
         self._keep_raw = raw
         return x, center, scale
 
@@ -303,16 +299,14 @@ class InferenceKeypointsModel:
         hms_b, tags_b = self.forward_tta(xb)
         K = self.net.num_kpts
         acc = [torch.empty_like(hms_b[0].contiguous()), torch.empty_like(hms_b[1].contiguous())]
-        stream = torch.cuda.current_stream(xb.device).cuda_stream
         wgt = 1.0 / len(scales)
         first = True
         for s in scales:
             hms = hms_b if s == 1.0 else self.forward_tta(self.prepare_input_scaled(raw_image, s, mn)[0])[0]
             for st in range(2):
                 src = hms[st]
-                _lib.check(self._lib.hh_resize_accumulate(src.data_ptr(), src.stride(0), 1, K, src.shape[2], src.shape[3],
-                                                          acc[st].data_ptr(), acc[st].stride(0), acc[st].shape[2], acc[st].shape[3],
-                                                          wgt, int(first), stream))
+                _lib.launch(xb.device, self._lib.hh_resize_accumulate, src.data_ptr(), src.stride(0), 1, K, src.shape[2], src.shape[3],
+                            acc[st].data_ptr(), acc[st].stride(0), acc[st].shape[2], acc[st].shape[3], wgt, int(first))
             first = False
         return acc, [t.contiguous() for t in tags_b], xb, center, scale
 
@@ -325,28 +319,16 @@ class InferenceKeypointsModel:
     def prepare_input(self, image: np.ndarray):
         """model.py:70-76: resize-align -> ToTensor -> Normalize -> [1,3,h,w] on device.  Only the raw uint8 image
         crosses PCIe; warp + normalisation run in hh_preprocess_u8."""
-        size, center, scale = get_multi_scale_size(image, self.input_size, 1, 1)
-        m = dst_to_src_matrix(center, scale, size)  # destination -> source, as cv2.warpAffine inverts the forward matrix
-        raw = torch.from_numpy(np.ascontiguousarray(image, dtype=np.uint8)).to(self.device)
-        x = torch.empty((1, 3, size[1], size[0]), device=self.device, dtype=torch.float32)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        with torch.cuda.device(x.device):
-            _lib.check(self._lib.hh_preprocess_u8(raw.data_ptr(), image.shape[0], image.shape[1],
-                                                  m.ctypes.data_as(C.POINTER(C.c_double)), x.data_ptr(), size[1], size[0],
-                                                  IMAGENET_MEAN.ctypes.data_as(C.POINTER(C.c_float)),
-                                                  IMAGENET_STD.ctypes.data_as(C.POINTER(C.c_float)), stream))
-        self._keep_raw = raw
-        return x, center, scale
+        return self.prepare_input_scaled(image, 1, 1)
 
     def _forward_with_mirror(self, x: Tensor) -> tuple[Tensor, Tensor]:
         """forward_raw of the images [:B] and their mirror images [B:] (model.py:85-86), nothing merged yet."""
         B, _, H, W = x.shape
-        stream = torch.cuda.current_stream(x.device).cuda_stream
         # the images and their mirror images as ONE batch of 2B: images of a batch are independent (same bits as two passes), and
         # a forward costs ~2 ms of launch structure whatever the batch -- a single image is a chain of ~350 dependent launches
         x2 = torch.empty((2 * B, 3, H, W), device=x.device, dtype=x.dtype)
         x2[:B].copy_(x)
-        _lib.check(self._lib.hh_flip_images(x.data_ptr(), x2[B:].data_ptr(), B, 3, H, W, stream))
+        _lib.launch(x.device, self._lib.hh_flip_images, x.data_ptr(), x2[B:].data_ptr(), B, 3, H, W)
         return self.net.forward_raw(x2)
 
     @torch.no_grad()
@@ -379,22 +361,20 @@ class InferenceKeypointsModel:
             parts.append(per)
         acc = [torch.empty((n, K, h // 4, w // 4), device=x1.device, dtype=torch.float32),
                torch.empty((n, K, h // 2, w // 2), device=x1.device, dtype=torch.float32)]
-        stream = torch.cuda.current_stream(x1.device).cuda_stream
         wgt = 1.0 / len(scales)
         cuts = sorted({lo for per in parts for lo, _, _, _ in per} | {n})
         table = (_ScaleSrc * len(scales))()
-        with torch.cuda.device(x1.device):
-            for a, b in zip(cuts[:-1], cuts[1:]):
-                for st in range(2):
-                    for si, per in enumerate(parts):
-                        lo, _, *stages = next(p for p in per if p[0] <= a < p[1])
-                        hm, hmf = stages[st]  # [*, >=K, h_s, w_s]: the heatmaps are the first K channels
-                        table[si] = _ScaleSrc(hm.data_ptr() + 4 * (a - lo) * hm.stride(0), hm.stride(0),
-                                              hmf.data_ptr() + 4 * (a - lo) * hmf.stride(0) if hmf is not None else None,
-                                              hmf.stride(0) if hmf is not None else 0, hm.shape[2], hm.shape[3], wgt)
-                    dst = acc[st][a:b]
-                    _lib.check(self._lib.hh_multi_scale_aggregate(table, len(scales), self._perm.ctypes.data, b - a, K, dst.data_ptr(),
-                                                                  dst.stride(0), dst.shape[2], dst.shape[3], stream))
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            for st in range(2):
+                for si, per in enumerate(parts):
+                    lo, _, *stages = next(p for p in per if p[0] <= a < p[1])
+                    hm, hmf = stages[st]  # [*, >=K, h_s, w_s]: the heatmaps are the first K channels
+                    table[si] = _ScaleSrc(hm.data_ptr() + 4 * (a - lo) * hm.stride(0), hm.stride(0),
+                                          hmf.data_ptr() + 4 * (a - lo) * hmf.stride(0) if hmf is not None else None,
+                                          hmf.stride(0) if hmf is not None else 0, hm.shape[2], hm.shape[3], wgt)
+                dst = acc[st][a:b]
+                _lib.launch(x1.device, self._lib.hh_multi_scale_aggregate, table, len(scales), self._perm.ctypes.data, b - a, K, dst.data_ptr(),
+                            dst.stride(0), dst.shape[2], dst.shape[3])
         return acc, tags
 
     @torch.no_grad()
@@ -406,18 +386,16 @@ class InferenceKeypointsModel:
             init, dec = self.net.forward_raw(x)
             return [init[:, :K], dec], [init[:, K:]]
         B, _, H, W = x.shape
-        stream = torch.cuda.current_stream(x.device).cuda_stream
         init2, dec2 = self._forward_with_mirror(x)
         init, init_f, dec, dec_f = init2[:B], init2[B:], dec2[:B], dec2[B:]
         tags2 = torch.empty((B, K, H // 4, W // 4), device=x.device, dtype=torch.float32)
         hq, wq = H // 4, W // 4
         p = self._perm.ctypes.data
         # stage 0: heatmaps = init[:, :K] (batch stride 2K planes), tags = init[:, K:]
-        _lib.check(self._lib.hh_flip_merge(init.data_ptr(), init.stride(0), init_f.data_ptr(), init_f.stride(0),
-                                           init_f[:, K:].data_ptr(), init_f.stride(0), tags2.data_ptr(), tags2.stride(0), p, B, K,
-                                           hq, wq, stream))
-        _lib.check(self._lib.hh_flip_merge(dec.data_ptr(), dec.stride(0), dec_f.data_ptr(), dec_f.stride(0), None, 0, None, 0, p,
-                                           B, K, 2 * hq, 2 * wq, stream))
+        _lib.launch(x.device, self._lib.hh_flip_merge, init.data_ptr(), init.stride(0), init_f.data_ptr(), init_f.stride(0),
+                    init_f[:, K:].data_ptr(), init_f.stride(0), tags2.data_ptr(), tags2.stride(0), p, B, K, hq, wq)
+        _lib.launch(x.device, self._lib.hh_flip_merge, dec.data_ptr(), dec.stride(0), dec_f.data_ptr(), dec_f.stride(0), None, 0, None, 0, p,
+                    B, K, 2 * hq, 2 * wq)
         return [init[:, :K], dec], [init[:, K:], tags2]
 
     @torch.no_grad()
@@ -492,7 +470,7 @@ class InferenceKeypointsModel:
                 jobs.setdefault(c["sizes"], []).append((c["images"], c["sub_batches"]))
         i1 = pass_scales.index(1)
         results: list = [None] * n
-        mean, std = IMAGENET_MEAN.ctypes.data_as(C.POINTER(C.c_float)), IMAGENET_STD.ctypes.data_as(C.POINTER(C.c_float))
+        mean, std = IMAGENET_MEAN.ctypes.data, IMAGENET_STD.ctypes.data
 
         def finish(job):
             """device -> host results of one enqueued batch, un-warp, result objects"""
@@ -555,9 +533,9 @@ class InferenceKeypointsModel:
                     def prepare(si):
                         ws, hs = sizes[si]
                         xs = torch.empty((nb, 3, hs, ws), device=self.device, dtype=torch.float32)
-                        with torch.cuda.device(xs.device):  # one launch for the whole batch, whatever the raw sizes
-                            _lib.check(self._lib.hh_preprocess_u8_batch(raw.data_ptr(), raw.data_ptr() + desc_off + 64 * nb * si, nb,
-                                                                        xs.data_ptr(), hs, ws, mean, std, cur.cuda_stream))
+                        # one launch for the whole batch, whatever the raw sizes
+                        _lib.launch(xs.device, self._lib.hh_preprocess_u8_batch, raw.data_ptr(), raw.data_ptr() + desc_off + 64 * nb * si, nb,
+                                    xs.data_ptr(), hs, ws, mean, std)
                         return xs
 
                     x = prepare(i1)

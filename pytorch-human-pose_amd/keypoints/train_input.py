@@ -311,23 +311,22 @@ class TrainInput:
             images = torch.empty((B, 3, S, S), device=dev, dtype=torch.float32)
             masks = [torch.empty((B, s, s), device=dev, dtype=torch.float32) for s in self.hm_sizes]
             heatmaps = [torch.empty((B, K, s, s), device=dev, dtype=torch.float32) for s in self.hm_sizes]
-            fp = C.POINTER(C.c_float)
-            base, stream = raw.data_ptr(), cur.cuda_stream
+            base = raw.data_ptr()
             if M:  # the canvases first: the two warp launches below read them
-                _lib.check(lib.hh_mosaic_u8_batch(base, base + mosaic_off, mdescs.ctypes.data, M, S, stream))
-            _lib.check(lib.hh_train_images_u8_batch(base, base + desc_off, B, images.data_ptr(), S, S, self.mean.ctypes.data_as(fp),
-                                                    self.std.ctypes.data_as(fp), stream))
+                _lib.launch(dev, lib.hh_mosaic_u8_batch, base, base + mosaic_off, mdescs.ctypes.data, M, S)
+            _lib.launch(dev, lib.hh_train_images_u8_batch, base, base + desc_off, B, images.data_ptr(), S, S, self.mean.ctypes.data,
+                        self.std.ctypes.data)
             stage_hw = (C.c_int * (2 * nst))(*[s for s in self.hm_sizes for _ in range(2)])
             outs = (C.c_void_p * nst)(*[m.data_ptr() for m in masks])
-            _lib.check(lib.hh_train_masks_u8_batch(base, base + desc_off, B, nst, stage_hw, outs, stream))
+            _lib.launch(dev, lib.hh_train_masks_u8_batch, base, base + desc_off, B, nst, stage_hw, outs)
             device_joints = []
             for i, s in enumerate(self.hm_sizes):
                 packed, counts = pack_joints(stage_joints[i], K, s, s)
                 self.last_h2d_bytes += packed.nbytes + counts.nbytes
                 dj = DeviceJoints(torch.from_numpy(packed).to(dev), torch.from_numpy(counts).to(dev), (K, s, s))
                 table, reach = self._tables_dev[i], self.tables[i][1]
-                _lib.check(lib.hh_render_heatmaps(dj.packed.data_ptr(), dj.counts.data_ptr(), B, packed.shape[1], K, table.data_ptr(),
-                                                  table.shape[0], reach, heatmaps[i].data_ptr(), s, s, stream))
+                _lib.launch(dev, lib.hh_render_heatmaps, dj.packed.data_ptr(), dj.counts.data_ptr(), B, packed.shape[1], K, table.data_ptr(),
+                            table.shape[0], reach, heatmaps[i].data_ptr(), s, s)
                 device_joints.append(dj)
         return images, heatmaps, masks, device_joints
 

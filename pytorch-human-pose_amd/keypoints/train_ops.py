@@ -9,6 +9,7 @@ import torch
 from torch import Tensor
 
 from .. import _lib
+from .._lib import launch as _launch, ptr as _ptr
 
 
 ACT_DTYPES = {torch.bfloat16: _lib.ACT_BF16, torch.float16: _lib.ACT_F16}
@@ -31,16 +32,6 @@ def _act(first: Tensor, *others) -> int:
 
 
 BN_BLOCKS = 256  # HH_BN_BLOCKS of csrc/kernels.h: the BatchNorm reductions write BN_BLOCKS * C * 2 partial sums into their scratch
-
-
-def _launch(dev, fn, *args) -> None:
-    """One C-ABI call with `dev` current, on its current stream (the last argument of every entry point); raises on its status."""
-    with torch.cuda.device(dev):
-        _lib.check(fn(*args, torch.cuda.current_stream(dev).cuda_stream))
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
 
 
 def _conv_geometry(wshape, stride: int, data_grad: bool, H: int = 0, W: int = 0):

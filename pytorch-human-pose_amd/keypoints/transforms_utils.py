@@ -68,9 +68,7 @@ def warp_affine(image: np.ndarray, m: np.ndarray, size, device="cuda:0") -> np.n
         raise ValueError("warp_affine: uint8 [h, w, 3] images only")
     raw = torch.from_numpy(img).to(device)
     out = torch.empty((h_out, w_out, 3), device=raw.device, dtype=torch.uint8)
-    with torch.cuda.device(raw.device):
-        _lib.check(lib.hh_warp_affine_u8(raw.data_ptr(), img.shape[0], img.shape[1], inv.ctypes.data_as(dp), out.data_ptr(), h_out, w_out,
-                                         torch.cuda.current_stream(raw.device).cuda_stream))
+    _lib.launch(raw.device, lib.hh_warp_affine_u8, raw.data_ptr(), img.shape[0], img.shape[1], inv.ctypes.data_as(dp), out.data_ptr(), h_out, w_out)
     return out.cpu().numpy()
 
 

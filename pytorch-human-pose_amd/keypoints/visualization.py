@@ -236,10 +236,8 @@ def render_frames_device(frames: list, tables: list, alphas, bgr=False) -> list:
         descs[j] = (src, rel + out_at[j], f.shape[0], f.shape[1], first, counts[j], w0, w1, FLAG_BGR if bgrs[j] else 0, 0)
         first += counts[j]
     buf[:upload].copy_(host, non_blocking=True)
-    with torch.cuda.device(device):
-        _lib.check(lib.hh_render_poses_u8_batch(base, buf.data_ptr(), descs.ctypes.data, buf.data_ptr() + prim_at if total_prims else None,
-                                                prims.ctypes.data if total_prims else None, total_prims, n,
-                                                torch.cuda.current_stream(device).cuda_stream))
+    _lib.launch(device, lib.hh_render_poses_u8_batch, base, buf.data_ptr(), descs.ctypes.data, buf.data_ptr() + prim_at if total_prims else None,
+                prims.ctypes.data if total_prims else None, total_prims, n)
     return [buf[o:o + int(f.shape[0]) * int(f.shape[1]) * 3].view(int(f.shape[0]), int(f.shape[1]), 3) for o, f in zip(out_at, frames)]
 
 
@@ -249,9 +247,7 @@ def resize_device(src: torch.Tensor, W: int, H: int) -> torch.Tensor:
         raise ValueError("resize_device: a contiguous device uint8 [h,w], [h,w,1] or [h,w,3] tensor is needed")
     ch = 1 if src.dim() == 2 else int(src.shape[2])
     out = torch.empty((H, W) + tuple(src.shape[2:]), dtype=torch.uint8, device=src.device)
-    with torch.cuda.device(src.device):
-        _lib.check(_lib.load().hh_resize_u8(src.data_ptr(), src.shape[0], src.shape[1], ch, out.data_ptr(), H, W,
-                                            torch.cuda.current_stream(src.device).cuda_stream))
+    _lib.launch(src.device, _lib.load().hh_resize_u8, src.data_ptr(), src.shape[0], src.shape[1], ch, out.data_ptr(), H, W)
     return out
 
 
@@ -370,10 +366,8 @@ def panels_device(image: torch.Tensor, placed: list, Hc: int, Wc: int, lut: np.n
     elif not (canvas.dtype == torch.uint8 and canvas.device == device and canvas.is_contiguous() and pitch is not None
               and canvas.numel() >= (Hc - 1) * pitch + Wc * 3):
         raise ValueError("panels_device: the canvas must be a contiguous device uint8 buffer that holds Hc rows of `pitch` bytes")
-    with torch.cuda.device(device):
-        _lib.check(_lib.load().hh_heatmap_panels_u8(buf.data_ptr(), table.ctypes.data, n, image.data_ptr(), H, W, buf.data_ptr() + lut_at,
-                                                    canvas.data_ptr(), Hc, Wc, pitch, scratch.data_ptr(),
-                                                    torch.cuda.current_stream(device).cuda_stream))
+    _lib.launch(device, _lib.load().hh_heatmap_panels_u8, buf.data_ptr(), table.ctypes.data, n, image.data_ptr(), H, W, buf.data_ptr() + lut_at,
+                canvas.data_ptr(), Hc, Wc, pitch, scratch.data_ptr())
     return canvas
 
 
@@ -385,9 +379,8 @@ def unnormalize_device(x: torch.Tensor, mean=MEAN, std=STD) -> torch.Tensor:
         raise ValueError("unnormalize_device: a device float32 [3,H,W] tensor is needed")
     x = x.contiguous()
     out = torch.empty((x.shape[1], x.shape[2], 3), dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.load().hh_unnormalize_u8(x.data_ptr(), x.shape[1], x.shape[2], (C.c_double * 3)(*mean), (C.c_double * 3)(*std), out.data_ptr(),
-                                                 torch.cuda.current_stream(x.device).cuda_stream))
+    _lib.launch(x.device, _lib.load().hh_unnormalize_u8, x.data_ptr(), x.shape[1], x.shape[2], (C.c_double * 3)(*mean), (C.c_double * 3)(*std),
+                out.data_ptr())
     return out
 
 
@@ -404,9 +397,7 @@ def resize_scaled_device(src: torch.Tensor, fx: float, fy: float) -> torch.Tenso
     ch = 1 if src.dim() == 2 else int(src.shape[2])
     H, W = scaled_size(src.shape[0], fy), scaled_size(src.shape[1], fx)
     out = torch.empty((H, W) + tuple(src.shape[2:]), dtype=torch.uint8, device=src.device)
-    with torch.cuda.device(src.device):
-        _lib.check(_lib.load().hh_resize_u8_scaled(src.data_ptr(), src.shape[0], src.shape[1], ch, float(fx), float(fy), out.data_ptr(), H, W,
-                                                   torch.cuda.current_stream(src.device).cuda_stream))
+    _lib.launch(src.device, _lib.load().hh_resize_u8_scaled, src.data_ptr(), src.shape[0], src.shape[1], ch, float(fx), float(fy), out.data_ptr(), H, W)
     return out
 
 

@@ -156,7 +156,7 @@ class _DeviceOptimizer(torch.optim.Optimizer):
             self._fill_group(groups[gi], group)
         upload = 0
         tb, gb = rows.tobytes(), groups.tobytes()
-        stream = torch.cuda.current_stream(T["dev"]).cuda_stream
+        stream = torch.cuda.current_stream(T["dev"])
         if T["sent_stream"] != stream:  # the copies of an earlier step are ordered before this one only on their own stream
             T["sent_tensors"] = T["sent_groups"] = None
             T["sent_stream"] = stream
@@ -194,9 +194,8 @@ class _DeviceOptimizer(torch.optim.Optimizer):
             dev, rows, groups = T["dev"], T["rows"], T["groups"]
             scale = self._scalar_ptr(getattr(self, "grad_scale", None), "grad_scale", dev)
             found = self._scalar_ptr(getattr(self, "found_inf", None), "found_inf", dev)
-            with torch.cuda.device(dev):
-                _lib.check(_lib.load().hh_optim_step(self.ALGO, rows.ctypes.data, len(rows), groups.ctypes.data, len(groups), scale, found,
-                                                     T["table"].data_ptr(), T["nbytes"], upload, torch.cuda.current_stream(dev).cuda_stream))
+            _lib.launch(dev, _lib.load().hh_optim_step, self.ALGO, rows.ctypes.data, len(rows), groups.ctypes.data, len(groups), scale, found,
+                        T["table"].data_ptr(), T["nbytes"], upload)
             self._sent(T, upload)
         return loss
 
@@ -208,10 +207,8 @@ class _DeviceOptimizer(torch.optim.Optimizer):
         if T is not None:
             dev, rows = T["dev"], T["rows"]
             upload &= UPLOAD_TENSORS
-            with torch.cuda.device(dev):
-                _lib.check(_lib.load().hh_grads_nonfinite(rows.ctypes.data, len(rows), len(T["groups"]), self._scalar_ptr(inv_scale, "inv_scale", dev),
-                                                          self._scalar_ptr(found_inf, "found_inf", dev), T["table"].data_ptr(), T["nbytes"], upload,
-                                                          torch.cuda.current_stream(dev).cuda_stream))
+            _lib.launch(dev, _lib.load().hh_grads_nonfinite, rows.ctypes.data, len(rows), len(T["groups"]), self._scalar_ptr(inv_scale, "inv_scale", dev),
+                        self._scalar_ptr(found_inf, "found_inf", dev), T["table"].data_ptr(), T["nbytes"], upload)
             self._sent(T, upload)
 
 
