@@ -295,6 +295,79 @@ typedef struct hh_mosaic_desc {
 } hh_mosaic_desc;
 int hh_mosaic_u8_batch(unsigned char *batch_base, const hh_mosaic_desc *descs_dev, const hh_mosaic_desc *descs_host, int n, int S,
                        void *stream);
+/* Crowd masks from COCO segmentations (get_crowd_mask, keypoints/datasets/coco.py:167-177, without the COCO API package): the host
+ * reduces every segment to a toggle list, the device fills all masks of a batch, of mixed sizes, in ONE launch.
+ *
+ * The rule.  A segment is one polygon or one run-length list for an image of h x w.  Every segment reduces to a toggle list: a
+ * strictly increasing list of uint32 positions in 0 .. h*w.  Pixels are numbered column-major, idx = x*h + y.  Pixel idx is covered
+ * by the segment iff the number of toggles <= idx is odd.  A mask byte is 0 where at least one of the mask's segments covers the pixel
+ * and 255 elsewhere ((m < 0.5) * 255 of coco.py:177 followed by transforms.py:159): segments combine as a UNION, not XOR.  A toggle
+ * equal to h*w is legal and changes nothing.
+ *
+ * Run-length segment (COCO's {"counts": [c0, c1, ...], "size": [h, w]} of an iscrowd object): runs alternate uncovered / covered,
+ *   starting with uncovered; the toggles are the cumulative sums c0, c0+c1, ... without the last; the sum must equal h*w; values that
+ *   occur an even number of times (zero-length runs) drop out, values that occur an odd number of times stay once.  (Formed in Python;
+ *   `counts` as a compressed string raises.)
+ * Polygon segment, xy[2k] doubles, k >= 3 (hh_crowd_polygon_toggles).  This is the COCO API's polygon conversion as recalled from its
+ *   C source; the package is not available where the fixtures are made, so parity with it is UNPINNED and this text is the contract:
+ *   1. Snap to a grid five times finer: X[j] = (int)(5*x_j + 0.5), Y[j] = (int)(5*y_j + 0.5) (product and sum in double, the
+ *      conversion truncates toward zero); X[k] = X[0], Y[k] = Y[0].
+ *   2. Walk every edge j -> j+1 as a dense point list (u, v).  dx = |X[j+1]-X[j]|, dy = |Y[j+1]-Y[j]|.  The edge is flipped when
+ *      (dx >= dy and X[j] > X[j+1]) or (dx < dy and Y[j] > Y[j+1]); (xs,ys) -> (xe,ye) are the endpoints after swapping if flipped.
+ *      If dx >= dy: s = (double)(ye-ys)/dx; for d = 0..dx: t = flipped ? dx-d : d, u = xs+t, v = (int)(ys + s*t + 0.5).
+ *      Otherwise:   s = (double)(xe-xs)/dy; for d = 0..dy: t = flipped ? dy-d : d, v = ys+t, u = (int)(xs + s*t + 0.5).
+ *      The points therefore always run from vertex j to vertex j+1.  A zero-length edge (dx = dy = 0) contributes the single point
+ *      (X[j], Y[j]).  No fused multiply-add.
+ *   3. Over the concatenation of all edges' points, for every i >= 1 with u[i] != u[i-1]:
+ *      xd = (double)(u[i] < u[i-1] ? u[i] : u[i]-1), then xd = (xd+0.5)/5 - 0.5; skip unless xd is an integer with 0 <= xd <= w-1;
+ *      yd = (double)min(v[i], v[i-1]), then yd = (yd+0.5)/5 - 0.5; clamp yd to [0, h], then yd = ceil(yd);
+ *      emit the position (int)xd * h + (int)yd.  (The clamp to h puts a toggle on the first position of the next column, which is
+ *      why the rule is stated on the linear index and not per column.)
+ *   4. Sort the positions and cancel even multiplicities.  The result is the toggle list.
+ *
+ * hh_crowd_polygon_toggles: host only, no GPU.  Writes the toggle list of one polygon to out[0 .. count) and returns count, or -1 with
+ *   hh_last_error set: for a null pointer, k < 3, a non-finite coordinate, h or w outside 1..16384, a coordinate whose five-fold value
+ *   5*x + 0.5 leaves the int range, or a list longer than `capacity` entries (nothing is written then).  The walk visits every grid
+ *   step of every edge, also of the part of a polygon that lies outside the image: its time is O(5 x perimeter), not O(image).
+ * hh_crowd_polygon_capacity: a capacity that always suffices, from the vertices alone in O(k), without walking: the sum over the edges
+ *   of min(dx / 5 + 2, 2w) (a position is emitted only where u steps onto a column centre, every fifth grid step).  Same refusals, -1.
+ *
+ * hh_crowd_masks_u8_batch: mask i is uint8 [h,w] at batch_base + mask_offset (any alignment) with the segments
+ *   seg_first .. seg_first + seg_count - 1 of the segment table; segment s has `count` uint32 toggles at batch_base + toggle_offset (a
+ *   multiple of 4) and can cover the columns col_first .. col_last only (inclusive; used to cull).  Every mask byte is written exactly
+ *   once; deterministic, no atomics; a mask without segments is all 255.  On the stream; nothing is synchronised.
+ * Validation: `descs_dev` / `segs_dev` are the DEVICE tables the kernel reads; `descs_host` / `segs_host` are the caller's HOST copies
+ *   of the same tables and `host_base` the HOST copy of the staged bytes (the toggles at the offsets the device sees them at): the host
+ *   copies are what is checked, device memory is never read back.  Returns 1 with hh_last_error set, before any launch, for a null
+ *   pointer (the segment tables may be null when num_segs is 0), n outside 1..65535, negative num_segs, batch_base not 4-byte aligned,
+ *   h or w outside 1..16384, a negative mask offset, a segment range outside [0, num_segs), a toggle offset that is negative or not a
+ *   multiple of 4, a negative count, toggles not strictly increasing or above h*w, a column range outside the image or one that does
+ *   not hold the segment's covered columns.  That masks and toggles lie inside the caller's buffer and that masks do not overlap each
+ *   other or the tables cannot be checked here.
+ * hh_crowd_mask_config: out = {tile rows, tile columns, threads per workgroup, per-chunk toggle capacity (0: toggles are read in
+ *   place, no chunking)}.
+ * hh_debug_crowd_masks_host: the same tile walk compiled for the host, one mask into mask[h*w] (mask_offset is not applied), with the
+ *   same validation.
+ * (Additive entry points: HH_ABI_VERSION stays 3.)                                                                             */
+typedef struct hh_crowd_mask_desc {
+    long long mask_offset;         /* bytes from batch_base: uint8 [h,w] out */
+    int h, w;
+    int seg_first, seg_count;      /* this mask's rows of the segment table */
+} hh_crowd_mask_desc;
+typedef struct hh_crowd_seg_desc {
+    long long toggle_offset;       /* bytes from batch_base: `count` uint32 toggles */
+    int count;
+    int col_first, col_last;       /* inclusive */
+    int reserved;
+} hh_crowd_seg_desc;
+long long hh_crowd_polygon_capacity(const double *xy, int k, int h, int w);
+long long hh_crowd_polygon_toggles(const double *xy, int k, int h, int w, unsigned int *out, long long capacity);
+int hh_crowd_masks_u8_batch(unsigned char *batch_base, const hh_crowd_mask_desc *descs_dev, const hh_crowd_seg_desc *segs_dev,
+                            const hh_crowd_mask_desc *descs_host, const hh_crowd_seg_desc *segs_host, const unsigned char *host_base, int n,
+                            int num_segs, void *stream);
+int hh_crowd_mask_config(int out[4]);
+int hh_debug_crowd_masks_host(unsigned char *mask, const hh_crowd_mask_desc *desc_host, const hh_crowd_seg_desc *segs_host,
+                              const unsigned char *host_base, int num_segs);
 /* Pose overlays: plot_connections (keypoints/visualization.py:43-90, with draw_elipsis :13-40) for n frames of mixed sizes in ONE
  * launch, on the raw uint8 RGB frames that are on the device for hh_preprocess_u8 anyway.  The host forms the primitive table
  * (keypoints/visualization.py build_primitives here); the kernel does the per-pixel work; the result is bit-identical to this text

@@ -11,6 +11,7 @@
 #include "render_math.h"
 #include "panel_math.h"
 #include "coco_eval_math.h"
+#include "crowd_mask_math.h"
 
 const char *hh_get_error();
 int hh_tap_read_impl(hh_net *n, int index, float *host);
@@ -487,6 +488,82 @@ int hh_coco_evaluate_host(const hh_coco_tables *tables_host, const double *oks_i
     if (!match && !oks_out) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
     if (coco_tables_check(fn, nullptr, tables_host)) return 1;
     coco_eval_host(*reinterpret_cast<const CocoTables *>(tables_host), oks_in, oks_in ? nullptr : oks_out, match, dt_match, dt_ignore, gt_ignore);
+    return 0;
+}
+
+int hh_crowd_mask_config(int out[4])
+{
+    if (!out) { hh_set_error("hh_crowd_mask_config: null pointer"); return 1; }
+    out[0] = CROWD_TH, out[1] = CROWD_TW, out[2] = CROWD_THREADS, out[3] = 0;  // no per-chunk toggle capacity: toggles are read in place
+    return 0;
+}
+
+long long hh_crowd_polygon_capacity(const double *xy, int k, int h, int w)
+{
+    const char *fn = "hh_crowd_polygon_capacity";
+    if (!xy) { hh_set_error(std::string(fn) + ": null pointer"); return -1; }
+    if (const char *why = crowd_polygon_check(xy, k, h, w)) { hh_set_error(std::string(fn) + ": " + why); return -1; }
+    return crowd_polygon_bound(xy, k, w);
+}
+
+long long hh_crowd_polygon_toggles(const double *xy, int k, int h, int w, unsigned int *out, long long capacity)
+{
+    const char *fn = "hh_crowd_polygon_toggles";
+    if (!xy || (!out && capacity > 0)) { hh_set_error(std::string(fn) + ": null pointer"); return -1; }
+    if (capacity < 0) { hh_set_error(std::string(fn) + ": negative capacity"); return -1; }
+    if (const char *why = crowd_polygon_check(xy, k, h, w)) { hh_set_error(std::string(fn) + ": " + why); return -1; }
+    std::vector<uint32_t> pos;
+    crowd_polygon_walk(xy, k, h, w, pos);
+    crowd_cancel(pos);
+    if ((long long)pos.size() > capacity) {
+        hh_set_error(std::string(fn) + ": " + std::to_string(pos.size()) + " toggles do not fit the capacity " + std::to_string(capacity));
+        return -1;
+    }
+    if (!pos.empty()) memcpy(out, pos.data(), pos.size() * sizeof(uint32_t));
+    return (long long)pos.size();
+}
+
+// The checks of a crowd-mask call that need no device, on the caller's host copies.
+static int crowd_check(const char *fn, const hh_crowd_mask_desc *descs_host, const hh_crowd_seg_desc *segs_host, const unsigned char *host_base, int n,
+                       int num_segs, int *max_tiles)
+{
+    static_assert(sizeof(hh_crowd_mask_desc) == sizeof(CrowdMaskDesc) && sizeof(hh_crowd_seg_desc) == sizeof(CrowdSegDesc), "table layout");
+    if (!descs_host || !host_base || (num_segs > 0 && !segs_host)) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if (n <= 0 || n > 65535) { hh_set_error(std::string(fn) + ": need 0 < n <= 65535"); return 1; }
+    if (num_segs < 0) { hh_set_error(std::string(fn) + ": negative table length"); return 1; }
+    int tiles = 1;
+    for (int b = 0; b < n; ++b) {
+        const CrowdMaskDesc &d = reinterpret_cast<const CrowdMaskDesc *>(descs_host)[b];
+        const char *why = crowd_check_mask(d, reinterpret_cast<const CrowdSegDesc *>(segs_host), num_segs, host_base);
+        if (why) { hh_set_error(std::string(fn) + ": mask " + std::to_string(b) + ": " + why); return 1; }
+        tiles = std::max(tiles, ((d.w + CROWD_TW - 1) / CROWD_TW) * ((d.h + CROWD_TH - 1) / CROWD_TH));
+    }
+    *max_tiles = tiles;
+    return 0;
+}
+
+int hh_crowd_masks_u8_batch(unsigned char *batch_base, const hh_crowd_mask_desc *descs_dev, const hh_crowd_seg_desc *segs_dev,
+                            const hh_crowd_mask_desc *descs_host, const hh_crowd_seg_desc *segs_host, const unsigned char *host_base, int n,
+                            int num_segs, void *stream)
+{
+    const char *fn = "hh_crowd_masks_u8_batch";
+    if (!batch_base || !descs_dev || (num_segs > 0 && !segs_dev)) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if ((uintptr_t)batch_base % 4) { hh_set_error(std::string(fn) + ": batch_base must be 4-byte aligned"); return 1; }
+    int max_tiles = 0;
+    if (crowd_check(fn, descs_host, segs_host, host_base, n, num_segs, &max_tiles)) return 1;
+    HH_CHECK_HIP(launch_crowd_masks(batch_base, reinterpret_cast<const CrowdMaskDesc *>(descs_dev), reinterpret_cast<const CrowdSegDesc *>(segs_dev), n,
+                                    max_tiles, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_debug_crowd_masks_host(unsigned char *mask, const hh_crowd_mask_desc *desc_host, const hh_crowd_seg_desc *segs_host, const unsigned char *host_base,
+                              int num_segs)
+{
+    const char *fn = "hh_debug_crowd_masks_host";
+    if (!mask) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    int max_tiles = 0;
+    if (crowd_check(fn, desc_host, segs_host, host_base, 1, num_segs, &max_tiles)) return 1;
+    crowd_mask_host(mask, *reinterpret_cast<const CrowdMaskDesc *>(desc_host), reinterpret_cast<const CrowdSegDesc *>(segs_host), host_base);
     return 0;
 }
 

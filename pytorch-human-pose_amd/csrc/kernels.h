@@ -376,6 +376,11 @@ struct CocoTables;
 hipError_t launch_coco_eval(int mode, const CocoTables &dev, const double *oks_in, double *oks_out, int32_t *dt_match, uint8_t *dt_ignore, uint8_t *gt_ignore,
                             hipStream_t s);
 void coco_eval_host(const CocoTables &t, const double *oks_in, double *oks_out, bool match, int32_t *dt_match, uint8_t *dt_ignore, uint8_t *gt_ignore);
+// Crowd masks from toggle lists (hh_crowd_mask_desc / hh_crowd_seg_desc of include/hhrnet.h; structs, predicate, tile walk and the host's
+// polygon walk in crowd_mask_math.h, kernel in crowd_mask.hip): n masks in one launch, `max_tiles` = the largest mask's tile count.
+struct CrowdMaskDesc;
+struct CrowdSegDesc;
+hipError_t launch_crowd_masks(unsigned char *base, const CrowdMaskDesc *descs, const CrowdSegDesc *segs, int n, int max_tiles, hipStream_t s);
 // target heatmaps from the packed joints (train_input.hip); n = table side = 2 * reach + 1 <= HH_RENDER_MAX_N, w <= HH_RENDER_MAX_W
 #define HH_RENDER_MAX_N 63
 #define HH_RENDER_MAX_W 4096

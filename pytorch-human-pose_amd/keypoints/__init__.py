@@ -5,6 +5,7 @@ from .results import InferenceKeypointsResult, KeypointsResult
 
 __all__ = ["HigherHRNet", "MPPEHeatmapParser", "InferenceKeypointsModel", "InferenceKeypointsResult", "KeypointsModel", "KeypointsModule"]
 from .loss import AEGroupingLoss, AEKeypointsLoss, HeatmapsLoss
-from . import coco_eval, evaluation, targets
+from . import coco_eval, crowd_mask, evaluation, targets
+from .crowd_mask import CrowdSegments, crowd_masks, get_crowd_mask, raw_sample
 from .train_input import Mosaic, TrainInput, mosaic_joints
 from .visualization import DEFAULT_PALETTE, build_primitives, jet_lut, plot_connections, plot_heatmaps

@@ -28,6 +28,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .. import _lib
+from . import crowd_mask as cm
 from .loss import DeviceJoints, pack_joints
 from .targets import JointsGenerator
 from .transforms_utils import COCO_FLIP_INDEX
@@ -237,7 +238,11 @@ class TrainInput:
     def build(self, samples, params):
         """samples: [(uint8 [h,w,3] image, bool [h,w] crowd mask, float [P,K,3] joints) or Mosaic of four of them], params: [AugParams]
         (of a 2S x 2S image for a Mosaic) -> (images [B,3,S,S], [heatmaps [B,K,s,s]], [masks [B,s,s]], [DeviceJoints]) on the device,
-        in the current stream."""
+        in the current stream.  The crowd mask of a sample or tile may be a `crowd_mask.CrowdSegments` of the image's size instead
+        of a dense array (`crowd_mask.raw_sample` makes such samples from COCO annotations); dense and segment samples may be mixed.
+        A segment sample's mask bytes are not staged: its toggles and descriptors travel in the same copy, and one
+        hh_crowd_masks_u8_batch launch per batch fills the masks behind the staged bytes of the device buffer, before the mosaic and
+        warp launches.  A batch of dense samples takes exactly the path it took before: same bytes, same launches."""
         import torch
         lib = _lib.load()
         B, S, K, nst = len(samples), self.out_size, self.num_kpts, len(self.hm_sizes)
@@ -258,22 +263,34 @@ class TrainInput:
             slots.append(list(range(first, first + 4)) if isinstance(entry, Mosaic) else first)
         R, M = len(raws), sum(isinstance(e, Mosaic) for e in samples)
         shapes = [img.shape[:2] for img, _, _ in raws]
-        sizes = [h * w * 3 for h, w in shapes] + [h * w for h, w in shapes]
+        # a raw sample whose second element is a CrowdSegments ships no mask bytes: its toggles and descriptors travel instead
+        seg_raws = [r for r, (_, mask, _) in enumerate(raws) if isinstance(mask, cm.CrowdSegments)]
+        seg_items = [raws[r][1] for r in seg_raws]
+        sizes = [h * w * 3 for h, w in shapes] + [0 if isinstance(mask, cm.CrowdSegments) else h * w for (h, w), (_, mask, _) in zip(shapes, raws)]
         offs = np.cumsum([0] + sizes)
         desc_off = (int(offs[-1]) + 63) // 64 * 64  # the descriptors travel behind the pixels and masks, in the same copy
         mosaic_off = desc_off + _TRAIN_DESC.itemsize * B
-        total = mosaic_off + _MOSAIC_DESC.itemsize * M
+        crowd_off = mosaic_off + _MOSAIC_DESC.itemsize * M  # (a multiple of 8: both descriptor sizes are)
+        total = crowd_off + cm.tables_bytes(seg_items)
         # the canvases of the mosaic samples lie behind the staged bytes in the device buffer; nothing of them is copied
         canvas_off = (total + 63) // 64 * 64
+        # ... and behind them the masks of the segment samples, which hh_crowd_masks_u8_batch fills there
+        fill_offs = canvas_off + M * 16 * S * S + np.cumsum([0] + [(s.h * s.w + 3) // 4 * 4 for s in seg_items])
+        mask_at_raw = [int(offs[R + r]) for r in range(R)]
+        for i, r in enumerate(seg_raws):
+            mask_at_raw[r] = int(fill_offs[i])
         if M and (S % 4 or S < 4):
             raise _lib.HHError("TrainInput.build: a mosaic needs an out_size that is a multiple of 4 (hh_mosaic_u8_batch)")
         turn, host = self._staging(total)
         hview = host.numpy()
         descs = hview[desc_off:mosaic_off].view(_TRAIN_DESC)
-        mdescs = hview[mosaic_off:total].view(_MOSAIC_DESC)
+        mdescs = hview[mosaic_off:crowd_off].view(_MOSAIC_DESC)
+        crowd_desc_at, crowd_seg_at, crowd_nseg = cm.fill_tables(seg_items, fill_offs[:-1], hview, crowd_off)
         for r, (img, mask, _) in enumerate(raws):
             h, w = shapes[r]
             np.copyto(hview[offs[r]:offs[r + 1]].reshape(h, w, 3), img)
+            if isinstance(mask, cm.CrowdSegments):
+                continue
             mview = hview[offs[R + r]:offs[R + r + 1]].reshape(h, w)
             np.multiply(mask, 255, out=mview, casting="unsafe")  # (mask * 255).astype(np.uint8), transforms.py:159
         stage_joints = [[] for _ in range(nst)]
@@ -281,12 +298,12 @@ class TrainInput:
         for b, (entry, p) in enumerate(zip(samples, params)):
             if isinstance(entry, Mosaic):
                 image_at, mask_at = canvas_off + m * 16 * S * S, canvas_off + m * 16 * S * S + 12 * S * S
-                mdescs[m] = ([(int(offs[r]), int(offs[R + r]), *shapes[r]) for r in slots[b]], image_at, mask_at)
+                mdescs[m] = ([(int(offs[r]), mask_at_raw[r], *shapes[r]) for r in slots[b]], image_at, mask_at)
                 h = w = 2 * S
                 joints = mosaic_joints(entry.tiles, S, K)
                 m += 1
             else:
-                image_at, mask_at, (h, w), joints = int(offs[slots[b]]), int(offs[R + slots[b]]), shapes[slots[b]], entry[2]
+                image_at, mask_at, (h, w), joints = int(offs[slots[b]]), mask_at_raw[slots[b]], shapes[slots[b]], entry[2]
             mat_image, mats, _, ints = self.geometry(h, w, joints, p)
             inv_mask = np.zeros((MAX_STAGES, 6))
             for i, mat in enumerate(mats):
@@ -297,22 +314,24 @@ class TrainInput:
         dev = torch.device(self.device)
         with torch.cuda.device(dev):
             cur = torch.cuda.current_stream(dev)
-            if M:
-                raw = torch.empty(canvas_off + M * 16 * S * S, device=dev, dtype=torch.uint8)
+            if M or seg_items:
+                raw = torch.empty(int(fill_offs[-1]), device=dev, dtype=torch.uint8)
                 raw[:total].copy_(host[:total], non_blocking=True)
             else:
                 raw = host[:total].to(dev, non_blocking=True)
             copied = torch.cuda.Event()
             copied.record(cur)
             self._stage_free[turn] = copied
-            self.last_h2d_bytes, self.last_launches = total, 2 + nst + (1 if M else 0)
+            self.last_h2d_bytes, self.last_launches = total, 2 + nst + (1 if M else 0) + (1 if seg_items else 0)
             if self._tables_dev is None:
                 self._tables_dev = [torch.from_numpy(t).to(dev) for t, _ in self.tables]
             images = torch.empty((B, 3, S, S), device=dev, dtype=torch.float32)
             masks = [torch.empty((B, s, s), device=dev, dtype=torch.float32) for s in self.hm_sizes]
             heatmaps = [torch.empty((B, K, s, s), device=dev, dtype=torch.float32) for s in self.hm_sizes]
             base = raw.data_ptr()
-            if M:  # the canvases first: the two warp launches below read them
+            if seg_items:  # the masks of the segment samples first: the mosaic and the mask warp read them
+                cm.launch(dev, base, host.data_ptr(), crowd_desc_at, crowd_seg_at, len(seg_items), crowd_nseg)
+            if M:  # the canvases next: the two warp launches below read them
                 _lib.launch(dev, lib.hh_mosaic_u8_batch, base, base + mosaic_off, mdescs.ctypes.data, M, S)
             _lib.launch(dev, lib.hh_train_images_u8_batch, base, base + desc_off, B, images.data_ptr(), S, S, self.mean.ctypes.data,
                         self.std.ctypes.data)
