@@ -25,6 +25,22 @@ extern "C" {
 #define HH_DTYPE_FP8 2  /* OCP e4m3 MFMA operands (v_mfma_f32_32x32x64_f8f6f4), fp32 accumulate, e4m3 NHWC activations with one
                            scale per tensor, e4m3 weights with one scale per output channel; needs hh_calibrate (BASELINE.json
                            configs[4]; no reference precedent: the reference infers in fp32, keypoints/model.py:79-83)     */
+#define HH_DTYPE_F16 3  /* fp16 MFMA operands (v_mfma_f32_32x32x16_f16), fp32 accumulate, fp16 NHWC activations, packed weights fp16,
+                           outputs fp32 as for bf16: the format every GPU forward of the reference runs in (torch.autocast(float16)).
+                           The plan -- ops, lanes, fusions, workspace -- is the bf16 handle's; the kernels are the same templates over
+                           the element type.  Semantics, those of HH_ACT_F16 below (the same element traits):
+                             - every store rounds to nearest even;
+                             - a value beyond +-65504 becomes +-inf.  It is NOT saturated: an overflowing activation shows in the
+                               outputs as inf / NaN instead of as a plausible wrong map (check a checkpoint's range with
+                               hh_set_taps / hh_tap_read maxima against 65504);
+                             - subnormals are kept by every store and every fp32 <-> fp16 conversion.  Whether the f16 MFMA keeps
+                               subnormal INPUTS is what the subnormal case of tests/test_gpu_train_f16_lattice.py decides;
+                             - BatchNorm-folded weights are rounded to fp16 on the host: one below 2^-14 in magnitude loses mantissa
+                               bits, one below 2^-25 becomes zero, and one beyond +-65504 makes hh_finalize FAIL with the parameter's
+                               name (it does not load an inf).  Biases / BN shifts stay fp32.
+                           hh_calibrate on such a handle is an error.  A handle created under a debug switch that reaches a kernel
+                           without an fp16 form (HH_NO_STEM_FUSED, HH_BB32=tile) is refused by hh_create.
+                           (One new constant, no new symbol: HH_ABI_VERSION stays 3.)                                         */
 
 typedef struct hh_net hh_net;
 typedef struct hh_decoder hh_decoder;
@@ -53,8 +69,9 @@ int hh_param_shape(const hh_net *net, int index, int64_t shape[4]); /* returns n
 /* load_state_dict(): base/model.py:155-175. `host` is fp32 (int64 counters are ignored);
  * unknown names and shape mismatches are errors (strict=True semantics).                */
 int hh_load_weights(hh_net *net, const char *name, const float *host, const int64_t *shape, int ndim);
-/* Folds eval-mode BatchNorm (eps 1e-5) into the preceding conv, packs bf16 kernel-layout
- * weights and uploads them.  Fails if any parameter was never loaded.  Synchronous.     */
+/* Folds eval-mode BatchNorm (eps 1e-5) into the preceding conv, packs kernel-layout weights in the handle's
+ * element type and uploads them.  Fails if any parameter was never loaded, and on an HH_DTYPE_F16 handle if a
+ * folded weight exceeds the fp16 range (the message names the parameter).  Synchronous.  */
 int hh_finalize(hh_net *net);
 
 /* fp8 handles only: sets the per-tensor activation scales from `rounds` (0 = 2) forwards over a calibration batch

@@ -15,12 +15,14 @@ from ...keypoints.architectures.spec import classification_hrnet_rows
 
 
 class ClassificationHRNet(EngineModule):
-    def __init__(self, C: int = 32, num_classes: int = 1000):
+    """`dtype="bf16"` (default) or `"fp16"`: the element type of the inference engine (see HigherHRNet; the classifier has no fp8 form)."""
+
+    def __init__(self, C: int = 32, num_classes: int = 1000, dtype: str = "bf16"):
         super().__init__()
         self.C = C
         self.num_classes = num_classes
         self.stages_C = [C, 2 * C, 4 * C, 8 * C]
-        self._init_engine(classification_hrnet_rows(C, num_classes), lambda lib: lib.hh_create_classifier(C, num_classes, 1))
+        self._init_engine(classification_hrnet_rows(C, num_classes), lambda lib, code: lib.hh_create_classifier(C, num_classes, code), dtype)
 
     def forward(self, images: Tensor) -> Tensor:
         if self.training:  # batch-stat BatchNorm, differentiable: keypoints/train_net.py on the training kernels (bf16 activations by default)

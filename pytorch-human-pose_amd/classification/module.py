@@ -27,9 +27,15 @@ class ClassificationResult:
 
 
 class ClassificationModule:
+    """eval_dtype: the element type of the inference engine that `validation_step` runs ("bf16" / "fp16").  None (default) leaves the
+    net's engine as it is; a name calls `net.set_engine_dtype` once, here."""
+
     def __init__(self, model: ClassificationModel, loss_fn: ClassificationLoss, optimizer: torch.optim.Optimizer,
-                 idx2label: dict | None = None):
+                 idx2label: dict | None = None, eval_dtype: str | None = None):
         self.model, self.loss_fn, self.optimizer, self.idx2label = model, loss_fn, optimizer, idx2label
+        self.eval_dtype = eval_dtype
+        if eval_dtype is not None:
+            model._bare().set_engine_dtype(eval_dtype)
 
     def batch_to_device(self, batch):
         images, targets = batch

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(NTHR, 1) void bb_fused_kernel(const BBParams p)
     const int r = lane & 31, h = lane >> 5;
 
     u32x4 ident[2];  // the residual enters through the matrix pipe
-    ident_frags(r, h, ident);
+    ident_frags<ElemBF16>(r, h, ident);
 
     // ---- tile-invariant per-thread geometry
     int pl_off[NPL], pl_yx[NPL];  // prefetch unit i: element offset from the tile's patch origin, (py << 8) | px
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(NTHR, 1) void bb_fused_kernel(const BBParams p)
     auto store_rows = [&](int q) {  // ReLU, bf16, 16 contiguous bytes per lane straight to HBM
         const int oy = prev_oy0 + wave * 2 + q, ox = prev_ox0 + r;
         u32x4 o[2];
-        pack_rows16(acc2[q], o);
+        pack_rows16<ElemBF16>(acc2[q], o);
         bf16_raw *dst = prev_out + ((ptrdiff_t)(wave * 2 + q) * p.W + r) * p.out_cs + 8 * h;
         if (!(prev & (oy < p.H) & (ox < p.W))) dst = p.trash + 8 * h;  // select, not a branch: lanes outside the image (and the
         *reinterpret_cast<u32x4 *>(dst) = o[0];                         // first tile, which has no predecessor) hit a dummy line
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(NTHR, 1) void bb_fused_kernel(const BBParams p)
                 // conv2 zero-pads the *feature map*: mid pixels outside the image are 0, not conv1(padding)
                 const bool outside = ((unsigned)gy >= (unsigned)p.H) | ((unsigned)gx >= (unsigned)p.W);
                 u32x4 o[2];
-                pack_rows16(acc[q], o);
+                pack_rows16<ElemBF16>(acc[q], o);
                 *reinterpret_cast<u32x4 *>(lds_m + maddr[q]) = o[0];
                 *reinterpret_cast<u32x4 *>(lds_m + maddr[q] + 32) = o[1];
                 if (outside) {  // only tiles on the image border have such lanes

@@ -37,6 +37,8 @@ constexpr int NWL = (W_UNITS + NTHR - 1) / NTHR;    // 5 (the last round is half
 
 size_t bb64_lds_bytes() { return PATCH_BYTES + MID_BYTES + W_BYTES + 2 * C * 4; }
 
+// E: the element type (ElemBF16 / ElemF16 of mfma_dev.h)
+template <typename E>
 __global__ __launch_bounds__(NTHR, 1) void bb64_fused_kernel(const BBParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -53,7 +55,7 @@ __global__ __launch_bounds__(NTHR, 1) void bb64_fused_kernel(const BBParams p)
 
     // identity A fragments (rows = couts of this cout tile, k = cin of the 32-channel chunk ct): residual via the matrix pipe
     u32x4 ident[2];
-    ident_frags(r, h, ident);
+    ident_frags<E>(r, h, ident);
 
     // ---- tile-invariant geometry
     int pl_yx[NPL];  // prefetch unit i: (py << 8) | px inside the patch (py = 255: an idle unit of the last round)
@@ -134,7 +136,7 @@ __global__ __launch_bounds__(NTHR, 1) void bb64_fused_kernel(const BBParams p)
     auto store_rows = [&](int q) {
         const int oy = prev_oy0 + part * 2 + q, ox = prev_ox0 + r;
         u32x4 o[2];
-        pack_rows16(acc2[q], o);
+        pack_rows16<E>(acc2[q], o);
         bf16_raw *dst = prev_out + ((ptrdiff_t)(part * 2 + q) * p.W + r) * p.out_cs + ct * 32 + 8 * h;
         if (!(prev & (oy < p.H) & (ox < p.W))) dst = p.trash + 8 * h;
         *reinterpret_cast<u32x4 *>(dst) = o[0];
@@ -190,8 +192,7 @@ __global__ __launch_bounds__(NTHR, 1) void bb64_fused_kernel(const BBParams p)
                     }
 #pragma unroll
                     for (int q = 0; q < NQ; ++q)
-                        acc[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[st & 1]),
-                                                                         __builtin_bit_cast(bf16x8, fb[st & 1][q]), acc[q], 0, 0, 0);
+                        acc[q] = E::mfma(fa[st & 1], fb[st & 1][q], acc[q]);
                     if constexpr (c == 0 && st >= 12 && st < 14) {
 #pragma unroll
                         for (int q = 0; q < NQ; ++q) {
@@ -223,15 +224,14 @@ __global__ __launch_bounds__(NTHR, 1) void bb64_fused_kernel(const BBParams p)
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
                     const u32x4 x = *reinterpret_cast<const u32x4 *>(lds_p + ((part * 2 + q + 2) * IW + r + 2) * PS + ct * 64 + kk * 32 + h * 16);
-                    acc2[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ident[kk]), __builtin_bit_cast(bf16x8, x),
-                                                                      acc2[q], 0, 0, 0);
+                    acc2[q] = E::mfma(ident[kk], x, acc2[q]);
                 }
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
                 const int gy = oy0 - 1 + (myx[q] >> 8), gx = ox0 - 1 + (myx[q] & 255);
                 const bool outside = ((unsigned)gy >= (unsigned)p.H) | ((unsigned)gx >= (unsigned)p.W);
                 u32x4 o[2];
-                pack_rows16(acc[q], o);
+                pack_rows16<E>(acc[q], o);
                 *reinterpret_cast<u32x4 *>(lds_m + maddr[q]) = outside ? u32x4{0u, 0u, 0u, 0u} : o[0];
                 *reinterpret_cast<u32x4 *>(lds_m + maddr[q] + 32) = outside ? u32x4{0u, 0u, 0u, 0u} : o[1];
             }
@@ -279,8 +279,7 @@ __global__ __launch_bounds__(NTHR, 1) void bb64_fused_kernel(const BBParams p)
                 static_for<3>([&](auto kyc) {
                     constexpr int ky = decltype(kyc)::value, j = i - ky;
                     if constexpr (j >= 0 && j < 2)
-                        acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[cb & 1][ky]),
-                                                                          __builtin_bit_cast(bf16x8, fb[s & 1]), acc2[j], 0, 0, 0);
+                        acc2[j] = E::mfma(fa[cb & 1][ky], fb[s & 1], acc2[j]);
                 });
                 __builtin_amdgcn_sched_group_barrier(0x8, nm, 0);
             });
@@ -302,9 +301,14 @@ __global__ __launch_bounds__(NTHR, 1) void bb64_fused_kernel(const BBParams p)
     if (p.clk && tid == 0) atomicMax(p.clk + 1, wall_clock64());
 }
 
-hipError_t bb64_fused_init() { return bb_tile_init(bb64_fused_kernel, bb64_lds_bytes()); }
-
-hipError_t bb64_fused_launch(BBParams p, int num_cus, hipStream_t s)
+hipError_t bb64_fused_init()
 {
-    return bb_tile_launch(bb64_fused_kernel, TH, TW, NTHR, bb64_lds_bytes(), p, num_cus, s);
+    const hipError_t e = bb_tile_init(bb64_fused_kernel<ElemBF16>, bb64_lds_bytes());
+    return e != hipSuccess ? e : bb_tile_init(bb64_fused_kernel<ElemF16>, bb64_lds_bytes());
+}
+
+hipError_t bb64_fused_launch(BBParams p, int num_cus, hipStream_t s, int act_dtype)
+{
+    if (act_dtype != 0 && act_dtype != 1) return hipErrorInvalidValue;
+    return bb_tile_launch(act_dtype ? bb64_fused_kernel<ElemF16> : bb64_fused_kernel<ElemBF16>, TH, TW, NTHR, bb64_lds_bytes(), p, num_cus, s);
 }

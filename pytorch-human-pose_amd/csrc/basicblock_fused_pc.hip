@@ -64,7 +64,7 @@ static_assert(LDS_BYTES_FIN <= 160 * 1024, "LDS");
 // operand (32 pixels x 16 channels per k half) of two more MFMAs against the head's weights (B: 16 channels x 32 couts, K real), so
 // the block output is never stored (-134 MB written, -134 MB read at B = 32 @ 512^2) and the head's launch disappears.  The result
 // tile is D[pixel 8q + 4h + t][cout r] in d[4q + t]: a lane stores four float4 per row, 16 consecutive bytes of one channel plane.
-template <bool FIN>
+template <typename E, bool FIN>
 __device__ __forceinline__ void bbpc_body(const BBParams &p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -239,7 +239,7 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
                 const int gxe = g.ox0 - 1 + mcol;
                 const bool outside = (rowmap(g.b, g.oy0 - 1 + mrow) < 0) | ((unsigned)gxe >= (unsigned)p.W);
                 u32x4 o[2];
-                pack_rows16(acc[RP + (EDGE ? 0 : -1)], o);
+                pack_rows16<E>(acc[RP + (EDGE ? 0 : -1)], o);
 #pragma unroll
                 for (int mm = 0; mm < 2; ++mm)
                     *reinterpret_cast<u32x4 *>(smem + mcur + (mrow * MW + mcol) * 64 + ((2 * mm + h) << 4)) = outside ? u32x4{0u, 0u, 0u, 0u} : o[mm];
@@ -259,15 +259,12 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
                     static_for<3>([&](auto kyc) {
                         constexpr int ky = decltype(kyc)::value, j = i - ky;
                         if constexpr (j >= 0 && j < RP)
-                            acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wreg[(ky * 3 + kx) * 2 + kk]),
-                                                                             __builtin_bit_cast(bf16x8, fb[s % NFB]),
-                                                                             (c == 0 && ky == 0) ? b0 : acc[j], 0, 0, 0);
+                            acc[j] = E::mfma(wreg[(ky * 3 + kx) * 2 + kk], fb[s % NFB], (c == 0 && ky == 0) ? b0 : acc[j]);
                     });
                     __builtin_amdgcn_sched_group_barrier(0x8, nm, 0);
                 } else {
                     constexpr int ie = RP + (EDGE ? 0 : -1);  // (only instantiated with EDGE)
-                    acc[ie] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wreg[s]), __builtin_bit_cast(bf16x8, fb[s % NFB]),
-                                                                      s == 0 ? b0 : acc[ie], 0, 0, 0);
+                    acc[ie] = E::mfma(wreg[s], fb[s % NFB], s == 0 ? b0 : acc[ie]);
                     __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
                 }
             });
@@ -279,7 +276,7 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
             for (int j = 0; j < RP; ++j) {
                 const int m = 4 * wj + j;
                 u32x4 o[2];
-                pack_rows16(acc[j], o);
+                pack_rows16<E>(acc[j], o);
                 if (rowmap(g.b, g.oy0 - 1 + m) < 0) o[0] = o[1] = u32x4{0u, 0u, 0u, 0u};
                 else if (ragged) {
                     const bool outside = g.ox0 - 1 + r >= p.W;
@@ -324,7 +321,7 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
                 for (int j = 0; j < RC; ++j) {
                     const int fr = rowmap(g.b, g.oy0 + c0 + j);
                     u32x4 o[2];
-                    pack_rows16(acc[j], o);
+                    pack_rows16<E>(acc[j], o);
                     const bool ok = (fr >= 0) & (ox < p.W);
                     const unsigned voff = ok ? (unsigned)((fr * p.W + ox) * p.out_cs * 2 + 16 * h) : OOB;
                     // (cache policy 0: nt stores make the block itself faster, 128x128 28.5 -> 25.4 us, and the forward SLOWER, 4.67 -> 4.72 ms: the next launch reads the output)
@@ -373,8 +370,8 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
                                 const unsigned d[4] = {s0[0], s1[0], s0[1], s1[1]};
 #pragma unroll
                                 for (int t = 0; t < 4; ++t) {
-                                    acc[j][8 * m + 2 * t + 0] = b0[8 * m + 2 * t + 0] + __uint_as_float(d[t] << 16);
-                                    acc[j][8 * m + 2 * t + 1] = b0[8 * m + 2 * t + 1] + __uint_as_float(d[t] & 0xffff0000u);
+                                    acc[j][8 * m + 2 * t + 0] = b0[8 * m + 2 * t + 0] + E::lo(d[t]);
+                                    acc[j][8 * m + 2 * t + 1] = b0[8 * m + 2 * t + 1] + E::hi(d[t]);
                                 }
                             }
                     }
@@ -403,8 +400,7 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
                         static_for<3>([&](auto kyc) {
                             constexpr int ky = decltype(kyc)::value, j = i - ky;
                             if constexpr (j >= 0 && j < RC)
-                                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wreg[(ky * 3 + kx) * 2 + kk]),
-                                                                                 __builtin_bit_cast(bf16x8, fb[s % NFBC]), acc[j], 0, 0, 0);
+                                acc[j] = E::mfma(wreg[(ky * 3 + kx) * 2 + kk], fb[s % NFBC], acc[j]);
                         });
                         __builtin_amdgcn_sched_group_barrier(0x8, nm, 0);
                     });
@@ -424,10 +420,10 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
 #pragma unroll
                         for (int j = 0; j < RC; ++j) {
                             u32x4 o[2];
-                            pack_rows16(acc[j], o);
+                            pack_rows16<E>(acc[j], o);
                             const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // (an inline constant: no registers)
-                            f32x16 d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, o[0]), __builtin_bit_cast(bf16x8, fw0), zero, 0, 0, 0);
-                            d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, o[1]), __builtin_bit_cast(bf16x8, fw1), d, 0, 0, 0);
+                            f32x16 d = E::mfma(o[0], fw0, zero);
+                            d = E::mfma(o[1], fw1, d);
                             const int y = g.oy0 + c0 + j;
                             const bool wrap = y >= p.VH;
                             const int ya = wrap ? y - p.VH : y, bb = wrap ? g.b + 1 : g.b;
@@ -465,14 +461,22 @@ __device__ __forceinline__ void bbpc_body(const BBParams &p)
 #endif
 }
 
-__global__ __launch_bounds__(NTHR, 1) void bbpc_kernel(const BBParams p) { bbpc_body<false>(p); }
-__global__ __launch_bounds__(NTHR, 1) void bbpc_final_kernel(const BBParams p) { bbpc_body<true>(p); }
+// E: the element type (ElemBF16 / ElemF16 of mfma_dev.h): the MFMA form, the residual unpack and the 16-bit pack; tiles, LDS layout and
+// the hand-placed reads do not depend on it.
+template <typename E> __global__ __launch_bounds__(NTHR, 1) void bbpc_kernel(const BBParams p) { bbpc_body<E, false>(p); }
+template <typename E> __global__ __launch_bounds__(NTHR, 1) void bbpc_final_kernel(const BBParams p) { bbpc_body<E, true>(p); }
 
 hipError_t bbpc_init()
 {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(bbpc_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(bbpc_final_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_FIN);
+    const void *plain[2] = {reinterpret_cast<const void *>(bbpc_kernel<ElemBF16>), reinterpret_cast<const void *>(bbpc_kernel<ElemF16>)};
+    const void *fin[2] = {reinterpret_cast<const void *>(bbpc_final_kernel<ElemBF16>), reinterpret_cast<const void *>(bbpc_final_kernel<ElemF16>)};
+    for (int i = 0; i < 2; ++i) {
+        hipError_t e = hipFuncSetAttribute(plain[i], hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+        if (e != hipSuccess) return e;
+        e = hipFuncSetAttribute(fin[i], hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_FIN);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 // 32-bit buffer offsets: both tensors must stay below 2 GB (the engine falls back to the tile form otherwise)
@@ -554,15 +558,18 @@ bool bbpc_cover(int B, int H, int W, int tall, int num_cus, long long counts[4])
     return true;
 }
 
-hipError_t bbpc_launch(BBParams p, int num_cus, hipStream_t s)
+hipError_t bbpc_launch(BBParams p, int num_cus, hipStream_t s, int act_dtype)
 {
+    if (act_dtype != 0 && act_dtype != 1) return hipErrorInvalidValue;
     const int grid = bbpc_plan(p, num_cus);
     if (p.fin_out) {
         if (!bbpc_final_supported(p)) return hipErrorInvalidValue;
-        HH_LAUNCH(bbpc_final_kernel, dim3(grid), dim3(NTHR), LDS_BYTES_FIN, s, p);
+        if (act_dtype) HH_LAUNCH(bbpc_final_kernel<ElemF16>, dim3(grid), dim3(NTHR), LDS_BYTES_FIN, s, p);
+        else HH_LAUNCH(bbpc_final_kernel<ElemBF16>, dim3(grid), dim3(NTHR), LDS_BYTES_FIN, s, p);
     } else {
         if (!bbpc_supported(p)) return hipErrorInvalidValue;
-        HH_LAUNCH(bbpc_kernel, dim3(grid), dim3(NTHR), LDS_BYTES, s, p);
+        if (act_dtype) HH_LAUNCH(bbpc_kernel<ElemF16>, dim3(grid), dim3(NTHR), LDS_BYTES, s, p);
+        else HH_LAUNCH(bbpc_kernel<ElemBF16>, dim3(grid), dim3(NTHR), LDS_BYTES, s, p);
     }
     return hipGetLastError();
 }

@@ -11,16 +11,17 @@
 
 namespace {
 // inverse for the residual: 16 bytes (couts 16m+8h..+7) per m -> added onto the accumulator in C layout
+template <typename E>
 __device__ __forceinline__ void add_rows16(f32x16 &acc, const u32x4 v[2])
 {
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
         auto s0 = __builtin_amdgcn_permlane32_swap(v[m][0], v[m][2], false, false);
         auto s1 = __builtin_amdgcn_permlane32_swap(v[m][1], v[m][3], false, false);
-        acc[8 * m + 0] += bf16_lo(s0[0]); acc[8 * m + 1] += bf16_hi(s0[0]);
-        acc[8 * m + 2] += bf16_lo(s1[0]); acc[8 * m + 3] += bf16_hi(s1[0]);
-        acc[8 * m + 4] += bf16_lo(s0[1]); acc[8 * m + 5] += bf16_hi(s0[1]);
-        acc[8 * m + 6] += bf16_lo(s1[1]); acc[8 * m + 7] += bf16_hi(s1[1]);
+        acc[8 * m + 0] += E::lo(s0[0]); acc[8 * m + 1] += E::hi(s0[0]);
+        acc[8 * m + 2] += E::lo(s1[0]); acc[8 * m + 3] += E::hi(s1[0]);
+        acc[8 * m + 4] += E::lo(s0[1]); acc[8 * m + 5] += E::hi(s0[1]);
+        acc[8 * m + 6] += E::lo(s1[1]); acc[8 * m + 7] += E::hi(s1[1]);
     }
 }
 constexpr int W3_BYTES = 256 * 64 * 2;  // conv3 / downsample: packed [cout group 4][chunk 2][c8 4][64][8] (conv_mfma family, NT = 2)
@@ -35,7 +36,8 @@ constexpr int W1_BYTES = 64 * 256 * 2;  // next conv1: packed [chunk 8][c8 4][64
 // Workgroups: eight waves per CU where the registers allow it -- MODE 0 (64 KB of weights) and MODE 3 without a next conv1 (64 KB)
 // as two workgroups of 256 threads, MODE 1 (96 KB) as one of 512 (81 -> 58 us); MODE 2 (128 KB, 241 registers) and MODE 3 with a
 // next conv1 stay at one workgroup of 256 threads: with 512 they spill (149 -> 185 us).
-template <int MODE>
+// E: the element type (ElemBF16 / ElemF16 of mfma_dev.h)
+template <typename E, int MODE>
 __global__ __launch_bounds__(MODE == 1 ? 512 : 256, (MODE == 0 || MODE == 3) ? 2 : 1) void junction_kernel(const JuncParams p)
 {
     constexpr int NT = MODE == 1 ? 512 : 256;
@@ -128,18 +130,18 @@ __global__ __launch_bounds__(MODE == 1 ? 512 : 256, (MODE == 0 || MODE == 3) ? 2
                         const int m = half * 4 + mm;
                         const int unit = (((m >> 1) * 2 + (s >> 1)) * 4 + (s & 1) * 2 + h) * 64 + (m & 1) * 32 + r;
                         const u32x4 a = *reinterpret_cast<const u32x4 *>(lds_w3a + unit * 16);
-                        acc[mm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bta[s]), acc[mm], 0, 0, 0);
+                        acc[mm] = E::mfma(a, bta[s], acc[mm]);
                         if (MODE == 2) {
                             const u32x4 ad = *reinterpret_cast<const u32x4 *>(lds_wd + unit * 16);
-                            acc[mm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ad), __builtin_bit_cast(bf16x8, bx[s]), acc[mm], 0, 0, 0);
+                            acc[mm] = E::mfma(ad, bx[s], acc[mm]);
                         }
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
 #pragma unroll
                 for (int mm = 0; mm < 4; ++mm) {
-                    if (MODE == 3) add_rows16(acc[mm], rv[mm]);
-                    pack_rows16(acc[mm], rv[mm]);  // (rv now holds what the previous junction would have stored)
+                    if (MODE == 3) add_rows16<E>(acc[mm], rv[mm]);
+                    pack_rows16<E>(acc[mm], rv[mm]);  // (rv now holds what the previous junction would have stored)
                 }
             }
             init_acc(0);
@@ -150,10 +152,10 @@ __global__ __launch_bounds__(MODE == 1 ? 512 : 256, (MODE == 0 || MODE == 3) ? 2
                     const int m = half * 4 + mm;
                     const int unit = (((m >> 1) * 2 + (s >> 1)) * 4 + (s & 1) * 2 + h) * 64 + (m & 1) * 32 + r;
                     const u32x4 a = *reinterpret_cast<const u32x4 *>(lds_w3 + unit * 16);
-                    acc[mm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bt[s]), acc[mm], 0, 0, 0);
+                    acc[mm] = E::mfma(a, bt[s], acc[mm]);
                     if (MODE == 1) {
                         const u32x4 ad = *reinterpret_cast<const u32x4 *>(lds_wd + unit * 16);
-                        acc[mm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ad), __builtin_bit_cast(bf16x8, bx[s]), acc[mm], 0, 0, 0);
+                        acc[mm] = E::mfma(ad, bx[s], acc[mm]);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);  // keep the weight-fragment reads of later k-steps from piling up in registers
@@ -161,8 +163,8 @@ __global__ __launch_bounds__(MODE == 1 ? 512 : 256, (MODE == 0 || MODE == 3) ? 2
 #pragma unroll
             for (int mm = 0; mm < 4; ++mm) {
                 const int m = half * 4 + mm;
-                if (MODE != 1) add_rows16(acc[mm], rv[mm]);
-                pack_rows16(acc[mm], yf[m]);
+                if (MODE != 1) add_rows16<E>(acc[mm], rv[mm]);
+                pack_rows16<E>(acc[mm], yf[m]);
                 if (valid && p.y) {
                     bf16_raw *dst = p.y + (size_t)pix * p.y_cs + m * 32 + h * 8;
                     *reinterpret_cast<u32x4 *>(dst) = yf[m][0];
@@ -186,15 +188,14 @@ __global__ __launch_bounds__(MODE == 1 ? 512 : 256, (MODE == 0 || MODE == 3) ? 2
             for (int t = 0; t < 2; ++t) {
                 const int unit = ((s >> 1) * 4 + (s & 1) * 2 + h) * 64 + t * 32 + r;
                 const u32x4 a = *reinterpret_cast<const u32x4 *>(lds_w1 + unit * 16);
-                acc2[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, yf[s >> 1][s & 1]),
-                                                                 acc2[t], 0, 0, 0);
+                acc2[t] = E::mfma(a, yf[s >> 1][s & 1], acc2[t]);
             }
             if (s & 1) __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             u32x4 o[2];
-            pack_rows16(acc2[t], o);
+            pack_rows16<E>(acc2[t], o);
             if (valid) {
                 bf16_raw *dst = p.t1 + (size_t)pix * p.t1_cs + t * 32 + h * 8;
                 *reinterpret_cast<u32x4 *>(dst) = o[0];
@@ -213,16 +214,19 @@ static size_t junc_lds(int mode, bool w1 = true)
 
 hipError_t junction_init()
 {
-    const void *fns[4] = {reinterpret_cast<const void *>(junction_kernel<0>), reinterpret_cast<const void *>(junction_kernel<1>),
-                          reinterpret_cast<const void *>(junction_kernel<2>), reinterpret_cast<const void *>(junction_kernel<3>)};
-    for (int m = 0; m < 4; ++m) {
-        hipError_t e = hipFuncSetAttribute(fns[m], hipFuncAttributeMaxDynamicSharedMemorySize, (int)junc_lds(m));
+    const void *fns[8] = {reinterpret_cast<const void *>(junction_kernel<ElemBF16, 0>), reinterpret_cast<const void *>(junction_kernel<ElemBF16, 1>),
+                          reinterpret_cast<const void *>(junction_kernel<ElemBF16, 2>), reinterpret_cast<const void *>(junction_kernel<ElemBF16, 3>),
+                          reinterpret_cast<const void *>(junction_kernel<ElemF16, 0>), reinterpret_cast<const void *>(junction_kernel<ElemF16, 1>),
+                          reinterpret_cast<const void *>(junction_kernel<ElemF16, 2>), reinterpret_cast<const void *>(junction_kernel<ElemF16, 3>)};
+    for (int m = 0; m < 8; ++m) {
+        hipError_t e = hipFuncSetAttribute(fns[m], hipFuncAttributeMaxDynamicSharedMemorySize, (int)junc_lds(m & 3));
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-hipError_t junction_launch(const JuncParams &p, int num_cus, hipStream_t s)
+template <typename E>
+static hipError_t junction_launch_e(const JuncParams &p, int num_cus, hipStream_t s)
 {
     const bool ds = p.x != nullptr, pair = p.t2a != nullptr;
     const int mode = pair ? (ds ? 2 : 3) : (ds ? 1 : 0);
@@ -232,10 +236,17 @@ hipError_t junction_launch(const JuncParams &p, int num_cus, hipStream_t s)
     const int per_cu = lds <= 80 * 1024 ? 2 : 1;
     const int grid = ngroups < num_cus * per_cu ? ngroups : num_cus * per_cu;
     switch (mode) {
-    case 0: HH_LAUNCH(junction_kernel<0>, dim3(grid), dim3(256), lds, s, p); break;
-    case 1: HH_LAUNCH(junction_kernel<1>, dim3(grid), dim3(512), lds, s, p); break;
-    case 2: HH_LAUNCH(junction_kernel<2>, dim3(grid), dim3(256), lds, s, p); break;
-    default: HH_LAUNCH(junction_kernel<3>, dim3(grid), dim3(256), lds, s, p); break;
+    case 0: HH_LAUNCH((junction_kernel<E, 0>), dim3(grid), dim3(256), lds, s, p); break;
+    case 1: HH_LAUNCH((junction_kernel<E, 1>), dim3(grid), dim3(512), lds, s, p); break;
+    case 2: HH_LAUNCH((junction_kernel<E, 2>), dim3(grid), dim3(256), lds, s, p); break;
+    default: HH_LAUNCH((junction_kernel<E, 3>), dim3(grid), dim3(256), lds, s, p); break;
     }
     return hipGetLastError();
+}
+
+hipError_t junction_launch(const JuncParams &p, int num_cus, hipStream_t s, int act_dtype)
+{
+    if (act_dtype == 0) return junction_launch_e<ElemBF16>(p, num_cus, s);
+    if (act_dtype == 1) return junction_launch_e<ElemF16>(p, num_cus, s);
+    return hipErrorInvalidValue;
 }

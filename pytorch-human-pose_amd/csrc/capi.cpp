@@ -21,23 +21,39 @@ extern "C" {
 int hh_abi_version(void) { return HH_ABI_VERSION; }
 const char *hh_last_error(void) { return hh_get_error(); }
 
+// stem_conv.hip and basicblock_fused.hip (the tile form) exist in bf16 only: an fp16 handle whose switches reach them would run bf16
+// arithmetic on fp16 bits.  Deletes the handle and returns true when refused.
+static bool f16_switch_refused(hh_net *n)
+{
+    if (n->dtype != HH_DTYPE_F16 || (!n->sw.no_stem_fused && !n->sw.bb32_tile)) return false;
+    hh_set_error(std::string("hh_create: HH_DTYPE_F16 with ") + (n->sw.no_stem_fused ? "HH_NO_STEM_FUSED" : "HH_BB32=tile") +
+                 ": that debug switch reaches a kernel that has no fp16 form");
+    delete n;
+    return true;
+}
+
 hh_net *hh_create(int num_kpts, int C, int dtype)
 {
-    if (dtype != HH_DTYPE_BF16 && dtype != HH_DTYPE_FP8) { hh_set_error("hh_create: dtype must be HH_DTYPE_BF16 or HH_DTYPE_FP8"); return nullptr; }
+    if (dtype != HH_DTYPE_BF16 && dtype != HH_DTYPE_FP8 && dtype != HH_DTYPE_F16) {
+        hh_set_error("hh_create: dtype must be HH_DTYPE_BF16 (1), HH_DTYPE_FP8 (2) or HH_DTYPE_F16 (3)");
+        return nullptr;
+    }
     if (num_kpts <= 0 || num_kpts > 64 || C <= 0 || C % 16) { hh_set_error("hh_create: need 0 < num_kpts <= 64 and C % 16 == 0"); return nullptr; }
     hh_net *n = new hh_net();
     n->K = num_kpts; n->C = C; n->dtype = dtype;
     n->sw = PlanSwitches::from_env();
+    if (f16_switch_refused(n)) return nullptr;
     n->build();
     return n;
 }
 hh_net *hh_create_classifier(int C, int num_classes, int dtype)
 {
-    if (dtype != HH_DTYPE_BF16) { hh_set_error("hh_create_classifier: only HH_DTYPE_BF16 is implemented"); return nullptr; }
+    if (dtype != HH_DTYPE_BF16 && dtype != HH_DTYPE_F16) { hh_set_error("hh_create_classifier: dtype must be HH_DTYPE_BF16 (1) or HH_DTYPE_F16 (3)"); return nullptr; }
     if (C <= 0 || C % 16 || num_classes <= 0) { hh_set_error("hh_create_classifier: need C % 16 == 0 and num_classes > 0"); return nullptr; }
     hh_net *n = new hh_net();
     n->K = 17; n->C = C; n->dtype = dtype; n->kind = 1; n->num_classes = num_classes;
     n->sw = PlanSwitches::from_env();
+    if (f16_switch_refused(n)) return nullptr;
     n->build();
     return n;
 }

@@ -1,4 +1,4 @@
-// Implicit-GEMM convolution on gfx950 matrix cores (v_mfma_f32_32x32x16_bf16; _f16 on the training path's fp16 form), NHWC bf16 / fp16.
+// Implicit-GEMM convolution on gfx950 matrix cores (v_mfma_f32_32x32x16_bf16; _f16 for fp16 activations: the training path's fp16 form and HH_DTYPE_F16 handles), NHWC bf16 / fp16.
 //
 // Replaces the ATen conv2d / conv_transpose2d + batch_norm + relu + add chain the
 // reference dispatches per layer (hrnet.py:38-45,83-100,190,202,254,265,354-356;
@@ -467,11 +467,8 @@ typedef void (*conv_fn)(const ConvParams);
 #define CFG_FN(ks, s, kc, nt, wc, pt, tw, db) conv_mfma_kernel<ElemBF16, ks, s, kc, nt, wc, pt, tw, db>,
 static const conv_fn g_fns[] = {CONV_CONFIGS(CFG_FN)};
 #undef CFG_FN
-// fp16 (act_dtype 1): the training path's instantiations.  hh_conv2d never picks a two-buffer (DB) one -- only the inference
-// engine does, which stays bf16 -- so those have no fp16 form and launching one is an error.
-template <int KS, int S, int KC, int NT, int WC, int PT, int TW, int DB>
-static constexpr conv_fn f16_fn() { if constexpr (DB) return nullptr; else return conv_mfma_kernel<ElemF16, KS, S, KC, NT, WC, PT, TW, 0>; }
-#define CFG_FN(ks, s, kc, nt, wc, pt, tw, db) f16_fn<ks, s, kc, nt, wc, pt, tw, db>(),
+// fp16 (act_dtype 1): the training path's instantiations and those of HH_DTYPE_F16 inference handles (which also pick the two-buffer ones)
+#define CFG_FN(ks, s, kc, nt, wc, pt, tw, db) conv_mfma_kernel<ElemF16, ks, s, kc, nt, wc, pt, tw, db>,
 static const conv_fn g_fns_f16[] = {CONV_CONFIGS(CFG_FN)};
 #undef CFG_FN
 
@@ -484,7 +481,6 @@ hipError_t conv_init()
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(g_fns[i]),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_configs[i].lds_bytes());
         if (e != hipSuccess) return e;
-        if (!g_fns_f16[i]) continue;
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(g_fns_f16[i]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_configs[i].lds_bytes());
         if (e != hipSuccess) return e;
     }
@@ -494,7 +490,7 @@ hipError_t conv_init()
 hipError_t conv_launch(int cfg_index, const ConvParams &p, hipStream_t stream, int act_dtype)
 {
     const conv_fn fn = act_dtype == 0 ? g_fns[cfg_index] : (act_dtype == 1 ? g_fns_f16[cfg_index] : nullptr);
-    if (!fn) return hipErrorInvalidValue;  // unknown element type, or an instantiation without an fp16 form
+    if (!fn) return hipErrorInvalidValue;  // unknown element type
     const ConvConfig &c = g_configs[cfg_index];
     const unsigned tiles = (unsigned)p.B * p.tiles_y * p.tiles_x, sf = (unsigned)p.ncg * (p.nphase > 1 ? p.nphase : 1);
     const unsigned grid = sf > 1 ? (tiles + 7) / 8 * 8 * sf : tiles;  // groups of 8 tiles x sf variants (see the kernel)

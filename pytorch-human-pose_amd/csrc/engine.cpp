@@ -2,6 +2,7 @@
 // /root/reference/src/keypoints/architectures/{hrnet.py:342-385, higher_hrnet.py:47-81} as
 // a flat list of fused launches; parameter names are the reference's state-dict keys.
 #include "engine.h"
+#include "f16_host.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -57,6 +58,18 @@ static inline float bf2f(bf16_raw h)
     float f;
     memcpy(&f, &u, 4);
     return f;
+}
+bf16_raw hh_net::cvt16(float f) const { return act() ? hh_f32_to_f16(f) : f2bf(f); }
+float hh_net::widen16(bf16_raw v) const { return act() ? hh_f16_to_f32(v) : bf2f(v); }
+int hh_net::check_packed(const std::vector<bf16_raw> &packed, const std::string &param_name) const
+{
+    if (!act()) return 0;
+    for (bf16_raw v : packed)
+        if (hh_f16_is_inf(v)) {
+            hh_set_error("hh_finalize: " + param_name + ": a BatchNorm-folded weight exceeds the fp16 range (+-65504); use a bf16 handle for this checkpoint");
+            return 1;
+        }
+    return 0;
 }
 
 // ------------------------------------------------------------------------- parameters
@@ -247,7 +260,7 @@ struct Builder {
         for (int u = 0; u < 4; ++u) {
             const std::string up = prefix + "." + std::to_string(u);
             const bool fused_fp8 = n.dtype == 2 && bb_fp8_supported(C) && branch == 0;  // highest-resolution branch / deconv head
-            if (((C == 32 || (C == 64 && !n.sw.no_bb64)) && n.dtype != 2) || fused_fp8) {  // fused kernels, ping-pong x <-> m (a tile reads its neighbours' halo: no in-place)
+            if (((C == 32 || (C == 64 && !n.sw.no_bb64)) && n.is16()) || fused_fp8) {  // fused kernels, ping-pong x <-> m (a tile reads its neighbours' halo: no in-place)
                 Op o;
                 o.kind = OP_BB;
                 o.layer = L(up + ".conv1", up + ".bn1", C, C, 3, 1);
@@ -281,7 +294,7 @@ struct Builder {
         // stem (hrnet.py:354-358,378-384)
         // bf16: both stem convolutions in ONE kernel (stem_fused.hip), the half-resolution intermediate never leaves the CU
         // (HH_NO_STEM_FUSED=1 and the fp8 path: two launches through the tensor S1)
-        const bool stem_fused = n.dtype != 2 && !n.sw.no_stem_fused;
+        const bool stem_fused = n.is16() && !n.sw.no_stem_fused;
         const int S1 = stem_fused ? -1 : T(64, 1), X = T(64, 2);
         {   // conv1 reads the fp32 NCHW images itself (stem_conv.hip): no layout pass, no padded input channels
             Op o;
@@ -299,7 +312,7 @@ struct Builder {
         // bf16: the junctions work in pairs -- units 0 and 2 do not store their 256-channel y, units 1 and 3 make it again per pixel
         // from the previous unit's t2 (two more 1x1 GEMMs) -- so conv2 alternates between two t2 tensors
         // (HH_NO_JUNC_PAIR=1: every junction stores y and the next one reads it)
-        const bool jpair = n.dtype != 2 && !n.sw.no_junc_pair;
+        const bool jpair = n.is16() && !n.sw.no_junc_pair;
         const int t1 = T(64, 2), t2 = T(64, 2), t2b = jpair ? T(64, 2) : t2, Y = T(256, 2);
         // conv3 (+ downsample) of unit u and conv1 of unit u+1 are both 1x1: one junction kernel makes y and the next t1 in a
         // single pass over the 256-channel tensor (bottleneck_junction.hip)
@@ -351,7 +364,7 @@ struct Builder {
 
         // bf16 handles fold init_heatmaps_head into the transposed conv (ConvLayer::fold_w): the buffer is [feats | 1 | zero pad] and
         // the 1x1 head leaves the chain of dependent launches (it runs beside the deconv head on lane 1)
-        const bool head_fold = n.dtype != 2 && n.kind == 0 && !n.sw.no_head_fold;
+        const bool head_fold = n.is16() && n.kind == 0 && !n.sw.no_head_fold;
         const int catC = head_fold ? round_up(C + 1, 16) : round_up(C + 2 * K, 16);
         const int CAT = T(catC, 2, true);  // [feats | init heatmaps | zero pad] = torch.cat of higher_hrnet.py:73
         n.tensors[CAT].shared_scale = true;
@@ -398,7 +411,7 @@ struct Builder {
                     // bf16, 32-channel branch 0: output 0 as ONE launch (fusion_up.hip) that runs the 1x1 terms once per low-resolution
                     // pixel and keeps them on the chip; it waits for every source up front.  (HH_NO_FUSED_UPSUM=1: a 1x1 launch per
                     // source as each becomes ready, then upadd_kernel -- the same bits)
-                    if (i == 0 && n.dtype != 2 && w[0] == 32 && !n.sw.no_fused_upsum) {
+                    if (i == 0 && n.is16() && w[0] == 32 && !n.sw.no_fused_upsum) {
                         Op o;
                         o.kind = OP_UPSUM; o.in = x[0]; o.out = OUT; o.C = w[0]; o.relu = 1; o.lane = lane;
                         for (int j = 1; j < nsc; ++j) {
@@ -426,7 +439,7 @@ struct Builder {
                     // output's, so the sum of those convs is one conv over the concatenated channels -- one launch instead of i
                     // dependent ones on the lane that already has the longest chain.  Its inputs must share a pixel stride: chain
                     // intermediates are allocated with the stride of branch i-1.  (HH_NO_FUSION_MERGE=1: one launch per source)
-                    if (i >= 2 && n.dtype != 2 && !n.sw.no_fusion_merge) {
+                    if (i >= 2 && n.is16() && !n.sw.no_fusion_merge) {
                         int srcs[3] = {-1, -1, -1};
                         ConvLayer ml;
                         ml.cout = w[i]; ml.ks = 3; ml.stride = 2; ml.cin = 0;
@@ -571,7 +584,7 @@ struct Builder {
             o.hi = hi_heads; n.layers[o.layer].hi = hi_heads;
             // bf16, 32 channels: the head runs in the last block's epilogue (basicblock_fused_pc.hip, FIN) and this op is skipped --
             // decided per forward in enqueue() (not with taps on: "deconv#0" is the block output that is then never stored)
-            if (n.dtype != 2 && C == 32 && K <= 32 && n.ops[last_bb].kind == OP_BB) {
+            if (n.is16() && C == 32 && K <= 32 && n.ops[last_bb].kind == OP_BB) {
                 n.layers[o.layer].fin_head = true;
                 n.ops[last_bb].fin = (int)n.ops.size() - 1;
             }
@@ -614,9 +627,9 @@ void hh_net::assign_fp8_formats()
     }
 }
 
-// Kernel-order weight image: [cout_group][cin_chunk][tap][KC/8][COUT_T][8] bf16, BN scale folded in, zero padded.
+// Kernel-order weight image: [cout_group][cin_chunk][tap][KC/8][COUT_T][8] bf16 (act_dtype 1: fp16), BN scale folded in, zero padded.
 void hh_pack_weights(const float *W, const float *scale, int ks, int cin, int cout, int KC, int COUT_T, bool transposed,
-                     int py, int px, std::vector<bf16_raw> &packed)
+                     int py, int px, std::vector<bf16_raw> &packed, int act_dtype)
 {
     const int coutp = round_up(cout, COUT_T), ncg = coutp / COUT_T, cin_pad = round_up(cin, KC);
     const int nch = cin_pad / KC, taps = ks * ks, C8 = KC / 8;
@@ -638,7 +651,7 @@ void hh_pack_weights(const float *W, const float *scale, int ks, int cin, int co
                             float v;
                             if (transposed) v = W[(((size_t)ci * cout + co) * 4 + ky) * 4 + kx];
                             else v = W[(((size_t)co * cin + ci) * ks + ky) * ks + kx];
-                            packed[o] = f2bf(v * scale[co]);
+                            packed[o] = act_dtype ? hh_f32_to_f16(v * scale[co]) : f2bf(v * scale[co]);
                         }
             }
 }
@@ -709,9 +722,10 @@ int hh_net::finalize()
                 const float sc = bn_fold(l.bn, co, nullptr, &shift[co]);
                 for (int t = 0; t < 27; ++t) {
                     const int kk = t / 16, hh = (t % 16) / 8, j = t % 8;
-                    packed[((((co / 32) * 2 + kk) * 2 + hh) * 32 + co % 32) * 8 + j] = f2bf(W[(size_t)co * 27 + t] * sc);
+                    packed[((((co / 32) * 2 + kk) * 2 + hh) * 32 + co % 32) * 8 + j] = cvt16(W[(size_t)co * 27 + t] * sc);
                 }
             }
+            if (check_packed(packed, l.conv + ".weight")) return 1;
             if (hh_upload(&l.d_w, packed.data(), packed.size() * 2) || hh_upload(&l.d_bias, shift.data(), 64 * 4)) return 1;
             continue;
         }
@@ -743,11 +757,14 @@ int hh_net::finalize()
                     shift[co] += sh;
                     for (int ci = 0; ci < l.mcin[m]; ++ci)
                         for (int t = 0; t < 9; ++t) Wm[((size_t)co * l.cin + c0 + ci) * 9 + t] = Wj[((size_t)co * l.mcin[m] + ci) * 9 + t] * sc;
+                    if (act())  // (per source, so that the message names the conv the weight belongs to)
+                        for (int i = 0; i < l.mcin[m] * 9; ++i)
+                            if (hh_f16_is_inf(hh_f32_to_f16(Wj[(size_t)co * l.mcin[m] * 9 + i] * sc))) return check_packed({0x7c00}, l.mconv[m] + ".weight");
                 }
                 c0 += l.mcin[m];
             }
             std::vector<bf16_raw> packed;
-            hh_pack_weights(Wm.data(), one.data(), 3, l.cin, l.cout, l.KC, COUT_T, false, 0, 0, packed);
+            hh_pack_weights(Wm.data(), one.data(), 3, l.cin, l.cout, l.KC, COUT_T, false, 0, 0, packed, act());
             if (hh_upload(&l.d_w, packed.data(), packed.size() * 2) || hh_upload(&l.d_bias, shift.data(), (size_t)coutp * 4)) return 1;
             continue;
         }
@@ -772,19 +789,20 @@ int hh_net::finalize()
         if (l.transposed && l.py < 0) {
             for (int ph = 0; ph < 4; ++ph) {
                 std::vector<bf16_raw> one;
-                hh_pack_weights(W.data(), scale.data(), l.ks, l.cin, l.cout, l.KC, COUT_T, true, ph >> 1, ph & 1, one);
+                hh_pack_weights(W.data(), scale.data(), l.ks, l.cin, l.cout, l.KC, COUT_T, true, ph >> 1, ph & 1, one, act());
                 l.phase_stride = one.size();
                 packed.insert(packed.end(), one.begin(), one.end());
             }
         } else
-            hh_pack_weights(W.data(), scale.data(), l.ks, l.cin, l.cout, l.KC, COUT_T, l.transposed, l.py, l.px, packed);
+            hh_pack_weights(W.data(), scale.data(), l.ks, l.cin, l.cout, l.KC, COUT_T, l.transposed, l.py, l.px, packed, act());
+        if (check_packed(packed, l.conv + ".weight")) return 1;
         if (hh_upload(&l.d_w, packed.data(), packed.size() * 2) || hh_upload(&l.d_bias, shift.data(), (size_t)coutp * 4)) return 1;
         if (l.fin_head) {  // B fragments of the head inside bbpc_final_kernel: lane (cout r, half h) of k half m holds cin 16m + 8h .. +7
             std::vector<bf16_raw> wf(2 * 2 * 32 * 8, 0);
             for (int m = 0; m < 2; ++m)
                 for (int hh = 0; hh < 2; ++hh)
                     for (int co = 0; co < l.cout; ++co)
-                        for (int j = 0; j < 8; ++j) wf[(((m * 2 + hh) * 32) + co) * 8 + j] = f2bf(W[(size_t)co * l.cin + 16 * m + 8 * hh + j] * scale[co]);
+                        for (int j = 0; j < 8; ++j) wf[(((m * 2 + hh) * 32) + co) * 8 + j] = cvt16(W[(size_t)co * l.cin + 16 * m + 8 * hh + j] * scale[co]);
             if (hh_upload(&l.d_wfin, wf.data(), wf.size() * 2)) return 1;
         }
     }
@@ -835,11 +853,12 @@ int hh_net::reserve(int B, int H, int W)
             if (alloc(bytes, (void **)&t.ptr)) return 1;
             if (sw.poison_ws) HH_CHECK_HIP(hipMemset(t.ptr, 0xFF, bytes));
             if (t.zero_init) HH_CHECK_HIP(hipMemset(t.ptr, 0, bytes));
-            if (t.ones_channel >= 0 && dtype != 2) {  // bf16 1.0 = 0x3F80 in channel `ones_channel` of every pixel
+            if (t.ones_channel >= 0 && is16()) {  // 1.0 (bf16 0x3F80, fp16 0x3C00) in channel `ones_channel` of every pixel
                 const size_t npix = (size_t)nB * (nH >> t.shift) * (nW >> t.shift);
                 char *c0 = (char *)t.ptr + (size_t)t.ones_channel * 2;
-                HH_CHECK_HIP(hipMemset2D(c0, (size_t)t.C * 2, 0x80, 1, npix));
-                HH_CHECK_HIP(hipMemset2D(c0 + 1, (size_t)t.C * 2, 0x3F, 1, npix));
+                const bf16_raw one = cvt16(1.f);
+                HH_CHECK_HIP(hipMemset2D(c0, (size_t)t.C * 2, one & 0xff, 1, npix));
+                HH_CHECK_HIP(hipMemset2D(c0 + 1, (size_t)t.C * 2, one >> 8, 1, npix));
             }
         }
         if (dtype == 2 && t.b16) {
@@ -1036,7 +1055,7 @@ int hh_net::enqueue(const float *images, int B, int H, int W, float *o1, float *
                 HH_CHECK_HIP(hipMalloc((void **)&d_pool, (size_t)B * op.C * 4));
                 pool_cap = B * op.C;
             }
-            HH_CHECK_HIP(launch_avgpool(ti.ptr, ti.C, d_pool, B, (H >> ti.shift) * (W >> ti.shift), op.C, s));
+            HH_CHECK_HIP(launch_avgpool(ti.ptr, ti.C, d_pool, B, (H >> ti.shift) * (W >> ti.shift), op.C, s, act()));
             break;
         }
         case OP_LINEAR:
@@ -1091,9 +1110,10 @@ int hh_net::enqueue_stem(const Op &op, const float *images, int B, int H, int W,
         q.B = B; q.H = H; q.W = W;
         if (!stem_fused_supported(q)) { hh_set_error("hh_forward: the fused stem needs H, W multiples of 4 and images below 2 GB (HH_NO_STEM_FUSED=1)"); return 1; }
         if (prof_enabled && prof_record(op, HH_CFG_STEM_FUSED, op_cost(op, B, H, W), &q.clk)) return 1;
-        HH_CHECK_HIP(stem_fused_launch(q, num_cus, s));
+        HH_CHECK_HIP(stem_fused_launch(q, num_cus, s, act()));
         return 0;
     }
+    if (act()) { hh_set_error("hh_forward: stem_conv.hip has no fp16 form"); return 1; }  // (hh_create refuses HH_NO_STEM_FUSED on an fp16 handle)
     StemParams p{};
     p.images = images; p.w = l.d_w; p.bias = l.d_bias;
     p.out = tensors[op.out].ptr; p.out_cs = tensors[op.out].C;
@@ -1118,7 +1138,7 @@ int hh_net::enqueue_upadd(const Op &op, int B, int H, int W, hipStream_t s)
     }
     p.out = o.ptr; p.out_cs = o.C; p.out_coff = 0;
     p.B = B; p.H = H >> b.shift; p.W = W >> b.shift; p.C = op.C; p.relu = op.relu;
-    HH_CHECK_HIP(launch_upadd(p, s));
+    HH_CHECK_HIP(launch_upadd(p, s, act()));
     return 0;
 }
 
@@ -1140,7 +1160,7 @@ int hh_net::enqueue_upsum(const Op &op, int B, int H, int W, hipStream_t s)  // 
     p.out = o.ptr; p.out_cs = o.C;
     p.B = B; p.H = H >> b0.shift; p.W = W >> b0.shift;
     if (prof_enabled && prof_record(op, HH_CFG_FUSION_UP, op_cost(op, B, H, W), &p.clk)) return 1;
-    HH_CHECK_HIP(fusion_up_launch(p, s));
+    HH_CHECK_HIP(fusion_up_launch(p, s, act()));
     return 0;
 }
 
@@ -1161,7 +1181,7 @@ int hh_net::enqueue_junc(const Op &op, int B, int H, int W, hipStream_t s)
     if (op.out >= 0) { p.y = tensors[op.out].ptr; p.y_cs = tensors[op.out].C; }
     p.npix = B * (H >> ti.shift) * (W >> ti.shift);
     if (prof_enabled && prof_record(op, HH_CFG_JUNCTION, op_cost(op, B, H, W), &p.clk)) return 1;
-    HH_CHECK_HIP(junction_launch(p, num_cus, s));
+    HH_CHECK_HIP(junction_launch(p, num_cus, s, act()));
     return 0;
 }
 
@@ -1189,8 +1209,9 @@ int hh_net::enqueue_bb(const Op &op, int B, int H, int W, float *o2, bool multi,
     // runs: forward 4.48 -> 4.39 ms, +1.5-2 % img/s (three alternations, profiles/r03_ab.md); a quarter of the chip for the
     // 64-channel block loses 6 %.  Alone (outside an HR module, or with the lanes off): all of the chip.
     const int fat = multi && op.siblings ? (num_cus + 1) / 2 : num_cus;
-    if (l1.cout == 64) HH_CHECK_HIP(bb64_fused_launch(p, fat, s));
-    else if (!sw.bb32_tile && bbpc_supported(p)) HH_CHECK_HIP(bbpc_launch(p, fat, s));
+    if (l1.cout == 64) HH_CHECK_HIP(bb64_fused_launch(p, fat, s, act()));
+    else if (!sw.bb32_tile && bbpc_supported(p)) HH_CHECK_HIP(bbpc_launch(p, fat, s, act()));
+    else if (act()) { hh_set_error("hh_forward: the tile-form 32-channel block (tensors of 2 GB and more) has no fp16 form"); return 1; }
     else HH_CHECK_HIP(bb_fused_launch(p, num_cus, s));
     return 0;
 }
@@ -1228,7 +1249,7 @@ int hh_net::enqueue_conv(const Op &op, int B, int H, int W, float *o1, float *o2
     p.tiles_x = (p.Wo + c.TW - 1) / c.TW;
     p.tiles_y = (p.Ho + c.th() - 1) / c.th();
     if (prof_enabled && prof_record(op, cfg, op_cost(op, B, H, W), &p.clk)) return 1;
-    HH_CHECK_HIP(conv_launch(cfg, p, s));
+    HH_CHECK_HIP(conv_launch(cfg, p, s, act()));  // (an fp8 handle's op.hi convs: bf16)
     return 0;
 }
 
@@ -1455,7 +1476,9 @@ int hh_tap_read_impl(hh_net *n, int index, float *host)
     for (int b = 0; b < B; ++b)
         for (int c = 0; c < t.C; ++c)
             for (int y = 0; y < h; ++y)
-                for (int x = 0; x < w; ++x)
-                    host[(((size_t)b * t.C + c) * h + y) * w + x] = bf2f(tmp[(((size_t)b * h + y) * w + x) * d.C + t.coff + c]);
+                for (int x = 0; x < w; ++x) {
+                    const bf16_raw v = tmp[(((size_t)b * h + y) * w + x) * d.C + t.coff + c];
+                    host[(((size_t)b * t.C + c) * h + y) * w + x] = n->widen16(v);  // (an fp8 handle's 16-bit taps are bf16: act() == 0)
+                }
     return 0;
 }

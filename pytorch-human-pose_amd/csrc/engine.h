@@ -1,5 +1,5 @@
 // Host-side engine: builds the HigherHRNet layer plan from (num_kpts, C), owns the
-// parameters under the reference's state-dict names, folds BN, packs bf16 weights for the
+// parameters under the reference's state-dict names, folds BN, packs bf16 (or fp16 / e4m3) weights for the
 // MFMA kernels and executes the plan on a HIP stream.
 #pragma once
 #include <map>
@@ -10,7 +10,7 @@
 
 void hh_set_error(const std::string &msg);
 void hh_pack_weights(const float *W, const float *scale, int ks, int cin, int cout, int KC, int COUT_T, bool transposed,
-                     int py, int px, std::vector<unsigned short> &packed);
+                     int py, int px, std::vector<unsigned short> &packed, int act_dtype = 0);
 #define HH_CHECK_HIP(expr)                                                                             \
     do {                                                                                               \
         hipError_t _e = (expr);                                                                        \
@@ -218,6 +218,14 @@ struct hh_net {
     std::vector<float> amax;      // host copy, kept over the calibration rounds (running maximum); [2 * ops]: the second half holds the
                                   // intermediate-tile maxima of fused BasicBlocks
     int elem() const { return dtype == 2 ? 1 : 2; }  // bytes per activation element
+    // A 16-bit engine (HH_DTYPE_BF16 or HH_DTYPE_F16): one plan -- the same ops, lanes, fusions and workspace -- whose kernels are
+    // instantiated over the element type; act() is the act_dtype its launches pass (0 = bf16, 1 = fp16, kernels.h).
+    bool is16() const { return dtype != 2; }
+    int act() const { return dtype == 3 ? 1 : 0; }
+    bf16_raw cvt16(float f) const;    // fp32 -> this handle's 16-bit element (host side, round to nearest even)
+    float widen16(bf16_raw v) const;  // and back
+    // fp16 handles: a packed weight image that holds +-inf (a BN-folded weight beyond +-65504) fails hh_finalize with the parameter's name
+    int check_packed(const std::vector<bf16_raw> &packed, const std::string &param_name) const;
 
     const std::vector<float> &param(const std::string &name) const { return params[param_index.at(name)].data; }
     int build();

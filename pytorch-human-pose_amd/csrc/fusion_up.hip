@@ -1,4 +1,4 @@
-// Output 0 of a FusionLayer (hrnet.py:166-229) in ONE launch, 32-channel branch 0 (bf16 handles):
+// Output 0 of a FusionLayer (hrnet.py:166-229) in ONE launch, 32-channel branch 0 (bf16 and fp16 handles; written out for bf16 below):
 //
 //     out = relu(x0 + up(u1) + up(u2) [+ up(u3)]),   u_j = bf16(b_j + W_j x_j)   (1x1 conv + folded BN at the resolution of x_j)
 //
@@ -20,7 +20,7 @@ constexpr int TH = 8, TW = 32, CO = 32;  // branch-0 tile, output channels
 
 // One wave: u_J for 32 consecutive pixels (index 32 * COL ..) of the tile's J-shifted footprint, into LDS [pixel][32] bf16.
 // x_J has 32 << J channels = (2 << J) k-steps.
-template <int J, int COL>
+template <typename E, int J, int COL>
 __device__ __forceinline__ void source_tile(const FusionUpParams &p, int b, int oy0, int ox0, bf16_raw *lds_u, int lane)
 {
     constexpr int FW = TW >> J, NPX = (TH >> J) * FW, NSTEP = 2 << J;
@@ -48,7 +48,7 @@ __device__ __forceinline__ void source_tile(const FusionUpParams &p, int b, int 
     });
     static_for<NSTEP>([&](auto sc) {
         constexpr int s = decltype(sc)::value;
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa[s]), __builtin_bit_cast(bf16x8, fb[s]), acc, 0, 0, 0);
+        acc = E::mfma(fa[s], fb[s], acc);
     });
     if (q < NPX) {
         unsigned *dst = reinterpret_cast<unsigned *>(lds_u + q * CO + 4 * h);
@@ -56,13 +56,15 @@ __device__ __forceinline__ void source_tile(const FusionUpParams &p, int b, int 
         static_for<4>([&](auto gc) {
             constexpr int g = decltype(gc)::value;
             *reinterpret_cast<uint2 *>(dst + 4 * g) =
-                make_uint2(pack_bf16x2(acc[4 * g + 0], acc[4 * g + 1], nofloor), pack_bf16x2(acc[4 * g + 2], acc[4 * g + 3], nofloor));
+                make_uint2(E::pack(acc[4 * g + 0], acc[4 * g + 1], nofloor), E::pack(acc[4 * g + 2], acc[4 * g + 3], nofloor));
         });
     }
 }
 
 }  // namespace
 
+// E: the element type (ElemBF16 / ElemF16 of mfma_dev.h)
+template <typename E>
 __global__ __launch_bounds__(256) void fusion_up_kernel(const FusionUpParams p)
 {
     __shared__ __attribute__((aligned(16))) bf16_raw u1[(TH >> 1) * (TW >> 1) * CO];
@@ -91,10 +93,10 @@ __global__ __launch_bounds__(256) void fusion_up_kernel(const FusionUpParams p)
 
     // 1x1 terms: wave 0 / 1 = the two 32-pixel halves of x1's footprint, wave 2 = x2's, wave 3 = x3's (wave-uniform branches)
     const int wave = tid >> 6, lane = tid & 63;
-    if (wave == 0) source_tile<1, 0>(p, b, oy0, ox0, u1, lane);
-    else if (wave == 1) source_tile<1, 1>(p, b, oy0, ox0, u1, lane);
-    else if (wave == 2) { if (p.nsrc >= 2) source_tile<2, 0>(p, b, oy0, ox0, u2, lane); }
-    else if (p.nsrc >= 3) source_tile<3, 0>(p, b, oy0, ox0, u3, lane);
+    if (wave == 0) source_tile<E, 1, 0>(p, b, oy0, ox0, u1, lane);
+    else if (wave == 1) source_tile<E, 1, 1>(p, b, oy0, ox0, u1, lane);
+    else if (wave == 2) { if (p.nsrc >= 2) source_tile<E, 2, 0>(p, b, oy0, ox0, u2, lane); }
+    else if (p.nsrc >= 3) source_tile<E, 3, 0>(p, b, oy0, ox0, u3, lane);
     __syncthreads();
 
     // upadd_kernel's sum: base, then the sources in j order, fp32, ReLU, one rounding
@@ -103,12 +105,12 @@ __global__ __launch_bounds__(256) void fusion_up_kernel(const FusionUpParams p)
         const int u = 256 * i + tid, px = u >> 2, c8 = u & 3;
         const int ly = px / TW, lx = px % TW;
         const u32x4 bv = base[i];
-        float v[8] = {bf16_lo(bv[0]), bf16_hi(bv[0]), bf16_lo(bv[1]), bf16_hi(bv[1]),
-                      bf16_lo(bv[2]), bf16_hi(bv[2]), bf16_lo(bv[3]), bf16_hi(bv[3])};
+        float v[8] = {E::lo(bv[0]), E::hi(bv[0]), E::lo(bv[1]), E::hi(bv[1]),
+                      E::lo(bv[2]), E::hi(bv[2]), E::lo(bv[3]), E::hi(bv[3])};
         auto add = [&](const bf16_raw *lds, int J) {
             const u32x4 uv = *reinterpret_cast<const u32x4 *>(lds + ((ly >> J) * (TW >> J) + (lx >> J)) * CO + c8 * 8);
-            v[0] += bf16_lo(uv[0]); v[1] += bf16_hi(uv[0]); v[2] += bf16_lo(uv[1]); v[3] += bf16_hi(uv[1]);
-            v[4] += bf16_lo(uv[2]); v[5] += bf16_hi(uv[2]); v[6] += bf16_lo(uv[3]); v[7] += bf16_hi(uv[3]);
+            v[0] += E::lo(uv[0]); v[1] += E::hi(uv[0]); v[2] += E::lo(uv[1]); v[3] += E::hi(uv[1]);
+            v[4] += E::lo(uv[2]); v[5] += E::hi(uv[2]); v[6] += E::lo(uv[3]); v[7] += E::hi(uv[3]);
         };
         add(u1, 1);
         if (p.nsrc >= 2) add(u2, 2);
@@ -117,19 +119,20 @@ __global__ __launch_bounds__(256) void fusion_up_kernel(const FusionUpParams p)
         for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
         if (valid[i])
             *reinterpret_cast<u32x4 *>(p.out + opix[i] * p.out_cs + c8 * 8) =  // (upadd_kernel's pack)
-                u32x4{round_bf16x2(v[0], v[1]), round_bf16x2(v[2], v[3]), round_bf16x2(v[4], v[5]), round_bf16x2(v[6], v[7])};
+                u32x4{E::round2(v[0], v[1]), E::round2(v[2], v[3]), E::round2(v[4], v[5]), E::round2(v[6], v[7])};
     });
     if (p.clk && tid == 0 && blockIdx.x + 256 >= gridDim.x) atomicMax(p.clk + 1, wall_clock64());
 }
 
 bool fusion_up_supported(int C, int nsrc) { return C == CO && nsrc >= 1 && nsrc <= 3; }
 
-hipError_t fusion_up_launch(FusionUpParams p, hipStream_t s)
+hipError_t fusion_up_launch(FusionUpParams p, hipStream_t s, int act_dtype)
 {
-    if (!fusion_up_supported(CO, p.nsrc)) return hipErrorInvalidValue;
+    if (!fusion_up_supported(CO, p.nsrc) || (act_dtype != 0 && act_dtype != 1)) return hipErrorInvalidValue;
     p.tiles_x = (p.W + TW - 1) / TW;
     p.tiles_y = (p.H + TH - 1) / TH;
     const unsigned grid = (unsigned)p.B * p.tiles_y * p.tiles_x;
-    HH_LAUNCH(fusion_up_kernel, dim3(grid), dim3(256), 0, s, p);
+    if (act_dtype) HH_LAUNCH(fusion_up_kernel<ElemF16>, dim3(grid), dim3(256), 0, s, p);
+    else HH_LAUNCH(fusion_up_kernel<ElemBF16>, dim3(grid), dim3(256), 0, s, p);
     return hipGetLastError();
 }

@@ -5,10 +5,10 @@
 
 #include <hip/hip_ext.h>
 
-typedef uint16_t bf16_raw;  // storage type of a bf16 element in HBM (and of an fp16 one on the training path)
+typedef uint16_t bf16_raw;  // storage type of a bf16 element in HBM (and of an fp16 one: the training path's fp16 form, HH_DTYPE_F16 handles)
 // act_dtype of the training launchers: the element type of activations and packed weights, 0 = bf16, 1 = fp16 (HH_ACT_BF16 / HH_ACT_F16
-// of hhrnet.h); anything else is hipErrorInvalidValue.  The two-buffer conv instantiations have no fp16 form (only the inference
-// engine, which is bf16, picks them).
+// of hhrnet.h); anything else is hipErrorInvalidValue.  The fused inference kernels take the same parameter: an HH_DTYPE_F16 handle
+// passes 1.
 
 // Per-launch timing probe (bench.py's roofline line).  When the engine arms it, the NEXT forward-path kernel launch of this
 // thread goes through hipExtLaunchKernelGGL with a start / stop event pair: the runtime fills those from the dispatch packet's
@@ -206,11 +206,11 @@ hipError_t bb_fused_launch(BBParams p, int num_cus, hipStream_t s);
 hipError_t bbpc_init();
 bool bbpc_supported(const BBParams &p);
 bool bbpc_final_supported(const BBParams &p);
-hipError_t bbpc_launch(BBParams p, int num_cus, hipStream_t s);
+hipError_t bbpc_launch(BBParams p, int num_cus, hipStream_t s, int act_dtype = 0);
 // the same block for the 64-channel branch (basicblock_fused_c64.hip): weights packed KS=3,S=1,KC=32,NT=2 ([chunk][tap][4][64][8])
 #define HH_CFG_BB64_FUSED 103
 hipError_t bb64_fused_init();
-hipError_t bb64_fused_launch(BBParams p, int num_cus, hipStream_t s);
+hipError_t bb64_fused_launch(BBParams p, int num_cus, hipStream_t s, int act_dtype = 0);
 
 // Junction of two stage-0 Bottlenecks (bottleneck_junction.hip): y = relu(W3 t2 + shift (+ Wd x | + res)), t1 = relu(W1 y + shift1)
 struct JuncParams {
@@ -228,7 +228,7 @@ struct JuncParams {
 };
 #define HH_CFG_JUNCTION 101  // pseudo instantiation index used by the profiler
 hipError_t junction_init();
-hipError_t junction_launch(const JuncParams &p, int num_cus, hipStream_t s);
+hipError_t junction_launch(const JuncParams &p, int num_cus, hipStream_t s, int act_dtype = 0);
 
 // First stem conv (stem_conv.hip): fp32 NCHW images -> conv3x3 s2 p1 (3->64) + BN + ReLU -> bf16 NHWC [B,H/2,W/2,out_cs]
 struct StemParams {
@@ -258,7 +258,7 @@ struct StemFusedParams {
 #define HH_CFG_STEM_FUSED 106
 hipError_t stem_fused_init();
 bool stem_fused_supported(const StemFusedParams &p);
-hipError_t stem_fused_launch(const StemFusedParams &p, int num_cus, hipStream_t s);
+hipError_t stem_fused_launch(const StemFusedParams &p, int num_cus, hipStream_t s, int act_dtype = 0);
 
 
 // out[b,y,x,c] = act(base[b,y,x,c] + sum_j up_j[b, y>>sh_j, x>>sh_j, c]),  c in [0,C)
@@ -285,7 +285,7 @@ struct FusionUpParams {
 };
 #define HH_CFG_FUSION_UP 107  // pseudo instantiation index used by the profiler
 bool fusion_up_supported(int C, int nsrc);
-hipError_t fusion_up_launch(FusionUpParams p, hipStream_t s);
+hipError_t fusion_up_launch(FusionUpParams p, hipStream_t s, int act_dtype = 0);
 hipError_t launch_upadd_backward(const bf16_raw *dy, const bf16_raw *out, int relu, int B, int H, int W, int C, bf16_raw *g, bf16_raw *const *dup,
                                  const int *up_shift, int nup, hipStream_t s, int act_dtype = 0);
 // the same on e4m3 tensors: out = e4m3(act(base * base_scale + sum_j up_j * up_scale[j]) * out_inv_scale); C multiple of 16

@@ -10,7 +10,7 @@
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));  // fp16: the training path only
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));  // fp16: the training path and HH_DTYPE_F16 inference handles
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -55,8 +55,8 @@ __device__ __forceinline__ float bf16_lo(unsigned u) { return __builtin_bit_cast
 __device__ __forceinline__ float bf16_hi(unsigned u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
 __device__ __forceinline__ unsigned short f2bf_dev(float f) { return __builtin_bit_cast(unsigned short, (__bf16)f); }
 
-// ---- fp16 pairs in a dword (the training path's second element type; the inference engine stays bf16)
-// Semantics of every fp16 store of the training kernels:
+// ---- fp16 pairs in a dword (the second element type of the training path and of the inference engine)
+// Semantics of every fp16 store of the training and inference kernels:
 //   * round to nearest even (v_cvt_pk_f16_f32 / v_cvt_f16_f32);
 //   * a value beyond +-65504 becomes +-inf, it is NOT saturated: the loss scaler detects an overflowing scale by it;
 //   * NaN / inf pass through (an operand of an MFMA or of the fp32 arithmetic around it, they reach every sum they enter);
@@ -76,36 +76,6 @@ __device__ __forceinline__ unsigned round_f16x2(float a, float b)
 __device__ __forceinline__ float f16_lo(unsigned u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u & 0xffffu)); }
 __device__ __forceinline__ float f16_hi(unsigned u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u >> 16)); }
 __device__ __forceinline__ unsigned short f2h_dev(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
-
-// 32 couts of one pixel: lanes (r,0) hold couts 8g..8g+3, lanes (r,1) couts 8g+4..8g+7 in acc[4g..4g+3].
-// Returns for m = 0,1 the 16 bytes (bf16, ReLU applied) of couts 16m+8h .. 16m+8h+7 of this lane's pixel.
-__device__ __forceinline__ void pack_rows16(const f32x16 &acc, u32x4 out[2])
-{
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        unsigned x0 = pack_relu_bf16x2(acc[8 * m + 0], acc[8 * m + 1]), x1 = pack_relu_bf16x2(acc[8 * m + 2], acc[8 * m + 3]);
-        unsigned y0 = pack_relu_bf16x2(acc[8 * m + 4], acc[8 * m + 5]), y1 = pack_relu_bf16x2(acc[8 * m + 6], acc[8 * m + 7]);
-        // lanes 0-31: X = couts 16m..+3, Y = 16m+8..+11; lanes 32-63: X = 16m+4..+7, Y = 16m+12..+15.
-        // swap X[32..63] <-> Y[0..31]: lanes 0-31 end with (X,Y) = couts 16m..16m+7, lanes 32-63 with 16m+8..16m+15
-        auto s0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
-        auto s1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
-        out[m] = u32x4{s0[0], s1[0], s0[1], s1[1]};
-    }
-}
-
-// Identity A fragments (rows = couts, k = cin) of lane (r, h): fragment kk has A[r][k] = 1 where 16*kk + k == r.  A residual added
-// as two more MFMAs against them is exact (x * 1.0 in fp32).
-__device__ __forceinline__ void ident_frags(int r, int h, u32x4 ident[2])
-{
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-        const int j = r - 16 * kk - 8 * h;  // element index inside this lane's 8-wide k slice
-        const unsigned one = (j & 1) ? 0x3f800000u : 0x00003f80u;  // bf16 1.0 in the high / low half of a dword
-        const bool on = j >= 0 && j < 8;
-        ident[kk] = u32x4{on && (j >> 1) == 0 ? one : 0u, on && (j >> 1) == 1 ? one : 0u, on && (j >> 1) == 2 ? one : 0u,
-                          on && (j >> 1) == 3 ? one : 0u};
-    }
-}
 
 // ---- fp8 (e4m3) path
 // four fp32 -> four e4m3 bytes (round to nearest even), clamped to the finite range +-448 ...
@@ -159,11 +129,12 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 
 }  // namespace
 
-// ---- the element type of a training kernel as a compile-time parameter: the 16-bit storage format of the activations and of the
+// ---- the element type of a kernel as a compile-time parameter: the 16-bit storage format of the activations and of the
 // packed weights, and the MFMA form that multiplies them.  Everything else of a kernel (tiling, staging, the fp32 accumulators,
 // the int16 ReLU clamp, the transposing LDS reads) does not depend on it.  ElemBF16 is the code the kernels had written out.  (Outside the
 // unnamed namespace: a kernel instantiated over these types keeps an ordinary external symbol.)
 struct ElemBF16 {
+    static constexpr unsigned ONE = 0x3f80u;  // 1.0
     static __device__ __forceinline__ unsigned pack(float a, float b, i16x2 floor) { return pack_bf16x2(a, b, floor); }
     static __device__ __forceinline__ unsigned round2(float a, float b) { return round_bf16x2(a, b); }
     static __device__ __forceinline__ float lo(unsigned u) { return bf16_lo(u); }
@@ -176,6 +147,7 @@ struct ElemBF16 {
     }
 };
 struct ElemF16 {
+    static constexpr unsigned ONE = 0x3c00u;  // 1.0
     static __device__ __forceinline__ unsigned pack(float a, float b, i16x2 floor) { return pack_f16x2(a, b, floor); }
     static __device__ __forceinline__ unsigned round2(float a, float b) { return round_f16x2(a, b); }
     static __device__ __forceinline__ float lo(unsigned u) { return f16_lo(u); }
@@ -187,6 +159,41 @@ struct ElemF16 {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
     }
 };
+
+namespace {
+// 32 couts of one pixel: lanes (r,0) hold couts 8g..8g+3, lanes (r,1) couts 8g+4..8g+7 in acc[4g..4g+3].
+// Returns for m = 0,1 the 16 bytes (E elements, ReLU applied) of couts 16m+8h .. 16m+8h+7 of this lane's pixel.
+template <typename E>
+__device__ __forceinline__ void pack_rows16(const f32x16 &acc, u32x4 out[2])
+{
+    const i16x2 relu = {0, 0};
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        unsigned x0 = E::pack(acc[8 * m + 0], acc[8 * m + 1], relu), x1 = E::pack(acc[8 * m + 2], acc[8 * m + 3], relu);
+        unsigned y0 = E::pack(acc[8 * m + 4], acc[8 * m + 5], relu), y1 = E::pack(acc[8 * m + 6], acc[8 * m + 7], relu);
+        // lanes 0-31: X = couts 16m..+3, Y = 16m+8..+11; lanes 32-63: X = 16m+4..+7, Y = 16m+12..+15.
+        // swap X[32..63] <-> Y[0..31]: lanes 0-31 end with (X,Y) = couts 16m..16m+7, lanes 32-63 with 16m+8..16m+15
+        auto s0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
+        auto s1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
+        out[m] = u32x4{s0[0], s1[0], s0[1], s1[1]};
+    }
+}
+
+// Identity A fragments (rows = couts, k = cin) of lane (r, h): fragment kk has A[r][k] = 1 where 16*kk + k == r.  A residual added
+// as two more MFMAs against them is exact (x * 1.0 in fp32).
+template <typename E>
+__device__ __forceinline__ void ident_frags(int r, int h, u32x4 ident[2])
+{
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+        const int j = r - 16 * kk - 8 * h;  // element index inside this lane's 8-wide k slice
+        const unsigned one = (j & 1) ? E::ONE << 16 : E::ONE;  // E's 1.0 in the high / low half of a dword
+        const bool on = j >= 0 && j < 8;
+        ident[kk] = u32x4{on && (j >> 1) == 0 ? one : 0u, on && (j >> 1) == 1 ? one : 0u, on && (j >> 1) == 2 ? one : 0u,
+                          on && (j >> 1) == 3 ? one : 0u};
+    }
+}
+}  // namespace
 
 // ---- host side of the tile-form BasicBlock kernels: one persistent workgroup per CU walks TH x TW output tiles
 typedef void (*BBTileKernel)(const BBParams);

@@ -31,6 +31,8 @@ constexpr int OFF_PATCH = MID_BYTES, OFF_BIAS = OFF_PATCH + PATCH_BYTES, LDS_BYT
 constexpr int RD = 3, NFB = RD + 1;
 }  // namespace
 
+// E: the element type (ElemBF16 / ElemF16 of mfma_dev.h)
+template <typename E>
 __global__ __launch_bounds__(256, 1) void stem_fused_kernel(const StemFusedParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -102,7 +104,7 @@ __global__ __launch_bounds__(256, 1) void stem_fused_kernel(const StemFusedParam
 #pragma unroll
         for (int it = 0; it < NLD; ++it) {
             const int i = tid + 256 * it;
-            if (it + 1 < NLD || i < NVAL) patch[i] = __builtin_bit_cast(unsigned short, (__bf16)pv[it]);
+            if (it + 1 < NLD || i < NVAL) patch[i] = E::cvt(pv[it]);
         }
     };
     // conv1 gather: tap t = kk*16 + 8h + j -> (c, ky, kx) = (t / 9, (t % 9) / 3, t % 3); taps >= 27 read the zero slot
@@ -158,9 +160,9 @@ __global__ __launch_bounds__(256, 1) void stem_fused_kernel(const StemFusedParam
                 f32x16 acc = bias1[ct];
 #pragma unroll
                 for (int kk = 0; kk < 2; ++kk)
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a1[ct][kk]), __builtin_bit_cast(bf16x8, bf[qi][kk]), acc, 0, 0, 0);
+                    acc = E::mfma(a1[ct][kk], bf[qi][kk], acc);
                 u32x4 o[2];
-                pack_rows16(acc, o);
+                pack_rows16<E>(acc, o);
                 if (m < MPIX) {
                     *reinterpret_cast<u32x4 *>(dst + ct * 64) = inside ? o[0] : u32x4{0u, 0u, 0u, 0u};
                     *reinterpret_cast<u32x4 *>(dst + ct * 64 + 32) = inside ? o[1] : u32x4{0u, 0u, 0u, 0u};
@@ -185,10 +187,10 @@ __global__ __launch_bounds__(256, 1) void stem_fused_kernel(const StemFusedParam
                 constexpr int s = decltype(sc)::value;
                 if constexpr (s + RD < 36) ldb(std::integral_constant<int, s + RD>{}, (s + RD) % NFB);
                 lds_wait<(35 - s < RD ? 35 - s : RD)>(fb[s % NFB]);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w2r[s]), __builtin_bit_cast(bf16x8, fb[s % NFB]), acc, 0, 0, 0);
+                acc = E::mfma(w2r[s], fb[s % NFB], acc);
             });
             u32x4 o[2];
-            pack_rows16(acc, o);
+            pack_rows16<E>(acc, o);
             const int oy = g.oy0 + row2, ox = g.ox0 + r;
             const bool ok = (oy < H2) & (ox < W2);
             const auto rs_out = __builtin_amdgcn_make_buffer_rsrc(p.out + (size_t)g.b * out_elems, 0, (int)(out_elems * 2), 0x00020000);
@@ -203,7 +205,9 @@ __global__ __launch_bounds__(256, 1) void stem_fused_kernel(const StemFusedParam
 
 hipError_t stem_fused_init()
 {
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(stem_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(stem_fused_kernel<ElemBF16>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(stem_fused_kernel<ElemF16>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
 }
 
 bool stem_fused_supported(const StemFusedParams &p)
@@ -211,11 +215,13 @@ bool stem_fused_supported(const StemFusedParams &p)
     return p.H % 4 == 0 && p.W % 4 == 0 && (size_t)3 * p.H * p.W * 4 < 0x7fffffffull && (size_t)(p.H / 4) * (p.W / 4) * p.out_cs * 2 < 0x7fffffffull;
 }
 
-hipError_t stem_fused_launch(const StemFusedParams &p, int num_cus, hipStream_t s)
+hipError_t stem_fused_launch(const StemFusedParams &p, int num_cus, hipStream_t s, int act_dtype)
 {
+    if (act_dtype != 0 && act_dtype != 1) return hipErrorInvalidValue;
     const int H2 = p.H >> 2, W2 = p.W >> 2;
     const int ntiles = p.B * ((H2 + T2H - 1) / T2H) * ((W2 + T2W - 1) / T2W);
     const int grid = ntiles < num_cus ? ntiles : num_cus;
-    HH_LAUNCH(stem_fused_kernel, dim3(grid), dim3(256), LDS_BYTES, s, p);
+    if (act_dtype) HH_LAUNCH(stem_fused_kernel<ElemF16>, dim3(grid), dim3(256), LDS_BYTES, s, p);
+    else HH_LAUNCH(stem_fused_kernel<ElemBF16>, dim3(grid), dim3(256), LDS_BYTES, s, p);
     return hipGetLastError();
 }

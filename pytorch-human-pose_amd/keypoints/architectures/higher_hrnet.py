@@ -4,7 +4,7 @@ Stands in for `/root/reference/src/keypoints/architectures/higher_hrnet.py:47-81
 (`HigherHRNet(num_kpts, C).forward(images) -> ([hm_1/4, hm_1/2], tags_1/4)`); it registers
 in `KeypointsConfig.architectures` (keypoints/config.py:93-95) under the same name, owns
 parameters under the reference's 1810 state-dict keys, and loads `higher_hrnet_32.pt`
-unchanged.  Inference runs entirely in csrc/libhhrnet.so (bf16 MFMA kernels, BN folded);
+unchanged.  Inference runs entirely in csrc/libhhrnet.so (bf16 or fp16 MFMA kernels, BN folded);
 there is no ATen / CPU fallback.
 """
 from __future__ import annotations
@@ -38,16 +38,34 @@ class EngineModule(nn.Module):
     """nn.Module whose parameters live under the reference's state-dict keys and whose forward runs in the HIP engine."""
 
     TRAIN_PRECISIONS = ("bf16", "fp16")
+    DTYPES = {"bf16": 1, "fp16": 3}  # engine dtypes (HH_DTYPE_* of hhrnet.h) the subclass accepts
 
-    def _init_engine(self, rows, create) -> None:
+    def _init_engine(self, rows, create, dtype: str = "bf16") -> None:
+        """`create(lib, code)` -> hh_net* for the HH_DTYPE_* code of `dtype`; kept, so that set_engine_dtype can make the handle again."""
         self.train_precision = "bf16"
         attach_modules(self, rows)
         self._lib = _lib.load()
-        self._handle = _NetHandle(self._lib, create(self._lib))
-        self._h = self._handle.ptr
-        self._dirty = True
+        self._create = create
+        self._new_handle(dtype)
         self.use_graph = True
         self.register_load_state_dict_post_hook(lambda m, _k: m.mark_dirty())
+
+    def _new_handle(self, dtype: str) -> None:
+        if dtype not in self.DTYPES:
+            raise ValueError(f"{type(self).__name__}: engine dtype {dtype!r} is not one of {tuple(self.DTYPES)}")
+        handle = _NetHandle(self._lib, self._create(self._lib, self.DTYPES[dtype]))  # (raises before the old handle is let go)
+        self._handle = handle
+        self._h = handle.ptr
+        self.engine_dtype = dtype
+        self._dirty = True
+
+    def set_engine_dtype(self, dtype: str) -> None:
+        """The element type of the INFERENCE engine (eval-mode forward): destroys the handle and creates one of `dtype`, and marks the
+        weights dirty, so the next forward folds and packs them again -- the net then gives the bits of a fresh net of that dtype with
+        the same state dict.  Workspace, cached graphs, taps and (fp8) calibration of the old handle are gone.  Parameters and the
+        training precision (set_train_precision) are not affected."""
+        if dtype != self.engine_dtype:
+            self._new_handle(dtype)
 
     def set_train_precision(self, precision: str) -> None:
         """The activation type of the training forward / backward (.train() mode, keypoints/train_net.py): "bf16" (default) or "fp16",
@@ -75,7 +93,7 @@ class EngineModule(nn.Module):
         return [self._lib.hh_param_name(self._h, i).decode() for i in range(n)]
 
     def sync_weights(self) -> None:
-        """state_dict -> hh_load_weights (fp32 host copies) -> hh_finalize (BN fold + bf16 pack)."""
+        """state_dict -> hh_load_weights (fp32 host copies) -> hh_finalize (BN fold + pack in the engine dtype)."""
         for name, t in self.state_dict().items():
             if name.endswith("num_batches_tracked"):
                 continue
@@ -122,19 +140,22 @@ class EngineModule(nn.Module):
 
 
 class HigherHRNet(EngineModule):
-    """`dtype="bf16"` (default) or `"fp8"` (BASELINE.json configs[4]: OCP e4m3 MFMA operands and activations; an extension, the
-    reference has one precision).  An fp8 net needs `calibrate(images)` once after its weights are loaded."""
+    """`dtype="bf16"` (default), `"fp16"` or `"fp8"`.
+    "fp16": fp16 MFMA operands and activations, the precision every GPU forward of the reference runs in (torch.autocast(float16)):
+    about eight times closer to the fp32 maps than bf16 (three more mantissa bits), at the price of fp16's range -- an activation beyond
+    +-65504 becomes inf and shows as non-finite outputs, a BN-folded weight beyond it makes the weight sync fail with the parameter's
+    name (check a checkpoint with set_taps / read_taps maxima).
+    "fp8" (BASELINE.json configs[4]: OCP e4m3 MFMA operands and activations; an extension, the reference has no such precision) needs
+    `calibrate(images)` once after its weights are loaded."""
 
-    DTYPES = {"bf16": 1, "fp8": 2}
+    DTYPES = {"bf16": 1, "fp8": 2, "fp16": 3}
 
     def __init__(self, num_kpts: int, C: int = 32, dtype: str = "bf16"):
         super().__init__()
         self.num_kpts = num_kpts
         self.C = C
         self.num_deconv_layers = 1
-        self.engine_dtype = dtype
-        code = self.DTYPES[dtype]
-        self._init_engine(higher_hrnet_rows(num_kpts, C), lambda lib: lib.hh_create(num_kpts, C, code))
+        self._init_engine(higher_hrnet_rows(num_kpts, C), lambda lib, code: lib.hh_create(num_kpts, C, code), dtype)
 
     def calibrate(self, images: Tensor, rounds: int = 2) -> None:
         """fp8 only: per-tensor activation scales from forwards over `images` [B,3,H,W] (hh_calibrate).  Weight changes

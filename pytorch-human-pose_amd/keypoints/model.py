@@ -114,11 +114,14 @@ class KeypointsModule:
     runs under fp16 autocast with one GradScaler per optimizer, whose state goes into every checkpoint (base/module.py:71,109-127).
     precision="fp16" is that: fp16 activations (HigherHRNet.set_train_precision), `scalers = {"optim": GradScaler}`, and the
     reference's sequence scale(loss).backward() / scaler.step(optimizer) / scaler.update(); the metrics are the unscaled values.
-    precision="bf16" (default) keeps activations in bf16, which needs no scaler: `scalers` is {}.  Parameters are fp32 either way."""
+    precision="bf16" (default) keeps activations in bf16, which needs no scaler: `scalers` is {}.  Parameters are fp32 either way.
+    eval_dtype: the element type of the inference engine that `validation_step` runs ("bf16" / "fp16" / ..., the net's DTYPES).  None
+    (default) leaves the net's engine as it is; a name calls `net.set_engine_dtype` once, here -- eval_dtype="fp16" makes the
+    validation of an fp16 training run infer in the precision it trains in (and the reference validates in)."""
 
     PRECISIONS = ("bf16", "fp16")
 
-    def __init__(self, model: KeypointsModel, loss_fn, optimizer: torch.optim.Optimizer, precision: str = "bf16"):
+    def __init__(self, model: KeypointsModel, loss_fn, optimizer: torch.optim.Optimizer, precision: str = "bf16", eval_dtype: str | None = None):
         if precision not in self.PRECISIONS:
             raise ValueError(f"KeypointsModule: precision {precision!r} is not one of {self.PRECISIONS}")
         self.model, self.loss_fn, self.optimizer, self.precision = model, loss_fn, optimizer, precision
@@ -127,6 +130,9 @@ class KeypointsModule:
         scaler_cls = GradScaler if is_device_optimizer(optimizer) else torch.amp.GradScaler
         self.scalers: dict = {"optim": scaler_cls("cuda")} if precision == "fp16" else {}
         model._bare().set_train_precision(precision)
+        self.eval_dtype = eval_dtype
+        if eval_dtype is not None:
+            model._bare().set_engine_dtype(eval_dtype)
 
     def state_dict(self) -> dict:
         """The module's own checkpoint entries in the reference's format (base/module.py:109-127): {"scalers": {name: state}}."""
