@@ -852,6 +852,37 @@ int hh_optim_step(int algo, const hh_optim_tensor *tensors_host, int ntensors, c
 int hh_grads_nonfinite(const hh_optim_tensor *tensors_host, int ntensors, int ngroups, const float *inv_scale, float *found_inf,
                        void *table_dev, int64_t table_bytes, int upload, void *stream);
 
+/* Gradient statistics and clipping by global norm on that table (csrc/grad_stats.hip; optim.clip_grad_norm_ and
+ * optimizer.grad_stats() of pytorch-human-pose_amd/optim.py): torch.nn.utils.clip_grad_norm_ and the per-layer mean / max |grad|
+ * that the reference's trainer lists as its open TODO (src/base/trainer.py:23-26), from ONE read of the gradients.
+ * (Additive entry points: HH_ABI_VERSION stays 3.  hh_optim_table_bytes and the two structs are unchanged.)
+ *
+ * hh_grad_stats_bytes: the size of `work_dev` for these tensors; -1 on a bad argument.  work_dev (16-byte aligned) begins with
+ *   float totals[4] = {total_l2, total_inf, coef, unused} and float rows[ntensors][4] = {l2, absmax, absmean, nonfinite_count} per
+ *   tensor in table order; behind them the per-tensor fp64 sums of squares, one 24-byte record per 4096-element chunk (double sum of
+ *   g^2, double sum of |g|, float max |g|, int non-finite count) and the index of every tensor's first chunk, all written on the device.
+ * hh_grad_stats: one launch over all chunks, one per tensor, one that forms the totals.  With found_inf != NULL the first is also
+ *   hh_grads_nonfinite, with the same stored bits: *found_inf = 1.0f on an inf / NaN (the caller zeroes it first), g *= *inv_scale in
+ *   place unless inv_scale is NULL or holds 1.  The statistics are those of the value that is stored (the unscaled gradient).
+ *   Squares and sums are formed in fp64 and added in one fixed order (no floating-point atomics): the same bits on every run.
+ *   total_l2 = (float)sqrt(sum over all elements of g^2), rounded once; total_inf = max of the absmax column.
+ *   NaN / inf, as g.norm(), g.abs().max() and g.abs().mean(): a NaN anywhere in a tensor makes its l2, absmax and absmean NaN, an inf
+ *   (without a NaN) makes them inf, and the totals follow; a tensor with numel == 0 has the row {0, 0, 0, 0}.
+ * hh_grad_clip: after hh_grad_stats on the same table_dev and work_dev.  One launch: coef = max_norm / (total + 1e-6f) in fp32, at
+ *   most 1 (torch's arithmetic; total = total_l2 or total_inf by norm_type), stored to totals[2]; g = g * coef in place.  Nothing is
+ *   stored to a gradient when coef >= 1 (multiplying by 1.0f is the identity), nor when found_inf != NULL and *found_inf != 0: that
+ *   step is skipped by hh_optim_step anyway and the gradients stay as the unscale pass left them.  DIFFERENCE: torch would multiply
+ *   them by 0 or NaN there.  Without found_inf a non-finite total gives torch's coefficient (0 or NaN) and torch's gradients.
+ * Non-zero (nothing launched or copied) for what hh_grads_nonfinite refuses, a null or misaligned work_dev, a work_dev smaller than
+ * hh_grad_stats_bytes, inv_scale without found_inf, a max_norm that is negative or NaN, an unknown norm type.                       */
+#define HH_GRAD_NORM_L2 0
+#define HH_GRAD_NORM_INF 1
+int64_t hh_grad_stats_bytes(const hh_optim_tensor *tensors_host, int ntensors, int ngroups);
+int hh_grad_stats(const hh_optim_tensor *tensors_host, int ntensors, int ngroups, const float *inv_scale, float *found_inf,
+                  void *table_dev, int64_t table_bytes, int upload, void *work_dev, int64_t work_bytes, void *stream);
+int hh_grad_clip(const hh_optim_tensor *tensors_host, int ntensors, int ngroups, float max_norm, int norm_type, const float *found_inf,
+                 void *table_dev, int64_t table_bytes, void *work_dev, int64_t work_bytes, void *stream);
+
 /* Multi-scale test-time augmentation (BASELINE.json configs[3]; an extension: the reference only calls its resize helper
  * with scale 1, keypoints/model.py:73): dst[B,K,H,W] (+)= weight * bilinear(src[B,K,h,w] -> HxW) with the arithmetic of
  * F.interpolate(mode="bilinear", align_corners=False); init != 0 overwrites dst.  Batch strides in elements.            */

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 from torch import Tensor
 
+from ..optim import clip_grad_norm_
 from .loss import ClassificationLoss
 from .model import ClassificationModel
 
@@ -28,11 +29,15 @@ class ClassificationResult:
 
 class ClassificationModule:
     """eval_dtype: the element type of the inference engine that `validation_step` runs ("bf16" / "fp16").  None (default) leaves the
-    net's engine as it is; a name calls `net.set_engine_dtype` once, here."""
+    net's engine as it is; a name calls `net.set_engine_dtype` once, here.
+    max_grad_norm (not in the reference; None = off, the step is exactly the reference's sequence): the gradients are clipped to this
+    global norm (grad_norm_type: 2 or inf) between the backward and the step by optim.clip_grad_norm_ -- on the optimizer's device
+    table for an optimizer of ..optim, with torch's function for any other -- and metrics["grad_norm"] is the norm before clipping."""
 
     def __init__(self, model: ClassificationModel, loss_fn: ClassificationLoss, optimizer: torch.optim.Optimizer,
-                 idx2label: dict | None = None, eval_dtype: str | None = None):
+                 idx2label: dict | None = None, eval_dtype: str | None = None, max_grad_norm: float | None = None, grad_norm_type: float = 2.0):
         self.model, self.loss_fn, self.optimizer, self.idx2label = model, loss_fn, optimizer, idx2label
+        self.max_grad_norm, self.grad_norm_type = max_grad_norm, grad_norm_type
         self.eval_dtype = eval_dtype
         if eval_dtype is not None:
             model._bare().set_engine_dtype(eval_dtype)
@@ -53,6 +58,8 @@ class ClassificationModule:
         self.optimizer.zero_grad()
         loss.backward()
         metrics = self.loss_fn.metrics()
+        if self.max_grad_norm is not None:
+            metrics["grad_norm"] = clip_grad_norm_(self.optimizer, self.max_grad_norm, self.grad_norm_type).item()
         self.optimizer.step()
         self.model._bare().mark_dirty()
         return metrics

@@ -8,6 +8,7 @@
 #include "../../include/hhrnet.h"
 #include "engine.h"
 #include "optim_math.h"
+#include "grad_stats_math.h"
 #include "render_math.h"
 #include "panel_math.h"
 #include "coco_eval_math.h"
@@ -1152,6 +1153,57 @@ int hh_grads_nonfinite(const hh_optim_tensor *tensors_host, int ntensors, int ng
     if (optim_upload(tensors_host, ntensors, nullptr, ngroups, nchunks, upload, (char *)table_dev, (hipStream_t)stream)) return 1;
     const OptimTensor *td = (const OptimTensor *)table_dev;
     HH_CHECK_HIP(launch_grads_nonfinite(td, (const OptimChunk *)(td + ntensors), (int)nchunks, inv_scale, found_inf, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- gradient statistics and clipping by global norm (grad_stats.hip) on the same table; the workspace's layout is grad_work's.
+static_assert(sizeof(GradPartial) == 24 && sizeof(GradTotals) == 16 && sizeof(GradRow) == 16, "grad_stats workspace layout");
+
+// the checks hh_grad_stats and hh_grad_clip share, in hh_grads_nonfinite's order; -> the chunk count, or -1 with the error set
+static int64_t grad_check(const char *who, const hh_optim_tensor *t, int ntensors, int ngroups, const void *table_dev, int64_t table_bytes,
+                          const void *work_dev, int64_t work_bytes)
+{
+    const std::string w(who);
+    if (!table_dev || !work_dev) { hh_set_error(w + ": null device table or workspace"); return -1; }
+    if ((uintptr_t)table_dev % 16 || (uintptr_t)work_dev % 16) { hh_set_error(w + ": table_dev and work_dev must be 16-byte aligned"); return -1; }
+    const int64_t nchunks = optim_count_chunks(t, ntensors, ngroups, who);
+    if (nchunks < 0) return -1;
+    if (table_bytes < optim_bytes(ntensors, ngroups, nchunks)) { hh_set_error(w + ": table buffer too small (hh_optim_table_bytes)"); return -1; }
+    if (work_bytes < grad_work_bytes(ntensors, nchunks)) { hh_set_error(w + ": workspace too small (hh_grad_stats_bytes)"); return -1; }
+    for (int i = 0; i < ntensors; ++i)
+        if (!t[i].grad) { hh_set_error(w + ": null gradient pointer in the tensor table"); return -1; }
+    return nchunks;
+}
+
+int64_t hh_grad_stats_bytes(const hh_optim_tensor *tensors_host, int ntensors, int ngroups)
+{
+    const int64_t nchunks = optim_count_chunks(tensors_host, ntensors, ngroups, "hh_grad_stats_bytes");
+    return nchunks < 0 ? -1 : (int64_t)grad_work_bytes(ntensors, nchunks);
+}
+
+int hh_grad_stats(const hh_optim_tensor *tensors_host, int ntensors, int ngroups, const float *inv_scale, float *found_inf, void *table_dev,
+                  int64_t table_bytes, int upload, void *work_dev, int64_t work_bytes, void *stream)
+{
+    if (inv_scale && !found_inf) { hh_set_error("hh_grad_stats: inv_scale needs found_inf (the unscale pass is the non-finite check)"); return 1; }
+    if (upload != 0 && upload != HH_OPTIM_UPLOAD_TENSORS) { hh_set_error("hh_grad_stats: upload is 0 or HH_OPTIM_UPLOAD_TENSORS"); return 1; }
+    const int64_t nchunks = grad_check("hh_grad_stats", tensors_host, ntensors, ngroups, table_dev, table_bytes, work_dev, work_bytes);
+    if (nchunks < 0) return 1;
+    if (nchunks && optim_upload(tensors_host, ntensors, nullptr, ngroups, nchunks, upload, (char *)table_dev, (hipStream_t)stream)) return 1;
+    const OptimTensor *td = (const OptimTensor *)table_dev;
+    HH_CHECK_HIP(launch_grad_stats(td, ntensors, (const OptimChunk *)(td + ntensors), (int)nchunks, inv_scale, found_inf, work_dev, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_grad_clip(const hh_optim_tensor *tensors_host, int ntensors, int ngroups, float max_norm, int norm_type, const float *found_inf,
+                 void *table_dev, int64_t table_bytes, void *work_dev, int64_t work_bytes, void *stream)
+{
+    if (!(max_norm >= 0.0f)) { hh_set_error("hh_grad_clip: max_norm must be a number >= 0"); return 1; }
+    if (norm_type != HH_GRAD_NORM_L2 && norm_type != HH_GRAD_NORM_INF) { hh_set_error("hh_grad_clip: unknown norm type (HH_GRAD_NORM_L2 = 0, HH_GRAD_NORM_INF = 1)"); return 1; }
+    const int64_t nchunks = grad_check("hh_grad_clip", tensors_host, ntensors, ngroups, table_dev, table_bytes, work_dev, work_bytes);
+    if (nchunks < 0) return 1;
+    const OptimTensor *td = (const OptimTensor *)table_dev;
+    HH_CHECK_HIP(launch_grad_clip(td, ntensors, (const OptimChunk *)(td + ntensors), (int)nchunks, max_norm, norm_type, found_inf, work_dev,
+                                  (hipStream_t)stream));
     return 0;
 }
 

@@ -450,3 +450,9 @@ hipError_t launch_optim_step(int algo, const OptimTensor *tensors, int ntensors,
                              const float *grad_scale, const float *found_inf, int advance_steps, hipStream_t s);
 hipError_t launch_grads_nonfinite(const OptimTensor *tensors, const OptimChunk *chunks, int nchunks, const float *inv_scale, float *found_inf,
                                   hipStream_t s);
+// Gradient statistics and clipping by global norm over the same table (grad_stats.hip; arithmetic and the workspace's layout in
+// grad_stats_math.h).  `work` is the device workspace of grad_work_bytes(ntensors, nchunks).
+hipError_t launch_grad_stats(const OptimTensor *tensors, int ntensors, const OptimChunk *chunks, int nchunks, const float *inv_scale,
+                             float *found_inf, void *work, hipStream_t s);
+hipError_t launch_grad_clip(const OptimTensor *tensors, int ntensors, const OptimChunk *chunks, int nchunks, float max_norm, int norm_type,
+                            const float *found_inf, void *work, hipStream_t s);

@@ -11,6 +11,7 @@ import torch
 from torch import Tensor, nn
 
 from .. import _lib
+from ..optim import clip_grad_norm_
 from .grouping import MPPEHeatmapParser
 from .results import InferenceKeypointsResult, transform_coords
 import ctypes as C
@@ -117,18 +118,26 @@ class KeypointsModule:
     precision="bf16" (default) keeps activations in bf16, which needs no scaler: `scalers` is {}.  Parameters are fp32 either way.
     eval_dtype: the element type of the inference engine that `validation_step` runs ("bf16" / "fp16" / ..., the net's DTYPES).  None
     (default) leaves the net's engine as it is; a name calls `net.set_engine_dtype` once, here -- eval_dtype="fp16" makes the
-    validation of an fp16 training run infer in the precision it trains in (and the reference validates in)."""
+    validation of an fp16 training run infer in the precision it trains in (and the reference validates in).
+    max_grad_norm (not in the reference; None = off, the step is exactly the sequence above): the gradients are clipped to this global
+    norm (grad_norm_type: 2 or inf) between the backward and the step -- bf16: backward, clip, step; fp16: scale(loss).backward(),
+    scaler.unscale_, clip, scaler.step, scaler.update -- and metrics["grad_norm"] is the norm before clipping.  optim.clip_grad_norm_
+    does it: on the optimizer's device table for an optimizer of ..optim, with torch's function for any other."""
 
     PRECISIONS = ("bf16", "fp16")
 
-    def __init__(self, model: KeypointsModel, loss_fn, optimizer: torch.optim.Optimizer, precision: str = "bf16", eval_dtype: str | None = None):
+    def __init__(self, model: KeypointsModel, loss_fn, optimizer: torch.optim.Optimizer, precision: str = "bf16", eval_dtype: str | None = None,
+                 max_grad_norm: float | None = None, grad_norm_type: float = 2.0):
         if precision not in self.PRECISIONS:
             raise ValueError(f"KeypointsModule: precision {precision!r} is not one of {self.PRECISIONS}")
         self.model, self.loss_fn, self.optimizer, self.precision = model, loss_fn, optimizer, precision
+        self.max_grad_norm, self.grad_norm_type = max_grad_norm, grad_norm_type
         # (an optimizer of ..optim gets the scaler whose non-finite check is one launch over its table; any other, torch's own)
         from ..optim import GradScaler, is_device_optimizer
         scaler_cls = GradScaler if is_device_optimizer(optimizer) else torch.amp.GradScaler
         self.scalers: dict = {"optim": scaler_cls("cuda")} if precision == "fp16" else {}
+        if max_grad_norm is not None and is_device_optimizer(optimizer):
+            optimizer.collect_grad_stats = True  # the scaler's unscale launch leaves the statistics the clip needs
         model._bare().set_train_precision(precision)
         self.eval_dtype = eval_dtype
         if eval_dtype is not None:
@@ -157,15 +166,23 @@ class KeypointsModule:
         loss = loss + push_losses[0] + pull_losses[0]
         self.optimizer.zero_grad()
         scaler = self.scalers.get("optim")
+        grad_norm = None
         if scaler is None:
             loss.backward()
+            if self.max_grad_norm is not None:
+                grad_norm = clip_grad_norm_(self.optimizer, self.max_grad_norm, self.grad_norm_type)
             self.optimizer.step()
         else:  # (module.py:55-60; a step whose gradients hold an inf / NaN is skipped and the scale halved)
             scaler.scale(loss).backward()
+            if self.max_grad_norm is not None:
+                scaler.unscale_(self.optimizer)
+                grad_norm = clip_grad_norm_(self.optimizer, self.max_grad_norm, self.grad_norm_type)
             scaler.step(self.optimizer)
             scaler.update()
         self.model._bare().mark_dirty()
         metrics = {"loss": loss.detach().item()}
+        if grad_norm is not None:
+            metrics["grad_norm"] = grad_norm.item()
         for i, hl in enumerate(hm_losses):
             metrics[f"hm_{i}_loss"] = hl.item()
         for i in range(len(push_losses)):

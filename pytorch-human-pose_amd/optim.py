@@ -9,6 +9,10 @@ amsgrad, maximize, differentiable, dampening != 0, sparse gradients, parameters 
 `_step_supports_amp_scaling = True`: a torch.amp.GradScaler hands `grad_scale` / `found_inf` to step() and never reads them on the
 host; a step with non-finite gradients is skipped on the device.  `GradScaler` below replaces the scaler's foreach non-finite check
 by one launch over the same table.  There is no fall-back to torch kernels.
+
+Between the backward and the step (csrc/grad_stats.hip): `clip_grad_norm_(optimizer, max_norm)` is torch.nn.utils.clip_grad_norm_ over
+the same table, and `optimizer.grad_stats()` gives per-parameter l2 / max / mean |grad| and the count of non-finite elements -- one
+read of the gradients for both, and none at all after `GradScaler.unscale_`, whose launch leaves the statistics behind.
 """
 from __future__ import annotations
 
@@ -130,7 +134,8 @@ class _DeviceOptimizer(torch.optim.Optimizer):
             raise _lib.HHError(lib.hh_last_error().decode())
         self._rows = dict(mask=mask, active=active, rows=rows, dev=dev, nbytes=nbytes,
                           table=torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev),
-                          groups=np.zeros(ngroups, dtype=_GROUP), sent_tensors=None, sent_groups=None, sent_stream=None, keep=keep)
+                          groups=np.zeros(ngroups, dtype=_GROUP), sent_tensors=None, sent_groups=None, sent_stream=None, keep=keep,
+                          params=[params[i] for i in active])
         return self._rows
 
     def _table(self):
@@ -197,19 +202,96 @@ class _DeviceOptimizer(torch.optim.Optimizer):
             _lib.launch(dev, _lib.load().hh_optim_step, self.ALGO, rows.ctypes.data, len(rows), groups.ctypes.data, len(groups), scale, found,
                         T["table"].data_ptr(), T["nbytes"], upload)
             self._sent(T, upload)
+            T["stats_fresh"] = False  # (gradient statistics of before this step are not reused after it)
         return loss
 
     @torch.no_grad()
     def check_grads_nonfinite(self, found_inf: torch.Tensor, inv_scale: torch.Tensor | None = None) -> None:
         """One launch over every gradient: found_inf (fp32 device scalar, zeroed by the caller) becomes 1 if any element is inf or
-        NaN, and the gradients are multiplied by inv_scale in place unless it is None or holds 1 (GradScaler.unscale_)."""
+        NaN, and the gradients are multiplied by inv_scale in place unless it is None or holds 1 (GradScaler.unscale_).  With
+        `collect_grad_stats` set (clip_grad_norm_ and grad_stats() set it, and so does a module built with max_grad_norm) the same
+        read of the gradients also leaves their statistics -- of the unscaled values -- for those two to reuse; the stored bits and
+        the flag are the same either way."""
         T, upload = self._table()
         if T is not None:
             dev, rows = T["dev"], T["rows"]
             upload &= UPLOAD_TENSORS
-            _lib.launch(dev, _lib.load().hh_grads_nonfinite, rows.ctypes.data, len(rows), len(T["groups"]), self._scalar_ptr(inv_scale, "inv_scale", dev),
-                        self._scalar_ptr(found_inf, "found_inf", dev), T["table"].data_ptr(), T["nbytes"], upload)
+            scale, found = self._scalar_ptr(inv_scale, "inv_scale", dev), self._scalar_ptr(found_inf, "found_inf", dev)
+            if self.collect_grad_stats:
+                work = self._work(T)
+                _lib.launch(dev, _lib.load().hh_grad_stats, rows.ctypes.data, len(rows), len(T["groups"]), scale, found, T["table"].data_ptr(),
+                            T["nbytes"], upload, work.data_ptr(), T["work_bytes"])
+                T["stats_fresh"], T["stats_found_inf"] = True, found_inf  # (kept alive: the clip launch reads it)
+            else:
+                _lib.launch(dev, _lib.load().hh_grads_nonfinite, rows.ctypes.data, len(rows), len(T["groups"]), scale, found, T["table"].data_ptr(),
+                            T["nbytes"], upload)
             self._sent(T, upload)
+
+    # ---- gradient statistics and clipping by global norm (csrc/grad_stats.hip)
+    collect_grad_stats = False
+
+    def zero_grad(self, set_to_none: bool = True) -> None:
+        super().zero_grad(set_to_none)
+        if self._rows is not None:
+            self._rows["stats_fresh"] = False
+
+    @staticmethod
+    def _work(T):
+        """the statistics workspace of this table (hh_grad_stats_bytes), allocated on first use"""
+        if T.get("work") is None:
+            lib = _lib.load()
+            nbytes = lib.hh_grad_stats_bytes(T["rows"].ctypes.data, len(T["rows"]), len(T["groups"]))
+            if nbytes < 0:
+                raise _lib.HHError(lib.hh_last_error().decode())
+            T["work_bytes"], T["work"] = nbytes, torch.empty(max(nbytes, 16), dtype=torch.uint8, device=T["dev"])
+        return T["work"]
+
+    def _grad_stats_pass(self, recompute: bool):
+        """-> the table record with current statistics in its workspace (None when no parameter has a gradient).
+
+        FRESH statistics are reused instead of reading the gradients again (and the table is not even gathered again).  They are fresh
+        when they come from this optimizer's latest check_grads_nonfinite (GradScaler.unscale_) and there was no step(), zero_grad() or
+        clip_grad_norm_ on it since.  They describe the gradients as that check stored them: unscaled, not yet clipped.  Code that
+        writes to the gradients, or replaces them, between unscale_ and the clip passes recompute=True.  Anything else -- a call
+        without a preceding check, or recompute=True -- runs a statistics launch of its own over the gradients as they are now."""
+        self.collect_grad_stats = True
+        T = self._rows
+        if not recompute and T is not None and T.get("stats_fresh"):
+            return T
+        T, upload = self._table()
+        if T is None:
+            return None
+        upload &= UPLOAD_TENSORS
+        work, rows = self._work(T), T["rows"]
+        _lib.launch(T["dev"], _lib.load().hh_grad_stats, rows.ctypes.data, len(rows), len(T["groups"]), None, None, T["table"].data_ptr(),
+                    T["nbytes"], upload, work.data_ptr(), T["work_bytes"])
+        T["stats_fresh"], T["stats_found_inf"] = False, None
+        self._sent(T, upload)
+        return T
+
+    @staticmethod
+    def _totals(T):
+        return T["work"][:16].view(torch.float32)  # total_l2, total_inf, coef of the last clip, unused
+
+    @torch.no_grad()
+    def grad_stats(self, recompute: bool = False):
+        """-> (params, stats): the parameters that have a gradient, in table order, and an [n, 4] fp32 device tensor with one row
+        [l2 norm, max |g|, mean |g|, number of inf / NaN elements] per parameter (STAT_L2 .. STAT_NONFINITE).  Nothing is read on the
+        host.  A NaN in a gradient makes its three figures NaN, an inf makes them inf.  Reuses fresh statistics (`_grad_stats_pass`
+        says what fresh means; recompute=True forces a new pass over the gradients as they are now)."""
+        T = self._grad_stats_pass(recompute)
+        if T is None:
+            dev = next((p.device for g in self.param_groups for p in g["params"]), None)
+            return [], torch.zeros(0, 4, dtype=torch.float32, device=dev)
+        n = len(T["rows"])
+        return list(T["params"]), T["work"][16:16 + 16 * n].view(torch.float32).view(n, 4).clone()
+
+    @torch.no_grad()
+    def clip_coef(self) -> torch.Tensor:
+        """the coefficient the last clip_grad_norm_ over this optimizer multiplied by (1 where it did not engage): 0-dim, on the device"""
+        if self._rows is None or self._rows.get("work") is None:
+            raise ValueError(f"{type(self).__name__}: no clip_grad_norm_ has run on the current table")
+        return self._totals(self._rows)[2].clone()
 
 
 def _refuse(name, **flags):
@@ -309,7 +391,12 @@ class SGD(_DeviceOptimizer):
 
 class GradScaler(torch.amp.GradScaler):
     """torch.amp.GradScaler whose non-finite check (and unscale_) over an optimizer of this module is one launch instead of the foreach
-    family; any other optimizer goes through the parent.  State dict and public behaviour are the parent's."""
+    family; any other optimizer goes through the parent.  State dict and public behaviour are the parent's.
+
+    unscale_(optimizer) on an optimizer with `collect_grad_stats` set (clip_grad_norm_ / grad_stats() set it on first use, a module
+    built with max_grad_norm at once) produces the gradient statistics in the launch that checks and unscales, at no extra read.  They
+    stay FRESH -- clip_grad_norm_ and grad_stats() reuse them instead of reading the gradients again -- until the optimizer's next
+    step(), zero_grad() or clip_grad_norm_; both take recompute=True to force a new pass."""
 
     def _unscale_grads_(self, optimizer, inv_scale, found_inf, allow_fp16):
         if not isinstance(optimizer, _DeviceOptimizer):
@@ -330,3 +417,52 @@ def create_optimizer(net: torch.nn.Module, name: str, **params) -> torch.optim.O
 
 def is_device_optimizer(optimizer) -> bool:
     return isinstance(optimizer, _DeviceOptimizer)
+
+
+STAT_L2, STAT_ABSMAX, STAT_ABSMEAN, STAT_NONFINITE = 0, 1, 2, 3  # the columns of grad_stats()'s rows
+NORM_L2, NORM_INF = 0, 1  # HH_GRAD_NORM_* of include/hhrnet.h
+
+
+def grad_stats_rows(named_parameters, params) -> dict:
+    """{name: row} of grad_stats()'s `stats` for the entries of `named_parameters` (net.named_parameters(), or any iterable of
+    (name, parameter)) that have a row; `params` is grad_stats()'s first result.  A logger prints per-layer mean / max |grad| with
+    one copy of `stats` to the host: stats.cpu()[row, STAT_ABSMEAN], [row, STAT_ABSMAX]."""
+    row = {id(p): r for r, p in enumerate(params)}
+    return {name: row[id(p)] for name, p in named_parameters if id(p) in row}
+
+
+def clip_grad_norm_(optimizer, max_norm: float, norm_type: float = 2.0, error_if_nonfinite: bool = False, recompute: bool = False) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_ over the optimizer's parameters that have a gradient -> the total norm (before clipping), a
+    0-dim fp32 tensor on the device.  norm_type is 2 or inf; anything else, or a max_norm that is negative or NaN, raises ValueError.
+
+    A device optimizer of this module: one read of the gradients for the statistics (none where GradScaler.unscale_ has just left
+    fresh ones -- `_DeviceOptimizer._grad_stats_pass` says what fresh means, recompute=True forces a new pass), and one launch that
+    multiplies them by coef = max_norm / (total + 1e-6) in torch's fp32 arithmetic and stores nothing where coef >= 1.  The total is
+    formed from fp64 sums in one fixed order and rounded once, so it is the correctly rounded norm up to fp64's own error and the same
+    bits on every run; torch accumulates in fp32.  Nothing is read on the host, except with error_if_nonfinite=True: that is one host
+    read of the total, before anything is scaled, and raises RuntimeError like torch.  DIFFERENCE from torch: after a
+    GradScaler.unscale_ that found an inf / NaN the gradients are left as they are (torch multiplies them by 0 or NaN); that step is
+    skipped either way.  Any other optimizer: torch's function over its parameters."""
+    max_norm, norm_type = float(max_norm), float(norm_type)
+    if norm_type not in (2.0, float("inf")):
+        raise ValueError(f"clip_grad_norm_: norm_type {norm_type!r} is not supported (2 or inf)")
+    if not max_norm >= 0.0:
+        raise ValueError(f"clip_grad_norm_: max_norm must be a number >= 0, got {max_norm!r}")
+    if not isinstance(optimizer, _DeviceOptimizer):
+        params = [p for group in optimizer.param_groups for p in group["params"]]
+        return torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type, error_if_nonfinite=error_if_nonfinite)
+    with torch.no_grad():
+        T = optimizer._grad_stats_pass(recompute)
+        if T is None:
+            dev = next((p.device for g in optimizer.param_groups for p in g["params"]), None)
+            return torch.zeros((), dtype=torch.float32, device=dev)
+        code = NORM_INF if norm_type != 2.0 else NORM_L2
+        total = optimizer._totals(T)[code].clone()
+        if error_if_nonfinite and not bool(torch.isfinite(total)):
+            raise RuntimeError(f"The total norm of order {norm_type} for gradients from `parameters` is non-finite, so it cannot be clipped. "
+                               "To disable this error and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`")
+        rows = T["rows"]
+        _lib.launch(T["dev"], _lib.load().hh_grad_clip, rows.ctypes.data, len(rows), len(T["groups"]), max_norm, code,
+                    _lib.ptr(T.get("stats_found_inf")), T["table"].data_ptr(), T["nbytes"], T["work"].data_ptr(), T["work_bytes"])
+        T["stats_fresh"] = False  # (the gradients may have been scaled: the statistics no longer describe them)
+        return total
