@@ -883,6 +883,48 @@ int hh_grad_stats(const hh_optim_tensor *tensors_host, int ntensors, int ngroups
 int hh_grad_clip(const hh_optim_tensor *tensors_host, int ntensors, int ngroups, float max_norm, int norm_type, const float *found_inf,
                  void *table_dev, int64_t table_bytes, void *work_dev, int64_t work_bytes, void *stream);
 
+/* Exponential moving average (EMA) of the weights next to that table (csrc/ema.hip; optim.ModelEMA of pytorch-human-pose_amd/optim.py):
+ * what torch.optim.swa_utils.AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(decay)) keeps, updated inside the optimizer's step
+ * launch, with a one-launch exchange of weights and average.  (Additive entry points: HH_ABI_VERSION stays 3.  hh_optim_tensor,
+ * hh_optim_group, hh_optim_table_bytes and hh_optim_step are unchanged.)
+ * RULE, per element in fp32 with every operation rounded on its own, n = *n_averaged before the call:
+ *   n == 0:    ema = value, the bits copied
+ *   otherwise: d = warmup ? min(decay, (1 + n) / (10 + n)) : decay in fp64;  w = (float)(1.0 - d), rounded once;
+ *              ema = ema + w * (value - ema)
+ *   and then *n_averaged = n + 1 (a one-workgroup launch behind the update: no workgroup reads a counter that one of the same launch
+ *   has advanced).  n_averaged is a device int64 scalar, like torch's.
+ * DIFFERENCES from torch: (1) this one formula serves every w; torch's lerp switches to another form at w >= 0.5.  (2) With
+ *   *found_inf != 0 nothing is stored at all: average and counter keep their bits, like the parameters, the optimizer state and the
+ *   step counters of the skipped step; torch's AveragedModel, which cannot see the skip, would update and count.
+ * hh_ema_row: one averaged fp32 tensor, `value` the live one (a parameter or a buffer) and `ema` its average, both dense with numel
+ *   elements and the same memory layout.
+ * hh_ema_table_bytes: the size of `ema_table_dev` for these rows next to an optimizer table of `ntensors` rows (0 for hh_ema_update /
+ *   hh_ema_swap); -1 on a bad argument.  The table holds the rows, one entry per 4096-element chunk, and the row indices.
+ * hh_ema_update: the stand-alone update of every row, one launch plus the counter's; found_inf may be NULL.  For any optimizer that
+ *   is not hh_optim_step.  upload != 0 copies the table into table_dev first (as in hh_optim_step: 0 where table_dev still holds the
+ *   same rows from the previous call of the SAME entry point; the three entry points lay the chunk list out differently).
+ * hh_ema_swap: one launch that exchanges value and ema element by element; twice is the identity, bit for bit.
+ * hh_optim_step_ema: hh_optim_step with its arguments, plus: the average of tensor i is rows_host[row_of_tensor[i]].ema (-1: this
+ *   tensor has none and is stepped as by hh_optim_step; that row's `value` is not read, the optimizer row's param is the value), and
+ *   every row that no tensor names is updated from its own `value` in the same launch (frozen parameters, floating-point buffers).
+ *   Parameter, gradient, state and step-counter bits are the ones hh_optim_step stores for the same arguments.
+ * Non-zero (nothing launched or copied) for: a null row table with nrows > 0, a null or misaligned (16 bytes) or too-small device
+ * table, a negative numel, a null value / ema pointer, a decay outside [0, 1] or NaN, a null n_averaged, and in hh_optim_step_ema
+ * whatever hh_optim_step refuses, a null row_of_tensor, a row index outside [-1, nrows), a row named by two tensors, and an optimizer
+ * row whose numel differs from its EMA row's.                                                                                        */
+typedef struct hh_ema_row {
+    float *value, *ema;
+    int64_t numel;
+} hh_ema_row;
+int64_t hh_ema_table_bytes(const hh_ema_row *rows_host, int nrows, int ntensors);
+int hh_ema_update(const hh_ema_row *rows_host, int nrows, double decay, int warmup, int64_t *n_averaged, const float *found_inf,
+                  void *table_dev, int64_t table_bytes, int upload, void *stream);
+int hh_ema_swap(const hh_ema_row *rows_host, int nrows, void *table_dev, int64_t table_bytes, int upload, void *stream);
+int hh_optim_step_ema(int algo, const hh_optim_tensor *tensors_host, int ntensors, const hh_optim_group *groups_host, int ngroups,
+                      const float *grad_scale, const float *found_inf, void *table_dev, int64_t table_bytes, int upload,
+                      const hh_ema_row *rows_host, int nrows, const int32_t *row_of_tensor, double decay, int warmup, int64_t *n_averaged,
+                      void *ema_table_dev, int64_t ema_table_bytes, int ema_upload, void *stream);
+
 /* Multi-scale test-time augmentation (BASELINE.json configs[3]; an extension: the reference only calls its resize helper
  * with scale 1, keypoints/model.py:73): dst[B,K,H,W] (+)= weight * bilinear(src[B,K,h,w] -> HxW) with the arithmetic of
  * F.interpolate(mode="bilinear", align_corners=False); init != 0 overwrites dst.  Batch strides in elements.            */

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from ..keypoints.model import BaseModel, parse_checkpoint
+from ..keypoints.model import BaseModel, checkpoint_weights, parse_checkpoint
 from .input import ClsInput, inference_geometry
 
 
@@ -59,13 +59,11 @@ class InferenceClassificationModel:
         if ckpt_path is not None:
             self.load_checkpoint(ckpt_path)
 
-    def load_checkpoint(self, ckpt_path: str) -> None:
+    def load_checkpoint(self, ckpt_path: str, use_ema: bool = False) -> None:
         """base/model.py:167-175: a trainer checkpoint keeps the weights under ["module"]["model"]; a bare state dict is loaded as
-        it is."""
+        it is.  use_ema=True loads the averaged weights under ["module"]["ema"]["model"] instead (KeyError where there are none)."""
         ckpt = torch.load(ckpt_path, map_location="cpu")
-        if "module" in ckpt.keys():
-            ckpt = ckpt["module"]["model"]
-        self.net.load_state_dict(parse_checkpoint(ckpt))
+        self.net.load_state_dict(parse_checkpoint(checkpoint_weights(ckpt, use_ema)))
 
     def prepare_inputs(self, images: list) -> torch.Tensor:
         """[uint8 HWC image] -> [B,3,input_size,input_size] on the device: Resize(input_size) + CenterCrop(input_size) + Normalize."""

@@ -6,13 +6,14 @@ their gradients, the pooled features, the Linear and the loss are fp32.  The met
 one device -> host read per step (the reference copies the logits to the host and runs topk there)."""
 from __future__ import annotations
 
+import contextlib
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 from torch import Tensor
 
-from ..optim import clip_grad_norm_
+from ..optim import ModelEMA, clip_grad_norm_
 from .loss import ClassificationLoss
 from .model import ClassificationModel
 
@@ -32,15 +33,29 @@ class ClassificationModule:
     net's engine as it is; a name calls `net.set_engine_dtype` once, here.
     max_grad_norm (not in the reference; None = off, the step is exactly the reference's sequence): the gradients are clipped to this
     global norm (grad_norm_type: 2 or inf) between the backward and the step by optim.clip_grad_norm_ -- on the optimizer's device
-    table for an optimizer of ..optim, with torch's function for any other -- and metrics["grad_norm"] is the norm before clipping."""
+    table for an optimizer of ..optim, with torch's function for any other -- and metrics["grad_norm"] is the norm before clipping.
+    ema_decay (not in the reference; None = off: the step as before, bit for bit, and no "ema" entry in state_dict()): a number keeps
+    an exponential moving average of the weights, `self.ema = optim.ModelEMA(net, optimizer, ema_decay, ema_warmup, ema_use_buffers)`,
+    updated inside the step launch of an optimizer of ..optim and by ema.update() after any other's.  validation_step runs on the
+    averaged weights (ema.applied()); state_dict() / load_state_dict() carry {"ema": ModelEMA.state_dict()}."""
 
     def __init__(self, model: ClassificationModel, loss_fn: ClassificationLoss, optimizer: torch.optim.Optimizer,
-                 idx2label: dict | None = None, eval_dtype: str | None = None, max_grad_norm: float | None = None, grad_norm_type: float = 2.0):
+                 idx2label: dict | None = None, eval_dtype: str | None = None, max_grad_norm: float | None = None, grad_norm_type: float = 2.0,
+                 ema_decay: float | None = None, ema_warmup: bool = False, ema_use_buffers: bool = False):
         self.model, self.loss_fn, self.optimizer, self.idx2label = model, loss_fn, optimizer, idx2label
+        self.ema = None if ema_decay is None else ModelEMA(model.net, optimizer, ema_decay, ema_warmup, ema_use_buffers)
         self.max_grad_norm, self.grad_norm_type = max_grad_norm, grad_norm_type
         self.eval_dtype = eval_dtype
         if eval_dtype is not None:
             model._bare().set_engine_dtype(eval_dtype)
+
+    def state_dict(self) -> dict:
+        """The module's own checkpoint entries: {"ema": ...} with ema_decay set, nothing otherwise (this module has no scaler)."""
+        return {} if self.ema is None else {"ema": self.ema.state_dict()}
+
+    def load_state_dict(self, state_dict: dict) -> None:
+        if self.ema is not None:
+            self.ema.load_state_dict(state_dict["ema"])
 
     def batch_to_device(self, batch):
         images, targets = batch
@@ -61,6 +76,8 @@ class ClassificationModule:
         if self.max_grad_norm is not None:
             metrics["grad_norm"] = clip_grad_norm_(self.optimizer, self.max_grad_norm, self.grad_norm_type).item()
         self.optimizer.step()
+        if self.ema is not None and self.ema.optimizer is None:  # (attached to a device optimizer it was updated inside the step)
+            self.ema.update()
         self.model._bare().mark_dirty()
         return metrics
 
@@ -71,7 +88,7 @@ class ClassificationModule:
         was_training = net.training
         net.eval()
         try:
-            with torch.no_grad():
+            with torch.no_grad(), (self.ema.applied() if self.ema is not None else contextlib.nullcontext()):
                 logits = self.model.net(images)
                 self.loss_fn.calculate_loss(targets, logits)
         finally:

@@ -9,6 +9,7 @@
 #include "engine.h"
 #include "optim_math.h"
 #include "grad_stats_math.h"
+#include "ema_math.h"
 #include "render_math.h"
 #include "panel_math.h"
 #include "coco_eval_math.h"
@@ -1109,32 +1110,179 @@ static int optim_upload(const hh_optim_tensor *t, int ntensors, const hh_optim_g
     return 0;
 }
 
-int hh_optim_step(int algo, const hh_optim_tensor *tensors_host, int ntensors, const hh_optim_group *groups_host, int ngroups,
-                  const float *grad_scale, const float *found_inf, void *table_dev, int64_t table_bytes, int upload, void *stream)
+// the checks of hh_optim_step (and of hh_optim_step_ema, which steps the same table); -> the chunk count, or -1 with the error set
+static int64_t optim_step_check(const char *who, int algo, const hh_optim_tensor *tensors_host, int ntensors, const hh_optim_group *groups_host,
+                                int ngroups, const void *table_dev, int64_t table_bytes, int upload)
 {
-    if (algo != HH_OPTIM_ADAM && algo != HH_OPTIM_ADAMW && algo != HH_OPTIM_SGD) { hh_set_error("hh_optim_step: unknown algorithm (HH_OPTIM_ADAM = 0, HH_OPTIM_ADAMW = 1, HH_OPTIM_SGD = 2)"); return 1; }
-    if (!groups_host || !table_dev) { hh_set_error("hh_optim_step: null group table or device table"); return 1; }
-    if (upload < 0 || upload > HH_OPTIM_UPLOAD_ALL) { hh_set_error("hh_optim_step: upload is a mask of HH_OPTIM_UPLOAD_TENSORS | HH_OPTIM_UPLOAD_GROUPS"); return 1; }
-    if ((uintptr_t)table_dev % 16) { hh_set_error("hh_optim_step: table_dev must be 16-byte aligned"); return 1; }
-    const int64_t nchunks = optim_count_chunks(tensors_host, ntensors, ngroups, "hh_optim_step");
-    if (nchunks < 0) return 1;
-    if (table_bytes < optim_bytes(ntensors, ngroups, nchunks)) { hh_set_error("hh_optim_step: table buffer too small (hh_optim_table_bytes)"); return 1; }
+    const std::string w(who);
+    if (algo != HH_OPTIM_ADAM && algo != HH_OPTIM_ADAMW && algo != HH_OPTIM_SGD) { hh_set_error(w + ": unknown algorithm (HH_OPTIM_ADAM = 0, HH_OPTIM_ADAMW = 1, HH_OPTIM_SGD = 2)"); return -1; }
+    if (!groups_host || !table_dev) { hh_set_error(w + ": null group table or device table"); return -1; }
+    if (upload < 0 || upload > HH_OPTIM_UPLOAD_ALL) { hh_set_error(w + ": upload is a mask of HH_OPTIM_UPLOAD_TENSORS | HH_OPTIM_UPLOAD_GROUPS"); return -1; }
+    if ((uintptr_t)table_dev % 16) { hh_set_error(w + ": table_dev must be 16-byte aligned"); return -1; }
+    const int64_t nchunks = optim_count_chunks(tensors_host, ntensors, ngroups, who);
+    if (nchunks < 0) return -1;
+    if (table_bytes < optim_bytes(ntensors, ngroups, nchunks)) { hh_set_error(w + ": table buffer too small (hh_optim_table_bytes)"); return -1; }
     const bool adam = algo != HH_OPTIM_SGD;
     for (int g = 0; g < ngroups; ++g) {
         const hh_optim_group &gr = groups_host[g];
-        if (adam && !(gr.beta1 >= 0.0 && gr.beta1 < 1.0 && gr.beta2 >= 0.0 && gr.beta2 < 1.0)) { hh_set_error("hh_optim_step: betas must lie in [0, 1)"); return 1; }
+        if (adam && !(gr.beta1 >= 0.0 && gr.beta1 < 1.0 && gr.beta2 >= 0.0 && gr.beta2 < 1.0)) { hh_set_error(w + ": betas must lie in [0, 1)"); return -1; }
     }
     for (int i = 0; i < ntensors; ++i) {
         const hh_optim_tensor &t = tensors_host[i];
         const bool need_s0 = adam || groups_host[t.group].momentum != 0.0;
-        if (!t.param || !t.grad || (need_s0 && !t.state0) || (adam && (!t.state1 || !t.step))) { hh_set_error("hh_optim_step: null pointer in the tensor table"); return 1; }
+        if (!t.param || !t.grad || (need_s0 && !t.state0) || (adam && (!t.state1 || !t.step))) { hh_set_error(w + ": null pointer in the tensor table"); return -1; }
     }
+    return nchunks;
+}
+
+int hh_optim_step(int algo, const hh_optim_tensor *tensors_host, int ntensors, const hh_optim_group *groups_host, int ngroups,
+                  const float *grad_scale, const float *found_inf, void *table_dev, int64_t table_bytes, int upload, void *stream)
+{
+    const int64_t nchunks = optim_step_check("hh_optim_step", algo, tensors_host, ntensors, groups_host, ngroups, table_dev, table_bytes, upload);
+    if (nchunks < 0) return 1;
     if (!nchunks) return 0;
     if (optim_upload(tensors_host, ntensors, groups_host, ngroups, nchunks, upload, (char *)table_dev, (hipStream_t)stream)) return 1;
     const OptimTensor *td = (const OptimTensor *)table_dev;
     const OptimChunk *cd = (const OptimChunk *)(td + ntensors);
     const OptimGroup *gd = (const OptimGroup *)(cd + nchunks);
-    HH_CHECK_HIP(launch_optim_step(algo, td, ntensors, gd, cd, (int)nchunks, grad_scale, found_inf, adam ? 1 : 0, (hipStream_t)stream));
+    HH_CHECK_HIP(launch_optim_step(algo, td, ntensors, gd, cd, (int)nchunks, grad_scale, found_inf, algo != HH_OPTIM_SGD ? 1 : 0, (hipStream_t)stream));
+    return 0;
+}
+
+// ---- weight EMA (ema.hip).  Table layout in the EMA table: [rows][chunks][row_of: one int per optimizer tensor].  The chunk list is of
+// all rows (hh_ema_update, hh_ema_swap) or of the rows no optimizer tensor names (hh_optim_step_ema); the buffer is sized for all.
+static_assert(sizeof(hh_ema_row) == sizeof(EmaRow) && sizeof(EmaRow) == 24, "hh_ema_row layout");
+
+// -> the chunk count of all rows, or -1 with the error set
+static int64_t ema_count_chunks(const char *who, const hh_ema_row *rows, int nrows)
+{
+    const std::string w(who);
+    if (nrows < 0) { hh_set_error(w + ": need nrows >= 0"); return -1; }
+    if (nrows && !rows) { hh_set_error(w + ": null row table"); return -1; }
+    int64_t nchunks = 0;
+    for (int i = 0; i < nrows; ++i) {
+        if (rows[i].numel < 0) { hh_set_error(w + ": negative numel in the row table"); return -1; }
+        if (!rows[i].value || !rows[i].ema) { hh_set_error(w + ": null pointer in the row table"); return -1; }
+        nchunks += (rows[i].numel + OPTIM_CHUNK - 1) / OPTIM_CHUNK;
+    }
+    if (nchunks > 0x7fffffffLL) { hh_set_error(w + ": more than 2^31 - 1 chunks"); return -1; }
+    return nchunks;
+}
+
+static int64_t ema_bytes(int nrows, int64_t nchunks, int ntensors)
+{
+    return (int64_t)nrows * (int64_t)sizeof(EmaRow) + nchunks * (int64_t)sizeof(OptimChunk) + (int64_t)ntensors * (int64_t)sizeof(int);
+}
+
+// the checks the three entry points share; -> the chunk count of all rows, or -1 with the error set
+static int64_t ema_check(const char *who, const hh_ema_row *rows, int nrows, int ntensors, const void *table_dev, int64_t table_bytes)
+{
+    const std::string w(who);
+    if (!table_dev) { hh_set_error(w + ": null EMA device table"); return -1; }
+    if ((uintptr_t)table_dev % 16) { hh_set_error(w + ": the EMA device table must be 16-byte aligned"); return -1; }
+    const int64_t nchunks = ema_count_chunks(who, rows, nrows);
+    if (nchunks < 0) return -1;
+    if (table_bytes < ema_bytes(nrows, nchunks, ntensors)) { hh_set_error(w + ": EMA table buffer too small (hh_ema_table_bytes)"); return -1; }
+    return nchunks;
+}
+
+static bool ema_decay_ok(const char *who, double decay, const int64_t *n_averaged)
+{
+    if (!(decay >= 0.0 && decay <= 1.0)) { hh_set_error(std::string(who) + ": decay must lie in [0, 1]"); return false; }
+    if (!n_averaged) { hh_set_error(std::string(who) + ": null n_averaged"); return false; }
+    return true;
+}
+
+// Ships [rows][chunks of the rows with skip[row] == 0][row_of] with one async copy; -> the number of chunks listed, -1 on a HIP error.
+// `nall` is the chunk count of all rows: row_of sits behind room for that many, whatever is listed.
+static int64_t ema_upload(const hh_ema_row *rows, int nrows, const char *skip, const int32_t *row_of, int ntensors, int64_t nall, int upload,
+                          char *table_dev, hipStream_t stream)
+{
+    int64_t listed = 0;
+    for (int i = 0; i < nrows; ++i)
+        if (!skip || !skip[i]) listed += (rows[i].numel + OPTIM_CHUNK - 1) / OPTIM_CHUNK;
+    if (!upload) return listed;
+    static thread_local std::vector<char> host;
+    const size_t rb = (size_t)nrows * sizeof(EmaRow), cb = (size_t)nall * sizeof(OptimChunk), ib = (size_t)ntensors * sizeof(int);
+    host.assign(rb + cb + ib, 0);
+    if (rb) std::memcpy(host.data(), rows, rb);
+    OptimChunk *c = (OptimChunk *)(host.data() + rb);
+    for (int i = 0; i < nrows; ++i) {
+        if (skip && skip[i]) continue;
+        const int n = (int)((rows[i].numel + OPTIM_CHUNK - 1) / OPTIM_CHUNK);
+        for (int k = 0; k < n; ++k) *c++ = OptimChunk{i, k};
+    }
+    if (ib) std::memcpy(host.data() + rb + cb, row_of, ib);
+    if (!host.empty() && hipMemcpyAsync(table_dev, host.data(), host.size(), hipMemcpyHostToDevice, stream) != hipSuccess) {
+        hh_set_error("hipMemcpyAsync of the EMA table failed");
+        return -1;
+    }
+    return listed;
+}
+
+int64_t hh_ema_table_bytes(const hh_ema_row *rows_host, int nrows, int ntensors)
+{
+    if (ntensors < 0) { hh_set_error("hh_ema_table_bytes: need ntensors >= 0"); return -1; }
+    const int64_t nchunks = ema_count_chunks("hh_ema_table_bytes", rows_host, nrows);
+    return nchunks < 0 ? -1 : ema_bytes(nrows, nchunks, ntensors);
+}
+
+int hh_ema_update(const hh_ema_row *rows_host, int nrows, double decay, int warmup, int64_t *n_averaged, const float *found_inf, void *table_dev,
+                  int64_t table_bytes, int upload, void *stream)
+{
+    if (!ema_decay_ok("hh_ema_update", decay, n_averaged)) return 1;
+    const int64_t nall = ema_check("hh_ema_update", rows_host, nrows, 0, table_dev, table_bytes);
+    if (nall < 0) return 1;
+    if (ema_upload(rows_host, nrows, nullptr, nullptr, 0, nall, upload, (char *)table_dev, (hipStream_t)stream) < 0) return 1;
+    const EmaRow *rd = (const EmaRow *)table_dev;
+    HH_CHECK_HIP(launch_ema_update(rd, (const OptimChunk *)(rd + nrows), (int)nall, decay, warmup != 0, (long long *)n_averaged, found_inf,
+                                   (hipStream_t)stream));
+    return 0;
+}
+
+int hh_ema_swap(const hh_ema_row *rows_host, int nrows, void *table_dev, int64_t table_bytes, int upload, void *stream)
+{
+    const int64_t nall = ema_check("hh_ema_swap", rows_host, nrows, 0, table_dev, table_bytes);
+    if (nall < 0) return 1;
+    if (ema_upload(rows_host, nrows, nullptr, nullptr, 0, nall, upload, (char *)table_dev, (hipStream_t)stream) < 0) return 1;
+    const EmaRow *rd = (const EmaRow *)table_dev;
+    HH_CHECK_HIP(launch_ema_swap(rd, (const OptimChunk *)(rd + nrows), (int)nall, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_optim_step_ema(int algo, const hh_optim_tensor *tensors_host, int ntensors, const hh_optim_group *groups_host, int ngroups,
+                      const float *grad_scale, const float *found_inf, void *table_dev, int64_t table_bytes, int upload,
+                      const hh_ema_row *rows_host, int nrows, const int32_t *row_of_tensor, double decay, int warmup, int64_t *n_averaged,
+                      void *ema_table_dev, int64_t ema_table_bytes, int ema_upload_flag, void *stream)
+{
+    const char *who = "hh_optim_step_ema";
+    const int64_t nchunks = optim_step_check(who, algo, tensors_host, ntensors, groups_host, ngroups, table_dev, table_bytes, upload);
+    if (nchunks < 0) return 1;
+    if (!ema_decay_ok(who, decay, n_averaged)) return 1;
+    const int64_t nall = ema_check(who, rows_host, nrows, ntensors, ema_table_dev, ema_table_bytes);
+    if (nall < 0) return 1;
+    if (ntensors && !row_of_tensor) { hh_set_error("hh_optim_step_ema: null row_of_tensor"); return 1; }
+    std::vector<char> named((size_t)nrows, 0);
+    for (int i = 0; i < ntensors; ++i) {
+        const int32_t r = row_of_tensor[i];
+        if (r < -1 || r >= nrows) { hh_set_error("hh_optim_step_ema: row index outside [-1, nrows)"); return 1; }
+        if (r < 0) continue;
+        if (named[r]) { hh_set_error("hh_optim_step_ema: an EMA row is named by two tensors"); return 1; }
+        named[r] = 1;
+        if (rows_host[r].numel != tensors_host[i].numel) { hh_set_error("hh_optim_step_ema: an optimizer row and its EMA row differ in numel"); return 1; }
+    }
+    if (nchunks && optim_upload(tensors_host, ntensors, groups_host, ngroups, nchunks, upload, (char *)table_dev, (hipStream_t)stream)) return 1;
+    const int64_t nonly = ema_upload(rows_host, nrows, named.data(), row_of_tensor, ntensors, nall, ema_upload_flag, (char *)ema_table_dev, (hipStream_t)stream);
+    if (nonly < 0) return 1;
+    const OptimTensor *td = (const OptimTensor *)table_dev;
+    const OptimChunk *cd = (const OptimChunk *)(td + ntensors);
+    const OptimGroup *gd = (const OptimGroup *)(cd + nchunks);
+    const EmaRow *rd = (const EmaRow *)ema_table_dev;
+    const OptimChunk *od = (const OptimChunk *)(rd + nrows);
+    const int *row_of = (const int *)(od + nall);
+    if (nchunks + nonly > 0x7fffffffLL) { hh_set_error("hh_optim_step_ema: more than 2^31 - 1 chunks"); return 1; }
+    HH_CHECK_HIP(launch_optim_step_ema(algo, td, ntensors, gd, cd, (int)nchunks, grad_scale, found_inf, algo != HH_OPTIM_SGD ? 1 : 0, rd, row_of, od,
+                                       (int)nonly, decay, warmup != 0, (long long *)n_averaged, (hipStream_t)stream));
     return 0;
 }
 

@@ -456,3 +456,13 @@ hipError_t launch_grad_stats(const OptimTensor *tensors, int ntensors, const Opt
                              float *found_inf, void *work, hipStream_t s);
 hipError_t launch_grad_clip(const OptimTensor *tensors, int ntensors, const OptimChunk *chunks, int nchunks, float max_norm, int norm_type,
                             const float *found_inf, void *work, hipStream_t s);
+// Weight EMA (ema.hip; arithmetic in ema_math.h): the optimizer step with the average as a fifth stream plus `nonly` chunks of rows the
+// optimizer does not step, the stand-alone update, and the swap.  The update launches are followed by the one-workgroup tail that
+// advances the counters.
+struct EmaRow;
+hipError_t launch_optim_step_ema(int algo, const OptimTensor *tensors, int ntensors, const OptimGroup *groups, const OptimChunk *chunks, int nchunks,
+                                 const float *grad_scale, const float *found_inf, int advance_steps, const EmaRow *rows, const int *row_of,
+                                 const OptimChunk *only_chunks, int nonly, double decay, int warmup, long long *n_averaged, hipStream_t s);
+hipError_t launch_ema_update(const EmaRow *rows, const OptimChunk *chunks, int nchunks, double decay, int warmup, long long *n_averaged,
+                             const float *found_inf, hipStream_t s);
+hipError_t launch_ema_swap(const EmaRow *rows, const OptimChunk *chunks, int nchunks, hipStream_t s);

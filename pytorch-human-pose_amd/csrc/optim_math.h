@@ -101,10 +101,20 @@ HH_HD bool optim_aligned16(OptimPtr a, OptimPtr b, OptimPtr c, OptimPtr d)
     return (((unsigned long long)a | (unsigned long long)b | (unsigned long long)c | (unsigned long long)d) & 15ull) == 0;
 }
 
+// An optional fifth stream of the walk below: `ptr` is its address for this tensor (NULL: this tensor has none), apply() its new value
+// from its old one and the stepped parameter.  OptimNoFifth is none at all, the walk of optim_step_kernel; ema_math.h has the other.
+struct OptimNoFifth {
+    enum { ON = 0 };
+    float *ptr;
+    HH_HD float apply(float old, float) const { return old; }
+};
+
 // Thread `tid` of OPTIM_THREADS's share of one chunk: the whole memory walk of optim_step_kernel.  16-byte accesses where the chunk's
 // four addresses allow them (a chunk starts 16 KiB into its tensor, so the tensors' own addresses decide), scalar ones for any other
-// chunk and for the last numel % 4 elements.  unscale: g / scale is used and written back.
-template <int ALGO> HH_HD void optim_chunk_update(const OptimTensor &t, int chunk, const OptimCoefs &c, bool unscale, float scale, int tid)
+// chunk and for the last numel % 4 elements.  unscale: g / scale is used and written back.  A fifth stream joins the alignment test
+// (it alone misaligned: the scalar path for all five) and is read and written next to p.
+template <int ALGO, class Fifth = OptimNoFifth>
+HH_HD void optim_chunk_update(const OptimTensor &t, int chunk, const OptimCoefs &c, bool unscale, float scale, int tid, const Fifth fifth = Fifth{nullptr})
 {
     const long long base = (long long)chunk * OPTIM_CHUNK;
     const long long left = t.numel - base;
@@ -113,8 +123,10 @@ template <int ALGO> HH_HD void optim_chunk_update(const OptimTensor &t, int chun
     const bool use_s0 = ALGO != OPTIM_SGD || c.has_momentum, use_s1 = ALGO != OPTIM_SGD;
     const OptimPtr p = (OptimPtr)(t.p + base), g = (OptimPtr)(t.g + base), s0 = use_s0 ? (OptimPtr)(t.s0 + base) : nullptr,
                    s1 = use_s1 ? (OptimPtr)(t.s1 + base) : nullptr;
+    const bool use_e = Fifth::ON && fifth.ptr != nullptr;
+    const OptimPtr e = use_e ? (OptimPtr)(fifth.ptr + base) : nullptr;
     int done = 0;  // elements the 16-byte path covers
-    if (optim_aligned16(p, g, s0, s1)) {
+    if (optim_aligned16(p, g, s0, s1) && (!Fifth::ON || ((unsigned long long)e & 15ull) == 0)) {
         const int n4 = n >> 2;
         done = n4 << 2;
 #pragma unroll
@@ -124,6 +136,7 @@ template <int ALGO> HH_HD void optim_chunk_update(const OptimTensor &t, int chun
                 OptimF4 pv = ((OptimPtr4)p)[i], gv = ((OptimPtr4)g)[i];
                 OptimF4 av = use_s0 ? ((OptimPtr4)s0)[i] : OptimF4{0.f, 0.f, 0.f, 0.f};
                 OptimF4 bv = use_s1 ? ((OptimPtr4)s1)[i] : OptimF4{0.f, 0.f, 0.f, 0.f};
+                OptimF4 ev = use_e ? ((OptimPtr4)e)[i] : OptimF4{0.f, 0.f, 0.f, 0.f};
                 if (unscale) {
                     gv.x = gv.x / scale; gv.y = gv.y / scale; gv.z = gv.z / scale; gv.w = gv.w / scale;
                     ((OptimPtr4)g)[i] = gv;
@@ -135,6 +148,10 @@ template <int ALGO> HH_HD void optim_chunk_update(const OptimTensor &t, int chun
                 ((OptimPtr4)p)[i] = pv;
                 if (use_s0) ((OptimPtr4)s0)[i] = av;
                 if (use_s1) ((OptimPtr4)s1)[i] = bv;
+                if (use_e) {
+                    ev.x = fifth.apply(ev.x, pv.x); ev.y = fifth.apply(ev.y, pv.y); ev.z = fifth.apply(ev.z, pv.z); ev.w = fifth.apply(ev.w, pv.w);
+                    ((OptimPtr4)e)[i] = ev;
+                }
             }
         }
     }
@@ -148,6 +165,7 @@ template <int ALGO> HH_HD void optim_chunk_update(const OptimTensor &t, int chun
         p[i] = pv;
         if (use_s0) s0[i] = av;
         if (use_s1) s1[i] = bv;
+        if (use_e) e[i] = fifth.apply(e[i], pv);
     }
 }
 

@@ -6,6 +6,8 @@ ckpt["module"]["model"] or a bare state dict, prefixes `module.` / `_orig_mod.` 
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 import torch
 from torch import Tensor, nn
@@ -30,6 +32,19 @@ def parse_checkpoint(ckpt: dict) -> dict:
             k = k.replace(p, "")
         out[k] = v
     return out
+
+
+def checkpoint_weights(ckpt: dict, use_ema: bool = False) -> dict:
+    """The state dict of the net inside a loaded checkpoint: ckpt["module"]["model"], or the checkpoint itself where it is a bare state
+    dict; with use_ema the averaged weights under ckpt["module"]["ema"]["model"] (KeyError naming the missing entry otherwise)."""
+    if use_ema:
+        node, path = ckpt, "checkpoint"
+        for key in ("module", "ema", "model"):
+            if not isinstance(node, dict) or key not in node:
+                raise KeyError(f'load_checkpoint(use_ema=True): the checkpoint has no ["module"]["ema"]["model"] entry ({path} lacks "{key}")')
+            node, path = node[key], f'{path}["{key}"]'
+        return node
+    return ckpt["module"]["model"] if "module" in ckpt.keys() else ckpt
 
 
 class BaseModel:
@@ -122,18 +137,25 @@ class KeypointsModule:
     max_grad_norm (not in the reference; None = off, the step is exactly the sequence above): the gradients are clipped to this global
     norm (grad_norm_type: 2 or inf) between the backward and the step -- bf16: backward, clip, step; fp16: scale(loss).backward(),
     scaler.unscale_, clip, scaler.step, scaler.update -- and metrics["grad_norm"] is the norm before clipping.  optim.clip_grad_norm_
-    does it: on the optimizer's device table for an optimizer of ..optim, with torch's function for any other."""
+    does it: on the optimizer's device table for an optimizer of ..optim, with torch's function for any other.
+    ema_decay (not in the reference; None = off: the step as before, bit for bit, and no "ema" entry in state_dict()): a number keeps
+    an exponential moving average of the weights, `self.ema = optim.ModelEMA(net, optimizer, ema_decay, ema_warmup, ema_use_buffers)`.
+    With an optimizer of ..optim it is updated inside the step launch and follows the scaler's skip; after any other optimizer's step
+    training_step calls ema.update() (an fp16 step skipped by torch's scaler is then still averaged and counted, as by torch's
+    AveragedModel: the host cannot know).  validation_step runs on the averaged weights (ema.applied()) and state_dict() carries them."""
 
     PRECISIONS = ("bf16", "fp16")
 
     def __init__(self, model: KeypointsModel, loss_fn, optimizer: torch.optim.Optimizer, precision: str = "bf16", eval_dtype: str | None = None,
-                 max_grad_norm: float | None = None, grad_norm_type: float = 2.0):
+                 max_grad_norm: float | None = None, grad_norm_type: float = 2.0, ema_decay: float | None = None, ema_warmup: bool = False,
+                 ema_use_buffers: bool = False):
         if precision not in self.PRECISIONS:
             raise ValueError(f"KeypointsModule: precision {precision!r} is not one of {self.PRECISIONS}")
         self.model, self.loss_fn, self.optimizer, self.precision = model, loss_fn, optimizer, precision
         self.max_grad_norm, self.grad_norm_type = max_grad_norm, grad_norm_type
         # (an optimizer of ..optim gets the scaler whose non-finite check is one launch over its table; any other, torch's own)
-        from ..optim import GradScaler, is_device_optimizer
+        from ..optim import GradScaler, ModelEMA, is_device_optimizer
+        self.ema = None if ema_decay is None else ModelEMA(model.net, optimizer, ema_decay, ema_warmup, ema_use_buffers)
         scaler_cls = GradScaler if is_device_optimizer(optimizer) else torch.amp.GradScaler
         self.scalers: dict = {"optim": scaler_cls("cuda")} if precision == "fp16" else {}
         if max_grad_norm is not None and is_device_optimizer(optimizer):
@@ -144,12 +166,18 @@ class KeypointsModule:
             model._bare().set_engine_dtype(eval_dtype)
 
     def state_dict(self) -> dict:
-        """The module's own checkpoint entries in the reference's format (base/module.py:109-127): {"scalers": {name: state}}."""
-        return {"scalers": {name: scaler.state_dict() for name, scaler in self.scalers.items()}}
+        """The module's own checkpoint entries in the reference's format (base/module.py:109-127): {"scalers": {name: state}}, and
+        with ema_decay set {"ema": ModelEMA.state_dict()} next to it."""
+        sd = {"scalers": {name: scaler.state_dict() for name, scaler in self.scalers.items()}}
+        if self.ema is not None:
+            sd["ema"] = self.ema.state_dict()
+        return sd
 
     def load_state_dict(self, state_dict: dict) -> None:
         for name, scaler in self.scalers.items():
             scaler.load_state_dict(state_dict["scalers"][name])
+        if self.ema is not None:
+            self.ema.load_state_dict(state_dict["ema"])
 
     def batch_to_device(self, batch):
         images, heatmaps, masks, joints = batch
@@ -179,6 +207,8 @@ class KeypointsModule:
                 grad_norm = clip_grad_norm_(self.optimizer, self.max_grad_norm, self.grad_norm_type)
             scaler.step(self.optimizer)
             scaler.update()
+        if self.ema is not None and self.ema.optimizer is None:  # (attached to a device optimizer it was updated inside the step)
+            self.ema.update()
         self.model._bare().mark_dirty()
         metrics = {"loss": loss.detach().item()}
         if grad_norm is not None:
@@ -196,7 +226,7 @@ class KeypointsModule:
         reference decodes image by image on the host; here the whole batch goes through one hh_decode."""
         from .results import KeypointsResult
         images, heatmaps, masks, joints = batch
-        with torch.no_grad():
+        with torch.no_grad(), (self.ema.applied() if self.ema is not None else contextlib.nullcontext()):
             stages_hms, tags = self.model.net(images)
             hm_losses, push_losses, pull_losses = self.loss_fn.calculate_loss(stages_hms, tags, heatmaps, masks, joints)
         loss = hm_losses[0] + hm_losses[1] + push_losses[0] + pull_losses[0]
@@ -290,13 +320,12 @@ class InferenceKeypointsModel:
         if ckpt_path is not None:
             self.load_checkpoint(ckpt_path)
 
-    def load_checkpoint(self, ckpt_path: str) -> None:
+    def load_checkpoint(self, ckpt_path: str, use_ema: bool = False) -> None:
         """base/model.py:167-175: a trainer checkpoint keeps the weights under ["module"]["model"]; a bare state dict (the
-        published pretrained/higher_hrnet_32.pt) is loaded as it is."""
+        published pretrained/higher_hrnet_32.pt) is loaded as it is.  use_ema=True loads the averaged weights a module trained with
+        ema_decay has put under ["module"]["ema"]["model"] instead, and raises KeyError where there are none."""
         ckpt = torch.load(ckpt_path, map_location="cpu")
-        if "module" in ckpt.keys():
-            ckpt = ckpt["module"]["model"]
-        self.net.load_state_dict(parse_checkpoint(ckpt))
+        self.net.load_state_dict(parse_checkpoint(checkpoint_weights(ckpt, use_ema)))
 
     def prepare_input_scaled(self, image: np.ndarray, current_scale: float, min_scale: float):
         """prepare_input for one entry of a multi-scale test (get_multi_scale_size, base/transforms/utils.py:60-86)."""

@@ -13,8 +13,13 @@ by one launch over the same table.  There is no fall-back to torch kernels.
 Between the backward and the step (csrc/grad_stats.hip): `clip_grad_norm_(optimizer, max_norm)` is torch.nn.utils.clip_grad_norm_ over
 the same table, and `optimizer.grad_stats()` gives per-parameter l2 / max / mean |grad| and the count of non-finite elements -- one
 read of the gradients for both, and none at all after `GradScaler.unscale_`, whose launch leaves the statistics behind.
+
+`ModelEMA` (csrc/ema.hip) keeps an exponential moving average of a net's weights.  Attached to an optimizer of this module it is
+updated inside the step launch and follows the step's skip; `swap()` / `applied()` exchange weights and average in one launch.
 """
 from __future__ import annotations
+
+import contextlib
 
 import numpy as np
 import torch
@@ -28,7 +33,8 @@ _TENSOR = np.dtype([("param", "<u8"), ("grad", "<u8"), ("state0", "<u8"), ("stat
                     ("group", "<i4"), ("reserved", "<i4")])
 _GROUP = np.dtype([("lr", "<f8"), ("beta1", "<f8"), ("beta2", "<f8"), ("eps", "<f8"), ("weight_decay", "<f8"), ("momentum", "<f8"),
                    ("nesterov", "<i4"), ("reserved", "<i4")])
-assert _TENSOR.itemsize == 56 and _GROUP.itemsize == 56
+_EMA_ROW = np.dtype([("value", "<u8"), ("ema", "<u8"), ("numel", "<i8")])  # hh_ema_row (24 bytes)
+assert _TENSOR.itemsize == 56 and _GROUP.itemsize == 56 and _EMA_ROW.itemsize == 24
 
 
 class _DeviceOptimizer(torch.optim.Optimizer):
@@ -57,6 +63,7 @@ class _DeviceOptimizer(torch.optim.Optimizer):
         if len(devices) > 1:
             raise ValueError(f"{type(self).__name__}: all parameters must be on one device, got {sorted(map(str, devices))}")
         self._rows = None  # the table of the current active set
+        self._ema = None   # an attached ModelEMA: step() then runs the fused launch
 
     # ---- per-algorithm parts
     def _check_group(self, group) -> None:
@@ -195,12 +202,22 @@ class _DeviceOptimizer(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         T, upload = self._table()
+        ema = getattr(self, "_ema", None)
+        if T is None and ema is not None:  # nothing to step: the average still follows the weights, under the same skip rule
+            ema.update(getattr(self, "found_inf", None))
         if T is not None:
             dev, rows, groups = T["dev"], T["rows"], T["groups"]
             scale = self._scalar_ptr(getattr(self, "grad_scale", None), "grad_scale", dev)
             found = self._scalar_ptr(getattr(self, "found_inf", None), "found_inf", dev)
-            _lib.launch(dev, _lib.load().hh_optim_step, self.ALGO, rows.ctypes.data, len(rows), groups.ctypes.data, len(groups), scale, found,
-                        T["table"].data_ptr(), T["nbytes"], upload)
+            if ema is None:
+                _lib.launch(dev, _lib.load().hh_optim_step, self.ALGO, rows.ctypes.data, len(rows), groups.ctypes.data, len(groups), scale, found,
+                            T["table"].data_ptr(), T["nbytes"], upload)
+            else:
+                E, ema_upload = ema._table("step", T)
+                _lib.launch(dev, _lib.load().hh_optim_step_ema, self.ALGO, rows.ctypes.data, len(rows), groups.ctypes.data, len(groups), scale,
+                            found, T["table"].data_ptr(), T["nbytes"], upload, E["rows"].ctypes.data, len(E["rows"]), E["row_of"].ctypes.data,
+                            ema.decay, int(ema.warmup), ema.n_averaged.data_ptr(), E["table"].data_ptr(), E["nbytes"], ema_upload)
+                ema._sent(E, ema_upload)
             self._sent(T, upload)
             T["stats_fresh"] = False  # (gradient statistics of before this step are not reused after it)
         return loss
@@ -403,6 +420,197 @@ class GradScaler(torch.amp.GradScaler):
             return super()._unscale_grads_(optimizer, inv_scale, found_inf, allow_fp16)
         optimizer.check_grads_nonfinite(found_inf, inv_scale)
         return {found_inf.device: found_inf}
+
+
+class ModelEMA:
+    """Exponential moving average of a net's weights on the device (csrc/ema.hip), in place of torch.optim.swa_utils.AveragedModel(
+    multi_avg_fn=get_ema_multi_avg_fn(decay)).
+
+    The rule, per element in fp32, n = n_averaged before the update: n == 0 copies the weights' bits; otherwise
+    d = min(decay, (1 + n) / (10 + n)) with warmup, decay without, in fp64, w = float32(1 - d) rounded once, ema += w * (value - ema).
+    DIFFERENCES from torch: this one form serves every w (torch's lerp switches form at w >= 0.5), and a step that the optimizer skips
+    on found_inf leaves the average and n_averaged alone (AveragedModel cannot see the skip, so it updates and counts).
+
+    Averaged: every parameter of the bare net (DistributedDataParallel unwrapped), trainable or frozen, and with use_buffers=True
+    every floating-point buffer (BatchNorm running statistics).  Integer buffers are never averaged.  state_dict()["model"] is a state
+    dict of the net: averages where there are any, the net's own buffers of the moment of the call elsewhere (torch's use_buffers=False
+    behaviour).  All averaged tensors must be dense fp32 on one GPU; anything else raises ValueError.
+
+    With an optimizer of this module the EMA attaches itself: optimizer.step() then updates the average of every parameter it steps in
+    the step launch, from the new value still in registers, and every other averaged tensor in further workgroups of the same launch;
+    there is nothing else to call.  With any other optimizer call update() after its step: one launch over the same rows.  Neither
+    reads the device on the host; n_averaged is a 0-dim int64 device tensor.  Pointers of the live tensors are gathered at every call
+    (parameters move under .to(); buffers are replaced)."""
+
+    def __init__(self, net: torch.nn.Module, optimizer=None, decay: float = 0.9998, warmup: bool = False, use_buffers: bool = False):
+        from torch.nn.parallel import DistributedDataParallel as DDP
+        decay = float(decay)
+        if not 0.0 <= decay <= 1.0:  # (NaN fails too)
+            raise ValueError(f"ModelEMA: decay must lie in [0, 1], got {decay!r}")
+        self.net = net.module if isinstance(net, DDP) else net
+        self.decay, self.warmup, self.use_buffers = decay, bool(warmup), bool(use_buffers)
+        # (owner module, key, is a buffer): the live tensor is looked up at every call
+        self._slots, self._names = [], []
+        seen = set()
+        for prefix, mod in self.net.named_modules():
+            kinds = [(mod._parameters, False)] + ([(mod._buffers, True)] if self.use_buffers else [])
+            for store, is_buf in kinds:
+                for key, t in store.items():
+                    if t is None or id(t) in seen or (is_buf and (not t.is_floating_point() or key in mod._non_persistent_buffers_set)):
+                        continue
+                    seen.add(id(t))
+                    self._slots.append(store)
+                    self._names.append((prefix + "." if prefix else "") + key)
+        self._keys = [n.rpartition(".")[2] for n in self._names]
+        live = self._live()
+        if not live:
+            raise ValueError("ModelEMA: the net has no parameters")
+        devices = {t.device for t in live}
+        for name, t in zip(self._names, live):
+            if t.dtype != torch.float32 or not t.is_cuda or t.layout != torch.strided:
+                raise ValueError(f"ModelEMA: {name} must be a dense fp32 tensor on the GPU, got {t.dtype} on {t.device}")
+            if not t.is_contiguous() and not (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)):
+                raise ValueError(f"ModelEMA: {name} must be dense (contiguous or channels_last)")
+        if len(devices) > 1:
+            raise ValueError(f"ModelEMA: all averaged tensors must be on one device, got {sorted(map(str, devices))}")
+        self.device = live[0].device
+        self.averages = {name: torch.empty_like(t, memory_format=torch.preserve_format) for name, t in zip(self._names, live)}
+        self.n_averaged = torch.zeros((), dtype=torch.int64, device=self.device)
+        self._filled = False  # known on the host to hold averages (n_averaged != 0); read from the device outside the step only
+        rows = np.zeros(len(live), dtype=_EMA_ROW)
+        rows["ema"] = [self.averages[n].data_ptr() for n in self._names]
+        rows["numel"] = [t.numel() for t in live]
+        self._rows = rows
+        self._tables: dict = {}  # one device table per entry point ("step", "update", "swap": their chunk lists differ)
+        self.optimizer = None
+        if optimizer is not None and is_device_optimizer(optimizer):
+            if optimizer._ema is not None and optimizer._ema is not self:
+                raise ValueError("ModelEMA: the optimizer already has an EMA attached")
+            optimizer._ema = self
+            self.optimizer = optimizer
+
+    def adopt_average(self, name: str, tensor: torch.Tensor) -> None:
+        """Keeps the average of `name` in `tensor` from now on, contents as they are: e.g. a view into one flat buffer that is
+        all-reduced or written out as a whole.  Dense fp32 on the EMA's device, with the averaged tensor's shape and strides."""
+        old = self.averages[name]
+        if (tensor.dtype != torch.float32 or tensor.device != old.device or tensor.shape != old.shape
+                or (tensor.stride() != old.stride() and old.numel() > 1)):
+            raise ValueError(f"ModelEMA.adopt_average: {name} needs an fp32 tensor of shape {tuple(old.shape)}, strides {old.stride()} on {old.device}")
+        self.averages[name] = tensor
+        self._rows["ema"][self._names.index(name)] = tensor.data_ptr()
+
+    def _live(self):
+        return [store[key] for store, key in zip(self._slots, self._keys)]
+
+    def _table(self, mode: str, T=None):
+        """-> (table record of `mode`, upload flag) with this call's pointers gathered; `T` is the optimizer's table record ("step")."""
+        rows = self._rows
+        E = self._tables.get(mode)
+        rebuild = E is None or E["of"] is not T
+        if mode == "step" and not rebuild:
+            # the step reads `value` only of the rows the optimizer does not step (its own rows carry the parameters' addresses)
+            for r in E["only"]:
+                rows["value"][r] = self._slots[r][self._keys[r]].data_ptr()
+        else:
+            # (like the optimizer's rows: checked when the step's table is built, and at every call outside the step)
+            live = self._live()
+            for name, t, numel in zip(self._names, live, rows["numel"]):
+                if t.numel() != numel or t.dtype != torch.float32 or t.device != self.device:
+                    raise ValueError(f"ModelEMA: {name} is now {tuple(t.shape)} {t.dtype} on {t.device}; the average was made for {int(numel)} "
+                                     f"fp32 elements on {self.device}")
+            rows["value"] = [t.data_ptr() for t in live]
+        if rebuild:
+            ntensors = len(T["rows"]) if T is not None else 0
+            lib = _lib.load()
+            nbytes = lib.hh_ema_table_bytes(rows.ctypes.data, len(rows), ntensors)
+            if nbytes < 0:
+                raise _lib.HHError(lib.hh_last_error().decode())
+            row_of = np.full(max(ntensors, 1), -1, dtype=np.int32)
+            if T is not None:  # a rebuilt optimizer table rebuilds the mapping
+                mine = {id(t): r for r, t in enumerate(live)}
+                row_of[:ntensors] = [mine.get(id(p), -1) for p in T["params"]]
+            named = set(row_of.tolist())
+            E = self._tables[mode] = dict(of=T, rows=rows, row_of=row_of, nbytes=nbytes, sent=None, sent_stream=None,
+                                          only=[r for r in range(len(rows)) if r not in named],
+                                          table=torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device))
+        stream = torch.cuda.current_stream(self.device)
+        if E["sent_stream"] != stream:
+            E["sent"], E["sent_stream"] = None, stream
+        E["pending"] = rows.tobytes()
+        return E, int(E["sent"] != E["pending"])
+
+    @staticmethod
+    def _sent(E, upload) -> None:
+        pending = E.pop("pending")
+        if upload:
+            E["sent"] = pending
+
+    @torch.no_grad()
+    def update(self, found_inf: torch.Tensor | None = None) -> None:
+        """The stand-alone update, one launch over every averaged tensor; with found_inf (fp32 device scalar) != 0 nothing is stored."""
+        E, upload = self._table("update")
+        found = _DeviceOptimizer._scalar_ptr(found_inf, "found_inf", self.device)
+        _lib.launch(self.device, _lib.load().hh_ema_update, E["rows"].ctypes.data, len(E["rows"]), self.decay, int(self.warmup),
+                    self.n_averaged.data_ptr(), found, E["table"].data_ptr(), E["nbytes"], upload)
+        self._sent(E, upload)
+
+    def _ensure_filled(self) -> None:
+        """Before any update the average IS the weights (AveragedModel starts as a copy).  The averages' storage is first written by
+        the n == 0 update; whoever looks at them earlier (swap, state_dict) gets that copy made here.  One host read of n_averaged per
+        call until it is non-zero; never from step() / update()."""
+        if not self._filled:
+            self._filled = bool(self.n_averaged.item() != 0)
+            if not self._filled:
+                with torch.no_grad():
+                    torch._foreach_copy_([self.averages[n] for n in self._names], [t.detach() for t in self._live()])
+
+    @torch.no_grad()
+    def swap(self) -> None:
+        """Exchanges the net's weights and their averages in place, one launch; twice is the identity, bit for bit.  The net is told
+        (mark_dirty) so that an inference engine folds the weights it now holds."""
+        self._ensure_filled()
+        E, upload = self._table("swap")
+        _lib.launch(self.device, _lib.load().hh_ema_swap, E["rows"].ctypes.data, len(E["rows"]), E["table"].data_ptr(), E["nbytes"], upload)
+        self._sent(E, upload)
+        if hasattr(self.net, "mark_dirty"):
+            self.net.mark_dirty()
+
+    @contextlib.contextmanager
+    def applied(self):
+        """`with ema.applied():` the net holds the averaged weights inside and its own again after."""
+        self.swap()
+        try:
+            yield self
+        finally:
+            self.swap()
+
+    def state_dict(self) -> dict:
+        self._ensure_filled()
+        model = {}
+        for name, t in self.net.state_dict().items():
+            avg = self.averages.get(name)
+            model[name] = avg if avg is not None else t.detach().clone()
+        return {"model": model, "n_averaged": self.n_averaged, "decay": self.decay, "warmup": self.warmup, "use_buffers": self.use_buffers}
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict: dict) -> None:
+        if bool(state_dict["use_buffers"]) != self.use_buffers:
+            raise ValueError(f"ModelEMA: the state dict was made with use_buffers={state_dict['use_buffers']!r}, this EMA with {self.use_buffers!r}")
+        decay = float(state_dict["decay"])
+        if not 0.0 <= decay <= 1.0:
+            raise ValueError(f"ModelEMA: decay must lie in [0, 1], got {decay!r}")
+        model = state_dict["model"]
+        missing = [n for n in self._names if n not in model]
+        if missing:
+            raise KeyError(f"ModelEMA: the state dict lacks the averages of {missing[:5]}{' ...' if len(missing) > 5 else ''}")
+        for name in self._names:
+            if tuple(model[name].shape) != tuple(self.averages[name].shape):
+                raise ValueError(f"ModelEMA: {name} has shape {tuple(model[name].shape)} in the state dict, {tuple(self.averages[name].shape)} here")
+        for name in self._names:
+            self.averages[name].copy_(model[name])
+        self.n_averaged.copy_(torch.as_tensor(state_dict["n_averaged"]).to(torch.int64).reshape(()))
+        self.decay, self.warmup = decay, bool(state_dict["warmup"])
+        self._filled = False
 
 
 # utils/optim.py:10-18 of the reference: the three with a kernel here, the other four torch's own
