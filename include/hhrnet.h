@@ -594,6 +594,82 @@ int hh_coco_evaluate(const hh_coco_tables *tables_dev, const hh_coco_tables *tab
                      unsigned char *gt_ignore, void *stream);
 int hh_coco_evaluate_host(const hh_coco_tables *tables_host, const double *oks_in, double *oks_out, int32_t *dt_match,
                           unsigned char *dt_ignore, unsigned char *gt_ignore);
+/* Pose tracking across video frames behind hh_decode (csrc/track.hip, csrc/track_math.h; keypoints/tracking.py PoseTracker): person ids
+ * that persist from frame to frame and One-Euro smoothed coordinates, one launch for a whole chunk of frames, on hh_decode's device
+ * outputs before they are copied anywhere.  An extension: the reference has no tracker (its video_processing_fn sorts people by mean
+ * tag and colours by limb).  (Additive entry points: HH_ABI_VERSION stays 3.)
+ *
+ * STREAMS AND FRAMES.  A call handles S independent streams of F consecutive frames each, stream-major: frame f of stream s is row
+ *   b = s * F + f of the decode's batch, B = S * F.  One workgroup per stream walks its frames in order; streams share nothing.
+ * STATE.  `state`: S * hh_track_state_bytes(K, max_tracks) bytes of device memory, 8-byte aligned, owned by the caller, opaque; stream s
+ *   owns the s-th block.  All zero = empty (hh_track_reset: one memset of nstreams consecutive blocks).  Per stream: the number of ids
+ *   issued (next_id - 1) and a frame counter; per slot: id (0 = free), hits, misses, the last matched raw pose xy[K] and score[K] as
+ *   floats, its box area, and xhat / dxhat of the filter per coordinate as doubles.  The kernel keeps the block in LDS during the frame
+ *   loop when it fits there next to the max_tracks x max_people similarity matrix and the frame's staged rows, in global memory otherwise (or when params.reserved
+ *   bit 0 is set: a test switch); the results are the same bits.
+ * INPUTS: hh_decode's outputs joints [B,max_people,K,3+E], scores [B,max_people], num_people [B], flags [B] (may be NULL = all 0).
+ *   Coordinates are model-input pixels.
+ * RULE for one frame of one stream, fp64 with every operation rounded on its own (compiled with -ffp-contract=off), joint scores and
+ *   thresholds compared as floats:
+ *   1. Row d < min(num_people, max_people) is VALID if scores[d] >= min_person_score, at least min_joints of its joints have
+ *      score > joint_thr, and neither HH_DECODE_FALLBACK nor HH_DECODE_SOLVER_GUARD is set in the frame's flags.  Every other row gets
+ *      id 0.  A frame with HH_DECODE_SOLVER_GUARD has no detections at all, and out_flags carries HH_TRACK_SOLVER_GUARD.
+ *   2. For each live track t (id != 0) and valid row d, over the joints k labelled in both (score > joint_thr in the track's last
+ *      matched pose and in the row), k ascending:
+ *        dx = (double)x_d - (double)x_t, dy likewise;  e_k = ((dx*dx + dy*dy) / vars[k]) / (area_t + 2^-52) / 2
+ *        S[t][d] = (sum of exp(-e_k)) / n_common if n_common >= min_common and n_common > 0, else 0
+ *      vars[k] = (2 sigma_k)^2 is the caller's.  area_t = (max x - min x) * (max y - min y) over the labelled joints of the row the
+ *      track last matched, in doubles, and 1 if that is below 1.  The track's pose is the last MATCHED RAW pose, neither filtered nor
+ *      predicted: matching does not depend on the smoothing.  All other entries of S are 0.
+ *   3. Greedy assignment, comparisons only: among the pairs with S >= min_oks whose track and row are both still free, take the one
+ *      with the largest S, then the lowest track id, then the lowest d; repeat until none is left.
+ *   4. A matched track: Te = (misses + 1) / fps, hits += 1, misses = 0, area from the row; per joint labelled in the row xy and score
+ *      are replaced, a joint unlabelled in the row keeps its xy with score 0.  An unmatched track: misses += 1, and it is freed when
+ *      misses > max_age.  Then the valid rows nobody matched, d ascending, open tracks in the free slots, lowest first (a slot freed in
+ *      this frame counts), with id = ++issued, hits 1, misses 0; ids start at 1 and are never reused within a stream.  Rows left over
+ *      keep id 0 and out_flags carries HH_TRACK_POOL_FULL.
+ *   5. One-Euro filter per coordinate x of every labelled joint of a matched row, pi = 3.141592653589793:
+ *        alpha(c) = 1.0 / (1.0 + (1.0 / ((2.0 * pi) * c)) / Te)
+ *        dx = (x - xhat) / Te;  dxhat = alpha(d_cutoff) * dx + (1.0 - alpha(d_cutoff)) * dxhat
+ *        c = min_cutoff + beta * fabs(dxhat);  xhat = alpha(c) * x + (1.0 - alpha(c)) * xhat
+ *      A joint labelled now that was not labelled at the track's previous match, and every joint of a track opened in this frame,
+ *      starts afresh: xhat = x, dxhat = 0.
+ * OUTPUTS (device): track_ids int32 [B,max_people] (0 = no track); smooth float [B,max_people,K,2] = xhat rounded once to fp32 for the
+ *   labelled joints of tracked rows, the row's raw x, y everywhere else; out_flags int32 [B].  Every element is written exactly once
+ *   per call; nothing but the state carries over between calls.  Deterministic.
+ * hh_track_step: the fused launch.  hh_track_step_host: the same code compiled for the host over HOST memory (state included).
+ * hh_track_similarity: only the S matrices, sim double [S,max_tracks,max_people], of ONE frame per stream (B = S) against the current
+ *   state, which is not changed.  hh_track_assign: only step 3 on n caller's matrices sim [n,T,P] (device) with ids int32 [n,T]
+ *   (0 = the row is no live track; the live ids of a matrix must be distinct) -> match int32 [n,T] = the row's d or -1;
+ *   hh_track_assign_host: the same over host memory.
+ * Each returns 1 with hh_last_error set, before any launch, for a null pointer (flags excepted), a state or sim pointer that is not
+ *   8-byte aligned, any other pointer that is not 4-byte aligned, K, max_tracks or max_people outside 1..64, E outside 0..64, negative
+ *   S, F, n, a vars entry that is not finite and > 0, a non-finite or non-positive fps, min_cutoff or d_cutoff, a negative or
+ *   non-finite beta, a negative max_age, min_joints or min_common, a min_oks outside (0, 1], a negative or non-finite joint_thr, a NaN
+ *   min_person_score.  */
+#define HH_TRACK_MAX_TRACKS 64
+#define HH_TRACK_MAX_K 64
+#define HH_TRACK_MAX_PEOPLE 64
+#define HH_TRACK_SOLVER_GUARD 2
+#define HH_TRACK_POOL_FULL 4
+typedef struct hh_track_params {
+    double vars[HH_TRACK_MAX_K];  /* the first K are read */
+    double fps, min_cutoff, beta, d_cutoff, min_oks;
+    float joint_thr, min_person_score;
+    int32_t K, E, max_people, max_tracks, max_age, min_joints, min_common;
+    int32_t reserved;             /* 0 (bit 0: keep the state in global memory) */
+} hh_track_params;
+int64_t hh_track_state_bytes(int K, int max_tracks);
+int hh_track_reset(void *state, int K, int max_tracks, int nstreams, void *stream);
+int hh_track_step(const hh_track_params *params, void *state, const float *joints, const float *scores, const int32_t *num_people,
+                  const int32_t *flags, int S, int F, int32_t *track_ids, float *smooth, int32_t *out_flags, void *stream);
+int hh_track_step_host(const hh_track_params *params, void *state, const float *joints, const float *scores, const int32_t *num_people,
+                       const int32_t *flags, int S, int F, int32_t *track_ids, float *smooth, int32_t *out_flags);
+int hh_track_similarity(const hh_track_params *params, void *state, const float *joints, const float *scores, const int32_t *num_people,
+                        const int32_t *flags, int S, double *sim, void *stream);
+int hh_track_assign(const double *sim, const int32_t *ids, int n, int T, int P, double min_oks, int32_t *match, void *stream);
+int hh_track_assign_host(const double *sim, const int32_t *ids, int n, int T, int P, double min_oks, int32_t *match);
+
 /* HeatmapGenerator (coco.py:77-121) as a gather over the packed joints the grouping loss takes (hh_loss_ae_grouping: joints int32
  * [B,P,K,3] = x, y, vis from JointsGenerator, coco.py:124-137; num_people [B]): out fp32 [B,K,h,w], each element the maximum over
  * the image's people p < num_people[b] with vis > 0 and (x, y) inside the map of table[y - y_p + reach][x - x_p + reach] where that

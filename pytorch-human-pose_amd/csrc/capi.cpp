@@ -14,6 +14,7 @@
 #include "panel_math.h"
 #include "coco_eval_math.h"
 #include "crowd_mask_math.h"
+#include "track_math.h"
 
 const char *hh_get_error();
 int hh_tap_read_impl(hh_net *n, int index, float *host);
@@ -506,6 +507,101 @@ int hh_coco_evaluate_host(const hh_coco_tables *tables_host, const double *oks_i
     if (!match && !oks_out) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
     if (coco_tables_check(fn, nullptr, tables_host)) return 1;
     coco_eval_host(*reinterpret_cast<const CocoTables *>(tables_host), oks_in, oks_in ? nullptr : oks_out, match, dt_match, dt_ignore, gt_ignore);
+    return 0;
+}
+
+// The checks of a tracking call: the parameter block (track_check) and the pointers.  Nothing behind a device pointer is read.
+static int track_args_check(const char *fn, const hh_track_params *params, const void *state, const float *joints, const float *scores,
+                            const int32_t *num_people, const int32_t *flags, int S, int F)
+{
+    static_assert(sizeof(hh_track_params) == sizeof(TrackParams), "parameter layout");
+    static_assert(HH_TRACK_MAX_TRACKS == TRACK_MAX_TRACKS && HH_TRACK_MAX_K == TRACK_MAX_K && HH_TRACK_MAX_PEOPLE == TRACK_MAX_PEOPLE &&
+                      HH_TRACK_SOLVER_GUARD == TRACK_SOLVER_GUARD && HH_TRACK_POOL_FULL == TRACK_POOL_FULL && HH_DECODE_FALLBACK == TRACK_DECODE_FALLBACK &&
+                      HH_DECODE_SOLVER_GUARD == TRACK_DECODE_SOLVER_GUARD,
+                  "limits and flags of include/hhrnet.h");
+    if (!params || !state || !joints || !scores || !num_people) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if ((uintptr_t)state % 8) { hh_set_error(std::string(fn) + ": state is not 8-byte aligned"); return 1; }
+    if ((uintptr_t)joints % 4 || (uintptr_t)scores % 4 || (uintptr_t)num_people % 4 || (uintptr_t)flags % 4) { hh_set_error(std::string(fn) + ": an input is not 4-byte aligned"); return 1; }
+    if (S < 0 || F < 0 || (int64_t)S * F > (1 << 24)) { hh_set_error(std::string(fn) + ": S and F must be >= 0 and S * F <= 2^24"); return 1; }
+    if (const char *why = track_check(reinterpret_cast<const TrackParams *>(params))) { hh_set_error(std::string(fn) + ": " + why); return 1; }
+    return 0;
+}
+static int track_outputs_check(const char *fn, const int32_t *track_ids, const float *smooth, const int32_t *out_flags)
+{
+    if (!track_ids || !smooth || !out_flags) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if ((uintptr_t)track_ids % 4 || (uintptr_t)smooth % 4 || (uintptr_t)out_flags % 4) { hh_set_error(std::string(fn) + ": an output is not 4-byte aligned"); return 1; }
+    return 0;
+}
+static int track_assign_check(const char *fn, const double *sim, const int32_t *ids, int n, int T, int P, double min_oks, const int32_t *match)
+{
+    if (!sim || !ids || !match) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if ((uintptr_t)sim % 8 || (uintptr_t)ids % 4 || (uintptr_t)match % 4) { hh_set_error(std::string(fn) + ": sim must be 8-byte, ids and match 4-byte aligned"); return 1; }
+    if (n < 0 || n > (1 << 24)) { hh_set_error(std::string(fn) + ": n outside 0..2^24"); return 1; }
+    if (T < 1 || T > TRACK_MAX_TRACKS || P < 1 || P > TRACK_MAX_PEOPLE) { hh_set_error(std::string(fn) + ": T and P must lie in 1..64"); return 1; }
+    if (!(min_oks > 0.0) || !(min_oks <= 1.0)) { hh_set_error(std::string(fn) + ": min_oks outside (0, 1]"); return 1; }
+    return 0;
+}
+
+int64_t hh_track_state_bytes(int K, int max_tracks)
+{
+    if (K < 1 || K > TRACK_MAX_K || max_tracks < 1 || max_tracks > TRACK_MAX_TRACKS) { hh_set_error("hh_track_state_bytes: K and max_tracks must lie in 1..64"); return -1; }
+    return track_state_bytes(K, max_tracks);
+}
+
+int hh_track_reset(void *state, int K, int max_tracks, int nstreams, void *stream)
+{
+    const char *fn = "hh_track_reset";
+    if (!state) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if ((uintptr_t)state % 8) { hh_set_error(std::string(fn) + ": state is not 8-byte aligned"); return 1; }
+    if (K < 1 || K > TRACK_MAX_K || max_tracks < 1 || max_tracks > TRACK_MAX_TRACKS || nstreams < 0 || nstreams > (1 << 24)) {
+        hh_set_error(std::string(fn) + ": K and max_tracks must lie in 1..64, nstreams in 0..2^24");
+        return 1;
+    }
+    if (nstreams) HH_CHECK_HIP(hipMemsetAsync(state, 0, (size_t)nstreams * track_state_bytes(K, max_tracks), (hipStream_t)stream));
+    return 0;
+}
+
+int hh_track_step(const hh_track_params *params, void *state, const float *joints, const float *scores, const int32_t *num_people, const int32_t *flags, int S,
+                  int F, int32_t *track_ids, float *smooth, int32_t *out_flags, void *stream)
+{
+    const char *fn = "hh_track_step";
+    if (track_outputs_check(fn, track_ids, smooth, out_flags) || track_args_check(fn, params, state, joints, scores, num_people, flags, S, F)) return 1;
+    HH_CHECK_HIP(launch_track_step(*reinterpret_cast<const TrackParams *>(params), state, joints, scores, num_people, flags, S, F, track_ids, smooth, out_flags,
+                                   (hipStream_t)stream));
+    return 0;
+}
+
+int hh_track_step_host(const hh_track_params *params, void *state, const float *joints, const float *scores, const int32_t *num_people, const int32_t *flags,
+                       int S, int F, int32_t *track_ids, float *smooth, int32_t *out_flags)
+{
+    const char *fn = "hh_track_step_host";
+    if (track_outputs_check(fn, track_ids, smooth, out_flags) || track_args_check(fn, params, state, joints, scores, num_people, flags, S, F)) return 1;
+    track_step_host(*reinterpret_cast<const TrackParams *>(params), state, joints, scores, num_people, flags, S, F, track_ids, smooth, out_flags);
+    return 0;
+}
+
+int hh_track_similarity(const hh_track_params *params, void *state, const float *joints, const float *scores, const int32_t *num_people, const int32_t *flags,
+                        int S, double *sim, void *stream)
+{
+    const char *fn = "hh_track_similarity";
+    if (!sim) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if ((uintptr_t)sim % 8) { hh_set_error(std::string(fn) + ": sim is not 8-byte aligned"); return 1; }
+    if (track_args_check(fn, params, state, joints, scores, num_people, flags, S, 1)) return 1;
+    HH_CHECK_HIP(launch_track_similarity(*reinterpret_cast<const TrackParams *>(params), state, joints, scores, num_people, flags, S, sim, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_track_assign(const double *sim, const int32_t *ids, int n, int T, int P, double min_oks, int32_t *match, void *stream)
+{
+    if (track_assign_check("hh_track_assign", sim, ids, n, T, P, min_oks, match)) return 1;
+    HH_CHECK_HIP(launch_track_assign(sim, ids, n, T, P, min_oks, match, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_track_assign_host(const double *sim, const int32_t *ids, int n, int T, int P, double min_oks, int32_t *match)
+{
+    if (track_assign_check("hh_track_assign_host", sim, ids, n, T, P, min_oks, match)) return 1;
+    for (int m = 0; m < n; ++m) track_assign_host(sim + (size_t)m * T * P, ids + (size_t)m * T, T, P, min_oks, match + (size_t)m * T, nullptr);
     return 0;
 }
 

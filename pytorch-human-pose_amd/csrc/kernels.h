@@ -376,6 +376,16 @@ struct CocoTables;
 hipError_t launch_coco_eval(int mode, const CocoTables &dev, const double *oks_in, double *oks_out, int32_t *dt_match, uint8_t *dt_ignore, uint8_t *gt_ignore,
                             hipStream_t s);
 void coco_eval_host(const CocoTables &t, const double *oks_in, double *oks_out, bool match, int32_t *dt_match, uint8_t *dt_ignore, uint8_t *gt_ignore);
+// Pose tracking across frames (hh_track_params of include/hhrnet.h; struct, state layout and per-slot / per-joint code in track_math.h, kernels in
+// track.hip): S streams of F frames in one launch; the similarity matrices alone; the greedy assignment alone on n matrices; the step on the host.
+struct TrackParams;
+hipError_t launch_track_step(const TrackParams &p, void *state, const float *joints, const float *scores, const int32_t *num_people, const int32_t *flags, int S,
+                             int F, int32_t *track_ids, float *smooth, int32_t *out_flags, hipStream_t s);
+hipError_t launch_track_similarity(const TrackParams &p, void *state, const float *joints, const float *scores, const int32_t *num_people, const int32_t *flags,
+                                   int S, double *sim, hipStream_t s);
+hipError_t launch_track_assign(const double *sim, const int32_t *ids, int n, int T, int P, double min_oks, int32_t *match, hipStream_t s);
+void track_step_host(const TrackParams &p, void *state, const float *joints, const float *scores, const int32_t *num_people, const int32_t *flags, int S, int F,
+                     int32_t *track_ids, float *smooth, int32_t *out_flags);
 // Crowd masks from toggle lists (hh_crowd_mask_desc / hh_crowd_seg_desc of include/hhrnet.h; structs, predicate, tile walk and the host's
 // polygon walk in crowd_mask_math.h, kernel in crowd_mask.hip): n masks in one launch, `max_tiles` = the largest mask's tile count.
 struct CrowdMaskDesc;

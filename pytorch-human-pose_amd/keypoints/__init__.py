@@ -5,7 +5,8 @@ from .results import InferenceKeypointsResult, KeypointsResult
 
 __all__ = ["HigherHRNet", "MPPEHeatmapParser", "InferenceKeypointsModel", "InferenceKeypointsResult", "KeypointsModel", "KeypointsModule"]
 from .loss import AEGroupingLoss, AEKeypointsLoss, HeatmapsLoss
-from . import coco_eval, crowd_mask, evaluation, targets
+from . import coco_eval, crowd_mask, evaluation, targets, tracking
 from .crowd_mask import CrowdSegments, crowd_masks, get_crowd_mask, raw_sample
 from .train_input import Mosaic, TrainInput, mosaic_joints
+from .tracking import PoseTracker
 from .visualization import DEFAULT_PALETTE, build_primitives, jet_lut, plot_connections, plot_heatmaps

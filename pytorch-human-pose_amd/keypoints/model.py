@@ -481,7 +481,7 @@ class InferenceKeypointsModel:
 
     @torch.no_grad()
     def infer_images(self, raw_images: list[np.ndarray], annots: list | None = None, max_batch: int = 32,
-                     scales=None, render: dict | None = None) -> list[InferenceKeypointsResult]:
+                     scales=None, render: dict | None = None, tracker=None) -> list[InferenceKeypointsResult]:
         """The batched path behind the reference's single-image interface (`__call__` per image, bin/eval.py:18-49): images are
         bucketed by model-input shape, every bucket runs as batches of up to `max_batch` -- ONE host->device copy of the raw
         uint8 pixels, hh_preprocess_u8 per image into one [B,3,h,w] tensor, one (flip-TTA) forward, one hh_decode, one
@@ -496,7 +496,15 @@ class InferenceKeypointsModel:
         overlay frame of `result.plot_connections(color_mode, alpha)` (B,G,R order if `bgr`; resized to `out_height` with the aspect
         ratio kept, as the reference's resize_with_aspect_ratio, if given).  The frames of a batch are drawn in ONE
         hh_render_poses_u8_batch from the staged device pixels of that batch, which stay alive until then; with render=None nothing
-        of the pipeline changes."""
+        of the pipeline changes.  color_mode="track" (needs `tracker`) draws the smoothed coordinates, each person in the colour of its id.
+        `tracker` = a keypoints.tracking.PoseTracker with one stream: `raw_images` are consecutive frames of ONE clip.  All must share
+        one model-input shape (else ValueError, before any launch) and that of the frames the tracker saw before (else reset() it).  The
+        chunks are fed in order, each as one hh_track_step behind its hh_decode on the same stream with frames_per_stream = the chunk
+        length; ids and smoothed coordinates come back in the batch's one device->host hand-over.  Every result gains `.track_ids`
+        (int32 [P], 0 = no track) and `.kpts_coords_smooth` ([P,K,2], raw-image pixels), aligned with its rows.  With tracker=None
+        nothing of the pipeline changes."""
+        if render is not None and render.get("color_mode") == "track" and tracker is None:
+            raise ValueError("infer_images: render color_mode 'track' needs a tracker")
         if render is not None:
             unknown = set(render) - {"color_mode", "alpha", "bgr", "out_height"}
             if unknown:
@@ -521,6 +529,13 @@ class InferenceKeypointsModel:
             for c in plan:
                 jobs.setdefault(c["sizes"], []).append((c["images"], c["sub_batches"]))
         i1 = pass_scales.index(1)
+        if tracker is not None and n:
+            if tracker.streams != 1:
+                raise ValueError("infer_images: the tracker must have one stream (the images are one clip)")
+            shapes = {tuple(sizes[i1]) for sizes in jobs}
+            if len(shapes) != 1:
+                raise ValueError(f"infer_images: the frames of a tracked clip must share one model-input shape, got (w, h) = {sorted(shapes)}")
+            tracker.bind_input_shape(next(iter(shapes))[::-1])
         results: list = [None] * n
         mean, std = IMAGENET_MEAN.ctypes.data, IMAGENET_STD.ctypes.data
 
@@ -528,7 +543,7 @@ class InferenceKeypointsModel:
             """device -> host results of one enqueued batch, un-warp, result objects"""
             chunk, (w, h), x, hms, tags, host_out, done, staged = job
             done.synchronize()
-            lists = self._parser.to_lists(*host_out)  # (copies what it returns: the pinned buffers are reused two batches later)
+            lists = self._parser.to_lists(*host_out[:4])  # (copies what it returns: the pinned buffers are reused two batches later)
             self.model_input_shape = (h, w)
             for j, i in enumerate(chunk):
                 joints, scores = lists[j]
@@ -536,6 +551,10 @@ class InferenceKeypointsModel:
                 results[i] = InferenceKeypointsResult(raw_images[i], annots[i], x[j], coords, joints[..., 2], joints[..., 3:], scores,
                                                       self.det_thr, self.tag_thr, self.limbs, [t[j:j + 1] for t in hms],
                                                       [t[j:j + 1] for t in tags])
+                if tracker is not None:
+                    p = len(joints)
+                    results[i].track_ids = host_out[4][j, :p].numpy().copy()
+                    results[i].kpts_coords_smooth = transform_coords(host_out[5][j, :p].numpy(), geo[i][1], geo[i][2], (w, h)).astype(coords.dtype)
             if staged is not None:
                 self._render_chunk([results[i] for i in chunk], *staged, **render)
 
@@ -593,6 +612,8 @@ class InferenceKeypointsModel:
                     x = prepare(i1)
                     hms, tags = self.forward_tta(x) if subs is None else self._multi_scale_maps_batch(pass_scales, subs, x, prepare)
                     out = self._parser.decode_batch_device(hms[0], hms[1], tags, adjust=True, refine=True)
+                    if tracker is not None:
+                        out = out + tracker.update_device(*out, frames_per_stream=nb)[:2]
                     # device -> host into pinned buffers kept per pipeline slot (allocating pinned memory costs ~0.4 ms per array);
                     # finish() of this slot's previous batch ran before this point and copied what it keeps
                     key = (turn, tuple((tuple(t.shape), t.dtype) for t in out))
@@ -634,7 +655,9 @@ class InferenceKeypointsModel:
         frames, tables = [], []
         for j, r in enumerate(results):
             frames.append(raw[int(offs[j]):int(offs[j + 1])].view(r.raw_image.shape))
-            tables.append(vz.build_primitives(r.kpts_coords, r.kpts_scores, r.limbs, r.det_thr, color_mode, vz.DEFAULT_PALETTE, alpha))
+            by_id = color_mode == "track"
+            tables.append(vz.build_primitives(r.kpts_coords_smooth if by_id else r.kpts_coords, r.kpts_scores, r.limbs, r.det_thr, color_mode,
+                                              vz.DEFAULT_PALETTE, alpha, ids=r.track_ids if by_id else None))
         out = vz.render_frames_device(frames, tables, alpha, bgr)
         if out_height is not None:
             out = [f if f.shape[0] == out_height else vz.resize_device(f, int(out_height * f.shape[1] / f.shape[0]), out_height) for f in out]
@@ -647,17 +670,48 @@ class InferenceKeypointsModel:
         for j, (r, f) in enumerate(zip(results, out)):
             r.rendered = hv[int(sizes[j]):int(sizes[j + 1])].reshape(tuple(f.shape)).copy()
 
-    def video_frame(self, image: np.ndarray):
+    def _call_tracked(self, raw_image: np.ndarray, tracker) -> InferenceKeypointsResult:
+        """`self(raw_image, None)` with one hh_track_step behind the decode on the same stream (one frame of the tracker's one stream)."""
+        if tracker.streams != 1:
+            raise ValueError("video_frame: the tracker must have one stream")
+        size = get_multi_scale_size(raw_image, self.input_size, 1, 1)[0]
+        tracker.bind_input_shape((size[1], size[0]))  # (raises before any launch)
+
+        def run():
+            x, center, scale = self.prepare_input(raw_image)
+            h, w = self.model_input_shape = tuple(x.shape[-2:])
+            hms, tags = self.forward_tta(x)
+            out = self._parser.decode_batch_device(hms[0], hms[1], tags, adjust=True, refine=True)
+            ids, smooth, _ = tracker.update_device(*out, frames_per_stream=1)
+            joints, scores = self._parser.to_lists(*out)[0]
+            p = len(joints)
+            coords = transform_coords(joints[..., :2], center, scale, (w, h))
+            result = InferenceKeypointsResult(raw_image, None, x[0], coords, joints[..., 2], joints[..., 3:], scores, self.det_thr, self.tag_thr,
+                                              self.limbs, hms, tags)
+            result.track_ids = ids[0, :p].cpu().numpy()
+            result.kpts_coords_smooth = transform_coords(smooth[0, :p].cpu().numpy(), center, scale, (w, h)).astype(coords.dtype)
+            return result
+        return self._on_fast_stream(run)
+
+    def video_frame(self, image: np.ndarray, tracker=None):
         """`video_processing_fn` (keypoints/bin/inference.py:49-75) without its text labels -> (result, out_frame): one inference,
         the people ordered by their mean tag (same colours for the same person from frame to frame), limb colours at alpha 0.65 with
         thr = det_thr, B,G,R order, resized to height 640 (new_w = int(640 * w / h); no resize launch when h == 640).  The frame is
         drawn from the uint8 pixels prepare_input already put on the device: the raw image crosses PCIe once, the finished frame
-        comes back through one pinned buffer."""
+        comes back through one pinned buffer.
+        `tracker` = a keypoints.tracking.PoseTracker with one stream (an extension): the frame is the next one of the tracker's clip; the
+        result carries `.track_ids` and `.kpts_coords_smooth` (see infer_images) and the overlay draws the smoothed coordinates, every
+        person in the colour of its id (color_mode "track") instead of the tag order and the limb colours."""
         from . import visualization as vz
-        result = self(image, None)
+        if tracker is not None:
+            result = self._call_tracked(image, tracker)
+            table = vz.build_primitives(result.kpts_coords_smooth, result.kpts_scores, result.limbs, result.det_thr, "track", vz.DEFAULT_PALETTE, 0.65,
+                                        ids=result.track_ids)
+        else:
+            result = self(image, None)
+            order = np.argsort(result.kpts_tags.mean(axis=1)[:, 0])
+            table = vz.build_primitives(result.kpts_coords[order], result.kpts_scores[order], result.limbs, result.det_thr, "limb", vz.DEFAULT_PALETTE, 0.65)
         raw = self._keep_raw  # uint8 [h,w,3] on the device (prepare_input)
-        order = np.argsort(result.kpts_tags.mean(axis=1)[:, 0])
-        table = vz.build_primitives(result.kpts_coords[order], result.kpts_scores[order], result.limbs, result.det_thr, "limb", vz.DEFAULT_PALETTE, 0.65)
         frame = vz.render_frames_device([raw], [table], 0.65, bgr=True)[0]
         h, w = raw.shape[:2]
         if h != 640:

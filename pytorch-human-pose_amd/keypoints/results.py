@@ -95,6 +95,8 @@ class InferenceKeypointsResult:
     _stage_hms: list | None = None
     _tags: list | None = None
     rendered: np.ndarray | None = None  # infer_images(render=...): the finished overlay frame
+    track_ids: np.ndarray | None = None  # with a PoseTracker: int32 [P], 0 = no track
+    kpts_coords_smooth: np.ndarray | None = None  # with a PoseTracker: [P,K,2] raw-image pixels, One-Euro filtered
 
     @classmethod
     def from_preds(cls, raw_image, annot, model_input_image: Tensor, kpts_heatmaps: list[Tensor], tags_heatmaps: list[Tensor],

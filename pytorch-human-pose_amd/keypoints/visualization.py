@@ -79,16 +79,26 @@ def table_of(rows: list) -> np.ndarray:
     return table
 
 
-def build_primitives(coords, scores, limbs, thr, color_mode, palette=DEFAULT_PALETTE, alpha: float = 0.8, return_direction: bool = False):
+def build_primitives(coords, scores, limbs, thr, color_mode, palette=DEFAULT_PALETTE, alpha: float = 0.8, return_direction: bool = False, ids=None):
     """The primitive table of one frame in draw order (structured array of hh_render_prim): numpy only, float64 / int64.
     coords [P,K,2] (x, y), scores [P,K] or [P,K,1]; `limbs` may be None (keypoints only).  `alpha` is only checked (the weights
     belong to the frame's descriptor: blend_weights).  Raises where the reference would raise (a palette shorter than needed) and
     where the table cannot express the frame (a coordinate beyond +-2^23, an axis or radius beyond 32767).
-    `return_direction`: also the float64 (c, s) of every row before its one rounding to fp32 ([N,2]; (1, 0) for discs and rings)."""
+    `return_direction`: also the float64 (c, s) of every row before its one rounding to fp32 ([N,2]; (1, 0) for discs and rings).
+    color_mode "track" (an extension, keypoints/tracking.py): `ids` [P] are the people's track ids; a person is drawn like in "person"
+    mode but in palette row (id - 1) % len(palette), whatever its row, and a person with id 0 is not drawn."""
     blend_weights(alpha)
-    if color_mode not in ("person", "limb"):
-        raise ValueError(f"color_mode {color_mode!r} is not 'person' or 'limb'")
+    if color_mode not in ("person", "limb", "track"):
+        raise ValueError(f"color_mode {color_mode!r} is not 'person', 'limb' or 'track'")
     coords = np.asarray(coords, dtype=np.float64)
+    if color_mode == "track":
+        if ids is None:
+            raise ValueError("color_mode 'track' needs ids")
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        if len(ids) != len(coords):
+            raise ValueError(f"{len(ids)} ids for {len(coords)} people")
+        tracked = ids != 0
+        coords, scores, ids = coords[tracked], np.asarray(scores, dtype=np.float64).reshape(len(ids), -1)[tracked], ids[tracked]
     P = len(coords)
     if P == 0:
         return (np.zeros(0, PRIM), np.zeros((0, 2))) if return_direction else np.zeros(0, PRIM)
@@ -99,7 +109,7 @@ def build_primitives(coords, scores, limbs, thr, color_mode, palette=DEFAULT_PAL
         raise ValueError("non-finite keypoint coordinate")
     palette = np.asarray(palette)
     limbs = list(limbs) if limbs is not None else []
-    need = P if color_mode == "person" else max(len(limbs), K)
+    need = P if color_mode == "person" else 1 if color_mode == "track" else max(len(limbs), K)
     if len(palette) < need:
         raise IndexError(f"palette of {len(palette)} colours, {need} needed")
     xy = np.trunc(coords)  # int(): toward zero
@@ -117,7 +127,7 @@ def build_primitives(coords, scores, limbs, thr, color_mode, palette=DEFAULT_PAL
     dirs = np.zeros((P, L + 2 * K, 2))
     dirs[..., 0] = 1.0
     keep = np.zeros((P, L + 2 * K), bool)
-    person = np.arange(P)[:, None]
+    person = np.arange(P)[:, None] if color_mode != "track" else ((ids - 1) % len(palette))[:, None]
     if L:
         k0, k1 = np.array(limbs, np.int64).reshape(L, 2).T
         x1, y1, x2, y2 = xy[:, k0, 0], xy[:, k0, 1], xy[:, k1, 0], xy[:, k1, 1]
@@ -141,7 +151,7 @@ def build_primitives(coords, scores, limbs, thr, color_mode, palette=DEFAULT_PAL
         cx, cy = (x1 + x2) // 2, (y1 + y2) // 2  # floor division
         e = full[:, :L]
         e["cx"], e["cy"], e["A"], e["B"], e["c"], e["s"], e["kind"] = cx, cy, 2 * a + 1, 2 * b + 1, c32, s32, ELLIPSE
-        e["rgb"] = palette[person if color_mode == "person" else np.arange(L)[None, :], :3] + np.zeros((P, L, 1), np.uint8)
+        e["rgb"] = palette[person if color_mode != "limb" else np.arange(L)[None, :], :3] + np.zeros((P, L, 1), np.uint8)
         e["box"] = _boxes(cx, cy, ex, ey)
         dirs[:, :L, 0], dirs[:, :L, 1] = c, s
         keep[:, :L] = valid
@@ -150,7 +160,7 @@ def build_primitives(coords, scores, limbs, thr, color_mode, palette=DEFAULT_PAL
         radius = (size + ring)[:, None] + np.zeros((P, K), np.int64)
         k["cx"], k["cy"], k["A"], k["B"], k["c"], k["kind"] = xy[..., 0], xy[..., 1], radius, radius, 1.0, RING if ring else DISC
         if not ring:
-            k["rgb"] = palette[person if color_mode == "person" else np.arange(K)[None, :], :3] + np.zeros((P, K, 1), np.uint8)
+            k["rgb"] = palette[person if color_mode != "limb" else np.arange(K)[None, :], :3] + np.zeros((P, K, 1), np.uint8)
         k["box"] = _boxes(xy[..., 0], xy[..., 1], radius, radius)
         keep[:, L + ring::2] = drawn
     table = np.ascontiguousarray(full[keep])
