@@ -532,6 +532,81 @@ int hh_debug_heatmap_panels_host(const hh_panel_map *maps, int n, const unsigned
 int hh_unnormalize_u8(const float *x_chw, int H, int W, const double mean[3], const double stdv[3], unsigned char *out_hwc, void *stream);
 int hh_resize_u8_scaled(const unsigned char *src, int h, int w, int channels, double fx, double fy, unsigned char *dst, int H, int W,
                         void *stream);
+/* Baseline JPEG on the device: the files the reference's video and directory paths end in (cv2.VideoWriter "MJPG",
+ * src/base/datasets/video.py:93-106; the .jpg plots of src/base/datasets/base.py:140 and src/base/callbacks.py:234,371), for n rendered
+ * frames or figures of mixed sizes, qualities and subsamplings in ONE call of three launches.  The frames leave the GPU compressed.
+ * tests/jpeg_ref.py restates the rule in numpy; device, host (hh_debug_jpeg_encode_host) and numpy agree byte for byte, because
+ * everything below is integer arithmetic.  `>>` is a floor shift, `/` truncates.
+ *
+ * Input: a uint8 image [h,w,3], `pitch` bytes between rows, R,G,B or (flags bit 0) B,G,R: the flag swaps the channels on read, the
+ *   stream always holds the true colours.  1 <= h, w <= 65535.
+ * Output: one baseline sequential JFIF stream (SOF0, 8 bit, 3 components, Huffman).
+ * 1. Padding to a multiple of the MCU (16 x 16 for subsampling 420, 8 x 8 for 444) by repeating the last row and column.
+ * 2. Colour (libjpeg's 16-bit fixed point):  Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *                                            Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *                                            Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16
+ * 3. 4:2:0 chroma: (a + b + c + d + 2) >> 2 over each 2 x 2 group (this project's rule; libjpeg alternates its bias).
+ * 4. FDCT on s = sample - 128 with T[u][x] = round(2^14 c(u) cos((2x + 1) u pi / 16)), c(0) = sqrt(1/8), c(u) = 1/2 otherwise (row 0
+ *    is all 5793; the other magnitudes are 8035 6811 4551 1598 for odd u, 7568 3135 for u = 2, 6, and 5793 for u = 4):
+ *    rows A[y][u] = (sum_x s[y][x] T[u][x] + 1024) >> 11, columns F[v][u] = sum_y A[y][u] T[v][y] = the coefficient times 2^17.
+ *    Bound: |s| <= 128 and the largest row sum of |T| is 8 * 5793 = 46344 (46344, 41990, 42812, 41990, 46344, ... for u = 0, 1, 2, ...),
+ *    so |A| <= (46344 * 128 + 1024) >> 11 = 2897 and |F| <= 2897 * 46344 = 134258568 < 2^27.1: both inside int32.  (Measured over the
+ *    sign-pattern inputs that maximise each coefficient: |A| <= 2896.)
+ * 5. Quantisation: q = sign(F) ((|F| + (Q << 16)) / (Q << 17)): to nearest, half away from zero.  Q = clamp((base scale + 50) / 100,
+ *    1, 255) with base from the Annex K luminance table (component 1) or chrominance table (components 2, 3) and libjpeg's scale =
+ *    5000 / quality below quality 50, 200 - 2 quality from there on; quality 1..100.  Then AC is clamped to +-1023 and DC to
+ *    -1024..1023: a guard (the sign patterns reach |AC| = 1020 and DC = -1024 at Q = 1).
+ * 6. Entropy coding: zigzag order, the four Annex K Huffman tables, DC as the difference to the previous block of the same component,
+ *    ZRL for zero runs above 15, EOB unless coefficient 63 is non-zero.  The restart interval is one MCU row (DRI = MCUs per row):
+ *    every interval starts with DC predictions 0, is padded with 1-bits to a byte and byte-stuffed (FF -> FF 00), and each but the last
+ *    is followed by RSTm, m = row & 7.  Intervals are independent and byte aligned: that is what makes the stream parallel.
+ * 7. Segments: SOI; APP0 (JFIF 1.01, units 0, density 1:1, no thumbnail); DQT table 0, DQT table 1 (zigzag order); SOF0 (component 1
+ *    sampling 2x2 or 1x1 with Tq 0, components 2 and 3 1x1 with Tq 1); DHT DC0, DC1, AC0, AC1; DRI; SOS (component 1 tables 0/0,
+ *    components 2 and 3 tables 1/1, Ss 0, Se 63, Ah/Al 0); the intervals; EOI.  The header is 629 bytes.
+ * Stated deviations from libjpeg: the chroma bias of step 3, the FDCT's own rounding (step 4), the restart intervals.  Any baseline
+ *   decoder reads the stream; byte parity with libjpeg or cv2.imwrite is not a goal.
+ *
+ * The size bound.  One block costs at most 22 + 63 * 26 = 1660 bits: a DC code of at most 11 bits with 11 value bits, and 63 non-zero
+ *   AC coefficients of at most 16 code bits and 10 value bits each (a zero never costs more: a ZRL of at most 11 bits stands for 16 of
+ *   them, the EOB of at most 4 bits needs one).  An interval of nblk blocks (6 per MCU in 420, 3 in 444) therefore has at most
+ *   2 * ceil(1660 nblk / 8) bytes, every byte stuffed, and hh_jpeg_bound = 629 + rows * (2 * ceil(1660 nblk / 8) + 2), the 2 being the
+ *   RSTm or EOI.  Every buffer is sized by it: the LDS bit buffer of the entropy kernel holds 64 blocks at 1660 bits, the workspace one
+ *   slot of the interval's bound per interval, the output hh_jpeg_bound per frame.  Nothing is sized by typical content.
+ *
+ * hh_jpeg_bound / hh_jpeg_workspace_bytes: the bytes of output capacity and of workspace (a multiple of 16) one h x w frame needs;
+ *   -1 with hh_last_error set for a size outside 1..65535 or a subsampling other than 420 or 444.
+ * hh_jpeg_quant_tables: out[2][64] = the luminance and chrominance divisors at `quality`, in zigzag order.
+ * hh_jpeg_config: out[4] = blocks per pass of the entropy kernel (one wave per interval, one lane per block), the per-block bound in
+ *   bits, the header's bytes, MCUs per workgroup of the transform kernel (a wave each).
+ * hh_jpeg_encode_u8_batch: one hh_jpeg_desc of 64 bytes per frame.  Source and stream lie at batch_base + src_offset and batch_base +
+ *   out_offset (one base for both, never dereferenced itself), the frame's scratch at workspace + ws_offset (a multiple of 16;
+ *   hh_jpeg_workspace_bytes of room; no clearing needed, nothing is carried from call to call).  lengths_dev[i] receives the stream's
+ *   length, at most the bound.  Bytes beyond the length are not written.  Deterministic.  descs_dev is what the kernels read, descs_host
+ *   the caller's HOST copy of the same rows, and that is what is checked (device memory is never read back).  Returns 1 with
+ *   hh_last_error set, before any launch, for a null pointer, n outside 1..65535, a misaligned descs_dev (8), workspace (16) or
+ *   lengths_dev (4), h or w outside 1..65535, "quality outside 1..100", "subsampling must be 420 or 444", "pitch below 3 * w", an unknown
+ *   flag, "output capacity below hh_jpeg_bound", a bound beyond int32, a negative offset, a frame whose scratch does not lie inside
+ *   workspace_bytes.  That frames and streams lie inside the caller's buffer cannot be checked here.
+ * hh_debug_jpeg_encode_host: the same rule (csrc/jpeg_math.h) in plain C++ on one frame in HOST memory (src and out are the frame's
+ *   own buffers; the descriptor's offsets are not applied); same validation.  For tests, tools/jpeg_host_check.cpp, and as the
+ *   yardstick of the GPU tests.
+ * hh_debug_jpeg_fdct: step 4 alone on one block of samples (absolute sum at most 8192 = 64 * 128, which keeps F inside int32): rows_out = A, cols_out = F,
+ *   both [8][8] in natural order.
+ * (Additive entry points: HH_ABI_VERSION stays 3.)                                                                           */
+typedef struct hh_jpeg_desc {
+    long long src_offset, out_offset, out_capacity, ws_offset, pitch;
+    int32_t h, w;
+    int32_t quality, subsampling;
+    int32_t flags, reserved;
+} hh_jpeg_desc;
+long long hh_jpeg_bound(int h, int w, int subsampling);
+long long hh_jpeg_workspace_bytes(int h, int w, int subsampling);
+int hh_jpeg_quant_tables(int quality, int32_t out[128]);
+int hh_jpeg_config(int out[4]);
+int hh_jpeg_encode_u8_batch(unsigned char *batch_base, const hh_jpeg_desc *descs_dev, const hh_jpeg_desc *descs_host, int n,
+                            unsigned char *workspace, long long workspace_bytes, int32_t *lengths_dev, void *stream);
+int hh_debug_jpeg_encode_host(const unsigned char *src, const hh_jpeg_desc *desc, unsigned char *out, long long *length);
+int hh_debug_jpeg_fdct(const int32_t samples[64], int32_t rows_out[64], int32_t cols_out[64]);
 /* COCO keypoint scoring on the device: computeOks + evaluateImg of pycocotools' COCOeval(iouType="keypoints") as keypoints/coco_eval.py
  * restates them (`_oks`, `_evaluate_img`; the `eval_coco` step of keypoints/bin/eval.py:52-65), for every image, area range and threshold
  * in ONE launch over packed tables.  What is pinned is "device = this repository's host evaluator"; parity with pycocotools itself stays

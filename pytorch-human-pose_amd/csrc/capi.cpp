@@ -1,4 +1,5 @@
 // extern "C" surface declared in include/hhrnet.h (network part).
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -15,6 +16,7 @@
 #include "coco_eval_math.h"
 #include "crowd_mask_math.h"
 #include "track_math.h"
+#include "jpeg_math.h"
 
 const char *hh_get_error();
 int hh_tap_read_impl(hh_net *n, int index, float *host);
@@ -350,6 +352,98 @@ int hh_debug_render_host(const unsigned char *src, unsigned char *dst, const hh_
     RenderDesc d = *reinterpret_cast<const RenderDesc *>(desc);  // src and dst are the frame's own buffers here
     d.src_offset = d.dst_offset = 0;
     render_debug_host(src, dst, d, reinterpret_cast<const RenderPrim *>(prims));
+    return 0;
+}
+
+// Baseline JPEG (jpeg.hip, jpeg_math.h).
+static const char *jpeg_check_sub(int h, int w, int subsampling)
+{
+    if (h < 1 || w < 1 || h > 65535 || w > 65535) return "h and w must lie in 1..65535";
+    if (subsampling != 420 && subsampling != 444) return "subsampling must be 420 or 444";
+    return nullptr;
+}
+
+long long hh_jpeg_bound(int h, int w, int subsampling)
+{
+    const char *why = jpeg_check_sub(h, w, subsampling);
+    if (why) { hh_set_error(std::string("hh_jpeg_bound: ") + why); return -1; }
+    return jpeg_bound(jpeg_geom(h, w, subsampling));
+}
+
+long long hh_jpeg_workspace_bytes(int h, int w, int subsampling)
+{
+    const char *why = jpeg_check_sub(h, w, subsampling);
+    if (why) { hh_set_error(std::string("hh_jpeg_workspace_bytes: ") + why); return -1; }
+    return jpeg_geom(h, w, subsampling).ws_bytes;
+}
+
+int hh_jpeg_quant_tables(int quality, int32_t out[128])
+{
+    if (!out) { hh_set_error("hh_jpeg_quant_tables: null pointer"); return 1; }
+    if (quality < 1 || quality > 100) { hh_set_error("hh_jpeg_quant_tables: quality outside 1..100"); return 1; }
+    for (int t = 0; t < 2; ++t)
+        for (int k = 0; k < 64; ++k) out[t * 64 + k] = jpeg_quant(quality, t, k);
+    return 0;
+}
+
+int hh_jpeg_config(int out[4])
+{
+    if (!out) { hh_set_error("hh_jpeg_config: null pointer"); return 1; }
+    out[0] = JPEG_ENT_LANES, out[1] = JPEG_BLOCK_BITS, out[2] = JPEG_HEADER_BYTES, out[3] = JPEG_MCUS_PER_GROUP;
+    return 0;
+}
+
+int hh_jpeg_encode_u8_batch(unsigned char *batch_base, const hh_jpeg_desc *descs_dev, const hh_jpeg_desc *descs_host, int n,
+                            unsigned char *workspace, long long workspace_bytes, int32_t *lengths_dev, void *stream)
+{
+    static_assert(sizeof(hh_jpeg_desc) == sizeof(JpegDesc), "table layout");
+    const std::string fn = "hh_jpeg_encode_u8_batch";
+    if (!batch_base || !descs_dev || !descs_host || !workspace || !lengths_dev) { hh_set_error(fn + ": null pointer"); return 1; }
+    if (n <= 0 || n > 65535) { hh_set_error(fn + ": need 0 < n <= 65535"); return 1; }
+    if ((uintptr_t)descs_dev % 8 || (uintptr_t)workspace % 16 || (uintptr_t)lengths_dev % 4) {
+        hh_set_error(fn + ": descs_dev must be 8-byte, workspace 16-byte and lengths_dev 4-byte aligned");
+        return 1;
+    }
+    int max_mcus = 1, max_rows = 1;
+    for (int b = 0; b < n; ++b) {
+        const JpegDesc &d = reinterpret_cast<const JpegDesc *>(descs_host)[b];
+        const char *why = jpeg_check_desc(d);
+        if (why) { hh_set_error(fn + ": frame " + std::to_string(b) + ": " + why); return 1; }
+        const JpegGeom g = jpeg_geom(d.h, d.w, d.subsampling);
+        if (d.ws_offset + g.ws_bytes > workspace_bytes) { hh_set_error(fn + ": frame " + std::to_string(b) + ": workspace below hh_jpeg_workspace_bytes"); return 1; }
+        max_mcus = std::max(max_mcus, g.mrows * g.mcols);
+        max_rows = std::max(max_rows, g.mrows);
+    }
+    HH_CHECK_HIP(launch_jpeg_encode(batch_base, reinterpret_cast<const JpegDesc *>(descs_dev), n, max_mcus, max_rows, workspace, lengths_dev,
+                                    (hipStream_t)stream));
+    return 0;
+}
+
+int hh_debug_jpeg_encode_host(const unsigned char *src, const hh_jpeg_desc *desc, unsigned char *out, long long *length)
+{
+    const std::string fn = "hh_debug_jpeg_encode_host";
+    if (!src || !desc || !out || !length) { hh_set_error(fn + ": null pointer"); return 1; }
+    const JpegDesc &d = *reinterpret_cast<const JpegDesc *>(desc);
+    const char *why = jpeg_check_desc(d);
+    if (why) { hh_set_error(fn + ": " + why); return 1; }
+    std::vector<JpegVec8> work((size_t)jpeg_geom(d.h, d.w, d.subsampling).nblk * 8);
+    *length = jpeg_encode_host(src, d, out, work[0].v);
+    return 0;
+}
+
+int hh_debug_jpeg_fdct(const int32_t samples[64], int32_t rows_out[64], int32_t cols_out[64])
+{
+    if (!samples || !rows_out || !cols_out) { hh_set_error("hh_debug_jpeg_fdct: null pointer"); return 1; }
+    long long sum = 0;  // sum |s| <= 8192 (what a block of samples has at most) keeps |F| <= 8035 * (8035 * 8192 / 2048 + 8) < 2^31
+    for (int i = 0; i < 64; ++i) sum += samples[i] < 0 ? -(long long)samples[i] : samples[i];
+    if (sum > 8192) { hh_set_error("hh_debug_jpeg_fdct: the samples' absolute sum exceeds 8192"); return 1; }
+    memcpy(rows_out, samples, 64 * sizeof(int32_t));
+    for (int y = 0; y < 8; ++y) jpeg_fdct_row(rows_out + y * 8);
+    for (int u = 0; u < 8; ++u) {
+        int32_t F[8];
+        jpeg_fdct_col(rows_out, u, F);
+        for (int v = 0; v < 8; ++v) cols_out[v * 8 + u] = F[v];
+    }
     return 0;
 }
 

@@ -361,6 +361,11 @@ hipError_t launch_render_poses(unsigned char *base, const RenderDesc *descs, con
 void render_debug_host(const unsigned char *src, unsigned char *dst, const RenderDesc &d, const RenderPrim *prims);
 hipError_t launch_resize_u8(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, hipStream_t s);
 hipError_t launch_resize_u8_scaled(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, double fx, double fy, hipStream_t s);
+// Baseline JPEG (hh_jpeg_desc of include/hhrnet.h; struct and arithmetic in jpeg_math.h, kernels in jpeg.hip): n frames in three
+// launches, `max_mcus` / `max_rows` = the largest frame's MCU count / MCU rows.
+struct JpegDesc;
+hipError_t launch_jpeg_encode(unsigned char *base, const JpegDesc *descs, int n, int max_mcus, int max_rows, unsigned char *ws, int32_t *lengths,
+                              hipStream_t s);
 // Heatmap panels (hh_panel_map of include/hhrnet.h; struct and arithmetic in panel_math.h, kernels in panels.hip): the min/max launch
 // (only if any_minmax) and the paint launch of one figure; the same figure on the host; the un-normalise of the model input.
 struct PanelMap;

@@ -9,4 +9,6 @@ from . import coco_eval, crowd_mask, evaluation, targets, tracking
 from .crowd_mask import CrowdSegments, crowd_masks, get_crowd_mask, raw_sample
 from .train_input import Mosaic, TrainInput, mosaic_joints
 from .tracking import PoseTracker
+from . import jpeg
+from .jpeg import MJPEGWriter, encode_jpeg_device, save_jpeg
 from .visualization import DEFAULT_PALETTE, build_primitives, jet_lut, plot_connections, plot_heatmaps

@@ -496,7 +496,10 @@ class InferenceKeypointsModel:
         overlay frame of `result.plot_connections(color_mode, alpha)` (B,G,R order if `bgr`; resized to `out_height` with the aspect
         ratio kept, as the reference's resize_with_aspect_ratio, if given).  The frames of a batch are drawn in ONE
         hh_render_poses_u8_batch from the staged device pixels of that batch, which stay alive until then; with render=None nothing
-        of the pipeline changes.  color_mode="track" (needs `tracker`) draws the smoothed coordinates, each person in the colour of its id.
+        of the pipeline changes.  With `jpeg=dict(quality=90, subsampling="420")` among the render options the frames of a batch are
+        encoded on the GPU in ONE hh_jpeg_encode_u8_batch behind their render launch (keypoints/jpeg.py) and every result carries
+        `.rendered_jpeg` (bytes; true colours also with `bgr`) in place of `.rendered`: no raw frame is copied back.
+        color_mode="track" (needs `tracker`) draws the smoothed coordinates, each person in the colour of its id.
         `tracker` = a keypoints.tracking.PoseTracker with one stream: `raw_images` are consecutive frames of ONE clip.  All must share
         one model-input shape (else ValueError, before any launch) and that of the frames the tracker saw before (else reset() it).  The
         chunks are fed in order, each as one hh_track_step behind its hh_decode on the same stream with frames_per_stream = the chunk
@@ -506,7 +509,7 @@ class InferenceKeypointsModel:
         if render is not None and render.get("color_mode") == "track" and tracker is None:
             raise ValueError("infer_images: render color_mode 'track' needs a tracker")
         if render is not None:
-            unknown = set(render) - {"color_mode", "alpha", "bgr", "out_height"}
+            unknown = set(render) - {"color_mode", "alpha", "bgr", "out_height", "jpeg"}
             if unknown:
                 raise ValueError(f"infer_images: unknown render option(s) {sorted(unknown)}")
         n = len(raw_images)
@@ -646,9 +649,10 @@ class InferenceKeypointsModel:
         return results
 
     def _render_chunk(self, results: list, raw: Tensor, offs, color_mode: str = "person", alpha: float = 0.8, bgr: bool = False,
-                      out_height: int | None = None) -> None:
+                      out_height: int | None = None, jpeg: dict | None = None) -> None:
         """`.rendered` of the results of one batch: one render launch on the batch's staged pixels (`raw`: the device copy of the
-        staging buffer, image j at bytes offs[j]..offs[j+1]), the optional resizes, one pinned buffer back."""
+        staging buffer, image j at bytes offs[j]..offs[j+1]), the optional resizes, one pinned buffer back.  With `jpeg`:
+        `.rendered_jpeg` instead, one encode call on the device frames, only the compressed bytes back."""
         from . import visualization as vz
         cur = torch.cuda.current_stream(self.device)
         raw.record_stream(cur)
@@ -661,6 +665,11 @@ class InferenceKeypointsModel:
         out = vz.render_frames_device(frames, tables, alpha, bgr)
         if out_height is not None:
             out = [f if f.shape[0] == out_height else vz.resize_device(f, int(out_height * f.shape[1] / f.shape[0]), out_height) for f in out]
+        if jpeg is not None:
+            from .jpeg import encode_jpeg_device
+            for r, data in zip(results, encode_jpeg_device(out, bgr=bgr, **jpeg)):
+                r.rendered_jpeg = data
+            return
         sizes = np.cumsum([0] + [f.numel() for f in out])
         host = torch.empty(int(sizes[-1]), dtype=torch.uint8, pin_memory=True)
         for j, f in enumerate(out):
@@ -693,7 +702,7 @@ class InferenceKeypointsModel:
             return result
         return self._on_fast_stream(run)
 
-    def video_frame(self, image: np.ndarray, tracker=None):
+    def video_frame(self, image: np.ndarray, tracker=None, jpeg: dict | None = None):
         """`video_processing_fn` (keypoints/bin/inference.py:49-75) without its text labels -> (result, out_frame): one inference,
         the people ordered by their mean tag (same colours for the same person from frame to frame), limb colours at alpha 0.65 with
         thr = det_thr, B,G,R order, resized to height 640 (new_w = int(640 * w / h); no resize launch when h == 640).  The frame is
@@ -701,7 +710,10 @@ class InferenceKeypointsModel:
         comes back through one pinned buffer.
         `tracker` = a keypoints.tracking.PoseTracker with one stream (an extension): the frame is the next one of the tracker's clip; the
         result carries `.track_ids` and `.kpts_coords_smooth` (see infer_images) and the overlay draws the smoothed coordinates, every
-        person in the colour of its id (color_mode "track") instead of the tag order and the limb colours."""
+        person in the colour of its id (color_mode "track") instead of the tag order and the limb colours.
+        `jpeg` = dict(quality=90, subsampling="420") (an extension): out_frame is the 640-high frame as a JFIF stream (bytes), encoded on the
+        GPU (keypoints/jpeg.py) with bgr=True, so that the stream holds the true colours; what `MJPEGWriter.write` takes.  The raw frame
+        is not copied back."""
         from . import visualization as vz
         if tracker is not None:
             result = self._call_tracked(image, tracker)
@@ -716,6 +728,9 @@ class InferenceKeypointsModel:
         h, w = raw.shape[:2]
         if h != 640:
             frame = vz.resize_device(frame, int(640 * w / h), 640)
+        if jpeg is not None:
+            from .jpeg import encode_jpeg_device
+            return result, encode_jpeg_device([frame], bgr=True, **jpeg)[0]
         return result, vz.to_host(frame)
 
     def __call__(self, raw_image: np.ndarray, annot: list | None) -> InferenceKeypointsResult:

@@ -63,7 +63,11 @@ class KeypointsResult:
             r._assign(j, s)
 
     def plot(self) -> dict[str, np.ndarray]:
-        """results.py:126-155 after set_preds(): {"heatmaps": figure}.  Left, the connections overlay on the un-normalised model input
+        from . import visualization as vis
+        return {name: vis.to_host(figure) for name, figure in self._plot_device().items()}
+
+    def _plot_device(self) -> dict[str, Tensor]:
+        """results.py:126-155 after set_preds(): {"heatmaps": figure}, on the device.  Left, the connections overlay on the un-normalised model input
         (thr = det_thr, alpha = 0.8); right, per stage a one-row grid of that stage's maps clipped to 0..1 (stage 0 resized twice, as
         set_preds resizes it) followed, while the stage index is below the embedding dimension (1), by a one-row grid of the tags with
         min-max; the grids stacked, shrunk by 0.4 and put next to the overlay.  Everything per pixel runs on the GPU
@@ -77,7 +81,15 @@ class KeypointsResult:
         grids = [([(vis.NESTED, m, None, vis.CLIP) for m in a], 1, 5), ([(vis.SINGLE, m, None, vis.MINMAX) for m in tags], 1, 5),
                  ([(vis.SINGLE, m, None, vis.CLIP) for m in b], 1, 5)]
         figure = vis.figure_device(image, grids, 0.4)
-        return {"heatmaps": vis.to_host(vis.stack_horizontally_device([connections, figure]))}
+        return {"heatmaps": vis.stack_horizontally_device([connections, figure])}
+
+    def plot_jpeg(self, quality: int = 90, subsampling="444") -> dict[str, bytes]:
+        """plot() as the .jpg files the reference's callbacks save (src/base/callbacks.py:234,371): every figure encoded on the GPU from
+        its device canvas (keypoints/jpeg.py), one encode call, only the compressed bytes copied back.  4:4:4 by default: the panels
+        have thin coloured lines."""
+        from .jpeg import encode_jpeg_device
+        figures = self._plot_device()
+        return dict(zip(figures, encode_jpeg_device(list(figures.values()), quality, subsampling)))
 
 
 @dataclass
@@ -95,6 +107,7 @@ class InferenceKeypointsResult:
     _stage_hms: list | None = None
     _tags: list | None = None
     rendered: np.ndarray | None = None  # infer_images(render=...): the finished overlay frame
+    rendered_jpeg: bytes | None = None  # infer_images(render=dict(jpeg=...)): that frame as a JFIF stream, in place of `rendered`
     track_ids: np.ndarray | None = None  # with a PoseTracker: int32 [P], 0 = no track
     kpts_coords_smooth: np.ndarray | None = None  # with a PoseTracker: [P,K,2] raw-image pixels, One-Euro filtered
 
@@ -117,7 +130,7 @@ class InferenceKeypointsResult:
         from .visualization import plot_connections
         return plot_connections(self.raw_image, self.kpts_coords, self.kpts_scores, self.limbs, self.det_thr, color_mode, alpha)
 
-    def plot_heatmaps_figure(self) -> np.ndarray:
+    def _heatmaps_figure_device(self) -> Tensor:
         """results.py:317-328: the K stage-average maps and the K tag maps of the first embedding, both with min-max, each as a grid of
         two rows over the un-normalised model input, stacked and shrunk by 0.6 -> uint8 [h,w,3].  Painted on the GPU from the stage
         outputs (hh_heatmap_panels_u8); only the finished figure is copied to the host."""
@@ -126,7 +139,24 @@ class InferenceKeypointsResult:
         tags = self._tags[0][0].float().contiguous()
         image = vis.unnormalize_device(self.model_input_image.to(a.device, torch.float32))
         grids = [([(vis.AVERAGE, q, h, vis.MINMAX) for q, h in zip(a, b)], 2, 5), ([(vis.SINGLE, m, None, vis.MINMAX) for m in tags], 2, 5)]
-        return vis.to_host(vis.figure_device(image, grids, 0.6))
+        return vis.figure_device(image, grids, 0.6)
+
+    def plot_heatmaps_figure(self) -> np.ndarray:
+        from . import visualization as vis
+        return vis.to_host(self._heatmaps_figure_device())
+
+    def plot_jpeg(self, quality: int = 90, subsampling="444") -> dict[str, bytes]:
+        """plot() as the .jpg files the reference's perform_inference saves (src/base/datasets/base.py:140): the same figures, drawn and
+        encoded on the GPU (keypoints/jpeg.py) in one encode call; only the compressed bytes are copied back.  4:4:4 by default: the
+        overlays and panels have thin coloured lines."""
+        from . import visualization as vis
+        from .jpeg import encode_jpeg_device
+        image = np.ascontiguousarray(self.raw_image, dtype=np.uint8)
+        table = vis.build_primitives(self.kpts_coords, self.kpts_scores, self.limbs, self.det_thr, "person", vis.DEFAULT_PALETTE, 0.8)
+        figures = {"connections": vis.render_frames_device([image], [table], 0.8)[0]}
+        if self._stage_hms is not None and self._tags is not None and self.model_input_image is not None:
+            figures["heatmaps"] = self._heatmaps_figure_device()
+        return dict(zip(figures, encode_jpeg_device(list(figures.values()), quality, subsampling)))
 
     def plot(self) -> dict[str, np.ndarray]:
         """results.py:300-339 as far as it is built here: {"connections": ...} and, when the result holds its stage maps, tags and
