@@ -607,6 +607,91 @@ int hh_jpeg_encode_u8_batch(unsigned char *batch_base, const hh_jpeg_desc *descs
                             unsigned char *workspace, long long workspace_bytes, int32_t *lengths_dev, void *stream);
 int hh_debug_jpeg_encode_host(const unsigned char *src, const hh_jpeg_desc *desc, unsigned char *out, long long *length);
 int hh_debug_jpeg_fdct(const int32_t samples[64], int32_t rows_out[64], int32_t cols_out[64]);
+/* Baseline JPEG decoded on the device: the reference's `np.array(Image.open(path).convert("RGB"))` (src/base/datasets/base.py:174,194,
+ * src/classification/datasets/imagenet.py:49) for n streams of mixed sizes, samplings and tables in ONE call of three launches.  Only
+ * the compressed bytes and a small table cross the bus.  The target is the same bytes as Pillow (libjpeg-turbo), not a tolerance:
+ * tests/golden/jpeg_decode.npz holds Pillow's pixels, tests/jpeg_decode_ref.py restates the rule in numpy; device, host
+ * (hh_debug_jpeg_decode_host), numpy and Pillow agree byte for byte on that corpus.  Integer arithmetic only; `>>` is arithmetic.
+ *
+ * Accepted: SOF0, 8 bit; 1 component (grayscale, replicated to three channels) or 3 components Y/Cb/Cr; sampling 4:4:4, 4:2:2 (h2v1),
+ *   4:2:0 (h2v2); one interleaved scan of all components; up to 4 DC and 4 AC Huffman tables (standard or optimised); 8- or 16-bit
+ *   quantiser tables; any DRI or none; APPn and COM are skipped.
+ * Refused by name by hh_jpeg_parse, on the host, before anything is staged or launched: "progressive streams (SOF2)", any other SOF,
+ *   "arithmetic coding", "12-bit precision", "4 components", "unsupported sampling" (4:4:0, 4:1:1, ...), "more than one scan", "an Adobe
+ *   marker with transform 0 (RGB)", "missing tables", "a dimension of 0", "dimensions beyond what int32 offsets allow", "truncated
+ *   header", restart markers that do not match the interval or are out of sequence.
+ * a. Entropy decoding (ITU T.81 F.2): FF 00 is FF; DC prediction per component, 0 at the start and after each RSTm; coefficients in
+ *    natural order.
+ * b. IDCT: libjpeg's jidctint ("islow") on coefficient x divisor (integer multiply): CONST_BITS 13, PASS1_BITS 2, columns first,
+ *    descaled by 11 with rounding, rows descaled by 18 with rounding; the constants 2446 3196 4433 6270 7373 9633 12299 15137 16069
+ *    16819 20995 25172; sample = clamp(result + 128, 0, 255).  (libjpeg's C code wraps results beyond +-512 through a 1024-entry
+ *    table; the SIMD code Pillow runs saturates instead, and Pillow's output decides: see tests/jpeg_decode_ref.py.)
+ * c. Chroma upsampling, libjpeg's "fancy" filters, with edges at the component's true size ceil(w / 2) x ceil(h / 2):
+ *    h2v2: s[c] = 3 near[c] + far[c], far = the row above for the upper output row, below for the lower, the edge row itself at the first
+ *      and last row; even outputs (3 s[c] + s[c-1] + 8) >> 4, odd outputs (3 s[c] + s[c+1] + 7) >> 4, the missing neighbour = s[c].
+ *    h2v1: even outputs (3 c + left + 1) >> 2, odd (3 c + right + 2) >> 2; the first and last output equal the edge sample.
+ *    A chroma width <= 2 (image width <= 4): plain replication in both axes.
+ * d. Colour: R = Y + ((91881 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16)
+ *    with cb = Cb - 128, cr = Cr - 128, each clamped to 0..255.  Flag bit 0 stores B,G,R.
+ *
+ * hh_jpeg_parse: walks the markers of one stream in HOST memory and fills the info (all refusals happen here).
+ * A segment is the run of MCUs one lane decodes.  hh_jpeg_restart_segments: with DRI, one segment per restart interval from a byte scan
+ *   for RSTm, no Huffman work, predictors 0.  hh_jpeg_index_host: one Huffman pass on the host (symbol lengths and DC sums only) that
+ *   records an entry every mcus_per_segment MCUs (<= 0: one MCU row, our encoder's interval; a parameter, not a measured optimum),
+ *   counted anew at every restart; it validates the stream ("the scan cannot be walked: <status>").  Both refuse a capacity below the
+ *   number of entries.  A file's index is built once and reused.
+ * hh_jpeg_decode_workspace_bytes: int16 coefficients of the MCU grid plus the block-padded component planes (a multiple of 16).
+ * hh_jpeg_decode_tables_bytes: info (112) + quantiser and Huffman lookup tables (7808) + 32 nseg.  hh_jpeg_decode_tables writes that
+ *   block (HOST) for a stream and its entries.  Nothing is sized by typical content.
+ * hh_jpeg_decode_u8_batch: one hh_jpeg_dec_desc of 64 bytes per image; stream, table block and destination lie at batch_base + their
+ *   offsets (one base, never dereferenced itself), scratch at workspace + ws_offset.  descs_host / infos_host are the caller's HOST
+ *   copies of the descriptors and of the infos the table blocks start with: they are what is checked.  status_dev[i] is cleared, then
+ *   raised to the largest code a lane of image i met: 1 bad Huffman code, 2 zero run past coefficient 63, 3 bytes exhausted, 4 missing
+ *   or unexpected RSTm, 5 bad segment; that lane ends there.  No input makes a kernel read or write outside the image's stream,
+ *   workspace and destination: every byte read is bounded by the segment's and the scan's end, every block by the segment's own extent
+ *   cut to the MCU grid.  Returns 1 with hh_last_error set, before any launch or clearing, for a null pointer, n outside 1..65535,
+ *   misaligned descs_dev (8) / workspace (16) / status_dev (4) / table block (16), an info hh_jpeg_parse cannot have written, "negative
+ *   offset", "pitch below 3 * w", an unknown flag, nseg < 1, a scan outside stream_length, "table block below
+ *   hh_jpeg_decode_tables_bytes", "workspace below hh_jpeg_decode_workspace_bytes".
+ * hh_debug_jpeg_decode_host: the whole rule on one stream in HOST memory into dst (entries NULL: its own segments); *status receives the
+ *   code, a nonzero one also returns 1.  For tests, tools/jpeg_decode_host_check.cpp, and as the yardstick of the GPU tests.
+ * (Additive entry points: HH_ABI_VERSION stays 3.)                                                                           */
+typedef struct hh_jpeg_stream_info {
+    long long scan_offset, scan_end;
+    int32_t h, w, ncomp;
+    int32_t sampling;          /* 444, 422, 420; 400: grayscale */
+    int32_t restart_interval;  /* MCUs; 0: none */
+    int32_t hs, vs;            /* luminance blocks per MCU across and down */
+    int32_t mcols, mrows;
+    int32_t bpm;               /* blocks per MCU */
+    int32_t qt[3], dc[3], ac[3];
+    int32_t nseg_restart;
+    int32_t adobe_transform;   /* -1: none */
+    int32_t reserved[3];
+} hh_jpeg_stream_info;
+typedef struct hh_jpeg_segment {
+    int32_t first_mcu, mcu_count;
+    int32_t byte_offset, bit_offset;
+    int32_t pred[3];
+    int32_t byte_end;          /* (end of the segment's bytes) << 1 | (an RSTm follows) */
+} hh_jpeg_segment;
+typedef struct hh_jpeg_dec_desc {
+    long long stream_offset, tables_offset, tables_bytes, dst_offset, ws_offset, pitch;
+    int32_t stream_length, nseg;
+    int32_t flags, reserved;
+} hh_jpeg_dec_desc;
+int hh_jpeg_parse(const unsigned char *bytes, long long len, hh_jpeg_stream_info *info);
+int hh_jpeg_restart_segments(const unsigned char *bytes, long long len, hh_jpeg_segment *entries, int capacity, int *n);
+int hh_jpeg_index_host(const unsigned char *bytes, long long len, int mcus_per_segment, hh_jpeg_segment *entries, int capacity, int *n);
+long long hh_jpeg_decode_workspace_bytes(const hh_jpeg_stream_info *info);
+long long hh_jpeg_decode_tables_bytes(const hh_jpeg_stream_info *info, int nseg);
+int hh_jpeg_decode_tables(const unsigned char *bytes, long long len, const hh_jpeg_segment *entries, int nseg, unsigned char *out,
+                          long long out_bytes);
+int hh_jpeg_decode_u8_batch(unsigned char *batch_base, const hh_jpeg_dec_desc *descs_dev, const hh_jpeg_dec_desc *descs_host,
+                            const hh_jpeg_stream_info *infos_host, int n, unsigned char *workspace, long long workspace_bytes,
+                            int32_t *status_dev, void *stream);
+int hh_debug_jpeg_decode_host(const unsigned char *bytes, long long len, const hh_jpeg_segment *entries, int nseg, int flags,
+                              unsigned char *dst, long long pitch, int *status);
 /* COCO keypoint scoring on the device: computeOks + evaluateImg of pycocotools' COCOeval(iouType="keypoints") as keypoints/coco_eval.py
  * restates them (`_oks`, `_evaluate_img`; the `eval_coco` step of keypoints/bin/eval.py:52-65), for every image, area range and threshold
  * in ONE launch over packed tables.  What is pinned is "device = this repository's host evaluator"; parity with pycocotools itself stays

@@ -17,6 +17,7 @@
 #include "crowd_mask_math.h"
 #include "track_math.h"
 #include "jpeg_math.h"
+#include "jpeg_dec_math.h"
 
 const char *hh_get_error();
 int hh_tap_read_impl(hh_net *n, int index, float *host);
@@ -444,6 +445,167 @@ int hh_debug_jpeg_fdct(const int32_t samples[64], int32_t rows_out[64], int32_t 
         jpeg_fdct_col(rows_out, u, F);
         for (int v = 0; v < 8; ++v) cols_out[v * 8 + u] = F[v];
     }
+    return 0;
+}
+
+// Baseline JPEG decode (jpeg_decode.hip, jpeg_dec_math.h).
+static_assert(sizeof(hh_jpeg_stream_info) == sizeof(JpegStreamInfo) && sizeof(hh_jpeg_segment) == sizeof(JpegSegment) &&
+                  sizeof(hh_jpeg_dec_desc) == sizeof(JpegDecDesc),
+              "table layout");
+static const char *const JPEG_STATUS_NAME[6] = {"ok", "bad Huffman code", "zero run past coefficient 63", "bytes exhausted",
+                                                "missing or unexpected RSTm", "bad segment"};
+
+// What the kernels trust of a stream's info; nullptr if it is what hh_jpeg_parse can have written.
+static const char *jpeg_dec_check_info(const JpegStreamInfo &I)
+{
+    if (I.h < 1 || I.w < 1 || I.h > 65535 || I.w > 65535) return "bad stream info: h and w must lie in 1..65535";
+    const bool grey = I.ncomp == 1 && I.hs == 1 && I.vs == 1 && I.bpm == 1;
+    const bool colour = I.ncomp == 3 && (I.hs == 1 || I.hs == 2) && (I.vs == 1 || I.vs == I.hs) && I.bpm == I.hs * I.vs + 2;
+    if (!grey && !colour) return "bad stream info: components or sampling";
+    if (I.mcols != (I.w + 8 * I.hs - 1) / (8 * I.hs) || I.mrows != (I.h + 8 * I.vs - 1) / (8 * I.vs)) return "bad stream info: the MCU grid";
+    if ((long long)I.mcols * I.hs * 8 * 3 * ((long long)I.mrows * I.vs * 8) > INT32_MAX || (long long)I.mcols * I.mrows * I.bpm * 128 > INT32_MAX)
+        return "dimensions beyond what int32 offsets allow";
+    for (int c = 0; c < 3; ++c)
+        if ((I.qt[c] | I.dc[c] | I.ac[c]) & ~3) return "bad stream info: a table id outside 0..3";
+    if (I.scan_offset < 2 || I.scan_end < I.scan_offset || I.scan_end > INT32_MAX) return "bad stream info: the scan's bytes";
+    return nullptr;
+}
+
+int hh_jpeg_parse(const unsigned char *bytes, long long len, hh_jpeg_stream_info *info)
+{
+    if (!bytes || !info) { hh_set_error("hh_jpeg_parse: null pointer"); return 1; }
+    const char *why = jpeg_dec_parse(bytes, len, reinterpret_cast<JpegStreamInfo *>(info), nullptr);
+    if (why) { hh_set_error(std::string("hh_jpeg_parse: ") + why); return 1; }
+    return 0;
+}
+
+int hh_jpeg_restart_segments(const unsigned char *bytes, long long len, hh_jpeg_segment *entries, int capacity, int *n)
+{
+    const std::string fn = "hh_jpeg_restart_segments";
+    if (!bytes || !entries || !n) { hh_set_error(fn + ": null pointer"); return 1; }
+    JpegStreamInfo I;
+    const char *why = jpeg_dec_parse(bytes, len, &I, nullptr);
+    if (!why && !I.restart_interval) why = "the stream has no restart interval (use hh_jpeg_index_host)";
+    if (!why && capacity < I.nseg_restart) why = "capacity below the number of segments";
+    if (!why) why = jpeg_dec_restart_segments(bytes, I, reinterpret_cast<JpegSegment *>(entries));
+    if (why) { hh_set_error(fn + ": " + why); return 1; }
+    *n = I.nseg_restart;
+    return 0;
+}
+
+int hh_jpeg_index_host(const unsigned char *bytes, long long len, int mcus_per_segment, hh_jpeg_segment *entries, int capacity, int *n)
+{
+    const std::string fn = "hh_jpeg_index_host";
+    if (!bytes || !entries || !n) { hh_set_error(fn + ": null pointer"); return 1; }
+    JpegStreamInfo I;
+    std::vector<JpegDecTables> T(1);
+    const char *why = jpeg_dec_parse(bytes, len, &I, &T[0]);
+    int status = 0;
+    if (!why) why = jpeg_dec_index(bytes, len, I, T[0], mcus_per_segment > 0 ? mcus_per_segment : I.mcols, reinterpret_cast<JpegSegment *>(entries), capacity, n, &status);
+    if (why) { hh_set_error(fn + ": " + why + (status ? std::string(": ") + JPEG_STATUS_NAME[status] : std::string())); return 1; }
+    return 0;
+}
+
+long long hh_jpeg_decode_workspace_bytes(const hh_jpeg_stream_info *info)
+{
+    const char *why = info ? jpeg_dec_check_info(*reinterpret_cast<const JpegStreamInfo *>(info)) : "null pointer";
+    if (why) { hh_set_error(std::string("hh_jpeg_decode_workspace_bytes: ") + why); return -1; }
+    return jpeg_dec_geom(*reinterpret_cast<const JpegStreamInfo *>(info)).ws_bytes;
+}
+
+long long hh_jpeg_decode_tables_bytes(const hh_jpeg_stream_info *info, int nseg)
+{
+    const char *why = info ? jpeg_dec_check_info(*reinterpret_cast<const JpegStreamInfo *>(info)) : "null pointer";
+    if (!why && nseg < 1) why = "nseg must be at least 1";
+    if (why) { hh_set_error(std::string("hh_jpeg_decode_tables_bytes: ") + why); return -1; }
+    return jpeg_dec_tables_bytes(nseg);
+}
+
+int hh_jpeg_decode_tables(const unsigned char *bytes, long long len, const hh_jpeg_segment *entries, int nseg, unsigned char *out, long long out_bytes)
+{
+    const std::string fn = "hh_jpeg_decode_tables";
+    if (!bytes || !entries || !out) { hh_set_error(fn + ": null pointer"); return 1; }
+    if (nseg < 1 || out_bytes < jpeg_dec_tables_bytes(nseg)) { hh_set_error(fn + ": room below hh_jpeg_decode_tables_bytes"); return 1; }
+    JpegStreamInfo I;
+    std::vector<JpegDecTables> T(1);
+    const char *why = jpeg_dec_parse(bytes, len, &I, &T[0]);
+    if (why) { hh_set_error(fn + ": " + why); return 1; }
+    memcpy(out, &I, sizeof(I));
+    memcpy(out + JPEG_DEC_TABLES_AT, &T[0], sizeof(JpegDecTables));
+    memcpy(out + JPEG_DEC_SEGS_AT, entries, (size_t)nseg * sizeof(JpegSegment));
+    return 0;
+}
+
+int hh_jpeg_decode_u8_batch(unsigned char *batch_base, const hh_jpeg_dec_desc *descs_dev, const hh_jpeg_dec_desc *descs_host,
+                            const hh_jpeg_stream_info *infos_host, int n, unsigned char *workspace, long long workspace_bytes, int32_t *status_dev,
+                            void *stream)
+{
+    const std::string fn = "hh_jpeg_decode_u8_batch";
+    if (!batch_base || !descs_dev || !descs_host || !infos_host || !workspace || !status_dev) { hh_set_error(fn + ": null pointer"); return 1; }
+    if (n < 1 || n > 65535) { hh_set_error(fn + ": need 1 <= n <= 65535"); return 1; }
+    if ((uintptr_t)descs_dev % 8 || (uintptr_t)workspace % 16 || (uintptr_t)status_dev % 4) {
+        hh_set_error(fn + ": descs_dev must be 8-byte, workspace 16-byte and status_dev 4-byte aligned");
+        return 1;
+    }
+    int max_seg = 1, max_blk = 1, max_h = 1, max_w = 1;
+    for (int b = 0; b < n; ++b) {
+        const JpegDecDesc &d = reinterpret_cast<const JpegDecDesc *>(descs_host)[b];
+        const JpegStreamInfo &I = reinterpret_cast<const JpegStreamInfo *>(infos_host)[b];
+        const char *why = jpeg_dec_check_info(I);
+        if (!why && (d.stream_offset < 0 || d.tables_offset < 0 || d.dst_offset < 0 || d.ws_offset < 0)) why = "negative offset";
+        if (!why && d.pitch < 3ll * I.w) why = "pitch below 3 * w";
+        if (!why && (d.flags & ~1)) why = "unknown flag";
+        if (!why && d.nseg < 1) why = "nseg must be at least 1";
+        if (!why && (d.stream_length < 1 || I.scan_end > d.stream_length)) why = "the scan's bytes lie outside the stream's length";
+        if (!why && d.tables_bytes < jpeg_dec_tables_bytes(d.nseg)) why = "table block below hh_jpeg_decode_tables_bytes";
+        if (!why && ((uintptr_t)(batch_base + d.tables_offset) % 16 || d.ws_offset % 16)) why = "the table block and ws_offset must be 16-byte aligned";
+        const JpegDecGeom g = jpeg_dec_geom(I);
+        if (!why && d.ws_offset + g.ws_bytes > workspace_bytes) why = "workspace below hh_jpeg_decode_workspace_bytes";
+        if (why) { hh_set_error(fn + ": image " + std::to_string(b) + ": " + why); return 1; }
+        max_seg = std::max(max_seg, d.nseg), max_blk = std::max(max_blk, g.nblk), max_h = std::max(max_h, I.h), max_w = std::max(max_w, I.w);
+    }
+    HH_CHECK_HIP(hipMemsetAsync(status_dev, 0, (size_t)n * 4, (hipStream_t)stream));
+    HH_CHECK_HIP(launch_jpeg_decode(batch_base, reinterpret_cast<const JpegDecDesc *>(descs_dev), n, max_seg, max_blk, max_h, max_w, workspace, status_dev,
+                                    (hipStream_t)stream));
+    return 0;
+}
+
+int hh_debug_jpeg_decode_host(const unsigned char *bytes, long long len, const hh_jpeg_segment *entries, int nseg, int flags, unsigned char *dst,
+                              long long pitch, int *status)
+{
+    const std::string fn = "hh_debug_jpeg_decode_host";
+    if (!bytes || !dst) { hh_set_error(fn + ": null pointer"); return 1; }
+    if (status) *status = 0;
+    JpegStreamInfo I;
+    std::vector<JpegDecTables> T(1);
+    const char *why = jpeg_dec_parse(bytes, len, &I, &T[0]);
+    if (!why && pitch < 3ll * I.w) why = "pitch below 3 * w";
+    if (!why && (flags & ~1)) why = "unknown flag";
+    if (!why && entries && nseg < 1) why = "nseg must be at least 1";
+    std::vector<JpegSegment> own;
+    if (!why && !entries) {
+        if (I.restart_interval) {
+            own.resize(I.nseg_restart);
+            why = jpeg_dec_restart_segments(bytes, I, own.data());
+        } else {  // the whole scan as one segment: no index is needed for a single lane
+            JpegSegment all = {0, I.mcols * I.mrows, (int32_t)I.scan_offset, 0, {0, 0, 0}, (int32_t)(I.scan_end << 1)};
+            own.push_back(all);
+        }
+        entries = reinterpret_cast<const hh_jpeg_segment *>(own.data());
+        nseg = (int)own.size();
+    }
+    if (why) { hh_set_error(fn + ": " + why); return 1; }
+    const JpegDecGeom g = jpeg_dec_geom(I);
+    std::vector<JpegVec8> ws((size_t)g.ws_bytes / 16 + 1);
+    memset(ws.data(), 0, ws.size() * 16);
+    int st = 0;
+    for (int s = 0; s < nseg; ++s) {
+        const int one = jpeg_dec_segment<true>(bytes, (int)len, I, T[0].huff, reinterpret_cast<const JpegSegment *>(entries)[s], ws[0].v, nullptr, nullptr);
+        st = std::max(st, one);
+    }
+    if (status) *status = st;
+    jpeg_dec_pixels_host(reinterpret_cast<unsigned char *>(ws.data()), I, T[0], flags & 1, dst, pitch);
+    if (st) { hh_set_error(fn + ": status " + std::to_string(st) + " (" + JPEG_STATUS_NAME[st] + ")"); return 1; }
     return 0;
 }
 

@@ -10,5 +10,5 @@ from .crowd_mask import CrowdSegments, crowd_masks, get_crowd_mask, raw_sample
 from .train_input import Mosaic, TrainInput, mosaic_joints
 from .tracking import PoseTracker
 from . import jpeg
-from .jpeg import MJPEGWriter, encode_jpeg_device, save_jpeg
+from .jpeg import JpegImage, JpegIndexCache, MJPEGReader, MJPEGWriter, build_jpeg_index, decode_jpeg_device, encode_jpeg_device, jpeg_info, load_jpeg, save_jpeg
 from .visualization import DEFAULT_PALETTE, build_primitives, jet_lut, plot_connections, plot_heatmaps

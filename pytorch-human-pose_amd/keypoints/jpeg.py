@@ -3,10 +3,17 @@ figures where they already are (hh_jpeg_encode_u8_batch: one call of three launc
 that entry point in include/hhrnet.h), and the Motion-JPEG AVI of `cv2.VideoWriter(..., "MJPG", ...)` (src/base/datasets/video.py:93-106)
 as a pure-Python RIFF writer.  Only compressed bytes cross to the host.  There is no CPU fallback: `encode_jpeg_host` is the same rule
 compiled for the host, for tests.
+
+The way back is here too: `decode_jpeg_device` / `load_jpeg` stand for the reference's `np.array(Image.open(path).convert("RGB"))`
+(src/base/datasets/base.py:174,194) with Pillow's own bytes as the target (hh_jpeg_decode_u8_batch: one call of three launches for a
+batch of mixed streams; the rule is written at that entry point), `JpegImage` is what `TrainInput.build` takes in place of a pixel
+array, and `MJPEGReader` reads back what `MJPEGWriter` wrote.  `decode_jpeg_host` is the same rule compiled for the host, for tests.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
+import os
 import struct
 
 import numpy as np
@@ -248,3 +255,320 @@ class MJPEGWriter:
     def __exit__(self, *exc):
         self.close()
         return False
+
+
+# ------------------------------------------------------------------------------------------------------------------ decoding
+# hh_jpeg_stream_info, hh_jpeg_segment, hh_jpeg_dec_desc of include/hhrnet.h
+INFO = np.dtype([("scan_offset", "<i8"), ("scan_end", "<i8"), ("h", "<i4"), ("w", "<i4"), ("ncomp", "<i4"), ("sampling", "<i4"),
+                 ("restart_interval", "<i4"), ("hs", "<i4"), ("vs", "<i4"), ("mcols", "<i4"), ("mrows", "<i4"), ("bpm", "<i4"), ("qt", "<i4", (3,)),
+                 ("dc", "<i4", (3,)), ("ac", "<i4", (3,)), ("nseg_restart", "<i4"), ("adobe_transform", "<i4"), ("reserved", "<i4", (3,))])
+SEGMENT = np.dtype([("first_mcu", "<i4"), ("mcu_count", "<i4"), ("byte_offset", "<i4"), ("bit_offset", "<i4"), ("pred", "<i4", (3,)), ("byte_end", "<i4")])
+DEC_DESC = np.dtype([("stream_offset", "<i8"), ("tables_offset", "<i8"), ("tables_bytes", "<i8"), ("dst_offset", "<i8"), ("ws_offset", "<i8"),
+                     ("pitch", "<i8"), ("stream_length", "<i4"), ("nseg", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
+assert INFO.itemsize == 112 and SEGMENT.itemsize == 32 and DEC_DESC.itemsize == 64
+STATUS_NAMES = ("ok", "bad Huffman code", "zero run past coefficient 63", "bytes exhausted", "missing or unexpected RSTm", "bad segment")
+
+JpegInfo = collections.namedtuple("JpegInfo", "h w components sampling restart_interval mcu_cols mcu_rows scan_offset scan_end")
+
+
+def _bytes_view(data) -> np.ndarray:
+    a = np.frombuffer(data, np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    if a.size == 0:
+        raise _lib.HHError("hh_jpeg_parse: not a JPEG stream (no SOI)")
+    return a
+
+
+def _parse(a: np.ndarray) -> np.ndarray:
+    info = np.zeros(1, INFO)
+    _lib.check(_lib.load().hh_jpeg_parse(a.ctypes.data, a.size, info.ctypes.data))
+    return info
+
+
+def jpeg_info(data) -> JpegInfo:
+    """hh_jpeg_parse: the header of one stream; every stream the decoder does not take is refused here, by name (HHError)."""
+    i = _parse(_bytes_view(data))[0]
+    return JpegInfo(int(i["h"]), int(i["w"]), int(i["ncomp"]), int(i["sampling"]), int(i["restart_interval"]), int(i["mcols"]), int(i["mrows"]),
+                    int(i["scan_offset"]), int(i["scan_end"]))
+
+
+def _index_count(i, mps: int) -> int:
+    nmcu, ri = int(i["mcols"]) * int(i["mrows"]), int(i["restart_interval"])
+    if not ri:
+        return -(-nmcu // mps)
+    return nmcu // ri * -(-ri // mps) + -(-(nmcu % ri) // mps)
+
+
+def build_jpeg_index(data, mcus_per_segment: int | None = None) -> np.ndarray:
+    """hh_jpeg_index_host: one Huffman pass on the host -> the stream's segments (SEGMENT rows), an entry every `mcus_per_segment` MCUs
+    (default: one MCU row; a parameter, not a measured optimum).  The pass validates the stream; one it cannot walk is refused by
+    name.  A file's index does not change: build it once (JpegIndexCache) and hand it to every decode."""
+    a = _bytes_view(data)
+    i = _parse(a)[0]
+    mps = int(i["mcols"]) if mcus_per_segment is None else int(mcus_per_segment)
+    if mps < 1:
+        raise ValueError("build_jpeg_index: mcus_per_segment must be at least 1")
+    entries = np.zeros(_index_count(i, mps), SEGMENT)
+    n = C.c_int(0)
+    _lib.check(_lib.load().hh_jpeg_index_host(a.ctypes.data, a.size, mps, entries.ctypes.data, len(entries), C.byref(n)))
+    return entries[:n.value]
+
+
+def _segments(a: np.ndarray, info, index) -> np.ndarray:
+    """The segments one decode uses: the supplied index, else the restart intervals (a byte scan), else an index built on the spot."""
+    if index is not None:
+        index = np.ascontiguousarray(index)
+        if index.dtype != SEGMENT or index.ndim != 1 or len(index) < 1:
+            raise ValueError("a JPEG index is a non-empty 1-d array of jpeg.SEGMENT rows (build_jpeg_index)")
+        return index
+    if int(info["restart_interval"]):
+        entries = np.zeros(int(info["nseg_restart"]), SEGMENT)
+        n = C.c_int(0)
+        _lib.check(_lib.load().hh_jpeg_restart_segments(a.ctypes.data, a.size, entries.ctypes.data, len(entries), C.byref(n)))
+        return entries[:n.value]
+    return build_jpeg_index(a)
+
+
+class JpegIndexCache:
+    """path -> the file's index, built on first use; an entry is dropped when the file's size or mtime changes."""
+
+    def __init__(self, mcus_per_segment: int | None = None):
+        self.mcus_per_segment = mcus_per_segment
+        self._entries: dict = {}
+
+    def get(self, path, data=None) -> np.ndarray:
+        st = os.stat(path)
+        key = os.fspath(path)
+        hit = self._entries.get(key)
+        if hit is not None and hit[0] == (st.st_size, st.st_mtime_ns):
+            return hit[1]
+        if data is None:
+            with open(path, "rb") as f:
+                data = f.read()
+        index = build_jpeg_index(data, self.mcus_per_segment)
+        self._entries[key] = ((st.st_size, st.st_mtime_ns), index)
+        return index
+
+    def __len__(self) -> int:
+        return len(self._entries)
+
+
+class JpegImage:
+    """A compressed image where `TrainInput.build` takes a pixel array: the stream's bytes with `.h`, `.w`, `.shape`, `.dtype` and `.ndim`
+    of the uint8 [h,w,3] array it decodes to.  The header is parsed here (a stream the decoder does not take is refused by name), the
+    segments are the supplied `index`, else the stream's restart intervals, else an index built (and so validated) here."""
+
+    dtype = np.dtype(np.uint8)
+    ndim = 3
+
+    def __init__(self, data, index=None):
+        self.data = _bytes_view(data)
+        self.info = _parse(self.data)
+        self.segments = _segments(self.data, self.info[0], index)
+        self.h, self.w = int(self.info[0]["h"]), int(self.info[0]["w"])
+        self.shape = (self.h, self.w, 3)
+        lib = _lib.load()
+        self.ws_bytes = int(lib.hh_jpeg_decode_workspace_bytes(self.info.ctypes.data))
+        self.tables_bytes = int(lib.hh_jpeg_decode_tables_bytes(self.info.ctypes.data, len(self.segments)))
+        if self.ws_bytes < 0 or self.tables_bytes < 0:
+            _lib.check(1)
+
+    def staged_bytes(self) -> int:
+        """What crosses the bus for this image: the stream and its table block, each rounded up to 16."""
+        return _align(self.data.size, 16) + _align(self.tables_bytes, 16)
+
+    def stage(self, hview: np.ndarray, at: int) -> tuple[int, int]:
+        """Stream and table block into the staging bytes at `at` (a multiple of 16) -> (stream offset, tables offset)."""
+        tables_at = at + _align(self.data.size, 16)
+        hview[at:at + self.data.size] = self.data
+        out = hview[tables_at:tables_at + self.tables_bytes]
+        _lib.check(_lib.load().hh_jpeg_decode_tables(self.data.ctypes.data, self.data.size, self.segments.ctypes.data, len(self.segments),
+                                                     out.ctypes.data, self.tables_bytes))
+        return at, tables_at
+
+
+def launch_decode(dev, base: int, descs_dev: int, descs: np.ndarray, infos: np.ndarray, work, status_dev: int) -> None:
+    """hh_jpeg_decode_u8_batch on the current stream of `dev` (three launches behind the clearing of the statuses)."""
+    _lib.launch(dev, _lib.load().hh_jpeg_decode_u8_batch, base, descs_dev, descs.ctypes.data, infos.ctypes.data, len(descs), work.data_ptr(),
+                work.numel(), status_dev)
+
+
+def raise_status(statuses, what: str = "hh_jpeg_decode_u8_batch") -> None:
+    bad = [(i, int(s)) for i, s in enumerate(statuses) if int(s)]
+    if bad:
+        i, s = bad[0]
+        name = STATUS_NAMES[s] if 0 <= s < len(STATUS_NAMES) else "unknown"
+        raise _lib.HHError(f"{what}: image {i}: status {s} ({name})" + (f"; also images {[j for j, _ in bad[1:]]}" if len(bad) > 1 else ""))
+
+
+def decode_jpeg_device(streams: list, index=None, bgr=False, device=None, out=None) -> list:
+    """One hh_jpeg_decode_u8_batch, on the current stream, for a batch of JPEG streams (bytes, uint8 arrays or JpegImage) of mixed sizes,
+    samplings and tables -> one uint8 [h,w,3] device tensor per stream, R,G,B or (`bgr`: one value or one per stream) B,G,R.  `index`:
+    None, or one entry per stream (None or a build_jpeg_index result); a stream without DRI and without an index has its index built
+    on the spot.  Bytes, tables and descriptors travel in one pinned copy; then one read of the n statuses: a nonzero one raises
+    HHError naming the image and the code.  `out`: optional destinations, one uint8 [h,w,3] device tensor (or row-pitched view) per
+    stream, written in place of fresh tensors.  `decode_jpeg_device.last_status` / `.last_h2d_bytes` keep the statuses and the uploaded
+    bytes of the last call (the statuses also when it raises)."""
+    n = len(streams)
+    if n == 0:
+        return []
+    idx = _per_frame(index, n) if isinstance(index, (list, tuple)) else [index] * n
+    if index is not None and not isinstance(index, (list, tuple)) and n != 1:
+        raise ValueError("decode_jpeg_device: `index` is a list with one entry per stream")
+    items = [s if isinstance(s, JpegImage) else JpegImage(s, i) for s, i in zip(streams, idx)]
+    bgrs = _per_frame(bgr, n)
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    at = _align(DEC_DESC.itemsize * n, 16)
+    places = []
+    for it in items:
+        places.append(at)
+        at += it.staged_bytes()
+    upload = at
+    status_at = _align(at, 16)
+    at = status_at + 4 * n
+    dst_at = []
+    for it in items:
+        at = _align(at, 16)
+        dst_at.append(at)
+        at += it.h * it.w * 3 if out is None else 0
+    ws_at = np.cumsum([0] + [it.ws_bytes for it in items])
+    host = torch.empty(upload, dtype=torch.uint8).pin_memory()
+    hv = host.numpy()
+    hv[:] = 0
+    descs = hv[:DEC_DESC.itemsize * n].view(DEC_DESC)
+    infos = np.concatenate([it.info for it in items])
+    buf = torch.empty(at, dtype=torch.uint8, device=device)  # [descriptors | streams and tables | statuses | pixels]
+    work = torch.empty(max(int(ws_at[-1]), 16), dtype=torch.uint8, device=device)
+    if out is not None:
+        if len(out) != n:
+            raise ValueError("decode_jpeg_device: one destination per stream")
+        for o, it in zip(out, items):
+            if not (isinstance(o, torch.Tensor) and o.dtype == torch.uint8 and tuple(o.shape) == it.shape and o.device == buf.device and o.stride(2) == 1
+                    and o.stride(1) == 3):
+                raise ValueError("a destination must be a uint8 [h,w,3] device tensor (or a row-pitched view of one) of the stream's size")
+    base = min([buf.data_ptr()] + ([o.data_ptr() for o in out] if out is not None else []))
+    rel = buf.data_ptr() - base
+    for j, it in enumerate(items):
+        stream_at, tables_at = it.stage(hv, places[j])
+        dst = rel + dst_at[j] if out is None else out[j].data_ptr() - base
+        pitch = 3 * it.w if out is None else int(out[j].stride(0))
+        descs[j] = (rel + stream_at, rel + tables_at, it.tables_bytes, dst, int(ws_at[j]), pitch, it.data.size, len(it.segments), FLAG_BGR if bgrs[j] else 0, 0)
+    buf[:upload].copy_(host, non_blocking=True)
+    launch_decode(device, base, buf.data_ptr(), descs, infos, work, buf.data_ptr() + status_at)
+    status_host = torch.empty(n, dtype=torch.int32, pin_memory=True)
+    status_host.copy_(buf[status_at:status_at + 4 * n].view(torch.int32), non_blocking=True)
+    torch.cuda.current_stream(device).synchronize()
+    decode_jpeg_device.last_h2d_bytes, decode_jpeg_device.last_status = upload, status_host.numpy().copy()
+    raise_status(status_host.numpy())
+    if out is not None:
+        return list(out)
+    return [buf[o:o + it.h * it.w * 3].view(it.h, it.w, 3) for o, it in zip(dst_at, items)]
+
+
+def decode_jpeg_host(data, bgr: bool = False, index=None, pitch: int | None = None) -> np.ndarray:
+    """hh_debug_jpeg_decode_host: one stream through the rule compiled for the host -> uint8 [h,w,3] (tests and the GPU tests' yardstick;
+    needs the library, no GPU).  `index`: decode from these segments instead of the stream's own."""
+    a = _bytes_view(data)
+    i = _parse(a)[0]
+    h, w = int(i["h"]), int(i["w"])
+    pitch = 3 * w if pitch is None else int(pitch)
+    out = np.zeros((h, max(pitch, 3 * w)), np.uint8)
+    status = C.c_int(0)
+    seg = None if index is None else np.ascontiguousarray(index)
+    _lib.check(_lib.load().hh_debug_jpeg_decode_host(a.ctypes.data, a.size, None if seg is None else seg.ctypes.data, 0 if seg is None else len(seg),
+                                                     FLAG_BGR if bgr else 0, out.ctypes.data, pitch, C.byref(status)))
+    return np.ascontiguousarray(out[:, :3 * w]).reshape(h, w, 3)
+
+
+def load_jpeg(path, device=None, cache: JpegIndexCache | None = None, bgr: bool = False):
+    """`np.array(Image.open(path).convert("RGB"))` with the pixels formed on the device -> uint8 [h,w,3] device tensor.  `cache`: a
+    JpegIndexCache that keeps the file's index from call to call."""
+    with open(path, "rb") as f:
+        data = f.read()
+    index = None
+    if cache is not None and not jpeg_info(data).restart_interval:
+        index = cache.get(path, data)
+    return decode_jpeg_device([data], [index], bgr, device)[0]
+
+
+class MJPEGReader:
+    """The inverse of MJPEGWriter, pure Python: walks RIFF 'AVI ' -> LIST 'hdrl' ('avih', 'strh', 'strf') -> LIST 'movi' -> 'idx1' and
+    hands out the frames' JPEG streams.  len(), fps, width, height, reader[i] -> bytes, iteration; read(i, n, device) decodes n frames in
+    one hh_jpeg_decode_u8_batch call.  A file that is not an MJPG AVI, or whose index is cut short, is refused by name."""
+
+    def __init__(self, path):
+        with open(path, "rb") as f:
+            self._data = f.read()
+        d = self._data
+        if len(d) < 12 or d[:4] != b"RIFF" or d[8:12] != b"AVI ":
+            raise ValueError("MJPEGReader: not a RIFF AVI file")
+        self.fps = self.width = self.height = None
+        movi = idx = None
+        handler = None
+        for fourcc, at, size in self._chunks(12, len(d)):
+            if fourcc == b"LIST" and d[at:at + 4] == b"hdrl":
+                for f2, a2, s2 in self._chunks(at + 4, at + size):
+                    if f2 == b"avih" and s2 >= 40:
+                        self.width, self.height = struct.unpack_from("<II", d, a2 + 32)
+                    elif f2 == b"LIST" and d[a2:a2 + 4] == b"strl":
+                        for f3, a3, s3 in self._chunks(a2 + 4, a2 + s2):
+                            if f3 == b"strh" and s3 >= 28 and d[a3:a3 + 4] == b"vids":
+                                handler = d[a3 + 4:a3 + 8]
+                                scale, rate = struct.unpack_from("<II", d, a3 + 20)
+                                self.fps = rate / scale if scale else None
+            elif fourcc == b"LIST" and d[at:at + 4] == b"movi":
+                movi = (at, size)
+            elif fourcc == b"idx1":
+                idx = (at, size)
+        if handler is None or movi is None or self.fps is None:
+            raise ValueError("MJPEGReader: not an AVI with a video stream and a 'movi' list")
+        if handler.upper() != b"MJPG":
+            raise ValueError(f"MJPEGReader: not an MJPG AVI (the video stream's handler is {handler!r})")
+        if self.fps == int(self.fps):
+            self.fps = int(self.fps)
+        if idx is None:
+            raise ValueError("MJPEGReader: truncated file: no 'idx1' chunk")
+        nframes_at = None
+        for fourcc, at, size in self._chunks(12, len(d)):
+            if fourcc == b"LIST" and d[at:at + 4] == b"hdrl":
+                for f2, a2, s2 in self._chunks(at + 4, at + size):
+                    if f2 == b"avih":
+                        nframes_at = struct.unpack_from("<I", d, a2 + 16)[0]
+        if idx[1] % 16 or idx[0] + idx[1] > len(d):
+            raise ValueError("MJPEGReader: truncated 'idx1' chunk")
+        self._frames = []
+        for e in range(idx[1] // 16):
+            cid, _, off, size = struct.unpack_from("<4sIII", d, idx[0] + 16 * e)
+            if cid[2:] not in (b"dc", b"db"):
+                continue
+            start = movi[0] + off + 8  # offsets count from the 'movi' fourcc; 8: the chunk's own header
+            if start + size > movi[0] + movi[1] or d[start - 8:start - 4] != cid or struct.unpack_from("<I", d, start - 4)[0] != size:
+                raise ValueError(f"MJPEGReader: index entry {e} does not point at a frame chunk")
+            self._frames.append((start, size))
+        if nframes_at is not None and nframes_at != len(self._frames):
+            raise ValueError(f"MJPEGReader: truncated 'idx1' chunk: {len(self._frames)} entries for {nframes_at} frames")
+
+    def _chunks(self, at: int, end: int):
+        d = self._data
+        while at + 8 <= end:
+            fourcc, size = d[at:at + 4], struct.unpack_from("<I", d, at + 4)[0]
+            if at + 8 + size > len(d):
+                raise ValueError(f"MJPEGReader: truncated file: chunk {fourcc!r} passes the end")
+            yield fourcc, at + 8, size
+            at += 8 + size + (size & 1)
+
+    def __len__(self) -> int:
+        return len(self._frames)
+
+    def __getitem__(self, i: int) -> bytes:
+        start, size = self._frames[i]
+        return self._data[start:start + size]
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+    def read(self, i: int = 0, n: int | None = None, device=None, bgr: bool = False) -> list:
+        """Frames i .. i + n - 1 decoded on the device in one call -> uint8 [h,w,3] tensors."""
+        n = len(self) - i if n is None else n
+        if i < 0 or n < 0 or i + n > len(self):
+            raise IndexError("MJPEGReader.read: frames outside the file")
+        return decode_jpeg_device([self[k] for k in range(i, i + n)], None, bgr, device)

@@ -29,6 +29,7 @@ import numpy as np
 
 from .. import _lib
 from . import crowd_mask as cm
+from . import jpeg as jp
 from .loss import DeviceJoints, pack_joints
 from .targets import JointsGenerator
 from .transforms_utils import COCO_FLIP_INDEX
@@ -54,6 +55,11 @@ class AugParams:
     flip: bool
 
 
+def _hw(img) -> tuple:
+    """(h, w) of a sample's image: a pixel array, or a jpeg.JpegImage (which carries the size of what it decodes to)."""
+    return tuple(img.shape[:2]) if isinstance(img, jp.JpegImage) else np.asarray(img).shape[:2]
+
+
 class Mosaic:
     """A batch entry of `TrainInput.build` that stands where a raw sample may stand: four raw samples (image, mask, joints) that are
     resized to out_size x out_size each and tiled top-left, top-right, bottom-left, bottom-right (coco.py:318-325)."""
@@ -71,7 +77,7 @@ def mosaic_joints(tiles, S: int, num_kpts: int = 17) -> np.ndarray:
     joints given as a float array are not.  The tiles' arrays are not modified."""
     out = [np.zeros((0, num_kpts, 3))]
     for i, (img, _, joints) in enumerate(tiles):
-        h, w = np.asarray(img).shape[:2]
+        h, w = _hw(img)
         k = np.array(joints).reshape(-1, num_kpts, 3)  # a copy that keeps the dtype
         hidden = k[:, :, 2] <= 0
         k[:, :, 0] = k[:, :, 0] * (S / w) + (i % 2) * S
@@ -157,7 +163,7 @@ class _Mode:
                 s = Mosaic([s] + [pool[random.randint(0, len(pool) - 1)] for _ in range(3)])
                 params.append(self.draw(2 * S, 2 * S))
             else:
-                params.append(self.draw(*np.asarray(s[0]).shape[:2]))
+                params.append(self.draw(*_hw(s[0])))
             entries.append(s)
         return entries, params
 
@@ -179,7 +185,11 @@ class TrainInput:
     `mosaic_probability` is the field of the reference's dataset (both modes honour it: the dataset decides, not the transform).
     With a value > 0 a mode is called as `ti.train(samples, pool)`: `pool` is any object with len() and [i] -> (image, mask, joints)
     raw samples (the reference's get_raw_data), from which the three other tiles of a mosaic are drawn.  `build` takes a
-    `Mosaic(tiles)` wherever it takes a raw sample."""
+    `Mosaic(tiles)` wherever it takes a raw sample.
+
+    The image of a sample or of a mosaic tile may be a `jpeg.JpegImage` (the file's compressed bytes) instead of a pixel array: its
+    pixels are decoded on the device and never cross the bus.  `jpeg_status()` reads the decoder's per-image statuses of the last
+    build."""
 
     def __init__(self, out_size: int, hm_resolutions, max_rotation: int = 30, min_scale: float = 0.75, max_scale: float = 1.5,
                  scale_type: str = "short", max_translate: int = 40, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225),
@@ -202,6 +212,8 @@ class TrainInput:
         self._stage_free = [None, None]  # ... and the event behind the copy that last read each
         self._turn = 0
         self.last_h2d_bytes = self.last_launches = 0  # of the last build(): what tools/train_input_time.py reports
+        self.last_staged_bytes = 0  # the part of last_h2d_bytes that is the one staged copy (the rest: the joint tables)
+        self._jpeg_status = None    # the device statuses of the last build's JpegImage samples
 
     # ------------------------------------------------------------------ host half (no GPU)
     def geometry(self, height: int, width: int, joints, p: AugParams):
@@ -242,7 +254,12 @@ class TrainInput:
         of a dense array (`crowd_mask.raw_sample` makes such samples from COCO annotations); dense and segment samples may be mixed.
         A segment sample's mask bytes are not staged: its toggles and descriptors travel in the same copy, and one
         hh_crowd_masks_u8_batch launch per batch fills the masks behind the staged bytes of the device buffer, before the mosaic and
-        warp launches.  A batch of dense samples takes exactly the path it took before: same bytes, same launches."""
+        warp launches.  A batch of dense samples takes exactly the path it took before: same bytes, same launches.
+        The image of a sample or tile may be a `jpeg.JpegImage`, mixed freely with arrays: its stream and table block travel in the same
+        copy (behind the crowd tables), its h * w * 3 pixel slot lies behind the staged bytes of the device buffer, and ONE
+        hh_jpeg_decode_u8_batch call (three launches) fills all such slots before the crowd-mask, mosaic and warp launches.  Nothing
+        synchronises here: `jpeg_status()` reads the statuses afterwards.  A batch without a JpegImage takes exactly the path it took
+        before: same bytes, same launches."""
         import torch
         lib = _lib.load()
         B, S, K, nst = len(samples), self.out_size, self.num_kpts, len(self.hm_sizes)
@@ -266,12 +283,19 @@ class TrainInput:
         # a raw sample whose second element is a CrowdSegments ships no mask bytes: its toggles and descriptors travel instead
         seg_raws = [r for r, (_, mask, _) in enumerate(raws) if isinstance(mask, cm.CrowdSegments)]
         seg_items = [raws[r][1] for r in seg_raws]
-        sizes = [h * w * 3 for h, w in shapes] + [0 if isinstance(mask, cm.CrowdSegments) else h * w for (h, w), (_, mask, _) in zip(shapes, raws)]
+        jpeg_raws = [r for r, (img, _, _) in enumerate(raws) if isinstance(img, jp.JpegImage)]
+        jpeg_items = [raws[r][0] for r in jpeg_raws]
+        sizes = [0 if isinstance(img, jp.JpegImage) else h * w * 3 for (h, w), (img, _, _) in zip(shapes, raws)] + [0 if isinstance(mask, cm.CrowdSegments) else h * w for (h, w), (_, mask, _) in zip(shapes, raws)]
         offs = np.cumsum([0] + sizes)
         desc_off = (int(offs[-1]) + 63) // 64 * 64  # the descriptors travel behind the pixels and masks, in the same copy
         mosaic_off = desc_off + _TRAIN_DESC.itemsize * B
         crowd_off = mosaic_off + _MOSAIC_DESC.itemsize * M  # (a multiple of 8: both descriptor sizes are)
         total = crowd_off + cm.tables_bytes(seg_items)
+        # a JpegImage ships its stream and table block behind the crowd tables: [decode descriptors | stream, tables | ...], 16-aligned
+        jpeg_off = (total + 15) // 16 * 16
+        jpeg_places = jpeg_off + jp.DEC_DESC.itemsize * len(jpeg_items) + np.cumsum([0] + [it.staged_bytes() for it in jpeg_items])
+        if jpeg_items:
+            total = int(jpeg_places[-1])
         # the canvases of the mosaic samples lie behind the staged bytes in the device buffer; nothing of them is copied
         canvas_off = (total + 63) // 64 * 64
         # ... and behind them the masks of the segment samples, which hh_crowd_masks_u8_batch fills there
@@ -279,6 +303,13 @@ class TrainInput:
         mask_at_raw = [int(offs[R + r]) for r in range(R)]
         for i, r in enumerate(seg_raws):
             mask_at_raw[r] = int(fill_offs[i])
+        # ... and behind those the pixel slots of the JpegImage samples, which hh_jpeg_decode_u8_batch fills there, and its statuses
+        pixel_offs = (int(fill_offs[-1]) + 15) // 16 * 16 + np.cumsum([0] + [(it.h * it.w * 3 + 15) // 16 * 16 for it in jpeg_items])
+        image_at_raw = [int(offs[r]) for r in range(R)]
+        for i, r in enumerate(jpeg_raws):
+            image_at_raw[r] = int(pixel_offs[i])
+        status_off = int(pixel_offs[-1])
+        device_bytes = status_off + 4 * len(jpeg_items) if jpeg_items else int(fill_offs[-1])
         if M and (S % 4 or S < 4):
             raise _lib.HHError("TrainInput.build: a mosaic needs an out_size that is a multiple of 4 (hh_mosaic_u8_batch)")
         turn, host = self._staging(total)
@@ -286,9 +317,17 @@ class TrainInput:
         descs = hview[desc_off:mosaic_off].view(_TRAIN_DESC)
         mdescs = hview[mosaic_off:crowd_off].view(_MOSAIC_DESC)
         crowd_desc_at, crowd_seg_at, crowd_nseg = cm.fill_tables(seg_items, fill_offs[:-1], hview, crowd_off)
+        if jpeg_items:
+            jdescs = hview[jpeg_off:jpeg_off + jp.DEC_DESC.itemsize * len(jpeg_items)].view(jp.DEC_DESC)
+            jinfos = np.concatenate([it.info for it in jpeg_items])
+            ws_offs = np.cumsum([0] + [it.ws_bytes for it in jpeg_items])
+            for i, it in enumerate(jpeg_items):
+                stream_at, tables_at = it.stage(hview, int(jpeg_places[i]))
+                jdescs[i] = (stream_at, tables_at, it.tables_bytes, int(pixel_offs[i]), int(ws_offs[i]), 3 * it.w, it.data.size, len(it.segments), 0, 0)
         for r, (img, mask, _) in enumerate(raws):
             h, w = shapes[r]
-            np.copyto(hview[offs[r]:offs[r + 1]].reshape(h, w, 3), img)
+            if not isinstance(img, jp.JpegImage):
+                np.copyto(hview[offs[r]:offs[r + 1]].reshape(h, w, 3), img)
             if isinstance(mask, cm.CrowdSegments):
                 continue
             mview = hview[offs[R + r]:offs[R + r + 1]].reshape(h, w)
@@ -298,12 +337,12 @@ class TrainInput:
         for b, (entry, p) in enumerate(zip(samples, params)):
             if isinstance(entry, Mosaic):
                 image_at, mask_at = canvas_off + m * 16 * S * S, canvas_off + m * 16 * S * S + 12 * S * S
-                mdescs[m] = ([(int(offs[r]), mask_at_raw[r], *shapes[r]) for r in slots[b]], image_at, mask_at)
+                mdescs[m] = ([(image_at_raw[r], mask_at_raw[r], *shapes[r]) for r in slots[b]], image_at, mask_at)
                 h = w = 2 * S
                 joints = mosaic_joints(entry.tiles, S, K)
                 m += 1
             else:
-                image_at, mask_at, (h, w), joints = int(offs[slots[b]]), mask_at_raw[slots[b]], shapes[slots[b]], entry[2]
+                image_at, mask_at, (h, w), joints = image_at_raw[slots[b]], mask_at_raw[slots[b]], shapes[slots[b]], entry[2]
             mat_image, mats, _, ints = self.geometry(h, w, joints, p)
             inv_mask = np.zeros((MAX_STAGES, 6))
             for i, mat in enumerate(mats):
@@ -314,21 +353,27 @@ class TrainInput:
         dev = torch.device(self.device)
         with torch.cuda.device(dev):
             cur = torch.cuda.current_stream(dev)
-            if M or seg_items:
-                raw = torch.empty(int(fill_offs[-1]), device=dev, dtype=torch.uint8)
+            if M or seg_items or jpeg_items:
+                raw = torch.empty(device_bytes, device=dev, dtype=torch.uint8)
                 raw[:total].copy_(host[:total], non_blocking=True)
             else:
                 raw = host[:total].to(dev, non_blocking=True)
             copied = torch.cuda.Event()
             copied.record(cur)
             self._stage_free[turn] = copied
-            self.last_h2d_bytes, self.last_launches = total, 2 + nst + (1 if M else 0) + (1 if seg_items else 0)
+            self.last_h2d_bytes, self.last_launches = total, 2 + nst + (1 if M else 0) + (1 if seg_items else 0) + (3 if jpeg_items else 0)
+            self.last_staged_bytes = total
             if self._tables_dev is None:
                 self._tables_dev = [torch.from_numpy(t).to(dev) for t, _ in self.tables]
             images = torch.empty((B, 3, S, S), device=dev, dtype=torch.float32)
             masks = [torch.empty((B, s, s), device=dev, dtype=torch.float32) for s in self.hm_sizes]
             heatmaps = [torch.empty((B, K, s, s), device=dev, dtype=torch.float32) for s in self.hm_sizes]
             base = raw.data_ptr()
+            self._jpeg_status = None
+            if jpeg_items:  # the pixels of the JpegImage samples first of all: everything below reads them
+                work = torch.empty(max(int(ws_offs[-1]), 16), device=dev, dtype=torch.uint8)
+                jp.launch_decode(dev, base, base + jpeg_off, jdescs, jinfos, work, base + status_off)
+                self._jpeg_status = raw[status_off:status_off + 4 * len(jpeg_items)].view(torch.int32)
             if seg_items:  # the masks of the segment samples first: the mosaic and the mask warp read them
                 cm.launch(dev, base, host.data_ptr(), crowd_desc_at, crowd_seg_at, len(seg_items), crowd_nseg)
             if M:  # the canvases next: the two warp launches below read them
@@ -348,6 +393,17 @@ class TrainInput:
                             table.shape[0], reach, heatmaps[i].data_ptr(), s, s)
                 device_joints.append(dj)
         return images, heatmaps, masks, device_joints
+
+    def jpeg_status(self, check: bool = True) -> np.ndarray:
+        """The decoder's statuses of the last build's JpegImage samples, in batch order (tiles of a mosaic in tile order): int32 [n], 0 =
+        decoded.  This is the read `build` does not do: it waits for the build's work.  `check`: a nonzero status raises HHError naming
+        the image and the code.  (A sample whose index the host built was validated there already.)"""
+        if self._jpeg_status is None:
+            return np.zeros(0, np.int32)
+        status = self._jpeg_status.cpu().numpy()
+        if check:
+            jp.raise_status(status, "TrainInput.build (hh_jpeg_decode_u8_batch)")
+        return status
 
     @staticmethod
     def _invert(lib, m, dp) -> np.ndarray:
