@@ -692,6 +692,64 @@ int hh_jpeg_decode_u8_batch(unsigned char *batch_base, const hh_jpeg_dec_desc *d
                             int32_t *status_dev, void *stream);
 int hh_debug_jpeg_decode_host(const unsigned char *bytes, long long len, const hh_jpeg_segment *entries, int nseg, int flags,
                               unsigned char *dst, long long pitch, int *status);
+/* Window decode: only a rectangle of the image is turned into pixels (the classifier's crop; classification/input.py).
+ *
+ * The rule.  For a window (top, left, height, width) inside the image the destination receives height x width x 3 bytes that equal,
+ *   byte for byte, rows top .. top+height-1 and columns left .. left+width-1 of what hh_jpeg_decode_u8_batch writes for the whole
+ *   image (so they also equal Pillow's pixels).  Steps a-d above hold as they stand: the fancy-upsampling edge rules stay tied to the
+ *   component's true size and to the image's edges, never to the window's, and "chroma width <= 2: replicate" is decided by the
+ *   image's width, never by the window's.
+ * The MCU rectangle.  An output pixel of a subsampled axis reads its chroma sample and one neighbour on each side (rule c).  Luma rows
+ *   t .. b need chroma rows max(0, (t >> 1) - 1) .. min(ch - 1, (b >> 1) + 1) when vs == 2 and rows t .. b when vs == 1; the same
+ *   across with hs (h2v1 needs the +-1 column as well).  The rectangle is the MCUs that hold the window's luma samples and those
+ *   chroma samples (grayscale: the luma samples).
+ * Work done (derived, not measured).  Only segments with at least one MCU in the rectangle are selected (with a finer index not a
+ *   contiguous set).  A lane walks its segment from the segment's first MCU, stores coefficients only for MCUs inside the rectangle and
+ *   ends after the segment's last MCU inside it.  Coefficients and component planes are laid out for the rectangle
+ *   (hh_jpeg_decode_window_workspace_bytes); the IDCT launch covers the rectangle's blocks, the colour launch the window's pixels; the
+ *   grids are sized by the batch's largest.  Three launches per call, whatever the batch.
+ * Staged bytes.  The slice [slice[0], slice[1]) of the file runs from the first selected segment's byte_offset to the last selected
+ *   segment's end; nothing else of the stream is needed.  hh_jpeg_decode_window_select reports the count of selected segments and
+ *   the slice; hh_jpeg_decode_window_tables (HOST) also writes the table block (hh_jpeg_decode_tables_bytes(info, *nsel)) that holds
+ *   only the selected segments, their byte offsets and the info's scan_offset / scan_end rebased to the slice (scan_offset 0).  The
+ *   descriptor's stream_offset / stream_length are the slice's.  The device bit reader knows no second origin; its bound is as
+ *   before: every byte read lies inside the slice, cut to the segment's end.
+ * Status.  status_dev[i] reports what the WALKED part of the scan met (codes as above).  "Data where the RSTm should stand" is checked
+ *   only by a lane that walked its segment to the end.  Damage outside the walked part is not seen: the host index pass (or the
+ *   restart scan) has validated the stream once per file, and that stays the gate.
+ * Safety.  No input makes a kernel read or write outside the image's shipped slice, its window workspace and its height x pitch
+ *   destination.  hh_jpeg_decode_window_u8_batch (one hh_jpeg_win_desc of 80 bytes per image: the fields of hh_jpeg_dec_desc, then
+ *   the window; infos_host: the rebased infos of the table blocks) returns 1 with hh_last_error set, before any launch or clearing,
+ *   for everything hh_jpeg_decode_u8_batch refuses and for "the window is empty", "the window leaves the image", "pitch below
+ *   3 * width", "workspace below hh_jpeg_decode_window_workspace_bytes", "table block below hh_jpeg_decode_tables_bytes", "no selected
+ *   segment"; select / tables refuse "no segment holds an MCU of the window's rectangle".
+ * hh_debug_jpeg_decode_window_host: the same shared code (csrc/jpeg_dec_math.h) on one stream in HOST memory, through the same
+ *   select / tables / slice steps (the slice is copied out, so nothing outside it can be read); *counts (may be NULL) receives what
+ *   was done.  A window equal to the whole image gives the bytes of hh_jpeg_decode_u8_batch, which is not routed through this code.
+ * (Additive entry points: HH_ABI_VERSION stays 3.)                                                                           */
+typedef struct hh_jpeg_window {
+    int32_t top, left, height, width;
+} hh_jpeg_window;
+typedef struct hh_jpeg_win_desc {
+    long long stream_offset, tables_offset, tables_bytes, dst_offset, ws_offset, pitch;
+    int32_t stream_length, nseg;   /* the slice's length; the selected segments */
+    int32_t flags, reserved;
+    hh_jpeg_window window;
+} hh_jpeg_win_desc;
+typedef struct hh_jpeg_window_counts {
+    long long segments_walked, mcus_walked, mcus_stored, blocks_transformed, pixels_written, stream_bytes;
+} hh_jpeg_window_counts;
+long long hh_jpeg_decode_window_workspace_bytes(const hh_jpeg_stream_info *info, const hh_jpeg_window *window);
+int hh_jpeg_decode_window_select(const hh_jpeg_stream_info *info, const hh_jpeg_segment *entries, int nseg, const hh_jpeg_window *window,
+                                 int *nsel, long long slice[2]);
+int hh_jpeg_decode_window_tables(const unsigned char *bytes, long long len, const hh_jpeg_segment *entries, int nseg,
+                                 const hh_jpeg_window *window, unsigned char *out, long long out_bytes, int *nsel, long long slice[2]);
+int hh_jpeg_decode_window_u8_batch(unsigned char *batch_base, const hh_jpeg_win_desc *descs_dev, const hh_jpeg_win_desc *descs_host,
+                                   const hh_jpeg_stream_info *infos_host, int n, unsigned char *workspace, long long workspace_bytes,
+                                   int32_t *status_dev, void *stream);
+int hh_debug_jpeg_decode_window_host(const unsigned char *bytes, long long len, const hh_jpeg_segment *entries, int nseg,
+                                     const hh_jpeg_window *window, int flags, unsigned char *dst, long long pitch, int *status,
+                                     hh_jpeg_window_counts *counts);
 /* COCO keypoint scoring on the device: computeOks + evaluateImg of pycocotools' COCOeval(iouType="keypoints") as keypoints/coco_eval.py
  * restates them (`_oks`, `_evaluate_img`; the `eval_coco` step of keypoints/bin/eval.py:52-65), for every image, area range and threshold
  * in ONE launch over packed tables.  What is pinned is "device = this repository's host evaluator"; parity with pycocotools itself stays

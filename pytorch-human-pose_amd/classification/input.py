@@ -12,6 +12,9 @@ The raw pixels of every sample's source rectangle (the crop; not the image aroun
 host->device copy from a pinned, double-buffered staging area.  The result is what `ClassificationModule.training_step` /
 `validation_step` take: (images [B,3,S,S] fp32, targets int64), on the device.
 There is no CPU path.
+A sample's image may also be a `keypoints.jpeg.JpegImage`, the file's compressed bytes: its crop rectangle is then the window of ONE
+hh_jpeg_decode_window_u8_batch call per batch (three launches in front of the one above), and only the byte slice and the table block
+that window needs cross, in the same copy (`ClsInput.build`).  The result is bit-identical to the batch built from the decoded arrays.
 
 UNPINNED: torchvision is not installed where this project is built and tested, so (a) the ORDER and kind of the random draws of
 `random_resized_crop_params` follow torchvision's published `RandomResizedCrop.get_params` / `RandomHorizontalFlip.forward` but
@@ -28,12 +31,18 @@ from dataclasses import dataclass
 import numpy as np
 
 from .. import _lib
+from ..keypoints import jpeg as jp
 from ..keypoints.transforms_utils import IMAGENET_MEAN, IMAGENET_STD
 
 # hh_crop_desc of include/hhrnet.h (56 bytes)
 _CROP_DESC = np.dtype([("image_offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("top", "<i4"), ("left", "<i4"), ("ch", "<i4"), ("cw", "<i4"),
                        ("rh", "<i4"), ("rw", "<i4"), ("oy", "<i4"), ("ox", "<i4"), ("flip", "<i4"), ("antialias", "<i4")])
 assert _CROP_DESC.itemsize == 56
+
+
+def _hw(img) -> tuple:
+    """(h, w) of a sample's image: a pixel array, or a jpeg.JpegImage (which carries the size of what it decodes to)."""
+    return tuple(img.shape[:2]) if isinstance(img, jp.JpegImage) else np.asarray(img).shape[:2]
 
 
 @dataclass
@@ -132,12 +141,13 @@ class ClsInput:
         self._stage_free = [None, None]  # ... and the event behind the copy that last read each
         self._turn = 0
         self.last_h2d_bytes = self.last_launches = 0  # of the last build(): what tools/cls_input_time.py reports
+        self._jpeg_status = None  # the device statuses of the last build's JpegImage samples
 
     def train(self, samples):
-        return self.build(samples, [random_resized_crop_params(*np.asarray(s[0]).shape[:2]) for s in samples])
+        return self.build(samples, [random_resized_crop_params(*_hw(s[0])) for s in samples])
 
     def inference(self, samples):
-        return self.build(samples, [inference_geometry(*np.asarray(s[0]).shape[:2], resize=self.resize, crop=self.out_size) for s in samples])
+        return self.build(samples, [inference_geometry(*_hw(s[0]), resize=self.resize, crop=self.out_size) for s in samples])
 
     def window(self, height: int, width: int, p) -> CropWindow:
         """One sample's parameters in the general form."""
@@ -173,7 +183,14 @@ class ClsInput:
 
     def build(self, samples, params):
         """samples: [(uint8 [h,w,3] image, int target)], params: one CropParams / (rh, rw, oy, ox) / CropWindow per sample ->
-        (images [B,3,S,S] fp32, targets [B] int64) on the device, in the current stream."""
+        (images [B,3,S,S] fp32, targets [B] int64) on the device, in the current stream.
+        A sample's image may be a `jpeg.JpegImage` (the file's compressed bytes), mixed freely with arrays: its source rectangle is its
+        decode window.  The slice of the stream that the window's segments need and their table block travel in the same copy, behind
+        the targets; its height x width x 3 pixel slot lies behind the staged bytes of the device buffer, and ONE
+        hh_jpeg_decode_window_u8_batch call (three launches) fills all such slots before the resized-crop launch, which reads a slot
+        exactly as it reads a shipped crop.  Nothing synchronises here: `jpeg_status()` reads the statuses afterwards.  A stream the
+        decoder does not take (progressive, CMYK, ...) is refused by name at `JpegImage(...)`: pass such a file as a Pillow array in
+        the same batch; there is no silent fallback.  A batch without a JpegImage takes exactly the path it took before."""
         import torch
         lib = _lib.load()
         B, S = len(samples), self.out_size
@@ -181,38 +198,84 @@ class ClsInput:
             raise ValueError("ClsInput.build: one parameter set per sample, at least one sample")
         windows = []
         for b, ((img, _), p) in enumerate(zip(samples, params)):
-            if not isinstance(img, np.ndarray) or img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3:
-                raise ValueError("ClsInput.build: uint8 [h,w,3] images only")
+            if not isinstance(img, jp.JpegImage) and (not isinstance(img, np.ndarray) or img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3):
+                raise ValueError("ClsInput.build: uint8 [h,w,3] images (or jpeg.JpegImage) only")
             q = self.window(img.shape[0], img.shape[1], p)
             # only the source rectangle is staged and shipped (a slice would silently clip a rectangle that leaves the image)
             if q.height <= 0 or q.width <= 0 or q.top < 0 or q.left < 0 or q.top + q.height > img.shape[0] or q.left + q.width > img.shape[1]:
                 raise _lib.HHError(f"ClsInput.build: sample {b}: crop rectangle outside its image (or empty)")
             windows.append(q)
         shapes = [(q.height, q.width) for q in windows]
-        offs, desc_off, target_off, total = self.layout(shapes)
+        jpeg_at = [b for b, (img, _) in enumerate(samples) if isinstance(img, jp.JpegImage)]
+        # a JpegImage ships no pixels: its slot in the pixel area is empty
+        offs, desc_off, target_off, total = self.layout([(0, 0) if isinstance(img, jp.JpegImage) else hw for hw, (img, _) in zip(shapes, samples)])
+        image_at = [int(o) for o in offs[:-1]]
+        if jpeg_at:
+            # behind the targets, 16-aligned: [decode descriptors | slice, tables | ...]; behind the staged bytes, on the device only:
+            # the pixel slots the decode fills, then its statuses
+            plans = [samples[b][0].window_plan((windows[b].top, windows[b].left, *shapes[b])) for b in jpeg_at]
+            jpeg_off = (total + 15) // 16 * 16
+            places = jpeg_off + (jp.WIN_DESC.itemsize * len(jpeg_at) + 15) // 16 * 16 + np.cumsum([0] + [p.staged_bytes for p in plans])
+            total = int(places[-1])
+            pixel_offs = (total + 15) // 16 * 16 + np.cumsum([0] + [(h * w * 3 + 15) // 16 * 16 for h, w in (shapes[b] for b in jpeg_at)])
+            for i, b in enumerate(jpeg_at):
+                image_at[b] = int(pixel_offs[i])
+            status_off = int(pixel_offs[-1])
+            device_bytes = status_off + 4 * len(jpeg_at)
         turn, host = self._staging(total)
         hview = host.numpy()
         descs = hview[desc_off:target_off].view(_CROP_DESC)
-        targets_host = hview[target_off:total].view(np.int64)
+        targets_host = hview[target_off:target_off + 8 * B].view(np.int64)
         for b, ((img, target), q) in enumerate(zip(samples, windows)):
             h, w = shapes[b]
-            np.copyto(hview[offs[b]:offs[b + 1]].reshape(h, w, 3), img[q.top:q.top + h, q.left:q.left + w])
+            if not isinstance(img, jp.JpegImage):
+                np.copyto(hview[offs[b]:offs[b + 1]].reshape(h, w, 3), img[q.top:q.top + h, q.left:q.left + w])
             # the shipped image IS the crop: tap indices are relative to the crop and never leave it, so nothing else is read
-            descs[b] = (int(offs[b]), h, w, 0, 0, h, w, q.rh, q.rw, q.oy, q.ox, int(bool(q.flip)), int(bool(q.antialias)))
+            descs[b] = (image_at[b], h, w, 0, 0, h, w, q.rh, q.rw, q.oy, q.ox, int(bool(q.flip)), int(bool(q.antialias)))
             targets_host[b] = int(target)
+        if jpeg_at:
+            jdescs = hview[jpeg_off:jpeg_off + jp.WIN_DESC.itemsize * len(jpeg_at)].view(jp.WIN_DESC)
+            jinfos = []
+            ws_offs = np.cumsum([0] + [p.ws_bytes for p in plans])
+            for i, (b, p) in enumerate(zip(jpeg_at, plans)):
+                it = samples[b][0]
+                stream_at, tables_at, _, info = it.stage_window(hview, int(places[i]), p.window, p)
+                jinfos.append(info)
+                jdescs[i] = it.window_desc(p, stream_at, tables_at, image_at[b], int(ws_offs[i]), 3 * shapes[b][1])
 
         dev = torch.device(self.device)
         with torch.cuda.device(dev):
             cur = torch.cuda.current_stream(dev)
-            raw = host[:total].to(dev, non_blocking=True)
+            if jpeg_at:
+                raw = torch.empty(device_bytes, device=dev, dtype=torch.uint8)
+                raw[:total].copy_(host[:total], non_blocking=True)
+            else:
+                raw = host[:total].to(dev, non_blocking=True)
             copied = torch.cuda.Event()
             copied.record(cur)
             self._stage_free[turn] = copied
-            self.last_h2d_bytes, self.last_launches = total, 1
+            self.last_h2d_bytes, self.last_launches = total, 4 if jpeg_at else 1
             images = torch.empty((B, 3, S, S), device=dev, dtype=torch.float32)
             base = raw.data_ptr()
+            self._jpeg_status = None
+            if jpeg_at:  # the pixels of the JpegImage samples first: the launch below reads them
+                work = torch.empty(max(int(ws_offs[-1]), 16), device=dev, dtype=torch.uint8)
+                jp.launch_decode_window(dev, base, base + jpeg_off, jdescs, np.concatenate(jinfos), work, base + status_off)
+                self._jpeg_status = raw[status_off:status_off + 4 * len(jpeg_at)].view(torch.int32)
             # the descriptors are checked on their HOST copy in the staging buffer (nothing is read back from the device)
             _lib.launch(dev, lib.hh_resized_crop_u8_batch, base, base + desc_off, descs.ctypes.data, B, images.data_ptr(), S, S,
                         self.mean.ctypes.data, self.std.ctypes.data)
-            targets = raw[target_off:total].view(torch.int64)
+            targets = raw[target_off:target_off + 8 * B].view(torch.int64)
         return images, targets
+
+    def jpeg_status(self, check: bool = True) -> np.ndarray:
+        """The decoder's statuses of the last build's JpegImage samples, in batch order: int32 [n], 0 = decoded.  This is the read
+        `build` does not do: it waits for the build's work.  `check`: a nonzero status raises HHError naming the image (its position
+        among the JpegImage samples) and the code.  A status covers the walked part of the scan only; the index pass (or restart scan)
+        of `JpegImage(...)` has validated the whole stream."""
+        if self._jpeg_status is None:
+            return np.zeros(0, np.int32)
+        status = self._jpeg_status.cpu().numpy()
+        if check:
+            jp.raise_status(status, "ClsInput.build (hh_jpeg_decode_window_u8_batch)")
+        return status

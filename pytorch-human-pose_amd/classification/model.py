@@ -9,6 +9,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from ..keypoints import jpeg as jp
 from ..keypoints.model import BaseModel, checkpoint_weights, parse_checkpoint
 from .input import ClsInput, inference_geometry
 
@@ -66,8 +67,12 @@ class InferenceClassificationModel:
         self.net.load_state_dict(parse_checkpoint(checkpoint_weights(ckpt, use_ema)))
 
     def prepare_inputs(self, images: list) -> torch.Tensor:
-        """[uint8 HWC image] -> [B,3,input_size,input_size] on the device: Resize(input_size) + CenterCrop(input_size) + Normalize."""
+        """[uint8 HWC image] -> [B,3,input_size,input_size] on the device: Resize(input_size) + CenterCrop(input_size) + Normalize.
+        An image may also be a `jpeg.JpegImage` or the raw `bytes` of a JPEG file: its pixels are then formed on the device by the
+        batch's one window-decode call (`ClsInput.build`).  A stream the decoder does not take (progressive, CMYK, ...) raises by name
+        here; pass such a file as a Pillow array in the same batch."""
         size = self.input_size
+        images = [jp.JpegImage(im) if isinstance(im, (bytes, bytearray, memoryview)) else im for im in images]
         geometry = [inference_geometry(im.shape[0], im.shape[1], resize=size, crop=size) for im in images]
         return self._input.build([(im, 0) for im in images], geometry)[0]
 
@@ -87,7 +92,8 @@ class InferenceClassificationModel:
 
     def infer_images(self, raw_images: list, target_labels: list | None = None, max_batch: int = 32) -> list:
         """One record per image, in order, from batches of up to `max_batch` images of any sizes (one input launch + one engine
-        forward per batch): what `__call__` returns for each."""
+        forward per batch): what `__call__` returns for each.  An image may be a uint8 array, a `jpeg.JpegImage` or a JPEG file's
+        `bytes` (three more launches per batch that holds one); a record's `raw_image` is what was passed."""
         if target_labels is not None and len(target_labels) != len(raw_images):
             raise ValueError("infer_images: one target label per image")
         out = []
@@ -98,5 +104,5 @@ class InferenceClassificationModel:
             out += self._records(chunk, logits, None if target_labels is None else target_labels[i:i + max_batch])
         return out
 
-    def __call__(self, raw_image: np.ndarray, target_label: int | str | None = None) -> InferenceClassificationResult:
+    def __call__(self, raw_image, target_label: int | str | None = None) -> InferenceClassificationResult:
         return self.infer_images([raw_image], [target_label])[0]

@@ -456,7 +456,8 @@ static const char *const JPEG_STATUS_NAME[6] = {"ok", "bad Huffman code", "zero 
                                                 "missing or unexpected RSTm", "bad segment"};
 
 // What the kernels trust of a stream's info; nullptr if it is what hh_jpeg_parse can have written.
-static const char *jpeg_dec_check_info(const JpegStreamInfo &I)
+// rebased: the info of a window decode's table block, whose scan is the shipped slice (scan_offset 0).
+static const char *jpeg_dec_check_info(const JpegStreamInfo &I, bool rebased = false)
 {
     if (I.h < 1 || I.w < 1 || I.h > 65535 || I.w > 65535) return "bad stream info: h and w must lie in 1..65535";
     const bool grey = I.ncomp == 1 && I.hs == 1 && I.vs == 1 && I.bpm == 1;
@@ -467,7 +468,7 @@ static const char *jpeg_dec_check_info(const JpegStreamInfo &I)
         return "dimensions beyond what int32 offsets allow";
     for (int c = 0; c < 3; ++c)
         if ((I.qt[c] | I.dc[c] | I.ac[c]) & ~3) return "bad stream info: a table id outside 0..3";
-    if (I.scan_offset < 2 || I.scan_end < I.scan_offset || I.scan_end > INT32_MAX) return "bad stream info: the scan's bytes";
+    if (I.scan_offset < (rebased ? 0 : 2) || I.scan_end < I.scan_offset || I.scan_end > INT32_MAX) return "bad stream info: the scan's bytes";
     return nullptr;
 }
 
@@ -605,6 +606,140 @@ int hh_debug_jpeg_decode_host(const unsigned char *bytes, long long len, const h
     }
     if (status) *status = st;
     jpeg_dec_pixels_host(reinterpret_cast<unsigned char *>(ws.data()), I, T[0], flags & 1, dst, pitch);
+    if (st) { hh_set_error(fn + ": status " + std::to_string(st) + " (" + JPEG_STATUS_NAME[st] + ")"); return 1; }
+    return 0;
+}
+
+// The window decode (the rule: hh_jpeg_decode_window_u8_batch in include/hhrnet.h).
+static_assert(sizeof(hh_jpeg_window) == sizeof(JpegWindow) && sizeof(hh_jpeg_win_desc) == sizeof(JpegWinDesc) &&
+                  sizeof(hh_jpeg_window_counts) == sizeof(JpegWinCounts),
+              "table layout");
+
+long long hh_jpeg_decode_window_workspace_bytes(const hh_jpeg_stream_info *info, const hh_jpeg_window *window)
+{
+    const char *why = info && window ? jpeg_dec_check_info(*reinterpret_cast<const JpegStreamInfo *>(info), true) : "null pointer";
+    if (!why) why = jpeg_win_check(*reinterpret_cast<const JpegStreamInfo *>(info), *reinterpret_cast<const JpegWindow *>(window));
+    if (why) { hh_set_error(std::string("hh_jpeg_decode_window_workspace_bytes: ") + why); return -1; }
+    const JpegStreamInfo &I = *reinterpret_cast<const JpegStreamInfo *>(info);
+    return jpeg_win_geom(I, jpeg_win_rect(I, *reinterpret_cast<const JpegWindow *>(window))).ws_bytes;
+}
+
+int hh_jpeg_decode_window_select(const hh_jpeg_stream_info *info, const hh_jpeg_segment *entries, int nseg, const hh_jpeg_window *window, int *nsel,
+                                 long long slice[2])
+{
+    const std::string fn = "hh_jpeg_decode_window_select";
+    if (!info || !entries || !window || !nsel || !slice) { hh_set_error(fn + ": null pointer"); return 1; }
+    const JpegStreamInfo &I = *reinterpret_cast<const JpegStreamInfo *>(info);
+    const JpegWindow &W = *reinterpret_cast<const JpegWindow *>(window);
+    const char *why = jpeg_dec_check_info(I);
+    if (!why && nseg < 1) why = "nseg must be at least 1";
+    if (!why) why = jpeg_win_check(I, W);
+    if (!why) why = jpeg_win_select(I, jpeg_win_rect(I, W), reinterpret_cast<const JpegSegment *>(entries), nseg, nsel, slice);
+    if (why) { hh_set_error(fn + ": " + why); return 1; }
+    return 0;
+}
+
+int hh_jpeg_decode_window_tables(const unsigned char *bytes, long long len, const hh_jpeg_segment *entries, int nseg, const hh_jpeg_window *window,
+                                 unsigned char *out, long long out_bytes, int *nsel, long long slice[2])
+{
+    const std::string fn = "hh_jpeg_decode_window_tables";
+    if (!bytes || !entries || !window || !out || !nsel || !slice) { hh_set_error(fn + ": null pointer"); return 1; }
+    JpegStreamInfo I;
+    std::vector<JpegDecTables> T(1);
+    const JpegWindow &W = *reinterpret_cast<const JpegWindow *>(window);
+    const char *why = nseg < 1 ? "nseg must be at least 1" : jpeg_dec_parse(bytes, len, &I, &T[0]);
+    if (!why) why = jpeg_win_check(I, W);
+    int n = 0;
+    long long sl[2] = {0, 0};
+    if (!why) why = jpeg_win_select(I, jpeg_win_rect(I, W), reinterpret_cast<const JpegSegment *>(entries), nseg, &n, sl);
+    if (!why && out_bytes < jpeg_dec_tables_bytes(n)) why = "room below hh_jpeg_decode_tables_bytes of the selected segments";
+    if (why) { hh_set_error(fn + ": " + why); return 1; }
+    jpeg_win_tables(I, T[0], jpeg_win_rect(I, W), reinterpret_cast<const JpegSegment *>(entries), nseg, sl, out);
+    *nsel = n, slice[0] = sl[0], slice[1] = sl[1];
+    return 0;
+}
+
+int hh_jpeg_decode_window_u8_batch(unsigned char *batch_base, const hh_jpeg_win_desc *descs_dev, const hh_jpeg_win_desc *descs_host,
+                                   const hh_jpeg_stream_info *infos_host, int n, unsigned char *workspace, long long workspace_bytes,
+                                   int32_t *status_dev, void *stream)
+{
+    const std::string fn = "hh_jpeg_decode_window_u8_batch";
+    if (!batch_base || !descs_dev || !descs_host || !infos_host || !workspace || !status_dev) { hh_set_error(fn + ": null pointer"); return 1; }
+    if (n < 1 || n > 65535) { hh_set_error(fn + ": need 1 <= n <= 65535"); return 1; }
+    if ((uintptr_t)descs_dev % 8 || (uintptr_t)workspace % 16 || (uintptr_t)status_dev % 4) {
+        hh_set_error(fn + ": descs_dev must be 8-byte, workspace 16-byte and status_dev 4-byte aligned");
+        return 1;
+    }
+    int max_seg = 1, max_blk = 1, max_h = 1, max_w = 1;
+    for (int b = 0; b < n; ++b) {
+        const JpegWinDesc &wd = reinterpret_cast<const JpegWinDesc *>(descs_host)[b];
+        const JpegDecDesc &d = wd.d;
+        const JpegStreamInfo &I = reinterpret_cast<const JpegStreamInfo *>(infos_host)[b];  // (rebased to the slice: hh_jpeg_decode_window_tables)
+        const char *why = jpeg_dec_check_info(I, true);
+        if (!why) why = jpeg_win_check(I, wd.win);
+        if (!why && (d.stream_offset < 0 || d.tables_offset < 0 || d.dst_offset < 0 || d.ws_offset < 0)) why = "negative offset";
+        if (!why && d.pitch < 3ll * wd.win.width) why = "pitch below 3 * width";
+        if (!why && (d.flags & ~1)) why = "unknown flag";
+        if (!why && d.nseg < 1) why = "no selected segment (nseg must be at least 1)";
+        if (!why && (d.stream_length < 1 || I.scan_end > d.stream_length)) why = "the scan's bytes lie outside the slice's length";
+        if (!why && d.tables_bytes < jpeg_dec_tables_bytes(d.nseg)) why = "table block below hh_jpeg_decode_tables_bytes";
+        if (!why && ((uintptr_t)(batch_base + d.tables_offset) % 16 || d.ws_offset % 16)) why = "the table block and ws_offset must be 16-byte aligned";
+        if (why) { hh_set_error(fn + ": image " + std::to_string(b) + ": " + why); return 1; }
+        const JpegDecGeom g = jpeg_win_geom(I, jpeg_win_rect(I, wd.win));
+        if (d.ws_offset + g.ws_bytes > workspace_bytes) {
+            hh_set_error(fn + ": image " + std::to_string(b) + ": workspace below hh_jpeg_decode_window_workspace_bytes");
+            return 1;
+        }
+        max_seg = std::max(max_seg, d.nseg), max_blk = std::max(max_blk, g.nblk), max_h = std::max(max_h, wd.win.height), max_w = std::max(max_w, wd.win.width);
+    }
+    HH_CHECK_HIP(hipMemsetAsync(status_dev, 0, (size_t)n * 4, (hipStream_t)stream));
+    HH_CHECK_HIP(launch_jpeg_decode_window(batch_base, reinterpret_cast<const JpegWinDesc *>(descs_dev), n, max_seg, max_blk, max_h, max_w, workspace,
+                                           status_dev, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_debug_jpeg_decode_window_host(const unsigned char *bytes, long long len, const hh_jpeg_segment *entries, int nseg, const hh_jpeg_window *window,
+                                     int flags, unsigned char *dst, long long pitch, int *status, hh_jpeg_window_counts *counts)
+{
+    const std::string fn = "hh_debug_jpeg_decode_window_host";
+    if (!bytes || !dst || !window) { hh_set_error(fn + ": null pointer"); return 1; }
+    if (status) *status = 0;
+    JpegStreamInfo I;
+    std::vector<JpegDecTables> T(1);
+    const JpegWindow &W = *reinterpret_cast<const JpegWindow *>(window);
+    const char *why = jpeg_dec_parse(bytes, len, &I, &T[0]);
+    if (!why) why = jpeg_win_check(I, W);
+    if (!why && pitch < 3ll * W.width) why = "pitch below 3 * width";
+    if (!why && (flags & ~1)) why = "unknown flag";
+    if (!why && entries && nseg < 1) why = "nseg must be at least 1";
+    std::vector<JpegSegment> own;
+    if (!why && !entries) {
+        if (I.restart_interval) {
+            own.resize(I.nseg_restart);
+            why = jpeg_dec_restart_segments(bytes, I, own.data());
+        } else {
+            JpegSegment all = {0, I.mcols * I.mrows, (int32_t)I.scan_offset, 0, {0, 0, 0}, (int32_t)(I.scan_end << 1)};
+            own.push_back(all);
+        }
+        entries = reinterpret_cast<const hh_jpeg_segment *>(own.data());
+        nseg = (int)own.size();
+    }
+    const JpegSegment *seg = reinterpret_cast<const JpegSegment *>(entries);
+    const JpegWinRect R = why ? JpegWinRect() : jpeg_win_rect(I, W);
+    int nsel = 0;
+    long long slice[2] = {0, 0};
+    if (!why) why = jpeg_win_select(I, R, seg, nseg, &nsel, slice);
+    if (why) { hh_set_error(fn + ": " + why); return 1; }
+    // what the device receives: the table block of the selected segments, the slice in a block of its own, the rectangle's workspace
+    std::vector<JpegVec8> block((size_t)jpeg_dec_tables_bytes(nsel) / 16 + 1), ws((size_t)jpeg_win_geom(I, R).ws_bytes / 16 + 1);
+    jpeg_win_tables(I, T[0], R, seg, nseg, slice, reinterpret_cast<unsigned char *>(block.data()));
+    const std::vector<unsigned char> part(bytes + slice[0], bytes + slice[1]);
+    memset(ws.data(), 0, ws.size() * 16);
+    JpegWinCounts local = {0, 0, 0, 0, 0, 0};
+    const int st = jpeg_dec_window_host(part.data(), (int)part.size(), reinterpret_cast<const unsigned char *>(block.data()), nsel, W, flags & 1,
+                                        reinterpret_cast<unsigned char *>(ws.data()), dst, pitch, &local, nullptr);
+    if (counts) memcpy(counts, &local, sizeof(local));
+    if (status) *status = st;
     if (st) { hh_set_error(fn + ": status " + std::to_string(st) + " (" + JPEG_STATUS_NAME[st] + ")"); return 1; }
     return 0;
 }

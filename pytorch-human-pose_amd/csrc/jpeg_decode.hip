@@ -83,3 +83,75 @@ hipError_t launch_jpeg_decode(unsigned char *base, const JpegDecDesc *descs, int
     hipLaunchKernelGGL(jpeg_dec_colour_kernel, dim3((max_w + 63) / 64, (max_h + 3) / 4, n), dim3(64, 4), 0, s, base, ws, descs);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------------------------- window decode
+// hh_jpeg_decode_window_u8_batch: the same three launches over a window's MCU rectangle (jpeg_win_rect).  The table block holds only
+// the segments with an MCU in the rectangle, and the stream is the slice they need, offsets rebased to it (jpeg_win_tables): a lane
+// walks its segment from its first MCU to its last MCU inside the rectangle and stores only the MCUs inside; the IDCT covers the
+// rectangle's blocks, the colour launch the window's pixels.  Coefficients and planes are laid out for the rectangle (jpeg_win_geom).
+__global__ __launch_bounds__(64) void jpeg_win_entropy_kernel(const unsigned char *__restrict__ base, unsigned char *__restrict__ ws,
+                                                              const JpegWinDesc *__restrict__ descs, int32_t *__restrict__ status)
+{
+    __shared__ JpegHuff huff[8];
+    const JpegWinDesc wd = descs[blockIdx.z];
+    const JpegDecDesc &d = wd.d;
+    if ((int)blockIdx.x * 64 >= d.nseg) return;  // (the whole workgroup: the grid is sized for the image with most selected segments)
+    const unsigned char *tab = jpeg_dec_tables(base, d);
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(tab + JPEG_DEC_TABLES_AT + offsetof(JpegDecTables, huff));
+    for (int i = threadIdx.x; i < (int)(sizeof(huff) / 4); i += 64) reinterpret_cast<uint32_t *>(huff)[i] = src[i];
+    __syncthreads();
+    const int s = (int)blockIdx.x * 64 + (int)threadIdx.x;
+    if (s >= d.nseg) return;
+    const JpegStreamInfo I = *reinterpret_cast<const JpegStreamInfo *>(tab);
+    const JpegSegment sg = reinterpret_cast<const JpegSegment *>(tab + JPEG_DEC_SEGS_AT)[s];
+    const int st = jpeg_dec_window_segment(base + d.stream_offset, d.stream_length, I, huff, sg, jpeg_win_rect(I, wd.win),
+                                           reinterpret_cast<int16_t *>(ws + d.ws_offset), nullptr, nullptr);
+    if (st) atomicMax(status + blockIdx.z, st);
+}
+
+__global__ __launch_bounds__(8 * JPEG_DEC_IDCT_BLOCKS) void jpeg_win_idct_kernel(const unsigned char *__restrict__ base, unsigned char *__restrict__ ws,
+                                                                                 const JpegWinDesc *__restrict__ descs)
+{
+    __shared__ int32_t tmp[JPEG_DEC_IDCT_BLOCKS * JPEG_DEC_LDS_STRIDE];
+    const JpegWinDesc wd = descs[blockIdx.z];
+    const unsigned char *tab = jpeg_dec_tables(base, wd.d);
+    const JpegStreamInfo I = *reinterpret_cast<const JpegStreamInfo *>(tab);
+    const JpegWinRect R = jpeg_win_rect(I, wd.win);
+    const JpegDecGeom g = jpeg_win_geom(I, R);
+    if ((int)blockIdx.x * JPEG_DEC_IDCT_BLOCKS >= g.nblk) return;  // (the whole workgroup)
+    const int t = threadIdx.x & 7, lb = threadIdx.x >> 3;
+    const int blk = (int)blockIdx.x * JPEG_DEC_IDCT_BLOCKS + lb;
+    const bool have = blk < g.nblk;
+    unsigned char *iws = ws + wd.d.ws_offset;
+    int c = 0;
+    long long at = 0;
+    if (have) {
+        jpeg_win_block_place(I, R, g, blk, c, at);
+        const uint16_t *q = reinterpret_cast<const uint16_t *>(tab + JPEG_DEC_TABLES_AT) + (I.qt[c] & 3) * 64;
+        jpeg_idct_col(reinterpret_cast<const int16_t *>(iws) + (size_t)blk * 64, q, t, tmp + lb * JPEG_DEC_LDS_STRIDE);
+    }
+    __syncthreads();
+    if (have) *reinterpret_cast<JpegRow8 *>(iws + at + (size_t)t * g.pw[c]) = jpeg_idct_row(tmp + lb * JPEG_DEC_LDS_STRIDE + t * 8);
+}
+
+__global__ __launch_bounds__(256) void jpeg_win_colour_kernel(unsigned char *__restrict__ base, const unsigned char *__restrict__ ws,
+                                                              const JpegWinDesc *__restrict__ descs)
+{
+    const JpegWinDesc wd = descs[blockIdx.z];
+    const int x = (int)blockIdx.x * 64 + (int)threadIdx.x, y = (int)blockIdx.y * 4 + (int)threadIdx.y;
+    if (x >= wd.win.width || y >= wd.win.height) return;
+    const JpegStreamInfo I = *reinterpret_cast<const JpegStreamInfo *>(jpeg_dec_tables(base, wd.d));
+    const JpegWinRect R = jpeg_win_rect(I, wd.win);
+    jpeg_win_pixel(ws + wd.d.ws_offset, I, R, jpeg_win_geom(I, R), wd.win.top + y, wd.win.left + x, wd.d.flags & 1,
+                   base + wd.d.dst_offset + (size_t)y * (size_t)wd.d.pitch + (size_t)x * 3);
+}
+
+hipError_t launch_jpeg_decode_window(unsigned char *base, const JpegWinDesc *descs, int n, int max_seg, int max_blk, int max_h, int max_w,
+                                     unsigned char *ws, int32_t *status, hipStream_t s)
+{
+    hipLaunchKernelGGL(jpeg_win_entropy_kernel, dim3((max_seg + 63) / 64, 1, n), dim3(64), 0, s, base, ws, descs, status);
+    hipLaunchKernelGGL(jpeg_win_idct_kernel, dim3((max_blk + JPEG_DEC_IDCT_BLOCKS - 1) / JPEG_DEC_IDCT_BLOCKS, 1, n), dim3(8 * JPEG_DEC_IDCT_BLOCKS), 0, s,
+                       base, ws, descs);
+    hipLaunchKernelGGL(jpeg_win_colour_kernel, dim3((max_w + 63) / 64, (max_h + 3) / 4, n), dim3(64, 4), 0, s, base, ws, descs);
+    return hipGetLastError();
+}

@@ -371,6 +371,11 @@ hipError_t launch_jpeg_encode(unsigned char *base, const JpegDesc *descs, int n,
 struct JpegDecDesc;
 hipError_t launch_jpeg_decode(unsigned char *base, const JpegDecDesc *descs, int n, int max_seg, int max_blk, int max_h, int max_w, unsigned char *ws,
                               int32_t *status, hipStream_t s);
+// The window decode (hh_jpeg_win_desc): the same three launches, sized by the largest count of selected segments, the largest MCU
+// rectangle's blocks and the largest window.
+struct JpegWinDesc;
+hipError_t launch_jpeg_decode_window(unsigned char *base, const JpegWinDesc *descs, int n, int max_seg, int max_blk, int max_h, int max_w,
+                                     unsigned char *ws, int32_t *status, hipStream_t s);
 // Heatmap panels (hh_panel_map of include/hhrnet.h; struct and arithmetic in panel_math.h, kernels in panels.hip): the min/max launch
 // (only if any_minmax) and the paint launch of one figure; the same figure on the host; the un-normalise of the model input.
 struct PanelMap;

@@ -8,6 +8,9 @@ The way back is here too: `decode_jpeg_device` / `load_jpeg` stand for the refer
 (src/base/datasets/base.py:174,194) with Pillow's own bytes as the target (hh_jpeg_decode_u8_batch: one call of three launches for a
 batch of mixed streams; the rule is written at that entry point), `JpegImage` is what `TrainInput.build` takes in place of a pixel
 array, and `MJPEGReader` reads back what `MJPEGWriter` wrote.  `decode_jpeg_host` is the same rule compiled for the host, for tests.
+With `windows=` / `window=` only a rectangle of each image is decoded (hh_jpeg_decode_window_u8_batch: the same bytes as those rows and
+columns of the whole decode, from the segments and the byte slice that rectangle needs): what `classification.input.ClsInput` does with
+a `JpegImage` sample's crop.
 """
 from __future__ import annotations
 
@@ -266,9 +269,24 @@ SEGMENT = np.dtype([("first_mcu", "<i4"), ("mcu_count", "<i4"), ("byte_offset", 
 DEC_DESC = np.dtype([("stream_offset", "<i8"), ("tables_offset", "<i8"), ("tables_bytes", "<i8"), ("dst_offset", "<i8"), ("ws_offset", "<i8"),
                      ("pitch", "<i8"), ("stream_length", "<i4"), ("nseg", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
 assert INFO.itemsize == 112 and SEGMENT.itemsize == 32 and DEC_DESC.itemsize == 64
+# hh_jpeg_window, hh_jpeg_win_desc (hh_jpeg_dec_desc, then the window), hh_jpeg_window_counts
+WINDOW = np.dtype([("top", "<i4"), ("left", "<i4"), ("height", "<i4"), ("width", "<i4")])
+WIN_DESC = np.dtype(DEC_DESC.descr + [("window", WINDOW)])
+WIN_COUNTS = np.dtype([(k, "<i8") for k in ("segments_walked", "mcus_walked", "mcus_stored", "blocks_transformed", "pixels_written", "stream_bytes")])
+assert WINDOW.itemsize == 16 and WIN_DESC.itemsize == 80 and WIN_COUNTS.itemsize == 48
 STATUS_NAMES = ("ok", "bad Huffman code", "zero run past coefficient 63", "bytes exhausted", "missing or unexpected RSTm", "bad segment")
 
 JpegInfo = collections.namedtuple("JpegInfo", "h w components sampling restart_interval mcu_cols mcu_rows scan_offset scan_end")
+# what a window decode of one image needs: the count of selected segments, the slice [first, end) of the file, the sizes of its table
+# block and workspace, and what crosses the bus (slice and table block, each rounded up to 16)
+WindowPlan = collections.namedtuple("WindowPlan", "window nsel slice tables_bytes ws_bytes staged_bytes")
+
+
+def _window(window) -> np.ndarray:
+    top, left, height, width = (int(v) for v in window)
+    w = np.zeros(1, WINDOW)
+    w[0] = (top, left, height, width)
+    return w
 
 
 def _bytes_view(data) -> np.ndarray:
@@ -385,6 +403,46 @@ class JpegImage:
                                                      out.ctypes.data, self.tables_bytes))
         return at, tables_at
 
+    def window_plan(self, window) -> WindowPlan:
+        """hh_jpeg_decode_window_select for (top, left, height, width): the segments with an MCU in the window's MCU rectangle, the byte
+        slice they need, the table block's and the workspace's size.  A window that is empty or leaves the image is refused by name."""
+        lib = _lib.load()
+        w = _window(window)
+        nsel, sl = C.c_int(0), (C.c_longlong * 2)()
+        _lib.check(lib.hh_jpeg_decode_window_select(self.info.ctypes.data, self.segments.ctypes.data, len(self.segments), w.ctypes.data, C.byref(nsel), sl))
+        tables = int(lib.hh_jpeg_decode_tables_bytes(self.info.ctypes.data, nsel.value))
+        ws = int(lib.hh_jpeg_decode_window_workspace_bytes(self.info.ctypes.data, w.ctypes.data))
+        if tables < 0 or ws < 0:
+            _lib.check(1)
+        return WindowPlan(tuple(int(v) for v in w[0]), nsel.value, (int(sl[0]), int(sl[1])), tables, ws, _align(int(sl[1] - sl[0]), 16) + _align(tables, 16))
+
+    def stage_window(self, hview: np.ndarray, at: int, window, plan: WindowPlan | None = None) -> tuple[int, int, WindowPlan, np.ndarray]:
+        """The window's slice of the stream and its table block (selected segments only, offsets rebased to the slice) into the staging
+        bytes at `at` (a multiple of 16) -> (slice offset, tables offset, the plan, the rebased info the block starts with).  `plan`: this window's
+        `window_plan`, where the caller has it already."""
+        plan = self.window_plan(window) if plan is None else plan
+        first, end = plan.slice
+        tables_at = at + _align(end - first, 16)
+        hview[at:at + end - first] = self.data[first:end]
+        out = hview[tables_at:tables_at + plan.tables_bytes]
+        w = _window(window)
+        nsel, sl = C.c_int(0), (C.c_longlong * 2)()
+        _lib.check(_lib.load().hh_jpeg_decode_window_tables(self.data.ctypes.data, self.data.size, self.segments.ctypes.data, len(self.segments),
+                                                            w.ctypes.data, out.ctypes.data, plan.tables_bytes, C.byref(nsel), sl))
+        return at, tables_at, plan, out[:INFO.itemsize].view(INFO).copy()
+
+    def window_desc(self, plan: WindowPlan, stream_at: int, tables_at: int, dst_at: int, ws_at: int, pitch: int, bgr: bool = False) -> tuple:
+        """One WIN_DESC row for a staged window."""
+        return (stream_at, tables_at, plan.tables_bytes, dst_at, ws_at, pitch, plan.slice[1] - plan.slice[0], plan.nsel, FLAG_BGR if bgr else 0, 0,
+                plan.window)
+
+
+def launch_decode_window(dev, base: int, descs_dev: int, descs: np.ndarray, infos: np.ndarray, work, status_dev: int) -> None:
+    """hh_jpeg_decode_window_u8_batch on the current stream of `dev` (three launches behind the clearing of the statuses); `infos`: the
+    rebased infos `stage_window` returned."""
+    _lib.launch(dev, _lib.load().hh_jpeg_decode_window_u8_batch, base, descs_dev, descs.ctypes.data, infos.ctypes.data, len(descs), work.data_ptr(),
+                work.numel(), status_dev)
+
 
 def launch_decode(dev, base: int, descs_dev: int, descs: np.ndarray, infos: np.ndarray, work, status_dev: int) -> None:
     """hh_jpeg_decode_u8_batch on the current stream of `dev` (three launches behind the clearing of the statuses)."""
@@ -400,17 +458,25 @@ def raise_status(statuses, what: str = "hh_jpeg_decode_u8_batch") -> None:
         raise _lib.HHError(f"{what}: image {i}: status {s} ({name})" + (f"; also images {[j for j, _ in bad[1:]]}" if len(bad) > 1 else ""))
 
 
-def decode_jpeg_device(streams: list, index=None, bgr=False, device=None, out=None) -> list:
+def decode_jpeg_device(streams: list, index=None, bgr=False, device=None, out=None, windows=None) -> list:
     """One hh_jpeg_decode_u8_batch, on the current stream, for a batch of JPEG streams (bytes, uint8 arrays or JpegImage) of mixed sizes,
     samplings and tables -> one uint8 [h,w,3] device tensor per stream, R,G,B or (`bgr`: one value or one per stream) B,G,R.  `index`:
     None, or one entry per stream (None or a build_jpeg_index result); a stream without DRI and without an index has its index built
     on the spot.  Bytes, tables and descriptors travel in one pinned copy; then one read of the n statuses: a nonzero one raises
     HHError naming the image and the code.  `out`: optional destinations, one uint8 [h,w,3] device tensor (or row-pitched view) per
     stream, written in place of fresh tensors.  `decode_jpeg_device.last_status` / `.last_h2d_bytes` keep the statuses and the uploaded
-    bytes of the last call (the statuses also when it raises)."""
+    bytes of the last call (the statuses also when it raises).
+    `windows`: None, or one entry per stream, (top, left, height, width) or None (the whole image).  With any window given the call is
+    ONE hh_jpeg_decode_window_u8_batch: only the segments that hold an MCU of a window's MCU rectangle and the byte slice they need
+    cross the bus, only the window is turned into pixels, and that stream's tensor (and `out` entry) is [height, width, 3]."""
     n = len(streams)
     if n == 0:
         return []
+    if windows is not None:
+        if len(windows) != n:
+            raise ValueError("decode_jpeg_device: `windows` has one entry per stream")
+        if any(w is not None for w in windows):
+            return _decode_windows(streams, index, bgr, device, out, windows)
     idx = _per_frame(index, n) if isinstance(index, (list, tuple)) else [index] * n
     if index is not None and not isinstance(index, (list, tuple)) and n != 1:
         raise ValueError("decode_jpeg_device: `index` is a list with one entry per stream")
@@ -464,10 +530,84 @@ def decode_jpeg_device(streams: list, index=None, bgr=False, device=None, out=No
     return [buf[o:o + it.h * it.w * 3].view(it.h, it.w, 3) for o, it in zip(dst_at, items)]
 
 
-def decode_jpeg_host(data, bgr: bool = False, index=None, pitch: int | None = None) -> np.ndarray:
+def _decode_windows(streams, index, bgr, device, out, windows) -> list:
+    """decode_jpeg_device with windows: the same layout and the same one copy, through hh_jpeg_decode_window_u8_batch."""
+    n = len(streams)
+    idx = _per_frame(index, n) if isinstance(index, (list, tuple)) else [index] * n
+    if index is not None and not isinstance(index, (list, tuple)) and n != 1:
+        raise ValueError("decode_jpeg_device: `index` is a list with one entry per stream")
+    items = [s if isinstance(s, JpegImage) else JpegImage(s, i) for s, i in zip(streams, idx)]
+    wins = [(0, 0, it.h, it.w) if w is None else tuple(int(v) for v in w) for it, w in zip(items, windows)]
+    plans = [it.window_plan(w) for it, w in zip(items, wins)]
+    bgrs = _per_frame(bgr, n)
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    at = _align(WIN_DESC.itemsize * n, 16)
+    places = []
+    for p in plans:
+        places.append(at)
+        at += p.staged_bytes
+    upload = at
+    status_at = _align(at, 16)
+    at = status_at + 4 * n
+    dst_at = []
+    for p in plans:
+        at = _align(at, 16)
+        dst_at.append(at)
+        at += p.window[2] * p.window[3] * 3 if out is None else 0
+    ws_at = np.cumsum([0] + [p.ws_bytes for p in plans])
+    host = torch.empty(upload, dtype=torch.uint8).pin_memory()
+    hv = host.numpy()
+    hv[:] = 0
+    descs = hv[:WIN_DESC.itemsize * n].view(WIN_DESC)
+    buf = torch.empty(at, dtype=torch.uint8, device=device)  # [descriptors | slices and tables | statuses | pixels]
+    work = torch.empty(max(int(ws_at[-1]), 16), dtype=torch.uint8, device=device)
+    if out is not None:
+        if len(out) != n:
+            raise ValueError("decode_jpeg_device: one destination per stream")
+        for o, p in zip(out, plans):
+            if not (isinstance(o, torch.Tensor) and o.dtype == torch.uint8 and tuple(o.shape) == (p.window[2], p.window[3], 3) and o.device == buf.device
+                    and o.stride(2) == 1 and o.stride(1) == 3):
+                raise ValueError("a destination must be a uint8 [height,width,3] device tensor (or a row-pitched view of one) of the window's size")
+    base = min([buf.data_ptr()] + ([o.data_ptr() for o in out] if out is not None else []))
+    rel = buf.data_ptr() - base
+    infos = []
+    for j, (it, p) in enumerate(zip(items, plans)):
+        stream_at, tables_at, p, info = it.stage_window(hv, places[j], p.window, p)
+        infos.append(info)
+        dst = rel + dst_at[j] if out is None else out[j].data_ptr() - base
+        pitch = 3 * p.window[3] if out is None else int(out[j].stride(0))
+        descs[j] = it.window_desc(p, rel + stream_at, rel + tables_at, dst, int(ws_at[j]), pitch, bgrs[j])
+    buf[:upload].copy_(host, non_blocking=True)
+    launch_decode_window(device, base, buf.data_ptr(), descs, np.concatenate(infos), work, buf.data_ptr() + status_at)
+    status_host = torch.empty(n, dtype=torch.int32, pin_memory=True)
+    status_host.copy_(buf[status_at:status_at + 4 * n].view(torch.int32), non_blocking=True)
+    torch.cuda.current_stream(device).synchronize()
+    decode_jpeg_device.last_h2d_bytes, decode_jpeg_device.last_status = upload, status_host.numpy().copy()
+    raise_status(status_host.numpy(), "hh_jpeg_decode_window_u8_batch")
+    if out is not None:
+        return list(out)
+    return [buf[o:o + p.window[2] * p.window[3] * 3].view(p.window[2], p.window[3], 3) for o, p in zip(dst_at, plans)]
+
+
+def decode_jpeg_host(data, bgr: bool = False, index=None, pitch: int | None = None, window=None, counts: dict | None = None) -> np.ndarray:
     """hh_debug_jpeg_decode_host: one stream through the rule compiled for the host -> uint8 [h,w,3] (tests and the GPU tests' yardstick;
-    needs the library, no GPU).  `index`: decode from these segments instead of the stream's own."""
+    needs the library, no GPU).  `index`: decode from these segments instead of the stream's own.  `window` (top, left, height, width):
+    hh_debug_jpeg_decode_window_host instead -> uint8 [height,width,3]; `counts`: a dict that receives what that decode did (segments and
+    MCUs walked, MCUs stored, blocks transformed, pixels written, stream bytes needed)."""
     a = _bytes_view(data)
+    if window is not None:
+        win = _window(window)
+        hh, ww = int(win[0]["height"]), int(win[0]["width"])
+        pitch = 3 * ww if pitch is None else int(pitch)
+        out = np.zeros((max(hh, 0), max(pitch, 3 * ww, 0)), np.uint8)
+        status, cnt = C.c_int(0), np.zeros(1, WIN_COUNTS)
+        seg = None if index is None else np.ascontiguousarray(index)
+        _lib.check(_lib.load().hh_debug_jpeg_decode_window_host(a.ctypes.data, a.size, None if seg is None else seg.ctypes.data, 0 if seg is None else len(seg),
+                                                                win.ctypes.data, FLAG_BGR if bgr else 0, out.ctypes.data, pitch, C.byref(status),
+                                                                cnt.ctypes.data))
+        if counts is not None:
+            counts.update({k: int(cnt[0][k]) for k in WIN_COUNTS.names})
+        return np.ascontiguousarray(out[:, :3 * ww]).reshape(hh, ww, 3)
     i = _parse(a)[0]
     h, w = int(i["h"]), int(i["w"])
     pitch = 3 * w if pitch is None else int(pitch)
@@ -479,14 +619,17 @@ def decode_jpeg_host(data, bgr: bool = False, index=None, pitch: int | None = No
     return np.ascontiguousarray(out[:, :3 * w]).reshape(h, w, 3)
 
 
-def load_jpeg(path, device=None, cache: JpegIndexCache | None = None, bgr: bool = False):
+def load_jpeg(path, device=None, cache: JpegIndexCache | None = None, bgr: bool = False, window=None):
     """`np.array(Image.open(path).convert("RGB"))` with the pixels formed on the device -> uint8 [h,w,3] device tensor.  `cache`: a
-    JpegIndexCache that keeps the file's index from call to call."""
+    JpegIndexCache that keeps the file's index from call to call.  `window` (top, left, height, width): only that rectangle is decoded
+    -> uint8 [height,width,3]."""
     with open(path, "rb") as f:
         data = f.read()
     index = None
     if cache is not None and not jpeg_info(data).restart_interval:
         index = cache.get(path, data)
+    if window is not None:
+        return decode_jpeg_device([data], [index], bgr, device, windows=[window])[0]
     return decode_jpeg_device([data], [index], bgr, device)[0]
 
 
