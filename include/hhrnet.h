@@ -652,7 +652,8 @@ int hh_debug_jpeg_fdct(const int32_t samples[64], int32_t rows_out[64], int32_t 
  *   cut to the MCU grid.  Returns 1 with hh_last_error set, before any launch or clearing, for a null pointer, n outside 1..65535,
  *   misaligned descs_dev (8) / workspace (16) / status_dev (4) / table block (16), an info hh_jpeg_parse cannot have written, "negative
  *   offset", "pitch below 3 * w", an unknown flag, nseg < 1, a scan outside stream_length, "table block below
- *   hh_jpeg_decode_tables_bytes", "workspace below hh_jpeg_decode_workspace_bytes".
+ *   hh_jpeg_decode_tables_bytes", "workspace below hh_jpeg_decode_workspace_bytes".  It is the window decode (below) of the window
+ *   (0, 0, h, w), whose MCU rectangle is the MCU grid: the same kernels, with the whole stream and all nseg segments shipped.
  * hh_debug_jpeg_decode_host: the whole rule on one stream in HOST memory into dst (entries NULL: its own segments); *status receives the
  *   code, a nonzero one also returns 1.  For tests, tools/jpeg_decode_host_check.cpp, and as the yardstick of the GPU tests.
  * (Additive entry points: HH_ABI_VERSION stays 3.)                                                                           */
@@ -725,7 +726,7 @@ int hh_debug_jpeg_decode_host(const unsigned char *bytes, long long len, const h
  *   segment"; select / tables refuse "no segment holds an MCU of the window's rectangle".
  * hh_debug_jpeg_decode_window_host: the same shared code (csrc/jpeg_dec_math.h) on one stream in HOST memory, through the same
  *   select / tables / slice steps (the slice is copied out, so nothing outside it can be read); *counts (may be NULL) receives what
- *   was done.  A window equal to the whole image gives the bytes of hh_jpeg_decode_u8_batch, which is not routed through this code.
+ *   was done.  A window equal to the whole image gives the bytes of hh_jpeg_decode_u8_batch, which is the decode of that window.
  * (Additive entry points: HH_ABI_VERSION stays 3.)                                                                           */
 typedef struct hh_jpeg_window {
     int32_t top, left, height, width;

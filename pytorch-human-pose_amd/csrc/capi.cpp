@@ -511,7 +511,8 @@ long long hh_jpeg_decode_workspace_bytes(const hh_jpeg_stream_info *info)
 {
     const char *why = info ? jpeg_dec_check_info(*reinterpret_cast<const JpegStreamInfo *>(info)) : "null pointer";
     if (why) { hh_set_error(std::string("hh_jpeg_decode_workspace_bytes: ") + why); return -1; }
-    return jpeg_dec_geom(*reinterpret_cast<const JpegStreamInfo *>(info)).ws_bytes;
+    const JpegStreamInfo &I = *reinterpret_cast<const JpegStreamInfo *>(info);
+    return jpeg_dec_geom(I, jpeg_full_rect(I)).ws_bytes;
 }
 
 long long hh_jpeg_decode_tables_bytes(const hh_jpeg_stream_info *info, int nseg)
@@ -537,11 +538,32 @@ int hh_jpeg_decode_tables(const unsigned char *bytes, long long len, const hh_jp
     return 0;
 }
 
-int hh_jpeg_decode_u8_batch(unsigned char *batch_base, const hh_jpeg_dec_desc *descs_dev, const hh_jpeg_dec_desc *descs_host,
-                            const hh_jpeg_stream_info *infos_host, int n, unsigned char *workspace, long long workspace_bytes, int32_t *status_dev,
-                            void *stream)
+// One image of a batch call, `win`: its window (hh_jpeg_decode_window_u8_batch, whose info is rebased to the shipped slice:
+// hh_jpeg_decode_window_tables) or null (hh_jpeg_decode_u8_batch: the whole image) -> the refusal or nullptr, and the geometry.
+static const char *jpeg_dec_check_image(const unsigned char *batch_base, const JpegDecDesc &d, const JpegStreamInfo &I, const JpegWindow *win,
+                                        long long workspace_bytes, JpegDecGeom *g)
 {
-    const std::string fn = "hh_jpeg_decode_u8_batch";
+    const char *why = jpeg_dec_check_info(I, win != nullptr);
+    if (!why && win) why = jpeg_win_check(I, *win);
+    if (!why && (d.stream_offset < 0 || d.tables_offset < 0 || d.dst_offset < 0 || d.ws_offset < 0)) why = "negative offset";
+    if (!why && d.pitch < 3ll * (win ? win->width : I.w)) why = win ? "pitch below 3 * width" : "pitch below 3 * w";
+    if (!why && (d.flags & ~1)) why = "unknown flag";
+    if (!why && d.nseg < 1) why = win ? "no selected segment (nseg must be at least 1)" : "nseg must be at least 1";
+    if (!why && (d.stream_length < 1 || I.scan_end > d.stream_length))
+        why = win ? "the scan's bytes lie outside the slice's length" : "the scan's bytes lie outside the stream's length";
+    if (!why && d.tables_bytes < jpeg_dec_tables_bytes(d.nseg)) why = "table block below hh_jpeg_decode_tables_bytes";
+    if (!why && ((uintptr_t)(batch_base + d.tables_offset) % 16 || d.ws_offset % 16)) why = "the table block and ws_offset must be 16-byte aligned";
+    if (why) return why;
+    *g = jpeg_dec_geom(I, jpeg_win_rect(I, win ? *win : jpeg_full_window(I)));
+    if (d.ws_offset + g->ws_bytes > workspace_bytes) return win ? "workspace below hh_jpeg_decode_window_workspace_bytes" : "workspace below hh_jpeg_decode_workspace_bytes";
+    return nullptr;
+}
+
+// Both batch entries.  windowed: the descriptors are JpegWinDesc (a JpegDecDesc, then the window), else JpegDecDesc.
+static int jpeg_decode_batch(const std::string &fn, bool windowed, unsigned char *batch_base, const void *descs_dev, const void *descs_host,
+                             const hh_jpeg_stream_info *infos_host, int n, unsigned char *workspace, long long workspace_bytes, int32_t *status_dev,
+                             void *stream)
+{
     if (!batch_base || !descs_dev || !descs_host || !infos_host || !workspace || !status_dev) { hh_set_error(fn + ": null pointer"); return 1; }
     if (n < 1 || n > 65535) { hh_set_error(fn + ": need 1 <= n <= 65535"); return 1; }
     if ((uintptr_t)descs_dev % 8 || (uintptr_t)workspace % 16 || (uintptr_t)status_dev % 4) {
@@ -550,64 +572,95 @@ int hh_jpeg_decode_u8_batch(unsigned char *batch_base, const hh_jpeg_dec_desc *d
     }
     int max_seg = 1, max_blk = 1, max_h = 1, max_w = 1;
     for (int b = 0; b < n; ++b) {
-        const JpegDecDesc &d = reinterpret_cast<const JpegDecDesc *>(descs_host)[b];
+        const JpegWinDesc *wd = windowed ? static_cast<const JpegWinDesc *>(descs_host) + b : nullptr;
+        const JpegDecDesc &d = wd ? wd->d : static_cast<const JpegDecDesc *>(descs_host)[b];
         const JpegStreamInfo &I = reinterpret_cast<const JpegStreamInfo *>(infos_host)[b];
-        const char *why = jpeg_dec_check_info(I);
-        if (!why && (d.stream_offset < 0 || d.tables_offset < 0 || d.dst_offset < 0 || d.ws_offset < 0)) why = "negative offset";
-        if (!why && d.pitch < 3ll * I.w) why = "pitch below 3 * w";
-        if (!why && (d.flags & ~1)) why = "unknown flag";
-        if (!why && d.nseg < 1) why = "nseg must be at least 1";
-        if (!why && (d.stream_length < 1 || I.scan_end > d.stream_length)) why = "the scan's bytes lie outside the stream's length";
-        if (!why && d.tables_bytes < jpeg_dec_tables_bytes(d.nseg)) why = "table block below hh_jpeg_decode_tables_bytes";
-        if (!why && ((uintptr_t)(batch_base + d.tables_offset) % 16 || d.ws_offset % 16)) why = "the table block and ws_offset must be 16-byte aligned";
-        const JpegDecGeom g = jpeg_dec_geom(I);
-        if (!why && d.ws_offset + g.ws_bytes > workspace_bytes) why = "workspace below hh_jpeg_decode_workspace_bytes";
+        const JpegWindow *win = wd ? &wd->win : nullptr;
+        JpegDecGeom g;
+        const char *why = jpeg_dec_check_image(batch_base, d, I, win, workspace_bytes, &g);
         if (why) { hh_set_error(fn + ": image " + std::to_string(b) + ": " + why); return 1; }
-        max_seg = std::max(max_seg, d.nseg), max_blk = std::max(max_blk, g.nblk), max_h = std::max(max_h, I.h), max_w = std::max(max_w, I.w);
+        max_seg = std::max(max_seg, d.nseg), max_blk = std::max(max_blk, g.nblk);
+        max_h = std::max(max_h, win ? win->height : I.h), max_w = std::max(max_w, win ? win->width : I.w);
     }
     HH_CHECK_HIP(hipMemsetAsync(status_dev, 0, (size_t)n * 4, (hipStream_t)stream));
-    HH_CHECK_HIP(launch_jpeg_decode(batch_base, reinterpret_cast<const JpegDecDesc *>(descs_dev), n, max_seg, max_blk, max_h, max_w, workspace, status_dev,
-                                    (hipStream_t)stream));
+    HH_CHECK_HIP(windowed ? launch_jpeg_decode(batch_base, static_cast<const JpegWinDesc *>(descs_dev), n, max_seg, max_blk, max_h, max_w, workspace, status_dev,
+                                               (hipStream_t)stream)
+                          : launch_jpeg_decode(batch_base, static_cast<const JpegDecDesc *>(descs_dev), n, max_seg, max_blk, max_h, max_w, workspace, status_dev,
+                                               (hipStream_t)stream));
+    return 0;
+}
+
+int hh_jpeg_decode_u8_batch(unsigned char *batch_base, const hh_jpeg_dec_desc *descs_dev, const hh_jpeg_dec_desc *descs_host,
+                            const hh_jpeg_stream_info *infos_host, int n, unsigned char *workspace, long long workspace_bytes, int32_t *status_dev,
+                            void *stream)
+{
+    return jpeg_decode_batch("hh_jpeg_decode_u8_batch", false, batch_base, descs_dev, descs_host, infos_host, n, workspace, workspace_bytes, status_dev, stream);
+}
+
+// The segments of a stream when the caller gave none: its restart intervals, or the whole scan as one segment (no index is needed for
+// a single lane).
+static const char *jpeg_own_segments(const unsigned char *bytes, const JpegStreamInfo &I, std::vector<JpegSegment> &own)
+{
+    if (I.restart_interval) {
+        own.resize(I.nseg_restart);
+        return jpeg_dec_restart_segments(bytes, I, own.data());
+    }
+    own.push_back(JpegSegment{0, I.mcols * I.mrows, (int32_t)I.scan_offset, 0, {0, 0, 0}, (int32_t)(I.scan_end << 1)});
+    return nullptr;
+}
+
+// Both host twins.  window: null for the whole image, which is decoded from the stream and the entries as they are given
+// (hh_jpeg_decode_tables); a window from the selected segments and their slice (hh_jpeg_decode_window_tables).
+static int jpeg_decode_host(const std::string &fn, const unsigned char *bytes, long long len, const hh_jpeg_segment *entries, int nseg,
+                            const hh_jpeg_window *window, int flags, unsigned char *dst, long long pitch, int *status, hh_jpeg_window_counts *counts)
+{
+    if (status) *status = 0;
+    JpegStreamInfo I;
+    std::vector<JpegDecTables> T(1);
+    const char *why = jpeg_dec_parse(bytes, len, &I, &T[0]);
+    const JpegWindow W = why ? JpegWindow() : window ? *reinterpret_cast<const JpegWindow *>(window) : jpeg_full_window(I);
+    if (!why && window) why = jpeg_win_check(I, W);
+    if (!why && pitch < 3ll * W.width) why = window ? "pitch below 3 * width" : "pitch below 3 * w";
+    if (!why && (flags & ~1)) why = "unknown flag";
+    if (!why && entries && nseg < 1) why = "nseg must be at least 1";
+    std::vector<JpegSegment> own;
+    if (!why && !entries) {
+        why = jpeg_own_segments(bytes, I, own);
+        entries = reinterpret_cast<const hh_jpeg_segment *>(own.data());
+        nseg = (int)own.size();
+    }
+    const JpegSegment *seg = reinterpret_cast<const JpegSegment *>(entries);
+    const JpegWinRect R = why ? JpegWinRect() : jpeg_win_rect(I, W);
+    int nsel = nseg;
+    long long slice[2] = {0, len};
+    if (!why && window) why = jpeg_win_select(I, R, seg, nseg, &nsel, slice);
+    if (why) { hh_set_error(fn + ": " + why); return 1; }
+    // what the device receives: the table block, the stream or the slice in a block of its own, the rectangle's workspace
+    const std::vector<unsigned char> part(bytes + slice[0], bytes + slice[1]);
+    std::vector<JpegVec8> block((size_t)jpeg_dec_tables_bytes(nsel) / 16 + 1), ws((size_t)jpeg_dec_geom(I, R).ws_bytes / 16 + 1);
+    unsigned char *blk = reinterpret_cast<unsigned char *>(block.data());
+    if (window) {
+        jpeg_win_tables(I, T[0], R, seg, nseg, slice, blk);
+    } else {
+        memcpy(blk, &I, sizeof(I));
+        memcpy(blk + JPEG_DEC_TABLES_AT, &T[0], sizeof(JpegDecTables));
+        memcpy(blk + JPEG_DEC_SEGS_AT, seg, (size_t)nseg * sizeof(JpegSegment));
+    }
+    memset(ws.data(), 0, ws.size() * 16);
+    JpegWinCounts local = {0, 0, 0, 0, 0, 0};
+    const int st = jpeg_dec_window_host(part.data(), (int)part.size(), blk, nsel, W, flags & 1, reinterpret_cast<unsigned char *>(ws.data()), dst, pitch, &local,
+                                        nullptr);
+    if (counts) memcpy(counts, &local, sizeof(local));
+    if (status) *status = st;
+    if (st) { hh_set_error(fn + ": status " + std::to_string(st) + " (" + JPEG_STATUS_NAME[st] + ")"); return 1; }
     return 0;
 }
 
 int hh_debug_jpeg_decode_host(const unsigned char *bytes, long long len, const hh_jpeg_segment *entries, int nseg, int flags, unsigned char *dst,
                               long long pitch, int *status)
 {
-    const std::string fn = "hh_debug_jpeg_decode_host";
-    if (!bytes || !dst) { hh_set_error(fn + ": null pointer"); return 1; }
-    if (status) *status = 0;
-    JpegStreamInfo I;
-    std::vector<JpegDecTables> T(1);
-    const char *why = jpeg_dec_parse(bytes, len, &I, &T[0]);
-    if (!why && pitch < 3ll * I.w) why = "pitch below 3 * w";
-    if (!why && (flags & ~1)) why = "unknown flag";
-    if (!why && entries && nseg < 1) why = "nseg must be at least 1";
-    std::vector<JpegSegment> own;
-    if (!why && !entries) {
-        if (I.restart_interval) {
-            own.resize(I.nseg_restart);
-            why = jpeg_dec_restart_segments(bytes, I, own.data());
-        } else {  // the whole scan as one segment: no index is needed for a single lane
-            JpegSegment all = {0, I.mcols * I.mrows, (int32_t)I.scan_offset, 0, {0, 0, 0}, (int32_t)(I.scan_end << 1)};
-            own.push_back(all);
-        }
-        entries = reinterpret_cast<const hh_jpeg_segment *>(own.data());
-        nseg = (int)own.size();
-    }
-    if (why) { hh_set_error(fn + ": " + why); return 1; }
-    const JpegDecGeom g = jpeg_dec_geom(I);
-    std::vector<JpegVec8> ws((size_t)g.ws_bytes / 16 + 1);
-    memset(ws.data(), 0, ws.size() * 16);
-    int st = 0;
-    for (int s = 0; s < nseg; ++s) {
-        const int one = jpeg_dec_segment<true>(bytes, (int)len, I, T[0].huff, reinterpret_cast<const JpegSegment *>(entries)[s], ws[0].v, nullptr, nullptr);
-        st = std::max(st, one);
-    }
-    if (status) *status = st;
-    jpeg_dec_pixels_host(reinterpret_cast<unsigned char *>(ws.data()), I, T[0], flags & 1, dst, pitch);
-    if (st) { hh_set_error(fn + ": status " + std::to_string(st) + " (" + JPEG_STATUS_NAME[st] + ")"); return 1; }
-    return 0;
+    if (!bytes || !dst) { hh_set_error("hh_debug_jpeg_decode_host: null pointer"); return 1; }
+    return jpeg_decode_host("hh_debug_jpeg_decode_host", bytes, len, entries, nseg, nullptr, flags, dst, pitch, status, nullptr);
 }
 
 // The window decode (the rule: hh_jpeg_decode_window_u8_batch in include/hhrnet.h).
@@ -621,7 +674,7 @@ long long hh_jpeg_decode_window_workspace_bytes(const hh_jpeg_stream_info *info,
     if (!why) why = jpeg_win_check(*reinterpret_cast<const JpegStreamInfo *>(info), *reinterpret_cast<const JpegWindow *>(window));
     if (why) { hh_set_error(std::string("hh_jpeg_decode_window_workspace_bytes: ") + why); return -1; }
     const JpegStreamInfo &I = *reinterpret_cast<const JpegStreamInfo *>(info);
-    return jpeg_win_geom(I, jpeg_win_rect(I, *reinterpret_cast<const JpegWindow *>(window))).ws_bytes;
+    return jpeg_dec_geom(I, jpeg_win_rect(I, *reinterpret_cast<const JpegWindow *>(window))).ws_bytes;
 }
 
 int hh_jpeg_decode_window_select(const hh_jpeg_stream_info *info, const hh_jpeg_segment *entries, int nseg, const hh_jpeg_window *window, int *nsel,
@@ -663,85 +716,15 @@ int hh_jpeg_decode_window_u8_batch(unsigned char *batch_base, const hh_jpeg_win_
                                    const hh_jpeg_stream_info *infos_host, int n, unsigned char *workspace, long long workspace_bytes,
                                    int32_t *status_dev, void *stream)
 {
-    const std::string fn = "hh_jpeg_decode_window_u8_batch";
-    if (!batch_base || !descs_dev || !descs_host || !infos_host || !workspace || !status_dev) { hh_set_error(fn + ": null pointer"); return 1; }
-    if (n < 1 || n > 65535) { hh_set_error(fn + ": need 1 <= n <= 65535"); return 1; }
-    if ((uintptr_t)descs_dev % 8 || (uintptr_t)workspace % 16 || (uintptr_t)status_dev % 4) {
-        hh_set_error(fn + ": descs_dev must be 8-byte, workspace 16-byte and status_dev 4-byte aligned");
-        return 1;
-    }
-    int max_seg = 1, max_blk = 1, max_h = 1, max_w = 1;
-    for (int b = 0; b < n; ++b) {
-        const JpegWinDesc &wd = reinterpret_cast<const JpegWinDesc *>(descs_host)[b];
-        const JpegDecDesc &d = wd.d;
-        const JpegStreamInfo &I = reinterpret_cast<const JpegStreamInfo *>(infos_host)[b];  // (rebased to the slice: hh_jpeg_decode_window_tables)
-        const char *why = jpeg_dec_check_info(I, true);
-        if (!why) why = jpeg_win_check(I, wd.win);
-        if (!why && (d.stream_offset < 0 || d.tables_offset < 0 || d.dst_offset < 0 || d.ws_offset < 0)) why = "negative offset";
-        if (!why && d.pitch < 3ll * wd.win.width) why = "pitch below 3 * width";
-        if (!why && (d.flags & ~1)) why = "unknown flag";
-        if (!why && d.nseg < 1) why = "no selected segment (nseg must be at least 1)";
-        if (!why && (d.stream_length < 1 || I.scan_end > d.stream_length)) why = "the scan's bytes lie outside the slice's length";
-        if (!why && d.tables_bytes < jpeg_dec_tables_bytes(d.nseg)) why = "table block below hh_jpeg_decode_tables_bytes";
-        if (!why && ((uintptr_t)(batch_base + d.tables_offset) % 16 || d.ws_offset % 16)) why = "the table block and ws_offset must be 16-byte aligned";
-        if (why) { hh_set_error(fn + ": image " + std::to_string(b) + ": " + why); return 1; }
-        const JpegDecGeom g = jpeg_win_geom(I, jpeg_win_rect(I, wd.win));
-        if (d.ws_offset + g.ws_bytes > workspace_bytes) {
-            hh_set_error(fn + ": image " + std::to_string(b) + ": workspace below hh_jpeg_decode_window_workspace_bytes");
-            return 1;
-        }
-        max_seg = std::max(max_seg, d.nseg), max_blk = std::max(max_blk, g.nblk), max_h = std::max(max_h, wd.win.height), max_w = std::max(max_w, wd.win.width);
-    }
-    HH_CHECK_HIP(hipMemsetAsync(status_dev, 0, (size_t)n * 4, (hipStream_t)stream));
-    HH_CHECK_HIP(launch_jpeg_decode_window(batch_base, reinterpret_cast<const JpegWinDesc *>(descs_dev), n, max_seg, max_blk, max_h, max_w, workspace,
-                                           status_dev, (hipStream_t)stream));
-    return 0;
+    return jpeg_decode_batch("hh_jpeg_decode_window_u8_batch", true, batch_base, descs_dev, descs_host, infos_host, n, workspace, workspace_bytes, status_dev,
+                             stream);
 }
 
 int hh_debug_jpeg_decode_window_host(const unsigned char *bytes, long long len, const hh_jpeg_segment *entries, int nseg, const hh_jpeg_window *window,
                                      int flags, unsigned char *dst, long long pitch, int *status, hh_jpeg_window_counts *counts)
 {
-    const std::string fn = "hh_debug_jpeg_decode_window_host";
-    if (!bytes || !dst || !window) { hh_set_error(fn + ": null pointer"); return 1; }
-    if (status) *status = 0;
-    JpegStreamInfo I;
-    std::vector<JpegDecTables> T(1);
-    const JpegWindow &W = *reinterpret_cast<const JpegWindow *>(window);
-    const char *why = jpeg_dec_parse(bytes, len, &I, &T[0]);
-    if (!why) why = jpeg_win_check(I, W);
-    if (!why && pitch < 3ll * W.width) why = "pitch below 3 * width";
-    if (!why && (flags & ~1)) why = "unknown flag";
-    if (!why && entries && nseg < 1) why = "nseg must be at least 1";
-    std::vector<JpegSegment> own;
-    if (!why && !entries) {
-        if (I.restart_interval) {
-            own.resize(I.nseg_restart);
-            why = jpeg_dec_restart_segments(bytes, I, own.data());
-        } else {
-            JpegSegment all = {0, I.mcols * I.mrows, (int32_t)I.scan_offset, 0, {0, 0, 0}, (int32_t)(I.scan_end << 1)};
-            own.push_back(all);
-        }
-        entries = reinterpret_cast<const hh_jpeg_segment *>(own.data());
-        nseg = (int)own.size();
-    }
-    const JpegSegment *seg = reinterpret_cast<const JpegSegment *>(entries);
-    const JpegWinRect R = why ? JpegWinRect() : jpeg_win_rect(I, W);
-    int nsel = 0;
-    long long slice[2] = {0, 0};
-    if (!why) why = jpeg_win_select(I, R, seg, nseg, &nsel, slice);
-    if (why) { hh_set_error(fn + ": " + why); return 1; }
-    // what the device receives: the table block of the selected segments, the slice in a block of its own, the rectangle's workspace
-    std::vector<JpegVec8> block((size_t)jpeg_dec_tables_bytes(nsel) / 16 + 1), ws((size_t)jpeg_win_geom(I, R).ws_bytes / 16 + 1);
-    jpeg_win_tables(I, T[0], R, seg, nseg, slice, reinterpret_cast<unsigned char *>(block.data()));
-    const std::vector<unsigned char> part(bytes + slice[0], bytes + slice[1]);
-    memset(ws.data(), 0, ws.size() * 16);
-    JpegWinCounts local = {0, 0, 0, 0, 0, 0};
-    const int st = jpeg_dec_window_host(part.data(), (int)part.size(), reinterpret_cast<const unsigned char *>(block.data()), nsel, W, flags & 1,
-                                        reinterpret_cast<unsigned char *>(ws.data()), dst, pitch, &local, nullptr);
-    if (counts) memcpy(counts, &local, sizeof(local));
-    if (status) *status = st;
-    if (st) { hh_set_error(fn + ": status " + std::to_string(st) + " (" + JPEG_STATUS_NAME[st] + ")"); return 1; }
-    return 0;
+    if (!bytes || !dst || !window) { hh_set_error("hh_debug_jpeg_decode_window_host: null pointer"); return 1; }
+    return jpeg_decode_host("hh_debug_jpeg_decode_window_host", bytes, len, entries, nseg, window, flags, dst, pitch, status, counts);
 }
 
 int hh_resize_u8(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, void *stream)

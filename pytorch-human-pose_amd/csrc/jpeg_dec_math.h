@@ -1,10 +1,10 @@
 // The baseline JPEG decoder (jpeg_decode.hip; the rule is stated at hh_jpeg_decode_u8_batch in include/hhrnet.h), kept apart from the
 // kernels so that the same text compiles for the host (hh_jpeg_parse, hh_jpeg_index_host, hh_debug_jpeg_decode_host,
-// tools/jpeg_decode_host_check.cpp): the marker walk with its refusals, the Huffman lookup tables, the bit reader, one segment's entropy
-// decode (templated on whether coefficients are stored), libjpeg's islow IDCT, its fancy upsampling, the colour step, and a whole
-// stream decoded in plain loops; and the window decode (hh_jpeg_decode_window_u8_batch, tools/jpeg_window_host_check.cpp): the MCU
-// rectangle, the selection of segments, the rebased table block, the windowed segment walk.  Integer arithmetic only; `>>` is an
-// arithmetic shift.
+// hh_debug_jpeg_decode_window_host, tools/jpeg_decode_host_check.cpp, tools/jpeg_window_host_check.cpp): the marker walk with its
+// refusals, the Huffman lookup tables, the bit reader, one segment's entropy decode, libjpeg's islow IDCT, its fancy upsampling, the
+// colour step, and a decode in plain loops.  A decode is always the decode of a window's MCU rectangle (hh_jpeg_decode_window_u8_batch);
+// the whole image is the window that covers it, whose rectangle is the MCU grid.  What only a true window needs comes last: the
+// selection of segments and the rebased table block.  Integer arithmetic only; `>>` is an arithmetic shift.
 #ifndef HH_JPEG_DEC_MATH_H
 #define HH_JPEG_DEC_MATH_H
 #include <stdint.h>
@@ -54,6 +54,19 @@ struct JpegDecDesc {
     int32_t flags, reserved;  // bit 0: store B,G,R
 };
 static_assert(sizeof(JpegDecDesc) == 64, "table layout");
+struct JpegWindow {  // hh_jpeg_window (16 bytes)
+    int32_t top, left, height, width;
+};
+static_assert(sizeof(JpegWindow) == 16, "table layout");
+struct JpegWinDesc {  // hh_jpeg_win_desc (80 bytes): JpegDecDesc, whose stream is the shipped slice, and the window
+    JpegDecDesc d;
+    JpegWindow win;
+};
+static_assert(sizeof(JpegWinDesc) == 80, "table layout");
+struct JpegWinCounts {  // hh_jpeg_window_counts (48 bytes)
+    long long segments_walked, mcus_walked, mcus_stored, blocks_transformed, pixels_written, stream_bytes;
+};
+static_assert(sizeof(JpegWinCounts) == 48, "table layout");
 
 // One Huffman table as the decoder reads it: the 8-bit first level (length << 8 | symbol, 0: longer than 8 bits or no code), and for the
 // lengths 9..16 libjpeg's maxcode / valptr pair (valoff = valptr - mincode; maxcode -1: no code of that length).
@@ -81,26 +94,55 @@ static constexpr uint8_t JPEG_ZZ[64] = {
      0,  1,  8, 16,  9,  2,  3, 10, 17, 24, 32, 25, 18, 11,  4,  5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13,  6,  7, 14, 21, 28,
     35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
+// The MCU rectangle of a window inside the image: an output pixel of a subsampled axis reads its chroma sample and one neighbour on
+// each side (rule c), clamped to the component's true size, so luma rows t..b need chroma rows max(0, (t >> 1) - 1) ..
+// min(ch - 1, (b >> 1) + 1) when vs == 2, and likewise across with hs (also for h2v1).  The rectangle is the MCUs that hold the
+// window's luma samples and those chroma samples.
+struct JpegWinRect {
+    int mx0, mx1, my0, my1;  // inclusive
+    int cols, rows;
+};
+HH_JDHD JpegWinRect jpeg_win_rect(const JpegStreamInfo &I, const JpegWindow &W)
+{
+    const int t = W.top, b = W.top + W.height - 1, l = W.left, r = W.left + W.width - 1;
+    JpegWinRect R;
+    R.mx0 = l / (8 * I.hs), R.mx1 = r / (8 * I.hs), R.my0 = t / (8 * I.vs), R.my1 = b / (8 * I.vs);
+    if (I.ncomp == 3 && I.hs == 2) {
+        const int cw = (I.w + 1) / 2, c0 = (l >> 1) - 1 < 0 ? 0 : (l >> 1) - 1, c1 = (r >> 1) + 1 > cw - 1 ? cw - 1 : (r >> 1) + 1;
+        R.mx0 = c0 / 8 < R.mx0 ? c0 / 8 : R.mx0, R.mx1 = c1 / 8 > R.mx1 ? c1 / 8 : R.mx1;
+    }
+    if (I.ncomp == 3 && I.vs == 2) {
+        const int ch = (I.h + 1) / 2, c0 = (t >> 1) - 1 < 0 ? 0 : (t >> 1) - 1, c1 = (b >> 1) + 1 > ch - 1 ? ch - 1 : (b >> 1) + 1;
+        R.my0 = c0 / 8 < R.my0 ? c0 / 8 : R.my0, R.my1 = c1 / 8 > R.my1 ? c1 / 8 : R.my1;
+    }
+    R.cols = R.mx1 - R.mx0 + 1, R.rows = R.my1 - R.my0 + 1;
+    return R;
+}
+// The whole image as a window, and its rectangle: the MCU grid (mx1 = (w - 1) / (8 hs) = mcols - 1, and likewise down).
+HH_JDHD JpegWindow jpeg_full_window(const JpegStreamInfo &I) { return JpegWindow{0, 0, I.h, I.w}; }
+HH_JDHD JpegWinRect jpeg_full_rect(const JpegStreamInfo &I) { return jpeg_win_rect(I, jpeg_full_window(I)); }
+
+// The workspace of a rectangle's decode: its coefficients, then its component planes (cw / ch stay the image's).
 struct JpegDecGeom {
-    int nmcu, nblk;            // MCUs and blocks of the image
+    int nmcu, nblk;            // MCUs and blocks of the rectangle
     int pw[3], ph[3];          // the padded component planes: whole blocks
     int cw[3], ch[3];          // the components' true sizes
     long long coef_bytes;      // int16 [nblk][64], natural order, not yet dequantised
     long long plane_at[3];     // from the image's workspace
     long long ws_bytes;        // a multiple of 16
 };
-HH_JDHD JpegDecGeom jpeg_dec_geom(const JpegStreamInfo &I)
+HH_JDHD JpegDecGeom jpeg_dec_geom(const JpegStreamInfo &I, const JpegWinRect &R)
 {
     JpegDecGeom g;
-    g.nmcu = I.mcols * I.mrows;
+    g.nmcu = R.cols * R.rows;
     g.nblk = g.nmcu * I.bpm;
     g.coef_bytes = (long long)g.nblk * 128;
     long long at = g.coef_bytes;
     for (int c = 0; c < 3; ++c) {
         const int hs = c == 0 ? I.hs : 1, vs = c == 0 ? I.vs : 1;
         const bool have = c < I.ncomp;
-        g.pw[c] = have ? I.mcols * hs * 8 : 0;
-        g.ph[c] = have ? I.mrows * vs * 8 : 0;
+        g.pw[c] = have ? R.cols * hs * 8 : 0;
+        g.ph[c] = have ? R.rows * vs * 8 : 0;
         g.cw[c] = c == 0 ? I.w : (I.w + I.hs - 1) / I.hs;
         g.ch[c] = c == 0 ? I.h : (I.h + I.vs - 1) / I.vs;
         g.plane_at[c] = at;
@@ -232,11 +274,29 @@ struct JpegExtent {
 // The component of block j of an MCU.
 HH_JDHD int jpeg_dec_block_comp(const JpegStreamInfo &I, int j) { return j < I.hs * I.vs ? 0 : j - I.hs * I.vs + 1; }
 
-// One segment: its MCUs into coefs (the image's [nblk][64]).  Every stream byte read lies in [scan_offset, min(byte_end, length));
-// every coefficient written in the blocks [first_mcu * bpm, (first_mcu + mcu_count) * bpm) after both were cut to the image's grid.
-template <bool STORE>
+// The last MCU of [first, first + count) that lies inside the rectangle, or -1: where a lane's walk ends, and whether it has one.
+// With the whole grid as the rectangle no clause applies (ly <= mrows - 1 = my1, lx >= 0 = mx0, ly >= 0 = my0, lx <= mcols - 1 = mx1):
+// the result is the segment's last MCU.
+HH_JDHD int jpeg_win_last(const JpegStreamInfo &I, const JpegWinRect &R, int first, int count)
+{
+    const int last = first + count - 1;
+    int ly = last / I.mcols, lx = last % I.mcols;
+    if (ly > R.my1) ly = R.my1, lx = I.mcols - 1;
+    if (lx < R.mx0) ly -= 1, lx = I.mcols - 1;  // (this row's part lies left of the rectangle: the row before, whole)
+    if (ly < R.my0) return -1;
+    const int cand = ly * I.mcols + (lx < R.mx1 ? lx : R.mx1);  // the largest MCU of the rectangle <= last
+    return cand >= first ? cand : -1;
+}
+
+// One segment: walked from its first MCU to its last MCU inside the rectangle; coefficients are stored for the MCUs inside (coefs: the
+// rectangle's [rows * cols * bpm][64]), the others are walked without storing.  Every stream byte read lies in [scan_offset,
+// min(byte_end, length)) of the stream (a window's: the shipped slice); every coefficient written in a block of the rectangle, after
+// the segment's MCU range was cut to the image's grid.  The RSTm check applies only to a walk that reached the segment's end.
+// With the whole grid as the rectangle (jpeg_full_rect) `stop` is the segment's last MCU (see jpeg_win_last) and `inside` is always
+// true, since 0 <= mx < mcols and 0 <= my < mrows for every MCU of the grid: every MCU is stored at (first_mcu + m) * bpm, the walk
+// always reaches the segment's end, and ext->max_coef is one past the last MCU begun.
 HH_JDHD int jpeg_dec_segment(const unsigned char *stream, int length, const JpegStreamInfo &I, const JpegHuff *huff, const JpegSegment &sg,
-                             int16_t *coefs, int pred_out[3], JpegExtent *ext)
+                             const JpegWinRect &R, int16_t *coefs, JpegWinCounts *counts, JpegExtent *ext)
 {
     const int nmcu = I.mcols * I.mrows;
     const long long lim = I.scan_end < length ? I.scan_end : length;
@@ -244,28 +304,39 @@ HH_JDHD int jpeg_dec_segment(const unsigned char *stream, int length, const Jpeg
     if (sg.first_mcu < 0 || sg.first_mcu >= nmcu || sg.mcu_count < 1 || sg.mcu_count > nmcu - sg.first_mcu || sg.byte_offset < I.scan_offset ||
         sg.byte_offset > end || (sg.bit_offset & ~7))
         return JPEG_ST_SEGMENT;
+    const int stop = jpeg_win_last(I, R, sg.first_mcu, sg.mcu_count);
+    if (stop < 0) return JPEG_ST_OK;  // (no MCU of the rectangle: the host does not select such a segment)
     JpegBits br;
     br.init(stream, sg.byte_offset, end);
     br.refill();
     br.drop(sg.bit_offset);
     int pred[3] = {sg.pred[0], sg.pred[1], sg.pred[2]};
     int status = JPEG_ST_OK;
-    int m = 0;
+    int my = sg.first_mcu / I.mcols, mx = sg.first_mcu % I.mcols;
+    long long stored = 0, top = 0;
+    int m = sg.first_mcu;
 #pragma unroll 1
-    for (; m < sg.mcu_count && !status; ++m) {
+    for (; m <= stop && !status; ++m) {
+        const bool inside = mx >= R.mx0 && mx <= R.mx1 && my >= R.my0 && my <= R.my1;
+        const size_t at = ((size_t)(my - R.my0) * R.cols + (size_t)(mx - R.mx0)) * I.bpm;  // (read only when inside)
 #pragma unroll 1
         for (int j = 0; j < I.bpm && !status; ++j) {
             const int c = jpeg_dec_block_comp(I, j);
-            status = jpeg_dec_block<STORE>(br, huff[I.dc[c] & 3], huff[4 + (I.ac[c] & 3)], pred[c],
-                                           STORE ? coefs + ((size_t)(sg.first_mcu + m) * I.bpm + j) * 64 : nullptr);
+            const JpegHuff &dc = huff[I.dc[c] & 3], &ac = huff[4 + (I.ac[c] & 3)];
+            status = inside ? jpeg_dec_block<true>(br, dc, ac, pred[c], coefs + (at + j) * 64) : jpeg_dec_block<false>(br, dc, ac, pred[c], nullptr);
         }
+        if (inside) {
+            ++stored;
+            if ((long long)(at + I.bpm) * 64 > top) top = (long long)(at + I.bpm) * 64;
+        }
+        if (++mx == I.mcols) mx = 0, ++my;
     }
-    if (!status && (sg.byte_end & 1) && (br.real() >= 8 || br.pos < end)) status = JPEG_ST_RESTART;  // data where the RSTm should stand
-    if (pred_out) pred_out[0] = pred[0], pred_out[1] = pred[1], pred_out[2] = pred[2];
+    // data where the RSTm should stand
+    if (!status && stop == sg.first_mcu + sg.mcu_count - 1 && (sg.byte_end & 1) && (br.real() >= 8 || br.pos < end)) status = JPEG_ST_RESTART;
+    if (counts) counts->segments_walked += 1, counts->mcus_walked += m - sg.first_mcu, counts->mcus_stored += stored;
     if (ext) {
         if (br.pos > ext->max_byte) ext->max_byte = br.pos;
-        const long long top = (long long)(sg.first_mcu + m) * I.bpm * 64;
-        if (STORE && top > ext->max_coef) ext->max_coef = top;
+        if (top > ext->max_coef) ext->max_coef = top;
     }
     return status;
 }
@@ -330,171 +401,8 @@ HH_JDHD JpegRow8 jpeg_idct_row(const int32_t *ws_row)
     for (int x = 0; x < 8; ++x) r.v[x] = (unsigned char)jpeg_idct_sample(v[x]);
     return r;
 }
-// Where block `blk` of the image lies: its component, and its first sample in that component's plane.
-HH_JDHD void jpeg_dec_block_place(const JpegStreamInfo &I, const JpegDecGeom &g, int blk, int &c, long long &at)
-{
-    const int mcu = blk / I.bpm, j = blk % I.bpm;
-    const int my = mcu / I.mcols, mx = mcu % I.mcols;
-    c = jpeg_dec_block_comp(I, j);
-    const int hs = c == 0 ? I.hs : 1, vs = c == 0 ? I.vs : 1;
-    const int by = c == 0 ? j / I.hs : 0, bx = c == 0 ? j % I.hs : 0;
-    at = g.plane_at[c] + (long long)((my * vs + by) * 8) * g.pw[c] + (mx * hs + bx) * 8;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- upsampling, colour
-// The chroma sample of output pixel (y, x) from a plane of true size cw x ch (libjpeg's fancy filters; plain replication when cw <= 2).
-HH_JDHD int jpeg_dec_chroma(const unsigned char *plane, int pitch, int cw, int ch, int hs, int vs, int y, int x)
-{
-    if (hs == 1) return plane[(size_t)y * pitch + x];
-    const int c = x >> 1;
-    if (cw <= 2) return plane[(size_t)(vs == 2 ? y >> 1 : y) * pitch + c];
-    if (vs == 1) {
-        const unsigned char *row = plane + (size_t)y * pitch;
-        const int v = row[c];
-        if (x & 1) return c == cw - 1 ? v : (3 * v + row[c + 1] + 2) >> 2;
-        return c == 0 ? v : (3 * v + row[c - 1] + 1) >> 2;
-    }
-    const int r = y >> 1;
-    int far = (y & 1) ? r + 1 : r - 1;
-    far = far < 0 ? 0 : far > ch - 1 ? ch - 1 : far;
-    const unsigned char *near_row = plane + (size_t)r * pitch, *far_row = plane + (size_t)far * pitch;
-    const int s = 3 * near_row[c] + far_row[c];
-    if (x & 1) {
-        const int cn = c == cw - 1 ? c : c + 1;
-        return (3 * s + 3 * near_row[cn] + far_row[cn] + 7) >> 4;
-    }
-    const int cp = c == 0 ? c : c - 1;
-    return (3 * s + 3 * near_row[cp] + far_row[cp] + 8) >> 4;
-}
-HH_JDHD int jpeg_dec_clamp(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
-// Output pixel (y, x) of the image from its planes -> dst[0..2].
-HH_JDHD void jpeg_dec_pixel(const unsigned char *ws, const JpegStreamInfo &I, const JpegDecGeom &g, int y, int x, bool bgr, unsigned char *dst)
-{
-    const int Y = ws[g.plane_at[0] + (size_t)y * g.pw[0] + x];
-    if (I.ncomp == 1) {
-        dst[0] = dst[1] = dst[2] = (unsigned char)Y;
-        return;
-    }
-    const int cb = jpeg_dec_chroma(ws + g.plane_at[1], g.pw[1], g.cw[1], g.ch[1], I.hs, I.vs, y, x) - 128;
-    const int cr = jpeg_dec_chroma(ws + g.plane_at[2], g.pw[2], g.cw[2], g.ch[2], I.hs, I.vs, y, x) - 128;
-    const int R = jpeg_dec_clamp(Y + ((91881 * cr + 32768) >> 16));
-    const int B = jpeg_dec_clamp(Y + ((116130 * cb + 32768) >> 16));
-    const int G = jpeg_dec_clamp(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
-    dst[bgr ? 2 : 0] = (unsigned char)R, dst[1] = (unsigned char)G, dst[bgr ? 0 : 2] = (unsigned char)B;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- window decode
-// hh_jpeg_decode_window_u8_batch of include/hhrnet.h: the pixels of a window (top, left, height, width) of the image, the same bytes the
-// whole decode writes there.  Nothing above is altered or rerouted; what is restated here is only where a block and a sample LIE (in
-// a workspace laid out for the window's MCU rectangle), never how a value is formed.
-struct JpegWindow {  // hh_jpeg_window (16 bytes)
-    int32_t top, left, height, width;
-};
-static_assert(sizeof(JpegWindow) == 16, "table layout");
-struct JpegWinDesc {  // hh_jpeg_win_desc (80 bytes): JpegDecDesc, whose stream is the shipped slice, and the window
-    JpegDecDesc d;
-    JpegWindow win;
-};
-static_assert(sizeof(JpegWinDesc) == 80, "table layout");
-struct JpegWinCounts {  // hh_jpeg_window_counts (48 bytes)
-    long long segments_walked, mcus_walked, mcus_stored, blocks_transformed, pixels_written, stream_bytes;
-};
-static_assert(sizeof(JpegWinCounts) == 48, "table layout");
-
-// The MCU rectangle of a window inside the image: an output pixel of a subsampled axis reads its chroma sample and one neighbour on
-// each side (rule c), clamped to the component's true size, so luma rows t..b need chroma rows max(0, (t >> 1) - 1) ..
-// min(ch - 1, (b >> 1) + 1) when vs == 2, and likewise across with hs (also for h2v1).  The rectangle is the MCUs that hold the
-// window's luma samples and those chroma samples.
-struct JpegWinRect {
-    int mx0, mx1, my0, my1;  // inclusive
-    int cols, rows;
-};
-HH_JDHD JpegWinRect jpeg_win_rect(const JpegStreamInfo &I, const JpegWindow &W)
-{
-    const int t = W.top, b = W.top + W.height - 1, l = W.left, r = W.left + W.width - 1;
-    JpegWinRect R;
-    R.mx0 = l / (8 * I.hs), R.mx1 = r / (8 * I.hs), R.my0 = t / (8 * I.vs), R.my1 = b / (8 * I.vs);
-    if (I.ncomp == 3 && I.hs == 2) {
-        const int cw = (I.w + 1) / 2, c0 = (l >> 1) - 1 < 0 ? 0 : (l >> 1) - 1, c1 = (r >> 1) + 1 > cw - 1 ? cw - 1 : (r >> 1) + 1;
-        R.mx0 = c0 / 8 < R.mx0 ? c0 / 8 : R.mx0, R.mx1 = c1 / 8 > R.mx1 ? c1 / 8 : R.mx1;
-    }
-    if (I.ncomp == 3 && I.vs == 2) {
-        const int ch = (I.h + 1) / 2, c0 = (t >> 1) - 1 < 0 ? 0 : (t >> 1) - 1, c1 = (b >> 1) + 1 > ch - 1 ? ch - 1 : (b >> 1) + 1;
-        R.my0 = c0 / 8 < R.my0 ? c0 / 8 : R.my0, R.my1 = c1 / 8 > R.my1 ? c1 / 8 : R.my1;
-    }
-    R.cols = R.mx1 - R.mx0 + 1, R.rows = R.my1 - R.my0 + 1;
-    return R;
-}
-// The workspace of a rectangle: jpeg_dec_geom's layout with the rectangle in the place of the MCU grid (cw / ch stay the image's).
-HH_JDHD JpegDecGeom jpeg_win_geom(const JpegStreamInfo &I, const JpegWinRect &R)
-{
-    JpegStreamInfo J = I;
-    J.mcols = R.cols, J.mrows = R.rows;
-    return jpeg_dec_geom(J);
-}
-// The last MCU of [first, first + count) that lies inside the rectangle, or -1: where a lane's walk ends, and whether it has one.
-HH_JDHD int jpeg_win_last(const JpegStreamInfo &I, const JpegWinRect &R, int first, int count)
-{
-    const int last = first + count - 1;
-    int ly = last / I.mcols, lx = last % I.mcols;
-    if (ly > R.my1) ly = R.my1, lx = I.mcols - 1;
-    if (lx < R.mx0) ly -= 1, lx = I.mcols - 1;  // (this row's part lies left of the rectangle: the row before, whole)
-    if (ly < R.my0) return -1;
-    const int cand = ly * I.mcols + (lx < R.mx1 ? lx : R.mx1);  // the largest MCU of the rectangle <= last
-    return cand >= first ? cand : -1;
-}
-
-// One segment of a window decode: walked from its first MCU to its last MCU inside the rectangle; coefficients are stored for the
-// MCUs inside (coefs: the rectangle's [rows * cols * bpm][64]), the others are walked without storing.  Bounds as jpeg_dec_segment:
-// every stream byte read lies in [scan_offset, min(byte_end, length)) of the shipped slice; every coefficient written in a block of
-// the rectangle.  The RSTm check applies only to a walk that reached the segment's end.
-HH_JDHD int jpeg_dec_window_segment(const unsigned char *stream, int length, const JpegStreamInfo &I, const JpegHuff *huff, const JpegSegment &sg,
-                                    const JpegWinRect &R, int16_t *coefs, JpegWinCounts *counts, JpegExtent *ext)
-{
-    const int nmcu = I.mcols * I.mrows;
-    const long long lim = I.scan_end < length ? I.scan_end : length;
-    const int end = (sg.byte_end >> 1) < lim ? (sg.byte_end >> 1) : (int)lim;
-    if (sg.first_mcu < 0 || sg.first_mcu >= nmcu || sg.mcu_count < 1 || sg.mcu_count > nmcu - sg.first_mcu || sg.byte_offset < I.scan_offset ||
-        sg.byte_offset > end || (sg.bit_offset & ~7))
-        return JPEG_ST_SEGMENT;
-    const int stop = jpeg_win_last(I, R, sg.first_mcu, sg.mcu_count);
-    if (stop < 0) return JPEG_ST_OK;  // (no MCU of the rectangle: the host does not select such a segment)
-    JpegBits br;
-    br.init(stream, sg.byte_offset, end);
-    br.refill();
-    br.drop(sg.bit_offset);
-    int pred[3] = {sg.pred[0], sg.pred[1], sg.pred[2]};
-    int status = JPEG_ST_OK;
-    int my = sg.first_mcu / I.mcols, mx = sg.first_mcu % I.mcols;
-    long long stored = 0, top = 0;
-    int m = sg.first_mcu;
-#pragma unroll 1
-    for (; m <= stop && !status; ++m) {
-        const bool inside = mx >= R.mx0 && mx <= R.mx1 && my >= R.my0 && my <= R.my1;
-        const size_t at = ((size_t)(my - R.my0) * R.cols + (size_t)(mx - R.mx0)) * I.bpm;  // (read only when inside)
-#pragma unroll 1
-        for (int j = 0; j < I.bpm && !status; ++j) {
-            const int c = jpeg_dec_block_comp(I, j);
-            const JpegHuff &dc = huff[I.dc[c] & 3], &ac = huff[4 + (I.ac[c] & 3)];
-            status = inside ? jpeg_dec_block<true>(br, dc, ac, pred[c], coefs + (at + j) * 64) : jpeg_dec_block<false>(br, dc, ac, pred[c], nullptr);
-        }
-        if (inside) {
-            ++stored;
-            if ((long long)(at + I.bpm) * 64 > top) top = (long long)(at + I.bpm) * 64;
-        }
-        if (++mx == I.mcols) mx = 0, ++my;
-    }
-    if (!status && stop == sg.first_mcu + sg.mcu_count - 1 && (sg.byte_end & 1) && (br.real() >= 8 || br.pos < end)) status = JPEG_ST_RESTART;
-    if (counts) counts->segments_walked += 1, counts->mcus_walked += m - sg.first_mcu, counts->mcus_stored += stored;
-    if (ext) {
-        if (br.pos > ext->max_byte) ext->max_byte = br.pos;
-        if (top > ext->max_coef) ext->max_coef = top;
-    }
-    return status;
-}
-
-// Where block `blk` of the rectangle lies (jpeg_dec_block_place with the rectangle's grid; g = jpeg_win_geom).
-HH_JDHD void jpeg_win_block_place(const JpegStreamInfo &I, const JpegWinRect &R, const JpegDecGeom &g, int blk, int &c, long long &at)
+// Where block `blk` of the rectangle lies: its component, and its first sample in that component's plane (g = jpeg_dec_geom(I, R)).
+HH_JDHD void jpeg_dec_block_place(const JpegStreamInfo &I, const JpegWinRect &R, const JpegDecGeom &g, int blk, int &c, long long &at)
 {
     const int mcu = blk / I.bpm, j = blk % I.bpm;
     const int ry = mcu / R.cols, rx = mcu % R.cols;
@@ -503,9 +411,12 @@ HH_JDHD void jpeg_win_block_place(const JpegStreamInfo &I, const JpegWinRect &R,
     const int by = c == 0 ? j / I.hs : 0, bx = c == 0 ? j % I.hs : 0;
     at = g.plane_at[c] + (long long)((ry * vs + by) * 8) * g.pw[c] + (rx * hs + bx) * 8;
 }
-// jpeg_dec_chroma on a plane that starts at row oy, column ox of the component: the same taps and the same edges (cw, ch: the
-// component's true size; the replication case by the image's width), only the addresses are relative to (oy, ox).
-HH_JDHD int jpeg_win_chroma(const unsigned char *plane, int pitch, int oy, int ox, int cw, int ch, int hs, int vs, int y, int x)
+
+// ---------------------------------------------------------------------------------------------------------------- upsampling, colour
+// The chroma sample of output pixel (y, x) of the image (libjpeg's fancy filters; plain replication when cw <= 2) from a plane that
+// starts at row oy, column ox of the component (0, 0: the whole component): the taps and the edges go by the component's true size
+// cw x ch, only the addresses are relative to (oy, ox).
+HH_JDHD int jpeg_dec_chroma(const unsigned char *plane, int pitch, int oy, int ox, int cw, int ch, int hs, int vs, int y, int x)
 {
     if (hs == 1) return plane[(size_t)(y - oy) * pitch + (x - ox)];
     const int c = x >> 1;
@@ -528,8 +439,9 @@ HH_JDHD int jpeg_win_chroma(const unsigned char *plane, int pitch, int oy, int o
     const int cp = (c == 0 ? c : c - 1) - ox;
     return (3 * s + 3 * near_row[cp] + far_row[cp] + 8) >> 4;
 }
-// Pixel (y, x) of the IMAGE from the rectangle's planes -> dst[0..2] (jpeg_dec_pixel's colour step, unchanged).
-HH_JDHD void jpeg_win_pixel(const unsigned char *ws, const JpegStreamInfo &I, const JpegWinRect &R, const JpegDecGeom &g, int y, int x, bool bgr,
+HH_JDHD int jpeg_dec_clamp(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+// Pixel (y, x) of the IMAGE from the rectangle's planes -> dst[0..2].
+HH_JDHD void jpeg_dec_pixel(const unsigned char *ws, const JpegStreamInfo &I, const JpegWinRect &R, const JpegDecGeom &g, int y, int x, bool bgr,
                             unsigned char *dst)
 {
     const int Y = ws[g.plane_at[0] + (size_t)(y - R.my0 * I.vs * 8) * g.pw[0] + (x - R.mx0 * I.hs * 8)];
@@ -538,8 +450,8 @@ HH_JDHD void jpeg_win_pixel(const unsigned char *ws, const JpegStreamInfo &I, co
         return;
     }
     const int cy = R.my0 * 8, cx = R.mx0 * 8;  // the chroma planes' origin: one block per MCU, whatever the sampling
-    const int cb = jpeg_win_chroma(ws + g.plane_at[1], g.pw[1], cy, cx, g.cw[1], g.ch[1], I.hs, I.vs, y, x) - 128;
-    const int cr = jpeg_win_chroma(ws + g.plane_at[2], g.pw[2], cy, cx, g.cw[2], g.ch[2], I.hs, I.vs, y, x) - 128;
+    const int cb = jpeg_dec_chroma(ws + g.plane_at[1], g.pw[1], cy, cx, g.cw[1], g.ch[1], I.hs, I.vs, y, x) - 128;
+    const int cr = jpeg_dec_chroma(ws + g.plane_at[2], g.pw[2], cy, cx, g.cw[2], g.ch[2], I.hs, I.vs, y, x) - 128;
     const int Rr = jpeg_dec_clamp(Y + ((91881 * cr + 32768) >> 16));
     const int B = jpeg_dec_clamp(Y + ((116130 * cb + 32768) >> 16));
     const int G = jpeg_dec_clamp(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
@@ -830,24 +742,27 @@ inline const char *jpeg_dec_index(const unsigned char *b, long long len, const J
     return nullptr;
 }
 
-// Steps b to d of a whole image on the host: ws holds the coefficients, the planes are formed there, dst receives [h,w,3].
-inline void jpeg_dec_pixels_host(unsigned char *ws, const JpegStreamInfo &I, const JpegDecTables &T, bool bgr, unsigned char *dst, long long pitch)
+// Steps b to d of a window on the host: ws (jpeg_dec_geom(I, jpeg_win_rect(I, W)).ws_bytes, 16-byte aligned) holds the rectangle's
+// coefficients, the planes are formed there, dst receives [height,width,3].
+inline void jpeg_dec_window_pixels_host(unsigned char *ws, const JpegStreamInfo &I, const JpegDecTables &T, const JpegWindow &W, bool bgr,
+                                        unsigned char *dst, long long pitch)
 {
-    const JpegDecGeom g = jpeg_dec_geom(I);
+    const JpegWinRect R = jpeg_win_rect(I, W);
+    const JpegDecGeom g = jpeg_dec_geom(I, R);
     for (int blk = 0; blk < g.nblk; ++blk) {
         int c;
         long long at;
-        jpeg_dec_block_place(I, g, blk, c, at);
+        jpeg_dec_block_place(I, R, g, blk, c, at);
         int32_t tmp[64];
         const int16_t *coef = reinterpret_cast<const int16_t *>(ws) + (size_t)blk * 64;
-        for (int u = 0; u < 8; ++u) jpeg_idct_col(coef, T.q[I.qt[c]], u, tmp);
+        for (int u = 0; u < 8; ++u) jpeg_idct_col(coef, T.q[I.qt[c] & 3], u, tmp);
         for (int y = 0; y < 8; ++y) {
             const JpegRow8 r = jpeg_idct_row(tmp + y * 8);
             memcpy(ws + at + (size_t)y * g.pw[c], r.v, 8);
         }
     }
-    for (int y = 0; y < I.h; ++y)
-        for (int x = 0; x < I.w; ++x) jpeg_dec_pixel(ws, I, g, y, x, bgr, dst + (size_t)y * pitch + (size_t)x * 3);
+    for (int y = 0; y < W.height; ++y)
+        for (int x = 0; x < W.width; ++x) jpeg_dec_pixel(ws, I, R, g, W.top + y, W.left + x, bgr, dst + (size_t)y * pitch + (size_t)x * 3);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host only, window
@@ -901,8 +816,9 @@ inline void jpeg_win_tables(const JpegStreamInfo &I, const JpegDecTables &T, con
     }
 }
 
-// A window decode on the host, from what the device receives: the slice, its table block (jpeg_win_tables), a workspace of
-// jpeg_win_geom().ws_bytes (16-byte aligned) and the height x pitch destination -> the largest status of the walked part.
+// A decode on the host, from what the device receives: the stream (a window's: the slice), its table block (hh_jpeg_decode_tables, or
+// jpeg_win_tables), a workspace of jpeg_dec_geom().ws_bytes (16-byte aligned) and the height x pitch destination -> the largest status
+// of the walked part.
 inline int jpeg_dec_window_host(const unsigned char *slice, int slice_len, const unsigned char *block, int nsel, const JpegWindow &W, bool bgr,
                                 unsigned char *ws, unsigned char *dst, long long pitch, JpegWinCounts *counts, JpegExtent *ext)
 {
@@ -910,29 +826,18 @@ inline int jpeg_dec_window_host(const unsigned char *slice, int slice_len, const
     memcpy(&I, block, sizeof(I));
     const JpegDecTables *T = reinterpret_cast<const JpegDecTables *>(block + JPEG_DEC_TABLES_AT);
     const JpegWinRect R = jpeg_win_rect(I, W);
-    const JpegDecGeom g = jpeg_win_geom(I, R);
     int status = 0;
     for (int s = 0; s < nsel; ++s) {
         JpegSegment sg;
         memcpy(&sg, block + JPEG_DEC_SEGS_AT + (size_t)s * sizeof(sg), sizeof(sg));
-        const int st = jpeg_dec_window_segment(slice, slice_len, I, T->huff, sg, R, reinterpret_cast<int16_t *>(ws), counts, ext);
+        const int st = jpeg_dec_segment(slice, slice_len, I, T->huff, sg, R, reinterpret_cast<int16_t *>(ws), counts, ext);
         status = st > status ? st : status;
     }
-    for (int blk = 0; blk < g.nblk; ++blk) {
-        int c;
-        long long at;
-        jpeg_win_block_place(I, R, g, blk, c, at);
-        int32_t tmp[64];
-        const int16_t *coef = reinterpret_cast<const int16_t *>(ws) + (size_t)blk * 64;
-        for (int u = 0; u < 8; ++u) jpeg_idct_col(coef, T->q[I.qt[c] & 3], u, tmp);
-        for (int y = 0; y < 8; ++y) {
-            const JpegRow8 r = jpeg_idct_row(tmp + y * 8);
-            memcpy(ws + at + (size_t)y * g.pw[c], r.v, 8);
-        }
+    jpeg_dec_window_pixels_host(ws, I, *T, W, bgr, dst, pitch);
+    if (counts) {
+        counts->blocks_transformed += jpeg_dec_geom(I, R).nblk, counts->pixels_written += (long long)W.height * W.width;
+        counts->stream_bytes += slice_len;
     }
-    for (int y = 0; y < W.height; ++y)
-        for (int x = 0; x < W.width; ++x) jpeg_win_pixel(ws, I, R, g, W.top + y, W.left + x, bgr, dst + (size_t)y * pitch + (size_t)x * 3);
-    if (counts) counts->blocks_transformed += g.nblk, counts->pixels_written += (long long)W.height * W.width, counts->stream_bytes += slice_len;
     return status;
 }
 #endif

@@ -367,15 +367,11 @@ struct JpegDesc;
 hipError_t launch_jpeg_encode(unsigned char *base, const JpegDesc *descs, int n, int max_mcus, int max_rows, unsigned char *ws, int32_t *lengths,
                               hipStream_t s);
 // Baseline JPEG decode (hh_jpeg_dec_desc of include/hhrnet.h; structs and arithmetic in jpeg_dec_math.h, kernels in jpeg_decode.hip): n
-// streams in three launches behind the clearing of `status`; the grids are sized by the largest image's segments, blocks and size.
-struct JpegDecDesc;
-hipError_t launch_jpeg_decode(unsigned char *base, const JpegDecDesc *descs, int n, int max_seg, int max_blk, int max_h, int max_w, unsigned char *ws,
+// streams in three launches behind the clearing of `status`.  Desc: JpegDecDesc (the whole image) or JpegWinDesc (hh_jpeg_win_desc: a
+// window); the grids are sized by the largest count of (selected) segments, the largest MCU rectangle's blocks and the largest window.
+template <class Desc>
+hipError_t launch_jpeg_decode(unsigned char *base, const Desc *descs, int n, int max_seg, int max_blk, int max_h, int max_w, unsigned char *ws,
                               int32_t *status, hipStream_t s);
-// The window decode (hh_jpeg_win_desc): the same three launches, sized by the largest count of selected segments, the largest MCU
-// rectangle's blocks and the largest window.
-struct JpegWinDesc;
-hipError_t launch_jpeg_decode_window(unsigned char *base, const JpegWinDesc *descs, int n, int max_seg, int max_blk, int max_h, int max_w,
-                                     unsigned char *ws, int32_t *status, hipStream_t s);
 // Heatmap panels (hh_panel_map of include/hhrnet.h; struct and arithmetic in panel_math.h, kernels in panels.hip): the min/max launch
 // (only if any_minmax) and the paint launch of one figure; the same figure on the host; the un-normalise of the model input.
 struct PanelMap;

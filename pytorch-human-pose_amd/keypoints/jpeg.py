@@ -436,18 +436,27 @@ class JpegImage:
         return (stream_at, tables_at, plan.tables_bytes, dst_at, ws_at, pitch, plan.slice[1] - plan.slice[0], plan.nsel, FLAG_BGR if bgr else 0, 0,
                 plan.window)
 
+    def whole_plan(self) -> WindowPlan:
+        """The record `window_plan` gives, for the whole-image entry: every segment, the whole stream, the MCU grid's workspace."""
+        return WindowPlan((0, 0, self.h, self.w), len(self.segments), (0, self.data.size), self.tables_bytes, self.ws_bytes, self.staged_bytes())
+
+    def stage_plan(self, hview: np.ndarray, at: int, plan: WindowPlan, windowed: bool) -> tuple[int, int, np.ndarray]:
+        """`stage` (a `whole_plan`) or `stage_window` -> (stream offset, tables offset, the info the library validates the image by)."""
+        if not windowed:
+            return (*self.stage(hview, at), self.info)
+        stream_at, tables_at, _, info = self.stage_window(hview, at, plan.window, plan)
+        return stream_at, tables_at, info
+
+
+def launch_decode(dev, base: int, descs_dev: int, descs: np.ndarray, infos: np.ndarray, work, status_dev: int, entry: str = "hh_jpeg_decode_u8_batch") -> None:
+    """`entry` on the current stream of `dev` (three launches behind the clearing of the statuses): hh_jpeg_decode_u8_batch with DEC_DESC
+    rows, or hh_jpeg_decode_window_u8_batch with WIN_DESC rows and, as `infos`, the rebased infos `stage_window` returned."""
+    _lib.launch(dev, getattr(_lib.load(), entry), base, descs_dev, descs.ctypes.data, infos.ctypes.data, len(descs), work.data_ptr(), work.numel(),
+                status_dev)
+
 
 def launch_decode_window(dev, base: int, descs_dev: int, descs: np.ndarray, infos: np.ndarray, work, status_dev: int) -> None:
-    """hh_jpeg_decode_window_u8_batch on the current stream of `dev` (three launches behind the clearing of the statuses); `infos`: the
-    rebased infos `stage_window` returned."""
-    _lib.launch(dev, _lib.load().hh_jpeg_decode_window_u8_batch, base, descs_dev, descs.ctypes.data, infos.ctypes.data, len(descs), work.data_ptr(),
-                work.numel(), status_dev)
-
-
-def launch_decode(dev, base: int, descs_dev: int, descs: np.ndarray, infos: np.ndarray, work, status_dev: int) -> None:
-    """hh_jpeg_decode_u8_batch on the current stream of `dev` (three launches behind the clearing of the statuses)."""
-    _lib.launch(dev, _lib.load().hh_jpeg_decode_u8_batch, base, descs_dev, descs.ctypes.data, infos.ctypes.data, len(descs), work.data_ptr(),
-                work.numel(), status_dev)
+    launch_decode(dev, base, descs_dev, descs, infos, work, status_dev, "hh_jpeg_decode_window_u8_batch")
 
 
 def raise_status(statuses, what: str = "hh_jpeg_decode_u8_batch") -> None:
@@ -472,76 +481,19 @@ def decode_jpeg_device(streams: list, index=None, bgr=False, device=None, out=No
     n = len(streams)
     if n == 0:
         return []
-    if windows is not None:
-        if len(windows) != n:
-            raise ValueError("decode_jpeg_device: `windows` has one entry per stream")
-        if any(w is not None for w in windows):
-            return _decode_windows(streams, index, bgr, device, out, windows)
+    if windows is not None and len(windows) != n:
+        raise ValueError("decode_jpeg_device: `windows` has one entry per stream")
+    windowed = windows is not None and any(w is not None for w in windows)
+    desc_t, entry = (WIN_DESC, "hh_jpeg_decode_window_u8_batch") if windowed else (DEC_DESC, "hh_jpeg_decode_u8_batch")
     idx = _per_frame(index, n) if isinstance(index, (list, tuple)) else [index] * n
     if index is not None and not isinstance(index, (list, tuple)) and n != 1:
         raise ValueError("decode_jpeg_device: `index` is a list with one entry per stream")
     items = [s if isinstance(s, JpegImage) else JpegImage(s, i) for s, i in zip(streams, idx)]
+    # one plan per stream: without any window the whole stream and every segment, else the slice and the segments of its window
+    plans = [it.window_plan((0, 0, it.h, it.w) if w is None else w) for it, w in zip(items, windows)] if windowed else [it.whole_plan() for it in items]
     bgrs = _per_frame(bgr, n)
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    at = _align(DEC_DESC.itemsize * n, 16)
-    places = []
-    for it in items:
-        places.append(at)
-        at += it.staged_bytes()
-    upload = at
-    status_at = _align(at, 16)
-    at = status_at + 4 * n
-    dst_at = []
-    for it in items:
-        at = _align(at, 16)
-        dst_at.append(at)
-        at += it.h * it.w * 3 if out is None else 0
-    ws_at = np.cumsum([0] + [it.ws_bytes for it in items])
-    host = torch.empty(upload, dtype=torch.uint8).pin_memory()
-    hv = host.numpy()
-    hv[:] = 0
-    descs = hv[:DEC_DESC.itemsize * n].view(DEC_DESC)
-    infos = np.concatenate([it.info for it in items])
-    buf = torch.empty(at, dtype=torch.uint8, device=device)  # [descriptors | streams and tables | statuses | pixels]
-    work = torch.empty(max(int(ws_at[-1]), 16), dtype=torch.uint8, device=device)
-    if out is not None:
-        if len(out) != n:
-            raise ValueError("decode_jpeg_device: one destination per stream")
-        for o, it in zip(out, items):
-            if not (isinstance(o, torch.Tensor) and o.dtype == torch.uint8 and tuple(o.shape) == it.shape and o.device == buf.device and o.stride(2) == 1
-                    and o.stride(1) == 3):
-                raise ValueError("a destination must be a uint8 [h,w,3] device tensor (or a row-pitched view of one) of the stream's size")
-    base = min([buf.data_ptr()] + ([o.data_ptr() for o in out] if out is not None else []))
-    rel = buf.data_ptr() - base
-    for j, it in enumerate(items):
-        stream_at, tables_at = it.stage(hv, places[j])
-        dst = rel + dst_at[j] if out is None else out[j].data_ptr() - base
-        pitch = 3 * it.w if out is None else int(out[j].stride(0))
-        descs[j] = (rel + stream_at, rel + tables_at, it.tables_bytes, dst, int(ws_at[j]), pitch, it.data.size, len(it.segments), FLAG_BGR if bgrs[j] else 0, 0)
-    buf[:upload].copy_(host, non_blocking=True)
-    launch_decode(device, base, buf.data_ptr(), descs, infos, work, buf.data_ptr() + status_at)
-    status_host = torch.empty(n, dtype=torch.int32, pin_memory=True)
-    status_host.copy_(buf[status_at:status_at + 4 * n].view(torch.int32), non_blocking=True)
-    torch.cuda.current_stream(device).synchronize()
-    decode_jpeg_device.last_h2d_bytes, decode_jpeg_device.last_status = upload, status_host.numpy().copy()
-    raise_status(status_host.numpy())
-    if out is not None:
-        return list(out)
-    return [buf[o:o + it.h * it.w * 3].view(it.h, it.w, 3) for o, it in zip(dst_at, items)]
-
-
-def _decode_windows(streams, index, bgr, device, out, windows) -> list:
-    """decode_jpeg_device with windows: the same layout and the same one copy, through hh_jpeg_decode_window_u8_batch."""
-    n = len(streams)
-    idx = _per_frame(index, n) if isinstance(index, (list, tuple)) else [index] * n
-    if index is not None and not isinstance(index, (list, tuple)) and n != 1:
-        raise ValueError("decode_jpeg_device: `index` is a list with one entry per stream")
-    items = [s if isinstance(s, JpegImage) else JpegImage(s, i) for s, i in zip(streams, idx)]
-    wins = [(0, 0, it.h, it.w) if w is None else tuple(int(v) for v in w) for it, w in zip(items, windows)]
-    plans = [it.window_plan(w) for it, w in zip(items, wins)]
-    bgrs = _per_frame(bgr, n)
-    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    at = _align(WIN_DESC.itemsize * n, 16)
+    at = _align(desc_t.itemsize * n, 16)
     places = []
     for p in plans:
         places.append(at)
@@ -558,8 +510,8 @@ def _decode_windows(streams, index, bgr, device, out, windows) -> list:
     host = torch.empty(upload, dtype=torch.uint8).pin_memory()
     hv = host.numpy()
     hv[:] = 0
-    descs = hv[:WIN_DESC.itemsize * n].view(WIN_DESC)
-    buf = torch.empty(at, dtype=torch.uint8, device=device)  # [descriptors | slices and tables | statuses | pixels]
+    descs = hv[:desc_t.itemsize * n].view(desc_t)
+    buf = torch.empty(at, dtype=torch.uint8, device=device)  # [descriptors | streams or slices, and tables | statuses | pixels]
     work = torch.empty(max(int(ws_at[-1]), 16), dtype=torch.uint8, device=device)
     if out is not None:
         if len(out) != n:
@@ -567,23 +519,23 @@ def _decode_windows(streams, index, bgr, device, out, windows) -> list:
         for o, p in zip(out, plans):
             if not (isinstance(o, torch.Tensor) and o.dtype == torch.uint8 and tuple(o.shape) == (p.window[2], p.window[3], 3) and o.device == buf.device
                     and o.stride(2) == 1 and o.stride(1) == 3):
-                raise ValueError("a destination must be a uint8 [height,width,3] device tensor (or a row-pitched view of one) of the window's size")
+                raise ValueError("a destination must be a uint8 [height,width,3] device tensor (or a row-pitched view of one) of the stream's or its window's size")
     base = min([buf.data_ptr()] + ([o.data_ptr() for o in out] if out is not None else []))
     rel = buf.data_ptr() - base
     infos = []
     for j, (it, p) in enumerate(zip(items, plans)):
-        stream_at, tables_at, p, info = it.stage_window(hv, places[j], p.window, p)
+        stream_at, tables_at, info = it.stage_plan(hv, places[j], p, windowed)
         infos.append(info)
         dst = rel + dst_at[j] if out is None else out[j].data_ptr() - base
         pitch = 3 * p.window[3] if out is None else int(out[j].stride(0))
-        descs[j] = it.window_desc(p, rel + stream_at, rel + tables_at, dst, int(ws_at[j]), pitch, bgrs[j])
+        descs[j] = it.window_desc(p, rel + stream_at, rel + tables_at, dst, int(ws_at[j]), pitch, bgrs[j])[:len(desc_t.names)]  # (DEC_DESC: no window)
     buf[:upload].copy_(host, non_blocking=True)
-    launch_decode_window(device, base, buf.data_ptr(), descs, np.concatenate(infos), work, buf.data_ptr() + status_at)
+    launch_decode(device, base, buf.data_ptr(), descs, np.concatenate(infos), work, buf.data_ptr() + status_at, entry)
     status_host = torch.empty(n, dtype=torch.int32, pin_memory=True)
     status_host.copy_(buf[status_at:status_at + 4 * n].view(torch.int32), non_blocking=True)
     torch.cuda.current_stream(device).synchronize()
     decode_jpeg_device.last_h2d_bytes, decode_jpeg_device.last_status = upload, status_host.numpy().copy()
-    raise_status(status_host.numpy(), "hh_jpeg_decode_window_u8_batch")
+    raise_status(status_host.numpy(), entry)
     if out is not None:
         return list(out)
     return [buf[o:o + p.window[2] * p.window[3] * 3].view(p.window[2], p.window[3], 3) for o, p in zip(dst_at, plans)]
@@ -595,28 +547,25 @@ def decode_jpeg_host(data, bgr: bool = False, index=None, pitch: int | None = No
     hh_debug_jpeg_decode_window_host instead -> uint8 [height,width,3]; `counts`: a dict that receives what that decode did (segments and
     MCUs walked, MCUs stored, blocks transformed, pixels written, stream bytes needed)."""
     a = _bytes_view(data)
+    lib = _lib.load()
     if window is not None:
         win = _window(window)
         hh, ww = int(win[0]["height"]), int(win[0]["width"])
-        pitch = 3 * ww if pitch is None else int(pitch)
-        out = np.zeros((max(hh, 0), max(pitch, 3 * ww, 0)), np.uint8)
-        status, cnt = C.c_int(0), np.zeros(1, WIN_COUNTS)
-        seg = None if index is None else np.ascontiguousarray(index)
-        _lib.check(_lib.load().hh_debug_jpeg_decode_window_host(a.ctypes.data, a.size, None if seg is None else seg.ctypes.data, 0 if seg is None else len(seg),
-                                                                win.ctypes.data, FLAG_BGR if bgr else 0, out.ctypes.data, pitch, C.byref(status),
-                                                                cnt.ctypes.data))
-        if counts is not None:
-            counts.update({k: int(cnt[0][k]) for k in WIN_COUNTS.names})
-        return np.ascontiguousarray(out[:, :3 * ww]).reshape(hh, ww, 3)
-    i = _parse(a)[0]
-    h, w = int(i["h"]), int(i["w"])
-    pitch = 3 * w if pitch is None else int(pitch)
-    out = np.zeros((h, max(pitch, 3 * w)), np.uint8)
+        cnt = np.zeros(1, WIN_COUNTS)
+        entry, before, after = lib.hh_debug_jpeg_decode_window_host, (win.ctypes.data,), (cnt.ctypes.data,)
+    else:
+        i = _parse(a)[0]
+        hh, ww = int(i["h"]), int(i["w"])
+        entry, before, after = lib.hh_debug_jpeg_decode_host, (), ()
+    pitch = 3 * ww if pitch is None else int(pitch)
+    out = np.zeros((max(hh, 0), max(pitch, 3 * ww, 0)), np.uint8)
     status = C.c_int(0)
     seg = None if index is None else np.ascontiguousarray(index)
-    _lib.check(_lib.load().hh_debug_jpeg_decode_host(a.ctypes.data, a.size, None if seg is None else seg.ctypes.data, 0 if seg is None else len(seg),
-                                                     FLAG_BGR if bgr else 0, out.ctypes.data, pitch, C.byref(status)))
-    return np.ascontiguousarray(out[:, :3 * w]).reshape(h, w, 3)
+    _lib.check(entry(a.ctypes.data, a.size, None if seg is None else seg.ctypes.data, 0 if seg is None else len(seg), *before, FLAG_BGR if bgr else 0,
+                     out.ctypes.data, pitch, C.byref(status), *after))
+    if window is not None and counts is not None:
+        counts.update({k: int(cnt[0][k]) for k in WIN_COUNTS.names})
+    return np.ascontiguousarray(out[:, :3 * ww]).reshape(hh, ww, 3)
 
 
 def load_jpeg(path, device=None, cache: JpegIndexCache | None = None, bgr: bool = False, window=None):

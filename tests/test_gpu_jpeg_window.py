@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from conftest import PKG
-from test_jpeg_decode_cpu import corpus, truncated_stream
+from test_jpeg_decode_cpu import corpus, names, truncated_stream
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -93,6 +93,33 @@ def test_decode_jpeg_device_with_windows_and_with_whole_images_mixed_in(J, batch
         assert np.array_equal(g.cpu().numpy(), corpus()[name][1])
     with pytest.raises(ValueError, match="one entry per stream"):
         J.decode_jpeg_device(streams[:3], device=DEV, windows=[None] * 2)
+
+
+def test_the_whole_image_entry_is_the_window_entry_with_every_window_the_whole_image(J, pkg):
+    """One batch through hh_jpeg_decode_u8_batch and through hh_jpeg_decode_window_u8_batch with the windows (0, 0, h, w): every
+    sampling, restart segments, a 2-MCU index, the smallest stream of the corpus (one MCU) and a truncated stream, which ends in its
+    status in both calls (the destinations are given, so the pixels are there although the call raises)."""
+    cut, cut_index = truncated_stream(J)
+    smallest = min(names(), key=lambda n: (corpus()[n][1].size, len(corpus()[n][0])))  # the fewest pixels (1 x 1), then the fewest bytes
+    picks = [("444_17x23_noise_q30_plain", None), ("422_21x43_noise_q90_plain", 2), ("420_120x200_scene_q90_rows1", None),
+             ("400_17x23_scene_q90_plain", None), (smallest, None)]
+    items = [J.JpegImage(corpus()[n][0], None if mps is None else J.build_jpeg_index(corpus()[n][0], mps)) for n, mps in picks]
+    items.append(J.JpegImage(cut, cut_index))
+    infos = [J.jpeg_info(it.data) for it in items]
+    assert {i.sampling for i in infos} == {444, 422, 420, 400} and infos[2].restart_interval and infos[4].mcu_cols * infos[4].mcu_rows == 1
+    runs = []
+    for windows in (None, [(0, 0, it.h, it.w) for it in items]):
+        out = [torch.full(it.shape, 0xA5, dtype=torch.uint8, device=DEV) for it in items]
+        with pytest.raises(pkg._lib.HHError, match=r"image 5: status 3 \(bytes exhausted\)"):
+            J.decode_jpeg_device(items, device=DEV, out=out, windows=windows)
+        runs.append((J.decode_jpeg_device.last_status.tolist(), [o.cpu().numpy() for o in out], J.decode_jpeg_device.last_h2d_bytes))
+    (status_a, pixels_a, bytes_a), (status_b, pixels_b, bytes_b) = runs
+    assert status_a == status_b == [0, 0, 0, 0, 0, 3]
+    for j, (name, _) in enumerate(picks):
+        assert np.array_equal(pixels_a[j], pixels_b[j]) and np.array_equal(pixels_a[j], corpus()[name][1]), name
+    # which entry ran: 64-byte descriptors and whole streams against 80-byte descriptors and the windows' slices
+    assert bytes_a == 64 * 6 + sum(it.staged_bytes() for it in items)
+    assert bytes_b == 80 * 6 + sum(it.window_plan((0, 0, it.h, it.w)).staged_bytes for it in items) < bytes_a
 
 
 def test_load_jpeg_with_a_window(J, tmp_path):

@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from conftest import PKG
-from test_jpeg_decode_cpu import corpus, names
+from test_jpeg_decode_cpu import bad_code_stream, corpus, names, truncated_stream
 
 
 @pytest.fixture(scope="module")
@@ -145,6 +145,33 @@ def test_a_small_window_does_strictly_less_than_the_whole_image(J):
     assert whole["stream_bytes"] == info.scan_end - info.scan_offset
     # a whole-image window gives the bytes of the whole decode
     assert np.array_equal(J.decode_jpeg_host(data, window=(0, 0, 120, 200)), J.decode_jpeg_host(data))
+
+
+def test_the_whole_image_is_the_window_that_covers_it(J, pkg):
+    """What the one decoder rests on: hh_debug_jpeg_decode_host and hh_debug_jpeg_decode_window_host with the window (0, 0, h, w) give
+    the same bytes through every segment set, the window's rectangle is the MCU grid, and a malformed scan ends in the same status."""
+    for name in names():
+        data = corpus()[name][0]
+        info = J.jpeg_info(data)
+        nmcu = info.mcu_cols * info.mcu_rows
+        bpm = 1 if info.components == 1 else FACTORS[info.sampling][0] * FACTORS[info.sampling][1] + 2
+        for key, index in indexes(name).items():
+            counts = {}
+            got = J.decode_jpeg_host(data, index=index, window=(0, 0, info.h, info.w), counts=counts)
+            assert np.array_equal(got, J.decode_jpeg_host(data, index=index)), (name, key)
+            assert counts["mcus_walked"] == counts["mcus_stored"] == nmcu and counts["blocks_transformed"] == nmcu * bpm, (name, key, counts)
+            assert counts["pixels_written"] == info.h * info.w, (name, key, counts)
+
+    def status(stream, index, window):
+        with pytest.raises(pkg._lib.HHError, match=r"status \d") as e:
+            J.decode_jpeg_host(stream, index=index, window=window)
+        return int(re.search(r"status (\d)", str(e.value)).group(1))
+
+    cut, index = truncated_stream(J)
+    bad, _ = bad_code_stream(J, pkg)
+    for stream, index, want in ((cut, index, 3), (bad, None, 1)):
+        info = J.jpeg_info(stream)
+        assert status(stream, index, None) == status(stream, index, (0, 0, info.h, info.w)) == want
 
 
 def test_window_plan_reports_the_selected_segments_and_the_slice(J):

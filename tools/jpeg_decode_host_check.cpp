@@ -71,13 +71,14 @@ static int decode(const unsigned char *bytes, long long len, const std::vector<J
         ++n_refused;
         status = -1;
     } else {
-        const JpegDecGeom g = jpeg_dec_geom(I);
+        const JpegWinRect R = jpeg_full_rect(I);  // the whole image: the rectangle is the MCU grid
+        const JpegDecGeom g = jpeg_dec_geom(I, R);
         void *ws = nullptr;
         if (posix_memalign(&ws, 16, (size_t)g.ws_bytes)) abort();
         memset(ws, 0x5a, (size_t)g.ws_bytes);
         JpegExtent ext = {0, 0};
         for (size_t s = 0; s < seg.size(); ++s) {
-            const int st = jpeg_dec_segment<true>(stream, (int)len, I, T->huff, seg[s], (int16_t *)ws, nullptr, &ext);
+            const int st = jpeg_dec_segment(stream, (int)len, I, T->huff, seg[s], R, (int16_t *)ws, nullptr, &ext);
             if (st < 0 || st > 5) bad = 1, fprintf(stderr, "FAILED: status %d\n", st);
             else if (st > status) status = st;
         }
@@ -87,7 +88,7 @@ static int decode(const unsigned char *bytes, long long len, const std::vector<J
         }
         // steps b to d run whatever the status, as the kernels do: the planes and the destination stay inside their blocks
         unsigned char *dst = (unsigned char *)malloc((size_t)I.h * I.w * 3);
-        jpeg_dec_pixels_host((unsigned char *)ws, I, *T, false, dst, 3ll * I.w);
+        jpeg_dec_window_pixels_host((unsigned char *)ws, I, *T, jpeg_full_window(I), false, dst, 3ll * I.w);
         if (!status && pixels_out) pixels_out->assign(dst, dst + (size_t)I.h * I.w * 3);
         ++n_status[status];
         if (!status) ++n_clean;

@@ -18,7 +18,7 @@
 // height x 3 * width.  A read or write one byte outside any of them is an AddressSanitizer report.  Besides: the extents the
 // segment walk reports must lie inside the slice and the rectangle's coefficients; every case ends in a refusal by name, a status
 // or a clean decode; and no status-0 result differs from the same rows and columns of the whole-image decode of the same bytes
-// through the same segments (jpeg_dec_segment + jpeg_dec_pixels_host, whatever status that decode has: damage outside the walked part
+// through the same segments (jpeg_dec_segment + jpeg_dec_window_pixels_host over the MCU grid, whatever status that decode has: damage outside the walked part
 // is not the window's).  Exit status 0: all of that held.
 #include <cstdio>
 #include <cstdlib>
@@ -54,13 +54,14 @@ static std::vector<unsigned char> make_stream(int h, int w, int sub, int quality
 // The whole image of `len` bytes through `seg`, whatever the status -> its pixels [h][w][3].
 static std::vector<unsigned char> whole(const unsigned char *stream, long long len, const JpegStreamInfo &I, const JpegDecTables &T, const std::vector<JpegSegment> &seg)
 {
-    const JpegDecGeom g = jpeg_dec_geom(I);
+    const JpegWinRect R = jpeg_full_rect(I);
+    const JpegDecGeom g = jpeg_dec_geom(I, R);
     void *ws = nullptr;
     if (posix_memalign(&ws, 16, (size_t)g.ws_bytes)) abort();
     memset(ws, 0, (size_t)g.ws_bytes);
-    for (size_t s = 0; s < seg.size(); ++s) jpeg_dec_segment<true>(stream, (int)len, I, T.huff, seg[s], (int16_t *)ws, nullptr, nullptr);
+    for (size_t s = 0; s < seg.size(); ++s) jpeg_dec_segment(stream, (int)len, I, T.huff, seg[s], R, (int16_t *)ws, nullptr, nullptr);
     std::vector<unsigned char> px((size_t)I.h * I.w * 3);
-    jpeg_dec_pixels_host((unsigned char *)ws, I, T, false, px.data(), 3ll * I.w);
+    jpeg_dec_window_pixels_host((unsigned char *)ws, I, T, jpeg_full_window(I), false, px.data(), 3ll * I.w);
     free(ws);
     return px;
 }
@@ -103,7 +104,7 @@ static int decode(const unsigned char *bytes, long long len, const std::vector<J
         unsigned char *part = (unsigned char *)malloc((size_t)part_len);
         memcpy(part, stream + slice[0], (size_t)part_len);
         void *block = nullptr, *ws = nullptr;
-        const JpegDecGeom g = jpeg_win_geom(I, R);
+        const JpegDecGeom g = jpeg_dec_geom(I, R);
         if (posix_memalign(&block, 16, (size_t)jpeg_dec_tables_bytes(nsel)) || posix_memalign(&ws, 16, (size_t)g.ws_bytes)) abort();
         jpeg_win_tables(I, *T, R, seg.data(), (int)seg.size(), slice, (unsigned char *)block);
         memset(ws, 0x5a, (size_t)g.ws_bytes);
