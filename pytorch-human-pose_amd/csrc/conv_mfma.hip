@@ -34,9 +34,22 @@ __device__ long long g_conv_dbg[8192 * 8];
 // buffers take what one KC = 32 buffer took, so the launches keep sharing CUs with the other branch lanes.
 // E: the element type (ElemBF16 / ElemF16 of mfma_dev.h): the residual unpack, the MFMA form and the 16-bit store; the fp32 NCHW
 // epilogue does not depend on it.
-template <typename E, int KS, int S, int KC, int NT, int WC, int PT, int TW, int DB>
+//
+// DUAL = 1 (conv_dual_launch; the 3x3 stride-1 8x32 form with KC = 32, NT = 1, PT = 2 only): the launch also computes a SECOND conv
+// over the same input -- 3x3, stride 2, pad 1, 64 couts, with its own weights, bias and output tensor (ConvParams::w2 / bias2 /
+// out2): the stage-0 -> 1 transition pair, whose two launches both read the 256-channel stage-0 output.  The 4x16 stride-2 outputs
+// under an 8x32 tile need only pixels of the patch the tile stages anyway (rows oy0-1 .. oy0+7, columns ox0-1 .. ox0+31), so the
+// input crosses the memory system once.  Wave w owns the secondary tile (output rows 2(w>>1), 2(w>>1)+1 x 16 pixels; couts
+// 32(w&1) .. +31): one more accumulator, its B fragments read from the patch with a column step of 2 pixels, its A fragments
+// (weights, in the packing of the stride-2 launch: 16-channel chunks) read from global memory straight into registers one chunk
+// ahead -- they are used once per tile, and another 36 KB of LDS per chunk would leave one workgroup per CU.  Per output element
+// the MFMA sequence is that of the separate launches (primary: untouched; secondary: 16-channel chunks ascending, taps ky-major
+// inside, accumulator started from the bias), so both tensors are bit-identical to the two-launch plan, which HH_NO_TRANS_DUAL=1
+// restores: it is the second implementation the tests compare this one against (tests/test_gpu_transition_dual.py).
+template <typename E, int KS, int S, int KC, int NT, int WC, int PT, int TW, int DB, int DUAL = 0>
 __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
 {
+    static_assert(!DUAL || (KS == 3 && S == 1 && KC == 32 && NT == 1 && WC == 1 && PT == 2 && TW == 32 && !DB), "the dual form: config 0 only");
     constexpr int RPT = 32 / TW;  // image rows covered by one 32-pixel MFMA column tile
     constexpr int WP = 4 / WC;    // waves along pixels
     constexpr int TH = WP * PT * RPT;
@@ -231,6 +244,26 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
                 }
     }
 
+    // ---- DUAL: the secondary conv's state.  Step j = kk * 9 + ky * 3 + kx of a 32-channel chunk (kk: its 16-channel half) is the
+    //      stride-2 launch's k-step (chunk16 = 2 * chunk + kk, tap = ky * 3 + kx).  a2[j]: the step's A fragment, 128 16-byte units
+    //      apart in the packed image ([chunk16][tap][half h][64 couts][8]).
+    constexpr int NS2 = DUAL ? 18 : 1;
+    [[maybe_unused]] u32x4 a2[NS2];
+    [[maybe_unused]] f32x16 acc2;
+    [[maybe_unused]] const u32x4 *w2_lane = nullptr;
+    [[maybe_unused]] int pb2 = 0;  // patch byte offset of this lane's secondary pixel at tap (0, 0), k half h
+    if constexpr (DUAL) {
+        const int q2 = wave >> 1, ct2 = wave & 1;
+        w2_lane = reinterpret_cast<const u32x4 *>(p.w2) + h * 64 + ct2 * 32 + r;
+        pb2 = ((2 * (2 * q2 + (r >> 4))) * PW + 2 * (r & 15)) * PS + h * 16;
+        static_for<NS2>([&](auto jc) { a2[decltype(jc)::value] = w2_lane[decltype(jc)::value * 128]; });
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 bv = *reinterpret_cast<const float4 *>(p.bias2 + ct2 * 32 + 8 * g + 4 * h);
+            acc2[4 * g + 0] = bv.x + 0.f; acc2[4 * g + 1] = bv.y + 0.f; acc2[4 * g + 2] = bv.z + 0.f; acc2[4 * g + 3] = bv.w + 0.f;
+        }
+    }
+
     // ---- MFMA over taps x 16-channel k-steps of one chunk.  LDS fragment reads run one k-step ahead
     //      (sched_group_barrier pins the order) and, when `more_c`, the next chunk's global loads are spread over the
     //      k-steps, LPS per step: issued in a burst they back-pressure the CU's load path (~10 B/cycle) and the MFMAs wait
@@ -272,6 +305,17 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
             constexpr int NC = 3 * (KC / 16), NR = PT + 2, NS = NC * NR;
             constexpr int LPR = (NL + NS - 1) / NS;
             u32x4 fa[2][3][NT], fb[2];
+            [[maybe_unused]] u32x4 fb2[2];
+            // DUAL: secondary step j2 = 3 * c + i rides on step (c, i) of the primary for i < 3 (NR = 4: 18 of the 24 steps)
+            [[maybe_unused]] auto ldb2 = [&](int j2, int buf) {
+                const int kk = j2 / 9, ky = (j2 % 9) / 3, kx = j2 % 3;
+                fb2[buf] = *reinterpret_cast<const u32x4 *>(lds_p + roff + pb2 + (ky * PW + kx) * PS + kk * 32);
+            };
+            constexpr int A2D = 6;
+            [[maybe_unused]] auto reload_a2 = [&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                a2[j] = w2_lane[(size_t)(chunk + 1) * (2 * NS2 * 64) + j * 128];
+            };
             auto lda = [&](int c, int buf) {
                 const int kx = c / (KC / 16), kk = c % (KC / 16);
 #pragma unroll
@@ -288,12 +332,16 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
             };
             lda(0, 0);
             ldb(0, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 3 * NT + 1, 0);
+            if constexpr (DUAL) ldb2(0, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 3 * NT + 1 + DUAL, 0);
             static_for<NS>([&](auto sc) {
                 constexpr int s = decltype(sc)::value, c = s / NR, i = s % NR;
-                constexpr int nread = (s + 1 < NS ? 1 : 0) + ((i == 0 && c + 1 < NC) ? 3 * NT : 0);
+                constexpr bool sec = DUAL && i < 3, sec_next = DUAL && s + 1 < NS && (s + 1) % NR < 3;
+                constexpr int j2 = 3 * c + i, j2n = 3 * ((s + 1) / NR) + (s + 1) % NR;  // this / the next step's secondary k-step
+                constexpr int nread = (s + 1 < NS ? 1 : 0) + ((i == 0 && c + 1 < NC) ? 3 * NT : 0) + (sec_next ? 1 : 0);
                 if constexpr (s + 1 < NS) ldb(s + 1, (s + 1) & 1);
                 if constexpr (i == 0 && c + 1 < NC) lda(c + 1, (c + 1) & 1);  // next combo's weights, a whole combo ahead
+                if constexpr (sec_next) ldb2(j2n, j2n & 1);
                 if constexpr (nread > 0) __builtin_amdgcn_sched_group_barrier(0x100, nread, 0);
                 static_for<LPR>([&](auto lc) { stage_slot(std::integral_constant<int, s * LPR + decltype(lc)::value>{}, std::integral_constant<int, NS * LPR>{}); });
                 {   // pin the step's staging between its LDS reads and its MFMAs: left alone, the scheduler gathers the loads of
@@ -310,8 +358,20 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
                         for (int nt = 0; nt < NT; ++nt)
                             acc[nt][pt] = E::mfma(fa[c & 1][ky][nt], fb[s & 1], acc[nt][pt]);
                 });
-                __builtin_amdgcn_sched_group_barrier(0x8, NT * (hi - lo + 1), 0);
+                if constexpr (sec) acc2 = E::mfma(a2[j2], fb2[j2 & 1], acc2);
+                __builtin_amdgcn_sched_group_barrier(0x8, NT * (hi - lo + 1) + (sec ? 1 : 0), 0);
+                // a spent fragment's register takes the same step of the next chunk -- A2D steps later, so that about a quarter of the
+                // 18 fragments are dead at any time (all 18 live: 7 VGPRs went to scratch); the reloads of the last A2D steps follow the loop
+                if constexpr (DUAL && more && s >= A2D && (s - A2D) % NR < 3) {
+                    reload_a2(std::integral_constant<int, 3 * ((s - A2D) / NR) + (s - A2D) % NR>{});
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                }
             });
+            if constexpr (DUAL && more)
+                static_for<A2D>([&](auto tc) {
+                    constexpr int s = NS - A2D + decltype(tc)::value;
+                    if constexpr (s % NR < 3) reload_a2(std::integral_constant<int, 3 * (s / NR) + s % NR>{});
+                });
             return;
         }
         u32x4 fa[2][NT], fb[2][PT];
@@ -432,6 +492,24 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p)
             }
         }
     }
+    if constexpr (DUAL) {  // secondary: lane = pixel (2 rows x 16), the wave's 32 couts; stored as the primary's 16-bit NHWC form
+        const int Y = (oy0 >> 1) + 2 * (wave >> 1) + (r >> 4), X = (ox0 >> 1) + (r & 15);
+        const bool valid = Y < p.Ho2 && X < p.Wo2;
+        const size_t pix = ((size_t)b * p.Ho2 + Y) * p.Wo2 + X;
+        const short fl = p.relu ? (short)0 : (short)-32768;
+        const i16x2 floor = {fl, fl};
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            const unsigned x0 = E::pack(acc2[8 * m + 0], acc2[8 * m + 1], floor);
+            const unsigned x1 = E::pack(acc2[8 * m + 2], acc2[8 * m + 3], floor);
+            const unsigned y0 = E::pack(acc2[8 * m + 4], acc2[8 * m + 5], floor);
+            const unsigned y1 = E::pack(acc2[8 * m + 6], acc2[8 * m + 7], floor);
+            auto s0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
+            auto s1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
+            const int c0 = (wave & 1) * 32 + 16 * m + 8 * h;
+            if (valid) *reinterpret_cast<u32x4 *>(p.out2 + pix * p.out2_cs + p.out2_coff + c0) = u32x4{s0[0], s1[0], s0[1], s1[1]};
+        }
+    }
     CONV_STAMP(6);
     if (p.clk && tid == 0 && blockIdx.x + 256 >= gridDim.x) atomicMax(p.clk + 1, wall_clock64());
 }
@@ -472,6 +550,9 @@ static const conv_fn g_fns[] = {CONV_CONFIGS(CFG_FN)};
 static const conv_fn g_fns_f16[] = {CONV_CONFIGS(CFG_FN)};
 #undef CFG_FN
 
+// the dual form (DUAL = 1) of config 0; not in the table: the engine asks for it by name (conv_dual_launch)
+static const conv_fn g_fn_dual[2] = {conv_mfma_kernel<ElemBF16, 3, 1, 32, 1, 1, 2, 32, 0, 1>, conv_mfma_kernel<ElemF16, 3, 1, 32, 1, 1, 2, 32, 0, 1>};
+
 int conv_num_configs() { return (int)(sizeof(g_configs) / sizeof(g_configs[0])); }
 const ConvConfig &conv_config(int i) { return g_configs[i]; }
 
@@ -482,6 +563,10 @@ hipError_t conv_init()
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_configs[i].lds_bytes());
         if (e != hipSuccess) return e;
         e = hipFuncSetAttribute(reinterpret_cast<const void *>(g_fns_f16[i]), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_configs[i].lds_bytes());
+        if (e != hipSuccess) return e;
+    }
+    for (const conv_fn fn : g_fn_dual) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g_configs[0].lds_bytes());
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -495,5 +580,18 @@ hipError_t conv_launch(int cfg_index, const ConvParams &p, hipStream_t stream, i
     const unsigned tiles = (unsigned)p.B * p.tiles_y * p.tiles_x, sf = (unsigned)p.ncg * (p.nphase > 1 ? p.nphase : 1);
     const unsigned grid = sf > 1 ? (tiles + 7) / 8 * 8 * sf : tiles;  // groups of 8 tiles x sf variants (see the kernel)
     HH_LAUNCH(fn, dim3(grid), dim3(256), c.lds_bytes(), stream, p);
+    return hipGetLastError();
+}
+
+hipError_t conv_dual_launch(const ConvParams &p, hipStream_t stream, int act_dtype)
+{
+    if (act_dtype != 0 && act_dtype != 1) return hipErrorInvalidValue;  // unknown element type
+    const ConvConfig &c = g_configs[0];
+    // what the kernel's dual form takes for granted
+    if (c.KS != 3 || c.S != 1 || c.KC != 32 || c.NT != 1 || c.PT != 2 || c.TW != 32 || c.DB) return hipErrorInvalidValue;
+    if (!p.w2 || !p.bias2 || !p.out2 || !p.out || p.res || p.out_f32 || p.ncg != 1 || p.nphase > 1 || p.nch0 || p.cin % 32 || p.pad_y != 1 || p.pad_x != 1 ||
+        p.osy != 1 || p.osx != 1 || p.Ho != p.Hin || p.Wo != p.Win || p.Ho2 != p.Hin / 2 || p.Wo2 != p.Win / 2 || p.out2_cs < 64)
+        return hipErrorInvalidValue;
+    HH_LAUNCH(g_fn_dual[act_dtype], dim3((unsigned)p.B * p.tiles_y * p.tiles_x), dim3(256), c.lds_bytes(), stream, p);
     return hipGetLastError();
 }

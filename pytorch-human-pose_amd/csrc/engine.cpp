@@ -32,6 +32,7 @@ PlanSwitches PlanSwitches::from_env()
     s.poison_ws = on("HH_POISON_WS");
     s.poison_lds = on("HH_POISON_LDS");
     s.no_head_fold = on("HH_NO_HEAD_FOLD");
+    s.no_trans_dual = on("HH_NO_TRANS_DUAL");
     s.no_conv_db = on("HH_NO_CONV_DB");
     s.no_final_fuse = on("HH_NO_FINAL_FUSE");
     s.keep_waits = on("HH_KEEP_WAITS");
@@ -355,8 +356,18 @@ struct Builder {
         {
             const std::string tp = bb + ".stages.0.transition_layer.transition_blocks";
             join(2);
-            lane = 0; cb(tp + ".0", "0", "1", 256, w[0], 3, 1, Y, x[0], 1);
-            lane = 1; cb(tp + ".1", "0", "1", 256, w[1], 3, 2, Y, x[1], 1);
+            // 16-bit W32: both convs in ONE launch on lane 0 (conv_mfma.hip, DUAL): the stride-2 outputs of a tile come from the patch
+            // the stride-1 conv stages, so Y is read once; lane 1 starts stage 1 behind that launch.  (HH_NO_TRANS_DUAL=1, W48 and
+            // fp8 handles: one launch per lane)
+            lane = 0;
+            Op &t0 = cb(tp + ".0", "0", "1", 256, w[0], 3, 1, Y, x[0], 1);
+            if (n.is16() && w[0] == 32 && !n.sw.no_trans_dual) {
+                t0.layer2 = L(tp + ".1.0", tp + ".1.1", 256, w[1], 3, 2);
+                t0.out2 = x[1];
+                dep(0, 1);
+            } else {
+                lane = 1; cb(tp + ".1", "0", "1", 256, w[1], 3, 2, Y, x[1], 1);
+            }
             lane = 0;
         }
         tap("stages.0#0", x[0], w[0]);
@@ -1244,6 +1255,24 @@ int hh_net::enqueue_conv(const Op &op, int B, int H, int W, float *o1, float *o2
         if (op.in3 >= 0) p.src_delta2 = tensors[op.in3].ptr - (ti.ptr + op.in_coff);
     }
     p.cout_store = op.cout_store >= 0 ? op.cout_store : round_up(l.cout, 8);
+    if (op.layer2 >= 0) {  // the dual transition launch: config 0's tiles for every map width, layer2's stride-2 conv beside it
+        const ConvLayer &l2 = layers[op.layer2];
+        const TensorDesc &t2 = tensors[op.out2];
+        const ConvConfig &c = conv_config(0);
+        if (dtype == 2 || l.ks != 3 || l.stride != 1 || l.KC != c.KC || l.NT != c.NT || l.db || l.ncg != 1 || l2.ks != 3 || l2.stride != 2 || l2.KC != 16 ||
+            l2.NT != 2 || l2.ncg != 1 || l2.cin_pad != l.cin_pad || t2.shift != ti.shift + 1) {
+            hh_set_error("plan: the dual transition launch does not fit conv_mfma.hip (HH_NO_TRANS_DUAL=1)");
+            return 1;
+        }
+        p.w2 = l2.d_w; p.bias2 = l2.d_bias;
+        p.out2 = t2.ptr; p.out2_cs = t2.C; p.out2_coff = 0;
+        p.Ho2 = p.Hin / 2; p.Wo2 = p.Win / 2;
+        p.tiles_x = (p.Wo + c.TW - 1) / c.TW;
+        p.tiles_y = (p.Ho + c.th() - 1) / c.th();
+        if (prof_enabled && prof_record(op, HH_CFG_TRANS_DUAL, op_cost(op, B, H, W), &p.clk)) return 1;
+        HH_CHECK_HIP(conv_dual_launch(p, s, act()));
+        return 0;
+    }
     const int cfg = hh_pick_config(l.ks, l.stride, l.KC, l.NT, p.Wo, l.db);
     const ConvConfig &c = conv_config(cfg);
     p.tiles_x = (p.Wo + c.TW - 1) / c.TW;
@@ -1315,7 +1344,7 @@ int hh_net::check_plan(std::string *why) const
         if (l >= lc.open) { if (why) *why = "op " + std::to_string(i) + " runs on a lane that was never forked"; return 1; }
         std::vector<int> rd, wr;
         switch (op.kind) {
-        case OP_CONV: rd = {op.in, op.res, op.in2, op.in3}; wr = {op.out}; break;
+        case OP_CONV: rd = {op.in, op.res, op.in2, op.in3}; wr = {op.out, op.out2}; break;
         case OP_UPADD: case OP_UPSUM: rd = {op.in, op.up[0], op.up[1], op.up[2]}; wr = {op.out}; break;
         case OP_BB: rd = {op.in}; wr = {op.out}; break;
         case OP_JUNC: rd = {op.in, op.in2, op.res, op.in3}; wr = {op.out, op.out2}; break;
@@ -1418,6 +1447,12 @@ OpCost hh_net::op_cost(const Op &op, int B, int H, int W, bool fin) const
         c.flops = 2.0 * opix * acin * l.cout * l.ks * l.ks;
         c.bytes = (e4m3 ? 1.0 : 2.0) * ((double)B * hin * win * acin + acin * l.cout * l.ks * l.ks * nph) +
                   (out_e + res_e + (op.f32_out ? 4 : 0)) * opix * l.cout;
+        if (op.layer2 >= 0) {  // dual transition launch: + the stride-2 conv's FLOPs, weights and output; the input is read once
+            const ConvLayer &l2 = layers[op.layer2];
+            const double opix2 = (double)B * (hin / 2) * (win / 2);
+            c.flops += 2.0 * opix2 * l2.cin * l2.cout * 9.0;
+            c.bytes += 2.0 * l2.cin * l2.cout * 9.0 + 2.0 * opix2 * l2.cout;
+        }
         break;
     }
     default:

@@ -77,7 +77,8 @@ enum OpKind { OP_CONV, OP_UPADD, OP_TAP, OP_BB, OP_JOIN, OP_AVGPOOL, OP_LINEAR, 
 
 struct Op {
     OpKind kind = OP_CONV;
-    int layer = -1, layer2 = -1;  // layer2: second conv of a fused BasicBlock / downsample conv of a junction (-1: none)
+    int layer = -1, layer2 = -1;  // layer2: second conv of a fused BasicBlock / downsample conv of a junction / OP_CONV: the stride-2 conv
+                                  // of the dual transition launch, which writes out2 (-1: none)
     int layer3 = -1;              // OP_JUNC: first conv of the next Bottleneck (-1: none)
     int layer4 = -1;              // OP_JUNC, pair mode: conv3 of the PREVIOUS Bottleneck, whose output is made again from in3 (= its t2) instead of read
     int in2 = -1, out2 = -1;      // OP_JUNC: downsample input x, and the t1 output
@@ -158,6 +159,8 @@ struct PlanSwitches {
                                    // (test_tall_layout_vs_per_image_layout, test_schedule_and_fusion_switches)
     bool no_conv_db = false;       // HH_NO_CONV_DB=1: the 128- / 256-channel 3x3 convs on the single-buffer KC = 32 instantiations (round 2)
                                    // (test_schedule_and_fusion_switches)
+    bool no_trans_dual = false;    // HH_NO_TRANS_DUAL=1: the stage-0 -> 1 transition as its two launches, one per lane (default, 16-bit W32: one
+                                   // dual-output launch on lane 0, bit-identical) (test_dual_transition_equals_the_two_launches)
     bool no_head_fold = false;     // HH_NO_HEAD_FOLD=1: init_heatmaps_head writes its output into the concat buffer, the transposed conv reads it
                                    // (test_head_folded_into_the_transposed_conv)
     bool fp8_trunk8 = false;       // HH_FP8_TRUNK=e4m3: fp8 handles re-quantise the residual trunk to e4m3 in every block (the round-2 plan)

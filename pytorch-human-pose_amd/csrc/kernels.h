@@ -56,6 +56,14 @@ struct ConvParams {
     // in + src_delta1 elements, the rest from in + src_delta2.  nch0 = 0: a single input.
     int nch0, nch1;
     ptrdiff_t src_delta1, src_delta2;
+    // Dual launch (conv_dual_launch): a second, stride-2 3x3 conv (pad 1, 64 couts, ReLU as `relu`) over the SAME input, computed from
+    // the patch the first one stages.  w2: its weights packed as for its own launch (KC = 16, COUT_T = 64), bias2: 64 floats,
+    // out2: [B, Ho2, Wo2, out2_cs] with Ho2 = Hin / 2, Wo2 = Win / 2.
+    const bf16_raw *w2;
+    const float *bias2;
+    bf16_raw *out2;
+    int out2_cs, out2_coff;
+    int Ho2, Wo2;
 };
 
 // Tile configuration of one kernel instantiation.
@@ -78,6 +86,10 @@ const ConvConfig &conv_config(int i);
 // Launches config `cfg_index`; the grid is B*tiles_y*tiles_x*ncg blocks of 256 threads.
 hipError_t conv_launch(int cfg_index, const ConvParams &p, hipStream_t stream, int act_dtype = 0);
 hipError_t conv_init();  // raises the dynamic-LDS limit of every instantiation
+// The stage-0 -> 1 transition pair as ONE launch: config 0 (3x3 stride 1, 32 couts, 8x32 tiles; `p` as for conv_launch) plus the
+// stride-2 64-cout conv of p.w2 / p.bias2 / p.out2 over the same staged patch.  Needs ncg = 1, no residual, no fp32 output.
+#define HH_CFG_TRANS_DUAL 108  // pseudo instantiation index used by the profiler
+hipError_t conv_dual_launch(const ConvParams &p, hipStream_t stream, int act_dtype = 0);
 
 // ---- fp8 path (conv_fp8.hip): e4m3 NHWC activations with one scale per tensor, e4m3 weights with one scale per cout
 struct Fp8ConvParams {
