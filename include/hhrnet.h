@@ -11,6 +11,14 @@
  * addresses (e.g. torch.Tensor.data_ptr()); `stream` is a hipStream_t passed as void*
  * (NULL = the legacy default stream).  Calls are asynchronous on `stream` unless noted.
  * A handle is not re-entrant; different handles may be used from different threads.
+ *
+ * The `typedef struct hh_x { ... } hh_x;` blocks and the HH_* macros / enumerators below are the ONLY definition of the descriptor
+ * tables, limits and flags: the kernels under csrc/ include this file and take these types, and the Python binding parses these
+ * bodies into numpy dtypes (_lib.struct_dtype).  Keep a body to what that parser reads: fixed-width scalars, int, long long, float,
+ * double, pointers, arrays bounded by a number or an HH_* macro defined above the struct, earlier hh_* structs by value; no
+ * bit-fields, unions or function pointers.  Where the library and Python had spelled a field differently the spelling here won,
+ * except for two that were changed here without moving a byte: hh_render_prim.rgb[3] (was r, g, b) and hh_jpeg_win_desc as
+ * { hh_jpeg_dec_desc d; hh_jpeg_window window; } (was the ten fields of the decode descriptor written out again).
  */
 #ifndef HHRNET_H
 #define HHRNET_H
@@ -450,7 +458,7 @@ typedef struct hh_render_prim {
     int32_t cx, cy;
     uint16_t A, B;
     float c, s;
-    uint8_t r, g, b, kind;
+    uint8_t rgb[3], kind; /* the colour as drawn into the R,G,B frame (one array, as every user fills it; the bytes r, g, b of before) */
     int16_t x0, y0, x1, y1;
 } hh_render_prim;
 typedef struct hh_render_desc {
@@ -732,11 +740,9 @@ typedef struct hh_jpeg_window {
     int32_t top, left, height, width;
 } hh_jpeg_window;
 typedef struct hh_jpeg_win_desc {
-    long long stream_offset, tables_offset, tables_bytes, dst_offset, ws_offset, pitch;
-    int32_t stream_length, nseg;   /* the slice's length; the selected segments */
-    int32_t flags, reserved;
+    hh_jpeg_dec_desc d;            /* stream_offset / stream_length: the shipped slice; nseg: the selected segments */
     hh_jpeg_window window;
-} hh_jpeg_win_desc;
+} hh_jpeg_win_desc;                /* (the same 80 bytes as before, when the fields of `d` were written out here a second time) */
 typedef struct hh_jpeg_window_counts {
     long long segments_walked, mcus_walked, mcus_stored, blocks_transformed, pixels_written, stream_bytes;
 } hh_jpeg_window_counts;

@@ -1,4 +1,5 @@
-"""ctypes binding of csrc/libhhrnet.so (the C-ABI declared in include/hhrnet.h).
+"""ctypes binding of csrc/libhhrnet.so (the C-ABI declared in include/hhrnet.h): signatures, constants and the layout of every
+descriptor struct are read from that header, which is their only definition.
 
 There is no CPU fallback: if the HIP library cannot be loaded every product entry point
 raises.  `build()` compiles it in-tree with hipcc for gfx950 (works without a GPU).
@@ -11,6 +12,7 @@ import os
 import re
 import subprocess
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -47,14 +49,50 @@ def _kind(decl: str, proto: str, is_return: bool = False):
     return _SCALARS[base]
 
 
-def parse_header(text: str) -> tuple[dict, dict]:
-    """include/hhrnet.h -> ({entry point: (restype, [argtypes])}, {HH_* macro with an integer value: value}).  Every statement that
-    is not a typedef or an enum must be a prototype `ret hh_name(args);` whose types are known: anything else raises, nothing is
-    guessed (a wrong argument kind would corrupt a call silently)."""
+# what a struct field may be made of; a pointer of any type is an address (marked, so that struct_ctype can make it a c_void_p)
+_FIELDS = {"int": "<i4", "int32_t": "<i4", "uint32_t": "<u4", "int64_t": "<i8", "long long": "<i8", "float": "<f4", "double": "<f8",
+           "uint8_t": "u1", "int16_t": "<i2", "uint16_t": "<u2"}
+_POINTER = np.dtype("<u8", metadata={"pointer": True})
+
+
+def _struct(name: str, body: str, consts: dict, structs: dict) -> np.dtype:
+    """The aligned numpy dtype of one `typedef struct hh_x { body } hh_x;`: scalars, pointers (`<u8`), arrays bounded by numbers or
+    HH_* macros, earlier hh_* structs."""
+    fields = []
+    for decl in filter(None, (" ".join(d.replace("*", " * ").split()) for d in body.split(";"))):
+        one = r"(?:\* (?:const )?)*\w+(?:\[\w+\])*"  # a declarator: `x`, `* x`, `* const * x`, `x[6]`, `x[HH_N][6]`
+        m = re.fullmatch(rf"(?:const )?([\w ]+?) ({one}(?: ?, ?{one})*)", decl)
+        base = structs.get(m.group(1)) or _FIELDS.get(m.group(1)) if m else None
+        if m is None or base is None and not all("*" in item for item in m.group(2).split(",")):
+            raise HHError(f"{HEADER}: cannot derive a field type for `{decl}` in struct {name}")
+        for item in m.group(2).split(","):
+            field, *dims = re.findall(r"\w+", item.replace("const ", ""))
+            shape = tuple(int(d) if d.isdigit() else consts.get(d, -1) for d in dims)
+            if min(shape, default=1) < 1:
+                raise HHError(f"{HEADER}: array bound of `{field}` in struct {name} is neither a number nor a parsed HH_* macro")
+            fields.append((field, _POINTER if "*" in item else base, shape))
+    if len({f[0] for f in fields}) != len(fields) or not fields:
+        raise HHError(f"{HEADER}: struct {name} is empty or repeats a field name")
+    return np.dtype(fields, align=True)
+
+
+def _parse(text: str) -> tuple[dict, dict, dict]:
+    """include/hhrnet.h -> (signatures, constants, struct dtypes); see parse_header and parse_structs."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     consts = {k: int(v) for k, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(HH_\w+)[ \t]+(\d+)[ \t]*$", text, flags=re.M)}
     text = re.sub(r"^[ \t]*#[^\n]*$", " ", text, flags=re.M)  # preprocessor lines
-    text = re.sub(r"\{[^{}]*\}", " ", text)                  # struct and enum bodies
+    for body in re.findall(r"\benum\s*\{([^{}]*)\}\s*;", text):
+        consts.update((k, int(v)) for k, v in re.findall(r"(HH_\w+)\s*=\s*(\d+)\s*(?:,|$)", body))
+    text = re.sub(r"\benum\s*\{[^{}]*\}", "enum", text)
+    structs = {}
+
+    def struct(m):
+        name, body, alias = m.groups()
+        if alias != name or "{" in body or name in structs:
+            raise HHError(f"{HEADER}: struct {name} nests a struct or union, is not closed by `}} {name};`, or is repeated")
+        structs[name] = _struct(name, body, consts, structs)
+        return " "
+    text = re.sub(r"\btypedef\s+struct\s+(hh_\w+)\s*\{(.*?)\}\s*(\w*)\s*;", struct, text, flags=re.S)
     text = re.sub(r'extern\s+"C"\s*\{|\}', " ", text)        # the extern "C" bracket
     sigs = {}
     for stmt in text.split(";"):
@@ -67,13 +105,48 @@ def parse_header(text: str) -> tuple[dict, dict]:
         ret, name, params = m.groups()
         params = [] if params.strip() == "void" else params.split(",")
         sigs[name] = (_kind(ret, proto, is_return=True), [_kind(p, proto) for p in params])
-    return sigs, consts
+    return sigs, consts, structs
+
+
+def parse_header(text: str) -> tuple[dict, dict]:
+    """include/hhrnet.h -> ({entry point: (restype, [argtypes])}, {HH_* macro or enumerator with an integer value: value}).  Every
+    statement that is not a typedef or an enum must be a prototype `ret hh_name(args);` whose types are known, and every field of
+    every struct body must be understood (parse_structs): anything else raises, nothing is guessed (a wrong argument kind or field
+    offset would corrupt a call silently)."""
+    return _parse(text)[:2]
+
+
+def parse_structs(text: str) -> dict:
+    """include/hhrnet.h -> {hh_* struct: its numpy dtype, laid out as the C compiler lays it out (align=True)}."""
+    return _parse(text)[2]
 
 
 @functools.cache
-def _header() -> tuple[dict, dict]:
+def _header() -> tuple[dict, dict, dict]:
     with open(HEADER) as f:
-        return parse_header(f.read())
+        return _parse(f.read())
+
+
+def const(name: str) -> int:
+    """The value of the macro or enumerator HH_<name> of include/hhrnet.h."""
+    return _header()[1]["HH_" + name]
+
+
+def struct_dtype(name: str) -> np.dtype:
+    """The one definition of a descriptor table's row in Python: the dtype derived from the struct's body in include/hhrnet.h."""
+    return _header()[2][name]
+
+
+def struct_ctype(name: str):
+    """The same field list as a ctypes.Structure class, for the few structs that are passed one at a time with byref()."""
+    fields = []
+    for field in struct_dtype(name).names:
+        base, shape = struct_dtype(name)[field].subdtype or (struct_dtype(name)[field], ())
+        kind = C.c_void_p if (base.metadata or {}).get("pointer") else np.ctypeslib.as_ctypes_type(base)
+        for n in reversed(shape):
+            kind = kind * n
+        fields.append((field, kind))
+    return type(name, (C.Structure,), {"_fields_": fields})
 
 
 # the act_dtype of the *_dt training entry points

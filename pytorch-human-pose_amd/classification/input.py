@@ -35,9 +35,7 @@ from ..keypoints import jpeg as jp
 from ..keypoints.transforms_utils import IMAGENET_MEAN, IMAGENET_STD
 
 # hh_crop_desc of include/hhrnet.h (56 bytes)
-_CROP_DESC = np.dtype([("image_offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("top", "<i4"), ("left", "<i4"), ("ch", "<i4"), ("cw", "<i4"),
-                       ("rh", "<i4"), ("rw", "<i4"), ("oy", "<i4"), ("ox", "<i4"), ("flip", "<i4"), ("antialias", "<i4")])
-assert _CROP_DESC.itemsize == 56
+_CROP_DESC = _lib.struct_dtype("hh_crop_desc")
 
 
 def _hw(img) -> tuple:

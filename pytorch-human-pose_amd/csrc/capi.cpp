@@ -216,9 +216,8 @@ int hh_preprocess_u8(const unsigned char *image_hwc, int h, int w, const double 
 int hh_preprocess_u8_batch(const unsigned char *images_base, const hh_image_desc *descs_dev, int n, float *out_nchw, int H, int W,
                            const float mean[3], const float stdv[3], void *stream)
 {
-    static_assert(sizeof(hh_image_desc) == sizeof(HHImageDesc) && sizeof(HHImageDesc) == 64, "descriptor layout");
     if (!images_base || !descs_dev || !out_nchw || n <= 0 || n > 65535 || H <= 0 || W <= 0) { hh_set_error("hh_preprocess_u8_batch: bad argument"); return 1; }
-    HH_CHECK_HIP(launch_preprocess_batch(images_base, reinterpret_cast<const HHImageDesc *>(descs_dev), n, out_nchw, H, W, mean, stdv,
+    HH_CHECK_HIP(launch_preprocess_batch(images_base, descs_dev, n, out_nchw, H, W, mean, stdv,
                                          (hipStream_t)stream));
     return 0;
 }
@@ -226,10 +225,9 @@ int hh_preprocess_u8_batch(const unsigned char *images_base, const hh_image_desc
 int hh_train_images_u8_batch(const unsigned char *batch_base, const hh_train_desc *descs_dev, int n, float *out_nchw, int H, int W,
                              const float mean[3], const float stdv[3], void *stream)
 {
-    static_assert(sizeof(hh_train_desc) == sizeof(HHTrainDesc) && sizeof(HHTrainDesc) == 272 && HH_TRAIN_MAX_STAGES == HH_TRAIN_STAGES, "descriptor layout");
     if (!batch_base || !descs_dev || !out_nchw || !mean || !stdv) { hh_set_error("hh_train_images_u8_batch: null pointer"); return 1; }
     if (n <= 0 || n > 65535 || H <= 0 || W <= 0 || (int64_t)H * W > (1 << 30)) { hh_set_error("hh_train_images_u8_batch: need 0 < n <= 65535 and 0 < H * W <= 2^30"); return 1; }
-    HH_CHECK_HIP(launch_train_images(batch_base, reinterpret_cast<const HHTrainDesc *>(descs_dev), n, out_nchw, H, W, mean, stdv, (hipStream_t)stream));
+    HH_CHECK_HIP(launch_train_images(batch_base, descs_dev, n, out_nchw, H, W, mean, stdv, (hipStream_t)stream));
     return 0;
 }
 
@@ -249,14 +247,13 @@ int hh_train_masks_u8_batch(const unsigned char *batch_base, const hh_train_desc
         total += (int64_t)st.h[k] * st.w[k];
     }
     if (total > (1 << 30)) { hh_set_error("hh_train_masks_u8_batch: the stages' pixel count exceeds 2^30"); return 1; }
-    HH_CHECK_HIP(launch_train_masks(batch_base, reinterpret_cast<const HHTrainDesc *>(descs_dev), n, st, (hipStream_t)stream));
+    HH_CHECK_HIP(launch_train_masks(batch_base, descs_dev, n, st, (hipStream_t)stream));
     return 0;
 }
 
 int hh_resized_crop_u8_batch(const unsigned char *batch_base, const hh_crop_desc *descs_dev, const hh_crop_desc *descs_host, int n, float *out_nchw,
                              int H, int W, const float mean[3], const float stdv[3], void *stream)
 {
-    static_assert(sizeof(hh_crop_desc) == sizeof(HHCropDesc) && sizeof(HHCropDesc) == 56, "descriptor layout");
     const char *fn = "hh_resized_crop_u8_batch";
     if (!batch_base || !descs_dev || !descs_host || !out_nchw || !mean || !stdv) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
     if (n <= 0 || n > 65535 || H <= 0 || W <= 0 || H > HH_CROP_MAX_EXTENT || W > HH_CROP_MAX_EXTENT || (int64_t)H * W > (1 << 30)) {
@@ -276,13 +273,12 @@ int hh_resized_crop_u8_batch(const unsigned char *batch_base, const hh_crop_desc
         if (d.top < 0 || d.left < 0 || (int64_t)d.top + d.ch > d.h || (int64_t)d.left + d.cw > d.w) { hh_set_error(who + "crop rectangle outside its image"); return 1; }
         if (d.oy < 0 || d.ox < 0 || (int64_t)d.oy + H > d.rh || (int64_t)d.ox + W > d.rw) { hh_set_error(who + "output window outside the virtual resized crop"); return 1; }
     }
-    HH_CHECK_HIP(launch_resized_crop(batch_base, reinterpret_cast<const HHCropDesc *>(descs_dev), n, out_nchw, H, W, mean, stdv, (hipStream_t)stream));
+    HH_CHECK_HIP(launch_resized_crop(batch_base, descs_dev, n, out_nchw, H, W, mean, stdv, (hipStream_t)stream));
     return 0;
 }
 
 int hh_mosaic_u8_batch(unsigned char *batch_base, const hh_mosaic_desc *descs_dev, const hh_mosaic_desc *descs_host, int n, int S, void *stream)
 {
-    static_assert(sizeof(hh_mosaic_desc) == sizeof(HHMosaicDesc) && sizeof(HHMosaicDesc) == 112 && sizeof(hh_mosaic_tile) == sizeof(HHMosaicTile), "descriptor layout");
     const char *fn = "hh_mosaic_u8_batch";
     if (!batch_base || !descs_dev || !descs_host) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
     if (n <= 0 || n > 65535) { hh_set_error(std::string(fn) + ": need 0 < n <= 65535"); return 1; }
@@ -301,7 +297,7 @@ int hh_mosaic_u8_batch(unsigned char *batch_base, const hh_mosaic_desc *descs_de
             if (q.image_offset < 0 || q.mask_offset < 0) { hh_set_error(tile + "negative offset"); return 1; }
         }
     }
-    HH_CHECK_HIP(launch_mosaic(batch_base, reinterpret_cast<const HHMosaicDesc *>(descs_dev), n, S, (hipStream_t)stream));
+    HH_CHECK_HIP(launch_mosaic(batch_base, descs_dev, n, S, (hipStream_t)stream));
     return 0;
 }
 
@@ -315,14 +311,13 @@ int hh_render_config(int out[4])
 // The checks of a render call that need no device: every frame's descriptor and its primitives, on the caller's host copy.
 static int render_check(const char *fn, const hh_render_desc *descs_host, const hh_render_prim *prims_host, int num_prims, int n, int *max_tiles)
 {
-    static_assert(sizeof(hh_render_desc) == sizeof(RenderDesc) && sizeof(hh_render_prim) == sizeof(RenderPrim), "table layout");
     if (n <= 0 || n > 65535) { hh_set_error(std::string(fn) + ": need 0 < n <= 65535"); return 1; }
     if (num_prims < 0) { hh_set_error(std::string(fn) + ": negative table length"); return 1; }
     int tiles = 1;
     for (int b = 0; b < n; ++b) {
-        const RenderDesc &d = reinterpret_cast<const RenderDesc *>(descs_host)[b];
+        const RenderDesc &d = descs_host[b];
         if (d.prim_count > 0 && !prims_host) { hh_set_error(std::string(fn) + ": null primitive table"); return 1; }
-        const char *why = render_check_frame(d, reinterpret_cast<const RenderPrim *>(prims_host), num_prims, HH_RENDER_MAX_PRIMS);
+        const char *why = render_check_frame(d, prims_host, num_prims, HH_RENDER_MAX_PRIMS);
         if (why) { hh_set_error(std::string(fn) + ": frame " + std::to_string(b) + ": " + why); return 1; }
         const int t = ((d.h + RENDER_TH - 1) / RENDER_TH) * ((d.w + RENDER_TW - 1) / RENDER_TW);
         tiles = t > tiles ? t : tiles;
@@ -339,7 +334,7 @@ int hh_render_poses_u8_batch(unsigned char *batch_base, const hh_render_desc *de
     if ((uintptr_t)descs_dev % 8 || (uintptr_t)prims_dev % 4) { hh_set_error(std::string(fn) + ": descs_dev must be 8-byte and prims_dev 4-byte aligned"); return 1; }
     int max_tiles = 0;
     if (render_check(fn, descs_host, prims_host, num_prims, n, &max_tiles)) return 1;
-    HH_CHECK_HIP(launch_render_poses(batch_base, reinterpret_cast<const RenderDesc *>(descs_dev), reinterpret_cast<const RenderPrim *>(prims_dev), n,
+    HH_CHECK_HIP(launch_render_poses(batch_base, descs_dev, prims_dev, n,
                                      max_tiles, (hipStream_t)stream));
     return 0;
 }
@@ -350,9 +345,9 @@ int hh_debug_render_host(const unsigned char *src, unsigned char *dst, const hh_
     if (!src || !dst || !desc) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
     int max_tiles = 0;
     if (render_check(fn, desc, prims, num_prims, 1, &max_tiles)) return 1;
-    RenderDesc d = *reinterpret_cast<const RenderDesc *>(desc);  // src and dst are the frame's own buffers here
+    RenderDesc d = *desc;  // src and dst are the frame's own buffers here
     d.src_offset = d.dst_offset = 0;
-    render_debug_host(src, dst, d, reinterpret_cast<const RenderPrim *>(prims));
+    render_debug_host(src, dst, d, prims);
     return 0;
 }
 
@@ -397,7 +392,6 @@ int hh_jpeg_config(int out[4])
 int hh_jpeg_encode_u8_batch(unsigned char *batch_base, const hh_jpeg_desc *descs_dev, const hh_jpeg_desc *descs_host, int n,
                             unsigned char *workspace, long long workspace_bytes, int32_t *lengths_dev, void *stream)
 {
-    static_assert(sizeof(hh_jpeg_desc) == sizeof(JpegDesc), "table layout");
     const std::string fn = "hh_jpeg_encode_u8_batch";
     if (!batch_base || !descs_dev || !descs_host || !workspace || !lengths_dev) { hh_set_error(fn + ": null pointer"); return 1; }
     if (n <= 0 || n > 65535) { hh_set_error(fn + ": need 0 < n <= 65535"); return 1; }
@@ -407,7 +401,7 @@ int hh_jpeg_encode_u8_batch(unsigned char *batch_base, const hh_jpeg_desc *descs
     }
     int max_mcus = 1, max_rows = 1;
     for (int b = 0; b < n; ++b) {
-        const JpegDesc &d = reinterpret_cast<const JpegDesc *>(descs_host)[b];
+        const JpegDesc &d = descs_host[b];
         const char *why = jpeg_check_desc(d);
         if (why) { hh_set_error(fn + ": frame " + std::to_string(b) + ": " + why); return 1; }
         const JpegGeom g = jpeg_geom(d.h, d.w, d.subsampling);
@@ -415,7 +409,7 @@ int hh_jpeg_encode_u8_batch(unsigned char *batch_base, const hh_jpeg_desc *descs
         max_mcus = std::max(max_mcus, g.mrows * g.mcols);
         max_rows = std::max(max_rows, g.mrows);
     }
-    HH_CHECK_HIP(launch_jpeg_encode(batch_base, reinterpret_cast<const JpegDesc *>(descs_dev), n, max_mcus, max_rows, workspace, lengths_dev,
+    HH_CHECK_HIP(launch_jpeg_encode(batch_base, descs_dev, n, max_mcus, max_rows, workspace, lengths_dev,
                                     (hipStream_t)stream));
     return 0;
 }
@@ -424,7 +418,7 @@ int hh_debug_jpeg_encode_host(const unsigned char *src, const hh_jpeg_desc *desc
 {
     const std::string fn = "hh_debug_jpeg_encode_host";
     if (!src || !desc || !out || !length) { hh_set_error(fn + ": null pointer"); return 1; }
-    const JpegDesc &d = *reinterpret_cast<const JpegDesc *>(desc);
+    const JpegDesc &d = *desc;
     const char *why = jpeg_check_desc(d);
     if (why) { hh_set_error(fn + ": " + why); return 1; }
     std::vector<JpegVec8> work((size_t)jpeg_geom(d.h, d.w, d.subsampling).nblk * 8);
@@ -449,9 +443,6 @@ int hh_debug_jpeg_fdct(const int32_t samples[64], int32_t rows_out[64], int32_t 
 }
 
 // Baseline JPEG decode (jpeg_decode.hip, jpeg_dec_math.h).
-static_assert(sizeof(hh_jpeg_stream_info) == sizeof(JpegStreamInfo) && sizeof(hh_jpeg_segment) == sizeof(JpegSegment) &&
-                  sizeof(hh_jpeg_dec_desc) == sizeof(JpegDecDesc),
-              "table layout");
 static const char *const JPEG_STATUS_NAME[6] = {"ok", "bad Huffman code", "zero run past coefficient 63", "bytes exhausted",
                                                 "missing or unexpected RSTm", "bad segment"};
 
@@ -475,7 +466,7 @@ static const char *jpeg_dec_check_info(const JpegStreamInfo &I, bool rebased = f
 int hh_jpeg_parse(const unsigned char *bytes, long long len, hh_jpeg_stream_info *info)
 {
     if (!bytes || !info) { hh_set_error("hh_jpeg_parse: null pointer"); return 1; }
-    const char *why = jpeg_dec_parse(bytes, len, reinterpret_cast<JpegStreamInfo *>(info), nullptr);
+    const char *why = jpeg_dec_parse(bytes, len, info, nullptr);
     if (why) { hh_set_error(std::string("hh_jpeg_parse: ") + why); return 1; }
     return 0;
 }
@@ -488,7 +479,7 @@ int hh_jpeg_restart_segments(const unsigned char *bytes, long long len, hh_jpeg_
     const char *why = jpeg_dec_parse(bytes, len, &I, nullptr);
     if (!why && !I.restart_interval) why = "the stream has no restart interval (use hh_jpeg_index_host)";
     if (!why && capacity < I.nseg_restart) why = "capacity below the number of segments";
-    if (!why) why = jpeg_dec_restart_segments(bytes, I, reinterpret_cast<JpegSegment *>(entries));
+    if (!why) why = jpeg_dec_restart_segments(bytes, I, entries);
     if (why) { hh_set_error(fn + ": " + why); return 1; }
     *n = I.nseg_restart;
     return 0;
@@ -502,22 +493,22 @@ int hh_jpeg_index_host(const unsigned char *bytes, long long len, int mcus_per_s
     std::vector<JpegDecTables> T(1);
     const char *why = jpeg_dec_parse(bytes, len, &I, &T[0]);
     int status = 0;
-    if (!why) why = jpeg_dec_index(bytes, len, I, T[0], mcus_per_segment > 0 ? mcus_per_segment : I.mcols, reinterpret_cast<JpegSegment *>(entries), capacity, n, &status);
+    if (!why) why = jpeg_dec_index(bytes, len, I, T[0], mcus_per_segment > 0 ? mcus_per_segment : I.mcols, entries, capacity, n, &status);
     if (why) { hh_set_error(fn + ": " + why + (status ? std::string(": ") + JPEG_STATUS_NAME[status] : std::string())); return 1; }
     return 0;
 }
 
 long long hh_jpeg_decode_workspace_bytes(const hh_jpeg_stream_info *info)
 {
-    const char *why = info ? jpeg_dec_check_info(*reinterpret_cast<const JpegStreamInfo *>(info)) : "null pointer";
+    const char *why = info ? jpeg_dec_check_info(*info) : "null pointer";
     if (why) { hh_set_error(std::string("hh_jpeg_decode_workspace_bytes: ") + why); return -1; }
-    const JpegStreamInfo &I = *reinterpret_cast<const JpegStreamInfo *>(info);
+    const JpegStreamInfo &I = *info;
     return jpeg_dec_geom(I, jpeg_full_rect(I)).ws_bytes;
 }
 
 long long hh_jpeg_decode_tables_bytes(const hh_jpeg_stream_info *info, int nseg)
 {
-    const char *why = info ? jpeg_dec_check_info(*reinterpret_cast<const JpegStreamInfo *>(info)) : "null pointer";
+    const char *why = info ? jpeg_dec_check_info(*info) : "null pointer";
     if (!why && nseg < 1) why = "nseg must be at least 1";
     if (why) { hh_set_error(std::string("hh_jpeg_decode_tables_bytes: ") + why); return -1; }
     return jpeg_dec_tables_bytes(nseg);
@@ -574,8 +565,8 @@ static int jpeg_decode_batch(const std::string &fn, bool windowed, unsigned char
     for (int b = 0; b < n; ++b) {
         const JpegWinDesc *wd = windowed ? static_cast<const JpegWinDesc *>(descs_host) + b : nullptr;
         const JpegDecDesc &d = wd ? wd->d : static_cast<const JpegDecDesc *>(descs_host)[b];
-        const JpegStreamInfo &I = reinterpret_cast<const JpegStreamInfo *>(infos_host)[b];
-        const JpegWindow *win = wd ? &wd->win : nullptr;
+        const JpegStreamInfo &I = infos_host[b];
+        const JpegWindow *win = wd ? &wd->window : nullptr;
         JpegDecGeom g;
         const char *why = jpeg_dec_check_image(batch_base, d, I, win, workspace_bytes, &g);
         if (why) { hh_set_error(fn + ": image " + std::to_string(b) + ": " + why); return 1; }
@@ -618,7 +609,7 @@ static int jpeg_decode_host(const std::string &fn, const unsigned char *bytes, l
     JpegStreamInfo I;
     std::vector<JpegDecTables> T(1);
     const char *why = jpeg_dec_parse(bytes, len, &I, &T[0]);
-    const JpegWindow W = why ? JpegWindow() : window ? *reinterpret_cast<const JpegWindow *>(window) : jpeg_full_window(I);
+    const JpegWindow W = why ? JpegWindow() : window ? *window : jpeg_full_window(I);
     if (!why && window) why = jpeg_win_check(I, W);
     if (!why && pitch < 3ll * W.width) why = window ? "pitch below 3 * width" : "pitch below 3 * w";
     if (!why && (flags & ~1)) why = "unknown flag";
@@ -626,10 +617,10 @@ static int jpeg_decode_host(const std::string &fn, const unsigned char *bytes, l
     std::vector<JpegSegment> own;
     if (!why && !entries) {
         why = jpeg_own_segments(bytes, I, own);
-        entries = reinterpret_cast<const hh_jpeg_segment *>(own.data());
+        entries = own.data();
         nseg = (int)own.size();
     }
-    const JpegSegment *seg = reinterpret_cast<const JpegSegment *>(entries);
+    const JpegSegment *seg = entries;
     const JpegWinRect R = why ? JpegWinRect() : jpeg_win_rect(I, W);
     int nsel = nseg;
     long long slice[2] = {0, len};
@@ -664,17 +655,14 @@ int hh_debug_jpeg_decode_host(const unsigned char *bytes, long long len, const h
 }
 
 // The window decode (the rule: hh_jpeg_decode_window_u8_batch in include/hhrnet.h).
-static_assert(sizeof(hh_jpeg_window) == sizeof(JpegWindow) && sizeof(hh_jpeg_win_desc) == sizeof(JpegWinDesc) &&
-                  sizeof(hh_jpeg_window_counts) == sizeof(JpegWinCounts),
-              "table layout");
 
 long long hh_jpeg_decode_window_workspace_bytes(const hh_jpeg_stream_info *info, const hh_jpeg_window *window)
 {
-    const char *why = info && window ? jpeg_dec_check_info(*reinterpret_cast<const JpegStreamInfo *>(info), true) : "null pointer";
-    if (!why) why = jpeg_win_check(*reinterpret_cast<const JpegStreamInfo *>(info), *reinterpret_cast<const JpegWindow *>(window));
+    const char *why = info && window ? jpeg_dec_check_info(*info, true) : "null pointer";
+    if (!why) why = jpeg_win_check(*info, *window);
     if (why) { hh_set_error(std::string("hh_jpeg_decode_window_workspace_bytes: ") + why); return -1; }
-    const JpegStreamInfo &I = *reinterpret_cast<const JpegStreamInfo *>(info);
-    return jpeg_dec_geom(I, jpeg_win_rect(I, *reinterpret_cast<const JpegWindow *>(window))).ws_bytes;
+    const JpegStreamInfo &I = *info;
+    return jpeg_dec_geom(I, jpeg_win_rect(I, *window)).ws_bytes;
 }
 
 int hh_jpeg_decode_window_select(const hh_jpeg_stream_info *info, const hh_jpeg_segment *entries, int nseg, const hh_jpeg_window *window, int *nsel,
@@ -682,12 +670,12 @@ int hh_jpeg_decode_window_select(const hh_jpeg_stream_info *info, const hh_jpeg_
 {
     const std::string fn = "hh_jpeg_decode_window_select";
     if (!info || !entries || !window || !nsel || !slice) { hh_set_error(fn + ": null pointer"); return 1; }
-    const JpegStreamInfo &I = *reinterpret_cast<const JpegStreamInfo *>(info);
-    const JpegWindow &W = *reinterpret_cast<const JpegWindow *>(window);
+    const JpegStreamInfo &I = *info;
+    const JpegWindow &W = *window;
     const char *why = jpeg_dec_check_info(I);
     if (!why && nseg < 1) why = "nseg must be at least 1";
     if (!why) why = jpeg_win_check(I, W);
-    if (!why) why = jpeg_win_select(I, jpeg_win_rect(I, W), reinterpret_cast<const JpegSegment *>(entries), nseg, nsel, slice);
+    if (!why) why = jpeg_win_select(I, jpeg_win_rect(I, W), entries, nseg, nsel, slice);
     if (why) { hh_set_error(fn + ": " + why); return 1; }
     return 0;
 }
@@ -699,15 +687,15 @@ int hh_jpeg_decode_window_tables(const unsigned char *bytes, long long len, cons
     if (!bytes || !entries || !window || !out || !nsel || !slice) { hh_set_error(fn + ": null pointer"); return 1; }
     JpegStreamInfo I;
     std::vector<JpegDecTables> T(1);
-    const JpegWindow &W = *reinterpret_cast<const JpegWindow *>(window);
+    const JpegWindow &W = *window;
     const char *why = nseg < 1 ? "nseg must be at least 1" : jpeg_dec_parse(bytes, len, &I, &T[0]);
     if (!why) why = jpeg_win_check(I, W);
     int n = 0;
     long long sl[2] = {0, 0};
-    if (!why) why = jpeg_win_select(I, jpeg_win_rect(I, W), reinterpret_cast<const JpegSegment *>(entries), nseg, &n, sl);
+    if (!why) why = jpeg_win_select(I, jpeg_win_rect(I, W), entries, nseg, &n, sl);
     if (!why && out_bytes < jpeg_dec_tables_bytes(n)) why = "room below hh_jpeg_decode_tables_bytes of the selected segments";
     if (why) { hh_set_error(fn + ": " + why); return 1; }
-    jpeg_win_tables(I, T[0], jpeg_win_rect(I, W), reinterpret_cast<const JpegSegment *>(entries), nseg, sl, out);
+    jpeg_win_tables(I, T[0], jpeg_win_rect(I, W), entries, nseg, sl, out);
     *nsel = n, slice[0] = sl[0], slice[1] = sl[1];
     return 0;
 }
@@ -773,12 +761,8 @@ int hh_unnormalize_u8(const float *x_chw, int H, int W, const double mean[3], co
 static int panels_check(const char *fn, const hh_panel_map *maps_host, int n, const void *image, int H, int W, const void *lut, const void *canvas, int Hc,
                         int Wc, long long pitch, bool *any_minmax)
 {
-    static_assert(sizeof(hh_panel_map) == sizeof(PanelMap), "table layout");
-    static_assert(HH_PANEL_MAX_MAPS == PANEL_MAX_MAPS && HH_PANEL_PARTS == PANEL_PARTS, "limits of include/hhrnet.h");
-    static_assert(HH_PANEL_DIRECT == PANEL_DIRECT && HH_PANEL_SINGLE == PANEL_SINGLE && HH_PANEL_NESTED == PANEL_NESTED && HH_PANEL_AVERAGE == PANEL_AVERAGE, "kinds");
-    static_assert(HH_PANEL_CLIP == PANEL_CLIP && HH_PANEL_MINMAX == PANEL_MINMAX, "flags");
     if (!maps_host || !image || !lut || !canvas) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
-    const char *why = panel_check(reinterpret_cast<const PanelMap *>(maps_host), n, H, W, Hc, Wc, pitch);
+    const char *why = panel_check(maps_host, n, H, W, Hc, Wc, pitch);
     if (why) { hh_set_error(std::string(fn) + ": " + why); return 1; }
     *any_minmax = false;
     for (int i = 0; i < n; ++i) *any_minmax |= (maps_host[i].flags & HH_PANEL_MINMAX) != 0;
@@ -794,7 +778,7 @@ int hh_heatmap_panels_u8(const hh_panel_map *maps_dev, const hh_panel_map *maps_
     if ((uintptr_t)maps_dev % 8) { hh_set_error(std::string(fn) + ": maps_dev must be 8-byte aligned"); return 1; }
     if (panels_check(fn, maps_host, n, image, H, W, lut, canvas, Hc, Wc, pitch, &any_minmax)) return 1;
     if (any_minmax && (!scratch || (uintptr_t)scratch % 4)) { hh_set_error(std::string(fn) + ": a map asks for min-max and scratch is null or misaligned"); return 1; }
-    HH_CHECK_HIP(launch_panels(reinterpret_cast<const PanelMap *>(maps_dev), n, any_minmax, image, H, W, lut, canvas, Hc, Wc, pitch, scratch, (hipStream_t)stream));
+    HH_CHECK_HIP(launch_panels(maps_dev, n, any_minmax, image, H, W, lut, canvas, Hc, Wc, pitch, scratch, (hipStream_t)stream));
     return 0;
 }
 
@@ -805,7 +789,7 @@ int hh_debug_heatmap_panels_host(const hh_panel_map *maps, int n, const unsigned
     bool any_minmax = false;
     if (panels_check(fn, maps, n, image, H, W, lut, canvas, Hc, Wc, pitch, &any_minmax)) return 1;
     std::vector<PanelRange> ranges(n);
-    panels_debug_host(reinterpret_cast<const PanelMap *>(maps), n, image, H, W, lut, canvas, Hc, Wc, pitch, ranges.data());
+    panels_debug_host(maps, n, image, H, W, lut, canvas, Hc, Wc, pitch, ranges.data());
     return 0;
 }
 
@@ -813,12 +797,8 @@ int hh_debug_heatmap_panels_host(const hh_panel_map *maps, int n, const unsigned
 // pointers are there and aligned and that its counts are the host copy's.  Nothing behind a device pointer is read.
 static int coco_tables_check(const char *fn, const hh_coco_tables *dev, const hh_coco_tables *host)
 {
-    static_assert(sizeof(hh_coco_tables) == sizeof(CocoTables), "table layout");
-    static_assert(HH_COCO_MAX_DET == COCO_MAX_DET && HH_COCO_MAX_GT == COCO_MAX_GT && HH_COCO_MAX_K == COCO_MAX_K && HH_COCO_MAX_T == COCO_MAX_T &&
-                      HH_COCO_MAX_A == COCO_MAX_A && HH_COCO_GT_IGNORE == COCO_GT_IGNORE && HH_COCO_GT_CROWD == COCO_GT_CROWD,
-                  "limits and flags of include/hhrnet.h");
     char msg[192];
-    const char *why = coco_check(reinterpret_cast<const CocoTables *>(host), msg, sizeof msg);
+    const char *why = coco_check(host, msg, sizeof msg);
     if (why) { hh_set_error(std::string(fn) + ": " + why); return 1; }
     if (!dev) return 0;  // (the host entry point)
     const void *p8[] = {dev->oks_off, dev->dt_xy, dev->dt_score, dev->dt_area, dev->gt_xyv, dev->gt_area, dev->gt_bbox, dev->vars, dev->area_rng, dev->thr};
@@ -847,7 +827,7 @@ int hh_coco_oks(const hh_coco_tables *tables_dev, const hh_coco_tables *tables_h
     if (!tables_dev || !oks) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
     if ((uintptr_t)oks % 8) { hh_set_error(std::string(fn) + ": oks is not 8-byte aligned"); return 1; }
     if (coco_tables_check(fn, tables_dev, tables_host)) return 1;
-    HH_CHECK_HIP(launch_coco_eval(1, *reinterpret_cast<const CocoTables *>(tables_dev), nullptr, oks, nullptr, nullptr, nullptr, (hipStream_t)stream));
+    HH_CHECK_HIP(launch_coco_eval(1, *tables_dev, nullptr, oks, nullptr, nullptr, nullptr, (hipStream_t)stream));
     return 0;
 }
 
@@ -858,7 +838,7 @@ int hh_coco_match(const hh_coco_tables *tables_dev, const hh_coco_tables *tables
     if (!tables_dev || !oks) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
     if ((uintptr_t)oks % 8) { hh_set_error(std::string(fn) + ": oks is not 8-byte aligned"); return 1; }
     if (coco_outputs_check(fn, dt_match, dt_ignore, gt_ignore) || coco_tables_check(fn, tables_dev, tables_host)) return 1;
-    HH_CHECK_HIP(launch_coco_eval(2, *reinterpret_cast<const CocoTables *>(tables_dev), oks, nullptr, dt_match, dt_ignore, gt_ignore, (hipStream_t)stream));
+    HH_CHECK_HIP(launch_coco_eval(2, *tables_dev, oks, nullptr, dt_match, dt_ignore, gt_ignore, (hipStream_t)stream));
     return 0;
 }
 
@@ -868,7 +848,7 @@ int hh_coco_evaluate(const hh_coco_tables *tables_dev, const hh_coco_tables *tab
     const char *fn = "hh_coco_evaluate";
     if (!tables_dev) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
     if (coco_outputs_check(fn, dt_match, dt_ignore, gt_ignore) || coco_tables_check(fn, tables_dev, tables_host)) return 1;
-    HH_CHECK_HIP(launch_coco_eval(0, *reinterpret_cast<const CocoTables *>(tables_dev), nullptr, nullptr, dt_match, dt_ignore, gt_ignore, (hipStream_t)stream));
+    HH_CHECK_HIP(launch_coco_eval(0, *tables_dev, nullptr, nullptr, dt_match, dt_ignore, gt_ignore, (hipStream_t)stream));
     return 0;
 }
 
@@ -880,7 +860,7 @@ int hh_coco_evaluate_host(const hh_coco_tables *tables_host, const double *oks_i
     if (match && coco_outputs_check(fn, dt_match, dt_ignore, gt_ignore)) return 1;
     if (!match && !oks_out) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
     if (coco_tables_check(fn, nullptr, tables_host)) return 1;
-    coco_eval_host(*reinterpret_cast<const CocoTables *>(tables_host), oks_in, oks_in ? nullptr : oks_out, match, dt_match, dt_ignore, gt_ignore);
+    coco_eval_host(*tables_host, oks_in, oks_in ? nullptr : oks_out, match, dt_match, dt_ignore, gt_ignore);
     return 0;
 }
 
@@ -888,16 +868,11 @@ int hh_coco_evaluate_host(const hh_coco_tables *tables_host, const double *oks_i
 static int track_args_check(const char *fn, const hh_track_params *params, const void *state, const float *joints, const float *scores,
                             const int32_t *num_people, const int32_t *flags, int S, int F)
 {
-    static_assert(sizeof(hh_track_params) == sizeof(TrackParams), "parameter layout");
-    static_assert(HH_TRACK_MAX_TRACKS == TRACK_MAX_TRACKS && HH_TRACK_MAX_K == TRACK_MAX_K && HH_TRACK_MAX_PEOPLE == TRACK_MAX_PEOPLE &&
-                      HH_TRACK_SOLVER_GUARD == TRACK_SOLVER_GUARD && HH_TRACK_POOL_FULL == TRACK_POOL_FULL && HH_DECODE_FALLBACK == TRACK_DECODE_FALLBACK &&
-                      HH_DECODE_SOLVER_GUARD == TRACK_DECODE_SOLVER_GUARD,
-                  "limits and flags of include/hhrnet.h");
     if (!params || !state || !joints || !scores || !num_people) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
     if ((uintptr_t)state % 8) { hh_set_error(std::string(fn) + ": state is not 8-byte aligned"); return 1; }
     if ((uintptr_t)joints % 4 || (uintptr_t)scores % 4 || (uintptr_t)num_people % 4 || (uintptr_t)flags % 4) { hh_set_error(std::string(fn) + ": an input is not 4-byte aligned"); return 1; }
     if (S < 0 || F < 0 || (int64_t)S * F > (1 << 24)) { hh_set_error(std::string(fn) + ": S and F must be >= 0 and S * F <= 2^24"); return 1; }
-    if (const char *why = track_check(reinterpret_cast<const TrackParams *>(params))) { hh_set_error(std::string(fn) + ": " + why); return 1; }
+    if (const char *why = track_check(params)) { hh_set_error(std::string(fn) + ": " + why); return 1; }
     return 0;
 }
 static int track_outputs_check(const char *fn, const int32_t *track_ids, const float *smooth, const int32_t *out_flags)
@@ -911,14 +886,14 @@ static int track_assign_check(const char *fn, const double *sim, const int32_t *
     if (!sim || !ids || !match) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
     if ((uintptr_t)sim % 8 || (uintptr_t)ids % 4 || (uintptr_t)match % 4) { hh_set_error(std::string(fn) + ": sim must be 8-byte, ids and match 4-byte aligned"); return 1; }
     if (n < 0 || n > (1 << 24)) { hh_set_error(std::string(fn) + ": n outside 0..2^24"); return 1; }
-    if (T < 1 || T > TRACK_MAX_TRACKS || P < 1 || P > TRACK_MAX_PEOPLE) { hh_set_error(std::string(fn) + ": T and P must lie in 1..64"); return 1; }
+    if (T < 1 || T > HH_TRACK_MAX_TRACKS || P < 1 || P > HH_TRACK_MAX_PEOPLE) { hh_set_error(std::string(fn) + ": T and P must lie in 1..64"); return 1; }
     if (!(min_oks > 0.0) || !(min_oks <= 1.0)) { hh_set_error(std::string(fn) + ": min_oks outside (0, 1]"); return 1; }
     return 0;
 }
 
 int64_t hh_track_state_bytes(int K, int max_tracks)
 {
-    if (K < 1 || K > TRACK_MAX_K || max_tracks < 1 || max_tracks > TRACK_MAX_TRACKS) { hh_set_error("hh_track_state_bytes: K and max_tracks must lie in 1..64"); return -1; }
+    if (K < 1 || K > HH_TRACK_MAX_K || max_tracks < 1 || max_tracks > HH_TRACK_MAX_TRACKS) { hh_set_error("hh_track_state_bytes: K and max_tracks must lie in 1..64"); return -1; }
     return track_state_bytes(K, max_tracks);
 }
 
@@ -927,7 +902,7 @@ int hh_track_reset(void *state, int K, int max_tracks, int nstreams, void *strea
     const char *fn = "hh_track_reset";
     if (!state) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
     if ((uintptr_t)state % 8) { hh_set_error(std::string(fn) + ": state is not 8-byte aligned"); return 1; }
-    if (K < 1 || K > TRACK_MAX_K || max_tracks < 1 || max_tracks > TRACK_MAX_TRACKS || nstreams < 0 || nstreams > (1 << 24)) {
+    if (K < 1 || K > HH_TRACK_MAX_K || max_tracks < 1 || max_tracks > HH_TRACK_MAX_TRACKS || nstreams < 0 || nstreams > (1 << 24)) {
         hh_set_error(std::string(fn) + ": K and max_tracks must lie in 1..64, nstreams in 0..2^24");
         return 1;
     }
@@ -940,7 +915,7 @@ int hh_track_step(const hh_track_params *params, void *state, const float *joint
 {
     const char *fn = "hh_track_step";
     if (track_outputs_check(fn, track_ids, smooth, out_flags) || track_args_check(fn, params, state, joints, scores, num_people, flags, S, F)) return 1;
-    HH_CHECK_HIP(launch_track_step(*reinterpret_cast<const TrackParams *>(params), state, joints, scores, num_people, flags, S, F, track_ids, smooth, out_flags,
+    HH_CHECK_HIP(launch_track_step(*params, state, joints, scores, num_people, flags, S, F, track_ids, smooth, out_flags,
                                    (hipStream_t)stream));
     return 0;
 }
@@ -950,7 +925,7 @@ int hh_track_step_host(const hh_track_params *params, void *state, const float *
 {
     const char *fn = "hh_track_step_host";
     if (track_outputs_check(fn, track_ids, smooth, out_flags) || track_args_check(fn, params, state, joints, scores, num_people, flags, S, F)) return 1;
-    track_step_host(*reinterpret_cast<const TrackParams *>(params), state, joints, scores, num_people, flags, S, F, track_ids, smooth, out_flags);
+    track_step_host(*params, state, joints, scores, num_people, flags, S, F, track_ids, smooth, out_flags);
     return 0;
 }
 
@@ -961,7 +936,7 @@ int hh_track_similarity(const hh_track_params *params, void *state, const float 
     if (!sim) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
     if ((uintptr_t)sim % 8) { hh_set_error(std::string(fn) + ": sim is not 8-byte aligned"); return 1; }
     if (track_args_check(fn, params, state, joints, scores, num_people, flags, S, 1)) return 1;
-    HH_CHECK_HIP(launch_track_similarity(*reinterpret_cast<const TrackParams *>(params), state, joints, scores, num_people, flags, S, sim, (hipStream_t)stream));
+    HH_CHECK_HIP(launch_track_similarity(*params, state, joints, scores, num_people, flags, S, sim, (hipStream_t)stream));
     return 0;
 }
 
@@ -1015,14 +990,13 @@ long long hh_crowd_polygon_toggles(const double *xy, int k, int h, int w, unsign
 static int crowd_check(const char *fn, const hh_crowd_mask_desc *descs_host, const hh_crowd_seg_desc *segs_host, const unsigned char *host_base, int n,
                        int num_segs, int *max_tiles)
 {
-    static_assert(sizeof(hh_crowd_mask_desc) == sizeof(CrowdMaskDesc) && sizeof(hh_crowd_seg_desc) == sizeof(CrowdSegDesc), "table layout");
     if (!descs_host || !host_base || (num_segs > 0 && !segs_host)) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
     if (n <= 0 || n > 65535) { hh_set_error(std::string(fn) + ": need 0 < n <= 65535"); return 1; }
     if (num_segs < 0) { hh_set_error(std::string(fn) + ": negative table length"); return 1; }
     int tiles = 1;
     for (int b = 0; b < n; ++b) {
-        const CrowdMaskDesc &d = reinterpret_cast<const CrowdMaskDesc *>(descs_host)[b];
-        const char *why = crowd_check_mask(d, reinterpret_cast<const CrowdSegDesc *>(segs_host), num_segs, host_base);
+        const CrowdMaskDesc &d = descs_host[b];
+        const char *why = crowd_check_mask(d, segs_host, num_segs, host_base);
         if (why) { hh_set_error(std::string(fn) + ": mask " + std::to_string(b) + ": " + why); return 1; }
         tiles = std::max(tiles, ((d.w + CROWD_TW - 1) / CROWD_TW) * ((d.h + CROWD_TH - 1) / CROWD_TH));
     }
@@ -1039,7 +1013,7 @@ int hh_crowd_masks_u8_batch(unsigned char *batch_base, const hh_crowd_mask_desc 
     if ((uintptr_t)batch_base % 4) { hh_set_error(std::string(fn) + ": batch_base must be 4-byte aligned"); return 1; }
     int max_tiles = 0;
     if (crowd_check(fn, descs_host, segs_host, host_base, n, num_segs, &max_tiles)) return 1;
-    HH_CHECK_HIP(launch_crowd_masks(batch_base, reinterpret_cast<const CrowdMaskDesc *>(descs_dev), reinterpret_cast<const CrowdSegDesc *>(segs_dev), n,
+    HH_CHECK_HIP(launch_crowd_masks(batch_base, descs_dev, segs_dev, n,
                                     max_tiles, (hipStream_t)stream));
     return 0;
 }
@@ -1051,7 +1025,7 @@ int hh_debug_crowd_masks_host(unsigned char *mask, const hh_crowd_mask_desc *des
     if (!mask) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
     int max_tiles = 0;
     if (crowd_check(fn, desc_host, segs_host, host_base, 1, num_segs, &max_tiles)) return 1;
-    crowd_mask_host(mask, *reinterpret_cast<const CrowdMaskDesc *>(desc_host), reinterpret_cast<const CrowdSegDesc *>(segs_host), host_base);
+    crowd_mask_host(mask, *desc_host, segs_host, host_base);
     return 0;
 }
 
@@ -1516,15 +1490,14 @@ int hh_linear_backward(const float *x, const float *w, const float *dy, int B, i
 
 int hh_softmax_xent(const float *logits, const int64_t *targets, int B, int N, float *dlogits, hh_xent_result *result, void *stream)
 {
-    static_assert(sizeof(hh_xent_result) == sizeof(XentResult) && sizeof(long long) == sizeof(int64_t), "hh_xent_result layout");
+    static_assert(sizeof(long long) == sizeof(int64_t), "targets");
     if (!logits || !targets || !result || B <= 0 || N <= 0) { hh_set_error("hh_softmax_xent: bad argument"); return 1; }
-    HH_CHECK_HIP(launch_softmax_xent(logits, (const long long *)targets, B, N, dlogits, (XentResult *)result, (hipStream_t)stream));
+    HH_CHECK_HIP(launch_softmax_xent(logits, (const long long *)targets, B, N, dlogits, result, (hipStream_t)stream));
     return 0;
 }
 
 // ---- device optimizer step (optim.hip).  Table layout in table_dev: [tensors][chunks][groups], each 8-byte aligned.
-static_assert(sizeof(hh_optim_tensor) == sizeof(OptimTensor) && sizeof(hh_optim_group) == sizeof(OptimGroup) && sizeof(OptimTensor) == 56 &&
-              sizeof(OptimGroup) == 56 && sizeof(OptimChunk) == 8, "hh_optim_tensor / hh_optim_group layout");
+static_assert(sizeof(OptimChunk) == 8, "chunk list layout");
 
 // the checks every entry point shares; -> the chunk count, or -1 with the error set
 static int64_t optim_count_chunks(const hh_optim_tensor *t, int ntensors, int ngroups, const char *who)
@@ -1621,7 +1594,6 @@ int hh_optim_step(int algo, const hh_optim_tensor *tensors_host, int ntensors, c
 
 // ---- weight EMA (ema.hip).  Table layout in the EMA table: [rows][chunks][row_of: one int per optimizer tensor].  The chunk list is of
 // all rows (hh_ema_update, hh_ema_swap) or of the rows no optimizer tensor names (hh_optim_step_ema); the buffer is sized for all.
-static_assert(sizeof(hh_ema_row) == sizeof(EmaRow) && sizeof(EmaRow) == 24, "hh_ema_row layout");
 
 // -> the chunk count of all rows, or -1 with the error set
 static int64_t ema_count_chunks(const char *who, const hh_ema_row *rows, int nrows)

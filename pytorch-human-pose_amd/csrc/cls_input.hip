@@ -59,14 +59,14 @@ __device__ __forceinline__ AxisTaps axis_taps(int i, int in, int out, int antial
     return t;
 }
 
-__global__ __launch_bounds__(CROP_THREADS) void resized_crop_kernel(const unsigned char *__restrict__ base, const HHCropDesc *__restrict__ descs,
+__global__ __launch_bounds__(CROP_THREADS) void resized_crop_kernel(const unsigned char *__restrict__ base, const hh_crop_desc *__restrict__ descs,
                                                                     float *__restrict__ out, int H, int W, float m0, float m1, float m2,
                                                                     float s0, float s1, float s2)
 {
     __shared__ float to_tensor[256];
     __shared__ float rows[CROP_CHUNK][3][CROP_TW];
     const int tid = threadIdx.x, xi = tid % CROP_TW, yi = tid / CROP_TW;
-    const HHCropDesc d = descs[blockIdx.z];
+    const hh_crop_desc d = descs[blockIdx.z];
     to_tensor[tid] = (float)tid / 255.0f;  // CROP_THREADS == 256
 
     const int x = blockIdx.x * CROP_TW + xi, y = blockIdx.y * CROP_TH + yi;
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(CROP_THREADS) void resized_crop_kernel(const unsign
     for (int c = 0; c < 3; ++c) o[(size_t)c * H * W] = (acc[c] - mean[c]) / stdv[c];
 }
 
-hipError_t launch_resized_crop(const unsigned char *base, const HHCropDesc *descs, int n, float *out, int H, int W, const float mean[3],
+hipError_t launch_resized_crop(const unsigned char *base, const hh_crop_desc *descs, int n, float *out, int H, int W, const float mean[3],
                                const float stdv[3], hipStream_t s)
 {
     hipLaunchKernelGGL(resized_crop_kernel, dim3((W + CROP_TW - 1) / CROP_TW, (H + CROP_TH - 1) / CROP_TH, n), dim3(CROP_THREADS), 0, s, base, descs,

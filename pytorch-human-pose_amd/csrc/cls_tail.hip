@@ -105,7 +105,7 @@ hipError_t launch_linear_backward(const float *x, const float *w, const float *d
 // no logit is read at the target's index.  The row losses are added wave by wave in row order, then the 16 waves in order.
 #define XENT_WAVES 16
 __global__ __launch_bounds__(64 * XENT_WAVES) void softmax_xent_kernel(const float *__restrict__ z, const long long *__restrict__ targets, int B,
-                                                                        int N, float *__restrict__ dz, XentResult *__restrict__ result)
+                                                                        int N, float *__restrict__ dz, hh_xent_result *__restrict__ result)
 {
     __shared__ double sh_loss[XENT_WAVES];
     __shared__ int sh_cnt[XENT_WAVES][3];
@@ -153,12 +153,12 @@ __global__ __launch_bounds__(64 * XENT_WAVES) void softmax_xent_kernel(const flo
         double s = 0.0;
         int c1 = 0, c5 = 0, f = 0;
         for (int w = 0; w < XENT_WAVES; ++w) { s += sh_loss[w]; c1 += sh_cnt[w][0]; c5 += sh_cnt[w][1]; f |= sh_cnt[w][2]; }
-        XentResult r;
+        hh_xent_result r;
         r.loss = (float)(s / (double)B); r.top1 = c1; r.top5 = c5; r.flags = (unsigned)f;
         *result = r;
     }
 }
-hipError_t launch_softmax_xent(const float *logits, const long long *targets, int B, int N, float *dlogits, XentResult *result, hipStream_t s)
+hipError_t launch_softmax_xent(const float *logits, const long long *targets, int B, int N, float *dlogits, hh_xent_result *result, hipStream_t s)
 {
     hipLaunchKernelGGL(softmax_xent_kernel, dim3(1), dim3(64 * XENT_WAVES), 0, s, logits, targets, B, N, dlogits, result);
     return hipGetLastError();

@@ -20,9 +20,9 @@ __global__ __launch_bounds__(COCO_THREADS) void coco_eval_kernel(const CocoTable
                                                                  int32_t *__restrict__ dt_match, uint8_t *__restrict__ dt_ignore,
                                                                  uint8_t *__restrict__ gt_ignore)
 {
-    __shared__ double s_oks[COCO_MAX_DET * COCO_MAX_GT];
-    __shared__ double s_gt_area[COCO_MAX_GT], s_dt_area[COCO_MAX_DET];
-    __shared__ uint8_t s_gt_flags[COCO_MAX_GT];
+    __shared__ double s_oks[HH_COCO_MAX_DET * HH_COCO_MAX_GT];
+    __shared__ double s_gt_area[HH_COCO_MAX_GT], s_dt_area[HH_COCO_MAX_DET];
+    __shared__ uint8_t s_gt_flags[HH_COCO_MAX_GT];
     const int i = blockIdx.x, tid = threadIdx.x;  // i < I = the grid's size
     const int d0 = t.dt_off[i], D = t.dt_off[i + 1] - d0, g0 = t.gt_off[i], G = t.gt_off[i + 1] - g0;  // D <= 32, G <= 128 (checked by the caller)
     const int pairs = D * G;                                                                               // <= 4096 = the LDS array
@@ -64,7 +64,7 @@ hipError_t launch_coco_eval(int mode, const CocoTables &dev, const double *oks_i
 
 void coco_eval_host(const CocoTables &t, const double *oks_in, double *oks_out, bool match, int32_t *dt_match, uint8_t *dt_ignore, uint8_t *gt_ignore)
 {
-    double *scratch = new double[COCO_MAX_DET * COCO_MAX_GT];
+    double *scratch = new double[HH_COCO_MAX_DET * HH_COCO_MAX_GT];
     for (int i = 0; i < t.I; ++i) coco_image_host(t, i, oks_in, oks_out, scratch, match, dt_match, dt_ignore, gt_ignore);
     delete[] scratch;
 }

@@ -10,6 +10,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/hhrnet.h"
+
 #if defined(__HIPCC__)
 #define HH_CHD __host__ __device__ __forceinline__
 #else
@@ -19,31 +21,13 @@
 #pragma clang fp contract(off)
 #endif
 
-// The limits (HH_COCO_* of include/hhrnet.h).  One workgroup owns one image: its D x G OKS values live in LDS (32 KB of fp64 at the limits),
+// The limits are HH_COCO_* of include/hhrnet.h.  One workgroup owns one image: its D x G OKS values live in LDS (32 KB of fp64 at the limits),
 // one lane walks one (area range, threshold) with the "ground truth taken" set as two 64-bit words, so A * T <= 64 = one wave.
-enum { COCO_MAX_DET = 32, COCO_MAX_GT = 128, COCO_MAX_K = 64, COCO_MAX_T = 16, COCO_MAX_A = 4, COCO_THREADS = 256 };
-enum { COCO_GT_IGNORE = 1, COCO_GT_CROWD = 2 };
-static_assert(COCO_MAX_A * COCO_MAX_T <= 64 && COCO_MAX_GT == 128, "one wave of walks, two words of ground truths");
+enum { COCO_THREADS = 256 };
+static_assert(HH_COCO_MAX_A * HH_COCO_MAX_T <= 64 && HH_COCO_MAX_GT == 128, "one wave of walks, two words of ground truths");
 
-// hh_coco_tables of include/hhrnet.h (13 pointers + 8 int32 = 136 bytes).
-struct CocoTables {
-    const int32_t *dt_off;    // [I + 1] detections of image i: rows dt_off[i] .. dt_off[i + 1] - 1, score-descending, already cut
-    const int32_t *gt_off;    // [I + 1]
-    const int64_t *oks_off;   // [I + 1] oks_off[i] = sum over j < i of D_j * G_j: where image i's D x G matrix starts in a concatenated buffer
-    const double *dt_xy;      // [N, K, 2]
-    const double *dt_score;   // [N] (not read by the kernels: the accumulate's sort key, kept with the rows it belongs to)
-    const double *dt_area;    // [N]
-    const double *gt_xyv;     // [M, K, 3]
-    const double *gt_area;    // [M]
-    const double *gt_bbox;    // [M, 4] x, y, w, h
-    const uint8_t *gt_flags;  // [M] COCO_GT_IGNORE | COCO_GT_CROWD
-    const double *vars;       // [K] (2 sigma)^2
-    const double *area_rng;   // [A, 2] lo, hi
-    const double *thr;        // [T]
-    int32_t I, N, M, K, A, T;
-    int32_t reserved[2];
-};
-static_assert(sizeof(CocoTables) == 136, "table layout");
+using CocoTables = hh_coco_tables;
+static_assert(sizeof(hh_coco_tables) == 136, "ABI 3");
 
 // np.max((0, a)) of one element: NaN stays NaN.
 HH_CHD double coco_pos(double a) { return a <= 0.0 ? 0.0 : a; }
@@ -76,7 +60,7 @@ HH_CHD double coco_oks_pair(const double *xy, const double *xyv, const double *b
 
 // The ground truths of one image for one area range as two bit sets over the packed (original) order: ignored, and crowd.
 struct CocoGtSets { uint64_t ign[2], crowd[2]; };
-HH_CHD bool coco_gt_ignored(double area, int flags, double lo, double hi) { return (flags & COCO_GT_IGNORE) || area < lo || area > hi; }
+HH_CHD bool coco_gt_ignored(double area, int flags, double lo, double hi) { return (flags & HH_COCO_GT_IGNORE) || area < lo || area > hi; }
 HH_CHD CocoGtSets coco_gt_sets(const double *gt_area, const uint8_t *gt_flags, int G, double lo, double hi)
 {
     CocoGtSets s;
@@ -88,7 +72,7 @@ HH_CHD CocoGtSets coco_gt_sets(const double *gt_area, const uint8_t *gt_flags, i
         for (int b = 0; b < 64 && w * 64 + b < G; ++b) {
             const int g = w * 64 + b;
             if (coco_gt_ignored(gt_area[g], gt_flags[g], lo, hi)) s.ign[w] |= 1ull << b;
-            if (gt_flags[g] & COCO_GT_CROWD) s.crowd[w] |= 1ull << b;
+            if (gt_flags[g] & HH_COCO_GT_CROWD) s.crowd[w] |= 1ull << b;
         }
     return s;
 }
@@ -155,7 +139,7 @@ HH_CHD void coco_match_walk(const double *oks, int D, int G, const CocoGtSets &s
 inline const char *coco_check(const CocoTables *t, char *msg, size_t msg_len);
 
 // One image on the host, what a workgroup does.  oks_in: read the image's matrix from it (match only); otherwise compute it into `scratch`
-// (COCO_MAX_DET * COCO_MAX_GT doubles) and, if oks_out, store it there.  `match`: run the walks and write the three outputs.
+// (HH_COCO_MAX_DET * HH_COCO_MAX_GT doubles) and, if oks_out, store it there.  `match`: run the walks and write the three outputs.
 inline void coco_image_host(const CocoTables &t, int i, const double *oks_in, double *oks_out, double *scratch, bool match, int32_t *dt_match,
                             uint8_t *dt_ignore, uint8_t *gt_ignore)
 {
@@ -189,9 +173,9 @@ inline const char *coco_check(const CocoTables *t, char *msg, size_t msg_len)
         !t->vars || !t->area_rng || !t->thr)
         return "null pointer";
     if (t->I < 0 || t->I > (1 << 24) || t->N < 0 || t->M < 0) return "image, detection or ground-truth count out of range";
-    if (t->K < 1 || t->K > COCO_MAX_K) return "K outside 1..64";
-    if (t->T < 1 || t->T > COCO_MAX_T) return "T outside 1..HH_COCO_MAX_T (16)";
-    if (t->A < 1 || t->A > COCO_MAX_A) return "A outside 1..HH_COCO_MAX_A (4)";
+    if (t->K < 1 || t->K > HH_COCO_MAX_K) return "K outside 1..64";
+    if (t->T < 1 || t->T > HH_COCO_MAX_T) return "T outside 1..HH_COCO_MAX_T (16)";
+    if (t->A < 1 || t->A > HH_COCO_MAX_A) return "A outside 1..HH_COCO_MAX_A (4)";
     if ((long long)t->N * t->A * t->T > (1ll << 31) - 1 || (long long)t->M * t->A > (1ll << 31) - 1) return "output beyond 2^31 elements";
     if (t->dt_off[0] != 0 || t->gt_off[0] != 0 || t->oks_off[0] != 0) return "offsets do not start at 0";
     for (int i = 0; i < t->I; ++i) {
@@ -200,11 +184,11 @@ inline const char *coco_check(const CocoTables *t, char *msg, size_t msg_len)
             snprintf(msg, msg_len, "non-monotone or out-of-range offsets at image %d", i);
             return msg;
         }
-        if (D > COCO_MAX_DET) {
+        if (D > HH_COCO_MAX_DET) {
             snprintf(msg, msg_len, "image %d has %lld detections, over HH_COCO_MAX_DET (32)", i, D);
             return msg;
         }
-        if (G > COCO_MAX_GT) {
+        if (G > HH_COCO_MAX_GT) {
             snprintf(msg, msg_len, "image %d has %lld ground truths, over HH_COCO_MAX_GT (128)", i, G);
             return msg;
         }

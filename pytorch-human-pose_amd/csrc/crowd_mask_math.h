@@ -12,6 +12,8 @@
 #include <algorithm>
 #include <vector>
 
+#include "../../include/hhrnet.h"
+
 #if defined(__HIPCC__)
 #define HH_CHD __host__ __device__ __forceinline__
 #else
@@ -28,19 +30,9 @@
 enum { CROWD_TW = 256, CROWD_TH = 32, CROWD_THREADS = 256, CROWD_MAX_SIDE = 16384 };
 static_assert(CROWD_TW == CROWD_THREADS && CROWD_TH == 32 && CROWD_TW % 4 == 0, "one lane per tile column, one bit per tile row");
 
-// hh_crowd_mask_desc / hh_crowd_seg_desc of include/hhrnet.h (24 bytes each).
-struct CrowdMaskDesc {
-    long long mask_offset;         // bytes from batch_base: uint8 [h,w] out, any alignment
-    int32_t h, w;
-    int32_t seg_first, seg_count;  // this mask's segments in the segment table
-};
-struct CrowdSegDesc {
-    long long toggle_offset;       // bytes from batch_base: `count` uint32 toggles, a multiple of 4
-    int32_t count;
-    int32_t col_first, col_last;   // inclusive: the columns the segment can cover (a lane outside skips the segment)
-    int32_t reserved;
-};
-static_assert(sizeof(CrowdMaskDesc) == 24 && sizeof(CrowdSegDesc) == 24, "table layout");
+using CrowdMaskDesc = hh_crowd_mask_desc;
+using CrowdSegDesc = hh_crowd_seg_desc;
+static_assert(sizeof(hh_crowd_mask_desc) == 24 && sizeof(hh_crowd_seg_desc) == 24, "ABI 3");
 
 // The number of toggles <= idx (an upper-bound search): pixel idx is covered by the segment iff it is odd.
 HH_CHD uint32_t crowd_upper_bound(const uint32_t *t, uint32_t n, uint32_t idx)

@@ -84,16 +84,16 @@ hipError_t launch_optim_step_ema(int algo, const OptimTensor *tensors, int ntens
                                  const OptimChunk *only_chunks, int nonly, double decay, int warmup, long long *n_averaged, hipStream_t s)
 {
     const dim3 grid(nchunks + nonly), block(OPTIM_THREADS);
-    if (algo != OPTIM_ADAM && algo != OPTIM_ADAMW && algo != OPTIM_SGD) return hipErrorInvalidValue;
+    if (algo != HH_OPTIM_ADAM && algo != HH_OPTIM_ADAMW && algo != HH_OPTIM_SGD) return hipErrorInvalidValue;
     if (nchunks + nonly > 0) {
-        if (algo == OPTIM_ADAM)
-            hipLaunchKernelGGL(optim_step_ema_kernel<OPTIM_ADAM>, grid, block, 0, s, tensors, groups, chunks, nchunks, grad_scale, found_inf, rows, row_of,
+        if (algo == HH_OPTIM_ADAM)
+            hipLaunchKernelGGL(optim_step_ema_kernel<HH_OPTIM_ADAM>, grid, block, 0, s, tensors, groups, chunks, nchunks, grad_scale, found_inf, rows, row_of,
                                only_chunks, decay, warmup, n_averaged);
-        else if (algo == OPTIM_ADAMW)
-            hipLaunchKernelGGL(optim_step_ema_kernel<OPTIM_ADAMW>, grid, block, 0, s, tensors, groups, chunks, nchunks, grad_scale, found_inf, rows, row_of,
+        else if (algo == HH_OPTIM_ADAMW)
+            hipLaunchKernelGGL(optim_step_ema_kernel<HH_OPTIM_ADAMW>, grid, block, 0, s, tensors, groups, chunks, nchunks, grad_scale, found_inf, rows, row_of,
                                only_chunks, decay, warmup, n_averaged);
         else
-            hipLaunchKernelGGL(optim_step_ema_kernel<OPTIM_SGD>, grid, block, 0, s, tensors, groups, chunks, nchunks, grad_scale, found_inf, rows, row_of,
+            hipLaunchKernelGGL(optim_step_ema_kernel<HH_OPTIM_SGD>, grid, block, 0, s, tensors, groups, chunks, nchunks, grad_scale, found_inf, rows, row_of,
                                only_chunks, decay, warmup, n_averaged);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;

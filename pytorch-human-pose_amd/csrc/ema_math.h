@@ -13,7 +13,8 @@
 #define HH_EMA_MATH_H
 #include "optim_math.h"
 
-struct EmaRow { float *value, *ema; long long numel; };  // hh_ema_row of include/hhrnet.h, 24 bytes
+using EmaRow = hh_ema_row;
+static_assert(sizeof(hh_ema_row) == 24, "ABI 3");
 
 struct EmaCoef {
     float w;   // 1 - d

@@ -67,7 +67,7 @@ HH_HD GradPartial grad_chunk_stats(const OptimTensor &t, int chunk, bool scale, 
     const long long base = (long long)chunk * OPTIM_CHUNK;
     const long long left = t.numel - base;
     const int n = left < OPTIM_CHUNK ? (int)left : (int)OPTIM_CHUNK;
-    const OptimPtr g = (OptimPtr)(t.g + base);
+    const OptimPtr g = (OptimPtr)(t.grad + base);
     GradPartial a = grad_partial_zero();
     bool seen = false;
     int done = 0;
@@ -150,7 +150,7 @@ HH_HD void grad_chunk_scale(const OptimTensor &t, int chunk, float coef, int tid
     const long long base = (long long)chunk * OPTIM_CHUNK;
     const long long left = t.numel - base;
     const int n = left < OPTIM_CHUNK ? (int)left : (int)OPTIM_CHUNK;
-    const OptimPtr g = (OptimPtr)(t.g + base);
+    const OptimPtr g = (OptimPtr)(t.grad + base);
     int done = 0;
     if (optim_aligned16(g, nullptr, nullptr, nullptr)) {
         const int n4 = n >> 2;

@@ -16,57 +16,18 @@
 #define HH_JDHD inline
 #endif
 
-// hh_jpeg_stream_info of include/hhrnet.h (112 bytes)
-struct JpegStreamInfo {
-    long long scan_offset, scan_end;  // the entropy-coded bytes: [scan_offset, scan_end) of the stream (scan_end: the EOI, or the length)
-    int32_t h, w, ncomp;
-    int32_t sampling;          // 444, 422, 420; 400: grayscale
-    int32_t restart_interval;  // MCUs, 0: none
-    int32_t hs, vs;            // luminance blocks per MCU, across and down
-    int32_t mcols, mrows;      // the MCU grid
-    int32_t bpm;               // blocks per MCU: hs * vs + 2, or 1
-    int32_t qt[3], dc[3], ac[3];  // per component: quantiser, DC and AC table ids 0..3
-    int32_t nseg_restart;      // restart intervals in the scan (0 without DRI)
-    int32_t adobe_transform;   // -1: no Adobe marker
-    int32_t reserved[3];
-};
-static_assert(sizeof(JpegStreamInfo) == 112, "table layout");
+#include "../../include/hhrnet.h"
 
-// hh_jpeg_segment of include/hhrnet.h (32 bytes): the run of MCUs one lane decodes
-struct JpegSegment {
-    int32_t first_mcu, mcu_count;
-    int32_t byte_offset, bit_offset;  // the first unread bit: `bit_offset` (0..7) bits of the data byte at stream + byte_offset are spent
-    int32_t pred[3];                  // the DC predictors at that point
-    int32_t byte_end;                 // bits [31:1]: the segment's bytes end here (a marker, or scan_end); bit 0: an RSTm follows, so the
-                                      // segment must end within its last byte
-};
-static_assert(sizeof(JpegSegment) == 32, "table layout");
-
-// hh_jpeg_dec_desc of include/hhrnet.h (64 bytes)
-struct JpegDecDesc {
-    long long stream_offset;  // bytes from batch_base: the stream
-    long long tables_offset;  // bytes from batch_base: JpegStreamInfo | JpegDecTables | nseg JpegSegment; the address is a multiple of 16
-    long long tables_bytes;   // the room there: >= jpeg_dec_tables_bytes(nseg)
-    long long dst_offset;     // bytes from batch_base: uint8 [h,w,3], `pitch` bytes between rows
-    long long ws_offset;      // bytes from the workspace: jpeg_dec_geom().ws_bytes of room, a multiple of 16
-    long long pitch;
-    int32_t stream_length, nseg;
-    int32_t flags, reserved;  // bit 0: store B,G,R
-};
-static_assert(sizeof(JpegDecDesc) == 64, "table layout");
-struct JpegWindow {  // hh_jpeg_window (16 bytes)
-    int32_t top, left, height, width;
-};
-static_assert(sizeof(JpegWindow) == 16, "table layout");
-struct JpegWinDesc {  // hh_jpeg_win_desc (80 bytes): JpegDecDesc, whose stream is the shipped slice, and the window
-    JpegDecDesc d;
-    JpegWindow win;
-};
-static_assert(sizeof(JpegWinDesc) == 80, "table layout");
-struct JpegWinCounts {  // hh_jpeg_window_counts (48 bytes)
-    long long segments_walked, mcus_walked, mcus_stored, blocks_transformed, pixels_written, stream_bytes;
-};
-static_assert(sizeof(JpegWinCounts) == 48, "table layout");
+// The tables of the decode are the public structs.  hh_jpeg_dec_desc.tables_offset leads to JpegStreamInfo | JpegDecTables | nseg
+// JpegSegment at a multiple of 16; a hh_jpeg_win_desc is a hh_jpeg_dec_desc, whose stream is the shipped slice, and the window.
+using JpegStreamInfo = hh_jpeg_stream_info;
+using JpegSegment = hh_jpeg_segment;
+using JpegDecDesc = hh_jpeg_dec_desc;
+using JpegWindow = hh_jpeg_window;
+using JpegWinDesc = hh_jpeg_win_desc;
+using JpegWinCounts = hh_jpeg_window_counts;
+static_assert(sizeof(hh_jpeg_stream_info) == 112 && sizeof(hh_jpeg_segment) == 32 && sizeof(hh_jpeg_dec_desc) == 64 && sizeof(hh_jpeg_window) == 16 &&
+              sizeof(hh_jpeg_win_desc) == 80 && sizeof(hh_jpeg_window_counts) == 48, "ABI 3");
 
 // One Huffman table as the decoder reads it: the 8-bit first level (length << 8 | symbol, 0: longer than 8 bits or no code), and for the
 // lengths 9..16 libjpeg's maxcode / valptr pair (valoff = valptr - mincode; maxcode -1: no code of that length).

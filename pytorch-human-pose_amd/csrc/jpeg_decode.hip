@@ -26,7 +26,7 @@
 __device__ __forceinline__ const JpegDecDesc &jpeg_desc(const JpegDecDesc &d) { return d; }
 __device__ __forceinline__ const JpegDecDesc &jpeg_desc(const JpegWinDesc &wd) { return wd.d; }
 __device__ __forceinline__ JpegWindow jpeg_desc_window(const JpegDecDesc &, const JpegStreamInfo &I) { return jpeg_full_window(I); }
-__device__ __forceinline__ JpegWindow jpeg_desc_window(const JpegWinDesc &wd, const JpegStreamInfo &) { return wd.win; }
+__device__ __forceinline__ JpegWindow jpeg_desc_window(const JpegWinDesc &wd, const JpegStreamInfo &) { return wd.window; }
 
 template <class Desc>
 __global__ __launch_bounds__(64) void jpeg_dec_entropy_kernel(const unsigned char *__restrict__ base, unsigned char *__restrict__ ws,

@@ -14,18 +14,10 @@
 #define HH_JHD inline
 #endif
 
-// hh_jpeg_desc of include/hhrnet.h (64 bytes).
-struct JpegDesc {
-    long long src_offset;    // bytes from batch_base: uint8 [h,w,3], `pitch` bytes between rows
-    long long out_offset;    // bytes from batch_base: the stream
-    long long out_capacity;  // >= jpeg_bound
-    long long ws_offset;     // bytes from the workspace: this frame's jpeg_geom().ws_bytes, a multiple of 16
-    long long pitch;
-    int32_t h, w;
-    int32_t quality, subsampling;  // 1..100; 420 or 444
-    int32_t flags, reserved;       // bit 0: the source is B,G,R
-};
-static_assert(sizeof(JpegDesc) == 64, "table layout");
+#include "../../include/hhrnet.h"
+
+using JpegDesc = hh_jpeg_desc;
+static_assert(sizeof(hh_jpeg_desc) == 64, "ABI 3");
 
 // The worst case of one block: a DC code of at most 11 bits (chrominance, category 11) with 11 value bits, and 63 coefficients that
 // are all non-zero, each an AC code of at most 16 bits with at most 10 value bits (|AC| <= 1023).  A zero coefficient never costs more:

@@ -5,6 +5,10 @@
 
 #include <hip/hip_ext.h>
 
+// The descriptor tables that cross the C boundary are the structs of the public header, the only definition of their layout: kernels
+// and launchers take the hh_* types themselves.  Each size is asserted once, beside the code that owns the struct (ABI version 3).
+#include "../../include/hhrnet.h"
+
 typedef uint16_t bf16_raw;  // storage type of a bf16 element in HBM (and of an fp16 one: the training path's fp16 form, HH_DTYPE_F16 handles)
 // act_dtype of the training launchers: the element type of activations and packed weights, 0 = bf16, 1 = fp16 (HH_ACT_BF16 / HH_ACT_F16
 // of hhrnet.h); anything else is hipErrorInvalidValue.  The fused inference kernels take the same parameter: an HH_DTYPE_F16 handle
@@ -326,57 +330,40 @@ hipError_t launch_linear(const float *x, const float *w, const float *bias, floa
 hipError_t launch_avgpool_backward(const float *g, bf16_raw *dx, int B, int HW, int C, hipStream_t s, int act_dtype = 0);
 hipError_t launch_linear_backward(const float *x, const float *w, const float *dy, int B, int K, int N, float *dx, float *dw, float *db,
                                   hipStream_t s);
-struct XentResult { float loss; int top1, top5; unsigned flags; };  // hh_xent_result of include/hhrnet.h
-hipError_t launch_softmax_xent(const float *logits, const long long *targets, int B, int N, float *dlogits, XentResult *result, hipStream_t s);
+static_assert(sizeof(hh_xent_result) == 16, "ABI 3");
+hipError_t launch_softmax_xent(const float *logits, const long long *targets, int B, int N, float *dlogits, hh_xent_result *result, hipStream_t s);
 
-struct HHImageDesc {  // one raw image of a batch (hh_image_desc of include/hhrnet.h): 64 bytes
-    long long offset;  // bytes from the batch's base pointer to the image's first pixel
-    int h, w;
-    double inv[6];     // destination -> source affine
-};
-hipError_t launch_preprocess_batch(const unsigned char *base, const HHImageDesc *descs, int n, float *out, int H, int W,
+static_assert(sizeof(hh_image_desc) == 64, "ABI 3");  // one raw image of a batch
+hipError_t launch_preprocess_batch(const unsigned char *base, const hh_image_desc *descs, int n, float *out, int H, int W,
                                    const float mean[3], const float stdv[3], hipStream_t s);
 hipError_t launch_warp_affine_u8(const unsigned char *img, int h, int w, const double inv[6], unsigned char *out, int H, int W, hipStream_t s);
 hipError_t launch_preprocess(const unsigned char *img, int h, int w, const double inv[6], float *out, int H, int W,
                              const float mean[3], const float stdv[3], hipStream_t s);
 // The training input (hh_train_desc of include/hhrnet.h): one sample's raw image and crowd mask in the batch buffer, its flip
 // flag, and the destination -> source affines of the image and of every stage's mask.
-#define HH_TRAIN_STAGES 4
-struct HHTrainDesc {
-    long long image_offset, mask_offset;  // bytes from the batch's base pointer
-    int h, w, flip, reserved;
-    double inv_image[6];
-    double inv_mask[HH_TRAIN_STAGES][6];
-};
-struct TrainMaskStages { float *out[HH_TRAIN_STAGES]; int h[HH_TRAIN_STAGES], w[HH_TRAIN_STAGES], n; };
-hipError_t launch_train_images(const unsigned char *base, const HHTrainDesc *descs, int n, float *out, int H, int W, const float mean[3],
+static_assert(sizeof(hh_train_desc) == 272, "ABI 3");
+struct TrainMaskStages { float *out[HH_TRAIN_MAX_STAGES]; int h[HH_TRAIN_MAX_STAGES], w[HH_TRAIN_MAX_STAGES], n; };
+hipError_t launch_train_images(const unsigned char *base, const hh_train_desc *descs, int n, float *out, int H, int W, const float mean[3],
                                const float stdv[3], hipStream_t s);
-hipError_t launch_train_masks(const unsigned char *base, const HHTrainDesc *descs, int n, const TrainMaskStages &st, hipStream_t s);
+hipError_t launch_train_masks(const unsigned char *base, const hh_train_desc *descs, int n, const TrainMaskStages &st, hipStream_t s);
 // The classifier's input (hh_crop_desc of include/hhrnet.h, cls_input.hip): one sample's raw image, its source rectangle, the size of
 // the virtual resized crop and the output window inside it.  56 bytes.
-struct HHCropDesc {
-    long long image_offset;  // bytes from the batch's base pointer
-    int h, w, top, left, ch, cw, rh, rw, oy, ox, flip, antialias;
-};
-hipError_t launch_resized_crop(const unsigned char *base, const HHCropDesc *descs, int n, float *out, int H, int W, const float mean[3],
+static_assert(sizeof(hh_crop_desc) == 56, "ABI 3");
+hipError_t launch_resized_crop(const unsigned char *base, const hh_crop_desc *descs, int n, float *out, int H, int W, const float mean[3],
                                const float stdv[3], hipStream_t s);
 // The mosaic of the training input (hh_mosaic_desc of include/hhrnet.h, train_mosaic.hip): four raw tiles (image + crowd mask) and the
 // two canvases they are resized into, all as byte offsets from the batch's base pointer.  112 bytes.
-struct HHMosaicTile { long long image_offset, mask_offset; int h, w; };
-struct HHMosaicDesc { HHMosaicTile tile[4]; long long canvas_image_offset, canvas_mask_offset; };
-hipError_t launch_mosaic(unsigned char *base, const HHMosaicDesc *descs, int n, int S, hipStream_t s);
+static_assert(sizeof(hh_mosaic_tile) == 24 && sizeof(hh_mosaic_desc) == 112, "ABI 3");
+hipError_t launch_mosaic(unsigned char *base, const hh_mosaic_desc *descs, int n, int S, hipStream_t s);
 // Pose overlays (hh_render_desc / hh_render_prim of include/hhrnet.h; structs and arithmetic in render_math.h, kernels in render.hip):
 // n frames in one launch, `max_tiles` = the largest frame's tile count; the same walk on the host for one frame; the general 8-bit resize.
-struct RenderDesc;
-struct RenderPrim;
-hipError_t launch_render_poses(unsigned char *base, const RenderDesc *descs, const RenderPrim *prims, int n, int max_tiles, hipStream_t s);
-void render_debug_host(const unsigned char *src, unsigned char *dst, const RenderDesc &d, const RenderPrim *prims);
+hipError_t launch_render_poses(unsigned char *base, const hh_render_desc *descs, const hh_render_prim *prims, int n, int max_tiles, hipStream_t s);
+void render_debug_host(const unsigned char *src, unsigned char *dst, const hh_render_desc &d, const hh_render_prim *prims);
 hipError_t launch_resize_u8(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, hipStream_t s);
 hipError_t launch_resize_u8_scaled(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, double fx, double fy, hipStream_t s);
 // Baseline JPEG (hh_jpeg_desc of include/hhrnet.h; struct and arithmetic in jpeg_math.h, kernels in jpeg.hip): n frames in three
 // launches, `max_mcus` / `max_rows` = the largest frame's MCU count / MCU rows.
-struct JpegDesc;
-hipError_t launch_jpeg_encode(unsigned char *base, const JpegDesc *descs, int n, int max_mcus, int max_rows, unsigned char *ws, int32_t *lengths,
+hipError_t launch_jpeg_encode(unsigned char *base, const hh_jpeg_desc *descs, int n, int max_mcus, int max_rows, unsigned char *ws, int32_t *lengths,
                               hipStream_t s);
 // Baseline JPEG decode (hh_jpeg_dec_desc of include/hhrnet.h; structs and arithmetic in jpeg_dec_math.h, kernels in jpeg_decode.hip): n
 // streams in three launches behind the clearing of `status`.  Desc: JpegDecDesc (the whole image) or JpegWinDesc (hh_jpeg_win_desc: a
@@ -386,34 +373,29 @@ hipError_t launch_jpeg_decode(unsigned char *base, const Desc *descs, int n, int
                               int32_t *status, hipStream_t s);
 // Heatmap panels (hh_panel_map of include/hhrnet.h; struct and arithmetic in panel_math.h, kernels in panels.hip): the min/max launch
 // (only if any_minmax) and the paint launch of one figure; the same figure on the host; the un-normalise of the model input.
-struct PanelMap;
 struct PanelRange;
-hipError_t launch_panels(const PanelMap *maps, int n, bool any_minmax, const unsigned char *image, int H, int W, const unsigned char *lut,
+hipError_t launch_panels(const hh_panel_map *maps, int n, bool any_minmax, const unsigned char *image, int H, int W, const unsigned char *lut,
                          unsigned char *canvas, int Hc, int Wc, long long pitch, float *parts, hipStream_t s);
-void panels_debug_host(const PanelMap *maps, int n, const unsigned char *image, int H, int W, const unsigned char *lut, unsigned char *canvas, int Hc,
+void panels_debug_host(const hh_panel_map *maps, int n, const unsigned char *image, int H, int W, const unsigned char *lut, unsigned char *canvas, int Hc,
                        int Wc, long long pitch, PanelRange *ranges);
 hipError_t launch_unnormalize_u8(const float *x, int H, int W, unsigned char *out, const double *mean, const double *stdv, hipStream_t s);
 // COCO keypoint scoring (hh_coco_tables of include/hhrnet.h; struct, OKS and matching walk in coco_eval_math.h, kernel in coco_eval.hip):
 // mode 0 = OKS + matching fused, 1 = OKS only into oks_out, 2 = matching only from oks_in; the same on the host.
-struct CocoTables;
-hipError_t launch_coco_eval(int mode, const CocoTables &dev, const double *oks_in, double *oks_out, int32_t *dt_match, uint8_t *dt_ignore, uint8_t *gt_ignore,
+hipError_t launch_coco_eval(int mode, const hh_coco_tables &dev, const double *oks_in, double *oks_out, int32_t *dt_match, uint8_t *dt_ignore, uint8_t *gt_ignore,
                             hipStream_t s);
-void coco_eval_host(const CocoTables &t, const double *oks_in, double *oks_out, bool match, int32_t *dt_match, uint8_t *dt_ignore, uint8_t *gt_ignore);
+void coco_eval_host(const hh_coco_tables &t, const double *oks_in, double *oks_out, bool match, int32_t *dt_match, uint8_t *dt_ignore, uint8_t *gt_ignore);
 // Pose tracking across frames (hh_track_params of include/hhrnet.h; struct, state layout and per-slot / per-joint code in track_math.h, kernels in
 // track.hip): S streams of F frames in one launch; the similarity matrices alone; the greedy assignment alone on n matrices; the step on the host.
-struct TrackParams;
-hipError_t launch_track_step(const TrackParams &p, void *state, const float *joints, const float *scores, const int32_t *num_people, const int32_t *flags, int S,
+hipError_t launch_track_step(const hh_track_params &p, void *state, const float *joints, const float *scores, const int32_t *num_people, const int32_t *flags, int S,
                              int F, int32_t *track_ids, float *smooth, int32_t *out_flags, hipStream_t s);
-hipError_t launch_track_similarity(const TrackParams &p, void *state, const float *joints, const float *scores, const int32_t *num_people, const int32_t *flags,
+hipError_t launch_track_similarity(const hh_track_params &p, void *state, const float *joints, const float *scores, const int32_t *num_people, const int32_t *flags,
                                    int S, double *sim, hipStream_t s);
 hipError_t launch_track_assign(const double *sim, const int32_t *ids, int n, int T, int P, double min_oks, int32_t *match, hipStream_t s);
-void track_step_host(const TrackParams &p, void *state, const float *joints, const float *scores, const int32_t *num_people, const int32_t *flags, int S, int F,
+void track_step_host(const hh_track_params &p, void *state, const float *joints, const float *scores, const int32_t *num_people, const int32_t *flags, int S, int F,
                      int32_t *track_ids, float *smooth, int32_t *out_flags);
 // Crowd masks from toggle lists (hh_crowd_mask_desc / hh_crowd_seg_desc of include/hhrnet.h; structs, predicate, tile walk and the host's
 // polygon walk in crowd_mask_math.h, kernel in crowd_mask.hip): n masks in one launch, `max_tiles` = the largest mask's tile count.
-struct CrowdMaskDesc;
-struct CrowdSegDesc;
-hipError_t launch_crowd_masks(unsigned char *base, const CrowdMaskDesc *descs, const CrowdSegDesc *segs, int n, int max_tiles, hipStream_t s);
+hipError_t launch_crowd_masks(unsigned char *base, const hh_crowd_mask_desc *descs, const hh_crowd_seg_desc *segs, int n, int max_tiles, hipStream_t s);
 // target heatmaps from the packed joints (train_input.hip); n = table side = 2 * reach + 1 <= HH_RENDER_MAX_N, w <= HH_RENDER_MAX_W
 #define HH_RENDER_MAX_N 63
 #define HH_RENDER_MAX_W 4096
@@ -476,26 +458,23 @@ hipError_t conv_wgrad_launch(const WgradParams &p, int ks, int stride, float *dw
 
 // Device optimizer step (optim.hip): one launch over a device-resident table.  The table's structs and the arithmetic are in
 // optim_math.h (shared with a host build).
-struct OptimTensor;
-struct OptimGroup;
 struct OptimChunk;
-hipError_t launch_optim_step(int algo, const OptimTensor *tensors, int ntensors, const OptimGroup *groups, const OptimChunk *chunks, int nchunks,
+hipError_t launch_optim_step(int algo, const hh_optim_tensor *tensors, int ntensors, const hh_optim_group *groups, const OptimChunk *chunks, int nchunks,
                              const float *grad_scale, const float *found_inf, int advance_steps, hipStream_t s);
-hipError_t launch_grads_nonfinite(const OptimTensor *tensors, const OptimChunk *chunks, int nchunks, const float *inv_scale, float *found_inf,
+hipError_t launch_grads_nonfinite(const hh_optim_tensor *tensors, const OptimChunk *chunks, int nchunks, const float *inv_scale, float *found_inf,
                                   hipStream_t s);
 // Gradient statistics and clipping by global norm over the same table (grad_stats.hip; arithmetic and the workspace's layout in
 // grad_stats_math.h).  `work` is the device workspace of grad_work_bytes(ntensors, nchunks).
-hipError_t launch_grad_stats(const OptimTensor *tensors, int ntensors, const OptimChunk *chunks, int nchunks, const float *inv_scale,
+hipError_t launch_grad_stats(const hh_optim_tensor *tensors, int ntensors, const OptimChunk *chunks, int nchunks, const float *inv_scale,
                              float *found_inf, void *work, hipStream_t s);
-hipError_t launch_grad_clip(const OptimTensor *tensors, int ntensors, const OptimChunk *chunks, int nchunks, float max_norm, int norm_type,
+hipError_t launch_grad_clip(const hh_optim_tensor *tensors, int ntensors, const OptimChunk *chunks, int nchunks, float max_norm, int norm_type,
                             const float *found_inf, void *work, hipStream_t s);
 // Weight EMA (ema.hip; arithmetic in ema_math.h): the optimizer step with the average as a fifth stream plus `nonly` chunks of rows the
 // optimizer does not step, the stand-alone update, and the swap.  The update launches are followed by the one-workgroup tail that
 // advances the counters.
-struct EmaRow;
-hipError_t launch_optim_step_ema(int algo, const OptimTensor *tensors, int ntensors, const OptimGroup *groups, const OptimChunk *chunks, int nchunks,
-                                 const float *grad_scale, const float *found_inf, int advance_steps, const EmaRow *rows, const int *row_of,
+hipError_t launch_optim_step_ema(int algo, const hh_optim_tensor *tensors, int ntensors, const hh_optim_group *groups, const OptimChunk *chunks, int nchunks,
+                                 const float *grad_scale, const float *found_inf, int advance_steps, const hh_ema_row *rows, const int *row_of,
                                  const OptimChunk *only_chunks, int nonly, double decay, int warmup, long long *n_averaged, hipStream_t s);
-hipError_t launch_ema_update(const EmaRow *rows, const OptimChunk *chunks, int nchunks, double decay, int warmup, long long *n_averaged,
+hipError_t launch_ema_update(const hh_ema_row *rows, const OptimChunk *chunks, int nchunks, double decay, int warmup, long long *n_averaged,
                              const float *found_inf, hipStream_t s);
-hipError_t launch_ema_swap(const EmaRow *rows, const OptimChunk *chunks, int nchunks, hipStream_t s);
+hipError_t launch_ema_swap(const hh_ema_row *rows, const OptimChunk *chunks, int nchunks, hipStream_t s);

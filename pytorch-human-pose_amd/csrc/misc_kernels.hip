@@ -403,17 +403,17 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const unsigned char *__
     preprocess_pixel(img, h, w, inv, out, H, W, i, mean, stdv);
 }
 // a batch of raw images of any sizes into one [n,3,H,W] tensor: blockIdx.y = image, its descriptor read from device memory
-__global__ __launch_bounds__(256) void preprocess_batch_kernel(const unsigned char *__restrict__ base, const HHImageDesc *__restrict__ descs,
+__global__ __launch_bounds__(256) void preprocess_batch_kernel(const unsigned char *__restrict__ base, const hh_image_desc *__restrict__ descs,
                                                                float *__restrict__ out, int H, int W, float m0, float m1, float m2,
                                                                float s0, float s1, float s2)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= H * W) return;
-    const HHImageDesc d = descs[blockIdx.y];
+    const hh_image_desc d = descs[blockIdx.y];
     const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
-    preprocess_pixel(base + d.offset, d.h, d.w, d.inv, out + (size_t)blockIdx.y * 3 * H * W, H, W, i, mean, stdv);
+    preprocess_pixel(base + d.offset, d.h, d.w, d.dst_to_src, out + (size_t)blockIdx.y * 3 * H * W, H, W, i, mean, stdv);
 }
-hipError_t launch_preprocess_batch(const unsigned char *base, const HHImageDesc *descs, int n, float *out, int H, int W,
+hipError_t launch_preprocess_batch(const unsigned char *base, const hh_image_desc *descs, int n, float *out, int H, int W,
                                    const float mean[3], const float stdv[3], hipStream_t s)
 {
     hipLaunchKernelGGL(preprocess_batch_kernel, dim3((H * W + 255) / 256, n), dim3(256), 0, s, base, descs, out, H, W, mean[0], mean[1],
@@ -432,14 +432,14 @@ hipError_t launch_preprocess(const unsigned char *img, int h, int w, const doubl
 // ToTensor + Normalize).  One descriptor per sample (hh_train_desc of include/hhrnet.h) lies behind the pixels and masks in the
 // batch buffer.  The flip is an index reversal on the DESTINATION column after the warp: cv's adelta / X0 rounding is per
 // destination column, so a flip folded into the matrix would not give the same bits.
-__global__ __launch_bounds__(256) void train_images_kernel(const unsigned char *__restrict__ base, const HHTrainDesc *__restrict__ descs,
+__global__ __launch_bounds__(256) void train_images_kernel(const unsigned char *__restrict__ base, const hh_train_desc *__restrict__ descs,
                                                            float *__restrict__ out, int H, int W, float m0, float m1, float m2,
                                                            float s0, float s1, float s2)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= H * W) return;
-    const HHTrainDesc *d = descs + blockIdx.y;
-    const double inv[6] = {d->inv_image[0], d->inv_image[1], d->inv_image[2], d->inv_image[3], d->inv_image[4], d->inv_image[5]};
+    const hh_train_desc *d = descs + blockIdx.y;
+    const double inv[6] = {d->image_dst_to_src[0], d->image_dst_to_src[1], d->image_dst_to_src[2], d->image_dst_to_src[3], d->image_dst_to_src[4], d->image_dst_to_src[5]};
     const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
     const int x = i % W, y = i / W;
     int v[3];
@@ -448,7 +448,7 @@ __global__ __launch_bounds__(256) void train_images_kernel(const unsigned char *
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[(size_t)c * H * W] = ((float)v[c] / 255.0f - mean[c]) / stdv[c];
 }
-hipError_t launch_train_images(const unsigned char *base, const HHTrainDesc *descs, int n, float *out, int H, int W, const float mean[3],
+hipError_t launch_train_images(const unsigned char *base, const hh_train_desc *descs, int n, float *out, int H, int W, const float mean[3],
                                const float stdv[3], hipStream_t s)
 {
     hipLaunchKernelGGL(train_images_kernel, dim3((H * W + 255) / 256, n), dim3(256), 0, s, base, descs, out, H, W, mean[0], mean[1],
@@ -457,22 +457,22 @@ hipError_t launch_train_images(const unsigned char *base, const HHTrainDesc *des
 }
 // the crowd masks of every stage (transforms.py:155-163): warpAffine((mask * 255).astype(uint8)) / 255 > 0.5, i.e. the warped
 // byte >= 128, as 1.0f / 0.0f; blockIdx.x walks the stages' pixels one stage after the other
-__global__ __launch_bounds__(256) void train_masks_kernel(const unsigned char *__restrict__ base, const HHTrainDesc *__restrict__ descs,
+__global__ __launch_bounds__(256) void train_masks_kernel(const unsigned char *__restrict__ base, const hh_train_desc *__restrict__ descs,
                                                           const TrainMaskStages st)
 {
     int i = blockIdx.x * 256 + threadIdx.x, k = 0;
     while (k < st.n && i >= st.h[k] * st.w[k]) i -= st.h[k] * st.w[k], ++k;
     if (k >= st.n) return;
     const int H = st.h[k], W = st.w[k];
-    const HHTrainDesc *d = descs + blockIdx.y;
-    const double *m = d->inv_mask[k];
+    const hh_train_desc *d = descs + blockIdx.y;
+    const double *m = d->mask_dst_to_src[k];
     const double inv[6] = {m[0], m[1], m[2], m[3], m[4], m[5]};
     const int x = i % W, y = i / W;
     int v[1];
     warp_pixel_u8<1>(base + d->mask_offset, d->h, d->w, inv, x, y, v);
     st.out[k][(size_t)blockIdx.y * H * W + (size_t)y * W + (d->flip ? W - 1 - x : x)] = v[0] >= 128 ? 1.0f : 0.0f;
 }
-hipError_t launch_train_masks(const unsigned char *base, const HHTrainDesc *descs, int n, const TrainMaskStages &st, hipStream_t s)
+hipError_t launch_train_masks(const unsigned char *base, const hh_train_desc *descs, int n, const TrainMaskStages &st, hipStream_t s)
 {
     int total = 0;
     for (int k = 0; k < st.n; ++k) total += st.h[k] * st.w[k];

@@ -76,9 +76,9 @@ hipError_t launch_optim_step(int algo, const OptimTensor *tensors, int ntensors,
 {
     if (nchunks <= 0) return hipSuccess;
     const dim3 grid(nchunks), block(OPTIM_THREADS);
-    if (algo == OPTIM_ADAM) hipLaunchKernelGGL(optim_step_kernel<OPTIM_ADAM>, grid, block, 0, s, tensors, groups, chunks, grad_scale, found_inf);
-    else if (algo == OPTIM_ADAMW) hipLaunchKernelGGL(optim_step_kernel<OPTIM_ADAMW>, grid, block, 0, s, tensors, groups, chunks, grad_scale, found_inf);
-    else if (algo == OPTIM_SGD) hipLaunchKernelGGL(optim_step_kernel<OPTIM_SGD>, grid, block, 0, s, tensors, groups, chunks, grad_scale, found_inf);
+    if (algo == HH_OPTIM_ADAM) hipLaunchKernelGGL(optim_step_kernel<HH_OPTIM_ADAM>, grid, block, 0, s, tensors, groups, chunks, grad_scale, found_inf);
+    else if (algo == HH_OPTIM_ADAMW) hipLaunchKernelGGL(optim_step_kernel<HH_OPTIM_ADAMW>, grid, block, 0, s, tensors, groups, chunks, grad_scale, found_inf);
+    else if (algo == HH_OPTIM_SGD) hipLaunchKernelGGL(optim_step_kernel<HH_OPTIM_SGD>, grid, block, 0, s, tensors, groups, chunks, grad_scale, found_inf);
     else return hipErrorInvalidValue;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !advance_steps) return e;

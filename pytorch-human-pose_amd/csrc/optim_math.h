@@ -5,17 +5,18 @@
 #define HH_OPTIM_MATH_H
 #include <math.h>
 
+#include "../../include/hhrnet.h"
+
 #if defined(__HIPCC__)
 #define HH_HD __host__ __device__ __forceinline__
 #else
 #define HH_HD inline
 #endif
 
-enum { OPTIM_ADAM = 0, OPTIM_ADAMW = 1, OPTIM_SGD = 2 };  // HH_OPTIM_* of include/hhrnet.h
-
 // The device table: hh_optim_tensor / hh_optim_group of include/hhrnet.h, and the chunk list hh_optim_step builds.
-struct OptimTensor { float *p, *g, *s0, *s1, *step; long long numel; int group, reserved; };           // 56 bytes
-struct OptimGroup { double lr, beta1, beta2, eps, weight_decay, momentum; int nesterov, reserved; };  // 56 bytes
+using OptimTensor = hh_optim_tensor;
+using OptimGroup = hh_optim_group;
+static_assert(sizeof(hh_optim_tensor) == 56 && sizeof(hh_optim_group) == 56, "ABI 3");
 struct OptimChunk { int tensor, chunk; };  // elements [chunk * OPTIM_CHUNK, + OPTIM_CHUNK) of tensors[tensor]
 enum { OPTIM_CHUNK = 4096, OPTIM_THREADS = 256, OPTIM_ROUNDS = OPTIM_CHUNK / (OPTIM_THREADS * 4) };
 static_assert(OPTIM_ROUNDS * OPTIM_THREADS * 4 == OPTIM_CHUNK, "a chunk is a whole number of 4-element rounds of the workgroup");
@@ -58,7 +59,7 @@ HH_HD OptimCoefs optim_coefs(int algo, double lr, double beta1, double beta2, do
     c.momentum = (float)momentum;
     c.has_momentum = momentum != 0.0;
     c.nesterov = nesterov;
-    if (algo == OPTIM_SGD) {
+    if (algo == HH_OPTIM_SGD) {
         c.bc2_sqrt = 1.0f;
         c.step_size = (float)lr;
     } else {
@@ -72,7 +73,7 @@ HH_HD OptimCoefs optim_coefs(int algo, double lr, double beta1, double beta2, do
 // One element.  g is the unscaled gradient; s0 / s1 are exp_avg / exp_avg_sq (Adam, AdamW) or momentum_buffer / unused (SGD).
 template <int ALGO> HH_HD void optim_update(float &p, float g, float &s0, float &s1, const OptimCoefs &c)
 {
-    if (ALGO == OPTIM_SGD) {
+    if (ALGO == HH_OPTIM_SGD) {
         if (c.has_wd) g = g + c.wd * p;
         if (c.has_momentum) {
             const float buf = c.momentum * s0 + g;
@@ -82,7 +83,7 @@ template <int ALGO> HH_HD void optim_update(float &p, float g, float &s0, float 
         p = p - c.step_size * g;
     } else {
         if (c.has_wd) {
-            if (ALGO == OPTIM_ADAMW) p = p * c.decay;
+            if (ALGO == HH_OPTIM_ADAMW) p = p * c.decay;
             else g = g + c.wd * p;
         }
         const float m = s0 + c.om_b1 * (g - s0);
@@ -120,9 +121,9 @@ HH_HD void optim_chunk_update(const OptimTensor &t, int chunk, const OptimCoefs 
     const long long left = t.numel - base;
     const int n = left < OPTIM_CHUNK ? (int)left : (int)OPTIM_CHUNK;
     // SGD: s1 is unused, and s0 only with momentum (hh_optim_step checks that it is there then)
-    const bool use_s0 = ALGO != OPTIM_SGD || c.has_momentum, use_s1 = ALGO != OPTIM_SGD;
-    const OptimPtr p = (OptimPtr)(t.p + base), g = (OptimPtr)(t.g + base), s0 = use_s0 ? (OptimPtr)(t.s0 + base) : nullptr,
-                   s1 = use_s1 ? (OptimPtr)(t.s1 + base) : nullptr;
+    const bool use_s0 = ALGO != HH_OPTIM_SGD || c.has_momentum, use_s1 = ALGO != HH_OPTIM_SGD;
+    const OptimPtr p = (OptimPtr)(t.param + base), g = (OptimPtr)(t.grad + base), s0 = use_s0 ? (OptimPtr)(t.state0 + base) : nullptr,
+                   s1 = use_s1 ? (OptimPtr)(t.state1 + base) : nullptr;
     const bool use_e = Fifth::ON && fifth.ptr != nullptr;
     const OptimPtr e = use_e ? (OptimPtr)(fifth.ptr + base) : nullptr;
     int done = 0;  // elements the 16-byte path covers
@@ -175,7 +176,7 @@ HH_HD bool optim_chunk_nonfinite(const OptimTensor &t, int chunk, bool scale, fl
     const long long base = (long long)chunk * OPTIM_CHUNK;
     const long long left = t.numel - base;
     const int n = left < OPTIM_CHUNK ? (int)left : (int)OPTIM_CHUNK;
-    const OptimPtr g = (OptimPtr)(t.g + base);
+    const OptimPtr g = (OptimPtr)(t.grad + base);
     bool bad = false;
     int done = 0;
     if (optim_aligned16(g, nullptr, nullptr, nullptr)) {

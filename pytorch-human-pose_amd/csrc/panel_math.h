@@ -13,6 +13,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/hhrnet.h"
+
 #if defined(__HIPCC__)
 #include "decode_dev.h"  // Lin, src_index, bilerp (device)
 #define HH_PHD __host__ __device__ __forceinline__
@@ -26,23 +28,14 @@ struct Lin { int i0, i1; float w0, w1; };
 #pragma clang fp contract(off)
 #endif
 
-enum { PANEL_DIRECT = 0, PANEL_SINGLE = 1, PANEL_NESTED = 2, PANEL_AVERAGE = 3 };  // HH_PANEL_* of include/hhrnet.h
-enum { PANEL_CLIP = 1, PANEL_MINMAX = 2 };
 // The launch geometry.  Paint: a workgroup of PANEL_TH x PANEL_TW / PANEL_PX threads owns one PANEL_TH x PANEL_TW tile of the canvas, a
 // thread PANEL_PX horizontally adjacent pixels of it; the figure's cells are culled against the tile, one per lane, so a figure has at
-// most PANEL_MAX_MAPS = the workgroup's size maps.  Min/max: PANEL_PARTS workgroups per map, each leaving one (max, min) pair.
-enum { PANEL_TH = 16, PANEL_TW = 64, PANEL_PX = 4, PANEL_THREADS = PANEL_TH * PANEL_TW / PANEL_PX, PANEL_MAX_MAPS = PANEL_THREADS, PANEL_PARTS = 32 };
-static_assert(PANEL_THREADS == 256 && PANEL_TW % PANEL_PX == 0, "one lane per map of a figure, whole pixel groups per tile row");
+// most HH_PANEL_MAX_MAPS = the workgroup's size maps.  Min/max: HH_PANEL_PARTS workgroups per map, each leaving one (max, min) pair.
+enum { PANEL_TH = 16, PANEL_TW = 64, PANEL_PX = 4, PANEL_THREADS = PANEL_TH * PANEL_TW / PANEL_PX };
+static_assert(PANEL_THREADS == HH_PANEL_MAX_MAPS && PANEL_TW % PANEL_PX == 0, "one lane per map of a figure, whole pixel groups per tile row");
 
-// hh_panel_map of include/hhrnet.h (40 bytes).
-struct PanelMap {
-    const float *src;    // DIRECT [H,W]; SINGLE [h,w]; NESTED, AVERAGE: the quarter-resolution map [h,w]
-    const float *src2;   // AVERAGE: the half-resolution map [2h,2w]; otherwise unused
-    int32_t h, w;        // size of src
-    int32_t kind, flags; // PANEL_*; PANEL_CLIP | PANEL_MINMAX
-    int32_t oy, ox;      // the cell's origin in the canvas
-};
-static_assert(sizeof(PanelMap) == 40, "table layout");
+using PanelMap = hh_panel_map;
+static_assert(sizeof(hh_panel_map) == 40, "ABI 3");
 
 // F.interpolate(mode="bilinear", align_corners=False) of torch CPU: the host forms of decode_dev.h's src_index / bilerp.
 HH_PH Lin src_index(int in_size, float scale, int dst)
@@ -78,15 +71,15 @@ HH_PHD float panel_fma(float a, float b, float c)
 HH_PHD float panel_half_tap(const PanelMap &m, int r, int c)
 {
     const float up = bilerp(m.src, m.w, src_index(m.h, 0.5f, r), src_index(m.w, 0.5f, c));
-    if (m.kind == PANEL_NESTED) return up;
+    if (m.kind == HH_PANEL_NESTED) return up;
     return (up + m.src2[(size_t)r * (2 * m.w) + c]) / 2.0f;
 }
 
 // The value of map m at pixel (y, x) of its H x W cell, 0 <= y < H, 0 <= x < W.
 HH_PHD float panel_value(const PanelMap &m, int H, int W, int y, int x)
 {
-    if (m.kind == PANEL_DIRECT) return m.src[(size_t)y * W + x];
-    if (m.kind == PANEL_SINGLE) {
+    if (m.kind == HH_PANEL_DIRECT) return m.src[(size_t)y * W + x];
+    if (m.kind == HH_PANEL_SINGLE) {
         const float sy = (float)m.h / (float)H, sx = (float)m.w / (float)W;  // torch's area_pixel_compute_scale, as hh_decode forms it
         return bilerp(m.src, m.w, src_index(m.h, sy, y), src_index(m.w, sx, x));
     }
@@ -102,7 +95,7 @@ HH_PHD float panel_value(const PanelMap &m, int H, int W, int y, int x)
 // Step 1: np.clip(v, 0, 1); NaN stays NaN.
 HH_PHD float panel_clip(float v, int flags)
 {
-    if (flags & PANEL_CLIP) v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
+    if (flags & HH_PANEL_CLIP) v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
     return v;
 }
 
@@ -144,7 +137,7 @@ HH_PHD uint8_t panel_blend(uint8_t img, uint8_t colour)
 // Steps 2-4: the value after step 1 -> index into the colour table.
 HH_PHD int panel_colour_index(float v, int flags, PanelRange r)
 {
-    if (flags & PANEL_MINMAX) v = (v - r.mx) / (r.mx - r.mn);
+    if (flags & HH_PANEL_MINMAX) v = (v - r.mx) / (r.mx - r.mn);
     return 255 - panel_level(v * 255.0f);
 }
 
@@ -159,18 +152,18 @@ HH_PHD uint8_t panel_unnormalize(float x, double sd, double mean)
 // What hh_heatmap_panels_u8 refuses, on the caller's host copy of the table; nullptr = accepted.
 inline const char *panel_check(const PanelMap *maps, int n, int H, int W, int Hc, int Wc, long long pitch)
 {
-    if (n < 1 || n > PANEL_MAX_MAPS) return "need 1..HH_PANEL_MAX_MAPS (256) maps";
+    if (n < 1 || n > HH_PANEL_MAX_MAPS) return "need 1..HH_PANEL_MAX_MAPS (256) maps";
     if (H < 1 || W < 1 || Hc < 1 || Wc < 1 || H > 16384 || W > 16384 || Hc > 16384 || Wc > 16384) return "cell or canvas side outside 1..16384";
     if (pitch < (long long)Wc * 3) return "pitch smaller than a canvas row";
     if (pitch > (1ll << 30)) return "pitch beyond 2^30 bytes";
     for (int i = 0; i < n; ++i) {
         const PanelMap &m = maps[i];
-        if (m.kind < PANEL_DIRECT || m.kind > PANEL_AVERAGE) return "unknown map kind";
-        if (m.flags & ~(PANEL_CLIP | PANEL_MINMAX)) return "unknown flag";
-        if (!m.src || (m.kind == PANEL_AVERAGE && !m.src2)) return "null map pointer";
+        if (m.kind < HH_PANEL_DIRECT || m.kind > HH_PANEL_AVERAGE) return "unknown map kind";
+        if (m.flags & ~(HH_PANEL_CLIP | HH_PANEL_MINMAX)) return "unknown flag";
+        if (!m.src || (m.kind == HH_PANEL_AVERAGE && !m.src2)) return "null map pointer";
         if (m.h < 1 || m.w < 1 || m.h > 16384 || m.w > 16384) return "source side outside 1..16384";
-        if (m.kind == PANEL_DIRECT && (m.h != H || m.w != W)) return "a DIRECT map must have the cell's size";
-        if ((m.kind == PANEL_NESTED || m.kind == PANEL_AVERAGE) && (4 * m.h != H || 4 * m.w != W)) return "a NESTED or AVERAGE map must be a quarter of the cell's size";
+        if (m.kind == HH_PANEL_DIRECT && (m.h != H || m.w != W)) return "a DIRECT map must have the cell's size";
+        if ((m.kind == HH_PANEL_NESTED || m.kind == HH_PANEL_AVERAGE) && (4 * m.h != H || 4 * m.w != W)) return "a NESTED or AVERAGE map must be a quarter of the cell's size";
         if (m.oy < 0 || m.ox < 0 || (long long)m.oy + H > Hc || (long long)m.ox + W > Wc) return "cell outside the canvas";
     }
     return nullptr;
@@ -183,7 +176,7 @@ inline void panel_figure_host(const PanelMap *maps, int n, const uint8_t *image,
 {
     for (int i = 0; i < n; ++i) {
         ranges[i] = panel_range_first(0.f);
-        if (!(maps[i].flags & PANEL_MINMAX)) continue;
+        if (!(maps[i].flags & HH_PANEL_MINMAX)) continue;
         PanelRange r = panel_range_first(panel_clip(panel_value(maps[i], H, W, 0, 0), maps[i].flags));
         for (int y = 0; y < H; ++y)
             for (int x = 0; x < W; ++x) r = panel_range_join(r, panel_range_first(panel_clip(panel_value(maps[i], H, W, y, x), maps[i].flags)));

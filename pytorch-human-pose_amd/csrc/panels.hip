@@ -3,7 +3,7 @@
 // is stated at hh_heatmap_panels_u8 in include/hhrnet.h; its arithmetic is panel_math.h, shared with the host.  A full-resolution fp32
 // map is never stored: both passes resample the stage outputs where they need a value (decode_dev.h's bilinear).
 //
-// panels_minmax_kernel: grid (PANEL_PARTS, n).  The PANEL_PARTS workgroups of a map that asks for min-max walk its H x W pixels
+// panels_minmax_kernel: grid (HH_PANEL_PARTS, n).  The HH_PANEL_PARTS workgroups of a map that asks for min-max walk its H x W pixels
 // interleaved, each thread keeping a running maximum, minimum and a saw-a-NaN bit; a wave reduces through shuffles, the four waves through
 // LDS, and thread 0 stores the part's (max, min) pair, both NaN if any lane saw one.  Every pair that the paint pass reads is written
 // by this launch, unconditionally: there is no atomic, no counter and nothing that has to be cleared between calls.  A part without
@@ -11,7 +11,7 @@
 //
 // panels_paint_kernel: a workgroup of 256 threads owns one PANEL_TH x PANEL_TW = 16 x 64 tile of the canvas, a thread PANEL_PX = 4
 // horizontally adjacent pixels of it.  Each lane tests one map's cell against the tile; the survivors are compacted into LDS in table
-// order (ballot within a wave, the waves' counts prefixed through LDS); each wave then joins the PANEL_PARTS pairs of the listed maps that
+// order (ballot within a wave, the waves' counts prefixed through LDS); each wave then joins the HH_PANEL_PARTS pairs of the listed maps that
 // use min-max.  A pixel takes the last listed cell that holds it (a later map overwrites an earlier one) or is zero: padding and unused
 // cells are written by the same launch.  Every canvas byte of the Wc * 3 row bytes is written exactly once by exactly one thread.  Cell
 // origins and the pitch are arbitrary, so a thread's 12 bytes are stored as three dwords only when they are 4-byte aligned and all four
@@ -26,11 +26,11 @@ __global__ __launch_bounds__(PANEL_THREADS) void panels_minmax_kernel(const Pane
     __shared__ float smx[PANEL_WAVES], smn[PANEL_WAVES];
     __shared__ int sbad[PANEL_WAVES];
     const PanelMap m = maps[blockIdx.y];
-    if (!(m.flags & PANEL_MINMAX)) return;  // (the whole workgroup)
+    if (!(m.flags & HH_PANEL_MINMAX)) return;  // (the whole workgroup)
     const int total = H * W;                // <= 2^28 (checked by the caller)
     float mx = -INFINITY, mn = INFINITY;
     bool bad = false;
-    for (int idx = (int)blockIdx.x * PANEL_THREADS + (int)threadIdx.x; idx < total; idx += PANEL_PARTS * PANEL_THREADS) {
+    for (int idx = (int)blockIdx.x * PANEL_THREADS + (int)threadIdx.x; idx < total; idx += HH_PANEL_PARTS * PANEL_THREADS) {
         const float v = panel_clip(panel_value(m, H, W, idx / W, idx % W), m.flags);
         bad |= v != v;
         mx = v > mx ? v : mx;
@@ -54,7 +54,7 @@ __global__ __launch_bounds__(PANEL_THREADS) void panels_minmax_kernel(const Pane
             mn = smn[v] < mn ? smn[v] : mn;
             b |= sbad[v];
         }
-        float *o = parts + ((size_t)blockIdx.y * PANEL_PARTS + blockIdx.x) * 2;  // < n * PANEL_PARTS * 2 floats
+        float *o = parts + ((size_t)blockIdx.y * HH_PANEL_PARTS + blockIdx.x) * 2;  // < n * HH_PANEL_PARTS * 2 floats
         o[0] = b ? NAN : mx;
         o[1] = b ? NAN : mn;
     }
@@ -64,9 +64,9 @@ __global__ __launch_bounds__(PANEL_THREADS) void panels_paint_kernel(const Panel
                                                                      int W, const unsigned char *__restrict__ lut, unsigned char *__restrict__ canvas, int Hc,
                                                                      int Wc, long long pitch, const float *__restrict__ parts, int xtiles)
 {
-    __shared__ PanelMap list[PANEL_MAX_MAPS];
-    __shared__ int list_index[PANEL_MAX_MAPS];
-    __shared__ PanelRange range[PANEL_MAX_MAPS];
+    __shared__ PanelMap list[HH_PANEL_MAX_MAPS];
+    __shared__ int list_index[HH_PANEL_MAX_MAPS];
+    __shared__ PanelRange range[HH_PANEL_MAX_MAPS];
     __shared__ unsigned char slut[768];
     __shared__ int wave_count[PANEL_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(PANEL_THREADS) void panels_paint_kernel(const Panel
 
     PanelMap mine;
     bool keep = false;
-    if (tid < n) {  // n <= PANEL_MAX_MAPS = the workgroup's size
+    if (tid < n) {  // n <= HH_PANEL_MAX_MAPS = the workgroup's size
         mine = maps[tid];
         keep = mine.ox <= tx1 && mine.ox + W - 1 >= tx0 && mine.oy <= ty1 && mine.oy + H - 1 >= ty0;
     }
@@ -91,7 +91,7 @@ __global__ __launch_bounds__(PANEL_THREADS) void panels_paint_kernel(const Panel
         total += c;
     }
     if (keep) {
-        const int at = before + __popcll(bal & ((1ull << lane) - 1ull));  // < total <= PANEL_MAX_MAPS
+        const int at = before + __popcll(bal & ((1ull << lane) - 1ull));  // < total <= HH_PANEL_MAX_MAPS
         list[at] = mine;
         list_index[at] = tid;
     }
@@ -99,10 +99,10 @@ __global__ __launch_bounds__(PANEL_THREADS) void panels_paint_kernel(const Panel
     // the listed maps' ranges: wave v joins the parts of entries v, v + PANEL_WAVES, ... (uniform per wave)
     for (int k = wave; k < total; k += PANEL_WAVES) {
         PanelRange r = panel_range_first(0.f);
-        if (list[k].flags & PANEL_MINMAX) {
-            const float *p = parts + (size_t)list_index[k] * PANEL_PARTS * 2;
-            r.mx = lane < PANEL_PARTS ? p[lane * 2] : -INFINITY;
-            r.mn = lane < PANEL_PARTS ? p[lane * 2 + 1] : INFINITY;
+        if (list[k].flags & HH_PANEL_MINMAX) {
+            const float *p = parts + (size_t)list_index[k] * HH_PANEL_PARTS * 2;
+            r.mx = lane < HH_PANEL_PARTS ? p[lane * 2] : -INFINITY;
+            r.mn = lane < HH_PANEL_PARTS ? p[lane * 2 + 1] : INFINITY;
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) {
                 PanelRange o;
@@ -150,7 +150,7 @@ hipError_t launch_panels(const PanelMap *maps, int n, bool any_minmax, const uns
                          unsigned char *canvas, int Hc, int Wc, long long pitch, float *parts, hipStream_t s)
 {
     if (any_minmax) {
-        hipLaunchKernelGGL(panels_minmax_kernel, dim3(PANEL_PARTS, n), dim3(PANEL_THREADS), 0, s, maps, H, W, parts);
+        hipLaunchKernelGGL(panels_minmax_kernel, dim3(HH_PANEL_PARTS, n), dim3(PANEL_THREADS), 0, s, maps, H, W, parts);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -86,7 +86,7 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_poses_kernel(unsigned c
             for (int k = 0; k < total; ++k) {
                 const RenderPrim p = list[k];
                 if (y < p.y0 || y > p.y1 || x + RENDER_PX - 1 < p.x0 || x > p.x1) continue;
-                const uint32_t colour = p.r | p.g << 8 | p.b << 16;
+                const uint32_t colour = p.rgb[0] | p.rgb[1] << 8 | p.rgb[2] << 16;
 #pragma unroll
                 for (int e = 0; e < RENDER_PX; ++e)
                     if (render_inside(p, x + e, y)) conn[e] = colour;

@@ -16,30 +16,17 @@
 #pragma clang fp contract(off)
 #endif
 
-enum { RENDER_DISC = 0, RENDER_RING = 1, RENDER_ELLIPSE = 2 };  // HH_RENDER_DISC / _RING / _ELLIPSE of include/hhrnet.h
+#include "../../include/hhrnet.h"
+
 // The launch geometry, reported by hh_render_config: a workgroup of RENDER_TW / RENDER_PX x RENDER_TH threads owns one RENDER_TH x
 // RENDER_TW tile of the output, a thread RENDER_PX horizontally adjacent pixels of it; the frame's primitives are culled against the
 // tile RENDER_CHUNK at a time, one per lane.
 enum { RENDER_TH = 16, RENDER_TW = 64, RENDER_PX = 4, RENDER_THREADS = RENDER_TH * RENDER_TW / RENDER_PX, RENDER_CHUNK = RENDER_THREADS };
 static_assert(RENDER_THREADS == 256 && RENDER_TW % RENDER_PX == 0, "one lane per primitive of a chunk, whole pixel groups per tile row");
 
-// hh_render_prim of include/hhrnet.h (32 bytes).
-struct RenderPrim {
-    int32_t cx, cy;              // centre, may lie outside the frame
-    uint16_t A, B;               // disc: A = B = r; ring: A = B = R; ellipse: A = 2a + 1, B = 2b + 1
-    float c, s;                  // ellipse: unit direction of the A axis, rounded once to fp32
-    uint8_t r, g, b, kind;       // colour as drawn into the RGB frame, RENDER_*
-    int16_t x0, y0, x1, y1;      // inclusive bounding box, clipped to 0..16383 (empty: x1 < x0 or y1 < y0)
-};
-// hh_render_desc of include/hhrnet.h (48 bytes).
-struct RenderDesc {
-    long long src_offset, dst_offset;  // bytes from batch_base: uint8 RGB [h,w,3] in, uint8 [h,w,3] out
-    int32_t h, w;
-    int32_t prim_offset, prim_count;   // this frame's primitives in the table, in draw order
-    float w0, w1;                      // (float)(1.0 - alpha), (float)alpha
-    int32_t flags, reserved;           // bit 0: store B,G,R
-};
-static_assert(sizeof(RenderPrim) == 32 && sizeof(RenderDesc) == 48, "table layout");
+using RenderPrim = hh_render_prim;
+using RenderDesc = hh_render_desc;
+static_assert(sizeof(hh_render_prim) == 32 && sizeof(hh_render_desc) == 48, "ABI 3");
 
 // Does the primitive's box meet the tile [tx0, tx1] x [ty0, ty1] (inclusive, already inside the frame)?
 HH_RHD bool render_box_meets(const RenderPrim &p, int tx0, int ty0, int tx1, int ty1)
@@ -54,7 +41,7 @@ HH_RHD bool render_inside(const RenderPrim &p, int x, int y)
 {
     if (x < p.x0 || x > p.x1 || y < p.y0 || y > p.y1) return false;
     const int dx = x - p.cx, dy = y - p.cy;
-    if (p.kind == RENDER_ELLIPSE) {
+    if (p.kind == HH_RENDER_ELLIPSE) {
         // one order, every operation rounded to fp32: u = dx c + dy s, v = dy c - dx s, (2u B)^2 + (2v A)^2 <= (A B)^2
         const float fx = (float)dx, fy = (float)dy, Af = (float)p.A, Bf = (float)p.B;
         const float t0 = fx * p.c, t1 = fy * p.s, t2 = fy * p.c, t3 = fx * p.s;
@@ -67,8 +54,8 @@ HH_RHD bool render_inside(const RenderPrim &p, int x, int y)
         return lhs <= rhs;
     }
     const int d2 = dx * dx + dy * dy, R = (int)p.A;
-    if (p.kind == RENDER_DISC) return d2 <= R * R + R;
-    return d2 > R * R - R && d2 <= R * R + R;  // RENDER_RING
+    if (p.kind == HH_RENDER_DISC) return d2 <= R * R + R;
+    return d2 > R * R - R && d2 <= R * R + R;  // HH_RENDER_RING
 }
 
 // addWeighted on one channel: rintf(img w0 + conn w1), products and sum rounded separately, clamped to 0..255.
@@ -101,7 +88,7 @@ inline void render_frame_host(const uint8_t *src, uint8_t *dst, const RenderDesc
                         for (int i = 0; i < n; ++i)
                             if (render_inside(list[i], x, y)) {
                                 uint8_t *c = conn[y - ty0][x - tx0];
-                                c[0] = list[i].r, c[1] = list[i].g, c[2] = list[i].b;
+                                c[0] = list[i].rgb[0], c[1] = list[i].rgb[1], c[2] = list[i].rgb[2];
                             }
             }
             for (int y = ty0; y <= ty1; ++y)
@@ -124,13 +111,13 @@ inline const char *render_check_frame(const RenderDesc &d, const RenderPrim *pri
     if (d.flags & ~1) return "unknown flag";
     for (int i = 0; i < d.prim_count; ++i) {
         const RenderPrim &p = prims[d.prim_offset + i];
-        if (p.kind > RENDER_ELLIPSE) return "unknown primitive kind";
+        if (p.kind > HH_RENDER_ELLIPSE) return "unknown primitive kind";
         if (p.A < 1 || p.B < 1) return "primitive with A or B < 1";
-        if (p.kind != RENDER_ELLIPSE && p.A > 32767) return "disc or ring radius above 32767";
+        if (p.kind != HH_RENDER_ELLIPSE && p.A > 32767) return "disc or ring radius above 32767";
         if (p.cx < -(1 << 23) || p.cx > (1 << 23) || p.cy < -(1 << 23) || p.cy > (1 << 23)) return "primitive centre beyond 2^23";
         if (p.x0 < 0 || p.y0 < 0 || p.x1 > 16383 || p.y1 > 16383) return "bounding box outside 0..16383";
         // the box may not reach further from the centre than the exact forms allow (an empty box is always fine)
-        const long long reach = p.kind == RENDER_ELLIPSE ? 65536 : 32767;
+        const long long reach = p.kind == HH_RENDER_ELLIPSE ? 65536 : 32767;
         if (p.x0 <= p.x1 && p.y0 <= p.y1 &&
             ((long long)p.x0 - p.cx < -reach || (long long)p.x1 - p.cx > reach || (long long)p.y0 - p.cy < -reach || (long long)p.y1 - p.cy > reach))
             return "bounding box too far from the centre (32767 for discs and rings, 65536 for ellipses)";

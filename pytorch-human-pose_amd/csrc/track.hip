@@ -55,10 +55,10 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_kernel(const TrackParams 
                                                               int32_t *__restrict__ out_flags, double *__restrict__ sim_out)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ double s_te[TRACK_MAX_TRACKS], s_ad[TRACK_MAX_TRACKS];
+    __shared__ double s_te[HH_TRACK_MAX_TRACKS], s_ad[HH_TRACK_MAX_TRACKS];
     __shared__ uint64_t s_valid;
-    __shared__ int s_det_slot[TRACK_MAX_PEOPLE], s_slot_id[TRACK_MAX_TRACKS];
-    __shared__ unsigned char s_fresh[TRACK_MAX_TRACKS];
+    __shared__ int s_det_slot[HH_TRACK_MAX_PEOPLE], s_slot_id[HH_TRACK_MAX_TRACKS];
+    __shared__ unsigned char s_fresh[HH_TRACK_MAX_TRACKS];
     const int tid = threadIdx.x, s = blockIdx.x;  // s < S = the grid's size
     const int T = p.max_tracks, P = p.max_people, K = p.K, W = 3 + p.E;
     double *s_sim = reinterpret_cast<double *>(smem);  // [T, P]
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_kernel(const TrackParams 
         __syncthreads();
         if (tid < 64) {
             bool v = false;
-            if (tid < P && tid < n && !(fl & (TRACK_DECODE_FALLBACK | TRACK_DECODE_SOLVER_GUARD))) v = track_det_valid(s_det + (size_t)tid * K * 3, 3, scores[b * P + tid], p);
+            if (tid < P && tid < n && !(fl & (HH_DECODE_FALLBACK | HH_DECODE_SOLVER_GUARD))) v = track_det_valid(s_det + (size_t)tid * K * 3, 3, scores[b * P + tid], p);
             const uint64_t m = __ballot(v);
             if (tid == 0) s_valid = m;
             s_det_slot[tid] = -1;
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_kernel(const TrackParams 
                 const int nfree = track_popcount(free_set), nun = track_popcount(unmatched);
                 st.hdr[0] = issued + (nun < nfree ? nun : nfree);
                 st.hdr[1] += 1;
-                out_flags[b] = (fl & TRACK_DECODE_SOLVER_GUARD ? TRACK_SOLVER_GUARD : 0) | (nun > nfree ? TRACK_POOL_FULL : 0);
+                out_flags[b] = (fl & HH_DECODE_SOLVER_GUARD ? HH_TRACK_SOLVER_GUARD : 0) | (nun > nfree ? HH_TRACK_POOL_FULL : 0);
             }
         }
         __syncthreads();

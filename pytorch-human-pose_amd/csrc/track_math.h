@@ -12,6 +12,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "../../include/hhrnet.h"
+
 #if defined(__HIPCC__)
 #define HH_THD __host__ __device__ __forceinline__
 #else
@@ -21,18 +23,12 @@
 #pragma clang fp contract(off)
 #endif
 
-// The limits (HH_TRACK_* of include/hhrnet.h).  One lane of one wave owns one track slot and the detections of a frame are a 64-bit set.
-enum { TRACK_MAX_TRACKS = 64, TRACK_MAX_K = 64, TRACK_MAX_PEOPLE = 64, TRACK_THREADS = 256 };
-enum { TRACK_DECODE_FALLBACK = 1, TRACK_DECODE_SOLVER_GUARD = 2, TRACK_SOLVER_GUARD = 2, TRACK_POOL_FULL = 4 };
+// One lane of one wave owns one track slot and the detections of a frame are a 64-bit set: the limits HH_TRACK_MAX_* are 64.
+enum { TRACK_THREADS = 256 };
+static_assert(HH_TRACK_MAX_TRACKS == 64 && HH_TRACK_MAX_PEOPLE == 64, "one wave of slots, a 64-bit set of detections");
 
-// hh_track_params of include/hhrnet.h (592 bytes; passed to the kernel by value).
-struct TrackParams {
-    double vars[TRACK_MAX_K];  // (2 sigma_k)^2
-    double fps, min_cutoff, beta, d_cutoff, min_oks;
-    float joint_thr, min_person_score;
-    int32_t K, E, max_people, max_tracks, max_age, min_joints, min_common, reserved;
-};
-static_assert(sizeof(TrackParams) == 592, "parameter layout");
+using TrackParams = hh_track_params;  // passed to the kernel by value
+static_assert(sizeof(hh_track_params) == 592, "ABI 3");
 
 // One stream's state: header {issued ids, frames seen, 0, 0}, then per slot id / hits / misses / pad, the box area of the last matched
 // pose, the filter's xhat and dxhat per coordinate, the last matched raw pose and its joint scores.  All zero = empty.
@@ -235,7 +231,7 @@ inline void track_assign_host(const double *sim, const int32_t *ids, int T, int 
 inline uint64_t track_frame_valid_host(const TrackParams &p, const float *joints_b, const float *scores_b, int n, int flags)
 {
     uint64_t valid = 0;
-    if (flags & (TRACK_DECODE_FALLBACK | TRACK_DECODE_SOLVER_GUARD)) return 0;
+    if (flags & (HH_DECODE_FALLBACK | HH_DECODE_SOLVER_GUARD)) return 0;
     n = n < 0 ? 0 : (n > p.max_people ? p.max_people : n);
     for (int d = 0; d < n; ++d)
         if (track_det_valid(joints_b + (size_t)d * p.K * (3 + p.E), 3 + p.E, scores_b[d], p)) valid |= (uint64_t)1 << d;
@@ -260,7 +256,7 @@ inline void track_frame_host(const TrackParams &p, unsigned char *state, const f
     const TrackState st = track_state_view(state, K, T);
     const uint64_t valid = track_frame_valid_host(p, joints_b, scores_b, n, flags);
     track_similarity_host(p, st, joints_b, valid, sim);
-    int32_t match[TRACK_MAX_TRACKS];
+    int32_t match[HH_TRACK_MAX_TRACKS];
     uint64_t taken = 0;
     track_assign_host(sim, st.id, T, P, p.min_oks, match, &taken);
     uint64_t free_set = 0;
@@ -268,10 +264,10 @@ inline void track_frame_host(const TrackParams &p, unsigned char *state, const f
         if (track_slot_free(st, t, match[t], p)) free_set |= (uint64_t)1 << t;
     const uint64_t unmatched = valid & ~taken;
     const int issued = st.hdr[0];
-    int det_slot[TRACK_MAX_PEOPLE];
+    int det_slot[HH_TRACK_MAX_PEOPLE];
     for (int d = 0; d < P; ++d) det_slot[d] = -1;
-    bool fresh[TRACK_MAX_TRACKS];
-    double Te[TRACK_MAX_TRACKS];
+    bool fresh[HH_TRACK_MAX_TRACKS];
+    double Te[HH_TRACK_MAX_TRACKS];
     for (int t = 0; t < T; ++t) {
         const int det = track_slot_update(st, t, match[t], free_set, unmatched, issued, joints_b, 3 + p.E, p, &fresh[t], &Te[t]);
         if (det >= 0) det_slot[det] = t;
@@ -279,7 +275,7 @@ inline void track_frame_host(const TrackParams &p, unsigned char *state, const f
     const int nfree = track_popcount(free_set), nun = track_popcount(unmatched);
     st.hdr[0] = issued + (nun < nfree ? nun : nfree);
     st.hdr[1] += 1;
-    *out_flags_b = (flags & TRACK_DECODE_SOLVER_GUARD ? TRACK_SOLVER_GUARD : 0) | (nun > nfree ? TRACK_POOL_FULL : 0);
+    *out_flags_b = (flags & HH_DECODE_SOLVER_GUARD ? HH_TRACK_SOLVER_GUARD : 0) | (nun > nfree ? HH_TRACK_POOL_FULL : 0);
     for (int d = 0; d < P; ++d) {
         const int t = det_slot[d];
         const float *det = joints_b + (size_t)d * K * (3 + p.E);
@@ -297,9 +293,9 @@ inline void track_frame_host(const TrackParams &p, unsigned char *state, const f
 inline const char *track_check(const TrackParams *p)
 {
     if (!p) return "null pointer";
-    if (p->K < 1 || p->K > TRACK_MAX_K) return "K outside 1..HH_TRACK_MAX_K (64)";
-    if (p->max_tracks < 1 || p->max_tracks > TRACK_MAX_TRACKS) return "max_tracks outside 1..HH_TRACK_MAX_TRACKS (64)";
-    if (p->max_people < 1 || p->max_people > TRACK_MAX_PEOPLE) return "max_people outside 1..HH_TRACK_MAX_PEOPLE (64)";
+    if (p->K < 1 || p->K > HH_TRACK_MAX_K) return "K outside 1..HH_TRACK_MAX_K (64)";
+    if (p->max_tracks < 1 || p->max_tracks > HH_TRACK_MAX_TRACKS) return "max_tracks outside 1..HH_TRACK_MAX_TRACKS (64)";
+    if (p->max_people < 1 || p->max_people > HH_TRACK_MAX_PEOPLE) return "max_people outside 1..HH_TRACK_MAX_PEOPLE (64)";
     if (p->E < 0 || p->E > 64) return "E outside 0..64";
     for (int k = 0; k < p->K; ++k)
         if (!(p->vars[k] > 0.0) || !isfinite(p->vars[k])) return "vars must be finite and > 0";

@@ -22,12 +22,12 @@
 #define MOSAIC_TY 4     // thread rows
 #define MOSAIC_ROWS 4   // output rows per thread (rows yi, yi + MOSAIC_TY, ...): a block spans 16 output rows
 
-__global__ __launch_bounds__(MOSAIC_TX *MOSAIC_TY) void mosaic_kernel(unsigned char *base, const HHMosaicDesc *__restrict__ descs, int S,
+__global__ __launch_bounds__(MOSAIC_TX *MOSAIC_TY) void mosaic_kernel(unsigned char *base, const hh_mosaic_desc *__restrict__ descs, int S,
                                                                       int xtiles)
 {
     const int xi = threadIdx.x % MOSAIC_TX, yi = threadIdx.x / MOSAIC_TX;
     const int quad = blockIdx.y;
-    const HHMosaicDesc &d = descs[blockIdx.z];
+    const hh_mosaic_desc &d = descs[blockIdx.z];
     const int h = d.tile[quad].h, w = d.tile[quad].w;
     const unsigned char *img = base + d.tile[quad].image_offset, *msk = base + d.tile[quad].mask_offset;
     const int x0 = ((int)(blockIdx.x % xtiles) * MOSAIC_TX + xi) * MOSAIC_PX;  // S % 4 == 0: a thread's four pixels are all inside or all outside
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(MOSAIC_TX *MOSAIC_TY) void mosaic_kernel(unsigned c
     }
 }
 
-hipError_t launch_mosaic(unsigned char *base, const HHMosaicDesc *descs, int n, int S, hipStream_t s)
+hipError_t launch_mosaic(unsigned char *base, const hh_mosaic_desc *descs, int n, int S, hipStream_t s)
 {
     const int xtiles = (S + MOSAIC_TX * MOSAIC_PX - 1) / (MOSAIC_TX * MOSAIC_PX), ytiles = (S + MOSAIC_TY * MOSAIC_ROWS - 1) / (MOSAIC_TY * MOSAIC_ROWS);
     hipLaunchKernelGGL(mosaic_kernel, dim3(xtiles * ytiles, 4, n), dim3(MOSAIC_TX * MOSAIC_TY), 0, s, base, descs, S, xtiles);

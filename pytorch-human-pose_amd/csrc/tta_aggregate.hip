@@ -11,6 +11,7 @@
 #include "engine.h"
 #include "../../include/hhrnet.h"
 
+static_assert(sizeof(hh_scale_src) == 48, "ABI 3");
 struct AggSrc {
     const float *hm, *hmf;  // hmf null: plain source
     long long bs, fbs;      // batch strides in elements

@@ -24,6 +24,8 @@ from operator import itemgetter
 
 import numpy as np
 
+from .. import _lib
+
 KPT_OKS_SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0
 IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
 REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
@@ -218,12 +220,10 @@ def eval_coco(annots_path: str, results_path: str, device=None) -> np.ndarray:
 
 # ---------------------------------------------------------------------- the device path
 _TABLE_FIELDS = ("dt_off", "gt_off", "oks_off", "dt_xy", "dt_score", "dt_area", "gt_xyv", "gt_area", "gt_bbox", "gt_flags", "vars", "area_rng", "thr")
-GT_IGNORE, GT_CROWD = 1, 2  # HH_COCO_GT_IGNORE / HH_COCO_GT_CROWD of include/hhrnet.h
+GT_IGNORE, GT_CROWD = _lib.const("COCO_GT_IGNORE"), _lib.const("COCO_GT_CROWD")
 
 
-class CocoTables(ctypes.Structure):
-    """hh_coco_tables of include/hhrnet.h: 13 addresses, the six counts."""
-    _fields_ = [(n, ctypes.c_void_p) for n in _TABLE_FIELDS] + [(n, ctypes.c_int32) for n in "INMKAT"] + [("reserved", ctypes.c_int32 * 2)]
+CocoTables = _lib.struct_ctype("hh_coco_tables")  # 13 addresses, the six counts
 
 
 def _column(dicts, key, default=None):
@@ -339,7 +339,6 @@ def match_tables_device(tables: dict, device):
     """pack -> one copy -> hh_coco_evaluate -> the three match tables back as numpy: dt_match int32 [A,T,N] (row of the ground-truth
     table + 1, 0 = unmatched), dt_ignore bool [A,T,N], gt_ignore bool [A,M]."""
     import torch
-    from .. import _lib
     lib = _lib.load()
     A, T, N, M = len(tables["area_rng"]), len(tables["thr"]), len(tables["dt_score"]), len(tables["gt_area"])
     blob, offs = blob_layout(tables)
@@ -360,7 +359,6 @@ def match_tables_device(tables: dict, device):
 def match_tables_host(tables: dict, oks_in=None, want_oks: bool = False):
     """The same through hh_coco_evaluate_host (csrc/coco_eval_math.h compiled for the host): (dt_match, dt_ignore, gt_ignore[, oks]).
     `oks_in`: a concatenated float64 buffer to match on instead of computing it (the host form of hh_coco_match)."""
-    from .. import _lib
     lib = _lib.load()
     A, T, N, M = len(tables["area_rng"]), len(tables["thr"]), len(tables["dt_score"]), len(tables["gt_area"])
     dt_match, dt_ignore, gt_ignore = np.zeros(A * T * N + 1, np.int32), np.zeros(A * T * N + 1, np.uint8), np.zeros(A * M + 1, np.uint8)

@@ -25,9 +25,7 @@ import numpy as np
 from .. import _lib
 
 # hh_crowd_mask_desc / hh_crowd_seg_desc of include/hhrnet.h (24 bytes each)
-MASK_DESC = np.dtype([("mask_offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("seg_first", "<i4"), ("seg_count", "<i4")])
-SEG_DESC = np.dtype([("toggle_offset", "<i8"), ("count", "<i4"), ("col_first", "<i4"), ("col_last", "<i4"), ("reserved", "<i4")])
-assert MASK_DESC.itemsize == 24 and SEG_DESC.itemsize == 24
+MASK_DESC, SEG_DESC = _lib.struct_dtype("hh_crowd_mask_desc"), _lib.struct_dtype("hh_crowd_seg_desc")
 MAX_SIDE = 16384
 CHUNK_BYTES = 64 << 20  # mask bytes per launch of `crowd_masks`
 

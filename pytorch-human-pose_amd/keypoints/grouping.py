@@ -101,12 +101,13 @@ class MPPEHeatmapParser:
         pseudo-person in float64 arrays (np.concatenate of int32 coordinates with float32 scores / tags promotes), its joint
         scores the Python float 0.01 and the person score their float64 mean."""
         j, s, n, f = joints.cpu().numpy(), scores.cpu().numpy(), num.cpu().numpy(), flags.cpu().numpy()
-        if (f & 2).any():
-            raise _lib.HHError(f"decode: the assignment solver hit its iteration guard on image(s) {np.nonzero(f & 2)[0].tolist()}")
+        guard = f & _lib.const("DECODE_SOLVER_GUARD")
+        if guard.any():
+            raise _lib.HHError(f"decode: the assignment solver hit its iteration guard on image(s) {np.nonzero(guard)[0].tolist()}")
         out = []
         for b in range(j.shape[0]):
             jb, sb = j[b, : n[b]].copy(), s[b, : n[b]].copy()
-            if f[b] & 1:
+            if f[b] & _lib.const("DECODE_FALLBACK"):
                 jb = jb.astype(np.float64)
                 jb[..., 2] = 0.01
                 sb = jb[..., 2].mean(1)

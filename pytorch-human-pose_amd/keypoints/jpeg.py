@@ -25,9 +25,7 @@ import torch
 from .. import _lib
 
 # hh_jpeg_desc of include/hhrnet.h
-DESC = np.dtype([("src_offset", "<i8"), ("out_offset", "<i8"), ("out_capacity", "<i8"), ("ws_offset", "<i8"), ("pitch", "<i8"), ("h", "<i4"),
-                 ("w", "<i4"), ("quality", "<i4"), ("subsampling", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
-assert DESC.itemsize == 64
+DESC = _lib.struct_dtype("hh_jpeg_desc")
 FLAG_BGR = 1
 
 
@@ -262,18 +260,8 @@ class MJPEGWriter:
 
 # ------------------------------------------------------------------------------------------------------------------ decoding
 # hh_jpeg_stream_info, hh_jpeg_segment, hh_jpeg_dec_desc of include/hhrnet.h
-INFO = np.dtype([("scan_offset", "<i8"), ("scan_end", "<i8"), ("h", "<i4"), ("w", "<i4"), ("ncomp", "<i4"), ("sampling", "<i4"),
-                 ("restart_interval", "<i4"), ("hs", "<i4"), ("vs", "<i4"), ("mcols", "<i4"), ("mrows", "<i4"), ("bpm", "<i4"), ("qt", "<i4", (3,)),
-                 ("dc", "<i4", (3,)), ("ac", "<i4", (3,)), ("nseg_restart", "<i4"), ("adobe_transform", "<i4"), ("reserved", "<i4", (3,))])
-SEGMENT = np.dtype([("first_mcu", "<i4"), ("mcu_count", "<i4"), ("byte_offset", "<i4"), ("bit_offset", "<i4"), ("pred", "<i4", (3,)), ("byte_end", "<i4")])
-DEC_DESC = np.dtype([("stream_offset", "<i8"), ("tables_offset", "<i8"), ("tables_bytes", "<i8"), ("dst_offset", "<i8"), ("ws_offset", "<i8"),
-                     ("pitch", "<i8"), ("stream_length", "<i4"), ("nseg", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
-assert INFO.itemsize == 112 and SEGMENT.itemsize == 32 and DEC_DESC.itemsize == 64
-# hh_jpeg_window, hh_jpeg_win_desc (hh_jpeg_dec_desc, then the window), hh_jpeg_window_counts
-WINDOW = np.dtype([("top", "<i4"), ("left", "<i4"), ("height", "<i4"), ("width", "<i4")])
-WIN_DESC = np.dtype(DEC_DESC.descr + [("window", WINDOW)])
-WIN_COUNTS = np.dtype([(k, "<i8") for k in ("segments_walked", "mcus_walked", "mcus_stored", "blocks_transformed", "pixels_written", "stream_bytes")])
-assert WINDOW.itemsize == 16 and WIN_DESC.itemsize == 80 and WIN_COUNTS.itemsize == 48
+INFO, SEGMENT, DEC_DESC, WINDOW, WIN_DESC, WIN_COUNTS = (_lib.struct_dtype("hh_jpeg_" + k) for k in (
+    "stream_info", "segment", "dec_desc", "window", "win_desc", "window_counts"))
 STATUS_NAMES = ("ok", "bad Huffman code", "zero run past coefficient 63", "bytes exhausted", "missing or unexpected RSTm", "bad segment")
 
 JpegInfo = collections.namedtuple("JpegInfo", "h w components sampling restart_interval mcu_cols mcu_rows scan_offset scan_end")
@@ -432,8 +420,8 @@ class JpegImage:
         return at, tables_at, plan, out[:INFO.itemsize].view(INFO).copy()
 
     def window_desc(self, plan: WindowPlan, stream_at: int, tables_at: int, dst_at: int, ws_at: int, pitch: int, bgr: bool = False) -> tuple:
-        """One WIN_DESC row for a staged window."""
-        return (stream_at, tables_at, plan.tables_bytes, dst_at, ws_at, pitch, plan.slice[1] - plan.slice[0], plan.nsel, FLAG_BGR if bgr else 0, 0,
+        """One WIN_DESC row for a staged window: (the DEC_DESC row `d`, the window)."""
+        return ((stream_at, tables_at, plan.tables_bytes, dst_at, ws_at, pitch, plan.slice[1] - plan.slice[0], plan.nsel, FLAG_BGR if bgr else 0, 0),
                 plan.window)
 
     def whole_plan(self) -> WindowPlan:
@@ -528,7 +516,8 @@ def decode_jpeg_device(streams: list, index=None, bgr=False, device=None, out=No
         infos.append(info)
         dst = rel + dst_at[j] if out is None else out[j].data_ptr() - base
         pitch = 3 * p.window[3] if out is None else int(out[j].stride(0))
-        descs[j] = it.window_desc(p, rel + stream_at, rel + tables_at, dst, int(ws_at[j]), pitch, bgrs[j])[:len(desc_t.names)]  # (DEC_DESC: no window)
+        row = it.window_desc(p, rel + stream_at, rel + tables_at, dst, int(ws_at[j]), pitch, bgrs[j])
+        descs[j] = row if windowed else row[0]  # (DEC_DESC: no window)
     buf[:upload].copy_(host, non_blocking=True)
     launch_decode(device, base, buf.data_ptr(), descs, np.concatenate(infos), work, buf.data_ptr() + status_at, entry)
     status_host = torch.empty(n, dtype=torch.int32, pin_memory=True)

@@ -16,7 +16,6 @@ from .. import _lib
 from ..optim import clip_grad_norm_
 from .grouping import MPPEHeatmapParser
 from .results import InferenceKeypointsResult, transform_coords
-import ctypes as C
 
 from .transforms_utils import COCO_FLIP_INDEX, IMAGENET_MEAN, IMAGENET_STD, dst_to_src_matrix, get_multi_scale_size
 
@@ -249,14 +248,8 @@ class KeypointsModule:
         return metrics, results
 
 
-# hh_image_desc of include/hhrnet.h (64 bytes): byte offset of the image in the batch buffer, its size, destination -> source affine
-_IMAGE_DESC = np.dtype([("offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("inv", "<f8", (6,))])
-
-
-# hh_scale_src of include/hhrnet.h (48 bytes): one source of hh_multi_scale_aggregate
-class _ScaleSrc(C.Structure):
-    _fields_ = [("hm", C.c_void_p), ("bstride", C.c_longlong), ("hm_flipped", C.c_void_p), ("flipped_bstride", C.c_longlong),
-                ("h", C.c_int), ("w", C.c_int), ("weight", C.c_float)]
+# byte offset of the image in the batch buffer, its size, destination -> source affine; one source of hh_multi_scale_aggregate
+_IMAGE_DESC, _ScaleSrc = _lib.struct_dtype("hh_image_desc"), _lib.struct_ctype("hh_scale_src")
 
 
 class _Shape:
@@ -573,7 +566,7 @@ class InferenceKeypointsModel:
                 nb = len(chunk)
                 offs = np.cumsum([0] + [raw_images[i].size for i in chunk])
                 desc_off = (int(offs[-1]) + 63) // 64 * 64  # the image descriptors travel behind the pixels, in the same copy
-                total = desc_off + 64 * nb * len(sizes)  # (one block of them per scale)
+                total = desc_off + _IMAGE_DESC.itemsize * nb * len(sizes)  # (one block of them per scale)
                 if stage[turn] is None or stage[turn].numel() < total:
                     stage[turn] = torch.empty(total, dtype=torch.uint8).pin_memory()
                 elif stage_free[turn] is not None:

@@ -12,17 +12,12 @@ import torch
 from .. import _lib
 from .coco_eval import KPT_OKS_SIGMAS
 
-MAX_TRACKS, MAX_K, MAX_PEOPLE = (_lib._header()[1][k] for k in ("HH_TRACK_MAX_TRACKS", "HH_TRACK_MAX_K", "HH_TRACK_MAX_PEOPLE"))
-SOLVER_GUARD, POOL_FULL = _lib._header()[1]["HH_TRACK_SOLVER_GUARD"], _lib._header()[1]["HH_TRACK_POOL_FULL"]
+MAX_TRACKS, MAX_K, MAX_PEOPLE, SOLVER_GUARD, POOL_FULL = (
+    _lib.const("TRACK_" + k) for k in ("MAX_TRACKS", "MAX_K", "MAX_PEOPLE", "SOLVER_GUARD", "POOL_FULL"))
 STATE_GLOBAL = 1  # hh_track_params.reserved bit 0: keep the state in global memory (tests)
 
 
-class Params(C.Structure):
-    """hh_track_params of include/hhrnet.h"""
-    _fields_ = [("vars", C.c_double * MAX_K), ("fps", C.c_double), ("min_cutoff", C.c_double), ("beta", C.c_double), ("d_cutoff", C.c_double),
-                ("min_oks", C.c_double), ("joint_thr", C.c_float), ("min_person_score", C.c_float), ("K", C.c_int32), ("E", C.c_int32),
-                ("max_people", C.c_int32), ("max_tracks", C.c_int32), ("max_age", C.c_int32), ("min_joints", C.c_int32), ("min_common", C.c_int32),
-                ("reserved", C.c_int32)]
+Params = _lib.struct_ctype("hh_track_params")
 
 
 def make_params(num_kpts=17, max_people=30, max_tracks=64, sigmas=KPT_OKS_SIGMAS, min_oks=0.3, max_age=30, joint_thr=0.05, min_joints=3,

@@ -34,15 +34,8 @@ from .loss import DeviceJoints, pack_joints
 from .targets import JointsGenerator
 from .transforms_utils import COCO_FLIP_INDEX
 
-MAX_STAGES = 4  # HH_TRAIN_MAX_STAGES
-# hh_train_desc of include/hhrnet.h (272 bytes)
-_TRAIN_DESC = np.dtype([("image_offset", "<i8"), ("mask_offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("flip", "<i4"), ("reserved", "<i4"),
-                        ("inv_image", "<f8", (6,)), ("inv_mask", "<f8", (MAX_STAGES, 6))])
-assert _TRAIN_DESC.itemsize == 272
-# hh_mosaic_desc of include/hhrnet.h (112 bytes)
-_MOSAIC_TILE = np.dtype([("image_offset", "<i8"), ("mask_offset", "<i8"), ("h", "<i4"), ("w", "<i4")])
-_MOSAIC_DESC = np.dtype([("tile", _MOSAIC_TILE, (4,)), ("canvas_image_offset", "<i8"), ("canvas_mask_offset", "<i8")])
-assert _MOSAIC_DESC.itemsize == 112
+MAX_STAGES = _lib.const("TRAIN_MAX_STAGES")
+_TRAIN_DESC, _MOSAIC_DESC = _lib.struct_dtype("hh_train_desc"), _lib.struct_dtype("hh_mosaic_desc")
 
 
 @dataclass

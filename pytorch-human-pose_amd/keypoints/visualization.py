@@ -17,14 +17,9 @@ import torch
 
 from .. import _lib
 
-# hh_render_prim / hh_render_desc of include/hhrnet.h
-PRIM = np.dtype([("cx", "<i4"), ("cy", "<i4"), ("A", "<u2"), ("B", "<u2"), ("c", "<f4"), ("s", "<f4"), ("rgb", "u1", (3,)), ("kind", "u1"),
-                 ("box", "<i2", (4,))])
-DESC = np.dtype([("src_offset", "<i8"), ("dst_offset", "<i8"), ("h", "<i4"), ("w", "<i4"), ("prim_offset", "<i4"), ("prim_count", "<i4"),
-                 ("w0", "<f4"), ("w1", "<f4"), ("flags", "<i4"), ("reserved", "<i4")])
-assert PRIM.itemsize == 32 and DESC.itemsize == 48
-DISC, RING, ELLIPSE = 0, 1, 2
-MAX_PRIMS = 4096       # HH_RENDER_MAX_PRIMS
+PRIM, DESC = _lib.struct_dtype("hh_render_prim"), _lib.struct_dtype("hh_render_desc")
+DISC, RING, ELLIPSE = (_lib.const(k) for k in ("RENDER_DISC", "RENDER_RING", "RENDER_ELLIPSE"))
+MAX_PRIMS = _lib.const("RENDER_MAX_PRIMS")
 MAX_SIDE = 16384
 MAX_COORD = 1 << 23
 FLAG_BGR = 1
@@ -51,7 +46,7 @@ def _box(cx: int, cy: int, ex: int, ey: int):
 
 def _boxes(cx, cy, ex, ey) -> np.ndarray:
     """_box on arrays -> [..., 4]."""
-    return np.stack([np.clip(cx - ex, 0, MAX_SIDE), np.clip(cy - ey, 0, MAX_SIDE), np.clip(cx + ex, -1, MAX_SIDE - 1), np.clip(cy + ey, -1, MAX_SIDE - 1)], -1)
+    return np.clip(cx - ex, 0, MAX_SIDE), np.clip(cy - ey, 0, MAX_SIDE), np.clip(cx + ex, -1, MAX_SIDE - 1), np.clip(cy + ey, -1, MAX_SIDE - 1)
 
 
 def ellipse_prim(cx: int, cy: int, a: int, b: int, c, s, colour) -> tuple:
@@ -62,14 +57,14 @@ def ellipse_prim(cx: int, cy: int, a: int, b: int, c, s, colour) -> tuple:
     # half extents of the rotated ellipse plus 2: beyond the fp32 rounding of the inside test
     ha, hb, cd, sd = a + 0.5, b + 0.5, float(c), float(s)
     ex, ey = int(np.sqrt((ha * cd) ** 2 + (hb * sd) ** 2)) + 2, int(np.sqrt((ha * sd) ** 2 + (hb * cd) ** 2)) + 2
-    return (cx, cy, 2 * a + 1, 2 * b + 1, c, s, tuple(colour)[:3], ELLIPSE, _box(cx, cy, ex, ey))
+    return (cx, cy, 2 * a + 1, 2 * b + 1, c, s, tuple(colour)[:3], ELLIPSE, *_box(cx, cy, ex, ey))
 
 
 def circle_prim(cx: int, cy: int, radius: int, colour, ring: bool = False) -> tuple:
     """One hh_render_prim row: the filled disc of `radius`, or the one-pixel ring of `radius` (ring=True)."""
     if not 1 <= radius <= 32767:
         raise ValueError("radius outside 1..32767")
-    return (cx, cy, radius, radius, 1.0, 0.0, tuple(colour)[:3], RING if ring else DISC, _box(cx, cy, radius, radius))
+    return (cx, cy, radius, radius, 1.0, 0.0, tuple(colour)[:3], RING if ring else DISC, *_box(cx, cy, radius, radius))
 
 
 def table_of(rows: list) -> np.ndarray:
@@ -152,7 +147,7 @@ def build_primitives(coords, scores, limbs, thr, color_mode, palette=DEFAULT_PAL
         e = full[:, :L]
         e["cx"], e["cy"], e["A"], e["B"], e["c"], e["s"], e["kind"] = cx, cy, 2 * a + 1, 2 * b + 1, c32, s32, ELLIPSE
         e["rgb"] = palette[person if color_mode != "limb" else np.arange(L)[None, :], :3] + np.zeros((P, L, 1), np.uint8)
-        e["box"] = _boxes(cx, cy, ex, ey)
+        e["x0"], e["y0"], e["x1"], e["y1"] = _boxes(cx, cy, ex, ey)
         dirs[:, :L, 0], dirs[:, :L, 1] = c, s
         keep[:, :L] = valid
     for ring in (0, 1):
@@ -161,7 +156,7 @@ def build_primitives(coords, scores, limbs, thr, color_mode, palette=DEFAULT_PAL
         k["cx"], k["cy"], k["A"], k["B"], k["c"], k["kind"] = xy[..., 0], xy[..., 1], radius, radius, 1.0, RING if ring else DISC
         if not ring:
             k["rgb"] = palette[person if color_mode != "limb" else np.arange(K)[None, :], :3] + np.zeros((P, K, 1), np.uint8)
-        k["box"] = _boxes(xy[..., 0], xy[..., 1], radius, radius)
+        k["x0"], k["y0"], k["x1"], k["y1"] = _boxes(xy[..., 0], xy[..., 1], radius, radius)
         keep[:, L + ring::2] = drawn
     table = np.ascontiguousarray(full[keep])
     return (table, dirs[keep]) if return_direction else table
@@ -281,13 +276,9 @@ def plot_connections(image: np.ndarray, grouped_kpts_coords, grouped_kpts_scores
 
 
 # ---------------------------------------------------------------- heatmap panels (hh_heatmap_panels_u8)
-# hh_panel_map of include/hhrnet.h
-PANEL = np.dtype([("src", "<u8"), ("src2", "<u8"), ("h", "<i4"), ("w", "<i4"), ("kind", "<i4"), ("flags", "<i4"), ("oy", "<i4"), ("ox", "<i4")])
-assert PANEL.itemsize == 40
-DIRECT, SINGLE, NESTED, AVERAGE = 0, 1, 2, 3   # HH_PANEL_*
-CLIP, MINMAX = 1, 2
-PANEL_MAX_MAPS = 256                           # HH_PANEL_MAX_MAPS
-PANEL_PARTS = 32                               # HH_PANEL_PARTS
+PANEL = _lib.struct_dtype("hh_panel_map")
+DIRECT, SINGLE, NESTED, AVERAGE, CLIP, MINMAX, PANEL_MAX_MAPS, PANEL_PARTS = (
+    _lib.const("PANEL_" + k) for k in ("DIRECT", "SINGLE", "NESTED", "AVERAGE", "CLIP", "MINMAX", "MAX_MAPS", "PARTS"))
 MEAN = (0.485, 0.456, 0.406)                   # base/transforms/base.py:5-6
 STD = (0.229, 0.224, 0.225)
 

@@ -26,16 +26,9 @@ import torch
 
 from . import _lib
 
-ALGO_ADAM, ALGO_ADAMW, ALGO_SGD = 0, 1, 2  # HH_OPTIM_* of include/hhrnet.h
-UPLOAD_TENSORS, UPLOAD_GROUPS, UPLOAD_ALL = 1, 2, 3
-# hh_optim_tensor / hh_optim_group of include/hhrnet.h (56 bytes each)
-_TENSOR = np.dtype([("param", "<u8"), ("grad", "<u8"), ("state0", "<u8"), ("state1", "<u8"), ("step", "<u8"), ("numel", "<i8"),
-                    ("group", "<i4"), ("reserved", "<i4")])
-_GROUP = np.dtype([("lr", "<f8"), ("beta1", "<f8"), ("beta2", "<f8"), ("eps", "<f8"), ("weight_decay", "<f8"), ("momentum", "<f8"),
-                   ("nesterov", "<i4"), ("reserved", "<i4")])
-_EMA_ROW = np.dtype([("value", "<u8"), ("ema", "<u8"), ("numel", "<i8")])  # hh_ema_row (24 bytes)
-assert _TENSOR.itemsize == 56 and _GROUP.itemsize == 56 and _EMA_ROW.itemsize == 24
-
+ALGO_ADAM, ALGO_ADAMW, ALGO_SGD = (_lib.const("OPTIM_" + k) for k in ("ADAM", "ADAMW", "SGD"))
+UPLOAD_TENSORS, UPLOAD_GROUPS, UPLOAD_ALL = (_lib.const("OPTIM_UPLOAD_" + k) for k in ("TENSORS", "GROUPS", "ALL"))
+_TENSOR, _GROUP, _EMA_ROW = (_lib.struct_dtype(k) for k in ("hh_optim_tensor", "hh_optim_group", "hh_ema_row"))
 
 class _DeviceOptimizer(torch.optim.Optimizer):
     """What the three classes share: the descriptor table, its upkeep, and the two launches.
@@ -628,7 +621,7 @@ def is_device_optimizer(optimizer) -> bool:
 
 
 STAT_L2, STAT_ABSMAX, STAT_ABSMEAN, STAT_NONFINITE = 0, 1, 2, 3  # the columns of grad_stats()'s rows
-NORM_L2, NORM_INF = 0, 1  # HH_GRAD_NORM_* of include/hhrnet.h
+NORM_L2, NORM_INF = _lib.const("GRAD_NORM_L2"), _lib.const("GRAD_NORM_INF")
 
 
 def grad_stats_rows(named_parameters, params) -> dict:

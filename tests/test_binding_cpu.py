@@ -1,6 +1,6 @@
-"""The Python binding's two policies, each in one place (`_lib.py`): ctypes signatures derived from include/hhrnet.h, and `launch`,
-the one way device work is enqueued (device guard, that device's current stream last, status checked).  No GPU needed: the device
-guard and the stream lookup are replaced by recorders."""
+"""The Python binding's policies, each in one place (`_lib.py`): ctypes signatures, constants and descriptor-struct layouts derived
+from include/hhrnet.h, and `launch`, the one way device work is enqueued (device guard, that device's current stream last, status
+checked).  No GPU needed: the device guard and the stream lookup are replaced by recorders."""
 import contextlib
 import ctypes as C
 import glob
@@ -75,6 +75,127 @@ def test_unparseable_prototype_raises(pkg, bad):
     good = "int hh_new_thing(const float *x, int64_t n,\n                 const double m[6], long long pitch, float eps, void *stream);"
     sigs, _ = pkg._lib.parse_header(header.replace(marker, marker + "\n" + good))
     assert sigs["hh_new_thing"] == (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_float, C.c_void_p])
+
+
+# ---------------------------------------------------------------- descriptor structs
+SIZES = {"hh_image_desc": 64, "hh_train_desc": 272, "hh_mosaic_tile": 24, "hh_mosaic_desc": 112, "hh_crowd_mask_desc": 24, "hh_crowd_seg_desc": 24,
+         "hh_render_prim": 32, "hh_render_desc": 48, "hh_panel_map": 40, "hh_jpeg_desc": 64, "hh_jpeg_stream_info": 112, "hh_jpeg_segment": 32,
+         "hh_jpeg_dec_desc": 64, "hh_jpeg_window": 16, "hh_jpeg_win_desc": 80, "hh_jpeg_window_counts": 48, "hh_coco_tables": 136,
+         "hh_track_params": 592, "hh_crop_desc": 56, "hh_xent_result": 16, "hh_optim_tensor": 56, "hh_optim_group": 56, "hh_ema_row": 24,
+         "hh_scale_src": 48}
+
+
+def _structs(pkg, text=None):
+    return pkg._lib.parse_structs(open(pkg._lib.HEADER).read() if text is None else text)
+
+
+def _layout(dt):
+    """[(field, offset, numpy kind string with the array shape)] of a struct dtype, in declaration order."""
+    return [(n, dt.fields[n][1], (dt[n].subdtype[0].str + str(list(dt[n].shape))) if dt[n].subdtype else dt[n].str) for n in dt.names]
+
+
+def test_struct_sizes_written_out(pkg):
+    structs = _structs(pkg)
+    assert {n: dt.itemsize for n, dt in structs.items()} == SIZES  # ABI version 3: every struct of the header, no other
+    assert all(pkg._lib.struct_dtype(n) == dt for n, dt in structs.items())
+
+
+def test_struct_fields_written_out(pkg):
+    S = _structs(pkg)
+    # a nested struct
+    assert _layout(S["hh_mosaic_tile"]) == [("image_offset", 0, "<i8"), ("mask_offset", 8, "<i8"), ("h", 16, "<i4"), ("w", 20, "<i4")]
+    assert S["hh_mosaic_desc"].names == ("tile", "canvas_image_offset", "canvas_mask_offset")
+    assert S["hh_mosaic_desc"]["tile"].subdtype == (S["hh_mosaic_tile"], (4,))
+    assert [S["hh_mosaic_desc"].fields[n][1] for n in S["hh_mosaic_desc"].names] == [0, 96, 104]
+    assert S["hh_jpeg_win_desc"].names == ("d", "window") and S["hh_jpeg_win_desc"]["d"] == S["hh_jpeg_dec_desc"]
+    assert S["hh_jpeg_win_desc"].fields["window"] == (S["hh_jpeg_window"], 64)
+    # a 2-d array bounded by a macro
+    assert _layout(S["hh_train_desc"]) == [("image_offset", 0, "<i8"), ("mask_offset", 8, "<i8"), ("h", 16, "<i4"), ("w", 20, "<i4"), ("flip", 24, "<i4"),
+                                           ("reserved", 28, "<i4"), ("image_dst_to_src", 32, "<f8[6]"), ("mask_dst_to_src", 80, "<f8[4, 6]")]
+    # pointers
+    assert _layout(S["hh_optim_tensor"]) == [("param", 0, "<u8"), ("grad", 8, "<u8"), ("state0", 16, "<u8"), ("state1", 24, "<u8"), ("step", 32, "<u8"),
+                                             ("numel", 40, "<i8"), ("group", 48, "<i4"), ("reserved", 52, "<i4")]
+    assert _layout(S["hh_panel_map"]) == [("src", 0, "<u8"), ("src2", 8, "<u8"), ("h", 16, "<i4"), ("w", 20, "<i4"), ("kind", 24, "<i4"),
+                                          ("flags", 28, "<i4"), ("oy", 32, "<i4"), ("ox", 36, "<i4")]
+    # small members, and tail padding (48 bytes for 44 of fields)
+    assert _layout(S["hh_render_prim"]) == [("cx", 0, "<i4"), ("cy", 4, "<i4"), ("A", 8, "<u2"), ("B", 10, "<u2"), ("c", 12, "<f4"), ("s", 16, "<f4"),
+                                            ("rgb", 20, "|u1[3]"), ("kind", 23, "|u1"), ("x0", 24, "<i2"), ("y0", 26, "<i2"), ("x1", 28, "<i2"),
+                                            ("y1", 30, "<i2")]
+    assert _layout(S["hh_scale_src"])[-3:] == [("h", 32, "<i4"), ("w", 36, "<i4"), ("weight", 40, "<f4")]
+    # the ctypes form of the same list
+    T = pkg._lib.struct_ctype("hh_coco_tables")
+    assert C.sizeof(T) == 136 and [(n, getattr(T, n).offset) for n, _ in T._fields_] == [(n, S["hh_coco_tables"].fields[n][1]) for n in S["hh_coco_tables"].names]
+    assert all(k is C.c_void_p for _, k in T._fields_[:13]) and T._fields_[-1][1] is C.c_int32 * 2
+
+
+def test_struct_layouts_equal_the_compilers(pkg, tmp_path):
+    """sizeof and every offsetof, as the host C compiler reports them for include/hhrnet.h, against the derived dtypes."""
+    import shutil
+    import subprocess
+    cc = next((c for c in ("cc", "gcc", "/opt/rocm/lib/llvm/bin/clang", "/opt/rocm/llvm/bin/clang") if shutil.which(c)), None)
+    assert cc is not None, "no host C compiler (cc, gcc, ROCm's clang)"
+    structs = _structs(pkg)
+    lines = ['#include <stddef.h>', '#include <stdio.h>', f'#include "{pkg._lib.HEADER}"', "int main(void) {"]
+    for name, dt in structs.items():
+        lines.append(f'    printf("{name} %zu", sizeof({name}));')
+        lines += [f'    printf(" {f}=%zu", offsetof({name}, {f}));' for f in dt.names]
+        lines.append('    printf("\\n");')
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines + ["    return 0;", "}", ""]))
+    subprocess.run([cc, "-std=c99", str(src), "-o", str(tmp_path / "layout")], check=True)
+    out = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout
+    want = "".join(f"{n} {dt.itemsize}" + "".join(f" {f}={dt.fields[f][1]}" for f in dt.names) + "\n" for n, dt in structs.items())
+    assert len(structs) == len(SIZES) and out == want
+
+
+def test_struct_parser_notices_edits(pkg):
+    header = open(pkg._lib.HEADER).read()
+    a, b = "    int32_t h, w;\n    int32_t prim_offset, prim_count;\n", "    int32_t prim_offset, prim_count;\n    int32_t h, w;\n"
+    assert header.count(a) == 1  # (inside hh_render_desc)
+    was, now = _structs(pkg)["hh_render_desc"], _structs(pkg, header.replace(a, b))["hh_render_desc"]
+    assert was.itemsize == now.itemsize == 48
+    assert [was.fields[n][1] for n in ("h", "w", "prim_offset", "prim_count")] == [16, 20, 24, 28]
+    assert [now.fields[n][1] for n in ("h", "w", "prim_offset", "prim_count")] == [24, 28, 16, 20]
+    stages = "#define HH_TRAIN_MAX_STAGES 4"
+    assert header.count(stages) == 1
+    assert _structs(pkg, header.replace(stages, "#define HH_TRAIN_MAX_STAGES 5"))["hh_train_desc"].itemsize == 272 + 48
+
+
+@pytest.mark.parametrize("bad", [
+    "size_t n;",                              # a type the table of kinds does not list
+    "struct hh_image_desc d;",                # a struct that is not spelled as a parsed hh_* typedef
+    "hh_ema_row row;",                        # a struct defined further down
+    "int flags : 3;",                         # a bit-field
+    "union { int i; float f; } u;",           # a union
+    "int (*callback)(int);",                  # a function pointer
+    "double m[HH_NO_SUCH_LIMIT];",            # a bound that is no parsed macro
+    "double m[2 * 3];",                       # a bound that is an expression
+    "double m[0];",                           # no room
+    "int h;",                                 # a name twice
+])
+def test_unparseable_struct_body_raises(pkg, bad):
+    header = open(pkg._lib.HEADER).read()
+    marker = "typedef struct hh_image_desc {"
+    assert header.count(marker) == 1
+    added = "typedef struct hh_new_thing {\n    int h, w;\n    %s\n} hh_new_thing;\n"
+    with pytest.raises(pkg._lib.HHError, match="hh_new_thing"):
+        pkg._lib.parse_header(header.replace(marker, added % bad + marker))
+    # the same text with a well-formed addition parses: pointers, macro-bounded and 2-d arrays, a nested struct, several names per line
+    good = "const float *src, *const *list;\n    long long at[HH_TRAIN_MAX_STAGES][2];\n    hh_image_desc image[2];\n    uint8_t a, b[3];"
+    dt = _structs(pkg, header.replace("typedef struct hh_train_desc {", added % good + "typedef struct hh_train_desc {"))["hh_new_thing"]
+    assert _layout(dt)[:5] == [("h", 0, "<i4"), ("w", 4, "<i4"), ("src", 8, "<u8"), ("list", 16, "<u8"), ("at", 24, "<i8[4, 2]")]
+    assert dt.fields["image"][1] == 88 and dt.fields["a"][1] == 216 and dt.fields["b"][1] == 217 and dt.itemsize == 224
+
+
+def test_no_module_restates_a_table():
+    """The descriptor tables and their sizes are written in include/hhrnet.h alone: outside _lib.py the package has no dtype literal,
+    no ctypes field list and no itemsize assertion."""
+    import re
+    files = [f for f in glob.glob(os.path.join(REPO, PKG, "**", "*.py"), recursive=True) if os.path.basename(f) != "_lib.py"]
+    assert len(files) > 20
+    hits = [(os.path.relpath(f, REPO), m.group(0)) for f in files
+            for m in re.finditer(r"np\.dtype\(\s*\[|_fields_\s*=|assert[^\n]*itemsize\s*==|ctypes\.Structure|C\.Structure", open(f).read())]
+    assert hits == []
 
 
 # ---------------------------------------------------------------- launch

@@ -241,7 +241,7 @@ def test_the_batch_entry_refuses_by_name_before_any_launch(J, pkg):
         desc = np.zeros(1, J.WIN_DESC)
         desc[0] = item.window_desc(plan, stream_at, 1024 + tables_at, 65536, 0, 3 * win[3])
         for k, v in fields.items():
-            desc[0][k] = v
+            (desc["d"] if k in J.DEC_DESC.names else desc)[k][0] = v  # (hh_jpeg_win_desc: the decode descriptor `d`, then the window)
         return lib.hh_jpeg_decode_window_u8_batch(base, descs_dev, desc.ctypes.data, info.ctypes.data, n, work, ws_bytes, status, None), lib.hh_last_error().decode()
 
     wrong = info.copy()

@@ -227,8 +227,8 @@ def test_render_refusals_before_any_device_call(pkg, vis):
                      (dict(w0=float("nan")), "finite"), (dict(w1=float("inf")), "finite"), (dict(flags=2), "flag"),
                      (dict(prim=dict(kind=3)), "kind"), (dict(prim=dict(A=0)), "A or B"), (dict(prim=dict(B=0)), "A or B"),
                      (dict(prim=dict(A=40000)), "radius"), (dict(prim=dict(cx=1 << 24)), "centre"), (dict(prim=dict(cy=-(1 << 24))), "centre"),
-                     (dict(prim=dict(box=(-1, 0, 5, 5))), "box"), (dict(prim=dict(box=(0, 0, 16384, 5))), "box"),
-                     (dict(prim=dict(cx=-40000, box=(0, 0, 5, 5))), "too far")):
+                     (dict(prim=dict(x0=-1, y0=0, x1=5, y1=5)), "box"), (dict(prim=dict(x0=0, y0=0, x1=16384, y1=5)), "box"),
+                     (dict(prim=dict(cx=-40000, x0=0, y0=0, x1=5, y1=5)), "too far")):
         assert call(**kw) != 0 and word in _err(lib), (kw, _err(lib))
     assert call(n=3, h=0) != 0 and "frame 2" in _err(lib)  # the last of three frames
     rows = [vis.circle_prim(3, 3, 2, (1, 2, 3))] * (MAX_PRIMS + 1)

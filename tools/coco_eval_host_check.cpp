@@ -57,7 +57,7 @@ static int run(int K)
         }
         gt_area[m] = rnd() < 0.3 ? 1024.0 : 500 + 20000 * rnd();
         gt_bbox[4 * m] = 1000; gt_bbox[4 * m + 1] = 1000; gt_bbox[4 * m + 2] = 10 + 20 * rnd(); gt_bbox[4 * m + 3] = 10 + 20 * rnd();
-        gt_flags[m] = (uint8_t)((kind <= 1 ? COCO_GT_IGNORE : 0) | (kind == 1 ? COCO_GT_CROWD : 0));
+        gt_flags[m] = (uint8_t)((kind <= 1 ? HH_COCO_GT_IGNORE : 0) | (kind == 1 ? HH_COCO_GT_CROWD : 0));
     }
     for (int n = 0; n < N; ++n) {
         for (int k = 0; k < K * 2; ++k) dt_xy[(size_t)n * K * 2 + k] = 1000 + 40 * rnd();
@@ -89,7 +89,7 @@ static int run(int K)
     vars[K - 1] = keep;
 
     const size_t n_match = (size_t)A * T * N, n_gt = (size_t)A * M, n_oks = (size_t)oks_off[I];
-    double *scratch = block<double>(COCO_MAX_DET * COCO_MAX_GT);
+    double *scratch = block<double>(HH_COCO_MAX_DET * HH_COCO_MAX_GT);
     int32_t *m1 = block<int32_t>(n_match), *m2 = block<int32_t>(n_match);
     uint8_t *i1 = block<uint8_t>(n_match), *i2 = block<uint8_t>(n_match), *g1 = block<uint8_t>(n_gt), *g2 = block<uint8_t>(n_gt);
     double *o1 = block<double>(n_oks), *o2 = block<double>(n_oks);

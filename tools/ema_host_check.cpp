@@ -47,7 +47,7 @@ static int differ(const float *a, const float *b, long long n) { return memcmp(a
 
 template <int ALGO> static int run(int align, long long n_averaged, double decay, int warmup)
 {
-    const OptimGroup gr = {ALGO == OPTIM_SGD ? 0.05 : 1e-3, 0.9, 0.999, 1e-8, 1e-2, 0.9, 1, 0};
+    const OptimGroup gr = {ALGO == HH_OPTIM_SGD ? 0.05 : 1e-3, 0.9, 0.999, 1e-8, 1e-2, 0.9, 1, 0};
     const OptimCoefs c = optim_coefs(ALGO, gr.lr, gr.beta1, gr.beta2, gr.eps, gr.weight_decay, gr.momentum, gr.nesterov, 8.0);
     const EmaCoef ec = ema_coef(decay, warmup, n_averaged);
     int bad = 0;
@@ -59,8 +59,8 @@ template <int ALGO> static int run(int align, long long n_averaged, double decay
         for (long long i = 0; i < n; ++i) s1A.ptr[i] *= s1A.ptr[i];
         if (n > 2) { pA.ptr[0] = -0.0f; eA.ptr[1] = 1e-41f; }
         Buf gA(g0, 0), pB(pA, poff), gB(g0, 0), s0B(s0A, 0), s1B(s1A, 0), eB(eA, eoff), e0(eA, 0);
-        const OptimTensor tA = {pA.ptr, gA.ptr, s0A.ptr, ALGO != OPTIM_SGD ? s1A.ptr : nullptr, nullptr, n, 0, 0};
-        const OptimTensor tB = {pB.ptr, gB.ptr, s0B.ptr, ALGO != OPTIM_SGD ? s1B.ptr : nullptr, nullptr, n, 0, 0};
+        const OptimTensor tA = {pA.ptr, gA.ptr, s0A.ptr, ALGO != HH_OPTIM_SGD ? s1A.ptr : nullptr, nullptr, n, 0, 0};
+        const OptimTensor tB = {pB.ptr, gB.ptr, s0B.ptr, ALGO != HH_OPTIM_SGD ? s1B.ptr : nullptr, nullptr, n, 0, 0};
         const EmaRow rB = {pB.ptr, eB.ptr, n};
         const int nchunks = (int)((n + OPTIM_CHUNK - 1) / OPTIM_CHUNK);
         for (int ch = 0; ch < nchunks; ++ch)
@@ -80,7 +80,7 @@ template <int ALGO> static int run(int align, long long n_averaged, double decay
         }
         // a NULL fifth stream is the plain walk
         Buf pC(pB, poff), gC(gB, 0), s0C(s0B, 0), s1C(s1B, 0);
-        const OptimTensor tC = {pC.ptr, gC.ptr, s0C.ptr, ALGO != OPTIM_SGD ? s1C.ptr : nullptr, nullptr, n, 0, 0};
+        const OptimTensor tC = {pC.ptr, gC.ptr, s0C.ptr, ALGO != HH_OPTIM_SGD ? s1C.ptr : nullptr, nullptr, n, 0, 0};
         for (int ch = 0; ch < nchunks; ++ch)
             for (int tid = 0; tid < OPTIM_THREADS; ++tid) {
                 optim_chunk_update<ALGO, EmaFifth>(tC, ch, c, false, 1.0f, tid, EmaFifth{nullptr, ec});
@@ -105,7 +105,7 @@ int main()
         for (long long n : {0LL, 1LL, 7LL, 1000000LL})
             for (double decay : {0.9998, 0.5, 0.0, 1.0})
                 for (int warmup : {0, 1}) {
-                    const int b = run<OPTIM_ADAM>(align, n, decay, warmup) + run<OPTIM_ADAMW>(align, n, decay, warmup) + run<OPTIM_SGD>(align, n, decay, warmup);
+                    const int b = run<HH_OPTIM_ADAM>(align, n, decay, warmup) + run<HH_OPTIM_ADAMW>(align, n, decay, warmup) + run<HH_OPTIM_SGD>(align, n, decay, warmup);
                     if (b) printf("align %d  n_averaged %lld  decay %g  warmup %d: %d mismatches\n", align, n, decay, warmup, b);
                     bad += b;
                     ++cases;

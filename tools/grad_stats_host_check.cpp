@@ -67,7 +67,7 @@ struct Table {
         tensor_sumsq.resize(NT);
     }
     ~Table() { for (Buf *b : bufs) delete b; }
-    float *g(int k) { return tensors[k].g; }
+    float *g(int k) { return tensors[k].grad; }
 };
 
 static GradPartial block_reduce(GradPartial *thread)  // OPTIM_THREADS records -> the block's, as grad_block_reduce of grad_stats.hip

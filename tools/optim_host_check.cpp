@@ -43,8 +43,8 @@ template <int ALGO> static int run(int step0, bool unscale)
     std::vector<Buf *> bufs;
     std::vector<OptimTensor> tensors;
     std::vector<std::vector<float>> orig;  // p, g, s0, s1 per tensor
-    const OptimGroup groups[2] = {{ALGO == OPTIM_SGD ? 0.05 : 1e-3, 0.9, 0.999, 1e-8, ALGO == OPTIM_SGD ? 1e-4 : 0.0, 0.9, 1, 0},
-                                  {ALGO == OPTIM_SGD ? 0.01 : 3e-3, 0.9, 0.999, 1e-8, ALGO == OPTIM_SGD ? 0.0 : 1e-2, 0.0, 0, 0}};
+    const OptimGroup groups[2] = {{ALGO == HH_OPTIM_SGD ? 0.05 : 1e-3, 0.9, 0.999, 1e-8, ALGO == HH_OPTIM_SGD ? 1e-4 : 0.0, 0.9, 1, 0},
+                                  {ALGO == HH_OPTIM_SGD ? 0.01 : 3e-3, 0.9, 0.999, 1e-8, ALGO == HH_OPTIM_SGD ? 0.0 : 1e-2, 0.0, 0, 0}};
     const float scale = unscale ? 65536.0f : 1.0f;
     float step_counter[NT];
     for (int k = 0; k < NT; ++k) {
@@ -61,9 +61,9 @@ template <int ALGO> static int run(int step0, bool unscale)
         }
         for (Buf *b : {p, g, s0, s1}) orig.emplace_back(b->ptr, b->ptr + n);
         step_counter[k] = (float)step0;
-        const bool need_s0 = ALGO != OPTIM_SGD || groups[k % 2].momentum != 0.0;
-        tensors.push_back(OptimTensor{p->ptr, g->ptr, need_s0 ? s0->ptr : nullptr, ALGO != OPTIM_SGD ? s1->ptr : nullptr,
-                                      ALGO != OPTIM_SGD ? &step_counter[k] : nullptr, n, k % 2, 0});
+        const bool need_s0 = ALGO != HH_OPTIM_SGD || groups[k % 2].momentum != 0.0;
+        tensors.push_back(OptimTensor{p->ptr, g->ptr, need_s0 ? s0->ptr : nullptr, ALGO != HH_OPTIM_SGD ? s1->ptr : nullptr,
+                                      ALGO != HH_OPTIM_SGD ? &step_counter[k] : nullptr, n, k % 2, 0});
     }
     std::vector<OptimChunk> chunks;
     for (int k = 0; k < NT; ++k)
@@ -88,19 +88,19 @@ template <int ALGO> static int run(int step0, bool unscale)
         for (long long i = 0; i < SIZES[k]; ++i) {
             float p = orig[4 * k][i], g = orig[4 * k + 1][i] / scale, a = orig[4 * k + 2][i], b = orig[4 * k + 3][i];
             optim_update<ALGO>(p, g, a, b, c);
-            bad += memcmp(&p, &t.p[i], 4) != 0;
-            if (t.s0) bad += memcmp(&a, &t.s0[i], 4) != 0;
-            if (t.s1) bad += memcmp(&b, &t.s1[i], 4) != 0;
-            if (unscale) bad += memcmp(&g, &t.g[i], 4) != 0;
+            bad += memcmp(&p, &t.param[i], 4) != 0;
+            if (t.state0) bad += memcmp(&a, &t.state0[i], 4) != 0;
+            if (t.state1) bad += memcmp(&b, &t.state1[i], 4) != 0;
+            if (unscale) bad += memcmp(&g, &t.grad[i], 4) != 0;
         }
     }
     // a planted inf in the last element of the last tensor, a NaN in the first of the first
-    tensors[NT - 1].g[SIZES[NT - 1] - 1] = INFINITY;
+    tensors[NT - 1].grad[SIZES[NT - 1] - 1] = INFINITY;
     int hits = 0;
     for (const OptimChunk &ck : chunks)
         for (int tid = 0; tid < OPTIM_THREADS; ++tid) hits += optim_chunk_nonfinite(tensors[ck.tensor], ck.chunk, false, 1.0f, tid);
     bad += hits != 1;
-    tensors[0].g[0] = NAN;
+    tensors[0].grad[0] = NAN;
     hits = 0;
     for (const OptimChunk &ck : chunks)
         for (int tid = 0; tid < OPTIM_THREADS; ++tid) hits += optim_chunk_nonfinite(tensors[ck.tensor], ck.chunk, true, 0.5f, tid);
@@ -114,9 +114,9 @@ int main()
 {
     int bad = 0;
     for (int step0 : {0, 1, 999, 99999})
-        for (bool unscale : {false, true}) bad += run<OPTIM_ADAM>(step0, unscale) + run<OPTIM_ADAMW>(step0, unscale);
+        for (bool unscale : {false, true}) bad += run<HH_OPTIM_ADAM>(step0, unscale) + run<HH_OPTIM_ADAMW>(step0, unscale);
     for (int step0 : {0, 1})
-        for (bool unscale : {false, true}) bad += run<OPTIM_SGD>(step0, unscale);
+        for (bool unscale : {false, true}) bad += run<HH_OPTIM_SGD>(step0, unscale);
     printf(bad ? "FAILED\n" : "ok\n");
     return bad ? 1 : 0;
 }

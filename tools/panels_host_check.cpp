@@ -48,9 +48,9 @@ static int run(int hq, int wq, int K, int nrows, int pad, int slack)
             memset(&m, 0, sizeof(m));
             m.kind = kind;
             m.flags = (k + kind) % 4;
-            m.h = kind == PANEL_DIRECT ? H : (kind == PANEL_SINGLE && (k & 1) ? 2 * hq : hq);
-            m.w = kind == PANEL_DIRECT ? W : (kind == PANEL_SINGLE && (k & 1) ? 2 * wq : wq);
-            float *a = plane(m.h, m.w, k), *b = kind == PANEL_AVERAGE ? plane(2 * hq, 2 * wq, -1) : nullptr;
+            m.h = kind == HH_PANEL_DIRECT ? H : (kind == HH_PANEL_SINGLE && (k & 1) ? 2 * hq : hq);
+            m.w = kind == HH_PANEL_DIRECT ? W : (kind == HH_PANEL_SINGLE && (k & 1) ? 2 * wq : wq);
+            float *a = plane(m.h, m.w, k), *b = kind == HH_PANEL_AVERAGE ? plane(2 * hq, 2 * wq, -1) : nullptr;
             blocks.push_back(a);
             if (b) blocks.push_back(b);
             m.src = a; m.src2 = b;

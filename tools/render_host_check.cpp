@@ -29,9 +29,9 @@ static RenderPrim prim(int kind, int cx, int cy, int a, int b, double ang)
     RenderPrim p;
     memset(&p, 0, sizeof(p));
     p.kind = (uint8_t)kind; p.cx = cx; p.cy = cy;
-    p.r = (uint8_t)rnd(); p.g = (uint8_t)rnd(); p.b = (uint8_t)rnd();
+    for (uint8_t &v : p.rgb) v = (uint8_t)rnd();
     int ex, ey;
-    if (kind == RENDER_ELLIPSE) {
+    if (kind == HH_RENDER_ELLIPSE) {
         p.A = (uint16_t)(2 * a + 1); p.B = (uint16_t)(2 * b + 1); p.c = (float)cos(ang); p.s = (float)sin(ang);
         const double ha = a + 0.5, hb = b + 0.5;
         ex = (int)sqrt(ha * p.c * ha * p.c + hb * p.s * hb * p.s) + 2; ey = (int)sqrt(ha * p.s * ha * p.s + hb * p.c * hb * p.c) + 2;
@@ -55,7 +55,7 @@ static int run(int h, int w, int count, int flags)
         int cx = (int)(rnd() % (unsigned)(w + 40)) - 20, cy = (int)(rnd() % (unsigned)(h + 40)) - 20;
         if (i % 17 == 5) cx = w + 500, ++outside;           // wholly outside
         if (i % 17 == 11) cy = -(1 << 22);                  // far outside: the box is empty, dx is never formed for a pixel
-        table[i] = prim(kind, cx, cy, kind == RENDER_ELLIPSE ? (int)(rnd() % 60) : 1 + (int)(rnd() % 9), (int)(rnd() % 5), 0.1 * i);
+        table[i] = prim(kind, cx, cy, kind == HH_RENDER_ELLIPSE ? (int)(rnd() % 60) : 1 + (int)(rnd() % 9), (int)(rnd() % 5), 0.1 * i);
     }
     RenderDesc d;
     memset(&d, 0, sizeof(d));

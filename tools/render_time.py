@@ -83,7 +83,7 @@ def direct_launch(frame_dev, table, alpha, bgr):
 def survivors(table, cfg):
     Th, Tw = cfg[0], cfg[1]
     ty, tx = np.arange(0, H, Th), np.arange(0, W, Tw)
-    x0, y0, x1, y1 = (table["box"][:, k].astype(np.int64) for k in range(4))
+    x0, y0, x1, y1 = (table[k].astype(np.int64) for k in ("x0", "y0", "x1", "y1"))
     meets_x = (x0[:, None] <= np.minimum(tx + Tw, W)[None] - 1) & (x1[:, None] >= tx[None])
     meets_y = (y0[:, None] <= np.minimum(ty + Th, H)[None] - 1) & (y1[:, None] >= ty[None])
     per_tile = (meets_y[:, :, None] & meets_x[:, None, :]).sum(0)

@@ -67,7 +67,7 @@ static int run(int K, int T, int P, int E, int frames, int people)
             scores.ptr[(size_t)f * P + d] = d < n ? 0.5f : 0.f;
         }
         num.ptr[f] = f % 9 == 4 ? P + 3 : (f % 9 == 8 ? -2 : n);  // beyond the table and negative: clamped
-        flags.ptr[f] = f % 10 == 6 ? TRACK_DECODE_FALLBACK : (f % 10 == 9 ? TRACK_DECODE_SOLVER_GUARD : 0);
+        flags.ptr[f] = f % 10 == 6 ? HH_DECODE_FALLBACK : (f % 10 == 9 ? HH_DECODE_SOLVER_GUARD : 0);
     }
     for (size_t i = 0; i < smooth.n; ++i) smooth.ptr[i] = smooth2.ptr[i] = NAN;
     int bad = 0;
@@ -93,7 +93,7 @@ static int run(int K, int T, int P, int E, int frames, int people)
             if (st.id[t]) { if (live_prev[st.id[t]]) ++bad; live_prev[st.id[t]] = 1; }  // one slot per id
             if (st.id[t] && st.misses[t] > p.max_age) ++bad;
         }
-        if ((flags.ptr[f] & TRACK_DECODE_SOLVER_GUARD) && !(out_flags.ptr[f] & TRACK_SOLVER_GUARD)) ++bad;
+        if ((flags.ptr[f] & HH_DECODE_SOLVER_GUARD) && !(out_flags.ptr[f] & HH_TRACK_SOLVER_GUARD)) ++bad;
     }
     for (size_t i = 0; i < smooth.n; ++i) bad += std::isnan(smooth.ptr[i]) ? 1 : 0;
     // the whole clip in one walk: the same bytes
