@@ -676,7 +676,7 @@ typedef struct hh_jpeg_stream_info {
     int32_t qt[3], dc[3], ac[3];
     int32_t nseg_restart;
     int32_t adobe_transform;   /* -1: none */
-    int32_t reserved[3];
+    int32_t reserved[3];       /* 0 from hh_jpeg_parse; the device index (below) uses [0]: its status, [1]: 1 = entries to be filled */
 } hh_jpeg_stream_info;
 typedef struct hh_jpeg_segment {
     int32_t first_mcu, mcu_count;
@@ -757,6 +757,70 @@ int hh_jpeg_decode_window_u8_batch(unsigned char *batch_base, const hh_jpeg_win_
 int hh_debug_jpeg_decode_window_host(const unsigned char *bytes, long long len, const hh_jpeg_segment *entries, int nseg,
                                      const hh_jpeg_window *window, int flags, unsigned char *dst, long long pitch, int *status,
                                      hh_jpeg_window_counts *counts);
+/* The index of a restart-less stream built on the device: no Huffman work on the host before the bytes cross the bus, and segments as
+ * fine as one likes (the entropy launch of the decode is bound by the length of one lane's walk).  Huffman codes self-synchronise: a
+ * decoder started at an arbitrary bit soon falls into step with the true symbol sequence (Weissenberger & Schmidt, "Accelerating JPEG
+ * decompression on GPUs", 2021).
+ *
+ * The rule.
+ * Which streams.  For a stream without DRI that hh_jpeg_parse accepts, hh_jpeg_index_device_batch writes into the image's table block
+ *   the same hh_jpeg_segment entries that hh_jpeg_index_host(bytes, len, mcus_per_segment, ...) writes, bit for bit: first_mcu,
+ *   mcu_count, byte_offset, bit_offset, pred[3], byte_end.  Parity is defined against that function and nothing else.  The count is
+ *   ceil(mcols mrows / mcus_per_segment), known from the header alone.
+ * Algorithm (all arithmetic in csrc/jpeg_dec_math.h, shared by host and device: JpegBits, jpeg_dec_symbol, jpeg_dec_block<false>,
+ *   jpeg_bits_where, jpeg_idx_walk).  The scan's bytes [scan_offset, min(scan_end, stream_length)) are cut into subsequences of
+ *   subseq_bytes; one lane takes one subsequence.  Lane 0 starts at the true state: scan_offset, bit 0, block 0 of the MCU.  Every other
+ *   lane starts at the first data bit of its subsequence (a 00 that follows an FF is skipped) and assumes a block boundary with
+ *   block-in-MCU index 0.  A lane's state at a block boundary is the canonical bit position plus the block's index in the MCU; the
+ *   canonical position is byte_offset / bit_offset exactly as hh_jpeg_index_host forms them (an FF 00 pair is one byte, the offset
+ *   points at the FF).  DC predictors are not part of the state: only the differences are summed, with uint32 wrap.  Each lane decodes
+ *   whole blocks up to its first boundary at or past the start of the next subsequence and records that exit state, its block count
+ *   and its DC sums per component.  Then the lanes synchronise until nothing changes: a lane whose start state differs from its
+ *   predecessor's exit state takes that state and decodes again.  Lane 0 is true, so after k passes lanes 0..k are true, and the loop
+ *   ends after at most as many passes as there are lanes.  Exclusive scans over block counts and DC sums follow; in a last walk from
+ *   the verified start states each lane writes the entries whose MCU boundary it crosses, pred = prefix + running sum.
+ * Several rounds.  One workgroup owns one image.  A stream with more subsequences than the workgroup has lanes is processed in rounds
+ *   of that many; the verified end state, block count and DC sums of one round are the true start of the next.
+ * Status.  Speculative lanes report nothing.  Only the last walk, which is on the true chain, reports: status_dev[i] is cleared first,
+ *   then set to the code hh_jpeg_index_host meets on the same stream: 0, or 1 bad Huffman code, 2 zero run past coefficient 63, 3 bytes
+ *   exhausted.  A nonzero code is also written to reserved[0] of the info at the head of the image's table block on the DEVICE, and the
+ *   entropy launch of hh_jpeg_decode_u8_batch skips an image whose table block carries one (its pixels are then unspecified, inside
+ *   its own destination; its decode status stays 0, so the larger of the two calls' codes is the index's).
+ * Invariants, held by construction.  Every loop is bounded by the subsequence count (the passes of a round: the round's lanes; the
+ *   rounds: ceil(subsequences / lanes)), the block count mcols mrows bpm (a lane's walk ends after that many blocks at the latest), or
+ *   the scan's length (the bit reader).  No workgroup ever waits for another: no spins, no grid-wide barriers, no cooperative launch;
+ *   the only waits are the barriers of one workgroup, reached by all of its lanes.  Every byte read lies inside the image's stream
+ *   ([scan_offset, min(scan_end, stream_length))).  Every write lies inside the image's table block (entries below nseg, the info's
+ *   reserved[0]) or its status word.
+ * Streams with DRI keep hh_jpeg_restart_segments (a byte scan with no Huffman work already); cutting restart intervals finer on the
+ *   device is out of scope.  The index launch skips such images, and every image whose table block was not written by
+ *   hh_jpeg_index_tables (reserved[1] of its info is not 1): host-indexed, DRI and device-indexed images mix freely in one batch.
+ *
+ * hh_jpeg_index_config: out[4] = lanes per workgroup (1024), the default subseq_bytes (32: the fastest of 16..512 in profiles/jpeg_index.md), the minimum subseq_bytes (4), the default
+ *   mcus_per_segment (2: the finest size measured, profiles/jpeg_index.md; a parameter, not an optimum).
+ * hh_jpeg_index_workspace_bytes: the global scratch of one image.  Derived, not measured: a round's states (one exit state per lane)
+ *   live in LDS and what a round hands to the next is one state, one block count and three sums, so the answer is 0 for every stream
+ *   and `workspace` may be NULL; -1 with hh_last_error set for an info hh_jpeg_parse cannot have written or a refused subseq_bytes.
+ * hh_jpeg_index_tables (HOST): the table block of hh_jpeg_decode_tables for a stream without DRI, with every entry's first_mcu /
+ *   mcu_count filled and its offsets and predictors zero, and reserved[1] of the info set to 1 (the device is to fill the entries).
+ *   *nseg receives the count.  The whole block crosses the bus with the stream (32 nseg bytes of it are the blank entries).
+ * hh_jpeg_index_device_batch: one launch on `stream`, in front of hh_jpeg_decode_u8_batch on the same stream with the same
+ *   hh_jpeg_dec_desc rows.  Returns 1 with hh_last_error set, before any launch or clearing, for everything the decode refuses, for
+ *   subseq_bytes below the minimum or not a multiple of 4, mcus_per_segment < 1, workspace_bytes < 0, and for an image to be indexed
+ *   whose nseg is not the count of mcus_per_segment.
+ * hh_debug_jpeg_index_sync_host: the same shared code on one stream in HOST memory with `lanes` subsequences per round; *n entries
+ *   (0 with a nonzero *status, which also returns 1); counts (may be NULL) receives six numbers: rounds, passes that changed a lane in
+ *   all, the same in the worst round, subsequences, blocks decoded in all, blocks decoded by the last walk (the true chain).  For tests and
+ *   tools/jpeg_index_host_check.cpp, and as the yardstick of the GPU tests.
+ * (Additive entry points: HH_ABI_VERSION stays 3.)                                                                           */
+int hh_jpeg_index_config(int out[4]);
+long long hh_jpeg_index_workspace_bytes(const hh_jpeg_stream_info *info, int subseq_bytes);
+int hh_jpeg_index_tables(const unsigned char *bytes, long long len, int mcus_per_segment, unsigned char *out, long long out_bytes, int *nseg);
+int hh_jpeg_index_device_batch(unsigned char *batch_base, const hh_jpeg_dec_desc *descs_dev, const hh_jpeg_dec_desc *descs_host,
+                               const hh_jpeg_stream_info *infos_host, int n, int mcus_per_segment, int subseq_bytes, unsigned char *workspace,
+                               long long workspace_bytes, int32_t *status_dev, void *stream);
+int hh_debug_jpeg_index_sync_host(const unsigned char *bytes, long long len, int mcus_per_segment, int subseq_bytes, int lanes,
+                                  hh_jpeg_segment *entries, int capacity, int *n, int *status, long long counts[6]);
 /* COCO keypoint scoring on the device: computeOks + evaluateImg of pycocotools' COCOeval(iouType="keypoints") as keypoints/coco_eval.py
  * restates them (`_oks`, `_evaluate_img`; the `eval_coco` step of keypoints/bin/eval.py:52-65), for every image, area range and threshold
  * in ONE launch over packed tables.  What is pinned is "device = this repository's host evaluator"; parity with pycocotools itself stays

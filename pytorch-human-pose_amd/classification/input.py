@@ -198,6 +198,9 @@ class ClsInput:
         for b, ((img, _), p) in enumerate(zip(samples, params)):
             if not isinstance(img, jp.JpegImage) and (not isinstance(img, np.ndarray) or img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3):
                 raise ValueError("ClsInput.build: uint8 [h,w,3] images (or jpeg.JpegImage) only")
+            if isinstance(img, jp.JpegImage) and img.device_index:
+                raise ValueError("ClsInput.build: a device-indexed JpegImage (index='device') is refused: the crop's window needs the offsets on "
+                                 "the host, and training files come back every epoch (jpeg.JpegIndexCache)")
             q = self.window(img.shape[0], img.shape[1], p)
             # only the source rectangle is staged and shipped (a slice would silently clip a rectangle that leaves the image)
             if q.height <= 0 or q.width <= 0 or q.top < 0 or q.left < 0 or q.top + q.height > img.shape[0] or q.left + q.width > img.shape[1]:

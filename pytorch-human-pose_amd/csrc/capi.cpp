@@ -588,6 +588,87 @@ int hh_jpeg_decode_u8_batch(unsigned char *batch_base, const hh_jpeg_dec_desc *d
     return jpeg_decode_batch("hh_jpeg_decode_u8_batch", false, batch_base, descs_dev, descs_host, infos_host, n, workspace, workspace_bytes, status_dev, stream);
 }
 
+// The index built on the device (jpeg_index.hip; the rule: hh_jpeg_index_device_batch in include/hhrnet.h).
+int hh_jpeg_index_config(int out[4])
+{
+    if (!out) { hh_set_error("hh_jpeg_index_config: null pointer"); return 1; }
+    out[0] = JPEG_IDX_LANES, out[1] = JPEG_IDX_SUBSEQ, out[2] = JPEG_IDX_SUBSEQ_MIN, out[3] = JPEG_IDX_MPS;
+    return 0;
+}
+
+long long hh_jpeg_index_workspace_bytes(const hh_jpeg_stream_info *info, int subseq_bytes)
+{
+    const char *why = info ? jpeg_dec_check_info(*info) : "null pointer";
+    if (!why) why = jpeg_idx_check_params(1, subseq_bytes);
+    if (why) { hh_set_error(std::string("hh_jpeg_index_workspace_bytes: ") + why); return -1; }
+    return 0;  // (a round's states live in LDS, what it hands on in registers: see the header)
+}
+
+int hh_jpeg_index_tables(const unsigned char *bytes, long long len, int mcus_per_segment, unsigned char *out, long long out_bytes, int *nseg)
+{
+    const std::string fn = "hh_jpeg_index_tables";
+    if (!bytes || !out || !nseg) { hh_set_error(fn + ": null pointer"); return 1; }
+    JpegStreamInfo I;
+    std::vector<JpegDecTables> T(1);
+    const char *why = jpeg_dec_parse(bytes, len, &I, &T[0]);
+    if (!why && mcus_per_segment < 1) why = "mcus_per_segment must be at least 1";
+    if (!why && I.restart_interval) why = "the stream has a restart interval (use hh_jpeg_restart_segments)";
+    const int n = why ? 0 : jpeg_dec_index_count(I, mcus_per_segment);
+    if (!why && out_bytes < jpeg_dec_tables_bytes(n)) why = "room below hh_jpeg_decode_tables_bytes";
+    if (!why && (uintptr_t)(out + JPEG_DEC_SEGS_AT) % alignof(JpegSegment)) why = "the table block must be 4-byte aligned";
+    if (why) { hh_set_error(fn + ": " + why); return 1; }
+    I.reserved[1] = JPEG_IDX_PENDING;
+    memcpy(out, &I, sizeof(I));
+    memcpy(out + JPEG_DEC_TABLES_AT, &T[0], sizeof(JpegDecTables));
+    jpeg_idx_blank(I, mcus_per_segment, reinterpret_cast<JpegSegment *>(out + JPEG_DEC_SEGS_AT), n);
+    *nseg = n;
+    return 0;
+}
+
+int hh_jpeg_index_device_batch(unsigned char *batch_base, const hh_jpeg_dec_desc *descs_dev, const hh_jpeg_dec_desc *descs_host,
+                               const hh_jpeg_stream_info *infos_host, int n, int mcus_per_segment, int subseq_bytes, unsigned char *workspace,
+                               long long workspace_bytes, int32_t *status_dev, void *stream)
+{
+    const std::string fn = "hh_jpeg_index_device_batch";
+    (void)workspace;  // (no global scratch: hh_jpeg_index_workspace_bytes is 0)
+    if (!batch_base || !descs_dev || !descs_host || !infos_host || !status_dev) { hh_set_error(fn + ": null pointer"); return 1; }
+    if (n < 1 || n > 65535) { hh_set_error(fn + ": need 1 <= n <= 65535"); return 1; }
+    if ((uintptr_t)descs_dev % 8 || (uintptr_t)status_dev % 4) { hh_set_error(fn + ": descs_dev must be 8-byte and status_dev 4-byte aligned"); return 1; }
+    const char *bad = jpeg_idx_check_params(mcus_per_segment, subseq_bytes);
+    if (!bad && workspace_bytes < 0) bad = "workspace_bytes is negative";
+    if (bad) { hh_set_error(fn + ": " + bad); return 1; }
+    bool any = false;
+    for (int b = 0; b < n; ++b) {
+        const JpegDecDesc &d = descs_host[b];
+        const JpegStreamInfo &I = infos_host[b];
+        JpegDecGeom g;
+        const char *why = jpeg_dec_check_image(batch_base, d, I, nullptr, 1ll << 62, &g);  // (the decode's workspace is the decode's to check)
+        const bool pending = !why && !I.restart_interval && I.reserved[1] == JPEG_IDX_PENDING;
+        if (pending && d.nseg != jpeg_dec_index_count(I, mcus_per_segment)) why = "nseg is not the entry count of mcus_per_segment (hh_jpeg_index_tables)";
+        if (why) { hh_set_error(fn + ": image " + std::to_string(b) + ": " + why); return 1; }
+        any = any || pending;
+    }
+    HH_CHECK_HIP(hipMemsetAsync(status_dev, 0, (size_t)n * 4, (hipStream_t)stream));
+    if (any) HH_CHECK_HIP(launch_jpeg_index(batch_base, descs_dev, n, mcus_per_segment, subseq_bytes, status_dev, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_debug_jpeg_index_sync_host(const unsigned char *bytes, long long len, int mcus_per_segment, int subseq_bytes, int lanes, hh_jpeg_segment *entries,
+                                  int capacity, int *n, int *status, long long counts[6])
+{
+    const std::string fn = "hh_debug_jpeg_index_sync_host";
+    if (!bytes || !entries || !n) { hh_set_error(fn + ": null pointer"); return 1; }
+    JpegStreamInfo I;
+    std::vector<JpegDecTables> T(1);
+    const char *why = jpeg_dec_parse(bytes, len, &I, &T[0]);
+    int st = 0;
+    if (status) *status = 0;
+    if (!why) why = jpeg_idx_sync_host(bytes, len, I, T[0], mcus_per_segment, subseq_bytes, lanes, entries, capacity, n, &st, reinterpret_cast<JpegIdxCounts *>(counts));
+    if (status) *status = st;
+    if (why) { hh_set_error(fn + ": " + why + (st ? std::string(": ") + JPEG_STATUS_NAME[st] : std::string())); return 1; }
+    return 0;
+}
+
 // The segments of a stream when the caller gave none: its restart intervals, or the whole scan as one segment (no index is needed for
 // a single lane).
 static const char *jpeg_own_segments(const unsigned char *bytes, const JpegStreamInfo &I, std::vector<JpegSegment> &own)

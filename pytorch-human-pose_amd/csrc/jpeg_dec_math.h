@@ -9,6 +9,7 @@
 #define HH_JPEG_DEC_MATH_H
 #include <stdint.h>
 #include <string.h>
+#include <vector>  // (the host twin of the index, jpeg_idx_sync_host)
 
 #if defined(__HIPCC__)
 #define HH_JDHD __host__ __device__ __forceinline__
@@ -162,6 +163,25 @@ struct JpegBits {
     HH_JDHD bool starved() const { return n < fake; }  // bits that are not there were consumed
     HH_JDHD int real() const { return n - fake; }      // unread bits of the stream in the buffer
 };
+
+// The canonical position of a reader that is not starved: the byte that holds the next unread bit and that bit's index in it, found by
+// going back from the reader's position over the unread bits.  An FF 00 pair is one byte and the position points at its FF.  `floor`:
+// where the reader began (no byte before it is looked at).
+HH_JDHD void jpeg_bits_where(const JpegBits &br, int floor, int &p, int &bit)
+{
+    int unread = br.real();
+    p = br.pos;
+    while (unread >= 8) {  // a whole data byte back: FF 00 is one
+        --p;
+        if (br.p[p] == 0 && p > floor && br.p[p - 1] == 0xff) --p;
+        unread -= 8;
+    }
+    if (unread) {
+        --p;
+        if (br.p[p] == 0 && p > floor && br.p[p - 1] == 0xff) --p;
+    }
+    bit = unread ? 8 - unread : 0;
+}
 
 // -> the symbol, or -1 for a code no table entry has.  Needs 16 bits in the buffer.
 HH_JDHD int jpeg_dec_symbol(JpegBits &br, const JpegHuff &H)
@@ -683,17 +703,9 @@ inline const char *jpeg_dec_index(const unsigned char *b, long long len, const J
                 return "the scan cannot be walked";
             }
             if (!tail) {
-                int unread = br.real(), p = br.pos;
-                while (unread >= 8) {  // a whole data byte back: FF 00 is one
-                    --p;
-                    if (b[p] == 0 && p > walk.byte_offset && b[p - 1] == 0xff) --p;
-                    unread -= 8;
-                }
-                if (unread) {
-                    --p;
-                    if (b[p] == 0 && p > walk.byte_offset && b[p - 1] == 0xff) --p;
-                }
-                walk.byte_offset = p, walk.bit_offset = unread ? 8 - unread : 0;
+                int p, bit;
+                jpeg_bits_where(br, walk.byte_offset, p, bit);
+                walk.byte_offset = p, walk.bit_offset = bit;
                 walk.first_mcu += walk.mcu_count;
             }
         }
@@ -800,5 +812,197 @@ inline int jpeg_dec_window_host(const unsigned char *slice, int slice_len, const
         counts->stream_bytes += slice_len;
     }
     return status;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the device index
+// The index of a restart-less stream without a sequential Huffman pass (the rule: hh_jpeg_index_device_batch in include/hhrnet.h).  The
+// scan's bytes [S, E) are cut into subsequences of B bytes, one lane each.  What lanes hand to each other is a state at a block
+// boundary, packed into one word: the canonical byte position (jpeg_bits_where) << 6 | the bit in that byte << 3 | the block's index
+// in its MCU.  jpeg_idx_walk is one lane's walk, written once for the host and the device; how the lanes of a round wait for each
+// other differs (loops in jpeg_idx_sync_host below, barriers in jpeg_index.hip).
+enum { JPEG_IDX_LANES = 1024, JPEG_IDX_SUBSEQ = 32, JPEG_IDX_SUBSEQ_MIN = 4, JPEG_IDX_MPS = 2 };
+enum { JPEG_IDX_PENDING = 1 };  // info.reserved[1] of a table block whose entries the device is to fill (hh_jpeg_index_tables)
+typedef unsigned long long JpegIdxKey;
+static constexpr JpegIdxKey JPEG_IDX_NONE = ~0ull;  // no state: the walk met an error or ran out of blocks
+HH_JDHD JpegIdxKey jpeg_idx_key(int p, int bit, int j) { return (JpegIdxKey)(uint32_t)p << 6 | (JpegIdxKey)(uint32_t)bit << 3 | (JpegIdxKey)(uint32_t)j; }
+
+struct JpegIdxLane {
+    JpegIdxKey exit;  // the first boundary at or past `limit`, or JPEG_IDX_NONE
+    uint32_t count;   // whole blocks decoded
+    uint32_t dc[3];   // the sums of their DC differences per component (uint32 wrap, as jpeg_dec_block adds them)
+    int status;       // what stopped the walk (reported by the last walk only)
+};
+
+// The scan's bytes as the index walks them, and how many subsequences of B bytes they make (at least one: lane 0 always walks).
+HH_JDHD int jpeg_idx_scan_end(const JpegStreamInfo &I, long long length) { return (int)(I.scan_end < length ? I.scan_end : length); }
+HH_JDHD long long jpeg_idx_subsequences(const JpegStreamInfo &I, long long length, int B)
+{
+    const long long bytes = (long long)jpeg_idx_scan_end(I, length) - I.scan_offset;
+    return bytes > 0 ? (bytes + B - 1) / B : 1;
+}
+// Where lane k >= 1 begins before it knows better: the first data bit of its subsequence (a 00 behind an FF belongs to that FF), at a
+// block boundary, block 0 of an MCU.  S + k B < E, and S + k B - 1 >= S: both bytes lie in the scan.
+HH_JDHD JpegIdxKey jpeg_idx_guess(const unsigned char *b, const JpegStreamInfo &I, long long k, int B)
+{
+    int p = (int)(I.scan_offset + k * B);
+    if (b[p] == 0 && b[p - 1] == 0xff) p += 1;
+    return jpeg_idx_key(p, 0, 0);
+}
+// One past the last byte of subsequence k: the start of the next one, or no limit for the last.
+HH_JDHD int jpeg_idx_limit(const JpegStreamInfo &I, long long nsub, long long k, int B) { return k + 1 < nsub ? (int)(I.scan_offset + (k + 1) * B) : INT32_MAX; }
+
+// One lane: whole blocks from the state `from` up to the first boundary whose canonical byte is at or past `limit`, but no further
+// than block `total` of the image, the walk's first block being block g0 (a speculative lane does not know its g0: 0, which makes
+// `total` a plain bound on its loop).  EMIT (the last walk, from a verified state, with the true g0 and the DC sums `dcpre` of all
+// blocks before g0): the entry of every boundary in front of a block g with g % (mps bpm) == 0 is written, if it lies below nseg.
+// Every byte read lies in [from's byte, E) of the stream; every entry written below seg + nseg; the loop ends after at most
+// total - g0 blocks.
+template <bool EMIT>
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline void jpeg_idx_walk(const unsigned char *b, int E, const JpegStreamInfo &I, const JpegHuff *huff, JpegIdxKey from, int limit, long long g0, long long total,
+                          int mps, const uint32_t *dcpre, JpegSegment *seg, int nseg, JpegIdxLane &out)
+{
+    const int start = (int)(from >> 6);
+    int cp = start, cb = (int)(from >> 3) & 7, j = (int)from & 7;
+    out.exit = JPEG_IDX_NONE, out.count = 0, out.dc[0] = out.dc[1] = out.dc[2] = 0, out.status = JPEG_ST_OK;
+    if (j >= I.bpm) return;  // (no state a walk hands on)
+    JpegBits br;
+    br.init(b, start, E);
+    br.refill();
+    br.drop(cb);
+    int pred[3] = {0, 0, 0};
+    const long long period = (long long)mps * I.bpm, nmcu = (long long)I.mcols * I.mrows;
+    long long phase = EMIT ? g0 % period : 0, entry = EMIT ? g0 / period : 0;
+    bool known = true;  // (cp, cb) is the position of the boundary in front of the next block
+#pragma unroll 1
+    for (long long g = g0;; ++g) {
+        const bool emit = EMIT && phase == 0 && g < total;
+        if (!known && (emit || br.pos >= limit)) jpeg_bits_where(br, start, cp, cb), known = true;  // (the canonical byte is never behind br.pos)
+        if (known && cp >= limit) {
+            out.exit = jpeg_idx_key(cp, cb, j);
+            return;
+        }
+        if (g >= total) return;
+        if (emit && entry < nseg) {
+            JpegSegment e;
+            e.first_mcu = (int32_t)(entry * mps);
+            e.mcu_count = (int32_t)(nmcu - entry * mps < mps ? nmcu - entry * mps : mps);
+            e.byte_offset = cp, e.bit_offset = cb;
+            for (int c = 0; c < 3; ++c) e.pred[c] = (int32_t)(dcpre[c] + (uint32_t)pred[c]);
+            e.byte_end = (int32_t)(I.scan_end << 1);
+            seg[entry] = e;
+        }
+        const int c = jpeg_dec_block_comp(I, j);
+        const int st = jpeg_dec_block<false>(br, huff[I.dc[c] & 3], huff[4 + (I.ac[c] & 3)], pred[c], nullptr);
+        if (st) {
+            out.status = st;
+            return;
+        }
+        out.count += 1, out.dc[c] = (uint32_t)pred[c];
+        j = j + 1 == I.bpm ? 0 : j + 1;
+        known = false;
+        if (EMIT && ++phase == period) phase = 0, ++entry;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host only, index
+// The entries as hh_jpeg_index_tables ships them: first_mcu / mcu_count filled, offsets and predictors zero.
+inline void jpeg_idx_blank(const JpegStreamInfo &I, int mps, JpegSegment *seg, int n)
+{
+    const long long nmcu = (long long)I.mcols * I.mrows;
+    memset(seg, 0, (size_t)n * sizeof(JpegSegment));
+    for (long long i = 0; i < n; ++i) seg[i].first_mcu = (int32_t)(i * mps), seg[i].mcu_count = (int32_t)(nmcu - i * mps < mps ? nmcu - i * mps : mps);
+}
+
+inline const char *jpeg_idx_check_params(int mps, int B)
+{
+    if (mps < 1) return "mcus_per_segment must be at least 1";
+    if (B < JPEG_IDX_SUBSEQ_MIN) return "subseq_bytes below the minimum (hh_jpeg_index_config)";
+    if (B % 4) return "subseq_bytes must be a multiple of 4";
+    return nullptr;
+}
+
+// What hh_debug_jpeg_index_sync_host reports, in the order of its counts[6].
+struct JpegIdxCounts {
+    long long rounds, iterations, iterations_worst, subsequences, blocks_decoded, blocks_true;
+};
+static_assert(sizeof(JpegIdxCounts) == 48, "counts[6]");
+// The kernel's procedure in plain loops, `lanes` subsequences per round.  A barrier of the kernel is a loop boundary here; where the
+// kernel's lanes read their predecessors' exits before any of them writes its own, the loop runs from the last lane down.
+inline const char *jpeg_idx_sync_host(const unsigned char *b, long long len, const JpegStreamInfo &I, const JpegDecTables &T, int mps, int B, int lanes,
+                                      JpegSegment *seg, int capacity, int *count, int *status, JpegIdxCounts *counts)
+{
+    *count = 0, *status = 0;
+    JpegIdxCounts local;
+    memset(&local, 0, sizeof(local));
+    if (counts) *counts = local;
+    const char *why = jpeg_idx_check_params(mps, B);
+    if (why) return why;
+    if (lanes < 1 || lanes > (1 << 20)) return "lanes must lie in 1..1048576";
+    if (I.restart_interval) return "the stream has a restart interval (use hh_jpeg_restart_segments)";
+    const int nseg = jpeg_dec_index_count(I, mps);
+    if (nseg > capacity) return "capacity below the number of segments";
+    jpeg_idx_blank(I, mps, seg, nseg);
+    const int E = jpeg_idx_scan_end(I, len);
+    const long long nsub = jpeg_idx_subsequences(I, len, B), total = (long long)I.mcols * I.mrows * I.bpm;
+    local.subsequences = nsub;
+    JpegIdxKey carry = jpeg_idx_key((int)I.scan_offset, 0, 0);  // lane 0 of the stream starts at the true state
+    long long g = 0;
+    uint32_t dc[3] = {0, 0, 0};
+    int st = 0;
+    std::vector<JpegIdxKey> start((size_t)(nsub < lanes ? nsub : lanes));
+    std::vector<JpegIdxLane> lane(start.size());
+    for (long long k0 = 0; k0 < nsub && g < total && carry != JPEG_IDX_NONE; k0 += lanes) {
+        const int n = (int)(nsub - k0 < lanes ? nsub - k0 : lanes);
+        local.rounds += 1;
+        for (int t = 0; t < n; ++t) {
+            start[t] = t == 0 ? carry : jpeg_idx_guess(b, I, k0 + t, B);
+            jpeg_idx_walk<false>(b, E, I, T.huff, start[t], jpeg_idx_limit(I, nsub, k0 + t, B), 0, total, mps, nullptr, nullptr, 0, lane[t]);
+            local.blocks_decoded += lane[t].count;
+        }
+        // lane 0 is true, so after k passes lanes 0..k are: at most n passes
+        long long passes = 0;
+        for (int it = 0; it < n; ++it) {
+            bool changed = false;
+            for (int t = n - 1; t >= 1; --t) {
+                const JpegIdxKey prev = lane[t - 1].exit;
+                if (prev == JPEG_IDX_NONE || prev == start[t]) continue;
+                start[t] = prev, changed = true;
+                jpeg_idx_walk<false>(b, E, I, T.huff, start[t], jpeg_idx_limit(I, nsub, k0 + t, B), 0, total, mps, nullptr, nullptr, 0, lane[t]);
+                local.blocks_decoded += lane[t].count;
+            }
+            if (!changed) break;
+            ++passes;
+        }
+        local.iterations += passes;
+        if (passes > local.iterations_worst) local.iterations_worst = passes;
+        // the last walk: the lanes up to the first one without an exit are on the true chain
+        int bad = n;
+        for (int t = n - 1; t >= 0; --t)
+            if (lane[t].exit == JPEG_IDX_NONE) bad = t;
+        long long gt = g;
+        uint32_t dct[3] = {dc[0], dc[1], dc[2]};
+        for (int t = 0; t < n; ++t) {
+            if (t <= bad && gt < total) {
+                JpegIdxLane last;
+                jpeg_idx_walk<true>(b, E, I, T.huff, start[t], jpeg_idx_limit(I, nsub, k0 + t, B), gt, total, mps, dct, seg, nseg, last);
+                local.blocks_decoded += last.count, local.blocks_true += last.count;
+                if (last.status > st) st = last.status;
+            }
+            gt += lane[t].count;
+            for (int c = 0; c < 3; ++c) dct[c] += lane[t].dc[c];
+        }
+        g = gt, dc[0] = dct[0], dc[1] = dct[1], dc[2] = dct[2];
+        carry = bad < n ? JPEG_IDX_NONE : lane[n - 1].exit;
+    }
+    if (counts) *counts = local;
+    if (st) {
+        *status = st;
+        return "the scan cannot be walked";
+    }
+    *count = nseg;
+    return nullptr;
 }
 #endif

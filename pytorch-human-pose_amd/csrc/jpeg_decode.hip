@@ -43,6 +43,7 @@ __global__ __launch_bounds__(64) void jpeg_dec_entropy_kernel(const unsigned cha
     const int s = (int)blockIdx.x * 64 + (int)threadIdx.x;
     if (s >= d.nseg) return;
     const JpegStreamInfo I = *reinterpret_cast<const JpegStreamInfo *>(tab);
+    if (I.reserved[0]) return;  // (the device index met an error in this stream and left its entries unfinished: jpeg_index.hip)
     const JpegSegment sg = reinterpret_cast<const JpegSegment *>(tab + JPEG_DEC_SEGS_AT)[s];
     const int st = jpeg_dec_segment(base + d.stream_offset, d.stream_length, I, huff, sg, jpeg_win_rect(I, jpeg_desc_window(desc, I)),
                                     reinterpret_cast<int16_t *>(ws + d.ws_offset), nullptr, nullptr);

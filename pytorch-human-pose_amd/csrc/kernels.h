@@ -371,6 +371,9 @@ hipError_t launch_jpeg_encode(unsigned char *base, const hh_jpeg_desc *descs, in
 template <class Desc>
 hipError_t launch_jpeg_decode(unsigned char *base, const Desc *descs, int n, int max_seg, int max_blk, int max_h, int max_w, unsigned char *ws,
                               int32_t *status, hipStream_t s);
+// The index of restart-less streams built on the device (jpeg_index.hip; the rule: hh_jpeg_index_device_batch in include/hhrnet.h): one
+// launch, one workgroup per image, behind the clearing of `status`; it fills the entries of the table blocks that ask for it.
+hipError_t launch_jpeg_index(unsigned char *base, const hh_jpeg_dec_desc *descs, int n, int mps, int subseq_bytes, int32_t *status, hipStream_t s);
 // Heatmap panels (hh_panel_map of include/hhrnet.h; struct and arithmetic in panel_math.h, kernels in panels.hip): the min/max launch
 // (only if any_minmax) and the paint launch of one figure; the same figure on the host; the un-normalise of the model input.
 struct PanelRange;

@@ -10,7 +10,8 @@ batch of mixed streams; the rule is written at that entry point), `JpegImage` is
 array, and `MJPEGReader` reads back what `MJPEGWriter` wrote.  `decode_jpeg_host` is the same rule compiled for the host, for tests.
 With `windows=` / `window=` only a rectangle of each image is decoded (hh_jpeg_decode_window_u8_batch: the same bytes as those rows and
 columns of the whole decode, from the segments and the byte slice that rectangle needs): what `classification.input.ClsInput` does with
-a `JpegImage` sample's crop.
+a `JpegImage` sample's crop.  With `index="device"` the index of a restart-less stream is built on the GPU in front of the decode
+(hh_jpeg_index_device_batch: no Huffman pass on the host; for files that are read once, as in inference and evaluation).
 """
 from __future__ import annotations
 
@@ -262,6 +263,7 @@ class MJPEGWriter:
 # hh_jpeg_stream_info, hh_jpeg_segment, hh_jpeg_dec_desc of include/hhrnet.h
 INFO, SEGMENT, DEC_DESC, WINDOW, WIN_DESC, WIN_COUNTS = (_lib.struct_dtype("hh_jpeg_" + k) for k in (
     "stream_info", "segment", "dec_desc", "window", "win_desc", "window_counts"))
+INDEX_COUNTS = ("rounds", "iterations", "iterations_worst", "subsequences", "blocks_decoded", "blocks_true")  # counts[6] of hh_debug_jpeg_index_sync_host
 STATUS_NAMES = ("ok", "bad Huffman code", "zero run past coefficient 63", "bytes exhausted", "missing or unexpected RSTm", "bad segment")
 
 JpegInfo = collections.namedtuple("JpegInfo", "h w components sampling restart_interval mcu_cols mcu_rows scan_offset scan_end")
@@ -358,23 +360,69 @@ class JpegIndexCache:
         return len(self._entries)
 
 
+def index_config() -> tuple[int, int, int, int]:
+    """hh_jpeg_index_config: (lanes per workgroup, default subseq_bytes, minimum subseq_bytes, default mcus_per_segment) of the index
+    built on the device."""
+    cfg = (C.c_int * 4)()
+    _lib.check(_lib.load().hh_jpeg_index_config(cfg))
+    return tuple(cfg)
+
+
+def index_sync_host(data, mcus_per_segment: int, subseq_bytes: int, lanes: int, capacity: int | None = None) -> tuple[np.ndarray, int, dict]:
+    """hh_debug_jpeg_index_sync_host: the device index's shared code on the host with `lanes` subsequences per round -> (the entries,
+    the status, the counts: rounds, iterations, iterations_worst, subsequences, blocks_decoded, blocks_true).  A stream the last walk
+    cannot walk gives no entries and its status (1 bad code, 2 run past 63, 3 bytes exhausted); every other refusal raises HHError by
+    name (tests, tools/jpeg_index_time.py; needs the library, no GPU)."""
+    a = _bytes_view(data)
+    i = _parse(a)[0]
+    cap = max(_index_count(i, max(int(mcus_per_segment), 1)), 1) if capacity is None else int(capacity)
+    entries = np.zeros(max(cap, 1), SEGMENT)
+    n, status = C.c_int(0), C.c_int(0)
+    counts = np.zeros(len(INDEX_COUNTS), np.int64)
+    rc = _lib.load().hh_debug_jpeg_index_sync_host(a.ctypes.data, a.size, int(mcus_per_segment), int(subseq_bytes), int(lanes), entries.ctypes.data, cap,
+                                                   C.byref(n), C.byref(status), counts.ctypes.data)
+    if rc and not status.value:
+        _lib.check(rc)
+    return entries[:n.value], status.value, dict(zip(INDEX_COUNTS, (int(v) for v in counts)))
+
+
 class JpegImage:
     """A compressed image where `TrainInput.build` takes a pixel array: the stream's bytes with `.h`, `.w`, `.shape`, `.dtype` and `.ndim`
     of the uint8 [h,w,3] array it decodes to.  The header is parsed here (a stream the decoder does not take is refused by name), the
-    segments are the supplied `index`, else the stream's restart intervals, else an index built (and so validated) here."""
+    segments are the supplied `index`, else the stream's restart intervals, else an index built (and so validated) here.
+    `index="device"`: no Huffman pass on the host; the entries (one every `mcus_per_segment` MCUs, default index_config()[3]) are filled
+    on the GPU by hh_jpeg_index_device_batch in front of the decode (`decode_jpeg_device`, `InferenceKeypointsModel.infer_images`).
+    `.segments` is None and `.device_index` True.  A stream with DRI given index="device" silently keeps its restart segments (a byte
+    scan, no Huffman work either; `.device_index` is False).  A device-indexed image has no offsets on the host: a window decode,
+    `TrainInput.build` and `ClsInput.build` refuse it by name (their files come back every epoch: JpegIndexCache)."""
 
     dtype = np.dtype(np.uint8)
     ndim = 3
 
-    def __init__(self, data, index=None):
+    def __init__(self, data, index=None, mcus_per_segment: int | None = None):
         self.data = _bytes_view(data)
         self.info = _parse(self.data)
-        self.segments = _segments(self.data, self.info[0], index)
+        self.device_index = False
+        self.mcus_per_segment = None
+        if isinstance(index, str):
+            if index != "device":
+                raise ValueError(f"JpegImage: index {index!r} is not 'device', None or a build_jpeg_index result")
+            mps = index_config()[3] if mcus_per_segment is None else int(mcus_per_segment)
+            if mps < 1:
+                raise ValueError("JpegImage: mcus_per_segment must be at least 1")
+            index = None
+            if not int(self.info[0]["restart_interval"]):
+                self.device_index, self.mcus_per_segment = True, mps
+                self.info["reserved"][0][1] = 1  # (what hh_jpeg_index_tables writes: the device is to fill the entries)
+        elif mcus_per_segment is not None:
+            raise ValueError("JpegImage: mcus_per_segment belongs to index='device' (a host index is cut by build_jpeg_index)")
+        self.segments = None if self.device_index else _segments(self.data, self.info[0], index)
+        self.nseg = _index_count(self.info[0], self.mcus_per_segment) if self.device_index else len(self.segments)
         self.h, self.w = int(self.info[0]["h"]), int(self.info[0]["w"])
         self.shape = (self.h, self.w, 3)
         lib = _lib.load()
         self.ws_bytes = int(lib.hh_jpeg_decode_workspace_bytes(self.info.ctypes.data))
-        self.tables_bytes = int(lib.hh_jpeg_decode_tables_bytes(self.info.ctypes.data, len(self.segments)))
+        self.tables_bytes = int(lib.hh_jpeg_decode_tables_bytes(self.info.ctypes.data, self.nseg))
         if self.ws_bytes < 0 or self.tables_bytes < 0:
             _lib.check(1)
 
@@ -383,10 +431,16 @@ class JpegImage:
         return _align(self.data.size, 16) + _align(self.tables_bytes, 16)
 
     def stage(self, hview: np.ndarray, at: int) -> tuple[int, int]:
-        """Stream and table block into the staging bytes at `at` (a multiple of 16) -> (stream offset, tables offset)."""
+        """Stream and table block into the staging bytes at `at` (a multiple of 16) -> (stream offset, tables offset).  A device-indexed
+        image's block comes from hh_jpeg_index_tables: its entries are blank but for first_mcu / mcu_count."""
         tables_at = at + _align(self.data.size, 16)
         hview[at:at + self.data.size] = self.data
         out = hview[tables_at:tables_at + self.tables_bytes]
+        if self.device_index:
+            n = C.c_int(0)
+            _lib.check(_lib.load().hh_jpeg_index_tables(self.data.ctypes.data, self.data.size, self.mcus_per_segment, out.ctypes.data, self.tables_bytes,
+                                                        C.byref(n)))
+            return at, tables_at
         _lib.check(_lib.load().hh_jpeg_decode_tables(self.data.ctypes.data, self.data.size, self.segments.ctypes.data, len(self.segments),
                                                      out.ctypes.data, self.tables_bytes))
         return at, tables_at
@@ -394,6 +448,8 @@ class JpegImage:
     def window_plan(self, window) -> WindowPlan:
         """hh_jpeg_decode_window_select for (top, left, height, width): the segments with an MCU in the window's MCU rectangle, the byte
         slice they need, the table block's and the workspace's size.  A window that is empty or leaves the image is refused by name."""
+        if self.device_index:
+            raise ValueError("a window decode needs the segments' offsets on the host: a device-indexed JpegImage (index='device') has none")
         lib = _lib.load()
         w = _window(window)
         nsel, sl = C.c_int(0), (C.c_longlong * 2)()
@@ -426,7 +482,7 @@ class JpegImage:
 
     def whole_plan(self) -> WindowPlan:
         """The record `window_plan` gives, for the whole-image entry: every segment, the whole stream, the MCU grid's workspace."""
-        return WindowPlan((0, 0, self.h, self.w), len(self.segments), (0, self.data.size), self.tables_bytes, self.ws_bytes, self.staged_bytes())
+        return WindowPlan((0, 0, self.h, self.w), self.nseg, (0, self.data.size), self.tables_bytes, self.ws_bytes, self.staged_bytes())
 
     def stage_plan(self, hview: np.ndarray, at: int, plan: WindowPlan, windowed: bool) -> tuple[int, int, np.ndarray]:
         """`stage` (a `whole_plan`) or `stage_window` -> (stream offset, tables offset, the info the library validates the image by)."""
@@ -455,7 +511,25 @@ def raise_status(statuses, what: str = "hh_jpeg_decode_u8_batch") -> None:
         raise _lib.HHError(f"{what}: image {i}: status {s} ({name})" + (f"; also images {[j for j, _ in bad[1:]]}" if len(bad) > 1 else ""))
 
 
-def decode_jpeg_device(streams: list, index=None, bgr=False, device=None, out=None, windows=None) -> list:
+def launch_index(dev, base: int, descs_dev: int, descs: np.ndarray, infos: np.ndarray, mcus_per_segment: int, subseq_bytes: int | None,
+                 status_dev: int) -> None:
+    """hh_jpeg_index_device_batch on the current stream of `dev`, in front of `launch_decode` with the same rows: one launch behind the
+    clearing of its own statuses; it fills the entries of the device-indexed images' table blocks and skips the others."""
+    sub = index_config()[1] if subseq_bytes is None else int(subseq_bytes)
+    _lib.launch(dev, _lib.load().hh_jpeg_index_device_batch, base, descs_dev, descs.ctypes.data, infos.ctypes.data, len(descs), int(mcus_per_segment), sub,
+                None, 0, status_dev)
+
+
+def index_mcus_per_segment(items: list, what: str):
+    """The one mcus_per_segment of the device-indexed images of a batch (one index call serves them all), or None without any."""
+    sizes = {it.mcus_per_segment for it in items if it.device_index}
+    if len(sizes) > 1:
+        raise ValueError(f"{what}: the device-indexed images of one batch must share one mcus_per_segment, got {sorted(sizes)}")
+    return next(iter(sizes), None)
+
+
+def decode_jpeg_device(streams: list, index=None, bgr=False, device=None, out=None, windows=None, mcus_per_segment: int | None = None,
+                       subseq_bytes: int | None = None, entries_out: list | None = None) -> list:
     """One hh_jpeg_decode_u8_batch, on the current stream, for a batch of JPEG streams (bytes, uint8 arrays or JpegImage) of mixed sizes,
     samplings and tables -> one uint8 [h,w,3] device tensor per stream, R,G,B or (`bgr`: one value or one per stream) B,G,R.  `index`:
     None, or one entry per stream (None or a build_jpeg_index result); a stream without DRI and without an index has its index built
@@ -465,7 +539,14 @@ def decode_jpeg_device(streams: list, index=None, bgr=False, device=None, out=No
     bytes of the last call (the statuses also when it raises).
     `windows`: None, or one entry per stream, (top, left, height, width) or None (the whole image).  With any window given the call is
     ONE hh_jpeg_decode_window_u8_batch: only the segments that hold an MCU of a window's MCU rectangle and the byte slice they need
-    cross the bus, only the window is turned into pixels, and that stream's tensor (and `out` entry) is [height, width, 3]."""
+    cross the bus, only the window is turned into pixels, and that stream's tensor (and `out` entry) is [height, width, 3].
+    `index="device"` (or "device" as a stream's entry of the list): the stream's index is built on the GPU, with no Huffman pass on the
+    host: ONE hh_jpeg_index_device_batch in front of the decode call, on the same stream with the same descriptors, fills the entries
+    (one every `mcus_per_segment` MCUs, default index_config()[3]; subsequences of `subseq_bytes`, default index_config()[1]) of
+    the images that need it; host-indexed, DRI (which keep their restart segments) and device-indexed streams mix freely.
+    `last_status` is then the larger of the two calls' codes per image.  A window of a device-indexed stream is refused by name
+    (ValueError): selecting its segments needs the offsets on the host.  `entries_out`: a list that receives, per stream, the SEGMENT
+    rows of its table block as the device holds them after the call (one more device-to-host copy; tests and tools)."""
     n = len(streams)
     if n == 0:
         return []
@@ -474,9 +555,13 @@ def decode_jpeg_device(streams: list, index=None, bgr=False, device=None, out=No
     windowed = windows is not None and any(w is not None for w in windows)
     desc_t, entry = (WIN_DESC, "hh_jpeg_decode_window_u8_batch") if windowed else (DEC_DESC, "hh_jpeg_decode_u8_batch")
     idx = _per_frame(index, n) if isinstance(index, (list, tuple)) else [index] * n
-    if index is not None and not isinstance(index, (list, tuple)) and n != 1:
+    if index is not None and not isinstance(index, (list, tuple, str)) and n != 1:
         raise ValueError("decode_jpeg_device: `index` is a list with one entry per stream")
-    items = [s if isinstance(s, JpegImage) else JpegImage(s, i) for s, i in zip(streams, idx)]
+    items = [s if isinstance(s, JpegImage) else JpegImage(s, i, mcus_per_segment if isinstance(i, str) else None) for s, i in zip(streams, idx)]
+    index_mps = index_mcus_per_segment(items, "decode_jpeg_device")
+    if windowed and index_mps is not None:
+        raise ValueError("decode_jpeg_device: a window decode needs the segments' offsets on the host: `windows` with a device-indexed stream "
+                         "(index='device') is refused")
     # one plan per stream: without any window the whole stream and every segment, else the slice and the segments of its window
     plans = [it.window_plan((0, 0, it.h, it.w) if w is None else w) for it, w in zip(items, windows)] if windowed else [it.whole_plan() for it in items]
     bgrs = _per_frame(bgr, n)
@@ -488,7 +573,7 @@ def decode_jpeg_device(streams: list, index=None, bgr=False, device=None, out=No
         at += p.staged_bytes
     upload = at
     status_at = _align(at, 16)
-    at = status_at + 4 * n
+    at = status_at + 4 * n * 2  # (the decode's statuses, then the index call's)
     dst_at = []
     for p in plans:
         at = _align(at, 16)
@@ -510,21 +595,34 @@ def decode_jpeg_device(streams: list, index=None, bgr=False, device=None, out=No
                 raise ValueError("a destination must be a uint8 [height,width,3] device tensor (or a row-pitched view of one) of the stream's or its window's size")
     base = min([buf.data_ptr()] + ([o.data_ptr() for o in out] if out is not None else []))
     rel = buf.data_ptr() - base
-    infos = []
+    infos, tables_places = [], []
     for j, (it, p) in enumerate(zip(items, plans)):
         stream_at, tables_at, info = it.stage_plan(hv, places[j], p, windowed)
         infos.append(info)
+        tables_places.append(tables_at)
         dst = rel + dst_at[j] if out is None else out[j].data_ptr() - base
         pitch = 3 * p.window[3] if out is None else int(out[j].stride(0))
         row = it.window_desc(p, rel + stream_at, rel + tables_at, dst, int(ws_at[j]), pitch, bgrs[j])
         descs[j] = row if windowed else row[0]  # (DEC_DESC: no window)
     buf[:upload].copy_(host, non_blocking=True)
-    launch_decode(device, base, buf.data_ptr(), descs, np.concatenate(infos), work, buf.data_ptr() + status_at, entry)
-    status_host = torch.empty(n, dtype=torch.int32, pin_memory=True)
-    status_host.copy_(buf[status_at:status_at + 4 * n].view(torch.int32), non_blocking=True)
+    infos = np.concatenate(infos)
+    ncalls = 1
+    if index_mps is not None:
+        launch_index(device, base, buf.data_ptr(), descs, infos, index_mps, subseq_bytes, buf.data_ptr() + status_at + 4 * n)
+        ncalls = 2
+    launch_decode(device, base, buf.data_ptr(), descs, infos, work, buf.data_ptr() + status_at, entry)
+    status_host = torch.empty(n * ncalls, dtype=torch.int32, pin_memory=True)
+    status_host.copy_(buf[status_at:status_at + 4 * n * ncalls].view(torch.int32), non_blocking=True)
+    if entries_out is not None:
+        spans = [(rel_at + it.tables_bytes - SEGMENT.itemsize * p.nsel, SEGMENT.itemsize * p.nsel) for rel_at, it, p in zip(tables_places, items, plans)]
+        packed = torch.cat([buf[o:o + ln] for o, ln in spans]).cpu().numpy() if not windowed else None
     torch.cuda.current_stream(device).synchronize()
-    decode_jpeg_device.last_h2d_bytes, decode_jpeg_device.last_status = upload, status_host.numpy().copy()
-    raise_status(status_host.numpy(), entry)
+    statuses = status_host.numpy().reshape(ncalls, n).max(axis=0)
+    decode_jpeg_device.last_h2d_bytes, decode_jpeg_device.last_status = upload, statuses.copy()
+    if entries_out is not None and packed is not None:
+        ends = np.cumsum([0] + [ln for _, ln in spans])
+        entries_out[:] = [packed[int(ends[j]):int(ends[j + 1])].view(SEGMENT).copy() for j in range(n)]
+    raise_status(statuses, "hh_jpeg_index_device_batch + " + entry if index_mps is not None else entry)
     if out is not None:
         return list(out)
     return [buf[o:o + p.window[2] * p.window[3] * 3].view(p.window[2], p.window[3], 3) for o, p in zip(dst_at, plans)]
@@ -557,12 +655,17 @@ def decode_jpeg_host(data, bgr: bool = False, index=None, pitch: int | None = No
     return np.ascontiguousarray(out[:, :3 * ww]).reshape(hh, ww, 3)
 
 
-def load_jpeg(path, device=None, cache: JpegIndexCache | None = None, bgr: bool = False, window=None):
+def load_jpeg(path, device=None, cache: JpegIndexCache | None = None, bgr: bool = False, window=None, index=None, mcus_per_segment: int | None = None):
     """`np.array(Image.open(path).convert("RGB"))` with the pixels formed on the device -> uint8 [h,w,3] device tensor.  `cache`: a
     JpegIndexCache that keeps the file's index from call to call.  `window` (top, left, height, width): only that rectangle is decoded
-    -> uint8 [height,width,3]."""
+    -> uint8 [height,width,3].  `index="device"`: the file's index is built on the GPU in front of the decode (no Huffman pass on the
+    host; for a file that is read once), one entry every `mcus_per_segment` MCUs; with it a `cache` or a `window` is refused (ValueError)."""
     with open(path, "rb") as f:
         data = f.read()
+    if index is not None:
+        if index != "device" or cache is not None or window is not None:
+            raise ValueError("load_jpeg: `index` is None or 'device', and 'device' goes with neither a cache nor a window (they need the offsets on the host)")
+        return decode_jpeg_device([data], "device", bgr, device, mcus_per_segment=mcus_per_segment)[0]
     index = None
     if cache is not None and not jpeg_info(data).restart_interval:
         index = cache.get(path, data)

@@ -324,7 +324,11 @@ class InferenceKeypointsModel:
         """prepare_input for one entry of a multi-scale test (get_multi_scale_size, base/transforms/utils.py:60-86)."""
         size, center, scale = get_multi_scale_size(image, self.input_size, current_scale, min_scale)
         m = dst_to_src_matrix(center, scale, size)  # destination -> source, as cv2.warpAffine inverts the forward matrix
-        raw = torch.from_numpy(np.ascontiguousarray(image, dtype=np.uint8)).to(self.device)
+        if hasattr(image, "stage"):  # a jpeg.JpegImage: only its bytes cross, its pixels are formed on the device (a bad stream raises)
+            from .jpeg import decode_jpeg_device
+            raw = decode_jpeg_device([image], device=self.device)[0]
+        else:
+            raw = torch.from_numpy(np.ascontiguousarray(image, dtype=np.uint8)).to(self.device)
         x = torch.empty((1, 3, size[1], size[0]), device=self.device, dtype=torch.float32)
         _lib.launch(x.device, self._lib.hh_preprocess_u8, raw.data_ptr(), image.shape[0], image.shape[1], m.ctypes.data, x.data_ptr(),
                     size[1], size[0], IMAGENET_MEAN.ctypes.data, IMAGENET_STD.ctypes.data)
@@ -498,15 +502,29 @@ class InferenceKeypointsModel:
         chunks are fed in order, each as one hh_track_step behind its hh_decode on the same stream with frames_per_stream = the chunk
         length; ids and smoothed coordinates come back in the batch's one device->host hand-over.  Every result gains `.track_ids`
         (int32 [P], 0 = no track) and `.kpts_coords_smooth` ([P,K,2], raw-image pixels), aligned with its rows.  With tracker=None
-        nothing of the pipeline changes."""
+        nothing of the pipeline changes.
+        An entry of `raw_images` may also be the `bytes` / `bytearray` / `memoryview` of a JPEG file or a `jpeg.JpegImage`, mixed freely
+        with arrays; bytes become `JpegImage(data, index="device")`: no Huffman pass and no pixel array on the host.  Bucketing reads
+        `.shape`.  The stream and table block of such an image travel in the batch's one pinned copy, behind the image descriptors; its
+        pixel slot lies behind the uploaded bytes in the same device buffer; ONE hh_jpeg_index_device_batch (for the images whose index
+        the device builds) and ONE hh_jpeg_decode_u8_batch fill the slots in front of hh_preprocess_u8_batch, which reads them exactly
+        as it reads shipped pixels, so `scales`, `render` and `tracker` work unchanged.  The decoder's statuses ride in the batch's
+        device->host hand-over; a nonzero one raises HHError naming the image when the batch's results are collected.  A file the
+        decoder refuses by name (progressive, CMYK, ...) is refused at `JpegImage(...)`: pass it as a Pillow array; there is no silent
+        fallback.  `.raw_image` of such a result is formed on first access by `decode_jpeg_host` (bit-identical to the device pixels)
+        and cached; no pixels are copied back.  A batch of arrays takes exactly the path it took before.  `self.last_h2d_bytes` keeps
+        the bytes the call uploaded."""
         if render is not None and render.get("color_mode") == "track" and tracker is None:
             raise ValueError("infer_images: render color_mode 'track' needs a tracker")
         if render is not None:
             unknown = set(render) - {"color_mode", "alpha", "bgr", "out_height", "jpeg"}
             if unknown:
                 raise ValueError(f"infer_images: unknown render option(s) {sorted(unknown)}")
+        from . import jpeg as jp
+        raw_images = [jp.JpegImage(img, index="device") if isinstance(img, (bytes, bytearray, memoryview)) else img for img in raw_images]
         n = len(raw_images)
         annots = annots if annots is not None else [None] * n
+        self.last_h2d_bytes = 0
         # (size, center, scale) now -- the bucket key --, the warp matrix when the image's batch is staged: the first batch should
         # not wait for n matrix inversions
         if scales is None:
@@ -537,8 +555,16 @@ class InferenceKeypointsModel:
 
         def finish(job):
             """device -> host results of one enqueued batch, un-warp, result objects"""
-            chunk, (w, h), x, hms, tags, host_out, done, staged = job
+            chunk, (w, h), x, hms, tags, host_out, done, staged, jpeg_at = job
             done.synchronize()
+            if jpeg_at:  # the decoder's statuses came with the results: the index call's codes, if it ran, behind the decode's
+                codes = host_out[-1].numpy().reshape(-1, len(jpeg_at)).max(axis=0)
+                bad = [(chunk[j], int(s)) for j, s in zip(jpeg_at, codes) if int(s)]
+                if bad:
+                    i, s = bad[0]
+                    name = jp.STATUS_NAMES[s] if 0 <= s < len(jp.STATUS_NAMES) else "unknown"
+                    raise _lib.HHError(f"infer_images: image {i}: its JPEG stream cannot be decoded: status {s} ({name})"
+                                       + (f"; also images {[k for k, _ in bad[1:]]}" if len(bad) > 1 else ""))
             lists = self._parser.to_lists(*host_out[:4])  # (copies what it returns: the pinned buffers are reused two batches later)
             self.model_input_shape = (h, w)
             for j, i in enumerate(chunk):
@@ -564,22 +590,50 @@ class InferenceKeypointsModel:
             for chunk, subs in chunks:
                 w, h = sizes[i1]
                 nb = len(chunk)
-                offs = np.cumsum([0] + [raw_images[i].size for i in chunk])
+                jpeg_at = [j for j, i in enumerate(chunk) if isinstance(raw_images[i], jp.JpegImage)]
+                offs = np.cumsum([0] + [0 if isinstance(raw_images[i], jp.JpegImage) else raw_images[i].size for i in chunk])
                 desc_off = (int(offs[-1]) + 63) // 64 * 64  # the image descriptors travel behind the pixels, in the same copy
                 total = desc_off + _IMAGE_DESC.itemsize * nb * len(sizes)  # (one block of them per scale)
+                starts = [int(o) for o in offs[:-1]]  # where image j's pixels lie in the device buffer
+                dev_total, jplan = total, None
+                if jpeg_at:
+                    # a JPEG image ships no pixels: [decode descriptors | stream, table block | ...] travel behind the image descriptors in
+                    # the same copy; the statuses and the pixel slots, which the decode fills, lie behind the uploaded bytes on the device
+                    items = [raw_images[chunk[j]] for j in jpeg_at]
+                    jdesc_off = (total + 15) // 16 * 16
+                    places = jdesc_off + jp.DEC_DESC.itemsize * len(items) + np.cumsum([0] + [it.staged_bytes() for it in items])
+                    total = int(places[-1])
+                    status_off = total  # (a multiple of 16)
+                    at = status_off + 8 * len(items)
+                    for j, it in zip(jpeg_at, items):
+                        starts[j] = at = (at + 15) // 16 * 16
+                        at += it.h * it.w * 3
+                    dev_total = at
+                    ws_offs = np.cumsum([0] + [it.ws_bytes for it in items])
+                    jplan = (items, jdesc_off, places, status_off, ws_offs, jp.index_mcus_per_segment(items, "infer_images"))
+                self.last_h2d_bytes += total
                 if stage[turn] is None or stage[turn].numel() < total:
                     stage[turn] = torch.empty(total, dtype=torch.uint8).pin_memory()
                 elif stage_free[turn] is not None:
                     stage_free[turn].synchronize()  # the copy that last read this buffer has finished
                 host = stage[turn]
                 hview = host.numpy()
-                descs = hview[desc_off:total].view(_IMAGE_DESC)
+                descs = hview[desc_off:desc_off + _IMAGE_DESC.itemsize * nb * len(sizes)].view(_IMAGE_DESC)
                 for j, i in enumerate(chunk):
                     img = raw_images[i]
-                    np.copyto(hview[offs[j]:offs[j + 1]].reshape(img.shape), img, casting="same_kind")
+                    if not isinstance(img, jp.JpegImage):
+                        np.copyto(hview[offs[j]:offs[j + 1]].reshape(img.shape), img, casting="same_kind")
                     for si, s in enumerate(pass_scales):
                         g = geo[i] if si == i1 else get_multi_scale_size(img, self.input_size, s, mn)
-                        descs[si * nb + j] = (int(offs[j]), img.shape[0], img.shape[1], self._dst_to_src(*g).reshape(6))
+                        descs[si * nb + j] = (starts[j], img.shape[0], img.shape[1], self._dst_to_src(*g).reshape(6))
+                jdescs = jinfos = None
+                if jplan is not None:
+                    items, jdesc_off, places, status_off, ws_offs, _ = jplan
+                    jdescs = hview[jdesc_off:jdesc_off + jp.DEC_DESC.itemsize * len(items)].view(jp.DEC_DESC)
+                    for k, (j, it) in enumerate(zip(jpeg_at, items)):
+                        stream_at, tables_at = it.stage(hview, int(places[k]))
+                        jdescs[k] = (stream_at, tables_at, it.tables_bytes, starts[j], int(ws_offs[k]), 3 * it.w, it.data.size, it.nseg, 0, 0)
+                    jinfos = np.concatenate([it.info for it in items])
 
                 # host -> device on a copy stream of its own, so that the pixels of this batch cross PCIe while the previous
                 # batch still computes (25 MB per batch of 32 512x512 images: ~1.7 ms that would otherwise sit on the compute stream)
@@ -588,14 +642,30 @@ class InferenceKeypointsModel:
                     # (the priority of the compute stream: at a lower one the result copies would wait for the whole next batch)
                     self._d2h_stream = torch.cuda.Stream(self.device, priority=torch.cuda.Stream.priority_range()[1])
                 with torch.cuda.stream(self._copy_stream):
-                    raw = host[:total].to(self.device, non_blocking=True)
+                    if jplan is None:
+                        raw = host[:total].to(self.device, non_blocking=True)
+                    else:  # (room behind the uploaded bytes for the statuses and the decoded pixels)
+                        raw = torch.empty(dev_total, dtype=torch.uint8, device=self.device)
+                        raw[:total].copy_(host[:total], non_blocking=True)
                     copied = torch.cuda.Event()
                     copied.record()
 
-                def run(chunk=chunk, raw=raw, copied=copied, desc_off=desc_off, w=w, h=h, turn=turn, nb=nb, sizes=sizes, subs=subs, offs=offs):
+                def run(chunk=chunk, raw=raw, copied=copied, desc_off=desc_off, w=w, h=h, turn=turn, nb=nb, sizes=sizes, subs=subs, offs=starts,
+                        jplan=jplan, jdescs=jdescs, jinfos=jinfos, jpeg_at=jpeg_at):
                     cur = torch.cuda.current_stream(self.device)
                     cur.wait_event(copied)
                     raw.record_stream(cur)
+                    jstatus = None
+                    if jplan is not None:
+                        # one index call (where an image's index is the device's to build) and one decode call fill the pixel slots in
+                        # front of the preprocess launches, which read them as they read shipped pixels
+                        items, jdesc_off, _, status_off, ws_offs, mps = jplan
+                        work = torch.empty(max(int(ws_offs[-1]), 16), dtype=torch.uint8, device=self.device)
+                        base, nj = raw.data_ptr(), len(items)
+                        if mps is not None:
+                            jp.launch_index(self.device, base, base + jdesc_off, jdescs, jinfos, mps, None, base + status_off + 4 * nj)
+                        jp.launch_decode(self.device, base, base + jdesc_off, jdescs, jinfos, work, base + status_off)
+                        jstatus = raw[status_off:status_off + 4 * nj * (2 if mps is not None else 1)].view(torch.int32)
 
                     def prepare(si):
                         ws, hs = sizes[si]
@@ -610,6 +680,8 @@ class InferenceKeypointsModel:
                     out = self._parser.decode_batch_device(hms[0], hms[1], tags, adjust=True, refine=True)
                     if tracker is not None:
                         out = out + tracker.update_device(*out, frames_per_stream=nb)[:2]
+                    if jstatus is not None:
+                        out = tuple(out) + (jstatus,)  # (the statuses ride in the same hand-over)
                     # device -> host into pinned buffers kept per pipeline slot (allocating pinned memory costs ~0.4 ms per array);
                     # finish() of this slot's previous batch ran before this point and copied what it keeps
                     key = (turn, tuple((tuple(t.shape), t.dtype) for t in out))
@@ -627,7 +699,7 @@ class InferenceKeypointsModel:
                     for t in out:
                         t.record_stream(self._d2h_stream)
                     staged = (raw, offs) if render is not None else None  # the batch's device pixels, kept until its render has run
-                    return (chunk, (w, h), x, hms, tags, host_out, done, staged), copied, raw
+                    return (chunk, (w, h), x, hms, tags, host_out, done, staged, jpeg_at if jstatus is not None else []), copied, raw
 
                 # (the model's high-priority stream, for batches as for single images: same-box alternation with the caller's
                 # stream, tools/api_throughput.py: 3820 / 3380 against 2600 / 2970 img/s)
@@ -644,14 +716,15 @@ class InferenceKeypointsModel:
     def _render_chunk(self, results: list, raw: Tensor, offs, color_mode: str = "person", alpha: float = 0.8, bgr: bool = False,
                       out_height: int | None = None, jpeg: dict | None = None) -> None:
         """`.rendered` of the results of one batch: one render launch on the batch's staged pixels (`raw`: the device copy of the
-        staging buffer, image j at bytes offs[j]..offs[j+1]), the optional resizes, one pinned buffer back.  With `jpeg`:
+        staging buffer, image j's h * w * 3 bytes from offs[j]), the optional resizes, one pinned buffer back.  With `jpeg`:
         `.rendered_jpeg` instead, one encode call on the device frames, only the compressed bytes back."""
         from . import visualization as vz
         cur = torch.cuda.current_stream(self.device)
         raw.record_stream(cur)
         frames, tables = [], []
         for j, r in enumerate(results):
-            frames.append(raw[int(offs[j]):int(offs[j + 1])].view(r.raw_image.shape))
+            shape = r.raw_shape  # (of a JPEG input too: its pixels were formed on the device, at offs[j])
+            frames.append(raw[int(offs[j]):int(offs[j]) + shape[0] * shape[1] * 3].view(shape))
             by_id = color_mode == "track"
             tables.append(vz.build_primitives(r.kpts_coords_smooth if by_id else r.kpts_coords, r.kpts_scores, r.limbs, r.det_thr, color_mode,
                                               vz.DEFAULT_PALETTE, alpha, ids=r.track_ids if by_id else None))
@@ -727,7 +800,13 @@ class InferenceKeypointsModel:
         return result, vz.to_host(frame)
 
     def __call__(self, raw_image: np.ndarray, annot: list | None) -> InferenceKeypointsResult:
-        """model.py:78-111"""
+        """model.py:78-111.  `raw_image` may also be the bytes of a JPEG file or a jpeg.JpegImage (see infer_images): the bytes cross,
+        the index (of bytes: on the device) and the pixels are formed on the GPU, and the result's `.raw_image` is decoded on the host
+        on first access."""
+        if isinstance(raw_image, (bytes, bytearray, memoryview)):
+            from .jpeg import JpegImage
+            raw_image = JpegImage(raw_image, index="device")
+
         def run():
             x, center, scale = self.prepare_input(raw_image)
             self.model_input_shape = tuple(x.shape[-2:])

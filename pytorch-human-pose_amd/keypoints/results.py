@@ -111,6 +111,11 @@ class InferenceKeypointsResult:
     track_ids: np.ndarray | None = None  # with a PoseTracker: int32 [P], 0 = no track
     kpts_coords_smooth: np.ndarray | None = None  # with a PoseTracker: [P,K,2] raw-image pixels, One-Euro filtered
 
+    @property
+    def raw_shape(self) -> tuple:
+        """`raw_image.shape` without forming the pixels of a JPEG input."""
+        return tuple(self.__dict__["_raw_image"].shape)
+
     @classmethod
     def from_preds(cls, raw_image, annot, model_input_image: Tensor, kpts_heatmaps: list[Tensor], tags_heatmaps: list[Tensor],
                    limbs, scale, center, det_thr: float = 0.05, tag_thr: float = 0.5, max_num_people: int = 30,
@@ -181,3 +186,17 @@ class InferenceKeypointsResult:
         f = torch.nn.functional.interpolate
         h, w = self.model_input_image.shape[-2:]
         return f(self._tags[0], size=[h, w], mode="bilinear", align_corners=False)[0].cpu().numpy()
+
+
+def _raw_image(self):
+    """The input image.  Of a JPEG input (a jpeg.JpegImage: only its bytes went to the device) the pixels are formed here on first
+    access by the host rule, which is bit-identical to the device's, and kept."""
+    raw = self.__dict__.get("_raw_image")
+    if hasattr(raw, "stage"):  # a jpeg.JpegImage
+        from .jpeg import decode_jpeg_host
+        raw = self.__dict__["_raw_image"] = decode_jpeg_host(raw.data)
+    return raw
+
+
+# (installed behind the dataclass decorator: the generated __init__ assigns through the setter)
+InferenceKeypointsResult.raw_image = property(_raw_image, lambda self, value: self.__dict__.__setitem__("_raw_image", value))

@@ -268,6 +268,9 @@ class TrainInput:
             for img, mask, _ in tiles:
                 if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or mask.shape != img.shape[:2]:
                     raise ValueError("TrainInput.build: uint8 [h,w,3] images with [h,w] crowd masks only")
+                if isinstance(img, jp.JpegImage) and img.device_index:
+                    raise ValueError("TrainInput.build: a device-indexed JpegImage (index='device') is refused: training files come back every "
+                                     "epoch, so build their index once on the host (jpeg.JpegIndexCache)")
             first = len(raws)
             raws.extend(tiles)
             slots.append(list(range(first, first + 4)) if isinstance(entry, Mosaic) else first)
