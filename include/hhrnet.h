@@ -473,6 +473,78 @@ int hh_render_poses_u8_batch(unsigned char *batch_base, const hh_render_desc *de
 int hh_render_config(int out[4]);
 int hh_debug_render_host(const unsigned char *src, unsigned char *dst, const hh_render_desc *desc, const hh_render_prim *prims, int num_prims);
 int hh_resize_u8(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, void *stream);
+/* Text labels: put_txt (utils/image.py:64-119), the one function through which the reference draws all of its text, for n uint8
+ * [h,w,3] frames of mixed sizes in ONE launch, IN PLACE, on the frames where they already lie on the device (behind the render and
+ * resize launches, in front of the copy back or the JPEG encode).  The host forms the primitive table (keypoints/text.py
+ * layout_put_txt here, which restates put_txt's arithmetic in integers); the kernel does the per-pixel work; the result is
+ * bit-identical to this text (tests/text_ref.py restates it in numpy).
+ *
+ * The rule.  put_txt(image, labels, vspace, font_scale, thickness = 1, loc, bg_color, txt_color, alpha) measures every label
+ * (width, height) = text_size(label, font_scale), forms txt_h = vspace + sum(height + vspace), txt_w = max(width) + 2 vspace, the
+ * box origin (_x, _y) from `loc` (tl tr bl br tc bc; Python's floor division), and draws, in this order:
+ *   one BOX   alpha < 1: the rectangle [_x, _x + txt_w) x [_y, _y + txt_h) blended with bg_color; otherwise (alpha == 1 included) the
+ *             INCLUSIVE rectangle [_x, _x + txt_w] x [_y, _y + txt_h] filled with bg_color: one pixel wider and taller, as cv2.rectangle
+ *             draws it (the reference's quirk, kept);
+ *   per label, top to bottom, its characters left to right from the origin (x, y + height) = baseline left, y advancing by height +
+ *             vspace: one GLYPH per character that has ink, its bitmap's top-left at (pen + left bearing, baseline + top), the pen
+ *             advancing by the character's integer advance.
+ * Pixel arithmetic, per channel, on the stored bytes (the caller gives colours in the frame's own channel order):
+ *   BOX   opaque: the colour.  Otherwise rintf(img * w0 + bg * w1) in fp32, the two products and the sum rounded separately, clamped
+ *         to 0..255; w0 = (float)(1.0 - alpha), w1 = (float)alpha, both formed in double on the host: the blend of the overlays above.
+ *   GLYPH with coverage c = atlas[offset + row * bitmap width + column]: (pix * (255 - c) + col * c + 127) / 255 in integers.
+ *   Primitives apply to a pixel in table order; two put_txt tables concatenated compose two boxes (plot_top_preds' target box).
+ * The font: text_size and the glyph bitmaps come from an atlas file that ships with the package (keypoints/data/, rasterised from
+ *   DejaVu Sans by tools/make_font_atlas.py): three size classes with cap heights 7, 11 and 15 pixels for font_scale 0.3, 0.5 and 0.7;
+ *   another font_scale takes the nearest class (the smaller on a tie); thickness != 1 is refused; a character outside 0x20..0x7E draws
+ *   as '?'.  height = the class's cap height, width = the sum of the integer advances.
+ * Stated deviations: (1) cv2's Hershey font is not available where this is built and is not guessed at: glyph shapes and, through
+ *   the text metrics, box sizes differ from cv2's.  Parity with cv2.putText / getTextSize is UNPINNED.  Everything in front of the
+ *   rasteriser IS pinned to the reference by tests/golden/text.npz, written by the reference's own put_txt, plot_top_preds and
+ *   draw_labels with a stand-in cv2 that answers getTextSize from this atlas and records rectangle / addWeighted / putText: the box,
+ *   the six locs, the alpha == 1 quirk, the weights, the colours, every label's origin and string.  (2) Primitives are clipped to the
+ *   frame; the reference's negative slice start, which wraps in numpy, is not imitated.
+ *
+ * The table: hh_text_prim rows of 32 bytes in draw order.  They ARE hh_render_prim rows (one definition), read as follows.
+ *   kind HH_TEXT_BOX:   (x0, y0)..(x1, y1) the inclusive rectangle clipped to the frame (x1 < x0 or y1 < y0: nothing), rgb the colour
+ *                       as stored, c = w0, s = w1, A = 1 opaque / 0 blended; B, cx, cy = 0.
+ *   kind HH_TEXT_GLYPH: (cx, cy) the bitmap's top-left in the frame (may be negative), A x B the bitmap's width x height, c = the
+ *                       offset of its A * B coverage bytes in the atlas (an integer below 2^24, exact in fp32), s = 0, rgb the colour,
+ *                       (x0, y0)..(x1, y1) the inclusive rectangle [cx, cx + A - 1] x [cy, cy + B - 1] clipped to the frame.
+ * The frame descriptors: one hh_text_desc per frame; they ARE hh_render_desc: the frame [h,w,3], tightly packed (w * 3 bytes a row,
+ *   any alignment), at batch_base + src_offset; dst_offset = src_offset (in place); its rows table[prim_offset .. prim_offset +
+ *   prim_count); w0, w1, flags and reserved are 0 (there is no flag yet).
+ * The tile list: int32 pairs (frame, tile), tile = ty * ceil(w / tile width) + tx, strictly ascending: the tiles that some
+ *   primitive's box touches, as hh_text_tiles lists them.  A workgroup takes one pair, culls the frame's primitives to its tile a
+ *   chunk at a time keeping the draw order within and across chunks, and neither reads nor writes a pixel that no primitive covers:
+ *   work scales with the labelled area.  Descriptors, table and tile list are meant to travel in one copy (the binding does so);
+ *   atlas_dev holds the atlas's atlas_len coverage bytes.
+ * Validation: on the caller's HOST copies, before any launch; returns 1 with hh_last_error set for a null pointer, n outside
+ *   1..65535, num_prims or num_tiles < 0, a misaligned device table, h or w outside 1..16384, a negative offset, dst_offset !=
+ *   src_offset, a primitive range outside the table, more than HH_TEXT_MAX_PRIMS primitives in one frame (refused, never capped), a
+ *   weight that is not finite, an unknown kind or flag, an empty or inverted glyph bitmap, a glyph whose coverage range leaves the
+ *   atlas or whose offset is no such integer, a coordinate beyond +-2^23, a box outside the frame or (glyph) outside its bitmap, a
+ *   tile pair that names no tile of its frame or does not ascend.  That frames lie inside the caller's buffer cannot be checked here.
+ * hh_text_tiles: validates as above and lists the touched tiles into tiles_host (room for `capacity` pairs); *count = how many there
+ *   are (call with capacity 0 to size the list).  num_tiles == 0 launches nothing.
+ * hh_text_check: the validation of hh_text_labels_u8_batch alone, on the same host copies; it launches nothing (tests).
+ * hh_text_config: out[4] = tile height, tile width, primitives culled per chunk, pixels per thread.
+ * hh_debug_text_host: one frame (its own HOST buffer, drawn in place; the descriptor's offsets are ignored) through the same tile
+ *   walk compiled for the host; `atlas` is the host copy.  Same validation.  For tests and tools/text_host_check.cpp.
+ * (Additive entry points: HH_ABI_VERSION stays 3.)                                                                           */
+#define HH_TEXT_MAX_PRIMS 4096 /* per frame */
+enum { HH_TEXT_BOX = 0, HH_TEXT_GLYPH = 1 };
+typedef hh_render_prim hh_text_prim;
+typedef hh_render_desc hh_text_desc;
+int hh_text_labels_u8_batch(unsigned char *batch_base, const hh_text_desc *descs_dev, const hh_text_desc *descs_host, const hh_text_prim *prims_dev,
+                            const hh_text_prim *prims_host, int num_prims, int n, const unsigned char *atlas_dev, long long atlas_len,
+                            const int32_t *tiles_dev, const int32_t *tiles_host, long long num_tiles, void *stream);
+int hh_text_tiles(const hh_text_desc *descs_host, const hh_text_prim *prims_host, int num_prims, int n, long long atlas_len, int32_t *tiles_host,
+                  long long capacity, long long *count);
+int hh_text_check(const hh_text_desc *descs_host, const hh_text_prim *prims_host, int num_prims, int n, long long atlas_len, const int32_t *tiles_host,
+                  long long num_tiles);
+int hh_text_config(int out[4]);
+int hh_debug_text_host(unsigned char *frame, const hh_text_desc *desc, const hh_text_prim *prims, int num_prims, const unsigned char *atlas,
+                       long long atlas_len);
 /* Heatmap panels: plot_heatmaps + make_grid of the reference (keypoints/visualization.py:93-110, utils/image.py:15-38) for every grid
  * of one figure in ONE call (one min/max launch, skipped when no map asks for it, and one paint launch), from the stage outputs of the
  * net as they are: no full-resolution fp32 map is stored or copied to the host.  tests/panels_ref.py restates the rule in numpy /

@@ -2,6 +2,7 @@ from .input import ClsInput, CropParams, CropWindow, inference_geometry, random_
 from .loss import ClassificationLoss
 from .model import ClassificationModel, InferenceClassificationModel, InferenceClassificationResult
 from .module import ClassificationModule, ClassificationResult
+from .visualization import plot_top_preds, plot_top_preds_batch
 
 __all__ = ["ClassificationLoss", "ClassificationModel", "ClassificationModule", "ClassificationResult", "ClsInput", "CropParams", "CropWindow",
-           "InferenceClassificationModel", "InferenceClassificationResult", "inference_geometry", "random_resized_crop_params"]
+           "InferenceClassificationModel", "InferenceClassificationResult", "inference_geometry", "plot_top_preds", "plot_top_preds_batch", "random_resized_crop_params"]

@@ -35,14 +35,28 @@ class ClassificationModel(BaseModel):
 
 @dataclass
 class InferenceClassificationResult:
-    """classification/results.py:39-68 without the plot: one image's logits, their softmax, the prediction (the arg-max, the lower
-    index on a tie, as `ClassificationResult` has it), its label and the target label."""
+    """classification/results.py:39-82: one image's logits, their softmax, the prediction (the arg-max, the lower index on a tie, as
+    `ClassificationResult` has it), its label, the target label and the label table that `plot()` reads."""
     raw_image: np.ndarray
     logits: np.ndarray
     probs: np.ndarray
     prediction: int
     pred_label: int | str
     target_label: int | str | None = None
+    idx2label: dict | None = None
+
+    def plot(self) -> dict[str, np.ndarray]:
+        """results.py:70-82: the raw image resized to height 512 (hh_resize_u8) with the five best "{p:.3f}:  {label}" lines and, with
+        a target, the green "Target:" box, drawn by one text launch -> {"top_preds": uint8 [512,w,3]}.  For a list of records,
+        `classification.plot_top_preds_batch` does the same in one upload, one text launch and one copy back."""
+        from .visualization import plot_top_preds_batch
+        return {"top_preds": plot_top_preds_batch([self])[0]}
+
+    def plot_jpeg(self, quality: int = 90, subsampling="444") -> dict[str, bytes]:
+        """plot() as a .jpg file: drawn and encoded on the GPU (keypoints/jpeg.py); only the compressed bytes are copied back."""
+        from ..keypoints.jpeg import encode_jpeg_device
+        from .visualization import plot_top_preds_device
+        return {"top_preds": encode_jpeg_device(plot_top_preds_device([self]), quality, subsampling)[0]}
 
 
 class InferenceClassificationModel:
@@ -87,7 +101,7 @@ class InferenceClassificationModel:
             e = np.exp(lg[i] - lg[i].max())
             pred = int(np.argmax(lg[i]))  # the first maximum: the lower index on a tie
             out.append(InferenceClassificationResult(im, lg[i], e / e.sum(), pred, self.idx2label[pred],
-                                                     None if target_labels is None else target_labels[i]))
+                                                     None if target_labels is None else target_labels[i], self.idx2label))
         return out
 
     def infer_images(self, raw_images: list, target_labels: list | None = None, max_batch: int = 32) -> list:

@@ -20,12 +20,39 @@ from .model import ClassificationModel
 
 @dataclass
 class ClassificationResult:
-    """One validation image (classification/results.py:13-24 without the plot): its logits, target and prediction (the arg-max,
-    the lower index on a tie)."""
+    """One validation image (classification/results.py:13-36): its logits, target and prediction (the arg-max, the lower index on a
+    tie).  `plot()` needs `model_input_image` (the normalised [3,H,W] input, kept on the device) and `idx2label`; validation_step
+    fills both."""
     logits: np.ndarray
     target: int
     prediction: int
     target_label: str | int | None = None
+    model_input_image: Tensor | None = None
+    idx2label: dict | None = None
+
+    def _plot_device(self) -> dict[str, Tensor]:
+        """results.py:26-36: probs = (exp(logits) + eps) / sum, eps of the logits' dtype; plot_top_preds on the un-normalised model
+        input (hh_unnormalize_u8), drawn by one text launch.  -> {"top_probs": device uint8 [H,W,3]}."""
+        from ..keypoints import visualization as vz
+        from .visualization import plot_top_preds
+        if self.model_input_image is None or self.idx2label is None:
+            raise ValueError("ClassificationResult.plot: needs model_input_image and idx2label")
+        exp_logits = np.exp(self.logits) + np.finfo(self.logits.dtype).eps
+        probs = exp_logits / np.sum(exp_logits)
+        x = self.model_input_image
+        image = vz.unnormalize_device((x if x.is_cuda else x.cuda()).to(torch.float32))
+        return {"top_probs": plot_top_preds(image, probs, self.idx2label, k=5, target_label=self.target_label)}
+
+    def plot(self) -> dict[str, np.ndarray]:
+        from ..keypoints.visualization import to_host
+        return {name: to_host(figure) for name, figure in self._plot_device().items()}
+
+    def plot_jpeg(self, quality: int = 90, subsampling="444") -> dict[str, bytes]:
+        """plot() as the .jpg file the reference's callbacks save: encoded on the GPU (keypoints/jpeg.py), only the compressed bytes
+        copied back."""
+        from ..keypoints.jpeg import encode_jpeg_device
+        figures = self._plot_device()
+        return dict(zip(figures, encode_jpeg_device(list(figures.values()), quality, subsampling)))
 
 
 class ClassificationModule:
@@ -98,5 +125,6 @@ class ClassificationModule:
         results = []
         for i in range(len(lg)):
             t = int(tg[i])
-            results.append(ClassificationResult(lg[i], t, int(np.argmax(lg[i])), self.idx2label[t] if self.idx2label is not None else None))
+            results.append(ClassificationResult(lg[i], t, int(np.argmax(lg[i])), self.idx2label[t] if self.idx2label is not None else None,
+                                                images[i], self.idx2label))
         return metrics, results

@@ -12,6 +12,7 @@
 #include "grad_stats_math.h"
 #include "ema_math.h"
 #include "render_math.h"
+#include "text_math.h"
 #include "panel_math.h"
 #include "coco_eval_math.h"
 #include "crowd_mask_math.h"
@@ -348,6 +349,112 @@ int hh_debug_render_host(const unsigned char *src, unsigned char *dst, const hh_
     RenderDesc d = *desc;  // src and dst are the frame's own buffers here
     d.src_offset = d.dst_offset = 0;
     render_debug_host(src, dst, d, prims);
+    return 0;
+}
+
+int hh_text_config(int out[4])
+{
+    if (!out) { hh_set_error("hh_text_config: null pointer"); return 1; }
+    out[0] = TEXT_TH, out[1] = TEXT_TW, out[2] = TEXT_CHUNK, out[3] = TEXT_PX;
+    return 0;
+}
+
+// The checks of a text call that need no device: every frame's descriptor and its primitives, on the caller's host copy.
+static int text_check(const char *fn, const hh_text_desc *descs_host, const hh_text_prim *prims_host, int num_prims, int n, long long atlas_len)
+{
+    if (n <= 0 || n > 65535) { hh_set_error(std::string(fn) + ": need 0 < n <= 65535"); return 1; }
+    if (num_prims < 0 || atlas_len < 0) { hh_set_error(std::string(fn) + ": negative table or atlas length"); return 1; }
+    for (int b = 0; b < n; ++b) {
+        const TextDesc &d = descs_host[b];
+        if (d.prim_count > 0 && !prims_host) { hh_set_error(std::string(fn) + ": null primitive table"); return 1; }
+        const char *why = text_check_frame(d, prims_host, num_prims, atlas_len);
+        if (why) { hh_set_error(std::string(fn) + ": frame " + std::to_string(b) + ": " + why); return 1; }
+    }
+    return 0;
+}
+
+int hh_text_tiles(const hh_text_desc *descs_host, const hh_text_prim *prims_host, int num_prims, int n, long long atlas_len, int32_t *tiles_host,
+                  long long capacity, long long *count)
+{
+    const char *fn = "hh_text_tiles";
+    if (!descs_host || !count || (capacity > 0 && !tiles_host) || (num_prims > 0 && !prims_host)) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if (capacity < 0) { hh_set_error(std::string(fn) + ": negative capacity"); return 1; }
+    if (text_check(fn, descs_host, prims_host, num_prims, n, atlas_len)) return 1;
+    std::vector<uint8_t> seen;
+    long long total = 0;
+    for (int b = 0; b < n; ++b) {
+        const TextDesc &d = descs_host[b];
+        seen.resize((size_t)text_xtiles(d.w) * text_ytiles(d.h));
+        const long long room = capacity > total ? capacity - total : 0;
+        total += text_list_tiles(d, prims_host, b, seen.data(), reinterpret_cast<TextTile *>(tiles_host) + (room ? total : 0), room);
+    }
+    *count = total;
+    return 0;
+}
+
+// A tile list names tiles of its frames, each at most once (two workgroups on one tile would both read and write it): strictly ascending.
+static int text_check_tiles(const char *fn, const hh_text_desc *descs_host, int n, const int32_t *tiles_host, long long num_tiles)
+{
+    const TextTile *t = reinterpret_cast<const TextTile *>(tiles_host);
+    for (long long i = 0; i < num_tiles; ++i) {
+        if (t[i].frame < 0 || t[i].frame >= n || t[i].tile < 0 || t[i].tile >= text_xtiles(descs_host[t[i].frame].w) * text_ytiles(descs_host[t[i].frame].h)) {
+            hh_set_error(std::string(fn) + ": tile " + std::to_string(i) + " names no tile of its frame");
+            return 1;
+        }
+        if (i && (t[i].frame < t[i - 1].frame || (t[i].frame == t[i - 1].frame && t[i].tile <= t[i - 1].tile))) {
+            hh_set_error(std::string(fn) + ": the tile list must ascend strictly");
+            return 1;
+        }
+    }
+    return 0;
+}
+
+// Everything a text call checks on the host copies.
+static int text_check_call(const char *fn, const hh_text_desc *descs_host, const hh_text_prim *prims_host, int num_prims, int n, long long atlas_len,
+                           const int32_t *tiles_host, long long num_tiles)
+{
+    if (!descs_host || (num_prims > 0 && !prims_host) || (num_tiles > 0 && !tiles_host)) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if (num_tiles < 0 || num_tiles > INT32_MAX) { hh_set_error(std::string(fn) + ": need 0 <= num_tiles < 2^31"); return 1; }
+    return text_check(fn, descs_host, prims_host, num_prims, n, atlas_len) || text_check_tiles(fn, descs_host, n, tiles_host, num_tiles);
+}
+
+int hh_text_check(const hh_text_desc *descs_host, const hh_text_prim *prims_host, int num_prims, int n, long long atlas_len, const int32_t *tiles_host,
+                  long long num_tiles)
+{
+    return text_check_call("hh_text_check", descs_host, prims_host, num_prims, n, atlas_len, tiles_host, num_tiles);
+}
+
+int hh_text_labels_u8_batch(unsigned char *batch_base, const hh_text_desc *descs_dev, const hh_text_desc *descs_host, const hh_text_prim *prims_dev,
+                            const hh_text_prim *prims_host, int num_prims, int n, const unsigned char *atlas_dev, long long atlas_len,
+                            const int32_t *tiles_dev, const int32_t *tiles_host, long long num_tiles, void *stream)
+{
+    const char *fn = "hh_text_labels_u8_batch";
+    if (!batch_base || !descs_dev || !descs_host || !atlas_dev || (num_prims > 0 && (!prims_dev || !prims_host)) || (num_tiles > 0 && (!tiles_dev || !tiles_host))) {
+        hh_set_error(std::string(fn) + ": null pointer");
+        return 1;
+    }
+    if ((uintptr_t)descs_dev % 8 || (uintptr_t)prims_dev % 4 || (uintptr_t)tiles_dev % 4) {
+        hh_set_error(std::string(fn) + ": descs_dev must be 8-byte, prims_dev and tiles_dev 4-byte aligned");
+        return 1;
+    }
+    if (text_check_call(fn, descs_host, prims_host, num_prims, n, atlas_len, tiles_host, num_tiles)) return 1;
+    if (num_tiles == 0) return 0;
+    HH_CHECK_HIP(launch_text_labels(batch_base, descs_dev, prims_dev, atlas_dev, tiles_dev, num_tiles, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_debug_text_host(unsigned char *frame, const hh_text_desc *desc, const hh_text_prim *prims, int num_prims, const unsigned char *atlas,
+                       long long atlas_len)
+{
+    const char *fn = "hh_debug_text_host";
+    if (!frame || !desc || !atlas) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if (text_check(fn, desc, prims, num_prims, 1, atlas_len)) return 1;
+    TextDesc d = *desc;  // frame is the frame's own buffer here
+    d.src_offset = d.dst_offset = 0;
+    std::vector<uint8_t> seen((size_t)text_xtiles(d.w) * text_ytiles(d.h));
+    std::vector<TextTile> tiles(seen.size());
+    const long long nt = text_list_tiles(d, prims, 0, seen.data(), tiles.data(), (long long)tiles.size());
+    text_debug_host(frame, d, prims, atlas, tiles.data(), nt);
     return 0;
 }
 

@@ -361,6 +361,11 @@ hipError_t launch_render_poses(unsigned char *base, const hh_render_desc *descs,
 void render_debug_host(const unsigned char *src, unsigned char *dst, const hh_render_desc &d, const hh_render_prim *prims);
 hipError_t launch_resize_u8(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, hipStream_t s);
 hipError_t launch_resize_u8_scaled(const unsigned char *src, int h, int w, int channels, unsigned char *dst, int H, int W, double fx, double fy, hipStream_t s);
+// Text labels (hh_text_desc / hh_text_prim of include/hhrnet.h; arithmetic in text_math.h, kernel in text.hip): the listed tiles of a
+// batch of frames in one launch, `tiles` = num_tiles (frame, tile) pairs; the same walk on the host for one frame.
+hipError_t launch_text_labels(unsigned char *base, const hh_text_desc *descs, const hh_text_prim *prims, const uint8_t *atlas, const void *tiles,
+                              long long num_tiles, hipStream_t s);
+void text_debug_host(unsigned char *frame, const hh_text_desc &d, const hh_text_prim *prims, const uint8_t *atlas, const void *tiles, long long num_tiles);
 // Baseline JPEG (hh_jpeg_desc of include/hhrnet.h; struct and arithmetic in jpeg_math.h, kernels in jpeg.hip): n frames in three
 // launches, `max_mcus` / `max_rows` = the largest frame's MCU count / MCU rows.
 hipError_t launch_jpeg_encode(unsigned char *base, const hh_jpeg_desc *descs, int n, int max_mcus, int max_rows, unsigned char *ws, int32_t *lengths,

@@ -12,3 +12,5 @@ from .tracking import PoseTracker
 from . import jpeg
 from .jpeg import JpegImage, JpegIndexCache, MJPEGReader, MJPEGWriter, build_jpeg_index, decode_jpeg_device, encode_jpeg_device, jpeg_info, load_jpeg, save_jpeg
 from .visualization import DEFAULT_PALETTE, build_primitives, jet_lut, plot_connections, plot_heatmaps
+from . import text
+from .text import layout_put_txt, load_font, put_txt, put_txt_device, put_txt_host, text_size, video_labels

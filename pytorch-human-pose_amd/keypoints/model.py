@@ -497,6 +497,9 @@ class InferenceKeypointsModel:
         encoded on the GPU in ONE hh_jpeg_encode_u8_batch behind their render launch (keypoints/jpeg.py) and every result carries
         `.rendered_jpeg` (bytes; true colours also with `bgr`) in place of `.rendered`: no raw frame is copied back.
         color_mode="track" (needs `tracker`) draws the smoothed coordinates, each person in the colour of its id.
+        With `labels=[[str, ...] or None, ...]` among the render options, one list per image, every finished frame (after the resize,
+        before the copy back or the encode) gets its list written on it as the reference's draw_labels writes a video frame's
+        (keypoints/text.py: loc="tl", alpha=0.6, font_scale=0.5), all frames of a batch in ONE hh_text_labels_u8_batch launch.
         `tracker` = a keypoints.tracking.PoseTracker with one stream: `raw_images` are consecutive frames of ONE clip.  All must share
         one model-input shape (else ValueError, before any launch) and that of the frames the tracker saw before (else reset() it).  The
         chunks are fed in order, each as one hh_track_step behind its hh_decode on the same stream with frames_per_stream = the chunk
@@ -517,9 +520,11 @@ class InferenceKeypointsModel:
         if render is not None and render.get("color_mode") == "track" and tracker is None:
             raise ValueError("infer_images: render color_mode 'track' needs a tracker")
         if render is not None:
-            unknown = set(render) - {"color_mode", "alpha", "bgr", "out_height", "jpeg"}
+            unknown = set(render) - {"color_mode", "alpha", "bgr", "out_height", "jpeg", "labels"}
             if unknown:
                 raise ValueError(f"infer_images: unknown render option(s) {sorted(unknown)}")
+            if render.get("labels") is not None and len(render["labels"]) != len(raw_images):
+                raise ValueError("infer_images: render labels: one list of strings (or None) per image")
         from . import jpeg as jp
         raw_images = [jp.JpegImage(img, index="device") if isinstance(img, (bytes, bytearray, memoryview)) else img for img in raw_images]
         n = len(raw_images)
@@ -578,7 +583,10 @@ class InferenceKeypointsModel:
                     results[i].track_ids = host_out[4][j, :p].numpy().copy()
                     results[i].kpts_coords_smooth = transform_coords(host_out[5][j, :p].numpy(), geo[i][1], geo[i][2], (w, h)).astype(coords.dtype)
             if staged is not None:
-                self._render_chunk([results[i] for i in chunk], *staged, **render)
+                options = dict(render)
+                if options.get("labels") is not None:
+                    options["labels"] = [render["labels"][i] for i in chunk]
+                self._render_chunk([results[i] for i in chunk], *staged, **options)
 
         # Two-deep software pipeline: while the GPU works on batch k the host stages the pixels of batch k+1 into a pinned
         # buffer and only then collects the results of batch k (two staging buffers, each guarded by the event of its last use).
@@ -714,10 +722,11 @@ class InferenceKeypointsModel:
         return results
 
     def _render_chunk(self, results: list, raw: Tensor, offs, color_mode: str = "person", alpha: float = 0.8, bgr: bool = False,
-                      out_height: int | None = None, jpeg: dict | None = None) -> None:
+                      out_height: int | None = None, jpeg: dict | None = None, labels: list | None = None) -> None:
         """`.rendered` of the results of one batch: one render launch on the batch's staged pixels (`raw`: the device copy of the
         staging buffer, image j's h * w * 3 bytes from offs[j]), the optional resizes, one pinned buffer back.  With `jpeg`:
-        `.rendered_jpeg` instead, one encode call on the device frames, only the compressed bytes back."""
+        `.rendered_jpeg` instead, one encode call on the device frames, only the compressed bytes back.  With `labels` (one list of
+        strings or None per result): one text launch on the finished device frames in front of either."""
         from . import visualization as vz
         cur = torch.cuda.current_stream(self.device)
         raw.record_stream(cur)
@@ -731,6 +740,10 @@ class InferenceKeypointsModel:
         out = vz.render_frames_device(frames, tables, alpha, bgr)
         if out_height is not None:
             out = [f if f.shape[0] == out_height else vz.resize_device(f, int(out_height * f.shape[1] / f.shape[0]), out_height) for f in out]
+        if labels is not None:
+            from . import text as tx
+            tx.put_txt_device(out, [tx.video_table(int(f.shape[0]), int(f.shape[1]), lines) if lines is not None else np.zeros(0, tx.PRIM)
+                                    for f, lines in zip(out, labels)])
         if jpeg is not None:
             from .jpeg import encode_jpeg_device
             for r, data in zip(results, encode_jpeg_device(out, bgr=bgr, **jpeg)):
@@ -768,8 +781,8 @@ class InferenceKeypointsModel:
             return result
         return self._on_fast_stream(run)
 
-    def video_frame(self, image: np.ndarray, tracker=None, jpeg: dict | None = None):
-        """`video_processing_fn` (keypoints/bin/inference.py:49-75) without its text labels -> (result, out_frame): one inference,
+    def video_frame(self, image: np.ndarray, tracker=None, jpeg: dict | None = None, labels: list | None = None):
+        """`video_processing_fn` (keypoints/bin/inference.py:49-75) -> (result, out_frame): one inference,
         the people ordered by their mean tag (same colours for the same person from frame to frame), limb colours at alpha 0.65 with
         thr = det_thr, B,G,R order, resized to height 640 (new_w = int(640 * w / h); no resize launch when h == 640).  The frame is
         drawn from the uint8 pixels prepare_input already put on the device: the raw image crosses PCIe once, the finished frame
@@ -779,7 +792,11 @@ class InferenceKeypointsModel:
         person in the colour of its id (color_mode "track") instead of the tag order and the limb colours.
         `jpeg` = dict(quality=90, subsampling="420") (an extension): out_frame is the 640-high frame as a JFIF stream (bytes), encoded on the
         GPU (keypoints/jpeg.py) with bgr=True, so that the stream holds the true colours; what `MJPEGWriter.write` takes.  The raw frame
-        is not copied back."""
+        is not copied back.
+        `labels` = a list of strings (`keypoints.text.video_labels(idx, num_frames, model_input_shape, speed_ms)` gives the reference's):
+        written on the finished 640-high B,G,R frame as InferenceVideoDataset.draw_labels writes them (base/datasets/video.py:168-176:
+        loc="tl", alpha=0.6, font_scale=0.5) by one hh_text_labels_u8_batch launch on the device frame, before it is copied back or
+        encoded: with `jpeg` the labelled frame never exists on the host.  labels=None: no text launch, the frame as before."""
         from . import visualization as vz
         if tracker is not None:
             result = self._call_tracked(image, tracker)
@@ -794,6 +811,9 @@ class InferenceKeypointsModel:
         h, w = raw.shape[:2]
         if h != 640:
             frame = vz.resize_device(frame, int(640 * w / h), 640)
+        if labels is not None:
+            from . import text as tx
+            tx.put_txt_device([frame], [tx.video_table(int(frame.shape[0]), int(frame.shape[1]), labels)])
         if jpeg is not None:
             from .jpeg import encode_jpeg_device
             return result, encode_jpeg_device([frame], bgr=True, **jpeg)[0]

@@ -4,8 +4,8 @@ Stands in for the non-plotting part of `/root/reference/src/keypoints/results.py
 (`InferenceKeypointsResult.from_preds`): stage-heatmap aggregation and decode run fused on
 the GPU (hh_decode), the coordinate un-warp (results.py:158-171,189-201) on the host.
 `plot_connections` / `plot` draw the pose overlay and the heatmap panels on the GPU (keypoints/visualization.py,
-hh_render_poses_u8_batch, hh_heatmap_panels_u8).  OKS helpers, the associative-embedding scatter and text labels are out of scope
-(SURVEY.md §2).
+hh_render_poses_u8_batch, hh_heatmap_panels_u8); text is keypoints/text.py (hh_text_labels_u8_batch).  OKS helpers and the
+associative-embedding scatter are out of scope.
 """
 from __future__ import annotations
 
