@@ -545,6 +545,65 @@ int hh_text_check(const hh_text_desc *descs_host, const hh_text_prim *prims_host
 int hh_text_config(int out[4]);
 int hh_debug_text_host(unsigned char *frame, const hh_text_desc *desc, const hh_text_prim *prims, int num_prims, const unsigned char *atlas,
                        long long atlas_len);
+/* Segmentation overlays: the per-object cv2.fillPoly + cv2.drawContours(thickness 1) + addWeighted(overlay, 0.4, image, 0.6) of the
+ * reference's plot_raw (keypoints/datasets/coco.py:383-398) for n uint8 RGB [h,w,3] frames of mixed sizes in ONE launch, on frames that
+ * are on the device already.  The host forms the tables (keypoints/sample_plot.py seg_tables here); the kernel does the per-pixel
+ * work; the result is bit-identical to this text (tests/seg_overlay_ref.py restates it in numpy).
+ *
+ * The tables.  Shapes: int32 rows of HH_SEG_SHAPE_INTS = 8, {kind, colour = r | g << 8 | b << 16, a, b, c, d, 0, 0}, in draw order.
+ *   HH_SEG_FILL  a = the first toggle as an index into the toggle table, b = the toggle count, c..d = an inclusive column range that
+ *                holds every covered column (used to cull).
+ *   HH_SEG_LINE  (a, b) -> (c, d) = the integer endpoints (xa, ya) -> (xb, yb) as given; they may lie outside the frame and be negative.
+ * Toggles: one uint32 table; a fill's toggles are strictly increasing positions in 0 .. h*w on the column-major pixel index
+ *   idx = x * h + y, the toggle lists of hh_crowd_polygon_toggles above.
+ * The rule.  overlay = image.  The frame's rows are walked in order and a later row overwrites an earlier one: a pixel ends up in the
+ * colour of the LAST row that covers it.
+ *   fill   pixel (x, y) of the h x w frame is covered iff the number of the row's toggles <= x * h + y is odd (the crowd mask's predicate).
+ *   line   dx = |xb - xa|, dy = |yb - ya|; every product in int64; floor_div rounds toward minus infinity.
+ *          dx == dy == 0: the single pixel (xa, ya).
+ *          dx >= dy: the ends are swapped if xa > xb; for x = xa..xb: y = ya + floor_div(2 (x - xa) (yb - ya) + dx, 2 dx).
+ *          otherwise: the ends are swapped if ya > yb; for y = ya..yb: x = xa + floor_div(2 (y - ya) (xb - xa) + dy, 2 dy).
+ *          (The nearest pixel of the minor coordinate, an exact tie toward plus infinity AFTER the swap: a line and its reverse draw the
+ *          same pixels.)  Pixels outside the frame are not drawn.
+ *   blend  over EVERY pixel, covered or not, per channel out = rintf(image * w0 + overlay * w1) in fp32, the two products and the sum
+ *          each rounded on their own, half to even, clamped to 0..255: the blend of hh_render_poses_u8_batch.  w0 is the image's weight,
+ *          w1 the overlay's (keypoints/visualization.py blend_weights(0.4) for the reference's figure).  An uncovered pixel p is therefore
+ *          rintf(p * w0 + p * w1), not p: addWeighted's behaviour, kept.
+ * The frame descriptors: hh_seg_desc ARE hh_render_desc (one definition, no new struct): the source [h,w,3] at batch_base + src_offset,
+ *   the output at batch_base + dst_offset, both tightly packed at any alignment; dst equals src (in place) or does not overlap it;
+ *   the frame's rows shapes[prim_offset .. prim_offset + prim_count); w0, w1; flags bit 0 = store B,G,R; reserved = 0.  Every output
+ *   byte is written exactly once, by one lane, also for prim_count == 0; no atomics; deterministic; nothing outside the frames, the
+ *   tables and the toggles is read.  That the frames of a batch do not overlap ONE ANOTHER, and lie inside the caller's buffer,
+ *   cannot be checked here.
+ * Stated deviations.  cv2.fillPoly's scan conversion and cv2.drawContours' line walk are not available where this is built and are not
+ *   guessed at: parity of the boundary pixels with cv2 is UNPINNED.  The fill is COCO's polygon rule on the truncated vertices shifted
+ *   by +0.5 (an integer vertex is a pixel centre, cv2's convention); with the contour it leaves no pixel uncovered whose centre lies
+ *   strictly inside the polygon (tests/test_sample_plot_cpu.py).  A run-length (iscrowd) object is one fill and no contour; the
+ *   reference turns it into polygons with cv2.findContours first.  Everything in front of the rasteriser IS pinned to the reference by
+ *   tests/golden/sample_plot.npz: which polygons, their truncation, order, colours and the blend weights.
+ * Validation: on the caller's HOST copies (device memory is never read back), before any launch; returns 1 with hh_last_error set for
+ *   a null pointer (the shape and toggle tables may be null when empty), n outside 1..65535, a negative count, a misaligned device
+ *   table (descs_dev 8 bytes, shapes_dev and toggles_dev 4), h or w outside 1..16384, a negative offset, a dst range that partially
+ *   overlaps its src, a row range outside the table, more than HH_SEG_MAX_SHAPES rows in one frame (refused, never capped), an
+ *   unknown kind or flag, a weight that is not finite or above 1e6 in magnitude, a colour above 0xFFFFFF, non-zero reserved ints, a fill
+ *   whose toggle range
+ *   leaves the table, whose toggles are not strictly increasing or exceed h*w, or whose column range is outside the frame or does not
+ *   hold its covered columns, a line endpoint beyond +-2^23.
+ * hh_seg_overlay_config: out[4] = tile rows, tile columns, threads per workgroup, shapes culled per chunk (a workgroup owns one tile
+ *   and walks the frame's rows a chunk at a time, keeping the draw order within and across chunks).
+ * hh_debug_seg_overlay_host: one frame through the same tile walk compiled for the host (src, dst: the frame's own HOST buffers, equal
+ *   or disjoint; the descriptor's offsets are ignored); same validation.  For tests and tools/seg_overlay_host_check.cpp.
+ * (Additive entry points: HH_ABI_VERSION stays 3.)                                                                           */
+#define HH_SEG_SHAPE_INTS 8
+#define HH_SEG_MAX_SHAPES 65535 /* per frame; refused, never capped */
+enum { HH_SEG_FILL = 0, HH_SEG_LINE = 1 };
+typedef hh_render_desc hh_seg_desc;
+int hh_seg_overlay_u8_batch(unsigned char *batch_base, const hh_seg_desc *descs_dev, const hh_seg_desc *descs_host, const int32_t *shapes_dev,
+                            const int32_t *shapes_host, int num_shapes, const unsigned int *toggles_dev, const unsigned int *toggles_host,
+                            long long num_toggles, int n, void *stream);
+int hh_seg_overlay_config(int out[4]);
+int hh_debug_seg_overlay_host(const unsigned char *src, unsigned char *dst, const hh_seg_desc *desc, const int32_t *shapes, int num_shapes,
+                              const unsigned int *toggles, long long num_toggles);
 /* Heatmap panels: plot_heatmaps + make_grid of the reference (keypoints/visualization.py:93-110, utils/image.py:15-38) for every grid
  * of one figure in ONE call (one min/max launch, skipped when no map asks for it, and one paint launch), from the stage outputs of the
  * net as they are: no full-resolution fp32 map is stored or copied to the host.  tests/panels_ref.py restates the rule in numpy /

@@ -13,6 +13,7 @@
 #include "ema_math.h"
 #include "render_math.h"
 #include "text_math.h"
+#include "seg_overlay_math.h"
 #include "panel_math.h"
 #include "coco_eval_math.h"
 #include "crowd_mask_math.h"
@@ -455,6 +456,64 @@ int hh_debug_text_host(unsigned char *frame, const hh_text_desc *desc, const hh_
     std::vector<TextTile> tiles(seen.size());
     const long long nt = text_list_tiles(d, prims, 0, seen.data(), tiles.data(), (long long)tiles.size());
     text_debug_host(frame, d, prims, atlas, tiles.data(), nt);
+    return 0;
+}
+
+// Segmentation overlays (seg_overlay.hip, seg_overlay_math.h).
+int hh_seg_overlay_config(int out[4])
+{
+    if (!out) { hh_set_error("hh_seg_overlay_config: null pointer"); return 1; }
+    out[0] = SEG_TH, out[1] = SEG_TW, out[2] = SEG_THREADS, out[3] = SEG_CHUNK;
+    return 0;
+}
+
+// The checks of an overlay call that need no device: every frame's descriptor, its shape rows and their toggles, on the caller's host copies.
+static int seg_check(const char *fn, const hh_seg_desc *descs_host, const int32_t *shapes_host, int num_shapes, const unsigned int *toggles_host,
+                     long long num_toggles, int n, int *max_tiles)
+{
+    if (n <= 0 || n > 65535) { hh_set_error(std::string(fn) + ": need 0 < n <= 65535"); return 1; }
+    if (num_shapes < 0 || num_toggles < 0) { hh_set_error(std::string(fn) + ": negative table length"); return 1; }
+    if (!descs_host || (num_shapes > 0 && !shapes_host) || (num_toggles > 0 && !toggles_host)) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    int tiles = 1;
+    for (int b = 0; b < n; ++b) {
+        const SegDesc &d = descs_host[b];
+        const char *why = seg_check_frame(d, reinterpret_cast<const SegShape *>(shapes_host), num_shapes, toggles_host, num_toggles);
+        if (why) { hh_set_error(std::string(fn) + ": frame " + std::to_string(b) + ": " + why); return 1; }
+        tiles = std::max(tiles, ((d.h + SEG_TH - 1) / SEG_TH) * ((d.w + SEG_TW - 1) / SEG_TW));
+    }
+    *max_tiles = tiles;
+    return 0;
+}
+
+int hh_seg_overlay_u8_batch(unsigned char *batch_base, const hh_seg_desc *descs_dev, const hh_seg_desc *descs_host, const int32_t *shapes_dev,
+                            const int32_t *shapes_host, int num_shapes, const unsigned int *toggles_dev, const unsigned int *toggles_host,
+                            long long num_toggles, int n, void *stream)
+{
+    const char *fn = "hh_seg_overlay_u8_batch";
+    if (!batch_base || !descs_dev || !descs_host || (num_shapes > 0 && !shapes_dev) || (num_toggles > 0 && !toggles_dev)) {
+        hh_set_error(std::string(fn) + ": null pointer");
+        return 1;
+    }
+    if ((uintptr_t)descs_dev % 8 || (uintptr_t)shapes_dev % 4 || (uintptr_t)toggles_dev % 4) {
+        hh_set_error(std::string(fn) + ": descs_dev must be 8-byte, shapes_dev and toggles_dev 4-byte aligned");
+        return 1;
+    }
+    int max_tiles = 0;
+    if (seg_check(fn, descs_host, shapes_host, num_shapes, toggles_host, num_toggles, n, &max_tiles)) return 1;
+    HH_CHECK_HIP(launch_seg_overlay(batch_base, descs_dev, shapes_dev, toggles_dev, n, max_tiles, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_debug_seg_overlay_host(const unsigned char *src, unsigned char *dst, const hh_seg_desc *desc, const int32_t *shapes, int num_shapes,
+                              const unsigned int *toggles, long long num_toggles)
+{
+    const char *fn = "hh_debug_seg_overlay_host";
+    if (!src || !dst) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    int max_tiles = 0;
+    if (seg_check(fn, desc, shapes, num_shapes, toggles, num_toggles, 1, &max_tiles)) return 1;
+    const long long bytes = (long long)desc->h * desc->w * 3;
+    if (src != dst && src < dst + bytes && dst < src + bytes) { hh_set_error(std::string(fn) + ": dst partially overlaps src"); return 1; }
+    seg_frame_host(src, dst, *desc, reinterpret_cast<const SegShape *>(shapes), toggles);
     return 0;
 }
 

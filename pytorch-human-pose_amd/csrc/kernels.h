@@ -366,6 +366,9 @@ hipError_t launch_resize_u8_scaled(const unsigned char *src, int h, int w, int c
 hipError_t launch_text_labels(unsigned char *base, const hh_text_desc *descs, const hh_text_prim *prims, const uint8_t *atlas, const void *tiles,
                               long long num_tiles, hipStream_t s);
 void text_debug_host(unsigned char *frame, const hh_text_desc &d, const hh_text_prim *prims, const uint8_t *atlas, const void *tiles, long long num_tiles);
+// Segmentation overlays (hh_seg_desc and the shape rows of include/hhrnet.h; arithmetic, host walk and validation in seg_overlay_math.h,
+// kernel in seg_overlay.hip): n frames in one launch, `max_tiles` = the largest frame's tile count.
+hipError_t launch_seg_overlay(unsigned char *base, const hh_seg_desc *descs, const int32_t *shapes, const unsigned int *toggles, int n, int max_tiles, hipStream_t s);
 // Baseline JPEG (hh_jpeg_desc of include/hhrnet.h; struct and arithmetic in jpeg_math.h, kernels in jpeg.hip): n frames in three
 // launches, `max_mcus` / `max_rows` = the largest frame's MCU count / MCU rows.
 hipError_t launch_jpeg_encode(unsigned char *base, const hh_jpeg_desc *descs, int n, int max_mcus, int max_rows, unsigned char *ws, int32_t *lengths,

@@ -14,3 +14,5 @@ from .jpeg import JpegImage, JpegIndexCache, MJPEGReader, MJPEGWriter, build_jpe
 from .visualization import DEFAULT_PALETTE, build_primitives, jet_lut, plot_connections, plot_heatmaps
 from . import text
 from .text import layout_put_txt, load_font, put_txt, put_txt_device, put_txt_host, text_size, video_labels
+from . import sample_plot
+from .sample_plot import plot_examples, plot_examples_jpeg, plot_raw, plot_sample, plot_segmentations, seg_tables

@@ -390,6 +390,33 @@ class TrainInput:
                 device_joints.append(dj)
         return images, heatmaps, masks, device_joints
 
+    def plot_examples(self, annotated, params=None, names=None, nrows: int = 1, stage_idxs=(1, 0), labels=None, device_out: bool = False):
+        """The figure the reference's DatasetExamplesCallback logs (CocoKeypointsDataset.plot_examples, coco.py:372-449), from a batch
+        built here.  annotated: [(image or jpeg.JpegImage, COCO annotation list)], or (image, annot, dense bool crowd mask) to ship that
+        mask instead of the annotation's segments.  Raw samples are made with crowd_mask.raw_sample, `params` are drawn with
+        `self.train.choose` when none are given, `build` makes the batch, `geometry` gives the per-stage integer joints, and
+        keypoints/sample_plot.py composes the figure on the device.  `names`: the file stems shown in the labels.
+        Mosaic samples are not plotted (a mosaic has no single raw image for the raw pane): with `mosaic_probability > 0` every
+        sample is shown as a plain sample and its augmentation is drawn with `self.train.draw`, without the mosaic's draws.
+        -> uint8 [H,W,3] numpy array, or the device tensor with `device_out` (for jpeg.encode_jpeg_device / save_jpeg)."""
+        from . import sample_plot as sp
+        from .visualization import to_host
+        raws = []
+        for entry in annotated:
+            h, w = _hw(entry[0])
+            _, segments, joints = cm.raw_sample(np.empty((h, w, 0), np.uint8), entry[1], self.num_kpts)  # (only the size is read)
+            raws.append((entry[0], entry[2] if len(entry) > 2 else segments, joints))
+        if params is None:  # (choose makes no draw besides the samples' own when mosaic_probability == 0)
+            params = self.train.choose(raws)[1] if self.mosaic_probability == 0 else [self.train.draw(*_hw(r[0])) for r in raws]
+        images, heatmaps, masks, _ = self.build(raws, params)
+        items = []
+        for b, (entry, raw, p) in enumerate(zip(annotated, raws, params)):
+            ints = self.geometry(*_hw(raw[0]), raw[2], p)[3]
+            sample = (images[b], [hm[b] for hm in heatmaps], [m[b] for m in masks], ints)
+            items.append((entry[0], entry[1], sample, str(names[b]) if names is not None else f"{b:012d}"))
+        figure = sp.plot_examples_device(items, nrows, stage_idxs, sp.COCO_LABELS if labels is None else labels)
+        return figure if device_out else to_host(figure)
+
     def jpeg_status(self, check: bool = True) -> np.ndarray:
         """The decoder's statuses of the last build's JpegImage samples, in batch order (tiles of a mosaic in tile order): int32 [n], 0 =
         decoded.  This is the read `build` does not do: it waits for the build's work.  `check`: a nonzero status raises HHError naming
