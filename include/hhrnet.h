@@ -1090,6 +1090,93 @@ int hh_track_similarity(const hh_track_params *params, void *state, const float 
 int hh_track_assign(const double *sim, const int32_t *ids, int n, int T, int P, double min_oks, int32_t *match, void *stream);
 int hh_track_assign_host(const double *sim, const int32_t *ids, int n, int T, int P, double min_oks, int32_t *match);
 
+/* Per-image OKS and PCKh against annotations, scored behind hh_decode (csrc/pose_score.hip, csrc/pose_score_math.h;
+ * keypoints/pose_score.py): the reference's match_preds_to_targets (keypoints/results.py:21-43), object_OKS / image_OKS
+ * (keypoints/datasets/coco.py:489-535, what InferenceKeypointsResult.calculate_OKS prints) and object_PCKh / image_PCKh
+ * (keypoints/datasets/mpii.py) for every image of a batch in ONE launch, one workgroup per image, on hh_decode's device outputs
+ * before they are copied anywhere.  This text is the specification.  All arithmetic is fp64, every operation rounds on its own
+ * (compiled with -ffp-contract=off), every sum runs in the stated order.  (Additive entry points: HH_ABI_VERSION stays 3.)
+ *
+ * TABLES of image i < B.
+ *   Predictions, `form`:
+ *   HH_POSE_PRED_DECODE: hh_decode's outputs in place.  P_i = min(num[i], max_people), and num[i] < 0 counts as 0.  Joint k of person p
+ *     is the two floats x, y at joints[i * image_stride + p * person_stride + k * joint_stride] (strides in floats); the person score is
+ *     scores[i * score_stride + p]; flags may be NULL (= all 0).  inv_affine [B,6] fp64 is the image's inverse resize matrix M, formed
+ *     by the host exactly as hh_transform_coords forms it (hh_get_affine_transform(..., inverse = 1, M)).  Un-warp, left to right:
+ *       x' = M0*x + M1*y + M2*1.0,  y' = M3*x + M4*y + M5*1.0     with x, y widened to fp64 first.
+ *     x', y' are rounded to float32 and widened again unless HH_DECODE_FALLBACK is set in flags[i]: transform_coords(...).astype(dtype)
+ *     gives float32 normally and float64 for the fallback pseudo-person.  In the fallback case the person score is the fp64 mean of K
+ *     values 0.01 (ascending sum divided by K), as MPPEHeatmapParser.to_lists forms it.
+ *   HH_POSE_PRED_F64: P_i = p_off[i+1] - p_off[i]; p_xy fp64 [P,K,2] and p_score fp64 [P], contiguous, used as they are (results that
+ *     already sit on the host; validation results, whose coordinates are model-input pixels).
+ *   Targets: rows t_off[i] .. t_off[i+1]-1 of t_xyv fp64 [T,K,3] (x, y, v), t_area fp64 [T] (the packer's polygon area + 2^-52) and
+ *     t_head fp64 [T] (the PCKh head size, 0 when unused).
+ *   Per call: vars[K] = (2 sigma_k)^2, formed by the caller; alpha = the PCKh threshold; metric = HH_POSE_METRIC_OKS or _PCKH.
+ *
+ * RULE for one image with P predictions and T targets; d2(p,t,k) = dx*dx + dy*dy with dx = px - tx, dy = py - ty.
+ *   0. status = HH_POSE_NONFINITE if an un-warped coordinate (DECODE) or p_xy value (F64) of a person p < P, or a person score, is not
+ *      finite; | HH_POSE_NO_PRED if P = 0 and T > 0.  With status != 0: value = NaN, and obj = NaN, kpt = NaN, match = -1 for every
+ *      target of the image; never a silent score.  Otherwise:
+ *   1. Walk order of the predictions: ascending person score, stable (equal scores by ascending index): argsort(kind="mergesort").
+ *   2. Matching.  n_t = #{k : v_tk > 0}.  D[p,t] = (sum over k with v_tk > 0, ascending k, of d2(p,t,k)) / n_t;  val = 1.0 / D (D = 0
+ *      gives +inf).  Target t takes the first prediction in walk order whose val is strictly greater than every earlier one, starting
+ *      from -inf.  Several targets may take the same prediction.  match[t] = that prediction's index in decode order.
+ *   3. HH_POSE_METRIC_OKS, target t with p = match[t]:  e_k = d2(p,t,k) / ((2.0 * vars[k]) * area_t);  kpt[t,k] = exp(-e_k) for
+ *      v_tk > 0, else -1;  obj[t] = oks_t = (sum of exp(-e_k) over the k with v_tk > 0, ascending) / n_t.
+ *   4. HH_POSE_METRIC_PCKH: if head_t == 0, obj[t] = -1 and kpt[t,k] = -1 for all k.  Otherwise
+ *      d_k = sqrt((px/h - tx/h)*(px/h - tx/h) + (py/h - ty/h)*(py/h - ty/h)),  hit_k = d_k < alpha;  kpt[t,k] = hit_k (1.0 or 0.0) for
+ *      v_tk > 0, else -1;  obj[t] = pckh_t = (number of hits over the k with v_tk > 0) / n_t.
+ *   5. Image value.  OKS: r_t = rint(oks_t * 1000.0) / 1000.0 (numpy's round(3); rint = to nearest, ties to even); value = (sum of r_t,
+ *      ascending t) / T.  PCKh: value = (sum of the pckh_t that are not -1, ascending t) / their number.  value = -1 when no target counts.
+ * Two stated differences from the reference: the sums run in ascending order where numpy sums pairwise from 8 elements up; the
+ * matched order is returned (match) instead of reordering the predictions in place.  exp is each side's library function.
+ *
+ * hh_polygon_area: the reference's cv2.contourArea(np.array(poly).reshape(-1, 2).astype(np.int32)) restated as an exact int64
+ *   shoelace: with (x_j, y_j) = the n points of xy [n,2] truncated toward zero, |sum over j of x_prev*y_j - y_prev*x_j| * 0.5, prev = j-1
+ *   cyclically; 0 for n < 3 (cv2 returns 0 for an empty contour; a 1- or 2-point contour has no area).  Host code: packing happens on
+ *   the host and polygons have variable length.  Parity with cv2 itself is UNPINNED (cv2 is absent where the fixtures are made).
+ *   Returns 1 for a null xy with n > 0, negative n, or a coordinate that is not finite or outside +-2^30.
+ *
+ * OUTPUTS (device): value fp64 [B]; obj fp64 [T_all], unrounded; kpt fp64 [T_all,K]; match int32 [T_all]; status int32 [B], with
+ *   T_all = t_off[B].  Every element is written exactly once; nothing is carried between calls; deterministic.
+ * hh_pose_score_batch: the launch.  The tables are plain arguments: the set of descriptor structs of ABI version 3 is closed.  A
+ *   table whose contents the host must check comes twice, as the device address the kernel reads (`*_dev`) and as the caller's host
+ *   copy of the same values (`*_host`), which is what is checked: device memory is never read back.  joints, scores, num, flags, p_xy,
+ *   p_score exist on the device only.  vars and alpha are host values and travel in the launch's arguments.  The arguments of the form
+ *   that is not chosen are not looked at (pass NULL / 0).
+ * hh_pose_score_host: the same text compiled for the host; every table lies in HOST memory (in either form) and is passed once.
+ * hh_pose_score_config: out = {threads per workgroup, dynamic LDS bytes at the maxima, HH_POSE_MAX_T, HH_POSE_MAX_P}.
+ * Refused with 1 before any launch, hh_last_error naming the image where there is one: a null pointer (flags excepted), an fp64 table
+ *   or output that is not 8-byte aligned, another that is not 4-byte aligned, B < 0 or over 2^24, K outside 1..HH_POSE_MAX_K,
+ *   max_people outside 1..HH_POSE_MAX_P or a negative stride (DECODE), offsets that do not start at 0 or that decrease, an image with
+ *   more than HH_POSE_MAX_T targets or HH_POSE_MAX_P predictions (refused, never capped), a target with no labelled joint, a
+ *   non-finite target value, an area or var that is not finite and > 0, a head size that is not finite and >= 0, a non-finite alpha or
+ *   inverse matrix, an unknown form or metric. */
+#define HH_POSE_MAX_T 128 /* targets per image */
+#define HH_POSE_MAX_P 64  /* predictions per image */
+#define HH_POSE_MAX_K 64
+enum { HH_POSE_PRED_DECODE = 0, HH_POSE_PRED_F64 = 1 };
+enum { HH_POSE_METRIC_OKS = 0, HH_POSE_METRIC_PCKH = 1 };
+enum { HH_POSE_NONFINITE = 1, HH_POSE_NO_PRED = 2 };
+int hh_pose_score_batch(int form, int metric, int B, int K,
+                        const float *joints, int64_t image_stride, int64_t person_stride, int64_t joint_stride, const float *scores,
+                        int64_t score_stride, const int32_t *num, const int32_t *flags, int max_people, const double *inv_affine_dev,
+                        const double *inv_affine_host,
+                        const int32_t *p_off_dev, const int32_t *p_off_host, const double *p_xy, const double *p_score,
+                        const int32_t *t_off_dev, const int32_t *t_off_host, const double *t_xyv_dev, const double *t_xyv_host,
+                        const double *t_area_dev, const double *t_area_host, const double *t_head_dev, const double *t_head_host,
+                        const double *vars_host, double alpha,
+                        double *value, double *obj, double *kpt, int32_t *match, int32_t *status, void *stream);
+int hh_pose_score_host(int form, int metric, int B, int K,
+                       const float *joints, int64_t image_stride, int64_t person_stride, int64_t joint_stride, const float *scores,
+                       int64_t score_stride, const int32_t *num, const int32_t *flags, int max_people, const double *inv_affine,
+                       const int32_t *p_off, const double *p_xy, const double *p_score,
+                       const int32_t *t_off, const double *t_xyv, const double *t_area, const double *t_head,
+                       const double *vars, double alpha,
+                       double *value, double *obj, double *kpt, int32_t *match, int32_t *status);
+int hh_polygon_area(const double *xy, int n, double *area);
+int hh_pose_score_config(int out[4]);
+
 /* HeatmapGenerator (coco.py:77-121) as a gather over the packed joints the grouping loss takes (hh_loss_ae_grouping: joints int32
  * [B,P,K,3] = x, y, vis from JointsGenerator, coco.py:124-137; num_people [B]): out fp32 [B,K,h,w], each element the maximum over
  * the image's people p < num_people[b] with vis > 0 and (x, y) inside the map of table[y - y_p + reach][x - x_p + reach] where that

@@ -16,6 +16,7 @@
 #include "seg_overlay_math.h"
 #include "panel_math.h"
 #include "coco_eval_math.h"
+#include "pose_score_math.h"
 #include "crowd_mask_math.h"
 #include "track_math.h"
 #include "jpeg_math.h"
@@ -1198,6 +1199,93 @@ int hh_track_assign_host(const double *sim, const int32_t *ids, int n, int T, in
 {
     if (track_assign_check("hh_track_assign_host", sim, ids, n, T, P, min_oks, match)) return 1;
     for (int m = 0; m < n; ++m) track_assign_host(sim + (size_t)m * T * P, ids + (size_t)m * T, T, P, min_oks, match + (size_t)m * T, nullptr);
+    return 0;
+}
+
+// The checks of a pose scoring call that need no device: the host copies' contents (pose_check) and the alignment of every pointer that
+// will be dereferenced.  `dev`: the addresses the kernel reads (for the host entry point the same struct as `host`).
+static int pose_args_check(const char *fn, const PoseTables &dev, const PoseTables &host, const double *vars, const double *value, const double *obj,
+                           const double *kpt, const int32_t *match, const int32_t *status)
+{
+    auto fail = [&](const char *why) { hh_set_error(std::string(fn) + ": " + why); return 1; };
+    if (!vars || !value || !obj || !kpt || !match || !status) return fail("null pointer");
+    char msg[192];
+    if (const char *why = pose_check(host, msg, sizeof msg)) return fail(why);
+    const bool decode = host.form == HH_POSE_PRED_DECODE;
+    const void *p8[] = {value, obj, kpt, dev.t_xyv, dev.t_area, dev.t_head, decode ? (const void *)dev.inv_affine : dev.p_xy, decode ? nullptr : dev.p_score};
+    const void *p4[] = {match, status, dev.t_off, decode ? (const void *)dev.joints : dev.p_off, decode ? (const void *)dev.scores : dev.p_off,
+                        decode ? (const void *)dev.num : dev.p_off};
+    for (const void *p : p8)
+        if ((uintptr_t)p % 8) return fail("an fp64 table or output is not 8-byte aligned");
+    for (const void *p : p4)
+        if ((uintptr_t)p % 4) return fail("a 4-byte table or output is not 4-byte aligned");
+    if (decode ? (!dev.joints || !dev.scores || !dev.num || !dev.inv_affine) : (!dev.p_off || !dev.p_xy || !dev.p_score)) return fail("null pointer");
+    if (!dev.t_off || !dev.t_xyv || !dev.t_area || !dev.t_head) return fail("null pointer");
+    if (decode && (uintptr_t)dev.flags % 4) return fail("a 4-byte table or output is not 4-byte aligned");
+    return 0;
+}
+static PoseTables pose_tables(int form, int metric, int B, int K, const float *joints, int64_t image_stride, int64_t person_stride, int64_t joint_stride,
+                              const float *scores, int64_t score_stride, const int32_t *num, const int32_t *flags, int max_people, const double *inv_affine,
+                              const int32_t *p_off, const double *p_xy, const double *p_score, const int32_t *t_off, const double *t_xyv, const double *t_area,
+                              const double *t_head, const double *vars, double alpha)
+{
+    PoseTables t = {};
+    t.joints = joints, t.scores = scores, t.num = num, t.flags = flags, t.inv_affine = inv_affine;
+    t.p_off = p_off, t.p_xy = p_xy, t.p_score = p_score;
+    t.t_off = t_off, t.t_xyv = t_xyv, t.t_area = t_area, t.t_head = t_head;
+    for (int k = 0; k < HH_POSE_MAX_K; ++k) t.vars[k] = vars && k < K && K <= HH_POSE_MAX_K ? vars[k] : 1.0;
+    t.alpha = alpha;
+    t.image_stride = image_stride, t.person_stride = person_stride, t.joint_stride = joint_stride, t.score_stride = score_stride;
+    t.B = B, t.K = K, t.form = form, t.metric = metric, t.max_people = max_people;
+    return t;
+}
+
+int hh_pose_score_batch(int form, int metric, int B, int K, const float *joints, int64_t image_stride, int64_t person_stride, int64_t joint_stride,
+                        const float *scores, int64_t score_stride, const int32_t *num, const int32_t *flags, int max_people, const double *inv_affine_dev,
+                        const double *inv_affine_host, const int32_t *p_off_dev, const int32_t *p_off_host, const double *p_xy, const double *p_score,
+                        const int32_t *t_off_dev, const int32_t *t_off_host, const double *t_xyv_dev, const double *t_xyv_host, const double *t_area_dev,
+                        const double *t_area_host, const double *t_head_dev, const double *t_head_host, const double *vars_host, double alpha, double *value,
+                        double *obj, double *kpt, int32_t *match, int32_t *status, void *stream)
+{
+    const char *fn = "hh_pose_score_batch";
+    const PoseTables dev = pose_tables(form, metric, B, K, joints, image_stride, person_stride, joint_stride, scores, score_stride, num, flags, max_people,
+                                       inv_affine_dev, p_off_dev, p_xy, p_score, t_off_dev, t_xyv_dev, t_area_dev, t_head_dev, vars_host, alpha);
+    const PoseTables host = pose_tables(form, metric, B, K, nullptr, image_stride, person_stride, joint_stride, nullptr, score_stride, nullptr, nullptr, max_people,
+                                        inv_affine_host, p_off_host, nullptr, nullptr, t_off_host, t_xyv_host, t_area_host, t_head_host, vars_host, alpha);
+    if (pose_args_check(fn, dev, host, vars_host, value, obj, kpt, match, status)) return 1;
+    int max_P = max_people;
+    if (form == HH_POSE_PRED_F64) {
+        max_P = 1;  // (an LDS array of no bytes is never indexed, but keep its address distinct from the wave slots')
+        for (int i = 0; i < B; ++i) max_P = std::max(max_P, p_off_host[i + 1] - p_off_host[i]);
+    }
+    HH_CHECK_HIP(launch_pose_score(dev, max_P, value, obj, kpt, match, status, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_pose_score_host(int form, int metric, int B, int K, const float *joints, int64_t image_stride, int64_t person_stride, int64_t joint_stride,
+                       const float *scores, int64_t score_stride, const int32_t *num, const int32_t *flags, int max_people, const double *inv_affine,
+                       const int32_t *p_off, const double *p_xy, const double *p_score, const int32_t *t_off, const double *t_xyv, const double *t_area,
+                       const double *t_head, const double *vars, double alpha, double *value, double *obj, double *kpt, int32_t *match, int32_t *status)
+{
+    const char *fn = "hh_pose_score_host";
+    const PoseTables t = pose_tables(form, metric, B, K, joints, image_stride, person_stride, joint_stride, scores, score_stride, num, flags, max_people, inv_affine,
+                                     p_off, p_xy, p_score, t_off, t_xyv, t_area, t_head, vars, alpha);
+    if (pose_args_check(fn, t, t, vars, value, obj, kpt, match, status)) return 1;
+    pose_score_host(t, value, obj, kpt, match, status);
+    return 0;
+}
+
+int hh_polygon_area(const double *xy, int n, double *area)
+{
+    if (!area) { hh_set_error("hh_polygon_area: null pointer"); return 1; }
+    if (pose_polygon_area(xy, n, area)) { hh_set_error("hh_polygon_area: null xy, negative n, or a coordinate that is not finite or outside +-2^30"); return 1; }
+    return 0;
+}
+
+int hh_pose_score_config(int out[4])
+{
+    if (!out) { hh_set_error("hh_pose_score_config: null pointer"); return 1; }
+    out[0] = POSE_THREADS, out[1] = (int)pose_lds_bytes(HH_POSE_MAX_P, HH_POSE_MAX_K), out[2] = HH_POSE_MAX_T, out[3] = HH_POSE_MAX_P;
     return 0;
 }
 

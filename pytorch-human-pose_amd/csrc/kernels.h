@@ -404,6 +404,12 @@ hipError_t launch_track_similarity(const hh_track_params &p, void *state, const 
 hipError_t launch_track_assign(const double *sim, const int32_t *ids, int n, int T, int P, double min_oks, int32_t *match, hipStream_t s);
 void track_step_host(const hh_track_params &p, void *state, const float *joints, const float *scores, const int32_t *num_people, const int32_t *flags, int S, int F,
                      int32_t *track_ids, float *smooth, int32_t *out_flags);
+// Per-image OKS / PCKh against annotations behind the decode (hh_pose_score_batch of include/hhrnet.h; tables, arithmetic and validation in
+// pose_score_math.h, kernel in pose_score.hip): B images in one launch, `max_P` = the largest prediction count an image can have (sizes
+// the LDS); the same on the host.
+struct PoseTables;
+hipError_t launch_pose_score(const PoseTables &t, int max_P, double *value, double *obj, double *kpt, int32_t *match, int32_t *status, hipStream_t s);
+void pose_score_host(const PoseTables &t, double *value, double *obj, double *kpt, int32_t *match, int32_t *status);
 // Crowd masks from toggle lists (hh_crowd_mask_desc / hh_crowd_seg_desc of include/hhrnet.h; structs, predicate, tile walk and the host's
 // polygon walk in crowd_mask_math.h, kernel in crowd_mask.hip): n masks in one launch, `max_tiles` = the largest mask's tile count.
 hipError_t launch_crowd_masks(unsigned char *base, const hh_crowd_mask_desc *descs, const hh_crowd_seg_desc *segs, int n, int max_tiles, hipStream_t s);

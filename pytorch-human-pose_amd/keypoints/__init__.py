@@ -16,3 +16,5 @@ from . import text
 from .text import layout_put_txt, load_font, put_txt, put_txt_device, put_txt_host, text_size, video_labels
 from . import sample_plot
 from .sample_plot import plot_examples, plot_examples_jpeg, plot_raw, plot_sample, plot_segmentations, seg_tables
+from . import pose_score
+from .pose_score import image_OKS, image_PCKh, match_preds_to_targets, object_OKS, object_PCKh, pack_targets

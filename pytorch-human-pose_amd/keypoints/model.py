@@ -15,7 +15,7 @@ from torch import Tensor, nn
 from .. import _lib
 from ..optim import clip_grad_norm_
 from .grouping import MPPEHeatmapParser
-from .results import InferenceKeypointsResult, transform_coords
+from .results import InferenceKeypointsResult, inverse_affine, transform_coords
 
 from .transforms_utils import COCO_FLIP_INDEX, IMAGENET_MEAN, IMAGENET_STD, dst_to_src_matrix, get_multi_scale_size
 
@@ -310,6 +310,7 @@ class InferenceKeypointsModel:
         self._copy_stream = None  # infer_images: host -> device of the next batch's pixels
         self._d2h_stream = None   # infer_images: result copies, beside the next batch's launches
         self._out_ring: dict = {}  # infer_images: pinned result buffers per pipeline slot and shape
+        self._score_stage = None  # infer_images(score=...): pinned buffers of the target tables, one per pipeline slot
         if ckpt_path is not None:
             self.load_checkpoint(ckpt_path)
 
@@ -478,7 +479,7 @@ class InferenceKeypointsModel:
 
     @torch.no_grad()
     def infer_images(self, raw_images: list[np.ndarray], annots: list | None = None, max_batch: int = 32,
-                     scales=None, render: dict | None = None, tracker=None) -> list[InferenceKeypointsResult]:
+                     scales=None, render: dict | None = None, tracker=None, score: str | None = None) -> list[InferenceKeypointsResult]:
         """The batched path behind the reference's single-image interface (`__call__` per image, bin/eval.py:18-49): images are
         bucketed by model-input shape, every bucket runs as batches of up to `max_batch` -- ONE host->device copy of the raw
         uint8 pixels, hh_preprocess_u8 per image into one [B,3,h,w] tensor, one (flip-TTA) forward, one hh_decode, one
@@ -506,6 +507,15 @@ class InferenceKeypointsModel:
         length; ids and smoothed coordinates come back in the batch's one device->host hand-over.  Every result gains `.track_ids`
         (int32 [P], 0 = no track) and `.kpts_coords_smooth` ([P,K,2], raw-image pixels), aligned with its rows.  With tracker=None
         nothing of the pipeline changes.
+        `score` = "oks" or "pckh": every image whose annot is not None is scored against it on the device (keypoints/pose_score.py): ONE
+        hh_pose_score_batch per batch behind its hh_decode (and behind the tracker's launch where there is one) on the same stream, reading
+        the decode's outputs in place with the image's inverse resize matrix (the scale-1 geometry with `scales`); the target tables cross
+        in one small pinned copy, the outputs ride as one more array in the batch's device->host hand-over.  Results gain `.oks`,
+        `.object_oks`, `.kpt_oks`, `.target_matches` (`.pckh`, `.object_pckh`, `.kpt_pckh` for "pckh", whose objects carry "head_xyxy"); a
+        later `calculate_OKS()` returns the stored value.  "oks" uses the COCO constants and is refused for a net of other than 17
+        keypoints, as is a parser that keeps more than 64 people; both before anything is enqueued.  The output array's size is rounded
+        up to a power of two, so the pinned result buffers are shared by batches of different target counts.  A batch without any annot
+        launches nothing; with score=None nothing of the pipeline changes.
         An entry of `raw_images` may also be the `bytes` / `bytearray` / `memoryview` of a JPEG file or a `jpeg.JpegImage`, mixed freely
         with arrays; bytes become `JpegImage(data, index="device")`: no Huffman pass and no pixel array on the host.  Bucketing reads
         `.shape`.  The stream and table block of such an image travel in the batch's one pinned copy, behind the image descriptors; its
@@ -525,7 +535,17 @@ class InferenceKeypointsModel:
                 raise ValueError(f"infer_images: unknown render option(s) {sorted(unknown)}")
             if render.get("labels") is not None and len(render["labels"]) != len(raw_images):
                 raise ValueError("infer_images: render labels: one list of strings (or None) per image")
+        if score not in (None, "oks", "pckh"):
+            raise ValueError(f"infer_images: score must be None, 'oks' or 'pckh', got {score!r}")
         from . import jpeg as jp
+        from . import pose_score as ps
+        if score is not None:  # what the launch would refuse, refused here before anything is enqueued
+            if self._parser.max_num_people > ps.MAX_P:
+                raise ValueError(f"infer_images: score= takes at most HH_POSE_MAX_P ({ps.MAX_P}) people per image, the parser keeps {self._parser.max_num_people}")
+            # "oks" uses the COCO constants and so needs the 17 COCO keypoints (ValueError otherwise); PCKh reads no variance
+            score_vars = ps.coco_variances(self._parser.num_kpts) if score == "oks" else np.ones(self._parser.num_kpts)
+            if self._score_stage is None:
+                self._score_stage = [ps.TableStage(), ps.TableStage()]  # pinned table buffers, one per pipeline slot
         raw_images = [jp.JpegImage(img, index="device") if isinstance(img, (bytes, bytearray, memoryview)) else img for img in raw_images]
         n = len(raw_images)
         annots = annots if annots is not None else [None] * n
@@ -560,7 +580,7 @@ class InferenceKeypointsModel:
 
         def finish(job):
             """device -> host results of one enqueued batch, un-warp, result objects"""
-            chunk, (w, h), x, hms, tags, host_out, done, staged, jpeg_at = job
+            chunk, (w, h), x, hms, tags, host_out, done, staged, jpeg_at, scored = job
             done.synchronize()
             if jpeg_at:  # the decoder's statuses came with the results: the index call's codes, if it ran, behind the decode's
                 codes = host_out[-1].numpy().reshape(-1, len(jpeg_at)).max(axis=0)
@@ -582,6 +602,14 @@ class InferenceKeypointsModel:
                     p = len(joints)
                     results[i].track_ids = host_out[4][j, :p].numpy().copy()
                     results[i].kpts_coords_smooth = transform_coords(host_out[5][j, :p].numpy(), geo[i][1], geo[i][2], (w, h)).astype(coords.dtype)
+            if scored is not None:
+                parts = scored.split(host_out[6 if tracker is not None else 4])
+                t_off = scored.t_off
+                for j, i in enumerate(chunk):
+                    if annots[i] is not None:
+                        a, b = int(t_off[j]), int(t_off[j + 1])
+                        value = float(parts["value"][j])
+                        results[i]._set_score(score, -1 if b == a else value, parts["obj"][a:b], parts["kpt"][a:b], parts["match"][a:b])
             if staged is not None:
                 options = dict(render)
                 if options.get("labels") is not None:
@@ -619,6 +647,12 @@ class InferenceKeypointsModel:
                     dev_total = at
                     ws_offs = np.cumsum([0] + [it.ws_bytes for it in items])
                     jplan = (items, jdesc_off, places, status_off, ws_offs, jp.index_mcus_per_segment(items, "infer_images"))
+                targets = None
+                if score is not None and any(annots[i] is not None for i in chunk):
+                    # the annotations are packed (and refused, if they must be) before anything of this batch is enqueued
+                    targets = ps.pack_targets([annots[i] for i in chunk], score, num_kpts=self._parser.num_kpts)
+                    inv = np.stack([inverse_affine(geo[i][1], geo[i][2], (w, h)) for i in chunk])
+                    targets = (targets, inv, score_vars)
                 self.last_h2d_bytes += total
                 if stage[turn] is None or stage[turn].numel() < total:
                     stage[turn] = torch.empty(total, dtype=torch.uint8).pin_memory()
@@ -659,7 +693,7 @@ class InferenceKeypointsModel:
                     copied.record()
 
                 def run(chunk=chunk, raw=raw, copied=copied, desc_off=desc_off, w=w, h=h, turn=turn, nb=nb, sizes=sizes, subs=subs, offs=starts,
-                        jplan=jplan, jdescs=jdescs, jinfos=jinfos, jpeg_at=jpeg_at):
+                        jplan=jplan, jdescs=jdescs, jinfos=jinfos, jpeg_at=jpeg_at, targets=targets):
                     cur = torch.cuda.current_stream(self.device)
                     cur.wait_event(copied)
                     raw.record_stream(cur)
@@ -688,6 +722,12 @@ class InferenceKeypointsModel:
                     out = self._parser.decode_batch_device(hms[0], hms[1], tags, adjust=True, refine=True)
                     if tracker is not None:
                         out = out + tracker.update_device(*out, frames_per_stream=nb)[:2]
+                    scored = None
+                    if targets is not None:
+                        # (this slot's previous batch has been collected, so its table copy has finished: the pinned buffer is free)
+                        scored = ps.score_device(targets[0], decode=tuple(out[:4]), inv_affine=targets[1], metric=score, variances=targets[2],
+                                                 stage=self._score_stage[turn])
+                        out = tuple(out) + (scored.blob,)
                     if jstatus is not None:
                         out = tuple(out) + (jstatus,)  # (the statuses ride in the same hand-over)
                     # device -> host into pinned buffers kept per pipeline slot (allocating pinned memory costs ~0.4 ms per array);
@@ -707,7 +747,7 @@ class InferenceKeypointsModel:
                     for t in out:
                         t.record_stream(self._d2h_stream)
                     staged = (raw, offs) if render is not None else None  # the batch's device pixels, kept until its render has run
-                    return (chunk, (w, h), x, hms, tags, host_out, done, staged, jpeg_at if jstatus is not None else []), copied, raw
+                    return (chunk, (w, h), x, hms, tags, host_out, done, staged, jpeg_at if jstatus is not None else [], scored), copied, raw
 
                 # (the model's high-priority stream, for batches as for single images: same-box alternation with the caller's
                 # stream, tools/api_throughput.py: 3820 / 3380 against 2600 / 2970 img/s)

@@ -4,8 +4,9 @@ Stands in for the non-plotting part of `/root/reference/src/keypoints/results.py
 (`InferenceKeypointsResult.from_preds`): stage-heatmap aggregation and decode run fused on
 the GPU (hh_decode), the coordinate un-warp (results.py:158-171,189-201) on the host.
 `plot_connections` / `plot` draw the pose overlay and the heatmap panels on the GPU (keypoints/visualization.py,
-hh_render_poses_u8_batch, hh_heatmap_panels_u8); text is keypoints/text.py (hh_text_labels_u8_batch).  OKS helpers and the
-associative-embedding scatter are out of scope.
+hh_render_poses_u8_batch, hh_heatmap_panels_u8); text is keypoints/text.py (hh_text_labels_u8_batch).  `calculate_OKS()` and the
+per-image scores of `infer_images(score=...)` are keypoints/pose_score.py (hh_pose_score_batch).  The associative-embedding scatter
+stays out of scope: it needs a rotated axis label and font sizes the text atlas does not have.
 """
 from __future__ import annotations
 
@@ -27,6 +28,15 @@ def transform_coords(kpts_coords: np.ndarray, center, scale, output_size) -> np.
     _lib.check(_lib.load().hh_transform_coords(xy.ctypes.data, xy.shape[0], float(center[0]), float(center[1]), float(scale[0]),
                                                float(output_size[0]), float(output_size[1]), out.ctypes.data))
     return out.reshape(kpts_coords.shape).astype(kpts_coords.dtype)
+
+
+def inverse_affine(center, scale, output_size) -> np.ndarray:
+    """The 2x3 matrix `transform_coords` applies (hh_get_affine_transform with inverse = 1), row-major float64 [6]: what the DECODE form
+    of hh_pose_score_batch takes per image."""
+    M = np.empty(6, np.float64)
+    _lib.check(_lib.load().hh_get_affine_transform(float(center[0]), float(center[1]), float(scale[0]), float(output_size[0]), float(output_size[1]), 1,
+                                                   M.ctypes.data))
+    return M
 
 
 class KeypointsResult:
@@ -110,6 +120,14 @@ class InferenceKeypointsResult:
     rendered_jpeg: bytes | None = None  # infer_images(render=dict(jpeg=...)): that frame as a JFIF stream, in place of `rendered`
     track_ids: np.ndarray | None = None  # with a PoseTracker: int32 [P], 0 = no track
     kpts_coords_smooth: np.ndarray | None = None  # with a PoseTracker: [P,K,2] raw-image pixels, One-Euro filtered
+    oks: float | None = None  # infer_images(score="oks") or calculate_OKS(): image_OKS against `annot`, -1 without a labelled object
+    object_oks: np.ndarray | None = None  # [T] unrounded OKS of every labelled object of `annot`, in annotation order
+    kpt_oks: np.ndarray | None = None  # [T,K] exp(-e_k) per joint, -1 for an unlabelled joint
+    target_matches: np.ndarray | None = None  # int32 [T]: the row of kpts_coords every labelled object took (the matching is the same
+    # for both metrics: whichever of the OKS / PCKh scorings ran last wrote it, with equal contents)
+    pckh: float | None = None  # infer_images(score="pckh"): image_PCKh against `annot` (objects carry "head_xyxy")
+    object_pckh: np.ndarray | None = None  # [T], -1 for a head of size 0
+    kpt_pckh: np.ndarray | None = None  # [T,K] 1 / 0 per joint, -1 for an unlabelled joint
 
     @property
     def raw_shape(self) -> tuple:
@@ -129,6 +147,28 @@ class InferenceKeypointsResult:
         coords = transform_coords(joints[..., :2], center, scale, (img_w, img_h))
         return cls(raw_image, annot, model_input_image, coords, joints[..., 2], joints[..., 3:], scores, det_thr, tag_thr, limbs,
                    kpts_heatmaps, tags_heatmaps)
+
+    def _set_score(self, metric: str, value: float, obj: np.ndarray, kpt: np.ndarray, match: np.ndarray) -> None:
+        if metric == "oks":
+            self.oks, self.object_oks, self.kpt_oks, self.target_matches = value, obj, kpt, match
+        else:
+            self.pckh, self.object_pckh, self.kpt_pckh, self.target_matches = value, obj, kpt, match
+
+    def calculate_OKS(self) -> float:
+        """results.py:265-298: image_OKS of the predictions matched to the annotation's labelled objects; -1 for an annotation without
+        one.  Computed on first call (hh_pose_score_host on this result's arrays, the F64 form) when the batch did not compute it
+        (`infer_images(score="oks")`).  Unlike the reference nothing is reordered in place: the matched order is `target_matches`."""
+        assert self.annot is not None, "Matching preds to targets is possible only when annotation is set"
+        if self.oks is None:
+            from . import pose_score as ps
+            K = self.kpts_coords.shape[1]
+            targets = ps.pack_targets([self.annot], "oks", num_kpts=K)
+            if targets["t_off"][-1] == 0:
+                self._set_score("oks", -1, np.zeros(0), np.zeros((0, K)), np.zeros(0, np.int32))
+            else:
+                out = ps.score_host(targets, preds=[(self.kpts_coords, self.obj_scores)], metric="oks", variances=ps.coco_variances(K))
+                self._set_score("oks", float(out["value"][0]), out["obj"], out["kpt"], out["match"])
+        return self.oks
 
     def plot_connections(self, color_mode: str = "person", alpha: float = 0.8) -> np.ndarray:
         """The reference's plot_connections on `raw_image` with thr = det_thr -> uint8 [h,w,3], drawn on the GPU."""
@@ -166,7 +206,8 @@ class InferenceKeypointsResult:
     def plot(self) -> dict[str, np.ndarray]:
         """results.py:300-339 as far as it is built here: {"connections": ...} and, when the result holds its stage maps, tags and
         model input, {"heatmaps": ...} (plot_heatmaps_figure).  The reference's "associative_embedding" entry is a matplotlib scatter:
-        out of scope."""
+        out of scope (a rotated axis label and font sizes the text atlas does not have).  The reference also prints calculate_OKS()
+        here when an annotation is set; call it yourself (`result.calculate_OKS()`, or `infer_images(score="oks")`)."""
         plots = {"connections": self.plot_connections()}
         if self._stage_hms is not None and self._tags is not None and self.model_input_image is not None:
             plots["heatmaps"] = self.plot_heatmaps_figure()
