@@ -31,6 +31,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .. import _lib
+from .._stage import PinnedRing, align
 from ..keypoints import jpeg as jp
 from ..keypoints.transforms_utils import IMAGENET_MEAN, IMAGENET_STD
 
@@ -135,9 +136,7 @@ class ClsInput:
         self.out_size, self.device, self.antialias = int(out_size), device, bool(antialias)
         self.resize = int(out_size / resize_ratio)  # transforms.py:26
         self.mean, self.std = np.asarray(mean, np.float32), np.asarray(std, np.float32)
-        self._stage = [None, None]       # pinned staging buffers ...
-        self._stage_free = [None, None]  # ... and the event behind the copy that last read each
-        self._turn = 0
+        self._ring = PinnedRing()  # pinned staging buffers, each with the event behind the copy that last read it
         self.last_h2d_bytes = self.last_launches = 0  # of the last build(): what tools/cls_input_time.py reports
         self._jpeg_status = None  # the device statuses of the last build's JpegImage samples
 
@@ -157,25 +156,13 @@ class ClsInput:
         rh, rw, oy, ox = p             # the whole image resized, a window of it
         return CropWindow(0, 0, height, width, rh, rw, oy, ox, False, self.antialias)
 
-    def _staging(self, total: int):
-        import torch
-        t = self._turn
-        self._turn ^= 1
-        if self._stage[t] is None or self._stage[t].numel() < total:
-            # (a larger buffer replaces the old one; the old one stays alive until its copy has run: torch keeps pinned blocks
-            # that a non_blocking copy still reads)
-            self._stage[t] = torch.empty(total, dtype=torch.uint8).pin_memory()
-        elif self._stage_free[t] is not None:
-            self._stage_free[t].synchronize()  # the copy that last read this buffer has finished
-        return t, self._stage[t]
-
     @staticmethod
     def layout(shapes) -> tuple:
         """Byte layout of the one buffer that crosses, from the (height, width) of every sample's source rectangle (only the crop is
         shipped, not the image around it): the pixels back to back, then (64-byte aligned) the descriptors, then the int64
         targets -> (image offsets, descriptor offset, target offset, total)."""
         offs = np.cumsum([0] + [h * w * 3 for h, w in shapes])
-        desc_off = (int(offs[-1]) + 63) // 64 * 64
+        desc_off = align(int(offs[-1]))
         target_off = desc_off + _CROP_DESC.itemsize * len(shapes)  # 56 B descriptors: a multiple of 8
         return offs, desc_off, target_off, target_off + 8 * len(shapes)
 
@@ -215,15 +202,15 @@ class ClsInput:
             # behind the targets, 16-aligned: [decode descriptors | slice, tables | ...]; behind the staged bytes, on the device only:
             # the pixel slots the decode fills, then its statuses
             plans = [samples[b][0].window_plan((windows[b].top, windows[b].left, *shapes[b])) for b in jpeg_at]
-            jpeg_off = (total + 15) // 16 * 16
-            places = jpeg_off + (jp.WIN_DESC.itemsize * len(jpeg_at) + 15) // 16 * 16 + np.cumsum([0] + [p.staged_bytes for p in plans])
+            jpeg_off = align(total, 16)
+            places = jpeg_off + align(jp.WIN_DESC.itemsize * len(jpeg_at), 16) + np.cumsum([0] + [p.staged_bytes for p in plans])
             total = int(places[-1])
-            pixel_offs = (total + 15) // 16 * 16 + np.cumsum([0] + [(h * w * 3 + 15) // 16 * 16 for h, w in (shapes[b] for b in jpeg_at)])
+            pixel_offs = align(total, 16) + np.cumsum([0] + [align(h * w * 3, 16) for h, w in (shapes[b] for b in jpeg_at)])
             for i, b in enumerate(jpeg_at):
                 image_at[b] = int(pixel_offs[i])
             status_off = int(pixel_offs[-1])
             device_bytes = status_off + 4 * len(jpeg_at)
-        turn, host = self._staging(total)
+        turn, host = self._ring.take(total)
         hview = host.numpy()
         descs = hview[desc_off:target_off].view(_CROP_DESC)
         targets_host = hview[target_off:target_off + 8 * B].view(np.int64)
@@ -254,7 +241,7 @@ class ClsInput:
                 raw = host[:total].to(dev, non_blocking=True)
             copied = torch.cuda.Event()
             copied.record(cur)
-            self._stage_free[turn] = copied
+            self._ring.release(turn, copied)
             self.last_h2d_bytes, self.last_launches = total, 4 if jpeg_at else 1
             images = torch.empty((B, 3, S, S), device=dev, dtype=torch.float32)
             base = raw.data_ptr()

@@ -7,6 +7,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._stage import Block, Layout, fill_frames, frames_to_host
 from ..keypoints import text as tx
 from ..keypoints import visualization as vz
 
@@ -42,7 +43,7 @@ def plot_top_preds(image, probs: np.ndarray, idx2label: dict, k: int = 5, target
     table = top_preds_table(image.shape[0], image.shape[1], probs, idx2label, k, target_label)
     if isinstance(image, torch.Tensor):
         return tx.put_txt_device([image.clone(memory_format=torch.contiguous_format)], [table])[0]
-    return _to_host(_plot_device([np.ascontiguousarray(image, dtype=np.uint8)], lambda frames: [table]))[0]
+    return frames_to_host(_plot_device([np.ascontiguousarray(image, dtype=np.uint8)], lambda frames: [table]))[0]
 
 
 def _resize_512(frame: torch.Tensor) -> torch.Tensor:
@@ -57,29 +58,17 @@ def _plot_device(images: list, tables_of, resize=None) -> list:
     if not torch.cuda.is_available():
         raise _lib.HHError("plot_top_preds needs the GPU: there is no CPU renderer")
     device = torch.device("cuda", torch.cuda.current_device())
-    sizes = np.cumsum([0] + [(im.size + 63) // 64 * 64 for im in images])
-    host = torch.empty(int(sizes[-1]), dtype=torch.uint8).pin_memory()
-    hv = host.numpy()
-    for at, im in zip(sizes, images):
-        if not (im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3):
-            raise ValueError("plot_top_preds: a uint8 [h,w,3] image is needed")
-        np.copyto(hv[at:at + im.size].reshape(im.shape), im)
-    dev = host.to(device, non_blocking=True)
-    frames = [dev[at:at + im.size].view(im.shape) for at, im in zip(sizes, images)]
+    if not all(im.dtype == np.uint8 and im.ndim == 3 and im.shape[2] == 3 for im in images):
+        raise ValueError("plot_top_preds: a uint8 [h,w,3] image is needed")
+    lay = Layout()
+    places = [lay.add(im.size) for im in images]
+    blk = Block(lay.pad(), lay.end, device)
+    fill_frames(blk, images, places)
+    blk.upload()
+    frames = [blk.tensor(at, im.shape) for at, im in zip(places, images)]
     if resize is not None:
         frames = [resize(f) for f in frames]
     return tx.put_txt_device(frames, tables_of(frames))
-
-
-def _to_host(frames: list) -> list:
-    """ONE copy back through one pinned buffer."""
-    sizes = np.cumsum([0] + [f.numel() for f in frames])
-    host = torch.empty(int(sizes[-1]), dtype=torch.uint8, pin_memory=True)
-    for at, f in zip(sizes, frames):
-        host[at:at + f.numel()].view(f.shape).copy_(f, non_blocking=True)
-    torch.cuda.current_stream(frames[0].device).synchronize()
-    hv = host.numpy()
-    return [hv[at:at + f.numel()].reshape(tuple(f.shape)).copy() for at, f in zip(sizes, frames)]
 
 
 def _inference_inputs(record):
@@ -104,4 +93,4 @@ def plot_top_preds_device(records: list) -> list:
 
 def plot_top_preds_batch(records: list) -> list[np.ndarray]:
     """[record.plot()["top_preds"] for record in records] in one upload, one text launch and one copy back."""
-    return _to_host(plot_top_preds_device(records)) if records else []
+    return frames_to_host(plot_top_preds_device(records)) if records else []

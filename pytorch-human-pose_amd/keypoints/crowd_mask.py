@@ -23,6 +23,7 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib
+from .._stage import Block, Layout, frames_to_host
 
 # hh_crowd_mask_desc / hh_crowd_seg_desc of include/hhrnet.h (24 bytes each)
 MASK_DESC, SEG_DESC = _lib.struct_dtype("hh_crowd_mask_desc"), _lib.struct_dtype("hh_crowd_seg_desc")
@@ -186,20 +187,18 @@ def crowd_masks(segments, device="cuda:0") -> list:
             nbytes += (segments[last].h * segments[last].w + 3) // 4 * 4  # every mask starts on a dword
             last += 1
         items = segments[first:last]
-        staged = (tables_bytes(items) + 63) // 64 * 64
-        offs = staged + np.cumsum([0] + [(s.h * s.w + 3) // 4 * 4 for s in items])
-        host = torch.empty(staged, dtype=torch.uint8).pin_memory()
-        desc_at, seg_at, nseg = fill_tables(items, offs[:-1], host.numpy(), 0)
+        lay = Layout()  # [tables and toggles | masks, each on a dword]
+        lay.add(tables_bytes(items))
+        staged = lay.pad()
+        offs = [lay.add(s.h * s.w, 4) for s in items]
         with torch.cuda.device(dev):
-            raw = torch.empty(int(offs[-1]), device=dev, dtype=torch.uint8)
-            raw[:staged].copy_(host, non_blocking=True)
-            launch(dev, raw.data_ptr(), host.data_ptr(), desc_at, seg_at, len(items), nseg)
-            back = torch.empty(int(offs[-1]) - staged, dtype=torch.uint8).pin_memory()
-            back.copy_(raw[staged:], non_blocking=True)
-            torch.cuda.current_stream(dev).synchronize()
-        flat = back.numpy()
-        for s, o in zip(items, offs[:-1] - staged):
-            out.append(flat[o:o + s.h * s.w].reshape(s.h, s.w) != 0)
+            blk = Block(staged, lay.pad(4), dev)
+            desc_at, seg_at, nseg = fill_tables(items, offs, blk.bytes, 0)
+            blk.upload()
+            launch(dev, blk.addr(0), blk.bytes.ctypes.data, desc_at, seg_at, len(items), nseg)
+            flat = frames_to_host([blk.tensor(staged, (lay.end - staged,))], copy=False)[0]
+        for s, o in zip(items, offs):
+            out.append(flat[o - staged:o - staged + s.h * s.w].reshape(s.h, s.w) != 0)
         first = last
     return out
 

@@ -24,14 +24,11 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._stage import Block, Layout, align, fill_frames, frames_to_host, per_frame, place_frames
 
 # hh_jpeg_desc of include/hhrnet.h
 DESC = _lib.struct_dtype("hh_jpeg_desc")
 FLAG_BGR = 1
-
-
-def _per_frame(value, n: int) -> list:
-    return list(value) if isinstance(value, (list, tuple)) else [value] * n
 
 
 def _subsampling(s) -> int:
@@ -104,10 +101,6 @@ def encode_jpeg_host(image: np.ndarray, quality: int = 90, subsampling="420", bg
     return out[:length.value].tobytes()
 
 
-def _align(n: int, a: int = 64) -> int:
-    return (n + a - 1) // a * a
-
-
 def encode_jpeg_device(frames: list, quality=90, subsampling="420", bgr=False, capacity=None) -> list[bytes]:
     """One hh_jpeg_encode_u8_batch, on the current stream, for a batch of frames of mixed sizes -> one JFIF stream (bytes) per frame.
     `frames`: uint8 [h,w,3], each a device tensor (read in place; a view whose rows are `pitch` >= 3 w bytes apart is allowed) or a numpy
@@ -119,67 +112,36 @@ def encode_jpeg_device(frames: list, quality=90, subsampling="420", bgr=False, c
     if n == 0:
         return []
     lib = _lib.load()
-    quals, subs, bgrs = _per_frame(quality, n), [_subsampling(s) for s in _per_frame(subsampling, n)], _per_frame(bgr, n)
-    on_dev = [isinstance(f, torch.Tensor) for f in frames]
+    quals, subs, bgrs = per_frame(quality, n), [_subsampling(s) for s in per_frame(subsampling, n)], per_frame(bgr, n)
     device = next((f.device for f in frames if isinstance(f, torch.Tensor)), None) or torch.device("cuda", torch.cuda.current_device())
-    at = _align(DESC.itemsize * n)
-    src_at, pitches = [], []
-    for f, dev in zip(frames, on_dev):
-        if dev:
-            if not (f.dtype == torch.uint8 and f.dim() == 3 and f.shape[2] == 3 and f.device == device and f.stride(2) == 1 and f.stride(1) == 3
-                    and f.stride(0) >= 3 * f.shape[1]):
-                raise ValueError("a device frame must be a uint8 [h,w,3] tensor (or a view of one with whole pixels and a row pitch) on one device")
-            src_at.append(None)
-            pitches.append(int(f.stride(0)))
-        else:
-            if not (isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.ndim == 3 and f.shape[2] == 3):
-                raise ValueError("a host frame must be a uint8 [h,w,3] array")
-            src_at.append(at)
-            pitches.append(int(f.shape[1]) * 3)
-            at = _align(at + f.size)
-    upload = at
-    len_at = at
-    at = _align(at + 4 * n)
+    lay = Layout()  # [descriptors | uploaded frames | lengths | streams, each with its bound of room]
+    lay.add(DESC.itemsize * n)
+    places = place_frames(lay, frames, device, pitched=True)
+    upload = lay.pad()
+    len_at = lay.add(4 * n)
     out_at, caps, ws_at, ws_total = [], [], [], 0
     for f, sub in zip(frames, subs):
         h, w = int(f.shape[0]), int(f.shape[1])
         cap, ws = lib.hh_jpeg_bound(h, w, sub), lib.hh_jpeg_workspace_bytes(h, w, sub)
         if cap < 0 or ws < 0:
             _lib.check(1)  # (refused by name: the size or the subsampling)
-        out_at.append(at)
         caps.append(int(cap) if capacity is None else int(capacity))
-        at = _align(at + caps[-1])
+        out_at.append(lay.add(caps[-1]))
         ws_at.append(ws_total)
         ws_total += int(ws)
-    host = torch.empty(upload, dtype=torch.uint8).pin_memory()
-    hv = host.numpy()
-    descs = hv[:DESC.itemsize * n].view(DESC)
-    buf = torch.empty(at, dtype=torch.uint8, device=device)  # [descriptors | uploaded frames | lengths | streams, each with its bound of room]
+    blk = Block(upload, lay.pad(), device, [f for f, at in zip(frames, places) if at is None])
+    descs = blk.host(0, n, DESC)
     work = torch.empty(max(ws_total, 16), dtype=torch.uint8, device=device)
-    # offsets are counted from the lowest address involved, so that none is negative (the base itself is never dereferenced)
-    base = min([buf.data_ptr()] + [f.data_ptr() for f, dev in zip(frames, on_dev) if dev])
-    rel = buf.data_ptr() - base
-    for j, f in enumerate(frames):
-        if on_dev[j]:
-            src = f.data_ptr() - base
-        else:
-            np.copyto(hv[src_at[j]:src_at[j] + f.size].reshape(f.shape), f)
-            src = rel + src_at[j]
-        descs[j] = (src, rel + out_at[j], caps[j], ws_at[j], pitches[j], f.shape[0], f.shape[1], int(quals[j]), subs[j], FLAG_BGR if bgrs[j] else 0, 0)
-    buf[:upload].copy_(host, non_blocking=True)
-    _lib.launch(device, lib.hh_jpeg_encode_u8_batch, base, buf.data_ptr(), descs.ctypes.data, n, work.data_ptr(), work.numel(), buf.data_ptr() + len_at)
-    stream = torch.cuda.current_stream(device)
-    lengths_host = torch.empty(n, dtype=torch.int32, pin_memory=True)
-    lengths_host.copy_(buf[len_at:len_at + 4 * n].view(torch.int32), non_blocking=True)
-    stream.synchronize()
-    lengths = [int(v) for v in lengths_host.numpy()]
+    for j, (f, src) in enumerate(zip(frames, fill_frames(blk, frames, places))):
+        pitch = int(f.shape[1]) * 3 if places[j] is not None else int(f.stride(0))
+        descs[j] = (src, blk.off(out_at[j]), caps[j], ws_at[j], pitch, f.shape[0], f.shape[1], int(quals[j]), subs[j], FLAG_BGR if bgrs[j] else 0, 0)
+    blk.upload()
+    _lib.launch(device, lib.hh_jpeg_encode_u8_batch, blk.base, blk.addr(0), descs.ctypes.data, n, work.data_ptr(), work.numel(), blk.addr(len_at))
+    lengths = [int(v) for v in frames_to_host([blk.tensor(len_at, (4 * n,))], copy=False)[0].view(np.int32)]
     if any(not 0 < ln <= cap for ln, cap in zip(lengths, caps)):
         raise _lib.HHError("hh_jpeg_encode_u8_batch: a stream's length lies outside its bound")
-    packed = torch.cat([buf[o:o + ln] for o, ln in zip(out_at, lengths)]) if n > 1 else buf[out_at[0]:out_at[0] + lengths[0]]
-    out_host = torch.empty(sum(lengths), dtype=torch.uint8, pin_memory=True)
-    out_host.copy_(packed, non_blocking=True)
-    stream.synchronize()
-    data = out_host.numpy().tobytes()
+    packed = torch.cat([blk.tensor(o, (ln,)) for o, ln in zip(out_at, lengths)]) if n > 1 else blk.tensor(out_at[0], (lengths[0],))
+    data = frames_to_host([packed], copy=False)[0].tobytes()
     ends = np.cumsum([0] + lengths)
     return [data[int(ends[j]):int(ends[j + 1])] for j in range(n)]
 
@@ -428,12 +390,12 @@ class JpegImage:
 
     def staged_bytes(self) -> int:
         """What crosses the bus for this image: the stream and its table block, each rounded up to 16."""
-        return _align(self.data.size, 16) + _align(self.tables_bytes, 16)
+        return align(self.data.size, 16) + align(self.tables_bytes, 16)
 
     def stage(self, hview: np.ndarray, at: int) -> tuple[int, int]:
         """Stream and table block into the staging bytes at `at` (a multiple of 16) -> (stream offset, tables offset).  A device-indexed
         image's block comes from hh_jpeg_index_tables: its entries are blank but for first_mcu / mcu_count."""
-        tables_at = at + _align(self.data.size, 16)
+        tables_at = at + align(self.data.size, 16)
         hview[at:at + self.data.size] = self.data
         out = hview[tables_at:tables_at + self.tables_bytes]
         if self.device_index:
@@ -458,7 +420,7 @@ class JpegImage:
         ws = int(lib.hh_jpeg_decode_window_workspace_bytes(self.info.ctypes.data, w.ctypes.data))
         if tables < 0 or ws < 0:
             _lib.check(1)
-        return WindowPlan(tuple(int(v) for v in w[0]), nsel.value, (int(sl[0]), int(sl[1])), tables, ws, _align(int(sl[1] - sl[0]), 16) + _align(tables, 16))
+        return WindowPlan(tuple(int(v) for v in w[0]), nsel.value, (int(sl[0]), int(sl[1])), tables, ws, align(int(sl[1] - sl[0]), 16) + align(tables, 16))
 
     def stage_window(self, hview: np.ndarray, at: int, window, plan: WindowPlan | None = None) -> tuple[int, int, WindowPlan, np.ndarray]:
         """The window's slice of the stream and its table block (selected segments only, offsets rebased to the slice) into the staging
@@ -466,7 +428,7 @@ class JpegImage:
         `window_plan`, where the caller has it already."""
         plan = self.window_plan(window) if plan is None else plan
         first, end = plan.slice
-        tables_at = at + _align(end - first, 16)
+        tables_at = at + align(end - first, 16)
         hview[at:at + end - first] = self.data[first:end]
         out = hview[tables_at:tables_at + plan.tables_bytes]
         w = _window(window)
@@ -554,7 +516,7 @@ def decode_jpeg_device(streams: list, index=None, bgr=False, device=None, out=No
         raise ValueError("decode_jpeg_device: `windows` has one entry per stream")
     windowed = windows is not None and any(w is not None for w in windows)
     desc_t, entry = (WIN_DESC, "hh_jpeg_decode_window_u8_batch") if windowed else (DEC_DESC, "hh_jpeg_decode_u8_batch")
-    idx = _per_frame(index, n) if isinstance(index, (list, tuple)) else [index] * n
+    idx = per_frame(index, n) if isinstance(index, (list, tuple)) else [index] * n
     if index is not None and not isinstance(index, (list, tuple, str)) and n != 1:
         raise ValueError("decode_jpeg_device: `index` is a list with one entry per stream")
     items = [s if isinstance(s, JpegImage) else JpegImage(s, i, mcus_per_segment if isinstance(i, str) else None) for s, i in zip(streams, idx)]
@@ -564,58 +526,46 @@ def decode_jpeg_device(streams: list, index=None, bgr=False, device=None, out=No
                          "(index='device') is refused")
     # one plan per stream: without any window the whole stream and every segment, else the slice and the segments of its window
     plans = [it.window_plan((0, 0, it.h, it.w) if w is None else w) for it, w in zip(items, windows)] if windowed else [it.whole_plan() for it in items]
-    bgrs = _per_frame(bgr, n)
+    bgrs = per_frame(bgr, n)
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    at = _align(desc_t.itemsize * n, 16)
-    places = []
-    for p in plans:
-        places.append(at)
-        at += p.staged_bytes
-    upload = at
-    status_at = _align(at, 16)
-    at = status_at + 4 * n * 2  # (the decode's statuses, then the index call's)
-    dst_at = []
-    for p in plans:
-        at = _align(at, 16)
-        dst_at.append(at)
-        at += p.window[2] * p.window[3] * 3 if out is None else 0
+    lay = Layout()  # [descriptors | streams or slices, and tables | statuses | pixels], 16-aligned
+    lay.add(desc_t.itemsize * n, 16)
+    places = [lay.add(p.staged_bytes, 16) for p in plans]  # (back to back: a multiple of 16 each)
+    upload = lay.end
+    status_at = lay.add(4 * n * 2, 16)  # (the decode's statuses, then the index call's)
+    dst_at = [lay.add(p.window[2] * p.window[3] * 3 if out is None else 0, 16) for p in plans]
     ws_at = np.cumsum([0] + [p.ws_bytes for p in plans])
-    host = torch.empty(upload, dtype=torch.uint8).pin_memory()
-    hv = host.numpy()
-    hv[:] = 0
-    descs = hv[:desc_t.itemsize * n].view(desc_t)
-    buf = torch.empty(at, dtype=torch.uint8, device=device)  # [descriptors | streams or slices, and tables | statuses | pixels]
     work = torch.empty(max(int(ws_at[-1]), 16), dtype=torch.uint8, device=device)
     if out is not None:
         if len(out) != n:
             raise ValueError("decode_jpeg_device: one destination per stream")
         for o, p in zip(out, plans):
-            if not (isinstance(o, torch.Tensor) and o.dtype == torch.uint8 and tuple(o.shape) == (p.window[2], p.window[3], 3) and o.device == buf.device
+            if not (isinstance(o, torch.Tensor) and o.dtype == torch.uint8 and tuple(o.shape) == (p.window[2], p.window[3], 3) and o.device == work.device
                     and o.stride(2) == 1 and o.stride(1) == 3):
                 raise ValueError("a destination must be a uint8 [height,width,3] device tensor (or a row-pitched view of one) of the stream's or its window's size")
-    base = min([buf.data_ptr()] + ([o.data_ptr() for o in out] if out is not None else []))
-    rel = buf.data_ptr() - base
+    blk = Block(upload, lay.end, device, out or (), zero=True)
+    descs = blk.host(0, n, desc_t)
     infos, tables_places = [], []
     for j, (it, p) in enumerate(zip(items, plans)):
-        stream_at, tables_at, info = it.stage_plan(hv, places[j], p, windowed)
+        stream_at, tables_at, info = it.stage_plan(blk.bytes, places[j], p, windowed)
         infos.append(info)
         tables_places.append(tables_at)
-        dst = rel + dst_at[j] if out is None else out[j].data_ptr() - base
+        dst = blk.off(dst_at[j]) if out is None else blk.off_of(out[j])
         pitch = 3 * p.window[3] if out is None else int(out[j].stride(0))
-        row = it.window_desc(p, rel + stream_at, rel + tables_at, dst, int(ws_at[j]), pitch, bgrs[j])
+        row = it.window_desc(p, blk.off(stream_at), blk.off(tables_at), dst, int(ws_at[j]), pitch, bgrs[j])
         descs[j] = row if windowed else row[0]  # (DEC_DESC: no window)
-    buf[:upload].copy_(host, non_blocking=True)
+    blk.upload()
     infos = np.concatenate(infos)
     ncalls = 1
     if index_mps is not None:
-        launch_index(device, base, buf.data_ptr(), descs, infos, index_mps, subseq_bytes, buf.data_ptr() + status_at + 4 * n)
+        launch_index(device, blk.base, blk.addr(0), descs, infos, index_mps, subseq_bytes, blk.addr(status_at + 4 * n))
         ncalls = 2
-    launch_decode(device, base, buf.data_ptr(), descs, infos, work, buf.data_ptr() + status_at, entry)
+    launch_decode(device, blk.base, blk.addr(0), descs, infos, work, blk.addr(status_at), entry)
     status_host = torch.empty(n * ncalls, dtype=torch.int32, pin_memory=True)
-    status_host.copy_(buf[status_at:status_at + 4 * n * ncalls].view(torch.int32), non_blocking=True)
+    status_host.copy_(blk.tensor(status_at, (4 * n * ncalls,)).view(torch.int32), non_blocking=True)
     if entries_out is not None:
         spans = [(rel_at + it.tables_bytes - SEGMENT.itemsize * p.nsel, SEGMENT.itemsize * p.nsel) for rel_at, it, p in zip(tables_places, items, plans)]
-        packed = torch.cat([buf[o:o + ln] for o, ln in spans]).cpu().numpy() if not windowed else None
+        packed = torch.cat([blk.tensor(o, (ln,)) for o, ln in spans]).cpu().numpy() if not windowed else None
     torch.cuda.current_stream(device).synchronize()
     statuses = status_host.numpy().reshape(ncalls, n).max(axis=0)
     decode_jpeg_device.last_h2d_bytes, decode_jpeg_device.last_status = upload, statuses.copy()
@@ -625,7 +575,7 @@ def decode_jpeg_device(streams: list, index=None, bgr=False, device=None, out=No
     raise_status(statuses, "hh_jpeg_index_device_batch + " + entry if index_mps is not None else entry)
     if out is not None:
         return list(out)
-    return [buf[o:o + p.window[2] * p.window[3] * 3].view(p.window[2], p.window[3], 3) for o, p in zip(dst_at, plans)]
+    return [blk.tensor(o, (p.window[2], p.window[3], 3)) for o, p in zip(dst_at, plans)]
 
 
 def decode_jpeg_host(data, bgr: bool = False, index=None, pitch: int | None = None, window=None, counts: dict | None = None) -> np.ndarray:

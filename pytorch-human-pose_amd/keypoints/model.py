@@ -13,6 +13,7 @@ import torch
 from torch import Tensor, nn
 
 from .. import _lib
+from .._stage import PinnedRing, align, frames_to_host
 from ..optim import clip_grad_norm_
 from .grouping import MPPEHeatmapParser
 from .results import InferenceKeypointsResult, inverse_affine, transform_coords
@@ -618,17 +619,15 @@ class InferenceKeypointsModel:
 
         # Two-deep software pipeline: while the GPU works on batch k the host stages the pixels of batch k+1 into a pinned
         # buffer and only then collects the results of batch k (two staging buffers, each guarded by the event of its last use).
-        stage = [None, None]
-        stage_free: list = [None, None]
+        staging = PinnedRing()
         pending = None
-        turn = 0
         for sizes, chunks in jobs.items():
             for chunk, subs in chunks:
                 w, h = sizes[i1]
                 nb = len(chunk)
                 jpeg_at = [j for j, i in enumerate(chunk) if isinstance(raw_images[i], jp.JpegImage)]
                 offs = np.cumsum([0] + [0 if isinstance(raw_images[i], jp.JpegImage) else raw_images[i].size for i in chunk])
-                desc_off = (int(offs[-1]) + 63) // 64 * 64  # the image descriptors travel behind the pixels, in the same copy
+                desc_off = align(int(offs[-1]))  # the image descriptors travel behind the pixels, in the same copy
                 total = desc_off + _IMAGE_DESC.itemsize * nb * len(sizes)  # (one block of them per scale)
                 starts = [int(o) for o in offs[:-1]]  # where image j's pixels lie in the device buffer
                 dev_total, jplan = total, None
@@ -636,13 +635,13 @@ class InferenceKeypointsModel:
                     # a JPEG image ships no pixels: [decode descriptors | stream, table block | ...] travel behind the image descriptors in
                     # the same copy; the statuses and the pixel slots, which the decode fills, lie behind the uploaded bytes on the device
                     items = [raw_images[chunk[j]] for j in jpeg_at]
-                    jdesc_off = (total + 15) // 16 * 16
+                    jdesc_off = align(total, 16)
                     places = jdesc_off + jp.DEC_DESC.itemsize * len(items) + np.cumsum([0] + [it.staged_bytes() for it in items])
                     total = int(places[-1])
                     status_off = total  # (a multiple of 16)
                     at = status_off + 8 * len(items)
                     for j, it in zip(jpeg_at, items):
-                        starts[j] = at = (at + 15) // 16 * 16
+                        starts[j] = at = align(at, 16)
                         at += it.h * it.w * 3
                     dev_total = at
                     ws_offs = np.cumsum([0] + [it.ws_bytes for it in items])
@@ -654,11 +653,7 @@ class InferenceKeypointsModel:
                     inv = np.stack([inverse_affine(geo[i][1], geo[i][2], (w, h)) for i in chunk])
                     targets = (targets, inv, score_vars)
                 self.last_h2d_bytes += total
-                if stage[turn] is None or stage[turn].numel() < total:
-                    stage[turn] = torch.empty(total, dtype=torch.uint8).pin_memory()
-                elif stage_free[turn] is not None:
-                    stage_free[turn].synchronize()  # the copy that last read this buffer has finished
-                host = stage[turn]
+                turn, host = staging.take(total)  # (the slot's index also picks this batch's _score_stage and _out_ring buffers)
                 hview = host.numpy()
                 descs = hview[desc_off:desc_off + _IMAGE_DESC.itemsize * nb * len(sizes)].view(_IMAGE_DESC)
                 for j, i in enumerate(chunk):
@@ -752,8 +747,7 @@ class InferenceKeypointsModel:
                 # (the model's high-priority stream, for batches as for single images: same-box alternation with the caller's
                 # stream, tools/api_throughput.py: 3820 / 3380 against 2600 / 2970 img/s)
                 job, copied, _raw = self._on_fast_stream(run)
-                stage_free[turn] = copied
-                turn ^= 1
+                staging.release(turn, copied)
                 if pending is not None:
                     finish(pending)
                 pending = job
@@ -789,14 +783,8 @@ class InferenceKeypointsModel:
             for r, data in zip(results, encode_jpeg_device(out, bgr=bgr, **jpeg)):
                 r.rendered_jpeg = data
             return
-        sizes = np.cumsum([0] + [f.numel() for f in out])
-        host = torch.empty(int(sizes[-1]), dtype=torch.uint8, pin_memory=True)
-        for j, f in enumerate(out):
-            host[int(sizes[j]):int(sizes[j + 1])].view(f.shape).copy_(f, non_blocking=True)
-        cur.synchronize()
-        hv = host.numpy()
-        for j, (r, f) in enumerate(zip(results, out)):
-            r.rendered = hv[int(sizes[j]):int(sizes[j + 1])].reshape(tuple(f.shape)).copy()
+        for r, frame in zip(results, frames_to_host(out)):
+            r.rendered = frame
 
     def _call_tracked(self, raw_image: np.ndarray, tracker) -> InferenceKeypointsResult:
         """`self(raw_image, None)` with one hh_track_step behind the decode on the same stream (one frame of the tracker's one stream)."""

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._stage import Block, Layout, fill_frames, per_frame, place_frames
 from . import crowd_mask as cm
 from . import text as tx
 from . import visualization as vis
@@ -220,10 +221,6 @@ def overlay_host(image: np.ndarray, shapes, toggles, alpha: float = OVERLAY_ALPH
     return out
 
 
-def _align(n: int, a: int = 64) -> int:
-    return (n + a - 1) // a * a
-
-
 def stage_overlay(frames: list, tables: list, alphas=OVERLAY_ALPHA, bgr=False, in_place: bool = False):
     """Everything of overlay_frames_device in front of the launch: the tables and the ONE async copy of descriptors, shapes, toggles and
     host frames from one pinned block.  -> a function that enqueues the launch on the current stream and returns the output tensors
@@ -234,71 +231,39 @@ def stage_overlay(frames: list, tables: list, alphas=OVERLAY_ALPHA, bgr=False, i
     if len(tables) != n:
         raise ValueError("overlay_frames_device: one (shapes, toggles) per frame")
     lib = _lib.load()
-    alphas = list(alphas) if np.ndim(alphas) else [alphas] * n
-    bgrs = list(bgr) if np.ndim(bgr) else [bgr] * n
-    on_dev = [isinstance(f, torch.Tensor) for f in frames]
+    alphas, bgrs = per_frame(alphas, n), per_frame(bgr, n)
     device = next((f.device for f in frames if isinstance(f, torch.Tensor)), None) or torch.device("cuda", torch.cuda.current_device())
     tabs = [_tables(*t) for t in tables]
     num_shapes, num_toggles = sum(len(s) for s, _ in tabs), sum(len(t) for _, t in tabs)
-    shape_at = _align(DESC.itemsize * n)
-    toggle_at = _align(shape_at + 4 * SHAPE_INTS * num_shapes)
-    at = _align(toggle_at + 4 * num_toggles)
-    src_at = []
-    for f, dev in zip(frames, on_dev):
-        if dev:
-            if not (f.dtype == torch.uint8 and f.is_contiguous() and f.dim() == 3 and f.shape[2] == 3 and f.device == device):
-                raise ValueError("a device frame must be a contiguous uint8 [h,w,3] tensor on one device")
-            src_at.append(None)
-        else:
-            if not (isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.ndim == 3 and f.shape[2] == 3):
-                raise ValueError("a host frame must be a uint8 [h,w,3] array")
-            src_at.append(at)
-            at = _align(at + f.size)
-    upload = at
-    out_at = []
-    for f, dev in zip(frames, on_dev):
-        if in_place:  # an uploaded frame is overwritten where it was uploaded to
-            out_at.append(None)
-            continue
-        out_at.append(at)
-        at = _align(at + int(f.shape[0]) * int(f.shape[1]) * 3)
-    host = torch.empty(upload, dtype=torch.uint8).pin_memory()
-    hv = host.numpy()
-    descs = hv[:DESC.itemsize * n].view(DESC)
-    shapes = hv[shape_at:shape_at + 4 * SHAPE_INTS * num_shapes].view(np.int32).reshape(-1, SHAPE_INTS)
-    toggles = hv[toggle_at:toggle_at + 4 * num_toggles].view(np.uint32)
-    buf = torch.empty(at, dtype=torch.uint8, device=device)  # [descriptors | shapes | toggles | uploaded frames | outputs]
-    # offsets are counted from the lowest address involved, so that none is negative (the base itself is never dereferenced)
-    base = min([buf.data_ptr()] + [f.data_ptr() for f, dev in zip(frames, on_dev) if dev])
-    rel = buf.data_ptr() - base
+    lay = Layout()  # [descriptors | shapes | toggles | uploaded frames | outputs]
+    lay.add(DESC.itemsize * n)
+    shape_at = lay.add(4 * SHAPE_INTS * num_shapes)
+    toggle_at = lay.add(4 * num_toggles)
+    places = place_frames(lay, frames, device)
+    upload = lay.pad()
+    sizes = [(int(f.shape[0]), int(f.shape[1]), 3) for f in frames]
+    # in place: an uploaded frame is overwritten where it was uploaded to, a device frame where it lies (None)
+    out_at = places if in_place else [lay.add(h * w * 3) for h, w, _ in sizes]
+    blk = Block(upload, lay.pad(), device, [f for f, at in zip(frames, places) if at is None])
+    descs = blk.host(0, n, DESC)
+    shapes = blk.host(shape_at, SHAPE_INTS * num_shapes, np.int32).reshape(-1, SHAPE_INTS)
+    toggles = blk.host(toggle_at, num_toggles, np.uint32)
     first = tog = 0
-    for j, (f, (s, t)) in enumerate(zip(frames, tabs)):
-        if on_dev[j]:
-            src = f.data_ptr() - base
-        else:
-            np.copyto(hv[src_at[j]:src_at[j] + f.size].reshape(f.shape), f)
-            src = rel + src_at[j]
+    for j, (src, (s, t)) in enumerate(zip(fill_frames(blk, frames, places), tabs)):
         shapes[first:first + len(s)] = s
         fills = shapes[first:first + len(s)]
         fills[fills[:, 0] == FILL, 2] += tog  # a fill's first toggle counts from the batch's table
         toggles[tog:tog + len(t)] = t
         w0, w1 = vis.blend_weights(alphas[j])
-        descs[j] = (src, src if in_place else rel + out_at[j], f.shape[0], f.shape[1], first, len(s), w0, w1, vis.FLAG_BGR if bgrs[j] else 0, 0)
+        descs[j] = (src, src if in_place else blk.off(out_at[j]), *sizes[j][:2], first, len(s), w0, w1, vis.FLAG_BGR if bgrs[j] else 0, 0)
         first += len(s)
         tog += len(t)
-    buf[:upload].copy_(host, non_blocking=True)
-    outs = []
-    for j, f in enumerate(frames):
-        size = int(f.shape[0]) * int(f.shape[1]) * 3
-        if in_place and on_dev[j]:
-            outs.append(f)
-        else:
-            o = src_at[j] if in_place else out_at[j]
-            outs.append(buf[o:o + size].view(int(f.shape[0]), int(f.shape[1]), 3))
+    blk.upload()
+    outs = [f if o is None else blk.tensor(o, size) for f, o, size in zip(frames, out_at, sizes)]
 
-    def launch():  # (keeps the frames, the device block and the host copies alive)
-        _lib.launch(device, lib.hh_seg_overlay_u8_batch, base, buf.data_ptr(), descs.ctypes.data, buf.data_ptr() + shape_at if num_shapes else None,
-                    shapes.ctypes.data if num_shapes else None, num_shapes, buf.data_ptr() + toggle_at if num_toggles else None,
+    def launch():  # (the block keeps the frames, the device bytes and the host copies alive)
+        _lib.launch(device, lib.hh_seg_overlay_u8_batch, blk.base, blk.addr(0), descs.ctypes.data, blk.addr(shape_at) if num_shapes else None,
+                    shapes.ctypes.data if num_shapes else None, num_shapes, blk.addr(toggle_at) if num_toggles else None,
                     toggles.ctypes.data if num_toggles else None, num_toggles, n)
         return outs
     launch.num_shapes, launch.num_toggles = num_shapes, num_toggles

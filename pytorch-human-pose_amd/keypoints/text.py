@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._stage import Block, Layout
 
 PRIM, DESC = _lib.struct_dtype("hh_render_prim"), _lib.struct_dtype("hh_render_desc")  # hh_text_prim, hh_text_desc are these
 BOX, GLYPH, MAX_PRIMS = _lib.const("TEXT_BOX"), _lib.const("TEXT_GLYPH"), _lib.const("TEXT_MAX_PRIMS")
@@ -187,10 +188,6 @@ def put_txt_host(image: np.ndarray, table: np.ndarray) -> np.ndarray:
     return out
 
 
-def _align(n: int, a: int = 64) -> int:
-    return (n + a - 1) // a * a
-
-
 def stage_put_txt(frames: list, tables: list):
     """Everything of put_txt_device in front of the launch: the validation on the host copies and the ONE async copy of descriptors,
     table and tile list from one pinned block.  -> a function that enqueues the launch on the current stream (tools/text_time.py
@@ -212,14 +209,9 @@ def stage_put_txt(frames: list, tables: list):
     total = int(sum(counts))
     prims = np.concatenate([np.ascontiguousarray(t, dtype=PRIM) for t in tables]) if total else np.zeros(0, PRIM)
     descs = np.zeros(n, DESC)
-    prim_at = _align(DESC.itemsize * n)
-    tile_at = _align(prim_at + PRIM.itemsize * total)
-    # offsets are counted from the lowest address involved, so that none is negative (the base itself is never dereferenced)
-    base = min(f.data_ptr() for f in frames)
     first = 0
-    for j, f in enumerate(frames):
-        at = f.data_ptr() - base
-        descs[j] = (at, at, f.shape[0], f.shape[1], first, counts[j], 0.0, 0.0, 0, 0)
+    for j, f in enumerate(frames):  # (the frames' offsets need the block's address: the tile list does not read them)
+        descs[j] = (0, 0, f.shape[0], f.shape[1], first, counts[j], 0.0, 0.0, 0, 0)
         first += counts[j]
     num_tiles = C.c_longlong(0)
     args = (descs.ctypes.data, prims.ctypes.data if total else None, total, n, len(fnt.coverage))
@@ -227,18 +219,21 @@ def stage_put_txt(frames: list, tables: list):
     nt = num_tiles.value
     if nt == 0:
         return None
-    host = torch.empty(tile_at + 8 * nt, dtype=torch.uint8).pin_memory()
-    hv = host.numpy()
-    hv[:DESC.itemsize * n] = descs.view(np.uint8)
-    hv[prim_at:prim_at + PRIM.itemsize * total] = prims.view(np.uint8)
-    tiles = hv[tile_at:]
+    lay = Layout()  # [descriptors | table | tile list]
+    lay.add(DESC.itemsize * n)
+    prim_at = lay.add(PRIM.itemsize * total)
+    tile_at = lay.add(8 * nt)
+    blk = Block(lay.end, lay.end, device, frames)
+    descs["src_offset"] = descs["dst_offset"] = [blk.off_of(f) for f in frames]
+    blk.host(0, DESC.itemsize * n)[:] = descs.view(np.uint8)  # (as bytes: a structured assignment goes field by field)
+    blk.host(prim_at, PRIM.itemsize * total)[:] = prims.view(np.uint8)
+    tiles = blk.host(tile_at, 8 * nt)
     _lib.check(lib.hh_text_tiles(*args, tiles.ctypes.data, nt, C.byref(num_tiles)))
-    buf = torch.empty(host.numel(), dtype=torch.uint8, device=device)  # [descriptors | table | tile list]
-    buf.copy_(host, non_blocking=True)
+    blk.upload()
 
-    def launch():  # (keeps the frames, the device block and the host copies alive)
-        _lib.launch(device, lib.hh_text_labels_u8_batch, base, buf.data_ptr(), descs.ctypes.data, buf.data_ptr() + prim_at, prims.ctypes.data, total, n,
-                    atlas.data_ptr(), len(fnt.coverage), buf.data_ptr() + tile_at, tiles.ctypes.data, nt)
+    def launch():  # (the block keeps the frames, the device bytes and the host copies alive)
+        _lib.launch(device, lib.hh_text_labels_u8_batch, blk.base, blk.addr(0), descs.ctypes.data, blk.addr(prim_at), prims.ctypes.data, total, n,
+                    atlas.data_ptr(), len(fnt.coverage), blk.addr(tile_at), tiles.ctypes.data, nt)
         return frames
     launch.num_tiles = nt
     return launch

@@ -28,6 +28,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .. import _lib
+from .._stage import PinnedRing, align
 from . import crowd_mask as cm
 from . import jpeg as jp
 from .loss import DeviceJoints, pack_joints
@@ -201,9 +202,7 @@ class TrainInput:
         self.train = _Mode(self, max_rotation, min_scale, max_scale, max_translate, 0.5)
         self.inference = _Mode(self, 0, 1, 1, 0, None)
         self._tables_dev = None
-        self._stage = [None, None]       # pinned staging buffers ...
-        self._stage_free = [None, None]  # ... and the event behind the copy that last read each
-        self._turn = 0
+        self._ring = PinnedRing()  # pinned staging buffers, each with the event behind the copy that last read it
         self.last_h2d_bytes = self.last_launches = 0  # of the last build(): what tools/train_input_time.py reports
         self.last_staged_bytes = 0  # the part of last_h2d_bytes that is the one staged copy (the rest: the joint tables)
         self._jpeg_status = None    # the device statuses of the last build's JpegImage samples
@@ -228,18 +227,6 @@ class TrainInput:
         return mat_image, mats, floats, ints
 
     # ------------------------------------------------------------------ device half
-    def _staging(self, total: int):
-        import torch
-        t = self._turn
-        self._turn ^= 1
-        if self._stage[t] is None or self._stage[t].numel() < total:
-            # (a larger buffer replaces the old one; the old one stays alive until its copy has run: torch keeps pinned blocks
-            # that a non_blocking copy still reads)
-            self._stage[t] = torch.empty(total, dtype=torch.uint8).pin_memory()
-        elif self._stage_free[t] is not None:
-            self._stage_free[t].synchronize()  # the copy that last read this buffer has finished
-        return t, self._stage[t]
-
     def build(self, samples, params):
         """samples: [(uint8 [h,w,3] image, bool [h,w] crowd mask, float [P,K,3] joints) or Mosaic of four of them], params: [AugParams]
         (of a 2S x 2S image for a Mosaic) -> (images [B,3,S,S], [heatmaps [B,K,s,s]], [masks [B,s,s]], [DeviceJoints]) on the device,
@@ -283,24 +270,24 @@ class TrainInput:
         jpeg_items = [raws[r][0] for r in jpeg_raws]
         sizes = [0 if isinstance(img, jp.JpegImage) else h * w * 3 for (h, w), (img, _, _) in zip(shapes, raws)] + [0 if isinstance(mask, cm.CrowdSegments) else h * w for (h, w), (_, mask, _) in zip(shapes, raws)]
         offs = np.cumsum([0] + sizes)
-        desc_off = (int(offs[-1]) + 63) // 64 * 64  # the descriptors travel behind the pixels and masks, in the same copy
+        desc_off = align(int(offs[-1]))  # the descriptors travel behind the pixels and masks, in the same copy
         mosaic_off = desc_off + _TRAIN_DESC.itemsize * B
         crowd_off = mosaic_off + _MOSAIC_DESC.itemsize * M  # (a multiple of 8: both descriptor sizes are)
         total = crowd_off + cm.tables_bytes(seg_items)
         # a JpegImage ships its stream and table block behind the crowd tables: [decode descriptors | stream, tables | ...], 16-aligned
-        jpeg_off = (total + 15) // 16 * 16
+        jpeg_off = align(total, 16)
         jpeg_places = jpeg_off + jp.DEC_DESC.itemsize * len(jpeg_items) + np.cumsum([0] + [it.staged_bytes() for it in jpeg_items])
         if jpeg_items:
             total = int(jpeg_places[-1])
         # the canvases of the mosaic samples lie behind the staged bytes in the device buffer; nothing of them is copied
-        canvas_off = (total + 63) // 64 * 64
+        canvas_off = align(total)
         # ... and behind them the masks of the segment samples, which hh_crowd_masks_u8_batch fills there
         fill_offs = canvas_off + M * 16 * S * S + np.cumsum([0] + [(s.h * s.w + 3) // 4 * 4 for s in seg_items])
         mask_at_raw = [int(offs[R + r]) for r in range(R)]
         for i, r in enumerate(seg_raws):
             mask_at_raw[r] = int(fill_offs[i])
         # ... and behind those the pixel slots of the JpegImage samples, which hh_jpeg_decode_u8_batch fills there, and its statuses
-        pixel_offs = (int(fill_offs[-1]) + 15) // 16 * 16 + np.cumsum([0] + [(it.h * it.w * 3 + 15) // 16 * 16 for it in jpeg_items])
+        pixel_offs = align(int(fill_offs[-1]), 16) + np.cumsum([0] + [align(it.h * it.w * 3, 16) for it in jpeg_items])
         image_at_raw = [int(offs[r]) for r in range(R)]
         for i, r in enumerate(jpeg_raws):
             image_at_raw[r] = int(pixel_offs[i])
@@ -308,7 +295,7 @@ class TrainInput:
         device_bytes = status_off + 4 * len(jpeg_items) if jpeg_items else int(fill_offs[-1])
         if M and (S % 4 or S < 4):
             raise _lib.HHError("TrainInput.build: a mosaic needs an out_size that is a multiple of 4 (hh_mosaic_u8_batch)")
-        turn, host = self._staging(total)
+        turn, host = self._ring.take(total)
         hview = host.numpy()
         descs = hview[desc_off:mosaic_off].view(_TRAIN_DESC)
         mdescs = hview[mosaic_off:crowd_off].view(_MOSAIC_DESC)
@@ -356,7 +343,7 @@ class TrainInput:
                 raw = host[:total].to(dev, non_blocking=True)
             copied = torch.cuda.Event()
             copied.record(cur)
-            self._stage_free[turn] = copied
+            self._ring.release(turn, copied)
             self.last_h2d_bytes, self.last_launches = total, 2 + nst + (1 if M else 0) + (1 if seg_items else 0) + (3 if jpeg_items else 0)
             self.last_staged_bytes = total
             if self._tables_dev is None:

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._stage import Block, Layout, fill_frames, frames_to_host, per_frame, place_frames
 
 PRIM, DESC = _lib.struct_dtype("hh_render_prim"), _lib.struct_dtype("hh_render_desc")
 DISC, RING, ELLIPSE = (_lib.const(k) for k in ("RENDER_DISC", "RENDER_RING", "RENDER_ELLIPSE"))
@@ -183,10 +184,6 @@ def render_host(image: np.ndarray, prims: np.ndarray, alpha: float, bgr: bool = 
     return out
 
 
-def _align(n: int, a: int = 64) -> int:
-    return (n + a - 1) // a * a
-
-
 def render_frames_device(frames: list, tables: list, alphas, bgr=False) -> list:
     """One hh_render_poses_u8_batch, on the current stream, for a batch of frames of mixed sizes.  `frames`: uint8 RGB [h,w,3], each a
     numpy array (uploaded here) or a contiguous device tensor (read in place; the caller keeps it alive until the stream has passed
@@ -196,54 +193,29 @@ def render_frames_device(frames: list, tables: list, alphas, bgr=False) -> list:
     n = len(frames)
     if n == 0:
         return []
-    lib = _lib.load()
-    alphas = list(alphas) if np.ndim(alphas) else [alphas] * n
-    bgrs = list(bgr) if np.ndim(bgr) else [bgr] * n
-    on_dev = [isinstance(f, torch.Tensor) for f in frames]
+    alphas, bgrs = per_frame(alphas, n), per_frame(bgr, n)
     device = next((f.device for f in frames if isinstance(f, torch.Tensor)), None) or torch.device("cuda", torch.cuda.current_device())
     counts = [len(t) for t in tables]
     total_prims = int(sum(counts))
-    prim_at = _align(DESC.itemsize * n)
-    at = _align(prim_at + PRIM.itemsize * total_prims)
-    src_at = []
-    for f, dev in zip(frames, on_dev):
-        if dev:
-            if not (f.dtype == torch.uint8 and f.is_contiguous() and f.dim() == 3 and f.shape[2] == 3 and f.device == device):
-                raise ValueError("a device frame must be a contiguous uint8 [h,w,3] tensor on one device")
-            src_at.append(None)
-        else:
-            if not (f.dtype == np.uint8 and f.ndim == 3 and f.shape[2] == 3):
-                raise ValueError("a host frame must be a uint8 [h,w,3] array")
-            src_at.append(at)
-            at = _align(at + f.size)
-    upload = at
-    out_at = []
-    for f in frames:
-        out_at.append(at)
-        at = _align(at + int(f.shape[0]) * int(f.shape[1]) * 3)
-    host = torch.empty(upload, dtype=torch.uint8).pin_memory()
-    hv = host.numpy()
-    descs = hv[:DESC.itemsize * n].view(DESC)
-    prims = hv[prim_at:prim_at + PRIM.itemsize * total_prims].view(PRIM)
-    buf = torch.empty(at, dtype=torch.uint8, device=device)  # [descriptors | table | uploaded frames | outputs]
-    # offsets are counted from the lowest address involved, so that none is negative (the base itself is never dereferenced)
-    base = min([buf.data_ptr()] + [f.data_ptr() for f, dev in zip(frames, on_dev) if dev])
-    rel = buf.data_ptr() - base
+    lay = Layout()  # [descriptors | table | uploaded frames | outputs]
+    lay.add(DESC.itemsize * n)
+    prim_at = lay.add(PRIM.itemsize * total_prims)
+    places = place_frames(lay, frames, device)
+    upload = lay.pad()
+    sizes = [(int(f.shape[0]), int(f.shape[1]), 3) for f in frames]
+    out_at = [lay.add(h * w * 3) for h, w, _ in sizes]
+    blk = Block(upload, lay.pad(), device, [f for f, at in zip(frames, places) if at is None])
+    descs, prims = blk.host(0, n, DESC), blk.host(prim_at, total_prims, PRIM)
     first = 0
-    for j, (f, t) in enumerate(zip(frames, tables)):
-        if on_dev[j]:
-            src = f.data_ptr() - base
-        else:
-            np.copyto(hv[src_at[j]:src_at[j] + f.size].reshape(f.shape), f)
-            src = rel + src_at[j]
-        prims[first:first + counts[j]] = t
+    for j, src in enumerate(fill_frames(blk, frames, places)):
+        prims[first:first + counts[j]] = tables[j]
         w0, w1 = blend_weights(alphas[j])
-        descs[j] = (src, rel + out_at[j], f.shape[0], f.shape[1], first, counts[j], w0, w1, FLAG_BGR if bgrs[j] else 0, 0)
+        descs[j] = (src, blk.off(out_at[j]), *sizes[j][:2], first, counts[j], w0, w1, FLAG_BGR if bgrs[j] else 0, 0)
         first += counts[j]
-    buf[:upload].copy_(host, non_blocking=True)
-    _lib.launch(device, lib.hh_render_poses_u8_batch, base, buf.data_ptr(), descs.ctypes.data, buf.data_ptr() + prim_at if total_prims else None,
+    blk.upload()
+    _lib.launch(device, _lib.load().hh_render_poses_u8_batch, blk.base, blk.addr(0), descs.ctypes.data, blk.addr(prim_at) if total_prims else None,
                 prims.ctypes.data if total_prims else None, total_prims, n)
-    return [buf[o:o + int(f.shape[0]) * int(f.shape[1]) * 3].view(int(f.shape[0]), int(f.shape[1]), 3) for o, f in zip(out_at, frames)]
+    return [blk.tensor(o, size) for o, size in zip(out_at, sizes)]
 
 
 def resize_device(src: torch.Tensor, W: int, H: int) -> torch.Tensor:
@@ -257,11 +229,8 @@ def resize_device(src: torch.Tensor, W: int, H: int) -> torch.Tensor:
 
 
 def to_host(t: torch.Tensor) -> np.ndarray:
-    """A finished frame back through one pinned buffer."""
-    host = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-    host.copy_(t, non_blocking=True)
-    torch.cuda.current_stream(t.device).synchronize()
-    return host.numpy().copy()
+    """A finished uint8 frame back through one pinned buffer (another dtype is refused: ValueError)."""
+    return frames_to_host([t])[0]
 
 
 def plot_connections(image: np.ndarray, grouped_kpts_coords, grouped_kpts_scores, limbs=None, thr: float = 0.05, color_mode: str = "person",
@@ -353,21 +322,21 @@ def panels_device(image: torch.Tensor, placed: list, Hc: int, Wc: int, lut: np.n
     if lut.shape != (256, 3):
         raise ValueError("panels_device: the colour table must be uint8 [256,3]")
     n = len(placed)
-    lut_at = _align(PANEL.itemsize * n)
-    host = torch.empty(lut_at + 768, dtype=torch.uint8).pin_memory()
-    hv = host.numpy()
-    table = hv[:PANEL.itemsize * n].view(PANEL)
+    lay = Layout()  # [table | colour table]
+    lay.add(PANEL.itemsize * n)
+    lut_at = lay.add(768)
+    blk = Block(lay.end, lay.end, device)
+    table = blk.host(0, n, PANEL)
     table[:] = _panel_table(placed, lambda t: t.data_ptr())
-    hv[lut_at:] = lut.reshape(-1)
-    buf = torch.empty(lut_at + 768, dtype=torch.uint8, device=device)
-    buf.copy_(host, non_blocking=True)
+    blk.host(lut_at, 768)[:] = lut.reshape(-1)
+    blk.upload()
     scratch = torch.empty(max(n, 1) * PANEL_PARTS * 2, dtype=torch.float32, device=device)
     if canvas is None:
         canvas, pitch = torch.empty((Hc, Wc, 3), dtype=torch.uint8, device=device), Wc * 3
     elif not (canvas.dtype == torch.uint8 and canvas.device == device and canvas.is_contiguous() and pitch is not None
               and canvas.numel() >= (Hc - 1) * pitch + Wc * 3):
         raise ValueError("panels_device: the canvas must be a contiguous device uint8 buffer that holds Hc rows of `pitch` bytes")
-    _lib.launch(device, _lib.load().hh_heatmap_panels_u8, buf.data_ptr(), table.ctypes.data, n, image.data_ptr(), H, W, buf.data_ptr() + lut_at,
+    _lib.launch(device, _lib.load().hh_heatmap_panels_u8, blk.addr(0), table.ctypes.data, n, image.data_ptr(), H, W, blk.addr(lut_at),
                 canvas.data_ptr(), Hc, Wc, pitch, scratch.data_ptr())
     return canvas
 
