@@ -23,10 +23,10 @@ def per_frame(value, n: int) -> list:
 
 class Layout:
     """Sections appended to one byte block.  `end` is the block's size so far: a caller notes `upload = layout.end` where the
-    device-only sections begin."""
+    device-only sections begin.  A caller with a layout of its own in front starts at its end."""
 
-    def __init__(self):
-        self.end = 0
+    def __init__(self, end: int = 0):
+        self.end = int(end)
 
     def add(self, nbytes: int, align_to: int = 64) -> int:
         """-> the offset of a new section of `nbytes`, the next multiple of `align_to`."""

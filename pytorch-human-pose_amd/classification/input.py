@@ -31,7 +31,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .. import _lib
-from .._stage import PinnedRing, align
+from .._stage import Layout, PinnedRing, align
 from ..keypoints import jpeg as jp
 from ..keypoints.transforms_utils import IMAGENET_MEAN, IMAGENET_STD
 
@@ -198,18 +198,16 @@ class ClsInput:
         # a JpegImage ships no pixels: its slot in the pixel area is empty
         offs, desc_off, target_off, total = self.layout([(0, 0) if isinstance(img, jp.JpegImage) else hw for hw, (img, _) in zip(shapes, samples)])
         image_at = [int(o) for o in offs[:-1]]
-        if jpeg_at:
-            # behind the targets, 16-aligned: [decode descriptors | slice, tables | ...]; behind the staged bytes, on the device only:
-            # the pixel slots the decode fills, then its statuses
-            plans = [samples[b][0].window_plan((windows[b].top, windows[b].left, *shapes[b])) for b in jpeg_at]
-            jpeg_off = align(total, 16)
-            places = jpeg_off + align(jp.WIN_DESC.itemsize * len(jpeg_at), 16) + np.cumsum([0] + [p.staged_bytes for p in plans])
-            total = int(places[-1])
-            pixel_offs = align(total, 16) + np.cumsum([0] + [align(h * w * 3, 16) for h, w in (shapes[b] for b in jpeg_at)])
-            for i, b in enumerate(jpeg_at):
-                image_at[b] = int(pixel_offs[i])
-            status_off = int(pixel_offs[-1])
-            device_bytes = status_off + 4 * len(jpeg_at)
+        # behind the targets, 16-aligned: [decode descriptors | slice, tables | ...]; behind the staged bytes, on the device only: the
+        # decode's statuses and the pixel slots it fills
+        jpegs = jp.JpegBatch([samples[b][0] for b in jpeg_at],
+                             [samples[b][0].window_plan((windows[b].top, windows[b].left, *shapes[b])) for b in jpeg_at], "ClsInput.build")
+        lay = Layout(total)
+        jpegs.place_upload(lay)
+        total = lay.end
+        jpegs.place_device(lay)
+        for b, at in zip(jpeg_at, jpegs.pixel_at):
+            image_at[b] = at
         turn, host = self._ring.take(total)
         hview = host.numpy()
         descs = hview[desc_off:target_off].view(_CROP_DESC)
@@ -221,21 +219,13 @@ class ClsInput:
             # the shipped image IS the crop: tap indices are relative to the crop and never leave it, so nothing else is read
             descs[b] = (image_at[b], h, w, 0, 0, h, w, q.rh, q.rw, q.oy, q.ox, int(bool(q.flip)), int(bool(q.antialias)))
             targets_host[b] = int(target)
-        if jpeg_at:
-            jdescs = hview[jpeg_off:jpeg_off + jp.WIN_DESC.itemsize * len(jpeg_at)].view(jp.WIN_DESC)
-            jinfos = []
-            ws_offs = np.cumsum([0] + [p.ws_bytes for p in plans])
-            for i, (b, p) in enumerate(zip(jpeg_at, plans)):
-                it = samples[b][0]
-                stream_at, tables_at, _, info = it.stage_window(hview, int(places[i]), p.window, p)
-                jinfos.append(info)
-                jdescs[i] = it.window_desc(p, stream_at, tables_at, image_at[b], int(ws_offs[i]), 3 * shapes[b][1])
+        jpegs.fill(hview)
 
         dev = torch.device(self.device)
         with torch.cuda.device(dev):
             cur = torch.cuda.current_stream(dev)
             if jpeg_at:
-                raw = torch.empty(device_bytes, device=dev, dtype=torch.uint8)
+                raw = torch.empty(lay.end, device=dev, dtype=torch.uint8)
                 raw[:total].copy_(host[:total], non_blocking=True)
             else:
                 raw = host[:total].to(dev, non_blocking=True)
@@ -245,11 +235,7 @@ class ClsInput:
             self.last_h2d_bytes, self.last_launches = total, 4 if jpeg_at else 1
             images = torch.empty((B, 3, S, S), device=dev, dtype=torch.float32)
             base = raw.data_ptr()
-            self._jpeg_status = None
-            if jpeg_at:  # the pixels of the JpegImage samples first: the launch below reads them
-                work = torch.empty(max(int(ws_offs[-1]), 16), device=dev, dtype=torch.uint8)
-                jp.launch_decode_window(dev, base, base + jpeg_off, jdescs, np.concatenate(jinfos), work, base + status_off)
-                self._jpeg_status = raw[status_off:status_off + 4 * len(jpeg_at)].view(torch.int32)
+            self._jpeg_status = jpegs.launch(raw)  # the pixels of the JpegImage samples first: the launch below reads them
             # the descriptors are checked on their HOST copy in the staging buffer (nothing is read back from the device)
             _lib.launch(dev, lib.hh_resized_crop_u8_batch, base, base + desc_off, descs.ctypes.data, B, images.data_ptr(), S, S,
                         self.mean.ctypes.data, self.std.ctypes.data)

@@ -461,10 +461,6 @@ def launch_decode(dev, base: int, descs_dev: int, descs: np.ndarray, infos: np.n
                 status_dev)
 
 
-def launch_decode_window(dev, base: int, descs_dev: int, descs: np.ndarray, infos: np.ndarray, work, status_dev: int) -> None:
-    launch_decode(dev, base, descs_dev, descs, infos, work, status_dev, "hh_jpeg_decode_window_u8_batch")
-
-
 def raise_status(statuses, what: str = "hh_jpeg_decode_u8_batch") -> None:
     bad = [(i, int(s)) for i, s in enumerate(statuses) if int(s)]
     if bad:
@@ -488,6 +484,69 @@ def index_mcus_per_segment(items: list, what: str):
     if len(sizes) > 1:
         raise ValueError(f"{what}: the device-indexed images of one batch must share one mcus_per_segment, got {sorted(sizes)}")
     return next(iter(sizes), None)
+
+
+class JpegBatch:
+    """The JpegImage inputs of one staged batch (`infer_images`, `TrainInput.build`, `ClsInput.build`): where their bytes lie in the
+    caller's one copy, where their pixels are formed on the device, the descriptor rows, the calls.  `plans`: one `window_plan` per
+    item for a window decode (WIN_DESC rows, hh_jpeg_decode_window_u8_batch); None decodes every image whole (DEC_DESC rows,
+    hh_jpeg_decode_u8_batch, with ONE hh_jpeg_index_device_batch in front where an item's index is the device's to build).  In order:
+    `place_upload` with the caller's Layout at the end of its uploaded bytes, `place_device` with it in the device-only tail, `fill`
+    on the pinned bytes, `launch` on the device buffer.  Without items every step does nothing: the caller's layout is unchanged."""
+
+    def __init__(self, items: list, plans: list | None = None, what: str = "JpegBatch"):
+        self.items, self.windowed = list(items), plans is not None
+        self.plans = list(plans) if self.windowed else [it.whole_plan() for it in self.items]
+        self.desc_t = WIN_DESC if self.windowed else DEC_DESC
+        self.index_mps = index_mcus_per_segment(self.items, what)
+        self.calls = 2 if self.index_mps is not None else 1  # (each call has statuses of its own: the decode's, then the index call's)
+        self.ws_at = np.cumsum([0] + [p.ws_bytes for p in self.plans])
+        self.pixel_at: list = []
+
+    def __len__(self) -> int:
+        return len(self.items)
+
+    def place_upload(self, lay: Layout) -> None:
+        """[descriptors | stream or slice, table block | ...], each 16-aligned (`staged_bytes` is a multiple of 16: back to back)."""
+        if self.items:
+            self.desc_at = lay.add(self.desc_t.itemsize * len(self), 16)
+            self.places = [lay.add(p.staged_bytes, 16) for p in self.plans]
+
+    def place_device(self, lay: Layout) -> None:
+        """[statuses, int32 per item and call | pixel slots, 16-aligned]: nothing of them is copied.  `pixel_at`: per item its slot."""
+        if self.items:
+            self.status_at = lay.add(4 * len(self) * self.calls, 4)
+            self.pixel_at = [lay.add(p.window[2] * p.window[3] * 3, 16) for p in self.plans]
+
+    def fill(self, hview: np.ndarray) -> None:
+        """Streams, table blocks and descriptor rows into the pinned bytes; the infos the library validates the rows by are kept."""
+        if not self.items:
+            return
+        self.descs = hview[self.desc_at:self.desc_at + self.desc_t.itemsize * len(self)].view(self.desc_t)
+        infos = []
+        for k, (it, p) in enumerate(zip(self.items, self.plans)):
+            stream_at, tables_at, info = it.stage_plan(hview, self.places[k], p, self.windowed)
+            infos.append(info)
+            row = it.window_desc(p, stream_at, tables_at, self.pixel_at[k], int(self.ws_at[k]), 3 * p.window[3])
+            self.descs[k] = row if self.windowed else row[0]  # (DEC_DESC: no window)
+        self.infos = np.concatenate(infos)
+
+    def launch(self, raw):
+        """The calls on the current stream, on `raw`, the device buffer whose first bytes are the filled ones -> the int32 view of the
+        statuses ([calls * n]; `codes` reduces a host copy), or None without items.  Nothing synchronises."""
+        if not self.items:
+            return None
+        base = raw.data_ptr()
+        work = torch.empty(max(int(self.ws_at[-1]), 16), dtype=torch.uint8, device=raw.device)
+        if self.index_mps is not None:
+            launch_index(raw.device, base, base + self.desc_at, self.descs, self.infos, self.index_mps, None, base + self.status_at + 4 * len(self))
+        launch_decode(raw.device, base, base + self.desc_at, self.descs, self.infos, work, base + self.status_at,
+                      "hh_jpeg_decode_window_u8_batch" if self.windowed else "hh_jpeg_decode_u8_batch")
+        return raw[self.status_at:self.status_at + 4 * len(self) * self.calls].view(torch.int32)
+
+    def codes(self, status: np.ndarray) -> np.ndarray:
+        """Per item the larger of the calls' codes."""
+        return np.asarray(status).reshape(self.calls, len(self)).max(axis=0)
 
 
 def decode_jpeg_device(streams: list, index=None, bgr=False, device=None, out=None, windows=None, mcus_per_segment: int | None = None,

@@ -13,11 +13,14 @@ import torch
 from torch import Tensor, nn
 
 from .. import _lib
-from .._stage import PinnedRing, align, frames_to_host
+from .._stage import frames_to_host
 from ..optim import clip_grad_norm_
+from . import _infer_pipeline as ip
+from . import jpeg as jp
+from . import pose_score as ps
+from ._infer_pipeline import _IMAGE_DESC, plan_multi_scale  # noqa: F401  (read from here by tests and tools)
 from .grouping import MPPEHeatmapParser
-from .results import InferenceKeypointsResult, inverse_affine, transform_coords
-
+from .results import InferenceKeypointsResult, transform_coords
 from .transforms_utils import COCO_FLIP_INDEX, IMAGENET_MEAN, IMAGENET_STD, dst_to_src_matrix, get_multi_scale_size
 
 COCO_LIMBS = [(15, 13), (13, 11), (16, 14), (14, 12), (11, 12), (5, 11), (6, 12), (5, 6), (5, 7), (6, 8), (7, 9), (8, 10),
@@ -249,47 +252,8 @@ class KeypointsModule:
         return metrics, results
 
 
-# byte offset of the image in the batch buffer, its size, destination -> source affine; one source of hh_multi_scale_aggregate
-_IMAGE_DESC, _ScaleSrc = _lib.struct_dtype("hh_image_desc"), _lib.struct_ctype("hh_scale_src")
-
-
-class _Shape:
-    """What get_multi_scale_size reads of an image: its shape."""
-
-    def __init__(self, h: int, w: int):
-        self.shape = (int(h), int(w))
-
-
-def plan_multi_scale(shapes, input_size: int, scales, max_batch: int) -> list[dict]:
-    """Host plan of the batched multi-scale test (pure arithmetic, no device): raw image shapes [(h, w), ...] -> chunks, each
-    {"images": indices into `shapes`, "sizes": the (w, h) of the model input at every scale, "sub_batches": per scale the
-    consecutive (lo, hi) ranges of the chunk that run as one forward}; all three follow the order of `scales`, which is the
-    accumulation order of `multi_scale_maps`.
-    Buckets: images whose model-input sizes agree at EVERY scale (get_multi_scale_size truncates per scale, so the scale-1 size
-    alone need not fix the others).  Chunks: at most `max_batch` images of a bucket.  Sub-batches at scale s: n_s =
-    min(len(chunk), max(1, max_batch * h_1*w_1 // (h_s*w_s))) images, so that no forward carries more input pixels than the
-    scale-1 forward of `max_batch` images that the single-scale path runs."""
-    scales = tuple(scales)
-    if 1.0 not in scales:
-        raise ValueError("plan_multi_scale: scales must contain 1.0 (the scale-1 pass provides the tags and the output geometry)")
-    if max_batch < 1:
-        raise ValueError("plan_multi_scale: max_batch must be >= 1")
-    mn = min(scales)
-    buckets: dict[tuple, list[int]] = {}
-    for i, (h, w) in enumerate(shapes):
-        key = tuple(tuple(get_multi_scale_size(_Shape(h, w), input_size, s, mn)[0]) for s in scales)
-        buckets.setdefault(key, []).append(i)
-    plan = []
-    for sizes, idxs in buckets.items():
-        w1, h1 = sizes[scales.index(1.0)]
-        for lo in range(0, len(idxs), max_batch):
-            chunk = idxs[lo:lo + max_batch]
-            subs = []
-            for (ws, hs) in sizes:
-                n_s = min(len(chunk), max(1, max_batch * h1 * w1 // (hs * ws)))
-                subs.append([(a, min(a + n_s, len(chunk))) for a in range(0, len(chunk), n_s)])
-            plan.append({"images": chunk, "sizes": sizes, "sub_batches": subs})
-    return plan
+# one source of hh_multi_scale_aggregate
+_ScaleSrc = _lib.struct_ctype("hh_scale_src")
 
 
 class InferenceKeypointsModel:
@@ -327,8 +291,7 @@ class InferenceKeypointsModel:
         size, center, scale = get_multi_scale_size(image, self.input_size, current_scale, min_scale)
         m = dst_to_src_matrix(center, scale, size)  # destination -> source, as cv2.warpAffine inverts the forward matrix
         if hasattr(image, "stage"):  # a jpeg.JpegImage: only its bytes cross, its pixels are formed on the device (a bad stream raises)
-            from .jpeg import decode_jpeg_device
-            raw = decode_jpeg_device([image], device=self.device)[0]
+            raw = jp.decode_jpeg_device([image], device=self.device)[0]
         else:
             raw = torch.from_numpy(np.ascontiguousarray(image, dtype=np.uint8)).to(self.device)
         x = torch.empty((1, 3, size[1], size[0]), device=self.device, dtype=torch.float32)
@@ -468,292 +431,47 @@ class InferenceKeypointsModel:
         cur.wait_stream(self._stream)
         return out
 
-    @staticmethod
-    def _dst_to_src(size, center, scale) -> np.ndarray:
-        """The destination -> source 2x3 matrix of the resize-align warp (what cv2.warpAffine inverts for itself)."""
-        return dst_to_src_matrix(center, scale, size)
-
     def _geometry(self, image: np.ndarray):
         """Resize-align geometry of one raw image: ((w, h) of the model input, center, scale, destination->source 2x3 matrix)."""
         size, center, scale = get_multi_scale_size(image, self.input_size, 1, 1)
-        return size, center, scale, self._dst_to_src(size, center, scale)
+        return size, center, scale, dst_to_src_matrix(center, scale, size)
 
     @torch.no_grad()
     def infer_images(self, raw_images: list[np.ndarray], annots: list | None = None, max_batch: int = 32,
                      scales=None, render: dict | None = None, tracker=None, score: str | None = None) -> list[InferenceKeypointsResult]:
-        """The batched path behind the reference's single-image interface (`__call__` per image, bin/eval.py:18-49): images are
-        bucketed by model-input shape, every bucket runs as batches of up to `max_batch` -- ONE host->device copy of the raw
-        uint8 pixels, hh_preprocess_u8 per image into one [B,3,h,w] tensor, one (flip-TTA) forward, one hh_decode, one
-        device->host copy of the small result arrays -- and every image gets the result `self(image, annot)` returns
-        (same kernels on the same per-image data: images of a batch are independent).
-        `scales` = tuple of scales: the multi-scale test of `call_multi_scale(image, annot, scales)` for every image, batched the
-        same way (plan_multi_scale: buckets by the sizes at every scale, chunks of up to `max_batch`): the raw pixels still cross
-        once, with one descriptor block per scale behind them; one hh_preprocess_u8_batch per scale, the forwards of the plan, one
-        hh_multi_scale_aggregate per stage (and image range) instead of the per-scale flip merges and accumulations, one
-        hh_decode on the averaged maps and the scale-1 tags.
-        `render` = dict(color_mode="person", alpha=0.8, bgr=False, out_height=None): every result also carries `.rendered`, the
-        overlay frame of `result.plot_connections(color_mode, alpha)` (B,G,R order if `bgr`; resized to `out_height` with the aspect
-        ratio kept, as the reference's resize_with_aspect_ratio, if given).  The frames of a batch are drawn in ONE
-        hh_render_poses_u8_batch from the staged device pixels of that batch, which stay alive until then; with render=None nothing
-        of the pipeline changes.  With `jpeg=dict(quality=90, subsampling="420")` among the render options the frames of a batch are
-        encoded on the GPU in ONE hh_jpeg_encode_u8_batch behind their render launch (keypoints/jpeg.py) and every result carries
-        `.rendered_jpeg` (bytes; true colours also with `bgr`) in place of `.rendered`: no raw frame is copied back.
-        color_mode="track" (needs `tracker`) draws the smoothed coordinates, each person in the colour of its id.
-        With `labels=[[str, ...] or None, ...]` among the render options, one list per image, every finished frame (after the resize,
-        before the copy back or the encode) gets its list written on it as the reference's draw_labels writes a video frame's
-        (keypoints/text.py: loc="tl", alpha=0.6, font_scale=0.5), all frames of a batch in ONE hh_text_labels_u8_batch launch.
-        `tracker` = a keypoints.tracking.PoseTracker with one stream: `raw_images` are consecutive frames of ONE clip.  All must share
-        one model-input shape (else ValueError, before any launch) and that of the frames the tracker saw before (else reset() it).  The
-        chunks are fed in order, each as one hh_track_step behind its hh_decode on the same stream with frames_per_stream = the chunk
-        length; ids and smoothed coordinates come back in the batch's one device->host hand-over.  Every result gains `.track_ids`
-        (int32 [P], 0 = no track) and `.kpts_coords_smooth` ([P,K,2], raw-image pixels), aligned with its rows.  With tracker=None
-        nothing of the pipeline changes.
-        `score` = "oks" or "pckh": every image whose annot is not None is scored against it on the device (keypoints/pose_score.py): ONE
-        hh_pose_score_batch per batch behind its hh_decode (and behind the tracker's launch where there is one) on the same stream, reading
-        the decode's outputs in place with the image's inverse resize matrix (the scale-1 geometry with `scales`); the target tables cross
-        in one small pinned copy, the outputs ride as one more array in the batch's device->host hand-over.  Results gain `.oks`,
-        `.object_oks`, `.kpt_oks`, `.target_matches` (`.pckh`, `.object_pckh`, `.kpt_pckh` for "pckh", whose objects carry "head_xyxy"); a
-        later `calculate_OKS()` returns the stored value.  "oks" uses the COCO constants and is refused for a net of other than 17
-        keypoints, as is a parser that keeps more than 64 people; both before anything is enqueued.  The output array's size is rounded
-        up to a power of two, so the pinned result buffers are shared by batches of different target counts.  A batch without any annot
-        launches nothing; with score=None nothing of the pipeline changes.
+        """The batched path behind the reference's single-image interface (`__call__` per image, bin/eval.py:18-49): every image gets
+        the result `self(image, annot)` returns, from batches of up to `max_batch` images of one model-input shape that run as a
+        two-deep pipeline.  The stages are in keypoints/_infer_pipeline.py; each option is described where it is implemented:
+        `scales` = tuple of scales, the multi-scale test of `call_multi_scale` for every image: `plan_batches`, `Pipeline._launch`.
+        `render` = dict(color_mode, alpha, bgr, out_height, jpeg, labels): every result carries `.rendered` (or `.rendered_jpeg`):
+        `check_options`, `Pipeline._render`.
+        `tracker` = a keypoints.tracking.PoseTracker with one stream, the images being consecutive frames of ONE clip: results gain
+        `.track_ids` and `.kpts_coords_smooth`: `plan_batches`, `Pipeline._launch`, `Pipeline.collect`.
+        `score` = "oks" or "pckh": every image whose annot is not None is scored against it on the device (keypoints/pose_score.py):
+        `check_options`, `Pipeline.stage`, `Pipeline._launch`, `Pipeline._attach_scores`.
         An entry of `raw_images` may also be the `bytes` / `bytearray` / `memoryview` of a JPEG file or a `jpeg.JpegImage`, mixed freely
-        with arrays; bytes become `JpegImage(data, index="device")`: no Huffman pass and no pixel array on the host.  Bucketing reads
-        `.shape`.  The stream and table block of such an image travel in the batch's one pinned copy, behind the image descriptors; its
-        pixel slot lies behind the uploaded bytes in the same device buffer; ONE hh_jpeg_index_device_batch (for the images whose index
-        the device builds) and ONE hh_jpeg_decode_u8_batch fill the slots in front of hh_preprocess_u8_batch, which reads them exactly
-        as it reads shipped pixels, so `scales`, `render` and `tracker` work unchanged.  The decoder's statuses ride in the batch's
-        device->host hand-over; a nonzero one raises HHError naming the image when the batch's results are collected.  A file the
-        decoder refuses by name (progressive, CMYK, ...) is refused at `JpegImage(...)`: pass it as a Pillow array; there is no silent
-        fallback.  `.raw_image` of such a result is formed on first access by `decode_jpeg_host` (bit-identical to the device pixels)
-        and cached; no pixels are copied back.  A batch of arrays takes exactly the path it took before.  `self.last_h2d_bytes` keeps
-        the bytes the call uploaded."""
-        if render is not None and render.get("color_mode") == "track" and tracker is None:
-            raise ValueError("infer_images: render color_mode 'track' needs a tracker")
-        if render is not None:
-            unknown = set(render) - {"color_mode", "alpha", "bgr", "out_height", "jpeg", "labels"}
-            if unknown:
-                raise ValueError(f"infer_images: unknown render option(s) {sorted(unknown)}")
-            if render.get("labels") is not None and len(render["labels"]) != len(raw_images):
-                raise ValueError("infer_images: render labels: one list of strings (or None) per image")
-        if score not in (None, "oks", "pckh"):
-            raise ValueError(f"infer_images: score must be None, 'oks' or 'pckh', got {score!r}")
-        from . import jpeg as jp
-        from . import pose_score as ps
-        if score is not None:  # what the launch would refuse, refused here before anything is enqueued
-            if self._parser.max_num_people > ps.MAX_P:
-                raise ValueError(f"infer_images: score= takes at most HH_POSE_MAX_P ({ps.MAX_P}) people per image, the parser keeps {self._parser.max_num_people}")
-            # "oks" uses the COCO constants and so needs the 17 COCO keypoints (ValueError otherwise); PCKh reads no variance
-            score_vars = ps.coco_variances(self._parser.num_kpts) if score == "oks" else np.ones(self._parser.num_kpts)
-            if self._score_stage is None:
-                self._score_stage = [ps.TableStage(), ps.TableStage()]  # pinned table buffers, one per pipeline slot
+        with arrays; bytes become `JpegImage(data, index="device")`: no Huffman pass and no pixel array on the host.  A file the decoder
+        refuses by name (progressive, CMYK, ...) is refused at `JpegImage(...)`: pass it as a Pillow array; there is no silent
+        fallback: `Pipeline.stage`, `Pipeline._launch`, `Pipeline.collect`.
+        With an option left at None nothing of the pipeline changes; a batch of arrays takes exactly the path it took before.
+        `self.last_h2d_bytes` keeps the bytes the call uploaded."""
+        score_vars = ip.check_options(render, tracker, score, len(raw_images), self._parser.num_kpts, self._parser.max_num_people)
+        if score is not None and self._score_stage is None:
+            self._score_stage = [ps.TableStage(), ps.TableStage()]  # pinned table buffers, one per pipeline slot
         raw_images = [jp.JpegImage(img, index="device") if isinstance(img, (bytes, bytearray, memoryview)) else img for img in raw_images]
-        n = len(raw_images)
-        annots = annots if annots is not None else [None] * n
+        annots = annots if annots is not None else [None] * len(raw_images)
         self.last_h2d_bytes = 0
-        # (size, center, scale) now -- the bucket key --, the warp matrix when the image's batch is staged: the first batch should
-        # not wait for n matrix inversions
-        if scales is None:
-            pass_scales, mn = (1,), 1
-            geo: list = [get_multi_scale_size(img, self.input_size, 1, 1) for img in raw_images]
-            buckets: dict[tuple, list[int]] = {}
-            for i, g in enumerate(geo):
-                buckets.setdefault(tuple(g[0]), []).append(i)
-            jobs = {(size,): [(idxs[lo:lo + max_batch], None) for lo in range(0, len(idxs), max_batch)] for size, idxs in buckets.items()}
-        else:
-            pass_scales = tuple(scales)
-            plan = plan_multi_scale([img.shape[:2] for img in raw_images], self.input_size, pass_scales, max_batch)
-            mn = min(pass_scales)
-            geo = [get_multi_scale_size(img, self.input_size, 1.0, mn) for img in raw_images]  # the un-warp is the scale-1 pass's
-            jobs = {}
-            for c in plan:
-                jobs.setdefault(c["sizes"], []).append((c["images"], c["sub_batches"]))
-        i1 = pass_scales.index(1)
-        if tracker is not None and n:
-            if tracker.streams != 1:
-                raise ValueError("infer_images: the tracker must have one stream (the images are one clip)")
-            shapes = {tuple(sizes[i1]) for sizes in jobs}
-            if len(shapes) != 1:
-                raise ValueError(f"infer_images: the frames of a tracked clip must share one model-input shape, got (w, h) = {sorted(shapes)}")
-            tracker.bind_input_shape(next(iter(shapes))[::-1])
-        results: list = [None] * n
-        mean, std = IMAGENET_MEAN.ctypes.data, IMAGENET_STD.ctypes.data
-
-        def finish(job):
-            """device -> host results of one enqueued batch, un-warp, result objects"""
-            chunk, (w, h), x, hms, tags, host_out, done, staged, jpeg_at, scored = job
-            done.synchronize()
-            if jpeg_at:  # the decoder's statuses came with the results: the index call's codes, if it ran, behind the decode's
-                codes = host_out[-1].numpy().reshape(-1, len(jpeg_at)).max(axis=0)
-                bad = [(chunk[j], int(s)) for j, s in zip(jpeg_at, codes) if int(s)]
-                if bad:
-                    i, s = bad[0]
-                    name = jp.STATUS_NAMES[s] if 0 <= s < len(jp.STATUS_NAMES) else "unknown"
-                    raise _lib.HHError(f"infer_images: image {i}: its JPEG stream cannot be decoded: status {s} ({name})"
-                                       + (f"; also images {[k for k, _ in bad[1:]]}" if len(bad) > 1 else ""))
-            lists = self._parser.to_lists(*host_out[:4])  # (copies what it returns: the pinned buffers are reused two batches later)
-            self.model_input_shape = (h, w)
-            for j, i in enumerate(chunk):
-                joints, scores = lists[j]
-                coords = transform_coords(joints[..., :2], geo[i][1], geo[i][2], (w, h))
-                results[i] = InferenceKeypointsResult(raw_images[i], annots[i], x[j], coords, joints[..., 2], joints[..., 3:], scores,
-                                                      self.det_thr, self.tag_thr, self.limbs, [t[j:j + 1] for t in hms],
-                                                      [t[j:j + 1] for t in tags])
-                if tracker is not None:
-                    p = len(joints)
-                    results[i].track_ids = host_out[4][j, :p].numpy().copy()
-                    results[i].kpts_coords_smooth = transform_coords(host_out[5][j, :p].numpy(), geo[i][1], geo[i][2], (w, h)).astype(coords.dtype)
-            if scored is not None:
-                parts = scored.split(host_out[6 if tracker is not None else 4])
-                t_off = scored.t_off
-                for j, i in enumerate(chunk):
-                    if annots[i] is not None:
-                        a, b = int(t_off[j]), int(t_off[j + 1])
-                        value = float(parts["value"][j])
-                        results[i]._set_score(score, -1 if b == a else value, parts["obj"][a:b], parts["kpt"][a:b], parts["match"][a:b])
-            if staged is not None:
-                options = dict(render)
-                if options.get("labels") is not None:
-                    options["labels"] = [render["labels"][i] for i in chunk]
-                self._render_chunk([results[i] for i in chunk], *staged, **options)
-
-        # Two-deep software pipeline: while the GPU works on batch k the host stages the pixels of batch k+1 into a pinned
-        # buffer and only then collects the results of batch k (two staging buffers, each guarded by the event of its last use).
-        staging = PinnedRing()
+        plan = ip.plan_batches(raw_images, self.input_size, scales, max_batch, tracker)
+        run = ip.Pipeline(self, plan, raw_images, annots, render, tracker, score, score_vars)
         pending = None
-        for sizes, chunks in jobs.items():
-            for chunk, subs in chunks:
-                w, h = sizes[i1]
-                nb = len(chunk)
-                jpeg_at = [j for j, i in enumerate(chunk) if isinstance(raw_images[i], jp.JpegImage)]
-                offs = np.cumsum([0] + [0 if isinstance(raw_images[i], jp.JpegImage) else raw_images[i].size for i in chunk])
-                desc_off = align(int(offs[-1]))  # the image descriptors travel behind the pixels, in the same copy
-                total = desc_off + _IMAGE_DESC.itemsize * nb * len(sizes)  # (one block of them per scale)
-                starts = [int(o) for o in offs[:-1]]  # where image j's pixels lie in the device buffer
-                dev_total, jplan = total, None
-                if jpeg_at:
-                    # a JPEG image ships no pixels: [decode descriptors | stream, table block | ...] travel behind the image descriptors in
-                    # the same copy; the statuses and the pixel slots, which the decode fills, lie behind the uploaded bytes on the device
-                    items = [raw_images[chunk[j]] for j in jpeg_at]
-                    jdesc_off = align(total, 16)
-                    places = jdesc_off + jp.DEC_DESC.itemsize * len(items) + np.cumsum([0] + [it.staged_bytes() for it in items])
-                    total = int(places[-1])
-                    status_off = total  # (a multiple of 16)
-                    at = status_off + 8 * len(items)
-                    for j, it in zip(jpeg_at, items):
-                        starts[j] = at = align(at, 16)
-                        at += it.h * it.w * 3
-                    dev_total = at
-                    ws_offs = np.cumsum([0] + [it.ws_bytes for it in items])
-                    jplan = (items, jdesc_off, places, status_off, ws_offs, jp.index_mcus_per_segment(items, "infer_images"))
-                targets = None
-                if score is not None and any(annots[i] is not None for i in chunk):
-                    # the annotations are packed (and refused, if they must be) before anything of this batch is enqueued
-                    targets = ps.pack_targets([annots[i] for i in chunk], score, num_kpts=self._parser.num_kpts)
-                    inv = np.stack([inverse_affine(geo[i][1], geo[i][2], (w, h)) for i in chunk])
-                    targets = (targets, inv, score_vars)
-                self.last_h2d_bytes += total
-                turn, host = staging.take(total)  # (the slot's index also picks this batch's _score_stage and _out_ring buffers)
-                hview = host.numpy()
-                descs = hview[desc_off:desc_off + _IMAGE_DESC.itemsize * nb * len(sizes)].view(_IMAGE_DESC)
-                for j, i in enumerate(chunk):
-                    img = raw_images[i]
-                    if not isinstance(img, jp.JpegImage):
-                        np.copyto(hview[offs[j]:offs[j + 1]].reshape(img.shape), img, casting="same_kind")
-                    for si, s in enumerate(pass_scales):
-                        g = geo[i] if si == i1 else get_multi_scale_size(img, self.input_size, s, mn)
-                        descs[si * nb + j] = (starts[j], img.shape[0], img.shape[1], self._dst_to_src(*g).reshape(6))
-                jdescs = jinfos = None
-                if jplan is not None:
-                    items, jdesc_off, places, status_off, ws_offs, _ = jplan
-                    jdescs = hview[jdesc_off:jdesc_off + jp.DEC_DESC.itemsize * len(items)].view(jp.DEC_DESC)
-                    for k, (j, it) in enumerate(zip(jpeg_at, items)):
-                        stream_at, tables_at = it.stage(hview, int(places[k]))
-                        jdescs[k] = (stream_at, tables_at, it.tables_bytes, starts[j], int(ws_offs[k]), 3 * it.w, it.data.size, it.nseg, 0, 0)
-                    jinfos = np.concatenate([it.info for it in items])
-
-                # host -> device on a copy stream of its own, so that the pixels of this batch cross PCIe while the previous
-                # batch still computes (25 MB per batch of 32 512x512 images: ~1.7 ms that would otherwise sit on the compute stream)
-                if self._copy_stream is None:
-                    self._copy_stream = torch.cuda.Stream(self.device)
-                    # (the priority of the compute stream: at a lower one the result copies would wait for the whole next batch)
-                    self._d2h_stream = torch.cuda.Stream(self.device, priority=torch.cuda.Stream.priority_range()[1])
-                with torch.cuda.stream(self._copy_stream):
-                    if jplan is None:
-                        raw = host[:total].to(self.device, non_blocking=True)
-                    else:  # (room behind the uploaded bytes for the statuses and the decoded pixels)
-                        raw = torch.empty(dev_total, dtype=torch.uint8, device=self.device)
-                        raw[:total].copy_(host[:total], non_blocking=True)
-                    copied = torch.cuda.Event()
-                    copied.record()
-
-                def run(chunk=chunk, raw=raw, copied=copied, desc_off=desc_off, w=w, h=h, turn=turn, nb=nb, sizes=sizes, subs=subs, offs=starts,
-                        jplan=jplan, jdescs=jdescs, jinfos=jinfos, jpeg_at=jpeg_at, targets=targets):
-                    cur = torch.cuda.current_stream(self.device)
-                    cur.wait_event(copied)
-                    raw.record_stream(cur)
-                    jstatus = None
-                    if jplan is not None:
-                        # one index call (where an image's index is the device's to build) and one decode call fill the pixel slots in
-                        # front of the preprocess launches, which read them as they read shipped pixels
-                        items, jdesc_off, _, status_off, ws_offs, mps = jplan
-                        work = torch.empty(max(int(ws_offs[-1]), 16), dtype=torch.uint8, device=self.device)
-                        base, nj = raw.data_ptr(), len(items)
-                        if mps is not None:
-                            jp.launch_index(self.device, base, base + jdesc_off, jdescs, jinfos, mps, None, base + status_off + 4 * nj)
-                        jp.launch_decode(self.device, base, base + jdesc_off, jdescs, jinfos, work, base + status_off)
-                        jstatus = raw[status_off:status_off + 4 * nj * (2 if mps is not None else 1)].view(torch.int32)
-
-                    def prepare(si):
-                        ws, hs = sizes[si]
-                        xs = torch.empty((nb, 3, hs, ws), device=self.device, dtype=torch.float32)
-                        # one launch for the whole batch, whatever the raw sizes
-                        _lib.launch(xs.device, self._lib.hh_preprocess_u8_batch, raw.data_ptr(), raw.data_ptr() + desc_off + 64 * nb * si, nb,
-                                    xs.data_ptr(), hs, ws, mean, std)
-                        return xs
-
-                    x = prepare(i1)
-                    hms, tags = self.forward_tta(x) if subs is None else self._multi_scale_maps_batch(pass_scales, subs, x, prepare)
-                    out = self._parser.decode_batch_device(hms[0], hms[1], tags, adjust=True, refine=True)
-                    if tracker is not None:
-                        out = out + tracker.update_device(*out, frames_per_stream=nb)[:2]
-                    scored = None
-                    if targets is not None:
-                        # (this slot's previous batch has been collected, so its table copy has finished: the pinned buffer is free)
-                        scored = ps.score_device(targets[0], decode=tuple(out[:4]), inv_affine=targets[1], metric=score, variances=targets[2],
-                                                 stage=self._score_stage[turn])
-                        out = tuple(out) + (scored.blob,)
-                    if jstatus is not None:
-                        out = tuple(out) + (jstatus,)  # (the statuses ride in the same hand-over)
-                    # device -> host into pinned buffers kept per pipeline slot (allocating pinned memory costs ~0.4 ms per array);
-                    # finish() of this slot's previous batch ran before this point and copied what it keeps
-                    key = (turn, tuple((tuple(t.shape), t.dtype) for t in out))
-                    ring = self._out_ring
-                    if key not in ring:
-                        ring[key] = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in out]
-                    # ... on a stream of their own behind the decode, so that the next batch's launches do not queue behind them
-                    decoded = torch.cuda.Event()
-                    decoded.record()
-                    with torch.cuda.stream(self._d2h_stream):
-                        self._d2h_stream.wait_event(decoded)
-                        host_out = [h.copy_(t, non_blocking=True) for h, t in zip(ring[key], out)]
-                        done = torch.cuda.Event()
-                        done.record()
-                    for t in out:
-                        t.record_stream(self._d2h_stream)
-                    staged = (raw, offs) if render is not None else None  # the batch's device pixels, kept until its render has run
-                    return (chunk, (w, h), x, hms, tags, host_out, done, staged, jpeg_at if jstatus is not None else [], scored), copied, raw
-
-                # (the model's high-priority stream, for batches as for single images: same-box alternation with the caller's
-                # stream, tools/api_throughput.py: 3820 / 3380 against 2600 / 2970 img/s)
-                job, copied, _raw = self._on_fast_stream(run)
-                staging.release(turn, copied)
-                if pending is not None:
-                    finish(pending)
-                pending = job
+        for sizes, chunk, subs in plan.jobs:
+            batch = run.enqueue(run.stage(sizes, chunk, subs))
+            if pending is not None:
+                run.collect(pending)
+            pending = batch
         if pending is not None:
-            finish(pending)
-        return results
+            run.collect(pending)
+        return run.results
 
     def _render_chunk(self, results: list, raw: Tensor, offs, color_mode: str = "person", alpha: float = 0.8, bgr: bool = False,
                       out_height: int | None = None, jpeg: dict | None = None, labels: list | None = None) -> None:
@@ -779,12 +497,31 @@ class InferenceKeypointsModel:
             tx.put_txt_device(out, [tx.video_table(int(f.shape[0]), int(f.shape[1]), lines) if lines is not None else np.zeros(0, tx.PRIM)
                                     for f, lines in zip(out, labels)])
         if jpeg is not None:
-            from .jpeg import encode_jpeg_device
-            for r, data in zip(results, encode_jpeg_device(out, bgr=bgr, **jpeg)):
+            for r, data in zip(results, jp.encode_jpeg_device(out, bgr=bgr, **jpeg)):
                 r.rendered_jpeg = data
             return
         for r, frame in zip(results, frames_to_host(out)):
             r.rendered = frame
+
+    def _single(self, raw_image, annot, tracker=None) -> InferenceKeypointsResult:
+        """One image on the fast stream: prepare_input, forward_tta, hh_decode, (`tracker`: one hh_track_step behind the decode on the
+        same stream, one frame of the tracker's one stream,) the result as `InferenceKeypointsResult.from_preds` builds it."""
+        def run():
+            x, center, scale = self.prepare_input(raw_image)
+            h, w = self.model_input_shape = tuple(x.shape[-2:])
+            hms, tags = self.forward_tta(x)
+            out = self._parser.decode_batch_device(hms[0], hms[1], tags, adjust=True, refine=True)
+            track = tracker.update_device(*out, frames_per_stream=1) if tracker is not None else None
+            joints, scores = self._parser.to_lists(*out)[0]
+            coords = transform_coords(joints[..., :2], center, scale, (w, h))
+            result = InferenceKeypointsResult(raw_image, annot, x[0], coords, joints[..., 2], joints[..., 3:], scores, self.det_thr, self.tag_thr,
+                                              self.limbs, hms, tags)
+            if track is not None:
+                p = len(joints)
+                result.track_ids = track[0][0, :p].cpu().numpy()
+                result.kpts_coords_smooth = transform_coords(track[1][0, :p].cpu().numpy(), center, scale, (w, h)).astype(coords.dtype)
+            return result
+        return self._on_fast_stream(run)
 
     def _call_tracked(self, raw_image: np.ndarray, tracker) -> InferenceKeypointsResult:
         """`self(raw_image, None)` with one hh_track_step behind the decode on the same stream (one frame of the tracker's one stream)."""
@@ -792,22 +529,7 @@ class InferenceKeypointsModel:
             raise ValueError("video_frame: the tracker must have one stream")
         size = get_multi_scale_size(raw_image, self.input_size, 1, 1)[0]
         tracker.bind_input_shape((size[1], size[0]))  # (raises before any launch)
-
-        def run():
-            x, center, scale = self.prepare_input(raw_image)
-            h, w = self.model_input_shape = tuple(x.shape[-2:])
-            hms, tags = self.forward_tta(x)
-            out = self._parser.decode_batch_device(hms[0], hms[1], tags, adjust=True, refine=True)
-            ids, smooth, _ = tracker.update_device(*out, frames_per_stream=1)
-            joints, scores = self._parser.to_lists(*out)[0]
-            p = len(joints)
-            coords = transform_coords(joints[..., :2], center, scale, (w, h))
-            result = InferenceKeypointsResult(raw_image, None, x[0], coords, joints[..., 2], joints[..., 3:], scores, self.det_thr, self.tag_thr,
-                                              self.limbs, hms, tags)
-            result.track_ids = ids[0, :p].cpu().numpy()
-            result.kpts_coords_smooth = transform_coords(smooth[0, :p].cpu().numpy(), center, scale, (w, h)).astype(coords.dtype)
-            return result
-        return self._on_fast_stream(run)
+        return self._single(raw_image, None, tracker)
 
     def video_frame(self, image: np.ndarray, tracker=None, jpeg: dict | None = None, labels: list | None = None):
         """`video_processing_fn` (keypoints/bin/inference.py:49-75) -> (result, out_frame): one inference,
@@ -843,8 +565,7 @@ class InferenceKeypointsModel:
             from . import text as tx
             tx.put_txt_device([frame], [tx.video_table(int(frame.shape[0]), int(frame.shape[1]), labels)])
         if jpeg is not None:
-            from .jpeg import encode_jpeg_device
-            return result, encode_jpeg_device([frame], bgr=True, **jpeg)[0]
+            return result, jp.encode_jpeg_device([frame], bgr=True, **jpeg)[0]
         return result, vz.to_host(frame)
 
     def __call__(self, raw_image: np.ndarray, annot: list | None) -> InferenceKeypointsResult:
@@ -852,13 +573,5 @@ class InferenceKeypointsModel:
         the index (of bytes: on the device) and the pixels are formed on the GPU, and the result's `.raw_image` is decoded on the host
         on first access."""
         if isinstance(raw_image, (bytes, bytearray, memoryview)):
-            from .jpeg import JpegImage
-            raw_image = JpegImage(raw_image, index="device")
-
-        def run():
-            x, center, scale = self.prepare_input(raw_image)
-            self.model_input_shape = tuple(x.shape[-2:])
-            hms, tags = self.forward_tta(x)
-            return InferenceKeypointsResult.from_preds(raw_image, annot, x[0], hms, tags, self.limbs, scale, center, self.det_thr,
-                                                       self.tag_thr, self.max_num_people, parser=self._parser)
-        return self._on_fast_stream(run)
+            raw_image = jp.JpegImage(raw_image, index="device")
+        return self._single(raw_image, annot)

@@ -28,7 +28,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .. import _lib
-from .._stage import PinnedRing, align
+from .._stage import Layout, PinnedRing, align
 from . import crowd_mask as cm
 from . import jpeg as jp
 from .loss import DeviceJoints, pack_joints
@@ -273,12 +273,11 @@ class TrainInput:
         desc_off = align(int(offs[-1]))  # the descriptors travel behind the pixels and masks, in the same copy
         mosaic_off = desc_off + _TRAIN_DESC.itemsize * B
         crowd_off = mosaic_off + _MOSAIC_DESC.itemsize * M  # (a multiple of 8: both descriptor sizes are)
-        total = crowd_off + cm.tables_bytes(seg_items)
+        lay = Layout(crowd_off + cm.tables_bytes(seg_items))
         # a JpegImage ships its stream and table block behind the crowd tables: [decode descriptors | stream, tables | ...], 16-aligned
-        jpeg_off = align(total, 16)
-        jpeg_places = jpeg_off + jp.DEC_DESC.itemsize * len(jpeg_items) + np.cumsum([0] + [it.staged_bytes() for it in jpeg_items])
-        if jpeg_items:
-            total = int(jpeg_places[-1])
+        jpegs = jp.JpegBatch(jpeg_items, what="TrainInput.build")
+        jpegs.place_upload(lay)
+        total = lay.end
         # the canvases of the mosaic samples lie behind the staged bytes in the device buffer; nothing of them is copied
         canvas_off = align(total)
         # ... and behind them the masks of the segment samples, which hh_crowd_masks_u8_batch fills there
@@ -286,13 +285,13 @@ class TrainInput:
         mask_at_raw = [int(offs[R + r]) for r in range(R)]
         for i, r in enumerate(seg_raws):
             mask_at_raw[r] = int(fill_offs[i])
-        # ... and behind those the pixel slots of the JpegImage samples, which hh_jpeg_decode_u8_batch fills there, and its statuses
-        pixel_offs = align(int(fill_offs[-1]), 16) + np.cumsum([0] + [align(it.h * it.w * 3, 16) for it in jpeg_items])
+        # ... and behind those the statuses and the pixel slots of the JpegImage samples, which hh_jpeg_decode_u8_batch fills there
+        lay.end = int(fill_offs[-1])
+        jpegs.place_device(lay)
+        device_bytes = lay.end
         image_at_raw = [int(offs[r]) for r in range(R)]
-        for i, r in enumerate(jpeg_raws):
-            image_at_raw[r] = int(pixel_offs[i])
-        status_off = int(pixel_offs[-1])
-        device_bytes = status_off + 4 * len(jpeg_items) if jpeg_items else int(fill_offs[-1])
+        for r, at in zip(jpeg_raws, jpegs.pixel_at):
+            image_at_raw[r] = at
         if M and (S % 4 or S < 4):
             raise _lib.HHError("TrainInput.build: a mosaic needs an out_size that is a multiple of 4 (hh_mosaic_u8_batch)")
         turn, host = self._ring.take(total)
@@ -300,13 +299,7 @@ class TrainInput:
         descs = hview[desc_off:mosaic_off].view(_TRAIN_DESC)
         mdescs = hview[mosaic_off:crowd_off].view(_MOSAIC_DESC)
         crowd_desc_at, crowd_seg_at, crowd_nseg = cm.fill_tables(seg_items, fill_offs[:-1], hview, crowd_off)
-        if jpeg_items:
-            jdescs = hview[jpeg_off:jpeg_off + jp.DEC_DESC.itemsize * len(jpeg_items)].view(jp.DEC_DESC)
-            jinfos = np.concatenate([it.info for it in jpeg_items])
-            ws_offs = np.cumsum([0] + [it.ws_bytes for it in jpeg_items])
-            for i, it in enumerate(jpeg_items):
-                stream_at, tables_at = it.stage(hview, int(jpeg_places[i]))
-                jdescs[i] = (stream_at, tables_at, it.tables_bytes, int(pixel_offs[i]), int(ws_offs[i]), 3 * it.w, it.data.size, len(it.segments), 0, 0)
+        jpegs.fill(hview)
         for r, (img, mask, _) in enumerate(raws):
             h, w = shapes[r]
             if not isinstance(img, jp.JpegImage):
@@ -352,11 +345,7 @@ class TrainInput:
             masks = [torch.empty((B, s, s), device=dev, dtype=torch.float32) for s in self.hm_sizes]
             heatmaps = [torch.empty((B, K, s, s), device=dev, dtype=torch.float32) for s in self.hm_sizes]
             base = raw.data_ptr()
-            self._jpeg_status = None
-            if jpeg_items:  # the pixels of the JpegImage samples first of all: everything below reads them
-                work = torch.empty(max(int(ws_offs[-1]), 16), device=dev, dtype=torch.uint8)
-                jp.launch_decode(dev, base, base + jpeg_off, jdescs, jinfos, work, base + status_off)
-                self._jpeg_status = raw[status_off:status_off + 4 * len(jpeg_items)].view(torch.int32)
+            self._jpeg_status = jpegs.launch(raw)  # the pixels of the JpegImage samples first of all: everything below reads them
             if seg_items:  # the masks of the segment samples first: the mosaic and the mask warp read them
                 cm.launch(dev, base, host.data_ptr(), crowd_desc_at, crowd_seg_at, len(seg_items), crowd_nseg)
             if M:  # the canvases next: the two warp launches below read them
