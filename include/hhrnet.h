@@ -1389,6 +1389,62 @@ int hh_linear_forward(const float *x, const float *w, const float *bias, int B, 
 int hh_linear_backward(const float *x, const float *w, const float *dy, int B, int K, int N, float *dx, float *dw, float *db, void *stream);
 int hh_softmax_xent(const float *logits, const int64_t *targets, int B, int N, float *dlogits, hh_xent_result *result, void *stream);
 
+/* Evaluation of the classifier on the device (csrc/cls_score.hip, csrc/cls_score_math.h; classification/evaluation.py ClsEvaluator,
+ * evaluate_images): top-k, rank, loss and the running state of a whole evaluation from a batch of logits, nothing read back.  The
+ * reference has no evaluation script (its bin/eval.py is a stub); the metric names are those of its get_metrics.
+ * (Additive entry points: HH_ABI_VERSION stays 3.)
+ *
+ * INPUTS: logits fp32 [B,N] contiguous, targets int64 [B] or NULL, 0 <= B <= HH_CLS_MAX_B, 1 <= N <= HH_CLS_MAX_N,
+ *   1 <= k <= HH_CLS_TOPK_MAX; k_eff = min(k, N).
+ * RULE for one row z[0..N), target t:
+ *   ORDER.  j comes before j' iff z_j > z_j', or z_j == z_j' and j < j' (ties go to the lower index, the project's rule; -0.0 == +0.0
+ *     is a tie).  It is decided on the logits as given, with comparisons only.  topk_idx[0..k_eff) = the first k_eff indices in this
+ *     order; entries k_eff..k-1 get index -1 and probability 0.
+ *   NON-FINITE ROW.  A row that holds a NaN or a +inf (-inf entries are ordinary), or that holds nothing but -inf (max z = -inf:
+ *     z - max is not a number), is a non-finite row: flag bit 1 (HH_CLS_NONFINITE); every topk_idx = -1, every topk_prob = 0,
+ *     rank = -1, row_loss = 0; it adds 1 to `nonfinite` and nothing else, whatever its target.
+ *   SOFTMAX.  m = max_j z_j; sum = sum_j (double)expf(z_j - m) in the per-row order of hh_softmax_xent: lane l of 64 adds its
+ *     elements j = l, l + 64, ... in ascending j into a double that starts at 0, then the 64 partial sums go through the shuffle tree
+ *     s_l += s_(l xor o) for o = 32, 16, 8, 4, 2, 1.  topk_prob_i = (float)((double)expf(z_i - m) / sum).
+ *   TARGET.  Without targets: rank = -1, row_loss = 0.  A t outside [0, N): flag bit 0 (HH_CLS_BAD_TARGET); the row adds 1 to
+ *     `bad_target` and otherwise only writes its top-k; rank = -1, row_loss = 0; no logit is read at its index.
+ *   RANK AND LOSS.  rank = #{j : z_j > z_t} + #{j < t : z_j == z_t};  row_loss = (float)(((double)m + log(sum)) - (double)z_t),
+ *     the double kept for the accumulator.  A top-1 hit is rank < 1, a top-k hit rank < k_eff.
+ * ACCUMULATOR (device; hh_cls_eval_bytes(N, with_confusion) bytes, 8-byte aligned, owned by the caller, set up by hh_cls_eval_reset).
+ *   It is passed as a plain pointer: the set of descriptor structs of ABI version 3 is closed, so its 64-byte header hh_cls_eval_acc is
+ *   defined in csrc/cls_score_math.h and stated here by offset (classification/evaluation.py ACC_HEADER is the same list):
+ *     int64 rows @0, top1 @8, topk @16, bad_target @24, nonfinite @32; double loss_sum @40; uint32 flags @48; int32 N @52,
+ *     with_confusion @56, reserved @60.
+ *   Behind the header: int32 per_class[3][N] = the scored rows, the top-1 hits and
+ *   the top-k hits by target class, then with confusion int32 conf[N][N], conf[t][topk_idx[0]] += 1 per scored row, then (8-byte
+ *   aligned) the call scratch: double [HH_CLS_MAX_B] and int32 [HH_CLS_MAX_B], all zero between calls.  A scored row (finite, target in
+ *   range) adds 1 to rows, its hits to top1 / topk, its row to per_class and conf.  The int32 tables limit one evaluation to 2^31 - 1
+ *   rows.  The accumulator is written only when both targets and acc are given; every per-row output pointer may be NULL.
+ *   ORDER OF loss_sum.  loss_sum grows by the scored rows' double losses one at a time, in ascending row order, so every byte of the
+ *     accumulator after an evaluation is independent of how its rows were split into calls (given the same device expf / log).
+ *   If the header's N is not the call's N (or with_confusion is not 0 / 1) the call sets flag bit 2 (HH_CLS_LAYOUT) and touches
+ *     nothing else of the accumulator.
+ * LAUNCHES.  hh_cls_score_batch is one launch without an accumulator and two with one: cls_score_kernel, one wave per row, four rows
+ *   per workgroup, which leaves each row's double loss and status in the scratch and adds to per_class / conf with vector atomics; then
+ *   cls_fold_kernel, one wave, which adds the scratch to the header in row order and zeroes it.  A row of N <= HH_CLS_ROW_REGS (1024)
+ *   is held in the wave's registers (16 per lane) across the passes; a longer one is read again from memory on every pass (max, sum,
+ *   rank, k_eff arg-max rounds), with the same results.
+ * hh_cls_score_host / hh_cls_eval_reset_host: the same text compiled for the host over HOST memory (accumulator included).
+ * Each returns 1 with hh_last_error set (hh_cls_eval_bytes: -1), before any launch, for a null logits pointer, B, N or k outside its
+ *   range, with_confusion not 0 / 1, an accumulator or targets pointer that is not 8-byte aligned, another that is not 4-byte aligned.  */
+#define HH_CLS_TOPK_MAX 8
+#define HH_CLS_MAX_B 1024
+#define HH_CLS_MAX_N 65536
+#define HH_CLS_ROW_REGS 1024
+enum { HH_CLS_BAD_TARGET = 1, HH_CLS_NONFINITE = 2, HH_CLS_LAYOUT = 4 };
+int64_t hh_cls_eval_bytes(int N, int with_confusion);
+int hh_cls_eval_reset(void *acc, int N, int with_confusion, void *stream);
+int hh_cls_eval_reset_host(void *acc, int N, int with_confusion);
+int hh_cls_score_batch(const float *logits, const int64_t *targets, int B, int N, int k, void *acc, int32_t *topk_idx, float *topk_prob,
+                       int32_t *rank, float *row_loss, void *stream);
+int hh_cls_score_host(const float *logits, const int64_t *targets, int B, int N, int k, void *acc, int32_t *topk_idx, float *topk_prob,
+                      int32_t *rank, float *row_loss);
+
 /* The end of the training step on the device (csrc/optim.hip): what torch.optim.Adam / AdamW / SGD and the GradScaler's non-finite
  * check do over ~900 parameter tensors, each as ONE launch over a device-resident table (the Python classes are
  * pytorch-human-pose_amd/optim.py; the reference picks its optimizer in utils/optim.py:40-45).  Parameters, gradients and state are

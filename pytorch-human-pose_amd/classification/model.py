@@ -118,5 +118,12 @@ class InferenceClassificationModel:
             out += self._records(chunk, logits, None if target_labels is None else target_labels[i:i + max_batch])
         return out
 
+    def infer_topk(self, raw_images: list, target_labels: list | None = None, k: int = 5, max_batch: int = 32) -> list:
+        """One light record (`evaluation.ClsTopK`) per image, in order: the k best classes, their probabilities and labels and, with a
+        target, its rank, picked on the device by hh_cls_score_batch behind each batch's forward: 2k + 1 numbers per image are copied
+        back instead of the N logits (and no softmax runs on the host).  Images as for `infer_images`."""
+        from .evaluation import infer_topk
+        return infer_topk(self, raw_images, target_labels, k, max_batch)
+
     def __call__(self, raw_image, target_label: int | str | None = None) -> InferenceClassificationResult:
         return self.infer_images([raw_image], [target_label])[0]

@@ -64,11 +64,15 @@ class ClassificationModule:
     ema_decay (not in the reference; None = off: the step as before, bit for bit, and no "ema" entry in state_dict()): a number keeps
     an exponential moving average of the weights, `self.ema = optim.ModelEMA(net, optimizer, ema_decay, ema_warmup, ema_use_buffers)`,
     updated inside the step launch of an optimizer of ..optim and by ema.update() after any other's.  validation_step runs on the
-    averaged weights (ema.applied()); state_dict() / load_state_dict() carry {"ema": ModelEMA.state_dict()}."""
+    averaged weights (ema.applied()); state_dict() / load_state_dict() carry {"ema": ModelEMA.state_dict()}.
+    evaluator (not in the reference; None = off, validation_step as before): an `evaluation.ClsEvaluator`; every validation_step also
+    adds its batch to it (one more launch pair, nothing read back), so an epoch's per-class accuracy and confusions are one
+    `evaluator.result()` away."""
 
     def __init__(self, model: ClassificationModel, loss_fn: ClassificationLoss, optimizer: torch.optim.Optimizer,
                  idx2label: dict | None = None, eval_dtype: str | None = None, max_grad_norm: float | None = None, grad_norm_type: float = 2.0,
-                 ema_decay: float | None = None, ema_warmup: bool = False, ema_use_buffers: bool = False):
+                 ema_decay: float | None = None, ema_warmup: bool = False, ema_use_buffers: bool = False, evaluator=None):
+        self.evaluator = evaluator
         self.model, self.loss_fn, self.optimizer, self.idx2label = model, loss_fn, optimizer, idx2label
         self.ema = None if ema_decay is None else ModelEMA(model.net, optimizer, ema_decay, ema_warmup, ema_use_buffers)
         self.max_grad_norm, self.grad_norm_type = max_grad_norm, grad_norm_type
@@ -118,6 +122,8 @@ class ClassificationModule:
             with torch.no_grad(), (self.ema.applied() if self.ema is not None else contextlib.nullcontext()):
                 logits = self.model.net(images)
                 self.loss_fn.calculate_loss(targets, logits)
+                if self.evaluator is not None:
+                    self.evaluator.update(logits, targets)
         finally:
             net.train(was_training)
         metrics = self.loss_fn.metrics()

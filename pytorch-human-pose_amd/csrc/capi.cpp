@@ -17,6 +17,7 @@
 #include "panel_math.h"
 #include "coco_eval_math.h"
 #include "pose_score_math.h"
+#include "cls_score_math.h"
 #include "crowd_mask_math.h"
 #include "track_math.h"
 #include "jpeg_math.h"
@@ -1272,6 +1273,50 @@ int hh_pose_score_host(int form, int metric, int B, int K, const float *joints, 
                                      p_off, p_xy, p_score, t_off, t_xyv, t_area, t_head, vars, alpha);
     if (pose_args_check(fn, t, t, vars, value, obj, kpt, match, status)) return 1;
     pose_score_host(t, value, obj, kpt, match, status);
+    return 0;
+}
+
+int64_t hh_cls_eval_bytes(int N, int with_confusion)
+{
+    if (const char *why = cls_check_shape(N, with_confusion)) { hh_set_error(std::string("hh_cls_eval_bytes: ") + why); return -1; }
+    return (int64_t)cls_acc_bytes(N, with_confusion);
+}
+
+static int cls_reset_check(const char *fn, const void *acc, int N, int with_confusion)
+{
+    if (!acc) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
+    if ((uintptr_t)acc % 8) { hh_set_error(std::string(fn) + ": acc is not 8-byte aligned"); return 1; }
+    if (const char *why = cls_check_shape(N, with_confusion)) { hh_set_error(std::string(fn) + ": " + why); return 1; }
+    return 0;
+}
+
+int hh_cls_eval_reset(void *acc, int N, int with_confusion, void *stream)
+{
+    if (cls_reset_check("hh_cls_eval_reset", acc, N, with_confusion)) return 1;
+    HH_CHECK_HIP(launch_cls_eval_reset(acc, N, with_confusion, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_cls_eval_reset_host(void *acc, int N, int with_confusion)
+{
+    if (cls_reset_check("hh_cls_eval_reset_host", acc, N, with_confusion)) return 1;
+    cls_reset_host(acc, N, with_confusion);
+    return 0;
+}
+
+int hh_cls_score_batch(const float *logits, const int64_t *targets, int B, int N, int k, void *acc, int32_t *topk_idx, float *topk_prob, int32_t *rank,
+                       float *row_loss, void *stream)
+{
+    if (const char *why = cls_check(logits, targets, B, N, k, acc, topk_idx, topk_prob, rank, row_loss)) { hh_set_error(std::string("hh_cls_score_batch: ") + why); return 1; }
+    HH_CHECK_HIP(launch_cls_score(logits, (const long long *)targets, B, N, k, acc, topk_idx, topk_prob, rank, row_loss, (hipStream_t)stream));
+    return 0;
+}
+
+int hh_cls_score_host(const float *logits, const int64_t *targets, int B, int N, int k, void *acc, int32_t *topk_idx, float *topk_prob, int32_t *rank,
+                      float *row_loss)
+{
+    if (const char *why = cls_check(logits, targets, B, N, k, acc, topk_idx, topk_prob, rank, row_loss)) { hh_set_error(std::string("hh_cls_score_host: ") + why); return 1; }
+    cls_score_host(logits, (const long long *)targets, B, N, k, acc, topk_idx, topk_prob, rank, row_loss);
     return 0;
 }
 

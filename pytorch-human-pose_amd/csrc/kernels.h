@@ -410,6 +410,13 @@ void track_step_host(const hh_track_params &p, void *state, const float *joints,
 struct PoseTables;
 hipError_t launch_pose_score(const PoseTables &t, int max_P, double *value, double *obj, double *kpt, int32_t *match, int32_t *status, hipStream_t s);
 void pose_score_host(const PoseTables &t, double *value, double *obj, double *kpt, int32_t *match, int32_t *status);
+// Evaluation of the classifier (hh_cls_score_batch of include/hhrnet.h; layout, order and the host's row in cls_score_math.h, kernels in
+// cls_score.hip): B <= HH_CLS_MAX_B rows in one launch, plus the one-wave fold when targets and an accumulator are given.
+hipError_t launch_cls_eval_reset(void *acc, int N, int with_confusion, hipStream_t s);
+hipError_t launch_cls_score(const float *logits, const long long *targets, int B, int N, int k, void *acc, int32_t *topk_idx, float *topk_prob,
+                            int32_t *rank, float *row_loss, hipStream_t s);
+void cls_score_host(const float *logits, const long long *targets, int B, int N, int k, void *acc, int32_t *topk_idx, float *topk_prob, int32_t *rank,
+                    float *row_loss);
 // Crowd masks from toggle lists (hh_crowd_mask_desc / hh_crowd_seg_desc of include/hhrnet.h; structs, predicate, tile walk and the host's
 // polygon walk in crowd_mask_math.h, kernel in crowd_mask.hip): n masks in one launch, `max_tiles` = the largest mask's tile count.
 hipError_t launch_crowd_masks(unsigned char *base, const hh_crowd_mask_desc *descs, const hh_crowd_seg_desc *segs, int n, int max_tiles, hipStream_t s);
