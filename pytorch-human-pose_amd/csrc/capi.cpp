@@ -26,6 +26,26 @@
 const char *hh_get_error();
 int hh_tap_read_impl(hh_net *n, int index, float *host);
 
+// The host checks of a drawing call (render, text, seg): n in 1..65535; `call_why`, the caller's refusal of the whole call; then per
+// frame a null table where rows are named (`no_table`) and frame(d) as "fn: frame b: why".  *max_tiles: the most th x tw tiles.
+template <class Frame>
+static int draw_check_frames(const char *fn, const hh_render_desc *descs_host, int n, const char *call_why, bool no_table, int th, int tw, int *max_tiles,
+                             Frame frame)
+{
+    if (n <= 0 || n > 65535) { hh_set_error(std::string(fn) + ": need 0 < n <= 65535"); return 1; }
+    if (call_why) { hh_set_error(std::string(fn) + ": " + call_why); return 1; }
+    int tiles = 1;
+    for (int b = 0; b < n; ++b) {
+        const hh_render_desc &d = descs_host[b];
+        if (d.prim_count > 0 && no_table) { hh_set_error(std::string(fn) + ": null primitive table"); return 1; }
+        const char *why = frame(d);
+        if (why) { hh_set_error(std::string(fn) + ": frame " + std::to_string(b) + ": " + why); return 1; }
+        tiles = std::max(tiles, ((d.h + th - 1) / th) * ((d.w + tw - 1) / tw));
+    }
+    if (max_tiles) *max_tiles = tiles;
+    return 0;
+}
+
 extern "C" {
 
 int hh_abi_version(void) { return HH_ABI_VERSION; }
@@ -315,19 +335,8 @@ int hh_render_config(int out[4])
 // The checks of a render call that need no device: every frame's descriptor and its primitives, on the caller's host copy.
 static int render_check(const char *fn, const hh_render_desc *descs_host, const hh_render_prim *prims_host, int num_prims, int n, int *max_tiles)
 {
-    if (n <= 0 || n > 65535) { hh_set_error(std::string(fn) + ": need 0 < n <= 65535"); return 1; }
-    if (num_prims < 0) { hh_set_error(std::string(fn) + ": negative table length"); return 1; }
-    int tiles = 1;
-    for (int b = 0; b < n; ++b) {
-        const RenderDesc &d = descs_host[b];
-        if (d.prim_count > 0 && !prims_host) { hh_set_error(std::string(fn) + ": null primitive table"); return 1; }
-        const char *why = render_check_frame(d, prims_host, num_prims, HH_RENDER_MAX_PRIMS);
-        if (why) { hh_set_error(std::string(fn) + ": frame " + std::to_string(b) + ": " + why); return 1; }
-        const int t = ((d.h + RENDER_TH - 1) / RENDER_TH) * ((d.w + RENDER_TW - 1) / RENDER_TW);
-        tiles = t > tiles ? t : tiles;
-    }
-    *max_tiles = tiles;
-    return 0;
+    return draw_check_frames(fn, descs_host, n, num_prims < 0 ? "negative table length" : nullptr, !prims_host, RENDER_TH, RENDER_TW, max_tiles,
+                             [&](const RenderDesc &d) { return render_check_frame(d, prims_host, num_prims, HH_RENDER_MAX_PRIMS); });
 }
 
 int hh_render_poses_u8_batch(unsigned char *batch_base, const hh_render_desc *descs_dev, const hh_render_desc *descs_host,
@@ -365,15 +374,8 @@ int hh_text_config(int out[4])
 // The checks of a text call that need no device: every frame's descriptor and its primitives, on the caller's host copy.
 static int text_check(const char *fn, const hh_text_desc *descs_host, const hh_text_prim *prims_host, int num_prims, int n, long long atlas_len)
 {
-    if (n <= 0 || n > 65535) { hh_set_error(std::string(fn) + ": need 0 < n <= 65535"); return 1; }
-    if (num_prims < 0 || atlas_len < 0) { hh_set_error(std::string(fn) + ": negative table or atlas length"); return 1; }
-    for (int b = 0; b < n; ++b) {
-        const TextDesc &d = descs_host[b];
-        if (d.prim_count > 0 && !prims_host) { hh_set_error(std::string(fn) + ": null primitive table"); return 1; }
-        const char *why = text_check_frame(d, prims_host, num_prims, atlas_len);
-        if (why) { hh_set_error(std::string(fn) + ": frame " + std::to_string(b) + ": " + why); return 1; }
-    }
-    return 0;
+    return draw_check_frames(fn, descs_host, n, num_prims < 0 || atlas_len < 0 ? "negative table or atlas length" : nullptr, !prims_host, TEXT_TH, TEXT_TW,
+                             nullptr, [&](const TextDesc &d) { return text_check_frame(d, prims_host, num_prims, atlas_len); });
 }
 
 int hh_text_tiles(const hh_text_desc *descs_host, const hh_text_prim *prims_host, int num_prims, int n, long long atlas_len, int32_t *tiles_host,
@@ -473,18 +475,11 @@ int hh_seg_overlay_config(int out[4])
 static int seg_check(const char *fn, const hh_seg_desc *descs_host, const int32_t *shapes_host, int num_shapes, const unsigned int *toggles_host,
                      long long num_toggles, int n, int *max_tiles)
 {
-    if (n <= 0 || n > 65535) { hh_set_error(std::string(fn) + ": need 0 < n <= 65535"); return 1; }
-    if (num_shapes < 0 || num_toggles < 0) { hh_set_error(std::string(fn) + ": negative table length"); return 1; }
-    if (!descs_host || (num_shapes > 0 && !shapes_host) || (num_toggles > 0 && !toggles_host)) { hh_set_error(std::string(fn) + ": null pointer"); return 1; }
-    int tiles = 1;
-    for (int b = 0; b < n; ++b) {
-        const SegDesc &d = descs_host[b];
-        const char *why = seg_check_frame(d, reinterpret_cast<const SegShape *>(shapes_host), num_shapes, toggles_host, num_toggles);
-        if (why) { hh_set_error(std::string(fn) + ": frame " + std::to_string(b) + ": " + why); return 1; }
-        tiles = std::max(tiles, ((d.h + SEG_TH - 1) / SEG_TH) * ((d.w + SEG_TW - 1) / SEG_TW));
-    }
-    *max_tiles = tiles;
-    return 0;
+    const bool null = !descs_host || (num_shapes > 0 && !shapes_host) || (num_toggles > 0 && !toggles_host);
+    const char *call_why = num_shapes < 0 || num_toggles < 0 ? "negative table length" : null ? "null pointer" : nullptr;
+    return draw_check_frames(fn, descs_host, n, call_why, false, SEG_TH, SEG_TW, max_tiles, [&](const SegDesc &d) {
+        return seg_check_frame(d, reinterpret_cast<const SegShape *>(shapes_host), num_shapes, toggles_host, num_toggles);
+    });
 }
 
 int hh_seg_overlay_u8_batch(unsigned char *batch_base, const hh_seg_desc *descs_dev, const hh_seg_desc *descs_host, const int32_t *shapes_dev,

@@ -11,15 +11,7 @@
 #include <string.h>
 
 #include "../../include/hhrnet.h"
-
-#if defined(__HIPCC__)
-#define HH_CHD __host__ __device__ __forceinline__
-#else
-#define HH_CHD inline
-#endif
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
+#include "host_dev.h"
 
 // The accumulator's header (include/hhrnet.h states it by offset: it is not one of the ABI's descriptor structs).
 struct hh_cls_eval_acc {
@@ -41,15 +33,15 @@ static_assert(sizeof(hh_cls_eval_acc) == 64, "the tables behind the header start
 enum { CLS_ST_SCORED = 1, CLS_ST_TOP1 = 2, CLS_ST_TOPK = 4, CLS_ST_BAD_TARGET = 8, CLS_ST_NONFINITE = 16 };
 
 // The blocks behind the header, as byte offsets from the accumulator's start (N and with_confusion checked by the caller).
-HH_CHD size_t cls_off_per_class() { return sizeof(hh_cls_eval_acc); }
-HH_CHD size_t cls_off_conf(int N) { return cls_off_per_class() + (size_t)3 * N * sizeof(int32_t); }
-HH_CHD size_t cls_off_loss(int N, int with_confusion)
+HH_HD size_t cls_off_per_class() { return sizeof(hh_cls_eval_acc); }
+HH_HD size_t cls_off_conf(int N) { return cls_off_per_class() + (size_t)3 * N * sizeof(int32_t); }
+HH_HD size_t cls_off_loss(int N, int with_confusion)
 {
     const size_t end = cls_off_conf(N) + (with_confusion ? (size_t)N * N * sizeof(int32_t) : 0);
     return (end + 7) & ~(size_t)7;
 }
-HH_CHD size_t cls_off_status(int N, int with_confusion) { return cls_off_loss(N, with_confusion) + (size_t)HH_CLS_MAX_B * sizeof(double); }
-HH_CHD size_t cls_acc_bytes(int N, int with_confusion) { return cls_off_status(N, with_confusion) + (size_t)HH_CLS_MAX_B * sizeof(int32_t); }
+HH_HD size_t cls_off_status(int N, int with_confusion) { return cls_off_loss(N, with_confusion) + (size_t)HH_CLS_MAX_B * sizeof(double); }
+HH_HD size_t cls_acc_bytes(int N, int with_confusion) { return cls_off_status(N, with_confusion) + (size_t)HH_CLS_MAX_B * sizeof(int32_t); }
 
 // the accumulator's blocks as pointers; ok = the header describes the layout the call assumes
 struct ClsAcc {
@@ -58,7 +50,7 @@ struct ClsAcc {
     double *loss;
     bool ok;
 };
-HH_CHD ClsAcc cls_acc_view(void *acc, int N)
+HH_HD ClsAcc cls_acc_view(void *acc, int N)
 {
     ClsAcc a;
     unsigned char *p = static_cast<unsigned char *>(acc);
@@ -73,10 +65,10 @@ HH_CHD ClsAcc cls_acc_view(void *acc, int N)
 }
 
 // j before j' in the order of the rule
-HH_CHD bool cls_before(float za, int ja, float zb, int jb) { return za > zb || (za == zb && ja < jb); }
+HH_HD bool cls_before(float za, int ja, float zb, int jb) { return za > zb || (za == zb && ja < jb); }
 // NaN or +inf
-HH_CHD bool cls_bad_value(float v) { return !(v < INFINITY); }
-HH_CHD float cls_neg_inf() { return -INFINITY; }
+HH_HD bool cls_bad_value(float v) { return !(v < INFINITY); }
+HH_HD float cls_neg_inf() { return -INFINITY; }
 
 inline const char *cls_check_shape(int N, int with_confusion)
 {

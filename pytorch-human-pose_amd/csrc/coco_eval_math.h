@@ -11,15 +11,7 @@
 #include <stdint.h>
 
 #include "../../include/hhrnet.h"
-
-#if defined(__HIPCC__)
-#define HH_CHD __host__ __device__ __forceinline__
-#else
-#define HH_CHD inline
-#endif
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
+#include "host_dev.h"
 
 // The limits are HH_COCO_* of include/hhrnet.h.  One workgroup owns one image: its D x G OKS values live in LDS (32 KB of fp64 at the limits),
 // one lane walks one (area range, threshold) with the "ground truth taken" set as two 64-bit words, so A * T <= 64 = one wave.
@@ -30,10 +22,10 @@ using CocoTables = hh_coco_tables;
 static_assert(sizeof(hh_coco_tables) == 136, "ABI 3");
 
 // np.max((0, a)) of one element: NaN stays NaN.
-HH_CHD double coco_pos(double a) { return a <= 0.0 ? 0.0 : a; }
+HH_HD double coco_pos(double a) { return a <= 0.0 ? 0.0 : a; }
 
 // computeOks for one pair, in the operation order of COCOKeypointsEval._oks.  xy: the detection's K x 2; xyv: the ground truth's K x 3.
-HH_CHD double coco_oks_pair(const double *xy, const double *xyv, const double *bbox, double area, const double *vars, int K)
+HH_HD double coco_oks_pair(const double *xy, const double *xyv, const double *bbox, double area, const double *vars, int K)
 {
     int k1 = 0;
     for (int k = 0; k < K; ++k) k1 += xyv[3 * k + 2] > 0.0 ? 1 : 0;
@@ -60,8 +52,8 @@ HH_CHD double coco_oks_pair(const double *xy, const double *xyv, const double *b
 
 // The ground truths of one image for one area range as two bit sets over the packed (original) order: ignored, and crowd.
 struct CocoGtSets { uint64_t ign[2], crowd[2]; };
-HH_CHD bool coco_gt_ignored(double area, int flags, double lo, double hi) { return (flags & HH_COCO_GT_IGNORE) || area < lo || area > hi; }
-HH_CHD CocoGtSets coco_gt_sets(const double *gt_area, const uint8_t *gt_flags, int G, double lo, double hi)
+HH_HD bool coco_gt_ignored(double area, int flags, double lo, double hi) { return (flags & HH_COCO_GT_IGNORE) || area < lo || area > hi; }
+HH_HD CocoGtSets coco_gt_sets(const double *gt_area, const uint8_t *gt_flags, int G, double lo, double hi)
 {
     CocoGtSets s;
     s.ign[0] = s.ign[1] = s.crowd[0] = s.crowd[1] = 0;
@@ -77,7 +69,7 @@ HH_CHD CocoGtSets coco_gt_sets(const double *gt_area, const uint8_t *gt_flags, i
     return s;
 }
 // gt_ignore of the image's G ground truths for one area, in packed order: writes out[0 .. G - 1].
-HH_CHD void coco_store_gt_ignore(const CocoGtSets &s, int G, uint8_t *out)
+HH_HD void coco_store_gt_ignore(const CocoGtSets &s, int G, uint8_t *out)
 {
 #if defined(__clang__)
 #pragma unroll
@@ -91,7 +83,7 @@ HH_CHD void coco_store_gt_ignore(const CocoGtSets &s, int G, uint8_t *out)
 // (ignored), each in packed order, so the permutation is never materialised.  dt_match[d] = gt_base + g + 1 of the matched ground truth
 // (its row in the packed table + 1) or 0; dt_ignore[d] = the matched ground truth's flag, or "the detection's area is outside the range"
 // when unmatched.  Writes exactly dt_match[0 .. D - 1] and dt_ignore[0 .. D - 1]; reads oks[0 .. D * G - 1], dt_area[0 .. D - 1].
-HH_CHD void coco_match_walk(const double *oks, int D, int G, const CocoGtSets &s, double t, const double *dt_area, double lo, double hi, int gt_base,
+HH_HD void coco_match_walk(const double *oks, int D, int G, const CocoGtSets &s, double t, const double *dt_area, double lo, double hi, int gt_base,
                             int32_t *dt_match, uint8_t *dt_ignore)
 {
     const double start = t < 1 - 1e-10 ? t : 1 - 1e-10;  // min([t, 1 - 1e-10])

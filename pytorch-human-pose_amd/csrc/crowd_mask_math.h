@@ -13,15 +13,7 @@
 #include <vector>
 
 #include "../../include/hhrnet.h"
-
-#if defined(__HIPCC__)
-#define HH_CHD __host__ __device__ __forceinline__
-#else
-#define HH_CHD inline
-#endif
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
+#include "host_dev.h"
 
 // The launch geometry, reported by hh_crowd_mask_config: a workgroup of CROWD_THREADS threads owns a tile of CROWD_TW columns x
 // CROWD_TH rows; in the first phase a lane owns one column of the tile and forms its CROWD_TH coverage bits in one uint32 (row r of
@@ -35,7 +27,7 @@ using CrowdSegDesc = hh_crowd_seg_desc;
 static_assert(sizeof(hh_crowd_mask_desc) == 24 && sizeof(hh_crowd_seg_desc) == 24, "ABI 3");
 
 // The number of toggles <= idx (an upper-bound search): pixel idx is covered by the segment iff it is odd.
-HH_CHD uint32_t crowd_upper_bound(const uint32_t *t, uint32_t n, uint32_t idx)
+HH_HD uint32_t crowd_upper_bound(const uint32_t *t, uint32_t n, uint32_t idx)
 {
     uint32_t lo = 0, hi = n;
     while (lo < hi) {
@@ -44,11 +36,11 @@ HH_CHD uint32_t crowd_upper_bound(const uint32_t *t, uint32_t n, uint32_t idx)
     }
     return lo;
 }
-HH_CHD bool crowd_covered(const uint32_t *t, uint32_t n, uint32_t idx) { return crowd_upper_bound(t, n, idx) & 1; }
+HH_HD bool crowd_covered(const uint32_t *t, uint32_t n, uint32_t idx) { return crowd_upper_bound(t, n, idx) & 1; }
 
 // Coverage of the pixels idx0 .. idx0 + rows - 1 (1 <= rows <= 32, all in one image column) as bits 0 .. rows - 1: one search for the
 // top pixel, then a cursor down the sorted list; a toggle at idx0 + r flips every bit from r on.  Bits from `rows` on are unspecified.
-HH_CHD uint32_t crowd_column_bits(const uint32_t *t, uint32_t n, uint32_t idx0, int rows)
+HH_HD uint32_t crowd_column_bits(const uint32_t *t, uint32_t n, uint32_t idx0, int rows)
 {
     uint32_t c = crowd_upper_bound(t, n, idx0);
     uint32_t bits = (c & 1) ? ~0u : 0u;
@@ -61,7 +53,7 @@ HH_CHD uint32_t crowd_column_bits(const uint32_t *t, uint32_t n, uint32_t idx0, 
 }
 
 // Column x of one mask, rows ty0 .. ty0 + rows - 1: the union over the mask's segments, each culled by its column range.
-HH_CHD uint32_t crowd_lane_bits(const unsigned char *base, const CrowdSegDesc *segs, const CrowdMaskDesc &d, int x, int ty0, int rows)
+HH_HD uint32_t crowd_lane_bits(const unsigned char *base, const CrowdSegDesc *segs, const CrowdMaskDesc &d, int x, int ty0, int rows)
 {
     uint32_t bits = 0;
     for (int s = d.seg_first; s < d.seg_first + d.seg_count; ++s) {

@@ -11,13 +11,8 @@
 #include <string.h>
 #include <vector>  // (the host twin of the index, jpeg_idx_sync_host)
 
-#if defined(__HIPCC__)
-#define HH_JDHD __host__ __device__ __forceinline__
-#else
-#define HH_JDHD inline
-#endif
-
 #include "../../include/hhrnet.h"
+#include "host_dev.h"
 
 // The tables of the decode are the public structs.  hh_jpeg_dec_desc.tables_offset leads to JpegStreamInfo | JpegDecTables | nseg
 // JpegSegment at a multiple of 16; a hh_jpeg_win_desc is a hh_jpeg_dec_desc, whose stream is the shipped slice, and the window.
@@ -45,7 +40,7 @@ struct JpegDecTables {
 };
 static_assert(sizeof(JpegDecTables) == 7808 && sizeof(JpegDecTables) % 16 == 0, "table layout");
 enum { JPEG_DEC_TABLES_AT = sizeof(JpegStreamInfo), JPEG_DEC_SEGS_AT = sizeof(JpegStreamInfo) + sizeof(JpegDecTables) };
-HH_JDHD long long jpeg_dec_tables_bytes(long long nseg) { return JPEG_DEC_SEGS_AT + nseg * (long long)sizeof(JpegSegment); }
+HH_HD long long jpeg_dec_tables_bytes(long long nseg) { return JPEG_DEC_SEGS_AT + nseg * (long long)sizeof(JpegSegment); }
 
 // status_dev codes
 enum { JPEG_ST_OK = 0, JPEG_ST_BAD_CODE = 1, JPEG_ST_RUN = 2, JPEG_ST_EXHAUSTED = 3, JPEG_ST_RESTART = 4, JPEG_ST_SEGMENT = 5 };
@@ -64,7 +59,7 @@ struct JpegWinRect {
     int mx0, mx1, my0, my1;  // inclusive
     int cols, rows;
 };
-HH_JDHD JpegWinRect jpeg_win_rect(const JpegStreamInfo &I, const JpegWindow &W)
+HH_HD JpegWinRect jpeg_win_rect(const JpegStreamInfo &I, const JpegWindow &W)
 {
     const int t = W.top, b = W.top + W.height - 1, l = W.left, r = W.left + W.width - 1;
     JpegWinRect R;
@@ -81,8 +76,8 @@ HH_JDHD JpegWinRect jpeg_win_rect(const JpegStreamInfo &I, const JpegWindow &W)
     return R;
 }
 // The whole image as a window, and its rectangle: the MCU grid (mx1 = (w - 1) / (8 hs) = mcols - 1, and likewise down).
-HH_JDHD JpegWindow jpeg_full_window(const JpegStreamInfo &I) { return JpegWindow{0, 0, I.h, I.w}; }
-HH_JDHD JpegWinRect jpeg_full_rect(const JpegStreamInfo &I) { return jpeg_win_rect(I, jpeg_full_window(I)); }
+HH_HD JpegWindow jpeg_full_window(const JpegStreamInfo &I) { return JpegWindow{0, 0, I.h, I.w}; }
+HH_HD JpegWinRect jpeg_full_rect(const JpegStreamInfo &I) { return jpeg_win_rect(I, jpeg_full_window(I)); }
 
 // The workspace of a rectangle's decode: its coefficients, then its component planes (cw / ch stay the image's).
 struct JpegDecGeom {
@@ -93,7 +88,7 @@ struct JpegDecGeom {
     long long plane_at[3];     // from the image's workspace
     long long ws_bytes;        // a multiple of 16
 };
-HH_JDHD JpegDecGeom jpeg_dec_geom(const JpegStreamInfo &I, const JpegWinRect &R)
+HH_HD JpegDecGeom jpeg_dec_geom(const JpegStreamInfo &I, const JpegWinRect &R)
 {
     JpegDecGeom g;
     g.nmcu = R.cols * R.rows;
@@ -123,11 +118,11 @@ struct JpegBits {
     uint64_t acc;  // the low n bits are unread
     int n, fake;
     bool stop;
-    HH_JDHD void init(const unsigned char *bytes, int at, int limit)
+    HH_HD void init(const unsigned char *bytes, int at, int limit)
     {
         p = bytes, pos = at, end = limit, acc = 0, n = 0, fake = 0, stop = false;
     }
-    HH_JDHD void refill()
+    HH_HD void refill()
     {
         // four bytes at once while they lie inside the segment and none of them is FF (no stuffing, no marker) ...
         while (n <= 32 && !stop && pos + 4 <= end) {
@@ -158,16 +153,16 @@ struct JpegBits {
             n += 8;
         }
     }
-    HH_JDHD uint32_t peek(int k) const { return (uint32_t)(acc >> (n - k)) & ((1u << k) - 1u); }  // 1 <= k <= 16 <= n
-    HH_JDHD void drop(int k) { n -= k; }
-    HH_JDHD bool starved() const { return n < fake; }  // bits that are not there were consumed
-    HH_JDHD int real() const { return n - fake; }      // unread bits of the stream in the buffer
+    HH_HD uint32_t peek(int k) const { return (uint32_t)(acc >> (n - k)) & ((1u << k) - 1u); }  // 1 <= k <= 16 <= n
+    HH_HD void drop(int k) { n -= k; }
+    HH_HD bool starved() const { return n < fake; }  // bits that are not there were consumed
+    HH_HD int real() const { return n - fake; }      // unread bits of the stream in the buffer
 };
 
 // The canonical position of a reader that is not starved: the byte that holds the next unread bit and that bit's index in it, found by
 // going back from the reader's position over the unread bits.  An FF 00 pair is one byte and the position points at its FF.  `floor`:
 // where the reader began (no byte before it is looked at).
-HH_JDHD void jpeg_bits_where(const JpegBits &br, int floor, int &p, int &bit)
+HH_HD void jpeg_bits_where(const JpegBits &br, int floor, int &p, int &bit)
 {
     int unread = br.real();
     p = br.pos;
@@ -184,7 +179,7 @@ HH_JDHD void jpeg_bits_where(const JpegBits &br, int floor, int &p, int &bit)
 }
 
 // -> the symbol, or -1 for a code no table entry has.  Needs 16 bits in the buffer.
-HH_JDHD int jpeg_dec_symbol(JpegBits &br, const JpegHuff &H)
+HH_HD int jpeg_dec_symbol(JpegBits &br, const JpegHuff &H)
 {
     const uint32_t e = H.look[br.peek(8)];
     if (e) {
@@ -201,11 +196,11 @@ HH_JDHD int jpeg_dec_symbol(JpegBits &br, const JpegHuff &H)
     }
     return -1;
 }
-HH_JDHD int jpeg_dec_extend(uint32_t v, int s) { return (int)v < (1 << (s - 1)) ? (int)v - (1 << s) + 1 : (int)v; }
+HH_HD int jpeg_dec_extend(uint32_t v, int s) { return (int)v < (1 << (s - 1)) ? (int)v - (1 << s) + 1 : (int)v; }
 
 // One block.  STORE: blk receives the 64 coefficients (natural order; zero first).  pred: the component's DC predictor.
 template <bool STORE>
-HH_JDHD int jpeg_dec_block(JpegBits &br, const JpegHuff &dc, const JpegHuff &ac, int &pred, int16_t *blk)
+HH_HD int jpeg_dec_block(JpegBits &br, const JpegHuff &dc, const JpegHuff &ac, int &pred, int16_t *blk)
 {
     if (STORE) {
         struct alignas(16) Z { int16_t v[8]; };
@@ -253,12 +248,12 @@ struct JpegExtent {
     long long max_byte, max_coef;  // one past the last stream byte read, one past the last coefficient written
 };
 // The component of block j of an MCU.
-HH_JDHD int jpeg_dec_block_comp(const JpegStreamInfo &I, int j) { return j < I.hs * I.vs ? 0 : j - I.hs * I.vs + 1; }
+HH_HD int jpeg_dec_block_comp(const JpegStreamInfo &I, int j) { return j < I.hs * I.vs ? 0 : j - I.hs * I.vs + 1; }
 
 // The last MCU of [first, first + count) that lies inside the rectangle, or -1: where a lane's walk ends, and whether it has one.
 // With the whole grid as the rectangle no clause applies (ly <= mrows - 1 = my1, lx >= 0 = mx0, ly >= 0 = my0, lx <= mcols - 1 = mx1):
 // the result is the segment's last MCU.
-HH_JDHD int jpeg_win_last(const JpegStreamInfo &I, const JpegWinRect &R, int first, int count)
+HH_HD int jpeg_win_last(const JpegStreamInfo &I, const JpegWinRect &R, int first, int count)
 {
     const int last = first + count - 1;
     int ly = last / I.mcols, lx = last % I.mcols;
@@ -276,7 +271,7 @@ HH_JDHD int jpeg_win_last(const JpegStreamInfo &I, const JpegWinRect &R, int fir
 // With the whole grid as the rectangle (jpeg_full_rect) `stop` is the segment's last MCU (see jpeg_win_last) and `inside` is always
 // true, since 0 <= mx < mcols and 0 <= my < mrows for every MCU of the grid: every MCU is stored at (first_mcu + m) * bpm, the walk
 // always reaches the segment's end, and ext->max_coef is one past the last MCU begun.
-HH_JDHD int jpeg_dec_segment(const unsigned char *stream, int length, const JpegStreamInfo &I, const JpegHuff *huff, const JpegSegment &sg,
+HH_HD int jpeg_dec_segment(const unsigned char *stream, int length, const JpegStreamInfo &I, const JpegHuff *huff, const JpegSegment &sg,
                              const JpegWinRect &R, int16_t *coefs, JpegWinCounts *counts, JpegExtent *ext)
 {
     const int nmcu = I.mcols * I.mrows;
@@ -326,7 +321,7 @@ HH_JDHD int jpeg_dec_segment(const unsigned char *stream, int length, const Jpeg
 // libjpeg's jidctint ("islow"): CONST_BITS 13, PASS1_BITS 2.  v[8] holds a column of dequantised coefficients (pass 1: descale by 11)
 // or a row of pass-1 results (pass 2: descale by 18); the results replace them.
 template <int SHIFT>
-HH_JDHD void jpeg_idct_1d(int32_t v[8])
+HH_HD void jpeg_idct_1d(int32_t v[8])
 {
     // (modular uint32 arithmetic: what a stream within the rule gives fits int32 and is the same; a malformed one wraps instead of
     // overflowing a signed type)
@@ -354,12 +349,12 @@ HH_JDHD void jpeg_idct_1d(int32_t v[8])
     v[3] = (int32_t)(tmp13 + tmp0 + half) >> SHIFT, v[4] = (int32_t)(tmp13 - tmp0 + half) >> SHIFT;
 }
 // The sample of a pass-2 result.
-HH_JDHD int jpeg_idct_sample(int32_t x)
+HH_HD int jpeg_idct_sample(int32_t x)
 {
     return x < -128 ? 0 : x > 127 ? 255 : x + 128;
 }
 // Column u of a block: dequantise (int16 coefficient x divisor, natural order) and pass 1, into ws (row stride 8).
-HH_JDHD void jpeg_idct_col(const int16_t *coef, const uint16_t *q, int u, int32_t *ws)
+HH_HD void jpeg_idct_col(const int16_t *coef, const uint16_t *q, int u, int32_t *ws)
 {
     int32_t v[8];
 #pragma unroll
@@ -371,7 +366,7 @@ HH_JDHD void jpeg_idct_col(const int16_t *coef, const uint16_t *q, int u, int32_
 struct alignas(8) JpegRow8 {
     unsigned char v[8];
 };
-HH_JDHD JpegRow8 jpeg_idct_row(const int32_t *ws_row)
+HH_HD JpegRow8 jpeg_idct_row(const int32_t *ws_row)
 {
     int32_t v[8];
 #pragma unroll
@@ -383,7 +378,7 @@ HH_JDHD JpegRow8 jpeg_idct_row(const int32_t *ws_row)
     return r;
 }
 // Where block `blk` of the rectangle lies: its component, and its first sample in that component's plane (g = jpeg_dec_geom(I, R)).
-HH_JDHD void jpeg_dec_block_place(const JpegStreamInfo &I, const JpegWinRect &R, const JpegDecGeom &g, int blk, int &c, long long &at)
+HH_HD void jpeg_dec_block_place(const JpegStreamInfo &I, const JpegWinRect &R, const JpegDecGeom &g, int blk, int &c, long long &at)
 {
     const int mcu = blk / I.bpm, j = blk % I.bpm;
     const int ry = mcu / R.cols, rx = mcu % R.cols;
@@ -397,7 +392,7 @@ HH_JDHD void jpeg_dec_block_place(const JpegStreamInfo &I, const JpegWinRect &R,
 // The chroma sample of output pixel (y, x) of the image (libjpeg's fancy filters; plain replication when cw <= 2) from a plane that
 // starts at row oy, column ox of the component (0, 0: the whole component): the taps and the edges go by the component's true size
 // cw x ch, only the addresses are relative to (oy, ox).
-HH_JDHD int jpeg_dec_chroma(const unsigned char *plane, int pitch, int oy, int ox, int cw, int ch, int hs, int vs, int y, int x)
+HH_HD int jpeg_dec_chroma(const unsigned char *plane, int pitch, int oy, int ox, int cw, int ch, int hs, int vs, int y, int x)
 {
     if (hs == 1) return plane[(size_t)(y - oy) * pitch + (x - ox)];
     const int c = x >> 1;
@@ -420,9 +415,9 @@ HH_JDHD int jpeg_dec_chroma(const unsigned char *plane, int pitch, int oy, int o
     const int cp = (c == 0 ? c : c - 1) - ox;
     return (3 * s + 3 * near_row[cp] + far_row[cp] + 8) >> 4;
 }
-HH_JDHD int jpeg_dec_clamp(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+HH_HD int jpeg_dec_clamp(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
 // Pixel (y, x) of the IMAGE from the rectangle's planes -> dst[0..2].
-HH_JDHD void jpeg_dec_pixel(const unsigned char *ws, const JpegStreamInfo &I, const JpegWinRect &R, const JpegDecGeom &g, int y, int x, bool bgr,
+HH_HD void jpeg_dec_pixel(const unsigned char *ws, const JpegStreamInfo &I, const JpegWinRect &R, const JpegDecGeom &g, int y, int x, bool bgr,
                             unsigned char *dst)
 {
     const int Y = ws[g.plane_at[0] + (size_t)(y - R.my0 * I.vs * 8) * g.pw[0] + (x - R.mx0 * I.hs * 8)];
@@ -824,7 +819,7 @@ enum { JPEG_IDX_LANES = 1024, JPEG_IDX_SUBSEQ = 32, JPEG_IDX_SUBSEQ_MIN = 4, JPE
 enum { JPEG_IDX_PENDING = 1 };  // info.reserved[1] of a table block whose entries the device is to fill (hh_jpeg_index_tables)
 typedef unsigned long long JpegIdxKey;
 static constexpr JpegIdxKey JPEG_IDX_NONE = ~0ull;  // no state: the walk met an error or ran out of blocks
-HH_JDHD JpegIdxKey jpeg_idx_key(int p, int bit, int j) { return (JpegIdxKey)(uint32_t)p << 6 | (JpegIdxKey)(uint32_t)bit << 3 | (JpegIdxKey)(uint32_t)j; }
+HH_HD JpegIdxKey jpeg_idx_key(int p, int bit, int j) { return (JpegIdxKey)(uint32_t)p << 6 | (JpegIdxKey)(uint32_t)bit << 3 | (JpegIdxKey)(uint32_t)j; }
 
 struct JpegIdxLane {
     JpegIdxKey exit;  // the first boundary at or past `limit`, or JPEG_IDX_NONE
@@ -834,22 +829,22 @@ struct JpegIdxLane {
 };
 
 // The scan's bytes as the index walks them, and how many subsequences of B bytes they make (at least one: lane 0 always walks).
-HH_JDHD int jpeg_idx_scan_end(const JpegStreamInfo &I, long long length) { return (int)(I.scan_end < length ? I.scan_end : length); }
-HH_JDHD long long jpeg_idx_subsequences(const JpegStreamInfo &I, long long length, int B)
+HH_HD int jpeg_idx_scan_end(const JpegStreamInfo &I, long long length) { return (int)(I.scan_end < length ? I.scan_end : length); }
+HH_HD long long jpeg_idx_subsequences(const JpegStreamInfo &I, long long length, int B)
 {
     const long long bytes = (long long)jpeg_idx_scan_end(I, length) - I.scan_offset;
     return bytes > 0 ? (bytes + B - 1) / B : 1;
 }
 // Where lane k >= 1 begins before it knows better: the first data bit of its subsequence (a 00 behind an FF belongs to that FF), at a
 // block boundary, block 0 of an MCU.  S + k B < E, and S + k B - 1 >= S: both bytes lie in the scan.
-HH_JDHD JpegIdxKey jpeg_idx_guess(const unsigned char *b, const JpegStreamInfo &I, long long k, int B)
+HH_HD JpegIdxKey jpeg_idx_guess(const unsigned char *b, const JpegStreamInfo &I, long long k, int B)
 {
     int p = (int)(I.scan_offset + k * B);
     if (b[p] == 0 && b[p - 1] == 0xff) p += 1;
     return jpeg_idx_key(p, 0, 0);
 }
 // One past the last byte of subsequence k: the start of the next one, or no limit for the last.
-HH_JDHD int jpeg_idx_limit(const JpegStreamInfo &I, long long nsub, long long k, int B) { return k + 1 < nsub ? (int)(I.scan_offset + (k + 1) * B) : INT32_MAX; }
+HH_HD int jpeg_idx_limit(const JpegStreamInfo &I, long long nsub, long long k, int B) { return k + 1 < nsub ? (int)(I.scan_offset + (k + 1) * B) : INT32_MAX; }
 
 // One lane: whole blocks from the state `from` up to the first boundary whose canonical byte is at or past `limit`, but no further
 // than block `total` of the image, the walk's first block being block g0 (a speculative lane does not know its g0: 0, which makes

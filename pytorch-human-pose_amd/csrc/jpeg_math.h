@@ -8,13 +8,8 @@
 #include <stdint.h>
 #include <string.h>
 
-#if defined(__HIPCC__)
-#define HH_JHD __host__ __device__ __forceinline__
-#else
-#define HH_JHD inline
-#endif
-
 #include "../../include/hhrnet.h"
+#include "host_dev.h"
 
 using JpegDesc = hh_jpeg_desc;
 static_assert(sizeof(hh_jpeg_desc) == 64, "ABI 3");
@@ -42,8 +37,8 @@ struct JpegGeom {
     long long ws_bytes;    // coefficients | slots | int32 interval lengths, a multiple of 16
 };
 // the worst-case bytes of one interval of nblk blocks: every bit used, padded to a byte, every byte stuffed
-HH_JHD long long jpeg_interval_bound(long long nblk) { return 2 * ((nblk * JPEG_BLOCK_BITS + 7) / 8); }
-HH_JHD JpegGeom jpeg_geom(int h, int w, int subsampling)
+HH_HD long long jpeg_interval_bound(long long nblk) { return 2 * ((nblk * JPEG_BLOCK_BITS + 7) / 8); }
+HH_HD JpegGeom jpeg_geom(int h, int w, int subsampling)
 {
     JpegGeom g;
     g.mcu = subsampling == 420 ? 16 : 8;
@@ -57,7 +52,7 @@ HH_JHD JpegGeom jpeg_geom(int h, int w, int subsampling)
     return g;
 }
 // the worst-case bytes of the stream: header, every interval at its bound followed by a marker (RSTm, or EOI after the last)
-HH_JHD long long jpeg_bound(const JpegGeom &g) { return JPEG_HEADER_BYTES + g.mrows * (jpeg_interval_bound(g.nblk) + 2); }
+HH_HD long long jpeg_bound(const JpegGeom &g) { return JPEG_HEADER_BYTES + g.mrows * (jpeg_interval_bound(g.nblk) + 2); }
 
 // T[u][x] = round(2^14 c(u) cos((2x + 1) u pi / 16)), c(0) = sqrt(1/8), c(u) = 1/2
 static constexpr int16_t JPEG_T[64] = {
@@ -104,7 +99,7 @@ static constexpr uint8_t JPEG_AC_VALS[2][162] = {
      246, 247, 248, 249, 250}};
 
 // Q of zigzag position k in table `tbl` (0 luminance, 1 chrominance) at `quality` 1..100: libjpeg's jpeg_quality_scaling
-HH_JHD int jpeg_quant(int quality, int tbl, int k)
+HH_HD int jpeg_quant(int quality, int tbl, int k)
 {
     const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
     const int q = (JPEG_QBASE[tbl][k] * scale + 50) / 100;
@@ -112,7 +107,7 @@ HH_JHD int jpeg_quant(int quality, int tbl, int k)
 }
 
 // One pixel -> Y, Cb, Cr (libjpeg's 16-bit fixed point; every numerator is positive, so >> is a plain division).
-HH_JHD void jpeg_ycc(int r, int g, int b, int &y, int &cb, int &cr)
+HH_HD void jpeg_ycc(int r, int g, int b, int &y, int &cb, int &cr)
 {
     y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
     cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
@@ -123,7 +118,7 @@ HH_JHD void jpeg_ycc(int r, int g, int b, int &y, int &cb, int &cr)
 // 444: the lane's one pixel into blocks 0 (Y), 1 (Cb), 2 (Cr).  420: the lane's 2 x 2 pixels into the Y blocks 0..3 (left to right, top
 // to bottom) and their rounded mean chroma into blocks 4 (Cb) and 5 (Cr).  Pixels beyond the frame repeat its last row and column:
 // every source index is y * pitch + x * 3 + c with y < h, x < w, c < 3.
-HH_JHD void jpeg_mcu_samples(const unsigned char *src, const JpegDesc &d, int my, int mx, int lane, int32_t *smp)
+HH_HD void jpeg_mcu_samples(const unsigned char *src, const JpegDesc &d, int my, int mx, int lane, int32_t *smp)
 {
     const int swap = d.flags & 1;
     if (d.subsampling == 420) {
@@ -153,7 +148,7 @@ HH_JHD void jpeg_mcu_samples(const unsigned char *src, const JpegDesc &d, int my
 
 // Row pass, in place on one row of 8 samples: A[u] = (sum_x s[x] T[u][x] + 1024) >> 11.  |s| <= 128 and the largest row sum of |T| is
 // 8 * 5793 = 46344, so |A| <= (46344 * 128 + 1024) >> 11 = 2897.
-HH_JHD void jpeg_fdct_row(int32_t *row)
+HH_HD void jpeg_fdct_row(int32_t *row)
 {
     int32_t s[8];
 #pragma unroll
@@ -168,7 +163,7 @@ HH_JHD void jpeg_fdct_row(int32_t *row)
 }
 
 // Column pass of column u of one block: F[v] = sum_y A[y][u] T[v][y] = 2^17 x the coefficient; |F| <= 2897 * 46344 < 2^27.1.
-HH_JHD void jpeg_fdct_col(const int32_t *A, int u, int32_t F[8])
+HH_HD void jpeg_fdct_col(const int32_t *A, int u, int32_t F[8])
 {
     int32_t a[8];
 #pragma unroll
@@ -183,7 +178,7 @@ HH_JHD void jpeg_fdct_col(const int32_t *A, int u, int32_t F[8])
 }
 
 // q = sign(F) ((|F| + (Q << 16)) / (Q << 17)), clamped to -1024..1023 (DC) or +-1023 (AC).  |F| + (Q << 16) < 2^27.1 + 2^24 < 2^32.
-HH_JHD int jpeg_quantise(int32_t F, int Q, bool dc)
+HH_HD int jpeg_quantise(int32_t F, int Q, bool dc)
 {
     const uint32_t a = F < 0 ? 0u - (uint32_t)F : (uint32_t)F;
     int q = (int)((a + ((uint32_t)Q << 16)) / ((uint32_t)Q << 17));
@@ -192,7 +187,7 @@ HH_JHD int jpeg_quantise(int32_t F, int Q, bool dc)
 }
 
 // Column u of one block through the column pass and the quantiser, into the block's zigzag order.  Qzz: this component's 64 divisors.
-HH_JHD void jpeg_fdct_col_quant(const int32_t *A, int u, const uint16_t *Qzz, int16_t *zz)
+HH_HD void jpeg_fdct_col_quant(const int32_t *A, int u, const uint16_t *Qzz, int16_t *zz)
 {
     int32_t F[8];
     jpeg_fdct_col(A, u, F);
@@ -204,8 +199,8 @@ HH_JHD void jpeg_fdct_col_quant(const int32_t *A, int u, const uint16_t *Qzz, in
 }
 
 // Block j of an interval (MCU j / bpm, block j % bpm of it): is it luminance, and which block holds its DC prediction (-1: none, 0).
-HH_JHD bool jpeg_block_is_luma(int j, int bpm) { return bpm == 6 ? j % 6 < 4 : j % 3 == 0; }
-HH_JHD int jpeg_pred_block(int j, int bpm)
+HH_HD bool jpeg_block_is_luma(int j, int bpm) { return bpm == 6 ? j % 6 < 4 : j % 3 == 0; }
+HH_HD int jpeg_pred_block(int j, int bpm)
 {
     if (bpm == 3) return j - 3;  // (negative in the first MCU)
     const int k = j % 6;
@@ -214,7 +209,7 @@ HH_JHD int jpeg_pred_block(int j, int bpm)
 }
 
 // Canonical codes from BITS / HUFFVAL: table[symbol] = length << 16 | code.  The table must be zero before.
-HH_JHD void jpeg_build_codes(const uint8_t *bits, const uint8_t *vals, uint32_t *table)
+HH_HD void jpeg_build_codes(const uint8_t *bits, const uint8_t *vals, uint32_t *table)
 {
     uint32_t code = 0;
     int p = 0;
@@ -226,14 +221,14 @@ HH_JHD void jpeg_build_codes(const uint8_t *bits, const uint8_t *vals, uint32_t 
 struct JpegCodes {
     uint32_t dc[2][16], ac[2][256];
 };
-HH_JHD void jpeg_build_table(JpegCodes *c, int t)  // t = 0..3: DC luminance, DC chrominance, AC luminance, AC chrominance
+HH_HD void jpeg_build_table(JpegCodes *c, int t)  // t = 0..3: DC luminance, DC chrominance, AC luminance, AC chrominance
 {
     if (t < 2) jpeg_build_codes(JPEG_DC_BITS[t], JPEG_DC_VALS, c->dc[t]);
     else jpeg_build_codes(JPEG_AC_BITS[t - 2], JPEG_AC_VALS[t - 2], c->ac[t - 2]);
 }
 
 // size category of v: the number of bits of |v|
-HH_JHD int jpeg_category(int v)
+HH_HD int jpeg_category(int v)
 {
     uint32_t a = v < 0 ? -v : v;
     int s = 0;
@@ -242,7 +237,7 @@ HH_JHD int jpeg_category(int v)
 }
 // Huffman code of `symbol` followed by the s value bits of v (v itself if positive, v - 1 in s bits if negative) -> sink.put(bits, count)
 template <class Sink>
-HH_JHD void jpeg_put_value(const uint32_t *table, int symbol, int v, int s, Sink &sink)
+HH_HD void jpeg_put_value(const uint32_t *table, int symbol, int v, int s, Sink &sink)
 {
     const uint32_t e = table[symbol];
     const uint32_t value = (uint32_t)(v < 0 ? v - 1 : v) & ((1u << s) - 1u);
@@ -254,7 +249,7 @@ struct alignas(16) JpegVec8 {
 // One block: its DC difference to `pred`, then the run-length coded AC coefficients, ZRL for runs above 15, EOB unless coefficient 63
 // is non-zero.  zz: 64 zigzag coefficients, 16-byte aligned, read as eight 16-byte vectors.
 template <class Sink>
-HH_JHD void jpeg_code_block(const int16_t *zz, int pred, const uint32_t *dc, const uint32_t *ac, Sink &sink)
+HH_HD void jpeg_code_block(const int16_t *zz, int pred, const uint32_t *dc, const uint32_t *ac, Sink &sink)
 {
     int run = 0;
 #pragma unroll 1
@@ -286,11 +281,11 @@ HH_JHD void jpeg_code_block(const int16_t *zz, int pred, const uint32_t *dc, con
 }
 struct JpegCountSink {
     int bits;
-    HH_JHD void put(uint32_t, int count) { bits += count; }
+    HH_HD void put(uint32_t, int count) { bits += count; }
 };
 
 // The JPEG_HEADER_BYTES bytes in front of the first interval: SOI, APP0, DQT 0, DQT 1, SOF0, DHT DC0 DC1 AC0 AC1, DRI, SOS.
-HH_JHD int jpeg_write_header(unsigned char *o, int h, int w, int subsampling, int quality, int mcols)
+HH_HD int jpeg_write_header(unsigned char *o, int h, int w, int subsampling, int quality, int mcols)
 {
     int n = 0;
 #define JPEG_B(x) o[n++] = (unsigned char)(x)
@@ -343,7 +338,7 @@ struct JpegHostSink {
     long long pos;
     uint64_t acc;
     int nacc;
-    HH_JHD void put(uint32_t bits, int count)
+    HH_HD void put(uint32_t bits, int count)
     {
         acc = acc << count | bits;
         nacc += count;

@@ -6,12 +6,7 @@
 #include <math.h>
 
 #include "../../include/hhrnet.h"
-
-#if defined(__HIPCC__)
-#define HH_HD __host__ __device__ __forceinline__
-#else
-#define HH_HD inline
-#endif
+#include "host_dev.h"
 
 // The device table: hh_optim_tensor / hh_optim_group of include/hhrnet.h, and the chunk list hh_optim_step builds.
 using OptimTensor = hh_optim_tensor;

@@ -14,31 +14,23 @@
 #include <stdint.h>
 
 #include "../../include/hhrnet.h"
-
+#include "host_dev.h"
 #if defined(__HIPCC__)
 #include "decode_dev.h"  // Lin, src_index, bilerp (device)
-#define HH_PHD __host__ __device__ __forceinline__
-#define HH_PH __host__ inline
 #else
 struct Lin { int i0, i1; float w0, w1; };
-#define HH_PHD inline
-#define HH_PH inline
-#endif
-#if defined(__clang__)
-#pragma clang fp contract(off)
 #endif
 
-// The launch geometry.  Paint: a workgroup of PANEL_TH x PANEL_TW / PANEL_PX threads owns one PANEL_TH x PANEL_TW tile of the canvas, a
-// thread PANEL_PX horizontally adjacent pixels of it; the figure's cells are culled against the tile, one per lane, so a figure has at
-// most HH_PANEL_MAX_MAPS = the workgroup's size maps.  Min/max: HH_PANEL_PARTS workgroups per map, each leaving one (max, min) pair.
-enum { PANEL_TH = 16, PANEL_TW = 64, PANEL_PX = 4, PANEL_THREADS = PANEL_TH * PANEL_TW / PANEL_PX };
-static_assert(PANEL_THREADS == HH_PANEL_MAX_MAPS && PANEL_TW % PANEL_PX == 0, "one lane per map of a figure, whole pixel groups per tile row");
+// The launch geometry.  Paint: the drawing tile of host_dev.h on the canvas; the cells are culled against it one per lane, so a figure
+// has at most HH_PANEL_MAX_MAPS = the workgroup's size maps.  Min/max: HH_PANEL_PARTS workgroups per map, each leaving one (max, min).
+enum { PANEL_TH = DRAW_TH, PANEL_TW = DRAW_TW, PANEL_PX = DRAW_PX, PANEL_THREADS = DRAW_THREADS };
+static_assert(PANEL_THREADS == HH_PANEL_MAX_MAPS, "one lane per map of a figure");
 
 using PanelMap = hh_panel_map;
 static_assert(sizeof(hh_panel_map) == 40, "ABI 3");
 
-// F.interpolate(mode="bilinear", align_corners=False) of torch CPU: the host forms of decode_dev.h's src_index / bilerp.
-HH_PH Lin src_index(int in_size, float scale, int dst)
+// F.interpolate(mode="bilinear", align_corners=False) of torch CPU: the host forms of decode_dev.h's src_index / bilerp (unqualified = host).
+inline Lin src_index(int in_size, float scale, int dst)
 {
     float r = fmaf(scale, (float)dst + 0.5f, -0.5f);
     if (r < 0.f) r = 0.f;
@@ -49,7 +41,7 @@ HH_PH Lin src_index(int in_size, float scale, int dst)
     o.i0 = a; o.i1 = a + (a < in_size - 1 ? 1 : 0); o.w1 = l1; o.w0 = 1.f - l1;
     return o;
 }
-HH_PH float bilerp(const float *img, int w, const Lin &ly, const Lin &lx)
+inline float bilerp(const float *img, int w, const Lin &ly, const Lin &lx)
 {
     const float *r0 = img + (size_t)ly.i0 * w, *r1 = img + (size_t)ly.i1 * w;
     const float a = fmaf(r0[lx.i0], lx.w0, r0[lx.i1] * lx.w1);
@@ -57,7 +49,7 @@ HH_PH float bilerp(const float *img, int w, const Lin &ly, const Lin &lx)
     return fmaf(a, ly.w0, b * ly.w1);
 }
 
-HH_PHD float panel_fma(float a, float b, float c)
+HH_HD float panel_fma(float a, float b, float c)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_fmaf(a, b, c);
@@ -68,7 +60,7 @@ HH_PHD float panel_fma(float a, float b, float c)
 
 // One half-resolution tap (r, c) of a NESTED / AVERAGE map: the quarter-resolution map resized x2 (avg_at of decode_dev.h), for AVERAGE
 // then averaged with the half-resolution stage.  Every index read lies inside [0, h) x [0, w) resp. [0, 2h) x [0, 2w) by src_index.
-HH_PHD float panel_half_tap(const PanelMap &m, int r, int c)
+HH_HD float panel_half_tap(const PanelMap &m, int r, int c)
 {
     const float up = bilerp(m.src, m.w, src_index(m.h, 0.5f, r), src_index(m.w, 0.5f, c));
     if (m.kind == HH_PANEL_NESTED) return up;
@@ -76,7 +68,7 @@ HH_PHD float panel_half_tap(const PanelMap &m, int r, int c)
 }
 
 // The value of map m at pixel (y, x) of its H x W cell, 0 <= y < H, 0 <= x < W.
-HH_PHD float panel_value(const PanelMap &m, int H, int W, int y, int x)
+HH_HD float panel_value(const PanelMap &m, int H, int W, int y, int x)
 {
     if (m.kind == HH_PANEL_DIRECT) return m.src[(size_t)y * W + x];
     if (m.kind == HH_PANEL_SINGLE) {
@@ -93,7 +85,7 @@ HH_PHD float panel_value(const PanelMap &m, int H, int W, int y, int x)
 }
 
 // Step 1: np.clip(v, 0, 1); NaN stays NaN.
-HH_PHD float panel_clip(float v, int flags)
+HH_HD float panel_clip(float v, int flags)
 {
     if (flags & HH_PANEL_CLIP) v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
     return v;
@@ -101,8 +93,8 @@ HH_PHD float panel_clip(float v, int flags)
 
 // The running (max, min) of a map in np.max / np.min semantics: a NaN makes both NaN.  (fmaxf / fminf would drop it.)
 struct PanelRange { float mx, mn; };
-HH_PHD PanelRange panel_range_first(float v) { PanelRange r; r.mx = v; r.mn = v; return r; }
-HH_PHD PanelRange panel_range_join(PanelRange a, PanelRange b)
+HH_HD PanelRange panel_range_first(float v) { PanelRange r; r.mx = v; r.mn = v; return r; }
+HH_HD PanelRange panel_range_join(PanelRange a, PanelRange b)
 {
     PanelRange r;
     if (a.mx != a.mx || b.mx != b.mx) { r.mx = r.mn = NAN; return r; }
@@ -112,13 +104,13 @@ HH_PHD PanelRange panel_range_join(PanelRange a, PanelRange b)
 }
 
 // Step 3: (uint8)(q) as numpy casts it: truncated toward zero as int32 (0 when q is not finite or outside int32), low 8 bits.
-HH_PHD int panel_level(float q)
+HH_HD int panel_level(float q)
 {
     int t = 0;
     if (q >= -2147483648.f && q < 2147483648.f) t = (int)q;
     return t & 255;
 }
-HH_PHD int panel_level_f64(double q)
+HH_HD int panel_level_f64(double q)
 {
     int t = 0;
     if (q >= -2147483648.0 && q < 2147483648.0) t = (int)q;
@@ -126,7 +118,7 @@ HH_PHD int panel_level_f64(double q)
 }
 
 // addWeighted(img, 0.25, colour, 0.75, 0) on one channel: render_blend of render_math.h with fixed weights.
-HH_PHD uint8_t panel_blend(uint8_t img, uint8_t colour)
+HH_HD uint8_t panel_blend(uint8_t img, uint8_t colour)
 {
     const float a = (float)img * 0.25f, b = (float)colour * 0.75f;
     float v = rintf(a + b);
@@ -135,14 +127,14 @@ HH_PHD uint8_t panel_blend(uint8_t img, uint8_t colour)
 }
 
 // Steps 2-4: the value after step 1 -> index into the colour table.
-HH_PHD int panel_colour_index(float v, int flags, PanelRange r)
+HH_HD int panel_colour_index(float v, int flags, PanelRange r)
 {
     if (flags & HH_PANEL_MINMAX) v = (v - r.mx) / (r.mx - r.mn);
     return 255 - panel_level(v * 255.0f);
 }
 
 // KeypointsTransform.inverse_transform on one element: ((double)x * std + mean) * 255 in float64, then the cast of step 3.
-HH_PHD uint8_t panel_unnormalize(float x, double sd, double mean)
+HH_HD uint8_t panel_unnormalize(float x, double sd, double mean)
 {
     const double p = (double)x * sd;
     const double s = p + mean;

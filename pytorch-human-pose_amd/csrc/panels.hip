@@ -10,13 +10,14 @@
 // pixels stores the identity (-inf, +inf).  Workgroups of maps without the flag return at once; the launch is skipped when no map has it.
 //
 // panels_paint_kernel: a workgroup of 256 threads owns one PANEL_TH x PANEL_TW = 16 x 64 tile of the canvas, a thread PANEL_PX = 4
-// horizontally adjacent pixels of it.  Each lane tests one map's cell against the tile; the survivors are compacted into LDS in table
-// order (ballot within a wave, the waves' counts prefixed through LDS); each wave then joins the HH_PANEL_PARTS pairs of the listed maps that
-// use min-max.  A pixel takes the last listed cell that holds it (a later map overwrites an earlier one) or is zero: padding and unused
+// horizontally adjacent pixels of it (draw_dev.h: draw_tile).  Each lane tests one map's cell against the tile; the survivors are
+// compacted into LDS in table order (the cull of draw_dev.h's draw_cull_slot, here with two arrays); each wave then joins the
+// HH_PANEL_PARTS pairs of the listed maps that use min-max.  A pixel takes the last listed cell that holds it (a later map overwrites an earlier one) or is zero: padding and unused
 // cells are written by the same launch.  Every canvas byte of the Wc * 3 row bytes is written exactly once by exactly one thread.  Cell
 // origins and the pitch are arbitrary, so a thread's 12 bytes are stored as three dwords only when they are 4-byte aligned and all four
 // pixels are inside the canvas, byte by byte otherwise (the right edge, and every row whose address is odd).
 #include "kernels.h"
+#include "draw_dev.h"
 #include "panel_math.h"
 
 #define PANEL_WAVES (PANEL_THREADS / 64)
@@ -70,8 +71,8 @@ __global__ __launch_bounds__(PANEL_THREADS) void panels_paint_kernel(const Panel
     __shared__ unsigned char slut[768];
     __shared__ int wave_count[PANEL_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ty0 = (int)(blockIdx.x / xtiles) * PANEL_TH, tx0 = (int)(blockIdx.x % xtiles) * PANEL_TW;  // inside the canvas by the grid's size
-    const int ty1 = min(ty0 + PANEL_TH, Hc) - 1, tx1 = min(tx0 + PANEL_TW, Wc) - 1;
+    const DrawTile t = draw_tile(blockIdx.x, xtiles, Hc, Wc, tid);  // inside the canvas by the grid's size
+    const int tx0 = t.tx0, ty0 = t.ty0, tx1 = t.tx1, ty1 = t.ty1, y = t.y, x = t.x, npx = t.npx;
     for (int i = tid; i < 768; i += PANEL_THREADS) slut[i] = lut[i];
 
     PanelMap mine;
@@ -80,6 +81,7 @@ __global__ __launch_bounds__(PANEL_THREADS) void panels_paint_kernel(const Panel
         mine = maps[tid];
         keep = mine.ox <= tx1 && mine.ox + W - 1 >= tx0 && mine.oy <= ty1 && mine.oy + H - 1 >= ty0;
     }
+    // draw_dev.h's draw_cull_slot written out: through the helper this kernel's SGPR count goes from 33 to 37 (tools/isa_diff.py)
     const unsigned long long bal = __ballot(keep);
     if (lane == 0) wave_count[wave] = __popcll(bal);
     __syncthreads();
@@ -114,8 +116,6 @@ __global__ __launch_bounds__(PANEL_THREADS) void panels_paint_kernel(const Panel
     }
     __syncthreads();
 
-    const int y = ty0 + tid / (PANEL_TW / PANEL_PX), x = tx0 + (tid % (PANEL_TW / PANEL_PX)) * PANEL_PX;
-    const int npx = (y <= ty1) ? min(PANEL_PX, tx1 - x + 1) : 0;  // pixels of this thread inside the canvas (<= 0: none)
     if (npx <= 0) return;
     uint8_t op[PANEL_PX * 3];
 #pragma unroll
@@ -136,9 +136,7 @@ __global__ __launch_bounds__(PANEL_THREADS) void panels_paint_kernel(const Panel
     }
     unsigned char *optr = canvas + (size_t)y * pitch + (size_t)x * 3;  // y < Hc, x + e < Wc for e < npx: inside the row's Wc * 3 bytes
     if (npx == PANEL_PX && ((uintptr_t)optr & 3) == 0) {
-        uint32_t *o4 = reinterpret_cast<uint32_t *>(optr);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) o4[q] = op[q * 4] | op[q * 4 + 1] << 8 | op[q * 4 + 2] << 16 | (uint32_t)op[q * 4 + 3] << 24;
+        draw_store_dwords<3>(optr, [&](int i) { return op[i]; });
     } else {
 #pragma unroll
         for (int i = 0; i < PANEL_PX * 3; ++i)

@@ -11,15 +11,7 @@
 #include <stdio.h>
 
 #include "../../include/hhrnet.h"
-
-#if defined(__HIPCC__)
-#define HH_PHD __host__ __device__ __forceinline__
-#else
-#define HH_PHD inline
-#endif
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
+#include "host_dev.h"
 
 // One workgroup owns one image.  Its un-warped predictions live in LDS ([P,K,2] fp64, 64 KB at the maxima), each of its POSE_WAVES waves
 // owns one target at a time (the target's row [K,3] and its K terms staged per wave); lane p of the wave holds D[p,t], so P <= 64 = one
@@ -42,21 +34,21 @@ struct PoseTables {
     int32_t B, K, form, metric, max_people;
 };
 
-HH_PHD size_t pose_lds_bytes(int P, int K) { return ((size_t)P * K * 2 + (size_t)POSE_WAVES * K * 4) * sizeof(double); }
+HH_HD size_t pose_lds_bytes(int P, int K) { return ((size_t)P * K * 2 + (size_t)POSE_WAVES * K * 4) * sizeof(double); }
 
-HH_PHD bool pose_finite(double v) { return v - v == 0.0; }
-HH_PHD double pose_nan() { return __builtin_nan(""); }
+HH_HD bool pose_finite(double v) { return v - v == 0.0; }
+HH_HD double pose_nan() { return __builtin_nan(""); }
 
-HH_PHD int pose_num_preds(const PoseTables &t, int i)
+HH_HD int pose_num_preds(const PoseTables &t, int i)
 {
     if (t.form == HH_POSE_PRED_F64) return t.p_off[i + 1] - t.p_off[i];
     const int n = t.num[i];
     return n < 0 ? 0 : n < t.max_people ? n : t.max_people;
 }
-HH_PHD bool pose_fallback(const PoseTables &t, int i) { return t.form == HH_POSE_PRED_DECODE && t.flags && (t.flags[i] & HH_DECODE_FALLBACK); }
+HH_HD bool pose_fallback(const PoseTables &t, int i) { return t.form == HH_POSE_PRED_DECODE && t.flags && (t.flags[i] & HH_DECODE_FALLBACK); }
 
 // Coordinate c (0 = x, 1 = y) of joint k of prediction p of image i, as the rule reads it.
-HH_PHD double pose_pred_coord(const PoseTables &t, int i, int p, int k, int c, bool fallback)
+HH_HD double pose_pred_coord(const PoseTables &t, int i, int p, int k, int c, bool fallback)
 {
     if (t.form == HH_POSE_PRED_F64) return t.p_xy[((size_t)(t.p_off[i] + p) * t.K + k) * 2 + c];
     const float *j = t.joints + (size_t)i * t.image_stride + (size_t)p * t.person_stride + (size_t)k * t.joint_stride;
@@ -65,7 +57,7 @@ HH_PHD double pose_pred_coord(const PoseTables &t, int i, int p, int k, int c, b
     const double u = M[0] * x + M[1] * y + M[2] * 1.0;
     return fallback ? u : (double)(float)u;
 }
-HH_PHD double pose_pred_score(const PoseTables &t, int i, int p, bool fallback)
+HH_HD double pose_pred_score(const PoseTables &t, int i, int p, bool fallback)
 {
     if (t.form == HH_POSE_PRED_F64) return t.p_score[t.p_off[i] + p];
     if (!fallback) return (double)t.scores[(size_t)i * t.score_stride + p];
@@ -75,14 +67,14 @@ HH_PHD double pose_pred_score(const PoseTables &t, int i, int p, bool fallback)
 }
 
 // The position of prediction p in the walk (ascending score, equal scores by ascending index); scores are finite.
-HH_PHD int pose_rank(const double *score, int P, int p)
+HH_HD int pose_rank(const double *score, int P, int p)
 {
     int r = 0;
     for (int q = 0; q < P; ++q) r += (score[q] < score[p] || (score[q] == score[p] && q < p)) ? 1 : 0;
     return r;
 }
 
-HH_PHD int pose_visible(const double *xyv, int K)
+HH_HD int pose_visible(const double *xyv, int K)
 {
     int n = 0;
     for (int k = 0; k < K; ++k) n += xyv[3 * k + 2] > 0.0 ? 1 : 0;
@@ -90,7 +82,7 @@ HH_PHD int pose_visible(const double *xyv, int K)
 }
 
 // val = 1 / D of one (prediction, target) pair: pxy [K,2], xyv [K,3], n = pose_visible(xyv) > 0.
-HH_PHD double pose_match_val(const double *pxy, const double *xyv, int K, int n)
+HH_HD double pose_match_val(const double *pxy, const double *xyv, int K, int n)
 {
     double sum = 0.0;
     for (int k = 0; k < K; ++k) {
@@ -103,10 +95,10 @@ HH_PHD double pose_match_val(const double *pxy, const double *xyv, int K, int n)
 
 // "a comes before b" for the strict-greater walk: the final holder is the first position in walk order that reaches the largest val, so
 // a reduction over (val, rank) in any order finds it.  A NaN val never holds (it is never greater).
-HH_PHD bool pose_better(double va, int ra, double vb, int rb) { return va > vb || (va == vb && ra < rb); }
+HH_HD bool pose_better(double va, int ra, double vb, int rb) { return va > vb || (va == vb && ra < rb); }
 
 // The per-joint term of target joint k against the matched prediction: exp(-e_k) or the hit, -1 for an unlabelled joint.
-HH_PHD double pose_term(const PoseTables &t, const double *pxy, const double *xyv, double area, double head, int k)
+HH_HD double pose_term(const PoseTables &t, const double *pxy, const double *xyv, double area, double head, int k)
 {
     if (!(xyv[3 * k + 2] > 0.0)) return -1.0;
     if (t.metric == HH_POSE_METRIC_OKS) {
@@ -119,7 +111,7 @@ HH_PHD double pose_term(const PoseTables &t, const double *pxy, const double *xy
 }
 
 // obj[t] from the K terms, ascending k.
-HH_PHD double pose_object(const double *term, int K, int n)
+HH_HD double pose_object(const double *term, int K, int n)
 {
     double sum = 0.0;
     for (int k = 0; k < K; ++k)
@@ -128,7 +120,7 @@ HH_PHD double pose_object(const double *term, int K, int n)
 }
 
 // The image value from its T object values, ascending t.
-HH_PHD double pose_image_value(const double *obj, int T, int metric)
+HH_HD double pose_image_value(const double *obj, int T, int metric)
 {
     double sum = 0.0;
     int n = 0;

@@ -5,9 +5,9 @@
 // hh_render_desc per frame; nothing but per-pixel work happens here.
 //
 // render_poses_kernel: a workgroup of 256 threads owns one RENDER_TH x RENDER_TW = 16 x 64 tile of one frame's output, a thread
-// RENDER_PX = 4 horizontally adjacent pixels of it.  The frame's primitives are walked RENDER_CHUNK = 256 at a time: each lane tests
-// one primitive's box against the tile, the survivors are compacted into LDS in draw order (ballot within a wave, the four waves'
-// counts prefixed through LDS), and every thread walks that list with render_inside, a later hit overwriting an earlier one.  Chunks
+// RENDER_PX = 4 horizontally adjacent pixels of it (draw_dev.h: draw_tile).  The frame's primitives are walked RENDER_CHUNK = 256 at
+// a time: each lane tests one primitive's box against the tile, the survivors are compacted into LDS in draw order (draw_dev.h:
+// draw_cull_slot), and every thread walks that list with render_inside, a later hit overwriting an earlier one.  Chunks
 // follow each other in draw order and a thread keeps its pixels' current colours in registers across them, so the order holds across
 // chunks and the list never needs more than one chunk of room (8 KB), whatever the frame's primitive count.  All lanes read the same
 // list entry at the same time: an LDS broadcast, no bank conflict.  Then the thread blends against the source pixels it read once at
@@ -18,6 +18,7 @@
 // resize_u8_kernel: the streaming kernel of train_mosaic.hip without its restrictions: any h, w, H, W >= 1, 1 or 3 channels, the same
 // taps (resize_dev.h) and the 2 x 2 mean at an exact factor of 2 on both axes.
 #include "kernels.h"
+#include "draw_dev.h"
 #include "render_math.h"
 #include "resize_dev.h"
 
@@ -29,27 +30,19 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_poses_kernel(unsigned c
     __shared__ RenderPrim list[RENDER_CHUNK];
     __shared__ int wave_count[RENDER_WAVES];
     const RenderDesc d = descs[blockIdx.z];
-    const int xtiles = (d.w + RENDER_TW - 1) / RENDER_TW;
-    const int ty0 = (int)(blockIdx.x / xtiles) * RENDER_TH, tx0 = (int)(blockIdx.x % xtiles) * RENDER_TW;
-    if (ty0 >= d.h) return;  // (the whole workgroup: the grid is sized for the largest frame of the batch)
-    const int ty1 = min(ty0 + RENDER_TH, d.h) - 1, tx1 = min(tx0 + RENDER_TW, d.w) - 1;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int y = ty0 + tid / (RENDER_TW / RENDER_PX), x = tx0 + (tid % (RENDER_TW / RENDER_PX)) * RENDER_PX;
-    const int npx = (y <= ty1) ? min(RENDER_PX, tx1 - x + 1) : 0;  // pixels of this thread inside the frame (<= 0: none)
+    const DrawTile t = draw_tile(blockIdx.x, (d.w + RENDER_TW - 1) / RENDER_TW, d.h, d.w, tid);
+    if (t.ty0 >= d.h) return;  // (the whole workgroup: the grid is sized for the largest frame of the batch)
+    const int tx0 = t.tx0, ty0 = t.ty0, tx1 = t.tx1, ty1 = t.ty1, y = t.y, x = t.x, npx = t.npx;
 
     // the source pixels, read once: y < h and x + e < w for e < npx, so every byte is inside the frame's h * w * 3
     uint8_t sp[RENDER_PX * 3];
+    const size_t at = ((size_t)(npx > 0 ? y : 0) * d.w + (npx > 0 ? x : 0)) * 3;
 #pragma unroll
     for (int i = 0; i < RENDER_PX * 3; ++i) sp[i] = 0;
-    const size_t at = ((size_t)(npx > 0 ? y : 0) * d.w + (npx > 0 ? x : 0)) * 3;
     const unsigned char *sptr = base + d.src_offset + at;
     if (npx == RENDER_PX && ((uintptr_t)sptr & 3) == 0) {
-        const uint32_t *s4 = reinterpret_cast<const uint32_t *>(sptr);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const uint32_t v = s4[q];
-            sp[q * 4] = v & 255, sp[q * 4 + 1] = (v >> 8) & 255, sp[q * 4 + 2] = (v >> 16) & 255, sp[q * 4 + 3] = v >> 24;
-        }
+        draw_load_dwords<3>(sptr, [&](int i, uint32_t v) { sp[i] = v; });
     } else {
 #pragma unroll
         for (int e = 0; e < RENDER_PX; ++e)
@@ -70,20 +63,11 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_poses_kernel(unsigned c
             mine = prims[d.prim_offset + i];
             keep = render_box_meets(mine, tx0, ty0, tx1, ty1);
         }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) wave_count[wave] = __popcll(m);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int v = 0; v < RENDER_WAVES; ++v) {
-            const int c = wave_count[v];
-            before += v < wave ? c : 0;
-            total += c;
-        }
-        if (keep) list[before + __popcll(m & ((1ull << lane) - 1ull))] = mine;  // < total <= RENDER_CHUNK
+        const DrawSlot cull = draw_cull_slot<RENDER_WAVES>(keep, lane, wave, wave_count);
+        if (keep) list[cull.slot] = mine;  // < cull.total <= RENDER_CHUNK
         __syncthreads();
         if (npx > 0)
-            for (int k = 0; k < total; ++k) {
+            for (int k = 0; k < cull.total; ++k) {
                 const RenderPrim p = list[k];
                 if (y < p.y0 || y > p.y1 || x + RENDER_PX - 1 < p.x0 || x > p.x1) continue;
                 const uint32_t colour = p.rgb[0] | p.rgb[1] << 8 | p.rgb[2] << 16;
@@ -104,9 +88,7 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_poses_kernel(unsigned c
             op[e * 3 + (bgr ? 2 - ch : ch)] = render_blend(sp[e * 3 + ch], (conn[e] >> (8 * ch)) & 255, d.w0, d.w1);
     unsigned char *optr = base + d.dst_offset + at;
     if (npx == RENDER_PX && ((uintptr_t)optr & 3) == 0) {
-        uint32_t *o4 = reinterpret_cast<uint32_t *>(optr);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) o4[q] = op[q * 4] | op[q * 4 + 1] << 8 | op[q * 4 + 2] << 16 | (uint32_t)op[q * 4 + 3] << 24;
+        draw_store_dwords<3>(optr, [&](int i) { return op[i]; });
     } else {
 #pragma unroll
         for (int e = 0; e < RENDER_PX; ++e)
@@ -177,9 +159,7 @@ __global__ __launch_bounds__(RESIZE_TX *RESIZE_TY) void resize_u8_kernel(const u
         }
         unsigned char *o = dst + ((size_t)y * W + x0) * CH;  // y < H, x0 + e < W for e < npx
         if (npx == RESIZE_PX && ((uintptr_t)o & 3) == 0) {
-            uint32_t *o4 = reinterpret_cast<uint32_t *>(o);
-#pragma unroll
-            for (int q = 0; q < CH; ++q) o4[q] = px[q * 4] | px[q * 4 + 1] << 8 | px[q * 4 + 2] << 16 | (uint32_t)px[q * 4 + 3] << 24;
+            draw_store_dwords<CH>(o, [&](int i) { return px[i]; });
         } else {
 #pragma unroll
             for (int i = 0; i < RESIZE_PX * CH; ++i)

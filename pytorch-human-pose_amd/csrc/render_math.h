@@ -7,29 +7,19 @@
 #include <math.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define HH_RHD __host__ __device__ __forceinline__
-#else
-#define HH_RHD inline
-#endif
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-
 #include "../../include/hhrnet.h"
+#include "host_dev.h"
 
-// The launch geometry, reported by hh_render_config: a workgroup of RENDER_TW / RENDER_PX x RENDER_TH threads owns one RENDER_TH x
-// RENDER_TW tile of the output, a thread RENDER_PX horizontally adjacent pixels of it; the frame's primitives are culled against the
-// tile RENDER_CHUNK at a time, one per lane.
-enum { RENDER_TH = 16, RENDER_TW = 64, RENDER_PX = 4, RENDER_THREADS = RENDER_TH * RENDER_TW / RENDER_PX, RENDER_CHUNK = RENDER_THREADS };
-static_assert(RENDER_THREADS == 256 && RENDER_TW % RENDER_PX == 0, "one lane per primitive of a chunk, whole pixel groups per tile row");
+// The launch geometry, reported by hh_render_config: the drawing tile of host_dev.h on the output; the frame's primitives are culled
+// against the tile RENDER_CHUNK at a time, one per lane.
+enum { RENDER_TH = DRAW_TH, RENDER_TW = DRAW_TW, RENDER_PX = DRAW_PX, RENDER_THREADS = DRAW_THREADS, RENDER_CHUNK = DRAW_THREADS };
 
 using RenderPrim = hh_render_prim;
 using RenderDesc = hh_render_desc;
 static_assert(sizeof(hh_render_prim) == 32 && sizeof(hh_render_desc) == 48, "ABI 3");
 
 // Does the primitive's box meet the tile [tx0, tx1] x [ty0, ty1] (inclusive, already inside the frame)?
-HH_RHD bool render_box_meets(const RenderPrim &p, int tx0, int ty0, int tx1, int ty1)
+HH_HD bool render_box_meets(const RenderPrim &p, int tx0, int ty0, int tx1, int ty1)
 {
     return p.x0 <= tx1 && p.x1 >= tx0 && p.y0 <= ty1 && p.y1 >= ty0;
 }
@@ -37,7 +27,7 @@ HH_RHD bool render_box_meets(const RenderPrim &p, int tx0, int ty0, int tx1, int
 // Is pixel (x, y) inside the primitive?  The box is a superset of every kind's set (the host forms it with a margin beyond the fp32
 // rounding of the ellipse test), so testing it first changes nothing and keeps dx, dy small enough for the exact int32 forms:
 // |dx|, |dy| <= 32767 inside a disc's or ring's box (render_check_frame), dx^2 + dy^2 < 2^31; an ellipse's dx, dy are exact in fp32.
-HH_RHD bool render_inside(const RenderPrim &p, int x, int y)
+HH_HD bool render_inside(const RenderPrim &p, int x, int y)
 {
     if (x < p.x0 || x > p.x1 || y < p.y0 || y > p.y1) return false;
     const int dx = x - p.cx, dy = y - p.cy;
@@ -59,12 +49,39 @@ HH_RHD bool render_inside(const RenderPrim &p, int x, int y)
 }
 
 // addWeighted on one channel: rintf(img w0 + conn w1), products and sum rounded separately, clamped to 0..255.
-HH_RHD uint8_t render_blend(uint8_t img, uint8_t conn, float w0, float w1)
+HH_HD uint8_t render_blend(uint8_t img, uint8_t conn, float w0, float w1)
 {
     const float a = (float)img * w0, b = (float)conn * w1;
     float v = rintf(a + b);
     v = v < 0.f ? 0.f : (v > 255.f ? 255.f : v);
     return (uint8_t)(int)v;
+}
+
+// The kernels' chunked cull on the host (the twins of render, text and seg): `count` items `chunk` at a time; of each chunk those
+// that meets() accepts go through make() into `list` in draw order, and walk(n) applies the n listed ones.
+template <class Src, class Item, class Meets, class Make, class Walk>
+inline void draw_chunks_host(const Src *items, int count, int chunk, Item *list, Meets meets, Make make, Walk walk)
+{
+    for (int first = 0; first < count; first += chunk) {
+        int n = 0;
+        for (int i = first; i < count && i < first + chunk; ++i)
+            if (meets(items[i])) list[n++] = make(items[i]);
+        walk(n);
+    }
+}
+
+// What every drawing call refuses in a frame's descriptor, in this order; nullptr = accepted.  `own`: the feature's refusal about the
+// two offsets, if any; the other wordings are the feature's too; weight_why = nullptr: no blend weights in the descriptor.
+inline const char *draw_check_frame(const hh_render_desc &d, const char *own, long long table_len, int max_prims, const char *range_why,
+                                    const char *max_why, const char *weight_why)
+{
+    if (d.h < 1 || d.w < 1 || d.h > 16384 || d.w > 16384) return "frame size outside 1..16384";
+    if (d.src_offset < 0 || d.dst_offset < 0) return "negative offset";
+    if (own) return own;
+    if (d.prim_count < 0 || d.prim_offset < 0 || (long long)d.prim_offset + d.prim_count > table_len) return range_why;
+    if (d.prim_count > max_prims) return max_why;
+    if (weight_why && (!(d.w0 == d.w0) || !(d.w1 == d.w1) || fabsf(d.w0) > 1e6f || fabsf(d.w1) > 1e6f)) return weight_why;
+    return nullptr;
 }
 
 // One frame on the host, in the kernel's own walk: tile by tile, the primitives culled chunk by chunk into a list in draw order, every
@@ -79,18 +96,18 @@ inline void render_frame_host(const uint8_t *src, uint8_t *dst, const RenderDesc
             for (int y = ty0; y <= ty1; ++y)
                 for (int x = tx0; x <= tx1; ++x)
                     for (int ch = 0; ch < 3; ++ch) conn[y - ty0][x - tx0][ch] = src[((size_t)y * w + x) * 3 + ch];
-            for (int base = 0; base < d.prim_count; base += RENDER_CHUNK) {
-                int n = 0;
-                for (int i = base; i < d.prim_count && i < base + RENDER_CHUNK; ++i)
-                    if (render_box_meets(prims[d.prim_offset + i], tx0, ty0, tx1, ty1)) list[n++] = prims[d.prim_offset + i];
-                for (int y = ty0; y <= ty1; ++y)
-                    for (int x = tx0; x <= tx1; ++x)
-                        for (int i = 0; i < n; ++i)
-                            if (render_inside(list[i], x, y)) {
-                                uint8_t *c = conn[y - ty0][x - tx0];
-                                c[0] = list[i].rgb[0], c[1] = list[i].rgb[1], c[2] = list[i].rgb[2];
-                            }
-            }
+            draw_chunks_host(
+                prims + d.prim_offset, d.prim_count, RENDER_CHUNK, list, [&](const RenderPrim &p) { return render_box_meets(p, tx0, ty0, tx1, ty1); },
+                [](const RenderPrim &p) { return p; },
+                [&](int n) {
+                    for (int y = ty0; y <= ty1; ++y)
+                        for (int x = tx0; x <= tx1; ++x)
+                            for (int i = 0; i < n; ++i)
+                                if (render_inside(list[i], x, y)) {
+                                    uint8_t *c = conn[y - ty0][x - tx0];
+                                    c[0] = list[i].rgb[0], c[1] = list[i].rgb[1], c[2] = list[i].rgb[2];
+                                }
+                });
             for (int y = ty0; y <= ty1; ++y)
                 for (int x = tx0; x <= tx1; ++x)
                     for (int ch = 0; ch < 3; ++ch) {
@@ -103,11 +120,9 @@ inline void render_frame_host(const uint8_t *src, uint8_t *dst, const RenderDesc
 // What hh_render_poses_u8_batch refuses, on the caller's host copy; nullptr = accepted.  `max_prims` is HH_RENDER_MAX_PRIMS.
 inline const char *render_check_frame(const RenderDesc &d, const RenderPrim *prims, long long table_len, int max_prims)
 {
-    if (d.h < 1 || d.w < 1 || d.h > 16384 || d.w > 16384) return "frame size outside 1..16384";
-    if (d.src_offset < 0 || d.dst_offset < 0) return "negative offset";
-    if (d.prim_count < 0 || d.prim_offset < 0 || (long long)d.prim_offset + d.prim_count > table_len) return "primitive range outside the table";
-    if (d.prim_count > max_prims) return "more than HH_RENDER_MAX_PRIMS primitives in one frame";
-    if (!(d.w0 == d.w0) || !(d.w1 == d.w1) || fabsf(d.w0) > 1e6f || fabsf(d.w1) > 1e6f) return "blend weight not finite";
+    if (const char *why = draw_check_frame(d, nullptr, table_len, max_prims, "primitive range outside the table",
+                                           "more than HH_RENDER_MAX_PRIMS primitives in one frame", "blend weight not finite"))
+        return why;
     if (d.flags & ~1) return "unknown flag";
     for (int i = 0; i < d.prim_count; ++i) {
         const RenderPrim &p = prims[d.prim_offset + i];

@@ -5,10 +5,9 @@
 //
 // seg_overlay_kernel: a workgroup of 256 threads owns one SEG_TH x SEG_TW = 32 x 128 tile of one frame.
 // Phase 1, column-wise: thread t owns SEG_ROWS = 16 rows of tile column t % 128 and keeps their overlay colours (SEG_COVERED | colour,
-// or 0) in 16 registers.  The frame's shapes are walked SEG_CHUNK = 256 at a time as render_poses_kernel walks its primitives: each
-// lane tests one shape against the tile, the survivors are compacted into LDS in draw order (ballot within a wave, the four waves'
-// counts prefixed through LDS), and every thread walks that list, all lanes reading the same entry at the same time (an LDS
-// broadcast).  A shape gives a thread the bitmask of its rows that it covers: a fill by one upper-bound search in its toggles and a
+// or 0) in 16 registers.  The frame's shapes are walked SEG_CHUNK = 256 at a time: each lane tests one shape against the tile, the
+// survivors are compacted into LDS in draw order (draw_dev.h: draw_cull_slot), and every thread walks that list, all lanes reading
+// the same entry at the same time (an LDS broadcast).  A shape gives a thread the bitmask of its rows that it covers: a fill by one upper-bound search in its toggles and a
 // cursor down the column (crowd_column_bits: column-major toggles, a lane per column), a line by its exact int64 rule, solved for the
 // column.  The registers persist across the list and across chunks, so the draw order holds within and across chunks, no thread ever
 // writes another thread's pixel, and the walk needs no barrier besides the cull's.
@@ -22,14 +21,10 @@
 // slots) and picks four by `head`.  Every output byte is written exactly once by exactly one lane, every source byte is read by the
 // lane that writes its pixel (so dst may be src); no atomics; nothing depends on the launch.
 #include "kernels.h"
+#include "draw_dev.h"
 #include "seg_overlay_math.h"
 
 #define SEG_WAVES (SEG_THREADS / 64)
-
-struct SegWide { uint32_t a, b, c; };  // 12 bytes on a 4-byte boundary: one dwordx3 access
-
-__device__ __forceinline__ uint32_t seg_load_px(const unsigned char *p) { return p[0] | p[1] << 8 | p[2] << 16; }
-__device__ __forceinline__ void seg_store_px(unsigned char *p, uint32_t v) { p[0] = v & 255, p[1] = v >> 8 & 255, p[2] = v >> 16 & 255; }
 
 __global__ __launch_bounds__(SEG_THREADS) void seg_overlay_kernel(unsigned char *base, const SegDesc *__restrict__ descs, const SegShape *__restrict__ shapes,
                                                                   const uint32_t *__restrict__ toggles)
@@ -61,20 +56,11 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_overlay_kernel(unsigned char 
             keep = seg_meets(s, tx0, ty0, tx1, ty1);
             mine = seg_item(s);
         }
-        const unsigned long long m = __ballot(keep);
-        if (lane == 0) wave_count[wave] = __popcll(m);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int v = 0; v < SEG_WAVES; ++v) {
-            const int c = wave_count[v];
-            before += v < wave ? c : 0;
-            total += c;
-        }
-        if (keep) list[before + __popcll(m & ((1ull << lane) - 1ull))] = mine;  // < total <= SEG_CHUNK
+        const DrawSlot cull = draw_cull_slot<SEG_WAVES>(keep, lane, wave, wave_count);
+        if (keep) list[cull.slot] = mine;  // < cull.total <= SEG_CHUNK
         __syncthreads();
         if (myrows > 0)
-            for (int k = 0; k < total; ++k) {
+            for (int k = 0; k < cull.total; ++k) {
                 const SegItem s = list[k];
                 // X < w and Y0 + myrows <= h: a fill's searches stay inside its own toggles (range checked on the host)
                 const uint32_t bits = seg_item_bits(s, toggles, d.h, X, Y0, myrows);
@@ -104,7 +90,7 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_overlay_kernel(unsigned char 
         const int head = (int)(reinterpret_cast<uintptr_t>(drow) & 3);
         const bool src_aligned = ((reinterpret_cast<uintptr_t>(srow) ^ reinterpret_cast<uintptr_t>(drow)) & 3) == 0;
         const uint32_t *orow = &own_lds[r * SEG_PITCH];
-        if (g < head && g < cols) seg_store_px(drow + 3 * g, seg_pixel(seg_load_px(srow + 3 * g), orow[g], w0, w1, flags));
+        if (g < head && g < cols) draw_store_px(drow + 3 * g, seg_pixel(draw_load_px(srow + 3 * g), orow[g], w0, w1, flags));
         const int p0 = head + SEG_PX * g;  // the tile column of this lane's first pixel; columns from `cols` on are not this tile's
         if (p0 >= cols) continue;
         const uint4 qa = *reinterpret_cast<const uint4 *>(&orow[SEG_PX * g]), qb = *reinterpret_cast<const uint4 *>(&orow[SEG_PX * g + 4]);
@@ -118,21 +104,21 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_overlay_kernel(unsigned char 
         const unsigned char *sp = srow + 3 * p0;
         unsigned char *dp = drow + 3 * p0;  // 4-byte aligned by the choice of head
         if (p0 + SEG_PX <= cols) {
-            uint32_t s0, s1, s2, s3;
+            uint32_t s[SEG_PX];
             if (src_aligned) {
-                const SegWide q = *reinterpret_cast<const SegWide *>(sp);
-                s0 = q.a & 0xffffffu, s1 = (q.a >> 24) | (q.b & 0xffffu) << 8, s2 = (q.b >> 16) | (q.c & 0xffu) << 16, s3 = q.c >> 8;
+                const DrawPx4 q = draw_load_px4(sp);
+                s[0] = q.v[0], s[1] = q.v[1], s[2] = q.v[2], s[3] = q.v[3];
             } else {
-                s0 = seg_load_px(sp), s1 = seg_load_px(sp + 3), s2 = seg_load_px(sp + 6), s3 = seg_load_px(sp + 9);
+                s[0] = draw_load_px(sp), s[1] = draw_load_px(sp + 3), s[2] = draw_load_px(sp + 6), s[3] = draw_load_px(sp + 9);
             }
-            const uint32_t r0 = seg_pixel(s0, o0, w0, w1, flags), r1 = seg_pixel(s1, o1, w0, w1, flags);
-            const uint32_t r2 = seg_pixel(s2, o2, w0, w1, flags), r3 = seg_pixel(s3, o3, w0, w1, flags);
-            *reinterpret_cast<SegWide *>(dp) = SegWide{r0 | r1 << 24, r1 >> 8 | r2 << 16, r2 >> 16 | r3 << 8};
+            const uint32_t r[SEG_PX] = {seg_pixel(s[0], o0, w0, w1, flags), seg_pixel(s[1], o1, w0, w1, flags), seg_pixel(s[2], o2, w0, w1, flags),
+                                        seg_pixel(s[3], o3, w0, w1, flags)};
+            draw_store_px4(dp, [&](int e) { return r[e]; });
         } else {
             const uint32_t o[SEG_PX] = {o0, o1, o2, o3};
 #pragma unroll
             for (int e = 0; e < SEG_PX; ++e)
-                if (p0 + e < cols) seg_store_px(dp + 3 * e, seg_pixel(seg_load_px(sp + 3 * e), o[e], w0, w1, flags));
+                if (p0 + e < cols) draw_store_px(dp + 3 * e, seg_pixel(draw_load_px(sp + 3 * e), o[e], w0, w1, flags));
         }
     }
 }

@@ -23,15 +23,15 @@ static_assert(sizeof(SegShape) == 32 && sizeof(hh_seg_desc) == 48, "ABI 3");
 // What the kernel keeps of a shape that survived the cull.
 struct SegItem { int32_t kind, colour, a, b, c, d; };
 
-HH_CHD long long seg_floor_div(long long n, long long d)  // d > 0; toward minus infinity
+HH_HD long long seg_floor_div(long long n, long long d)  // d > 0; toward minus infinity
 {
     const long long q = n / d;
     return (n % d != 0 && n < 0) ? q - 1 : q;
 }
-HH_CHD long long seg_ceil_div(long long n, long long d) { return -seg_floor_div(-n, d); }  // d > 0
+HH_HD long long seg_ceil_div(long long n, long long d) { return -seg_floor_div(-n, d); }  // d > 0
 
 // Does the shape meet the tile [tx0, tx1] x [ty0, ty1] (inclusive, inside the frame)?  A fill is culled by its column range alone.
-HH_CHD bool seg_meets(const SegShape &s, int tx0, int ty0, int tx1, int ty1)
+HH_HD bool seg_meets(const SegShape &s, int tx0, int ty0, int tx1, int ty1)
 {
     if (s.v[0] == HH_SEG_FILL) return s.v[3] > 0 && s.v[4] <= tx1 && s.v[5] >= tx0;
     const int xlo = s.v[2] < s.v[4] ? s.v[2] : s.v[4], xhi = s.v[2] < s.v[4] ? s.v[4] : s.v[2];
@@ -40,7 +40,7 @@ HH_CHD bool seg_meets(const SegShape &s, int tx0, int ty0, int tx1, int ty1)
 }
 
 // Bits 0 .. rows - 1 (1 <= rows <= SEG_ROWS): bit r set iff t0 <= r <= t1.
-HH_CHD uint32_t seg_run_bits(long long t0, long long t1, int rows)
+HH_HD uint32_t seg_run_bits(long long t0, long long t1, int rows)
 {
     if (t0 < 0) t0 = 0;
     if (t1 > rows - 1) t1 = rows - 1;
@@ -51,7 +51,7 @@ HH_CHD uint32_t seg_run_bits(long long t0, long long t1, int rows)
 // The rows Y0 .. Y0 + rows - 1 of image column X that the line (xa, ya) -> (xb, yb) draws, as bits 0 .. rows - 1.  Every product in
 // int64 (|coordinates| <= 2^23, so below 2^51).  Along x each column holds one pixel; along y the rows of a column are one run, found
 // by inverting the rule: floor_div(2 t sx + dy, 2 dy) == k  <=>  2 dy k - dy <= 2 t sx <= 2 dy k + dy - 1.
-HH_CHD uint32_t seg_line_bits(int xa, int ya, int xb, int yb, int X, int Y0, int rows)
+HH_HD uint32_t seg_line_bits(int xa, int ya, int xb, int yb, int X, int Y0, int rows)
 {
     const long long dx = xb > xa ? (long long)xb - xa : (long long)xa - xb, dy = yb > ya ? (long long)yb - ya : (long long)ya - yb;
     if (dx == 0 && dy == 0) return X == xa ? seg_run_bits((long long)ya - Y0, (long long)ya - Y0, rows) : 0u;
@@ -79,7 +79,7 @@ HH_CHD uint32_t seg_line_bits(int xa, int ya, int xb, int yb, int X, int Y0, int
 }
 
 // The same for any surviving shape: a fill's bits are the toggle predicate of crowd_mask_math.h over its own toggles.
-HH_CHD uint32_t seg_item_bits(const SegItem &s, const uint32_t *toggles, int h, int X, int Y0, int rows)
+HH_HD uint32_t seg_item_bits(const SegItem &s, const uint32_t *toggles, int h, int X, int Y0, int rows)
 {
     if (s.kind == HH_SEG_FILL) {
         if (X < s.c || X > s.d) return 0u;
@@ -88,10 +88,10 @@ HH_CHD uint32_t seg_item_bits(const SegItem &s, const uint32_t *toggles, int h, 
     return seg_line_bits(s.a, s.b, s.c, s.d, X, Y0, rows);
 }
 
-HH_CHD SegItem seg_item(const SegShape &s) { return SegItem{s.v[0], s.v[1], s.v[2], s.v[3], s.v[4], s.v[5]}; }
+HH_HD SegItem seg_item(const SegShape &s) { return SegItem{s.v[0], s.v[1], s.v[2], s.v[3], s.v[4], s.v[5]}; }
 
 // One pixel: src = r | g << 8 | b << 16 as read, own = SEG_COVERED | colour or 0 -> the three bytes as stored (flags bit 0: B,G,R).
-HH_CHD uint32_t seg_pixel(uint32_t src, uint32_t own, float w0, float w1, int flags)
+HH_HD uint32_t seg_pixel(uint32_t src, uint32_t own, float w0, float w1, int flags)
 {
     const uint32_t ov = (own & SEG_COVERED) ? own : src;
     const uint32_t c0 = render_blend((uint8_t)(src & 255), (uint8_t)(ov & 255), w0, w1);
@@ -111,21 +111,20 @@ inline void seg_frame_host(const uint8_t *src, uint8_t *dst, const SegDesc &d, c
         for (int tx0 = 0; tx0 < w; tx0 += SEG_TW) {
             const int ty1 = (ty0 + SEG_TH < h ? ty0 + SEG_TH : h) - 1, tx1 = (tx0 + SEG_TW < w ? tx0 + SEG_TW : w) - 1;
             std::fill(own.begin(), own.end(), 0u);
-            for (int first = 0; first < d.prim_count; first += SEG_CHUNK) {
-                int n = 0;
-                for (int i = first; i < d.prim_count && i < first + SEG_CHUNK; ++i)
-                    if (seg_meets(shapes[d.prim_offset + i], tx0, ty0, tx1, ty1)) list[n++] = seg_item(shapes[d.prim_offset + i]);
-                for (int t = 0; t < SEG_THREADS; ++t) {
-                    const int col = t % SEG_TW, X = tx0 + col, Y0 = ty0 + t / SEG_TW * SEG_ROWS;
-                    const int rows = (ty1 - Y0 + 1 < SEG_ROWS) ? ty1 - Y0 + 1 : SEG_ROWS;
-                    if (X > tx1 || rows < 1) continue;
-                    for (int k = 0; k < n; ++k) {
-                        const uint32_t bits = seg_item_bits(list[k], toggles, h, X, Y0, rows);
-                        for (int r = 0; r < rows; ++r)
-                            if (bits >> r & 1) own[(size_t)(Y0 - ty0 + r) * SEG_TW + col] = SEG_COVERED | (uint32_t)list[k].colour;
+            draw_chunks_host(
+                shapes + d.prim_offset, d.prim_count, SEG_CHUNK, list.data(), [&](const SegShape &s) { return seg_meets(s, tx0, ty0, tx1, ty1); }, seg_item,
+                [&](int n) {
+                    for (int t = 0; t < SEG_THREADS; ++t) {
+                        const int col = t % SEG_TW, X = tx0 + col, Y0 = ty0 + t / SEG_TW * SEG_ROWS;
+                        const int rows = (ty1 - Y0 + 1 < SEG_ROWS) ? ty1 - Y0 + 1 : SEG_ROWS;
+                        if (X > tx1 || rows < 1) continue;
+                        for (int k = 0; k < n; ++k) {
+                            const uint32_t bits = seg_item_bits(list[k], toggles, h, X, Y0, rows);
+                            for (int r = 0; r < rows; ++r)
+                                if (bits >> r & 1) own[(size_t)(Y0 - ty0 + r) * SEG_TW + col] = SEG_COVERED | (uint32_t)list[k].colour;
+                        }
                     }
-                }
-            }
+                });
             for (int y = ty0; y <= ty1; ++y)
                 for (int x = tx0; x <= tx1; ++x) {
                     const size_t at = ((size_t)y * w + x) * 3;
@@ -138,13 +137,11 @@ inline void seg_frame_host(const uint8_t *src, uint8_t *dst, const SegDesc &d, c
 // What hh_seg_overlay_u8_batch refuses for one frame, on the caller's host copies; nullptr = accepted.
 inline const char *seg_check_frame(const SegDesc &d, const SegShape *shapes, long long num_shapes, const uint32_t *toggles, long long num_toggles)
 {
-    if (d.h < 1 || d.w < 1 || d.h > 16384 || d.w > 16384) return "frame size outside 1..16384";
-    if (d.src_offset < 0 || d.dst_offset < 0) return "negative offset";
-    const long long bytes = (long long)d.h * d.w * 3;
-    if (d.dst_offset != d.src_offset && d.dst_offset < d.src_offset + bytes && d.src_offset < d.dst_offset + bytes) return "dst partially overlaps src";
-    if (d.prim_count < 0 || d.prim_offset < 0 || (long long)d.prim_offset + d.prim_count > num_shapes) return "shape range outside the table";
-    if (d.prim_count > HH_SEG_MAX_SHAPES) return "more than HH_SEG_MAX_SHAPES shapes in one frame";
-    if (!(d.w0 == d.w0) || !(d.w1 == d.w1) || fabsf(d.w0) > 1e6f || fabsf(d.w1) > 1e6f) return "blend weight not finite or above 1e6 in magnitude";
+    const long long bytes = (long long)d.h * d.w * 3;  // (reported only once the size and the offsets' sign have passed)
+    const bool overlap = d.dst_offset != d.src_offset && d.dst_offset < d.src_offset + bytes && d.src_offset < d.dst_offset + bytes;
+    if (const char *why = draw_check_frame(d, overlap ? "dst partially overlaps src" : nullptr, num_shapes, HH_SEG_MAX_SHAPES, "shape range outside the table",
+                                           "more than HH_SEG_MAX_SHAPES shapes in one frame", "blend weight not finite or above 1e6 in magnitude"))
+        return why;
     if (d.flags & ~1) return "unknown flag";
     if (d.reserved) return "non-zero reserved field";
     const uint32_t area = (uint32_t)d.h * (uint32_t)d.w;

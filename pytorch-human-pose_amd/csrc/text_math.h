@@ -9,19 +9,18 @@
 
 // The launch geometry, reported by hh_text_config: a workgroup of TEXT_THREADS owns one TEXT_TH x TEXT_TW tile of one frame, a thread
 // TEXT_PX horizontally adjacent pixels of it; the frame's primitives are culled against the tile TEXT_CHUNK at a time, one per lane.
-enum { TEXT_TH = 16, TEXT_TW = 64, TEXT_PX = 4, TEXT_THREADS = TEXT_TH * TEXT_TW / TEXT_PX, TEXT_CHUNK = TEXT_THREADS };
-static_assert(TEXT_THREADS == 256 && TEXT_TW % TEXT_PX == 0, "one lane per primitive of a chunk, whole pixel groups per tile row");
+enum { TEXT_TH = DRAW_TH, TEXT_TW = DRAW_TW, TEXT_PX = DRAW_PX, TEXT_THREADS = DRAW_THREADS, TEXT_CHUNK = DRAW_THREADS };
 
 using TextPrim = hh_text_prim;
 using TextDesc = hh_text_desc;
 struct TextTile { int32_t frame, tile; };  // tile = ty * xtiles + tx with xtiles = ceil(w / TEXT_TW)
 
-HH_RHD int text_xtiles(int w) { return (w + TEXT_TW - 1) / TEXT_TW; }
-HH_RHD int text_ytiles(int h) { return (h + TEXT_TH - 1) / TEXT_TH; }
+HH_HD int text_xtiles(int w) { return (w + TEXT_TW - 1) / TEXT_TW; }
+HH_HD int text_ytiles(int h) { return (h + TEXT_TH - 1) / TEXT_TH; }
 
 // One primitive on one pixel that lies inside its box; `px` = r | g << 8 | b << 16 as stored.  A glyph's box lies inside its bitmap
 // (text_check_frame), so the coverage index is inside [off, off + A * B), which lies inside the atlas.
-HH_RHD uint32_t text_apply(const TextPrim &p, const uint8_t *atlas, int x, int y, uint32_t px)
+HH_HD uint32_t text_apply(const TextPrim &p, const uint8_t *atlas, int x, int y, uint32_t px)
 {
     if (p.kind == HH_TEXT_BOX) {
         if (p.A) return p.rgb[0] | p.rgb[1] << 8 | p.rgb[2] << 16;
@@ -63,30 +62,29 @@ inline void text_tile_host(uint8_t *frame, const TextDesc &d, const TextPrim *pr
     const int xt = text_xtiles(d.w);
     const int ty0 = tile / xt * TEXT_TH, tx0 = tile % xt * TEXT_TW;
     const int ty1 = (ty0 + TEXT_TH < d.h ? ty0 + TEXT_TH : d.h) - 1, tx1 = (tx0 + TEXT_TW < d.w ? tx0 + TEXT_TW : d.w) - 1;
-    for (int base = 0; base < d.prim_count; base += TEXT_CHUNK) {
-        int n = 0;
-        for (int i = base; i < d.prim_count && i < base + TEXT_CHUNK; ++i)
-            if (render_box_meets(prims[d.prim_offset + i], tx0, ty0, tx1, ty1)) list[n++] = prims[d.prim_offset + i];
-        for (int i = 0; i < n; ++i) {
-            const TextPrim &p = list[i];
-            for (int y = p.y0 > ty0 ? p.y0 : ty0; y <= (p.y1 < ty1 ? p.y1 : ty1); ++y)
-                for (int x = p.x0 > tx0 ? p.x0 : tx0; x <= (p.x1 < tx1 ? p.x1 : tx1); ++x) {
-                    uint8_t *q = frame + ((size_t)y * d.w + x) * 3;
-                    const uint32_t v = text_apply(p, atlas, x, y, q[0] | q[1] << 8 | q[2] << 16);
-                    q[0] = v & 255, q[1] = (v >> 8) & 255, q[2] = (v >> 16) & 255;
-                }
-        }
-    }
+    draw_chunks_host(
+        prims + d.prim_offset, d.prim_count, TEXT_CHUNK, list, [&](const TextPrim &p) { return render_box_meets(p, tx0, ty0, tx1, ty1); },
+        [](const TextPrim &p) { return p; },
+        [&](int n) {
+            for (int i = 0; i < n; ++i) {
+                const TextPrim &p = list[i];
+                for (int y = p.y0 > ty0 ? p.y0 : ty0; y <= (p.y1 < ty1 ? p.y1 : ty1); ++y)
+                    for (int x = p.x0 > tx0 ? p.x0 : tx0; x <= (p.x1 < tx1 ? p.x1 : tx1); ++x) {
+                        uint8_t *q = frame + ((size_t)y * d.w + x) * 3;
+                        const uint32_t v = text_apply(p, atlas, x, y, q[0] | q[1] << 8 | q[2] << 16);
+                        q[0] = v & 255, q[1] = (v >> 8) & 255, q[2] = (v >> 16) & 255;
+                    }
+            }
+        });
 }
 
 // What hh_text_labels_u8_batch refuses in one frame, on the caller's host copy; nullptr = accepted.
 inline const char *text_check_frame(const TextDesc &d, const TextPrim *prims, long long table_len, long long atlas_len)
 {
-    if (d.h < 1 || d.w < 1 || d.h > 16384 || d.w > 16384) return "frame size outside 1..16384";
-    if (d.src_offset < 0 || d.dst_offset < 0) return "negative offset";
-    if (d.src_offset != d.dst_offset) return "frames are drawn in place: dst_offset must equal src_offset";
-    if (d.prim_count < 0 || d.prim_offset < 0 || (long long)d.prim_offset + d.prim_count > table_len) return "primitive range outside the table";
-    if (d.prim_count > HH_TEXT_MAX_PRIMS) return "more than HH_TEXT_MAX_PRIMS primitives in one frame";
+    const char *in_place = d.src_offset != d.dst_offset ? "frames are drawn in place: dst_offset must equal src_offset" : nullptr;
+    if (const char *why = draw_check_frame(d, in_place, table_len, HH_TEXT_MAX_PRIMS, "primitive range outside the table",
+                                           "more than HH_TEXT_MAX_PRIMS primitives in one frame", nullptr))
+        return why;
     if (d.flags != 0 || d.reserved != 0) return "unknown flag";
     for (int i = 0; i < d.prim_count; ++i) {
         const TextPrim &p = prims[d.prim_offset + i];

@@ -13,15 +13,7 @@
 #include <string.h>
 
 #include "../../include/hhrnet.h"
-
-#if defined(__HIPCC__)
-#define HH_THD __host__ __device__ __forceinline__
-#else
-#define HH_THD inline
-#endif
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
+#include "host_dev.h"
 
 // One lane of one wave owns one track slot and the detections of a frame are a 64-bit set: the limits HH_TRACK_MAX_* are 64.
 enum { TRACK_THREADS = 256 };
@@ -32,13 +24,13 @@ static_assert(sizeof(hh_track_params) == 592, "ABI 3");
 
 // One stream's state: header {issued ids, frames seen, 0, 0}, then per slot id / hits / misses / pad, the box area of the last matched
 // pose, the filter's xhat and dxhat per coordinate, the last matched raw pose and its joint scores.  All zero = empty.
-HH_THD int64_t track_state_bytes(int K, int T) { return ((int64_t)16 + 24 * (int64_t)T + 44 * (int64_t)T * K + 7) & ~(int64_t)7; }
+HH_HD int64_t track_state_bytes(int K, int T) { return ((int64_t)16 + 24 * (int64_t)T + 44 * (int64_t)T * K + 7) & ~(int64_t)7; }
 struct TrackState {
     int32_t *hdr, *id, *hits, *misses;
     double *area, *xhat, *dxhat;  // [T], [T,K,2], [T,K,2]
     float *xy, *score;            // [T,K,2], [T,K]
 };
-HH_THD TrackState track_state_view(unsigned char *base, int K, int T)
+HH_HD TrackState track_state_view(unsigned char *base, int K, int T)
 {
     TrackState s;
     s.hdr = (int32_t *)base;
@@ -55,7 +47,7 @@ HH_THD TrackState track_state_view(unsigned char *base, int K, int T)
 
 // A detection row is K joints of W floats: x, y, score and W - 3 more (3 + E in hh_decode's output; the kernel stages x, y, score: 3).
 // Step 1: is row `det` with person score `person` a valid detection?
-HH_THD bool track_det_valid(const float *det, int W, float person, const TrackParams &p)
+HH_HD bool track_det_valid(const float *det, int W, float person, const TrackParams &p)
 {
     int n = 0;
     for (int k = 0; k < p.K; ++k) n += det[(size_t)k * W + 2] > p.joint_thr ? 1 : 0;
@@ -64,7 +56,7 @@ HH_THD bool track_det_valid(const float *det, int W, float person, const TrackPa
 
 // Step 2: the similarity of a track's last matched raw pose and a detection.
 // (Without a branch on the labels, so that the loads of one joint do not wait for each other: a joint that does not count adds an exact 0.)
-HH_THD double track_similarity(const float *txy, const float *tscore, double area, const float *det, int W, const TrackParams &p)
+HH_HD double track_similarity(const float *txy, const float *tscore, double area, const float *det, int W, const TrackParams &p)
 {
     const double den = area + 2.220446049250313e-16;  // 2^-52
     double sum = 0.0;
@@ -82,7 +74,7 @@ HH_THD double track_similarity(const float *txy, const float *tscore, double are
 }
 
 // The box area of a detection's labelled joints, not less than 1 (1 when none is labelled).
-HH_THD double track_area(const float *det, int W, const TrackParams &p)
+HH_HD double track_area(const float *det, int W, const TrackParams &p)
 {
     double x0 = INFINITY, x1 = -INFINITY, y0 = INFINITY, y1 = -INFINITY;
     bool any = false;
@@ -99,7 +91,7 @@ HH_THD double track_area(const float *det, int W, const TrackParams &p)
 }
 
 // Step 3, one row: the best free detection of a track, the lowest d among equals; -1 when no free one reaches min_oks.
-HH_THD int track_row_best(const double *row, int P, uint64_t taken, double min_oks, double *best)
+HH_HD int track_row_best(const double *row, int P, uint64_t taken, double min_oks, double *best)
 {
     int bd = -1;
     double bs = 0.0;
@@ -113,7 +105,7 @@ HH_THD int track_row_best(const double *row, int P, uint64_t taken, double min_o
     return bd;
 }
 // Step 3, between rows: is candidate a (similarity, track id, detection; d < 0 = none) taken before candidate b?
-HH_THD bool track_better(double sa, int ida, int da, double sb, int idb, int db)
+HH_HD bool track_better(double sa, int ida, int da, double sb, int idb, int db)
 {
     if (da < 0) return false;
     if (db < 0) return true;
@@ -123,19 +115,19 @@ HH_THD bool track_better(double sa, int ida, int da, double sb, int idb, int db)
 }
 
 // The index of the j-th (0-based) set bit of mask, -1 if there are fewer.
-HH_THD int track_nth_bit(uint64_t mask, int j)
+HH_HD int track_nth_bit(uint64_t mask, int j)
 {
     for (int i = 0; i < j && mask; ++i) mask &= mask - 1;
     return mask ? __builtin_ctzll(mask) : -1;
 }
-HH_THD int track_popcount(uint64_t m)
+HH_HD int track_popcount(uint64_t m)
 {
     return __builtin_popcountll(m);
 }
 
 // Step 5 for one coordinate.  a_d = alpha(d_cutoff) for this Te.
-HH_THD double track_alpha(double cutoff, double Te) { return 1.0 / (1.0 + (1.0 / ((2.0 * 3.141592653589793) * cutoff)) / Te); }
-HH_THD void track_one_euro(double x, double Te, double a_d, const TrackParams &p, double *xhat, double *dxhat)
+HH_HD double track_alpha(double cutoff, double Te) { return 1.0 / (1.0 + (1.0 / ((2.0 * 3.141592653589793) * cutoff)) / Te); }
+HH_HD void track_one_euro(double x, double Te, double a_d, const TrackParams &p, double *xhat, double *dxhat)
 {
     const double dx = (x - *xhat) / Te;
     const double dh = a_d * dx + (1.0 - a_d) * *dxhat;
@@ -147,7 +139,7 @@ HH_THD void track_one_euro(double x, double Te, double a_d, const TrackParams &p
 
 // Steps 4 and 5 for joint k of a row that holds track slot t: replaces the slot's raw pose, runs or restarts the filter, writes the
 // row's smooth pair.  `fresh`: the track was opened in this frame.  Touches only element (t, k) of the state.
-HH_THD void track_joint_update(const TrackState &st, int t, int k, const float *det, int W, bool fresh, double Te, double a_d, const TrackParams &p,
+HH_HD void track_joint_update(const TrackState &st, int t, int k, const float *det, int W, bool fresh, double Te, double a_d, const TrackParams &p,
                                float *smooth)
 {
     const float *j = det + (size_t)k * W;
@@ -173,7 +165,7 @@ HH_THD void track_joint_update(const TrackState &st, int t, int k, const float *
 // What a frame's wave decides for slot t, given the assignment (det = the matched detection or -1), the free-slot set (slots that are
 // empty or expire in this frame) and the set of valid detections nobody matched: the j-th free slot takes the j-th such detection with
 // id issued + j + 1.  Returns the detection the slot holds after this frame (-1: none) and updates the slot's header.
-HH_THD int track_slot_update(const TrackState &st, int t, int det, uint64_t free_set, uint64_t unmatched, int issued, const float *joints_b, int W,
+HH_HD int track_slot_update(const TrackState &st, int t, int det, uint64_t free_set, uint64_t unmatched, int issued, const float *joints_b, int W,
                              const TrackParams &p, bool *fresh, double *Te)
 {
     *fresh = false;
@@ -201,7 +193,7 @@ HH_THD int track_slot_update(const TrackState &st, int t, int det, uint64_t free
     if (det >= 0) st.area[t] = track_area(joints_b + (size_t)det * p.K * W, W, p);
     return det;
 }
-HH_THD bool track_slot_free(const TrackState &st, int t, int det, const TrackParams &p)
+HH_HD bool track_slot_free(const TrackState &st, int t, int det, const TrackParams &p)
 {
     return st.id[t] == 0 || (det < 0 && st.misses[t] + 1 > p.max_age);
 }

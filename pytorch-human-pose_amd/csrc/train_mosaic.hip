@@ -15,6 +15,7 @@
 // pixels are formed once per thread, the row taps and weights once per row.  The gathers are byte loads (at most 4 source pixels
 // per output pixel); no LDS.  Every canvas byte is written exactly once by exactly one thread; nothing depends on the launch.
 #include "kernels.h"
+#include "draw_dev.h"
 #include "resize_dev.h"
 
 #define MOSAIC_PX 4     // output pixels per thread and row
@@ -73,10 +74,8 @@ __global__ __launch_bounds__(MOSAIC_TX *MOSAIC_TY) void mosaic_kernel(unsigned c
                 mk[e] = vertical_pass(m0[a] * wa + m0[b] * wb, m1[a] * wa + m1[b] * wb, ty.w0, ty.w1) ? 255 : 0;
             }
         }
-        uint32_t *oi = reinterpret_cast<uint32_t *>(cimg + (size_t)y * C2 * 3);  // 4-byte aligned: offsets, S and x0 are multiples of 4
-#pragma unroll
-        for (int q = 0; q < 3; ++q) oi[q] = px[q * 4] | px[q * 4 + 1] << 8 | px[q * 4 + 2] << 16 | (uint32_t)px[q * 4 + 3] << 24;
-        *reinterpret_cast<uint32_t *>(cmsk + (size_t)y * C2) = mk[0] | mk[1] << 8 | mk[2] << 16 | (uint32_t)mk[3] << 24;
+        draw_store_dwords<3>(cimg + (size_t)y * C2 * 3, [&](int i) { return px[i]; });  // 4-byte aligned: offsets, S and x0 are multiples of 4
+        draw_store_dwords<1>(cmsk + (size_t)y * C2, [&](int i) { return mk[i]; });
     }
 }
 
