@@ -156,6 +156,13 @@ int hh_debug_bb_compare(int B, int H, int W, int iters, float *max_diff, float *
  * (Additive diagnostic entry point: like hh_conv_config_double_buffered it leaves HH_ABI_VERSION at 3.)                       */
 int hh_debug_bb_cover(int B, int H, int W, int tall, int num_cus, int64_t counts[4]);
 
+/* The fused stem (stem_fused.hip) alone, on the handle's packed stem weights (bf16 and fp16 handles of the default plan, after
+ * hh_finalize): images [B,3,H,W] fp32 NCHW (device) -> out16 [B,H/4,W/4,64] raw 16-bit words in the handle's element type (device).
+ * H and W need only be multiples of 4, so the kernel's partial tiles and ragged widths can be run, which hh_forward's multiples of 32
+ * never reach; a handle created under HH_POISON_LDS=1 fills every CU's LDS with NaN patterns in front of the launch.
+ * (Additive diagnostic entry point: it leaves HH_ABI_VERSION at 3.)                                                              */
+int hh_debug_stem_fused(hh_net *net, const float *images, int B, int H, int W, void *out16, void *stream);
+
 /* Debug taps (parity tests): when enabled, hh_forward copies selected intermediate
  * activations; hh_tap_read converts one to fp32 NCHW on the host. Names follow the
  * reference module paths, e.g. "stages.2.blocks.3#1" = output 1 of backbone.stages[2].blocks[3]. */

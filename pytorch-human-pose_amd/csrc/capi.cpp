@@ -178,6 +178,27 @@ int hh_debug_check_plan(const hh_net *net)
     return 0;
 }
 
+// The fused stem alone on the handle's packed stem weights: any H, W the kernel accepts, not only the forward's multiples of 32.
+int hh_debug_stem_fused(hh_net *net, const float *images, int B, int H, int W, void *out16, void *stream)
+{
+    if (!net->finalized) { hh_set_error("hh_debug_stem_fused: call hh_finalize first"); return 1; }
+    if (!images || !out16 || B <= 0 || H <= 0 || W <= 0) { hh_set_error("hh_debug_stem_fused: null buffer or empty shape"); return 1; }
+    for (const Op &op : net->ops) {
+        if (op.kind != OP_STEM || op.layer2 < 0) continue;
+        const ConvLayer &l = net->layers[op.layer], &l2 = net->layers[op.layer2];
+        StemFusedParams q{};
+        q.images = images; q.w1 = l.d_w; q.b1 = l.d_bias; q.w2 = l2.d_w; q.b2 = l2.d_bias;
+        q.out = (bf16_raw *)out16; q.out_cs = 64;
+        q.B = B; q.H = H; q.W = W;
+        if (!stem_fused_supported(q)) { hh_set_error("hh_debug_stem_fused: H, W must be multiples of 4 and an image below 2 GB"); return 1; }
+        if (net->sw.poison_lds) HH_CHECK_HIP(launch_lds_poison(net->num_cus, (hipStream_t)stream));
+        HH_CHECK_HIP(stem_fused_launch(q, net->num_cus, (hipStream_t)stream, net->act()));
+        return 0;
+    }
+    hh_set_error("hh_debug_stem_fused: the handle's plan has no fused stem (HH_NO_STEM_FUSED, or an fp8 handle)");
+    return 1;
+}
+
 int hh_profile_enable(hh_net *net, int enable) { net->prof_enabled = enable != 0; net->prof_clk = enable == 2; net->prof_used = 0; return 0; }
 int hh_profile_count(const hh_net *net) { return (int)net->prof_used; }
 int hh_profile_get(hh_net *net, int i, int *cfg, double *flops, double *bytes, float *ms, float *kernel_ms, const char **layer)

@@ -272,6 +272,31 @@ struct StemFusedParams {
     unsigned long long *clk;  // optional device-clock probe
 };
 #define HH_CFG_STEM_FUSED 106
+// Input staging of stem_fused.hip, shared with the host walk of tools/stem_stage_host_check.cpp.  A tile of 2 x 32 outputs needs input
+// rows 4 oy0 - 3 .. 4 oy0 + 7 and columns 4 ox0 - 3 .. 4 ox0 + 127 of the three channel planes.  A patch row is staged as 34 aligned
+// float4 (columns 4 ox0 - 4 .. 4 ox0 + 131) and kept in LDS as 136 16-bit values: 3 x 11 rows x 34 = 1122 units of 16 bytes.  The
+// 256 staging threads move seven patch rows per round (thread = row tid / 34 of the round, vector tid % 34; threads 238..255 idle),
+// five rounds per tile.  Everything about a unit but its two range tests is the same for every tile.
+constexpr int STEM_T2H = 2, STEM_T2W = 32;              // tile of the final (1/4 resolution) map
+constexpr int STEM_PROWS = 4 * STEM_T2H + 3;            // 11 patch rows per channel plane
+constexpr int STEM_PVEC = (4 * STEM_T2W + 4 + 4) / 4;   // 34 float4 per patch row
+constexpr int STEM_PRS = 4 * STEM_PVEC;                 // 136: patch row stride in elements
+constexpr int STEM_STAGE_THREADS = 256, STEM_ROUND_ROWS = STEM_STAGE_THREADS / STEM_PVEC;                           // 7
+constexpr int STEM_ROUNDS = (3 * STEM_PROWS + STEM_ROUND_ROWS - 1) / STEM_ROUND_ROWS;                               // 5
+struct StemUnit { int c, py, v; bool act; };  // channel plane, patch row, float4 index inside the row; act: the thread has a unit this round
+__host__ __device__ inline StemUnit stem_unit(int tid, int round)
+{
+    const int rr = tid / STEM_PVEC, row = STEM_ROUND_ROWS * round + rr, c = row / STEM_PROWS;
+    return StemUnit{c, row - c * STEM_PROWS, tid - rr * STEM_PVEC, rr < STEM_ROUND_ROWS && row < 3 * STEM_PROWS};
+}
+// element offset of the unit's first value inside one image, relative to the tile's origin (row 4 oy0 - 3, column 4 ox0 - 4 of plane 0)
+__host__ __device__ inline int stem_unit_goff(const StemUnit &u, int H, int W) { return (u.c * H + u.py) * W + 4 * u.v; }
+__host__ __device__ inline int stem_tile_origin(int oy0, int ox0, int W) { return (4 * oy0 - 3) * W + 4 * ox0 - 4; }
+// the patch element (of 3 * STEM_PROWS * STEM_PRS) that receives the unit's first value
+__host__ __device__ inline int stem_unit_slot(const StemUnit &u) { return (u.c * STEM_PROWS + u.py) * STEM_PRS + 4 * u.v; }
+// the two range tests: outside the image a unit is conv1's zero padding (W % 4 == 0: the four columns are inside or outside together)
+__host__ __device__ inline bool stem_unit_row_ok(int py, int oy0, int H) { return (unsigned)(4 * oy0 - 3 + py) < (unsigned)H; }
+__host__ __device__ inline bool stem_unit_col_ok(int v, int ox0, int W) { return (unsigned)(4 * ox0 - 4 + 4 * v) < (unsigned)W; }
 hipError_t stem_fused_init();
 bool stem_fused_supported(const StemFusedParams &p);
 hipError_t stem_fused_launch(const StemFusedParams &p, int num_cus, hipStream_t s, int act_dtype = 0);
